@@ -13,6 +13,21 @@ RCCL/xGMI in four buckets that overlap with the backward pass (weak scaling:
 16 images per GPU).  `--mode e2e` drives FCN8s.train() from BatchGenerator over
 generated PNG files instead (host feeder + H2D included), `--mode infer` the
 serving loop.
+
+A plain run does only what its headline needs: set up, W warm-up steps, ONE
+timed region of exactly K steps, the outputs if `--dump-outputs DIR` is given,
+the line.  `--full` adds everything else this script measures: the median of
+three timed regions, the profiled pass (kernel groups, roofline, live PMC
+traffic), the gradient-exchange breakdown of multi-rank runs, the final loss,
+the loss-fetch timing and the backward check, the `secondary` legs and the CPU
+baseline.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in its last
+timed step as float32 `DIR/<name>.npy` (at most 64 MB in all; inputs are seeded,
+so two builds can be compared file for file): training -- `loss` (that step's
+loss), `params` and `grads` (the parameters after it and the gradients it
+computed; every tensor whole up to DUMP_TENSOR_CAP elements, a fixed seeded
+sample of that many beyond); inference -- `predictions` (the argmax map).
 """
 import argparse
 import json
@@ -41,7 +56,7 @@ DTYPE_LABEL = {"fp32": "f32", "bf16_fc": "bf16_fc+f32", "f32x3": "f32x3 (fp32 op
 
 
 COMMITTED_NOTE = ("committed profile (profiles/pmc_traffic.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                  "command on an MI355X, tools/collect_profiles.sh) -- not measured in this run (`--live-traffic` re-measures it; the default one-GPU training run does)")
+                  "command on an MI355X, tools/collect_profiles.sh) -- not measured in this run (`--live-traffic` re-measures it; the --full one-GPU training run does)")
 LIVE_NOTE = "live (two rocprofv3 --pmc passes of this command, 2 steps each, run by bench.py after its timed regions)"
 
 # kernel symbols of the HBM-bound groups (the library's HIP-event groups are keyed by what a launch is FOR; the PMC passes see symbols)
@@ -106,7 +121,12 @@ def live_pmc(argv):
         return None
     tmp = tempfile.mkdtemp(prefix="fcn8s_pmc_")
     env = dict(os.environ, TMPDIR="/tmp")
-    keep = [a for a in argv if a not in ("--live-traffic",)]
+    keep, it = [], iter(argv)
+    for a in it:                                  # (the profiled runs must not overwrite this run's --dump-outputs)
+        if a == "--dump-outputs":
+            next(it, None)
+        elif a != "--live-traffic" and not a.startswith("--dump-outputs="):
+            keep.append(a)
     base = [sys.executable, os.path.abspath(__file__)] + keep + ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--repeats", "1", "--no-live-traffic"]
     try:
         for ctr, d in (("FETCH_SIZE", "f"), ("WRITE_SIZE", "w")):
@@ -160,7 +180,7 @@ def physical_cores():
 
 
 def cpu_baseline_full(h, w, optimizer="sgd"):
-    """SURVEY 8d's CPU baseline to the letter (the default `cpu_baseline` of the one-GPU training line since round 5; ~100 s): the oracle on
+    """SURVEY 8d's CPU baseline to the letter (the default `cpu_baseline` of the --full one-GPU training line; ~100 s): the oracle on
     ALL physical cores of this host (count printed), the bs2 training step (fwd + bwd + optimizer) at the bench resolution 3 warm-up + 10
     timed runs, median; beside it (c1) 256x256 forward + argmax and the bs1 forward, 1 + 3 runs each."""
     import torch
@@ -334,11 +354,49 @@ def make_png_dataset(root, n, h, w, num_classes=20, seed=0):
     return os.path.join(root, "images"), os.path.join(root, "gt")
 
 
+DUMP_TENSOR_CAP = 131072          # --dump-outputs: elements kept per parameter / gradient tensor (params + grads of the 42 tensors: ~15 MB)
+DUMP_ARRAY_CAP = 1 << 23          # ... and per other output (32 MB: the argmax map of 16 x 1024x512 whole)
+
+
+def _dump_sample(n, cap, seed):
+    """Indices of a fixed, seeded sample of `cap` out of `n` elements (all of them if n <= cap), in ascending order."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+
+
+def dump_outputs(d, eng, mode, pred=None):
+    """--dump-outputs: what the timed path handed its caller in its last step, as float32 DIR/<name>.npy (module docstring)."""
+    import ctypes as C
+    import torch
+    from fcn8s_tensorflow_amd import _lib as L
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    if mode == "infer":
+        flat = pred.reshape(-1)
+        idx = torch.from_numpy(_dump_sample(flat.numel(), DUMP_ARRAY_CAP, [0, 0])).to(flat.device)
+        v = flat.index_select(0, idx).to(torch.float32).cpu().numpy()
+        out["predictions"] = v.reshape(tuple(pred.shape)) if v.size == flat.numel() else v
+    else:
+        loss = C.c_float(0.0)
+        L.check(L.lib.fcn8s_read_loss(eng.h, C.byref(loss)), eng.h)
+        out["loss"] = np.array([loss.value], np.float32)
+        idx = np.concatenate([off + _dump_sample(int(np.prod(shape)), DUMP_TENSOR_CAP, [1, i])
+                              for i, (shape, off) in enumerate(eng.specs.values())])
+        idx = torch.from_numpy(idx).to(eng.flat_params.device)
+        torch.cuda.synchronize()
+        out["params"] = eng.flat_params.index_select(0, idx).cpu().numpy()
+        out["grads"] = eng.flat_grads.index_select(0, idx).cpu().numpy()
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def e2e(args, emit=True):
     """FCN8s.train() end to end: PNG files -> BatchGenerator (decode, flip augmentation, `workers` processes) -> staging slots
     (pinned copy + H2D on the copy stream, one batch ahead) -> the training step, loss fetched every step as the reference does
-    (fcn8s_tensorflow.py:551-578).  Prints one JSON line with the end-to-end rate next to the resident-input rate of the same
-    process."""
+    (fcn8s_tensorflow.py:551-578).  Prints one JSON line with the end-to-end rate; `--full` adds the resident-input rate of the
+    same process and the rate of the feeder alone."""
+    import random
     import tempfile
     import torch
     from fcn8s_tensorflow_amd.fcn8s import FCN8s
@@ -351,13 +409,15 @@ def e2e(args, emit=True):
     gen = BatchGenerator(image_dirs=[img_root], image_file_extension='png', ground_truth_dirs=[gt_root],
                          image_name_split_separator='_leftImg8bit', ground_truth_suffix='_gtFine_labelIds',
                          check_existence=True, num_classes=20)
+    random.seed(0); np.random.seed(0)             # the feeder's shuffle and augmentation draws: the same batches in every run
     train_gen = gen.generate(batch_size=N, convert_to_one_hot=True, flip=0.5, shuffle=True, workers=args.workers)
-    # feeder alone: batches per second the host side can deliver (class-id form, what FCN8s.train pulls)
-    train_gen.next_ids()
-    tf0 = time.perf_counter()
-    for _ in range(4):
+    if args.full:
+        # feeder alone: batches per second the host side can deliver (class-id form, what FCN8s.train pulls)
         train_gen.next_ids()
-    feeder_ips = 4 * N / (time.perf_counter() - tf0)
+        tf0 = time.perf_counter()
+        for _ in range(4):
+            train_gen.next_ids()
+        feeder_ips = 4 * N / (time.perf_counter() - tf0)
     model = FCN8s(vgg16_dir='synthetic:0', num_classes=20, device_id=args.device or 0)
     if args.precision != "fp32":
         model.engine.set_precision(args.precision)
@@ -371,29 +431,34 @@ def e2e(args, emit=True):
         model.train(train_gen, epochs=1, steps_per_epoch=args.steps, learning_rate_schedule=sched, record_summaries=False)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t1
-    # the same step on device-resident inputs (what `--mode train` times), TF-Adam like FCN8s.train
-    rng = np.random.default_rng(0)
-    images = torch.from_numpy(rng.integers(0, 256, (N, H, W, 3), dtype=np.uint8)).cuda()
-    labels = torch.from_numpy(rng.integers(0, 20, (N, H, W), dtype=np.uint8)).cuda()
-    eng = model.engine
-    for _ in range(2):
-        eng.train_step(images, labels, 1e-4, fetch_loss=False)
-    torch.cuda.synchronize()
-    t2 = time.perf_counter()
-    for _ in range(args.steps):
-        eng.train_step(images, labels, 1e-4, fetch_loss=False)
-    torch.cuda.synchronize()
-    dres = time.perf_counter() - t2
-    value, resident = N * args.steps / dt, N * args.steps / dres
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model.engine, "train")
+    value = N * args.steps / dt
+    if args.full:
+        # the same step on device-resident inputs (what `--mode train` times), TF-Adam like FCN8s.train
+        rng = np.random.default_rng(0)
+        images = torch.from_numpy(rng.integers(0, 256, (N, H, W, 3), dtype=np.uint8)).cuda()
+        labels = torch.from_numpy(rng.integers(0, 20, (N, H, W), dtype=np.uint8)).cuda()
+        eng = model.engine
+        for _ in range(2):
+            eng.train_step(images, labels, 1e-4, fetch_loss=False)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        for _ in range(args.steps):
+            eng.train_step(images, labels, 1e-4, fetch_loss=False)
+        torch.cuda.synchronize()
+        dres = time.perf_counter() - t2
+        resident = N * args.steps / dres
     out = {"metric": "training images/sec at %dx%d bs%d, end to end (PNG decode + augmentation + H2D + FCN8s.train)" % (W, H, N)
                      + ("" if args.precision == "fp32" else " (%s arithmetic)" % args.precision),
            "value": round(value, 3), "unit": "images/sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
            "dtype": DTYPE_LABEL[args.precision], "data": "synthetic PNG files (%d pairs, generated in %.1f s)" % (4 * N, t_data),
            "config": {"workload": "FCN8s.train() from BatchGenerator(workers=%d, flip 0.5, one-hot contract) over %dx%d PNG pairs, %d images/step, TF-Adam, loss fetched every step"
-                                  % (args.workers, W, H, N), "global_batch": N, "parallelism": "dp1"},
-           "resident_input_images_per_sec": round(resident, 3), "e2e_over_resident": round(value / resident, 4),
-           "feeder_alone_images_per_sec": round(feeder_ips, 1), "host_cores": os.cpu_count()}
+                                  % (args.workers, W, H, N), "global_batch": N, "parallelism": "dp1"}}
+    if args.full:
+        out.update({"resident_input_images_per_sec": round(resident, 3), "e2e_over_resident": round(value / resident, 4),
+                    "feeder_alone_images_per_sec": round(feeder_ips, 1), "host_cores": os.cpu_count()})
     train_gen.close()
     with contextlib.redirect_stdout(io.StringIO()):
         model.close()
@@ -405,7 +470,7 @@ def e2e(args, emit=True):
 
 
 def secondary_legs(args, dev, budget_s=75.0):
-    """What earlier rounds claimed from builder-run profiles, now inside the driver-timed default line: short legs, run
+    """What earlier rounds claimed from builder-run profiles, now inside the --full one-GPU training line: short legs, run
     AFTER the headline regions on engines of their own, each 2 warm-up + a few timed steps between device synchronisations, inputs resident:
     the f32x3 arithmetic at config 3's shape, config 5's per-GPU shape (2048x1024, 4 images) in fp32 and in its own arithmetic (bf16 forward,
     and the bf16_train mode), batch-1 inference (config 2), and ten steps of FCN8s.train() end to end from PNG files.  Never the headline."""
@@ -461,6 +526,7 @@ def secondary_legs(args, dev, budget_s=75.0):
     def e2e_leg():
         a = _ap.Namespace(**vars(args))
         a.steps, a.warmup, a.workers, a.precision, a.device = 10, 2, min(32, max(2, (os.cpu_count() or 4) // 4)), "fp32", dev
+        a.dump_outputs = None                     # (the run's own outputs are the headline's)
         r = e2e(a, emit=False)
         return {k: r[k] for k in ("value", "ms_per_step", "steps", "resident_input_images_per_sec", "e2e_over_resident", "feeder_alone_images_per_sec", "data")} | {
             "workload": r["config"]["workload"]}
@@ -503,10 +569,10 @@ def main():
                     help="fp32 = the reference's arithmetic (the headline number); bf16_fc = BASELINE config 5's mode (forward "
                          "fc6/fc7 with bf16 operands on the bf16 MFMA, fp32 accumulate) -- reported as dtype 'bf16_fc+f32'")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-full", action="store_true", help="(default since round 5) `cpu_baseline` = SURVEY 8d to the letter: bs2 training step, 3 warm-up + 10 "
+    ap.add_argument("--cpu-baseline-full", action="store_true", help="(the default with --full) `cpu_baseline` = SURVEY 8d to the letter: bs2 training step, 3 warm-up + 10 "
                     "timed, all physical cores, ~100 s; the bounded sample of earlier rounds is reported beside it as `cpu_baseline_quick`")
     ap.add_argument("--cpu-baseline-quick", action="store_true", help="only the bounded ~25 s CPU sample (bs1, 1 + 3 runs, fastest thread count) as `cpu_baseline`")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` legs (f32x3, config 5's shape, batch-1 inference, end to end) of the default one-GPU training line")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` legs (f32x3, config 5's shape, batch-1 inference, end to end) of the --full one-GPU training line")
     ap.add_argument("--comm", default="torch", choices=["torch", "native"], help="who moves the gradient buckets for --gpus > 1: torch.distributed "
                     "(the default) or the library's own RCCL communicator behind the C ABI (fcn8s_comm_init / fcn8s_allreduce_bucket)")
     ap.add_argument("--mode", default="train", choices=["train", "infer", "e2e"],
@@ -516,16 +582,22 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL); 'gloo' lets the "
                     "multi-rank path be exercised on a single-GPU box together with --device")
     ap.add_argument("--device", type=int, default=None, help="HIP device ordinal (default: LOCAL_RANK)")
-    ap.add_argument("--repeats", type=int, default=3, help="how many times the timed region of exactly --steps steps is run; value / ms_per_step "
-                    "are those of the median region, all regions are listed in `timed_regions_ms_per_step`")
+    ap.add_argument("--repeats", type=int, default=None, help="how many times the timed region of exactly --steps steps is run (default 1; 3 with "
+                    "--full); value / ms_per_step are those of the median region, all regions are listed in `timed_regions_ms_per_step`")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline (module docstring); the CPU-baseline, "
+                    "secondary-leg and live-traffic options only act with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as float32 "
+                    "DIR/<name>.npy (module docstring)")
     ap.add_argument("--option", action="append", default=[], metavar="KEY=VALUE", help="library algorithm option (fcn8s_set_option), e.g. winograd_tile=4")
     ap.add_argument("--live-traffic", action="store_true", help="measure roofline.traffic now with two rocprofv3 --pmc passes (about a minute) instead of "
-                    "reading the committed profile.  Default: on for the plain one-GPU training run with the CPU baseline (the driver's "
-                    "bench line), when rocprofv3 is on PATH and this process is not itself being profiled; off otherwise")
+                    "reading the committed profile.  Default: on for the --full one-GPU training run with the CPU baseline, "
+                    "when rocprofv3 is on PATH and this process is not itself being profiled; off otherwise")
     ap.add_argument("--no-live-traffic", action="store_true", help="never spawn the rocprofv3 passes; roofline.traffic comes from profiles/pmc_traffic.json")
     ap.add_argument("--rank-timeout", type=float, default=600.0, help="seconds a collective (or the rendezvous) may wait for a peer before the process "
                     "group gives up; a rank that dies or hangs then ends the run with an `error` line instead of blocking it forever")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
     if args.mode == "e2e":
@@ -569,6 +641,19 @@ def main():
             sys.stdout.flush(); sys.stderr.flush()
             os._exit(1)                           # not sys.exit: a process group whose peer is gone can block in its destructor
         raise
+
+
+def headline(args, world, dt, N, H, W):
+    """The keys every result line carries: the metric of the timed region `dt` (seconds for args.steps steps) and what was run."""
+    return {
+        # BASELINE.json's metric string for its own configuration; any other size / batch / arithmetic says so in the metric itself
+        "metric": metric_name(args),
+        "value": round(N * world * args.steps / dt, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": DTYPE_LABEL[args.precision], "data": "synthetic",
+        "config": {"workload": "FCN-8s (VGG-16, fc6 7x7, 20 classes) %s step, %dx%d, %d images/GPU, %s, keep_prob 0.5"
+                               % (args.mode, W, H, N, "TF-Adam" if args.optimizer == "adam" else "SGD+momentum"),
+                   "global_batch": N * world, "parallelism": "dp%d" % world}}
 
 
 def run(args, state):
@@ -625,9 +710,8 @@ def run(args, state):
 
     def step():
         if args.mode == "train":
-            eng.train_step(images, labels, 1e-4, keep_prob=0.5, l2_rate=0.0, optimizer=opt, fetch_loss=False)
-        else:
-            eng.predict(images, argmax=True)
+            return eng.train_step(images, labels, 1e-4, keep_prob=0.5, l2_rate=0.0, optimizer=opt, fetch_loss=False)
+        return eng.predict(images, argmax=True)
 
     def fence():
         if under_launcher:
@@ -643,11 +727,11 @@ def run(args, state):
     mark("warmup done")
     # ---- the timed region: exactly K steps between two fences (barrier + device sync), no in-library event recording; the MAX over
     # ranks is the region's time.  The region is run --repeats times; the median region is the one reported (all are listed).
-    regions, per_rank_regions = [], []
+    regions, per_rank_regions, last = [], [], None
     for _ in range(max(1, args.repeats)):
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last = step()
         fence()
         dt_local = time.perf_counter() - t0
         if under_launcher:
@@ -662,6 +746,18 @@ def run(args, state):
     mid = order[(len(order) - 1) // 2]
     dt = regions[mid]
     per_rank_ms = [round(t / args.steps * 1e3, 3) for t in per_rank_regions[mid]]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, args.mode, last)
+    if not args.full:
+        if rank == 0:
+            out = headline(args, world, dt, N, H, W)
+            out.update({"timed_regions_ms_per_step": [round(t / args.steps * 1e3, 3) for t in regions], "per_rank_ms": per_rank_ms, "options": options})
+            state["done"] = True
+            print(json.dumps(out), flush=True)
+        eng.close()
+        if under_launcher:
+            dist.destroy_process_group()
+        return
     # ---- a second pass over the same steps with the library's HIP events on (recorded on the launch stream, one pair per
     # kernel launch): per-kernel durations for the roofline block.  Kept out of the timed region (the event pairs cost ~1 %).
     psteps = min(args.steps, 10)
@@ -793,8 +889,6 @@ def run(args, state):
             bcheck = {"error": repr(ex)}
 
     if rank == 0:
-        ms = dt / args.steps * 1e3
-        value = N * world * args.steps / dt
         scale = (H * W) / (512.0 * 1024.0)
         gflop_img = (TRAIN_GFLOP_PER_IMG_512x1024 if args.mode == "train" else FWD_GFLOP_PER_IMG_512x1024) * scale
         # dominant kernel family (by time) among the MFMA convolution groups
@@ -847,15 +941,8 @@ def run(args, state):
                 hbm_roof["traffic_over_algorithmic"] = round(gt["hbm_mb_per_pass"] * 1e6 / (g["bytes"] / args.steps), 3)
                 hbm_roof["traffic_over_algorithmic_lower_bound"] = round(gt["hbm_mb_per_pass_lower_bound"] * 1e6 / (g["bytes"] / args.steps), 3)
                 hbm_roof["traffic_detail"] = gt
-        out = {
-            # BASELINE.json's metric string for its own configuration; any other size / batch / arithmetic says so in the metric itself
-            "metric": metric_name(args),
-            "value": round(value, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": DTYPE_LABEL[args.precision], "data": "synthetic",
-            "config": {"workload": "FCN-8s (VGG-16, fc6 7x7, 20 classes) %s step, %dx%d, %d images/GPU, %s, keep_prob 0.5"
-                                   % (args.mode, W, H, N, "TF-Adam" if args.optimizer == "adam" else "SGD+momentum"),
-                       "global_batch": N * world, "parallelism": "dp%d" % world},
+        out = headline(args, world, dt, N, H, W)
+        out.update({
             # direct-convolution flop count per second; the Winograd layers execute 2.25-4x fewer
             # multiplies than that count, so this "effective" rate may exceed the matrix-core peak
             "effective_tflops_direct_conv_count": round(gflop_img * N * world * args.steps / dt / 1e3, 2),
@@ -887,7 +974,7 @@ def run(args, state):
             # sess.run, fcn8s_tensorflow.py:554-572); the same K steps with the fetch are timed separately, after the regions
             "loss_fetch": "deferred" if args.mode == "train" else None,
             "ms_per_step_with_loss_fetch": fetch_ms,
-        }
+        })
         default_line = (world == 1 and not under_launcher and args.mode == "train" and not args.no_cpu_baseline
                         and (N, H, W) == (16, 512, 1024) and args.precision == "fp32")
     eng.close()

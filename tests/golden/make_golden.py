@@ -3,6 +3,7 @@
 in this container (never shipped: only the input/output vectors are committed).
 
     python tests/golden/make_golden.py        # needs /root/reference
+    python tests/golden/make_golden.py confmat_pairs    # confmat_pairs.npz alone (needs the oracle/_ref build only)
 
 Sources exercised (reference file:line):
   helpers/ground_truth_conversion_utils.py:3-24   convert_IDs_to_IDs   (LUT gather)
@@ -151,8 +152,33 @@ def main():
                             class_avg=res["averageScoreClasses"],
                             cat_names=np.array(list(res["categoryScores"])), cat_scores=np.array(list(res["categoryScores"].values()), dtype=np.float64),
                             cat_avg=res["averageScoreCategories"])
+    native_confusion_pairs()
     print("golden fixtures written to", HERE)
 
 
+def native_confusion_pairs():
+    """confmat_pairs.npz: the reference's native confusion-matrix loop (oracle/_ref) on the two input pairs the suite checks its own
+    loops against (tests/test_oracle.py::test_confusion_c_restatement_matches_reference_build and
+    tests/test_cityscapes_eval.py::test_accumulation_maps_train_ids_back_and_ignores_void_ground_truth), so that neither needs the build."""
+    sys.path.insert(0, ROOT)
+    from fcn8s_tensorflow_amd import cityscapes_eval as ce
+    lib = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "libaddToConfusionMatrix.so"))
+    rng = np.random.default_rng(6)
+    gt = rng.integers(0, 20, (31, 17), dtype=np.uint8); pr = rng.integers(0, 20, (31, 17), dtype=np.uint8)
+    conf = np.zeros((20, 20), np.uint64)
+    lib.addToConfusionMatrix(ctypes.c_void_p(pr.ctypes.data), ctypes.c_void_p(gt.ctypes.data), 17, 31, ctypes.c_void_p(conf.ctypes.data), 20)
+    rng = np.random.default_rng(0)
+    ev_gt = rng.integers(0, 34, (2, 16, 32)).astype(np.uint8)
+    ev_pred = np.ascontiguousarray(ce.TRAINIDS_TO_IDS_ARRAY[ce.IDS_TO_TRAINIDS_ARRAY[ev_gt].astype(np.int64)])
+    ev_conf = np.zeros((34, 34), np.uint64)
+    lib.addToConfusionMatrix(ctypes.c_void_p(ev_pred.ctypes.data), ctypes.c_void_p(ev_gt.ctypes.data), ev_pred.shape[2],
+                             ev_pred.shape[0] * ev_pred.shape[1], ctypes.c_void_p(ev_conf.ctypes.data), 34)
+    np.savez_compressed(os.path.join(HERE, "confmat_pairs.npz"), gt=gt, pred=pr, conf=conf.astype(np.int64),
+                        eval_gt=ev_gt, eval_pred=ev_pred, eval_conf=ev_conf.astype(np.int64))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["confmat_pairs"]:
+        native_confusion_pairs()                 # this fixture alone (needs oracle/_ref only)
+    else:
+        main()

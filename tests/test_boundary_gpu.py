@@ -97,7 +97,7 @@ def test_bench_self_launches_two_ranks():
     """`python bench.py --gpus 2` without torchrun, exactly as the driver calls it for N > 1 (the ranks share this box's one GPU and
     exchange over gloo; on the 8-GPU node the same path runs one rank per GPU over RCCL)."""
     out = _run_bench("--gpus", "2", "--backend", "gloo", "--device", "0", "--steps", "2", "--warmup", "1", "--batch", "2",
-                     "--height", "64", "--width", "64", "--no-cpu-baseline")
+                     "--height", "64", "--width", "64", "--no-cpu-baseline", "--full")
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 4 and out["config"]["parallelism"] == "dp2"
     c = out["comm"]
     assert c["backend"] == "gloo" and c["rccl_ranks"] == 0 and out["rccl_ranks"] == 0 and c["ranks"] == 2       # gloo ranks are not RCCL ranks
@@ -113,7 +113,7 @@ def test_bench_eight_ranks_dry_run_on_one_gpu():
     ranks sharing this box's one GPU over gloo.  Eight per-rank times, global batch 8 x 2, all four buckets traced in backward-production
     order, every rank bound (or knowingly not) to its GPU's NUMA node, and the replicas still bit-identical after the timed steps."""
     out = _run_bench("--gpus", "8", "--backend", "gloo", "--device", "0", "--steps", "2", "--warmup", "1", "--repeats", "1", "--batch", "2",
-                     "--height", "64", "--width", "64", "--no-cpu-baseline", timeout=1500)
+                     "--height", "64", "--width", "64", "--no-cpu-baseline", "--full", timeout=1500)
     assert out["n_gpus"] == 8 and out["config"]["global_batch"] == 16 and out["config"]["parallelism"] == "dp8"
     assert len(out["per_rank_ms"]) == 8 and all(t > 0 for t in out["per_rank_ms"])
     c = out["comm"]
@@ -126,20 +126,20 @@ def test_bench_eight_ranks_dry_run_on_one_gpu():
 
 
 def test_bench_measures_roofline_traffic_live():
-    """The plain one-GPU training run re-measures roofline.traffic itself (two rocprofv3 --pmc passes of its own command after the timed
+    """The --full one-GPU training run re-measures roofline.traffic itself (two rocprofv3 --pmc passes of its own command after the timed
     regions); here forced on a small case: the line must say the figure is live and carry both counters of the dominant kernel."""
     import shutil
     if not shutil.which("rocprofv3"):
         pytest.skip("rocprofv3 not on PATH")
-    out = _run_bench("--steps", "2", "--warmup", "1", "--batch", "2", "--height", "128", "--width", "128", "--no-cpu-baseline", "--live-traffic", timeout=900)
+    out = _run_bench("--steps", "2", "--warmup", "1", "--batch", "2", "--height", "128", "--width", "128", "--no-cpu-baseline", "--full", "--live-traffic", timeout=900)
     r = out["roofline"]
     d = r["traffic_detail"]
     assert d and "error" not in d, d
     assert d["traffic_source"].startswith("live"), d
     assert r["traffic"] == round(d["hbm_mb_per_launch"] * 1e6) and d["fetch_mb"] > 0 and d["write_mb"] > 0
-    quiet = _run_bench("--steps", "2", "--warmup", "1", "--batch", "2", "--height", "128", "--width", "128", "--no-cpu-baseline")
+    quiet = _run_bench("--steps", "2", "--warmup", "1", "--batch", "2", "--height", "128", "--width", "128", "--no-cpu-baseline", "--full")
     src = (quiet["roofline"].get("traffic_detail") or {}).get("traffic_source", "committed")
-    assert not src.startswith("live")               # side benches stay quick: live only on request or in the default headline run
+    assert not src.startswith("live")               # side benches stay quick: live only on request or in the --full headline run
 
 
 def test_bench_under_torchrun_one_rank_rccl():
@@ -152,7 +152,7 @@ def test_bench_under_torchrun_one_rank_rccl():
     env = dict(os.environ); env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--height", "64", "--width", "64", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
+                        "--height", "64", "--width", "64", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     c = out["comm"]
@@ -202,7 +202,7 @@ def test_bench_under_torchrun_one_rank_native_rccl():
     env = dict(os.environ); env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--height", "64", "--width", "64", "--no-cpu-baseline", "--comm", "native"], capture_output=True, text=True, timeout=600, env=env)
+                        "--height", "64", "--width", "64", "--no-cpu-baseline", "--full", "--comm", "native"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     c = out["comm"]
@@ -293,10 +293,34 @@ def test_fused_step_marks_every_bucket_final():
 
 
 def test_bench_single_gpu_line_and_end_to_end_mode():
-    out = _run_bench("--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "64", "--no-cpu-baseline")
+    out = _run_bench("--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "64", "--no-cpu-baseline", "--full")
     assert out["n_gpus"] == 1 and out["roofline"]["bound"] == "mfma" and 0 < out["roofline"]["frac"] < 1
-    out = _run_bench("--mode", "e2e", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "64", "--workers", "2")
+    out = _run_bench("--mode", "e2e", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "64", "--workers", "2", "--full")
     assert out["value"] > 0 and out["resident_input_images_per_sec"] > 0 and "end to end" in out["metric"]
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times ONE region of exactly --steps steps and carries the headline only; --dump-outputs writes what the timed
+    path computed in its last step as float32 .npy files (< 64 MB): the loss, seeded samples of the parameters and gradients -- the same inputs
+    in a second run, hence the same outputs (to the order of the run's own floating-point sums); inference: the argmax map."""
+    args = ["--steps", "3", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "64"]
+    a = _run_bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    assert a["steps"] == 3 and a["timed_regions_ms_per_step"] == [a["ms_per_step"]] and a["value"] > 0
+    assert abs(a["value"] - 2 * 3 / (a["ms_per_step"] * 3e-3)) < 1e-2 * a["value"]
+    assert not {"roofline", "final_loss", "backward_check", "secondary", "cpu_baseline", "comm"} & set(a)
+    b = _run_bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["grads.npy", "loss.npy", "params.npy"] == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) < 64 << 20
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and x.shape == y.shape and np.isfinite(x).all() and np.abs(x).max() > 0, n
+        assert np.abs(x - y).max() <= 1e-3 * np.abs(x).max(), n
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")[0]) - np.log(20.0)) < 0.1
+    c = _run_bench("--mode", "infer", *args, "--dump-outputs", str(tmp_path / "c"))
+    assert c["steps"] == 3 and c["value"] > 0 and os.listdir(tmp_path / "c") == ["predictions.npy"]
+    p = np.load(tmp_path / "c" / "predictions.npy")
+    assert p.dtype == np.float32 and p.shape == (2, 64, 64) and p.min() >= 0 and p.max() < 20 and (p == np.round(p)).all()
 
 
 @pytest.mark.parametrize("N,H,W,Cin,Cout", [

@@ -47,16 +47,19 @@ def test_accumulation_maps_train_ids_back_and_ignores_void_ground_truth():
     for name, s in res["classScores"].items():
         assert np.isnan(s) or s == 1.0                                   # pixels on ignored ground truth never count as fp
     assert res["averageScoreClasses"] == 1.0
-    # the confusion matrix equals the reference's native loop on the same pair
+    # the confusion matrix equals the reference's native loop on the same pair (its answer stored in confmat_pairs.npz,
+    # tests/golden/make_golden.py; where oracle/_ref is built, it must still give it)
     import ctypes as C
+    d = np.load(os.path.join(GOLD, "confmat_pairs.npz"))
+    p = np.ascontiguousarray(ce.TRAINIDS_TO_IDS_ARRAY[pred_tid]); g = np.ascontiguousarray(gt)
+    np.testing.assert_array_equal(g, d["eval_gt"]); np.testing.assert_array_equal(p, d["eval_pred"])
+    np.testing.assert_array_equal(ev.conf, d["eval_conf"])
     so = os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref", "libaddToConfusionMatrix.so")
     if os.path.isfile(so):
-        ref = C.CDLL(so)
         conf = np.zeros((34, 34), np.uint64)
-        p = np.ascontiguousarray(ce.TRAINIDS_TO_IDS_ARRAY[pred_tid]); g = np.ascontiguousarray(gt)
-        ref.addToConfusionMatrix(p.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), p.shape[2], p.shape[0] * p.shape[1],
-                                 conf.ctypes.data_as(C.c_void_p), 34)
-        np.testing.assert_array_equal(ev.conf, conf.astype(np.int64))
+        C.CDLL(so).addToConfusionMatrix(p.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), p.shape[2], p.shape[0] * p.shape[1],
+                                        conf.ctypes.data_as(C.c_void_p), 34)
+        np.testing.assert_array_equal(conf.astype(np.int64), d["eval_conf"])
 
 
 @pytest.mark.gpu

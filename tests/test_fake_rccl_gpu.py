@@ -108,7 +108,7 @@ def test_bench_eight_native_ranks_on_one_gpu(tmp_path):
     communicator -- eight per-rank times, the 538 MB of gradients of the full-width network summed over eight ranks in four buckets, replicas bit-identical."""
     env = dict(os.environ); env["FCN8S_RCCL_LIBRARY"] = FAKE; env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--device", "0", "--comm", "native", "--steps", "2",
-                        "--warmup", "1", "--repeats", "1", "--batch", "1", "--height", "64", "--width", "64", "--no-cpu-baseline"],
+                        "--warmup", "1", "--repeats", "1", "--batch", "1", "--height", "64", "--width", "64", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -126,7 +126,7 @@ def test_bench_and_run_dp_over_the_native_communicator_two_ranks_on_one_gpu(tmp_
     communicator (over the stand-in), the replicas stay bit-identical, four buckets leave in backward-production order."""
     env = dict(os.environ); env["FCN8S_RCCL_LIBRARY"] = FAKE; env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--device", "0", "--comm", "native", "--steps", "3",
-                        "--warmup", "1", "--repeats", "1", "--batch", "2", "--height", "64", "--width", "64", "--no-cpu-baseline"],
+                        "--warmup", "1", "--repeats", "1", "--batch", "2", "--height", "64", "--width", "64", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

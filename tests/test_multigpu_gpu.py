@@ -80,7 +80,7 @@ def _check_dp_line(out, n, comm):
 def test_bench_n_ranks_over_rccl(n, comm):
     """`python bench.py --gpus N` as the driver calls it (no torchrun: it launches its own ranks), one rank per GPU over RCCL."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--repeats", "1", "--batch", "2",
-                        "--height", "64", "--width", "64", "--no-cpu-baseline", "--comm", comm], capture_output=True, text=True, timeout=900, env=_env())
+                        "--height", "64", "--width", "64", "--no-cpu-baseline", "--full", "--comm", comm], capture_output=True, text=True, timeout=900, env=_env())
     assert r.returncode == 0, r.stderr[-3000:]
     _check_dp_line(_json_line(r.stdout), n, comm)
 
@@ -94,7 +94,7 @@ def test_bench_under_torchrun_n_ranks_over_rccl():
         so.bind(("127.0.0.1", 0)); port = so.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--repeats", "1",
-                        "--batch", "2", "--height", "64", "--width", "64", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=_env())
+                        "--batch", "2", "--height", "64", "--width", "64", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=_env())
     assert r.returncode == 0, r.stderr[-3000:]
     _check_dp_line(_json_line(r.stdout), n, "torch")
 
@@ -103,7 +103,7 @@ def test_bench_under_torchrun_n_ranks_over_rccl():
 def test_bench_full_size_two_ranks_over_rccl():
     """Config 4's per-GPU shape (16 x 1024x512 per rank) on two ranks: the step with the exchange costs at most 10 % more than the same
     step without it (the budget of DESIGN section 6 is <= 1 ms of 58), and the replicas stay bit-identical."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=1800, env=_env())
     assert r.returncode == 0, r.stderr[-3000:]
     out = _json_line(r.stdout)

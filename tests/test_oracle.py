@@ -185,14 +185,17 @@ def test_golden_confusion_matrix_reference_native():
 
 
 def test_confusion_c_restatement_matches_reference_build(clib):
-    ref_so = os.path.join(ROOT, "oracle", "_ref", "libaddToConfusionMatrix.so")
-    if not os.path.isfile(ref_so):
-        pytest.skip("oracle/_ref not built (reference not present)")
-    ref = C.CDLL(ref_so)
+    # the reference build's answer on this pair is stored in confmat_pairs.npz (tests/golden/make_golden.py); where oracle/_ref is built, it must still give it
+    d = np.load(os.path.join(GOLD, "confmat_pairs.npz"))
     rng = np.random.default_rng(6)
     gt = rng.integers(0, 20, (31, 17), dtype=np.uint8); pr = rng.integers(0, 20, (31, 17), dtype=np.uint8)
-    c_ref = np.zeros((20, 20), np.uint64)
-    ref.addToConfusionMatrix(p(pr), p(gt), 17, 31, p(c_ref), 20)
+    np.testing.assert_array_equal(gt, d["gt"]); np.testing.assert_array_equal(pr, d["pred"])
+    c_ref = d["conf"].astype(np.uint64)
+    ref_so = os.path.join(ROOT, "oracle", "_ref", "libaddToConfusionMatrix.so")
+    if os.path.isfile(ref_so):
+        c_live = np.zeros((20, 20), np.uint64)
+        C.CDLL(ref_so).addToConfusionMatrix(p(pr), p(gt), 17, 31, p(c_live), 20)
+        np.testing.assert_array_equal(c_live, c_ref)
     c_mine = np.zeros((20, 20), np.int64)
     clib.orc_confusion(p(gt.astype(np.int64)), p(pr.astype(np.int64)), C.c_size_t(gt.size), p(c_mine), 20)
     np.testing.assert_array_equal(c_mine, c_ref.astype(np.int64))

@@ -6,7 +6,7 @@
 ARGS="$1"; R=$2; shift 2
 for i in $(seq 1 $R); do for l in "$@"; do
   cp scratch/lib_$l.so fcn8s_tensorflow_amd/libfcn8s_hip.so
-  python bench.py --no-cpu-baseline --no-live-traffic $ARGS 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-live-traffic $ARGS 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); g=d['kernel_groups_ms_per_step']
 print('%-8s'%'$l', d['value'], d['ms_per_step'], d['timed_regions_ms_per_step'], 'xform', g.get('wino_transform'), 'fwd', g.get('wino_gemm_fwd'), 'dgrad', g.get('wino_gemm_dgrad'), 'wgrad', g.get('wino_gemm_wgrad'))"

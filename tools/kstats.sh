@@ -5,7 +5,7 @@ PAT="$1"; shift
 export TMPDIR=/tmp
 OUT=gpurun_out/kstats
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o k -- python bench.py --no-cpu-baseline --steps 4 --warmup 2 "$@" > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o k -- python bench.py --full --no-cpu-baseline --steps 4 --warmup 2 "$@" > $OUT/bench.json 2> $OUT/bench.err
 python - "$PAT" <<'PY'
 import csv, glob, re, sys
 pat = re.compile(sys.argv[1])
