@@ -101,7 +101,7 @@ int main(int argc, char** argv)
     }
 
     /* (4) the split-phase step a data-parallel host drives: forward + loss, the backward pass bucket by bucket (a collective over
-     *     bucket b may start once call fcn8s_bucket_complete_after(m, b) has returned), then the update */
+     *     bucket b may start once call b has returned), then the update */
     {
         const int nb = fcn8s_num_buckets(m);
         float loss = 0.f;

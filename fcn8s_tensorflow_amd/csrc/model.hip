@@ -17,8 +17,6 @@
 #include <cstring>
 #include <cstdlib>
 #include <algorithm>
-#include <functional>
-#include <tuple>
 #include <mutex>
 #include <map>
 #include <set>
@@ -93,7 +91,6 @@ struct fcn8s_model {
     size_t bucket_off[FCN8S_MAX_BUCKETS] = {0}, bucket_n[FCN8S_MAX_BUCKETS] = {0};
     hipEvent_t bucket_ev[FCN8S_MAX_BUCKETS] = {nullptr};                 // recorded right behind the last kernel that writes into the bucket
     bool bucket_final[FCN8S_MAX_BUCKETS] = {false};                      // ... this backward pass (fcn8s_bucket_wait)
-    float* dz7_cur = nullptr; bool defer_fc_cur = false;                 // handed from backward phase 0 (decoder, fc7 weights) to phase 1 (fc6)
     // the library's own RCCL communicator (fcn8s_comm_*): one rank per model, collectives on a stream of its own behind the bucket events
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_world = 1;
     hipStream_t comm_stream = nullptr;
@@ -111,6 +108,7 @@ struct fcn8s_model {
     bool own_params = false, own_grads = false;
     float *d_w1pad = nullptr, *d_tph[3] = {nullptr, nullptr, nullptr};
     float *d_wino_u = nullptr, *d_wino_v = nullptr, *d_wino_m = nullptr;   // Winograd scratch: filters, transformed input / output
+    size_t ufl = 0;                                                       // floats of d_wino_u
     int wino_min_cin = 64;                                              // 3x3 layers with Cin >= this use Winograd; 0 = never
     int wino_tile = 6;                                                    // largest 3x3 output tile: F(6x6,3x3) / F(4x4,3x3) per layer by cost, F(2x2,3x3) fallback
     int wino_fc6 = 1;                                                     // fc6 7x7 as a 2x2 grid of 4x4 sub-filters in the Winograd domain
@@ -157,7 +155,6 @@ struct fcn8s_model {
     int bf16_infer_copies = 1;                                            // option: bf16_train's evaluation / prediction passes take the training pass's data flow (see forward())
     int bf16_rows_bn = 0;                                                 // option (A/B): 128 = the flat-position bf16 convolution takes its 128-column tile where it can (default: 64 columns)
     int bf16_acts = 1;                                                    // option: bf16_train training passes keep a conv -> conv activation only as the consumer's padded bf16 copy (the producer's epilogue writes it; no fp32 tensor, no conversion pass)
-    int bf16_fuse_convert = 0;                                            // option: let the producing convolution write its consumer's bf16 copy (measured: the 2-byte epilogue stores cost more than the conversion passes they replace -- off)
     int saved_wino_min_cin = -1, saved_wino_fc6 = -1;                      // the options the mode overrides (the direct path carries it), restored on leaving
     int bf16_copy_by_transform = 1;                                       // option: 0 = every bf16 layer converts its input with a pass of its own (round 3's path)
     hipStream_t stream = nullptr;
@@ -196,24 +193,6 @@ struct fcn8s_model {
                        size_t cap_img = 0, cap_lab = 0; hipEvent_t ready = nullptr, consumed = nullptr; bool used = false; };
     StageSlot slots[FCN8S_NUM_STAGE_SLOTS];
     hipStream_t copy_stream = nullptr;
-    // Deferred weight gradients.  Nothing in the backward pass consumes a weight gradient, so the MFMA-bound weight-gradient GEMMs of the
-    // deep layers (conv3_1 .. conv5_3 at level >= 1, fc6 / fc7 too at level 2) are held back and launched on `side` when the data-gradient
-    // chain reaches block `defer_start_block`: from there on it is HBM-bound (Winograd transforms and K = 64 / 128 position GEMMs of blocks
-    // 2 and 1), and the two kinds of work share the CUs.  Each deferred layer keeps its dM = A dY A^T in a buffer of its own.
-    int defer_wgrad = 0, defer_start_block = 2;                          // measured zero-sum (profiles/r03_overlap_*.txt): off by default
-    // Sharing CUs between the two kinds of work is zero-sum on gfx950 (profiles/r03_overlap_shared_cus.txt: both slow down by what the other
-    // gains); on DISJOINT CUs they do not disturb each other at all (tools/labs/cumask_lab.hip).  defer_tail_cus = n > 0: from the start block on
-    // the data-gradient chain moves to a stream restricted to the first n CUs and the held-back GEMMs run on the other 256 - n.
-    int defer_tail_cus = 0;
-    hipStream_t tail = nullptr; hipEvent_t tail_done = nullptr; bool on_tail = false;
-    int defer_level_now = 0;                                             // level the running backward pass uses (the bucket API caps it at 1)
-    hipStream_t side = nullptr; bool side_owned = false;
-    float* d_wino_u2 = nullptr; size_t ufl = 0;                          // dU scratch of the side stream (ufl floats, like d_wino_u)
-    std::vector<std::pair<hipEvent_t, std::function<void(hipStream_t)>>> deferred;   // (inputs-ready event on the main stream, launches)
-    std::vector<hipEvent_t> ev_pool; size_t ev_next = 0;
-    hipEvent_t side_done = nullptr;
-    hipStream_t launch_stream = nullptr;                                 // != nullptr while deferred work is being enqueued: ProfScope records there
-    float* dm_ptr = nullptr;                                             // where dm_layer's dM lives (d_wino_m or the layer's own buffer)
     std::vector<ProfGroup> groups;
     std::string err;
 };
@@ -318,13 +297,13 @@ struct ProfScope {
         fcn8s::g_last_kernel = nullptr;
         gid = (m->profile_detail && layer) ? group_id(m, (std::string(group) + ":" + layer).c_str()) : group_id(m, group);
         hipEventCreate(&a); hipEventCreate(&b);
-        hipEventRecord(a, m->launch_stream ? m->launch_stream : m->stream);
+        hipEventRecord(a, m->stream);
         m->groups[gid].flops += flops; m->groups[gid].bytes += bytes; m->groups[gid].launches += 1;
     }
     ~ProfScope()
     {
         if (gid < 0) return;
-        hipEventRecord(b, m->launch_stream ? m->launch_stream : m->stream);
+        hipEventRecord(b, m->stream);
         m->groups[gid].ev.emplace_back(a, b);
         if (fcn8s::g_last_kernel) {          // second view of the same launch, keyed by the kernel symbol that ran
             const int k = group_id(m, (std::string("kernel:") + fcn8s::g_last_kernel).c_str());
@@ -485,13 +464,12 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
                 auto xi = m->xg16.find(layer);
                 if (xi != m->xg16.end() && xi->second) { g.mask16 = xi->second + g16_off(bf16_guard_rows(3, W + 2), Cout); g.mask16_ps = g16_ps(N, H, W, 3); }
             }
-            // this gradient is the output gradient of layer e.yb_layer (same map): its padded bf16 copy is written by this kernel's epilogue
+            // this gradient is the output gradient of layer e.yb_layer (same map).  If that layer's gradients read nothing else (option bf16_acts), this kernel's
+            // epilogue writes its padded bf16 copy instead of the fp32 gradient, and takes its column sums, that layer's bias gradient, from the fp32 values
             const bool only16 = e.yb_layer && e.yb_only && m->bf16_acts && K == 3 && e.yb_K == 3 && Cout % 64 == 0;
-            if (e.yb_layer && (m->bf16_fuse_convert || only16) && K == 3 && e.yb_K == 3) { g.yb = g16_for(m, m->dyg16, m->dyg16_elems, e.yb_layer, N, H, W, Cout, e.yb_K, s); g.yb_pad = (e.yb_K - 1) / 2; g.yb_ps = g16_ps(N, H, W, e.yb_K); }
-            // ... and if that layer's gradients read nothing else (option bf16_acts), the fp32 gradient is not written: the epilogue also takes its column sums,
-            // that layer's bias gradient, from the fp32 values
+            if (only16) { g.yb = g16_for(m, m->dyg16, m->dyg16_elems, e.yb_layer, N, H, W, Cout, e.yb_K, s); g.yb_pad = (e.yb_K - 1) / 2; g.yb_ps = g16_ps(N, H, W, e.yb_K); }
             long long prow = 0;
-            if (g.yb && only16) {
+            if (g.yb) {
                 prow = ((long long)N * (H + 2) * (W + 2) + conv_bf16_rows_bm(Cout, g.rows_bn) - 1) / conv_bf16_rows_bm(Cout, g.rows_bn);
                 g.colpart = det_scratch(s, (size_t)prow * Cout);
                 if (g.colpart) g.y = nullptr; else prow = 0;
@@ -530,7 +508,7 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
         const int P = 64;
         const long long T = wino_tiles(6, N, H, W);
         IgemmArgs a{}; a.split = split_of(m);
-        a.x = m->dm_ptr ? m->dm_ptr : m->d_wino_m; a.w = m->d_wino_u; a.y = m->d_wino_v;
+        a.x = m->d_wino_m; a.w = m->d_wino_u; a.y = m->d_wino_v;
         a.N = 1; a.Ma = (int)T; a.Mb = 1; a.M = T;
         a.Hi = (int)T; a.Wi = 1; a.Cin = Cin; a.ldx = Cin;
         a.KW = 1; a.in_scale = 1; a.tap_step = 1; a.tap_off = 0; a.Ktot = Cin;
@@ -567,7 +545,7 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
             const int P = 49, Ng = 4 * Cout;
             const long long T = wino_tiles(4, N, H, W);
             IgemmArgs a{}; a.split = split_of(m);
-            a.x = m->dm_ptr ? m->dm_ptr : m->d_wino_m; a.w = kept->second; a.y = m->d_wino_v;
+            a.x = m->d_wino_m; a.w = kept->second; a.y = m->d_wino_v;
             a.N = 1; a.Ma = (int)T; a.Mb = 1; a.M = T;
             a.Hi = (int)T; a.Wi = 1; a.Cin = Cin; a.ldx = Cin;
             a.KW = 1; a.in_scale = 1; a.tap_step = 1; a.tap_off = 0; a.Ktot = Cin;
@@ -665,95 +643,14 @@ void tconv_dgrad(fcn8s_model* m, const float* dy, const float* w, float* dx, int
     else launch_igemm(a, 1, s);
 }
 
-// Deferred weight gradients (fcn8s_model::defer_wgrad): helpers
-hipEvent_t defer_event(fcn8s_model* m)
-{
-    if (m->ev_next == m->ev_pool.size()) { hipEvent_t e; hipEventCreateWithFlags(&e, hipEventDisableTiming); m->ev_pool.push_back(e); }
-    return m->ev_pool[m->ev_next++];
-}
-// CU-masked streams are made once per (device, mask) and never destroyed (destroying one and creating another hung on ROCm 7.2 in
-// tools/labs/cumask_lab.hip); models of one process share them, which only serialises their held-back work
-hipStream_t masked_stream(int device, int first, int count)
-{
-    static std::mutex mu;
-    static std::map<std::tuple<int, int, int>, hipStream_t> pool;
-    std::lock_guard<std::mutex> lk(mu);
-    auto key = std::make_tuple(device, first, count);
-    auto it = pool.find(key);
-    if (it != pool.end()) return it->second;
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, device) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    const int ncu = p.multiProcessorCount;
-    if (first < 0 || count <= 0 || first + count > ncu) return nullptr;
-    std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-    for (int c = first; c < first + count; ++c) mask[c / 32] |= 1u << (c % 32);
-    hipStream_t st = nullptr;
-    if (hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()) != hipSuccess) { (void)hipGetLastError(); st = nullptr; }
-    pool[key] = st;
-    return st;
-}
-int device_cus(int device)
-{
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, device) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return p.multiProcessorCount;
-}
-
-bool defer_ready(fcn8s_model* m)
-{
-    if (!m->side) {
-        const int ncu = device_cus(m->device);
-        if (m->defer_tail_cus > 0 && m->defer_tail_cus < ncu) {
-            m->tail = masked_stream(m->device, 0, m->defer_tail_cus);
-            m->side = m->tail ? masked_stream(m->device, m->defer_tail_cus, ncu - m->defer_tail_cus) : nullptr;
-            if (!m->side) m->tail = nullptr;
-            m->side_owned = false;
-        }
-        if (!m->side) {
-            int lo = 0, hi = 0;
-            hipDeviceGetStreamPriorityRange(&lo, &hi);             // lo = numerically greatest = lowest priority: the chain on the main stream goes first
-            if (hipStreamCreateWithPriority(&m->side, hipStreamNonBlocking, lo) != hipSuccess) { m->side = nullptr; (void)hipGetLastError(); return false; }
-            m->side_owned = true;
-        }
-        hipEventCreateWithFlags(&m->side_done, hipEventDisableTiming);
-        hipEventCreateWithFlags(&m->tail_done, hipEventDisableTiming);
-    }
-    if (!m->d_wino_u2 && hipMalloc((void**)&m->d_wino_u2, m->ufl * sizeof(float)) != hipSuccess) { m->d_wino_u2 = nullptr; (void)hipGetLastError(); return false; }
-    return true;
-}
-// launch everything held back so far on the side stream (each item waits for the event that marks its inputs ready)
-void flush_deferred(fcn8s_model* m, hipEvent_t here = nullptr)
-{
-    if (m->deferred.empty()) return;
-    // the host enqueues far ahead of the GPU: without this event the side stream would start each item as soon as its inputs exist, i.e. beside
-    // the MFMA-bound data-gradient GEMMs of the deep layers, which gains nothing.  It has to wait until the MAIN stream gets here.
-    if (!here) { here = defer_event(m); hipEventRecord(here, m->on_tail ? m->tail : m->stream); }
-    hipStreamWaitEvent(m->side, here, 0);
-    hipStream_t was = m->launch_stream;
-    m->launch_stream = m->side;
-    for (auto& d : m->deferred) { hipStreamWaitEvent(m->side, d.first, 0); d.second(m->side); }
-    m->launch_stream = was;
-    m->deferred.clear();
-}
-// end of the backward pass: the main stream continues only after the side stream has drained
-void join_deferred(fcn8s_model* m)
-{
-    flush_deferred(m);
-    if (m->on_tail) { hipEventRecord(m->tail_done, m->tail); hipStreamWaitEvent(m->stream, m->tail_done, 0); m->on_tail = false; m->launch_stream = nullptr; }
-    if (m->side && m->ev_next) { hipEventRecord(m->side_done, m->side); hipStreamWaitEvent(m->stream, m->side_done, 0); }
-    m->ev_next = 0;
-}
-
-// phase: 0 = everything on stream s; 1 = only what the data gradient needs (the transform of dz into dM) -- the weight gradient itself
-// is held back; 2 = the held-back part (GEMM, filter-gradient transform, bias gradient) on stream s.
 void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* dz, float* dw, float* db,
                 int N, int H, int W, int Cin, int Cout, int K, float alpha, hipStream_t s, int real_cin = 0,
-                const char* layer = nullptr, bool fuse_dgrad_input = false, const unsigned char* pool_idx = nullptr, int phase = 0)
+                const char* layer = nullptr, bool fuse_dgrad_input = false, const unsigned char* pool_idx = nullptr)
 {
     // the data gradient of the layer after this one may have written this layer's dM instead of dz (backward_blocks): dz then holds nothing
-    const bool promised = m && layer && phase != 2 && !m->dm_prefilled.empty() && m->dm_prefilled == layer;
-    if (m && phase != 2) m->dm_prefilled.clear();
-    if (m && m->keep_dy && layer && phase != 2) {
+    const bool promised = m && layer && !m->dm_prefilled.empty() && m->dm_prefilled == layer;
+    if (m) m->dm_prefilled.clear();
+    if (m && m->keep_dy && layer) {
         // (dz holds the layer's fp32 dY unless it was handed over in another form: dM from the next layer's data gradient, d(pool) with routing bytes, a bf16 copy only)
         Act& k = m->kept_dy[layer];
         const size_t n = (size_t)N * H * W * Cout;
@@ -808,11 +705,8 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
             const int tile = wino_tile_for(m, H, W, K), NP = wino_alpha(tile, K) * wino_alpha(tile, K);
             const long long T = wino_tiles(tile, N, H, W);
             const int Kg = wino_nsub(K) * wino_nsub(K) * Cin;           // rows of V / dU: [sub-filter][channel]
-            // a deferred layer keeps its dM in a buffer of its own ("dmk:<layer>", ensure_workspace) and its dU scratch on the side stream
-            float* dmbuf = m->d_wino_m; float* dubuf = m->d_wino_u;
-            if (phase) { dmbuf = m->acts.at(std::string("dmk:") + layer).p; dubuf = m->d_wino_u2; }
             WgradArgs g{}; g.split = split_of(m);
-            g.A = it->second.p; g.B = dmbuf; g.C = dubuf;
+            g.A = it->second.p; g.B = m->d_wino_m; g.C = m->d_wino_u;
             g.N = 1; g.Pa = 1; g.Pb = (int)T; g.P = T;
             g.Ha = 1; g.Wa = (int)T; g.Adim = Kg; g.lda = Kg; g.Areal = Kg;
             g.Bdim = Cout; g.ldb = Cout; g.KW = 1; g.a_scale = 1; g.tap_off = 0; g.ntaps = NP; g.ldc = Cout; g.alpha = 1.f; g.colsum = nullptr;
@@ -821,34 +715,30 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
             // transform V = B^T dz B is written into d_wino_v by the same kernel that writes dM (one read of dz)
             bool fused = false, dm_ready = false;
             const bool adj_bytes = fuse_dgrad_input && tile == 6 && K == 3 && Cin % 64 == 0 && Cout % 64 == 0;
-            const bool prefilled = promised && phase == 0 && adj_bytes && !pool_idx;      // dM already in d_wino_m (wino_dgrad_output_dout_kernel)
+            const bool prefilled = promised && adj_bytes && !pool_idx;      // dM already in d_wino_m (wino_dgrad_output_dout_kernel)
             if (promised && !prefilled) broken_promise();
             if (prefilled) dm_ready = true;
-            else if (phase != 2) {
-            { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cout * (pool_idx ? 0.3125 : 1.0) + ((fuse_dgrad_input && !adj_bytes) ? 2.0 : 1.0) * NP * T * Cout));
-              // pool_idx: dz is d(pool) [N,H/2,W/2,Cout]; the max-pool backward happens inside the transform (the caller checked eligibility)
-              // adjoint data gradient (tile 6): it consumes dM itself, no second transform of dz
-              if (adj_bytes) { launch_wino_dout(6, dz, dmbuf, N, H, W, Cout, s, 3, pool_idx); dm_ready = true; }
-              else {
-                  if (fuse_dgrad_input && tile >= 4 && K == 3) fused = launch_wino_input_dout(tile, dz, m->d_wino_v, dmbuf, N, H, W, Cout, s, pool_idx);
-                  if (!fused) launch_wino_dout(tile, dz, dmbuf, N, H, W, Cout, s, K);
-              } }
-            // fc6: the non-fused transform above left dM = A dz A^T in dmbuf; its adjoint data gradient (conv_same) consumes it
-            if (K == 7 && tile == 4 && !fused && Cin % 2 == 0 && bt_gemm_ok(Cout, 4 * Cin) && m->u_train.count(std::string(layer) + "#4")) dm_ready = true;
+            else {
+                { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cout * (pool_idx ? 0.3125 : 1.0) + ((fuse_dgrad_input && !adj_bytes) ? 2.0 : 1.0) * NP * T * Cout));
+                  // pool_idx: dz is d(pool) [N,H/2,W/2,Cout]; the max-pool backward happens inside the transform (the caller checked eligibility)
+                  // adjoint data gradient (tile 6): it consumes dM itself, no second transform of dz
+                  if (adj_bytes) { launch_wino_dout(6, dz, m->d_wino_m, N, H, W, Cout, s, 3, pool_idx); dm_ready = true; }
+                  else {
+                      if (fuse_dgrad_input && tile >= 4 && K == 3) fused = launch_wino_input_dout(tile, dz, m->d_wino_v, m->d_wino_m, N, H, W, Cout, s, pool_idx);
+                      if (!fused) launch_wino_dout(tile, dz, m->d_wino_m, N, H, W, Cout, s, K);
+                  } }
+                // fc6: the non-fused transform above left dM = A dz A^T in d_wino_m; its adjoint data gradient (conv_same) consumes it
+                if (K == 7 && tile == 4 && !fused && Cin % 2 == 0 && bt_gemm_ok(Cout, 4 * Cin) && m->u_train.count(std::string(layer) + "#4")) dm_ready = true;
             }
-            if (phase != 2) {
             m->fused_v_layer = fused ? layer : "";
             m->dm_layer = dm_ready ? layer : "";
-            m->dm_ptr = dmbuf;
-            }
-            if (phase == 1) return;
             { ProfScope ps(m, K == 7 ? "wino_gemm_fc6_wgrad" : "wino_gemm_wgrad", 2.0 * NP * T * Kg * Cout, 4.0 * NP * (T * (double)(Kg + Cout) + (double)Kg * Cout), layer); launch_wgrad(g, s); }
             { ProfScope ps(m, "wino_transform", 0, 4.0 * (9.0 + NP) * Cin * Cout + 4.0 * N * H * W * Cout * (tile >= 4 ? 1.0 / (tile * tile) : 1.0));
-              launch_wino_dfilter(tile, dubuf, dw, Cin, Cout, K, s);
+              launch_wino_dfilter(tile, m->d_wino_u, dw, Cin, Cout, K, s);
               // bias gradient = sum of dz over all pixels.  dM[(1,1)] = sum_kl A^T(k,1) dz[k][l] A^T(l,1) and column 1 of A^T is all ones:
               // the slab of position (1,1) holds the per-tile sums -- 16x fewer bytes than dz, and dz need not exist
               if (db) {
-                  if (tile >= 4) launch_colsum(dmbuf + (wino_alpha(tile, K) + 1) * wino_slab(T, Cout), db, T, Cout, s);
+                  if (tile >= 4) launch_colsum(m->d_wino_m + (wino_alpha(tile, K) + 1) * wino_slab(T, Cout), db, T, Cout, s);
                   else launch_colsum(dz, db, (long long)N * H * W, Cout, s);
               } }
             return;
@@ -1000,26 +890,6 @@ int ensure_workspace(fcn8s_model* m, int N, int H, int W)
                     cin = m->widths[b];
                 }
             if (fc6w) items.push_back({"wv:fc6", slab_floats(h5_, w5_, m->widths[4], 7), 0, 0, 0, nullptr});
-            if (m->defer_wgrad > 0) {
-                // deferred weight gradients: dM = A dY A^T of conv3_1 .. conv5_3 (and fc6, and fc7's dz) stays alive until the side stream has used it
-                int cin2 = m->widths[1];
-                for (int b = 2, hh = H / 4, ww = W / 4; b < 5; ++b, hh /= 2, ww /= 2)
-                    for (int i = 1; i <= kConvsPerBlock[b]; ++i) {
-                        const int cw = m->widths[b];
-                        if (cin2 >= m->wino_min_cin && cin2 % 64 == 0 && cw % 64 == 0 && wino_tile_for(m, hh, ww, 3) == 6) {
-                            char nm[40]; snprintf(nm, sizeof nm, "dmk:conv%d_%d", b + 1, i);
-                            items.push_back({nm, (size_t)64 * (size_t)wino_slab(wino_tiles(6, N, hh, ww), cw), 0, 0, 0, nullptr});
-                        }
-                        cin2 = cw;
-                    }
-                if (m->defer_wgrad > 1) {
-                    if (fc6w && m->widths[4] % 2 == 0 && bt_gemm_ok(m->widths[5], 4 * m->widths[4])) {
-                        const int al = wino_alpha(4, 7);
-                        items.push_back({"dmk:fc6", (size_t)al * al * (size_t)wino_slab(wino_tiles(4, N, h5_, w5_), m->widths[5]), 0, 0, 0, nullptr});
-                    }
-                    items.push_back({"dz:fc7", (size_t)N * h5_ * w5_ * m->widths[6], 0, 0, 0, nullptr});
-                }
-            }
         }
     }
 
@@ -1405,7 +1275,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                 }
                 // the next convolution of the block reads this output as ITS padded bf16 input: this kernel's epilogue writes that copy
                 unsigned short* yb = nullptr; char nx[32] = "";
-                if (cp && (m->bf16_fuse_convert || m->bf16_acts) && i < kConvsPerBlock[b]) { snprintf(nx, sizeof nx, "conv%d_%d", b + 1, i + 1); yb = xg16_for(m, nx, N, h, w, m->widths[b], 3, s); }
+                if (cp && m->bf16_acts && i < kConvsPerBlock[b]) { snprintf(nx, sizeof nx, "conv%d_%d", b + 1, i + 1); yb = xg16_for(m, nx, N, h, w, m->widths[b], 3, s); }
                 // the block's LAST convolution is read by its pool only, and pool1 / pool2 / pool5 only by bf16 convolutions: the pool then takes this output
                 // as a bf16 copy of the kernel's own geometry ("pool<b>in"), picks its maxima among the bf16 values (what bf16(max of the fp32 values) is anyway)
                 // and no fp32 tensor is written (pool3 / pool4 also feed the fp32 skip heads: their blocks keep the fp32 tensor)
@@ -1634,21 +1504,11 @@ void backward_head(fcn8s_model* m)
     // s7 = conv1x1(fc7)
     conv_wgrad(m, "score1x1_wgrad", A(m, "fc7"), m->ds7, Gp(m, "fc7_1x1/kernel"), Gp(m, "fc7_1x1/bias"), N, h5, w5, m->widths[6], C, 1, 1.f, s);
     l2_grad(m, "fc7_1x1/kernel");
-    // (level 2 of the deferred weight gradients: fc7's dz gets a buffer of its own so that the weight gradient can run later, on the side stream)
-    const bool defer_fc = m->defer_level_now >= 2 && m->acts.count("dz:fc7") && defer_ready(m);
-    float* dz7 = defer_fc ? A(m, "dz:fc7") : m->gbuf[0];
     { Epi e; e.mask = A(m, "fc7"); e.mask_scale = inv_keep;
-      conv_same(m, "score1x1_dgrad", m->ds7, WTp(m, "fc7_1x1/kernel"), dz7, N, h5, w5, C, m->widths[6], 1, e, s); }
+      conv_same(m, "score1x1_dgrad", m->ds7, WTp(m, "fc7_1x1/kernel"), m->gbuf[0], N, h5, w5, C, m->widths[6], 1, e, s); }
     // fc7
-    if (defer_fc) {
-        hipEvent_t ev = defer_event(m); hipEventRecord(ev, s);
-        m->deferred.emplace_back(ev, [m, dz7, N, h5, w5](hipStream_t ss) {
-            conv_wgrad(m, "fc7_wgrad", A(m, "fc6"), dz7, Gp(m, "fc7/weights"), Gp(m, "fc7/biases"), N, h5, w5, m->widths[5], m->widths[6], 1, 1.f, ss, 0, "fc7"); });
-    } else {
-        conv_wgrad(m, "fc7_wgrad", A(m, "fc6"), dz7, Gp(m, "fc7/weights"), Gp(m, "fc7/biases"), N, h5, w5, m->widths[5], m->widths[6], 1, 1.f, s, 0, "fc7");
-        mark_bucket_final(m, 0, s);
-    }
-    m->dz7_cur = dz7; m->defer_fc_cur = defer_fc;
+    conv_wgrad(m, "fc7_wgrad", A(m, "fc6"), m->gbuf[0], Gp(m, "fc7/weights"), Gp(m, "fc7/biases"), N, h5, w5, m->widths[5], m->widths[6], 1, 1.f, s, 0, "fc7");
+    mark_bucket_final(m, 0, s);
 }
 
 // backward phase 1: fc7's data gradient, fc6 (bucket 1 = {fc6}: final behind its weight gradient, before its data gradient is queued)
@@ -1658,20 +1518,11 @@ void backward_fc6(fcn8s_model* m)
     const int N = m->N, H = m->H, W = m->W;
     const int h5 = H / 32, w5 = W / 32;
     const float inv_keep = (m->train_mode && m->keep_prob < 1.f) ? 1.f / m->keep_prob : 1.f;
-    float* dz7 = m->dz7_cur; const bool defer_fc = m->defer_fc_cur;
     { Epi e; e.mask = A(m, "fc6"); e.mask_scale = inv_keep; e.w_fwd = Wp(m, "fc7/weights"); e.yb_layer = "fc6"; e.yb_K = m->fc6k;      // (w_fwd + the layer name: the bf16_train branch of conv_same)
-      conv_same(m, "fc7_dgrad", dz7, WTp(m, "fc7/weights"), m->gbuf[1], N, h5, w5, m->widths[6], m->widths[5], 1, e, s, 0, "fc7"); }
+      conv_same(m, "fc7_dgrad", m->gbuf[0], WTp(m, "fc7/weights"), m->gbuf[1], N, h5, w5, m->widths[6], m->widths[5], 1, e, s, 0, "fc7"); }
     // fc6
-    if (defer_fc && m->acts.count("dmk:fc6") && m->acts.count("wv:fc6") && m->u_train.count("fc6#4")) {
-        float* dz6 = m->gbuf[1];
-        conv_wgrad(m, "fc6_wgrad", A(m, "pool5"), dz6, Gp(m, "fc6/weights"), Gp(m, "fc6/biases"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, 1.f, s, 0, "fc6", false, nullptr, 1);
-        hipEvent_t ev = defer_event(m); hipEventRecord(ev, s);
-        m->deferred.emplace_back(ev, [m, dz6, N, h5, w5](hipStream_t ss) {
-            conv_wgrad(m, "fc6_wgrad", A(m, "pool5"), dz6, Gp(m, "fc6/weights"), Gp(m, "fc6/biases"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, 1.f, ss, 0, "fc6", false, nullptr, 2); });
-    } else {
-        conv_wgrad(m, "fc6_wgrad", A(m, "pool5"), m->gbuf[1], Gp(m, "fc6/weights"), Gp(m, "fc6/biases"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, 1.f, s, 0, "fc6");
-        mark_bucket_final(m, 1, s);
-    }
+    conv_wgrad(m, "fc6_wgrad", A(m, "pool5"), m->gbuf[1], Gp(m, "fc6/weights"), Gp(m, "fc6/biases"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, 1.f, s, 0, "fc6");
+    mark_bucket_final(m, 1, s);
     { Epi e; e.dgrad = 1; e.w_fwd = Wp(m, "fc6/weights"); e.lazy_wt = 1;      // (flipped + transposed copy only if the adjoint path is not taken)
       conv_same(m, "fc6_dgrad", m->gbuf[1], WTp(m, "fc6/weights"), m->gbuf[0], N, h5, w5, m->widths[5], m->widths[4], m->fc6k, e, s, 0, "fc6"); }
     m->gcur = 0;   // gbuf[0] holds d(pool5)
@@ -1680,21 +1531,9 @@ void backward_fc6(fcn8s_model* m)
 // blocks [b_hi .. b_lo] (1-based VGG block numbers), going backwards
 void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
 {
-    hipStream_t s = m->on_tail ? m->tail : m->stream;
+    hipStream_t s = m->stream;
     const int N = m->N;
     for (int b = b_hi; b >= b_lo; --b) {
-        if (b == m->defer_start_block && !m->deferred.empty()) {
-            // from here on the chain is HBM-bound: the held-back weight-gradient GEMMs run beside it -- on CUs of their own if masks are on
-            // (ONE event, recorded before anything is put on the side stream: the caller's stream may be the legacy default stream, on which
-            //  every operation -- an event record too -- first waits for all work already queued on blocking streams such as the masked ones)
-            hipEvent_t here = defer_event(m);
-            hipEventRecord(here, m->stream);
-            if (m->tail) {
-                hipStreamWaitEvent(m->tail, here, 0);
-                s = m->tail; m->on_tail = true; m->launch_stream = m->tail;
-            }
-            flush_deferred(m, here);
-        }
         const int h = m->H >> (b - 1), w = m->W >> (b - 1);      // resolution of this block's convs
         const int cw = m->widths[b - 1];
         const int nconv = kConvsPerBlock[b - 1];
@@ -1738,16 +1577,6 @@ void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
             const bool dgrad_wino = !first && m->wino_min_cin > 0 && cw >= m->wino_min_cin && m->d_wino_v && wino_tile_for(m, h, w) >= 4 &&
                                     cw % 16 == 0 && cin % 64 == 0;
             const unsigned char* pix = i == nconv ? pidx : nullptr;
-            const bool defer = m->defer_level_now >= 1 && b > m->defer_start_block && dgrad_wino && wino_tile_for(m, h, w) == 6 && cw % 64 == 0 &&
-                               m->acts.count(std::string("dmk:") + nm) && m->acts.count(std::string("wv:") + nm) && defer_ready(m);
-            if (defer) {
-                conv_wgrad(m, "conv3x3_wgrad", xin, dz, Gp(m, std::string(nm) + "/filter"), Gp(m, std::string(nm) + "/biases"),
-                           N, h, w, cin, cw, 3, 1.f, s, 0, nm, true, pix, 1);
-                hipEvent_t ev = defer_event(m); hipEventRecord(ev, s);
-                const std::string lname = nm;
-                m->deferred.emplace_back(ev, [m, lname, xin, dz, N, h, w, cin, cw, pix](hipStream_t ss) {
-                    conv_wgrad(m, "conv3x3_wgrad", xin, dz, Gp(m, lname + "/filter"), Gp(m, lname + "/biases"), N, h, w, cin, cw, 3, 1.f, ss, 0, lname.c_str(), true, pix, 2); });
-            } else
             conv_wgrad(m, first ? "conv1_1_wgrad" : "conv3x3_wgrad", xin, dz, Gp(m, std::string(nm) + "/filter"), Gp(m, std::string(nm) + "/biases"),
                        N, h, w, cin, cw, 3, 1.f, s, real_cin, nm, dgrad_wino, pix);
             if (first) break;
@@ -1760,7 +1589,7 @@ void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
                 const int cin_prev = i > 2 ? cw : (b > 1 ? m->widths[b - 2] : 4);
                 const bool prev_first = (b == 1 && i == 2);
                 e.yb_only = !prev_first && cin_prev % 64 == 0 && cw % 64 == 0;      // (conv1_1's weight gradient is exact fp32 and reads the fp32 tensor)
-                if (m->fuse_dgrad_dout && e.relu_bits_in && !prev_first && m->defer_level_now == 0 && m->train_mode && m->d_wino_m &&
+                if (m->fuse_dgrad_dout && e.relu_bits_in && !prev_first && m->train_mode && m->d_wino_m &&
                     wino_tile_for(m, h, w) == 6 && cw % 64 == 0 && cin_prev % 64 == 0 && m->acts.count(std::string("wv:") + inname)) {
                     e.dm_out = m->d_wino_m; e.dm_out_layer = inname;
                 }
@@ -1773,29 +1602,16 @@ void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
     }
 }
 
-int bucket_complete_after(const fcn8s_model* m, int bucket)
-{
-    if (m->defer_wgrad == 0 || (bucket <= 1 && m->defer_wgrad < 3)) return bucket;
-    return kNumBuckets - 1;           // weight gradients of conv3_1 .. conv5_3 (level 3: fc6 / fc7 too) are held back until the last call
-}
-
-// level_cap: 1 for the bucket-by-bucket API (buckets 0 and 1 -- fc7 + decoder, fc6 -- are final when their calls return, so that their
-// all-reduces can start at once; with deferred weight gradients the conv buckets are final after the last call, see
-// fcn8s_bucket_complete_after), 2 for the fused step
-int do_backward_bucket(fcn8s_model* m, int bucket, int level_cap)
+// bucket b is final when call b returns: buckets 0 and 1 (fc7 + decoder, fc6) are marked behind their weight gradients, the conv
+// buckets at the end of their calls -- so that each all-reduce can start at once
+int do_backward_bucket(fcn8s_model* m, int bucket)
 {
     t_deterministic = m->deterministic;
     if (!m->have_loss || !m->train_mode) return fail(m, FCN8S_ERR_STATE, "fcn8s_backward_bucket: call fcn8s_forward_loss first");
     if (bucket != m->next_bucket) return fail(m, FCN8S_ERR_STATE, "fcn8s_backward_bucket: buckets must be run in order 0, 1, ... fcn8s_num_buckets() - 1");
     if (bucket == 0) {
-        m->defer_level_now = m->defer_wgrad >= 3 ? 2 : std::min(m->defer_wgrad, level_cap);      // 3: the caller does not consume bucket 0 early
-        if (m->profile && m->profile_detail) m->defer_level_now = 0;      // per-layer timing wants one kernel at a time
-        // bf16_train has no Winograd-domain weight gradients to hold back, and a held-back fc6 / fc7 weight gradient would have to convert its operands on the side
-        // stream: the arithmetic of the mode must not depend on "defer_wgrad" (round 5's deferred fc7 lambda ran the fp32 kernel: ADVICE round 5)
-        if (bf16_train_mode(m)) m->defer_level_now = 0;
-        m->deferred.clear(); m->ev_next = 0; m->dyg16_filled.clear(); m->db_taken.clear(); m->dy_bf16_only.clear(); m->dz_unwritten.clear();
+        m->dyg16_filled.clear(); m->db_taken.clear(); m->dy_bf16_only.clear(); m->dz_unwritten.clear();
         m->dm_prefilled.clear();                                           // (a promise left over from a backward pass that ended in an error)
-        m->on_tail = false; m->launch_stream = nullptr;                    // (a backward pass that ended in an error may have left them set)
         for (int b = 0; b < kNumBuckets; ++b) m->bucket_final[b] = false;
         // (a caller that skipped fcn8s_apply_update after fcn8s_allreduce_bucket: the gradient buffer is about to be cleared and rewritten,
         //  so this stream first waits for whatever the library's communicator still has in flight on it)
@@ -1805,11 +1621,8 @@ int do_backward_bucket(fcn8s_model* m, int bucket, int level_cap)
     }
     else if (bucket == 1) backward_fc6(m);
     else if (bucket == 2) backward_blocks(m, 5, 4);
-    else { backward_blocks(m, 3, 1); join_deferred(m); }
-    // whatever this call completed and no kernel-exact point has marked yet (the conv buckets; everything held back to the last call)
-    // (the fused step, level_cap 2, marks nothing before its last call -- and there everything that is still open: bucket 2 as well)
-    for (int b = 0; b < kNumBuckets; ++b)
-        if (!m->bucket_final[b] && ((level_cap == 1 && bucket_complete_after(m, b) == bucket) || bucket == kNumBuckets - 1)) mark_bucket_final(m, b, m->stream);
+    else backward_blocks(m, 3, 1);
+    if (!m->bucket_final[bucket]) mark_bucket_final(m, bucket, m->stream);
     m->next_bucket = bucket + 1;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(m, FCN8S_ERR_HIP, std::string("backward launch: ") + hipGetErrorString(e));
@@ -1949,7 +1762,7 @@ int fcn8s_destroy(fcn8s_model* m)
     const std::string comm_text = rc_comm ? m->err : std::string();
     hipDeviceSynchronize();
     // the per-stream scratch of the streams this model ran on (the caller's stream may live on: what it holds is given back, the next user grows its own)
-    scratch_release(m->stream); if (m->side) scratch_release(m->side); if (m->tail) scratch_release(m->tail);
+    scratch_release(m->stream);
     for (auto& g : m->groups) for (auto& ev : g.ev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
     if (m->own_params && m->d_params) hipFree(m->d_params);
     if (m->own_grads && m->d_grads) hipFree(m->d_grads);
@@ -1957,11 +1770,6 @@ int fcn8s_destroy(fcn8s_model* m)
     if (m->d_v) hipFree(m->d_v);
     if (m->d_wt) hipFree(m->d_wt);
     if (m->d_w1pad) hipFree(m->d_w1pad);
-    if (m->d_wino_u2) hipFree(m->d_wino_u2);
-    if (m->side && m->side_owned) hipStreamDestroy(m->side);
-    if (m->tail_done) hipEventDestroy(m->tail_done);
-    if (m->side_done) hipEventDestroy(m->side_done);
-    for (auto e : m->ev_pool) hipEventDestroy(e);
     for (auto& e : m->bucket_ev) if (e) { hipEventDestroy(e); e = nullptr; }
     for (auto& kv : m->kept_dy) if (kv.second.p) hipFree(kv.second.p);
     for (auto& kv : m->u_train) if (kv.second) hipFree(kv.second);
@@ -2072,9 +1880,6 @@ static int* model_option(fcn8s_model* m, const std::string& key)
     if (key == "tconv_gemm") return &m->tconv_gemm;
     if (key == "fuse_dgrad_dout") return &m->fuse_dgrad_dout;
     if (key == "fuse_out_in") return &m->fuse_out_in;
-    if (key == "defer_wgrad") return &m->defer_wgrad;
-    if (key == "defer_start_block") return &m->defer_start_block;
-    if (key == "defer_tail_cus") return &m->defer_tail_cus;
     if (key == "bf16_gemm256") return &m->bf16_gemm256;
     if (key == "winograd_tile_hires") return &m->wino_tile_hires;
     if (key == "winograd_hires_pixels") return &m->wino_hires_pixels;
@@ -2083,7 +1888,6 @@ static int* model_option(fcn8s_model* m, const std::string& key)
     if (key == "bf16_copy_by_transform") return &m->bf16_copy_by_transform;
     if (key == "conv1_in_transform") return &m->conv1_in_transform;
     if (key == "deterministic") return &m->deterministic;
-    if (key == "bf16_fuse_convert") return &m->bf16_fuse_convert;
     if (key == "bf16_acts") return &m->bf16_acts;
     if (key == "bf16_rows_bn") return &m->bf16_rows_bn;
     if (key == "keep_output_gradients") return &m->keep_dy;
@@ -2110,7 +1914,7 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
         if (value < 1) return fail(m, FCN8S_ERR_BAD_ARG, "comm_timeout_ms must be >= 1");
         std::lock_guard<std::mutex> lk(m->comm_mu); m->comm_timeout_ms = value; return FCN8S_OK;
     }
-    if (k == "conv1_tiled" || k == "conv1_wgrad_mfma" || k == "bf16_copy_by_transform" || k == "conv1_in_transform" || k == "deterministic" || k == "bf16_fuse_convert" || k == "bf16_acts" || k == "bf16_rows_bn" || k == "bf16_fuse_pool" || k == "keep_output_gradients" || k == "bf16_infer_copies") {        // pick a kernel per launch: nothing cached depends on them
+    if (k == "conv1_tiled" || k == "conv1_wgrad_mfma" || k == "bf16_copy_by_transform" || k == "conv1_in_transform" || k == "deterministic" || k == "bf16_acts" || k == "bf16_rows_bn" || k == "bf16_fuse_pool" || k == "keep_output_gradients" || k == "bf16_infer_copies") {        // pick a kernel per launch: nothing cached depends on them
         *model_option(m, k) = k == "bf16_rows_bn" ? (int)value : (value ? 1 : 0);
         return FCN8S_OK;
     }
@@ -2126,20 +1930,10 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
     if (k == "winograd_tile" && value != 2 && value != 4 && value != 6) return fail(m, FCN8S_ERR_BAD_ARG, "winograd_tile must be 2, 4 or 6");
     if (k == "winograd_tile_hires" && value != 0 && value != 2 && value != 4 && value != 6) return fail(m, FCN8S_ERR_BAD_ARG, "winograd_tile_hires must be 0, 2, 4 or 6");
     if (k == "winograd_min_cin" && value < 0) return fail(m, FCN8S_ERR_BAD_ARG, "winograd_min_cin must be >= 0 (0 = direct convolution everywhere)");
-    if (k == "defer_wgrad" && (value < 0 || value > 3)) return fail(m, FCN8S_ERR_BAD_ARG, "defer_wgrad must be 0 .. 3");
     if (k == "fuse_out_in" && (value < 0 || value > 2)) return fail(m, FCN8S_ERR_BAD_ARG, "fuse_out_in must be 0, 1 or 2");
-    if (k == "defer_start_block" && (value < 1 || value > 4)) return fail(m, FCN8S_ERR_BAD_ARG, "defer_start_block must be 1 .. 4");
-    if (k == "defer_tail_cus" && (value < 0 || value > 248 || value % 8)) return fail(m, FCN8S_ERR_BAD_ARG, "defer_tail_cus must be a multiple of 8 in 0 .. 248");
     if (*slot == (int)value) return FCN8S_OK;
     HIPCHK(m, hipStreamSynchronize(m->stream));
     *slot = (k == "winograd_fc6" || k == "tconv_gemm") ? (value != 0) : (int)value;
-    if (k == "defer_tail_cus" && m->side) {         // the side / tail streams are re-made for the new split on next use
-        hipDeviceSynchronize();
-        if (m->side_owned) hipStreamDestroy(m->side);
-        m->side = m->tail = nullptr;
-        if (m->side_done) { hipEventDestroy(m->side_done); m->side_done = nullptr; }
-        if (m->tail_done) { hipEventDestroy(m->tail_done); m->tail_done = nullptr; }
-    }
     if (m->arena) { hipFree(m->arena); m->arena = nullptr; m->arena_bytes = 0; m->N = m->H = m->W = 0; m->acts.clear(); }
     m->have_forward = m->have_loss = false;
     for (auto& kv : m->u_cache) if (kv.second) hipFree(kv.second);
@@ -2265,7 +2059,7 @@ int fcn8s_backward_bucket(fcn8s_model* m, int bucket)
 {
     if (!m || bucket < 0 || bucket >= kNumBuckets) return fail(m, FCN8S_ERR_BAD_ARG, "bad bucket");
     take_deferred_error(nullptr);
-    int rc = do_backward_bucket(m, bucket, 1); if (rc) { take_deferred_error(nullptr); return rc; }
+    int rc = do_backward_bucket(m, bucket); if (rc) { take_deferred_error(nullptr); return rc; }
     return deferred_rc(m);
 }
 
@@ -2273,7 +2067,7 @@ int fcn8s_bucket_wait(fcn8s_model* m, int bucket, void* hip_stream)
 {
     if (!m || bucket < 0 || bucket >= kNumBuckets) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_bucket_wait: bad bucket");
     if (!m->bucket_final[bucket] || !m->bucket_ev[bucket])
-        return fail(m, FCN8S_ERR_STATE, "fcn8s_bucket_wait: the bucket's gradients are not queued yet (call fcn8s_backward_bucket up to fcn8s_bucket_complete_after(bucket) first)");
+        return fail(m, FCN8S_ERR_STATE, "fcn8s_bucket_wait: the bucket's gradients are not queued yet (call fcn8s_backward_bucket(bucket) first)");
     HIPCHK(m, hipStreamWaitEvent((hipStream_t)hip_stream, m->bucket_ev[bucket], 0));
     return FCN8S_OK;
 }
@@ -2281,7 +2075,7 @@ int fcn8s_bucket_wait(fcn8s_model* m, int bucket, void* hip_stream)
 int fcn8s_bucket_complete_after(const fcn8s_model* m, int bucket)
 {
     if (!m || bucket < 0 || bucket >= kNumBuckets) return -1;
-    return bucket_complete_after(m, bucket);
+    return bucket;                 // (kept for callers written when a bucket could become final at a later call)
 }
 
 // ---- the library's own RCCL communicator ------------------------------------------------------------------------------------------
@@ -2484,7 +2278,7 @@ int fcn8s_allreduce_bucket(fcn8s_model* m, int bucket)
     if (!m || bucket < 0 || bucket >= kNumBuckets) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_allreduce_bucket: bad bucket");
     if (m->comm_failed.load()) return comm_failed_rc(m, "fcn8s_allreduce_bucket");
     if (!m->comm) return fail(m, FCN8S_ERR_STATE, "fcn8s_allreduce_bucket: no communicator (fcn8s_comm_init first)");
-    if (!m->bucket_final[bucket]) return fail(m, FCN8S_ERR_STATE, "fcn8s_allreduce_bucket: the bucket's gradients are not queued yet (fcn8s_bucket_complete_after)");
+    if (!m->bucket_final[bucket]) return fail(m, FCN8S_ERR_STATE, "fcn8s_allreduce_bucket: the bucket's gradients are not queued yet (call fcn8s_backward_bucket(bucket) first)");
     if (m->comm_pending[bucket]) return fail(m, FCN8S_ERR_STATE, "fcn8s_allreduce_bucket: this bucket is already being reduced");
     HIPCHK(m, hipStreamWaitEvent(m->comm_stream, m->bucket_ev[bucket], 0));
     float* g = m->d_grads + m->bucket_off[bucket];
@@ -2619,11 +2413,8 @@ int fcn8s_train_step(fcn8s_model* m, const void* images, int dtype, const uint8_
     // backward pass, every bucket all-reduced as soon as it is final, 1/world in the update (a C caller must never get silently diverging replicas)
     const bool dp = (m->comm || m->comm_failed.load()) && m->comm_world > 1;
     for (int b = 0; b < kNumBuckets; ++b) {
-        take_deferred_error(nullptr);
-        rc = do_backward_bucket(m, b, dp ? 1 : 2); if (rc) { take_deferred_error(nullptr); return rc; }
-        rc = deferred_rc(m); if (rc) return rc;
-        if (dp) for (int r = 0; r < kNumBuckets; ++r)
-            if (bucket_complete_after(m, r) == b) { rc = fcn8s_allreduce_bucket(m, r); if (rc) return rc; }
+        rc = fcn8s_backward_bucket(m, b); if (rc) return rc;
+        if (dp) { rc = fcn8s_allreduce_bucket(m, b); if (rc) return rc; }
     }
     rc = fcn8s_apply_update(m, FCN8S_OPT_TF_ADAM, lr, dp ? 1.f / (float)m->comm_world : 1.f); if (rc) return rc;
     if (loss_out) { rc = fcn8s_read_loss(m, loss_out); if (rc) return rc; }

@@ -443,19 +443,15 @@ class Engine:
         L.check(L.lib.fcn8s_forward_loss(self.h, pi, dt, pl, N, H, W, float(keep_prob), float(l2_rate), where), self.h)
         self._release(ka)
         red = BucketReducer(self.flat_grads, self.buckets, self.pg, trace=trace, always=always, ready=self._bucket_ready)
-        # bucket b is final once the call `ready_after[b]` has returned (include/fcn8s_hip.h) -- by default call b itself: {fc7, decoder},
-        # {fc6}, {conv4, conv5}, {conv1 .. conv3} leave in that order, each while the rest of the backward pass runs
-        nb = self.num_buckets
-        ready_after = [int(L.lib.fcn8s_bucket_complete_after(self.h, b)) for b in range(nb)]
-        for b in range(nb):
+        # bucket b is final once call b has returned (include/fcn8s_hip.h): {fc7, decoder}, {fc6}, {conv4, conv5}, {conv1 .. conv3}
+        # leave in that order, each while the rest of the backward pass runs
+        for b in range(self.num_buckets):
             L.check(L.lib.fcn8s_backward_bucket(self.h, b), self.h)
             if reduce:
-                for r in range(nb):
-                    if ready_after[r] == b:
-                        if self.native_comm:
-                            L.check(L.lib.fcn8s_allreduce_bucket(self.h, r), self.h)
-                        else:
-                            red.reduce_bucket(r)
+                if self.native_comm:
+                    L.check(L.lib.fcn8s_allreduce_bucket(self.h, b), self.h)
+                else:
+                    red.reduce_bucket(b)
         red.wait()
         scale = (1.0 / self.comm_world) if (self.native_comm and reduce) else (red.grad_scale() if reduce else 1.0)
         L.check(L.lib.fcn8s_apply_update(self.h, optimizer, float(learning_rate), scale), self.h)     # (waits for the native all-reduces itself)

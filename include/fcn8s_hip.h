@@ -137,13 +137,11 @@ int fcn8s_train_step(fcn8s_model* m, const void* images, int image_dtype, const 
 /* split-phase form for data-parallel training (no counterpart in the single-device reference): forward + loss, then
  * the backward pass in fcn8s_num_buckets() calls, then the update.  The gradient buffer is cut into that many contiguous buckets in
  * backward-production order -- {fc7, decoder} (68 MB) | {fc6} (411 MB) | {conv4, conv5} (52 MB) | {conv1 .. conv3} (7 MB) at full
- * width -- and bucket b's gradients are final (stream-ordered) once the call
- * fcn8s_backward_bucket(m, fcn8s_bucket_complete_after(m, b)) has returned.  By default ("defer_wgrad" 0) that is call b itself, so
- * every bucket's exchange overlaps the rest of the backward pass; with defer_wgrad >= 1 the conv buckets (2, 3) are final only at the
- * last call, with defer_wgrad = 3 all four are.
+ * width -- and bucket b's gradients are final (stream-ordered) once fcn8s_backward_bucket(m, b) has returned, so every bucket's
+ * exchange overlaps the rest of the backward pass.  fcn8s_bucket_complete_after(m, b) returns b; it is kept for compatibility.
  * fcn8s_bucket_wait makes another stream (RCCL's, a torch side stream) wait for exactly the last kernel that writes into bucket b
  * -- for fc6 that is its weight gradient, 3 ms of data gradient earlier than the end of call 1 -- without blocking the host; it is
- * valid once the completing call has returned and until the next fcn8s_forward_loss.
+ * valid once call b has returned and until the next fcn8s_forward_loss.
  * `grad_scale` multiplies the gradients inside the update (1/world_size).      */
 int fcn8s_forward_loss(fcn8s_model* m, const void* images, int image_dtype, const uint8_t* label_ids,
                        int N, int H, int W, float keep_prob, float l2_rate, int where);
@@ -158,8 +156,8 @@ int fcn8s_read_loss(fcn8s_model* m, float* loss_out);                /* synchron
  * reference's Python and binds this ABI gets multi-GPU training without torch.distributed:
  *     rank 0: fcn8s_comm_unique_id(id)  -> hand the FCN8S_COMM_ID_BYTES bytes to every rank by any means (file, socket, MPI)
  *     all   : fcn8s_comm_init(m, id, FCN8S_COMM_ID_BYTES, rank, world);  fcn8s_comm_broadcast_params(m, 0)
- *     step  : fcn8s_forward_loss; for b in 0 .. fcn8s_num_buckets-1 { fcn8s_backward_bucket(m, b); for every bucket r with
- *             fcn8s_bucket_complete_after(m, r) == b: fcn8s_allreduce_bucket(m, r) }; fcn8s_apply_update(m, opt, lr, 1.0f / world)
+ *     step  : fcn8s_forward_loss; for b in 0 .. fcn8s_num_buckets-1 { fcn8s_backward_bucket(m, b); fcn8s_allreduce_bucket(m, b) };
+ *             fcn8s_apply_update(m, opt, lr, 1.0f / world)
  *     eval  : fcn8s_eval_step ...; fcn8s_comm_allreduce_metrics(m); fcn8s_metrics_get
  * fcn8s_allreduce_bucket queues an in-place SUM all-reduce of the bucket on a stream the library owns, behind the event of the last
  * kernel that writes into the bucket (never behind later backward kernels) and returns at once; fcn8s_comm_wait makes the model's
@@ -251,14 +249,6 @@ int fcn8s_get_precision(const fcn8s_model* m);
  *                              tile `tile_hires` (F(4x4) carries half the round-off of F(6x6); the layers next to the input see the longest sums)
  *     "winograd_fc6"      1    fc6 as a 2x2 grid of 4x4 sub-filters through F(4x4,4x4); 0 = direct 7x7
  *     "tconv_gemm"        1    the 16x16/8 transposed conv as one GEMM over output blocks (blocked logits); 0 = 64 sub-pixel phases
- *     "defer_wgrad"       0    deferred weight gradients (an experiment kept for its evidence, profiles/r03_overlap_*.txt: co-running gains nothing on
- *                              gfx950, on shared or on disjoint CUs): 1 = the weight-gradient GEMMs of conv3_1 .. conv5_3 are held back and run on a
- *                              second stream beside the end of the data-gradient chain (blocks 2 and 1); 2 = fc6 / fc7 as well (fused
- *                              fcn8s_train_step only: the bucket API keeps buckets 0 and 1 final at their own calls, for an early all-reduce);
- *                              3 = fc6 / fc7 through the bucket API too (fcn8s_bucket_complete_after then names the last call for every bucket)
- *     "defer_start_block" 2    the VGG block at whose backward pass the held-back GEMMs are launched
- *     "defer_tail_cus"    0    > 0: from that block on the data-gradient chain runs on a stream restricted to the first n CUs and the held-back
- *                              GEMMs on the remaining 256 - n (hipExtStreamCreateWithCUMask); 0: both share all CUs
  *     "fuse_dgrad_dout"   1    inside a VGG block the gather kernel of a conv's data gradient writes dM = A dZ A^T of the previous conv directly
  *                              (that conv's weight gradient and adjoint data gradient consume only dM): its dZ is never written; 0 = two kernels
  *     "fuse_out_in"       1    forward, inside a VGG block: the output transform of a conv is fused with the input transform of the next one (both
@@ -287,7 +277,6 @@ int fcn8s_get_precision(const fcn8s_model* m);
  *                              bf16 copies -- maxima and gradient routing among the bf16 values; the pooled maps pool1 / pool2 / pool5; the output gradient of a conv that
  *                              follows a bf16 conv, together with that layer's bias gradient).  fcn8s_get_activation of such a layer then returns FCN8S_ERR_STATE naming
  *                              this option; 0 keeps every fp32 tensor too (same values into every product: bit-identical losses and weight gradients)
- *     "bf16_fuse_convert" 0    FCN8S_PREC_BF16_TRAIN: the producing convolution's epilogue also writes its consumer's padded bf16 copy (measured slower)
  *     "bf16_fuse_pool"    1    FCN8S_PREC_BF16_TRAIN: the forward pools keep routing bytes (and write their consumer's bf16 copy), the max-pool backward kernel reads those bytes and
  *                              writes the last conv's padded bf16 dZ copy and bias gradient itself; 0 = plain pools + conversion passes
  *     "bf16_rows_bn"      0    FCN8S_PREC_BF16_TRAIN: 128 = the flat-position 3 x 3 convolution kernel takes its 128-column tile where it can (A/B; slower)

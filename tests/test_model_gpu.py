@@ -515,32 +515,29 @@ def test_frozen_parameters_cache_and_invalidation():
     e.close(); e2.close()
 
 
-@pytest.mark.parametrize("options", [{"defer_wgrad": 2}, {"defer_wgrad": 2, "defer_tail_cus": 96}, {"defer_wgrad": 1, "defer_start_block": 3}])
-def test_deferred_weight_gradients_change_nothing(options):
-    """The `defer_wgrad` experiment (weight-gradient GEMMs of the deep layers on a second stream, optionally on CUs of their own;
-    include/fcn8s_hip.h) only reorders independent work: a full-width fused training step and a split-phase step produce the gradients of the
-    default schedule."""
+def test_bucket_api_and_fused_step_give_the_same_gradients():
+    """A full-width split-phase step (fcn8s_forward_loss + fcn8s_backward_bucket) and the fused fcn8s_train_step run one schedule and
+    produce the same loss and gradients.  The retired schedule options are unknown keys now."""
+    import ctypes as C
+    from fcn8s_tensorflow_amd import _lib as L
     from fcn8s_tensorflow_amd.engine import Engine
     P = orc.init_params(20, seed=3, decoder_std_scale=30.0, bias_std=0.05)
     img, lab = batch(1, 192, 192, seed=9)
-    out = []
-    for opts in ({}, options):
-        e = Engine(20, options=opts)
-        for k, v in opts.items():
-            assert e.get_option(k) == v
-        e.set_params(P)
-        loss2 = e.forward_backward(img, lab, keep_prob=1.0, l2_rate=1e-3)               # bucket API (level capped at 1)
-        g2 = e.get_grads()
-        loss, step = e.train_step(img, lab, 1e-6, keep_prob=1.0, l2_rate=1e-3)         # fused step (level 2 allowed), same parameters
-        g1 = e.get_grads()                                                               # the gradients the update consumed
-        out.append((loss, g1, loss2, g2))
-        e.close()
-    (l0, g0, l20, g20), (l1, g1, l21, g21) = out
-    assert l0 == l1 and l20 == l21 and l0 == l20
-    for k in g0:
+    e = Engine(20)
+    for key in (b"defer_wgrad", b"defer_start_block", b"defer_tail_cus", b"bf16_fuse_convert"):
+        assert L.lib.fcn8s_set_option(e.h, key, 1) == L.ERR_NOT_FOUND, key
+        v = C.c_int64(-1)
+        assert L.lib.fcn8s_get_option(e.h, key, C.byref(v)) == L.ERR_NOT_FOUND, key
+    e.set_params(P)
+    loss2 = e.forward_backward(img, lab, keep_prob=1.0, l2_rate=1e-3)               # bucket API
+    g2 = e.get_grads()
+    loss, step = e.train_step(img, lab, 1e-6, keep_prob=1.0, l2_rate=1e-3)         # fused step, same parameters
+    g1 = e.get_grads()                                                               # the gradients the update consumed
+    e.close()
+    assert loss == loss2
+    for k in g2:
         # (split-K sums use float atomics: their order is not reproducible between two runs of the SAME schedule either)
-        assert rel(g1[k], g0[k]) < 1e-4, k
-        assert rel(g21[k], g20[k]) < 1e-4, k
+        assert rel(g1[k], g2[k]) < 1e-4, k
 
 
 def test_bf16_fc_256_tile_kernel():
@@ -660,15 +657,13 @@ def test_bf16_train_mode():
         assert l2 < 2e-2, (k, l2)
     d32 = max(float(np.linalg.norm(np.asarray(g_ref[k], np.float64) - g_32[k]) / (np.linalg.norm(g_32[k]) + 1e-30)) for k in g_ref)
     print("bf16_train: worst gradient tensor %s %.2e in L2 against the same-arithmetic oracle (that oracle is %.2e from the fp32 graph's gradients); %s" % (worst[0], worst[1], d32, stats))
-    # the mode's arithmetic does not depend on `defer_wgrad` (round 5's held-back fc7 weight gradient ran the fp32 kernel: ADVICE round 5): the same fc6 / fc7
-    # weight gradients at every level, to the round-off of their atomically joined split sums
-    for level in (2, 3):
-        e.set_option("defer_wgrad", level)
+    # the mode's arithmetic is the same on every backward pass (round 5's held-back fc7 weight gradient ran the fp32 kernel: ADVICE round 5): the same fc6 / fc7
+    # weight gradients on each repeat, to the round-off of their atomically joined split sums
+    for rep in range(2):
         e.forward_backward(img, onehot, keep_prob=1.0, l2_rate=1e-3)
         g2 = e.get_grads()
         for k in ("fc7/weights", "fc6/weights", "conv4_2/filter", "fc7/biases"):
-            assert rel(g2[k], g[k]) < 1e-5, (level, k, rel(g2[k], g[k]))
-    e.set_option("defer_wgrad", 0)
+            assert rel(g2[k], g[k]) < 1e-5, (rep, k, rel(g2[k], g[k]))
     # (5)
     loss2, step = e.train_step(img, lab, 1e-6, keep_prob=0.5)
     assert step == 1 and np.isfinite(loss2)
