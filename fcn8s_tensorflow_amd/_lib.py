@@ -79,6 +79,7 @@ SIGNATURES = {
     "fcn8s_metrics_raw": (_i, [_p, _p, _dp, _i64p]),
     "fcn8s_metrics_set_raw": (_i, [_p, _p, C.c_double, _i64]),
     "fcn8s_predict": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _i]),
+    "fcn8s_predict_tta": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _p, _i]),
     "fcn8s_global_step": (_i64, [_p]),
     "fcn8s_set_global_step": (_i, [_p, _i64]),
     "fcn8s_get_opt_state": (_i, [_p, _p, _p, _sz]),
@@ -98,6 +99,8 @@ SIGNATURES = {
     "fcn8s_profile_num_groups": (_i, [_p]),
     "fcn8s_profile_get": (_i, [_p, _i, C.POINTER(C.c_char_p), _dp, _i64p, _dp, _dp]),
     "fcn8s_op_preprocess": (_i, [_p, _p, _i, _p, _i64]),
+    "fcn8s_op_tta_input": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "fcn8s_op_tta_accumulate": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i, _p, _p]),
     "fcn8s_op_augment_u8": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i]),
     "fcn8s_op_resample_u8": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i]),
     "fcn8s_op_conv2d": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i]),

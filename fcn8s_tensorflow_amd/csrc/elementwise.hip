@@ -4,6 +4,7 @@
 // matrix, column sums (bias gradients), optimizer updates and the small weight
 // re-layouts.  16-byte vector accesses, grid-stride loops capped at 2048 blocks.
 #include "fcn8s_internal.h"
+#include "cv_resize.h"
 #include <math.h>
 #include <map>
 #include <mutex>
@@ -1122,31 +1123,7 @@ void launch_augment_u8(const unsigned char* img, const unsigned char* lab, unsig
 //   resize to (h',w')        : rh = Ho = h', rw = Wo = w', offset 0
 //   scale by f <= 1 / f > 1  : rh = int(H f), rw = int(W f), offset = +/- |int((H - rh) / 2)| ...
 //   translate by (dx,dy)     : rh = H, rw = W (exact copy), offset = (dy,dx)
-// INTER_LINEAR: f = float((d + 0.5) * scale - 0.5) with scale = 1 / (dst / src) in double; s = floor(f); f -= s; columns clamp s and zero f
-// at the borders, rows clamp the two row numbers; taps rounded to 11-bit fixed point; horizontal pass in int32; vertical pass
-// (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.  An exact 2x shrink in both directions is the 2x2 box mean (INTER_AREA).
-// INTER_NEAREST: s = min(floor(d * (1 / (dst / src))), src - 1).
-struct CvTap { int s; int w0, w1; };
-static __device__ __forceinline__ CvTap cv_linear_tap(int d, int src, int dst, bool clamp_index)
-{
-    const double scale = 1.0 / ((double)dst / (double)src);
-    float f = (float)__dsub_rn(__dmul_rn((double)d + 0.5, scale), 0.5);
-    int s = (int)floorf(f);
-    f = __fsub_rn(f, (float)s);
-    if (clamp_index) {
-        if (s < 0) { f = 0.f; s = 0; }
-        if (s >= src - 1) { f = 0.f; s = src - 1; }
-    }
-    CvTap t; t.s = s;
-    t.w0 = (int)rintf(__fmul_rn(__fsub_rn(1.f, f), 2048.f)); t.w1 = (int)rintf(__fmul_rn(f, 2048.f));
-    return t;
-}
-static __device__ __forceinline__ int cv_nearest_index(int d, int src, int dst)
-{
-    const double ifx = 1.0 / ((double)dst / (double)src);
-    const int s = (int)floor(__dmul_rn((double)d, ifx));
-    return s < src - 1 ? s : src - 1;
-}
+// The arithmetic of both interpolations: cv_resize.h.
 __global__ __launch_bounds__(256) void resample_u8_kernel(const unsigned char* __restrict__ img, const unsigned char* __restrict__ lab,
                                                           unsigned char* __restrict__ oimg, unsigned char* __restrict__ olab,
                                                           const int* __restrict__ params, int N, int H, int W, int Ho, int Wo, int void_id)
@@ -1164,30 +1141,10 @@ __global__ __launch_bounds__(256) void resample_u8_kernel(const unsigned char* _
         }
         if (olab) olab[i] = lab[((long long)n * H + cv_nearest_index(ry, H, rh)) * W + cv_nearest_index(rx, W, rw)];
         if (!oimg) continue;
-        const unsigned char* base = img + (long long)n * H * W * 3;
-        if (rh == H && rw == W) {
-            const long long src = ((long long)ry * W + rx) * 3;
-            oimg[i * 3] = base[src]; oimg[i * 3 + 1] = base[src + 1]; oimg[i * 3 + 2] = base[src + 2];
-            continue;
-        }
-        if (H == 2 * rh && W == 2 * rw) {
-            const unsigned char* p0 = base + ((long long)(2 * ry) * W + 2 * rx) * 3;
-            const unsigned char* p1 = p0 + (long long)W * 3;
+        int rgb[3];
+        cv_resize_linear_px(img + (long long)n * H * W * 3, H, W, rh, rw, ry, rx, rgb);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) oimg[i * 3 + c] = (unsigned char)(((int)p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2);
-            continue;
-        }
-        const CvTap tx = cv_linear_tap(rx, W, rw, true), ty = cv_linear_tap(ry, H, rh, false);
-        const int x1 = tx.s + 1 < W ? tx.s + 1 : W - 1;                       // (weight 0 there)
-        const int r0 = ty.s < 0 ? 0 : (ty.s >= H ? H - 1 : ty.s), r1 = ty.s + 1 < 0 ? 0 : (ty.s + 1 >= H ? H - 1 : ty.s + 1);
-        const unsigned char* q0 = base + (long long)r0 * W * 3;
-        const unsigned char* q1 = base + (long long)r1 * W * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int S0 = (int)q0[tx.s * 3 + c] * tx.w0 + (int)q0[x1 * 3 + c] * tx.w1;
-            const int S1 = (int)q1[tx.s * 3 + c] * tx.w0 + (int)q1[x1 * 3 + c] * tx.w1;
-            oimg[i * 3 + c] = (unsigned char)((((ty.w0 * (S0 >> 4)) >> 16) + ((ty.w1 * (S1 >> 4)) >> 16) + 2) >> 2);
-        }
+        for (int c = 0; c < 3; ++c) oimg[i * 3 + c] = (unsigned char)rgb[c];
     }
 }
 void launch_resample_u8(const unsigned char* img, const unsigned char* lab, unsigned char* oimg, unsigned char* olab, const int* params,

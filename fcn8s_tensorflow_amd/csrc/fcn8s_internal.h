@@ -262,6 +262,14 @@ void launch_augment_u8(const unsigned char* img, const unsigned char* lab, unsig
 // params: int[4] per image = {resized height, resized width, y offset, x offset}
 void launch_resample_u8(const unsigned char* img, const unsigned char* lab, unsigned char* oimg, unsigned char* olab, const int* params,
                         int N, int H, int W, int Ho, int Wo, int void_id, hipStream_t s);
+// tta.hip (fcn8s_predict_tta).  Input: image [N,H,W,3] (dtype 0 uint8, 1 float32 -- float only with Hs = H, Ws = W) -> x0 [N,Hp,Wp,4]: cv2
+// INTER_LINEAR resize to Hs x Ws (cv_resize.h), mirror if flip, BGR mean subtraction, zeros (the mean colour) outside [0,Hs)x[0,Ws)
+void launch_tta_input(const void* img, int dtype, int N, int H, int W, int Hs, int Ws, int Hp, int Wp, int flip, float* out4, hipStream_t s);
+// Accumulate: logits of the padded map described by `map` (map.H x map.W pixels; blocked or NHWC) over [0,Hs)x[0,Ws), un-mirrored if flip,
+// bilinear (half-pixel) to H x W, softmax; first: acc = p, else acc += p; last: (acc + p) / npasses -> softmax_out [N,H,W,C] and / or
+// argmax_out [N,H,W] (acc not written; may be nullptr when first and last)
+void launch_tta_accumulate(const float* logits, const PixMap& map, int N, int Hs, int Ws, int flip, int C, int H, int W, float* acc,
+                           int first, int last, int npasses, float* softmax_out, long long* argmax_out, hipStream_t s);
 // wrapping sum over every 61st element's bit pattern (weighted by position): changes whenever an optimizer step or a bulk copy touches the buffer
 void launch_fingerprint(const float* x, long long n, unsigned long long* out, hipStream_t s);
 void launch_init_normal(float* w, long long n, float stddev, int truncated, unsigned long long seed,

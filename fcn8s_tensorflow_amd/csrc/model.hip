@@ -140,6 +140,9 @@ struct fcn8s_model {
     int conv1_in_transform = 1;                                           // option: conv1_1 is evaluated inside conv1_2's input transform (its activation tensor is never written)
     unsigned short* d_wbf16 = nullptr; size_t wbf16_elems = 0;            // bf16 copy of one layer's kernel at a time (K-tile-major or transposed)
     std::map<std::string, unsigned short*> wbf16_cache;                   // ... per layer, valid while frozen
+    // fcn8s_predict_tta on a model that is not frozen keeps the storage of the banks it built (u_cache / wbf16_cache) but not their contents: the keys
+    // ("u:<key>" / "w:<key>") whose contents must be rebuilt before use, and whether the first frozen pass must rebuild the padded kernels + fingerprint
+    std::set<std::string> bank_stale; bool banks_stale = false;
     int bf16_gemm256 = 1;                                                 // bf16_fc mode: 256 x 256 LDS-DMA kernel -- 0 never, 1 when it fills the chip, 2 whenever shapes allow
     unsigned short* d_abf16 = nullptr; size_t abf16_elems = 0;            // bf16 copy of the layer's input activations
     // bf16 modes, training: zero-bordered padded bf16 copies of the inputs of conv3_1 .. conv5_3, one per layer (the border is written once, at
@@ -157,6 +160,10 @@ struct fcn8s_model {
     int bf16_acts = 1;                                                    // option: bf16_train training passes keep a conv -> conv activation only as the consumer's padded bf16 copy (the producer's epilogue writes it; no fp32 tensor, no conversion pass)
     int saved_wino_min_cin = -1, saved_wino_fc6 = -1;                      // the options the mode overrides (the direct path carries it), restored on leaving
     int bf16_copy_by_transform = 1;                                       // option: 0 = every bf16 layer converts its input with a pass of its own (round 3's path)
+    std::set<std::string> g16_stale;                                      // bf16_train copies ("x:<layer>" / "d:<layer>") whose zero border belongs to another shape (fcn8s_predict_tta re-plans)
+    int64_t ws_allocs = 0;                                                // statistic "workspace_allocations": device allocations for the workspace, the TTA scratch, the bf16 copies and the cached filter banks
+    bool x0_ready = false;                                                // forward(): x0 is already written (fcn8s_predict_tta's tta_input), skip the preprocess kernel
+    char* tta_buf = nullptr; size_t tta_bytes = 0;                        // fcn8s_predict_tta: staged images, accumulator, staged output (grown, never shrunk)
     hipStream_t stream = nullptr;
     int64_t step = 0;
     // workspace for the current (N,H,W)
@@ -414,8 +421,10 @@ void conv_winograd(fcn8s_model* m, int tile, int KS, const char* tag, const floa
     const bool fwd_call = std::string(tag).find("dgrad") == std::string::npos;      // (v_ready in a forward call = V written by the previous conv's fused output transform)
     if (m && m->frozen && layer && fwd_call) {
         float*& cu = m->u_cache[std::string(layer) + "#" + std::to_string(tile)];       // (the tile, hence the bank's shape, depends on the image size)
-        if (cu) { u = cu; u_cached = true; }
-        else if (hipMalloc((void**)&cu, (size_t)P * Kg * Cout * sizeof(float)) == hipSuccess) u = cu;       // filled below, reused from the next call on
+        const std::string key = "u:" + std::string(layer) + "#" + std::to_string(tile);
+        if (cu && !m->bank_stale.count(key)) { u = cu; u_cached = true; }
+        else if (cu) { u = cu; m->bank_stale.erase(key); }                                  // kept storage: refilled below
+        else if (hipMalloc((void**)&cu, (size_t)P * Kg * Cout * sizeof(float)) == hipSuccess) { u = cu; ++m->ws_allocs; }     // filled below, reused from the next call on
         else { cu = nullptr; (void)hipGetLastError(); }
         a.w = u;
     }
@@ -452,7 +461,7 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
         bool ok = true;
         if (m->wbf16_elems < wneed) {
             if (m->d_wbf16) { hipStreamSynchronize(s); hipFree(m->d_wbf16); m->d_wbf16 = nullptr; m->wbf16_elems = 0; }
-            if (hipMalloc((void**)&m->d_wbf16, wneed * sizeof(unsigned short)) != hipSuccess) { (void)hipGetLastError(); ok = false; } else m->wbf16_elems = wneed;
+            if (hipMalloc((void**)&m->d_wbf16, wneed * sizeof(unsigned short)) != hipSuccess) { (void)hipGetLastError(); ok = false; } else { m->wbf16_elems = wneed; ++m->ws_allocs; }
         }
         unsigned short* dyb = ok ? dyb_for(m, layer, x, N, H, W, Cin, K, s) : nullptr;
         if (dyb) {
@@ -776,25 +785,24 @@ void tconv_wgrad(fcn8s_model* m, const float* x, const float* dy, float* dw, int
 }
 
 // ---- workspace --------------------------------------------------------------------
-int ensure_workspace(fcn8s_model* m, int N, int H, int W)
+// The arena's layout for one (N, H, W): named items at 256-byte aligned offsets, then the staged images / labels, predictions and loss partials.
+struct WsItem { std::string name; size_t n; int h, w, c; float** extra; };
+struct WsPlan { std::vector<WsItem> items; std::vector<size_t> offs; size_t o_img = 0, o_lab = 0, o_pred = 0, o_part = 0, bytes = 0; };
+int check_shape(fcn8s_model* m, int N, int H, int W)
 {
     if (N <= 0) return fail(m, FCN8S_ERR_SHAPE, "batch size must be positive");
     if (H <= 0 || W <= 0 || H % 32 || W % 32)
         return fail(m, FCN8S_ERR_SHAPE, "image height and width must be positive multiples of 32 (five 2x2 pools, then x2, x2, x8 upsampling must line up with the skip connections)");
-    if (m->arena && m->N == N && m->H == H && m->W == W) return FCN8S_OK;
-    if (m->arena) { hipStreamSynchronize(m->stream); hipFree(m->arena); m->arena = nullptr; }
-    for (auto& kv : m->xbf16) if (kv.second) hipFree(kv.second);
-    m->xbf16.clear();
-    for (auto& kv : m->xg16) if (kv.second) hipFree(kv.second);
-    m->xg16.clear(); m->xg16_elems.clear();
-    for (auto& kv : m->dyg16) if (kv.second) hipFree(kv.second);
-    m->dyg16.clear(); m->dyg16_elems.clear(); m->xg16_filled.clear(); m->dyg16_filled.clear();
-    m->plan_N = N;                 // the batch size the per-layer Winograd tiles are chosen for (wino_tile_for), from here until the next re-plan
-    m->acts.clear();
-    m->have_forward = m->have_loss = false;
+    return FCN8S_OK;
+}
+// (sets m->plan_N = N: the batch size the per-layer Winograd tiles are chosen for, wino_tile_for, from here until the next re-plan)
+void plan_workspace(fcn8s_model* m, int N, int H, int W, WsPlan& pl)
+{
+    m->plan_N = N;
     const int C = m->C;
-    struct Item { std::string name; size_t n; int h, w, c; float** extra; };
-    std::vector<Item> items;
+    using Item = WsItem;
+    std::vector<Item>& items = pl.items;
+    items.clear(); pl.offs.clear();
     auto add = [&](const std::string& nm, int h, int w, int c, float** extra = nullptr) {
         items.push_back({nm, (size_t)N * h * w * c, h, w, c, extra});
     };
@@ -833,11 +841,8 @@ int ensure_workspace(fcn8s_model* m, int N, int H, int W)
     add("s7", h5, w5, C); add("p4", h4, w4, C); add("p3", h3, w3, C);
     add("a4", h4, w4, C); add("a3", h3, w3, C); add("logits", H, W, C);
     add("dlogits", H, W, C, &m->dlogits);
-    m->pm = PixMap{0, H, W, H / 8 + 1, W / 8 + 1, 8};
-    m->logits_b = m->dlogits_b = m->tg_A = m->tg_dA = nullptr;
     if (m->tconv_gemm) {
-        const size_t rows = (size_t)N * m->pm.QH * m->pm.QW;
-        m->pm.blocked = 1;
+        const size_t rows = (size_t)N * (H / 8 + 1) * (W / 8 + 1);
         items.push_back({"logits_b", rows * 64 * C, 0, 0, 0, &m->logits_b});
         items.push_back({"dlogits_b", rows * 64 * C, 0, 0, 0, &m->dlogits_b});
         items.push_back({"tg_A", rows * m->tg_kp, 0, 0, 0, &m->tg_A});
@@ -877,7 +882,6 @@ int ensure_workspace(fcn8s_model* m, int N, int H, int W)
             vmax = std::max(vmax, slab_floats(h5_, w5_, std::max(m->widths[4], m->widths[5]), 7));
             vmax = std::max(vmax, (size_t)al * al * (size_t)wino_slab(wino_tiles(4, N, h5_, w5_), std::max(m->widths[4], m->widths[5])));
         }
-        m->d_wino_v = m->d_wino_m = nullptr;
         if (vmax) { items.push_back({"wino_v", vmax, 0, 0, 0, &m->d_wino_v}); items.push_back({"wino_m", vmax, 0, 0, 0, &m->d_wino_m}); }
         if (m->wino_min_cin > 0) {    // the forward pass keeps each Winograd layer's transformed input for the weight gradient
             int cin = 3;
@@ -894,25 +898,78 @@ int ensure_workspace(fcn8s_model* m, int N, int H, int W)
     }
 
     size_t bytes = 0;
-    std::vector<size_t> offs;
-    for (auto& it : items) { offs.push_back(bytes); bytes = align_up(bytes + it.n * sizeof(float), 256); }
+    for (auto& it : items) { pl.offs.push_back(bytes); bytes = align_up(bytes + it.n * sizeof(float), 256); }
     const size_t npix = (size_t)N * H * W;
-    const size_t o_img = bytes;  bytes = align_up(bytes + npix * 3 * sizeof(float), 256);
-    const size_t o_lab = bytes;  bytes = align_up(bytes + npix, 256);
-    const size_t o_pred = bytes; bytes = align_up(bytes + npix * sizeof(long long), 256);
-    const size_t o_part = bytes; bytes = align_up(bytes + 4096 * sizeof(double), 256);
-    hipError_t e = hipMalloc((void**)&m->arena, bytes);
-    if (e != hipSuccess) { m->arena = nullptr; return fail(m, FCN8S_ERR_OOM, std::string("workspace hipMalloc failed: ") + hipGetErrorString(e)); }
-    m->arena_bytes = bytes;
-    for (size_t i = 0; i < items.size(); ++i) {
-        float* p = (float*)(m->arena + offs[i]);
-        if (items[i].extra) *items[i].extra = p;
-        Act a; a.p = p; a.n = items[i].n; a.H = items[i].h; a.W = items[i].w; a.C = items[i].c;
-        m->acts[items[i].name] = a;
+    pl.o_img = bytes;  bytes = align_up(bytes + npix * 3 * sizeof(float), 256);
+    pl.o_lab = bytes;  bytes = align_up(bytes + npix, 256);
+    pl.o_pred = bytes; bytes = align_up(bytes + npix * sizeof(long long), 256);
+    pl.o_part = bytes; bytes = align_up(bytes + 4096 * sizeof(double), 256);
+    pl.bytes = bytes;
+}
+// point the model's tensors into the arena (>= pl.bytes) at the plan's offsets
+void carve_workspace(fcn8s_model* m, int N, int H, int W, const WsPlan& pl)
+{
+    m->acts.clear();
+    m->have_forward = m->have_loss = false;
+    m->pm = PixMap{m->tconv_gemm ? 1 : 0, H, W, H / 8 + 1, W / 8 + 1, 8};
+    m->logits_b = m->dlogits_b = m->tg_A = m->tg_dA = nullptr;
+    m->d_wino_v = m->d_wino_m = nullptr;
+    for (size_t i = 0; i < pl.items.size(); ++i) {
+        float* p = (float*)(m->arena + pl.offs[i]);
+        if (pl.items[i].extra) *pl.items[i].extra = p;
+        Act a; a.p = p; a.n = pl.items[i].n; a.H = pl.items[i].h; a.W = pl.items[i].w; a.C = pl.items[i].c;
+        m->acts[pl.items[i].name] = a;
     }
-    m->d_images = m->arena + o_img; m->d_labels = (uint8_t*)(m->arena + o_lab);
-    m->d_pred = (long long*)(m->arena + o_pred); m->d_partials = (double*)(m->arena + o_part);
+    m->d_images = m->arena + pl.o_img; m->d_labels = (uint8_t*)(m->arena + pl.o_lab);
+    m->d_pred = (long long*)(m->arena + pl.o_pred); m->d_partials = (double*)(m->arena + pl.o_part);
     m->N = N; m->H = H; m->W = W;
+}
+int ensure_workspace(fcn8s_model* m, int N, int H, int W)
+{
+    int rc = check_shape(m, N, H, W); if (rc) return rc;
+    if (m->arena && m->N == N && m->H == H && m->W == W) return FCN8S_OK;
+    if (m->arena) { hipStreamSynchronize(m->stream); hipFree(m->arena); m->arena = nullptr; }
+    for (auto& kv : m->xbf16) if (kv.second) hipFree(kv.second);
+    m->xbf16.clear();
+    for (auto& kv : m->xg16) if (kv.second) hipFree(kv.second);
+    m->xg16.clear(); m->xg16_elems.clear();
+    for (auto& kv : m->dyg16) if (kv.second) hipFree(kv.second);
+    m->dyg16.clear(); m->dyg16_elems.clear(); m->xg16_filled.clear(); m->dyg16_filled.clear(); m->g16_stale.clear();
+    m->acts.clear();
+    m->have_forward = m->have_loss = false;
+    WsPlan pl;
+    plan_workspace(m, N, H, W, pl);
+    hipError_t e = hipMalloc((void**)&m->arena, pl.bytes);
+    if (e != hipSuccess) { m->arena = nullptr; return fail(m, FCN8S_ERR_OOM, std::string("workspace hipMalloc failed: ") + hipGetErrorString(e)); }
+    ++m->ws_allocs;
+    m->arena_bytes = pl.bytes;
+    carve_workspace(m, N, H, W, pl);
+    return FCN8S_OK;
+}
+// fcn8s_predict_tta: every pass runs in one arena of at least `bytes` (the largest pass's plan), re-carved when the pass shape changes.  The bf16_train
+// copies are kept and only their borders zeroed again (g16_for); the training-only copies of the bf16 forward modes (xbf16) are dropped on a re-plan.
+int ensure_workspace_at_least(fcn8s_model* m, int N, int H, int W, size_t bytes)
+{
+    int rc = check_shape(m, N, H, W); if (rc) return rc;
+    const bool same = m->arena && m->N == N && m->H == H && m->W == W;
+    if (same && m->arena_bytes >= bytes) return FCN8S_OK;
+    WsPlan pl;
+    plan_workspace(m, N, H, W, pl);
+    bytes = std::max(bytes, pl.bytes);
+    if (!m->arena || m->arena_bytes < bytes) {
+        if (m->arena) { hipStreamSynchronize(m->stream); hipFree(m->arena); m->arena = nullptr; m->arena_bytes = 0; m->N = m->H = m->W = 0; m->acts.clear(); }
+        hipError_t e = hipMalloc((void**)&m->arena, bytes);
+        if (e != hipSuccess) { m->arena = nullptr; return fail(m, FCN8S_ERR_OOM, std::string("workspace hipMalloc failed: ") + hipGetErrorString(e)); }
+        ++m->ws_allocs;
+        m->arena_bytes = bytes;
+    }
+    if (!same) {
+        if (!m->xbf16.empty()) { hipStreamSynchronize(m->stream); for (auto& kv : m->xbf16) if (kv.second) hipFree(kv.second); m->xbf16.clear(); }
+        for (auto& kv : m->xg16) m->g16_stale.insert("x:" + kv.first);
+        for (auto& kv : m->dyg16) m->g16_stale.insert("d:" + kv.first);
+        m->xg16_filled.clear(); m->dyg16_filled.clear();
+    }
+    carve_workspace(m, N, H, W, pl);
     return FCN8S_OK;
 }
 
@@ -1030,16 +1087,18 @@ bool bf16_conv_layer(fcn8s_model* m, const char* tag, const char* wname, const c
     if (m->wbf16_elems < wneed) {
         if (m->d_wbf16) { hipStreamSynchronize(s); hipFree(m->d_wbf16); m->d_wbf16 = nullptr; m->wbf16_elems = 0; }
         if (hipMalloc((void**)&m->d_wbf16, wneed * sizeof(unsigned short)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        m->wbf16_elems = wneed;
+        m->wbf16_elems = wneed; ++m->ws_allocs;
     }
     // weights: bf16, K-tile-major blocks for the 128 x 128 kernel or transposed [Cout][K] for the 256 x 256 one; with frozen parameters
     // (evaluation / serving loops) each layer's copy is made once and kept
     unsigned short* wbuf = m->d_wbf16;
     bool have = false;
     if (m->frozen) {
-        unsigned short*& c = m->wbf16_cache[std::string(wname) + (big ? "#t" : "#b")];
-        if (c) { wbuf = c; have = true; }
-        else if (hipMalloc((void**)&c, wneed * sizeof(unsigned short)) == hipSuccess) wbuf = c;
+        const std::string key = std::string(wname) + (big ? "#t" : "#b");
+        unsigned short*& c = m->wbf16_cache[key];
+        if (c && !m->bank_stale.count("w:" + key)) { wbuf = c; have = true; }
+        else if (c) { wbuf = c; m->bank_stale.erase("w:" + key); }                         // kept storage: refilled below
+        else if (hipMalloc((void**)&c, wneed * sizeof(unsigned short)) == hipSuccess) { wbuf = c; ++m->ws_allocs; }
         else { c = nullptr; (void)hipGetLastError(); }
     }
     if (!have) { ProfScope ps(m, "weight_relayout", 0, 6.0 * K * cout);
@@ -1048,7 +1107,7 @@ bool bf16_conv_layer(fcn8s_model* m, const char* tag, const char* wname, const c
     const size_t nin = (size_t)N * (h + 2 * pad) * (w + 2 * pad) * cin;
     if (nin % 8 == 0 && m->abf16_elems < nin && !(big && xb_ready)) {
         if (m->d_abf16) { hipStreamSynchronize(s); hipFree(m->d_abf16); m->d_abf16 = nullptr; m->abf16_elems = 0; }
-        if (hipMalloc((void**)&m->d_abf16, nin * sizeof(unsigned short)) == hipSuccess) m->abf16_elems = nin; else (void)hipGetLastError();
+        if (hipMalloc((void**)&m->d_abf16, nin * sizeof(unsigned short)) == hipSuccess) { m->abf16_elems = nin; ++m->ws_allocs; } else (void)hipGetLastError();
     }
     const double M = (double)Mrows;
     if (big && (xb_ready || (m->d_abf16 && m->abf16_elems >= nin))) {
@@ -1088,12 +1147,14 @@ unsigned short* g16_for(fcn8s_model* m, std::map<std::string, unsigned short*>& 
     const size_t need = (size_t)(R + 2 * G) * C;
     unsigned short*& p = bufs[layer];
     size_t& have = sizes[layer];
-    if (!p || have != need) {           // (another shape: another border)
+    const std::string stale_key = std::string(&bufs == &m->xg16 ? "x:" : "d:") + layer;
+    if (!p || have < need) {
         if (p) { hipStreamSynchronize(s); hipFree(p); p = nullptr; have = 0; }
         if (hipMalloc((void**)&p, need * sizeof(unsigned short)) != hipSuccess) { p = nullptr; (void)hipGetLastError(); return nullptr; }
-        have = need;
+        have = need; ++m->ws_allocs;
         hipMemsetAsync(p, 0, need * sizeof(unsigned short), s);
-    }
+        m->g16_stale.erase(stale_key);
+    } else if (m->g16_stale.erase(stale_key)) hipMemsetAsync(p, 0, need * sizeof(unsigned short), s);     // (another shape: another border)
     return p + g16_off(G, C);           // padded pixel 0 of plane 0 (planes are g16_ps() apart)
 }
 // the copy of layer `layer`'s INPUT (forward pass; read again by its weight gradient)
@@ -1126,6 +1187,7 @@ unsigned short* xb_by_transform(fcn8s_model* m, const char* layer, int N, int H,
     if (!p) {
         const size_t bytes = (size_t)N * (H + 2) * (W + 2) * Cin * sizeof(unsigned short);
         if (hipMalloc((void**)&p, bytes) != hipSuccess) { p = nullptr; (void)hipGetLastError(); m->xbf16.erase(layer); return nullptr; }
+        ++m->ws_allocs;
         hipMemsetAsync(p, 0, bytes, s);
     }
     return p;
@@ -1167,11 +1229,12 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
         m->u_cache.clear();
         for (auto& kv : m->wbf16_cache) if (kv.second) hipFree(kv.second);
         m->wbf16_cache.clear();
+        m->bank_stale.clear(); m->banks_stale = false;
     };
     hipStream_t s = m->stream;
     const int N = m->N, H = m->H, W = m->W, C = m->C;
     bool guard_pending = false;
-    if (m->frozen && !m->u_cache.empty()) {
+    if (m->frozen && !m->u_cache.empty() && !m->banks_stale) {
         // the caller promised constant parameters; a cheap strided fingerprint catches the promise being broken through a side
         // door (a torch optimizer or copy_ over views of ext_params): the cached filter banks are then rebuilt instead of reused.
         // The check does not hold the pass up: the fingerprint is taken first on the stream, the pass is enqueued behind it with the kept
@@ -1190,7 +1253,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
             if (fp != m->frozen_fp) drop_banks();
         }
     }
-    const bool fill_fp = m->frozen && m->u_cache.empty();
+    const bool fill_fp = m->frozen && (m->u_cache.empty() || m->banks_stale);       // (banks_stale: kept storage, contents to be rebuilt)
     if (!m->frozen || fill_fp) prepare_forward_weights(m);        // frozen and the kept banks still valid: so are the padded / phase-packed kernels
     m->fwd_train = train;
     // bf16_train, evaluation / prediction (round 6): the pass takes the TRAINING pass's data flow -- every layer's input as a padded bf16 copy written by its
@@ -1199,7 +1262,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
     // its logits are the training pass's bit for bit (keep_prob 1).  What it keeps for a backward pass that never comes (routing bytes) costs one byte per window.
     const bool cp = train || (bf16_train_mode(m) && m->bf16_infer_copies);
     m->rbits_ok.clear(); m->y_unwritten.clear(); m->in_bf16_only.clear(); m->fwd_v_layer.clear(); m->xg16_filled.clear();
-    { ProfScope ps(m, "preprocess", 0, (double)N * H * W * (16 + (dtype ? 12 : 3))); launch_preprocess(img_dev, dtype, A(m, "x0"), (long long)N * H * W, s); }
+    if (!m->x0_ready) { ProfScope ps(m, "preprocess", 0, (double)N * H * W * (16 + (dtype ? 12 : 3))); launch_preprocess(img_dev, dtype, A(m, "x0"), (long long)N * H * W, s); }
     const float* x = A(m, "x0");
     int h = H, w = W, cin = 4;
     for (int b = 0; b < 5; ++b) {
@@ -1402,6 +1465,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
         launch_fingerprint(m->d_params, (long long)m->total, m->d_fp, s);
         hipMemcpyAsync(&m->frozen_fp, m->d_fp, sizeof m->frozen_fp, hipMemcpyDeviceToHost, s);
         hipStreamSynchronize(s);
+        m->banks_stale = false;
     }
     if (guard_pending) {
         hipEventSynchronize(m->fp_event);
@@ -1803,6 +1867,7 @@ int fcn8s_destroy(fcn8s_model* m)
     }
     if (m->copy_stream) hipStreamDestroy(m->copy_stream);
     if (m->arena) hipFree(m->arena);
+    if (m->tta_buf) hipFree(m->tta_buf);
     delete m;
     // the model is gone either way; a communicator that had failed is reported once, with its reason in fcn8s_last_error(NULL)
     if (rc_comm) { g_last_error = comm_text; return rc_comm; }
@@ -1819,6 +1884,7 @@ static void drop_u_cache(fcn8s_model* m)
     m->u_cache.clear();
     for (auto& kv : m->wbf16_cache) if (kv.second) hipFree(kv.second);
     m->wbf16_cache.clear();
+    m->bank_stale.clear(); m->banks_stale = false;
 }
 int fcn8s_freeze_params(fcn8s_model* m, int frozen)
 {
@@ -1910,6 +1976,7 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
         }
         return fail(nullptr, FCN8S_ERR_NOT_FOUND, "fcn8s_set_option: unknown op-context option '" + k + "' (model options need a model)");
     }
+    if (k == "workspace_allocations" || k == "frozen") return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_option: '" + k + "' is read-only (the frozen state is set with fcn8s_freeze_params)");
     if (k == "comm_timeout_ms") {
         if (value < 1) return fail(m, FCN8S_ERR_BAD_ARG, "comm_timeout_ms must be >= 1");
         std::lock_guard<std::mutex> lk(m->comm_mu); m->comm_timeout_ms = value; return FCN8S_OK;
@@ -1940,6 +2007,7 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
     for (auto& kv : m->wbf16_cache) if (kv.second) hipFree(kv.second);
     m->wbf16_cache.clear();
     m->u_cache.clear();
+    m->bank_stale.clear(); m->banks_stale = false;
     for (auto& kv : m->u_train) if (kv.second) hipFree(kv.second);
     m->u_train.clear();
     return FCN8S_OK;
@@ -1957,6 +2025,8 @@ int fcn8s_get_option(const fcn8s_model* m, const char* key, int64_t* value)
         return FCN8S_ERR_NOT_FOUND;
     }
     if (k == "comm_timeout_ms") { *value = m->comm_timeout_ms; return FCN8S_OK; }
+    if (k == "workspace_allocations") { *value = m->ws_allocs; return FCN8S_OK; }
+    if (k == "frozen") { *value = m->frozen ? 1 : 0; return FCN8S_OK; }
     const int* slot = model_option(const_cast<fcn8s_model*>(m), k);
     if (!slot) return FCN8S_ERR_NOT_FOUND;
     *value = *slot;
@@ -2527,6 +2597,91 @@ int fcn8s_predict(fcn8s_model* m, const void* images, int dtype, int N, int H, i
     return FCN8S_OK;
 }
 
+// ---- multi-scale / flip inference (test-time augmentation) ----------------------------------------------------------------------
+// P = nscales x (1 + flip) passes, in the order (scale 0, scale 0 mirrored, scale 1, ...).  Pass k: the image resized to Hs x Ws (cv2 INTER_LINEAR,
+// bit-exact with resample_u8), mirrored, preprocessed and zero padded to Hp x Wp = 32 ceil(Hs / 32) x 32 ceil(Ws / 32) by tta_input straight into x0;
+// the predict forward; tta_accumulate reads the logits over [0,Hs)x[0,Ws) through the PixMap, un-mirrors, resizes them to H x W (half-pixel
+// bilinear), softmaxes and sums in pass order; the last pass writes the mean (or its argmax).  All passes share one arena sized for the largest,
+// and the call runs with frozen parameters: each transformed filter bank is built once.  A model that was not frozen keeps the banks' storage
+// after the call with its contents marked stale (bank_stale): the next call rebuilds each bank once into it, allocating nothing.
+int fcn8s_predict_tta(fcn8s_model* m, const void* images, int dtype, int N, int H, int W, const float* scales, int nscales, int flip,
+                      int argmax, void* out, int where)
+{
+    if (!m || !images || !out || !scales) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_tta: null argument");
+    if (dtype != FCN8S_IMG_U8 && dtype != FCN8S_IMG_F32) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_tta: unknown image dtype");
+    if (where != FCN8S_HOST && where != FCN8S_DEVICE) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_tta: `where` must be FCN8S_HOST or FCN8S_DEVICE");
+    if (nscales < 1 || nscales > 8) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_tta: between 1 and 8 scales");
+    if (N <= 0 || H <= 0 || W <= 0) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_tta: N, H and W must be positive");
+    int hs[8], ws[8], hp[8], wp[8];
+    for (int k = 0; k < nscales; ++k) {
+        const float sc = scales[k];
+        if (!std::isfinite(sc) || !(sc > 0.f) || sc > 4.f) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_tta: every scale must lie in (0, 4]");
+        hs[k] = std::max(1, (int)std::floor((double)H * (double)sc + 0.5));
+        ws[k] = std::max(1, (int)std::floor((double)W * (double)sc + 0.5));
+        hp[k] = (hs[k] + 31) / 32 * 32; wp[k] = (ws[k] + 31) / 32 * 32;
+        if (dtype == FCN8S_IMG_F32 && (hs[k] != H || ws[k] != W))
+            return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_tta: float32 images are taken only when no pass resizes them (every scale maps H x W to itself)");
+        if ((double)N * hp[k] * wp[k] > (double)(1LL << 31)) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_tta: a pass's padded shape is too large to plan");
+    }
+    flip = flip ? 1 : 0;
+    // the identity case is fcn8s_predict itself (bit for bit)
+    if (nscales == 1 && !flip && hs[0] == H && ws[0] == W && hp[0] == H && wp[0] == W) return fcn8s_predict(m, images, dtype, N, H, W, argmax, out, where);
+    const int P = nscales * (1 + flip), C = m->C;
+    size_t need = 0;
+    for (int k = 0; k < nscales; ++k) { WsPlan pl; plan_workspace(m, N, hp[k], wp[k], pl); need = std::max(need, pl.bytes); }
+    // scratch: the staged images (host input), the accumulator (P > 1), the staged output (host output)
+    const size_t npix = (size_t)N * H * W, eb = dtype == FCN8S_IMG_U8 ? 1 : 4;
+    const size_t b_img = where == FCN8S_HOST ? align_up(npix * 3 * eb, 256) : 0, b_acc = P > 1 ? align_up(npix * C * sizeof(float), 256) : 0;
+    const size_t b_out = where == FCN8S_HOST ? align_up(argmax ? npix * sizeof(long long) : npix * C * sizeof(float), 256) : 0;
+    if (m->tta_bytes < b_img + b_acc + b_out) {
+        if (m->tta_buf) { HIPCHK(m, hipStreamSynchronize(m->stream)); hipFree(m->tta_buf); m->tta_buf = nullptr; m->tta_bytes = 0; }
+        HIPCHK(m, hipMalloc((void**)&m->tta_buf, b_img + b_acc + b_out));
+        m->tta_bytes = b_img + b_acc + b_out; ++m->ws_allocs;
+    }
+    hipStream_t s = m->stream;
+    const void* img = images;
+    if (where == FCN8S_HOST) { HIPCHK(m, hipMemcpyAsync(m->tta_buf, images, npix * 3 * eb, hipMemcpyHostToDevice, s)); img = m->tta_buf; }
+    float* acc = b_acc ? (float*)(m->tta_buf + b_img) : nullptr;
+    void* dout = where == FCN8S_HOST ? (void*)(m->tta_buf + b_img + b_acc) : out;
+    float* sm = argmax ? nullptr : (float*)dout;
+    long long* am = argmax ? (long long*)dout : nullptr;
+    const bool was_frozen = m->frozen;
+    m->frozen = true;                     // the parameters are constant for the call: every pass after the first reuses the transformed banks
+    take_deferred_error(nullptr);
+    int rc = FCN8S_OK;
+    for (int pi = 0; pi < P && !rc; ++pi) {
+        const int k = pi / (1 + flip), f = flip ? pi % 2 : 0;
+        rc = ensure_workspace_at_least(m, N, hp[k], wp[k], need); if (rc) break;
+        { ProfScope ps(m, "tta_input", 0, (double)npix * 3 * eb + 16.0 * N * hp[k] * wp[k]);
+          launch_tta_input(img, dtype, N, H, W, hs[k], ws[k], hp[k], wp[k], f, A(m, "x0"), s); }
+        m->x0_ready = true;
+        rc = forward(m, img, dtype, 1.0f, false);
+        m->x0_ready = false;
+        if (rc) { take_deferred_error(nullptr); break; }
+        rc = deferred_rc(m); if (rc) break;
+        const PixMap pm = LGM(m) ? *LGM(m) : PixMap{0, hp[k], wp[k], 0, 0, 0};
+        const bool first = pi == 0, last = pi == P - 1;
+        // algorithmic bytes: the valid logits once, the accumulator read (not first) / written (not last), the result (last)
+        const double by = 4.0 * N * hs[k] * ws[k] * C + (first ? 0.0 : 4.0 * npix * C) + (last ? 0.0 : 4.0 * npix * C) + (last ? (argmax ? 8.0 * npix : 4.0 * npix * C) : 0.0);
+        { ProfScope ps(m, "tta_accumulate", 0, by);
+          launch_tta_accumulate(LG(m), pm, N, hs[k], ws[k], f, C, H, W, acc, first, last, P, sm, am, s); }
+    }
+    m->x0_ready = false;
+    if (!was_frozen) {                    // leave unfrozen: the banks stay allocated for the next call, their contents are stale from now on
+        for (auto& kv : m->u_cache) m->bank_stale.insert("u:" + kv.first);
+        for (auto& kv : m->wbf16_cache) m->bank_stale.insert("w:" + kv.first);
+        m->banks_stale = true;
+        m->frozen = false;
+    }
+    if (rc) return rc;
+    HIPCHK(m, hipGetLastError());
+    if (where == FCN8S_HOST) {
+        HIPCHK(m, hipMemcpyAsync(out, dout, argmax ? npix * sizeof(long long) : npix * C * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHK(m, hipStreamSynchronize(s));
+    }
+    return FCN8S_OK;
+}
+
 // ---- asynchronous host boundary ------------------------------------------------------------------
 int fcn8s_stage_inputs(fcn8s_model* m, int slot, const void* images, int dtype, const uint8_t* label_ids, int N, int H, int W,
                        void** images_dev, uint8_t** labels_dev)
@@ -2768,6 +2923,24 @@ int fcn8s_onehot_to_ids(void* stream, const void* onehot, int elem_bytes, int64_
 
 int fcn8s_op_preprocess(void* stream, const void* images, int dtype, float* out4, int64_t npix)
 { launch_preprocess(images, dtype, out4, npix, (hipStream_t)stream); OPCHK(); return FCN8S_OK; }
+
+int fcn8s_op_tta_input(void* stream, const uint8_t* images, int N, int H, int W, int Hs, int Ws, int Hp, int Wp, int flip, float* out4)
+{
+    if (!images || !out4 || N <= 0 || H <= 0 || W <= 0 || Hs <= 0 || Ws <= 0 || Hp < Hs || Wp < Ws)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "tta_input: bad argument");
+    launch_tta_input(images, FCN8S_IMG_U8, N, H, W, Hs, Ws, Hp, Wp, flip ? 1 : 0, out4, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_tta_accumulate(void* stream, const float* logits, int N, int Hp, int Wp, int Hs, int Ws, int flip, int C, int H, int W, float* acc,
+                            int first, int last, int npasses, float* softmax_out, int64_t* argmax_out)
+{
+    if (!logits || N <= 0 || Hs <= 0 || Ws <= 0 || Hp < Hs || Wp < Ws || C <= 0 || H <= 0 || W <= 0 || npasses < 1 || (!acc && !(first && last))
+        || (last && !softmax_out && !argmax_out) || ((uintptr_t)logits | (uintptr_t)acc | (uintptr_t)softmax_out) % 16)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "tta_accumulate: bad argument");
+    const PixMap pm{0, Hp, Wp, 0, 0, 0};
+    launch_tta_accumulate(logits, pm, N, Hs, Ws, flip ? 1 : 0, C, H, W, acc, first ? 1 : 0, last ? 1 : 0, npasses, softmax_out, (long long*)argmax_out, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
 
 int fcn8s_op_augment_u8(void* stream, const uint8_t* images, const uint8_t* labels, uint8_t* out_images, uint8_t* out_labels,
                         const int32_t* params, const uint8_t* vlut, int N, int H, int W, int Ho, int Wo, int void_id)

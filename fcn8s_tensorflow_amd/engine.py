@@ -20,6 +20,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib as L
+from . import tta
 from .dp import BucketReducer
 
 
@@ -670,6 +671,29 @@ class Engine:
             return out if argmax or self.logical_classes == self.num_classes else out[..., :self.logical_classes].contiguous()
         out = np.empty((N, H, W), np.int64) if argmax else np.empty((N, H, W, self.num_classes), np.float32)
         L.check(L.lib.fcn8s_predict(self.h, pi, dt, N, H, W, int(bool(argmax)), out.ctypes.data_as(C.c_void_p), where), self.h)
+        return out if argmax or self.logical_classes == self.num_classes else np.ascontiguousarray(out[..., :self.logical_classes])
+
+    def predict_tta(self, images, scales=(1.0,), flip=False, argmax=True):
+        """Multi-scale / left-right-flip prediction on images of any size (fcn8s_predict_tta; the pass rule is in tta.py): the mean over
+        the passes of the softmax resized to the input size, or its argmax.  Host or device inputs and outputs, as `predict`."""
+        sc = tta.validate(scales, flip)
+        self._sync_stream()
+        ka_i, pi, dt, where, nhw = self._images(images)
+        N, H, W = (int(x) for x in nhw)
+        if dt == L.IMG_F32 and tta.resizes(H, W, sc):
+            raise ValueError("float32 images are taken only when no pass resizes them; pass uint8 images to predict at scales %s" % (sc,))
+        arr = (C.c_float * len(sc))(*sc)
+        torch = self.torch
+        if where == L.DEVICE:
+            out = torch.empty((N, H, W), dtype=torch.int64, device=self.device) if argmax else \
+                torch.empty((N, H, W, self.num_classes), dtype=torch.float32, device=self.device)
+            L.check(L.lib.fcn8s_predict_tta(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), int(bool(argmax)),
+                                            C.c_void_p(out.data_ptr()), where), self.h)
+            self._release(ka_i)
+            return out if argmax or self.logical_classes == self.num_classes else out[..., :self.logical_classes].contiguous()
+        out = np.empty((N, H, W), np.int64) if argmax else np.empty((N, H, W, self.num_classes), np.float32)
+        L.check(L.lib.fcn8s_predict_tta(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), int(bool(argmax)),
+                                        out.ctypes.data_as(C.c_void_p), where), self.h)
         return out if argmax or self.logical_classes == self.num_classes else np.ascontiguousarray(out[..., :self.logical_classes])
 
     # ---- introspection (tests, bench) -----------------------------------------------------------

@@ -332,12 +332,17 @@ class FCN8s:
         self._evaluate(data_generator, metrics, num_batches, l2_regularization, description='Running evaluation')
         self.eval_dataset = dataset
 
-    def predict(self, images, argmax=True):
+    def predict(self, images, argmax=True, scales=None, flip=False):
         '''fcn8s_tensorflow.py:743-770.  `images`: array-like of rank 4 (a list of HWC arrays works).
-        Returns int64 class ids (N,H,W) or the float32 softmax (N,H,W,C).'''
+        Returns int64 class ids (N,H,W) or the float32 softmax (N,H,W,C).
+        Not in the reference: `scales` (1 to 8 factors in (0, 4]) and / or `flip` average the softmax over resized and mirrored passes
+        (multi-scale / flip test-time augmentation, see tta.py) and take images of any size; `scales=(1.0,)` alone predicts an image of
+        any size at its own resolution.  Without them, height and width must be multiples of 32, as in the reference.'''
         if isinstance(images, (list, tuple)):
             images = np.asarray(images)
-        return self.engine.predict(images, argmax=argmax)
+        if scales is None and not flip:
+            return self.engine.predict(images, argmax=argmax)
+        return self.engine.predict_tta(images, scales=(1.0,) if scales is None else scales, flip=flip, argmax=argmax)
 
     def predict_and_save(self,
                          results_dir,
@@ -347,8 +352,11 @@ class FCN8s:
                          image_file_extension='png',
                          include_unprocessed_image=False,
                          arrangement='vertical',
-                         overwrite_existing=True):
-        '''fcn8s_tensorflow.py:772-855 (PIL instead of scipy.misc / helpers.visualization_utils).'''
+                         overwrite_existing=True,
+                         scales=None,
+                         flip=False):
+        '''fcn8s_tensorflow.py:772-855 (PIL instead of scipy.misc / helpers.visualization_utils).  `scales` / `flip`: as in `predict`
+        (images of any size; `resize` is then optional).'''
         from PIL import Image
 
         if overwrite_existing and os.path.exists(results_dir):
@@ -366,16 +374,18 @@ class FCN8s:
         self.engine.freeze(True)            # constant weights for the whole directory
         try:
             for i in tr:
-                self._segment_file(image_paths[i], results_dir, color_map, resize, include_unprocessed_image, arrangement)
+                self._segment_file(image_paths[i], results_dir, color_map, resize, include_unprocessed_image, arrangement, scales, flip)
         finally:
             self.engine.freeze(False)
 
-    def predict_and_export_label_ids(self, results_dir, images_dir, resize=False, image_file_extension='png', overwrite_existing=True):
+    def predict_and_export_label_ids(self, results_dir, images_dir, resize=False, image_file_extension='png', overwrite_existing=True,
+                                     scales=None, flip=False):
         '''Not in the reference: runs every `*.png` below `images_dir` (sub-directories = cities, as in leftImg8bit/val) through the
         model and writes the argmax as single-channel label-id PNGs under the same file names into `results_dir` -- the input of the
         official scorer (cityscapesscripts/evaluation/evalPixelLevelSemanticLabeling.py:72-106, 553-555; cityscapes_eval.evaluate_directory
         here).  Predictions are train ids 0..19 (0 = void) mapped through labels.py:188-192; `resize=(h, w)` feeds the network a
-        resized image and writes the prediction back at the file's own size (nearest neighbour).'''
+        resized image and writes the prediction back at the file's own size (nearest neighbour).  `scales` / `flip`: as in `predict`
+        (multi-scale / flip averaging on images of any size; `resize` is then optional).'''
         from PIL import Image
         from . import cityscapes_eval as ce
         if self.num_classes != 20:
@@ -393,7 +403,7 @@ class FCN8s:
                 size = pil.size
                 if resize and not np.array_equal((pil.height, pil.width), resize):
                     pil = pil.resize((resize[1], resize[0]), Image.BILINEAR)
-                pred = np.asarray(self.predict([np.asarray(pil)], argmax=True))[0]
+                pred = np.asarray(self.predict([np.asarray(pil)], argmax=True, scales=scales, flip=flip))[0]
                 ids = Image.fromarray(ce.TRAINIDS_TO_IDS_ARRAY[pred])
                 if ids.size != size:
                     ids = ids.resize(size, Image.NEAREST)
@@ -402,7 +412,7 @@ class FCN8s:
             self.engine.freeze(False)
         return len(paths)
 
-    def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement):
+    def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement, scales=None, flip=False):
         '''Loop body of predict_and_save (fcn8s_tensorflow.py:829-855).'''
         from PIL import Image
         pil = Image.open(filepath).convert('RGB')
@@ -411,7 +421,7 @@ class FCN8s:
         image = np.asarray(pil)
         img_height, img_width, img_ch = image.shape
 
-        prediction = self.predict([image], argmax=False)
+        prediction = self.predict([image], argmax=False, scales=scales, flip=flip)
         processed = print_segmentation_onto_image(image=image, prediction=prediction, color_map=color_map)
 
         if include_unprocessed_image:

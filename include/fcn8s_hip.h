@@ -220,6 +220,22 @@ int fcn8s_metrics_set_raw(fcn8s_model* m, const int64_t* confusion, double loss_
  * argmax != 0: out = int64 [N,H,W]; else out = float32 softmax [N,H,W,C].        */
 int fcn8s_predict(fcn8s_model* m, const void* images, int image_dtype, int N, int H, int W,
                   int argmax, void* out, int where);
+/* ---- multi-scale / left-right-flip prediction (test-time augmentation) on images of any size ---------------------------------------- *
+ * images: N same-size images [N,H,W,3], H, W >= 1; scales: nscales (1..8) factors in (0, 4]; P = nscales * (1 + flip) passes: for each
+ * scale in order one pass, then (flip) its mirror image.  Pass of scale s: Hs = max(1, floor(H s + 0.5)), Ws likewise; the image is resized
+ * to Hs x Ws (cv2.resize INTER_LINEAR on uint8, bit-exact with fcn8s_op_resample_u8), mirrored (flipped pass), preprocessed and padded bottom /
+ * right to Hp x Wp = 32 ceil(Hs / 32) x 32 ceil(Ws / 32) with zeros in the preprocessed domain (the VGG mean colour); the predict forward of
+ * the current precision mode runs on it; its logits over [0,Hs)x[0,Ws), un-mirrored, are resized to H x W bilinearly with half-pixel
+ * centres (F.interpolate(mode='bilinear', align_corners=False)) and softmaxed.  out = the mean of the P softmaxes (summed in pass order in
+ * fp32): float32 [N,H,W,C], or (argmax != 0) its int64 argmax [N,H,W] (lowest index on ties).  scales = {1}, no flip, H and W multiples of
+ * 32: exactly fcn8s_predict.  float32 images are taken only when no pass resizes.  All passes share one workspace sized for the largest;
+ * a repeated identical call allocates and frees nothing (statistic "workspace_allocations").  The parameters are treated as frozen for the
+ * call (each transformed filter bank is built once); the model's frozen state is unchanged afterwards.  A model that is not frozen keeps
+ * the banks' storage between calls with their contents marked stale: every call rebuilds them once, into that storage.
+ * FCN8S_ERR_BAD_ARG: nscales outside 1..8, a scale outside (0, 4] or not finite, float32 images with a resizing pass;
+ * FCN8S_ERR_SHAPE: a pass's padded shape cannot be planned. */
+int fcn8s_predict_tta(fcn8s_model* m, const void* images, int image_dtype, int N, int H, int W, const float* scales, int nscales, int flip,
+                      int argmax, void* out, int where);
 
 /* ---- state that must round-trip: global_step :246,:526; Adam slots ---------- */
 int64_t fcn8s_global_step(const fcn8s_model* m);
@@ -285,6 +301,9 @@ int fcn8s_get_precision(const fcn8s_model* m);
  *     "keep_output_gradients" 0 (tests) every weighted layer's fp32 output gradient dY is copied as the backward pass hands it to the layer's weight gradient and can be read with
  *                              fcn8s_get_activation(m, "dy:<layer>", ...) (conv1_1 .. conv5_3, fc6, fc7); FCN8S_ERR_STATE for a layer whose gradient travelled in another form
  *                              (these ten pick a kernel per launch and drop nothing)
+ *     "workspace_allocations"  (read-only statistic; setting it is FCN8S_ERR_BAD_ARG) device allocations the model has made for its workspace,
+ *                              the scratch of fcn8s_predict_tta, its bf16 copies and its cached (frozen / TTA) filter banks
+ *     "frozen"                 (read-only) 1 while fcn8s_freeze_params(m, 1) holds
  *     "comm_timeout_ms" 600000 the communicator's watchdog (see fcn8s_comm_init): a collective older than this is given up, the communicator aborted
  *   op-context options (m == NULL): the arithmetic of the op-level entry points below, which have no model.  The value belongs to the
  *   CALLING THREAD (thread-local) and is read by that thread's later fcn8s_op_* calls only; no model ever reads it, so two models -- or a
@@ -329,6 +348,14 @@ int fcn8s_profile_get(fcn8s_model* m, int group, const char** name, double* tota
 /* ---- single ops on DEVICE pointers (unit parity tests; same kernels the model
  * uses).  `stream` may be NULL (default stream).                                 */
 int fcn8s_op_preprocess(void* stream, const void* images, int image_dtype, float* out4, int64_t npix);
+/* the two kernels of fcn8s_predict_tta on DEVICE pointers.  tta_input: uint8 [N,H,W,3] -> the forward's input [N,Hp,Wp,4] (resize to
+ * Hs x Ws as fcn8s_op_resample_u8, mirror if flip, fcn8s_op_preprocess's arithmetic, zeros outside [0,Hs)x[0,Ws)).  tta_accumulate: plain
+ * NHWC logits [N,Hp,Wp,C] over [0,Hs)x[0,Ws), un-mirrored if flip, bilinear (half-pixel) to H x W, softmax; first: acc = p, else acc += p;
+ * last: (acc + p) / npasses into softmax_out [N,H,W,C] and / or argmax_out [N,H,W] (acc is then not written; it may be NULL if first and
+ * last).  16-byte aligned float pointers. */
+int fcn8s_op_tta_input(void* stream, const uint8_t* images, int N, int H, int W, int Hs, int Ws, int Hp, int Wp, int flip, float* out4);
+int fcn8s_op_tta_accumulate(void* stream, const float* logits, int N, int Hp, int Wp, int Hs, int Ws, int flip, int C, int H, int W, float* acc,
+                            int first, int last, int npasses, float* softmax_out, int64_t* argmax_out);
 /* GPU-side augmentation of a uint8 batch on DEVICE pointers (the crop / canvas placement, horizontal flip and
  * brightness steps of data_generator/batch_generator.py:293-341, :469-486, which do not resample).  params: int32[4] per image =
  * {y offset, x offset, flip (0|1), brightness (0|1)}; out[n,y,x] = in[n, y+oy, (flip ? Wo-1-x : x) + ox], zero / void_id outside the
