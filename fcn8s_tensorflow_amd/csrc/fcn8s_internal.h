@@ -54,6 +54,7 @@ struct IgemmArgs {
     int batched; long long x_batch_stride, y_batch_stride;   // gridDim.z independent GEMMs (Winograd positions)
     int m_fastest;                                           // tile order, set by the launcher (see igemm.hip)
     int bt, ldw;                                             // bt: the B operand is stored transposed, w[z][n][k] with row stride ldw (plain batched GEMMs on the LDS-DMA kernel only)
+    int fixed_tile;                                          // 1: 128-row tiles (128 columns, 64 if Cout % 128), never split-K -- the choice depends on the caller's per-image geometry, not on M
     int split;                                               // 3: the LDS-DMA kernels take their products as six bf16 MFMAs of the operands split in three (FCN8S_PREC_F32X3); 2: three MFMAs of two pieces (FCN8S_PREC_F32X2); 0: f32 MFMA
 };
 void launch_igemm(const IgemmArgs& a, int phases, hipStream_t s);
@@ -256,6 +257,15 @@ void launch_wino_dgrad_output(const float* dv, const float* addend, const float*
                               int N, int H, int W, int C, hipStream_t s);
 bool launch_wino_out_in(const float* m, const float* bias, float* v, unsigned* rbits_out, int N, int H, int W, int C, hipStream_t s, bool always = false);   // conv L's output transform + conv L+1's input transform in one kernel (Y never written); false = shape not covered
 void launch_wino_dfilter(int tile, const float* du, float* dw, int Cin, int Cout, int KS, hipStream_t s);        // du[P][nsub*Cin][Cout] -> dw[KS*KS][Cin][Cout]
+// fc6 through 14x14 real-DFT tiles (fft_fc6.hip): 292 real GEMM planes, T = N * ceil(H/8) * ceil(W/8) tiles, slabs wino_slab(T, C) apart
+int fft_fc6_planes();
+long long fft_fc6_tiles(int N, int H, int W);
+void launch_fft_fc6_filter(const float* w, float* uf, int Cin, int Cout, hipStream_t s);                 // w[7][7][Cin][Cout] -> uf[292][Cin][Cout]
+void launch_fft_fc6_input(const float* x, float* xf, int N, int H, int W, int C, hipStream_t s);          // x[N,H,W,C] -> xf[292][T][C]
+void launch_fft_fc6_output(const float* yf, const float* bias, float* y, int N, int H, int W, int C, int relu, int dropout, float keep,
+                           unsigned long long seed, unsigned int stream_id, hipStream_t s);                 // yf[292][T][C] -> y[N,H,W,C] + epilogue
+void launch_fft_fc6_dout(const float* dz, float* dyf, int N, int H, int W, int C, hipStream_t s);         // transpose of the output transform
+void launch_fft_fc6_din(const float* dxf, float* patches, float* dx, int N, int H, int W, int C, hipStream_t s);   // transpose of the input transform (patches: T*196*C floats of scratch)
 // params: int[4] per image = {y offset, x offset, flip, brightness on/off}; vlut: [N][256] new V per old V (may be nullptr)
 void launch_augment_u8(const unsigned char* img, const unsigned char* lab, unsigned char* oimg, unsigned char* olab, const int* params,
                        const unsigned char* vlut, int N, int H, int W, int Ho, int Wo, int void_id, hipStream_t s);

@@ -1009,7 +1009,7 @@ static void launch_igemm_cfg(const IgemmArgs& a0, int phases, hipStream_t s)
     constexpr int splitk_min_kt = 64;        // fewest K-tiles a few-block launch must have before its reduction is split (32 measured slower at batch 1)
     const unsigned nblocks = grid.x * (unsigned)phases, nkt_all = (unsigned)(a.Ktot / BKF);
     // (deterministic mode: no split -- the partial sums would meet in atomics)
-    if (linear && !t_deterministic && ((grid.x < 512 && nkt_all >= 512) || (nblocks < 2048 && nkt_all >= (unsigned)splitk_min_kt))) {
+    if (linear && !t_deterministic && !a.fixed_tile && ((grid.x < 512 && nkt_all >= 512) || (nblocks < 2048 && nkt_all >= (unsigned)splitk_min_kt))) {
         unsigned ks = nkt_all >= 512 && grid.x < 512 ? 1024 / grid.x : 4096 / nblocks;
         if (ks > 8) ks = 8;
         if (ks > nkt_all / 16) ks = nkt_all / 16;
@@ -1087,6 +1087,8 @@ void launch_igemm(const IgemmArgs& a, int phases, hipStream_t s)
         const double tail = rem == 0 ? 0.0 : (rem == 1 ? 2.0 : (rem == 2 ? 2.4 : 3.0));
         return ((double)(n / bpc) * bpc + tail) * bm * bn / eff;
     };
+    if (a.fixed_tile && a.Cout % 128 == 0) { launch_igemm_cfg<128, 128, 2, 2>(a, phases, s); return; }
+    if (a.fixed_tile && a.Cout % 64 == 0)  { launch_igemm_cfg<128, 64, 2, 2>(a, phases, s); return; }
     if (a.Cout <= 32)      launch_igemm_cfg<128, 32, 4, 1>(a, phases, s);
     else if (a.Cout <= 64) {
         if (cost(128, 64, 4, 1.0) <= cost(64, 64, 4, 0.9)) launch_igemm_cfg<128, 64, 2, 2>(a, phases, s);

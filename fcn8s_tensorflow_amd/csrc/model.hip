@@ -112,6 +112,8 @@ struct fcn8s_model {
     int wino_min_cin = 64;                                              // 3x3 layers with Cin >= this use Winograd; 0 = never
     int wino_tile = 6;                                                    // largest 3x3 output tile: F(6x6,3x3) / F(4x4,3x3) per layer by cost, F(2x2,3x3) fallback
     int wino_fc6 = 1;                                                     // fc6 7x7 as a 2x2 grid of 4x4 sub-filters in the Winograd domain
+    int fc6_fft = 1;                                                      // ... and in the fp32 training step: forward + data gradient through 14x14 real-DFT tiles (fft_fc6.hip)
+    std::string fft6_ready;                                               // the layer whose FFT bank (u_train "<layer>#fft") this forward pass built
     int wino_tile_hires = 0, wino_hires_pixels = 0;                       // != 0: 3x3 layers on maps of at least wino_hires_pixels pixels (per image) use at most this tile
     int wino_force_tile = 0;                                              // != 0: every eligible 3x3 layer uses exactly this tile (op-level parity entry point)
     int precision = FCN8S_PREC_F32;                                       // FCN8S_PREC_BF16_FC: forward fc6 / fc7 on the bf16 MFMA
@@ -399,6 +401,75 @@ struct WinoEpi { const float* bias = nullptr; const float* addend = nullptr; con
                  unsigned* rbits_out = nullptr; const unsigned* rbits_in = nullptr; int skip_y = 0;
                  unsigned* in_rbits_out = nullptr;       // ReLU bit record of the INPUT, written by the input transform
                  float* next_v = nullptr; bool* fused_out = nullptr; };     // output transform fused with the next conv's input transform (winograd.hip: wino_out_in_kernel)
+// fc6 through 14x14 real-DFT tiles (fft_fc6.hip) in the fp32 training step of an unfrozen model.  Frozen inference keeps its cached
+// F(4x4,4x4) bank (at batch 1 the 2.45 GB DFT bank would cost more than it saves), the other precisions keep their own fc6 paths, and the
+// weight gradient stays in F(4x4,4x4) (V of pool5 is written here for it).  ci / co: channels of the FORWARD conv.
+// Only on maps where the DFT tiles multiply less than the alternative (per image: 292 planes per 8x8 tile against F(4x4,4x4)'s 196 per 4x4 tile,
+// or 49 per output for the direct form): at the training shape (32x16) 2336 against 6272; a 2x2 map (64x64 images) keeps F(4x4,4x4), 196 against 292.
+static bool fft6_cheaper(const fcn8s_model* m, int H, int W)
+{
+    const long long fft = 292LL * ((H + 7) / 8) * ((W + 7) / 8);
+    const long long other = wino_tile_for(m, H, W, 7) == 4 ? 196LL * (H / 4) * (W / 4) : 49LL * H * W;
+    return fft < other;
+}
+static bool fft6_shape_ok(const fcn8s_model* m, int ci, int co) { return m->wino_fc6 && m->fc6_fft && m->fc6k == 7 && ci % 16 == 0 && co % 128 == 0; }
+static bool fft6_on(const fcn8s_model* m, int N, int H, int W, int ci, int co)
+{
+    if (!m || !fft6_shape_ok(m, ci, co) || !fft6_cheaper(m, H, W) || m->precision != FCN8S_PREC_F32 || m->frozen || !m->d_wino_v || !m->d_wino_m) return false;
+    const long long T = fft_fc6_tiles(N, H, W);
+    auto v = m->acts.find("wino_v"), mm = m->acts.find("wino_m");
+    return v != m->acts.end() && mm != m->acts.end() && v->second.n >= (size_t)fft_fc6_planes() * (size_t)wino_slab(T, std::min(ci, co)) &&
+           mm->second.n >= std::max((size_t)fft_fc6_planes() * (size_t)wino_slab(T, std::max(ci, co)), (size_t)T * 196 * std::min(ci, co));
+}
+// the plane GEMMs: [T x K] x [K x Nc] per plane, 128-row tiles and no split-K whatever the batch (a DP shard computes the big batch's bits)
+static IgemmArgs fft6_gemm(const float* x, const float* w, float* y, long long T, int K, int Nc)
+{
+    IgemmArgs a{}; a.split = 0; a.fixed_tile = 1;
+    a.x = x; a.w = w; a.y = y;
+    a.N = 1; a.Ma = (int)T; a.Mb = 1; a.M = T;
+    a.Hi = (int)T; a.Wi = 1; a.Cin = K; a.ldx = K;
+    a.KW = 1; a.in_scale = 1; a.tap_step = 1; a.tap_off = 0; a.Ktot = K;
+    a.Ho = (int)T; a.Wo = 1; a.Cout = Nc; a.ldy = Nc;
+    a.out_scale = 1; a.phases_x = 1; a.w_phase_stride = (long long)K * Nc;
+    a.alpha = 1.f; a.mask_scale = 1.f;
+    a.batched = 1; a.x_batch_stride = wino_slab(T, K); a.y_batch_stride = wino_slab(T, Nc);
+    return a;
+}
+// forward: Uf (kept for the data gradient), Xf, the 292 plane GEMMs, the output transform with fc6's epilogue.  false: not taken (no bank memory)
+static bool conv_fft6_fwd(fcn8s_model* m, const char* layer, const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout,
+                          const float* bias, int relu, int dropout, float keep, unsigned int stream_id, hipStream_t s)
+{
+    const int P = fft_fc6_planes();
+    const long long T = fft_fc6_tiles(N, H, W);
+    float*& uf = m->u_train[std::string(layer) + "#fft"];
+    if (!uf && hipMalloc((void**)&uf, (size_t)P * Cin * Cout * sizeof(float)) != hipSuccess) { uf = nullptr; (void)hipGetLastError(); return false; }
+    auto wv = m->acts.find(std::string("wv:") + layer);      // the F(4x4,4x4) weight gradient's V of the input
+    const bool want_v = wv != m->acts.end() && wino_tile_for(m, H, W, 7) == 4;
+    { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((49.0 + P) * Cin * Cout + (double)N * H * W * Cin + (double)P * T * Cin));
+      launch_fft_fc6_filter(w, uf, Cin, Cout, s); launch_fft_fc6_input(x, m->d_wino_v, N, H, W, Cin, s); }
+    if (want_v) { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cin * 4 + 49.0 * wino_tiles(4, N, H, W) * 4 * Cin));
+                  launch_wino_input(4, x, wv->second.p, N, H, W, Cin, 7, s); }
+    const IgemmArgs a = fft6_gemm(m->d_wino_v, uf, m->d_wino_m, T, Cin, Cout);
+    { ProfScope ps(m, "fc6_fft_gemm_fwd", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
+    { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)P * T * Cout + (double)N * H * W * Cout));
+      launch_fft_fc6_output(m->d_wino_m, bias, y, N, H, W, Cout, relu, dropout, keep, m->seed, stream_id, s); }
+    m->fft6_ready = layer;
+    return true;
+}
+// data gradient (Cin = channels of dz, Cout = channels of dx): dYf = output^T(dz), dXf[p] = dYf[p] Uf[p]^T with this step's bank read
+// transposed, dx = input^T(dXf) (patch gradients, then the overlap-add gather)
+static void conv_fft6_dgrad(fcn8s_model* m, const char* layer, const float* dz, const float* uf, float* dx, int N, int H, int W, int Cin, int Cout, hipStream_t s)
+{
+    const int P = fft_fc6_planes();
+    const long long T = fft_fc6_tiles(N, H, W);
+    { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)N * H * W * Cin + (double)P * T * Cin)); launch_fft_fc6_dout(dz, m->d_wino_m, N, H, W, Cin, s); }
+    IgemmArgs a = fft6_gemm(m->d_wino_m, uf, m->d_wino_v, T, Cin, Cout);
+    a.bt = 1; a.ldw = Cin;
+    { ProfScope ps(m, "fc6_fft_gemm_dgrad", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
+    { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)P * T * Cout + 2.0 * 196.0 * T * Cout + (double)N * H * W * Cout));
+      launch_fft_fc6_din(m->d_wino_v, m->d_wino_m, dx, N, H, W, Cout, s); }
+}
+
 // KS = 3, or 7 (3x3 grid of 3x3 sub-filters, GEMM depth 9*Cin -- see winograd.hip)
 void conv_winograd(fcn8s_model* m, int tile, int KS, const char* tag, const float* x, const float* wk, float* y, float* u, float* v, float* mm,
                    int N, int H, int W, int Cin, int Cout, const WinoEpi& e, hipStream_t s, const char* layer, bool v_ready = false)
@@ -505,6 +576,17 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
     }
     if (bf16_train_mode(m) && m->train_mode && layer && e.mask && m->in_bf16_only.count(layer)) {
         defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient could not run on the bf16 kernel and its fp32 mask was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return false;
+    }
+    if (m && K == 7 && layer && !real_cin && e.alpha == 1.f && !e.addend && !e.mask && !e.pool_out && !e.relu_bits_out && !e.relu_bits_in) {
+        if (!e.dgrad && m->fwd_train && fft6_on(m, N, H, W, Cin, Cout) &&
+            conv_fft6_fwd(m, layer, x, w, y, N, H, W, Cin, Cout, e.bias, e.relu, e.dropout, e.keep, e.stream_id, s)) return false;
+        auto kept = m->u_train.find(std::string(layer) + "#fft");
+        if (e.dgrad && !e.bias && !e.relu && !e.dropout && m->fft6_ready == layer && kept != m->u_train.end() && kept->second &&
+            fft6_on(m, N, H, W, Cout, Cin) && bt_gemm_ok(Cin, Cout)) {
+            m->dm_layer.clear(); m->fused_v_layer.clear();
+            conv_fft6_dgrad(m, layer, x, kept->second, y, N, H, W, Cin, Cout, s);
+            return false;
+        }
     }
     const bool wino3 = m && K == 3 && m->wino_min_cin > 0 && Cin >= m->wino_min_cin && m->d_wino_v && wino_tile_for(m, H, W, 3) && !e.dropout;
     const bool wino7 = m && K == 7 && m->wino_fc6 && m->d_wino_v && wino_tile_for(m, H, W, 7) == 4;
@@ -737,7 +819,8 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
                       if (!fused) launch_wino_dout(tile, dz, m->d_wino_m, N, H, W, Cout, s, K);
                   } }
                 // fc6: the non-fused transform above left dM = A dz A^T in d_wino_m; its adjoint data gradient (conv_same) consumes it
-                if (K == 7 && tile == 4 && !fused && Cin % 2 == 0 && bt_gemm_ok(Cout, 4 * Cin) && m->u_train.count(std::string(layer) + "#4")) dm_ready = true;
+                // (not when this step's forward ran through the DFT tiles: a kept F(4x4,4x4) bank would be stale)
+                if (K == 7 && tile == 4 && !fused && Cin % 2 == 0 && bt_gemm_ok(Cout, 4 * Cin) && m->u_train.count(std::string(layer) + "#4") && m->fft6_ready != layer) dm_ready = true;
             }
             m->fused_v_layer = fused ? layer : "";
             m->dm_layer = dm_ready ? layer : "";
@@ -882,7 +965,14 @@ void plan_workspace(fcn8s_model* m, int N, int H, int W, WsPlan& pl)
             vmax = std::max(vmax, slab_floats(h5_, w5_, std::max(m->widths[4], m->widths[5]), 7));
             vmax = std::max(vmax, (size_t)al * al * (size_t)wino_slab(wino_tiles(4, N, h5_, w5_), std::max(m->widths[4], m->widths[5])));
         }
-        if (vmax) { items.push_back({"wino_v", vmax, 0, 0, 0, &m->d_wino_v}); items.push_back({"wino_m", vmax, 0, 0, 0, &m->d_wino_m}); }
+        size_t mmax = vmax;
+        if (fft6_shape_ok(m, m->widths[4], m->widths[5]) && fft6_cheaper(m, h5_, w5_)) {    // fc6 through DFT tiles: Xf / dXf in V, Yf / dYf and the patch gradients in M
+            const long long Tf = fft_fc6_tiles(N, h5_, w5_);
+            const int lo = std::min(m->widths[4], m->widths[5]), hi = std::max(m->widths[4], m->widths[5]);
+            vmax = std::max(vmax, (size_t)fft_fc6_planes() * (size_t)wino_slab(Tf, lo));
+            mmax = std::max(mmax, std::max((size_t)fft_fc6_planes() * (size_t)wino_slab(Tf, hi), (size_t)Tf * 196 * lo));
+        }
+        if (vmax) { items.push_back({"wino_v", vmax, 0, 0, 0, &m->d_wino_v}); items.push_back({"wino_m", mmax, 0, 0, 0, &m->d_wino_m}); }
         if (m->wino_min_cin > 0) {    // the forward pass keeps each Winograd layer's transformed input for the weight gradient
             int cin = 3;
             for (int b = 0, hh = H, ww = W; b < 5; ++b, hh /= 2, ww /= 2)
@@ -1256,6 +1346,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
     const bool fill_fp = m->frozen && (m->u_cache.empty() || m->banks_stale);       // (banks_stale: kept storage, contents to be rebuilt)
     if (!m->frozen || fill_fp) prepare_forward_weights(m);        // frozen and the kept banks still valid: so are the padded / phase-packed kernels
     m->fwd_train = train;
+    m->fft6_ready.clear();
     // bf16_train, evaluation / prediction (round 6): the pass takes the TRAINING pass's data flow -- every layer's input as a padded bf16 copy written by its
     // producer's epilogue (no fp32 conv -> conv tensor, no conversion pass), the flat-position kernel, pools on the bf16 copies -- instead of fp32 tensors converted
     // layer by layer for the tile kernel: 13.3 -> 9.3 ms per 16 x 1024x512 batch, 1.55 -> 1.18 ms per single image (profiles/r06_bf16_infer.txt).  Same products in the same order as the training pass:
@@ -1943,6 +2034,7 @@ static int* model_option(fcn8s_model* m, const std::string& key)
     if (key == "winograd_min_cin") return &m->wino_min_cin;
     if (key == "winograd_tile") return &m->wino_tile;
     if (key == "winograd_fc6") return &m->wino_fc6;
+    if (key == "fc6_fft") return &m->fc6_fft;
     if (key == "tconv_gemm") return &m->tconv_gemm;
     if (key == "fuse_dgrad_dout") return &m->fuse_dgrad_dout;
     if (key == "fuse_out_in") return &m->fuse_out_in;
@@ -2000,7 +2092,7 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
     if (k == "fuse_out_in" && (value < 0 || value > 2)) return fail(m, FCN8S_ERR_BAD_ARG, "fuse_out_in must be 0, 1 or 2");
     if (*slot == (int)value) return FCN8S_OK;
     HIPCHK(m, hipStreamSynchronize(m->stream));
-    *slot = (k == "winograd_fc6" || k == "tconv_gemm") ? (value != 0) : (int)value;
+    *slot = (k == "winograd_fc6" || k == "fc6_fft" || k == "tconv_gemm") ? (value != 0) : (int)value;
     if (m->arena) { hipFree(m->arena); m->arena = nullptr; m->arena_bytes = 0; m->N = m->H = m->W = 0; m->acts.clear(); }
     m->have_forward = m->have_loss = false;
     for (auto& kv : m->u_cache) if (kv.second) hipFree(kv.second);
