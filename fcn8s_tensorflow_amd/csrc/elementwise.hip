@@ -418,16 +418,38 @@ static __device__ __forceinline__ long long slot_pixel(long long slot, const Pix
 }
 
 // ---- K10: fused softmax cross-entropy (loss partial sums + dlogits) ---------
+// PH (XentPhase, fcn8s_internal.h) picks the loss: XENT_PLAIN is the reference's mean (the arithmetic of every default launch);
+// XENT_WEIGHTED gathers the class weight w_y (LDS) into the loss and the gradient scale and counts the valid pixels; XENT_OHEM_LOSS
+// writes the pixel-indexed l_p, its top-11-bit histogram and the counts |V|, |{l >= tau}| (no gradient, no loss partials);
+// XENT_OHEM_GRAD keeps the pixels with l_p >= t (l_p read back from that buffer: the kept set is exactly the selected one) and scales them
+// by w_y * gscale, t and gscale read from the device state the selection kernels left.
 constexpr int XENT_PIX_PER_BLOCK = 1024;
 int softmax_xent_blocks(long long npix)
 {
     long long b = (npix + XENT_PIX_PER_BLOCK - 1) / XENT_PIX_PER_BLOCK;
     return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
 }
-template <int C>   // C % 4 == 0: registers hold the pixel's logits
+constexpr int OHEM_BINS0 = 2048, OHEM_BINS1 = 2048, OHEM_BINS2 = 1024;     // l_p's float bits 31..21 / 20..10 / 9..0 (non-negative floats order as integers)
+
+// the block's valid / above-tau counts and (XENT_OHEM_LOSS) its LDS histogram, folded into the model's state: integer atomics, order-independent
+template <int PH>
+static __device__ __forceinline__ void xent_fold(unsigned nv, unsigned ntau, unsigned* cnt, const unsigned* hsh, const XentEx& x)
+{
+    for (int o = 32; o > 0; o >>= 1) { nv += __shfl_down(nv, o, 64); ntau += __shfl_down(ntau, o, 64); }
+    if ((threadIdx.x & 63) == 0) { atomicAdd(&cnt[0], nv); atomicAdd(&cnt[1], ntau); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&x.st->valid, (unsigned long long)cnt[0]);
+        if (PH == XENT_OHEM_LOSS) atomicAdd(&x.st->ntau, (unsigned long long)cnt[1]);
+    }
+    if constexpr (PH == XENT_OHEM_LOSS)
+        for (int i = threadIdx.x; i < OHEM_BINS0; i += blockDim.x) if (hsh[i]) atomicAdd(&x.hist[i], hsh[i]);
+}
+
+template <int C, int PH>   // C % 4 == 0: registers hold the pixel's logits
 __global__ __launch_bounds__(256) void softmax_xent_kernel_c(const float* logits, const uint8_t* labels,
                                                              float* dlogits, double* partials,
-                                                             long long npix, float gscale, float* colsum, const PixMap map)
+                                                             long long npix, float gscale, float* colsum, const PixMap map, const XentEx x)
 {
     // One thread = one pixel, but a pixel's C floats are C / 4 16-byte units 4 C bytes apart: read per thread, every load instruction of a
     // wave touches 64 x 16 B spread over 64 x 4C bytes (3.9 TB/s).  So a wave moves its 64 pixels as a block -- U coalesced 1 KiB
@@ -437,10 +459,22 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel_c(const float* logits
     __shared__ float4 patch[U > 1 ? 4 * 64 * U : 1];
     __shared__ double sh[4];
     __shared__ float cs[C];
+    __shared__ float wsh[PH != XENT_PLAIN ? C : 1];
+    __shared__ unsigned hsh[PH == XENT_OHEM_LOSS ? OHEM_BINS0 : 1];
+    __shared__ unsigned cnt[2];
     float csum[C];                             // colsum != nullptr: column sums of dlogits (= the last bias gradient), saves a pass over dlogits
 #pragma unroll
     for (int i = 0; i < C; ++i) csum[i] = 0.f;
     if (threadIdx.x < C) cs[threadIdx.x] = 0.f;
+    float tsel = 0.f, gsel = gscale;           // XENT_OHEM_GRAD: the threshold t and the scale 1 / |K|
+    unsigned nv = 0, ntau = 0;
+    if constexpr (PH != XENT_PLAIN) {
+        if (threadIdx.x < C) wsh[threadIdx.x] = x.cw[threadIdx.x];
+        if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+        if constexpr (PH == XENT_OHEM_LOSS) for (int i = threadIdx.x; i < OHEM_BINS0; i += blockDim.x) hsh[i] = 0;
+        if constexpr (PH == XENT_OHEM_GRAD) { tsel = x.st->t; gsel = x.st->gscale; }
+        __syncthreads();
+    }
     double lsum = 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float4* wp = patch + (U > 1 ? wave * 64 * U : 0);
@@ -476,22 +510,40 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel_c(const float* logits
             float vl = 0.f;
 #pragma unroll
             for (int i = 0; i < C; ++i) vl = (i == lab) ? v[i] : vl;
-            if (!ign) lsum += (double)(m + logf(s) - vl);
-            if (dlogits) {
-                const float inv = ign ? 0.f : gscale / s;
+            float gs = gscale;                          // this pixel's gradient scale
+            bool keep = !ign;
+            if constexpr (PH == XENT_PLAIN) {
+                if (!ign) lsum += (double)(m + logf(s) - vl);
+            } else if constexpr (PH == XENT_WEIGHTED) {
+                const float w = ign ? 0.f : wsh[lab];
+                gs = gscale * w; nv += !ign;
+                if (!ign) lsum += (double)w * (double)(m + logf(s) - vl);
+            } else if constexpr (PH == XENT_OHEM_LOSS) {
+                const float l = m + logf(s) - vl;          // >= 0: fl(m + log s) >= m >= v[lab]
+                if (!ign) { ++nv; ntau += l >= x.tau; atomicAdd(&hsh[__float_as_uint(l) >> 21], 1u); }
+                x.lbuf[pix] = ign ? -1.f : l;
+            } else {
+                const float l = x.lbuf[pix];               // -1 for an ignored pixel: never kept (t >= 0)
+                keep = !ign && l >= tsel;
+                const float w = keep ? wsh[lab] : 0.f;
+                gs = gsel * w;
+                if (keep) lsum += (double)w * (double)l;
+            }
+            if (PH != XENT_OHEM_LOSS && dlogits) {
+                const float inv = keep ? gs / s : 0.f;
 #pragma unroll
                 for (int i = 0; i < U; ++i) {
                     float4 t;
-                    t.x = e[4*i] * inv - ((4*i) == lab ? gscale : 0.f);
-                    t.y = e[4*i+1] * inv - ((4*i+1) == lab ? gscale : 0.f);
-                    t.z = e[4*i+2] * inv - ((4*i+2) == lab ? gscale : 0.f);
-                    t.w = e[4*i+3] * inv - ((4*i+3) == lab ? gscale : 0.f);
+                    t.x = e[4*i] * inv - ((4*i) == lab ? gs : 0.f);
+                    t.y = e[4*i+1] * inv - ((4*i+1) == lab ? gs : 0.f);
+                    t.z = e[4*i+2] * inv - ((4*i+2) == lab ? gs : 0.f);
+                    t.w = e[4*i+3] * inv - ((4*i+3) == lab ? gs : 0.f);
                     g[i] = t;
                     csum[4*i] += t.x; csum[4*i+1] += t.y; csum[4*i+2] += t.z; csum[4*i+3] += t.w;
                 }
             }
         }
-        if (dlogits) {
+        if (PH != XENT_OHEM_LOSS && dlogits) {
             if constexpr (U > 1) {
 #pragma unroll
                 for (int i = 0; i < U; ++i) wp[lane * U + i] = g[i];
@@ -503,6 +555,8 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel_c(const float* logits
             } else if (p < npix) reinterpret_cast<float4*>(dlogits)[p] = g[0];
         }
     }
+    if constexpr (PH == XENT_WEIGHTED || PH == XENT_OHEM_LOSS) xent_fold<PH>(nv, ntau, cnt, hsh, x);
+    if constexpr (PH == XENT_OHEM_LOSS) return;
     const double t = block_sum(lsum, sh);
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
     if (colsum && dlogits) {
@@ -517,16 +571,29 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel_c(const float* logits
         if (threadIdx.x < C) unsafeAtomicAdd(colsum + threadIdx.x, cs[threadIdx.x]);
     }
 }
+template <int PH>
 __global__ __launch_bounds__(256) void softmax_xent_kernel_any(const float* logits, const uint8_t* labels,
                                                                float* dlogits, double* partials,
-                                                               long long npix, int C, float gscale, const PixMap map)
+                                                               long long npix, int C, float gscale, const PixMap map, const XentEx x)
 {
     __shared__ double sh[4];
+    __shared__ float wsh[PH != XENT_PLAIN ? 64 : 1];
+    __shared__ unsigned hsh[PH == XENT_OHEM_LOSS ? OHEM_BINS0 : 1];
+    __shared__ unsigned cnt[2];
+    float tsel = 0.f, gsel = gscale;
+    unsigned nv = 0, ntau = 0;
+    if constexpr (PH != XENT_PLAIN) {
+        if (threadIdx.x < C) wsh[threadIdx.x] = x.cw[threadIdx.x];
+        if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+        if constexpr (PH == XENT_OHEM_LOSS) for (int i = threadIdx.x; i < OHEM_BINS0; i += blockDim.x) hsh[i] = 0;
+        if constexpr (PH == XENT_OHEM_GRAD) { tsel = x.st->t; gsel = x.st->gscale; }
+        __syncthreads();
+    }
     double lsum = 0;
     for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < npix;
          p += (long long)gridDim.x * blockDim.x) {
         const long long pix = slot_pixel(p, map);
-        if (pix < 0) { if (dlogits) for (int i = 0; i < C; ++i) dlogits[p * C + i] = 0.f; continue; }
+        if (pix < 0) { if (PH != XENT_OHEM_LOSS && dlogits) for (int i = 0; i < C; ++i) dlogits[p * C + i] = 0.f; continue; }
         const float* l = logits + p * C;
         float m = l[0];
         for (int i = 1; i < C; ++i) m = fmaxf(m, l[i]);
@@ -534,56 +601,157 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel_any(const float* logi
         for (int i = 0; i < C; ++i) s += expf(l[i] - m);
         const int lab = labels[pix];
         const bool ign = lab >= C;                 // see softmax_xent_kernel_c
-        if (!ign) lsum += (double)(m + logf(s) - l[lab]);
+        float gs = gscale;
+        bool keep = !ign;
+        if constexpr (PH == XENT_PLAIN) {
+            if (!ign) lsum += (double)(m + logf(s) - l[lab]);
+        } else if constexpr (PH == XENT_WEIGHTED) {
+            const float w = ign ? 0.f : wsh[lab];
+            gs = gscale * w; nv += !ign;
+            if (!ign) lsum += (double)w * (double)(m + logf(s) - l[lab]);
+        } else if constexpr (PH == XENT_OHEM_LOSS) {
+            const float lp = ign ? -1.f : m + logf(s) - l[lab];
+            if (!ign) { ++nv; ntau += lp >= x.tau; atomicAdd(&hsh[__float_as_uint(lp) >> 21], 1u); }
+            x.lbuf[pix] = lp;
+            continue;
+        } else {
+            const float lp = x.lbuf[pix];
+            keep = !ign && lp >= tsel;
+            const float w = keep ? wsh[lab] : 0.f;
+            gs = gsel * w;
+            if (keep) lsum += (double)w * (double)lp;
+        }
         if (dlogits) {
-            const float inv = ign ? 0.f : gscale / s;
-            for (int i = 0; i < C; ++i) dlogits[p * C + i] = expf(l[i] - m) * inv - (i == lab ? gscale : 0.f);
+            const float inv = keep ? gs / s : 0.f;
+            for (int i = 0; i < C; ++i) dlogits[p * C + i] = expf(l[i] - m) * inv - (i == lab ? gs : 0.f);
         }
     }
+    if constexpr (PH == XENT_WEIGHTED || PH == XENT_OHEM_LOSS) xent_fold<PH>(nv, ntau, cnt, hsh, x);
+    if constexpr (PH == XENT_OHEM_LOSS) return;
     const double t = block_sum(lsum, sh);
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+template <int PH>
+static void xent_launch(const float* logits, const uint8_t* labels, float* dlogits, double* partials, long long npix, long long nslot, int C,
+                        float gscale, float* colsum, const PixMap& pm, const XentEx& x, hipStream_t s)
+{
+    const int blocks = softmax_xent_blocks(npix);          // (the partial-sum count finalize_loss expects)
+    // the fused column sums (= the last bias gradient) of the blocks meet in atomics: deterministic mode takes them from dlogits in a pass of its own
+    // (slots outside the image hold zero gradient); so does the generic kernel
+    const bool fused = colsum && dlogits && (C == 20 || C == 4) && !t_deterministic;
+    float* cs = fused ? colsum : nullptr;
+    if (C == 20)     hipLaunchKernelGGL((softmax_xent_kernel_c<20, PH>), dim3(blocks), dim3(256), 0, s, logits, labels, dlogits, partials, nslot, gscale, cs, pm, x);
+    else if (C == 4) hipLaunchKernelGGL((softmax_xent_kernel_c<4, PH>), dim3(blocks), dim3(256), 0, s, logits, labels, dlogits, partials, nslot, gscale, cs, pm, x);
+    else             hipLaunchKernelGGL((softmax_xent_kernel_any<PH>), dim3(blocks), dim3(256), 0, s, logits, labels, dlogits, partials, nslot, C, gscale, pm, x);
+    if (colsum && dlogits && !fused) launch_colsum(dlogits, colsum, nslot, C, s);
 }
 void launch_softmax_xent(const float* logits, const uint8_t* labels, float* dlogits, double* partials,
                          long long npix, int C, float grad_scale, hipStream_t s, float* colsum, const PixMap* map, int N)
 {
     const PixMap pm = map ? *map : PixMap{0, 0, 0, 0, 0, 0};
+    xent_launch<XENT_PLAIN>(logits, labels, dlogits, partials, npix, pixmap_slots(pm, npix, N), C, grad_scale, colsum, pm, XentEx{}, s);
+}
+
+// ---- OHEM: the k-th largest l_p by radix selection, all on the device ----------------------------------------------------------------
+// Level 1 / 2 histogram bits 20..10 / 9..0 of the keys (= l_p's float bits, valid pixels only) whose higher bits equal the prefix fixed so
+// far; a level whose selection is already settled (st->active == 0) returns at once.
+__global__ __launch_bounds__(256) void ohem_refine_kernel(const float* __restrict__ lbuf, long long npix, const OhemState* st, unsigned* hist, int level)
+{
+    if (!st->active) return;
+    __shared__ unsigned h[OHEM_BINS1];
+    const int hi = level == 1 ? 21 : 10, shift = level == 1 ? 10 : 0;
+    const unsigned mask = level == 1 ? OHEM_BINS1 - 1 : OHEM_BINS2 - 1, want = st->prefix >> hi;
+    for (int i = threadIdx.x; i < OHEM_BINS1; i += blockDim.x) h[i] = 0;
+    __syncthreads();
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+        const unsigned key = __float_as_uint(lbuf[p]);
+        if ((int)key >= 0 && (key >> hi) == want) atomicAdd(&h[(key >> shift) & mask], 1u);    // (an ignored pixel holds -1: sign bit set)
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i <= (int)mask; i += blockDim.x) if (h[i]) atomicAdd(&hist[i], h[i]);
+}
+// One block.  Level 0 decides whether the selection is needed at all: k = min(min_kept, |V|); with k == 0 or |{l >= tau}| >= k the
+// k-th largest is >= tau, so t = tau and |K| = |{l >= tau}|.  Otherwise every level finds the bin that holds the k-th largest of the keys
+// under the prefix (chunk sums, a suffix scan over the 256 chunks, one thread walks the crossing chunk), and the last level fixes
+// t = l_(k) < tau and |K| = |{l >= l_(k)}| = (keys above the bin at every level) + (the bin's count).
+__global__ __launch_bounds__(256) void ohem_select_kernel(OhemState* st, const unsigned* hist, int level, long long min_kept, float tau)
+{
+    __shared__ unsigned long long part[256];
+    __shared__ unsigned long long krem, above0;
+    __shared__ int act;
+    const int t = threadIdx.x;
+    if (t == 0) {
+        if (level == 0) {
+            const unsigned long long V = st->valid, k = (unsigned long long)min_kept < V ? (unsigned long long)min_kept : V;
+            if (k == 0 || st->ntau >= k) {
+                st->active = 0; st->t = tau; st->kept = st->ntau; st->gscale = st->ntau ? 1.f / (float)st->ntau : 0.f;
+            } else { st->active = 1; st->krem = k; st->above = 0; st->prefix = 0; }
+        }
+        act = st->active; krem = st->krem; above0 = st->above;
+    }
+    __syncthreads();
+    if (!act) return;
+    const int nb = level == 2 ? OHEM_BINS2 : OHEM_BINS0, per = nb / 256, shift = level == 0 ? 21 : level == 1 ? 10 : 0;
+    unsigned long long c = 0;
+    for (int j = 0; j < per; ++j) c += hist[t * per + j];
+    part[t] = c;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {           // part[t] = sum of chunks t .. 255
+        const unsigned long long v = part[t] + (t + off < 256 ? part[t + off] : 0ull);
+        __syncthreads();
+        part[t] = v;
+        __syncthreads();
+    }
+    const unsigned long long incl = part[t], excl = t < 255 ? part[t + 1] : 0ull;
+    if (excl < krem && incl >= krem) {                   // exactly one chunk holds the k-th largest (krem >= 1, <= the keys under the prefix)
+        unsigned long long above = excl;
+        int bin = t * per;
+        unsigned h = 0;
+        for (int j = per - 1; j >= 0; --j) { h = hist[t * per + j]; if (above + h >= krem) { bin = t * per + j; break; } above += h; }
+        const unsigned prefix = st->prefix | ((unsigned)bin << shift);
+        st->prefix = prefix; st->krem = krem - above; st->above = above0 + above;
+        if (level == 2) {
+            const unsigned long long kept = above0 + above + h;
+            st->t = __uint_as_float(prefix); st->kept = kept; st->gscale = 1.f / (float)kept;
+        }
+    }
+}
+void launch_softmax_xent_ex(const float* logits, const uint8_t* labels, float* dlogits, double* partials, long long npix, int C, float grad_scale,
+                            hipStream_t s, float* colsum, const PixMap* map, int N, const XentEx& x, float ohem_thresh, long long ohem_min_kept)
+{
+    const PixMap pm = map ? *map : PixMap{0, 0, 0, 0, 0, 0};
     const long long nslot = pixmap_slots(pm, npix, N);
-    const int blocks = softmax_xent_blocks(npix);          // (the partial-sum count finalize_loss expects)
-    if (t_deterministic && colsum && dlogits && (C == 20 || C == 4)) {
-        // the fused column sums (= the last bias gradient) of the blocks meet in atomics: deterministic mode takes them from dlogits in a pass of its own
-        // (slots outside the image hold zero gradient)
-        if (C == 20) hipLaunchKernelGGL(softmax_xent_kernel_c<20>, dim3(blocks), dim3(256), 0, s, logits, labels, dlogits, partials, nslot, grad_scale, (float*)nullptr, pm);
-        else         hipLaunchKernelGGL(softmax_xent_kernel_c<4>, dim3(blocks), dim3(256), 0, s, logits, labels, dlogits, partials, nslot, grad_scale, (float*)nullptr, pm);
-        launch_colsum(dlogits, colsum, nslot, C, s);
-        return;
-    }
-    if (C == 20)
-        hipLaunchKernelGGL(softmax_xent_kernel_c<20>, dim3(blocks), dim3(256), 0, s, logits, labels, dlogits, partials, nslot, grad_scale, colsum, pm);
-    else if (C == 4)
-        hipLaunchKernelGGL(softmax_xent_kernel_c<4>, dim3(blocks), dim3(256), 0, s, logits, labels, dlogits, partials, nslot, grad_scale, colsum, pm);
-    else {
-        hipLaunchKernelGGL(softmax_xent_kernel_any, dim3(blocks), dim3(256), 0, s, logits, labels, dlogits, partials, nslot, C, grad_scale, pm);
-        if (colsum && dlogits) launch_colsum(dlogits, colsum, nslot, C, s);
-    }
+    hipMemsetAsync(x.st, 0, LOSS_SCRATCH_BYTES, s);                 // the state and the three histograms (x.hist follows x.st)
+    if (ohem_thresh <= 0.f) { xent_launch<XENT_WEIGHTED>(logits, labels, dlogits, partials, npix, nslot, C, grad_scale, colsum, pm, x, s); return; }
+    XentEx y = x;
+    y.tau = (float)(-log((double)ohem_thresh));
+    xent_launch<XENT_OHEM_LOSS>(logits, labels, nullptr, partials, npix, nslot, C, grad_scale, nullptr, pm, y, s);
+    const int rb = cap_blocks(npix, 1024);
+    hipLaunchKernelGGL(ohem_select_kernel, dim3(1), dim3(256), 0, s, x.st, x.hist, 0, ohem_min_kept, y.tau);
+    hipLaunchKernelGGL(ohem_refine_kernel, dim3(rb), dim3(256), 0, s, (const float*)x.lbuf, npix, (const OhemState*)x.st, x.hist + OHEM_BINS0, 1);
+    hipLaunchKernelGGL(ohem_select_kernel, dim3(1), dim3(256), 0, s, x.st, x.hist + OHEM_BINS0, 1, ohem_min_kept, y.tau);
+    hipLaunchKernelGGL(ohem_refine_kernel, dim3(rb), dim3(256), 0, s, (const float*)x.lbuf, npix, (const OhemState*)x.st, x.hist + OHEM_BINS0 + OHEM_BINS1, 2);
+    hipLaunchKernelGGL(ohem_select_kernel, dim3(1), dim3(256), 0, s, x.st, x.hist + OHEM_BINS0 + OHEM_BINS1, 2, ohem_min_kept, y.tau);
+    xent_launch<XENT_OHEM_GRAD>(logits, labels, dlogits, partials, npix, nslot, C, grad_scale, colsum, pm, y, s);
 }
 
 __global__ void finalize_loss_kernel(const double* partials, int nparts, long long npix, const float* regsum,
-                                     float rate, float* loss_out)
+                                     float rate, float* loss_out, const unsigned long long* den)
 {
     __shared__ double sh[4];
     double v = 0;
     for (int i = threadIdx.x; i < nparts; i += blockDim.x) v += partials[i];
     const double t = block_sum(v, sh);
     if (threadIdx.x == 0) {
-        const float ce = (float)(t / (double)npix);
+        const float ce = den ? (*den ? (float)(t / (double)*den) : 0.f) : (float)(t / (double)npix);
         const float reg = regsum ? 0.5f * rate * regsum[0] : 0.f;
         loss_out[0] = ce + reg;
     }
 }
 void launch_finalize_loss(const double* partials, int nparts, long long npix, const float* regsum,
-                          float rate, float* loss_out, hipStream_t s)
+                          float rate, float* loss_out, hipStream_t s, const unsigned long long* den)
 {
-    hipLaunchKernelGGL(finalize_loss_kernel, dim3(1), dim3(256), 0, s, partials, nparts, npix, regsum, rate, loss_out);
+    hipLaunchKernelGGL(finalize_loss_kernel, dim3(1), dim3(256), 0, s, partials, nparts, npix, regsum, rate, loss_out, den);
 }
 
 // ---- K13: softmax -> argmax (of the softmax output, lowest index on ties) ----

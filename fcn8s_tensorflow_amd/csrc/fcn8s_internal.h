@@ -185,9 +185,32 @@ int  softmax_xent_blocks(long long npix);
 void launch_softmax_xent(const float* logits, const uint8_t* labels, float* dlogits, double* partials,
                          long long npix, int C, float grad_scale, hipStream_t s, float* colsum = nullptr,   /* colsum[c] += sum_p dlogits[p,c] (zero-initialised by the caller) */
                          const PixMap* map = nullptr, int N = 0);
-// loss_out[0] = sum(partials)/npix + 0.5*rate*regsum[0]
+// The training loss's class weights and online hard-example mining (fcn8s_set_loss, include/fcn8s_hip.h).  The scratch is LOSS_SCRATCH_BYTES
+// of state and histograms (zeroed by launch_softmax_xent_ex) followed, for OHEM, by the pixel-indexed l_p buffer (float[npix]).
+enum XentPhase { XENT_PLAIN = 0, XENT_WEIGHTED = 1, XENT_OHEM_LOSS = 2, XENT_OHEM_GRAD = 3 };
+struct OhemState {
+    unsigned long long valid, ntau, kept;   // |V|, |{l >= tau}|, |K|
+    unsigned long long krem, above;         // selection: the rank still sought under the prefix, the keys above it
+    unsigned prefix; int active;            // the key bits fixed so far; 1 = the refinement levels run
+    float t, gscale;                        // the threshold t and the gradient scale 1 / |K|
+    unsigned pad[2];
+};
+static_assert(sizeof(OhemState) == 64, "OhemState: 64 bytes");
+constexpr size_t LOSS_SCRATCH_BYTES = sizeof(OhemState) + (2048 + 2048 + 1024) * sizeof(unsigned);
+struct XentEx {
+    const float* cw = nullptr;             // class weights, device float[C]
+    float* lbuf = nullptr;                 // OHEM: l_p per pixel (-1 = ignored pixel)
+    OhemState* st = nullptr;
+    unsigned* hist = nullptr;              // the three radix histograms, right behind st
+    float tau = 0.f;
+};
+// weighted (ohem_thresh == 0) or OHEM loss over the same blocked / plain logits as launch_softmax_xent; partials then hold sum w l_p, and
+// finalize_loss divides by st->kept (OHEM) or by npix (weighted).  No host synchronisation.
+void launch_softmax_xent_ex(const float* logits, const uint8_t* labels, float* dlogits, double* partials, long long npix, int C, float grad_scale,
+                            hipStream_t s, float* colsum, const PixMap* map, int N, const XentEx& x, float ohem_thresh, long long ohem_min_kept);
+// loss_out[0] = sum(partials)/npix + 0.5*rate*regsum[0]; with `den`: sum(partials)/den[0] (0 when den[0] == 0)
 void launch_finalize_loss(const double* partials, int nparts, long long npix, const float* regsum,
-                          float rate, float* loss_out, hipStream_t s);
+                          float rate, float* loss_out, hipStream_t s, const unsigned long long* den = nullptr);
 void launch_softmax_argmax(const float* logits, float* softmax_out, long long* argmax_out,
                            long long npix, int C, hipStream_t s, const PixMap* map = nullptr, int N = 0);
 // ---- the k = 2s transposed conv as one GEMM (see PixMap): operand / result re-layouts, all tiny next to the GEMMs -------------

@@ -189,6 +189,10 @@ struct fcn8s_model {
     float* h_loss = nullptr; hipEvent_t loss_ev = nullptr; bool loss_copied = false;   // pinned copy of d_loss, queued right after the loss kernels
     float* d_lastbias = nullptr;       // column sums of dlogits (gradient of the last transposed conv's bias), produced by the loss kernel
     double* d_partials = nullptr; long long* d_pred = nullptr;
+    // fcn8s_set_loss: the training loss (0 = the reference's mean, 1 = class-weighted, 2 = OHEM); weights in d_cw (float[64], made once by
+    // fcn8s_set_loss); loss_ws = LOSS_SCRATCH_BYTES of state and histograms + (OHEM) the l_p buffer, grown on first use (a "workspace_allocation")
+    int loss_mode = 0, last_loss_mode = 0; float ohem_thresh = 0.f; int64_t ohem_min_kept = 0;
+    float* d_cw = nullptr; char* loss_ws = nullptr; size_t loss_ws_bytes = 0;
     unsigned long long* d_conf = nullptr;
     double loss_sum = 0; int64_t loss_cnt = 0;
     float keep_prob = 1.f, l2_rate = 0.f;
@@ -1572,23 +1576,47 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
 const char* kDecoderKernels[6] = {"pool3_1x1/kernel", "pool4_1x1/kernel", "fc7_1x1/kernel", "fc7_conv2d_trans/kernel",
                                   "fc7_pool4_conv2d_trans/kernel", "fc7_pool4_pool3_conv2d_trans/kernel"};
 
+// the scratch of a configured training loss (fcn8s_set_loss): state + histograms, and for OHEM the l_p buffer of npix floats
+int ensure_loss_ws(fcn8s_model* m, long long npix)
+{
+    const size_t need = LOSS_SCRATCH_BYTES + (m->loss_mode == 2 ? (size_t)npix * sizeof(float) : 0);
+    if (m->loss_ws && m->loss_ws_bytes >= need) return FCN8S_OK;
+    if (m->loss_ws) { hipStreamSynchronize(m->stream); hipFree(m->loss_ws); m->loss_ws = nullptr; m->loss_ws_bytes = 0; }
+    HIPCHK(m, hipMalloc((void**)&m->loss_ws, need));
+    m->loss_ws_bytes = need; ++m->ws_allocs;
+    return FCN8S_OK;
+}
+
 int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool with_grad)
 {
     hipStream_t s = m->stream;
     const long long npix = (long long)m->N * m->H * m->W;
     const int nb = softmax_xent_blocks(npix);
-    { ProfScope ps(m, "softmax_xent", 0, (double)npix * (m->C * 4 * (with_grad ? 2 : 1) + 1));
+    const int mode = with_grad ? m->loss_mode : 0;            // evaluation keeps the reference's loss
+    if (mode) { int rc = ensure_loss_ws(m, npix); if (rc) return rc; }
+    OhemState* st = mode ? (OhemState*)m->loss_ws : nullptr;
+    // bytes: the logits once (+ dlogits) and the labels; OHEM reads the logits and labels twice and writes + reads l_p (its refinement
+    // passes, 4 bytes per pixel each when min_kept decides the threshold, are not counted)
+    const double xbytes = mode == 2 ? (double)npix * (m->C * 4 * 3 + 2 + 8) : (double)npix * (m->C * 4 * (with_grad ? 2 : 1) + 1);
+    { ProfScope ps(m, "softmax_xent", 0, xbytes);
       if (with_grad) hipMemsetAsync(m->d_lastbias, 0, 64 * sizeof(float), s);
       const bool blk = m->tconv_gemm && m->logits_b;
-      launch_softmax_xent(blk ? m->logits_b : A(m, "logits"), lab_dev, with_grad ? (blk ? m->dlogits_b : m->dlogits) : nullptr, m->d_partials, npix, m->C,
-                          1.0f / (float)npix, s, with_grad ? m->d_lastbias : nullptr, blk ? &m->pm : nullptr, m->N); }
+      if (mode) {
+          XentEx x; x.cw = m->d_cw; x.st = st; x.hist = (unsigned*)(m->loss_ws + sizeof(OhemState));
+          x.lbuf = mode == 2 ? (float*)(m->loss_ws + LOSS_SCRATCH_BYTES) : nullptr;
+          launch_softmax_xent_ex(blk ? m->logits_b : A(m, "logits"), lab_dev, blk ? m->dlogits_b : m->dlogits, m->d_partials, npix, m->C, 1.0f / (float)npix, s,
+                                 m->d_lastbias, blk ? &m->pm : nullptr, m->N, x, mode == 2 ? m->ohem_thresh : 0.f, (long long)m->ohem_min_kept);
+      } else
+          launch_softmax_xent(blk ? m->logits_b : A(m, "logits"), lab_dev, with_grad ? (blk ? m->dlogits_b : m->dlogits) : nullptr, m->d_partials, npix, m->C,
+                              1.0f / (float)npix, s, with_grad ? m->d_lastbias : nullptr, blk ? &m->pm : nullptr, m->N); }
+    if (with_grad) m->last_loss_mode = mode;
     const float* reg = nullptr;
     if (l2_rate != 0.f) {
         hipMemsetAsync(m->d_regsum, 0, sizeof(float), s);
         for (auto k : kDecoderKernels) launch_sumsq(Wp(m, k), m->d_regsum, (long long)P(m, k).numel, s);
         reg = m->d_regsum;
     }
-    launch_finalize_loss(m->d_partials, nb, npix, reg, l2_rate, m->d_loss, s);
+    launch_finalize_loss(m->d_partials, nb, npix, reg, l2_rate, m->d_loss, s, mode == 2 ? &st->kept : nullptr);
     // The loss is final here, a third of the way into a training step: queue its copy now, so that fcn8s_read_loss waits for this
     // point of the stream only and the host can go on queueing the next step while the backward pass runs (the reference fetches
     // the loss every step, fcn8s_tensorflow.py:554-578; waiting for the whole stream left the GPU idle for ~2 ms per step).
@@ -1959,6 +1987,8 @@ int fcn8s_destroy(fcn8s_model* m)
     if (m->copy_stream) hipStreamDestroy(m->copy_stream);
     if (m->arena) hipFree(m->arena);
     if (m->tta_buf) hipFree(m->tta_buf);
+    if (m->loss_ws) hipFree(m->loss_ws);
+    if (m->d_cw) hipFree(m->d_cw);
     delete m;
     // the model is gone either way; a communicator that had failed is reported once, with its reason in fcn8s_last_error(NULL)
     if (rc_comm) { g_last_error = comm_text; return rc_comm; }
@@ -2563,6 +2593,54 @@ int fcn8s_read_loss(fcn8s_model* m, float* loss_out)
     }
     HIPCHK(m, hipMemcpyAsync(loss_out, m->d_loss, sizeof(float), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(m, hipStreamSynchronize(m->stream));
+    return FCN8S_OK;
+}
+
+// the arguments of a weighted / OHEM loss (fcn8s_set_loss, fcn8s_op_softmax_xent_ex); weights on the host, or nullptr
+static int check_loss_args(fcn8s_model* m, const float* w, int nw, int C, float thresh, int64_t min_kept, const char* who)
+{
+    if (w) {
+        if (nw != C) return fail(m, FCN8S_ERR_BAD_ARG, std::string(who) + ": nweights must equal num_classes (" + std::to_string(C) + ")");
+        bool any = false;
+        for (int i = 0; i < nw; ++i) {
+            if (!std::isfinite(w[i]) || w[i] < 0.f) return fail(m, FCN8S_ERR_BAD_ARG, std::string(who) + ": class weights must be finite and >= 0");
+            any |= w[i] > 0.f;
+        }
+        if (!any) return fail(m, FCN8S_ERR_BAD_ARG, std::string(who) + ": class weights must not all be zero");
+    }
+    if (!(thresh == 0.f || (thresh > 0.f && thresh <= 1.f))) return fail(m, FCN8S_ERR_BAD_ARG, std::string(who) + ": ohem_thresh must be 0 (off) or in (0, 1]");
+    if (min_kept < 0) return fail(m, FCN8S_ERR_BAD_ARG, std::string(who) + ": ohem_min_kept must be >= 0");
+    return FCN8S_OK;
+}
+
+int fcn8s_set_loss(fcn8s_model* m, const float* class_weights, int nweights, float ohem_thresh, int64_t ohem_min_kept)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    int rc = check_loss_args(m, class_weights, nweights, m->C, ohem_thresh, ohem_min_kept, "fcn8s_set_loss"); if (rc) return rc;
+    const int mode = ohem_thresh > 0.f ? 2 : class_weights ? 1 : 0;
+    if (mode) {
+        if (!m->d_cw) HIPCHK(m, hipMalloc((void**)&m->d_cw, 64 * sizeof(float)));
+        std::vector<float> w(64, 0.f);
+        for (int c = 0; c < m->C; ++c) w[c] = class_weights ? class_weights[c] : 1.f;
+        HIPCHK(m, hipStreamSynchronize(m->stream));          // (a queued step may still read the old weights)
+        HIPCHK(m, hipMemcpy(m->d_cw, w.data(), 64 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    m->loss_mode = mode; m->ohem_thresh = ohem_thresh; m->ohem_min_kept = ohem_min_kept;
+    return FCN8S_OK;
+}
+
+int fcn8s_get_loss_stats(fcn8s_model* m, int64_t* valid, int64_t* kept, float* threshold)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!m->last_loss_mode || !m->loss_ws)
+        return fail(m, FCN8S_ERR_STATE, "fcn8s_get_loss_stats: the last training loss ran without a loss configuration (fcn8s_set_loss)");
+    OhemState st;
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(&st, m->loss_ws, sizeof st, hipMemcpyDeviceToHost));
+    const bool ohem = m->last_loss_mode == 2;
+    if (valid) *valid = (int64_t)st.valid;
+    if (kept) *kept = (int64_t)(ohem ? st.kept : st.valid);
+    if (threshold) *threshold = ohem ? st.t : 0.f;
     return FCN8S_OK;
 }
 
@@ -3251,6 +3329,36 @@ int fcn8s_op_softmax_xent(void* stream, const float* logits, const uint8_t* labe
     launch_softmax_xent(logits, labels, dlogits, part, npix, C, 1.0f / (float)npix, s);
     launch_finalize_loss(part, softmax_xent_blocks(npix), npix, nullptr, 0.f, loss_dev, s);
     hipStreamSynchronize(s); hipFree(part);
+    OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_softmax_xent_ex(void* stream, const float* logits, const uint8_t* labels, const float* class_weights_dev, float ohem_thresh,
+                             int64_t ohem_min_kept, float* dlogits, float* loss_dev, float* pixel_loss_dev, int64_t* stats_dev, int64_t npix, int C)
+{
+    if (!class_weights_dev && ohem_thresh == 0.f) return fcn8s_op_softmax_xent(stream, logits, labels, dlogits, loss_dev, npix, C);
+    if (!logits || !labels || !loss_dev || npix < 1 || C < 1 || C > 64) return fail(nullptr, FCN8S_ERR_BAD_ARG, "fcn8s_op_softmax_xent_ex: bad argument");
+    int rc = check_loss_args(nullptr, nullptr, C, C, ohem_thresh, ohem_min_kept, "fcn8s_op_softmax_xent_ex"); if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const bool ohem = ohem_thresh > 0.f;
+    const size_t lb = ohem && !pixel_loss_dev ? (size_t)npix * sizeof(float) : 0;
+    char* ws = nullptr;
+    if (hipMalloc((void**)&ws, 4096 * sizeof(double) + 64 * sizeof(float) + LOSS_SCRATCH_BYTES + lb) != hipSuccess) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+    double* part = (double*)ws;
+    float* ones = (float*)(ws + 4096 * sizeof(double));
+    char* sc = ws + 4096 * sizeof(double) + 64 * sizeof(float);
+    if (!class_weights_dev) { const std::vector<float> h(64, 1.f); hipMemcpyAsync(ones, h.data(), 64 * sizeof(float), hipMemcpyHostToDevice, s); hipStreamSynchronize(s); }
+    XentEx x; x.cw = class_weights_dev ? class_weights_dev : ones; x.st = (OhemState*)sc; x.hist = (unsigned*)(sc + sizeof(OhemState));
+    x.lbuf = ohem ? (pixel_loss_dev ? pixel_loss_dev : (float*)(sc + LOSS_SCRATCH_BYTES)) : nullptr;
+    launch_softmax_xent_ex(logits, labels, dlogits, part, npix, C, 1.0f / (float)npix, s, nullptr, nullptr, 0, x, ohem_thresh, (long long)ohem_min_kept);
+    launch_finalize_loss(part, softmax_xent_blocks(npix), npix, nullptr, 0.f, loss_dev, s, ohem ? &x.st->kept : nullptr);
+    OhemState st{};
+    hipMemcpyAsync(&st, x.st, sizeof st, hipMemcpyDeviceToHost, s);
+    hipStreamSynchronize(s);
+    if (stats_dev) {
+        uint32_t tb = 0; const float t = ohem ? st.t : 0.f; std::memcpy(&tb, &t, 4);
+        const int64_t h[3] = {(int64_t)st.valid, (int64_t)(ohem ? st.kept : st.valid), (int64_t)tb};
+        hipMemcpy(stats_dev, h, sizeof h, hipMemcpyHostToDevice);
+    }
+    hipFree(ws);
     OPCHK(); return FCN8S_OK;
 }
 int fcn8s_op_softmax_argmax(void* stream, const float* logits, float* sm, int64_t* am, int64_t npix, int C)

@@ -20,6 +20,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib as L
+from . import loss as loss_mod
 from . import tta
 from .dp import BucketReducer
 
@@ -123,6 +124,7 @@ class Engine:
         self._label_checks_left = 2
         self._label_calls = 0
         self._bad = None
+        self.loss_config = None              # set_loss: the training loss's configuration (None = the reference's mean)
         self.replica_check_every = 100      # data-parallel runs: compare global step + parameter checksum across ranks every so many steps (0 = never)
         self._sync_stream()
 
@@ -418,6 +420,27 @@ class Engine:
             raise ValueError("`precision` must be 'fp32', 'bf16_fc', 'f32x3', 'bf16_fwd', 'f32x2', 'bf16_fwd_x2' or 'bf16_train', but is '{}'.".format(precision))
         L.check(L.lib.fcn8s_set_precision(self.h, modes[precision]), self.h)
         self.precision = precision
+
+    def set_loss(self, class_weights=None, ohem_thresh=None, ohem_min_kept=100000):
+        """The training loss (fcn8s_set_loss; definitions in loss.py and include/fcn8s_hip.h): per-class weights in the caller's logical
+        class count (padded here with zeros to the library's multiple of 4) and / or OHEM with a probability threshold in (0, 1] and at
+        least `ohem_min_kept` pixels kept.  No arguments restore the reference's mean.  Evaluation keeps the reference's loss."""
+        w, t, k = loss_mod.validate(class_weights, ohem_thresh, ohem_min_kept, self.logical_classes)
+        if w is not None:
+            w = np.concatenate([w, np.zeros(self.num_classes - w.size, np.float32)]).astype(np.float32)
+            arr = (C.c_float * w.size)(*w.tolist())
+            L.check(L.lib.fcn8s_set_loss(self.h, arr, int(w.size), t, k), self.h)
+        else:
+            L.check(L.lib.fcn8s_set_loss(self.h, None, 0, t, k), self.h)
+        self.loss_config = None if (w is None and t == 0.0) else dict(
+            class_weights=None if class_weights is None else np.asarray(class_weights, np.float32).copy(),
+            ohem_thresh=ohem_thresh if t else None, ohem_min_kept=k)
+
+    def loss_stats(self):
+        """|V|, |K| and the threshold t of the last training loss (fcn8s_get_loss_stats; synchronises)."""
+        v = C.c_int64(); kp = C.c_int64(); t = C.c_float()
+        L.check(L.lib.fcn8s_get_loss_stats(self.h, C.byref(v), C.byref(kp), C.byref(t)), self.h)
+        return dict(valid=int(v.value), kept=int(kp.value), threshold=float(t.value))
 
     def train_step(self, images, labels, learning_rate, keep_prob=0.5, l2_rate=0.0,
                    optimizer=L.OPT_TF_ADAM, fetch_loss=True, reduce=True):

@@ -47,6 +47,7 @@ except Exception:  # pragma: no cover
         return _R(n)
 
 from . import _lib as L
+from . import loss as loss_mod
 from . import tf_bundle
 from .engine import Engine, padded_classes
 
@@ -196,12 +197,21 @@ class FCN8s:
               summaries_frequency=10,
               summaries_dir=None,
               summaries_name=None,
-              training_loss_display_averaging=3):
+              training_loss_display_averaging=3,
+              class_weights=None,
+              ohem_thresh=None,
+              ohem_min_kept=100000):
         '''Trains the model; arguments as fcn8s_tensorflow.py:424-503.  Summaries are written as TensorBoard
         event files (`<summaries_dir>/<summaries_name>[_eval]/events.out.tfevents.*`: total_loss, learning_rate and
         mean / stddev / max / min / histogram of the ten watched weight-bias pairs, :331-366) and, for reading
-        without TensorBoard, as JSON lines (`scalars.jsonl`) next to them; if `summaries_dir` is None nothing is recorded.'''
+        without TensorBoard, as JSON lines (`scalars.jsonl`) next to them; if `summaries_dir` is None nothing is recorded.
+        `class_weights` (one per class), `ohem_thresh` (a probability in (0, 1]) and `ohem_min_kept` set the training loss for the duration
+        of the call (Engine.set_loss, loss.py: class-weighted and / or hard-pixel-mined cross-entropy); the evaluations keep reporting the
+        reference's loss, and the previous loss configuration is restored when train() returns or raises.'''
         _check_metric_names(metrics)
+        custom_loss = class_weights is not None or bool(ohem_thresh)
+        if custom_loss:
+            loss_mod.validate(class_weights, ohem_thresh, ohem_min_kept, self.engine.logical_classes)
         if eval_dataset not in ('train', 'val'):
             raise ValueError("`eval_dataset` must be one of 'train' or 'val', but is '{}'.".format(eval_dataset))
         if eval_dataset == 'val' and (val_generator is None or val_steps is None):
@@ -224,7 +234,10 @@ class FCN8s:
         eval_source = {'train': (train_generator, steps_per_epoch, 'Evaluation on training dataset'),
                        'val': (val_generator, val_steps, 'Evaluation on validation dataset')}[eval_dataset]
 
+        prev_loss = self.engine.loss_config
         try:
+            if custom_loss:
+                self.engine.set_loss(class_weights, ohem_thresh, ohem_min_kept)
             for epoch in range(1, epochs + 1):
                 self._run_epoch(train_generator, steps_per_epoch, learning_rate_schedule, keep_prob, l2_regularization,
                                 'Epoch {}/{}'.format(epoch, epochs), training_loss_display_averaging,
@@ -249,6 +262,8 @@ class FCN8s:
                         if self._improved(name, i):
                             self.best_metric_values[i] = self.metric_values[i]
         finally:
+            if custom_loss:
+                self.engine.set_loss(**(prev_loss or {}))
             for log in (train_log, eval_log):          # the event files are complete and closed when train() returns or raises
                 if log is not None:
                     log.close()

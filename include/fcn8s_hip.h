@@ -151,6 +151,31 @@ int fcn8s_bucket_wait(fcn8s_model* m, int bucket, void* hip_stream);
 int fcn8s_apply_update(fcn8s_model* m, int optimizer, float learning_rate, float grad_scale);   /* waits (stream-ordered) for pending fcn8s_allreduce_bucket calls */
 int fcn8s_read_loss(fcn8s_model* m, float* loss_out);                /* synchronises */
 
+/* ---- the training objective: class weights and online hard-example mining (OHEM) -----------------------------------------------
+ * The reference trains reduce_mean(softmax_cross_entropy); that stays the default.  Definitions, per rank (a data-parallel run
+ * selects on each rank's own batch; there is no cross-rank selection):
+ *   P = N*H*W pixels of the batch; V = the valid pixels, label id < C (ids >= C stay "ignore"); l_p = the fp32 per-pixel loss
+ *   m + logf(sum exp(v - m)) - v[y_p] (>= 0) exactly as the default kernel computes it; w_c = the class weights (finite, >= 0,
+ *   not all zero; default all 1).
+ * Weighted (ohem_thresh == 0): L = (1/P) sum_{p in V} w_{y_p} l_p -- denominator P as the reference's reduce_mean, not sum w, so
+ *   that data-parallel shards keep matching the big batch under grad_scale = 1/world; dlogits_p = (w_{y_p}/P)(softmax_p - onehot_p).
+ *   All weights 1 give the default's loss, dlogits and gradients bit for bit.
+ * OHEM (ohem_thresh in (0, 1], a probability as in HRNet): tau = (float)(-log((double)ohem_thresh)); k = min(ohem_min_kept, |V|);
+ *   t = min(tau, l_(k)) if k > 0, else tau, with l_(k) the k-th largest l_p over V (multiplicity counts); K = {p in V : l_p >= t}
+ *   (ties at t all kept, |K| >= k); L = sum_{p in K} w_{y_p} l_p / |K| (0 when K is empty); dlogits_p = (w_{y_p}/|K|)(softmax_p -
+ *   onehot_p) on K, 0 elsewhere.  The selection (a radix select over l_p's float bits) runs on the device: no host round trip.
+ * In both modes the L2 term is added as before.  The configuration applies to the training losses only (fcn8s_forward_loss,
+ * fcn8s_train_step); fcn8s_eval_step, the metrics and prediction keep the reference's loss.  It survives fcn8s_set_precision and
+ * fcn8s_set_option.  Its scratch (state, histograms, OHEM's l_p buffer of P floats) is allocated on first use and counted in
+ * "workspace_allocations"; deterministic = 1 keeps OHEM bit-reproducible (integer histograms, per-block loss partials).
+ * fcn8s_set_loss: class_weights = host float[nweights], nweights == num_classes, or NULL (all 1); ohem_thresh = 0 (off) or in
+ *   (0, 1]; ohem_min_kept >= 0.  NULL weights with ohem_thresh 0 restore the default.  FCN8S_ERR_BAD_ARG for a wrong length,
+ *   weights negative / not finite / all zero, a threshold outside {0} U (0, 1] or min_kept < 0.
+ * fcn8s_get_loss_stats: |V|, |K| and t of the last training loss (synchronises, like fcn8s_read_loss); in the weighted mode
+ *   kept = |V| and threshold = 0.  FCN8S_ERR_STATE when that loss ran without a configuration.                                   */
+int fcn8s_set_loss(fcn8s_model* m, const float* class_weights, int nweights, float ohem_thresh, int64_t ohem_min_kept);
+int fcn8s_get_loss_stats(fcn8s_model* m, int64_t* valid, int64_t* kept, float* threshold);
+
 /* ---- data parallelism inside the library: one RCCL rank per model (SURVEY section 7 step 7, 8b "RCCL error"; the reference is one
  * tf.Session on one device, fcn8s_tensorflow.py:65, so there is nothing to cite for the collective itself).  A caller that keeps the
  * reference's Python and binds this ABI gets multi-GPU training without torch.distributed:
@@ -419,6 +444,13 @@ int fcn8s_op_conv2d_transpose_bwd(void* stream, const float* x, const float* w_k
                                   int N, int Hi, int Wi, int C, int K, int S);
 int fcn8s_op_softmax_xent(void* stream, const float* logits, const uint8_t* label_ids, float* dlogits,
                           float* loss_out_dev, int64_t npix, int C);
+/* the weighted / OHEM loss of fcn8s_set_loss on plain [npix, C] logits (C <= 64), gradient scale 1/npix (weighted) or 1/|K| (OHEM).
+ * class_weights_dev: device float[C] or NULL (all 1; not checked).  With NULL weights and ohem_thresh 0 this is fcn8s_op_softmax_xent.
+ * pixel_loss_dev (OHEM only, may be NULL): float[npix], l_p of every valid pixel and -1 for an ignored one.  stats_dev (may be NULL;
+ * untouched in the default case): int64[3] = |V|, |K| (|V| when weighted), the float bit pattern of t (0 when weighted).  Synchronises. */
+int fcn8s_op_softmax_xent_ex(void* stream, const float* logits, const uint8_t* label_ids, const float* class_weights_dev,
+                             float ohem_thresh, int64_t ohem_min_kept, float* dlogits, float* loss_out_dev,
+                             float* pixel_loss_dev, int64_t* stats_dev, int64_t npix, int C);
 int fcn8s_op_softmax_argmax(void* stream, const float* logits, float* softmax_out, int64_t* argmax_out,
                             int64_t npix, int C);
 int fcn8s_op_confusion(void* stream, const uint8_t* label_ids, const int64_t* pred_ids, int64_t npix,
