@@ -284,6 +284,7 @@ void launch_wino_dfilter(int tile, const float* du, float* dw, int Cin, int Cout
 int fft_fc6_planes();
 long long fft_fc6_tiles(int N, int H, int W);
 void launch_fft_fc6_filter(const float* w, float* uf, int Cin, int Cout, hipStream_t s);                 // w[7][7][Cin][Cout] -> uf[292][Cin][Cout]
+void launch_fft_fc6_dfilter(const float* duf, float* dw, int Cin, int Cout, hipStream_t s);              // transpose of the filter transform: duf[292][Cin][Cout] -> dw[7][7][Cin][Cout]
 void launch_fft_fc6_input(const float* x, float* xf, int N, int H, int W, int C, hipStream_t s);          // x[N,H,W,C] -> xf[292][T][C]
 void launch_fft_fc6_output(const float* yf, const float* bias, float* y, int N, int H, int W, int C, int relu, int dropout, float keep,
                            unsigned long long seed, unsigned int stream_id, hipStream_t s);                 // yf[292][T][C] -> y[N,H,W,C] + epilogue

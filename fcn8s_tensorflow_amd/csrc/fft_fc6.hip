@@ -9,6 +9,7 @@
 //
 //   forward        : Uf = filter(w), Xf = input(x), Yf[p] = Xf[p] Uf[p] (GEMM over Cin), y = output(Yf) (+ bias, ReLU, dropout)
 //   data gradient  : dYf = output^T(dz), dXf[p] = dYf[p] Uf[p]^T (same bank, read transposed), dx = input^T(dXf)
+//   weight gradient: dUf[p] = Xf[p]^T dYf[p] (the forward's Xf, the data gradient's dYf), dw = filter^T(dUf)
 //
 // The adjoint transforms are the exact transposes of the forward ones (the inverse real DFT weighs every frequency that has a conjugate
 // partner twice; its transpose keeps that factor, the forward DFT of the input has none).  tools/fft_fc6_probe.py and
@@ -84,6 +85,58 @@ __global__ __launch_bounds__(256) void fft_fc6_filter_kernel(const float* __rest
             for (int b = 0; b < 7; ++b) g[a][b] = w[(a * 7 + b) * CC + e];
         filter_col<0>(g, uf, e, CC); filter_col<1>(g, uf, e, CC); filter_col<2>(g, uf, e, CC); filter_col<3>(g, uf, e, CC);
         filter_col<4>(g, uf, e, CC); filter_col<5>(g, uf, e, CC); filter_col<6>(g, uf, e, CC); filter_col<7>(g, uf, e, CC);
+    }
+}
+
+// ---- transpose of the filter transform: duf[292][Cin][Cout] -> dw[7][7][Cin][Cout] (weight gradient) ---------------------
+// Gauss stage: uf = (cr, ci - cr, cr + ci) -> dcr = d0 - d1 + d2, dci = d1 + d2; real planes pass through.  The filter transform is a plain
+// forward DFT (the conjugate-pair factor beta / 196 lives in the output transform, so dYf and hence dUf already carry it): no factor here.
+// Column V: dr[a] = sum_u dcr cos(u a) - dci sin(u a), di[a] = sum_u dcr sin(u a) + dci cos(u a); dg[6 - a][6 - b] += dr[a] cos(V b) - di[a] sin(V b).
+template <int V>
+__device__ __forceinline__ void dfilter_col(const float* __restrict__ duf, float (&dg)[7][7], long long e, long long CC)
+{
+    constexpr int NU = nu_of(V);
+    float R[NU], I[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        if (is_real(u, V)) { R[u] = duf[realp(u, V) * CC + e]; I[u] = 0.f; }
+        else {
+            const float* p = duf + 3LL * cplx(u, V) * CC + e;
+            const float d0 = p[0], d1 = p[CC], d2 = p[2 * CC];
+            R[u] = d0 - d1 + d2; I[u] = d1 + d2;
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 7; ++a) {
+        float dr = 0.f, di = 0.f;
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            if (is_real(u, V)) { dr = fmaf(R[u], c14(u * a), dr); di = fmaf(R[u], s14(u * a), di); }
+            else {
+                dr = fmaf(R[u], c14(u * a), fmaf(I[u], -s14(u * a), dr));
+                di = fmaf(R[u], s14(u * a), fmaf(I[u], c14(u * a), di));
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < 7; ++b) dg[6 - a][6 - b] = fmaf(dr, c14(V * b), fmaf(di, -s14(V * b), dg[6 - a][6 - b]));
+    }
+}
+// one lane per (ci, co), plain stores: every element of dw has one writer
+__global__ __launch_bounds__(256) void fft_fc6_dfilter_kernel(const float* __restrict__ duf, float* __restrict__ dw, long long CC)
+{
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < CC; e += (long long)gridDim.x * 256) {
+        float dg[7][7];
+#pragma unroll
+        for (int a = 0; a < 7; ++a)
+#pragma unroll
+            for (int b = 0; b < 7; ++b) dg[a][b] = 0.f;
+        dfilter_col<0>(duf, dg, e, CC); FFT_FENCE; dfilter_col<1>(duf, dg, e, CC); FFT_FENCE; dfilter_col<2>(duf, dg, e, CC); FFT_FENCE;
+        dfilter_col<3>(duf, dg, e, CC); FFT_FENCE; dfilter_col<4>(duf, dg, e, CC); FFT_FENCE; dfilter_col<5>(duf, dg, e, CC); FFT_FENCE;
+        dfilter_col<6>(duf, dg, e, CC); FFT_FENCE; dfilter_col<7>(duf, dg, e, CC);
+#pragma unroll
+        for (int a = 0; a < 7; ++a)
+#pragma unroll
+            for (int b = 0; b < 7; ++b) dw[(a * 7 + b) * CC + e] = dg[a][b];
     }
 }
 
@@ -375,6 +428,11 @@ void launch_fft_fc6_filter(const float* w, float* uf, int Cin, int Cout, hipStre
 {
     const long long CC = (long long)Cin * Cout;
     hipLaunchKernelGGL(fft_fc6_filter_kernel, dim3(grid_for(CC)), dim3(256), 0, s, w, uf, CC);
+}
+void launch_fft_fc6_dfilter(const float* duf, float* dw, int Cin, int Cout, hipStream_t s)
+{
+    const long long CC = (long long)Cin * Cout;
+    hipLaunchKernelGGL(fft_fc6_dfilter_kernel, dim3(grid_for(CC)), dim3(256), 0, s, duf, dw, CC);
 }
 void launch_fft_fc6_input(const float* x, float* xf, int N, int H, int W, int C, hipStream_t s)
 {

@@ -114,6 +114,9 @@ struct fcn8s_model {
     int wino_fc6 = 1;                                                     // fc6 7x7 as a 2x2 grid of 4x4 sub-filters in the Winograd domain
     int fc6_fft = 1;                                                      // ... and in the fp32 training step: forward + data gradient through 14x14 real-DFT tiles (fft_fc6.hip)
     std::string fft6_ready;                                               // the layer whose FFT bank (u_train "<layer>#fft") this forward pass built
+    int fc6_fft_wgrad = 1;                                                // ... and its weight gradient too: 1 = from fft6_wgrad_min_tiles tiles up, 2 = at any tile count, 0 = F(4x4,4x4)
+    std::string fft6_xf;                                                  // the layer whose DFT input bank Xf this forward pass kept (its "wv:" slot) for that weight gradient
+    std::string fft6_dyf;                                                 // the layer whose dYf the weight gradient left in d_wino_m for the data gradient
     int wino_tile_hires = 0, wino_hires_pixels = 0;                       // != 0: 3x3 layers on maps of at least wino_hires_pixels pixels (per image) use at most this tile
     int wino_force_tile = 0;                                              // != 0: every eligible 3x3 layer uses exactly this tile (op-level parity entry point)
     int precision = FCN8S_PREC_F32;                                       // FCN8S_PREC_BF16_FC: forward fc6 / fc7 on the bf16 MFMA
@@ -425,6 +428,13 @@ static bool fft6_on(const fcn8s_model* m, int N, int H, int W, int ci, int co)
     return v != m->acts.end() && mm != m->acts.end() && v->second.n >= (size_t)fft_fc6_planes() * (size_t)wino_slab(T, std::min(ci, co)) &&
            mm->second.n >= std::max((size_t)fft_fc6_planes() * (size_t)wino_slab(T, std::max(ci, co)), (size_t)T * 196 * std::min(ci, co));
 }
+// The weight gradient in the DFT domain (dUf[p] = Xf[p]^T dYf[p], dW = filter^T(dUf)) multiplies 4.56 times per tile position and channel pair
+// against F(4x4,4x4)'s 12.25, but writes and reads a 292-plane bank of Cin x Cout (2.45 GB at 512 -> 4096) where F(4x4,4x4) has 196 planes:
+// a fixed cost per step that only enough tiles pay for.  Both costs scale with Cin x Cout, so the rule is a tile count.  Measured at 1024x512,
+// 512 -> 4096 (tools/layer_bench.py, whole step, DFT against F(4x4,4x4); profiles/r07_fc6_wgrad_tile_sweep.txt): T = 8 (one image) +0.24 ms,
+// T = 16 +0.04 ms, T = 32 -0.08 ms, T = 64 -0.65 ms, T = 128 (the bench shape) -0.8 ms.
+constexpr long long kFft6WgradMinTiles = 32;
+static bool fft6_wgrad_wanted(const fcn8s_model* m, long long T) { return m->fc6_fft_wgrad == 2 || (m->fc6_fft_wgrad == 1 && T >= kFft6WgradMinTiles); }
 // the plane GEMMs: [T x K] x [K x Nc] per plane, 128-row tiles and no split-K whatever the batch (a DP shard computes the big batch's bits)
 static IgemmArgs fft6_gemm(const float* x, const float* w, float* y, long long T, int K, int Nc)
 {
@@ -447,18 +457,42 @@ static bool conv_fft6_fwd(fcn8s_model* m, const char* layer, const float* x, con
     const long long T = fft_fc6_tiles(N, H, W);
     float*& uf = m->u_train[std::string(layer) + "#fft"];
     if (!uf && hipMalloc((void**)&uf, (size_t)P * Cin * Cout * sizeof(float)) != hipSuccess) { uf = nullptr; (void)hipGetLastError(); return false; }
-    auto wv = m->acts.find(std::string("wv:") + layer);      // the F(4x4,4x4) weight gradient's V of the input
-    const bool want_v = wv != m->acts.end() && wino_tile_for(m, H, W, 7) == 4;
+    auto wv = m->acts.find(std::string("wv:") + layer);      // the weight gradient's input operand: Xf (DFT domain) or V of F(4x4,4x4)
+    // the DFT-domain weight gradient reads this pass's Xf: kept in the layer's own slot, which nothing else writes before the backward pass
+    const bool dft_wgrad = wv != m->acts.end() && fft6_wgrad_wanted(m, T) && wv->second.n >= (size_t)P * (size_t)wino_slab(T, Cin) &&
+                           m->ufl >= (size_t)P * Cin * Cout;
+    const bool want_v = !dft_wgrad && wv != m->acts.end() && wino_tile_for(m, H, W, 7) == 4;
+    float* xf = dft_wgrad ? wv->second.p : m->d_wino_v;
     { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((49.0 + P) * Cin * Cout + (double)N * H * W * Cin + (double)P * T * Cin));
-      launch_fft_fc6_filter(w, uf, Cin, Cout, s); launch_fft_fc6_input(x, m->d_wino_v, N, H, W, Cin, s); }
+      launch_fft_fc6_filter(w, uf, Cin, Cout, s); launch_fft_fc6_input(x, xf, N, H, W, Cin, s); }
     if (want_v) { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cin * 4 + 49.0 * wino_tiles(4, N, H, W) * 4 * Cin));
                   launch_wino_input(4, x, wv->second.p, N, H, W, Cin, 7, s); }
-    const IgemmArgs a = fft6_gemm(m->d_wino_v, uf, m->d_wino_m, T, Cin, Cout);
+    const IgemmArgs a = fft6_gemm(xf, uf, m->d_wino_m, T, Cin, Cout);
     { ProfScope ps(m, "fc6_fft_gemm_fwd", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
     { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)P * T * Cout + (double)N * H * W * Cout));
       launch_fft_fc6_output(m->d_wino_m, bias, y, N, H, W, Cout, relu, dropout, keep, m->seed, stream_id, s); }
     m->fft6_ready = layer;
+    if (dft_wgrad) m->fft6_xf = layer;
     return true;
+}
+// weight gradient (Cin / Cout: channels of the forward conv): dYf = output^T(dz) into d_wino_m, where the data gradient then finds it;
+// dUf[p] = Xf[p]^T dYf[p] over the T tiles (292 planes, one K-slab: every element of dUf has one writer, plain stores); dW = filter^T(dUf);
+// the bias gradient is the column sum of dz
+static void conv_fft6_wgrad(fcn8s_model* m, const char* layer, const float* xf, const float* dz, float* dw, float* db, int N, int H, int W, int Cin, int Cout, hipStream_t s)
+{
+    const int P = fft_fc6_planes();
+    const long long T = fft_fc6_tiles(N, H, W);
+    { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)N * H * W * Cout + (double)P * T * Cout)); launch_fft_fc6_dout(dz, m->d_wino_m, N, H, W, Cout, s); }
+    m->fft6_dyf = layer;
+    WgradArgs g{}; g.split = 0;
+    g.A = xf; g.B = m->d_wino_m; g.C = m->d_wino_u;
+    g.N = 1; g.Pa = 1; g.Pb = (int)T; g.P = T;
+    g.Ha = 1; g.Wa = (int)T; g.Adim = Cin; g.lda = Cin; g.Areal = Cin;
+    g.Bdim = Cout; g.ldb = Cout; g.KW = 1; g.a_scale = 1; g.tap_off = 0; g.ntaps = P; g.ldc = Cout; g.alpha = 1.f; g.colsum = nullptr;
+    g.batched = 1; g.a_batch_stride = wino_slab(T, Cin); g.b_batch_stride = wino_slab(T, Cout); g.c_uninitialized = 1;
+    { ProfScope ps(m, "fc6_fft_gemm_wgrad", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_wgrad(g, s); }
+    { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * (P + 49.0) * Cin * Cout); launch_fft_fc6_dfilter(m->d_wino_u, dw, Cin, Cout, s); }
+    if (db) { ProfScope ps(m, "colsum", 0, 4.0 * N * H * W * Cout); launch_colsum(dz, db, (long long)N * H * W, Cout, s); }
 }
 // data gradient (Cin = channels of dz, Cout = channels of dx): dYf = output^T(dz), dXf[p] = dYf[p] Uf[p]^T with this step's bank read
 // transposed, dx = input^T(dXf) (patch gradients, then the overlap-add gather)
@@ -466,7 +500,8 @@ static void conv_fft6_dgrad(fcn8s_model* m, const char* layer, const float* dz, 
 {
     const int P = fft_fc6_planes();
     const long long T = fft_fc6_tiles(N, H, W);
-    { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)N * H * W * Cin + (double)P * T * Cin)); launch_fft_fc6_dout(dz, m->d_wino_m, N, H, W, Cin, s); }
+    if (m->fft6_dyf != layer) { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)N * H * W * Cin + (double)P * T * Cin)); launch_fft_fc6_dout(dz, m->d_wino_m, N, H, W, Cin, s); }
+    m->fft6_dyf.clear();        // (else the weight gradient just wrote dYf of this dz into d_wino_m)
     IgemmArgs a = fft6_gemm(m->d_wino_m, uf, m->d_wino_v, T, Cin, Cout);
     a.bt = 1; a.ldw = Cin;
     { ProfScope ps(m, "fc6_fft_gemm_dgrad", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
@@ -794,9 +829,17 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
     if (bf16_train_mode(m) && m->train_mode && layer && (m->in_bf16_only.count(layer) || m->dy_bf16_only.count(layer))) {
         defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's weight gradient could not run on the bf16 kernel and its fp32 input was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return;
     }
+    if (m && K == 7 && layer && alpha == 1.f && !real_cin && m->train_mode && !m->fft6_xf.empty() && m->fft6_xf == layer) {
+        m->fft6_xf.clear();                                    // weight gradient in the DFT domain (Xf kept by the forward pass)
+        if (promised) broken_promise();
+        m->dm_layer.clear(); m->fused_v_layer.clear();
+        conv_fft6_wgrad(m, layer, m->acts[std::string("wv:") + layer].p, dz, dw, db, N, H, W, Cin, Cout, s);
+        return;
+    }
     if (m && (K == 3 || K == 7) && layer && alpha == 1.f && !real_cin && m->train_mode) {
         auto it = m->acts.find(std::string("wv:") + layer);
-        if (it != m->acts.end() && m->d_wino_m) {             // weight gradient in the Winograd domain (V kept by the forward pass)
+        // (fc6's slot also exists on maps that only the DFT tiles cover, e.g. 10x13: no F(4x4,4x4) tile there)
+        if (it != m->acts.end() && m->d_wino_m && (K == 3 || wino_tile_for(m, H, W, 7) == 4)) {             // weight gradient in the Winograd domain (V kept by the forward pass)
             const int tile = wino_tile_for(m, H, W, K), NP = wino_alpha(tile, K) * wino_alpha(tile, K);
             const long long T = wino_tiles(tile, N, H, W);
             const int Kg = wino_nsub(K) * wino_nsub(K) * Cin;           // rows of V / dU: [sub-filter][channel]
@@ -987,7 +1030,11 @@ void plan_workspace(fcn8s_model* m, int N, int H, int W, WsPlan& pl)
                     }
                     cin = m->widths[b];
                 }
-            if (fc6w) items.push_back({"wv:fc6", slab_floats(h5_, w5_, m->widths[4], 7), 0, 0, 0, nullptr});
+            // fc6's slot holds V of F(4x4,4x4) or, when the weight gradient runs in the DFT domain, Xf: sized for either
+            size_t v6 = fc6w ? slab_floats(h5_, w5_, m->widths[4], 7) : 0;
+            if (fft6_shape_ok(m, m->widths[4], m->widths[5]) && fft6_cheaper(m, h5_, w5_) && fft6_wgrad_wanted(m, fft_fc6_tiles(N, h5_, w5_)))
+                v6 = std::max(v6, (size_t)fft_fc6_planes() * (size_t)wino_slab(fft_fc6_tiles(N, h5_, w5_), m->widths[4]));
+            if (v6) items.push_back({"wv:fc6", v6, 0, 0, 0, nullptr});
         }
     }
 
@@ -1350,7 +1397,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
     const bool fill_fp = m->frozen && (m->u_cache.empty() || m->banks_stale);       // (banks_stale: kept storage, contents to be rebuilt)
     if (!m->frozen || fill_fp) prepare_forward_weights(m);        // frozen and the kept banks still valid: so are the padded / phase-packed kernels
     m->fwd_train = train;
-    m->fft6_ready.clear();
+    m->fft6_ready.clear(); m->fft6_xf.clear(); m->fft6_dyf.clear();
     // bf16_train, evaluation / prediction (round 6): the pass takes the TRAINING pass's data flow -- every layer's input as a padded bf16 copy written by its
     // producer's epilogue (no fp32 conv -> conv tensor, no conversion pass), the flat-position kernel, pools on the bf16 copies -- instead of fp32 tensors converted
     // layer by layer for the tile kernel: 13.3 -> 9.3 ms per 16 x 1024x512 batch, 1.55 -> 1.18 ms per single image (profiles/r06_bf16_infer.txt).  Same products in the same order as the training pass:
@@ -1913,6 +1960,8 @@ int fcn8s_create(const fcn8s_config* cfg, fcn8s_model** out)
         int cmax = 0; for (int i = 0; i < 5; ++i) cmax = std::max(cmax, m->widths[i]);
         size_t ufl = 64 * (size_t)cmax * cmax;                        // F(6x6,3x3): 64 positions
         if (m->fc6k == 7) ufl = std::max(ufl, 49 * 4 * (size_t)m->widths[4] * m->widths[5]);   // fc6: 49 positions x 4 sub-filters
+        // ... or the 292 planes of its DFT-domain weight gradient (dUf; +0.8 GB at 512 -> 4096)
+        if (m->fc6k == 7 && m->widths[4] % 16 == 0 && m->widths[5] % 128 == 0) ufl = std::max(ufl, (size_t)fft_fc6_planes() * m->widths[4] * m->widths[5]);
         if ((e = hipMalloc((void**)&m->d_wino_u, ufl * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
         m->ufl = ufl;
     }
@@ -2065,6 +2114,7 @@ static int* model_option(fcn8s_model* m, const std::string& key)
     if (key == "winograd_tile") return &m->wino_tile;
     if (key == "winograd_fc6") return &m->wino_fc6;
     if (key == "fc6_fft") return &m->fc6_fft;
+    if (key == "fc6_fft_wgrad") return &m->fc6_fft_wgrad;
     if (key == "tconv_gemm") return &m->tconv_gemm;
     if (key == "fuse_dgrad_dout") return &m->fuse_dgrad_dout;
     if (key == "fuse_out_in") return &m->fuse_out_in;
@@ -2120,6 +2170,7 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
     if (k == "winograd_tile_hires" && value != 0 && value != 2 && value != 4 && value != 6) return fail(m, FCN8S_ERR_BAD_ARG, "winograd_tile_hires must be 0, 2, 4 or 6");
     if (k == "winograd_min_cin" && value < 0) return fail(m, FCN8S_ERR_BAD_ARG, "winograd_min_cin must be >= 0 (0 = direct convolution everywhere)");
     if (k == "fuse_out_in" && (value < 0 || value > 2)) return fail(m, FCN8S_ERR_BAD_ARG, "fuse_out_in must be 0, 1 or 2");
+    if (k == "fc6_fft_wgrad" && (value < 0 || value > 2)) return fail(m, FCN8S_ERR_BAD_ARG, "fc6_fft_wgrad must be 0, 1 or 2");
     if (*slot == (int)value) return FCN8S_OK;
     HIPCHK(m, hipStreamSynchronize(m->stream));
     *slot = (k == "winograd_fc6" || k == "fc6_fft" || k == "tconv_gemm") ? (value != 0) : (int)value;

@@ -396,7 +396,7 @@ class Engine:
         L.check(L.lib.fcn8s_freeze_params(self.h, 1 if frozen else 0), self.h)
 
     def set_option(self, key, value):
-        """fcn8s_set_option: 'winograd_min_cin', 'winograd_tile', 'winograd_fc6', 'fc6_fft', 'tconv_gemm' (defaults = the measured winners)."""
+        """fcn8s_set_option: 'winograd_min_cin', 'winograd_tile', 'winograd_fc6', 'fc6_fft', 'fc6_fft_wgrad', 'tconv_gemm' (defaults = the measured winners)."""
         L.check(L.lib.fcn8s_set_option(self.h, key.encode(), int(value)), self.h)
 
     def get_option(self, key):

@@ -291,6 +291,8 @@ int fcn8s_get_precision(const fcn8s_model* m);
  *     "winograd_fc6"      1    fc6 as a 2x2 grid of 4x4 sub-filters through F(4x4,4x4); 0 = direct 7x7
  *     "fc6_fft"           1    (with winograd_fc6) fc6's forward + data gradient in the fp32 training step of an unfrozen model through 14x14
  *                              real-DFT tiles, 292 GEMM planes (fft_fc6.hip); 0 = F(4x4,4x4) there too
+ *     "fc6_fft_wgrad"     1    (with fc6_fft) fc6's weight gradient in the same DFT domain when the step has at least 32 tiles of 8x8 (batch 4 at
+ *                              1024x512); 2 = at any tile count; 0 = F(4x4,4x4)
  *     "tconv_gemm"        1    the 16x16/8 transposed conv as one GEMM over output blocks (blocked logits); 0 = 64 sub-pixel phases
  *     "fuse_dgrad_dout"   1    inside a VGG block the gather kernel of a conv's data gradient writes dM = A dZ A^T of the previous conv directly
  *                              (that conv's weight gradient and adjoint data gradient consume only dM): its dZ is never written; 0 = two kernels
