@@ -19,6 +19,8 @@ MAX_BUCKETS = 8          # the number of gradient buckets is a run-time value: l
 COMM_ID_BYTES = 128
 NUM_STAGE_SLOTS = 3
 PREC_F32, PREC_BF16_FC, PREC_F32X3, PREC_BF16_FWD, PREC_F32X2, PREC_BF16_FWD_X2, PREC_BF16_TRAIN = 0, 1, 2, 3, 4, 5, 6
+PREC_FP8_INFER = 7
+FP8_LAYERS = 14   # inputs of conv1_2 .. conv5_3, fc6, fc7, in that order
 
 
 class Config(C.Structure):
@@ -89,6 +91,9 @@ SIGNATURES = {
     "fcn8s_freeze_params": (_i, [_p, _i]),
     "fcn8s_set_precision": (_i, [_p, _i]),
     "fcn8s_get_precision": (_i, [_p]),
+    "fcn8s_fp8_calibrate": (_i, [_p, _p, _i, _i, _i, _i, _i, _i]),
+    "fcn8s_fp8_get_calibration": (_i, [_p, _fp, _i]),
+    "fcn8s_fp8_set_calibration": (_i, [_p, _fp, _i]),
     "fcn8s_set_option": (_i, [_p, C.c_char_p, _i64]),
     "fcn8s_get_option": (_i, [_p, C.c_char_p, _i64p]),
     "fcn8s_get_activation": (_i, [_p, C.c_char_p, _p, _sz]),
@@ -110,6 +115,7 @@ SIGNATURES = {
     "fcn8s_op_conv3x3_winograd_fwd_bwd": (_i, [_p] * 11 + [_i] * 8),
     "fcn8s_op_conv2d_bf16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i]),
     "fcn8s_op_conv2d_bf16_train": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i]),
+    "fcn8s_op_conv2d_fp8": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i]),
     "fcn8s_op_conv2d_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i]),
     "fcn8s_op_maxpool2x2": (_i, [_p, _p, _p, _i, _i, _i, _i]),
     "fcn8s_op_maxpool2x2_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i]),

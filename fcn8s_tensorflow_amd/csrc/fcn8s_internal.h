@@ -100,6 +100,24 @@ void launch_w_to_bf16_t(const float* w, unsigned short* wt, int K, int Cout, hip
 void launch_f32_to_bf16_padded(const float* x, unsigned short* xp, int N, int H, int W, int C, int pad, hipStream_t s, long long ps = 0);      // ps: plane stride of xp in elements, 0 = [rows][C]
 int conv_bf16_rows_bm(int Cout, int rows_bn);      // positions per row tile (= per partial row of `colpart`) of the form launch_conv_bf16_256 picks
 bool launch_conv_bf16_256(const Bf16Conv256Args& a, hipStream_t s);
+// FCN8S_PREC_FP8_INFER (gemm_fp8.hip): e4m3 convolution on the MX MFMA.  xp: padded e4m3 copy of the input, pixel 0 of plane 0, 64-channel planes
+// xp_ps bytes apart (pad (K - 1) / 2); wq: [K K Cin / 64][Cout][64] e4m3 with per-column exponents ew; y = 2^(ex + ew) sum Xq Wq + bias (ReLU).
+// y (fp32 [M][Cout]) and / or yq (the consumer's padded copy: pad yq_pad, planes yq_ps bytes apart, q(y 2^-yq_exp)) may be NULL.  Cin, Cout % 64 == 0.
+struct Fp8ConvArgs {
+    const unsigned char* xp = nullptr; long long xp_ps = 0;
+    const unsigned char* wq = nullptr; const int* ew = nullptr;
+    const float* bias = nullptr; float* y = nullptr;
+    unsigned char* yq = nullptr; long long yq_ps = 0; int yq_pad = 0, yq_exp = 0;
+    int ex = 0, relu = 1;
+    int N = 0, H = 0, W = 0, Cin = 0, Cout = 0, K = 1;
+    long long M = 0;
+};
+bool launch_conv_fp8(const Fp8ConvArgs& a, hipStream_t s);
+void launch_w_to_fp8(const float* w, unsigned char* wq, int* ew, unsigned* amax_scratch, int rows, int Cout, hipStream_t s);
+void launch_f32_to_fp8_padded(const float* x, unsigned char* xq, int N, int H, int W, int C, int pad, long long ps, int ex, hipStream_t s);
+void launch_zero_border_fp8(unsigned char* xq, int planes, long long ps, int N, int H, int W, int pad, hipStream_t s);
+void launch_maxpool_fp8(const unsigned char* xq, long long xps, unsigned char* yq, long long yps, int N, int H, int W, int C, int ypad, hipStream_t s);
+void launch_amax(const float* x, long long n, unsigned* amax, hipStream_t s);
 // the padded bf16 copy of an output gradient (interior only: the border of xp is zero already) with db[c] += column sums of x on the way
 bool launch_f32_to_bf16_padded_colsum(const float* x, unsigned short* xp, float* db, int N, int H, int W, int C, int pad, hipStream_t s, long long ps = 0);
 // the kernel of a SAME convolution's data gradient as conv_bf16_256_kernel wants it: wt[Cin][(flipped taps, Cout)] bf16 (Cout % 8 == 0)

@@ -81,6 +81,11 @@ int take_deferred_error(std::string* text)
 }
 }  // namespace fcn8s
 
+// FCN8S_PREC_FP8_INFER: a layer's padded e4m3 input copy (64-channel planes ps bytes apart; the border is zeroed whenever the geometry changes) with the
+// exponent its codes carry, and a layer's quantized weight bank (planes [K K Cin / 64][Cout][64], per-column exponents, the amax scratch behind them)
+struct Q8Buf { unsigned char* p = nullptr; size_t bytes = 0; int N = 0, H = 0, W = 0, C = 0, pad = -1, ex = 0; long long ps = 0; };
+struct W8Bank { unsigned char* wq = nullptr; int* ew = nullptr; unsigned* amax = nullptr; size_t bytes = 0; };
+
 struct fcn8s_model {
     int C = 20, fc6k = 7, device = 0;
     int widths[7] = {64, 128, 256, 512, 512, 4096, 4096};
@@ -163,6 +168,11 @@ struct fcn8s_model {
     int bf16_infer_copies = 1;                                            // option: bf16_train's evaluation / prediction passes take the training pass's data flow (see forward())
     int bf16_rows_bn = 0;                                                 // option (A/B): 128 = the flat-position bf16 convolution takes its 128-column tile where it can (default: 64 columns)
     int bf16_acts = 1;                                                    // option: bf16_train training passes keep a conv -> conv activation only as the consumer's padded bf16 copy (the producer's epilogue writes it; no fp32 tensor, no conversion pass)
+    // FCN8S_PREC_FP8_INFER: the calibration (per FP8 layer the max |input| of the fp32 pass; it describes the parameters, not the mode), the device scratch of
+    // fcn8s_fp8_calibrate, the e4m3 copies (kept with the workspace) and the weight banks (valid across passes only while frozen: w8_valid)
+    bool fp8_calibrated = false, fp8_calibrating = false; float fp8_amax[FCN8S_FP8_LAYERS] = {}; unsigned* d_fp8_amax = nullptr;
+    std::map<std::string, Q8Buf> q8; std::set<std::string> q8_filled;
+    std::map<std::string, W8Bank> w8; std::set<std::string> w8_valid;
     int saved_wino_min_cin = -1, saved_wino_fc6 = -1;                      // the options the mode overrides (the direct path carries it), restored on leaving
     int bf16_copy_by_transform = 1;                                       // option: 0 = every bf16 layer converts its input with a pass of its own (round 3's path)
     std::set<std::string> g16_stale;                                      // bf16_train copies ("x:<layer>" / "d:<layer>") whose zero border belongs to another shape (fcn8s_predict_tta re-plans)
@@ -1076,6 +1086,8 @@ int ensure_workspace(fcn8s_model* m, int N, int H, int W)
     m->xg16.clear(); m->xg16_elems.clear();
     for (auto& kv : m->dyg16) if (kv.second) hipFree(kv.second);
     m->dyg16.clear(); m->dyg16_elems.clear(); m->xg16_filled.clear(); m->dyg16_filled.clear(); m->g16_stale.clear();
+    for (auto& kv : m->q8) if (kv.second.p) hipFree(kv.second.p);
+    m->q8.clear(); m->q8_filled.clear();
     m->acts.clear();
     m->have_forward = m->have_loss = false;
     WsPlan pl;
@@ -1361,6 +1373,125 @@ void wino_backward_operands(fcn8s_model* m, const char* layer, const float* x, c
     }
 }
 
+// ---- FCN8S_PREC_FP8_INFER ------------------------------------------------------------------------------------------------------------------------
+static inline bool fp8_mode(const fcn8s_model* m) { return m && m->precision == FCN8S_PREC_FP8_INFER; }
+// the modes that ride on the direct path (winograd_min_cin = 0, winograd_fc6 = 0 while they are on)
+static inline bool direct_mode(int precision) { return precision == FCN8S_PREC_BF16_TRAIN || precision == FCN8S_PREC_FP8_INFER; }
+const char* const kFp8Layers[FCN8S_FP8_LAYERS] = {"conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3",
+                                                  "conv5_1", "conv5_2", "conv5_3", "fc6", "fc7"};
+// the fp32 tensor that is layer L's input, its map's down-sampling factor and width index
+const char* const kFp8Inputs[FCN8S_FP8_LAYERS] = {"conv1_1", "pool1", "conv2_1", "pool2", "conv3_1", "conv3_2", "pool3", "conv4_1", "conv4_2", "pool4",
+                                                  "conv5_1", "conv5_2", "pool5", "fc6"};
+const int kFp8InDiv[FCN8S_FP8_LAYERS] = {1, 2, 2, 4, 4, 4, 8, 8, 8, 16, 16, 16, 32, 32};
+const int kFp8InWidth[FCN8S_FP8_LAYERS] = {0, 0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4, 5};
+static int fp8_layer(const char* name)
+{
+    for (int i = 0; i < FCN8S_FP8_LAYERS; ++i) if (!strcmp(name, kFp8Layers[i])) return i;
+    return -1;
+}
+// E(a): the smallest integer e with a <= 448 2^e; E(0) = 0
+static int fp8_exponent_host(float a)
+{
+    if (!(a > 0.f)) return 0;
+    int e = ilogb((double)a) - 8;
+    while ((double)a > ldexp(448.0, e)) ++e;
+    while ((double)a <= ldexp(448.0, e - 1)) --e;
+    return e;
+}
+static int fp8_ex(const fcn8s_model* m, const char* layer) { return fp8_exponent_host(m->fp8_amax[fp8_layer(layer)]); }
+// parameters changed: the calibration no longer describes them
+static void fp8_clear_calibration(fcn8s_model* m) { if (m) m->fp8_calibrated = false; }
+static int fp8_refuse_training(fcn8s_model* m, const char* who)
+{
+    return fail(m, FCN8S_ERR_STATE, std::string(who) + ": the fp8_infer precision is inference only (evaluation, prediction); switch to another precision with "
+                                    "fcn8s_set_precision to train");
+}
+// the e4m3 copies a pass uses: key, channels, consumer kernel size, down-sampling of the map (the 14 layer inputs and the copies the pools of blocks 1, 2, 5 read)
+struct Q8Spec { std::string key; int C, K, div; };
+static std::vector<Q8Spec> q8_specs(const fcn8s_model* m)
+{
+    std::vector<Q8Spec> v;
+    for (int L = 0; L < FCN8S_FP8_LAYERS; ++L) v.push_back({kFp8Layers[L], m->widths[kFp8InWidth[L]], L == 12 ? m->fc6k : (L == 13 ? 1 : 3), kFp8InDiv[L]});
+    v.push_back({"pool1in", m->widths[0], 3, 1}); v.push_back({"pool2in", m->widths[1], 3, 2}); v.push_back({"pool5in", m->widths[4], 3, 16});
+    return v;
+}
+static size_t q8_bytes(int N, int H, int W, int C, int K) { const int pad = (K - 1) / 2; return (size_t)N * (H + 2 * pad) * (W + 2 * pad) * C; }
+// copy `key` holds at least `bytes` (grown, never shrunk; a new buffer gets its border from the next q8_for)
+static bool q8_grow(fcn8s_model* m, const std::string& key, size_t bytes, hipStream_t s)
+{
+    Q8Buf& b = m->q8[key];
+    if (b.p && b.bytes >= bytes) return true;
+    if (b.p) { hipStreamSynchronize(s); hipFree(b.p); b.p = nullptr; b.bytes = 0; }
+    if (hipMalloc((void**)&b.p, bytes) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return false; }
+    ++m->ws_allocs; b.bytes = bytes; b.pad = -1;
+    return true;
+}
+// the padded e4m3 copy `key` for a K x K consumer on an H x W map of C channels, codes with exponent ex (nullptr: out of memory).  The producer writes every
+// interior position in every pass; when the geometry changes (another shape, a multi-scale pass) only the border of the new geometry is zeroed -- repeated
+// passes of one shape allocate and clear nothing.
+static Q8Buf* q8_for(fcn8s_model* m, const std::string& key, int N, int H, int W, int C, int K, int ex, hipStream_t s)
+{
+    const int pad = (K - 1) / 2;
+    if (!q8_grow(m, key, q8_bytes(N, H, W, C, K), s)) return nullptr;
+    Q8Buf& b = m->q8[key];
+    const long long R = (long long)N * (H + 2 * pad) * (W + 2 * pad);
+    if (b.N != N || b.H != H || b.W != W || b.C != C || b.pad != pad) {
+        launch_zero_border_fp8(b.p, C / 64, R * 64, N, H, W, pad, s);
+        b.N = N; b.H = H; b.W = W; b.C = C; b.pad = pad;
+    }
+    b.ps = R * 64; b.ex = ex;
+    return &b;
+}
+// a layer's quantized weight bank: rebuilt in every pass of a model that is not frozen, once while it is
+static const W8Bank* w8_for(fcn8s_model* m, const char* layer, const char* wname, int KK, int Cin, int Cout, hipStream_t s)
+{
+    W8Bank& b = m->w8[layer];
+    const size_t wbytes = (size_t)KK * Cin * Cout, need = wbytes + 8 * (size_t)Cout;
+    if (!b.wq || b.bytes < need) {
+        if (b.wq) { hipStreamSynchronize(s); hipFree(b.wq); b.wq = nullptr; b.bytes = 0; }
+        if (hipMalloc((void**)&b.wq, need) != hipSuccess) { (void)hipGetLastError(); b.wq = nullptr; return nullptr; }
+        ++m->ws_allocs; b.bytes = need; m->w8_valid.erase(layer);
+        b.ew = reinterpret_cast<int*>(b.wq + wbytes); b.amax = reinterpret_cast<unsigned*>(b.wq + wbytes + 4 * (size_t)Cout);
+    }
+    if (!(m->frozen && m->w8_valid.count(layer))) {
+        ProfScope ps(m, "fp8_quantize_w", 0, 8.0 * wbytes + (double)wbytes, layer);
+        launch_w_to_fp8(Wp(m, wname), b.wq, b.ew, b.amax, KK * Cin, Cout, s);
+        if (m->frozen) m->w8_valid.insert(layer);
+    }
+    return &b;
+}
+// one FP8 convolution: the input copy of `layer` (written by its producer in this pass, or converted here from the fp32 tensor x), output as fp32 y and / or
+// into the consumer's copy yq (codes with yq->ex)
+static int fp8_conv(fcn8s_model* m, const char* group, const char* layer, const float* x, int N, int H, int W, int Cin, int Cout, int K,
+                    float* y, const Q8Buf* yq, int yq_pad, hipStream_t s)
+{
+    const int Lx = fp8_layer(layer);
+    const std::string ln(layer);
+    const bool fc = ln == "fc6" || ln == "fc7";
+    const std::string wname = ln + (fc ? "/weights" : "/filter"), bname = ln + "/biases";
+    const int ex = fp8_ex(m, layer);
+    Q8Buf* xq = q8_for(m, ln, N, H, W, Cin, K, ex, s);
+    if (!xq) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of " + ln + "'s e4m3 input copy failed");
+    if (!m->q8_filled.count(ln)) {
+        // the fp32 input must have been written by this pass (conv1_1, pool3, pool4): never quantize a stale buffer
+        if (Lx < 0 || m->y_unwritten.count(kFp8Inputs[Lx]))
+            return fail(m, FCN8S_ERR_STATE, "fp8_infer: " + ln + "'s fp32 input " + (Lx < 0 ? std::string("?") : std::string(kFp8Inputs[Lx])) + " was not written by this pass");
+        ProfScope ps(m, "fp8_quantize_x", 0, 5.0 * N * H * W * Cin);
+        launch_f32_to_fp8_padded(x, xq->p, N, H, W, Cin, (K - 1) / 2, xq->ps, ex, s);
+        m->q8_filled.insert(ln);
+    }
+    const W8Bank* wb = w8_for(m, layer, wname.c_str(), K * K, Cin, Cout, s);
+    if (!wb) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of " + ln + "'s e4m3 weight bank failed");
+    Fp8ConvArgs a;
+    a.xp = xq->p; a.xp_ps = xq->ps; a.wq = wb->wq; a.ew = wb->ew; a.bias = Wp(m, bname); a.y = y;
+    if (yq) { a.yq = yq->p; a.yq_ps = yq->ps; a.yq_pad = yq_pad; a.yq_exp = yq->ex; }
+    a.ex = ex; a.relu = 1; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.K = K; a.M = (long long)N * H * W;
+    const double M = (double)a.M;
+    ProfScope ps(m, group, 2.0 * M * K * K * Cin * Cout, M * Cin + (y ? 4.0 : 0.0) * M * Cout + (yq ? 1.0 : 0.0) * M * Cout + (double)K * K * Cin * Cout, layer);
+    if (!launch_conv_fp8(a, s)) return fail(m, FCN8S_ERR_SHAPE, "fp8_infer: " + ln + " does not fit the e4m3 convolution kernel");
+    return FCN8S_OK;
+}
+
 int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, bool train)
 {
     t_deterministic = m->deterministic;
@@ -1374,6 +1505,12 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
     };
     hipStream_t s = m->stream;
     const int N = m->N, H = m->H, W = m->W, C = m->C;
+    // FCN8S_PREC_FP8_INFER: evaluation / prediction through the e4m3 kernels; the calibration pass (fcn8s_fp8_calibrate) is the fp32 direct path
+    const bool fp8 = fp8_mode(m) && !train && !m->fp8_calibrating;
+    if (fp8 && !m->fp8_calibrated)
+        return fail(m, FCN8S_ERR_STATE, "fp8_infer: the model has no FP8 calibration (never calibrated, or its parameters changed since): run fcn8s_fp8_calibrate "
+                                        "(Engine.calibrate_fp8 / FCN8s.calibrate_fp8) or restore one with fcn8s_fp8_set_calibration first");
+    if (fp8) m->q8_filled.clear();
     bool guard_pending = false;
     if (m->frozen && !m->u_cache.empty() && !m->banks_stale) {
         // the caller promised constant parameters; a cheap strided fingerprint catches the promise being broken through a side
@@ -1431,7 +1568,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                 e.skip_y = !train || pool_backward_fused(m, b + 1, true);
             }
             char nxt[32] = "";
-            if (m->fuse_out_in && !first && i < kConvsPerBlock[b] && !(bf16_fwd_mode(m) && b >= 2) && !bf16_train_mode(m) && (!train || e.relu_bits_out) &&
+            if (m->fuse_out_in && !first && i < kConvsPerBlock[b] && !(bf16_fwd_mode(m) && b >= 2) && !bf16_train_mode(m) && !fp8_mode(m) && (!train || e.relu_bits_out) &&
                 m->wino_min_cin > 0 && cin >= m->wino_min_cin && m->widths[b] >= m->wino_min_cin && m->widths[b] % 64 == 0 && cin % 16 == 0 &&
                 m->d_wino_v && wino_tile_for(m, h, w, 3) == 6) {
                 // this conv and the next one both run through F(6x6,3x3) on the same tile grid: its output transform writes the next conv's
@@ -1443,8 +1580,27 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                 auto it = m->acts.find(std::string("wv:") + nxt);
                 if (!train || it != m->acts.end()) { e.next_v = it != m->acts.end() ? it->second.p : m->d_wino_v; e.next_layer = nxt; }
             }
+            if (fp8 && !first) {
+                // FCN8S_PREC_FP8_INFER: the output goes to the next conv's e4m3 copy, to the copy the block's pool reads (blocks 1, 2, 5: codes with the exponent of
+                // the pool's consumer -- amax(pool) = amax(conv), q is monotone: the byte-max pool is exact), or to fp32 (blocks 3, 4: pool3 / pool4 feed the skip heads)
+                const int cout = m->widths[b];
+                std::string nx;
+                if (i < kConvsPerBlock[b]) { char t[32]; snprintf(t, sizeof t, "conv%d_%d", b + 1, i + 1); nx = t; }
+                else if (b != 2 && b != 3) { char t[32]; snprintf(t, sizeof t, "pool%din", b + 1); nx = t; }
+                const Q8Buf* yq = nullptr;
+                if (!nx.empty()) {
+                    const char* cons = kFp8Layers[fp8_layer(nm) + 1];           // the next FP8 layer: the next conv, or the pool's consumer
+                    yq = q8_for(m, nx, N, h, w, cout, 3, fp8_ex(m, cons), s);
+                    if (!yq) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed");
+                }
+                const int rc = fp8_conv(m, "conv3x3_fwd_fp8", nm, x, N, h, w, cin, cout, 3, yq ? nullptr : A(m, nm), yq, 1, s);
+                if (rc) return rc;
+                if (yq) { m->q8_filled.insert(nx); m->y_unwritten.insert(nm); }
+                x = A(m, nm); cin = cout;
+                continue;
+            }
             bool done = false;
-            if (first && !bf16_train_mode(m) && m->conv1_in_transform && m->widths[0] == 64 && kConvsPerBlock[0] == 2 && m->widths[0] >= m->wino_min_cin && m->wino_min_cin > 0 &&
+            if (first && !bf16_train_mode(m) && !fp8_mode(m) && m->conv1_in_transform && m->widths[0] == 64 && kConvsPerBlock[0] == 2 && m->widths[0] >= m->wino_min_cin && m->wino_min_cin > 0 &&
                 m->d_wino_v && wino_tile_for(m, h, w, 3) == 6) {
                 // conv1_1's only reader is conv1_2's F(6x6,3x3) input transform: that transform evaluates conv1_1 on its own patches, straight from the
                 // image (winograd.hip: wino_input_conv1_kernel), writes conv1_2's V -- into the buffer conv_same will look for it in -- and, in training,
@@ -1527,6 +1683,25 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
             x = A(m, nm); cin = m->widths[b];
         }
         snprintf(pn, sizeof pn, "pool%d", b + 1);
+        if (fp8) {
+            m->pool_fused[b] = false; m->pool_routed[b] = false;
+            if (b != 2 && b != 3) {
+                // byte max of the last conv's e4m3 copy straight into the consumer's copy (conv<b+2>_1, pad 1; fc6, pad (k - 1) / 2)
+                char pin[32], cons[32]; int ck = 3;
+                snprintf(pin, sizeof pin, "pool%din", b + 1);
+                if (b < 4) snprintf(cons, sizeof cons, "conv%d_1", b + 2); else { snprintf(cons, sizeof cons, "fc6"); ck = m->fc6k; }
+                Q8Buf* yq = q8_for(m, cons, N, h / 2, w / 2, cin, ck, fp8_ex(m, cons), s);
+                if (!yq) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed");
+                const Q8Buf& xi = m->q8[pin];
+                { ProfScope ps(m, "maxpool_fwd_fp8", 0, 1.25 * N * h * w * cin); launch_maxpool_fp8(xi.p, xi.ps, yq->p, yq->ps, N, h, w, cin, (ck - 1) / 2, s); }
+                m->q8_filled.insert(cons); m->y_unwritten.insert(pn);
+            } else {
+                ProfScope ps(m, "maxpool_fwd", 0, 4.0 * N * h * w * cin * 1.25);
+                launch_maxpool_fwd(x, A(m, pn), N, h, w, cin, s);
+            }
+            x = A(m, pn); h /= 2; w /= 2;
+            continue;
+        }
         m->pool_fused[b] = pooled && train;
         m->pool_routed[b] = false;
         if (!pooled && bf16_train_mode(m) && cp && m->bf16_fuse_pool && cin % 4 == 0) {
@@ -1564,7 +1739,14 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
     const int h5 = h, w5 = w;
     const bool drop = train && keep_prob < 1.f;
     m->drop_stream = (uint32_t)(2 * m->step);
-    if (bf16_train_mode(m)) {
+    if (fp8) {
+        // fc6 writes fc7's e4m3 copy only; fc7 writes fp32 for the fc7_1x1 head
+        const Q8Buf* q7 = q8_for(m, "fc7", N, h5, w5, m->widths[5], 1, fp8_ex(m, "fc7"), s);
+        if (!q7) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed");
+        int rc = fp8_conv(m, "fc6_fwd_fp8", "fc6", x, N, h5, w5, m->widths[4], m->widths[5], m->fc6k, nullptr, q7, 0, s); if (rc) return rc;
+        m->q8_filled.insert("fc7"); m->y_unwritten.insert("fc6");
+        rc = fp8_conv(m, "fc7_fwd_fp8", "fc7", A(m, "fc6"), N, h5, w5, m->widths[5], m->widths[6], 1, A(m, "fc7"), nullptr, 0, s); if (rc) return rc;
+    } else if (bf16_train_mode(m)) {
         unsigned short* xb6 = cp ? xg16_for(m, "fc6", N, h5, w5, m->widths[4], m->fc6k, s) : nullptr;
         if (xb6 && !m->xg16_filled.count("fc6")) { ProfScope ps(m, "bf16_convert", 0, 6.0 * N * h5 * w5 * m->widths[4]); launch_f32_to_bf16_padded(x, xb6, N, h5, w5, m->widths[4], (m->fc6k - 1) / 2, s, g16_ps(N, h5, w5, m->fc6k)); }
         unsigned short* xb7 = cp ? xg16_for(m, "fc7", N, h5, w5, m->widths[5], 1, s) : nullptr;
@@ -2010,6 +2192,9 @@ int fcn8s_destroy(fcn8s_model* m)
     for (auto& kv : m->wbf16_cache) if (kv.second) hipFree(kv.second);
     if (m->d_wbf16) hipFree(m->d_wbf16);
     if (m->d_abf16) hipFree(m->d_abf16);
+    for (auto& kv : m->q8) if (kv.second.p) hipFree(kv.second.p);
+    for (auto& kv : m->w8) if (kv.second.wq) hipFree(kv.second.wq);
+    if (m->d_fp8_amax) hipFree(m->d_fp8_amax);
     for (auto& kv : m->xbf16) if (kv.second) hipFree(kv.second);
     for (auto& kv : m->xg16) if (kv.second) hipFree(kv.second);
     for (auto& kv : m->dyg16) if (kv.second) hipFree(kv.second);
@@ -2048,6 +2233,7 @@ const char* fcn8s_last_error(const fcn8s_model* m) { return m ? m->err.c_str() :
 
 static void drop_u_cache(fcn8s_model* m)
 {
+    m->w8_valid.clear();                                  // (fp8_infer weight banks: storage kept, contents rebuilt by the next pass)
     if (m->u_cache.empty() && m->wbf16_cache.empty()) return;
     hipStreamSynchronize(m->stream);
     for (auto& kv : m->u_cache) if (kv.second) hipFree(kv.second);
@@ -2067,11 +2253,16 @@ int fcn8s_freeze_params(fcn8s_model* m, int frozen)
 int fcn8s_set_precision(fcn8s_model* m, int precision)
 {
     if (!m) return FCN8S_ERR_BAD_ARG;
-    if (precision < FCN8S_PREC_F32 || precision > FCN8S_PREC_BF16_TRAIN)
+    if (precision < FCN8S_PREC_F32 || precision > FCN8S_PREC_FP8_INFER)
         return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_precision: unknown precision");
     if (precision == FCN8S_PREC_BF16_TRAIN) {
         for (int i = 0; i < 7; ++i)
             if (m->widths[i] % 64) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_precision: the bf16_train mode needs every channel width to be a multiple of 64");
+    }
+    if (precision == FCN8S_PREC_FP8_INFER) {
+        for (int i = 0; i < 7; ++i)
+            if (m->widths[i] % 64) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_precision: the fp8_infer mode needs every channel width to be a multiple of 64");
+        if (m->fc6k % 2 == 0) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_precision: the fp8_infer mode needs an odd fc6 kernel size");
     }
     if (precision == FCN8S_PREC_BF16_FC || precision == FCN8S_PREC_BF16_FWD || precision == FCN8S_PREC_BF16_FWD_X2) {
         if (m->widths[4] % 32 || m->widths[5] % 128 || m->widths[6] % 128)
@@ -2090,10 +2281,15 @@ int fcn8s_set_precision(fcn8s_model* m, int precision)
         m->xg16.clear(); m->xg16_elems.clear();
         for (auto& kv : m->dyg16) if (kv.second) hipFree(kv.second);
         m->dyg16.clear(); m->dyg16_elems.clear(); m->xg16_filled.clear(); m->dyg16_filled.clear();
+        for (auto& kv : m->q8) if (kv.second.p) hipFree(kv.second.p);       // (fp8_infer's copies and weight banks; its calibration stays: it describes the parameters)
+        m->q8.clear(); m->q8_filled.clear();
+        for (auto& kv : m->w8) if (kv.second.wq) hipFree(kv.second.wq);
+        m->w8.clear(); m->w8_valid.clear();
         // bf16_train runs every convolution but conv1_1 as a DIRECT convolution on the bf16 MFMA, forward and backward: it rides on the library's
         // direct path (no Winograd transforms, the pools as kernels of their own, ReLU masks from the activations), i.e. on the settings
         // winograd_min_cin = 0 / winograd_fc6 = 0, which it takes over while it is on (and which need another workspace)
-        const bool was = m->precision == FCN8S_PREC_BF16_TRAIN, now = precision == FCN8S_PREC_BF16_TRAIN;
+        // (fp8_infer's calibration pass and its fp32 layers ride on the same direct path)
+        const bool was = direct_mode(m->precision), now = direct_mode(precision);
         if (was != now) {
             if (now) { m->saved_wino_min_cin = m->wino_min_cin; m->saved_wino_fc6 = m->wino_fc6; m->wino_min_cin = 0; m->wino_fc6 = 0; }
             else { if (m->saved_wino_min_cin >= 0) m->wino_min_cin = m->saved_wino_min_cin; if (m->saved_wino_fc6 >= 0) m->wino_fc6 = m->saved_wino_fc6; }
@@ -2105,6 +2301,64 @@ int fcn8s_set_precision(fcn8s_model* m, int precision)
     return FCN8S_OK;
 }
 int fcn8s_get_precision(const fcn8s_model* m) { return m ? m->precision : -1; }
+
+// FCN8S_PREC_FP8_INFER calibration: the fp32 forward pass of the mode (the direct path: every FP8 layer's input is materialised), then per FP8 layer the
+// maximum of |input|, accumulated on the device by an order-independent integer max (deterministic)
+int fcn8s_fp8_calibrate(fcn8s_model* m, const void* images, int dtype, int N, int H, int W, int where, int reset)
+{
+    if (!m || !images) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_fp8_calibrate: null argument");
+    if (!fp8_mode(m)) return fail(m, FCN8S_ERR_STATE, "fcn8s_fp8_calibrate: set the fp8_infer precision first (fcn8s_set_precision(m, FCN8S_PREC_FP8_INFER))");
+    int rc = ensure_workspace(m, N, H, W); if (rc) return rc;
+    const void* img; const uint8_t* lab;
+    rc = stage_inputs(m, images, dtype, nullptr, where, &img, &lab); if (rc) return rc;
+    if (!m->d_fp8_amax) HIPCHK(m, hipMalloc((void**)&m->d_fp8_amax, FCN8S_FP8_LAYERS * sizeof(unsigned)));
+    float start[FCN8S_FP8_LAYERS] = {};
+    if (!reset && m->fp8_calibrated) memcpy(start, m->fp8_amax, sizeof start);
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(m->d_fp8_amax, start, sizeof start, hipMemcpyHostToDevice));
+    take_deferred_error(nullptr);
+    m->fp8_calibrating = true;
+    rc = forward(m, img, dtype, 1.0f, false);
+    m->fp8_calibrating = false;
+    if (rc) { take_deferred_error(nullptr); return rc; }
+    rc = deferred_rc(m); if (rc) return rc;
+    {
+        double by = 0;
+        for (int L = 0; L < FCN8S_FP8_LAYERS; ++L) by += 4.0 * N * (H / kFp8InDiv[L]) * (W / kFp8InDiv[L]) * m->widths[kFp8InWidth[L]];
+        ProfScope ps(m, "fp8_calibrate", 0, by);
+        for (int L = 0; L < FCN8S_FP8_LAYERS; ++L) {
+            const char* in = kFp8Inputs[L];
+            auto it = m->acts.find(in);
+            if (it == m->acts.end() || !it->second.p || m->y_unwritten.count(in))
+                return fail(m, FCN8S_ERR_STATE, std::string("fcn8s_fp8_calibrate: the fp32 pass did not materialise ") + in);
+            const long long n = (long long)N * (H / kFp8InDiv[L]) * (W / kFp8InDiv[L]) * m->widths[kFp8InWidth[L]];
+            launch_amax(it->second.p, n, m->d_fp8_amax + L, m->stream);
+        }
+    }
+    unsigned bits[FCN8S_FP8_LAYERS];
+    HIPCHK(m, hipMemcpyAsync(bits, m->d_fp8_amax, sizeof bits, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    memcpy(m->fp8_amax, bits, sizeof bits);
+    m->fp8_calibrated = true;
+    return FCN8S_OK;
+}
+int fcn8s_fp8_get_calibration(const fcn8s_model* m, float* amax, int n)
+{
+    if (!m || !amax || n != FCN8S_FP8_LAYERS) return FCN8S_ERR_BAD_ARG;
+    if (!m->fp8_calibrated) return FCN8S_ERR_STATE;
+    memcpy(amax, m->fp8_amax, sizeof m->fp8_amax);
+    return FCN8S_OK;
+}
+int fcn8s_fp8_set_calibration(fcn8s_model* m, const float* amax, int n)
+{
+    if (!m || !amax) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_fp8_set_calibration: null argument");
+    if (n != FCN8S_FP8_LAYERS) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_fp8_set_calibration: needs FCN8S_FP8_LAYERS (14) maxima");
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(amax[i]) || amax[i] < 0.f) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_fp8_set_calibration: maxima must be finite and >= 0");
+    memcpy(m->fp8_amax, amax, sizeof m->fp8_amax);
+    m->fp8_calibrated = true;
+    return FCN8S_OK;
+}
 
 // Options select between maintained algorithm variants (parity reports separate the Winograd round-off from the summation order
 // with them); the defaults are the measured winners.  A model option drops the workspace and every cached filter bank.
@@ -2159,9 +2413,9 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
     }
     int* slot = model_option(m, k);
     if (!slot) return fail(m, FCN8S_ERR_NOT_FOUND, "fcn8s_set_option: unknown option '" + k + "'");
-    // FCN8S_PREC_BF16_TRAIN runs without Winograd transforms whatever these two say: while the mode is on a new value is kept for the day it is left
-    // (round 5 overwrote the live slot: the value was used by nobody and lost on leaving)
-    if (bf16_train_mode(m) && (k == "winograd_min_cin" || k == "winograd_fc6")) {
+    // FCN8S_PREC_BF16_TRAIN and FCN8S_PREC_FP8_INFER run without Winograd transforms whatever these two say: while such a mode is on a new value is kept
+    // for the day it is left (round 5 overwrote the live slot: the value was used by nobody and lost on leaving)
+    if (direct_mode(m->precision) && (k == "winograd_min_cin" || k == "winograd_fc6")) {
         if (value < 0) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_option: negative value");
         (k == "winograd_min_cin" ? m->saved_wino_min_cin : m->saved_wino_fc6) = (int)value;
         return FCN8S_OK;
@@ -2204,8 +2458,8 @@ int fcn8s_get_option(const fcn8s_model* m, const char* key, int64_t* value)
     if (!slot) return FCN8S_ERR_NOT_FOUND;
     *value = *slot;
     // (the caller's own setting, also while FCN8S_PREC_BF16_TRAIN keeps the live slots at 0)
-    if (bf16_train_mode(m) && k == "winograd_min_cin" && m->saved_wino_min_cin >= 0) *value = m->saved_wino_min_cin;
-    if (bf16_train_mode(m) && k == "winograd_fc6" && m->saved_wino_fc6 >= 0) *value = m->saved_wino_fc6;
+    if (direct_mode(m->precision) && k == "winograd_min_cin" && m->saved_wino_min_cin >= 0) *value = m->saved_wino_min_cin;
+    if (direct_mode(m->precision) && k == "winograd_fc6" && m->saved_wino_fc6 >= 0) *value = m->saved_wino_fc6;
     return FCN8S_OK;
 }
 
@@ -2245,6 +2499,7 @@ static int xfer_named(fcn8s_model* m, float* base, const char* name, void* host,
 int fcn8s_set_param(fcn8s_model* m, const char* name, const float* host, size_t n)
 {
     if (m && m->frozen) fcn8s_freeze_params(m, 0);      // parameters are about to change: leave the frozen state
+    fp8_clear_calibration(m);
     return xfer_named(m, m ? m->d_params : nullptr, name, (void*)host, n, true);
 }
 int fcn8s_get_param(fcn8s_model* m, const char* name, float* host, size_t n) { return xfer_named(m, m ? m->d_params : nullptr, name, host, n, false); }
@@ -2263,6 +2518,7 @@ int fcn8s_bucket_range(const fcn8s_model* m, int b, size_t* off, size_t* n)
 int fcn8s_init_params(fcn8s_model* m, uint64_t seed)
 {
     if (m && m->frozen) fcn8s_freeze_params(m, 0);      // parameters are about to change (or a training pass starts): leave the frozen state
+    fp8_clear_calibration(m);
     if (!m) return FCN8S_ERR_BAD_ARG;
     HIPCHK(m, hipMemsetAsync(m->d_params, 0, m->total * sizeof(float), m->stream));
     uint32_t sid = 1000;
@@ -2283,7 +2539,9 @@ int fcn8s_init_params(fcn8s_model* m, uint64_t seed)
 int fcn8s_forward_loss(fcn8s_model* m, const void* images, int dtype, const uint8_t* labels, int N, int H, int W,
                        float keep_prob, float l2_rate, int where)
 {
+    if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_forward_loss");
     if (m && m->frozen) fcn8s_freeze_params(m, 0);      // parameters are about to change (or a training pass starts): leave the frozen state
+    fp8_clear_calibration(m);
     if (!m || !images || !labels) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_forward_loss: null argument");
     if (!(keep_prob > 0.f && keep_prob <= 1.f)) return fail(m, FCN8S_ERR_BAD_ARG, "keep_prob must be in (0, 1]");
     int rc = ensure_workspace(m, N, H, W); if (rc) return rc;
@@ -2301,6 +2559,7 @@ int fcn8s_forward_loss(fcn8s_model* m, const void* images, int dtype, const uint
 int fcn8s_backward_bucket(fcn8s_model* m, int bucket)
 {
     if (!m || bucket < 0 || bucket >= kNumBuckets) return fail(m, FCN8S_ERR_BAD_ARG, "bad bucket");
+    if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_backward_bucket");
     take_deferred_error(nullptr);
     int rc = do_backward_bucket(m, bucket); if (rc) { take_deferred_error(nullptr); return rc; }
     return deferred_rc(m);
@@ -2566,6 +2825,7 @@ int fcn8s_comm_broadcast_params(fcn8s_model* m, int root)
     if (!m->comm) return fail(m, FCN8S_ERR_STATE, "fcn8s_comm_broadcast_params: no communicator (fcn8s_comm_init first)");
     if (root >= m->comm_world) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_comm_broadcast_params: root outside the communicator");
     if (m->frozen) fcn8s_freeze_params(m, 0);
+    fp8_clear_calibration(m);
     std::lock_guard<std::mutex> lk(m->comm_mu);          // (the watchdog may abort the communicator: not in the middle of an enqueue)
     if (!m->comm) return fail(m, FCN8S_ERR_RCCL, "fcn8s_comm_broadcast_params: " + m->comm_error);
     RCCLCHK(m, rccl()->Broadcast(m->d_params, m->d_params, m->total, ncclFloat, root, m->comm, m->stream));
@@ -2613,7 +2873,9 @@ int fcn8s_comm_allreduce_metrics(fcn8s_model* m)
 
 int fcn8s_apply_update(fcn8s_model* m, int optimizer, float lr, float grad_scale)
 {
+    if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_apply_update");
     if (m && m->frozen) fcn8s_freeze_params(m, 0);      // parameters are about to change (or a training pass starts): leave the frozen state
+    fp8_clear_calibration(m);
     if (!m) return FCN8S_ERR_BAD_ARG;
     if (m->comm_world > 1 && (m->comm || m->comm_failed.load())) { int rch = comm_wait_host(m, "fcn8s_apply_update"); if (rch) return rch; }
     { int rcw = fcn8s_comm_wait(m); if (rcw) return rcw; }      // gradient buckets still being all-reduced by the library's own communicator
@@ -2698,6 +2960,7 @@ int fcn8s_get_loss_stats(fcn8s_model* m, int64_t* valid, int64_t* kept, float* t
 int fcn8s_train_step(fcn8s_model* m, const void* images, int dtype, const uint8_t* labels, int N, int H, int W,
                      float lr, float keep_prob, float l2_rate, int where, float* loss_out, int64_t* step_out)
 {
+    if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_train_step");
     if (m && m->frozen) fcn8s_freeze_params(m, 0);      // parameters are about to change (or a training pass starts): leave the frozen state
     int rc = fcn8s_forward_loss(m, images, dtype, labels, N, H, W, keep_prob, l2_rate, where); if (rc) return rc;
     // a model with a communicator of more than one rank trains data-parallel through this entry point too: the bucket-by-bucket
@@ -2850,6 +3113,13 @@ int fcn8s_predict_tta(fcn8s_model* m, const void* images, int dtype, int N, int 
     const int P = nscales * (1 + flip), C = m->C;
     size_t need = 0;
     for (int k = 0; k < nscales; ++k) { WsPlan pl; plan_workspace(m, N, hp[k], wp[k], pl); need = std::max(need, pl.bytes); }
+    if (fp8_mode(m)) {                    // fp8_infer: every e4m3 copy sized for the largest pass up front (no reallocation between passes)
+        for (const Q8Spec& q : q8_specs(m)) {
+            size_t mx = 0;
+            for (int k = 0; k < nscales; ++k) mx = std::max(mx, q8_bytes(N, hp[k] / q.div, wp[k] / q.div, q.C, q.K));
+            if (!q8_grow(m, q.key, mx, m->stream)) return fail(m, FCN8S_ERR_OOM, "fcn8s_predict_tta: hipMalloc of an e4m3 copy failed");
+        }
+    }
     // scratch: the staged images (host input), the accumulator (P > 1), the staged output (host output)
     const size_t npix = (size_t)N * H * W, eb = dtype == FCN8S_IMG_U8 ? 1 : 4;
     const size_t b_img = where == FCN8S_HOST ? align_up(npix * 3 * eb, 256) : 0, b_acc = P > 1 ? align_up(npix * C * sizeof(float), 256) : 0;
@@ -2892,6 +3162,7 @@ int fcn8s_predict_tta(fcn8s_model* m, const void* images, int dtype, int N, int 
         for (auto& kv : m->u_cache) m->bank_stale.insert("u:" + kv.first);
         for (auto& kv : m->wbf16_cache) m->bank_stale.insert("w:" + kv.first);
         m->banks_stale = true;
+        m->w8_valid.clear();              // (fp8_infer: the weight banks are re-quantized by the next pass)
         m->frozen = false;
     }
     if (rc) return rc;
@@ -2992,6 +3263,32 @@ int fcn8s_get_activation(fcn8s_model* m, const char* name, float* host, size_t n
         HIPCHK(m, hipMemcpy(host, k->second.p, n * sizeof(float), hipMemcpyDeviceToHost));
         return FCN8S_OK;
     }
+    if (strncmp(name, "q8:", 3) == 0) {      // FCN8S_PREC_FP8_INFER: a layer's e4m3 input copy of the last pass, dequantized (2^ex code: exact in fp32) as [N,H,W,Cin]
+        auto k = m->q8.find(name + 3);
+        if (!fp8_mode(m) || k == m->q8.end() || !k->second.p || !m->q8_filled.count(name + 3) || fp8_layer(name + 3) < 0)
+            return fail(m, FCN8S_ERR_STATE, std::string("no e4m3 input copy of '") + (name + 3) + "': run an fp8_infer evaluation / prediction first (FP8 layers: conv1_2 .. conv5_3, fc6, fc7)");
+        const Q8Buf& b = k->second;
+        const size_t need = (size_t)b.N * b.H * b.W * b.C;
+        if (n != need) return fail(m, FCN8S_ERR_SHAPE, std::string("e4m3 copy of '") + (name + 3) + "' has " + std::to_string(need) + " elements");
+        std::vector<unsigned char> raw((size_t)b.ps * (b.C / 64));
+        HIPCHK(m, hipStreamSynchronize(m->stream));
+        HIPCHK(m, hipMemcpy(raw.data(), b.p, raw.size(), hipMemcpyDeviceToHost));
+        float lut[256];
+        for (int c = 0; c < 256; ++c) {
+            const int e = (c >> 3) & 15, mt = c & 7;
+            const double v = (e == 15 && mt == 7) ? NAN : (e ? ldexp(1.0 + mt / 8.0, e - 7) : ldexp((double)mt, -9));
+            lut[c] = (float)ldexp((c & 128) ? -v : v, b.ex);
+        }
+        const int Hp = b.H + 2 * b.pad, Wq = b.W + 2 * b.pad;
+        for (int nn = 0; nn < b.N; ++nn)
+            for (int y = 0; y < b.H; ++y)
+                for (int x = 0; x < b.W; ++x) {
+                    const long long q = ((long long)nn * Hp + y + b.pad) * Wq + x + b.pad;
+                    float* dst = host + (((size_t)nn * b.H + y) * b.W + x) * b.C;
+                    for (int c = 0; c < b.C; ++c) dst[c] = lut[raw[(size_t)(c >> 6) * b.ps + q * 64 + (c & 63)]];
+                }
+        return FCN8S_OK;
+    }
     auto it = m->acts.find(name);
     if (it == m->acts.end()) return fail(m, FCN8S_ERR_NOT_FOUND, std::string("unknown activation '") + name + "'");
     if (std::string(name) == "logits" && !m->logits_nhwc_valid && m->logits_b) {      // kept in the blocked GEMM layout: convert for the caller
@@ -3001,7 +3298,8 @@ int fcn8s_get_activation(fcn8s_model* m, const char* name, float* host, size_t n
     if (n != it->second.n) return fail(m, FCN8S_ERR_SHAPE, std::string("activation '") + name + "' has " + std::to_string(it->second.n) + " elements");
     if (m->y_unwritten.count(name))
         return fail(m, FCN8S_ERR_STATE, std::string("activation '") + name + "' was not materialised by the last forward pass: " +
-                                        (bf16_train_mode(m) ? "bf16_train keeps a conv -> conv activation only as the consumer's padded bf16 copy (option \"bf16_acts\" = 0 keeps the fp32 tensor too)" :
+                                        (fp8_mode(m) ? std::string("fp8_infer keeps it only as its consumer's e4m3 copy (fcn8s_get_activation(m, \"q8:<consumer>\", ...))") :
+                                         bf16_train_mode(m) ? "bf16_train keeps a conv -> conv activation only as the consumer's padded bf16 copy (option \"bf16_acts\" = 0 keeps the fp32 tensor too)" :
                                          std::string(name) == "conv1_1" ? "conv1_2's input transform evaluated it on its own patches (option \"conv1_in_transform\" = 0 keeps it)"
                                                                         : "its output transform wrote the next conv's transformed input directly (option \"fuse_out_in\" = 0 keeps it)"));
     HIPCHK(m, hipStreamSynchronize(m->stream));
@@ -3314,6 +3612,36 @@ int fcn8s_op_conv2d_bf16_train(void* stream, const float* x, const float* w, con
     if (db && dy) { hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), s); launch_colsum(dy, db, (long long)N * H * W, Cout, s); }
     cleanup();
     if (!ok) return fail(nullptr, FCN8S_ERR_SHAPE, "conv2d_bf16_train: a launch refused the shape");
+    OPCHK(); return FCN8S_OK;
+}
+
+// One K x K SAME convolution in the arithmetic of FCN8S_PREC_FP8_INFER on that mode's kernels (gemm_fp8.hip): x quantized with exponent x_exp into a padded
+// e4m3 copy, w per output channel, y = 2^(x_exp + ew) sum Xq Wq + bias (ReLU if relu)
+int fcn8s_op_conv2d_fp8(void* stream, const float* x, const float* w, const float* bias, float* y, int relu, int x_exp,
+                        int N, int H, int W, int Cin, int Cout, int K)
+{
+    if (!x || !w || !y) return fail(nullptr, FCN8S_ERR_BAD_ARG, "conv2d_fp8: null argument");
+    if (Cin % 64 || Cout % 64 || K % 2 == 0 || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "conv2d_fp8: needs Cin % 64 == 0, Cout % 64 == 0, K odd, positive sizes");
+    hipStream_t s = (hipStream_t)stream;
+    const int pad = (K - 1) / 2;
+    const long long R = (long long)N * (H + 2 * pad) * (W + 2 * pad);
+    const size_t xb = (size_t)R * Cin, wb = (size_t)K * K * Cin * Cout;
+    unsigned char *xq = nullptr, *wq = nullptr;
+    auto cleanup = [&]() { hipStreamSynchronize(s); if (xq) hipFree(xq); if (wq) hipFree(wq); };
+    if (hipMalloc((void**)&xq, xb) != hipSuccess || hipMalloc((void**)&wq, wb + 8 * (size_t)Cout) != hipSuccess) {
+        (void)hipGetLastError(); cleanup(); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+    }
+    hipMemsetAsync(xq, 0, xb, s);
+    launch_f32_to_fp8_padded(x, xq, N, H, W, Cin, pad, R * 64, x_exp, s);
+    int* ew = reinterpret_cast<int*>(wq + wb);
+    launch_w_to_fp8(w, wq, ew, reinterpret_cast<unsigned*>(wq + wb + 4 * (size_t)Cout), K * K * Cin, Cout, s);
+    Fp8ConvArgs a;
+    a.xp = xq; a.xp_ps = R * 64; a.wq = wq; a.ew = ew; a.bias = bias; a.y = y; a.ex = x_exp; a.relu = relu;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.K = K; a.M = (long long)N * H * W;
+    const bool ok = launch_conv_fp8(a, s);
+    cleanup();
+    if (!ok) return fail(nullptr, FCN8S_ERR_SHAPE, "conv2d_fp8: the launch refused the shape");
     OPCHK(); return FCN8S_OK;
 }
 

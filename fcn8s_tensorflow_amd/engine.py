@@ -413,11 +413,14 @@ class Engine:
         pieces per operand instead of three (16 significand bits enter each product: reduced precision, half the matrix work);
         'bf16_train' = mixed-precision training as it is usually meant: conv1_2 .. conv5_3, fc6 and fc7 as direct convolutions whose operands are
         rounded to bf16 in the forward pass, the data gradient AND the weight gradient (fp32 accumulate, fp32 master weights, everything else
-        exact fp32; no Winograd transforms)."""
+        exact fp32; no Winograd transforms); 'fp8_infer' = inference only: conv1_2 .. conv5_3, fc6 and fc7 with OCP e4m3 operands on the
+        block-scaled MX MFMA, static per-layer activation scales from `calibrate_fp8` and per-channel weight scales (fp8.py states the
+        arithmetic); training calls refuse it."""
         modes = {'fp32': L.PREC_F32, 'bf16_fc': L.PREC_BF16_FC, 'f32x3': L.PREC_F32X3, 'bf16_fwd': L.PREC_BF16_FWD,
-                 'f32x2': L.PREC_F32X2, 'bf16_fwd_x2': L.PREC_BF16_FWD_X2, 'bf16_train': L.PREC_BF16_TRAIN}
+                 'f32x2': L.PREC_F32X2, 'bf16_fwd_x2': L.PREC_BF16_FWD_X2, 'bf16_train': L.PREC_BF16_TRAIN, 'fp8_infer': L.PREC_FP8_INFER}
         if precision not in modes:
-            raise ValueError("`precision` must be 'fp32', 'bf16_fc', 'f32x3', 'bf16_fwd', 'f32x2', 'bf16_fwd_x2' or 'bf16_train', but is '{}'.".format(precision))
+            raise ValueError("`precision` must be 'fp32', 'bf16_fc', 'f32x3', 'bf16_fwd', 'f32x2', 'bf16_fwd_x2', 'bf16_train' or 'fp8_infer', "
+                             "but is '{}'.".format(precision))
         L.check(L.lib.fcn8s_set_precision(self.h, modes[precision]), self.h)
         self.precision = precision
 
@@ -695,6 +698,32 @@ class Engine:
         out = np.empty((N, H, W), np.int64) if argmax else np.empty((N, H, W, self.num_classes), np.float32)
         L.check(L.lib.fcn8s_predict(self.h, pi, dt, N, H, W, int(bool(argmax)), out.ctypes.data_as(C.c_void_p), where), self.h)
         return out if argmax or self.logical_classes == self.num_classes else np.ascontiguousarray(out[..., :self.logical_classes])
+
+    # ---- fp8_infer calibration (include/fcn8s_hip.h: fcn8s_fp8_calibrate) ---------------------------------------------------
+    def calibrate_fp8(self, images, reset=False):
+        """In the 'fp8_infer' precision: run the fp32 forward pass on `images` and fold each FP8 layer's max |input| into the calibration
+        (reset=True starts over).  Returns the calibration (`fp8_calibration()`)."""
+        self._sync_stream()
+        ka_i, pi, dt, where, nhw = self._images(images)
+        N, H, W = (int(x) for x in nhw)
+        L.check(L.lib.fcn8s_fp8_calibrate(self.h, pi, dt, N, H, W, where, int(bool(reset))), self.h)
+        del ka_i
+        return self.fp8_calibration()
+
+    def fp8_calibration(self):
+        """The FP8 calibration, float32[14] (the max |input| of conv1_2 .. conv5_3, fc6, fc7), or None if the model has none."""
+        a = np.empty(L.FP8_LAYERS, np.float32)
+        rc = L.lib.fcn8s_fp8_get_calibration(self.h, a.ctypes.data_as(L._fp), a.size)
+        if rc == L.ERR_STATE:
+            return None
+        L.check(rc, self.h)
+        return a
+
+    def set_fp8_calibration(self, amax):
+        a = np.ascontiguousarray(np.asarray(amax, dtype=np.float32).reshape(-1))
+        if a.size != L.FP8_LAYERS:
+            raise ValueError("an FP8 calibration has %d maxima, got %d" % (L.FP8_LAYERS, a.size))
+        L.check(L.lib.fcn8s_fp8_set_calibration(self.h, a.ctypes.data_as(L._fp), a.size), self.h)
 
     def predict_tta(self, images, scales=(1.0,), flip=False, argmax=True):
         """Multi-scale / left-right-flip prediction on images of any size (fcn8s_predict_tta; the pass rule is in tta.py): the mean over

@@ -107,6 +107,7 @@ class FCN8s:
             device_id = int(os.environ.get("LOCAL_RANK", "0"))
         rank = int(os.environ.get("RANK", "0"))
 
+        fp8_calibration = None
         tf_prefix = tf_bundle.find_bundle_prefix(model_load_dir) if model_load_dir is not None else None
         if model_load_dir is not None and tf_prefix is not None and not os.path.isfile(os.path.join(model_load_dir, 'fcn8s_meta.json')):
             # a TensorFlow SavedModel / Saver checkpoint written by the reference (:922-934): variables, Adam slots, global_step
@@ -126,6 +127,7 @@ class FCN8s:
             self.engine = Engine(padded_classes(self.num_classes), widths=meta.get("widths"), fc6_ksize=meta.get("fc6_ksize", 7),
                                  device_id=device_id, seed=seed + rank, logical_classes=self.num_classes)
             _load_checkpoint(self.engine, os.path.join(model_load_dir, "variables", "variables.npz"), with_state=True)
+            fp8_calibration = meta.get("fp8_calibration")
         else:
             self.engine = Engine(padded_classes(num_classes), widths=widths, fc6_ksize=fc6_ksize, device_id=device_id, seed=seed + rank,
                                  logical_classes=num_classes)
@@ -133,6 +135,8 @@ class FCN8s:
             if variables_load_dir is not None:
                 self.load_variables(variables_load_dir)
         self.engine.broadcast_params(0)
+        if fp8_calibration is not None:      # after the parameters: writing them clears a calibration
+            self.engine.set_fp8_calibration(fp8_calibration)
         self.engine.metrics_reset()
 
     # fcn8s_tensorflow.py:127-152 -- the encoder weights enter here
@@ -208,6 +212,9 @@ class FCN8s:
         `class_weights` (one per class), `ohem_thresh` (a probability in (0, 1]) and `ohem_min_kept` set the training loss for the duration
         of the call (Engine.set_loss, loss.py: class-weighted and / or hard-pixel-mined cross-entropy); the evaluations keep reporting the
         reference's loss, and the previous loss configuration is restored when train() returns or raises.'''
+        if self.engine.precision == 'fp8_infer':
+            raise ValueError("The 'fp8_infer' precision is inference only; switch the engine to another precision "
+                             "(e.g. model.engine.set_precision('bf16_train')) before training.")
         _check_metric_names(metrics)
         custom_loss = class_weights is not None or bool(ohem_thresh)
         if custom_loss:
@@ -337,6 +344,20 @@ class FCN8s:
 
         if self.engine.rank == 0:
             print(''.join('{}: {:.4f}  '.format(n, v) for n, v in zip(self.metric_names, self.metric_values)))
+
+    def calibrate_fp8(self, data_generator, num_batches):
+        '''Not in the reference: switch the engine to the inference-only 'fp8_infer' precision and calibrate its static per-layer activation
+        scales over `num_batches` batches of `data_generator` (the images of each batch; the first batch starts a new calibration).  After it,
+        `predict`, `predict_and_save`, `predict_and_export_label_ids`, `evaluate` and the multi-scale / flip keywords run in FP8; `save`
+        stores the calibration.  Returns it (float32[14], the max |input| of conv1_2 .. conv5_3, fc6, fc7).'''
+        if num_batches < 1:
+            raise ValueError("`num_batches` must be at least 1.")
+        self.engine.set_precision('fp8_infer')
+        cal = None
+        for i in range(num_batches):
+            batch = next(data_generator)
+            cal = self.engine.calibrate_fp8(batch[0], reset=(i == 0))
+        return cal
 
     def evaluate(self, data_generator, num_batches, metrics={'loss', 'mean_iou', 'accuracy'}, l2_regularization=0.0, dataset='val'):
         '''fcn8s_tensorflow.py:699-741'''
@@ -586,10 +607,14 @@ def _load_tf_tensors(engine, tensors, with_state=True):
 
 
 def _write_meta(target, engine, tags):
+    meta = {'format': 'fcn8s_tensorflow_amd/1', 'num_classes': engine.logical_classes, 'widths': list(engine.widths),
+            'fc6_ksize': engine.specs['fc6/weights'][0][0], 'tags': list(tags) if tags else None,
+            'global_step': engine.global_step}
+    cal = engine.fp8_calibration()
+    if cal is not None:                   # the 'fp8_infer' calibration (float32 values, stored exactly as Python floats)
+        meta['fp8_calibration'] = [float(v) for v in cal]
     with open(os.path.join(target, 'fcn8s_meta.json'), 'w') as f:
-        json.dump({'format': 'fcn8s_tensorflow_amd/1', 'num_classes': engine.logical_classes, 'widths': list(engine.widths),
-                   'fc6_ksize': engine.specs['fc6/weights'][0][0], 'tags': list(tags) if tags else None,
-                   'global_step': engine.global_step}, f)
+        json.dump(meta, f)
 
 
 def _read_meta(model_dir):

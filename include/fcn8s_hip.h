@@ -75,6 +75,24 @@ extern "C" {
                                     * sums fp32: forward y = conv(bf16 x, bf16 w); data gradient dx = conv^T(bf16 dy, bf16 w); weight gradient
                                     * dw = corr(bf16 x, bf16 dy); bias gradient, ReLU / dropout masks, pools, the loss, the decoder and the optimizer exact fp32
                                     * on fp32 master weights.  No Winograd transform runs in this mode.  Needs channel widths % 64 == 0. */
+#define FCN8S_PREC_FP8_INFER 7     /* INFERENCE ONLY: evaluation, prediction and multi-scale / flip prediction with the convolutions conv1_2 .. conv5_3, fc6 and fc7 on
+                                    * the block-scaled MX MFMA with OCP e4m3 operands (E4M3FN: max 448, min subnormal 2^-9, no infinities; not the fnuz format).
+                                    *   q(v)  = clamp v to [-448, 448], then round to nearest even e4m3 (on the device and the host; NaN stays NaN);
+                                    *   E(a)  = the smallest integer e with a <= 448 2^e, E(0) = 0 (power-of-two scales: every scaling is exact);
+                                    *   weights: per layer and output channel co, ew[co] = E(max |W[..., co]|), Wq = q(W 2^-ew[co]);
+                                    *   activations: per FP8 layer L, ex[L] = E(amax[L]) from calibration (fcn8s_fp8_calibrate); L's input exists only as a padded
+                                    *     e4m3 copy q(x 2^-ex[L]) in 64-channel planes, written by the producer (the previous conv's epilogue inside a block, fc6's for
+                                    *     fc7, the byte-max pool on the e4m3 copy of blocks 1, 2 and 5 -- exact: amax(pool) = amax(conv), q is monotone --, a conversion
+                                    *     of fp32 conv1_1 / pool3 / pool4);
+                                    *   output: y[co] = 2^(ex[L] + ew[co]) sum Xq Wq + b[co], then ReLU; fp32 products and sums.
+                                    * conv1_1 (3 input channels), the decoder, softmax / argmax, loss and metrics stay fp32; pool3 / pool4 / fc7 stay fp32 for the skip
+                                    * heads.  No split K: an image's logits do not depend on the batch it is predicted in.  Needs channel widths % 64 == 0.  Without a
+                                    * calibration an FP8 pass is FCN8S_ERR_STATE; every library call that changes parameters (fcn8s_set_param, fcn8s_init_params, the
+                                    * training calls, fcn8s_apply_update, fcn8s_comm_broadcast_params) clears it; writers of ext_params are on their own, as with
+                                    * fcn8s_freeze_params.  The calibration survives fcn8s_set_precision.  Training calls in this mode are FCN8S_ERR_STATE.  Frozen models
+                                    * quantize each weight bank once; others once per pass.  fcn8s_get_activation(m, "q8:<layer>") returns the dequantized values
+                                    * (2^ex code, exact in fp32) of the layer's e4m3 input copy as [N,H,W,Cin]. */
+#define FCN8S_FP8_LAYERS 14        /* inputs of conv1_2 .. conv5_3, fc6, fc7, in that order */
 
 typedef struct fcn8s_model fcn8s_model;
 
@@ -281,6 +299,14 @@ int fcn8s_freeze_params(fcn8s_model* m, int frozen);
 int fcn8s_set_precision(fcn8s_model* m, int precision);
 int fcn8s_get_precision(const fcn8s_model* m);
 
+/* FCN8S_PREC_FP8_INFER calibration.  fcn8s_fp8_calibrate (in that mode) runs the model's fp32 forward pass on the batch (keep_prob 1, direct
+ * convolutions: every FP8 layer's input is materialised) and records per FP8 layer the maximum of |input| (an order-independent max reduction:
+ * deterministic); calls accumulate the maximum until one with reset != 0 starts over.  get / set: n == FCN8S_FP8_LAYERS floats (finite, >= 0);
+ * get is FCN8S_ERR_STATE without a calibration. */
+int fcn8s_fp8_calibrate(fcn8s_model* m, const void* images, int image_dtype, int N, int H, int W, int where, int reset);
+int fcn8s_fp8_get_calibration(const fcn8s_model* m, float* amax, int n);
+int fcn8s_fp8_set_calibration(fcn8s_model* m, const float* amax, int n);
+
 /* Algorithm options (not in the reference).  They select between maintained variants of the same arithmetic so that a parity report can
  * separate Winograd round-off from summation order; the defaults are the measured winners and production code never sets them.
  *   model options (m != NULL; setting one drops the workspace and all cached filter banks):
@@ -432,6 +458,10 @@ int fcn8s_op_conv2d_bf16(void* stream, const float* x, const float* w_hwio, cons
 int fcn8s_op_conv2d_bf16_train(void* stream, const float* x, const float* w_hwio, const float* bias, float* y, int relu,
                                const float* dy, const float* mask, float* dx, float* dw, float* db,
                                int N, int H, int W, int Cin, int Cout, int K);
+/* One K x K SAME convolution in the arithmetic of FCN8S_PREC_FP8_INFER on that mode's kernel: x quantized with exponent x_exp (q(x 2^-x_exp)),
+ * w per output channel (ew = E(max |w[..., co]|)), y = 2^(x_exp + ew) sum Xq Wq + bias (ReLU if relu; bias may be NULL).  Cin, Cout % 64 == 0, K odd. */
+int fcn8s_op_conv2d_fp8(void* stream, const float* x, const float* w_hwio, const float* bias, float* y, int relu, int x_exp,
+                        int N, int H, int W, int Cin, int Cout, int K);
 int fcn8s_op_conv2d_bwd(void* stream, const float* x, const float* w_hwio, const float* dy,
                         float* dx, float* dw, float* db,
                         int N, int H, int W, int Cin, int Cout, int K);
