@@ -73,6 +73,8 @@ SIGNATURES = {
     "fcn8s_read_loss": (_i, [_p, _fp]),
     "fcn8s_set_loss": (_i, [_p, _p, _i, _f, _i64]),
     "fcn8s_get_loss_stats": (_i, [_p, _i64p, _i64p, _fp]),
+    "fcn8s_set_lovasz": (_i, [_p, _f, _f, _i, _i, _p, _i]),
+    "fcn8s_get_loss_terms": (_i, [_p, _fp, _fp, _fp]),
     "fcn8s_eval_step": (_i, [_p, _p, _i, _p, _i, _i, _i, _f, _i]),
     "fcn8s_metrics_reset": (_i, [_p]),
     "fcn8s_metrics_get": (_i, [_p, _dp, _dp, _dp]),
@@ -123,6 +125,7 @@ SIGNATURES = {
     "fcn8s_op_conv2d_transpose_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i]),
     "fcn8s_op_softmax_xent": (_i, [_p, _p, _p, _p, _p, _i64, _i]),
     "fcn8s_op_softmax_xent_ex": (_i, [_p, _p, _p, _p, _f, _i64, _p, _p, _p, _p, _i64, _i]),
+    "fcn8s_op_lovasz_softmax": (_i, [_p, _p, _i, _p, _i64, _i64, _i, _i, _p, _p, _p, _p]),
     "fcn8s_op_softmax_argmax": (_i, [_p, _p, _p, _p, _i64, _i]),
     "fcn8s_op_confusion": (_i, [_p, _p, _p, _i64, _p, _i]),
     "fcn8s_op_tf_adam": (_i, [_p, _p, _p, _p, _p, _i64, _i, _f, _f, _f, _f, _f]),

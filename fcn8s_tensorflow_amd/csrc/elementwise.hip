@@ -472,7 +472,7 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel_c(const float* logits
         if (threadIdx.x < C) wsh[threadIdx.x] = x.cw[threadIdx.x];
         if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
         if constexpr (PH == XENT_OHEM_LOSS) for (int i = threadIdx.x; i < OHEM_BINS0; i += blockDim.x) hsh[i] = 0;
-        if constexpr (PH == XENT_OHEM_GRAD) { tsel = x.st->t; gsel = x.st->gscale; }
+        if constexpr (PH == XENT_OHEM_GRAD) { tsel = x.st->t; gsel = x.st->gscale * x.ce_scale; }
         __syncthreads();
     }
     double lsum = 0;
@@ -586,7 +586,7 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel_any(const float* logi
         if (threadIdx.x < C) wsh[threadIdx.x] = x.cw[threadIdx.x];
         if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
         if constexpr (PH == XENT_OHEM_LOSS) for (int i = threadIdx.x; i < OHEM_BINS0; i += blockDim.x) hsh[i] = 0;
-        if constexpr (PH == XENT_OHEM_GRAD) { tsel = x.st->t; gsel = x.st->gscale; }
+        if constexpr (PH == XENT_OHEM_GRAD) { tsel = x.st->t; gsel = x.st->gscale * x.ce_scale; }
         __syncthreads();
     }
     double lsum = 0;
@@ -736,7 +736,7 @@ void launch_softmax_xent_ex(const float* logits, const uint8_t* labels, float* d
 }
 
 __global__ void finalize_loss_kernel(const double* partials, int nparts, long long npix, const float* regsum,
-                                     float rate, float* loss_out, const unsigned long long* den)
+                                     float rate, float* loss_out, const unsigned long long* den, float* terms)
 {
     __shared__ double sh[4];
     double v = 0;
@@ -746,12 +746,13 @@ __global__ void finalize_loss_kernel(const double* partials, int nparts, long lo
         const float ce = den ? (*den ? (float)(t / (double)*den) : 0.f) : (float)(t / (double)npix);
         const float reg = regsum ? 0.5f * rate * regsum[0] : 0.f;
         loss_out[0] = ce + reg;
+        if (terms) { terms[0] = ce; terms[1] = 0.f; terms[2] = reg; }
     }
 }
 void launch_finalize_loss(const double* partials, int nparts, long long npix, const float* regsum,
-                          float rate, float* loss_out, hipStream_t s, const unsigned long long* den)
+                          float rate, float* loss_out, hipStream_t s, const unsigned long long* den, float* terms)
 {
-    hipLaunchKernelGGL(finalize_loss_kernel, dim3(1), dim3(256), 0, s, partials, nparts, npix, regsum, rate, loss_out, den);
+    hipLaunchKernelGGL(finalize_loss_kernel, dim3(1), dim3(256), 0, s, partials, nparts, npix, regsum, rate, loss_out, den, terms);
 }
 
 // ---- K13: softmax -> argmax (of the softmax output, lowest index on ties) ----

@@ -221,14 +221,38 @@ struct XentEx {
     OhemState* st = nullptr;
     unsigned* hist = nullptr;              // the three radix histograms, right behind st
     float tau = 0.f;
+    float ce_scale = 1.f;                  // XENT_OHEM_GRAD: the gradient scale is st->gscale * ce_scale (fcn8s_set_lovasz's ce_weight)
 };
 // weighted (ohem_thresh == 0) or OHEM loss over the same blocked / plain logits as launch_softmax_xent; partials then hold sum w l_p, and
 // finalize_loss divides by st->kept (OHEM) or by npix (weighted).  No host synchronisation.
 void launch_softmax_xent_ex(const float* logits, const uint8_t* labels, float* dlogits, double* partials, long long npix, int C, float grad_scale,
                             hipStream_t s, float* colsum, const PixMap* map, int N, const XentEx& x, float ohem_thresh, long long ohem_min_kept);
-// loss_out[0] = sum(partials)/npix + 0.5*rate*regsum[0]; with `den`: sum(partials)/den[0] (0 when den[0] == 0)
+// loss_out[0] = sum(partials)/npix + 0.5*rate*regsum[0]; with `den`: sum(partials)/den[0] (0 when den[0] == 0); with `terms`: also
+// terms[0] = the cross-entropy term, terms[1] = 0, terms[2] = the L2 term (fcn8s_get_loss_terms)
 void launch_finalize_loss(const double* partials, int nparts, long long npix, const float* regsum,
-                          float rate, float* loss_out, hipStream_t s, const unsigned long long* den = nullptr);
+                          float rate, float* loss_out, hipStream_t s, const unsigned long long* den = nullptr, float* terms = nullptr);
+// ---- the Lovász-softmax loss (lovasz.hip; fcn8s_set_lovasz, fcn8s_op_lovasz_softmax in include/fcn8s_hip.h) ---------------------
+// One scratch of `bytes`: double-buffered keys + payloads [segment][class][pixel] (buffer 0's keys become the [class][pixel] gradient
+// plane after the sort), the per-tile digit histograms, foreground counts and loss partials, G, V, the participation scales, the
+// backward pass's column-sum partials and the Lovász term.
+struct LovaszLayout {
+    int nseg = 0, C = 0, tiles = 0; long long L = 0, nsc = 0;
+    size_t o_keys[2] = {0, 0}, o_pays[2] = {0, 0}, o_hist = 0, o_tcnt = 0, o_part = 0, o_G = 0, o_V = 0, o_w = 0, o_ncls = 0, o_colpart = 0, o_lov = 0;
+    size_t bytes = 0;
+};
+LovaszLayout lovasz_layout(long long npix, int nseg, int C);
+double lovasz_bytes(long long npix, int C, int nmask);        // the algorithmic bytes of the forward + backward stages (profile group "lovasz")
+// keys, sort, gradient plane and the loss; x = logits or probabilities in plain [npix, C] or blocked (map) slots; mask_dev = uint8[C] or
+// null (every class).  The Lovász term lands in ws + o_lov; class_loss (float[nseg C]) may be null.  With `terms` (the model): terms[1] =
+// the term and loss_out[0] = (lce terms[0] + llov terms[1]) + terms[2].
+void launch_lovasz_loss(const float* x, int is_logits, const uint8_t* labels, const PixMap* map, int N, long long npix, const LovaszLayout& y,
+                        int classes_all, const uint8_t* mask_dev, char* ws, float* class_loss, float* terms, float lce, float llov, float* loss_out,
+                        hipStream_t s);
+// out (+)= lambda d L_lov / d x (x = logits: the softmax Jacobian applied to the plane's rows; probabilities: the rows themselves); zero
+// rows for ignored pixels when !accumulate; colsum (may be null): += the column sums of the contribution, in a fixed order
+void launch_lovasz_backward(const float* x, int is_logits, const uint8_t* labels, const PixMap* map, int N, long long npix, const LovaszLayout& y,
+                            char* ws, float lambda, int accumulate, float* out, float* colsum, hipStream_t s);
+void launch_lovasz_total(float* terms, float lce, float* loss_out, hipStream_t s);   // no Lovász term: loss = lce terms[0] + terms[2], terms[1] = 0
 void launch_softmax_argmax(const float* logits, float* softmax_out, long long* argmax_out,
                            long long npix, int C, hipStream_t s, const PixMap* map = nullptr, int N = 0);
 // ---- the k = 2s transposed conv as one GEMM (see PixMap): operand / result re-layouts, all tiny next to the GEMMs -------------

@@ -206,6 +206,11 @@ struct fcn8s_model {
     // fcn8s_set_loss); loss_ws = LOSS_SCRATCH_BYTES of state and histograms + (OHEM) the l_p buffer, grown on first use (a "workspace_allocation")
     int loss_mode = 0, last_loss_mode = 0; float ohem_thresh = 0.f; int64_t ohem_min_kept = 0;
     float* d_cw = nullptr; char* loss_ws = nullptr; size_t loss_ws_bytes = 0;
+    // fcn8s_set_lovasz: L = lov_ce * (the cross-entropy above) + lov_w * L_lov + L2 (lov_on: not the default (1, 0)); the class mask in d_lovmask
+    // (uint8[64], made by fcn8s_set_lovasz); lov_ws = the sort's scratch (LovaszLayout), grown on first use (a "workspace_allocation");
+    // d_terms = the unscaled terms of the last training loss (ce, lovasz, l2; right behind d_lastbias), have_terms once a training loss ran
+    bool lov_on = false, have_terms = false; float lov_ce = 1.f, lov_w = 0.f; int lov_per_image = 0, lov_all = 0;
+    uint8_t* d_lovmask = nullptr; int lov_nmask = 0; char* lov_ws = nullptr; size_t lov_ws_bytes = 0; float* d_terms = nullptr;
     unsigned long long* d_conf = nullptr;
     double loss_sum = 0; int64_t loss_cnt = 0;
     float keep_prob = 1.f, l2_rate = 0.f;
@@ -1816,6 +1821,16 @@ int ensure_loss_ws(fcn8s_model* m, long long npix)
     return FCN8S_OK;
 }
 
+// the Lovász sort's scratch (fcn8s_set_lovasz), grown only
+int ensure_lovasz_ws(fcn8s_model* m, const LovaszLayout& y)
+{
+    if (m->lov_ws && m->lov_ws_bytes >= y.bytes) return FCN8S_OK;
+    if (m->lov_ws) { hipStreamSynchronize(m->stream); hipFree(m->lov_ws); m->lov_ws = nullptr; m->lov_ws_bytes = 0; }
+    HIPCHK(m, hipMalloc((void**)&m->lov_ws, y.bytes));
+    m->lov_ws_bytes = y.bytes; ++m->ws_allocs;
+    return FCN8S_OK;
+}
+
 int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool with_grad)
 {
     hipStream_t s = m->stream;
@@ -1824,6 +1839,15 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
     const int mode = with_grad ? m->loss_mode : 0;            // evaluation keeps the reference's loss
     if (mode) { int rc = ensure_loss_ws(m, npix); if (rc) return rc; }
     OhemState* st = mode ? (OhemState*)m->loss_ws : nullptr;
+    const bool lov = with_grad && m->lov_on;                    // evaluation keeps the reference's loss here too
+    const bool lov_sort = lov && m->lov_w != 0.f;
+    const float gscale = lov ? m->lov_ce * (1.0f / (float)npix) : 1.0f / (float)npix;    // (exactly 1 / npix at lov_ce == 1)
+    LovaszLayout ly;
+    if (lov_sort) {
+        if (npix / (m->lov_per_image ? m->N : 1) >= (1LL << 31)) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_lovasz: a segment holds 2^31 pixels or more");
+        ly = lovasz_layout(npix, m->lov_per_image ? m->N : 1, m->C);
+        int rc = ensure_lovasz_ws(m, ly); if (rc) return rc;
+    }
     // bytes: the logits once (+ dlogits) and the labels; OHEM reads the logits and labels twice and writes + reads l_p (its refinement
     // passes, 4 bytes per pixel each when min_kept decides the threshold, are not counted)
     const double xbytes = mode == 2 ? (double)npix * (m->C * 4 * 3 + 2 + 8) : (double)npix * (m->C * 4 * (with_grad ? 2 : 1) + 1);
@@ -1833,11 +1857,12 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
       if (mode) {
           XentEx x; x.cw = m->d_cw; x.st = st; x.hist = (unsigned*)(m->loss_ws + sizeof(OhemState));
           x.lbuf = mode == 2 ? (float*)(m->loss_ws + LOSS_SCRATCH_BYTES) : nullptr;
-          launch_softmax_xent_ex(blk ? m->logits_b : A(m, "logits"), lab_dev, blk ? m->dlogits_b : m->dlogits, m->d_partials, npix, m->C, 1.0f / (float)npix, s,
+          if (lov) x.ce_scale = m->lov_ce;
+          launch_softmax_xent_ex(blk ? m->logits_b : A(m, "logits"), lab_dev, blk ? m->dlogits_b : m->dlogits, m->d_partials, npix, m->C, gscale, s,
                                  m->d_lastbias, blk ? &m->pm : nullptr, m->N, x, mode == 2 ? m->ohem_thresh : 0.f, (long long)m->ohem_min_kept);
       } else
           launch_softmax_xent(blk ? m->logits_b : A(m, "logits"), lab_dev, with_grad ? (blk ? m->dlogits_b : m->dlogits) : nullptr, m->d_partials, npix, m->C,
-                              1.0f / (float)npix, s, with_grad ? m->d_lastbias : nullptr, blk ? &m->pm : nullptr, m->N); }
+                              gscale, s, with_grad ? m->d_lastbias : nullptr, blk ? &m->pm : nullptr, m->N); }
     if (with_grad) m->last_loss_mode = mode;
     const float* reg = nullptr;
     if (l2_rate != 0.f) {
@@ -1845,7 +1870,19 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
         for (auto k : kDecoderKernels) launch_sumsq(Wp(m, k), m->d_regsum, (long long)P(m, k).numel, s);
         reg = m->d_regsum;
     }
-    launch_finalize_loss(m->d_partials, nb, npix, reg, l2_rate, m->d_loss, s, mode == 2 ? &st->kept : nullptr);
+    launch_finalize_loss(m->d_partials, nb, npix, reg, l2_rate, m->d_loss, s, mode == 2 ? &st->kept : nullptr, with_grad ? m->d_terms : nullptr);
+    if (with_grad) m->have_terms = true;
+    if (lov_sort) {
+        // L_lov and its gradient: keys, sort, Jaccard scan (the loss, now final), then dlogits += lov_w d L_lov / d logits and the bias column sums
+        ProfScope ps(m, "lovasz", 0, lovasz_bytes(npix, m->C, m->lov_nmask));
+        const bool blk = m->tconv_gemm && m->logits_b;
+        const float* lg = blk ? m->logits_b : A(m, "logits");
+        launch_lovasz_loss(lg, 1, lab_dev, blk ? &m->pm : nullptr, m->N, npix, ly, m->lov_all, m->d_lovmask, m->lov_ws, nullptr, m->d_terms,
+                           m->lov_ce, m->lov_w, m->d_loss, s);
+        launch_lovasz_backward(lg, 1, lab_dev, blk ? &m->pm : nullptr, m->N, npix, ly, m->lov_ws, m->lov_w, 1, blk ? m->dlogits_b : m->dlogits,
+                               m->d_lastbias, s);
+    } else if (lov)
+        launch_lovasz_total(m->d_terms, m->lov_ce, m->d_loss, s);
     // The loss is final here, a third of the way into a training step: queue its copy now, so that fcn8s_read_loss waits for this
     // point of the stream only and the host can go on queueing the next step while the backward pass runs (the reference fetches
     // the loss every step, fcn8s_tensorflow.py:554-578; waiting for the whole stream left the GPU idle for ~2 ms per step).
@@ -2147,8 +2184,8 @@ int fcn8s_create(const fcn8s_config* cfg, fcn8s_model** out)
         if ((e = hipMalloc((void**)&m->d_wino_u, ufl * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
         m->ufl = ufl;
     }
-    if ((e = hipMalloc((void**)&m->d_loss, (2 + 64) * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
-    m->d_regsum = m->d_loss + 1; m->d_lastbias = m->d_loss + 2;
+    if ((e = hipMalloc((void**)&m->d_loss, (2 + 64 + 4) * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
+    m->d_regsum = m->d_loss + 1; m->d_lastbias = m->d_loss + 2; m->d_terms = m->d_loss + 2 + 64;
     if ((e = hipMalloc((void**)&m->d_conf, cc * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
     if ((e = hipMalloc((void**)&m->d_fp, sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
     m->tg_kp = (4 * m->C + 63) / 64 * 64;
@@ -2223,6 +2260,8 @@ int fcn8s_destroy(fcn8s_model* m)
     if (m->tta_buf) hipFree(m->tta_buf);
     if (m->loss_ws) hipFree(m->loss_ws);
     if (m->d_cw) hipFree(m->d_cw);
+    if (m->lov_ws) hipFree(m->lov_ws);
+    if (m->d_lovmask) hipFree(m->d_lovmask);
     delete m;
     // the model is gone either way; a communicator that had failed is reported once, with its reason in fcn8s_last_error(NULL)
     if (rc_comm) { g_last_error = comm_text; return rc_comm; }
@@ -2954,6 +2993,54 @@ int fcn8s_get_loss_stats(fcn8s_model* m, int64_t* valid, int64_t* kept, float* t
     if (valid) *valid = (int64_t)st.valid;
     if (kept) *kept = (int64_t)(ohem ? st.kept : st.valid);
     if (threshold) *threshold = ohem ? st.t : 0.f;
+    return FCN8S_OK;
+}
+
+// the arguments of fcn8s_set_lovasz (mask on the host, or nullptr = every class)
+static int check_lovasz_args(fcn8s_model* m, float ce_weight, float lovasz_weight, int per_image, int classes_all, const uint8_t* mask, int nmask, int C)
+{
+    if (!std::isfinite(ce_weight) || !std::isfinite(lovasz_weight) || ce_weight < 0.f || lovasz_weight < 0.f)
+        return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_lovasz: the weights must be finite and >= 0");
+    if (ce_weight == 0.f && lovasz_weight == 0.f) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_lovasz: the weights must not both be 0");
+    if ((per_image != 0 && per_image != 1) || (classes_all != 0 && classes_all != 1))
+        return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_lovasz: per_image and classes_all must be 0 or 1");
+    if (mask) {
+        if (nmask != C) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_lovasz: nmask must equal num_classes (" + std::to_string(C) + ")");
+        bool any = false;
+        for (int i = 0; i < nmask; ++i) any |= mask[i] != 0;
+        if (!any) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_lovasz: the class mask must not be all zero");
+    }
+    return FCN8S_OK;
+}
+
+int fcn8s_set_lovasz(fcn8s_model* m, float ce_weight, float lovasz_weight, int per_image, int classes_all, const uint8_t* class_mask, int nmask)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    int rc = check_lovasz_args(m, ce_weight, lovasz_weight, per_image, classes_all, class_mask, nmask, m->C); if (rc) return rc;
+    const bool on = !(ce_weight == 1.f && lovasz_weight == 0.f);
+    if (on) {
+        if (!m->d_lovmask) HIPCHK(m, hipMalloc((void**)&m->d_lovmask, 64));
+        uint8_t h[64] = {};
+        int n = 0;
+        for (int c = 0; c < m->C; ++c) { h[c] = class_mask ? (class_mask[c] != 0) : 1; n += h[c]; }
+        HIPCHK(m, hipStreamSynchronize(m->stream));          // (a queued step may still read the old mask)
+        HIPCHK(m, hipMemcpy(m->d_lovmask, h, 64, hipMemcpyHostToDevice));
+        m->lov_nmask = n;
+    }
+    m->lov_on = on; m->lov_ce = ce_weight; m->lov_w = on ? lovasz_weight : 0.f; m->lov_per_image = per_image; m->lov_all = classes_all;
+    return FCN8S_OK;
+}
+
+int fcn8s_get_loss_terms(fcn8s_model* m, float* ce, float* lovasz, float* l2)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!m->have_terms) return fail(m, FCN8S_ERR_STATE, "fcn8s_get_loss_terms: no training loss has run yet");
+    float t[3];
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(t, m->d_terms, sizeof t, hipMemcpyDeviceToHost));
+    if (ce) *ce = t[0];
+    if (lovasz) *lovasz = t[1];
+    if (l2) *l2 = t[2];
     return FCN8S_OK;
 }
 
@@ -3738,6 +3825,23 @@ int fcn8s_op_softmax_xent_ex(void* stream, const float* logits, const uint8_t* l
         hipMemcpy(stats_dev, h, sizeof h, hipMemcpyHostToDevice);
     }
     hipFree(ws);
+    OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_lovasz_softmax(void* stream, const float* x, int x_is_logits, const uint8_t* labels, int64_t nseg, int64_t seg_pixels, int C,
+                            int classes_all, const uint8_t* class_mask_dev, float* loss_out_dev, float* grad_out, float* class_loss_out)
+{
+    if (!x || !labels || !loss_out_dev || nseg < 1 || seg_pixels < 1 || C < 1 || C > 64 || (x_is_logits != 0 && x_is_logits != 1) ||
+        (classes_all != 0 && classes_all != 1) || nseg > 65535 || seg_pixels >= (1LL << 31))
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "fcn8s_op_lovasz_softmax: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const long long npix = (long long)nseg * seg_pixels;
+    const LovaszLayout y = lovasz_layout(npix, (int)nseg, C);
+    char* ws = nullptr;
+    if (hipMalloc((void**)&ws, y.bytes) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
+    launch_lovasz_loss(x, x_is_logits, labels, nullptr, 0, npix, y, classes_all, class_mask_dev, ws, class_loss_out, nullptr, 1.f, 1.f, nullptr, s);
+    hipMemcpyAsync(loss_out_dev, ws + y.o_lov, sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (grad_out) launch_lovasz_backward(x, x_is_logits, labels, nullptr, 0, npix, y, ws, 1.f, 0, grad_out, nullptr, s);
+    hipStreamSynchronize(s); hipFree(ws);
     OPCHK(); return FCN8S_OK;
 }
 int fcn8s_op_softmax_argmax(void* stream, const float* logits, float* sm, int64_t* am, int64_t npix, int C)

@@ -125,6 +125,7 @@ class Engine:
         self._label_calls = 0
         self._bad = None
         self.loss_config = None              # set_loss: the training loss's configuration (None = the reference's mean)
+        self.lovasz_config = None            # set_lovasz: the Lovász-softmax term's configuration (None = off)
         self.replica_check_every = 100      # data-parallel runs: compare global step + parameter checksum across ranks every so many steps (0 = never)
         self._sync_stream()
 
@@ -438,6 +439,25 @@ class Engine:
         self.loss_config = None if (w is None and t == 0.0) else dict(
             class_weights=None if class_weights is None else np.asarray(class_weights, np.float32).copy(),
             ohem_thresh=ohem_thresh if t else None, ohem_min_kept=k)
+
+    def set_lovasz(self, lovasz_weight, ce_weight=1.0, per_image=False, classes='present'):
+        """The Lovász-softmax term of the training loss (fcn8s_set_lovasz; definitions in include/fcn8s_hip.h, restated in loss.py):
+        L = ce_weight * (the cross-entropy of set_loss) + lovasz_weight * L_lov + L2.  `per_image` sorts each image on its own;
+        `classes` is 'present', 'all' or a list of logical class ids (the padding classes never take part).  set_lovasz(0) restores the
+        default.  Evaluation keeps the reference's loss."""
+        ce, lov, pi, ca, mask = loss_mod.validate_lovasz(lovasz_weight, ce_weight, per_image, classes, self.logical_classes)
+        full = np.zeros(self.num_classes, np.uint8)
+        full[:self.logical_classes] = mask
+        arr = (C.c_uint8 * self.num_classes)(*full.tolist())
+        L.check(L.lib.fcn8s_set_lovasz(self.h, ce, lov, pi, ca, arr, self.num_classes), self.h)
+        self.lovasz_config = None if (lov == 0.0 and ce == 1.0) else dict(
+            lovasz_weight=lov, ce_weight=ce, per_image=bool(pi), classes=classes if isinstance(classes, str) else list(classes))
+
+    def loss_terms(self):
+        """The unscaled terms of the last training loss: dict(ce, lovasz, l2) (fcn8s_get_loss_terms; synchronises)."""
+        ce = C.c_float(); lv = C.c_float(); l2 = C.c_float()
+        L.check(L.lib.fcn8s_get_loss_terms(self.h, C.byref(ce), C.byref(lv), C.byref(l2)), self.h)
+        return dict(ce=float(ce.value), lovasz=float(lv.value), l2=float(l2.value))
 
     def loss_stats(self):
         """|V|, |K| and the threshold t of the last training loss (fcn8s_get_loss_stats; synchronises)."""

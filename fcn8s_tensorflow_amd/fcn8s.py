@@ -204,14 +204,21 @@ class FCN8s:
               training_loss_display_averaging=3,
               class_weights=None,
               ohem_thresh=None,
-              ohem_min_kept=100000):
+              ohem_min_kept=100000,
+              lovasz_weight=0.0,
+              lovasz_per_image=False,
+              lovasz_classes='present',
+              ce_weight=1.0):
         '''Trains the model; arguments as fcn8s_tensorflow.py:424-503.  Summaries are written as TensorBoard
         event files (`<summaries_dir>/<summaries_name>[_eval]/events.out.tfevents.*`: total_loss, learning_rate and
         mean / stddev / max / min / histogram of the ten watched weight-bias pairs, :331-366) and, for reading
         without TensorBoard, as JSON lines (`scalars.jsonl`) next to them; if `summaries_dir` is None nothing is recorded.
         `class_weights` (one per class), `ohem_thresh` (a probability in (0, 1]) and `ohem_min_kept` set the training loss for the duration
         of the call (Engine.set_loss, loss.py: class-weighted and / or hard-pixel-mined cross-entropy); the evaluations keep reporting the
-        reference's loss, and the previous loss configuration is restored when train() returns or raises.'''
+        reference's loss, and the previous loss configuration is restored when train() returns or raises.
+        `lovasz_weight`, `lovasz_per_image`, `lovasz_classes` ('present', 'all' or a list of class ids) and `ce_weight` add the
+        Lovász-softmax term for the duration of the call (Engine.set_lovasz, loss.py: ce_weight * cross-entropy + lovasz_weight * Lovász);
+        the evaluations keep reporting the reference's loss, and the previous configuration is restored when train() returns or raises.'''
         if self.engine.precision == 'fp8_infer':
             raise ValueError("The 'fp8_infer' precision is inference only; switch the engine to another precision "
                              "(e.g. model.engine.set_precision('bf16_train')) before training.")
@@ -219,6 +226,9 @@ class FCN8s:
         custom_loss = class_weights is not None or bool(ohem_thresh)
         if custom_loss:
             loss_mod.validate(class_weights, ohem_thresh, ohem_min_kept, self.engine.logical_classes)
+        custom_lovasz = lovasz_weight != 0 or ce_weight != 1.0
+        if custom_lovasz:
+            loss_mod.validate_lovasz(lovasz_weight, ce_weight, lovasz_per_image, lovasz_classes, self.engine.logical_classes)
         if eval_dataset not in ('train', 'val'):
             raise ValueError("`eval_dataset` must be one of 'train' or 'val', but is '{}'.".format(eval_dataset))
         if eval_dataset == 'val' and (val_generator is None or val_steps is None):
@@ -242,9 +252,12 @@ class FCN8s:
                        'val': (val_generator, val_steps, 'Evaluation on validation dataset')}[eval_dataset]
 
         prev_loss = self.engine.loss_config
+        prev_lovasz = self.engine.lovasz_config
         try:
             if custom_loss:
                 self.engine.set_loss(class_weights, ohem_thresh, ohem_min_kept)
+            if custom_lovasz:
+                self.engine.set_lovasz(lovasz_weight, ce_weight, lovasz_per_image, lovasz_classes)
             for epoch in range(1, epochs + 1):
                 self._run_epoch(train_generator, steps_per_epoch, learning_rate_schedule, keep_prob, l2_regularization,
                                 'Epoch {}/{}'.format(epoch, epochs), training_loss_display_averaging,
@@ -271,6 +284,8 @@ class FCN8s:
         finally:
             if custom_loss:
                 self.engine.set_loss(**(prev_loss or {}))
+            if custom_lovasz:
+                self.engine.set_lovasz(**(prev_lovasz or dict(lovasz_weight=0.0)))
             for log in (train_log, eval_log):          # the event files are complete and closed when train() returns or raises
                 if log is not None:
                     log.close()

@@ -1,5 +1,6 @@
 """Class-weighted and hard-pixel-mined (OHEM) cross-entropy for training (fcn8s_set_loss): argument validation shared with the engine,
-a float64 restatement of both modes for the tests, and class-weight recipes computed from label counts on the host.
+a float64 restatement of both modes for the tests, and class-weight recipes computed from label counts on the host.  The Lovász-softmax
+term (fcn8s_set_lovasz) has its validation and float64 restatement at the end of the file.
 
 P = pixels of the batch, V = the valid pixels (label id < C), l_p = the per-pixel loss m + log(sum exp(v - m)) - v[y_p] (>= 0),
 w_c = the class weights.
@@ -127,3 +128,122 @@ def enet_weights(counts, c=1.02):
     if not c > 1.0:
         raise ValueError("`c` must be > 1 (the weights are 1 / ln(c + p))")
     return (1.0 / np.log(c + counts / counts.sum())).astype(np.float32)
+
+
+# ---- Lovász-softmax (fcn8s_set_lovasz; the definition is in include/fcn8s_hip.h) -------------------------------------------------------
+def validate_lovasz(lovasz_weight, ce_weight=1.0, per_image=False, classes='present', num_classes=None):
+    """-> (ce_weight, lovasz_weight, per_image 0/1, classes_all 0/1, uint8 mask [num_classes]); ValueError for what fcn8s_set_lovasz
+    rejects.  `classes`: 'present', 'all' or a list of class ids (participating whether present or not, as the published code's list)."""
+    def weight(v, name):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("`{}` must be a number, got {!r}".format(name, v))
+        if not math.isfinite(f) or f < 0:
+            raise ValueError("`{}` must be finite and >= 0, got {!r}".format(name, v))
+        return float(np.float32(f))
+    lov, ce = weight(lovasz_weight, 'lovasz_weight'), weight(ce_weight, 'ce_weight')
+    if lov == 0.0 and ce == 0.0:
+        raise ValueError("`lovasz_weight` and `ce_weight` must not both be 0")
+    if per_image not in (0, 1, False, True):
+        raise ValueError("`per_image` must be a bool, got {!r}".format(per_image))
+    mask = np.ones(num_classes, np.uint8)
+    if isinstance(classes, str):
+        if classes not in ('present', 'all'):
+            raise ValueError("`classes` must be 'present', 'all' or a list of class ids, got {!r}".format(classes))
+        classes_all = int(classes == 'all')
+    else:
+        ids = np.asarray(list(classes) if not isinstance(classes, np.ndarray) else classes).reshape(-1)
+        if ids.size == 0 or ids.dtype.kind not in 'iu' or (ids < 0).any() or (ids >= num_classes).any():
+            raise ValueError("`classes` must be a non-empty list of class ids in [0, {}), got {!r}".format(num_classes, classes))
+        mask[:] = 0
+        mask[ids] = 1
+        classes_all = 1
+    return ce, lov, int(bool(per_image)), classes_all, mask
+
+
+def lovasz_grad(fg_sorted):
+    """The Jaccard gradient g_r of a sorted foreground indicator in closed form (exact integer counts, float64):
+    foreground 1 / U_r, background I_r / (U_{r-1} U_r) with U_0 = G; G = 0: g_1 = 1, all other 0."""
+    fg = np.asarray(fg_sorted).astype(np.int64).reshape(-1)
+    n = fg.size
+    g = np.zeros(n)
+    if n == 0:
+        return g
+    G = int(fg.sum())
+    if G == 0:
+        g[0] = 1.0
+        return g
+    r = np.arange(1, n + 1, dtype=np.int64)
+    f = np.cumsum(fg)
+    U = (G + r - f).astype(np.float64)
+    Uprev = (G + r - 1 - (f - fg)).astype(np.float64)
+    I = (G - f).astype(np.float64)
+    return np.where(fg == 1, 1.0 / U, I / (Uprev * U))
+
+
+def lovasz_grad_cumsum(fg_sorted):
+    """The published form: J_r = 1 - I_r / U_r from cumulative sums, g = J_r - J_{r-1} (float64 here)."""
+    fg = np.asarray(fg_sorted, np.float64).reshape(-1)
+    if fg.size == 0:
+        return fg.copy()
+    gts = fg.sum()
+    inter = gts - np.cumsum(fg)
+    union = gts + np.cumsum(1.0 - fg)
+    j = 1.0 - inter / union
+    j[1:] = j[1:] - j[:-1]
+    return j
+
+
+def lovasz_restate(x, labels, N, per_image=False, classes='present', x_is='logits', num_classes=None):
+    """The Lovász-softmax loss in float64 with the closed-form gradient.  x (P, C): logits (torch's float64 softmax), or 'probs' (probabilities;
+    pass the device's fp32 ones so that the errors, e = float32(1 - p) for the foreground and p otherwise, and thus the order, are the
+    device's own).  labels (P,) ids (>= C: ignore); N images of P / N pixels each.
+    -> dict(loss, class_loss (S, C) (0 outside C_s), participating (S, C) bool, grad_prob (P, C) = d L / d prob, grad_logits (P, C) =
+    the softmax Jacobian applied to it)."""
+    x = np.asarray(x)
+    P, C = x.shape
+    lab = np.asarray(labels).reshape(-1).astype(np.int64)
+    _, _, _, classes_all, mask = validate_lovasz(1.0, 1.0, per_image, classes, num_classes or C)
+    if x_is == 'logits':
+        import torch                      # (torch's float64 softmax: the probabilities, and so the ties, of a torch restatement)
+        p = torch.softmax(torch.from_numpy(x.astype(np.float64)), 1).numpy()
+        pf = p
+    elif x_is == 'probs':
+        pf = x.astype(np.float32)
+        p = pf.astype(np.float64)
+    else:
+        raise ValueError("x_is must be 'logits' or 'probs'")
+    S = int(N) if per_image else 1
+    L = P // S
+    class_loss = np.zeros((S, C))
+    part = np.zeros((S, C), bool)
+    gp = np.zeros((P, C))
+    total = 0.0
+    for s in range(S):
+        off = s * L
+        idx = off + np.nonzero(lab[off:off + L] < C)[0]
+        ls = lab[idx]
+        G = np.array([(ls == c).sum() for c in range(C)])
+        on = (mask[:C] > 0) & ((G > 0) | bool(classes_all))
+        part[s] = on
+        ncs = int(on.sum())
+        seg = 0.0
+        for c in np.nonzero(on)[0]:
+            fg = ls == c
+            if x_is == 'probs':
+                e = np.where(fg, (np.float32(1.0) - pf[idx, c]).astype(np.float32), pf[idx, c]).astype(np.float64)
+            else:
+                e = np.where(fg, 1.0 - p[idx, c], p[idx, c])
+            order = np.argsort(-e, kind='stable')
+            g = lovasz_grad(fg[order])
+            lc = float(np.dot(e[order], g))
+            class_loss[s, c] = lc
+            seg += lc
+            sgn = np.sign(p[idx[order], c] - fg[order])
+            gp[idx[order], c] = g * sgn / (S * ncs)
+        total += seg / ncs if ncs else 0.0
+    valid = lab < C
+    gz = p * (gp - (gp * p).sum(1, keepdims=True))
+    gz[~valid] = 0.0
+    return dict(loss=total / S, class_loss=class_loss, participating=part, grad_prob=gp, grad_logits=gz)

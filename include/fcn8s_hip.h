@@ -194,6 +194,40 @@ int fcn8s_read_loss(fcn8s_model* m, float* loss_out);                /* synchron
 int fcn8s_set_loss(fcn8s_model* m, const float* class_weights, int nweights, float ohem_thresh, int64_t ohem_min_kept);
 int fcn8s_get_loss_stats(fcn8s_model* m, int64_t* valid, int64_t* kept, float* threshold);
 
+/* ---- the training objective: Lovász-softmax (Berman, Rannen Triki, Blaschko, CVPR 2018), a surrogate of the Jaccard index -------------
+ * Definitions, per training loss on each rank's own batch (as for OHEM):
+ *   P = N*H*W pixels, p = (n*H + h)*W + w, logits z, labels y_p (ids >= C: ignore).  prob[p,k] = expf(z_k - max) / sum in fp32, bit for
+ *   bit what fcn8s_op_softmax_argmax and prediction return (same expression, classes summed in order).
+ *   Segments s: the whole batch (per_image = 0) or each image (per_image = 1); V_s = the valid pixels of s; |S| = 1 or N.
+ *   Participating classes: a mask M over the library's C classes; classes_all = 0 ("present"): C_s = {c : M[c], G_{s,c} > 0};
+ *   classes_all = 1: C_s = {c : M[c]}.
+ *   Errors: fg = [y_p = c]; e_{p,c} = fl(1 - prob[p,c]) if fg, else prob[p,c] (all in [0, 1]).
+ *   Order pi_{s,c} over V_s: e descending, ties by ascending p (= torch.sort(e, descending=True, stable=True)).
+ *   Counts at rank r (1-based): f_r = foreground pixels among the first r, G = G_{s,c} = foreground pixels in V_s, I_r = G - f_r,
+ *   U_r = G + r - f_r.  Jaccard gradient (exact, cancellation-free; = the reference's J_r - J_{r-1}, J_r = 1 - I_r / U_r, J_0 = 0):
+ *   foreground at rank r: g_r = 1 / U_r; background: g_r = I_r / (U_{r-1} U_r), U_0 = G; G = 0: g_1 = 1, every other g_r = 0.
+ *   Evaluated in double from the exact integer counts and rounded to float once.
+ *   l_{s,c} = sum_r e_{pi(r)} g_r; a segment's loss = the mean of l_{s,c} over C_s (0 when C_s is empty); L_lov = the mean over all
+ *   |S| segments (an image without a participating class counts as 0).
+ *   L = ce_weight * L_ce + lovasz_weight * L_lov + (the L2 term as before).  L_ce is what fcn8s_set_loss configures (class weights and
+ *   OHEM act on the CE term only); (ce_weight, lovasz_weight) = (1, 0) is the default loss bit for bit.
+ *   Gradient: d L_lov / d prob[p,c] = g_{rank(p,c)} sgn(prob[p,c] - fg) / (|S| |C_s|) for c in C_s (sgn(0) = 0), 0 elsewhere and on ignored
+ *   pixels; dlogits += lovasz_weight * prob (q - <q, prob>) with q the pixel's row of d L_lov / d prob; it reaches the last transposed
+ *   conv's bias gradient too.
+ * Data parallel: with per_image = 1 and grad_scale = 1/world, equal shards give exactly the big batch's definition (a mean over the
+ * images); per_image = 0 sorts each rank's own batch, like OHEM.  The path is deterministic whatever the `deterministic` option says
+ * (integer counts, float sums in a fixed order, no float atomics).  The configuration applies to the training losses only
+ * (fcn8s_forward_loss, fcn8s_train_step); evaluation, the metrics and prediction keep the reference's loss.  It survives
+ * fcn8s_set_precision, fcn8s_set_option and fcn8s_set_loss.  The scratch (double-buffered keys and payloads of |S| x C x P/|S| entries,
+ * about 2 x 1.34 GB at 16 x 1024x512 x 20, plus histograms) is grown on first use and counted in "workspace_allocations"; the gradient
+ * plane reuses the first key buffer.  Profile group "lovasz".
+ * fcn8s_set_lovasz: ce_weight, lovasz_weight finite and >= 0, not both 0; per_image, classes_all in {0, 1}; class_mask = host
+ *   uint8[nmask], nmask == num_classes, not all zero (NULL: every class).  (1, 0, ...) restores the default.  FCN8S_ERR_BAD_ARG otherwise.
+ * fcn8s_get_loss_terms: the unscaled terms L_ce, L_lov (0 when the Lovász term is off) and the L2 term of the last training loss
+ *   (synchronises, like fcn8s_read_loss); FCN8S_ERR_STATE before any training loss.                                                  */
+int fcn8s_set_lovasz(fcn8s_model* m, float ce_weight, float lovasz_weight, int per_image, int classes_all, const uint8_t* class_mask, int nmask);
+int fcn8s_get_loss_terms(fcn8s_model* m, float* ce, float* lovasz, float* l2);
+
 /* ---- data parallelism inside the library: one RCCL rank per model (SURVEY section 7 step 7, 8b "RCCL error"; the reference is one
  * tf.Session on one device, fcn8s_tensorflow.py:65, so there is nothing to cite for the collective itself).  A caller that keeps the
  * reference's Python and binds this ABI gets multi-GPU training without torch.distributed:
@@ -483,6 +517,12 @@ int fcn8s_op_softmax_xent(void* stream, const float* logits, const uint8_t* labe
 int fcn8s_op_softmax_xent_ex(void* stream, const float* logits, const uint8_t* label_ids, const float* class_weights_dev,
                              float ohem_thresh, int64_t ohem_min_kept, float* dlogits, float* loss_out_dev,
                              float* pixel_loss_dev, int64_t* stats_dev, int64_t npix, int C);
+/* the Lovász-softmax loss of fcn8s_set_lovasz on plain [nseg * seg_pixels, C] data (C <= 64): x = logits (x_is_logits = 1) or
+ * probabilities (0; the errors are then taken from x itself); nseg segments of seg_pixels consecutive pixels each; class_mask_dev =
+ * device uint8[C] or NULL (every class).  loss_out_dev[0] = L_lov; grad_out (may be NULL) = d L_lov / d x, zero rows for ignored pixels;
+ * class_loss_out (may be NULL) = device float[nseg C], l_{s,c} (0 for a class outside C_s).  Synchronises. */
+int fcn8s_op_lovasz_softmax(void* stream, const float* x, int x_is_logits, const uint8_t* label_ids, int64_t nseg, int64_t seg_pixels, int C,
+                            int classes_all, const uint8_t* class_mask_dev, float* loss_out_dev, float* grad_out, float* class_loss_out);
 int fcn8s_op_softmax_argmax(void* stream, const float* logits, float* softmax_out, int64_t* argmax_out,
                             int64_t npix, int C);
 int fcn8s_op_confusion(void* stream, const uint8_t* label_ids, const int64_t* pred_ids, int64_t npix,
