@@ -29,6 +29,13 @@ class Config(C.Structure):
                 ("ext_params", C.c_void_p), ("ext_grads", C.c_void_p)]
 
 
+class CrfParams(C.Structure):
+    """fcn8s_crf_params (the mean-field CRF of fcn8s_predict_crf; defaults and validation: crf.py)."""
+    _fields_ = [("iterations", C.c_int32), ("radius", C.c_int32), ("dilation", C.c_int32),
+                ("w_appearance", C.c_float), ("w_smooth", C.c_float),
+                ("theta_alpha", C.c_float), ("theta_beta", C.c_float), ("theta_gamma", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/fcn8s_hip.h declares
 _p, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _i64, _dp, _i64p, _fp = C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_float)
@@ -86,6 +93,7 @@ SIGNATURES = {
     "fcn8s_metrics_set_raw": (_i, [_p, _p, C.c_double, _i64]),
     "fcn8s_predict": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _i]),
     "fcn8s_predict_tta": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _p, _i]),
+    "fcn8s_predict_crf": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _i, _p, _i]),
     "fcn8s_global_step": (_i64, [_p]),
     "fcn8s_set_global_step": (_i, [_p, _i64]),
     "fcn8s_get_opt_state": (_i, [_p, _p, _p, _sz]),
@@ -110,6 +118,8 @@ SIGNATURES = {
     "fcn8s_op_preprocess": (_i, [_p, _p, _i, _p, _i64]),
     "fcn8s_op_tta_input": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fcn8s_op_tta_accumulate": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i, _p, _p]),
+    "fcn8s_op_crf_work_floats": (_sz, [_i, _i, _i, _i, _p]),
+    "fcn8s_op_crf_meanfield": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "fcn8s_op_augment_u8": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i]),
     "fcn8s_op_resample_u8": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i]),
     "fcn8s_op_conv2d": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i]),

@@ -346,6 +346,14 @@ void launch_tta_input(const void* img, int dtype, int N, int H, int W, int Hs, i
 // argmax_out [N,H,W] (acc not written; may be nullptr when first and last)
 void launch_tta_accumulate(const float* logits, const PixMap& map, int N, int Hs, int Ws, int flip, int C, int H, int W, float* acc,
                            int first, int last, int npasses, float* softmax_out, long long* argmax_out, hipStream_t s);
+// crf.hip (fcn8s_op_crf_meanfield / fcn8s_predict_crf).  One mean-field update qin -> qout [N,H,W,C] (qout != qin, qout != prob; the definition is in
+// fcn8s_hip.h): messages from qin over the (2 radius + 1)^2 window of the given dilation weighted by the uint8 image img [N,H,W,3], unary log(prob),
+// softmax; am (may be nullptr): the argmax of qout.  Defers FCN8S_ERR_SHAPE for a C / radius that crf_shape_supported refuses.
+bool crf_shape_supported(int C, int radius);
+void launch_crf_meanfield(const float* qin, const float* prob, const unsigned char* img, int N, int H, int W, int C, int radius, int dilation,
+                          float w_app, float w_smooth, float theta_alpha, float theta_beta, float theta_gamma, float* qout, long long* am, hipStream_t s);
+// am[i] = argmax_c p[i, c], lowest index on ties
+void launch_crf_argmax(const float* p, long long npix, int C, long long* am, hipStream_t s);
 // wrapping sum over every 61st element's bit pattern (weighted by position): changes whenever an optimizer step or a bulk copy touches the buffer
 void launch_fingerprint(const float* x, long long n, unsigned long long* out, hipStream_t s);
 void launch_init_normal(float* w, long long n, float stddev, int truncated, unsigned long long seed,

@@ -178,6 +178,7 @@ struct fcn8s_model {
     std::set<std::string> g16_stale;                                      // bf16_train copies ("x:<layer>" / "d:<layer>") whose zero border belongs to another shape (fcn8s_predict_tta re-plans)
     int64_t ws_allocs = 0;                                                // statistic "workspace_allocations": device allocations for the workspace, the TTA scratch, the bf16 copies and the cached filter banks
     bool x0_ready = false;                                                // forward(): x0 is already written (fcn8s_predict_tta's tta_input), skip the preprocess kernel
+    char* crf_buf = nullptr; size_t crf_bytes = 0;                        // fcn8s_predict_crf: staged images, the mean softmax, the two mean-field buffers, staged output (grown, never shrunk)
     char* tta_buf = nullptr; size_t tta_bytes = 0;                        // fcn8s_predict_tta: staged images, accumulator, staged output (grown, never shrunk)
     hipStream_t stream = nullptr;
     int64_t step = 0;
@@ -2258,6 +2259,7 @@ int fcn8s_destroy(fcn8s_model* m)
     if (m->copy_stream) hipStreamDestroy(m->copy_stream);
     if (m->arena) hipFree(m->arena);
     if (m->tta_buf) hipFree(m->tta_buf);
+    if (m->crf_buf) hipFree(m->crf_buf);
     if (m->loss_ws) hipFree(m->loss_ws);
     if (m->d_cw) hipFree(m->d_cw);
     if (m->lov_ws) hipFree(m->lov_ws);
@@ -3261,6 +3263,85 @@ int fcn8s_predict_tta(fcn8s_model* m, const void* images, int dtype, int N, int 
     return FCN8S_OK;
 }
 
+// ---- mean-field CRF refinement (definition: fcn8s_hip.h at fcn8s_crf_params) ------------------------------------------------------
+// the field of p that lies outside its range, or nullptr
+static const char* crf_bad_field(const fcn8s_crf_params* p)
+{
+    if (p->iterations < 0 || p->iterations > 32) return "iterations (0..32)";
+    if (p->radius < 1 || p->radius > 7) return "radius (1..7)";
+    if (p->dilation < 1 || p->dilation > 8) return "dilation (1..8)";
+    if (!std::isfinite(p->w_appearance) || !(p->w_appearance >= 0.f)) return "w_appearance (finite, >= 0)";
+    if (!std::isfinite(p->w_smooth) || !(p->w_smooth >= 0.f)) return "w_smooth (finite, >= 0)";
+    if (!std::isfinite(p->theta_alpha) || !(p->theta_alpha > 0.f)) return "theta_alpha (finite, > 0)";
+    if (!std::isfinite(p->theta_beta) || !(p->theta_beta > 0.f)) return "theta_beta (finite, > 0)";
+    if (!std::isfinite(p->theta_gamma) || !(p->theta_gamma > 0.f)) return "theta_gamma (finite, > 0)";
+    return nullptr;
+}
+// iterations >= 1 updates from prob; update t writes q_out when it is the last and q_out is given, else work half (t & 1); m (may be nullptr): profile group
+static void crf_run(fcn8s_model* m, hipStream_t s, const float* prob, const uint8_t* images, int N, int H, int W, int C, const fcn8s_crf_params* p,
+                    float* work, float* q_out, long long* argmax_out)
+{
+    const size_t n = (size_t)N * H * W * C;
+    const long long npix = (long long)N * H * W;
+    const double taps = (double)(2 * p->radius + 1) * (2 * p->radius + 1) - 1;
+    const float* src = prob;
+    for (int t = 1; t <= p->iterations; ++t) {
+        const bool last = t == p->iterations;
+        float* dst = last && q_out ? q_out : work + (size_t)(t & 1) * n;
+        // algorithmic: read Q, read P, write Q, read the image (+ the argmax); 2 flops per FMA of the two messages
+        const double by = (double)npix * (12.0 * C + 3.0) + (last && argmax_out ? 8.0 * npix : 0.0), fl = (double)npix * taps * 4.0 * C;
+        auto launch = [&] {
+            launch_crf_meanfield(src, prob, images, N, H, W, C, p->radius, p->dilation, p->w_appearance, p->w_smooth, p->theta_alpha, p->theta_beta,
+                                 p->theta_gamma, dst, last ? argmax_out : nullptr, s);
+        };
+        if (m) { ProfScope ps(m, "crf_meanfield", fl, by); launch(); }
+        else launch();
+        src = dst;
+    }
+}
+
+int fcn8s_predict_crf(fcn8s_model* m, const void* images, int dtype, int N, int H, int W, const float* scales, int nscales, int flip,
+                      const fcn8s_crf_params* crf, int argmax, void* out, int where)
+{
+    if (!m) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_crf: null argument");
+    if (crf) { const char* bad = crf_bad_field(crf); if (bad) return fail(m, FCN8S_ERR_BAD_ARG, std::string("fcn8s_predict_crf: crf_params.") + bad + " is out of range"); }
+    if (!crf || crf->iterations == 0) return fcn8s_predict_tta(m, images, dtype, N, H, W, scales, nscales, flip, argmax, out, where);
+    if (!images || !out || !scales) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_crf: null argument");
+    if (dtype != FCN8S_IMG_U8) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_crf: the mean field (iterations > 0) reads the colours of uint8 images; float32 images are not taken");
+    if (where != FCN8S_HOST && where != FCN8S_DEVICE) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_crf: `where` must be FCN8S_HOST or FCN8S_DEVICE");
+    if (N <= 0 || H <= 0 || W <= 0) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_crf: N, H and W must be positive");
+    const int C = m->C;
+    if (!crf_shape_supported(C, crf->radius)) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_crf: this many classes do not fit the mean field's LDS tile at this radius");
+    // scratch: the staged images (host input), the mean softmax, the two mean-field buffers, the staged output (host output)
+    const size_t npix = (size_t)N * H * W, b_q = align_up(npix * C * sizeof(float), 256);
+    const bool host = where == FCN8S_HOST;
+    const size_t b_img = host ? align_up(npix * 3, 256) : 0;
+    const size_t b_out = host ? (argmax ? align_up(npix * sizeof(long long), 256) : b_q) : 0;
+    const size_t need = b_img + 3 * b_q + b_out;
+    if (m->crf_bytes < need) {
+        if (m->crf_buf) { HIPCHK(m, hipStreamSynchronize(m->stream)); hipFree(m->crf_buf); m->crf_buf = nullptr; m->crf_bytes = 0; }
+        HIPCHK(m, hipMalloc((void**)&m->crf_buf, need));
+        m->crf_bytes = need; ++m->ws_allocs;
+    }
+    hipStream_t s = m->stream;
+    const uint8_t* img = (const uint8_t*)images;
+    if (host) { HIPCHK(m, hipMemcpyAsync(m->crf_buf, images, npix * 3, hipMemcpyHostToDevice, s)); img = (const uint8_t*)m->crf_buf; }
+    float* prob = (float*)(m->crf_buf + b_img);
+    float* work = (float*)(m->crf_buf + b_img + b_q);          // 2 b_q bytes: crf_run's two halves of N H W C floats
+    void* dout = host ? (void*)(m->crf_buf + b_img + 3 * b_q) : out;
+    int rc = fcn8s_predict_tta(m, img, dtype, N, H, W, scales, nscales, flip, 0, prob, FCN8S_DEVICE); if (rc) return rc;
+    take_deferred_error(nullptr);
+    // argmax: Q^T goes to a work half; softmax: the last update writes it where it is wanted
+    crf_run(m, s, prob, img, N, H, W, C, crf, work, argmax ? nullptr : (float*)dout, argmax ? (long long*)dout : nullptr);
+    rc = deferred_rc(m); if (rc) return rc;
+    HIPCHK(m, hipGetLastError());
+    if (host) {
+        HIPCHK(m, hipMemcpyAsync(out, dout, argmax ? npix * sizeof(long long) : npix * C * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHK(m, hipStreamSynchronize(s));
+    }
+    return FCN8S_OK;
+}
+
 // ---- asynchronous host boundary ------------------------------------------------------------------
 int fcn8s_stage_inputs(fcn8s_model* m, int slot, const void* images, int dtype, const uint8_t* label_ids, int N, int H, int W,
                        void** images_dev, uint8_t** labels_dev)
@@ -3545,6 +3626,32 @@ int fcn8s_op_tta_accumulate(void* stream, const float* logits, int N, int Hp, in
         return fail(nullptr, FCN8S_ERR_BAD_ARG, "tta_accumulate: bad argument");
     const PixMap pm{0, Hp, Wp, 0, 0, 0};
     launch_tta_accumulate(logits, pm, N, Hs, Ws, flip ? 1 : 0, C, H, W, acc, first ? 1 : 0, last ? 1 : 0, npasses, softmax_out, (long long*)argmax_out, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
+
+size_t fcn8s_op_crf_work_floats(int N, int H, int W, int C, const fcn8s_crf_params* p)
+{
+    if (!p || N <= 0 || H <= 0 || W <= 0 || C <= 0 || crf_bad_field(p) || p->iterations == 0) return 0;
+    return 2 * (size_t)N * H * W * C;
+}
+int fcn8s_op_crf_meanfield(void* stream, const float* prob, const uint8_t* images, int N, int H, int W, int C, const fcn8s_crf_params* p,
+                           float* work, float* q_out, int64_t* argmax_out)
+{
+    if (!p) return fail(nullptr, FCN8S_ERR_BAD_ARG, "crf_meanfield: null crf_params");
+    if (const char* bad = crf_bad_field(p)) return fail(nullptr, FCN8S_ERR_BAD_ARG, std::string("crf_meanfield: crf_params.") + bad + " is out of range");
+    if (!prob || !images || (!q_out && !argmax_out) || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 || prob == q_out || (p->iterations > 0 && !work)
+        || ((uintptr_t)prob | (uintptr_t)work | (uintptr_t)q_out) % 16)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "crf_meanfield: bad argument (null or unaligned pointer, C not a multiple of 4, q_out == prob)");
+    if (!crf_shape_supported(C, p->radius)) return fail(nullptr, FCN8S_ERR_SHAPE, "crf_meanfield: this many classes do not fit the LDS tile at this radius");
+    hipStream_t s = (hipStream_t)stream;
+    take_deferred_error(nullptr);
+    if (p->iterations == 0) {
+        if (q_out && hipMemcpyAsync(q_out, prob, (size_t)N * H * W * C * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(nullptr, FCN8S_ERR_HIP, "crf_meanfield: the copy of prob failed");
+        if (argmax_out) launch_crf_argmax(prob, (long long)N * H * W, C, (long long*)argmax_out, s);
+    } else {
+        crf_run(nullptr, s, prob, images, N, H, W, C, p, work, q_out, (long long*)argmax_out);
+    }
     OPCHK(); return FCN8S_OK;
 }
 

@@ -20,6 +20,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib as L
+from . import crf as crf_mod
 from . import loss as loss_mod
 from . import tta
 from .dp import BucketReducer
@@ -765,6 +766,36 @@ class Engine:
             return out if argmax or self.logical_classes == self.num_classes else out[..., :self.logical_classes].contiguous()
         out = np.empty((N, H, W), np.int64) if argmax else np.empty((N, H, W, self.num_classes), np.float32)
         L.check(L.lib.fcn8s_predict_tta(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), int(bool(argmax)),
+                                        out.ctypes.data_as(C.c_void_p), where), self.h)
+        return out if argmax or self.logical_classes == self.num_classes else np.ascontiguousarray(out[..., :self.logical_classes])
+
+    def predict_crf(self, images, crf, scales=(1.0,), flip=False, argmax=True):
+        """`predict_tta` with these arguments followed by a mean-field CRF on its mean softmax and the uint8 images (fcn8s_predict_crf; the
+        definition and the parameters are in crf.py): Q^T float32 [N,H,W,C], or its argmax.  `crf`: True for the defaults, a dict of fields
+        or a crf.Params; None / False (or iterations = 0) is `predict_tta` itself.  Host or device inputs and outputs, as `predict`."""
+        params = crf_mod.resolve(crf)
+        if params is None:
+            return self.predict_tta(images, scales=scales, flip=flip, argmax=argmax)
+        sc = tta.validate(scales, flip)
+        self._sync_stream()
+        ka_i, pi, dt, where, nhw = self._images(images)
+        N, H, W = (int(x) for x in nhw)
+        if dt == L.IMG_F32 and params.iterations > 0:
+            raise ValueError("the CRF reads the colours of the uint8 images; float32 images are not taken with iterations > 0")
+        if dt == L.IMG_F32 and tta.resizes(H, W, sc):
+            raise ValueError("float32 images are taken only when no pass resizes them; pass uint8 images to predict at scales %s" % (sc,))
+        arr = (C.c_float * len(sc))(*sc)
+        cp = L.CrfParams(**params.as_dict())
+        torch = self.torch
+        if where == L.DEVICE:
+            out = torch.empty((N, H, W), dtype=torch.int64, device=self.device) if argmax else \
+                torch.empty((N, H, W, self.num_classes), dtype=torch.float32, device=self.device)
+            L.check(L.lib.fcn8s_predict_crf(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), C.byref(cp), int(bool(argmax)),
+                                            C.c_void_p(out.data_ptr()), where), self.h)
+            self._release(ka_i)
+            return out if argmax or self.logical_classes == self.num_classes else out[..., :self.logical_classes].contiguous()
+        out = np.empty((N, H, W), np.int64) if argmax else np.empty((N, H, W, self.num_classes), np.float32)
+        L.check(L.lib.fcn8s_predict_crf(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), C.byref(cp), int(bool(argmax)),
                                         out.ctypes.data_as(C.c_void_p), where), self.h)
         return out if argmax or self.logical_classes == self.num_classes else np.ascontiguousarray(out[..., :self.logical_classes])
 

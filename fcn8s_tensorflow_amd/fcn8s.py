@@ -47,6 +47,7 @@ except Exception:  # pragma: no cover
         return _R(n)
 
 from . import _lib as L
+from . import crf as crf_mod
 from . import loss as loss_mod
 from . import tf_bundle
 from .engine import Engine, padded_classes
@@ -383,14 +384,20 @@ class FCN8s:
         self._evaluate(data_generator, metrics, num_batches, l2_regularization, description='Running evaluation')
         self.eval_dataset = dataset
 
-    def predict(self, images, argmax=True, scales=None, flip=False):
+    def predict(self, images, argmax=True, scales=None, flip=False, crf=None):
         '''fcn8s_tensorflow.py:743-770.  `images`: array-like of rank 4 (a list of HWC arrays works).
         Returns int64 class ids (N,H,W) or the float32 softmax (N,H,W,C).
         Not in the reference: `scales` (1 to 8 factors in (0, 4]) and / or `flip` average the softmax over resized and mirrored passes
         (multi-scale / flip test-time augmentation, see tta.py) and take images of any size; `scales=(1.0,)` alone predicts an image of
-        any size at its own resolution.  Without them, height and width must be multiples of 32, as in the reference.'''
+        any size at its own resolution.  Without them, height and width must be multiples of 32, as in the reference.
+        `crf` (also not in the reference): refine the (mean) softmax by a mean-field CRF over a local window whose pairwise term reads
+        the colours of the uint8 input (crf.py; fcn8s_predict_crf) -- True for the default parameters, a dict of fields or a crf.Params to
+        override them, None / False for no CRF.  Images of any size, as with `scales=(1.0,)`.'''
         if isinstance(images, (list, tuple)):
             images = np.asarray(images)
+        params = crf_mod.resolve(crf)
+        if params is not None:
+            return self.engine.predict_crf(images, params, scales=(1.0,) if scales is None else scales, flip=flip, argmax=argmax)
         if scales is None and not flip:
             return self.engine.predict(images, argmax=argmax)
         return self.engine.predict_tta(images, scales=(1.0,) if scales is None else scales, flip=flip, argmax=argmax)
@@ -405,8 +412,9 @@ class FCN8s:
                          arrangement='vertical',
                          overwrite_existing=True,
                          scales=None,
-                         flip=False):
-        '''fcn8s_tensorflow.py:772-855 (PIL instead of scipy.misc / helpers.visualization_utils).  `scales` / `flip`: as in `predict`
+                         flip=False,
+                         crf=None):
+        '''fcn8s_tensorflow.py:772-855 (PIL instead of scipy.misc / helpers.visualization_utils).  `scales` / `flip` / `crf`: as in `predict`
         (images of any size; `resize` is then optional).'''
         from PIL import Image
 
@@ -425,17 +433,17 @@ class FCN8s:
         self.engine.freeze(True)            # constant weights for the whole directory
         try:
             for i in tr:
-                self._segment_file(image_paths[i], results_dir, color_map, resize, include_unprocessed_image, arrangement, scales, flip)
+                self._segment_file(image_paths[i], results_dir, color_map, resize, include_unprocessed_image, arrangement, scales, flip, crf)
         finally:
             self.engine.freeze(False)
 
     def predict_and_export_label_ids(self, results_dir, images_dir, resize=False, image_file_extension='png', overwrite_existing=True,
-                                     scales=None, flip=False):
+                                     scales=None, flip=False, crf=None):
         '''Not in the reference: runs every `*.png` below `images_dir` (sub-directories = cities, as in leftImg8bit/val) through the
         model and writes the argmax as single-channel label-id PNGs under the same file names into `results_dir` -- the input of the
         official scorer (cityscapesscripts/evaluation/evalPixelLevelSemanticLabeling.py:72-106, 553-555; cityscapes_eval.evaluate_directory
         here).  Predictions are train ids 0..19 (0 = void) mapped through labels.py:188-192; `resize=(h, w)` feeds the network a
-        resized image and writes the prediction back at the file's own size (nearest neighbour).  `scales` / `flip`: as in `predict`
+        resized image and writes the prediction back at the file's own size (nearest neighbour).  `scales` / `flip` / `crf`: as in `predict`
         (multi-scale / flip averaging on images of any size; `resize` is then optional).'''
         from PIL import Image
         from . import cityscapes_eval as ce
@@ -454,7 +462,8 @@ class FCN8s:
                 size = pil.size
                 if resize and not np.array_equal((pil.height, pil.width), resize):
                     pil = pil.resize((resize[1], resize[0]), Image.BILINEAR)
-                pred = np.asarray(self.predict([np.asarray(pil)], argmax=True, scales=scales, flip=flip))[0]
+                kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
+                pred = np.asarray(self.predict([np.asarray(pil)], argmax=True, scales=scales, flip=flip, **kw))[0]
                 ids = Image.fromarray(ce.TRAINIDS_TO_IDS_ARRAY[pred])
                 if ids.size != size:
                     ids = ids.resize(size, Image.NEAREST)
@@ -463,7 +472,7 @@ class FCN8s:
             self.engine.freeze(False)
         return len(paths)
 
-    def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement, scales=None, flip=False):
+    def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement, scales=None, flip=False, crf=None):
         '''Loop body of predict_and_save (fcn8s_tensorflow.py:829-855).'''
         from PIL import Image
         pil = Image.open(filepath).convert('RGB')
@@ -472,7 +481,8 @@ class FCN8s:
         image = np.asarray(pil)
         img_height, img_width, img_ch = image.shape
 
-        prediction = self.predict([image], argmax=False, scales=scales, flip=flip)
+        kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
+        prediction = self.predict([image], argmax=False, scales=scales, flip=flip, **kw)
         processed = print_segmentation_onto_image(image=image, prediction=prediction, color_map=color_map)
 
         if include_unprocessed_image:

@@ -314,6 +314,37 @@ int fcn8s_predict(fcn8s_model* m, const void* images, int image_dtype, int N, in
 int fcn8s_predict_tta(fcn8s_model* m, const void* images, int image_dtype, int N, int H, int W, const float* scales, int nscales, int flip,
                       int argmax, void* out, int where);
 
+/* ---- mean-field CRF refinement of a prediction (inference only; off unless asked for) ------------------------------------------------ *
+ * A locally connected conditional random field over the softmax whose pairwise term looks at the colours of the input image (the local
+ * window of Teichmann & Cipolla, "Convolutional CRFs", 2018; Potts compatibility).  Per image: probabilities P [H,W,C] (float32) and the
+ * uint8 RGB image I [H,W,3] of the same size.  For pixel i and every offset (dy, dx) in {-r..r}^2 * d other than (0, 0) whose neighbour
+ * j = i + (dy, dx) lies inside the image (neighbours outside contribute nothing, anywhere):
+ *     s2   = dy^2 + dx^2                      c2 = sum_rgb (I_i - I_j)^2                  (exact integers)
+ *     a_ij = exp(-s2 / (2 theta_alpha^2))                                                   (position only)
+ *     k_ij = exp(-s2 / (2 theta_alpha^2) - c2 / (2 theta_beta^2))                           (appearance)
+ *     g_ij = exp(-s2 / (2 theta_gamma^2))                                                   (smoothness)
+ *     U_i(l) = log(max(P_i(l), FLT_MIN)),   Q^0 = P
+ *     m_i(l) = w_appearance * sum_j k_ij Q_j^{t-1}(l) / sum_j a_ij  +  w_smooth * sum_j g_ij Q_j^{t-1}(l) / sum_j g_ij
+ *     Q_i^t  = softmax_l(U_i(l) + m_i(l)),   t = 1 .. iterations, all pixels at once (Jacobi)
+ * Both messages are divided by POSITION-ONLY sums: each lies in [0, 1] * w, a pixel with no similar neighbour receives almost no
+ * appearance message, and a pixel at the border is treated like one in the interior.  A pixel with no neighbour inside the image has m = 0.
+ * iterations = 0 returns P untouched, bit for bit.  The thetas and weights are float32; 1 / (2 theta^2) is formed in fp32.
+ * Accepted: iterations 0..32 (default 5), radius 1..7 (3), dilation 1..8 (1), w_appearance (4) and w_smooth (2) finite and >= 0,
+ * theta_alpha (8, pixels), theta_beta (13, colour units of 0..255) and theta_gamma (3, pixels) finite and > 0.  The defaults are a
+ * starting point in the usual range of the dense-CRF literature; their effect on a trained model's mean IoU has not been measured. */
+typedef struct fcn8s_crf_params {
+    int32_t iterations, radius, dilation;
+    float w_appearance, w_smooth, theta_alpha, theta_beta, theta_gamma;
+} fcn8s_crf_params;
+/* fcn8s_predict_tta with these arguments, followed by the mean field on its mean softmax (formed internally also when argmax != 0) and the
+ * caller's uint8 images at H x W: out = Q^T float32 [N,H,W,C], or (argmax != 0) its int64 argmax [N,H,W] (lowest index on ties).
+ * crf_params == NULL or iterations == 0: the result of fcn8s_predict_tta, bit for bit.  The CRF's buffers belong to the model's workspace:
+ * a repeated identical call allocates and frees nothing ("workspace_allocations").  Profile group "crf_meanfield" (one entry per update).
+ * FCN8S_ERR_BAD_ARG (the text names the field): a field outside the ranges above (NaN included), float32 images with iterations > 0
+ * (the colours must be the uint8 ones), whatever fcn8s_predict_tta refuses; nothing is launched then. */
+int fcn8s_predict_crf(fcn8s_model* m, const void* images, int image_dtype, int N, int H, int W, const float* scales, int nscales, int flip,
+                      const fcn8s_crf_params* crf_params, int argmax, void* out, int where);
+
 /* ---- state that must round-trip: global_step :246,:526; Adam slots ---------- */
 int64_t fcn8s_global_step(const fcn8s_model* m);
 int     fcn8s_set_global_step(fcn8s_model* m, int64_t step);
@@ -391,7 +422,7 @@ int fcn8s_fp8_set_calibration(fcn8s_model* m, const float* amax, int n);
  *                              fcn8s_get_activation(m, "dy:<layer>", ...) (conv1_1 .. conv5_3, fc6, fc7); FCN8S_ERR_STATE for a layer whose gradient travelled in another form
  *                              (these ten pick a kernel per launch and drop nothing)
  *     "workspace_allocations"  (read-only statistic; setting it is FCN8S_ERR_BAD_ARG) device allocations the model has made for its workspace,
- *                              the scratch of fcn8s_predict_tta, its bf16 copies and its cached (frozen / TTA) filter banks
+ *                              the scratch of fcn8s_predict_tta and fcn8s_predict_crf, its bf16 copies and its cached (frozen / TTA) filter banks
  *     "frozen"                 (read-only) 1 while fcn8s_freeze_params(m, 1) holds
  *     "comm_timeout_ms" 600000 the communicator's watchdog (see fcn8s_comm_init): a collective older than this is given up, the communicator aborted
  *   op-context options (m == NULL): the arithmetic of the op-level entry points below, which have no model.  The value belongs to the
@@ -445,6 +476,14 @@ int fcn8s_op_preprocess(void* stream, const void* images, int image_dtype, float
 int fcn8s_op_tta_input(void* stream, const uint8_t* images, int N, int H, int W, int Hs, int Ws, int Hp, int Wp, int flip, float* out4);
 int fcn8s_op_tta_accumulate(void* stream, const float* logits, int N, int Hp, int Wp, int Hs, int Ws, int flip, int C, int H, int W, float* acc,
                             int first, int last, int npasses, float* softmax_out, int64_t* argmax_out);
+/* the mean field of fcn8s_predict_crf on DEVICE pointers (definition: at fcn8s_crf_params): prob, q_out float32 [N,H,W,C] (16-byte aligned,
+ * C a multiple of 4), images uint8 [N,H,W,3]; work: scratch of fcn8s_op_crf_work_floats(N, H, W, C, p) floats (may be NULL when that is
+ * 0); q_out (Q^T) and argmax_out (int64 [N,H,W]) may each be NULL, not both.  prob is not written and may not overlap work or q_out.
+ * FCN8S_ERR_BAD_ARG for a field of p outside its range (the text names it), FCN8S_ERR_SHAPE if C floats of a tile do not fit the LDS
+ * (C <= 52 fits at every radius). */
+size_t fcn8s_op_crf_work_floats(int N, int H, int W, int C, const fcn8s_crf_params* p);
+int fcn8s_op_crf_meanfield(void* stream, const float* prob, const uint8_t* images, int N, int H, int W, int C, const fcn8s_crf_params* p,
+                           float* work, float* q_out, int64_t* argmax_out);
 /* GPU-side augmentation of a uint8 batch on DEVICE pointers (the crop / canvas placement, horizontal flip and
  * brightness steps of data_generator/batch_generator.py:293-341, :469-486, which do not resample).  params: int32[4] per image =
  * {y offset, x offset, flip (0|1), brightness (0|1)}; out[n,y,x] = in[n, y+oy, (flip ? Wo-1-x : x) + ox], zero / void_id outside the
