@@ -11,12 +11,19 @@ averaged over the labels with a defined score (:286-295).
 The label table is the reference author's modified one (`cityscapesscripts/helpers/labels.py:62-99`:
 trainId 0 = every ignored label, 1..19 = the evaluated classes).  The confusion matrix is accumulated by
 the library's HIP kernel when the inputs live on the GPU, by NumPy otherwise.
+
+The instance-level half of the evaluator (`evalInstLevelScore`, on by default there: generateInstanceStats :184-215, the instance
+loop of evaluatePair :595-635, getInstanceIouScoreForLabel :258-278, getInstanceIouScoreForCategory :332-351) is here as
+`instance_level=True`: per image an exact integer table (v, size, tp, cattp) of the instance values v > 1000 -- counted by
+`fcn8s_op_cityscapes_pair` in the same pass as the confusion matrix when the maps are on the GPU (include/fcn8s_hip.h has the definition),
+by NumPy otherwise -- and then, on the host for both routes, the evaluator's float64 sums in its own order (`instance_stats_add`).
 """
 from __future__ import annotations
 
 import ctypes as C
 import fnmatch
 import glob
+import json
 import math
 import os
 from collections import OrderedDict
@@ -141,26 +148,246 @@ def score_average(scores):
     return float('nan') if not vals else sum(vals) / len(vals)
 
 
+# ---------------------------------------------------------------------------------------------------------
+# instance-level scores (iIoU)
+# ---------------------------------------------------------------------------------------------------------
+AVG_CLASS_SIZE = {                                             # evalPixelLevelSemanticLabeling.py:148-159
+    "bicycle":     4672.3249222261,
+    "caravan":    36771.8241758242,
+    "motorcycle":  6298.7200839748,
+    "rider":       3930.4788056518,
+    "bus":        35732.1511111111,
+    "train":      67583.7075812274,
+    "car":        12794.0202738185,
+    "person":      3462.4756337644,
+    "truck":      27855.1264367816,
+    "trailer":    16926.9763313609,
+}
+HAS_INSTANCES_IDS = [i for _n, i, _t, _c, _ci, has, _ig, _col in LABELS if i >= 0 and has]
+INSTANCE_LABEL_IDS = [i for i in HAS_INSTANCES_IDS if i not in IGNORED_IDS]           # person .. bicycle without caravan / trailer
+ID_TO_CATEGORY = {i: c for _n, i, _t, c, *_r in LABELS}
+# generateInstanceStats :195-213: the categories all of whose labels (id >= 0) have instances, with ALL those ids (ignored ones included)
+INSTANCE_CATEGORY_TO_IDS = OrderedDict((c, ids) for c, ids in CATEGORY_TO_IDS.items() if all(i in HAS_INSTANCES_IDS for i in ids))
+DEFAULT_MAX_ENTRIES = 1024                                     # per image; a Cityscapes image holds a few hundred instances at most
+
+
+def new_instance_stats():
+    """generateInstanceStats (:184-215)"""
+    zero = lambda: OrderedDict((k, 0.0) for k in ("tp", "tpWeighted", "fn", "fnWeighted"))
+    return {"classes": OrderedDict((ID_TO_NAME[l], zero()) for l in INSTANCE_LABEL_IDS),
+            "categories": OrderedDict((c, zero()) for c in INSTANCE_CATEGORY_TO_IDS)}
+
+
+def instance_value_kind(v):
+    """What the evaluator does with a value v > 1000 of an instance map: 'count', 'skip' (ignoreInEval, :605) or 'bad' (its KeyError:
+    an evaluated label without instances, or no label at all)."""
+    label = int(v) // 1000
+    if label in INSTANCE_LABEL_IDS:
+        return 'count'
+    return 'skip' if label in IGNORED_IDS else 'bad'
+
+
+def _bad_instance_value(v):
+    return ValueError("Instance id {} in the ground truth: label {} is evaluated but has no instances (or does not exist).".format(int(v), int(v) // 1000))
+
+
+def instance_entries_numpy(pred_ids, inst):
+    """The integer half of the instance loop (:601-635) for one image: int64 rows (v, size, tp, cattp), ascending v, for the values
+    v > 1000 of `inst` whose label is counted.  pred_ids: label ids of the same shape."""
+    inst = np.asarray(inst); pred_ids = np.asarray(pred_ids)
+    if inst.shape != pred_ids.shape:
+        raise ValueError("Instance map of shape {} against a prediction of shape {}.".format(inst.shape, pred_ids.shape))
+    sel = inst > 1000
+    v = inst[sel].astype(np.int64); p = pred_ids[sel].astype(np.int64)
+    vals = np.unique(v)
+    kinds = [instance_value_kind(x) for x in vals]
+    for x, k in zip(vals, kinds):
+        if k == 'bad':
+            raise _bad_instance_value(x)
+    n = int(vals.max()) + 1 if vals.size else 0
+    lab = v // 1000
+    incat = np.zeros(v.shape, bool)
+    for ids in INSTANCE_CATEGORY_TO_IDS.values():
+        incat |= np.isin(lab, ids) & np.isin(p, ids)
+    size = np.bincount(v, minlength=n); tp = np.bincount(v[p == lab], minlength=n); cattp = np.bincount(v[incat], minlength=n)
+    keep = np.array([x for x, k in zip(vals, kinds) if k == 'count'], np.int64)
+    return np.stack([keep, size[keep], tp[keep], cattp[keep]], axis=1).astype(np.int64) if keep.size else np.zeros((0, 4), np.int64)
+
+
+def instance_stats_add(stats, entries):
+    """The float64 half of the instance loop (:609-635) for one image's rows (v, size, tp, cattp) in ascending v: the evaluator's own
+    operations in its own order, so the sums carry its bits whichever route counted the integers."""
+    for v, size, tp, cattp in np.asarray(entries, dtype=np.int64).reshape(-1, 4).tolist():
+        label = v // 1000
+        name = ID_TO_NAME[label]
+        weight = AVG_CLASS_SIZE[name] / float(size)
+        c = stats["classes"][name]
+        fn = size - tp
+        c["tp"] += tp; c["fn"] += fn
+        c["tpWeighted"] += float(tp) * weight; c["fnWeighted"] += float(fn) * weight
+        category = ID_TO_CATEGORY[label]
+        if category in stats["categories"]:
+            k = stats["categories"][category]
+            catfn = size - cattp
+            k["tp"] += cattp; k["fn"] += catfn
+            k["tpWeighted"] += float(cattp) * weight; k["fnWeighted"] += float(catfn) * weight
+    return stats
+
+
+def instance_iou_for_label(label, conf, stats):
+    """getInstanceIouScoreForLabel (:258-278)"""
+    if label in IGNORED_IDS or ID_TO_NAME[label] not in stats["classes"]:
+        return float('nan')
+    tp = stats["classes"][ID_TO_NAME[label]]["tpWeighted"]
+    fn = stats["classes"][ID_TO_NAME[label]]["fnWeighted"]
+    not_ignored = [l for l in EVAL_IDS if l != label]
+    fp = int(conf[not_ignored, label].sum())
+    denom = tp + fp + fn
+    return float('nan') if denom == 0 else float(tp) / denom
+
+
+def instance_iou_for_category(category, conf, stats):
+    """getInstanceIouScoreForCategory (:332-351)"""
+    if category not in stats["categories"]:
+        return float('nan')
+    ids = INSTANCE_CATEGORY_TO_IDS[category]
+    tp = stats["categories"][category]["tpWeighted"]
+    fn = stats["categories"][category]["fnWeighted"]
+    others = [l for l in EVAL_IDS if ID_TO_CATEGORY[int(l)] != category]
+    fp = int(conf[np.ix_(others, ids)].sum())
+    denom = tp + fp + fn
+    return float('nan') if denom == 0 else float(tp) / denom
+
+
+def _is_cuda_tensor(x):
+    try:
+        import torch
+    except ImportError:
+        return False
+    return isinstance(x, torch.Tensor) and x.is_cuda
+
+
+def pair_counts_device(pred, gt_label_ids, gt_instance_ids=None, max_entries=DEFAULT_MAX_ENTRIES):
+    """One `fcn8s_op_cityscapes_pair` call on maps that live on the GPU: `pred` int64 train ids (as `predict` returns them; consumed as
+    they are) or uint8 label ids, `gt_label_ids` uint8, `gt_instance_ids` 16-bit (torch.int16 holding the uint16 bits, or torch.uint16) or
+    None; shapes (H, W) or (N, H, W).  Returns (conf (34, 34) int64 ndarray of this call, [entries (K_n, 4) int64 per image] or None).
+    Only the matrix, the three counters per image and the entries come back to the host.  More instances than `max_entries` in an image:
+    the call is repeated once with the reported count."""
+    import torch
+    from . import _lib as L
+    dev = pred.device
+    if pred.dtype == torch.int64:
+        kind = 0
+    elif pred.dtype == torch.uint8:
+        kind = 1
+    else:
+        raise ValueError("`pred` must hold int64 train ids or uint8 label ids, not {}".format(pred.dtype))
+    if gt_label_ids.dtype != torch.uint8:
+        raise ValueError("`gt_label_ids` must be uint8, not {}".format(gt_label_ids.dtype))
+    if tuple(gt_label_ids.shape) != tuple(pred.shape) or pred.dim() not in (2, 3):
+        raise ValueError("prediction of shape {} against ground truth of shape {}".format(tuple(pred.shape), tuple(gt_label_ids.shape)))
+    N = 1 if pred.dim() == 2 else int(pred.shape[0])
+    P = pred.numel() // max(N, 1)
+    pred = pred.contiguous(); gt = gt_label_ids.to(dev).contiguous()
+    inst = None
+    if gt_instance_ids is not None:
+        inst = gt_instance_ids.to(dev)
+        if inst.element_size() != 2 or inst.is_floating_point():
+            raise ValueError("`gt_instance_ids` must be a 16-bit integer tensor (the uint16 instance map's bits), not {}".format(inst.dtype))
+        if tuple(inst.shape) != tuple(pred.shape):
+            raise ValueError("instance map of shape {} against a prediction of shape {}".format(tuple(inst.shape), tuple(pred.shape)))
+        inst = inst.contiguous()
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    counts = torch.empty((N, 3), dtype=torch.int64, device=dev)
+    work = torch.empty(L.lib.fcn8s_op_cityscapes_work_bytes(N), dtype=torch.uint8, device=dev) if inst is not None else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    for _attempt in range(2):
+        conf = torch.zeros(NUM_IDS * NUM_IDS, dtype=torch.int64, device=dev)
+        entries = torch.empty((N, max(int(max_entries), 1), 4), dtype=torch.int32, device=dev) if inst is not None else None
+        L.check(L.lib.fcn8s_op_cityscapes_pair(stream, ptr(gt), ptr(inst), ptr(pred), kind, N, P, ptr(conf), ptr(work), ptr(entries),
+                                               int(max_entries), ptr(counts)))
+        cnt = counts.cpu().numpy()
+        if int(cnt[:, 0].max()) <= max_entries:
+            break
+        max_entries = int(cnt[:, 0].max())
+    if cnt[:, 1].any():
+        bad_gt = int(gt.max()) >= NUM_IDS
+        raise ValueError("Unknown label with id {:}".format(int(gt.max())) if bad_gt else
+                         "{} predicted pixels hold an id outside the {}".format(int(cnt[:, 1].sum()), "train ids 0..19" if kind == 0 else "label ids 0..33"))
+    if cnt[:, 2].any():
+        vals = torch.unique(inst.view(torch.int16).to(torch.int32) & 0xFFFF).cpu().numpy()
+        raise _bad_instance_value([v for v in vals if v > 1000 and instance_value_kind(v) == 'bad'][0])
+    conf_np = conf.cpu().numpy().reshape(NUM_IDS, NUM_IDS)
+    if inst is None:
+        return conf_np, None
+    e = entries[:, :max(int(cnt[:, 0].max()), 1)].cpu().numpy().astype(np.int64)
+    return conf_np, [e[n, :int(cnt[n, 0])] for n in range(N)]
+
+
+def pair_counts_numpy(pred, gt_label_ids, gt_instance_ids=None, pred_is_train_ids=True):
+    """The NumPy route of the same definition, for one image or a stack of them: (conf (34, 34) int64, [entries per image] or None)."""
+    pred = np.asarray(pred); gt = np.asarray(gt_label_ids)
+    if pred.shape != gt.shape or pred.ndim not in (2, 3):
+        raise ValueError("prediction of shape {} against ground truth of shape {}".format(pred.shape, gt.shape))
+    if pred.size and (pred.min() < 0 or pred.max() >= (20 if pred_is_train_ids else NUM_IDS)):
+        raise ValueError("predicted pixels hold an id outside the {}".format("train ids 0..19" if pred_is_train_ids else "label ids 0..33"))
+    if gt.size and gt.max() >= NUM_IDS:
+        raise ValueError("Unknown label with id {:}".format(int(gt.max())))
+    pred_ids = TRAINIDS_TO_IDS_ARRAY[pred.astype(np.int64)] if pred_is_train_ids else pred
+    conf = confusion_add(np.zeros((NUM_IDS, NUM_IDS), np.int64), gt, pred_ids)
+    if gt_instance_ids is None:
+        return conf, None
+    inst = np.asarray(gt_instance_ids)
+    if inst.shape != pred.shape:
+        raise ValueError("instance map of shape {} against a prediction of shape {}".format(inst.shape, pred.shape))
+    if pred.ndim == 2:
+        return conf, [instance_entries_numpy(pred_ids, inst)]
+    return conf, [instance_entries_numpy(pred_ids[n], inst[n]) for n in range(pred.shape[0])]
+
+
 class PixelLevelEvaluator:
     """Accumulates the official confusion matrix from FCN-8s predictions (train ids, as `FCN8s.predict`
-    returns them) and Cityscapes `*_gtFine_labelIds` ground truth, and reports the 19-class scores."""
+    returns them) and Cityscapes `*_gtFine_labelIds` ground truth, and reports the 19-class scores; with `instance_level`, the
+    instance statistics from `*_gtFine_instanceIds` maps and the iIoU scores as well (the evaluator's default table)."""
 
-    def __init__(self):
+    def __init__(self, instance_level=False):
         self.conf = np.zeros((NUM_IDS, NUM_IDS), np.int64)
+        self.instance_level = bool(instance_level)
+        self.inst_stats = new_instance_stats() if self.instance_level else None
 
-    def add(self, pred_train_ids, gt_label_ids):
-        try:
+    def add(self, pred_train_ids, gt_label_ids, gt_instance_ids=None, pred_is_train_ids=True, max_entries=DEFAULT_MAX_ENTRIES):
+        """One image (H, W) or a stack (N, H, W).  Maps on the GPU (torch tensors; the prediction decides) are counted there by one
+        `fcn8s_op_cityscapes_pair` call and stay there; NumPy maps are counted by NumPy.  `pred_is_train_ids=False`: `pred_train_ids`
+        holds label ids 0..33 (uint8 on the GPU) instead."""
+        if self.instance_level and gt_instance_ids is None:
+            raise ValueError("an instance-level evaluation needs the ground truth's instance-id map (*_gtFine_instanceIds.png)")
+        if not self.instance_level:
+            gt_instance_ids = None
+        if _is_cuda_tensor(pred_train_ids):
             import torch
-            if isinstance(pred_train_ids, torch.Tensor):
-                lut = torch.as_tensor(TRAINIDS_TO_IDS_ARRAY.astype(np.int64), device=pred_train_ids.device)
-                pred_ids = lut[pred_train_ids.long()]
-                gt = gt_label_ids if isinstance(gt_label_ids, torch.Tensor) else torch.as_tensor(np.asarray(gt_label_ids))
-                confusion_add(self.conf, gt.to(pred_ids.device), pred_ids)
-                return
-        except ImportError:
-            pass
-        pred_ids = TRAINIDS_TO_IDS_ARRAY[np.asarray(pred_train_ids).astype(np.int64)]
-        confusion_add(self.conf, np.asarray(gt_label_ids), pred_ids)
+            pred = pred_train_ids
+            if pred_is_train_ids and pred.dtype != torch.int64:
+                pred = pred.long()
+            elif not pred_is_train_ids and pred.dtype != torch.uint8:
+                raise ValueError("label ids on the GPU must be uint8")
+            gt = gt_label_ids if isinstance(gt_label_ids, torch.Tensor) else torch.as_tensor(np.asarray(gt_label_ids))
+            gt = gt.to(device=pred.device, dtype=torch.uint8)
+            inst = gt_instance_ids
+            if inst is not None and not isinstance(inst, torch.Tensor):
+                inst = instance_map_tensor(inst, pred.device)
+            conf, entries = pair_counts_device(pred, gt, inst, max_entries)
+        else:
+            to_np = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+            inst = None
+            if gt_instance_ids is not None:
+                inst = to_np(gt_instance_ids)
+                if inst.dtype == np.int16:
+                    inst = inst.view(np.uint16)
+            conf, entries = pair_counts_numpy(to_np(pred_train_ids), to_np(gt_label_ids), inst, pred_is_train_ids)
+        self.conf += conf
+        if entries is not None:
+            for e in entries:
+                instance_stats_add(self.inst_stats, e)
 
     def class_scores(self):
         return OrderedDict((ID_TO_NAME[int(l)], iou_for_label(int(l), self.conf)) for l in range(NUM_IDS))
@@ -168,10 +395,61 @@ class PixelLevelEvaluator:
     def category_scores(self):
         return OrderedDict((c, iou_for_category(c, self.conf)) for c in CATEGORY_TO_IDS)
 
+    def class_inst_scores(self):
+        return OrderedDict((ID_TO_NAME[int(l)], instance_iou_for_label(int(l), self.conf, self.inst_stats)) for l in range(NUM_IDS))
+
+    def category_inst_scores(self):
+        return OrderedDict((c, instance_iou_for_category(c, self.conf, self.inst_stats)) for c in CATEGORY_TO_IDS)
+
     def results(self):
         cs, cat = self.class_scores(), self.category_scores()
-        return {"classScores": cs, "averageScoreClasses": score_average(cs),
-                "categoryScores": cat, "averageScoreCategories": score_average(cat)}
+        res = {"classScores": cs, "averageScoreClasses": score_average(cs),
+               "categoryScores": cat, "averageScoreCategories": score_average(cat)}
+        if self.instance_level:
+            ics, icat = self.class_inst_scores(), self.category_inst_scores()
+            res.update({"classInstScores": ics, "averageScoreInstClasses": score_average(ics),
+                        "categoryInstScores": icat, "averageScoreInstCategories": score_average(icat),
+                        "instStats": self.inst_stats})
+        return res
+
+
+def instance_map_tensor(inst, device):
+    """A uint16 instance-id map (NumPy) as the 16-bit tensor `fcn8s_op_cityscapes_pair` reads: the same bits, uploaded as torch.int16."""
+    import torch
+    a = np.ascontiguousarray(np.asarray(inst))
+    if a.dtype not in (np.uint16, np.int16):
+        if a.size and (a.min() < 0 or a.max() > 65535):
+            raise ValueError("instance ids do not fit 16 bits")
+        a = a.astype(np.uint16)
+    return torch.from_numpy(a.view(np.int16)).to(device)
+
+
+def result_dict(res):
+    """createResultDict (:355-376) of an instance-level result: the layout of the evaluator's resultPixelLevelSemanticLabeling.json."""
+    if "classInstScores" not in res or "confMatrix" not in res:
+        raise ValueError("result_dict needs the result of an instance-level evaluation of files (evaluate_file_pairs / evaluate_directory with instance_level=True)")
+    conf = np.asarray(res["confMatrix"])
+    whole = OrderedDict()
+    whole["confMatrix"] = conf.tolist()
+    whole["priors"] = OrderedDict(); whole["labels"] = OrderedDict()
+    total = float(conf.sum())
+    for label in range(NUM_IDS):
+        whole["priors"][ID_TO_NAME[label]] = float(conf[label, :].sum()) / total if total else float('nan')
+        whole["labels"][ID_TO_NAME[label]] = label
+    for k in ("classScores", "classInstScores", "categoryScores", "categoryInstScores"):
+        whole[k] = OrderedDict(res[k])
+    for k in ("averageScoreClasses", "averageScoreInstClasses", "averageScoreCategories", "averageScoreInstCategories"):
+        whole[k] = res[k]
+    return whole
+
+
+def write_result_json(res, path):
+    """writeJSONFile (:378-383): `result_dict(res)` as JSON, interchangeable with the evaluator's result file."""
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, 'w') as f:
+        f.write(json.dumps(result_dict(res), default=lambda o: o.__dict__, sort_keys=True, indent=4))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -199,13 +477,13 @@ def walk_predictions(prediction_path):
     return [(root, files) for root, _, files in os.walk(prediction_path)]
 
 
-def find_prediction(prediction_path, ground_truth_file, walk=None):
+def find_prediction(prediction_path, ground_truth_file, walk=None, extension='png'):
     """evalPixelLevelSemanticLabeling.py:72-106: the one file `<city>_<seq>_<frame>*.png` anywhere below `prediction_path`
     (`walk`: a walk_predictions() result to reuse, as the evaluator walks the tree once)."""
     if walk is None:
         walk = walk_predictions(prediction_path)
     city, seq, frame = cs_file_info(ground_truth_file)
-    pattern = "{}_{}_{}*.png".format(city, seq, frame)
+    pattern = "{}_{}_{}*.{}".format(city, seq, frame, extension)
     found = None
     for root, files in walk:
         for f in fnmatch.filter(files, pattern):
@@ -217,17 +495,29 @@ def find_prediction(prediction_path, ground_truth_file, walk=None):
     return found
 
 
-def evaluate_file_pairs(prediction_files, ground_truth_files, device=None):
-    """evaluateImgLists / evaluatePair (evalPixelLevelSemanticLabeling.py:454-498, 550-595): accumulate conf[gt, pred] over
+def instance_file_of(ground_truth_file):
+    """The instance-id map that belongs to a `*_labelIds.png` (:564)."""
+    return ground_truth_file.replace("labelIds", "instanceIds")
+
+
+def evaluate_file_pairs(prediction_files, ground_truth_files, device=None, instance_level=False):
+    """evaluateImgLists / evaluatePair (evalPixelLevelSemanticLabeling.py:454-498, 550-635): accumulate conf[gt, pred] over
     pairs of label-id PNGs with the evaluator's checks, then the class / category scores.  `device`: a torch cuda device
-    to count on the GPU (the library's confusion kernel), None = NumPy."""
+    to count on the GPU (the library's kernels), None = NumPy.  `instance_level`: also read each ground truth's `*_instanceIds.png`
+    and report the iIoU scores (`classInstScores`, `categoryInstScores`, their averages, `instStats`)."""
     from PIL import Image
     if len(prediction_files) != len(ground_truth_files):
         raise ValueError("List of images for prediction and groundtruth are not of equal size.")
-    ev = PixelLevelEvaluator()
+    ev = PixelLevelEvaluator(instance_level=instance_level)
     pixels = 0
     for pf, gf in zip(prediction_files, ground_truth_files):
         pred, gt = np.array(Image.open(pf)), np.array(Image.open(gf))
+        inst = None
+        if instance_level:
+            inf = instance_file_of(gf)
+            if inf == gf or not os.path.isfile(inf):
+                raise ValueError("Unable to load " + inf)
+            inst = np.array(Image.open(inf))
         if pred.ndim != 2:
             raise ValueError("Predicted image has multiple channels.")
         if pred.shape[1] != gt.shape[1]:
@@ -236,7 +526,17 @@ def evaluate_file_pairs(prediction_files, ground_truth_files, device=None):
             raise ValueError("Image heights of " + pf + " and " + gf + " are not equal.")
         if gt.max() >= NUM_IDS:
             raise ValueError("Unknown label with id {:}".format(int(gt.max())))
-        if device is not None:
+        if instance_level:
+            if inst.shape != gt.shape:
+                raise ValueError("Image sizes of " + instance_file_of(gf) + " and " + gf + " are not equal.")
+            if pred.max() >= NUM_IDS:
+                raise ValueError("Unknown label with id {:} in {}".format(int(pred.max()), pf))
+            if device is not None:
+                import torch
+                ev.add(torch.from_numpy(pred.astype(np.uint8)).to(device), gt.astype(np.uint8), inst, pred_is_train_ids=False)
+            else:
+                ev.add(pred, gt, inst, pred_is_train_ids=False)
+        elif device is not None:
             import torch
             confusion_add(ev.conf, torch.from_numpy(gt.astype(np.uint8)).to(device), torch.from_numpy(pred.astype(np.int64)).to(device))
         else:
@@ -250,11 +550,11 @@ def evaluate_file_pairs(prediction_files, ground_truth_files, device=None):
     return res
 
 
-def evaluate_directory(ground_truth_search, prediction_path, device=None):
+def evaluate_directory(ground_truth_search, prediction_path, device=None, instance_level=False):
     """The evaluator's no-argument mode (:667-676): every ground-truth file matching the glob (the official one is
     `<cityscapes>/gtFine/val/*/*_gtFine_labelIds.png`) against its prediction below `prediction_path`."""
     gts = sorted(glob.glob(ground_truth_search))
     if not gts:
         raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
     walk = walk_predictions(prediction_path)
-    return evaluate_file_pairs([find_prediction(prediction_path, g, walk) for g in gts], gts, device)
+    return evaluate_file_pairs([find_prediction(prediction_path, g, walk) for g in gts], gts, device, instance_level)

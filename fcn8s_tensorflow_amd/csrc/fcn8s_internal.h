@@ -354,6 +354,12 @@ void launch_crf_meanfield(const float* qin, const float* prob, const unsigned ch
                           float w_app, float w_smooth, float theta_alpha, float theta_beta, float theta_gamma, float* qout, long long* am, hipStream_t s);
 // am[i] = argmax_c p[i, c], lowest index on ties
 void launch_crf_argmax(const float* p, long long npix, int C, long long* am, hipStream_t s);
+// cityscapes.hip (fcn8s_op_cityscapes_pair; the definition is in fcn8s_hip.h).  One clear (work, or counts [N][3] when inst == nullptr), the counting kernel
+// (conf +=; with inst the per-image tables and error counters in work) and, with inst, the compaction of work into entries [N][max_entries][4] and counts [N][3].
+// P < 2^31; work: cityscapes_work_bytes(N) bytes, 16-byte aligned.
+size_t cityscapes_work_bytes(int N);
+void launch_cityscapes_pair(const uint8_t* gt, const uint16_t* inst, const void* pred, int pred_kind, int N, long long P,
+                            unsigned long long* conf, void* work, int* entries, int max_entries, unsigned long long* counts, hipStream_t s);
 // wrapping sum over every 61st element's bit pattern (weighted by position): changes whenever an optimizer step or a bulk copy touches the buffer
 void launch_fingerprint(const float* x, long long n, unsigned long long* out, hipStream_t s);
 void launch_init_normal(float* w, long long n, float stddev, int truncated, unsigned long long seed,

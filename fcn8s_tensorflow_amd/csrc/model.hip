@@ -3955,6 +3955,19 @@ int fcn8s_op_softmax_argmax(void* stream, const float* logits, float* sm, int64_
 { launch_softmax_argmax(logits, sm, (long long*)am, npix, C, (hipStream_t)stream); OPCHK(); return FCN8S_OK; }
 int fcn8s_op_confusion(void* stream, const uint8_t* labels, const int64_t* pred, int64_t npix, int64_t* conf, int C)
 { launch_confusion(labels, (const long long*)pred, npix, (unsigned long long*)conf, C, (hipStream_t)stream); OPCHK(); return FCN8S_OK; }
+size_t fcn8s_op_cityscapes_work_bytes(int N) { return cityscapes_work_bytes(N); }
+int fcn8s_op_cityscapes_pair(void* stream, const uint8_t* gt_label_ids, const uint16_t* gt_instance_ids, const void* pred, int pred_kind,
+                             int N, int64_t P, int64_t* conf, void* work, int32_t* entries, int max_entries, int64_t* counts)
+{
+    if (!gt_label_ids || !pred || !conf || !counts || (pred_kind != 0 && pred_kind != 1) || N <= 0 || P <= 0 || max_entries < 0
+        || (gt_instance_ids && (!entries || !work || (uintptr_t)work % 16)))
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "cityscapes_pair: bad argument (null pointer, pred_kind outside {0, 1}, N, P <= 0, max_entries < 0, or an instance map without entries / 16-byte aligned work)");
+    if (P >= (1LL << 31)) return fail(nullptr, FCN8S_ERR_SHAPE, "cityscapes_pair: an image has to have fewer than 2^31 pixels (32-bit counts per instance)");
+    take_deferred_error(nullptr);
+    launch_cityscapes_pair(gt_label_ids, gt_instance_ids, pred, pred_kind, N, P, (unsigned long long*)conf, work, entries, max_entries,
+                           (unsigned long long*)counts, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
 int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* mm, float* v, int64_t n, int t, float lr, float b1, float b2, float eps, float gs)
 {
     const float lr_t = lr * (float)std::sqrt(1.0 - std::pow((double)b2, (double)t)) / (float)(1.0 - std::pow((double)b1, (double)t));

@@ -472,6 +472,78 @@ class FCN8s:
             self.engine.freeze(False)
         return len(paths)
 
+    def evaluate_cityscapes(self, images_dir, ground_truth_search, resize=False, image_file_extension='png', scales=None, flip=False, crf=None,
+                            instance_level=True, json_path=None):
+        '''Not in the reference: the official Cityscapes pixel-level table (IoU and iIoU, for classes and for categories) of this model in
+        one call, scored where the predictions already are.  Every ground-truth file of the glob `ground_truth_search` (the official one is
+        `<cityscapes>/gtFine/val/*/*_gtFine_labelIds.png`) is paired with its image `<city>_<seq>_<frame>*.<ext>` below `images_dir`; per
+        image: decode, one upload, `predict` with `scales` / `flip` / `crf` on the device, upload of the label-id (and, with
+        `instance_level`, the `*_instanceIds.png`) map, one `fcn8s_op_cityscapes_pair` call that consumes the int64 argmax as it is.  The
+        prediction never visits the host and no file is written -- except with `resize=(h, w)`, where it comes back to the file's own size by
+        PIL's nearest neighbour exactly as `predict_and_export_label_ids` writes it.  Returns the dict of
+        `cityscapes_eval.evaluate_directory(..., instance_level=...)` -- which it equals exactly when that is run on the export of
+        `predict_and_export_label_ids` with the same arguments; `json_path`: also write it in the evaluator's result-file layout
+        (instance-level only).'''
+        from PIL import Image
+        import torch
+        from . import cityscapes_eval as ce
+        if self.num_classes != 20:
+            raise ValueError("the Cityscapes evaluation uses the 20 Cityscapes train ids; this model has {} classes.".format(self.num_classes))
+        if json_path is not None and not instance_level:
+            raise ValueError("`json_path` writes the evaluator's result file, which holds the instance-level scores: needs instance_level=True.")
+        gts = sorted(glob(ground_truth_search))
+        if not gts:
+            raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
+        walk = ce.walk_predictions(images_dir)
+        paths = [ce.find_prediction(images_dir, g, walk, extension=image_file_extension) for g in gts]
+        dev = self.engine.device
+        ev = ce.PixelLevelEvaluator(instance_level=instance_level)
+        pixels = 0
+        kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
+        tr = trange(len(gts), file=sys.stdout)
+        tr.set_description('Evaluating')
+        self.engine.freeze(True)
+        try:
+            for i in tr:
+                pil = Image.open(paths[i]).convert('RGB')
+                size = pil.size
+                if resize and not np.array_equal((pil.height, pil.width), resize):
+                    pil = pil.resize((resize[1], resize[0]), Image.BILINEAR)
+                image = torch.from_numpy(np.array(pil)[None]).to(dev)
+                pred = self.predict(image, argmax=True, scales=scales, flip=flip, **kw)[0]               # int64 train ids, on the device
+                train_ids = True
+                if pil.size != size:
+                    ids = Image.fromarray(ce.TRAINIDS_TO_IDS_ARRAY[pred.cpu().numpy()]).resize(size, Image.NEAREST)
+                    pred = torch.from_numpy(np.array(ids)).to(dev); train_ids = False
+                gt = np.array(Image.open(gts[i]))
+                if pred.shape[1] != gt.shape[1]:
+                    raise ValueError("Image widths of " + paths[i] + " and " + gts[i] + " are not equal.")
+                if pred.shape[0] != gt.shape[0]:
+                    raise ValueError("Image heights of " + paths[i] + " and " + gts[i] + " are not equal.")
+                if gt.max() >= ce.NUM_IDS:
+                    raise ValueError("Unknown label with id {:}".format(int(gt.max())))
+                inst = None
+                if instance_level:
+                    inf = ce.instance_file_of(gts[i])
+                    if inf == gts[i] or not os.path.isfile(inf):
+                        raise ValueError("Unable to load " + inf)
+                    inst = np.array(Image.open(inf))
+                    if inst.shape != gt.shape:
+                        raise ValueError("Image sizes of " + inf + " and " + gts[i] + " are not equal.")
+                    inst = ce.instance_map_tensor(inst, dev)
+                ev.add(pred, torch.from_numpy(gt.astype(np.uint8)).to(dev), inst, pred_is_train_ids=train_ids)
+                pixels += gt.size
+                if int(ev.conf.sum()) != pixels:
+                    raise ValueError("Number of analyzed pixels and entries in confusion matrix disagree: contMatrix {}, pixels {}".format(int(ev.conf.sum()), pixels))
+        finally:
+            self.engine.freeze(False)
+        res = ev.results()
+        res["confMatrix"] = ev.conf
+        res["nbPixels"] = pixels
+        if json_path is not None:
+            ce.write_result_json(res, json_path)
+        return res
+
     def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement, scales=None, flip=False, crf=None):
         '''Loop body of predict_and_save (fcn8s_tensorflow.py:829-855).'''
         from PIL import Image

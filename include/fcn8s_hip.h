@@ -566,6 +566,30 @@ int fcn8s_op_softmax_argmax(void* stream, const float* logits, float* softmax_ou
                             int64_t npix, int C);
 int fcn8s_op_confusion(void* stream, const uint8_t* label_ids, const int64_t* pred_ids, int64_t npix,
                        int64_t* conf, int C);
+/* The counting half of the official Cityscapes pixel-level evaluation (cityscapesscripts/evaluation/evalPixelLevelSemanticLabeling.py with
+ * evalInstLevelScore on, its default) for a batch of N images of P pixels each on DEVICE pointers, in one pass that reads every input byte once.
+ *   gt_label_ids [N,P] uint8 label ids 0..33; gt_instance_ids [N,P] uint16 (*_gtFine_instanceIds.png: a plain label id below 1000, or
+ *   label * 1000 + k), or NULL: confusion matrix only; pred [N,P]: pred_kind 0 = int64 train ids 0..19 as fcn8s_predict writes them, mapped to
+ *   label ids inside the kernel (labels.py trainId -> id; 0 -> 0), pred_kind 1 = uint8 label ids 0..33.
+ *   conf [34*34] int64: conf[gt * 34 + pred] += 1 for every pixel (the caller clears it; it accumulates over calls).
+ *   Instance statistics (:595-635).  Counted labels: person 24, rider 25, car 26, truck 27, bus 28, train 31, motorcycle 32, bicycle 33; category
+ *   id lists: human = {24, 25}, vehicle = {26 .. 33} (caravan 29 and trailer 30 belong to the list although their instances are skipped).  For every
+ *   value v > 1000 (strictly) of an image's instance map with L = v / 1000 a counted label:
+ *       size = #{inst == v},  tp = #{inst == v and pred == L},  cattp = #{inst == v and pred in ids(category(L))}
+ *   (the mask is the instance map's alone; gt is not consulted).  v with an ignoreInEval label (1000 < v < 7000, 9xxx, 10xxx, 14xxx .. 16xxx, 18xxx,
+ *   29xxx, 30xxx) is skipped as the evaluator skips it; v with an evaluated label that has no instances (7005, say) or with L > 33 is the
+ *   evaluator's KeyError: such pixels are counted in counts[n][2] and the caller refuses the image.
+ *   entries [N][max_entries][4] int32 = {v, size, tp, cattp} of image n in ascending v (np.unique's order); counts [N][3] int64 (written, not
+ *   accumulated) = {number of entries found -- it may exceed max_entries, then only the first max_entries were written and the call is to be
+ *   repeated with more room --, pixels whose gt or pred id is out of range (they are counted nowhere else), pixels of a bad v}.
+ *   The host turns entries into the weighted sums in float64, in the evaluator's order (cityscapes_eval.py): weight = avgClassSize[L] / size,
+ *   tpWeighted += tp * weight, fnWeighted += (size - tp) * weight, the category likewise with cattp; iIoU = tpW / (tpW + fp + fnW), fp from conf.
+ * work: fcn8s_op_cityscapes_work_bytes(N) bytes of 16-byte aligned device scratch (may be NULL without an instance map).  Integers only: two
+ * runs give the same bits.  Stream-ordered; does not synchronise.  FCN8S_ERR_BAD_ARG (nothing launched) for a NULL gt / pred / conf / counts,
+ * pred_kind outside {0, 1}, N <= 0, P <= 0, max_entries < 0, or an instance map with NULL entries / work; FCN8S_ERR_SHAPE for P >= 2^31. */
+size_t fcn8s_op_cityscapes_work_bytes(int N);
+int fcn8s_op_cityscapes_pair(void* stream, const uint8_t* gt_label_ids, const uint16_t* gt_instance_ids, const void* pred, int pred_kind,
+                             int N, int64_t P, int64_t* conf, void* work, int32_t* entries, int max_entries, int64_t* counts);
 int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* m, float* v, int64_t n, int t,
                      float lr, float beta1, float beta2, float eps, float grad_scale);
 int fcn8s_op_sgd_momentum(void* stream, float* theta, const float* g, float* buf, int64_t n,
