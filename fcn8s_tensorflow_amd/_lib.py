@@ -140,6 +140,7 @@ SIGNATURES = {
     "fcn8s_op_confusion": (_i, [_p, _p, _p, _i64, _p, _i]),
     "fcn8s_op_cityscapes_work_bytes": (_sz, [_i]),
     "fcn8s_op_cityscapes_pair": (_i, [_p, _p, _p, _p, _i, _i, _i64, _p, _p, _p, _i, _p]),
+    "fcn8s_op_boundary_pair": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "fcn8s_op_tf_adam": (_i, [_p, _p, _p, _p, _p, _i64, _i, _f, _f, _f, _f, _f]),
     "fcn8s_op_sgd_momentum": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f]),
 }

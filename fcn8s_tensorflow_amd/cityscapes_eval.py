@@ -345,15 +345,226 @@ def pair_counts_numpy(pred, gt_label_ids, gt_instance_ids=None, pred_is_train_id
     return conf, [instance_entries_numpy(pred_ids[n], inst[n]) for n in range(pred.shape[0])]
 
 
+# ---------------------------------------------------------------------------------------------------------
+# boundary measures: trimap IoU and boundary F-score
+# ---------------------------------------------------------------------------------------------------------
+# IoU over all pixels is dominated by the interiors of road, building and sky; a CRF or a test-time ensemble moves a few pixels around
+# every contour.  Two measures look only there (the definition, all integers, is in include/fcn8s_hip.h at fcn8s_op_boundary_pair):
+#   trimap IoU (Kraehenbuehl & Koltun 2011; Chen et al. 2015): the IoU restricted to the pixels within r of a ground-truth boundary;
+#   boundary F-score (Csurka et al., BMVC 2013): precision / recall of the predicted against the true contours of a class under a
+#   distance tolerance.
+# The counts are taken by `fcn8s_op_boundary_pair` when the maps are on the GPU, by NumPy otherwise; the scores are float64 on the host.
+MAX_BOUNDARY_RADIUS = 16
+BAD_ID = 255                                                   # what an id out of range takes part as
+
+
+def _check_radius(radius):
+    R = int(radius)
+    if R != radius or not 1 <= R <= MAX_BOUNDARY_RADIUS:
+        raise ValueError("`boundary_radius` must be an integer in 1..{}, not {!r}".format(MAX_BOUNDARY_RADIUS, radius))
+    return R
+
+
+def ring_of(d2, R):
+    """Smallest k >= 0 with k*k >= d2, R + 1 beyond R (and for 'nothing found', any d2 > R*R)."""
+    d2 = np.asarray(d2)
+    k = np.full(d2.shape, R + 1, np.int64)
+    for r in range(R, -1, -1):
+        k[d2 <= r * r] = r
+    return k
+
+
+def boundary_set(M):
+    """B(M): the pixels with a 4-neighbour inside the image that holds another value."""
+    M = np.asarray(M)
+    b = np.zeros(M.shape, bool)
+    v = M[:-1] != M[1:]; b[:-1] |= v; b[1:] |= v
+    h = M[:, :-1] != M[:, 1:]; b[:, :-1] |= h; b[:, 1:] |= h
+    return b
+
+
+def _half_disk(R):
+    """The offsets (d2, dy, dx) of one half of the disk of radius R without its centre (the other half is their negatives), ascending d2."""
+    return sorted((dy * dy + dx * dx, dy, dx) for dy in range(0, R + 1) for dx in range(-R, R + 1)
+                  if (dy > 0 or dx > 0) and dy * dy + dx * dx <= R * R)
+
+
+def _nearest_other_label(G, R):
+    """d2(p) = min |q - p|^2 over q != p inside the image with G[q] != G[p], R*R + 1 if there is none within R: shifted array
+    comparisons over the disk's offsets in ascending distance (a pair p, q that differs is a hit for both of them)."""
+    H, W = G.shape
+    big = R * R + 1
+    d2 = np.full((H, W), big, np.uint16)
+    for dd, dy, dx in _half_disk(R):
+        if dy >= H or abs(dx) >= W:
+            continue
+        a = (slice(0, H - dy), slice(max(0, -dx), W - max(0, dx)))                 # p
+        b = (slice(dy, H), slice(max(0, dx), W - max(0, -dx)))                     # q = p + (dy, dx)
+        hit = G[a] != G[b]
+        val = np.where(hit, np.uint16(dd), np.uint16(big))
+        np.minimum(d2[a], val, out=d2[a]); np.minimum(d2[b], val, out=d2[b])
+    return d2.astype(np.int64)
+
+
+def _nearest_contour_of_class(src, src_sel, tgt, tgt_b, R):
+    """For every pixel p of the mask `src_sel` with c = src[p]: min |q - p|^2 over q in tgt_b with tgt[q] == c (q = p allowed), R*R + 1 if
+    none within R.  Returns (classes, d2) over the selected pixels in np.nonzero order; only those pixels are searched."""
+    H, W = src.shape
+    ys, xs = np.nonzero(src_sel)
+    c = src[ys, xs]
+    big = R * R + 1
+    d2 = np.full(c.shape, big, np.int64)
+    pad = np.full((H + 2 * R, W + 2 * R), 254, np.uint8)                             # 254: no contour pixel of any class here
+    pad[R:R + H, R:R + W] = np.where(tgt_b, tgt, 254)
+    idx = np.arange(c.size)
+    half = _half_disk(R)
+    offsets = sorted([(0, 0, 0)] + half + [(dd, -dy, -dx) for dd, dy, dx in half])
+    for dd, dy, dx in offsets:
+        if idx.size == 0:
+            break
+        hit = pad[ys[idx] + (R + dy), xs[idx] + (R + dx)] == c[idx]
+        d2[idx[hit]] = dd                                                         # ascending: the first hit is the nearest
+        idx = idx[~hit]
+    return c, d2
+
+
+def boundary_tables_numpy(G, P, R):
+    """The definition for ONE image on label-id maps (uint8, an id out of range already replaced by BAD_ID = 255):
+    (rings [R + 1, 34, 34], bprec [R + 2, 34], brec [R + 2, 34], bad), int64."""
+    G = np.ascontiguousarray(G, dtype=np.uint8); P = np.ascontiguousarray(P, dtype=np.uint8)
+    if G.ndim != 2 or G.shape != P.shape or G.size == 0:
+        raise ValueError("ground truth of shape {} against a prediction of shape {}".format(G.shape, P.shape))
+    ok = (G < NUM_IDS) & (P < NUM_IDS)
+    g = G[ok].astype(np.int64); p = P[ok].astype(np.int64)
+    k = ring_of(_nearest_other_label(G, R), R)[ok]
+    rings = np.bincount((k - 1) * NUM_IDS * NUM_IDS + g * NUM_IDS + p, minlength=(R + 1) * NUM_IDS * NUM_IDS).reshape(R + 1, NUM_IDS, NUM_IDS)
+    BG, BP = boundary_set(G), boundary_set(P)
+    c, e2 = _nearest_contour_of_class(P, BP & ok, G, BG, R)
+    bprec = np.bincount(ring_of(e2, R) * NUM_IDS + c, minlength=(R + 2) * NUM_IDS).reshape(R + 2, NUM_IDS)
+    c, e2 = _nearest_contour_of_class(G, BG & ok, P, BP, R)
+    brec = np.bincount(ring_of(e2, R) * NUM_IDS + c, minlength=(R + 2) * NUM_IDS).reshape(R + 2, NUM_IDS)
+    return rings.astype(np.int64), bprec.astype(np.int64), brec.astype(np.int64), int(ok.size - ok.sum())
+
+
+def boundary_counts_numpy(pred, gt, radius, pred_is_train_ids=True):
+    """The NumPy route of fcn8s_op_boundary_pair's definition for one image (H, W) or a stack (N, H, W): `pred` train ids 0..19 (or, with
+    `pred_is_train_ids=False`, label ids 0..33) against the label ids `gt`.  Returns the int64 tables (rings [R + 1, 34, 34],
+    bprec [R + 2, 34], brec [R + 2, 34]) summed over the images.  An id out of range is refused."""
+    R = _check_radius(radius)
+    pred = np.asarray(pred); gt = np.asarray(gt)
+    if pred.shape != gt.shape or pred.ndim not in (2, 3) or pred.size == 0:
+        raise ValueError("prediction of shape {} against ground truth of shape {}".format(pred.shape, gt.shape))
+    if pred.min() < 0 or pred.max() >= (20 if pred_is_train_ids else NUM_IDS):
+        raise ValueError("predicted pixels hold an id outside the {}".format("train ids 0..19" if pred_is_train_ids else "label ids 0..33"))
+    if gt.min() < 0 or gt.max() >= NUM_IDS:
+        raise ValueError("Unknown label with id {:}".format(int(gt.max())))
+    ids = TRAINIDS_TO_IDS_ARRAY[pred.astype(np.int64)] if pred_is_train_ids else pred.astype(np.uint8)
+    gt = gt.astype(np.uint8)
+    if pred.ndim == 2:
+        ids, gt = ids[None], gt[None]
+    rings = np.zeros((R + 1, NUM_IDS, NUM_IDS), np.int64); bprec = np.zeros((R + 2, NUM_IDS), np.int64); brec = np.zeros((R + 2, NUM_IDS), np.int64)
+    for n in range(ids.shape[0]):
+        r, bp, br, _bad = boundary_tables_numpy(gt[n], ids[n], R)
+        rings += r; bprec += bp; brec += br
+    return rings, bprec, brec
+
+
+def boundary_counts_device(pred, gt_label_ids, radius):
+    """One `fcn8s_op_boundary_pair` call on maps that live on the GPU: `pred` int64 train ids (as `predict` returns them) or uint8 label
+    ids, `gt_label_ids` uint8, shapes (H, W) or (N, H, W).  Returns the int64 ndarrays (rings, bprec, brec) of this call, summed over the
+    images; only they and the count of out-of-range pixels come back to the host.  An id out of range is refused."""
+    import torch
+    from . import _lib as L
+    R = _check_radius(radius)
+    dev = pred.device
+    if pred.dtype == torch.int64:
+        kind = 0
+    elif pred.dtype == torch.uint8:
+        kind = 1
+    else:
+        raise ValueError("`pred` must hold int64 train ids or uint8 label ids, not {}".format(pred.dtype))
+    if gt_label_ids.dtype != torch.uint8:
+        raise ValueError("`gt_label_ids` must be uint8, not {}".format(gt_label_ids.dtype))
+    if tuple(gt_label_ids.shape) != tuple(pred.shape) or pred.dim() not in (2, 3) or pred.numel() == 0:
+        raise ValueError("prediction of shape {} against ground truth of shape {}".format(tuple(pred.shape), tuple(gt_label_ids.shape)))
+    N = 1 if pred.dim() == 2 else int(pred.shape[0])
+    H, W = int(pred.shape[-2]), int(pred.shape[-1])
+    pred = pred.contiguous(); gt = gt_label_ids.to(dev).contiguous()
+    nr, nb = (R + 1) * NUM_IDS * NUM_IDS, (R + 2) * NUM_IDS
+    out = torch.zeros(nr + 2 * nb + 1, dtype=torch.int64, device=dev)                # rings | bprec | brec | bad: one clear, one download
+    base = out.data_ptr()
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    L.check(L.lib.fcn8s_op_boundary_pair(stream, C.c_void_p(gt.data_ptr()), C.c_void_p(pred.data_ptr()), kind, N, H, W, R, C.c_void_p(base),
+                                         C.c_void_p(base + 8 * nr), C.c_void_p(base + 8 * (nr + nb)), C.c_void_p(base + 8 * (nr + 2 * nb))))
+    o = out.cpu().numpy()
+    if o[-1]:
+        bad_gt = int(gt.max()) >= NUM_IDS
+        raise ValueError("Unknown label with id {:}".format(int(gt.max())) if bad_gt else
+                         "{} predicted pixels hold an id outside the {}".format(int(o[-1]), "train ids 0..19" if kind == 0 else "label ids 0..33"))
+    return o[:nr].reshape(R + 1, NUM_IDS, NUM_IDS).copy(), o[nr:nr + nb].reshape(R + 2, NUM_IDS).copy(), o[nr + nb:nr + 2 * nb].reshape(R + 2, NUM_IDS).copy()
+
+
+def trimap_scores(rings):
+    """Trimap IoU from a rings table [R + 1, 34, 34]: the evaluator's own scores (`iou_for_label`, `iou_for_category`, `score_average`) on
+    the confusion matrix of the pixels within r of a ground-truth boundary, i.e. on the sum of the first r ring matrices.  Every list has
+    R + 1 entries: index r - 1 is the band of width r = 1..R, the last one is the whole image (all rings: the ordinary IoU)."""
+    rings = np.asarray(rings)
+    if rings.ndim != 3 or rings.shape[1:] != (NUM_IDS, NUM_IDS) or rings.shape[0] < 2:
+        raise ValueError("a rings table is [R + 1, 34, 34], not {}".format(rings.shape))
+    bands = np.cumsum(rings.astype(np.int64), axis=0)
+    cls = [OrderedDict((ID_TO_NAME[l], iou_for_label(l, b)) for l in range(NUM_IDS)) for b in bands]
+    cat = [OrderedDict((c, iou_for_category(c, b)) for c in CATEGORY_TO_IDS) for b in bands]
+    return {"trimapScoreClasses": [score_average(s) for s in cls],
+            "trimapScoreCategories": [score_average(s) for s in cat],
+            "trimapClassScores": OrderedDict((ID_TO_NAME[l], [s[ID_TO_NAME[l]] for s in cls]) for l in range(NUM_IDS))}
+
+
+def boundary_f_scores(bprec, brec):
+    """Boundary F-score from the tables bprec / brec [R + 2, 34].  For label c and tolerance t = 0..R: precision = sum(bprec[0..t, c]) /
+    sum(bprec[:, c]) (the share of c's predicted contour pixels that lie within t of a true contour pixel of c), recall likewise from brec,
+    F = 2 P R / (P + R); NaN where a denominator is 0 and for the labels the evaluation ignores.  `boundaryFScoreClasses[t]` is the mean
+    over the evaluated labels whose F is not NaN.  The counts are accumulated over all images before the division (the dataset-level
+    protocol of the Cityscapes IoU), not averaged per image as Csurka et al. do."""
+    bprec = np.asarray(bprec).astype(np.int64); brec = np.asarray(brec).astype(np.int64)
+    if bprec.ndim != 2 or bprec.shape[1] != NUM_IDS or bprec.shape[0] < 3 or brec.shape != bprec.shape:
+        raise ValueError("bprec / brec are [R + 2, 34] tables, not {} / {}".format(bprec.shape, brec.shape))
+    R = bprec.shape[0] - 2
+    nan = float('nan')
+    per = OrderedDict()
+    for l in range(NUM_IDS):
+        if l in IGNORED_IDS:
+            per[ID_TO_NAME[l]] = OrderedDict((k, [nan] * (R + 1)) for k in ("precision", "recall", "f"))
+            continue
+        np_, nr_ = int(bprec[:, l].sum()), int(brec[:, l].sum())
+        hp, hr = np.cumsum(bprec[:R + 1, l]), np.cumsum(brec[:R + 1, l])
+        prec = [int(h) / np_ if np_ else nan for h in hp]
+        rec = [int(h) / nr_ if nr_ else nan for h in hr]
+        f = [nan if (math.isnan(a) or math.isnan(b) or a + b == 0) else 2 * a * b / (a + b) for a, b in zip(prec, rec)]
+        per[ID_TO_NAME[l]] = OrderedDict((("precision", prec), ("recall", rec), ("f", f)))
+    mean = [score_average({n: s["f"][t] for n, s in per.items()}) for t in range(R + 1)]
+    return {"boundaryFScoreClasses": mean, "boundaryClassScores": per}
+
+
 class PixelLevelEvaluator:
     """Accumulates the official confusion matrix from FCN-8s predictions (train ids, as `FCN8s.predict`
     returns them) and Cityscapes `*_gtFine_labelIds` ground truth, and reports the 19-class scores; with `instance_level`, the
-    instance statistics from `*_gtFine_instanceIds` maps and the iIoU scores as well (the evaluator's default table)."""
+    instance statistics from `*_gtFine_instanceIds` maps and the iIoU scores as well (the evaluator's default table); with
+    `boundary_radius=R` (1..16), the trimap IoU for the band widths 1..R and the boundary F-score for the tolerances 0..R as well."""
 
-    def __init__(self, instance_level=False):
+    def __init__(self, instance_level=False, boundary_radius=None):
         self.conf = np.zeros((NUM_IDS, NUM_IDS), np.int64)
         self.instance_level = bool(instance_level)
         self.inst_stats = new_instance_stats() if self.instance_level else None
+        self.boundary_radius = None if boundary_radius is None else _check_radius(boundary_radius)
+        if self.boundary_radius is not None:
+            R = self.boundary_radius
+            self.rings = np.zeros((R + 1, NUM_IDS, NUM_IDS), np.int64)
+            self.bprec = np.zeros((R + 2, NUM_IDS), np.int64)
+            self.brec = np.zeros((R + 2, NUM_IDS), np.int64)
+
+    def add_boundary_tables(self, tables):
+        rings, bprec, brec = tables
+        self.rings += rings; self.bprec += bprec; self.brec += brec
 
     def add(self, pred_train_ids, gt_label_ids, gt_instance_ids=None, pred_is_train_ids=True, max_entries=DEFAULT_MAX_ENTRIES):
         """One image (H, W) or a stack (N, H, W).  Maps on the GPU (torch tensors; the prediction decides) are counted there by one
@@ -376,6 +587,8 @@ class PixelLevelEvaluator:
             if inst is not None and not isinstance(inst, torch.Tensor):
                 inst = instance_map_tensor(inst, pred.device)
             conf, entries = pair_counts_device(pred, gt, inst, max_entries)
+            if self.boundary_radius is not None:
+                self.add_boundary_tables(boundary_counts_device(pred, gt, self.boundary_radius))
         else:
             to_np = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
             inst = None
@@ -384,6 +597,8 @@ class PixelLevelEvaluator:
                 if inst.dtype == np.int16:
                     inst = inst.view(np.uint16)
             conf, entries = pair_counts_numpy(to_np(pred_train_ids), to_np(gt_label_ids), inst, pred_is_train_ids)
+            if self.boundary_radius is not None:
+                self.add_boundary_tables(boundary_counts_numpy(to_np(pred_train_ids), to_np(gt_label_ids), self.boundary_radius, pred_is_train_ids))
         self.conf += conf
         if entries is not None:
             for e in entries:
@@ -410,6 +625,14 @@ class PixelLevelEvaluator:
             res.update({"classInstScores": ics, "averageScoreInstClasses": score_average(ics),
                         "categoryInstScores": icat, "averageScoreInstCategories": score_average(icat),
                         "instStats": self.inst_stats})
+        if self.boundary_radius is not None:
+            R = self.boundary_radius
+            tri = trimap_scores(self.rings)
+            res.update({"boundaryRadius": R,
+                        "trimapScoreClasses": tri["trimapScoreClasses"][:R], "trimapScoreCategories": tri["trimapScoreCategories"][:R],
+                        "trimapClassScores": OrderedDict((n, v[:R]) for n, v in tri["trimapClassScores"].items()),
+                        "trimapRings": self.rings, "boundaryPrecisionCounts": self.bprec, "boundaryRecallCounts": self.brec})
+            res.update(boundary_f_scores(self.bprec, self.brec))
         return res
 
 
@@ -422,6 +645,10 @@ def instance_map_tensor(inst, device):
             raise ValueError("instance ids do not fit 16 bits")
         a = a.astype(np.uint16)
     return torch.from_numpy(a.view(np.int16)).to(device)
+
+
+BOUNDARY_RESULT_KEYS = ("boundaryRadius", "trimapScoreClasses", "trimapScoreCategories", "trimapClassScores", "boundaryFScoreClasses",
+                        "boundaryClassScores", "trimapRings", "boundaryPrecisionCounts", "boundaryRecallCounts")
 
 
 def result_dict(res):
@@ -440,6 +667,9 @@ def result_dict(res):
         whole[k] = OrderedDict(res[k])
     for k in ("averageScoreClasses", "averageScoreInstClasses", "averageScoreCategories", "averageScoreInstCategories"):
         whole[k] = res[k]
+    for k in BOUNDARY_RESULT_KEYS:                                 # not the evaluator's: present only after an evaluation with a boundary radius
+        if k in res:
+            whole[k] = res[k].tolist() if isinstance(res[k], np.ndarray) else res[k]
     return whole
 
 
@@ -500,15 +730,17 @@ def instance_file_of(ground_truth_file):
     return ground_truth_file.replace("labelIds", "instanceIds")
 
 
-def evaluate_file_pairs(prediction_files, ground_truth_files, device=None, instance_level=False):
+def evaluate_file_pairs(prediction_files, ground_truth_files, device=None, instance_level=False, boundary_radius=None):
     """evaluateImgLists / evaluatePair (evalPixelLevelSemanticLabeling.py:454-498, 550-635): accumulate conf[gt, pred] over
     pairs of label-id PNGs with the evaluator's checks, then the class / category scores.  `device`: a torch cuda device
     to count on the GPU (the library's kernels), None = NumPy.  `instance_level`: also read each ground truth's `*_instanceIds.png`
-    and report the iIoU scores (`classInstScores`, `categoryInstScores`, their averages, `instStats`)."""
+    and report the iIoU scores (`classInstScores`, `categoryInstScores`, their averages, `instStats`).  `boundary_radius=R`: also the
+    trimap IoU for the band widths 1..R around the ground-truth boundaries and the boundary F-score for the tolerances 0..R (the
+    `trimap*` / `boundary*` keys; `trimap_scores`, `boundary_f_scores`)."""
     from PIL import Image
     if len(prediction_files) != len(ground_truth_files):
         raise ValueError("List of images for prediction and groundtruth are not of equal size.")
-    ev = PixelLevelEvaluator(instance_level=instance_level)
+    ev = PixelLevelEvaluator(instance_level=instance_level, boundary_radius=boundary_radius)
     pixels = 0
     for pf, gf in zip(prediction_files, ground_truth_files):
         pred, gt = np.array(Image.open(pf)), np.array(Image.open(gf))
@@ -541,6 +773,15 @@ def evaluate_file_pairs(prediction_files, ground_truth_files, device=None, insta
             confusion_add(ev.conf, torch.from_numpy(gt.astype(np.uint8)).to(device), torch.from_numpy(pred.astype(np.int64)).to(device))
         else:
             confusion_add(ev.conf, gt, pred)
+        if boundary_radius is not None and not instance_level:         # (with instance_level, ev.add has counted them)
+            if device is not None:
+                import torch
+                if pred.max() >= NUM_IDS:
+                    raise ValueError("Unknown label with id {:} in {}".format(int(pred.max()), pf))
+                ev.add_boundary_tables(boundary_counts_device(torch.from_numpy(pred.astype(np.uint8)).to(device),
+                                                              torch.from_numpy(gt.astype(np.uint8)).to(device), boundary_radius))
+            else:
+                ev.add_boundary_tables(boundary_counts_numpy(pred, gt, boundary_radius, pred_is_train_ids=False))
         pixels += pred.size
         if int(ev.conf.sum()) != pixels:
             raise ValueError("Number of analyzed pixels and entries in confusion matrix disagree: contMatrix {}, pixels {}".format(int(ev.conf.sum()), pixels))
@@ -550,11 +791,11 @@ def evaluate_file_pairs(prediction_files, ground_truth_files, device=None, insta
     return res
 
 
-def evaluate_directory(ground_truth_search, prediction_path, device=None, instance_level=False):
+def evaluate_directory(ground_truth_search, prediction_path, device=None, instance_level=False, boundary_radius=None):
     """The evaluator's no-argument mode (:667-676): every ground-truth file matching the glob (the official one is
     `<cityscapes>/gtFine/val/*/*_gtFine_labelIds.png`) against its prediction below `prediction_path`."""
     gts = sorted(glob.glob(ground_truth_search))
     if not gts:
         raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
     walk = walk_predictions(prediction_path)
-    return evaluate_file_pairs([find_prediction(prediction_path, g, walk) for g in gts], gts, device, instance_level)
+    return evaluate_file_pairs([find_prediction(prediction_path, g, walk) for g in gts], gts, device, instance_level, boundary_radius)

@@ -360,6 +360,10 @@ void launch_crf_argmax(const float* p, long long npix, int C, long long* am, hip
 size_t cityscapes_work_bytes(int N);
 void launch_cityscapes_pair(const uint8_t* gt, const uint16_t* inst, const void* pred, int pred_kind, int N, long long P,
                             unsigned long long* conf, void* work, int* entries, int max_entries, unsigned long long* counts, hipStream_t s);
+// boundary.hip (fcn8s_op_boundary_pair; the definition is in fcn8s_hip.h).  One kernel; rings [R + 1][34][34], bprec / brec [R + 2][34] and bad [1] are
+// accumulated into.  1 <= R <= 16, H * W < 2^31.
+void launch_boundary_pair(const uint8_t* gt, const void* pred, int pred_kind, int N, int H, int W, int R, unsigned long long* rings,
+                          unsigned long long* bprec, unsigned long long* brec, unsigned long long* bad, hipStream_t s);
 // wrapping sum over every 61st element's bit pattern (weighted by position): changes whenever an optimizer step or a bulk copy touches the buffer
 void launch_fingerprint(const float* x, long long n, unsigned long long* out, hipStream_t s);
 void launch_init_normal(float* w, long long n, float stddev, int truncated, unsigned long long seed,

@@ -3968,6 +3968,17 @@ int fcn8s_op_cityscapes_pair(void* stream, const uint8_t* gt_label_ids, const ui
                            (unsigned long long*)counts, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
+int fcn8s_op_boundary_pair(void* stream, const uint8_t* gt_label_ids, const void* pred, int pred_kind, int N, int H, int W, int R,
+                           int64_t* rings, int64_t* bprec, int64_t* brec, int64_t* bad)
+{
+    if (!gt_label_ids || !pred || !rings || !bprec || !brec || !bad || (pred_kind != 0 && pred_kind != 1) || N <= 0 || H <= 0 || W <= 0 || R < 1 || R > 16)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "boundary_pair: bad argument (null pointer, pred_kind outside {0, 1}, N, H, W <= 0, or R outside 1 .. 16)");
+    if ((long long)H * W >= (1LL << 31)) return fail(nullptr, FCN8S_ERR_SHAPE, "boundary_pair: an image has to have fewer than 2^31 pixels");
+    take_deferred_error(nullptr);
+    launch_boundary_pair(gt_label_ids, pred, pred_kind, N, H, W, R, (unsigned long long*)rings, (unsigned long long*)bprec, (unsigned long long*)brec,
+                         (unsigned long long*)bad, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
 int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* mm, float* v, int64_t n, int t, float lr, float b1, float b2, float eps, float gs)
 {
     const float lr_t = lr * (float)std::sqrt(1.0 - std::pow((double)b2, (double)t)) / (float)(1.0 - std::pow((double)b1, (double)t));

@@ -473,7 +473,7 @@ class FCN8s:
         return len(paths)
 
     def evaluate_cityscapes(self, images_dir, ground_truth_search, resize=False, image_file_extension='png', scales=None, flip=False, crf=None,
-                            instance_level=True, json_path=None):
+                            instance_level=True, json_path=None, boundary_radius=None):
         '''Not in the reference: the official Cityscapes pixel-level table (IoU and iIoU, for classes and for categories) of this model in
         one call, scored where the predictions already are.  Every ground-truth file of the glob `ground_truth_search` (the official one is
         `<cityscapes>/gtFine/val/*/*_gtFine_labelIds.png`) is paired with its image `<city>_<seq>_<frame>*.<ext>` below `images_dir`; per
@@ -483,7 +483,10 @@ class FCN8s:
         PIL's nearest neighbour exactly as `predict_and_export_label_ids` writes it.  Returns the dict of
         `cityscapes_eval.evaluate_directory(..., instance_level=...)` -- which it equals exactly when that is run on the export of
         `predict_and_export_label_ids` with the same arguments; `json_path`: also write it in the evaluator's result-file layout
-        (instance-level only).'''
+        (instance-level only).  `boundary_radius=R` (1..16): one more call per image, `fcn8s_op_boundary_pair`, on the prediction and the
+        label map that are already on the device, and the trimap IoU for the band widths 1..R around the ground-truth boundaries and the
+        boundary F-score for the tolerances 0..R in the result (`cityscapes_eval.trimap_scores`, `boundary_f_scores`): what `scales`,
+        `flip` or `crf` change at the contours.  With None nothing more is launched and the dict is the one described above.'''
         from PIL import Image
         import torch
         from . import cityscapes_eval as ce
@@ -497,7 +500,7 @@ class FCN8s:
         walk = ce.walk_predictions(images_dir)
         paths = [ce.find_prediction(images_dir, g, walk, extension=image_file_extension) for g in gts]
         dev = self.engine.device
-        ev = ce.PixelLevelEvaluator(instance_level=instance_level)
+        ev = ce.PixelLevelEvaluator(instance_level=instance_level, boundary_radius=boundary_radius)
         pixels = 0
         kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
         tr = trange(len(gts), file=sys.stdout)

@@ -590,6 +590,31 @@ int fcn8s_op_confusion(void* stream, const uint8_t* label_ids, const int64_t* pr
 size_t fcn8s_op_cityscapes_work_bytes(int N);
 int fcn8s_op_cityscapes_pair(void* stream, const uint8_t* gt_label_ids, const uint16_t* gt_instance_ids, const void* pred, int pred_kind,
                              int N, int64_t P, int64_t* conf, void* work, int32_t* entries, int max_entries, int64_t* counts);
+/* Boundary measures of a segmentation against its ground truth -- the counting half of the trimap IoU (accuracy inside a band of width r around
+ * the ground-truth boundaries: Kraehenbuehl & Koltun 2011, Chen et al. 2015) and of the boundary F-score (Csurka et al., BMVC 2013) -- for a batch
+ * of N images of H x W pixels on DEVICE pointers.  All integers.
+ *   Per image: G = gt_label_ids (uint8 label ids 0..33), P = the predicted label ids (pred_kind 0: int64 train ids 0..19 through the same
+ *   trainId -> id table as fcn8s_op_cityscapes_pair; pred_kind 1: uint8 label ids 0..33).  R = the largest radius, 1 <= R <= 16.  Pixels outside
+ *   the image do not exist (the image edge is not a boundary).  Distances are squared Euclidean pixel distances dy^2 + dx^2.  The ring of a
+ *   squared distance d2 is the smallest integer k >= 0 with k^2 >= d2; if that is larger than R, or nothing was found within R, the ring is R + 1.
+ *   1. Trimap rings.  For pixel p, d2(p) = min over q != p with G[q] != G[p] of |q - p|^2; rings[ring(d2(p)) - 1][G[p]][P[p]] += 1.
+ *      rings is [R + 1][34][34] int64; index R (ring R + 1) holds the pixels farther than R from every other label.  The band of width r <= R is the
+ *      sum of the first r matrices; the sum of all R + 1 is the confusion matrix fcn8s_op_cityscapes_pair counts on the same pixels.  Raw label
+ *      ids are compared (a boundary towards an ignored label is a boundary).
+ *   2. Boundary sets.  For a map M, B(M) = the pixels that have a 4-neighbour inside the image with another value of M.
+ *   3. Boundary precision / recall counts.  For every p in B(P) with c = P[p]: e2(p) = min over q in B(G) with G[q] == c (q = p allowed, distance
+ *      0) of |q - p|^2; bprec[ring(e2(p))][c] += 1.  Symmetrically for every p in B(G) with c = G[p] against q in B(P) with P[q] == c:
+ *      brec[ring][c] += 1.  Both [R + 2][34] int64; ring 0 = coincident, ring R + 1 = unmatched within R.
+ *   4. An id out of range (gt > 33, train id outside 0..19, label id > 33) takes part in every comparison of its map as the id 255 (so it is a
+ *      boundary towards every valid neighbour and matches no class); a pixel whose own G or P id is out of range is counted in bad[0] and in none
+ *      of the three tables.  The Python layer refuses an image with bad != 0.
+ *   rings, bprec, brec and bad are accumulated into, over the N images and over calls (the caller clears them).  Integers only: two runs give the
+ *   same bits.  Any H, W and alignment.  Stream-ordered; does not synchronise; allocates nothing.  FCN8S_ERR_BAD_ARG (nothing launched) for a NULL
+ *   pointer, pred_kind outside {0, 1}, N, H or W <= 0, R outside 1..16; FCN8S_ERR_SHAPE for H * W >= 2^31.
+ *   Host side (cityscapes_eval.py): trimap IoU of width r = the evaluator's IoU on the summed first r matrices; boundary precision of class c at
+ *   tolerance t = sum(bprec[0..t][c]) / sum(bprec[:][c]), recall likewise from brec, F = 2 P R / (P + R). */
+int fcn8s_op_boundary_pair(void* stream, const uint8_t* gt_label_ids, const void* pred, int pred_kind, int N, int H, int W, int R,
+                           int64_t* rings, int64_t* bprec, int64_t* brec, int64_t* bad);
 int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* m, float* v, int64_t n, int t,
                      float lr, float beta1, float beta2, float eps, float grad_scale);
 int fcn8s_op_sgd_momentum(void* stream, float* theta, const float* g, float* buf, int64_t n,
