@@ -441,8 +441,9 @@ static bool fft6_on(const fcn8s_model* m, int N, int H, int W, int ci, int co)
     if (!m || !fft6_shape_ok(m, ci, co) || !fft6_cheaper(m, H, W) || m->precision != FCN8S_PREC_F32 || m->frozen || !m->d_wino_v || !m->d_wino_m) return false;
     const long long T = fft_fc6_tiles(N, H, W);
     auto v = m->acts.find("wino_v"), mm = m->acts.find("wino_m");
-    return v != m->acts.end() && mm != m->acts.end() && v->second.n >= (size_t)fft_fc6_planes() * (size_t)wino_slab(T, std::min(ci, co)) &&
-           mm->second.n >= std::max((size_t)fft_fc6_planes() * (size_t)wino_slab(T, std::max(ci, co)), (size_t)T * 196 * std::min(ci, co));
+    // (V holds Xf / dXf, ci channels; M holds Yf / dYf, co channels, then the patch gradients, ci channels -- whichever of ci, co is the larger)
+    return v != m->acts.end() && mm != m->acts.end() && v->second.n >= (size_t)fft_fc6_planes() * (size_t)wino_slab(T, ci) &&
+           mm->second.n >= std::max((size_t)fft_fc6_planes() * (size_t)wino_slab(T, co), (size_t)T * 196 * ci);
 }
 // The weight gradient in the DFT domain (dUf[p] = Xf[p]^T dYf[p], dW = filter^T(dUf)) multiplies 4.56 times per tile position and channel pair
 // against F(4x4,4x4)'s 12.25, but writes and reads a 292-plane bank of Cin x Cout (2.45 GB at 512 -> 4096) where F(4x4,4x4) has 196 planes:
@@ -451,6 +452,38 @@ static bool fft6_on(const fcn8s_model* m, int N, int H, int W, int ci, int co)
 // T = 16 +0.04 ms, T = 32 -0.08 ms, T = 64 -0.65 ms, T = 128 (the bench shape) -0.8 ms.
 constexpr long long kFft6WgradMinTiles = 32;
 static bool fft6_wgrad_wanted(const fcn8s_model* m, long long T) { return m->fc6_fft_wgrad == 2 || (m->fc6_fft_wgrad == 1 && T >= kFft6WgradMinTiles); }
+// fc6's share of the scratch for N maps of h5 x w5 (ci -> co channels), in floats; plan_workspace and fcn8s_op_conv7x7_fc6_fwd_bwd size by it.
+//   v_wino        : V / M of F(4x4,4x4) (the data gradient swaps the two roles; M has nsub = 1)
+//   v_fft, m_fft  : the DFT tiles: Xf / dXf in V, Yf / dYf and the patch gradients in M
+//   wv            : the layer's own slot: V of F(4x4,4x4) or, when the weight gradient runs in the DFT domain, Xf -- sized for either
+struct Fc6Scratch { size_t v_wino = 0, v_fft = 0, m_fft = 0, wv = 0; };
+static Fc6Scratch fc6_scratch_floats(const fcn8s_model* m, int N, int h5, int w5, int ci, int co)
+{
+    Fc6Scratch r;
+    const int hi = std::max(ci, co);
+    if (m->wino_fc6 && m->fc6k == 7 && wino_tile_for(m, h5, w5, 7) == 4 && ci % 16 == 0 && co % 64 == 0) {
+        const size_t P = (size_t)wino_alpha(4, 7) * wino_alpha(4, 7);
+        const int ns2 = wino_nsub(7) * wino_nsub(7);
+        const long long T = wino_tiles(4, N, h5, w5);
+        r.v_wino = std::max(P * (size_t)wino_slab(T, ns2 * hi), P * (size_t)wino_slab(T, hi));
+        r.wv = P * (size_t)wino_slab(T, ns2 * ci);
+    }
+    if (fft6_shape_ok(m, ci, co) && fft6_cheaper(m, h5, w5)) {
+        const size_t P = (size_t)fft_fc6_planes();
+        const long long T = fft_fc6_tiles(N, h5, w5);
+        r.v_fft = P * (size_t)wino_slab(T, ci);
+        r.m_fft = std::max(P * (size_t)wino_slab(T, co), (size_t)T * 196 * ci);
+        if (fft6_wgrad_wanted(m, T)) r.wv = std::max(r.wv, P * (size_t)wino_slab(T, ci));
+    }
+    return r;
+}
+// ... and of the filter-bank scratch d_wino_u: 49 positions x 4 sub-filters, or the 292 planes of the DFT-domain weight gradient (dUf; +0.8 GB at 512 -> 4096)
+static size_t fc6_bank_floats(int ci, int co)
+{
+    size_t n = 49 * 4 * (size_t)ci * co;
+    if (ci % 16 == 0 && co % 128 == 0) n = std::max(n, (size_t)fft_fc6_planes() * ci * co);
+    return n;
+}
 // the plane GEMMs: [T x K] x [K x Nc] per plane, 128-row tiles and no split-K whatever the batch (a DP shard computes the big batch's bits)
 static IgemmArgs fft6_gemm(const float* x, const float* w, float* y, long long T, int K, int Nc)
 {
@@ -1022,19 +1055,11 @@ void plan_workspace(fcn8s_model* m, int N, int H, int W, WsPlan& pl)
                 }
         }
         const int h5_ = H / 32, w5_ = W / 32;
-        const bool fc6w = m->wino_fc6 && m->fc6k == 7 && wino_tile_for(m, h5_, w5_, 7) == 4 && m->widths[4] % 16 == 0 && m->widths[5] % 64 == 0;
-        if (fc6w) {     // V: P * T * nsub^2 * c5;  M: P * T * c6  (the data gradient swaps the two roles; M has nsub = 1)
-            const int al = wino_alpha(4, 7);
-            vmax = std::max(vmax, slab_floats(h5_, w5_, std::max(m->widths[4], m->widths[5]), 7));
-            vmax = std::max(vmax, (size_t)al * al * (size_t)wino_slab(wino_tiles(4, N, h5_, w5_), std::max(m->widths[4], m->widths[5])));
-        }
+        const Fc6Scratch f6 = fc6_scratch_floats(m, N, h5_, w5_, m->widths[4], m->widths[5]);
+        vmax = std::max(vmax, f6.v_wino);      // V: P * T * nsub^2 * c5;  M: P * T * c6
         size_t mmax = vmax;
-        if (fft6_shape_ok(m, m->widths[4], m->widths[5]) && fft6_cheaper(m, h5_, w5_)) {    // fc6 through DFT tiles: Xf / dXf in V, Yf / dYf and the patch gradients in M
-            const long long Tf = fft_fc6_tiles(N, h5_, w5_);
-            const int lo = std::min(m->widths[4], m->widths[5]), hi = std::max(m->widths[4], m->widths[5]);
-            vmax = std::max(vmax, (size_t)fft_fc6_planes() * (size_t)wino_slab(Tf, lo));
-            mmax = std::max(mmax, std::max((size_t)fft_fc6_planes() * (size_t)wino_slab(Tf, hi), (size_t)Tf * 196 * lo));
-        }
+        vmax = std::max(vmax, f6.v_fft);       // fc6 through DFT tiles
+        mmax = std::max(mmax, f6.m_fft);
         if (vmax) { items.push_back({"wino_v", vmax, 0, 0, 0, &m->d_wino_v}); items.push_back({"wino_m", mmax, 0, 0, 0, &m->d_wino_m}); }
         if (m->wino_min_cin > 0) {    // the forward pass keeps each Winograd layer's transformed input for the weight gradient
             int cin = 3;
@@ -1047,10 +1072,7 @@ void plan_workspace(fcn8s_model* m, int N, int H, int W, WsPlan& pl)
                     cin = m->widths[b];
                 }
             // fc6's slot holds V of F(4x4,4x4) or, when the weight gradient runs in the DFT domain, Xf: sized for either
-            size_t v6 = fc6w ? slab_floats(h5_, w5_, m->widths[4], 7) : 0;
-            if (fft6_shape_ok(m, m->widths[4], m->widths[5]) && fft6_cheaper(m, h5_, w5_) && fft6_wgrad_wanted(m, fft_fc6_tiles(N, h5_, w5_)))
-                v6 = std::max(v6, (size_t)fft_fc6_planes() * (size_t)wino_slab(fft_fc6_tiles(N, h5_, w5_), m->widths[4]));
-            if (v6) items.push_back({"wv:fc6", v6, 0, 0, 0, nullptr});
+            if (f6.wv) items.push_back({"wv:fc6", f6.wv, 0, 0, 0, nullptr});
         }
     }
 
@@ -2179,9 +2201,7 @@ int fcn8s_create(const fcn8s_config* cfg, fcn8s_model** out)
     {
         int cmax = 0; for (int i = 0; i < 5; ++i) cmax = std::max(cmax, m->widths[i]);
         size_t ufl = 64 * (size_t)cmax * cmax;                        // F(6x6,3x3): 64 positions
-        if (m->fc6k == 7) ufl = std::max(ufl, 49 * 4 * (size_t)m->widths[4] * m->widths[5]);   // fc6: 49 positions x 4 sub-filters
-        // ... or the 292 planes of its DFT-domain weight gradient (dUf; +0.8 GB at 512 -> 4096)
-        if (m->fc6k == 7 && m->widths[4] % 16 == 0 && m->widths[5] % 128 == 0) ufl = std::max(ufl, (size_t)fft_fc6_planes() * m->widths[4] * m->widths[5]);
+        if (m->fc6k == 7) ufl = std::max(ufl, fc6_bank_floats(m->widths[4], m->widths[5]));
         if ((e = hipMalloc((void**)&m->d_wino_u, ufl * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
         m->ufl = ufl;
     }
@@ -3739,6 +3759,76 @@ int fcn8s_op_conv3x3_winograd_fwd_bwd(void* stream, const float* x, const float*
       conv_same(m, "op", dy, wt, dx, N, H, W, Cout, Cin, 3, e, s, 0, "op"); }
     cleanup();
     m->acts.clear();
+    OPCHK(); return FCN8S_OK;
+}
+
+// One 7x7 SAME convolution the way fc6 runs in an fp32 training step: conv_same in training mode, conv_wgrad, conv_same as the data gradient, on a bare
+// model with one layer called "op" -- which of the DFT tiles, F(4x4,4x4) and the direct kernels run is decided by the model's own rules (fft6_on,
+// fft6_wgrad_wanted, bt_gemm_ok, wino_tile_for), never by this function.  For tests only: it allocates and synchronises per call, so it says nothing about time.
+int fcn8s_op_conv7x7_fc6_fwd_bwd(void* stream, const float* x, const float* w, const float* bias, const float* dy,
+                                 float* y, float* dx, float* dw, float* db,
+                                 int N, int H, int W, int Cin, int Cout, int path, float keep_prob, uint64_t seed, int* dft_products)
+{
+    if (dft_products) *dft_products = 0;
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 16 || Cout % 128 || path < 0 || path > 2 || !(keep_prob > 0.f && keep_prob <= 1.f) ||
+        !x || !w || !dy || !y || !dx || !dw)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "conv7x7_fc6_fwd_bwd: needs Cin % 16 == 0, Cout % 128 == 0, path in {0,1,2}, keep_prob in (0, 1], non-null x, w, dy, y, dx, dw");
+    hipStream_t s = (hipStream_t)stream;
+    fcn8s_model mm; fcn8s_model* m = &mm;
+    m->stream = s; m->N = N; m->H = H; m->W = W; m->plan_N = N; m->seed = seed; m->keep_prob = keep_prob;
+    m->precision = t_op_split == 3 ? FCN8S_PREC_F32X3 : t_op_split == 2 ? FCN8S_PREC_F32X2 : FCN8S_PREC_F32;
+    m->fc6_fft = path != 0; m->fc6_fft_wgrad = path == 2 ? 2 : 0;
+    m->profile = true;                     // the launch counts of the three DFT plane GEMMs are what dft_products reports
+    // the scratch exactly as the model plans it for this shape (plan_workspace, fcn8s_create), each buffer an allocation of its own, all of it NaN:
+    // what a model's shared workspace holds behind a slab or a partial row tile is another layer's leftovers
+    const Fc6Scratch f6 = fc6_scratch_floats(m, N, H, W, Cin, Cout);
+    const size_t vmax = std::max(f6.v_wino, f6.v_fft), mmax = std::max(f6.v_wino, f6.m_fft);
+    std::vector<void*> owned;
+    auto dalloc = [&](size_t nfloats, bool poison) -> float* {
+        void* p = nullptr;
+        if (hipMalloc(&p, nfloats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        owned.push_back(p);
+        if (poison) hipMemsetAsync(p, 0xFF, nfloats * sizeof(float), s);
+        return (float*)p;
+    };
+    auto cleanup = [&]() {
+        hipStreamSynchronize(s);
+        for (void* p : owned) hipFree(p);
+        for (auto& kv : m->u_train) if (kv.second) hipFree(kv.second);
+        m->u_train.clear(); m->acts.clear();
+        for (auto& g : m->groups) for (auto& ev : g.ev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
+    };
+    bool ok = true;
+    auto slot = [&](const char* name, size_t n) -> float* {
+        float* p = dalloc(n, true);
+        if (!p) { ok = false; return nullptr; }
+        Act a; a.p = p; a.n = n; m->acts[name] = a;
+        return p;
+    };
+    if (vmax) { m->d_wino_v = slot("wino_v", vmax); m->d_wino_m = slot("wino_m", mmax); }
+    if (f6.wv) slot("wv:op", f6.wv);
+    m->ufl = fc6_bank_floats(Cin, Cout);
+    m->d_wino_u = dalloc(m->ufl, true);
+    float* wt = dalloc((size_t)49 * Cin * Cout, false);       // the flipped + transposed kernel of a forward-type data gradient (the model's d_wt)
+    if (!ok || !m->d_wino_u || !wt) { cleanup(); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
+    // forward, as forward() runs fc6 (step 0: dropout stream 0)
+    m->fwd_train = true; m->train_mode = true; m->drop_stream = 0;
+    { Epi e; e.bias = bias; e.relu = 1; e.dropout = keep_prob < 1.f; e.keep = keep_prob; e.stream_id = m->drop_stream;
+      conv_same(m, "fc6_fwd", x, w, y, N, H, W, Cin, Cout, 7, e, s, 0, "op"); }
+    // backward, as backward_fc6 runs it: the weight gradient first (it may leave dYf / dM for the data gradient), then the data gradient
+    hipMemsetAsync(dw, 0, (size_t)49 * Cin * Cout * sizeof(float), s);
+    if (db) hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), s);
+    conv_wgrad(m, "fc6_wgrad", x, dy, dw, db, N, H, W, Cin, Cout, 7, 1.f, s, 0, "op");
+    { Epi e; e.dgrad = 1; e.w_fwd = w; e.lazy_wt = 1;
+      conv_same(m, "fc6_dgrad", dy, wt, dx, N, H, W, Cout, Cin, 7, e, s, 0, "op"); }
+    if (dft_products)
+        for (const auto& g : m->groups) {
+            if (g.launches <= 0) continue;
+            if (g.name == "fc6_fft_gemm_fwd") *dft_products |= 1;
+            if (g.name == "fc6_fft_gemm_wgrad") *dft_products |= 2;
+            if (g.name == "fc6_fft_gemm_dgrad") *dft_products |= 4;
+        }
+    cleanup();
     OPCHK(); return FCN8S_OK;
 }
 

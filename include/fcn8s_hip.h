@@ -521,6 +521,23 @@ int fcn8s_op_conv2d_winograd(void* stream, const float* x, const float* w_hwio, 
 int fcn8s_op_conv3x3_winograd_fwd_bwd(void* stream, const float* x, const float* w_hwio, const float* bias, const float* dy, const float* dx_addend,
                                       float* y, float* pool, float* dx, float* dw, float* db,
                                       int N, int H, int W, int Cin, int Cout, int tile, int pooled, int mask_mode);
+/* One 7x7 SAME conv the way fc6 runs in an fp32 TRAINING step, forward and backward, through the model's own launch sequences and under the
+ * model's own rules for which kernels take a shape (Cin % 16 == 0, Cout % 128 == 0):
+ *   forward   y = dropout(relu(conv(x, w) + bias)); bias may be NULL; dropout only if keep_prob < 1, with `seed` and the Philox stream fc6 has in a
+ *             model's first step (element index NHWC, survivors scaled by 1 / keep_prob);
+ *   backward  dy = gradient w.r.t. the PRE-activation [N,H,W,Cout]; dw, db (may be NULL) and dx are assigned, not accumulated;
+ *   path      0 = option fc6_fft off: F(4x4,4x4) sub-filter Winograd where H and W are multiples of 4, else the direct kernels;
+ *             1 = forward and data gradient through the 14x14 real-DFT tiles, weight gradient outside the DFT domain (fc6_fft_wgrad = 0: what a
+ *                 model does below 32 tiles);  2 = fc6_fft_wgrad = 2: the weight gradient in the DFT domain too.
+ *             A path only permits: a map on which the DFT tiles multiply more than the alternative, a width the transposed-B GEMM does not take, or
+ *             a split-bf16 op context (option op_split_pieces; the DFT path is fp32 only) run what a model would run there.
+ *   dft_products (host, may be NULL) receives the products that did run in the DFT domain: bit 0 forward, bit 1 weight gradient, bit 2 data gradient.
+ * The scratch (wino_v, wino_m, the layer's wv slot, the filter-bank scratch) has exactly the sizes a model plans for this shape and is filled with
+ * NaNs before the forward pass, as a stand-in for the other layers' leftovers a model's shared workspace holds behind a slab or a partial row tile.
+ * keep_prob in (0, 1].  Not in the reference; for tests only -- it allocates and synchronises per call, so it says nothing about time. */
+int fcn8s_op_conv7x7_fc6_fwd_bwd(void* stream, const float* x, const float* w_hwio, const float* bias, const float* dy,
+                                 float* y, float* dx, float* dw, float* db,
+                                 int N, int H, int W, int Cin, int Cout, int path, float keep_prob, uint64_t seed, int* dft_products);
 /* the same SAME conv with bf16-rounded operands and fp32 accumulation on the bf16 MFMA (FCN8S_PREC_BF16_FC's kernel);
  * Cin % 32 == 0, Cout % 128 == 0, K odd */
 int fcn8s_op_conv2d_bf16(void* stream, const float* x, const float* w_hwio, const float* bias, float* y,
