@@ -6,6 +6,7 @@
 // predictions).
 #include "../../include/fcn8s_hip.h"
 #include "fcn8s_internal.h"
+#include "device_buffer.h"
 #include <cstdarg>
 
 #include <dlfcn.h>
@@ -83,8 +84,8 @@ int take_deferred_error(std::string* text)
 
 // FCN8S_PREC_FP8_INFER: a layer's padded e4m3 input copy (64-channel planes ps bytes apart; the border is zeroed whenever the geometry changes) with the
 // exponent its codes carry, and a layer's quantized weight bank (planes [K K Cin / 64][Cout][64], per-column exponents, the amax scratch behind them)
-struct Q8Buf { unsigned char* p = nullptr; size_t bytes = 0; int N = 0, H = 0, W = 0, C = 0, pad = -1, ex = 0; long long ps = 0; };
-struct W8Bank { unsigned char* wq = nullptr; int* ew = nullptr; unsigned* amax = nullptr; size_t bytes = 0; };
+struct Q8Buf { DeviceBuf<unsigned char> p; int N = 0, H = 0, W = 0, C = 0, pad = -1, ex = 0; long long ps = 0; };
+struct W8Bank { DeviceBuf<unsigned char> wq; int* ew = nullptr; unsigned* amax = nullptr; };      // (ew, amax: views into wq)
 
 struct fcn8s_model {
     int C = 20, fc6k = 7, device = 0;
@@ -109,10 +110,10 @@ struct fcn8s_model {
     std::thread comm_watch; std::atomic<bool> comm_watch_stop{false}, comm_failed{false};
     std::atomic<bool> comm_inflight[kCommSlots] = {}; int64_t comm_enq_ns[kCommSlots] = {0};
     std::string comm_error; int64_t comm_timeout_ms = 600000;
-    float *d_params = nullptr, *d_grads = nullptr, *d_m = nullptr, *d_v = nullptr, *d_wt = nullptr;
-    bool own_params = false, own_grads = false;
-    float *d_w1pad = nullptr, *d_tph[3] = {nullptr, nullptr, nullptr};
-    float *d_wino_u = nullptr, *d_wino_v = nullptr, *d_wino_m = nullptr;   // Winograd scratch: filters, transformed input / output
+    float *d_params = nullptr, *d_grads = nullptr;                        // views: the caller's ext_params / ext_grads, or ...
+    DeviceBuf<float> own_params, own_grads;                               // ... the model's own
+    DeviceBuf<float> d_m, d_v, d_wt, d_w1pad, d_tph[3];
+    DeviceBuf<float> d_wino_u; float *d_wino_v = nullptr, *d_wino_m = nullptr;   // Winograd scratch: filters (per model), transformed input / output (arena)
     size_t ufl = 0;                                                       // floats of d_wino_u
     int wino_min_cin = 64;                                              // 3x3 layers with Cin >= this use Winograd; 0 = never
     int wino_tile = 6;                                                    // largest 3x3 output tile: F(6x6,3x3) / F(4x4,3x3) per layer by cost, F(2x2,3x3) fallback
@@ -128,10 +129,10 @@ struct fcn8s_model {
     bool pool_fused[5] = {false, false, false, false, false};            // forward wrote pool_b + argmax bytes from conv_b_last's output transform
     // fcn8s_freeze_params: the caller promises constant parameters; Winograd-transformed filters are then kept per layer
     bool frozen = false;
-    unsigned long long frozen_fp = 0; unsigned long long* d_fp = nullptr;   // fingerprint of the parameter buffer the cached banks were built from
-    unsigned long long* h_fp = nullptr; hipEvent_t fp_event = nullptr;      // pinned landing place of the guard's fingerprint, and the event behind its copy
-    std::map<std::string, float*> u_cache;                               // layer -> transformed filter bank (hipMalloc'ed), valid while frozen
-    std::map<std::string, float*> u_train;                               // layer -> forward filter bank of the current training step: the adjoint data
+    unsigned long long frozen_fp = 0; DeviceBuf<unsigned long long> d_fp;   // fingerprint of the parameter buffer the cached banks were built from
+    PinnedBuf<unsigned long long> h_fp; hipEvent_t fp_event = nullptr;      // pinned landing place of the guard's fingerprint, and the event behind its copy
+    std::map<std::string, DeviceBuf<float>> u_cache;                     // layer -> transformed filter bank, valid while frozen
+    std::map<std::string, DeviceBuf<float>> u_train;                              // layer -> forward filter bank of the current training step: the adjoint data
                                                                          // gradient reads it as a transposed B operand (no second, transposed bank)
     bool fwd_train = false;                                              // forward() is running a training pass
     std::set<std::string> rbits_ok;                                       // layers whose forward pass wrote a ReLU bit mask ("rb:<layer>") this step
@@ -148,20 +149,20 @@ struct fcn8s_model {
     std::set<std::string> y_unwritten;                                    // layers whose activation tensor was not materialised by the last forward pass
     int conv1_tiled = 1, conv1_wgrad_mfma = 1;                            // options: conv1_1 forward on the spatial-tile kernel / its weight gradient on the matrix core
     int conv1_in_transform = 1;                                           // option: conv1_1 is evaluated inside conv1_2's input transform (its activation tensor is never written)
-    unsigned short* d_wbf16 = nullptr; size_t wbf16_elems = 0;            // bf16 copy of one layer's kernel at a time (K-tile-major or transposed)
-    std::map<std::string, unsigned short*> wbf16_cache;                   // ... per layer, valid while frozen
+    DeviceBuf<unsigned short> d_wbf16;                                    // bf16 copy of one layer's kernel at a time (K-tile-major or transposed)
+    std::map<std::string, DeviceBuf<unsigned short>> wbf16_cache;                 // ... per layer, valid while frozen
     // fcn8s_predict_tta on a model that is not frozen keeps the storage of the banks it built (u_cache / wbf16_cache) but not their contents: the keys
     // ("u:<key>" / "w:<key>") whose contents must be rebuilt before use, and whether the first frozen pass must rebuild the padded kernels + fingerprint
     std::set<std::string> bank_stale; bool banks_stale = false;
     int bf16_gemm256 = 1;                                                 // bf16_fc mode: 256 x 256 LDS-DMA kernel -- 0 never, 1 when it fills the chip, 2 whenever shapes allow
-    unsigned short* d_abf16 = nullptr; size_t abf16_elems = 0;            // bf16 copy of the layer's input activations
+    DeviceBuf<unsigned short> d_abf16;                                    // bf16 copy of the layer's input activations
     // bf16 modes, training: zero-bordered padded bf16 copies of the inputs of conv3_1 .. conv5_3, one per layer (the border is written once, at
     // allocation; the interior every step by that layer's Winograd input transform, wino_input_kernel<.., XB>); keyed by layer, dropped with the workspace
-    std::map<std::string, unsigned short*> xbf16;
+    std::map<std::string, DeviceBuf<unsigned short>> xbf16;
     // FCN8S_PREC_BF16_TRAIN: per layer, the zero-bordered bf16 copy of its INPUT with zeroed guard rows in front and behind (bf16_guard_rows), written by
     // the forward pass and read again by the layer's weight gradient
-    std::map<std::string, unsigned short*> xg16; std::map<std::string, size_t> xg16_elems;
-    std::map<std::string, unsigned short*> dyg16; std::map<std::string, size_t> dyg16_elems;     // ... per layer: the same kind of copy of its output gradient dY
+    using G16Map = std::map<std::string, DeviceBuf<unsigned short>>;
+    G16Map xg16, dyg16;                                                   // ... per layer: the same kind of copy of its output gradient dY
     std::set<std::string> db_taken;                                      // layers whose bias gradient the producer of their dY copy has already added (this backward pass)
     int bf16_fuse_pool = 1;                                               // option: bf16_train, the max-pool backward writes the last conv's bf16 dZ copy and bias gradient directly
     std::set<std::string> xg16_filled, dyg16_filled;                     // copies a producing kernel's epilogue has already written in this pass (no conversion pass)
@@ -170,7 +171,7 @@ struct fcn8s_model {
     int bf16_acts = 1;                                                    // option: bf16_train training passes keep a conv -> conv activation only as the consumer's padded bf16 copy (the producer's epilogue writes it; no fp32 tensor, no conversion pass)
     // FCN8S_PREC_FP8_INFER: the calibration (per FP8 layer the max |input| of the fp32 pass; it describes the parameters, not the mode), the device scratch of
     // fcn8s_fp8_calibrate, the e4m3 copies (kept with the workspace) and the weight banks (valid across passes only while frozen: w8_valid)
-    bool fp8_calibrated = false, fp8_calibrating = false; float fp8_amax[FCN8S_FP8_LAYERS] = {}; unsigned* d_fp8_amax = nullptr;
+    bool fp8_calibrated = false, fp8_calibrating = false; float fp8_amax[FCN8S_FP8_LAYERS] = {}; DeviceBuf<unsigned> d_fp8_amax;
     std::map<std::string, Q8Buf> q8; std::set<std::string> q8_filled;
     std::map<std::string, W8Bank> w8; std::set<std::string> w8_valid;
     int saved_wino_min_cin = -1, saved_wino_fc6 = -1;                      // the options the mode overrides (the direct path carries it), restored on leaving
@@ -178,41 +179,42 @@ struct fcn8s_model {
     std::set<std::string> g16_stale;                                      // bf16_train copies ("x:<layer>" / "d:<layer>") whose zero border belongs to another shape (fcn8s_predict_tta re-plans)
     int64_t ws_allocs = 0;                                                // statistic "workspace_allocations": device allocations for the workspace, the TTA scratch, the bf16 copies and the cached filter banks
     bool x0_ready = false;                                                // forward(): x0 is already written (fcn8s_predict_tta's tta_input), skip the preprocess kernel
-    char* crf_buf = nullptr; size_t crf_bytes = 0;                        // fcn8s_predict_crf: staged images, the mean softmax, the two mean-field buffers, staged output (grown, never shrunk)
-    char* tta_buf = nullptr; size_t tta_bytes = 0;                        // fcn8s_predict_tta: staged images, accumulator, staged output (grown, never shrunk)
+    DeviceBuf<char> crf_buf;                                              // fcn8s_predict_crf: staged images, the mean softmax, the two mean-field buffers, staged output (grown, never shrunk)
+    DeviceBuf<char> tta_buf;                                              // fcn8s_predict_tta: staged images, accumulator, staged output (grown, never shrunk)
     hipStream_t stream = nullptr;
     int64_t step = 0;
     // workspace for the current (N,H,W)
     int N = 0, H = 0, W = 0;
     int plan_N = 0;
-    char* arena = nullptr; size_t arena_bytes = 0;
+    DeviceBuf<char> arena;
     std::map<std::string, Act> acts;
     // option "keep_output_gradients" (tests): every weighted layer's fp32 output gradient dY, copied as the backward pass hands it to the layer's weight gradient;
     // read back through fcn8s_get_activation("dy:<layer>")
-    int keep_dy = 0; std::map<std::string, Act> kept_dy; std::set<std::string> dz_unwritten;      // dz_unwritten: layers whose fp32 dY the pool's backward kernel skipped
+    struct KeptDy { DeviceBuf<float> p; size_t n = 0; };                  // (n = 0: this pass handed the layer's dY over in another form)
+    int keep_dy = 0; std::map<std::string, KeptDy> kept_dy; std::set<std::string> dz_unwritten;      // dz_unwritten: layers whose fp32 dY the pool's backward kernel skipped
     // the last transposed conv (k = 2s = 16) as one GEMM over output blocks (PixMap, elementwise.hip): logits / dlogits live in that blocked layout
     int tconv_gemm = 1; PixMap pm{0, 0, 0, 0, 0, 0}; int tg_kp = 0;
     float *logits_b = nullptr, *dlogits_b = nullptr, *tg_A = nullptr, *tg_dA = nullptr;      // arena
-    float *tg_b2 = nullptr, *tg_b2t = nullptr, *tg_bias = nullptr, *tg_db2 = nullptr;         // per model
+    DeviceBuf<float> tg_b2, tg_b2t, tg_bias, tg_db2;                                          // per model
     bool logits_nhwc_valid = false;
     float *dlogits = nullptr, *da3 = nullptr, *da4 = nullptr, *ds7 = nullptr, *gskip3 = nullptr, *gskip4 = nullptr;
     float *gbuf[2] = {nullptr, nullptr};
     int gcur = 0;
     void* d_images = nullptr; uint8_t* d_labels = nullptr;
-    float *d_loss = nullptr, *d_regsum = nullptr, *d_softmax = nullptr;
-    float* h_loss = nullptr; hipEvent_t loss_ev = nullptr; bool loss_copied = false;   // pinned copy of d_loss, queued right after the loss kernels
+    DeviceBuf<float> d_loss; float *d_regsum = nullptr, *d_softmax = nullptr;       // (d_regsum, d_lastbias, d_terms: views into d_loss)
+    PinnedBuf<float> h_loss; hipEvent_t loss_ev = nullptr; bool loss_copied = false;   // pinned copy of d_loss, queued right after the loss kernels
     float* d_lastbias = nullptr;       // column sums of dlogits (gradient of the last transposed conv's bias), produced by the loss kernel
     double* d_partials = nullptr; long long* d_pred = nullptr;
     // fcn8s_set_loss: the training loss (0 = the reference's mean, 1 = class-weighted, 2 = OHEM); weights in d_cw (float[64], made once by
     // fcn8s_set_loss); loss_ws = LOSS_SCRATCH_BYTES of state and histograms + (OHEM) the l_p buffer, grown on first use (a "workspace_allocation")
     int loss_mode = 0, last_loss_mode = 0; float ohem_thresh = 0.f; int64_t ohem_min_kept = 0;
-    float* d_cw = nullptr; char* loss_ws = nullptr; size_t loss_ws_bytes = 0;
+    DeviceBuf<float> d_cw; DeviceBuf<char> loss_ws;
     // fcn8s_set_lovasz: L = lov_ce * (the cross-entropy above) + lov_w * L_lov + L2 (lov_on: not the default (1, 0)); the class mask in d_lovmask
     // (uint8[64], made by fcn8s_set_lovasz); lov_ws = the sort's scratch (LovaszLayout), grown on first use (a "workspace_allocation");
     // d_terms = the unscaled terms of the last training loss (ce, lovasz, l2; right behind d_lastbias), have_terms once a training loss ran
     bool lov_on = false, have_terms = false; float lov_ce = 1.f, lov_w = 0.f; int lov_per_image = 0, lov_all = 0;
-    uint8_t* d_lovmask = nullptr; int lov_nmask = 0; char* lov_ws = nullptr; size_t lov_ws_bytes = 0; float* d_terms = nullptr;
-    unsigned long long* d_conf = nullptr;
+    DeviceBuf<uint8_t> d_lovmask; int lov_nmask = 0; DeviceBuf<char> lov_ws; float* d_terms = nullptr;
+    DeviceBuf<unsigned long long> d_conf;
     double loss_sum = 0; int64_t loss_cnt = 0;
     float keep_prob = 1.f, l2_rate = 0.f;
     uint32_t drop_stream = 0;
@@ -221,12 +223,25 @@ struct fcn8s_model {
     const uint8_t* cur_labels = nullptr;
     bool profile = false, profile_detail = false;
     // pinned host staging + device slots filled on a copy stream (fcn8s_stage_inputs): the next batch's H2D overlaps this step's kernels
-    struct StageSlot { void* h_img = nullptr; uint8_t* h_lab = nullptr; void* d_img = nullptr; uint8_t* d_lab = nullptr;
-                       size_t cap_img = 0, cap_lab = 0; hipEvent_t ready = nullptr, consumed = nullptr; bool used = false; };
+    struct StageSlot { PinnedBuf<uint8_t> h_img, h_lab; DeviceBuf<uint8_t> d_img, d_lab;
+                       hipEvent_t ready = nullptr, consumed = nullptr; bool used = false; };
     StageSlot slots[FCN8S_NUM_STAGE_SLOTS];
     hipStream_t copy_stream = nullptr;
     std::vector<ProfGroup> groups;
     std::string err;
+    // Memory frees itself (the Buf members above).  Events and the copy stream are destroyed here; the caller has drained the device
+    // (fcn8s_destroy) or the stream (the bare models of the fcn8s_op_* entry points) first.
+    fcn8s_model() = default;
+    fcn8s_model(const fcn8s_model&) = delete;
+    ~fcn8s_model()
+    {
+        for (auto& g : groups) for (auto& ev : g.ev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
+        for (auto& e : bucket_ev) if (e) hipEventDestroy(e);
+        if (loss_ev) hipEventDestroy(loss_ev);
+        if (fp_event) hipEventDestroy(fp_event);
+        for (auto& sl : slots) { if (sl.ready) hipEventDestroy(sl.ready); if (sl.consumed) hipEventDestroy(sl.consumed); }
+        if (copy_stream) hipStreamDestroy(copy_stream);
+    }
 };
 
 namespace {
@@ -325,7 +340,7 @@ struct ProfScope {
     fcn8s_model* m; int gid = -1; hipEvent_t a = nullptr, b = nullptr; double fl = 0, by = 0;
     ProfScope(fcn8s_model* m_, const char* group, double flops, double bytes, const char* layer = nullptr) : m(m_), fl(flops), by(bytes)
     {
-        if (!m->profile) return;
+        if (!m || !m->profile) return;          // (no model: an op-level entry point, nothing to profile)
         fcn8s::g_last_kernel = nullptr;
         gid = (m->profile_detail && layer) ? group_id(m, (std::string(group) + ":" + layer).c_str()) : group_id(m, group);
         hipEventCreate(&a); hipEventCreate(&b);
@@ -396,7 +411,7 @@ static inline long long bf16_guard_rows(int K, int Wp) { return (long long)((K -
 #endif
 static inline long long g16_ps(int N, int H, int W, int K) { const int pad = (K - 1) / 2, Wp_ = W + 2 * pad; return A_PLANES ? ((long long)N * (H + 2 * pad) * Wp_ + 2 * bf16_guard_rows(K, Wp_)) * 32 : 0; }
 static inline long long g16_off(long long G, int C) { return A_PLANES ? G * 32 : G * C; }      // elements from the start of a copy's buffer to its padded pixel 0
-unsigned short* g16_for(fcn8s_model* m, std::map<std::string, unsigned short*>& bufs, std::map<std::string, size_t>& sizes, const char* layer, int N, int H, int W, int C, int K, hipStream_t s);
+unsigned short* g16_for(fcn8s_model* m, fcn8s_model::G16Map& bufs, const char* layer, int N, int H, int W, int C, int K, hipStream_t s);
 unsigned short* dyb_for(fcn8s_model* m, const char* layer, const float* dy, int N, int H, int W, int C, int K, hipStream_t s, float* db = nullptr, bool* db_done = nullptr);
 
 int wino_tile_for(const fcn8s_model* m, int H, int W, int K = 3)
@@ -484,10 +499,12 @@ static size_t fc6_bank_floats(int ci, int co)
     if (ci % 16 == 0 && co % 128 == 0) n = std::max(n, (size_t)fft_fc6_planes() * ci * co);
     return n;
 }
-// the plane GEMMs: [T x K] x [K x Nc] per plane, 128-row tiles and no split-K whatever the batch (a DP shard computes the big batch's bits)
+// One batched GEMM per transform position (a DFT plane, a Winograd position): [T x K] x [K x Nc] per position, the slabs wino_slab() apart.
+// split, fixed_tile and a transposed B operand (bt, ldw) are the caller's.  fc6's DFT planes take fixed_tile = 1: 128-row tiles and no
+// split-K whatever the batch (a DP shard computes the big batch's bits)
 static IgemmArgs fft6_gemm(const float* x, const float* w, float* y, long long T, int K, int Nc)
 {
-    IgemmArgs a{}; a.split = 0; a.fixed_tile = 1;
+    IgemmArgs a{};
     a.x = x; a.w = w; a.y = y;
     a.N = 1; a.Ma = (int)T; a.Mb = 1; a.M = T;
     a.Hi = (int)T; a.Wi = 1; a.Cin = K; a.ldx = K;
@@ -504,8 +521,8 @@ static bool conv_fft6_fwd(fcn8s_model* m, const char* layer, const float* x, con
 {
     const int P = fft_fc6_planes();
     const long long T = fft_fc6_tiles(N, H, W);
-    float*& uf = m->u_train[std::string(layer) + "#fft"];
-    if (!uf && hipMalloc((void**)&uf, (size_t)P * Cin * Cout * sizeof(float)) != hipSuccess) { uf = nullptr; (void)hipGetLastError(); return false; }
+    DeviceBuf<float>& uf = m->u_train[std::string(layer) + "#fft"];
+    if (!uf.grow((size_t)P * Cin * Cout * sizeof(float), s)) return false;
     auto wv = m->acts.find(std::string("wv:") + layer);      // the weight gradient's input operand: Xf (DFT domain) or V of F(4x4,4x4)
     // the DFT-domain weight gradient reads this pass's Xf: kept in the layer's own slot, which nothing else writes before the backward pass
     const bool dft_wgrad = wv != m->acts.end() && fft6_wgrad_wanted(m, T) && wv->second.n >= (size_t)P * (size_t)wino_slab(T, Cin) &&
@@ -516,7 +533,7 @@ static bool conv_fft6_fwd(fcn8s_model* m, const char* layer, const float* x, con
       launch_fft_fc6_filter(w, uf, Cin, Cout, s); launch_fft_fc6_input(x, xf, N, H, W, Cin, s); }
     if (want_v) { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cin * 4 + 49.0 * wino_tiles(4, N, H, W) * 4 * Cin));
                   launch_wino_input(4, x, wv->second.p, N, H, W, Cin, 7, s); }
-    const IgemmArgs a = fft6_gemm(xf, uf, m->d_wino_m, T, Cin, Cout);
+    IgemmArgs a = fft6_gemm(xf, uf, m->d_wino_m, T, Cin, Cout); a.fixed_tile = 1;
     { ProfScope ps(m, "fc6_fft_gemm_fwd", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
     { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)P * T * Cout + (double)N * H * W * Cout));
       launch_fft_fc6_output(m->d_wino_m, bias, y, N, H, W, Cout, relu, dropout, keep, m->seed, stream_id, s); }
@@ -552,7 +569,7 @@ static void conv_fft6_dgrad(fcn8s_model* m, const char* layer, const float* dz, 
     if (m->fft6_dyf != layer) { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)N * H * W * Cin + (double)P * T * Cin)); launch_fft_fc6_dout(dz, m->d_wino_m, N, H, W, Cin, s); }
     m->fft6_dyf.clear();        // (else the weight gradient just wrote dYf of this dz into d_wino_m)
     IgemmArgs a = fft6_gemm(m->d_wino_m, uf, m->d_wino_v, T, Cin, Cout);
-    a.bt = 1; a.ldw = Cin;
+    a.fixed_tile = 1; a.bt = 1; a.ldw = Cin;
     { ProfScope ps(m, "fc6_fft_gemm_dgrad", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
     { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)P * T * Cout + 2.0 * 196.0 * T * Cout + (double)N * H * W * Cout));
       launch_fft_fc6_din(m->d_wino_v, m->d_wino_m, dx, N, H, W, Cout, s); }
@@ -565,32 +582,22 @@ void conv_winograd(fcn8s_model* m, int tile, int KS, const char* tag, const floa
     const int P = wino_alpha(tile, KS) * wino_alpha(tile, KS), nsub2 = wino_nsub(KS) * wino_nsub(KS);
     const long long T = wino_tiles(tile, N, H, W);
     const int Kg = nsub2 * Cin;
-    IgemmArgs a{}; a.split = split_of(m);
-    a.x = v; a.w = u; a.y = mm;
-    a.N = 1; a.Ma = (int)T; a.Mb = 1; a.M = T;
-    a.Hi = (int)T; a.Wi = 1; a.Cin = Kg; a.ldx = Kg;
-    a.KW = 1; a.in_scale = 1; a.tap_step = 1; a.tap_off = 0; a.Ktot = Kg;
-    a.Ho = (int)T; a.Wo = 1; a.Cout = Cout; a.ldy = Cout;
-    a.out_scale = 1; a.phases_x = 1; a.w_phase_stride = (long long)Kg * Cout;
-    a.alpha = 1.f; a.mask_scale = 1.f;
-    a.batched = 1; a.x_batch_stride = wino_slab(T, Kg); a.y_batch_stride = wino_slab(T, Cout);
+    IgemmArgs a = fft6_gemm(v, u, mm, T, Kg, Cout); a.split = split_of(m);
     const double tb = 4.0 * ((double)N * H * W * Cin * nsub2 + (double)P * T * Kg), ob = 4.0 * ((double)N * H * W * Cout * ((e.pool ? (e.skip_y ? 0.25 : 1.25) : 1.0) + (e.rbits_in ? 1.0 / 32 : (e.mask ? 1.0 : 0.0)) + (e.addend ? 1.0 : 0.0) + (e.rbits_out ? 1.0 / 32 : 0.0)) + (double)P * T * Cout);   // y (+ pool) written, ReLU mask / skip addend read
     // frozen parameters (evaluate / predict loops): the transformed filter bank of each forward layer is computed once and kept
     bool u_cached = false;
     const bool fwd_call = std::string(tag).find("dgrad") == std::string::npos;      // (v_ready in a forward call = V written by the previous conv's fused output transform)
     if (m && m->frozen && layer && fwd_call) {
-        float*& cu = m->u_cache[std::string(layer) + "#" + std::to_string(tile)];       // (the tile, hence the bank's shape, depends on the image size)
+        DeviceBuf<float>& cu = m->u_cache[std::string(layer) + "#" + std::to_string(tile)];       // (the tile, hence the bank's shape, depends on the image size)
         const std::string key = "u:" + std::string(layer) + "#" + std::to_string(tile);
         if (cu && !m->bank_stale.count(key)) { u = cu; u_cached = true; }
         else if (cu) { u = cu; m->bank_stale.erase(key); }                                  // kept storage: refilled below
-        else if (hipMalloc((void**)&cu, (size_t)P * Kg * Cout * sizeof(float)) == hipSuccess) { u = cu; ++m->ws_allocs; }     // filled below, reused from the next call on
-        else { cu = nullptr; (void)hipGetLastError(); }
+        else if (cu.grow((size_t)P * Kg * Cout * sizeof(float), s, &m->ws_allocs)) u = cu;  // filled below, reused from the next call on (out of memory: the shared scratch)
         a.w = u;
     }
     if (m && !u_cached && m->fwd_train && layer && fwd_call && ((KS == 3 && tile == 6) || (KS == 7 && tile == 4))) {
-        float*& tu = m->u_train[std::string(layer) + "#" + std::to_string(tile)];
-        if (!tu && hipMalloc((void**)&tu, (size_t)P * Kg * Cout * sizeof(float)) != hipSuccess) { tu = nullptr; (void)hipGetLastError(); }
-        if (tu) { u = tu; a.w = u; }
+        DeviceBuf<float>& tu = m->u_train[std::string(layer) + "#" + std::to_string(tile)];
+        if (tu.grow((size_t)P * Kg * Cout * sizeof(float), s)) { u = tu; a.w = u; }
     }
     // v_ready: V was written together with the weight gradient's dM by the fused transform (launch_wino_input_dout)
     auto pre = [&]() { if (!u_cached) launch_wino_filter(tile, wk, u, Cin, Cout, KS, s); if (!v_ready) launch_wino_input(tile, x, v, N, H, W, Cin, KS, s, e.in_rbits_out); };
@@ -600,11 +607,9 @@ void conv_winograd(fcn8s_model* m, int tile, int KS, const char* tag, const floa
         launch_wino_output(tile, mm, e.bias, e.addend, e.mask, e.mask_scale, e.relu, (e.skip_y && e.pool) ? nullptr : y, N, H, W, Cout, e.dropout, e.keep, e.seed, e.stream_id, s, e.pool, e.pidx, KS, e.rbits_out, e.rbits_in); };
     // (bytes of the fused form: M read, the next conv's V written, the ReLU record)
     const double ob_fused = 4.0 * (2.0 * P * T * Cout + (e.rbits_out ? (double)N * H * W * Cout / 32 : 0.0));
-    if (m) {
-        { ProfScope ps(m, "wino_transform", 0, (v_ready ? 0.0 : tb) + (u_cached ? 0.0 : (double)(KS * KS + P * nsub2) * 4 * Cin * Cout)); pre(); }
-        { ProfScope ps(m, tag, 2.0 * P * T * Kg * Cout, 4.0 * P * (T * (double)(Kg + Cout) + (double)Kg * Cout), layer); launch_igemm(a, P, s); }
-        { ProfScope ps(m, "wino_transform", 0, ob); post(); if (e.fused_out && *e.fused_out && m->profile && !m->groups.empty()) { const int g = group_id(m, "wino_transform"); m->groups[g].bytes += ob_fused - ob; } }
-    } else { pre(); launch_igemm(a, P, s); post(); }
+    { ProfScope ps(m, "wino_transform", 0, (v_ready ? 0.0 : tb) + (u_cached ? 0.0 : (double)(KS * KS + P * nsub2) * 4 * Cin * Cout)); pre(); }
+    { ProfScope ps(m, tag, 2.0 * P * T * Kg * Cout, 4.0 * P * (T * (double)(Kg + Cout) + (double)Kg * Cout), layer); launch_igemm(a, P, s); }
+    { ProfScope ps(m, "wino_transform", 0, ob); post(); if (e.fused_out && *e.fused_out && m && m->profile && !m->groups.empty()) { const int g = group_id(m, "wino_transform"); m->groups[g].bytes += ob_fused - ob; } }
 }
 
 // SAME conv (or its data gradient when `w` holds flipped+transposed weights).  Returns true if e.pool_out was written.
@@ -617,11 +622,7 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
         // copy of dY with the flipped kernel, wt[ci][(flipped tap, co)] bf16, on conv_bf16_256_kernel; fp32 accumulate, fp32 epilogue (skip-path addend,
         // the ReLU / dropout mask of the layer's input).  w_fwd is the forward kernel [K][K][Cout here][Cin here].
         const size_t wneed = (size_t)K * K * Cin * Cout;
-        bool ok = true;
-        if (m->wbf16_elems < wneed) {
-            if (m->d_wbf16) { hipStreamSynchronize(s); hipFree(m->d_wbf16); m->d_wbf16 = nullptr; m->wbf16_elems = 0; }
-            if (hipMalloc((void**)&m->d_wbf16, wneed * sizeof(unsigned short)) != hipSuccess) { (void)hipGetLastError(); ok = false; } else { m->wbf16_elems = wneed; ++m->ws_allocs; }
-        }
+        const bool ok = m->d_wbf16.grow(wneed * sizeof(unsigned short), s, &m->ws_allocs);
         unsigned short* dyb = ok ? dyb_for(m, layer, x, N, H, W, Cin, K, s) : nullptr;
         if (dyb) {
             { ProfScope ps(m, "weight_relayout", 0, 6.0 * wneed); launch_w_to_bf16_flip_t(e.w_fwd, m->d_wbf16, K, Cout, Cin, s); }
@@ -635,7 +636,7 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
             // this gradient is the output gradient of layer e.yb_layer (same map).  If that layer's gradients read nothing else (option bf16_acts), this kernel's
             // epilogue writes its padded bf16 copy instead of the fp32 gradient, and takes its column sums, that layer's bias gradient, from the fp32 values
             const bool only16 = e.yb_layer && e.yb_only && m->bf16_acts && K == 3 && e.yb_K == 3 && Cout % 64 == 0;
-            if (only16) { g.yb = g16_for(m, m->dyg16, m->dyg16_elems, e.yb_layer, N, H, W, Cout, e.yb_K, s); g.yb_pad = (e.yb_K - 1) / 2; g.yb_ps = g16_ps(N, H, W, e.yb_K); }
+            if (only16) { g.yb = g16_for(m, m->dyg16, e.yb_layer, N, H, W, Cout, e.yb_K, s); g.yb_pad = (e.yb_K - 1) / 2; g.yb_ps = g16_ps(N, H, W, e.yb_K); }
             long long prow = 0;
             if (g.yb) {
                 prow = ((long long)N * (H + 2) * (W + 2) + conv_bf16_rows_bm(Cout, g.rows_bn) - 1) / conv_bf16_rows_bm(Cout, g.rows_bn);
@@ -686,15 +687,7 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
         m->dm_layer.clear(); m->fused_v_layer.clear();
         const int P = 64;
         const long long T = wino_tiles(6, N, H, W);
-        IgemmArgs a{}; a.split = split_of(m);
-        a.x = m->d_wino_m; a.w = m->d_wino_u; a.y = m->d_wino_v;
-        a.N = 1; a.Ma = (int)T; a.Mb = 1; a.M = T;
-        a.Hi = (int)T; a.Wi = 1; a.Cin = Cin; a.ldx = Cin;
-        a.KW = 1; a.in_scale = 1; a.tap_step = 1; a.tap_off = 0; a.Ktot = Cin;
-        a.Ho = (int)T; a.Wo = 1; a.Cout = Cout; a.ldy = Cout;
-        a.out_scale = 1; a.phases_x = 1; a.w_phase_stride = (long long)Cin * Cout;
-        a.alpha = 1.f; a.mask_scale = 1.f;
-        a.batched = 1; a.x_batch_stride = wino_slab(T, Cin); a.y_batch_stride = wino_slab(T, Cout);
+        IgemmArgs a = fft6_gemm(m->d_wino_m, m->d_wino_u, m->d_wino_v, T, Cin, Cout); a.split = split_of(m);
         auto kept = m->u_train.find(std::string(layer) + "#6");
         if (kept != m->u_train.end() && kept->second && bt_gemm_ok(Cin, Cout)) {
             a.w = kept->second; a.bt = 1; a.ldw = Cin;          // the forward bank U[xi][ci_fwd = Cout here][co_fwd = Cin here], read transposed
@@ -723,15 +716,7 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
             m->dm_layer.clear(); m->fused_v_layer.clear();
             const int P = 49, Ng = 4 * Cout;
             const long long T = wino_tiles(4, N, H, W);
-            IgemmArgs a{}; a.split = split_of(m);
-            a.x = m->d_wino_m; a.w = kept->second; a.y = m->d_wino_v;
-            a.N = 1; a.Ma = (int)T; a.Mb = 1; a.M = T;
-            a.Hi = (int)T; a.Wi = 1; a.Cin = Cin; a.ldx = Cin;
-            a.KW = 1; a.in_scale = 1; a.tap_step = 1; a.tap_off = 0; a.Ktot = Cin;
-            a.Ho = (int)T; a.Wo = 1; a.Cout = Ng; a.ldy = Ng;
-            a.out_scale = 1; a.phases_x = 1; a.w_phase_stride = (long long)Ng * Cin;
-            a.alpha = 1.f; a.mask_scale = 1.f;
-            a.batched = 1; a.x_batch_stride = wino_slab(T, Cin); a.y_batch_stride = wino_slab(T, Ng);
+            IgemmArgs a = fft6_gemm(m->d_wino_m, kept->second, m->d_wino_v, T, Cin, Ng); a.split = split_of(m);
             a.bt = 1; a.ldw = Cin;
             { ProfScope ps(m, "wino_gemm_fc6_dgrad", 2.0 * P * T * Cin * Ng, 4.0 * P * (T * (double)(Cin + Ng) + (double)Cin * Ng), layer); launch_igemm(a, P, s); }
             { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cout + (double)P * T * Ng)); launch_wino_dgrad_output_sub44(m->d_wino_v, y, N, H, W, Cout, s); }
@@ -740,8 +725,7 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
     }
     if (m) m->dm_layer.clear();
     if (e.lazy_wt && e.w_fwd) {
-        if (m) { ProfScope ps(m, "weight_relayout", 0, 8.0 * K * K * Cin * Cout); launch_flip_transpose(e.w_fwd, const_cast<float*>(w), K * K, Cout, Cin, s); }
-        else launch_flip_transpose(e.w_fwd, const_cast<float*>(w), K * K, Cout, Cin, s);
+        ProfScope ps(m, "weight_relayout", 0, 8.0 * K * K * Cin * Cout); launch_flip_transpose(e.w_fwd, const_cast<float*>(w), K * K, Cout, Cin, s);
     }
     if ((wino3 || wino7) && Cin % 16 == 0 && Cout % 64 == 0 && e.alpha == 1.f && !real_cin) {
         const bool dgrad = e.dgrad != 0;
@@ -783,8 +767,7 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
         }
         launch_igemm(a, 1, s);
     };
-    if (m) { ProfScope ps(m, group, flops, bytes, layer); run(); }
-    else run();
+    { ProfScope ps(m, group, flops, bytes, layer); run(); }
     return false;
 }
 
@@ -802,8 +785,7 @@ void tconv_fwd(fcn8s_model* m, const float* x, const float* wp, const float* bia
     a.phases_x = S; a.w_phase_stride = 4LL * C * C;
     a.alpha = 1.f; a.relu = 0; a.mask_scale = 1.f; a.dropout = 0;
     const double opix = (double)N * Hi * S * Wi * S;
-    if (m) { ProfScope ps(m, "tconv_fwd", 2.0 * opix * 4 * C * C, 4.0 * (opix * C * (addend ? 2 : 1) + (double)N * Hi * Wi * C)); launch_igemm(a, S * S, s); }
-    else launch_igemm(a, S * S, s);
+    ProfScope ps(m, "tconv_fwd", 2.0 * opix * 4 * C * C, 4.0 * (opix * C * (addend ? 2 : 1) + (double)N * Hi * Wi * C)); launch_igemm(a, S * S, s);
 }
 
 // data gradient of the transposed conv = stride-S conv of dy with the natural [kh,kw,Cout,Cin] kernel
@@ -818,8 +800,7 @@ void tconv_dgrad(fcn8s_model* m, const float* dy, const float* w, float* dx, int
     a.Ho = Hi; a.Wo = Wi; a.Cout = C; a.ldy = C;
     a.out_scale = 1; a.phases_x = 1; a.alpha = 1.f; a.mask_scale = 1.f;
     const double flops = 2.0 * a.M * K * K * C * C;
-    if (m) { ProfScope ps(m, "tconv_dgrad", flops, 4.0 * ((double)N * Hi * S * Wi * S * C + (double)a.M * C)); launch_igemm(a, 1, s); }
-    else launch_igemm(a, 1, s);
+    ProfScope ps(m, "tconv_dgrad", flops, 4.0 * ((double)N * Hi * S * Wi * S * C + (double)a.M * C)); launch_igemm(a, 1, s);
 }
 
 void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* dz, float* dw, float* db,
@@ -831,13 +812,12 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
     if (m) m->dm_prefilled.clear();
     if (m && m->keep_dy && layer) {
         // (dz holds the layer's fp32 dY unless it was handed over in another form: dM from the next layer's data gradient, d(pool) with routing bytes, a bf16 copy only)
-        Act& k = m->kept_dy[layer];
+        fcn8s_model::KeptDy& k = m->kept_dy[layer];
         const size_t n = (size_t)N * H * W * Cout;
-        if (promised || pool_idx || m->dy_bf16_only.count(layer) || m->dz_unwritten.count(layer)) k.n = 0;
-        else {
-            if (k.p && k.H != (int)(n >> 20)) { hipStreamSynchronize(s); hipFree(k.p); k.p = nullptr; }
-            if (!k.p && hipMalloc((void**)&k.p, n * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); k.p = nullptr; defer_error(FCN8S_ERR_OOM, "keep_output_gradients: %s's copy cannot be allocated", layer); }
-            if (k.p) { k.n = n; k.H = (int)(n >> 20); hipMemcpyAsync(k.p, dz, n * sizeof(float), hipMemcpyDeviceToDevice, s); }
+        k.n = 0;
+        if (!(promised || pool_idx || m->dy_bf16_only.count(layer) || m->dz_unwritten.count(layer))) {
+            if (k.p.grow(n * sizeof(float), s)) { k.n = n; hipMemcpyAsync(k.p, dz, n * sizeof(float), hipMemcpyDeviceToDevice, s); }
+            else defer_error(FCN8S_ERR_OOM, "keep_output_gradients: %s's copy cannot be allocated", layer);
         }
     }
     auto broken_promise = [&]() { defer_error(FCN8S_ERR_STATE, "%s was handed dM instead of dZ but does not take the Winograd-domain path", layer); };
@@ -944,8 +924,7 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
         if (first && launch_conv1_wgrad(x, dz, dw, db, N, H, W, Cout, m->conv1_wgrad_mfma, s)) return;
         launch_wgrad(a, s);
     };
-    if (m) { ProfScope ps(m, group, flops, bytes, layer); run(); }
-    else run();
+    { ProfScope ps(m, group, flops, bytes, layer); run(); }
 }
 
 void tconv_wgrad(fcn8s_model* m, const float* x, const float* dy, float* dw, int N, int Hi, int Wi, int C,
@@ -959,8 +938,7 @@ void tconv_wgrad(fcn8s_model* m, const float* x, const float* dy, float* dw, int
     a.KW = K; a.a_scale = S; a.tap_off = -(K - S) / 2; a.ntaps = K * K;
     a.ldc = C; a.alpha = 1.f; a.colsum = nullptr;
     auto run = [&]() { if (!launch_tconv_wgrad(x, dy, dw, N, Hi, Wi, C, K, S, s)) launch_wgrad(a, s); };
-    if (m) { ProfScope ps(m, "tconv_wgrad", 2.0 * a.P * K * K * C * C, 4.0 * ((double)N * Hi * S * Wi * S * C + (double)a.P * C)); run(); }
-    else run();
+    ProfScope ps(m, "tconv_wgrad", 2.0 * a.P * K * K * C * C, 4.0 * ((double)N * Hi * S * Wi * S * C + (double)a.P * C)); run();
 }
 
 // ---- workspace --------------------------------------------------------------------
@@ -1103,27 +1081,70 @@ void carve_workspace(fcn8s_model* m, int N, int H, int W, const WsPlan& pl)
     m->d_pred = (long long*)(m->arena + pl.o_pred); m->d_partials = (double*)(m->arena + pl.o_part);
     m->N = N; m->H = H; m->W = W;
 }
+// ---- buffer lifetimes ---------------------------------------------------------------
+// What the model allocates lazily dies with one of four things; each is one function, called from every place that means it.  Each waits for
+// the stream before it frees (a kernel in flight may still read the buffer).  fcn8s_destroy needs none of them: the members free themselves.
+//
+// The arena (another plan: another shape, precision class or layout option) and every view into it.
+void drop_arena(fcn8s_model* m)
+{
+    if (m->arena) hipStreamSynchronize(m->stream);
+    m->arena.reset();
+    m->N = m->H = m->W = 0; m->acts.clear();
+    m->have_forward = m->have_loss = false;
+}
+// The per-layer padded copies whose geometry is the workspace's shape: xbf16 (bf16 forward modes), xg16 / dyg16 (bf16_train), q8 (fp8_infer).
+// keep_regrowable (fcn8s_predict_tta's re-plans, ensure_workspace_at_least): a pass shape comes back many times per call, so the copies that
+// can serve another shape in place stay -- xg16 / dyg16 are only marked stale (g16_for zeroes the new border, and regrows if too small),
+// q8 re-borders itself on a geometry change (q8_for) -- and only xbf16, which is sized once and never checked again, is dropped.
+void drop_shape_copies(fcn8s_model* m, bool keep_regrowable = false)
+{
+    if (!m->xbf16.empty() || (!keep_regrowable && !(m->xg16.empty() && m->dyg16.empty() && m->q8.empty()))) hipStreamSynchronize(m->stream);
+    m->xbf16.clear();
+    m->xg16_filled.clear(); m->dyg16_filled.clear();
+    if (keep_regrowable) {
+        for (auto& kv : m->xg16) m->g16_stale.insert("x:" + kv.first);
+        for (auto& kv : m->dyg16) m->g16_stale.insert("d:" + kv.first);
+        return;
+    }
+    m->xg16.clear(); m->dyg16.clear(); m->g16_stale.clear();
+    m->q8.clear(); m->q8_filled.clear();
+}
+// The banks made from one version of the parameters and kept while the model is frozen: the Winograd filter banks (u_cache) and the bf16
+// kernels (wbf16_cache), with the record of which of them fcn8s_predict_tta left stale.  What else belongs to the occasion is a line at the
+// call site, because the occasions differ:
+//   fcn8s_freeze_params, fcn8s_set_precision  also clear w8_valid (fp8_infer's weight banks keep their storage; the next pass refills them)
+//   fcn8s_set_option                          leaves w8_valid alone (an option changes no parameter, and the e4m3 banks have one layout), and
+//                                             drops u_train as well (the tile option decides its banks' shape)
+//   forward()'s fingerprint guard             leaves w8_valid alone too: it only runs when u_cache has entries, which the direct path of
+//                                             fp8_infer never makes -- so a frozen fp8_infer model has no such guard at all
+void drop_banks(fcn8s_model* m)
+{
+    if (!m->u_cache.empty() || !m->wbf16_cache.empty()) hipStreamSynchronize(m->stream);
+    m->u_cache.clear(); m->wbf16_cache.clear();
+    m->bank_stale.clear(); m->banks_stale = false;
+}
+// Everything that belongs to the arithmetic of one precision: this step's forward banks (u_train -- a mode whose forward pass does not refresh
+// a bank must never find an old one), the frozen banks, the padded copies, and fp8_infer's weight banks (its calibration stays: it describes
+// the parameters, not the mode).
+void drop_precision_state(fcn8s_model* m)
+{
+    hipStreamSynchronize(m->stream);
+    m->u_train.clear();
+    drop_banks(m); m->w8_valid.clear();
+    drop_shape_copies(m);
+    m->w8.clear();
+}
+
 int ensure_workspace(fcn8s_model* m, int N, int H, int W)
 {
     int rc = check_shape(m, N, H, W); if (rc) return rc;
     if (m->arena && m->N == N && m->H == H && m->W == W) return FCN8S_OK;
-    if (m->arena) { hipStreamSynchronize(m->stream); hipFree(m->arena); m->arena = nullptr; }
-    for (auto& kv : m->xbf16) if (kv.second) hipFree(kv.second);
-    m->xbf16.clear();
-    for (auto& kv : m->xg16) if (kv.second) hipFree(kv.second);
-    m->xg16.clear(); m->xg16_elems.clear();
-    for (auto& kv : m->dyg16) if (kv.second) hipFree(kv.second);
-    m->dyg16.clear(); m->dyg16_elems.clear(); m->xg16_filled.clear(); m->dyg16_filled.clear(); m->g16_stale.clear();
-    for (auto& kv : m->q8) if (kv.second.p) hipFree(kv.second.p);
-    m->q8.clear(); m->q8_filled.clear();
-    m->acts.clear();
-    m->have_forward = m->have_loss = false;
+    drop_arena(m);
+    drop_shape_copies(m);
     WsPlan pl;
     plan_workspace(m, N, H, W, pl);
-    hipError_t e = hipMalloc((void**)&m->arena, pl.bytes);
-    if (e != hipSuccess) { m->arena = nullptr; return fail(m, FCN8S_ERR_OOM, std::string("workspace hipMalloc failed: ") + hipGetErrorString(e)); }
-    ++m->ws_allocs;
-    m->arena_bytes = pl.bytes;
+    if (!m->arena.grow(pl.bytes, m->stream, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "workspace hipMalloc failed: out of memory");
     carve_workspace(m, N, H, W, pl);
     return FCN8S_OK;
 }
@@ -1133,23 +1154,15 @@ int ensure_workspace_at_least(fcn8s_model* m, int N, int H, int W, size_t bytes)
 {
     int rc = check_shape(m, N, H, W); if (rc) return rc;
     const bool same = m->arena && m->N == N && m->H == H && m->W == W;
-    if (same && m->arena_bytes >= bytes) return FCN8S_OK;
+    if (same && m->arena.bytes() >= bytes) return FCN8S_OK;
     WsPlan pl;
     plan_workspace(m, N, H, W, pl);
     bytes = std::max(bytes, pl.bytes);
-    if (!m->arena || m->arena_bytes < bytes) {
-        if (m->arena) { hipStreamSynchronize(m->stream); hipFree(m->arena); m->arena = nullptr; m->arena_bytes = 0; m->N = m->H = m->W = 0; m->acts.clear(); }
-        hipError_t e = hipMalloc((void**)&m->arena, bytes);
-        if (e != hipSuccess) { m->arena = nullptr; return fail(m, FCN8S_ERR_OOM, std::string("workspace hipMalloc failed: ") + hipGetErrorString(e)); }
-        ++m->ws_allocs;
-        m->arena_bytes = bytes;
+    if (m->arena.bytes() < bytes) {
+        drop_arena(m);
+        if (!m->arena.grow(bytes, m->stream, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "workspace hipMalloc failed: out of memory");
     }
-    if (!same) {
-        if (!m->xbf16.empty()) { hipStreamSynchronize(m->stream); for (auto& kv : m->xbf16) if (kv.second) hipFree(kv.second); m->xbf16.clear(); }
-        for (auto& kv : m->xg16) m->g16_stale.insert("x:" + kv.first);
-        for (auto& kv : m->dyg16) m->g16_stale.insert("d:" + kv.first);
-        m->xg16_filled.clear(); m->dyg16_filled.clear();
-    }
+    if (!same) drop_shape_copies(m, true);
     carve_workspace(m, N, H, W, pl);
     return FCN8S_OK;
 }
@@ -1265,33 +1278,25 @@ bool bf16_conv_layer(fcn8s_model* m, const char* tag, const char* wname, const c
     const bool big = conv_bf16_256_ok(Mrows, cin, cout, any_shape ? 3 : m->bf16_gemm256);      // 256-row tiles, LDS-DMA, staggered wave groups
     if (!big && (!allow_small || cin % 32 || cout % 128)) return false;
     const size_t wneed = (size_t)K * cout;
-    if (m->wbf16_elems < wneed) {
-        if (m->d_wbf16) { hipStreamSynchronize(s); hipFree(m->d_wbf16); m->d_wbf16 = nullptr; m->wbf16_elems = 0; }
-        if (hipMalloc((void**)&m->d_wbf16, wneed * sizeof(unsigned short)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        m->wbf16_elems = wneed; ++m->ws_allocs;
-    }
+    if (!m->d_wbf16.grow(wneed * sizeof(unsigned short), s, &m->ws_allocs)) return false;
     // weights: bf16, K-tile-major blocks for the 128 x 128 kernel or transposed [Cout][K] for the 256 x 256 one; with frozen parameters
     // (evaluation / serving loops) each layer's copy is made once and kept
     unsigned short* wbuf = m->d_wbf16;
     bool have = false;
     if (m->frozen) {
         const std::string key = std::string(wname) + (big ? "#t" : "#b");
-        unsigned short*& c = m->wbf16_cache[key];
+        DeviceBuf<unsigned short>& c = m->wbf16_cache[key];
         if (c && !m->bank_stale.count("w:" + key)) { wbuf = c; have = true; }
         else if (c) { wbuf = c; m->bank_stale.erase("w:" + key); }                         // kept storage: refilled below
-        else if (hipMalloc((void**)&c, wneed * sizeof(unsigned short)) == hipSuccess) { wbuf = c; ++m->ws_allocs; }
-        else { c = nullptr; (void)hipGetLastError(); }
+        else if (c.grow(wneed * sizeof(unsigned short), s, &m->ws_allocs)) wbuf = c;       // (out of memory: the shared copy, rebuilt per pass)
     }
     if (!have) { ProfScope ps(m, "weight_relayout", 0, 6.0 * K * cout);
                  if (big) launch_w_to_bf16_t(Wp(m, wname), wbuf, K, cout, s); else launch_w_to_bf16_tiles(Wp(m, wname), wbuf, K, cout, s); }
     const int pad = big ? (k - 1) / 2 : 0;
     const size_t nin = (size_t)N * (h + 2 * pad) * (w + 2 * pad) * cin;
-    if (nin % 8 == 0 && m->abf16_elems < nin && !(big && xb_ready)) {
-        if (m->d_abf16) { hipStreamSynchronize(s); hipFree(m->d_abf16); m->d_abf16 = nullptr; m->abf16_elems = 0; }
-        if (hipMalloc((void**)&m->d_abf16, nin * sizeof(unsigned short)) == hipSuccess) { m->abf16_elems = nin; ++m->ws_allocs; } else (void)hipGetLastError();
-    }
+    if (nin % 8 == 0 && !(big && xb_ready)) m->d_abf16.grow(nin * sizeof(unsigned short), s, &m->ws_allocs);      // (out of memory: the paths below that need no copy)
     const double M = (double)Mrows;
-    if (big && (xb_ready || (m->d_abf16 && m->abf16_elems >= nin))) {
+    if (big && (xb_ready || (m->d_abf16 && m->d_abf16.elems() >= nin))) {
         if (!xb_ready) { ProfScope ps(m, "weight_relayout", 0, 4.0 * Mrows * cin + 2.0 * nin); launch_f32_to_bf16_padded(in, m->d_abf16, N, h, w, cin, pad, s); }
         Bf16Conv256Args g{};
         g.xp = xb_ready ? xb_ready : m->d_abf16; g.wt = wbuf; g.bias = Wp(m, bname); g.y = out;
@@ -1320,33 +1325,26 @@ bool bf16_conv_layer(fcn8s_model* m, const char* tag, const char* wname, const c
 
 // bf16_train: a guarded, zero-bordered bf16 buffer for layer `layer` out of `bufs` (allocated and zeroed on first use or when the shape grows: the
 // border and the guard rows are never written again, the interior is overwritten in every pass); returns the address of padded pixel 0 or nullptr
-unsigned short* g16_for(fcn8s_model* m, std::map<std::string, unsigned short*>& bufs, std::map<std::string, size_t>& sizes, const char* layer,
-                        int N, int H, int W, int C, int K, hipStream_t s)
+unsigned short* g16_for(fcn8s_model* m, fcn8s_model::G16Map& bufs, const char* layer, int N, int H, int W, int C, int K, hipStream_t s)
 {
     const int pad = (K - 1) / 2, Wp_ = W + 2 * pad;
     const long long G = bf16_guard_rows(K, Wp_), R = (long long)N * (H + 2 * pad) * Wp_;
     const size_t need = (size_t)(R + 2 * G) * C;
-    unsigned short*& p = bufs[layer];
-    size_t& have = sizes[layer];
-    const std::string stale_key = std::string(&bufs == &m->xg16 ? "x:" : "d:") + layer;
-    if (!p || have < need) {
-        if (p) { hipStreamSynchronize(s); hipFree(p); p = nullptr; have = 0; }
-        if (hipMalloc((void**)&p, need * sizeof(unsigned short)) != hipSuccess) { p = nullptr; (void)hipGetLastError(); return nullptr; }
-        have = need; ++m->ws_allocs;
-        hipMemsetAsync(p, 0, need * sizeof(unsigned short), s);
-        m->g16_stale.erase(stale_key);
-    } else if (m->g16_stale.erase(stale_key)) hipMemsetAsync(p, 0, need * sizeof(unsigned short), s);     // (another shape: another border)
+    DeviceBuf<unsigned short>& p = bufs[layer];
+    bool fresh = false;
+    if (!p.grow(need * sizeof(unsigned short), s, &m->ws_allocs, true, &fresh)) return nullptr;
+    if (m->g16_stale.erase(std::string(&bufs == &m->xg16 ? "x:" : "d:") + layer) && !fresh) hipMemsetAsync(p, 0, need * sizeof(unsigned short), s);     // (another shape: another border)
     return p + g16_off(G, C);           // padded pixel 0 of plane 0 (planes are g16_ps() apart)
 }
 // the copy of layer `layer`'s INPUT (forward pass; read again by its weight gradient)
-unsigned short* xg16_for(fcn8s_model* m, const char* layer, int N, int H, int W, int C, int K, hipStream_t s) { return g16_for(m, m->xg16, m->xg16_elems, layer, N, H, W, C, K, s); }
+unsigned short* xg16_for(fcn8s_model* m, const char* layer, int N, int H, int W, int C, int K, hipStream_t s) { return g16_for(m, m->xg16, layer, N, H, W, C, K, s); }
 // the copy of layer `layer`'s output gradient dY [N][H][W][C]: written by the kernel that produced dY if that was a bf16 data gradient
 // (dyg16_filled), else converted here, once (the layer's weight gradient asks first, its data gradient finds it)
 // db: the layer's bias gradient, db[c] += sum dY[., c] -- taken by the conversion kernel on its way through dY (*db_done says whether it was)
 unsigned short* dyb_for(fcn8s_model* m, const char* layer, const float* dy, int N, int H, int W, int C, int K, hipStream_t s, float* db, bool* db_done)
 {
     if (db_done) *db_done = false;
-    unsigned short* p = g16_for(m, m->dyg16, m->dyg16_elems, layer, N, H, W, C, K, s);
+    unsigned short* p = g16_for(m, m->dyg16, layer, N, H, W, C, K, s);
     if (!p) return nullptr;
     if (!m->dyg16_filled.count(layer)) {
         ProfScope ps(m, "bf16_convert", 0, 4.0 * N * H * W * C + 2.0 * N * H * W * C);
@@ -1364,13 +1362,9 @@ unsigned short* xb_by_transform(fcn8s_model* m, const char* layer, int N, int H,
 {
     if (!m->bf16_copy_by_transform || Cin % 8 || !m->acts.count(std::string("wv:") + layer) || wino_tile_for(m, H, W, 3) != 6) return nullptr;
     if (!conv_bf16_256_ok((long long)N * H * W, Cin, Cout, m->bf16_gemm256)) return nullptr;
-    unsigned short*& p = m->xbf16[layer];
-    if (!p) {
-        const size_t bytes = (size_t)N * (H + 2) * (W + 2) * Cin * sizeof(unsigned short);
-        if (hipMalloc((void**)&p, bytes) != hipSuccess) { p = nullptr; (void)hipGetLastError(); m->xbf16.erase(layer); return nullptr; }
-        ++m->ws_allocs;
-        hipMemsetAsync(p, 0, bytes, s);
-    }
+    DeviceBuf<unsigned short>& p = m->xbf16[layer];
+    // (sized once: the copies are dropped whenever the workspace is planned for another shape, drop_shape_copies)
+    if (!p && !p.grow((size_t)N * (H + 2) * (W + 2) * Cin * sizeof(unsigned short), s, &m->ws_allocs, true)) { m->xbf16.erase(layer); return nullptr; }
     return p;
 }
 
@@ -1394,9 +1388,8 @@ void wino_backward_operands(fcn8s_model* m, const char* layer, const float* x, c
       if (in_rbits_out && in_layer && KS == 3) m->rbits_ok.insert(in_layer); }
     const std::string key = std::string(layer) + "#" + std::to_string(tile);
     if ((KS == 3 && tile == 6) || (KS == 7 && tile == 4)) {
-        float*& tu = m->u_train[key];
-        if (!tu && hipMalloc((void**)&tu, (size_t)P * Kg * Cout * sizeof(float)) != hipSuccess) { tu = nullptr; (void)hipGetLastError(); }
-        if (tu) { ProfScope ps(m, "wino_transform", 0, (double)(KS * KS + P * nsub2) * 4 * Cin * Cout); launch_wino_filter(tile, wk, tu, Cin, Cout, KS, s); }
+        DeviceBuf<float>& tu = m->u_train[key];
+        if (tu.grow((size_t)P * Kg * Cout * sizeof(float), s)) { ProfScope ps(m, "wino_transform", 0, (double)(KS * KS + P * nsub2) * 4 * Cin * Cout); launch_wino_filter(tile, wk, tu, Cin, Cout, KS, s); }
         else m->u_train.erase(key);
     }
 }
@@ -1448,10 +1441,9 @@ static size_t q8_bytes(int N, int H, int W, int C, int K) { const int pad = (K -
 static bool q8_grow(fcn8s_model* m, const std::string& key, size_t bytes, hipStream_t s)
 {
     Q8Buf& b = m->q8[key];
-    if (b.p && b.bytes >= bytes) return true;
-    if (b.p) { hipStreamSynchronize(s); hipFree(b.p); b.p = nullptr; b.bytes = 0; }
-    if (hipMalloc((void**)&b.p, bytes) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return false; }
-    ++m->ws_allocs; b.bytes = bytes; b.pad = -1;
+    bool fresh = false;
+    if (!b.p.grow(bytes, s, &m->ws_allocs, false, &fresh)) return false;
+    if (fresh) b.pad = -1;
     return true;
 }
 // the padded e4m3 copy `key` for a K x K consumer on an H x W map of C channels, codes with exponent ex (nullptr: out of memory).  The producer writes every
@@ -1475,10 +1467,10 @@ static const W8Bank* w8_for(fcn8s_model* m, const char* layer, const char* wname
 {
     W8Bank& b = m->w8[layer];
     const size_t wbytes = (size_t)KK * Cin * Cout, need = wbytes + 8 * (size_t)Cout;
-    if (!b.wq || b.bytes < need) {
-        if (b.wq) { hipStreamSynchronize(s); hipFree(b.wq); b.wq = nullptr; b.bytes = 0; }
-        if (hipMalloc((void**)&b.wq, need) != hipSuccess) { (void)hipGetLastError(); b.wq = nullptr; return nullptr; }
-        ++m->ws_allocs; b.bytes = need; m->w8_valid.erase(layer);
+    bool fresh = false;
+    if (!b.wq.grow(need, s, &m->ws_allocs, false, &fresh)) return nullptr;
+    if (fresh) {
+        m->w8_valid.erase(layer);
         b.ew = reinterpret_cast<int*>(b.wq + wbytes); b.amax = reinterpret_cast<unsigned*>(b.wq + wbytes + 4 * (size_t)Cout);
     }
     if (!(m->frozen && m->w8_valid.count(layer))) {
@@ -1523,14 +1515,6 @@ static int fp8_conv(fcn8s_model* m, const char* group, const char* layer, const 
 int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, bool train)
 {
     t_deterministic = m->deterministic;
-    auto drop_banks = [&]() {
-        hipStreamSynchronize(m->stream);
-        for (auto& kv : m->u_cache) if (kv.second) hipFree(kv.second);
-        m->u_cache.clear();
-        for (auto& kv : m->wbf16_cache) if (kv.second) hipFree(kv.second);
-        m->wbf16_cache.clear();
-        m->bank_stale.clear(); m->banks_stale = false;
-    };
     hipStream_t s = m->stream;
     const int N = m->N, H = m->H, W = m->W, C = m->C;
     // FCN8S_PREC_FP8_INFER: evaluation / prediction through the e4m3 kernels; the calibration pass (fcn8s_fp8_calibrate) is the fp32 direct path
@@ -1546,7 +1530,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
         // The check does not hold the pass up: the fingerprint is taken first on the stream, the pass is enqueued behind it with the kept
         // banks, and the host compares when the (long finished) copy is looked at -- at the end of this function; a mismatch repeats the pass.
         launch_fingerprint(m->d_params, (long long)m->total, m->d_fp, s);
-        if (!m->h_fp && hipHostMalloc((void**)&m->h_fp, sizeof(unsigned long long)) != hipSuccess) { m->h_fp = nullptr; (void)hipGetLastError(); }
+        m->h_fp.grow(sizeof(unsigned long long), s);          // (no pinned memory: the synchronous comparison below)
         if (m->h_fp && !m->fp_event) hipEventCreateWithFlags(&m->fp_event, hipEventDisableTiming);
         if (m->h_fp && m->fp_event) {
             hipMemcpyAsync(m->h_fp, m->d_fp, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
@@ -1556,7 +1540,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
             unsigned long long fp = 0;
             hipMemcpyAsync(&fp, m->d_fp, sizeof fp, hipMemcpyDeviceToHost, s);
             hipStreamSynchronize(s);
-            if (fp != m->frozen_fp) drop_banks();
+            if (fp != m->frozen_fp) drop_banks(m);
         }
     }
     const bool fill_fp = m->frozen && (m->u_cache.empty() || m->banks_stale);       // (banks_stale: kept storage, contents to be rebuilt)
@@ -1822,7 +1806,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
     if (guard_pending) {
         hipEventSynchronize(m->fp_event);
         if (*m->h_fp != m->frozen_fp) {            // the parameters changed behind the library's back: this pass used stale banks -- again, without them
-            drop_banks();
+            drop_banks(m);
             return forward(m, img_dev, dtype, keep_prob, train);
         }
     }
@@ -1837,21 +1821,13 @@ const char* kDecoderKernels[6] = {"pool3_1x1/kernel", "pool4_1x1/kernel", "fc7_1
 int ensure_loss_ws(fcn8s_model* m, long long npix)
 {
     const size_t need = LOSS_SCRATCH_BYTES + (m->loss_mode == 2 ? (size_t)npix * sizeof(float) : 0);
-    if (m->loss_ws && m->loss_ws_bytes >= need) return FCN8S_OK;
-    if (m->loss_ws) { hipStreamSynchronize(m->stream); hipFree(m->loss_ws); m->loss_ws = nullptr; m->loss_ws_bytes = 0; }
-    HIPCHK(m, hipMalloc((void**)&m->loss_ws, need));
-    m->loss_ws_bytes = need; ++m->ws_allocs;
-    return FCN8S_OK;
+    return m->loss_ws.grow(need, m->stream, &m->ws_allocs) ? FCN8S_OK : fail(m, FCN8S_ERR_OOM, "the training loss's scratch cannot be allocated");
 }
 
 // the Lovász sort's scratch (fcn8s_set_lovasz), grown only
 int ensure_lovasz_ws(fcn8s_model* m, const LovaszLayout& y)
 {
-    if (m->lov_ws && m->lov_ws_bytes >= y.bytes) return FCN8S_OK;
-    if (m->lov_ws) { hipStreamSynchronize(m->stream); hipFree(m->lov_ws); m->lov_ws = nullptr; m->lov_ws_bytes = 0; }
-    HIPCHK(m, hipMalloc((void**)&m->lov_ws, y.bytes));
-    m->lov_ws_bytes = y.bytes; ++m->ws_allocs;
-    return FCN8S_OK;
+    return m->lov_ws.grow(y.bytes, m->stream, &m->ws_allocs) ? FCN8S_OK : fail(m, FCN8S_ERR_OOM, "the Lovasz sort's scratch cannot be allocated");
 }
 
 int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool with_grad)
@@ -1861,7 +1837,7 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
     const int nb = softmax_xent_blocks(npix);
     const int mode = with_grad ? m->loss_mode : 0;            // evaluation keeps the reference's loss
     if (mode) { int rc = ensure_loss_ws(m, npix); if (rc) return rc; }
-    OhemState* st = mode ? (OhemState*)m->loss_ws : nullptr;
+    OhemState* st = mode ? (OhemState*)m->loss_ws.get() : nullptr;
     const bool lov = with_grad && m->lov_on;                    // evaluation keeps the reference's loss here too
     const bool lov_sort = lov && m->lov_w != 0.f;
     const float gscale = lov ? m->lov_ce * (1.0f / (float)npix) : 1.0f / (float)npix;    // (exactly 1 / npix at lov_ce == 1)
@@ -2022,7 +1998,7 @@ void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
         if (!pidx && bf16_train_mode(m) && m->bf16_fuse_pool && m->train_mode && cw % 64 == 0) {
             // bf16_train: nobody reads the fp32 dZ of the block's last conv -- its weight and data gradients take the padded bf16 copy, its bias gradient the
             // column sums: the pool's backward kernel writes exactly those (gbuf[gcur ^ 1] stays unwritten; the "dz" handed on below is never dereferenced)
-            unsigned short* dzb = g16_for(m, m->dyg16, m->dyg16_elems, last, N, h, w, cw, 3, s);
+            unsigned short* dzb = g16_for(m, m->dyg16, last, N, h, w, cw, 3, s);
             if (dzb) {
                 ProfScope ps(m, "maxpool_bwd", 0, 4.0 * N * h * w * cw * (m->pool_routed[b - 1] ? 0.3125 : 1.25) + 2.0 * N * h * w * cw);
                 char ix[16]; snprintf(ix, sizeof ix, "pidx%d", b);
@@ -2104,8 +2080,9 @@ int do_backward_bucket(fcn8s_model* m, int bucket)
 int ensure_opt_state(fcn8s_model* m)
 {
     if (m->d_m) return FCN8S_OK;
-    HIPCHK(m, hipMalloc((void**)&m->d_m, m->total * sizeof(float)));
-    HIPCHK(m, hipMalloc((void**)&m->d_v, m->total * sizeof(float)));
+    if (!m->d_m.grow(m->total * sizeof(float), m->stream) || !m->d_v.grow(m->total * sizeof(float), m->stream)) {
+        m->d_m.reset(); return fail(m, FCN8S_ERR_OOM, "the optimizer's slots cannot be allocated");
+    }
     HIPCHK(m, hipMemsetAsync(m->d_m, 0, m->total * sizeof(float), m->stream));
     HIPCHK(m, hipMemsetAsync(m->d_v, 0, m->total * sizeof(float), m->stream));
     return FCN8S_OK;
@@ -2184,42 +2161,33 @@ int fcn8s_create(const fcn8s_config* cfg, fcn8s_model** out)
     }
     build_param_table(m->C, m->widths, m->fc6k, m->params, m->total, m->bucket_off, m->bucket_n);
     for (size_t i = 0; i < m->params.size(); ++i) m->index[m->params[i].name] = (int)i;
-    const size_t bytes = m->total * sizeof(float);
-    auto bail = [&](const char* what, hipError_t err) { std::string msg = std::string(what) + ": " + hipGetErrorString(err); fcn8s_destroy(m); return fail(nullptr, FCN8S_ERR_OOM, msg); };
-    if (cfg->ext_params) m->d_params = (float*)cfg->ext_params;
-    else { if ((e = hipMalloc((void**)&m->d_params, bytes)) != hipSuccess) return bail("hipMalloc(params)", e); m->own_params = true; hipMemset(m->d_params, 0, bytes); }
-    if (cfg->ext_grads) m->d_grads = (float*)cfg->ext_grads;
-    else { if ((e = hipMalloc((void**)&m->d_grads, bytes)) != hipSuccess) return bail("hipMalloc(grads)", e); m->own_grads = true; hipMemset(m->d_grads, 0, bytes); }
-    if ((e = hipMalloc((void**)&m->d_wt, bytes)) != hipSuccess) return bail("hipMalloc(wt)", e);
+    // (hipMalloc'ed memory is not zero: what is read before it is first written is cleared here)
+    bool ok = true;
+    auto dev = [&](auto& buf, size_t n, bool zero = false) { ok = ok && buf.grow(n * sizeof(*buf.get()), nullptr, nullptr, zero); };
+    if (cfg->ext_params) m->d_params = (float*)cfg->ext_params; else { dev(m->own_params, m->total, true); m->d_params = m->own_params; }
+    if (cfg->ext_grads) m->d_grads = (float*)cfg->ext_grads; else { dev(m->own_grads, m->total, true); m->d_grads = m->own_grads; }
+    dev(m->d_wt, m->total);
     // 12 taps x 4 channels: rows 36..47 (three padding taps of the LDS-DMA conv1_1 kernel) and the 64 floats behind them stay zero
-    if ((e = hipMalloc((void**)&m->d_w1pad, (12 * 4 * (size_t)m->widths[0] + 64) * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
-    hipMemset(m->d_w1pad, 0, (12 * 4 * (size_t)m->widths[0] + 64) * sizeof(float));
+    dev(m->d_w1pad, 12 * 4 * (size_t)m->widths[0] + 64, true);
     const size_t cc = (size_t)m->C * m->C;
-    if ((e = hipMalloc((void**)&m->d_tph[0], 16 * cc * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc((void**)&m->d_tph[1], 16 * cc * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc((void**)&m->d_tph[2], 256 * cc * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
+    dev(m->d_tph[0], 16 * cc); dev(m->d_tph[1], 16 * cc); dev(m->d_tph[2], 256 * cc);
     {
         int cmax = 0; for (int i = 0; i < 5; ++i) cmax = std::max(cmax, m->widths[i]);
-        size_t ufl = 64 * (size_t)cmax * cmax;                        // F(6x6,3x3): 64 positions
-        if (m->fc6k == 7) ufl = std::max(ufl, fc6_bank_floats(m->widths[4], m->widths[5]));
-        if ((e = hipMalloc((void**)&m->d_wino_u, ufl * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
-        m->ufl = ufl;
+        m->ufl = 64 * (size_t)cmax * cmax;                            // F(6x6,3x3): 64 positions
+        if (m->fc6k == 7) m->ufl = std::max(m->ufl, fc6_bank_floats(m->widths[4], m->widths[5]));
+        dev(m->d_wino_u, m->ufl);
     }
-    if ((e = hipMalloc((void**)&m->d_loss, (2 + 64 + 4) * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
+    dev(m->d_loss, 2 + 64 + 4, true);
     m->d_regsum = m->d_loss + 1; m->d_lastbias = m->d_loss + 2; m->d_terms = m->d_loss + 2 + 64;
-    if ((e = hipMalloc((void**)&m->d_conf, cc * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc((void**)&m->d_fp, sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
+    dev(m->d_conf, cc, true); dev(m->d_fp, 1);
     m->tg_kp = (4 * m->C + 63) / 64 * 64;
     {
         const size_t NC = 64 * (size_t)m->C, KP = (size_t)m->tg_kp;
-        if ((e = hipMalloc((void**)&m->tg_b2, 4 * (size_t)m->C * NC * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
-        if ((e = hipMalloc((void**)&m->tg_b2t, NC * KP * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
-        if ((e = hipMalloc((void**)&m->tg_db2, KP * NC * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
-        if ((e = hipMalloc((void**)&m->tg_bias, NC * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
+        dev(m->tg_b2, 4 * (size_t)m->C * NC); dev(m->tg_b2t, NC * KP); dev(m->tg_db2, KP * NC); dev(m->tg_bias, NC);
     }
-    hipMemset(m->d_conf, 0, cc * sizeof(unsigned long long));
-    hipMemset(m->d_loss, 0, 2 * sizeof(float));
-    if (hipHostMalloc((void**)&m->h_loss, 64, hipHostMallocDefault) != hipSuccess) { m->h_loss = nullptr; (void)hipGetLastError(); }
+    if (!ok) { fcn8s_destroy(m); return fail(nullptr, FCN8S_ERR_OOM, "fcn8s_create: out of device memory"); }
+    hipStreamSynchronize(nullptr);          // the clears above: done before a caller's stream touches the buffers
+    m->h_loss.grow(64, nullptr);            // (no pinned memory: the loss is read synchronously)
     if (hipEventCreateWithFlags(&m->loss_ev, hipEventDisableTiming) != hipSuccess) { m->loss_ev = nullptr; (void)hipGetLastError(); }
     *out = m;
     return FCN8S_OK;
@@ -2235,55 +2203,6 @@ int fcn8s_destroy(fcn8s_model* m)
     hipDeviceSynchronize();
     // the per-stream scratch of the streams this model ran on (the caller's stream may live on: what it holds is given back, the next user grows its own)
     scratch_release(m->stream);
-    for (auto& g : m->groups) for (auto& ev : g.ev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
-    if (m->own_params && m->d_params) hipFree(m->d_params);
-    if (m->own_grads && m->d_grads) hipFree(m->d_grads);
-    if (m->d_m) hipFree(m->d_m);
-    if (m->d_v) hipFree(m->d_v);
-    if (m->d_wt) hipFree(m->d_wt);
-    if (m->d_w1pad) hipFree(m->d_w1pad);
-    for (auto& e : m->bucket_ev) if (e) { hipEventDestroy(e); e = nullptr; }
-    for (auto& kv : m->kept_dy) if (kv.second.p) hipFree(kv.second.p);
-    for (auto& kv : m->u_train) if (kv.second) hipFree(kv.second);
-    if (m->d_wino_u) hipFree(m->d_wino_u);
-    for (auto& kv : m->u_cache) if (kv.second) hipFree(kv.second);
-    for (auto& kv : m->wbf16_cache) if (kv.second) hipFree(kv.second);
-    if (m->d_wbf16) hipFree(m->d_wbf16);
-    if (m->d_abf16) hipFree(m->d_abf16);
-    for (auto& kv : m->q8) if (kv.second.p) hipFree(kv.second.p);
-    for (auto& kv : m->w8) if (kv.second.wq) hipFree(kv.second.wq);
-    if (m->d_fp8_amax) hipFree(m->d_fp8_amax);
-    for (auto& kv : m->xbf16) if (kv.second) hipFree(kv.second);
-    for (auto& kv : m->xg16) if (kv.second) hipFree(kv.second);
-    for (auto& kv : m->dyg16) if (kv.second) hipFree(kv.second);
-    for (int i = 0; i < 3; ++i) if (m->d_tph[i]) hipFree(m->d_tph[i]);
-    if (m->d_loss) hipFree(m->d_loss);
-    if (m->h_loss) hipHostFree(m->h_loss);
-    if (m->loss_ev) hipEventDestroy(m->loss_ev);
-    if (m->d_conf) hipFree(m->d_conf);
-    if (m->d_fp) hipFree(m->d_fp);
-    if (m->h_fp) hipHostFree(m->h_fp);
-    if (m->fp_event) hipEventDestroy(m->fp_event);
-    if (m->tg_b2) hipFree(m->tg_b2);
-    if (m->tg_b2t) hipFree(m->tg_b2t);
-    if (m->tg_db2) hipFree(m->tg_db2);
-    if (m->tg_bias) hipFree(m->tg_bias);
-    for (auto& sl : m->slots) {
-        if (sl.h_img) hipHostFree(sl.h_img);
-        if (sl.h_lab) hipHostFree(sl.h_lab);
-        if (sl.d_img) hipFree(sl.d_img);
-        if (sl.d_lab) hipFree(sl.d_lab);
-        if (sl.ready) hipEventDestroy(sl.ready);
-        if (sl.consumed) hipEventDestroy(sl.consumed);
-    }
-    if (m->copy_stream) hipStreamDestroy(m->copy_stream);
-    if (m->arena) hipFree(m->arena);
-    if (m->tta_buf) hipFree(m->tta_buf);
-    if (m->crf_buf) hipFree(m->crf_buf);
-    if (m->loss_ws) hipFree(m->loss_ws);
-    if (m->d_cw) hipFree(m->d_cw);
-    if (m->lov_ws) hipFree(m->lov_ws);
-    if (m->d_lovmask) hipFree(m->d_lovmask);
     delete m;
     // the model is gone either way; a communicator that had failed is reported once, with its reason in fcn8s_last_error(NULL)
     if (rc_comm) { g_last_error = comm_text; return rc_comm; }
@@ -2292,21 +2211,10 @@ int fcn8s_destroy(fcn8s_model* m)
 
 const char* fcn8s_last_error(const fcn8s_model* m) { return m ? m->err.c_str() : g_last_error.c_str(); }
 
-static void drop_u_cache(fcn8s_model* m)
-{
-    m->w8_valid.clear();                                  // (fp8_infer weight banks: storage kept, contents rebuilt by the next pass)
-    if (m->u_cache.empty() && m->wbf16_cache.empty()) return;
-    hipStreamSynchronize(m->stream);
-    for (auto& kv : m->u_cache) if (kv.second) hipFree(kv.second);
-    m->u_cache.clear();
-    for (auto& kv : m->wbf16_cache) if (kv.second) hipFree(kv.second);
-    m->wbf16_cache.clear();
-    m->bank_stale.clear(); m->banks_stale = false;
-}
 int fcn8s_freeze_params(fcn8s_model* m, int frozen)
 {
     if (!m) return FCN8S_ERR_BAD_ARG;
-    if (!frozen || !m->frozen) drop_u_cache(m);          // entering or leaving: start from an empty cache
+    if (!frozen || !m->frozen) { drop_banks(m); m->w8_valid.clear(); }          // entering or leaving: start from an empty cache
     m->frozen = frozen != 0;
     return FCN8S_OK;
 }
@@ -2330,22 +2238,8 @@ int fcn8s_set_precision(fcn8s_model* m, int precision)
             return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_precision: the bf16 modes need conv5 width % 32 == 0 and fc6 / fc7 widths % 128 == 0");
     }
     if (precision != m->precision) {
-        // the forward filter banks kept for the adjoint data gradients belong to the arithmetic that made them (and a mode whose forward
-        // pass does not refresh a bank must never find an old one)
         HIPCHK(m, hipStreamSynchronize(m->stream));
-        for (auto& kv : m->u_train) if (kv.second) hipFree(kv.second);
-        m->u_train.clear();
-        drop_u_cache(m);
-        for (auto& kv : m->xbf16) if (kv.second) hipFree(kv.second);      // (the padded bf16 activation copies of the bf16 forward modes)
-        m->xbf16.clear();
-        for (auto& kv : m->xg16) if (kv.second) hipFree(kv.second);
-        m->xg16.clear(); m->xg16_elems.clear();
-        for (auto& kv : m->dyg16) if (kv.second) hipFree(kv.second);
-        m->dyg16.clear(); m->dyg16_elems.clear(); m->xg16_filled.clear(); m->dyg16_filled.clear();
-        for (auto& kv : m->q8) if (kv.second.p) hipFree(kv.second.p);       // (fp8_infer's copies and weight banks; its calibration stays: it describes the parameters)
-        m->q8.clear(); m->q8_filled.clear();
-        for (auto& kv : m->w8) if (kv.second.wq) hipFree(kv.second.wq);
-        m->w8.clear(); m->w8_valid.clear();
+        drop_precision_state(m);
         // bf16_train runs every convolution but conv1_1 as a DIRECT convolution on the bf16 MFMA, forward and backward: it rides on the library's
         // direct path (no Winograd transforms, the pools as kernels of their own, ReLU masks from the activations), i.e. on the settings
         // winograd_min_cin = 0 / winograd_fc6 = 0, which it takes over while it is on (and which need another workspace)
@@ -2354,8 +2248,7 @@ int fcn8s_set_precision(fcn8s_model* m, int precision)
         if (was != now) {
             if (now) { m->saved_wino_min_cin = m->wino_min_cin; m->saved_wino_fc6 = m->wino_fc6; m->wino_min_cin = 0; m->wino_fc6 = 0; }
             else { if (m->saved_wino_min_cin >= 0) m->wino_min_cin = m->saved_wino_min_cin; if (m->saved_wino_fc6 >= 0) m->wino_fc6 = m->saved_wino_fc6; }
-            if (m->arena) { hipFree(m->arena); m->arena = nullptr; m->arena_bytes = 0; m->N = m->H = m->W = 0; m->acts.clear(); }
-            m->have_forward = m->have_loss = false;
+            drop_arena(m);
         }
     }
     m->precision = precision;
@@ -2372,7 +2265,7 @@ int fcn8s_fp8_calibrate(fcn8s_model* m, const void* images, int dtype, int N, in
     int rc = ensure_workspace(m, N, H, W); if (rc) return rc;
     const void* img; const uint8_t* lab;
     rc = stage_inputs(m, images, dtype, nullptr, where, &img, &lab); if (rc) return rc;
-    if (!m->d_fp8_amax) HIPCHK(m, hipMalloc((void**)&m->d_fp8_amax, FCN8S_FP8_LAYERS * sizeof(unsigned)));
+    if (!m->d_fp8_amax.grow(FCN8S_FP8_LAYERS * sizeof(unsigned), m->stream)) return fail(m, FCN8S_ERR_OOM, "fcn8s_fp8_calibrate: out of device memory");
     float start[FCN8S_FP8_LAYERS] = {};
     if (!reset && m->fp8_calibrated) memcpy(start, m->fp8_amax, sizeof start);
     HIPCHK(m, hipStreamSynchronize(m->stream));
@@ -2452,6 +2345,7 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
 {
     if (!key) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_option: null key");
     const std::string k = key;
+    if (k == "device_bytes_live") return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_option: 'device_bytes_live' is read-only");
     if (!m) {
         if (k == "op_f32x3") { t_op_split = value ? 3 : 0; return FCN8S_OK; }
         if (k == "op_deterministic") { t_deterministic = value ? 1 : 0; return FCN8S_OK; }
@@ -2489,21 +2383,15 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
     if (*slot == (int)value) return FCN8S_OK;
     HIPCHK(m, hipStreamSynchronize(m->stream));
     *slot = (k == "winograd_fc6" || k == "fc6_fft" || k == "tconv_gemm") ? (value != 0) : (int)value;
-    if (m->arena) { hipFree(m->arena); m->arena = nullptr; m->arena_bytes = 0; m->N = m->H = m->W = 0; m->acts.clear(); }
-    m->have_forward = m->have_loss = false;
-    for (auto& kv : m->u_cache) if (kv.second) hipFree(kv.second);
-    for (auto& kv : m->wbf16_cache) if (kv.second) hipFree(kv.second);
-    m->wbf16_cache.clear();
-    m->u_cache.clear();
-    m->bank_stale.clear(); m->banks_stale = false;
-    for (auto& kv : m->u_train) if (kv.second) hipFree(kv.second);
-    m->u_train.clear();
+    drop_arena(m);
+    drop_banks(m); m->u_train.clear();
     return FCN8S_OK;
 }
 int fcn8s_get_option(const fcn8s_model* m, const char* key, int64_t* value)
 {
     if (!key || !value) return FCN8S_ERR_BAD_ARG;
     const std::string k = key;
+    if (k == "device_bytes_live") { *value = g_device_bytes_live.load(); return FCN8S_OK; }      // (process-wide: with or without a model)
     if (!m) {
         if (k == "op_f32x3") { *value = t_op_split == 3; return FCN8S_OK; }
         if (k == "op_deterministic") { *value = t_deterministic; return FCN8S_OK; }
@@ -2905,8 +2793,8 @@ int fcn8s_comm_allreduce_metrics(fcn8s_model* m)
     std::vector<double> h(n);
     for (size_t i = 0; i < cc; ++i) h[i] = (double)conf[i];
     h[cc] = ls; h[cc + 1] = (double)lc;
-    double* d = nullptr;
-    HIPCHK(m, hipMalloc((void**)&d, n * sizeof(double)));
+    DeviceBuf<double> d;                                 // (freed on return: every path below leaves behind the stream's synchronise)
+    if (!d.grow(n * sizeof(double), m->stream)) return fail(m, FCN8S_ERR_OOM, "fcn8s_comm_allreduce_metrics: out of device memory");
     hipMemcpyAsync(d, h.data(), n * sizeof(double), hipMemcpyHostToDevice, m->stream);
     ncclResult_t r = ncclSuccess; int rct = FCN8S_OK; bool gone = false;
     {
@@ -2924,7 +2812,6 @@ int fcn8s_comm_allreduce_metrics(fcn8s_model* m)
     }
     if (!gone && r == ncclSuccess && rct == FCN8S_OK && !m->comm_failed.load()) hipMemcpyAsync(h.data(), d, n * sizeof(double), hipMemcpyDeviceToHost, m->stream);
     hipStreamSynchronize(m->stream);                     // (behind a completed or aborted collective: returns)
-    hipFree(d);
     if (gone || m->comm_failed.load()) return comm_failed_rc(m, "fcn8s_comm_allreduce_metrics");
     if (r != ncclSuccess) return rccl_fail(m, "ncclAllReduce(metrics)", r);
     if (rct) return rct;
@@ -2993,7 +2880,7 @@ int fcn8s_set_loss(fcn8s_model* m, const float* class_weights, int nweights, flo
     int rc = check_loss_args(m, class_weights, nweights, m->C, ohem_thresh, ohem_min_kept, "fcn8s_set_loss"); if (rc) return rc;
     const int mode = ohem_thresh > 0.f ? 2 : class_weights ? 1 : 0;
     if (mode) {
-        if (!m->d_cw) HIPCHK(m, hipMalloc((void**)&m->d_cw, 64 * sizeof(float)));
+        if (!m->d_cw.grow(64 * sizeof(float), m->stream)) return fail(m, FCN8S_ERR_OOM, "fcn8s_set_loss: out of device memory");
         std::vector<float> w(64, 0.f);
         for (int c = 0; c < m->C; ++c) w[c] = class_weights ? class_weights[c] : 1.f;
         HIPCHK(m, hipStreamSynchronize(m->stream));          // (a queued step may still read the old weights)
@@ -3041,7 +2928,7 @@ int fcn8s_set_lovasz(fcn8s_model* m, float ce_weight, float lovasz_weight, int p
     int rc = check_lovasz_args(m, ce_weight, lovasz_weight, per_image, classes_all, class_mask, nmask, m->C); if (rc) return rc;
     const bool on = !(ce_weight == 1.f && lovasz_weight == 0.f);
     if (on) {
-        if (!m->d_lovmask) HIPCHK(m, hipMalloc((void**)&m->d_lovmask, 64));
+        if (!m->d_lovmask.grow(64, m->stream)) return fail(m, FCN8S_ERR_OOM, "fcn8s_set_lovasz: out of device memory");
         uint8_t h[64] = {};
         int n = 0;
         for (int c = 0; c < m->C; ++c) { h[c] = class_mask ? (class_mask[c] != 0) : 1; n += h[c]; }
@@ -3233,11 +3120,7 @@ int fcn8s_predict_tta(fcn8s_model* m, const void* images, int dtype, int N, int 
     const size_t npix = (size_t)N * H * W, eb = dtype == FCN8S_IMG_U8 ? 1 : 4;
     const size_t b_img = where == FCN8S_HOST ? align_up(npix * 3 * eb, 256) : 0, b_acc = P > 1 ? align_up(npix * C * sizeof(float), 256) : 0;
     const size_t b_out = where == FCN8S_HOST ? align_up(argmax ? npix * sizeof(long long) : npix * C * sizeof(float), 256) : 0;
-    if (m->tta_bytes < b_img + b_acc + b_out) {
-        if (m->tta_buf) { HIPCHK(m, hipStreamSynchronize(m->stream)); hipFree(m->tta_buf); m->tta_buf = nullptr; m->tta_bytes = 0; }
-        HIPCHK(m, hipMalloc((void**)&m->tta_buf, b_img + b_acc + b_out));
-        m->tta_bytes = b_img + b_acc + b_out; ++m->ws_allocs;
-    }
+    if (b_img + b_acc + b_out && !m->tta_buf.grow(b_img + b_acc + b_out, m->stream, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "fcn8s_predict_tta: its scratch cannot be allocated");
     hipStream_t s = m->stream;
     const void* img = images;
     if (where == FCN8S_HOST) { HIPCHK(m, hipMemcpyAsync(m->tta_buf, images, npix * 3 * eb, hipMemcpyHostToDevice, s)); img = m->tta_buf; }
@@ -3314,8 +3197,7 @@ static void crf_run(fcn8s_model* m, hipStream_t s, const float* prob, const uint
             launch_crf_meanfield(src, prob, images, N, H, W, C, p->radius, p->dilation, p->w_appearance, p->w_smooth, p->theta_alpha, p->theta_beta,
                                  p->theta_gamma, dst, last ? argmax_out : nullptr, s);
         };
-        if (m) { ProfScope ps(m, "crf_meanfield", fl, by); launch(); }
-        else launch();
+        { ProfScope ps(m, "crf_meanfield", fl, by); launch(); }
         src = dst;
     }
 }
@@ -3338,14 +3220,10 @@ int fcn8s_predict_crf(fcn8s_model* m, const void* images, int dtype, int N, int 
     const size_t b_img = host ? align_up(npix * 3, 256) : 0;
     const size_t b_out = host ? (argmax ? align_up(npix * sizeof(long long), 256) : b_q) : 0;
     const size_t need = b_img + 3 * b_q + b_out;
-    if (m->crf_bytes < need) {
-        if (m->crf_buf) { HIPCHK(m, hipStreamSynchronize(m->stream)); hipFree(m->crf_buf); m->crf_buf = nullptr; m->crf_bytes = 0; }
-        HIPCHK(m, hipMalloc((void**)&m->crf_buf, need));
-        m->crf_bytes = need; ++m->ws_allocs;
-    }
+    if (!m->crf_buf.grow(need, m->stream, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "fcn8s_predict_crf: its scratch cannot be allocated");
     hipStream_t s = m->stream;
     const uint8_t* img = (const uint8_t*)images;
-    if (host) { HIPCHK(m, hipMemcpyAsync(m->crf_buf, images, npix * 3, hipMemcpyHostToDevice, s)); img = (const uint8_t*)m->crf_buf; }
+    if (host) { HIPCHK(m, hipMemcpyAsync(m->crf_buf, images, npix * 3, hipMemcpyHostToDevice, s)); img = (const uint8_t*)m->crf_buf.get(); }
     float* prob = (float*)(m->crf_buf + b_img);
     float* work = (float*)(m->crf_buf + b_img + b_q);          // 2 b_q bytes: crf_run's two halves of N H W C floats
     void* dout = host ? (void*)(m->crf_buf + b_img + 3 * b_q) : out;
@@ -3373,24 +3251,10 @@ int fcn8s_stage_inputs(fcn8s_model* m, int slot, const void* images, int dtype, 
     const size_t npix = (size_t)N * H * W, ib = npix * 3 * (dtype == FCN8S_IMG_U8 ? 1 : 4), lb = label_ids ? npix : 0;
     if (!sl.ready) { HIPCHK(m, hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming)); HIPCHK(m, hipEventCreateWithFlags(&sl.consumed, hipEventDisableTiming)); }
     if (sl.used) HIPCHK(m, hipEventSynchronize(sl.ready));        // the previous copy out of this slot's pinned buffers has finished
-    if (sl.cap_img < ib) {
-        if (sl.used) HIPCHK(m, hipEventSynchronize(sl.consumed));
-        if (sl.h_img) hipHostFree(sl.h_img);
-        if (sl.d_img) hipFree(sl.d_img);
-        sl.h_img = nullptr; sl.d_img = nullptr; sl.cap_img = 0;
-        HIPCHK(m, hipHostMalloc(&sl.h_img, ib, hipHostMallocDefault));
-        HIPCHK(m, hipMalloc(&sl.d_img, ib));
-        sl.cap_img = ib;
-    }
-    if (lb && sl.cap_lab < lb) {
-        if (sl.used) HIPCHK(m, hipEventSynchronize(sl.consumed));
-        if (sl.h_lab) hipHostFree(sl.h_lab);
-        if (sl.d_lab) hipFree(sl.d_lab);
-        sl.h_lab = nullptr; sl.d_lab = nullptr; sl.cap_lab = 0;
-        HIPCHK(m, hipHostMalloc((void**)&sl.h_lab, lb, hipHostMallocDefault));
-        HIPCHK(m, hipMalloc((void**)&sl.d_lab, lb));
-        sl.cap_lab = lb;
-    }
+    // (a pair that grows: the step that last read the device half has finished with it -- `consumed` -- before the pair is freed)
+    if ((sl.d_img.bytes() < ib || sl.d_lab.bytes() < lb) && sl.used) HIPCHK(m, hipEventSynchronize(sl.consumed));
+    if (!sl.h_img.grow(ib, m->copy_stream) || !sl.d_img.grow(ib, m->copy_stream) || (lb && (!sl.h_lab.grow(lb, m->copy_stream) || !sl.d_lab.grow(lb, m->copy_stream))))
+        return fail(m, FCN8S_ERR_OOM, "fcn8s_stage_inputs: the slot's buffers cannot be allocated");
     memcpy(sl.h_img, images, ib);                         // pageable -> pinned on this (feeder) thread
     if (lb) memcpy(sl.h_lab, label_ids, lb);
     if (sl.used) HIPCHK(m, hipStreamWaitEvent(m->copy_stream, sl.consumed, 0));   // the step that last read this slot's device buffers
@@ -3399,7 +3263,7 @@ int fcn8s_stage_inputs(fcn8s_model* m, int slot, const void* images, int dtype, 
     HIPCHK(m, hipEventRecord(sl.ready, m->copy_stream));
     sl.used = true;
     if (images_dev) *images_dev = sl.d_img;
-    if (labels_dev) *labels_dev = lb ? sl.d_lab : nullptr;
+    if (labels_dev) *labels_dev = lb ? sl.d_lab.get() : nullptr;
     return FCN8S_OK;
 }
 int fcn8s_stage_wait(fcn8s_model* m, int slot)
@@ -3553,16 +3417,14 @@ int fcn8s_get_dropout_masks(fcn8s_model* m, float* h6, size_t n6, float* h7, siz
     const Act& a6 = m->acts.at("fc6"); const Act& a7 = m->acts.at("fc7");
     if (n6 != a6.n || n7 != a7.n) return fail(m, FCN8S_ERR_SHAPE, "mask size mismatch");
     const float keep = (m->train_mode ? m->keep_prob : 1.f);
-    float* d = nullptr;
-    const size_t nmax = n6 > n7 ? n6 : n7;
-    HIPCHK(m, hipMalloc((void**)&d, nmax * sizeof(float)));
+    DeviceBuf<float> d;
+    if (!d.grow(std::max(n6, n7) * sizeof(float), m->stream)) return fail(m, FCN8S_ERR_OOM, "fcn8s_get_dropout_masks: out of device memory");
     launch_dropout_mask(d, (long long)n6, keep, m->seed, m->drop_stream, m->stream);
     hipMemcpyAsync(h6, d, n6 * sizeof(float), hipMemcpyDeviceToHost, m->stream);
     hipStreamSynchronize(m->stream);
     launch_dropout_mask(d, (long long)n7, keep, m->seed, m->drop_stream + 1, m->stream);
     hipMemcpyAsync(h7, d, n7 * sizeof(float), hipMemcpyDeviceToHost, m->stream);
     hipStreamSynchronize(m->stream);
-    hipFree(d);
     return FCN8S_OK;
 }
 
@@ -3709,12 +3571,11 @@ int fcn8s_op_conv2d_winograd(void* stream, const float* x, const float* w, const
         return fail(nullptr, FCN8S_ERR_BAD_ARG, "conv2d_winograd: needs tile in {2,4,6} (4 for K = 7), K in {3,7}, Cin % 16, Cout % 32, even H and W (multiples of tile for tile 2 and 4)");
     hipStream_t s = (hipStream_t)stream;
     const size_t T = (size_t)wino_tiles(tile, N, H, W), P = (size_t)wino_alpha(tile, K) * wino_alpha(tile, K), Kg = (size_t)wino_nsub(K) * wino_nsub(K) * Cin;
-    float *u = nullptr, *v = nullptr, *mm = nullptr;
-    if (hipMalloc((void**)&u, P * Kg * Cout * 4) != hipSuccess || hipMalloc((void**)&v, P * (size_t)wino_slab(T, (int)Kg) * 4) != hipSuccess ||
-        hipMalloc((void**)&mm, P * (size_t)wino_slab(T, Cout) * 4) != hipSuccess) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+    DeviceBuf<float> u, v, mm;
+    if (!u.grow(P * Kg * Cout * 4, s) || !v.grow(P * (size_t)wino_slab(T, (int)Kg) * 4, s) || !mm.grow(P * (size_t)wino_slab(T, Cout) * 4, s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
     WinoEpi we; we.bias = bias; we.relu = relu;
     conv_winograd(nullptr, tile, K, "", x, w, y, u, v, mm, N, H, W, Cin, Cout, we, s, nullptr);
-    hipStreamSynchronize(s); hipFree(u); hipFree(v); hipFree(mm);
+    hipStreamSynchronize(s);
     OPCHK(); return FCN8S_OK;
 }
 
@@ -3734,31 +3595,32 @@ int fcn8s_op_conv3x3_winograd_fwd_bwd(void* stream, const float* x, const float*
     const int al = tile + 2, P = al * al, cmax = std::max(Cin, Cout);
     const size_t T = (size_t)wino_tiles(tile, N, H, W);
     const size_t slab_max = (size_t)P * (size_t)wino_slab((long long)T, cmax), slab_in = (size_t)P * (size_t)wino_slab((long long)T, Cin);
-    std::vector<void*> owned;
-    auto dalloc = [&](size_t nfloats) -> float* { void* p = nullptr; if (hipMalloc(&p, nfloats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return nullptr; } owned.push_back(p); return (float*)p; };
-    auto cleanup = [&]() { hipStreamSynchronize(s); for (void* p : owned) hipFree(p); for (auto& kv : m->u_train) if (kv.second) hipFree(kv.second); m->u_train.clear(); };
-    m->d_wino_u = dalloc((size_t)P * cmax * cmax); m->d_wino_v = dalloc(slab_max); m->d_wino_m = dalloc(slab_max);
-    float* wv = dalloc(slab_in); float* wt = dalloc((size_t)9 * Cin * Cout);
-    float* pidx = pooled ? dalloc(((size_t)N * (H / 2) * (W / 2) * Cout + 3) / 4) : nullptr;
-    float* rbits = mask_mode == 2 ? dalloc(wino_rbits_words(tile, N, H, W, Cin)) : nullptr;
-    if (!m->d_wino_u || !m->d_wino_v || !m->d_wino_m || !wv || !wt || (pooled && !pidx) || (mask_mode == 2 && !rbits)) { cleanup(); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
+    // (what the model keeps in its arena is this call's own; the model frees d_wino_u and the banks it makes behind this function's back)
+    DeviceBuf<float> wino_v, wino_m, wv, wt, pidx, rbits;
+    bool ok = true;
+    auto dalloc = [&](DeviceBuf<float>& b, size_t nfloats) { ok = ok && b.grow(nfloats * sizeof(float), s); };
+    dalloc(m->d_wino_u, (size_t)P * cmax * cmax); dalloc(wino_v, slab_max); dalloc(wino_m, slab_max);
+    dalloc(wv, slab_in); dalloc(wt, (size_t)9 * Cin * Cout);
+    if (pooled) dalloc(pidx, ((size_t)N * (H / 2) * (W / 2) * Cout + 3) / 4);
+    if (mask_mode == 2) dalloc(rbits, wino_rbits_words(tile, N, H, W, Cin));
+    if (!ok) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+    m->d_wino_v = wino_v; m->d_wino_m = wino_m;
     Act a; a.p = wv; a.n = slab_in; m->acts["wv:op"] = a;
     // forward (training mode: keeps V and the filter bank, writes the pool argmax bytes / the input's ReLU bit record)
     m->fwd_train = true; m->train_mode = true;
     { Epi e; e.bias = bias; e.relu = 1;
-      if (pooled) { e.pool_out = pool; e.pool_idx = (unsigned char*)pidx; e.skip_y = y == nullptr; }
-      if (mask_mode == 2) { e.in_relu_bits_out = (unsigned*)rbits; e.in_layer = "prev"; }
+      if (pooled) { e.pool_out = pool; e.pool_idx = (unsigned char*)pidx.get(); e.skip_y = y == nullptr; }
+      if (mask_mode == 2) { e.in_relu_bits_out = (unsigned*)rbits.get(); e.in_layer = "prev"; }
       conv_same(m, "op", x, w, y, N, H, W, Cin, Cout, 3, e, s, 0, "op"); }
     // backward: weight + bias gradient in the Winograd domain, then the data gradient (adjoint form for tile 6)
     hipMemsetAsync(dw, 0, (size_t)9 * Cin * Cout * sizeof(float), s);
     if (db) hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), s);
-    conv_wgrad(m, "op", x, dy, dw, db, N, H, W, Cin, Cout, 3, 1.f, s, 0, "op", tile >= 4, pooled ? (const unsigned char*)pidx : nullptr);
+    conv_wgrad(m, "op", x, dy, dw, db, N, H, W, Cin, Cout, 3, 1.f, s, 0, "op", tile >= 4, pooled ? (const unsigned char*)pidx.get() : nullptr);
     { Epi e; e.dgrad = 1; e.w_fwd = w; e.lazy_wt = 1; e.addend = dx_addend;
       if (mask_mode) { e.mask = x; e.mask_scale = 1.f; }
-      if (mask_mode == 2 && m->rbits_ok.count("prev")) e.relu_bits_in = (const unsigned*)rbits;
+      if (mask_mode == 2 && m->rbits_ok.count("prev")) e.relu_bits_in = (const unsigned*)rbits.get();
       conv_same(m, "op", dy, wt, dx, N, H, W, Cout, Cin, 3, e, s, 0, "op"); }
-    cleanup();
-    m->acts.clear();
+    hipStreamSynchronize(s);
     OPCHK(); return FCN8S_OK;
 }
 
@@ -3783,34 +3645,19 @@ int fcn8s_op_conv7x7_fc6_fwd_bwd(void* stream, const float* x, const float* w, c
     // what a model's shared workspace holds behind a slab or a partial row tile is another layer's leftovers
     const Fc6Scratch f6 = fc6_scratch_floats(m, N, H, W, Cin, Cout);
     const size_t vmax = std::max(f6.v_wino, f6.v_fft), mmax = std::max(f6.v_wino, f6.m_fft);
-    std::vector<void*> owned;
-    auto dalloc = [&](size_t nfloats, bool poison) -> float* {
-        void* p = nullptr;
-        if (hipMalloc(&p, nfloats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        owned.push_back(p);
-        if (poison) hipMemsetAsync(p, 0xFF, nfloats * sizeof(float), s);
-        return (float*)p;
-    };
-    auto cleanup = [&]() {
-        hipStreamSynchronize(s);
-        for (void* p : owned) hipFree(p);
-        for (auto& kv : m->u_train) if (kv.second) hipFree(kv.second);
-        m->u_train.clear(); m->acts.clear();
-        for (auto& g : m->groups) for (auto& ev : g.ev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
-    };
+    DeviceBuf<float> wino_v, wino_m, wv, wt;               // (wt: the flipped + transposed kernel of a forward-type data gradient, the model's d_wt)
     bool ok = true;
-    auto slot = [&](const char* name, size_t n) -> float* {
-        float* p = dalloc(n, true);
-        if (!p) { ok = false; return nullptr; }
-        Act a; a.p = p; a.n = n; m->acts[name] = a;
-        return p;
+    auto dalloc = [&](DeviceBuf<float>& b, size_t nfloats, bool poison, const char* slot = nullptr) {      // slot: also one of the model's named arena items
+        ok = ok && b.grow(nfloats * sizeof(float), s);
+        if (ok && poison) hipMemsetAsync(b, 0xFF, nfloats * sizeof(float), s);
+        if (ok && slot) { Act a; a.p = b; a.n = nfloats; m->acts[slot] = a; }
     };
-    if (vmax) { m->d_wino_v = slot("wino_v", vmax); m->d_wino_m = slot("wino_m", mmax); }
-    if (f6.wv) slot("wv:op", f6.wv);
+    if (vmax) { dalloc(wino_v, vmax, true, "wino_v"); dalloc(wino_m, mmax, true, "wino_m"); m->d_wino_v = wino_v; m->d_wino_m = wino_m; }
+    if (f6.wv) dalloc(wv, f6.wv, true, "wv:op");
     m->ufl = fc6_bank_floats(Cin, Cout);
-    m->d_wino_u = dalloc(m->ufl, true);
-    float* wt = dalloc((size_t)49 * Cin * Cout, false);       // the flipped + transposed kernel of a forward-type data gradient (the model's d_wt)
-    if (!ok || !m->d_wino_u || !wt) { cleanup(); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
+    dalloc(m->d_wino_u, m->ufl, true);
+    dalloc(wt, (size_t)49 * Cin * Cout, false);
+    if (!ok) { hipStreamSynchronize(s); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
     // forward, as forward() runs fc6 (step 0: dropout stream 0)
     m->fwd_train = true; m->train_mode = true; m->drop_stream = 0;
     { Epi e; e.bias = bias; e.relu = 1; e.dropout = keep_prob < 1.f; e.keep = keep_prob; e.stream_id = m->drop_stream;
@@ -3828,7 +3675,7 @@ int fcn8s_op_conv7x7_fc6_fwd_bwd(void* stream, const float* x, const float* w, c
             if (g.name == "fc6_fft_gemm_wgrad") *dft_products |= 2;
             if (g.name == "fc6_fft_gemm_dgrad") *dft_products |= 4;
         }
-    cleanup();
+    hipStreamSynchronize(s);
     OPCHK(); return FCN8S_OK;
 }
 
@@ -3837,13 +3684,13 @@ int fcn8s_op_conv2d_bf16(void* stream, const float* x, const float* w, const flo
 {
     if (Cin % 32 || Cout % 128 || K % 2 == 0) return fail(nullptr, FCN8S_ERR_BAD_ARG, "conv2d_bf16: needs Cin % 32 == 0, Cout % 128 == 0, K odd");
     hipStream_t s = (hipStream_t)stream;
-    unsigned short* wt = nullptr;
-    if (hipMalloc((void**)&wt, (size_t)K * K * Cin * Cout * 2) != hipSuccess) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+    DeviceBuf<unsigned short> wt;
+    if (!wt.grow((size_t)K * K * Cin * Cout * 2, s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
     launch_w_to_bf16_tiles(w, wt, K * K * Cin, Cout, s);
     Bf16ConvArgs a{};
     a.x = x; a.wt = wt; a.bias = bias; a.y = y; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.K = K; a.relu = relu;
     launch_conv_bf16(a, s);
-    hipStreamSynchronize(s); hipFree(wt);
+    hipStreamSynchronize(s);
     OPCHK(); return FCN8S_OK;
 }
 
@@ -3861,18 +3708,13 @@ int fcn8s_op_conv2d_bf16_train(void* stream, const float* x, const float* w, con
     // layout every kernel still takes -- plane stride 0 -- and the other bf16 modes use)
     const long long PS = t_op_planes ? (R + 2 * G) * 32 : 0;
     const long long OX = t_op_planes ? G * 32 : G * Cin, OY = t_op_planes ? G * 32 : G * Cout;
-    unsigned short *xb = nullptr, *dyb = nullptr, *wt = nullptr;
-    auto cleanup = [&]() { hipStreamSynchronize(s); if (xb) hipFree(xb); if (dyb) hipFree(dyb); if (wt) hipFree(wt); };
+    DeviceBuf<unsigned short> xb, dyb, wt;
     const size_t nx = (size_t)(R + 2 * G) * Cin, ny = (size_t)(R + 2 * G) * Cout, nw = (size_t)K * K * Cin * Cout;
-    if (hipMalloc((void**)&wt, nw * 2) != hipSuccess) { cleanup(); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
+    if (!wt.grow(nw * 2, s) || (x && !xb.grow(nx * 2, s, nullptr, true)) || (dy && !dyb.grow(ny * 2, s, nullptr, true))) { hipStreamSynchronize(s); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
     if (x) {
-        if (hipMalloc((void**)&xb, nx * 2) != hipSuccess) { cleanup(); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
-        hipMemsetAsync(xb, 0, nx * 2, s);
         launch_f32_to_bf16_padded(x, xb + OX, N, H, W, Cin, pad, s, PS);
     }
     if (dy) {
-        if (hipMalloc((void**)&dyb, ny * 2) != hipSuccess) { cleanup(); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
-        hipMemsetAsync(dyb, 0, ny * 2, s);
         launch_f32_to_bf16_padded(dy, dyb + OY, N, H, W, Cout, pad, s, PS);
     }
     bool ok = true;
@@ -3894,7 +3736,7 @@ int fcn8s_op_conv2d_bf16_train(void* stream, const float* x, const float* w, con
         ok = ok && launch_wgrad_bf16(g, s);
     }
     if (db && dy) { hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), s); launch_colsum(dy, db, (long long)N * H * W, Cout, s); }
-    cleanup();
+    hipStreamSynchronize(s);
     if (!ok) return fail(nullptr, FCN8S_ERR_SHAPE, "conv2d_bf16_train: a launch refused the shape");
     OPCHK(); return FCN8S_OK;
 }
@@ -3911,12 +3753,8 @@ int fcn8s_op_conv2d_fp8(void* stream, const float* x, const float* w, const floa
     const int pad = (K - 1) / 2;
     const long long R = (long long)N * (H + 2 * pad) * (W + 2 * pad);
     const size_t xb = (size_t)R * Cin, wb = (size_t)K * K * Cin * Cout;
-    unsigned char *xq = nullptr, *wq = nullptr;
-    auto cleanup = [&]() { hipStreamSynchronize(s); if (xq) hipFree(xq); if (wq) hipFree(wq); };
-    if (hipMalloc((void**)&xq, xb) != hipSuccess || hipMalloc((void**)&wq, wb + 8 * (size_t)Cout) != hipSuccess) {
-        (void)hipGetLastError(); cleanup(); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
-    }
-    hipMemsetAsync(xq, 0, xb, s);
+    DeviceBuf<unsigned char> xq, wq;
+    if (!xq.grow(xb, s, nullptr, true) || !wq.grow(wb + 8 * (size_t)Cout, s)) { hipStreamSynchronize(s); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
     launch_f32_to_fp8_padded(x, xq, N, H, W, Cin, pad, R * 64, x_exp, s);
     int* ew = reinterpret_cast<int*>(wq + wb);
     launch_w_to_fp8(w, wq, ew, reinterpret_cast<unsigned*>(wq + wb + 4 * (size_t)Cout), K * K * Cin, Cout, s);
@@ -3924,7 +3762,7 @@ int fcn8s_op_conv2d_fp8(void* stream, const float* x, const float* w, const floa
     a.xp = xq; a.xp_ps = R * 64; a.wq = wq; a.ew = ew; a.bias = bias; a.y = y; a.ex = x_exp; a.relu = relu;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.K = K; a.M = (long long)N * H * W;
     const bool ok = launch_conv_fp8(a, s);
-    cleanup();
+    hipStreamSynchronize(s);
     if (!ok) return fail(nullptr, FCN8S_ERR_SHAPE, "conv2d_fp8: the launch refused the shape");
     OPCHK(); return FCN8S_OK;
 }
@@ -3940,11 +3778,11 @@ int fcn8s_op_conv2d_bwd(void* stream, const float* x, const float* w, const floa
         conv_wgrad(nullptr, "", x, dy, dw, db, N, H, W, Cin, Cout, K, 1.f, s);
     } else if (db) { hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), s); launch_colsum(dy, db, (long long)N * H * W, Cout, s); }
     if (dx) {
-        float* wt = nullptr;
-        if (hipMalloc((void**)&wt, (size_t)K * K * Cin * Cout * sizeof(float)) != hipSuccess) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+        DeviceBuf<float> wt;
+        if (!wt.grow((size_t)K * K * Cin * Cout * sizeof(float), s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
         launch_flip_transpose(w, wt, K * K, Cin, Cout, s);
         Epi e; conv_same(nullptr, "", dy, wt, dx, N, H, W, Cout, Cin, K, e, s);
-        hipStreamSynchronize(s); hipFree(wt);
+        hipStreamSynchronize(s);
     }
     OPCHK(); return FCN8S_OK;
 }
@@ -3965,11 +3803,11 @@ int fcn8s_op_conv2d_transpose(void* stream, const float* x, const float* w, cons
 {
     if (C % 4 || K != 2 * S) return fail(nullptr, FCN8S_ERR_BAD_ARG, "conv2d_transpose: needs C%4==0 and K == 2*S");
     hipStream_t s = (hipStream_t)stream;
-    float* wp = nullptr;
-    if (hipMalloc((void**)&wp, (size_t)S * S * 4 * C * C * sizeof(float)) != hipSuccess) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+    DeviceBuf<float> wp;
+    if (!wp.grow((size_t)S * S * 4 * C * C * sizeof(float), s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
     launch_tconv_phase_pack(w, wp, K, S, C, s);
     tconv_fwd(nullptr, x, wp, bias, addend, y, N, Hi, Wi, C, K, S, s);
-    hipStreamSynchronize(s); hipFree(wp);
+    hipStreamSynchronize(s);
     OPCHK(); return FCN8S_OK;
 }
 
@@ -3987,11 +3825,11 @@ int fcn8s_op_conv2d_transpose_bwd(void* stream, const float* x, const float* w, 
 int fcn8s_op_softmax_xent(void* stream, const float* logits, const uint8_t* labels, float* dlogits, float* loss_dev, int64_t npix, int C)
 {
     hipStream_t s = (hipStream_t)stream;
-    double* part = nullptr;
-    if (hipMalloc((void**)&part, 4096 * sizeof(double)) != hipSuccess) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+    DeviceBuf<double> part;
+    if (!part.grow(4096 * sizeof(double), s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
     launch_softmax_xent(logits, labels, dlogits, part, npix, C, 1.0f / (float)npix, s);
     launch_finalize_loss(part, softmax_xent_blocks(npix), npix, nullptr, 0.f, loss_dev, s);
-    hipStreamSynchronize(s); hipFree(part);
+    hipStreamSynchronize(s);
     OPCHK(); return FCN8S_OK;
 }
 int fcn8s_op_softmax_xent_ex(void* stream, const float* logits, const uint8_t* labels, const float* class_weights_dev, float ohem_thresh,
@@ -4003,9 +3841,9 @@ int fcn8s_op_softmax_xent_ex(void* stream, const float* logits, const uint8_t* l
     hipStream_t s = (hipStream_t)stream;
     const bool ohem = ohem_thresh > 0.f;
     const size_t lb = ohem && !pixel_loss_dev ? (size_t)npix * sizeof(float) : 0;
-    char* ws = nullptr;
-    if (hipMalloc((void**)&ws, 4096 * sizeof(double) + 64 * sizeof(float) + LOSS_SCRATCH_BYTES + lb) != hipSuccess) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
-    double* part = (double*)ws;
+    DeviceBuf<char> ws;
+    if (!ws.grow(4096 * sizeof(double) + 64 * sizeof(float) + LOSS_SCRATCH_BYTES + lb, s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+    double* part = (double*)ws.get();
     float* ones = (float*)(ws + 4096 * sizeof(double));
     char* sc = ws + 4096 * sizeof(double) + 64 * sizeof(float);
     if (!class_weights_dev) { const std::vector<float> h(64, 1.f); hipMemcpyAsync(ones, h.data(), 64 * sizeof(float), hipMemcpyHostToDevice, s); hipStreamSynchronize(s); }
@@ -4021,7 +3859,6 @@ int fcn8s_op_softmax_xent_ex(void* stream, const float* logits, const uint8_t* l
         const int64_t h[3] = {(int64_t)st.valid, (int64_t)(ohem ? st.kept : st.valid), (int64_t)tb};
         hipMemcpy(stats_dev, h, sizeof h, hipMemcpyHostToDevice);
     }
-    hipFree(ws);
     OPCHK(); return FCN8S_OK;
 }
 int fcn8s_op_lovasz_softmax(void* stream, const float* x, int x_is_logits, const uint8_t* labels, int64_t nseg, int64_t seg_pixels, int C,
@@ -4033,12 +3870,12 @@ int fcn8s_op_lovasz_softmax(void* stream, const float* x, int x_is_logits, const
     hipStream_t s = (hipStream_t)stream;
     const long long npix = (long long)nseg * seg_pixels;
     const LovaszLayout y = lovasz_layout(npix, (int)nseg, C);
-    char* ws = nullptr;
-    if (hipMalloc((void**)&ws, y.bytes) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
+    DeviceBuf<char> ws;
+    if (!ws.grow(y.bytes, s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
     launch_lovasz_loss(x, x_is_logits, labels, nullptr, 0, npix, y, classes_all, class_mask_dev, ws, class_loss_out, nullptr, 1.f, 1.f, nullptr, s);
     hipMemcpyAsync(loss_out_dev, ws + y.o_lov, sizeof(float), hipMemcpyDeviceToDevice, s);
     if (grad_out) launch_lovasz_backward(x, x_is_logits, labels, nullptr, 0, npix, y, ws, 1.f, 0, grad_out, nullptr, s);
-    hipStreamSynchronize(s); hipFree(ws);
+    hipStreamSynchronize(s);
     OPCHK(); return FCN8S_OK;
 }
 int fcn8s_op_softmax_argmax(void* stream, const float* logits, float* sm, int64_t* am, int64_t npix, int C)

@@ -424,6 +424,7 @@ int fcn8s_fp8_set_calibration(fcn8s_model* m, const float* amax, int n);
  *     "workspace_allocations"  (read-only statistic; setting it is FCN8S_ERR_BAD_ARG) device allocations the model has made for its workspace,
  *                              the scratch of fcn8s_predict_tta and fcn8s_predict_crf, its bf16 copies and its cached (frozen / TTA) filter banks
  *     "frozen"                 (read-only) 1 while fcn8s_freeze_params(m, 1) holds
+ *     "device_bytes_live"      (read-only, process-wide: m may be NULL) device bytes the library's models and op-level calls hold right now (not the per-stream scratch)
  *     "comm_timeout_ms" 600000 the communicator's watchdog (see fcn8s_comm_init): a collective older than this is given up, the communicator aborted
  *   op-context options (m == NULL): the arithmetic of the op-level entry points below, which have no model.  The value belongs to the
  *   CALLING THREAD (thread-local) and is read by that thread's later fcn8s_op_* calls only; no model ever reads it, so two models -- or a
