@@ -360,6 +360,15 @@ struct ProfScope {
     }
 };
 
+// A count-only group of the detailed profile (fcn8s_profile_enable(m, 2)), "derived:<build step>": a FORWARD pass (re)built one more tensor from
+// the parameters alone -- a Winograd filter bank, a bf16 relayout of a kernel, the padded / phase-packed kernels.  No events, no time (ms, flops
+// and bytes stay 0: consumers that divide by ms skip such groups): what a frozen model's later passes must report as zero (fp8_infer's banks
+// have a timed group of their own, fp8_quantize_w).  The name is written at the build site, so a new build site needs its own line.
+static void prof_derived(fcn8s_model* m, const char* what)
+{
+    if (m && m->profile && m->profile_detail) m->groups[group_id(m, (std::string("derived:") + what).c_str())].launches += 1;
+}
+
 // ---- layer launchers ------------------------------------------------------------
 struct Epi { const float* bias = nullptr; const float* addend = nullptr; const float* mask = nullptr;
              float alpha = 1.f; int relu = 0; float mask_scale = 1.f; int dropout = 0; float keep = 1.f;
@@ -600,7 +609,7 @@ void conv_winograd(fcn8s_model* m, int tile, int KS, const char* tag, const floa
         if (tu.grow((size_t)P * Kg * Cout * sizeof(float), s)) { u = tu; a.w = u; }
     }
     // v_ready: V was written together with the weight gradient's dM by the fused transform (launch_wino_input_dout)
-    auto pre = [&]() { if (!u_cached) launch_wino_filter(tile, wk, u, Cin, Cout, KS, s); if (!v_ready) launch_wino_input(tile, x, v, N, H, W, Cin, KS, s, e.in_rbits_out); };
+    auto pre = [&]() { if (!u_cached) { prof_derived(m, "wino_filter_kernel"); launch_wino_filter(tile, wk, u, Cin, Cout, KS, s); } if (!v_ready) launch_wino_input(tile, x, v, N, H, W, Cin, KS, s, e.in_rbits_out); };
     auto post = [&]() {
         if (e.next_v && tile == 6 && KS == 3 && e.relu && e.bias && !e.addend && !e.mask && !e.dropout && !e.pool && !e.rbits_in &&
             launch_wino_out_in(mm, e.bias, e.next_v, e.rbits_out, N, H, W, Cout, s, m && m->fuse_out_in >= 2)) { if (e.fused_out) *e.fused_out = true; return; }
@@ -692,6 +701,7 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
         if (kept != m->u_train.end() && kept->second && bt_gemm_ok(Cin, Cout)) {
             a.w = kept->second; a.bt = 1; a.ldw = Cin;          // the forward bank U[xi][ci_fwd = Cout here][co_fwd = Cin here], read transposed
         } else {
+            // (a filter transform of the BACKWARD pass, into shared scratch: nothing a frozen model keeps, so no prof_derived count)
             ProfScope ps(m, "wino_transform", 0, (double)(9 + P) * 4 * Cin * Cout); launch_wino_filter(6, e.w_fwd, m->d_wino_u, Cout, Cin, 3, s, 1);
         }
         { ProfScope ps(m, "wino_gemm_dgrad", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
@@ -1110,28 +1120,35 @@ void drop_shape_copies(fcn8s_model* m, bool keep_regrowable = false)
     m->xg16.clear(); m->dyg16.clear(); m->g16_stale.clear();
     m->q8.clear(); m->q8_filled.clear();
 }
-// The banks made from one version of the parameters and kept while the model is frozen: the Winograd filter banks (u_cache) and the bf16
-// kernels (wbf16_cache), with the record of which of them fcn8s_predict_tta left stale.  What else belongs to the occasion is a line at the
-// call site, because the occasions differ:
-//   fcn8s_freeze_params, fcn8s_set_precision  also clear w8_valid (fp8_infer's weight banks keep their storage; the next pass refills them)
-//   fcn8s_set_option                          leaves w8_valid alone (an option changes no parameter, and the e4m3 banks have one layout), and
-//                                             drops u_train as well (the tile option decides its banks' shape)
-//   forward()'s fingerprint guard             leaves w8_valid alone too: it only runs when u_cache has entries, which the direct path of
-//                                             fp8_infer never makes -- so a frozen fp8_infer model has no such guard at all
-void drop_banks(fcn8s_model* m)
+// The banks made from one version of the parameters and kept while the model is frozen, of three kinds: the Winograd filter banks (u_cache)
+// and the bf16 kernels (wbf16_cache), with the record of which of them fcn8s_predict_tta left stale, and fp8_infer's e4m3 weight banks, which
+// keep their storage (w8) and lose only their validity (w8_valid: the next pass refills them).  Every occasion drops all three --
+// fcn8s_freeze_params, fcn8s_set_precision, a mismatch found by forward()'s fingerprint guard -- but one: fcn8s_set_option passes keep_w8 (an
+// option changes no parameter, and the e4m3 banks have one layout) and drops u_train as well (the tile option decides its banks' shape).
+void drop_banks(fcn8s_model* m, bool keep_w8 = false)
 {
     if (!m->u_cache.empty() || !m->wbf16_cache.empty()) hipStreamSynchronize(m->stream);
     m->u_cache.clear(); m->wbf16_cache.clear();
     m->bank_stale.clear(); m->banks_stale = false;
+    if (!keep_w8) m->w8_valid.clear();
+}
+// Whether a frozen model holds anything made from its parameters: a bank of any of the three kinds.  The padded / phase-packed kernels of
+// prepare_forward_weights and the fingerprint frozen_fp are made in the pass that makes the first of them.  This one rule answers both
+// questions forward() asks: "is there something the fingerprint guard must protect" and "must this pass rebuild and take the fingerprint".
+static bool keeps_banks(const fcn8s_model* m)
+{
+    return !m->u_cache.empty() || !m->wbf16_cache.empty() || !m->w8_valid.empty();
 }
 // Everything that belongs to the arithmetic of one precision: this step's forward banks (u_train -- a mode whose forward pass does not refresh
 // a bank must never find an old one), the frozen banks, the padded copies, and fp8_infer's weight banks (its calibration stays: it describes
-// the parameters, not the mode).
+// the parameters, not the mode).  Clearing u_train here is defensive: today every backward path that reads one of its banks also needs the
+// Winograd V (or the DFT bank, fft6_ready) that the SAME pass's forward wrote, and that forward refreshed the bank first -- no sequence of calls
+// reaches an old one.  It keeps that true for a path added later, and frees the banks of a mode that is no longer on.
 void drop_precision_state(fcn8s_model* m)
 {
     hipStreamSynchronize(m->stream);
     m->u_train.clear();
-    drop_banks(m); m->w8_valid.clear();
+    drop_banks(m);
     drop_shape_copies(m);
     m->w8.clear();
 }
@@ -1247,6 +1264,7 @@ int stage_inputs(fcn8s_model* m, const void* images, int dtype, const uint8_t* l
 void prepare_forward_weights(fcn8s_model* m)
 {
     hipStream_t s = m->stream;
+    prof_derived(m, "prepare_forward_weights");
     launch_pad_cin(Wp(m, "conv1_1/filter"), m->d_w1pad, 9, 3, 4, m->widths[0], s);
     launch_tconv_phase_pack(Wp(m, "fc7_conv2d_trans/kernel"), m->d_tph[0], 4, 2, m->C, s);
     launch_tconv_phase_pack(Wp(m, "fc7_pool4_conv2d_trans/kernel"), m->d_tph[1], 4, 2, m->C, s);
@@ -1291,6 +1309,7 @@ bool bf16_conv_layer(fcn8s_model* m, const char* tag, const char* wname, const c
         else if (c.grow(wneed * sizeof(unsigned short), s, &m->ws_allocs)) wbuf = c;       // (out of memory: the shared copy, rebuilt per pass)
     }
     if (!have) { ProfScope ps(m, "weight_relayout", 0, 6.0 * K * cout);
+                 prof_derived(m, big ? "w_to_bf16_t_kernel" : "w_to_bf16_tiles_kernel");
                  if (big) launch_w_to_bf16_t(Wp(m, wname), wbuf, K, cout, s); else launch_w_to_bf16_tiles(Wp(m, wname), wbuf, K, cout, s); }
     const int pad = big ? (k - 1) / 2 : 0;
     const size_t nin = (size_t)N * (h + 2 * pad) * (w + 2 * pad) * cin;
@@ -1311,7 +1330,7 @@ bool bf16_conv_layer(fcn8s_model* m, const char* tag, const char* wname, const c
     }
     if (!out) return false;
     if (!allow_small || cin % 32 || cout % 128) return false;
-    if (big) { launch_w_to_bf16_tiles(Wp(m, wname), m->d_wbf16, K, cout, s); wbuf = m->d_wbf16; }      // (could not take the 256 path after all)
+    if (big) { prof_derived(m, "w_to_bf16_tiles_kernel"); launch_w_to_bf16_tiles(Wp(m, wname), m->d_wbf16, K, cout, s); wbuf = m->d_wbf16; }      // (could not take the 256 path after all)
     Bf16ConvArgs a{};
     a.x = in; a.wt = wbuf; a.bias = Wp(m, bname); a.y = out;
     if (nin % 8 == 0 && m->d_abf16) {         // activations to bf16 once: the GEMM re-reads each A tile Cout/128 times
@@ -1389,7 +1408,7 @@ void wino_backward_operands(fcn8s_model* m, const char* layer, const float* x, c
     const std::string key = std::string(layer) + "#" + std::to_string(tile);
     if ((KS == 3 && tile == 6) || (KS == 7 && tile == 4)) {
         DeviceBuf<float>& tu = m->u_train[key];
-        if (tu.grow((size_t)P * Kg * Cout * sizeof(float), s)) { ProfScope ps(m, "wino_transform", 0, (double)(KS * KS + P * nsub2) * 4 * Cin * Cout); launch_wino_filter(tile, wk, tu, Cin, Cout, KS, s); }
+        if (tu.grow((size_t)P * Kg * Cout * sizeof(float), s)) { ProfScope ps(m, "wino_transform", 0, (double)(KS * KS + P * nsub2) * 4 * Cin * Cout); prof_derived(m, "wino_filter_kernel"); launch_wino_filter(tile, wk, tu, Cin, Cout, KS, s); }
         else m->u_train.erase(key);
     }
 }
@@ -1524,9 +1543,10 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                                         "(Engine.calibrate_fp8 / FCN8s.calibrate_fp8) or restore one with fcn8s_fp8_set_calibration first");
     if (fp8) m->q8_filled.clear();
     bool guard_pending = false;
-    if (m->frozen && !m->u_cache.empty() && !m->banks_stale) {
+    if (m->frozen && keeps_banks(m) && !m->banks_stale) {
         // the caller promised constant parameters; a cheap strided fingerprint catches the promise being broken through a side
-        // door (a torch optimizer or copy_ over views of ext_params): the cached filter banks are then rebuilt instead of reused.
+        // door (a torch optimizer or copy_ over views of ext_params): the kept banks -- Winograd filters, bf16 kernels, e4m3 weights --
+        // are then rebuilt instead of reused.
         // The check does not hold the pass up: the fingerprint is taken first on the stream, the pass is enqueued behind it with the kept
         // banks, and the host compares when the (long finished) copy is looked at -- at the end of this function; a mismatch repeats the pass.
         launch_fingerprint(m->d_params, (long long)m->total, m->d_fp, s);
@@ -1543,7 +1563,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
             if (fp != m->frozen_fp) drop_banks(m);
         }
     }
-    const bool fill_fp = m->frozen && (m->u_cache.empty() || m->banks_stale);       // (banks_stale: kept storage, contents to be rebuilt)
+    const bool fill_fp = m->frozen && (!keeps_banks(m) || m->banks_stale);          // (banks_stale: kept storage, contents to be rebuilt)
     if (!m->frozen || fill_fp) prepare_forward_weights(m);        // frozen and the kept banks still valid: so are the padded / phase-packed kernels
     m->fwd_train = train;
     m->fft6_ready.clear(); m->fft6_xf.clear(); m->fft6_dyf.clear();
@@ -2214,7 +2234,7 @@ const char* fcn8s_last_error(const fcn8s_model* m) { return m ? m->err.c_str() :
 int fcn8s_freeze_params(fcn8s_model* m, int frozen)
 {
     if (!m) return FCN8S_ERR_BAD_ARG;
-    if (!frozen || !m->frozen) { drop_banks(m); m->w8_valid.clear(); }          // entering or leaving: start from an empty cache
+    if (!frozen || !m->frozen) drop_banks(m);          // entering or leaving: start from an empty cache
     m->frozen = frozen != 0;
     return FCN8S_OK;
 }
@@ -2384,7 +2404,7 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
     HIPCHK(m, hipStreamSynchronize(m->stream));
     *slot = (k == "winograd_fc6" || k == "fc6_fft" || k == "tconv_gemm") ? (value != 0) : (int)value;
     drop_arena(m);
-    drop_banks(m); m->u_train.clear();
+    drop_banks(m, true); m->u_train.clear();
     return FCN8S_OK;
 }
 int fcn8s_get_option(const fcn8s_model* m, const char* key, int64_t* value)

@@ -354,9 +354,13 @@ int     fcn8s_set_opt_state(fcn8s_model* m, const float* host_m, const float* ho
 /* ---- introspection for parity tests ----------------------------------------- *
  * names: "pool3","pool4","fc7","logits", "conv1_1"... (post-ReLU activations)     */
 /* frozen = 1: the caller promises that the parameters stay constant (an evaluate() / predict loop, the reference's sessions never
- * train inside one, fcn8s_tensorflow.py:660-697, :743-770); the library then keeps derived tensors (Winograd-transformed filter
- * banks) across calls instead of rebuilding them per forward pass.  Any library call that changes parameters or starts a training
- * pass unfreezes; whoever writes into an external parameter buffer (fcn8s_config.ext_params) must call this with 0 first. */
+ * train inside one, fcn8s_tensorflow.py:660-697, :743-770); the library then keeps the tensors it derives from them across calls
+ * instead of rebuilding them per forward pass: the Winograd-transformed filter banks (per layer and tile), the bf16 relayouts of the
+ * kernels (the bf16 modes, FCN8S_PREC_BF16_TRAIN included), the e4m3 weight banks (FCN8S_PREC_FP8_INFER), and the padded conv1_1 /
+ * phase-packed transposed-convolution kernels.  Any library call that changes parameters or starts a training pass unfreezes; whoever
+ * writes into an external parameter buffer (fcn8s_config.ext_params) must call this with 0 first.  A writer who does not is caught by
+ * a fingerprint of the parameter buffer, taken at the head of every frozen pass that reuses a kept tensor of ANY of these kinds and
+ * compared at its end (off the critical path): on a mismatch all of them are dropped and the pass is run again without them. */
 int fcn8s_freeze_params(fcn8s_model* m, int frozen);
 
 /* Arithmetic mode (FCN8S_PREC_*); not in the reference, which is fp32 throughout.
@@ -459,7 +463,11 @@ uint32_t fcn8s_crc32c(const void* data, size_t nbytes, uint32_t crc);
 /* ---- in-library HIP-event timing of kernel groups (bench.py roofline) -------- *
  * groups: "conv3x3_fwd","conv3x3_dgrad","conv3x3_wgrad","fc_fwd","fc_dgrad","fc_wgrad",...
  * Fills total milliseconds, number of launches, algorithmic flops and bytes.
- * fcn8s_profile_enable(m, 2) splits the conv groups per layer ("conv3x3_fwd:conv1_2").  */
+ * fcn8s_profile_enable(m, 2) splits the conv groups per layer ("conv3x3_fwd:conv1_2"), and adds count-only groups "derived:<build step>"
+ * (launches only; ms, flops and bytes are 0 -- skip them before dividing by ms) for every tensor a forward pass (re)builds from the
+ * parameters alone.  The suffix names the build step, written at its call site, not necessarily one kernel: "derived:wino_filter_kernel",
+ * "derived:w_to_bf16_t_kernel", "derived:w_to_bf16_tiles_kernel", "derived:prepare_forward_weights" (the padded conv1_1 and phase-packed
+ * transposed-convolution kernels, four launches) -- what the later passes of a frozen model report as zero.  */
 int fcn8s_profile_enable(fcn8s_model* m, int on);
 int fcn8s_profile_reset(fcn8s_model* m);
 int fcn8s_profile_num_groups(const fcn8s_model* m);

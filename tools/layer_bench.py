@@ -30,7 +30,7 @@ def main():
     torch.cuda.synchronize()
     tot = 0
     for k, v in e.profile_results().items():
-        if k.startswith("kernel:"):
+        if k.startswith("kernel:") or v["ms"] <= 0:          # (a second view of the same launches; count-only groups such as "derived:...")
             continue
         ms = v["ms"] / args.steps; tot += ms
         extra = "%7.1f TF/s" % (v["flops"] / v["ms"] / 1e9) if v["flops"] else "%7.1f GB/s" % (v["bytes"] / v["ms"] / 1e6)
