@@ -78,6 +78,11 @@ SIGNATURES = {
     "fcn8s_comm_allreduce_metrics": (_i, [_p]),
     "fcn8s_apply_update": (_i, [_p, _i, _f, _f]),
     "fcn8s_read_loss": (_i, [_p, _fp]),
+    "fcn8s_accumulate_bucket": (_i, [_p, _i, _i]),
+    "fcn8s_accumulate_pending": (_i, [_p]),
+    "fcn8s_accumulate_discard": (_i, [_p]),
+    "fcn8s_set_grad_clip": (_i, [_p, _f]),
+    "fcn8s_get_update_stats": (_i, [_p, _fp, _fp, _fp, _i64p]),
     "fcn8s_set_loss": (_i, [_p, _p, _i, _f, _i64]),
     "fcn8s_get_loss_stats": (_i, [_p, _i64p, _i64p, _fp]),
     "fcn8s_set_lovasz": (_i, [_p, _f, _f, _i, _i, _p, _i]),
@@ -144,6 +149,10 @@ SIGNATURES = {
     "fcn8s_op_boundary_pair": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "fcn8s_op_tf_adam": (_i, [_p, _p, _p, _p, _p, _i64, _i, _f, _f, _f, _f, _f]),
     "fcn8s_op_sgd_momentum": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f]),
+    "fcn8s_op_grad_accumulate": (_i, [_p, _p, _p, _i64, _i]),
+    "fcn8s_op_grad_norm": (_i, [_p, _p, _i64, _f, _f, _p]),
+    "fcn8s_op_tf_adam_dev": (_i, [_p, _p, _p, _p, _p, _i64, _i, _f, _f, _f, _f, _p]),
+    "fcn8s_op_sgd_momentum_dev": (_i, [_p, _p, _p, _p, _i64, _f, _f, _p]),
 }
 
 

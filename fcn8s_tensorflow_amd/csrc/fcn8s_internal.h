@@ -283,6 +283,18 @@ void launch_tf_adam(float* theta, const float* g, float* m, float* v, long long 
                     float lr_t, float b1, float b2, float eps, float gscale, hipStream_t s);
 void launch_sgd_momentum(float* theta, const float* g, float* buf, long long n,
                          float lr, float mom, float gscale, hipStream_t s);
+// optim.hip: gradient accumulation over micro-batches, the global-norm clip and the optimizers that read their scale from the device
+void launch_grad_accumulate(float* dst, const float* src, long long n, int mode, hipStream_t s);   // mode 0: dst = src, 1: dst += src; any float alignment
+constexpr int kGradNormBlocks = 2048;                                      // blocks (and partials) of the norm pass: a constant, never the device's CU count
+struct UpdateStats { float norm, clip, scale; int ok; unsigned long long skipped; };      // what grad_norm_finalize writes (a model's slab)
+// S = sum (double)g^2 through `partials` (kGradNormBlocks doubles) in a fixed order; then {norm, c, s, ok} and, if !ok, ++skipped into `out`.
+// as_floats: `out` is float[5] = {norm, c, s, ok (1.0f / 0.0f), 0} instead (fcn8s_op_grad_norm); the word at index 3 is non-zero exactly when ok
+void launch_grad_norm(const float* g, long long n, float grad_scale, float max_norm, double* partials, void* out, bool as_floats, hipStream_t s);
+// launch_tf_adam / launch_sgd_momentum with gscale = *s_dev; *ok_dev == 0: nothing is touched
+void launch_tf_adam_dev(float* theta, const float* g, float* m, float* v, long long n,
+                        float lr_t, float b1, float b2, float eps, const float* s_dev, const int* ok_dev, hipStream_t s);
+void launch_sgd_momentum_dev(float* theta, const float* g, float* buf, long long n,
+                             float lr, float mom, const float* s_dev, const int* ok_dev, hipStream_t s);
 // weight re-layouts (run once per step, tiny next to the convs)
 void launch_flip_transpose(const float* w, float* wt, int taps, int Cin, int Cout, hipStream_t s); // wt[T-1-t][co][ci] = w[t][ci][co]
 void launch_pad_cin(const float* w, float* w4, int taps, int Cin, int Cinp, int Cout, hipStream_t s);

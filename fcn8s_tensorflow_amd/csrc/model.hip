@@ -214,6 +214,12 @@ struct fcn8s_model {
     // d_terms = the unscaled terms of the last training loss (ce, lovasz, l2; right behind d_lastbias), have_terms once a training loss ran
     bool lov_on = false, have_terms = false; float lov_ce = 1.f, lov_w = 0.f; int lov_per_image = 0, lov_all = 0;
     DeviceBuf<uint8_t> d_lovmask; int lov_nmask = 0; DeviceBuf<char> lov_ws; float* d_terms = nullptr;
+    // fcn8s_accumulate_bucket: the accumulator (total floats, the gradient buffer's buckets; grown at the first fold -- a "workspace_allocation" --
+    // and kept until the model goes), per bucket the micro-batches folded and not yet flushed, and whether this backward pass's bucket was taken
+    DeviceBuf<float> d_acc; int acc_k[FCN8S_MAX_BUCKETS] = {0}; bool acc_taken[FCN8S_MAX_BUCKETS] = {false};
+    // fcn8s_set_grad_clip: max_norm (0 = off); upd_ws = UpdateStats + the norm's kGradNormBlocks partial sums, made by fcn8s_set_grad_clip;
+    // last_update_clipped: the last fcn8s_apply_update ran the norm pass (fcn8s_get_update_stats)
+    float max_norm = 0.f; DeviceBuf<char> upd_ws; bool last_update_clipped = false;
     DeviceBuf<unsigned long long> d_conf;
     double loss_sum = 0; int64_t loss_cnt = 0;
     float keep_prob = 1.f, l2_rate = 0.f;
@@ -264,6 +270,7 @@ int deferred_rc(fcn8s_model* m)
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 const int kNumBuckets = 4;      // (what fcn8s_num_buckets reports; callers size nothing by a compile-time constant)
+const size_t kUpdPartialsOff = 32;      // fcn8s_model::upd_ws: UpdateStats, then (from this byte on) the norm pass's partial sums
 
 void build_param_table(int C, const int widths[7], int fc6k, std::vector<ParamInfo>& out, size_t& total,
                        size_t boff[FCN8S_MAX_BUCKETS], size_t bn[FCN8S_MAX_BUCKETS])
@@ -2521,6 +2528,7 @@ int fcn8s_forward_loss(fcn8s_model* m, const void* images, int dtype, const uint
     rc = deferred_rc(m); if (rc) return rc;
     rc = compute_loss(m, lab, l2_rate, true); if (rc) return rc;
     m->next_bucket = 0;
+    for (int b = 0; b < kNumBuckets; ++b) m->acc_taken[b] = false;
     HIPCHK(m, hipGetLastError());
     return FCN8S_OK;
 }
@@ -2839,25 +2847,101 @@ int fcn8s_comm_allreduce_metrics(fcn8s_model* m)
     return fcn8s_metrics_set_raw(m, conf.data(), h[cc], (int64_t)llround(h[cc + 1]));
 }
 
+int fcn8s_accumulate_bucket(fcn8s_model* m, int bucket, int flush)
+{
+    if (!m || bucket < 0 || bucket >= kNumBuckets) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_accumulate_bucket: bad bucket");
+    if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_accumulate_bucket");
+    if (!m->have_loss || !m->train_mode || bucket >= m->next_bucket || !m->bucket_final[bucket])
+        return fail(m, FCN8S_ERR_STATE, "fcn8s_accumulate_bucket: the bucket's gradients are not queued yet (call fcn8s_backward_bucket(bucket) after fcn8s_forward_loss first)");
+    if (m->acc_taken[bucket]) return fail(m, FCN8S_ERR_STATE, "fcn8s_accumulate_bucket: this backward pass's bucket has already been folded or flushed");
+    if (m->comm_pending[bucket]) return fail(m, FCN8S_ERR_STATE, "fcn8s_accumulate_bucket: this bucket is being all-reduced");
+    const size_t off = m->bucket_off[bucket]; const long long n = (long long)m->bucket_n[bucket];
+    if (!flush) {
+        if (!m->d_acc.grow(m->total * sizeof(float), m->stream, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "fcn8s_accumulate_bucket: the accumulator cannot be allocated");
+        const int mode = m->acc_k[bucket] ? 1 : 0;
+        { ProfScope ps(m, "grad_accumulate", 0, (mode ? 12.0 : 8.0) * n); launch_grad_accumulate(m->d_acc + off, m->d_grads + off, n, mode, m->stream); }
+        m->acc_k[bucket] += 1;
+    } else if (m->acc_k[bucket] > 0) {
+        { ProfScope ps(m, "grad_accumulate", 0, 12.0 * n); launch_grad_accumulate(m->d_grads + off, m->d_acc + off, n, 1, m->stream); }
+        m->acc_k[bucket] = 0;
+        mark_bucket_final(m, bucket, m->stream);          // the flush is now the last kernel that writes the bucket
+    }
+    m->acc_taken[bucket] = true;
+    HIPCHK(m, hipGetLastError());
+    return FCN8S_OK;
+}
+
+int fcn8s_accumulate_pending(const fcn8s_model* m)
+{
+    int k = 0;
+    if (m) for (int b = 0; b < kNumBuckets; ++b) k = m->acc_k[b] > k ? m->acc_k[b] : k;
+    return k;
+}
+
+int fcn8s_accumulate_discard(fcn8s_model* m)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    for (int b = 0; b < kNumBuckets; ++b) m->acc_k[b] = 0;
+    return FCN8S_OK;
+}
+
+int fcn8s_set_grad_clip(fcn8s_model* m, float max_norm)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!(max_norm >= 0.f)) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_grad_clip: max_norm must be 0 (off) or in (0, +inf]");
+    if (max_norm > 0.f && !m->upd_ws) {
+        if (!m->upd_ws.grow(kUpdPartialsOff + kGradNormBlocks * sizeof(double), m->stream, nullptr, true)) return fail(m, FCN8S_ERR_OOM, "fcn8s_set_grad_clip: out of device memory");
+    }
+    m->max_norm = max_norm;
+    return FCN8S_OK;
+}
+
+int fcn8s_get_update_stats(fcn8s_model* m, float* norm, float* clip_coef, float* scale, int64_t* skipped)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!m->last_update_clipped || !m->upd_ws)
+        return fail(m, FCN8S_ERR_STATE, "fcn8s_get_update_stats: the last update ran without a clip setting (fcn8s_set_grad_clip)");
+    UpdateStats st;
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(&st, m->upd_ws, sizeof st, hipMemcpyDeviceToHost));
+    if (norm) *norm = st.norm;
+    if (clip_coef) *clip_coef = st.clip;
+    if (scale) *scale = st.scale;
+    if (skipped) *skipped = (int64_t)st.skipped;
+    return FCN8S_OK;
+}
+
 int fcn8s_apply_update(fcn8s_model* m, int optimizer, float lr, float grad_scale)
 {
     if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_apply_update");
+    if (fcn8s_accumulate_pending(m) > 0)
+        return fail(m, FCN8S_ERR_STATE, "fcn8s_apply_update: micro-batches are folded and not flushed (fcn8s_accumulate_bucket(m, b, 1) on the last one, or fcn8s_accumulate_discard)");
     if (m && m->frozen) fcn8s_freeze_params(m, 0);      // parameters are about to change (or a training pass starts): leave the frozen state
     fp8_clear_calibration(m);
     if (!m) return FCN8S_ERR_BAD_ARG;
     if (m->comm_world > 1 && (m->comm || m->comm_failed.load())) { int rch = comm_wait_host(m, "fcn8s_apply_update"); if (rch) return rch; }
     { int rcw = fcn8s_comm_wait(m); if (rcw) return rcw; }      // gradient buckets still being all-reduced by the library's own communicator
     const int64_t t = m->step + 1;
+    // the clip: norm, c, s = grad_scale c and the guard's verdict stay on the device; the optimizer reads them there (no host round trip)
+    const bool clip = m->max_norm > 0.f && (optimizer == FCN8S_OPT_TF_ADAM || optimizer == FCN8S_OPT_SGD_MOMENTUM || optimizer == FCN8S_OPT_NONE);
+    UpdateStats* st = (UpdateStats*)m->upd_ws.get();
+    if (clip) {
+        ProfScope ps(m, "grad_norm", 0, 4.0 * m->total);
+        launch_grad_norm(m->d_grads, (long long)m->total, grad_scale, m->max_norm, (double*)(m->upd_ws + kUpdPartialsOff), st, false, m->stream);
+    }
+    m->last_update_clipped = clip;
     if (optimizer == FCN8S_OPT_TF_ADAM) {
         int rc = ensure_opt_state(m); if (rc) return rc;
         const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
         const float lr_t = lr * (float)std::sqrt(1.0 - std::pow((double)b2, (double)t)) / (float)(1.0 - std::pow((double)b1, (double)t));
         ProfScope ps(m, "adam", 0, 28.0 * m->total);
-        launch_tf_adam(m->d_params, m->d_grads, m->d_m, m->d_v, (long long)m->total, lr_t, b1, b2, eps, grad_scale, m->stream);
+        if (clip) launch_tf_adam_dev(m->d_params, m->d_grads, m->d_m, m->d_v, (long long)m->total, lr_t, b1, b2, eps, &st->scale, &st->ok, m->stream);
+        else launch_tf_adam(m->d_params, m->d_grads, m->d_m, m->d_v, (long long)m->total, lr_t, b1, b2, eps, grad_scale, m->stream);
     } else if (optimizer == FCN8S_OPT_SGD_MOMENTUM) {
         int rc = ensure_opt_state(m); if (rc) return rc;
         ProfScope ps(m, "sgd_momentum", 0, 20.0 * m->total);
-        launch_sgd_momentum(m->d_params, m->d_grads, m->d_m, (long long)m->total, lr, 0.9f, grad_scale, m->stream);
+        if (clip) launch_sgd_momentum_dev(m->d_params, m->d_grads, m->d_m, (long long)m->total, lr, 0.9f, &st->scale, &st->ok, m->stream);
+        else launch_sgd_momentum(m->d_params, m->d_grads, m->d_m, (long long)m->total, lr, 0.9f, grad_scale, m->stream);
     } else if (optimizer != FCN8S_OPT_NONE) return fail(m, FCN8S_ERR_BAD_ARG, "unknown optimizer");
     m->step = t;
     HIPCHK(m, hipGetLastError());
@@ -2982,11 +3066,16 @@ int fcn8s_train_step(fcn8s_model* m, const void* images, int dtype, const uint8_
     // a model with a communicator of more than one rank trains data-parallel through this entry point too: the bucket-by-bucket
     // backward pass, every bucket all-reduced as soon as it is final, 1/world in the update (a C caller must never get silently diverging replicas)
     const bool dp = (m->comm || m->comm_failed.load()) && m->comm_world > 1;
+    // micro-batches folded before this call (fcn8s_accumulate_bucket): this is the last one -- every bucket is flushed in front of its exchange
+    const int pending = fcn8s_accumulate_pending(m);
     for (int b = 0; b < kNumBuckets; ++b) {
         rc = fcn8s_backward_bucket(m, b); if (rc) return rc;
+        if (pending) { rc = fcn8s_accumulate_bucket(m, b, 1); if (rc) return rc; }
         if (dp) { rc = fcn8s_allreduce_bucket(m, b); if (rc) return rc; }
     }
-    rc = fcn8s_apply_update(m, FCN8S_OPT_TF_ADAM, lr, dp ? 1.f / (float)m->comm_world : 1.f); if (rc) return rc;
+    float gscale = dp ? 1.f / (float)m->comm_world : 1.f;
+    if (pending) gscale /= (float)(pending + 1);
+    rc = fcn8s_apply_update(m, FCN8S_OPT_TF_ADAM, lr, gscale); if (rc) return rc;
     if (loss_out) { rc = fcn8s_read_loss(m, loss_out); if (rc) return rc; }
     if (step_out) *step_out = m->step;
     return FCN8S_OK;
@@ -3933,5 +4022,32 @@ int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* mm, floa
 }
 int fcn8s_op_sgd_momentum(void* stream, float* theta, const float* g, float* buf, int64_t n, float lr, float mom, float gs)
 { launch_sgd_momentum(theta, g, buf, n, lr, mom, gs, (hipStream_t)stream); OPCHK(); return FCN8S_OK; }
+int fcn8s_op_grad_accumulate(void* stream, float* dst, const float* src, int64_t n, int mode)
+{
+    if (!dst || !src || n < 0 || (mode != 0 && mode != 1)) return fail(nullptr, FCN8S_ERR_BAD_ARG, "grad_accumulate: bad argument (null pointer, n < 0, or mode outside {0, 1})");
+    launch_grad_accumulate(dst, src, n, mode, (hipStream_t)stream); OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_grad_norm(void* stream, const float* g, int64_t n, float grad_scale, float max_norm, float* out5_dev)
+{
+    if (!g || !out5_dev || n < 0 || !(max_norm >= 0.f)) return fail(nullptr, FCN8S_ERR_BAD_ARG, "grad_norm: bad argument (null pointer, n < 0, or max_norm negative / NaN)");
+    DeviceBuf<double> partials;                          // (freed on return: behind the stream's synchronise)
+    if (!partials.grow(kGradNormBlocks * sizeof(double), (hipStream_t)stream)) return fail(nullptr, FCN8S_ERR_OOM, "grad_norm: out of device memory");
+    launch_grad_norm(g, n, grad_scale, max_norm, partials, out5_dev, true, (hipStream_t)stream);
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, FCN8S_ERR_HIP, hipGetErrorString(e));
+    OPCHK(); return FCN8S_OK;
+}
+// (out5_dev[3] is 1.0f or 0.0f: as an int it is non-zero exactly when the guard said ok)
+int fcn8s_op_tf_adam_dev(void* stream, float* theta, const float* g, float* mm, float* v, int64_t n, int t, float lr, float b1, float b2, float eps, const float* out5)
+{
+    if (!out5) return fail(nullptr, FCN8S_ERR_BAD_ARG, "tf_adam_dev: null out5_dev");
+    const float lr_t = lr * (float)std::sqrt(1.0 - std::pow((double)b2, (double)t)) / (float)(1.0 - std::pow((double)b1, (double)t));
+    launch_tf_adam_dev(theta, g, mm, v, n, lr_t, b1, b2, eps, out5 + 2, (const int*)(out5 + 3), (hipStream_t)stream); OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_sgd_momentum_dev(void* stream, float* theta, const float* g, float* buf, int64_t n, float lr, float mom, const float* out5)
+{
+    if (!out5) return fail(nullptr, FCN8S_ERR_BAD_ARG, "sgd_momentum_dev: null out5_dev");
+    launch_sgd_momentum_dev(theta, g, buf, n, lr, mom, out5 + 2, (const int*)(out5 + 3), (hipStream_t)stream); OPCHK(); return FCN8S_OK;
+}
 
 }  // extern "C"

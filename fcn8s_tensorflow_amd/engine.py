@@ -22,6 +22,7 @@ import numpy as np
 from . import _lib as L
 from . import crf as crf_mod
 from . import loss as loss_mod
+from . import optim as optim_mod
 from . import tta
 from .dp import BucketReducer
 
@@ -127,6 +128,7 @@ class Engine:
         self._bad = None
         self.loss_config = None              # set_loss: the training loss's configuration (None = the reference's mean)
         self.lovasz_config = None            # set_lovasz: the Lovász-softmax term's configuration (None = off)
+        self.grad_clip = None                # set_grad_clip: the global-norm clip's max_norm (None = off; inf = the non-finite guard alone)
         self.replica_check_every = 100      # data-parallel runs: compare global step + parameter checksum across ranks every so many steps (0 = never)
         self._sync_stream()
 
@@ -466,17 +468,63 @@ class Engine:
         L.check(L.lib.fcn8s_get_loss_stats(self.h, C.byref(v), C.byref(kp), C.byref(t)), self.h)
         return dict(valid=int(v.value), kept=int(kp.value), threshold=float(t.value))
 
+    def set_grad_clip(self, max_norm):
+        """The update's global-norm clip (fcn8s_set_grad_clip; definitions in include/fcn8s_hip.h, restated in optim.py): every update
+        first takes the norm of the (all-reduced, scaled) gradient on the device and multiplies the gradient by
+        max_norm / max(norm, max_norm) inside the optimizer kernel; an update whose norm is not finite is skipped.  `max_norm` in
+        (0, inf] -- inf = the guard alone --, None or 0 = off.  No host round trip: read the numbers with update_stats()."""
+        v = optim_mod.validate_clip(max_norm)
+        L.check(L.lib.fcn8s_set_grad_clip(self.h, v), self.h)
+        self.grad_clip = v if v > 0 else None
+
+    def update_stats(self):
+        """norm, clip_coef and scale of the last update and the updates skipped so far (fcn8s_get_update_stats; synchronises)."""
+        n = C.c_float(); c = C.c_float(); sc = C.c_float(); k = C.c_int64()
+        L.check(L.lib.fcn8s_get_update_stats(self.h, C.byref(n), C.byref(c), C.byref(sc), C.byref(k)), self.h)
+        return dict(norm=float(n.value), clip_coef=float(c.value), scale=float(sc.value), skipped=int(k.value))
+
+    @property
+    def pending_micro_batches(self):
+        """Micro-batches accumulated (accumulate_step) and not yet applied by a train_step."""
+        return int(L.lib.fcn8s_accumulate_pending(self.h))
+
+    def discard_accumulated(self):
+        """Forget the accumulated micro-batches (the accumulator's memory stays)."""
+        L.check(L.lib.fcn8s_accumulate_discard(self.h), self.h)
+
+    def accumulate_step(self, images, labels, keep_prob=0.5, l2_rate=0.0, fetch_loss=True):
+        """One micro-batch that is not the last of its update: forward, backward, and every gradient bucket folded into the model's
+        accumulator (fcn8s_accumulate_bucket).  No exchange, no update, the global step stays.  The train_step that follows is the
+        last micro-batch: it adds the accumulated gradients to its own in front of each bucket's exchange and divides its gradient
+        scale by the number of micro-batches.  Returns the micro-batch's loss (None without fetch_loss)."""
+        self._sync_stream()
+        ka, pi, dt, pl, where, nhw = self._inputs(images, labels)
+        N, H, W = (int(x) for x in nhw)
+        L.check(L.lib.fcn8s_forward_loss(self.h, pi, dt, pl, N, H, W, float(keep_prob), float(l2_rate), where), self.h)
+        self._release(ka)
+        for b in range(self.num_buckets):
+            L.check(L.lib.fcn8s_backward_bucket(self.h, b), self.h)
+            L.check(L.lib.fcn8s_accumulate_bucket(self.h, b, 0), self.h)
+        if not fetch_loss:
+            return None
+        loss = C.c_float(0.0)
+        L.check(L.lib.fcn8s_read_loss(self.h, C.byref(loss)), self.h)
+        return float(loss.value)
+
     def train_step(self, images, labels, learning_rate, keep_prob=0.5, l2_rate=0.0,
                    optimizer=L.OPT_TF_ADAM, fetch_loss=True, reduce=True):
         """sess.run([train_op, total_loss, global_step]) (fcn8s_tensorflow.py:554-572).
-        `reduce=False` skips the gradient exchange of a data-parallel run (measurement only: bench.py's local-only leg)."""
+        `reduce=False` skips the gradient exchange of a data-parallel run (measurement only: bench.py's local-only leg).
+        With micro-batches pending (accumulate_step) this is the last one of the update; with a clip set (set_grad_clip) the update is
+        clipped.  Both take the split-phase route below; without either the step is what it was."""
         self._sync_stream()
         ka, pi, dt, pl, where, nhw = self._inputs(images, labels)
         N, H, W = (int(x) for x in nhw)
         ws = self.world_size
         loss = C.c_float(0.0)
         always = bool(getattr(self, "dp_always", False)) and _dist() is not None
-        if ws == 1 and optimizer == L.OPT_TF_ADAM and not always and not self.native_comm:
+        pending = self.pending_micro_batches
+        if ws == 1 and optimizer == L.OPT_TF_ADAM and not always and not self.native_comm and not pending and self.grad_clip is None:
             step = C.c_int64(0)
             L.check(L.lib.fcn8s_train_step(self.h, pi, dt, pl, N, H, W, float(learning_rate), float(keep_prob),
                                            float(l2_rate), where, None, C.byref(step)), self.h)
@@ -495,6 +543,8 @@ class Engine:
         # leave in that order, each while the rest of the backward pass runs
         for b in range(self.num_buckets):
             L.check(L.lib.fcn8s_backward_bucket(self.h, b), self.h)
+            if pending:                                    # g[b] += acc[b]; the bucket's event moves behind the flush kernel
+                L.check(L.lib.fcn8s_accumulate_bucket(self.h, b, 1), self.h)
             if reduce:
                 if self.native_comm:
                     L.check(L.lib.fcn8s_allreduce_bucket(self.h, b), self.h)
@@ -502,6 +552,8 @@ class Engine:
                     red.reduce_bucket(b)
         red.wait()
         scale = (1.0 / self.comm_world) if (self.native_comm and reduce) else (red.grad_scale() if reduce else 1.0)
+        if pending:
+            scale = scale / (pending + 1)
         L.check(L.lib.fcn8s_apply_update(self.h, optimizer, float(learning_rate), scale), self.h)     # (waits for the native all-reduces itself)
         if trace is not None:
             t1 = self.torch.cuda.Event(enable_timing=True); t1.record()

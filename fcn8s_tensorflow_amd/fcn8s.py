@@ -49,6 +49,7 @@ except Exception:  # pragma: no cover
 from . import _lib as L
 from . import crf as crf_mod
 from . import loss as loss_mod
+from . import optim as optim_mod
 from . import tf_bundle
 from .engine import Engine, padded_classes
 
@@ -209,7 +210,9 @@ class FCN8s:
               lovasz_weight=0.0,
               lovasz_per_image=False,
               lovasz_classes='present',
-              ce_weight=1.0):
+              ce_weight=1.0,
+              accumulation_steps=1,
+              clip_global_norm=None):
         '''Trains the model; arguments as fcn8s_tensorflow.py:424-503.  Summaries are written as TensorBoard
         event files (`<summaries_dir>/<summaries_name>[_eval]/events.out.tfevents.*`: total_loss, learning_rate and
         mean / stddev / max / min / histogram of the ten watched weight-bias pairs, :331-366) and, for reading
@@ -219,7 +222,12 @@ class FCN8s:
         reference's loss, and the previous loss configuration is restored when train() returns or raises.
         `lovasz_weight`, `lovasz_per_image`, `lovasz_classes` ('present', 'all' or a list of class ids) and `ce_weight` add the
         Lovász-softmax term for the duration of the call (Engine.set_lovasz, loss.py: ce_weight * cross-entropy + lovasz_weight * Lovász);
-        the evaluations keep reporting the reference's loss, and the previous configuration is restored when train() returns or raises.'''
+        the evaluations keep reporting the reference's loss, and the previous configuration is restored when train() returns or raises.
+        `accumulation_steps` = A >= 1: an update consumes A batches from the generator (Engine.accumulate_step for the first A - 1,
+        Engine.train_step for the last; optim.py), its gradient is their mean and its reported loss the mean of their losses;
+        `steps_per_epoch`, the global step, the learning-rate schedule, `summaries_frequency` and the saves all count updates.
+        `clip_global_norm` (positive; inf = skip non-finite updates only) clips every update's gradient by its global norm for the duration
+        of the call (Engine.set_grad_clip); `grad_norm` and `clip_coef` then join the recorded scalars, on the steps that are recorded.'''
         if self.engine.precision == 'fp8_infer':
             raise ValueError("The 'fp8_infer' precision is inference only; switch the engine to another precision "
                              "(e.g. model.engine.set_precision('bf16_train')) before training.")
@@ -230,6 +238,7 @@ class FCN8s:
         custom_lovasz = lovasz_weight != 0 or ce_weight != 1.0
         if custom_lovasz:
             loss_mod.validate_lovasz(lovasz_weight, ce_weight, lovasz_per_image, lovasz_classes, self.engine.logical_classes)
+        accumulation_steps, max_norm = optim_mod.validate(accumulation_steps, clip_global_norm)
         if eval_dataset not in ('train', 'val'):
             raise ValueError("`eval_dataset` must be one of 'train' or 'val', but is '{}'.".format(eval_dataset))
         if eval_dataset == 'val' and (val_generator is None or val_steps is None):
@@ -254,7 +263,10 @@ class FCN8s:
 
         prev_loss = self.engine.loss_config
         prev_lovasz = self.engine.lovasz_config
+        prev_clip = self.engine.grad_clip
         try:
+            if max_norm:
+                self.engine.set_grad_clip(max_norm)
             if custom_loss:
                 self.engine.set_loss(class_weights, ohem_thresh, ohem_min_kept)
             if custom_lovasz:
@@ -262,7 +274,7 @@ class FCN8s:
             for epoch in range(1, epochs + 1):
                 self._run_epoch(train_generator, steps_per_epoch, learning_rate_schedule, keep_prob, l2_regularization,
                                 'Epoch {}/{}'.format(epoch, epochs), training_loss_display_averaging,
-                                train_log, summaries_frequency)
+                                train_log, summaries_frequency, accumulation_steps)
                 eval_epoch = epoch % eval_frequency == 0
 
                 if metrics and eval_epoch:
@@ -283,6 +295,10 @@ class FCN8s:
                         if self._improved(name, i):
                             self.best_metric_values[i] = self.metric_values[i]
         finally:
+            if self.engine.pending_micro_batches:      # an update that an exception cut short: its micro-batches must not leak into the next one
+                self.engine.discard_accumulated()
+            if max_norm:
+                self.engine.set_grad_clip(prev_clip)
             if custom_loss:
                 self.engine.set_loss(**(prev_loss or {}))
             if custom_lovasz:
@@ -291,21 +307,32 @@ class FCN8s:
                 if log is not None:
                     log.close()
 
-    def _run_epoch(self, generator, steps, schedule, keep_prob, l2_rate, title, window, log, log_every):
+    def _run_epoch(self, generator, steps, schedule, keep_prob, l2_rate, title, window, log, log_every, accumulation_steps=1):
         '''One epoch of train steps (fcn8s_tensorflow.py:542-590): a step runs with the schedule's value
-        at the global step before it; `training_loss` is the mean over the last `window` steps.'''
+        at the global step before it; `training_loss` is the mean over the last `window` steps.  With `accumulation_steps` = A > 1 a
+        step is one update over A batches: A - 1 accumulated micro-batches, then the train step; its loss is the mean of the A losses.'''
         recent = deque(maxlen=window)
         bar = trange(steps, file=sys.stdout, disable=self.engine.rank != 0)
         bar.set_description(title)
-        feed = _Feeder(self.engine, generator, steps)        # batch k+1 is decoded / staged / copied while step k runs
+        feed = _Feeder(self.engine, generator, steps * accumulation_steps)        # batch k+1 is decoded / staged / copied while step k runs
         try:
             for _ in bar:
                 lr = self._lr
+                micro = []
+                for _k in range(accumulation_steps - 1):
+                    images, labels = feed.next()
+                    micro.append(self.engine.accumulate_step(images, labels, keep_prob=keep_prob, l2_rate=l2_rate))
                 images, labels = feed.next()
                 loss, self.g_step = self.engine.train_step(images, labels, learning_rate=lr, keep_prob=keep_prob, l2_rate=l2_rate)
+                if micro:
+                    loss = float(np.mean(micro + [loss]))
                 self.variables_updated = True
                 if log is not None and (self.g_step - 1) % log_every == 0:
-                    log.add(self.g_step, total_loss=loss, learning_rate=lr)
+                    if self.engine.grad_clip is not None:      # (reading them synchronises: only on the steps that are recorded)
+                        st = self.engine.update_stats()
+                        log.add(self.g_step, total_loss=loss, learning_rate=lr, grad_norm=st['norm'], clip_coef=st['clip_coef'])
+                    else:
+                        log.add(self.g_step, total_loss=loss, learning_rate=lr)
                 recent.append(loss)
                 self.training_loss = float(np.mean(recent))
                 bar.set_postfix(ordered_dict={'loss': self.training_loss, 'learning rate': lr})

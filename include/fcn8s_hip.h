@@ -228,6 +228,45 @@ int fcn8s_get_loss_stats(fcn8s_model* m, int64_t* valid, int64_t* kept, float* t
 int fcn8s_set_lovasz(fcn8s_model* m, float ce_weight, float lovasz_weight, int per_image, int classes_all, const uint8_t* class_mask, int nmask);
 int fcn8s_get_loss_terms(fcn8s_model* m, float* ce, float* lovasz, float* l2);
 
+/* ---- the update: gradient accumulation over micro-batches, a global-norm clip and a non-finite guard (not in the reference, whose step is
+ * one batch, one tf.train.AdamOptimizer.minimize, fcn8s_tensorflow.py:256) ------------------------------------------------------------------
+ * Accumulation.  The model owns one accumulator acc of fcn8s_param_floats() floats, cut into the gradient buffer's buckets; it is allocated at
+ *   the first fold (one "workspace_allocation") and kept until fcn8s_destroy.  Bucket b has a pending count k_b >= 0.  After
+ *   fcn8s_backward_bucket(m, b) the caller makes ONE of two calls:
+ *     fold  (flush = 0; a micro-batch that is not the last): acc[b] = g[b] if k_b == 0, else acc[b] = acc[b] + g[b]; k_b += 1; g[b] untouched;
+ *     flush (flush = 1; the last micro-batch): g[b] = g[b] + acc[b]; k_b = 0.  With k_b == 0 it launches nothing.  The bucket's event is
+ *       recorded again behind the flush kernel, so fcn8s_bucket_wait and fcn8s_allreduce_bucket still wait for the last kernel that writes
+ *       the bucket: a data-parallel run exchanges once per update, on the last micro-batch, with the overlap it has without accumulation.
+ *   One fp32 add per element and call: after A micro-batches g = fl(fl(g1 + g2) + g3) ..., what NumPy float32 gives bit for bit.
+ *   Nothing is divided by A here: the caller passes grad_scale = 1 / (A * world) to the update as it passes 1 / world without accumulation.
+ *   The L2 term is in every micro-batch's g (A of them times 1/A: the big batch's).  For the default and the class-weighted loss (both with
+ *   denominator P) A micro-batches of n images at keep_prob = 1 are the batch of A n images up to fp32 summation order; OHEM and Lovász
+ *   select per micro-batch, as they select per rank.  Micro-batches may differ in shape and precision mode (the gradients are
+ *   parameter-sized fp32).  Profile group "grad_accumulate" (12 bytes per element and call, 8 for a first fold).
+ *   FCN8S_ERR_STATE: bucket b's fcn8s_backward_bucket has not run since the last fcn8s_forward_loss; a second fold / flush of b for the same
+ *   backward pass; the bucket is being all-reduced; fcn8s_apply_update while any k_b > 0 (parameters and step untouched: a forgotten flush
+ *   never loses gradients silently).  fcn8s_train_step flushes every bucket behind its backward call and divides its scale by (pending + 1).
+ * Clipping and the guard.  max_norm in (0, +inf], 0 = off (default).  When it is on, fcn8s_apply_update first computes on the device
+ *     S = sum_i (double)g_i^2 over the whole flat buffer, in a fixed order whatever "deterministic" says and on every device: 2048 blocks of
+ *         256 lanes; a lane adds the squares of its elements (in ascending index, stride 2048 * 256 float4) in double; lanes are summed per wave
+ *         by a shuffle tree, waves in index order; the 2048 block sums go to a slab, of which one block's lane t adds entries 8t .. 8t + 7 in
+ *         index order before the same tree.  No float atomics: two runs give the same bits.
+ *     norm = (float)(|grad_scale| * sqrt(S));   c = max_norm / fmaxf(norm, max_norm) in fp32 (tf.clip_by_global_norm; c = 1 for +inf);
+ *     s = grad_scale * c in fp32;               ok = isfinite(norm).
+ *   The optimizer kernel reads s and ok from device memory: gr = g * s where it computes g * grad_scale otherwise; if !ok it touches neither
+ *   the parameters nor the optimizer's slots and a device counter `skipped` goes up by one.  The global step (a host counter) advances either
+ *   way and the step does not synchronise.  max_norm = +inf therefore means "guard only".  norm <= max_norm gives s == grad_scale bit for
+ *   bit.  The norm is taken after the all-reduce: every replica computes the same s.  Profile group "grad_norm" (4 bytes per element).
+ *   The setting survives fcn8s_set_precision, fcn8s_set_option and freezing.  fcn8s_set_grad_clip: NaN or negative is FCN8S_ERR_BAD_ARG.
+ *   fcn8s_get_update_stats: norm, c, s of the last update and the updates skipped so far (synchronises); any pointer may be NULL;
+ *   FCN8S_ERR_STATE if the last update ran without a clip setting.  Under FCN8S_PREC_FP8_INFER fcn8s_accumulate_bucket refuses like the
+ *   other training calls.                                                                                                                  */
+int fcn8s_accumulate_bucket(fcn8s_model* m, int bucket, int flush);   /* after fcn8s_backward_bucket(m, bucket): 0 = fold, 1 = flush */
+int fcn8s_accumulate_pending(const fcn8s_model* m);                   /* micro-batches folded and not yet flushed (max over buckets) */
+int fcn8s_accumulate_discard(fcn8s_model* m);                         /* k_b = 0 for every b; keeps the memory */
+int fcn8s_set_grad_clip(fcn8s_model* m, float max_norm);
+int fcn8s_get_update_stats(fcn8s_model* m, float* norm, float* clip_coef, float* scale, int64_t* skipped);
+
 /* ---- data parallelism inside the library: one RCCL rank per model (SURVEY section 7 step 7, 8b "RCCL error"; the reference is one
  * tf.Session on one device, fcn8s_tensorflow.py:65, so there is nothing to cite for the collective itself).  A caller that keeps the
  * reference's Python and binds this ABI gets multi-GPU training without torch.distributed:
@@ -645,6 +684,16 @@ int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* m, float
                      float lr, float beta1, float beta2, float eps, float grad_scale);
 int fcn8s_op_sgd_momentum(void* stream, float* theta, const float* g, float* buf, int64_t n,
                           float lr, float momentum, float grad_scale);
+/* the kernels of fcn8s_accumulate_bucket and of the clipped update on DEVICE pointers of any float alignment.  grad_accumulate: mode 0:
+ * dst = src, 1: dst = dst + src, n floats.  grad_norm: out5_dev = float[5] {norm, c, s, ok (1 / 0), 0} of the n floats at g as defined at
+ * fcn8s_set_grad_clip (max_norm = 0: c = 1); it allocates its slab of partial sums and synchronises.  tf_adam_dev / sgd_momentum_dev:
+ * fcn8s_op_tf_adam / fcn8s_op_sgd_momentum with grad_scale = out5_dev[2]; out5_dev[3] == 0: nothing is touched. */
+int fcn8s_op_grad_accumulate(void* stream, float* dst, const float* src, int64_t n, int mode);
+int fcn8s_op_grad_norm(void* stream, const float* g, int64_t n, float grad_scale, float max_norm, float* out5_dev);
+int fcn8s_op_tf_adam_dev(void* stream, float* theta, const float* g, float* m, float* v, int64_t n, int t,
+                         float lr, float beta1, float beta2, float eps, const float* out5_dev);
+int fcn8s_op_sgd_momentum_dev(void* stream, float* theta, const float* g, float* buf, int64_t n,
+                              float lr, float momentum, const float* out5_dev);
 
 #ifdef __cplusplus
 }
