@@ -7,6 +7,7 @@
 #include "../../include/fcn8s_hip.h"
 #include "fcn8s_internal.h"
 #include "device_buffer.h"
+#include "pass_state.h"
 #include <cstdarg>
 
 #include <dlfcn.h>
@@ -119,14 +120,10 @@ struct fcn8s_model {
     int wino_tile = 6;                                                    // largest 3x3 output tile: F(6x6,3x3) / F(4x4,3x3) per layer by cost, F(2x2,3x3) fallback
     int wino_fc6 = 1;                                                     // fc6 7x7 as a 2x2 grid of 4x4 sub-filters in the Winograd domain
     int fc6_fft = 1;                                                      // ... and in the fp32 training step: forward + data gradient through 14x14 real-DFT tiles (fft_fc6.hip)
-    std::string fft6_ready;                                               // the layer whose FFT bank (u_train "<layer>#fft") this forward pass built
     int fc6_fft_wgrad = 1;                                                // ... and its weight gradient too: 1 = from fft6_wgrad_min_tiles tiles up, 2 = at any tile count, 0 = F(4x4,4x4)
-    std::string fft6_xf;                                                  // the layer whose DFT input bank Xf this forward pass kept (its "wv:" slot) for that weight gradient
-    std::string fft6_dyf;                                                 // the layer whose dYf the weight gradient left in d_wino_m for the data gradient
     int wino_tile_hires = 0, wino_hires_pixels = 0;                       // != 0: 3x3 layers on maps of at least wino_hires_pixels pixels (per image) use at most this tile
     int wino_force_tile = 0;                                              // != 0: every eligible 3x3 layer uses exactly this tile (op-level parity entry point)
     int precision = FCN8S_PREC_F32;                                       // FCN8S_PREC_BF16_FC: forward fc6 / fc7 on the bf16 MFMA
-    bool pool_fused[5] = {false, false, false, false, false};            // forward wrote pool_b + argmax bytes from conv_b_last's output transform
     // fcn8s_freeze_params: the caller promises constant parameters; Winograd-transformed filters are then kept per layer
     bool frozen = false;
     unsigned long long frozen_fp = 0; DeviceBuf<unsigned long long> d_fp;   // fingerprint of the parameter buffer the cached banks were built from
@@ -135,18 +132,10 @@ struct fcn8s_model {
     std::map<std::string, DeviceBuf<float>> u_train;                              // layer -> forward filter bank of the current training step: the adjoint data
                                                                          // gradient reads it as a transposed B operand (no second, transposed bank)
     bool fwd_train = false;                                              // forward() is running a training pass
-    std::set<std::string> rbits_ok;                                       // layers whose forward pass wrote a ReLU bit mask ("rb:<layer>") this step
-    std::string fused_v_layer;                                            // layer whose data-gradient input transform already sits in d_wino_v
-    std::string dm_layer;                                                 // layer whose dM = A dY A^T sits in d_wino_m, ready for the adjoint data gradient
-    std::string dm_prefilled;                                             // layer whose dM the data gradient of the layer after it has already written into d_wino_m (fused transform)
+    PassState pass;                                                       // what that pass and the backward pass behind it left for later launches (pass_state.h)
     int deterministic = 0;                                                // option: reductions split over blocks are joined in a fixed order (slabs + ordered sum) instead of atomics
     int fuse_dgrad_dout = 1;                                              // option: allow that fusion
     int fuse_out_in = 1;                                                  // option: inside a block, conv L's output transform writes conv L+1's V directly (Y is never written): 0 never, 1 unless the row ranges would get too short, 2 always
-    std::string fwd_v_layer;                                              // forward: layer whose V the previous layer's fused output transform has already written
-    bool pool_routed[5] = {false, false, false, false, false};           // bf16_train: the forward pool of block b kept its routing bytes (pidx<b>) for maxpool_bwd_bf16_route_kernel
-    std::set<std::string> dy_bf16_only;                                   // ... and layers whose fp32 OUTPUT GRADIENT was not written by this backward pass (their padded bf16 copy + the bias gradient were)
-    std::set<std::string> in_bf16_only;                                   // bf16_train, option bf16_acts: layers whose fp32 INPUT was not written by the last training forward pass (their padded bf16 copy is all there is)
-    std::set<std::string> y_unwritten;                                    // layers whose activation tensor was not materialised by the last forward pass
     int conv1_tiled = 1, conv1_wgrad_mfma = 1;                            // options: conv1_1 forward on the spatial-tile kernel / its weight gradient on the matrix core
     int conv1_in_transform = 1;                                           // option: conv1_1 is evaluated inside conv1_2's input transform (its activation tensor is never written)
     DeviceBuf<unsigned short> d_wbf16;                                    // bf16 copy of one layer's kernel at a time (K-tile-major or transposed)
@@ -163,20 +152,19 @@ struct fcn8s_model {
     // the forward pass and read again by the layer's weight gradient
     using G16Map = std::map<std::string, DeviceBuf<unsigned short>>;
     G16Map xg16, dyg16;                                                   // ... per layer: the same kind of copy of its output gradient dY
-    std::set<std::string> db_taken;                                      // layers whose bias gradient the producer of their dY copy has already added (this backward pass)
+    std::set<std::string> g16_stale;                                      // ... and which of the two maps' copies ("x:<layer>" / "d:<layer>") carry the zero border of another shape.  It lives and dies with the
+                                                                          // copies: drop_shape_copies marks them (fcn8s_predict_tta's re-plans) or clears it with the maps, g16_for zeroes a marked copy on its next use
     int bf16_fuse_pool = 1;                                               // option: bf16_train, the max-pool backward writes the last conv's bf16 dZ copy and bias gradient directly
-    std::set<std::string> xg16_filled, dyg16_filled;                     // copies a producing kernel's epilogue has already written in this pass (no conversion pass)
     int bf16_infer_copies = 1;                                            // option: bf16_train's evaluation / prediction passes take the training pass's data flow (see forward())
     int bf16_rows_bn = 0;                                                 // option (A/B): 128 = the flat-position bf16 convolution takes its 128-column tile where it can (default: 64 columns)
     int bf16_acts = 1;                                                    // option: bf16_train training passes keep a conv -> conv activation only as the consumer's padded bf16 copy (the producer's epilogue writes it; no fp32 tensor, no conversion pass)
     // FCN8S_PREC_FP8_INFER: the calibration (per FP8 layer the max |input| of the fp32 pass; it describes the parameters, not the mode), the device scratch of
     // fcn8s_fp8_calibrate, the e4m3 copies (kept with the workspace) and the weight banks (valid across passes only while frozen: w8_valid)
     bool fp8_calibrated = false, fp8_calibrating = false; float fp8_amax[FCN8S_FP8_LAYERS] = {}; DeviceBuf<unsigned> d_fp8_amax;
-    std::map<std::string, Q8Buf> q8; std::set<std::string> q8_filled;
+    std::map<std::string, Q8Buf> q8;
     std::map<std::string, W8Bank> w8; std::set<std::string> w8_valid;
     int saved_wino_min_cin = -1, saved_wino_fc6 = -1;                      // the options the mode overrides (the direct path carries it), restored on leaving
     int bf16_copy_by_transform = 1;                                       // option: 0 = every bf16 layer converts its input with a pass of its own (round 3's path)
-    std::set<std::string> g16_stale;                                      // bf16_train copies ("x:<layer>" / "d:<layer>") whose zero border belongs to another shape (fcn8s_predict_tta re-plans)
     int64_t ws_allocs = 0;                                                // statistic "workspace_allocations": device allocations for the workspace, the TTA scratch, the bf16 copies and the cached filter banks
     bool x0_ready = false;                                                // forward(): x0 is already written (fcn8s_predict_tta's tta_input), skip the preprocess kernel
     DeviceBuf<char> crf_buf;                                              // fcn8s_predict_crf: staged images, the mean softmax, the two mean-field buffers, staged output (grown, never shrunk)
@@ -191,7 +179,7 @@ struct fcn8s_model {
     // option "keep_output_gradients" (tests): every weighted layer's fp32 output gradient dY, copied as the backward pass hands it to the layer's weight gradient;
     // read back through fcn8s_get_activation("dy:<layer>")
     struct KeptDy { DeviceBuf<float> p; size_t n = 0; };                  // (n = 0: this pass handed the layer's dY over in another form)
-    int keep_dy = 0; std::map<std::string, KeptDy> kept_dy; std::set<std::string> dz_unwritten;      // dz_unwritten: layers whose fp32 dY the pool's backward kernel skipped
+    int keep_dy = 0; std::map<std::string, KeptDy> kept_dy;
     // the last transposed conv (k = 2s = 16) as one GEMM over output blocks (PixMap, elementwise.hip): logits / dlogits live in that blocked layout
     int tconv_gemm = 1; PixMap pm{0, 0, 0, 0, 0, 0}; int tg_kp = 0;
     float *logits_b = nullptr, *dlogits_b = nullptr, *tg_A = nullptr, *tg_dA = nullptr;      // arena
@@ -377,21 +365,26 @@ static void prof_derived(fcn8s_model* m, const char* what)
 }
 
 // ---- layer launchers ------------------------------------------------------------
-struct Epi { const float* bias = nullptr; const float* addend = nullptr; const float* mask = nullptr;
-             float alpha = 1.f; int relu = 0; float mask_scale = 1.f; int dropout = 0; float keep = 1.f;
-             uint32_t stream_id = 0; int dgrad = 0;      // dgrad: data-gradient launch (profile tag; never keeps V)
-             float* pool_out = nullptr;                  // 2x2/2 max-pool of the output, written by the Winograd output transform if that path runs
-             unsigned char* pool_idx = nullptr;          // ... with the per-window argmax bytes the backward pass routes the pool gradient by
-             unsigned* relu_bits_out = nullptr;          // forward, Winograd path: also record (y > 0), one bit per element
-             const unsigned* relu_bits_in = nullptr;     // data gradient, Winograd path: such a record of `mask` (read instead of the tensor)
-             const float* w_fwd = nullptr;
-             unsigned* in_relu_bits_out = nullptr;       // forward, Winograd path: record (x > 0) of the input too (see wino_input_kernel) ...
-             const char* in_layer = nullptr;              // ... under this producer's name in rbits_ok
-             int lazy_wt = 0;                            // data gradient: `w` is still to be filled from w_fwd (flip + transpose) if the adjoint path is not taken
-             float* dm_out = nullptr; const char* dm_out_layer = nullptr;   // adjoint data gradient: write dM of the producing layer (name) here instead of its dZ into y
-             float* next_v = nullptr; const char* next_layer = nullptr;   // forward, Winograd F(6x6) path: write the NEXT conv's V here instead of this conv's output
-             const char* yb_layer = nullptr; int yb_K = 3; bool yb_only = false;    // (yb_only: both of that layer's gradients take its bf16 copy -- the fp32 tensor may stay unwritten) // bf16_train data gradient: the layer whose output gradient this launch produces (its bf16 copy is written on the way), and that layer's kernel size
-             int skip_y = 0; };                          // Winograd path with pool_out: do not write the full-resolution output (only its pool is consumed)            // data gradient: the layer's forward kernel [3,3,Cout_of_this_conv... = Cin here][...] (adjoint Winograd path)
+struct ConvEpi { float alpha = 1.f; };                   // both directions: the product is scaled by alpha before the epilogue
+struct FwdEpi : ConvEpi {
+    const float* bias = nullptr; int relu = 0;
+    int dropout = 0; float keep = 1.f; uint32_t stream_id = 0;      // dropout behind the ReLU (fc6 / fc7): keep probability, counter stream of its random numbers
+    float* pool_out = nullptr; unsigned char* pool_idx = nullptr;   // 2x2/2 max-pool of the output, written by the Winograd output transform if that path runs, with the per-window argmax bytes the backward pass routes by
+    int skip_y = 0;                                      // Winograd path with pool_out: do not write the full-resolution output (only its pool is consumed)
+    unsigned* relu_bits_out = nullptr;                   // Winograd path: also record (y > 0), one bit per element
+    unsigned* in_relu_bits_out = nullptr; const char* in_layer = nullptr;   // Winograd path: record (x > 0) of the input too (wino_input_kernel), under this producer's name in pass.rbits_ok
+    float* next_v = nullptr; const char* next_layer = nullptr;     // Winograd F(6x6) path: write the NEXT conv's V here instead of this conv's output, and promise it to that conv (pass.fwd_v)
+};
+struct DgradEpi : ConvEpi {
+    const float* addend = nullptr;                       // added to dX (the skip paths' gradients)
+    const float* mask = nullptr; float mask_scale = 1.f; // dX *= (mask > 0) * mask_scale: the ReLU / dropout of the layer's input
+    const unsigned* relu_bits_in = nullptr;              // Winograd path: the bit record of (mask > 0), read instead of the tensor
+    const float* w_fwd = nullptr;                        // the layer's forward kernel [K,K,Cout here,Cin here] (adjoint Winograd paths, bf16_train)
+    int lazy_wt = 0;                                     // `w` is still to be filled from w_fwd (flip + transpose) if no path that reads w_fwd is taken
+    float* dm_out = nullptr; const char* dm_out_layer = nullptr;   // adjoint path: write dM of the producing layer here instead of its dZ into y, and promise it to that layer's weight gradient (pass.dm_prefilled)
+    const char* yb_layer = nullptr; int yb_K = 3;        // bf16_train: the layer whose output gradient this launch produces, and its kernel size
+    bool yb_only = false;                                // ... both of that layer's gradients take its bf16 copy: write the copy, the fp32 tensor may stay unwritten
+};
 
 // 3x3 SAME conv through Winograd F(tile x tile, 3x3): filter transform, input transform, (tile+2)^2 batched GEMMs
 // on the matrix cores (2.25x / 4x fewer MFMA flops than the direct form), output transform + fused epilogue.
@@ -553,8 +546,8 @@ static bool conv_fft6_fwd(fcn8s_model* m, const char* layer, const float* x, con
     { ProfScope ps(m, "fc6_fft_gemm_fwd", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
     { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)P * T * Cout + (double)N * H * W * Cout));
       launch_fft_fc6_output(m->d_wino_m, bias, y, N, H, W, Cout, relu, dropout, keep, m->seed, stream_id, s); }
-    m->fft6_ready = layer;
-    if (dft_wgrad) m->fft6_xf = layer;
+    m->pass.fft6_ready.give(layer);
+    if (dft_wgrad) m->pass.fft6_xf.give(layer);
     return true;
 }
 // weight gradient (Cin / Cout: channels of the forward conv): dYf = output^T(dz) into d_wino_m, where the data gradient then finds it;
@@ -565,7 +558,7 @@ static void conv_fft6_wgrad(fcn8s_model* m, const char* layer, const float* xf, 
     const int P = fft_fc6_planes();
     const long long T = fft_fc6_tiles(N, H, W);
     { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)N * H * W * Cout + (double)P * T * Cout)); launch_fft_fc6_dout(dz, m->d_wino_m, N, H, W, Cout, s); }
-    m->fft6_dyf = layer;
+    m->pass.fft6_dyf.give(layer);
     WgradArgs g{}; g.split = 0;
     g.A = xf; g.B = m->d_wino_m; g.C = m->d_wino_u;
     g.N = 1; g.Pa = 1; g.Pb = (int)T; g.P = T;
@@ -582,8 +575,10 @@ static void conv_fft6_dgrad(fcn8s_model* m, const char* layer, const float* dz, 
 {
     const int P = fft_fc6_planes();
     const long long T = fft_fc6_tiles(N, H, W);
-    if (m->fft6_dyf != layer) { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)N * H * W * Cin + (double)P * T * Cin)); launch_fft_fc6_dout(dz, m->d_wino_m, N, H, W, Cin, s); }
-    m->fft6_dyf.clear();        // (else the weight gradient just wrote dYf of this dz into d_wino_m)
+    if (!m->pass.fft6_dyf.take(layer)) {     // (else the weight gradient just wrote dYf of this dz into d_wino_m)
+        m->pass.fft6_dyf.drop();
+        ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)N * H * W * Cin + (double)P * T * Cin)); launch_fft_fc6_dout(dz, m->d_wino_m, N, H, W, Cin, s);
+    }
     IgemmArgs a = fft6_gemm(m->d_wino_m, uf, m->d_wino_v, T, Cin, Cout);
     a.fixed_tile = 1; a.bt = 1; a.ldw = Cin;
     { ProfScope ps(m, "fc6_fft_gemm_dgrad", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
@@ -591,8 +586,9 @@ static void conv_fft6_dgrad(fcn8s_model* m, const char* layer, const float* dz, 
       launch_fft_fc6_din(m->d_wino_v, m->d_wino_m, dx, N, H, W, Cout, s); }
 }
 
-// KS = 3, or 7 (3x3 grid of 3x3 sub-filters, GEMM depth 9*Cin -- see winograd.hip)
-void conv_winograd(fcn8s_model* m, int tile, int KS, const char* tag, const float* x, const float* wk, float* y, float* u, float* v, float* mm,
+// KS = 3, or 7 (3x3 grid of 3x3 sub-filters, GEMM depth 9*Cin -- see winograd.hip).  fwd: a forward convolution (its filter bank is kept for a
+// frozen model / for this step's adjoint data gradient), else the same algorithm as a data gradient on flipped + transposed weights
+void conv_winograd(fcn8s_model* m, int tile, int KS, bool fwd, const float* x, const float* wk, float* y, float* u, float* v, float* mm,
                    int N, int H, int W, int Cin, int Cout, const WinoEpi& e, hipStream_t s, const char* layer, bool v_ready = false)
 {
     const int P = wino_alpha(tile, KS) * wino_alpha(tile, KS), nsub2 = wino_nsub(KS) * wino_nsub(KS);
@@ -602,8 +598,8 @@ void conv_winograd(fcn8s_model* m, int tile, int KS, const char* tag, const floa
     const double tb = 4.0 * ((double)N * H * W * Cin * nsub2 + (double)P * T * Kg), ob = 4.0 * ((double)N * H * W * Cout * ((e.pool ? (e.skip_y ? 0.25 : 1.25) : 1.0) + (e.rbits_in ? 1.0 / 32 : (e.mask ? 1.0 : 0.0)) + (e.addend ? 1.0 : 0.0) + (e.rbits_out ? 1.0 / 32 : 0.0)) + (double)P * T * Cout);   // y (+ pool) written, ReLU mask / skip addend read
     // frozen parameters (evaluate / predict loops): the transformed filter bank of each forward layer is computed once and kept
     bool u_cached = false;
-    const bool fwd_call = std::string(tag).find("dgrad") == std::string::npos;      // (v_ready in a forward call = V written by the previous conv's fused output transform)
-    if (m && m->frozen && layer && fwd_call) {
+    const char* tag = KS == 7 ? (fwd ? "wino_gemm_fc6_fwd" : "wino_gemm_fc6_dgrad") : (fwd ? "wino_gemm_fwd" : "wino_gemm_dgrad");
+    if (m && m->frozen && layer && fwd) {
         DeviceBuf<float>& cu = m->u_cache[std::string(layer) + "#" + std::to_string(tile)];       // (the tile, hence the bank's shape, depends on the image size)
         const std::string key = "u:" + std::string(layer) + "#" + std::to_string(tile);
         if (cu && !m->bank_stale.count(key)) { u = cu; u_cached = true; }
@@ -611,11 +607,11 @@ void conv_winograd(fcn8s_model* m, int tile, int KS, const char* tag, const floa
         else if (cu.grow((size_t)P * Kg * Cout * sizeof(float), s, &m->ws_allocs)) u = cu;  // filled below, reused from the next call on (out of memory: the shared scratch)
         a.w = u;
     }
-    if (m && !u_cached && m->fwd_train && layer && fwd_call && ((KS == 3 && tile == 6) || (KS == 7 && tile == 4))) {
+    if (m && !u_cached && m->fwd_train && layer && fwd && ((KS == 3 && tile == 6) || (KS == 7 && tile == 4))) {
         DeviceBuf<float>& tu = m->u_train[std::string(layer) + "#" + std::to_string(tile)];
         if (tu.grow((size_t)P * Kg * Cout * sizeof(float), s)) { u = tu; a.w = u; }
     }
-    // v_ready: V was written together with the weight gradient's dM by the fused transform (launch_wino_input_dout)
+    // v_ready: V is already written (forward: by the previous conv's fused output transform; data gradient: with the weight gradient's dM)
     auto pre = [&]() { if (!u_cached) { prof_derived(m, "wino_filter_kernel"); launch_wino_filter(tile, wk, u, Cin, Cout, KS, s); } if (!v_ready) launch_wino_input(tile, x, v, N, H, W, Cin, KS, s, e.in_rbits_out); };
     auto post = [&]() {
         if (e.next_v && tile == 6 && KS == 3 && e.relu && e.bias && !e.addend && !e.mask && !e.dropout && !e.pool && !e.rbits_in &&
@@ -628,15 +624,72 @@ void conv_winograd(fcn8s_model* m, int tile, int KS, const char* tag, const floa
     { ProfScope ps(m, "wino_transform", 0, ob); post(); if (e.fused_out && *e.fused_out && m && m->profile && !m->groups.empty()) { const int g = group_id(m, "wino_transform"); m->groups[g].bytes += ob_fused - ob; } }
 }
 
-// SAME conv (or its data gradient when `w` holds flipped+transposed weights).  Returns true if e.pool_out was written.
-bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w, float* y,
-               int N, int H, int W, int Cin, int Cout, int K, const Epi& e, hipStream_t s, int real_cin = 0,
-               const char* layer = nullptr)
+// The direct form, where both directions end when no transform-domain path applies: the implicit-GEMM tile kernels or, for the 1x1 score heads, the
+// skinny kernels.  `a` arrives with the caller's epilogue (bias, addend, mask, alpha, relu, mask_scale, dropout, keep_prob, stream_id).
+static void conv_direct(fcn8s_model* m, const char* group, IgemmArgs a, const float* x, const float* w, float* y,
+                        int N, int H, int W, int Cin, int Cout, int K, hipStream_t s, int real_cin, const char* layer)
 {
-    if (bf16_train_mode(m) && m->train_mode && e.w_fwd && layer && !real_cin && e.alpha == 1.f && !e.bias && !e.relu && !e.dropout && Cin % 32 == 0 && Cout % 64 == 0) {
-        // FCN8S_PREC_BF16_TRAIN, data gradient of `layer` (here Cin = channels of dY, Cout = channels of dX): the SAME convolution of the padded bf16
-        // copy of dY with the flipped kernel, wt[ci][(flipped tap, co)] bf16, on conv_bf16_256_kernel; fp32 accumulate, fp32 epilogue (skip-path addend,
-        // the ReLU / dropout mask of the layer's input).  w_fwd is the forward kernel [K][K][Cout here][Cin here].
+    a.split = split_of(m);
+    a.x = x; a.w = w; a.y = y;
+    a.N = N; a.Ma = H; a.Mb = W; a.M = (long long)N * H * W;
+    a.Hi = H; a.Wi = W; a.Cin = Cin; a.ldx = Cin;
+    a.KW = K; a.in_scale = 1; a.tap_step = 1; a.tap_off = -(K - 1) / 2; a.Ktot = K * K * Cin;
+    a.Ho = H; a.Wo = W; a.Cout = Cout; a.ldy = Cout;
+    a.out_scale = 1; a.out_offy = 0; a.out_offx = 0; a.phases_x = 1; a.w_phase_stride = 0;
+    a.seed = m ? m->seed : 0;
+    const double rc = real_cin ? real_cin : Cin;
+    const double flops = 2.0 * a.M * K * K * rc * Cout;
+    const double bytes = 4.0 * (a.M * rc + (double)a.M * Cout + (double)K * K * rc * Cout);
+    // 1x1 score heads: one skinny dimension (skinny.hip); everything else goes through the general tile kernels
+    auto run = [&]() {
+        if (K == 1 && !real_cin && !a.addend && !a.relu && !a.dropout) {
+            if (Cout <= 32 && !a.mask && launch_head_fwd(x, w, a.bias, y, a.M, Cin, Cout, a.alpha, s, m ? m->d_wino_u : nullptr, m ? m->ufl : 0)) return;      // (the filter-bank scratch is idle between convolutions)
+            if (Cin <= 32 && !a.bias && launch_head_dgrad(x, w, a.mask, a.mask_scale, y, a.M, Cout, Cin, a.alpha, s)) return;
+        }
+        launch_igemm(a, 1, s);
+    };
+    { ProfScope ps(m, group, flops, bytes, layer); run(); }
+}
+
+// SAME conv, forward.  Returns true if e.pool_out was written.
+bool conv_fwd(fcn8s_model* m, const char* group, const float* x, const float* w, float* y,
+              int N, int H, int W, int Cin, int Cout, int K, const FwdEpi& e, hipStream_t s, int real_cin = 0,
+              const char* layer = nullptr)
+{
+    if (m && K == 7 && layer && !real_cin && e.alpha == 1.f && !e.pool_out && !e.relu_bits_out && m->fwd_train && fft6_on(m, N, H, W, Cin, Cout) &&
+        conv_fft6_fwd(m, layer, x, w, y, N, H, W, Cin, Cout, e.bias, e.relu, e.dropout, e.keep, e.stream_id, s)) return false;
+    if (m) m->pass.drop_backward_handoffs();
+    const bool wino3 = m && K == 3 && m->wino_min_cin > 0 && Cin >= m->wino_min_cin && m->d_wino_v && wino_tile_for(m, H, W, 3) && !e.dropout;
+    const bool wino7 = m && K == 7 && m->wino_fc6 && m->d_wino_v && wino_tile_for(m, H, W, 7) == 4;
+    if ((wino3 || wino7) && Cin % 16 == 0 && Cout % 64 == 0 && e.alpha == 1.f && !real_cin) {
+        const bool v_ready = m->pass.fwd_v.take(layer);      // written by the previous conv's fused output transform
+        m->pass.fwd_v.drop();                                // (another layer's V: a promise nobody collects any more)
+        float* vbuf = m->d_wino_v;
+        if (layer) { auto it = m->acts.find(std::string("wv:") + layer); if (it != m->acts.end()) vbuf = it->second.p; }      // training keeps V for the weight gradient
+        WinoEpi we; we.bias = e.bias; we.relu = e.relu;
+        we.dropout = e.dropout; we.keep = e.keep; we.seed = m->seed; we.stream_id = e.stream_id; we.pool = e.pool_out; we.pidx = e.pool_idx;
+        we.rbits_out = e.relu_bits_out; we.skip_y = e.skip_y && e.pool_out;
+        if (e.relu_bits_out && layer) m->pass.rbits_ok.insert(layer);
+        if (e.in_relu_bits_out && e.in_layer && K == 3) { we.in_rbits_out = e.in_relu_bits_out; m->pass.rbits_ok.insert(e.in_layer); }
+        bool fused_out = false;
+        if (e.next_v && e.next_layer) { we.next_v = e.next_v; we.fused_out = &fused_out; }
+        conv_winograd(m, wino_tile_for(m, H, W, K), K, true, x, w, y, m->d_wino_u, vbuf, m->d_wino_m, N, H, W, Cin, Cout, we, s, layer, v_ready);
+        if (fused_out) { m->pass.fwd_v.give(e.next_layer); if (layer) m->pass.y_unwritten.insert(layer); }
+        return e.pool_out != nullptr;
+    }
+    IgemmArgs a{}; a.bias = e.bias; a.alpha = e.alpha; a.relu = e.relu; a.mask_scale = 1.f; a.dropout = e.dropout; a.keep_prob = e.keep; a.stream_id = e.stream_id;
+    conv_direct(m, group, a, x, w, y, N, H, W, Cin, Cout, K, s, real_cin, layer);
+    return false;
+}
+
+// Data gradient of a SAME conv: x is dY (Cin channels), y is dX (Cout channels), `w` holds (or, e.lazy_wt, is to hold) the flipped + transposed weights.
+void conv_dgrad(fcn8s_model* m, const char* group, const float* x, const float* w, float* y,
+                int N, int H, int W, int Cin, int Cout, int K, const DgradEpi& e, hipStream_t s, const char* layer = nullptr)
+{
+    const bool bf16_step = bf16_train_mode(m) && m->train_mode && layer;
+    if (bf16_step && e.w_fwd && e.alpha == 1.f && Cin % 32 == 0 && Cout % 64 == 0) {
+        // FCN8S_PREC_BF16_TRAIN: the SAME convolution of the padded bf16 copy of dY with the flipped kernel, wt[ci][(flipped tap, co)] bf16, on
+        // conv_bf16_256_kernel; fp32 accumulate, fp32 epilogue (skip-path addend, the ReLU / dropout mask of the layer's input).
         const size_t wneed = (size_t)K * K * Cin * Cout;
         const bool ok = m->d_wbf16.grow(wneed * sizeof(unsigned short), s, &m->ws_allocs);
         unsigned short* dyb = ok ? dyb_for(m, layer, x, N, H, W, Cin, K, s) : nullptr;
@@ -665,42 +718,38 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
                            (g.y ? 4.0 : 0.0) * M * Cout + (g.yb ? 2.0 : 0.0) * M * Cout + (g.mask16 ? 2.0 : (e.mask ? 4.0 : 0.0)) * M * Cout + 2.0 * M * Cin + 2.0 * wneed, layer);
               done = launch_conv_bf16_256(g, s); }
             if (done) {
-                if (g.yb) m->dyg16_filled.insert(e.yb_layer);
+                if (g.yb) m->pass.dyg16_filled.insert(e.yb_layer);
                 if (g.colpart) {
                     ProfScope ps(m, "colsum", 0, 4.0 * prow * Cout);
                     launch_colsum(g.colpart, Gp(m, std::string(e.yb_layer) + "/biases"), prow, Cout, s);
-                    m->db_taken.insert(e.yb_layer); m->dy_bf16_only.insert(e.yb_layer);
+                    m->pass.db_taken.insert(e.yb_layer); m->pass.dy_bf16_only.insert(e.yb_layer);
                 }
-                return false;
+                return;
             }
-            if (g.colpart) { defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient was refused by the flat-position kernel", layer); return false; }
+            if (g.colpart) { defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient was refused by the flat-position kernel", layer); return; }
         }
     }
-    if (bf16_train_mode(m) && m->train_mode && layer && e.dgrad && m->dy_bf16_only.count(layer)) {
-        defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient could not run on the bf16 kernel and its fp32 output gradient was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return false;
+    if (bf16_step && m->pass.dy_bf16_only.count(layer)) {
+        defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient could not run on the bf16 kernel and its fp32 output gradient was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return;
     }
-    if (bf16_train_mode(m) && m->train_mode && layer && e.mask && m->in_bf16_only.count(layer)) {
-        defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient could not run on the bf16 kernel and its fp32 mask was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return false;
+    if (bf16_step && e.mask && m->pass.in_bf16_only.count(layer)) {
+        defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient could not run on the bf16 kernel and its fp32 mask was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return;
     }
-    if (m && K == 7 && layer && !real_cin && e.alpha == 1.f && !e.addend && !e.mask && !e.pool_out && !e.relu_bits_out && !e.relu_bits_in) {
-        if (!e.dgrad && m->fwd_train && fft6_on(m, N, H, W, Cin, Cout) &&
-            conv_fft6_fwd(m, layer, x, w, y, N, H, W, Cin, Cout, e.bias, e.relu, e.dropout, e.keep, e.stream_id, s)) return false;
+    // what the layer's weight gradient left in the scratch for this call; anything left for another layer is void, this convolution overwrites it
+    const bool dm_ready = m && m->pass.dm.take(layer), v_ready = m && m->pass.dgrad_v.take(layer);
+    if (m) m->pass.drop_backward_handoffs();
+    if (m && K == 7 && layer && e.alpha == 1.f && !e.addend && !e.mask && !e.relu_bits_in) {
         auto kept = m->u_train.find(std::string(layer) + "#fft");
-        if (e.dgrad && !e.bias && !e.relu && !e.dropout && m->fft6_ready == layer && kept != m->u_train.end() && kept->second &&
-            fft6_on(m, N, H, W, Cout, Cin) && bt_gemm_ok(Cin, Cout)) {
-            m->dm_layer.clear(); m->fused_v_layer.clear();
+        if (m->pass.fft6_ready.holds(layer) && kept != m->u_train.end() && kept->second && fft6_on(m, N, H, W, Cout, Cin) && bt_gemm_ok(Cin, Cout)) {
             conv_fft6_dgrad(m, layer, x, kept->second, y, N, H, W, Cin, Cout, s);
-            return false;
+            return;
         }
     }
-    const bool wino3 = m && K == 3 && m->wino_min_cin > 0 && Cin >= m->wino_min_cin && m->d_wino_v && wino_tile_for(m, H, W, 3) && !e.dropout;
+    const bool wino3 = m && K == 3 && m->wino_min_cin > 0 && Cin >= m->wino_min_cin && m->d_wino_v && wino_tile_for(m, H, W, 3);
     const bool wino7 = m && K == 7 && m->wino_fc6 && m->d_wino_v && wino_tile_for(m, H, W, 7) == 4;
-    if (m && wino3 && e.dgrad && layer && e.w_fwd && !m->dm_layer.empty() && m->dm_layer == layer && wino_tile_for(m, H, W, 3) == 6 &&
-        Cin % 64 == 0 && Cout % 64 == 0 && e.alpha == 1.f && !real_cin && !e.bias && !e.relu) {
+    if (wino3 && dm_ready && e.w_fwd && wino_tile_for(m, H, W, 3) == 6 && Cin % 64 == 0 && Cout % 64 == 0 && e.alpha == 1.f) {
         // Data gradient as the adjoint of the forward Winograd algorithm: dV[xi] = dM[xi] U[xi]^T with the dM = A dY A^T the weight
-        // gradient just built (d_wino_m) and the FORWARD filter bank, then dx = overlap-added B dV B^T.  (Here Cin = channels of dY,
-        // Cout = channels of dx; w_fwd is [3,3,Cout,Cin].)
-        m->dm_layer.clear(); m->fused_v_layer.clear();
+        // gradient just built (d_wino_m) and the FORWARD filter bank, then dx = overlap-added B dV B^T.  (w_fwd is [3,3,Cout,Cin].)
         const int P = 64;
         const long long T = wino_tiles(6, N, H, W);
         IgemmArgs a = fft6_gemm(m->d_wino_m, m->d_wino_u, m->d_wino_v, T, Cin, Cout); a.split = split_of(m);
@@ -716,76 +765,39 @@ bool conv_same(fcn8s_model* m, const char* group, const float* x, const float* w
             // the consumer of this gradient is the previous conv's weight gradient in the Winograd domain: hand it dM, skip dZ
             ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cout / 32 + 2.0 * P * T * Cout));
             launch_wino_dgrad_output_dout(m->d_wino_v, e.relu_bits_in, e.dm_out, N, H, W, Cout, s);
-            m->dm_prefilled = e.dm_out_layer;
-            return false;
+            m->pass.dm_prefilled.give(e.dm_out_layer);
+            return;
         }
         { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cout * (1.0 + (e.relu_bits_in ? 1.0 / 32 : (e.mask ? 1.0 : 0.0)) + (e.addend ? 1.0 : 0.0)) + (double)P * T * Cout));
           launch_wino_dgrad_output(m->d_wino_v, e.addend, e.mask, e.mask_scale, e.relu_bits_in, y, N, H, W, Cout, s); }
-        return false;
+        return;
     }
-    if (m && wino7 && e.dgrad && layer && !m->dm_layer.empty() && m->dm_layer == layer && e.alpha == 1.f && !real_cin && !e.bias && !e.relu && !e.mask && !e.addend &&
-        bt_gemm_ok(Cin, 4 * Cout)) {
+    if (wino7 && dm_ready && e.alpha == 1.f && !e.mask && !e.addend && bt_gemm_ok(Cin, 4 * Cout)) {
         auto kept = m->u_train.find(std::string(layer) + "#4");
         if (kept != m->u_train.end() && kept->second) {
             // fc6 data gradient as the adjoint of the forward sub-filter Winograd algorithm (here Cin = channels of dz = 4096, Cout = channels
             // of dx = 512): dV[xi][t][sub * Cout + c] = dM[xi][t][:] . U[xi][sub * Cout + c][:] with the forward bank of this step read as a
             // transposed B operand, then the overlap-add gather (winograd.hip).  No transform of dz, no second filter bank, no flipped copy.
-            m->dm_layer.clear(); m->fused_v_layer.clear();
             const int P = 49, Ng = 4 * Cout;
             const long long T = wino_tiles(4, N, H, W);
             IgemmArgs a = fft6_gemm(m->d_wino_m, kept->second, m->d_wino_v, T, Cin, Ng); a.split = split_of(m);
             a.bt = 1; a.ldw = Cin;
             { ProfScope ps(m, "wino_gemm_fc6_dgrad", 2.0 * P * T * Cin * Ng, 4.0 * P * (T * (double)(Cin + Ng) + (double)Cin * Ng), layer); launch_igemm(a, P, s); }
             { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cout + (double)P * T * Ng)); launch_wino_dgrad_output_sub44(m->d_wino_v, y, N, H, W, Cout, s); }
-            return false;
+            return;
         }
     }
-    if (m) m->dm_layer.clear();
     if (e.lazy_wt && e.w_fwd) {
         ProfScope ps(m, "weight_relayout", 0, 8.0 * K * K * Cin * Cout); launch_flip_transpose(e.w_fwd, const_cast<float*>(w), K * K, Cout, Cin, s);
     }
-    if ((wino3 || wino7) && Cin % 16 == 0 && Cout % 64 == 0 && e.alpha == 1.f && !real_cin) {
-        const bool dgrad = e.dgrad != 0;
-        float* vbuf = m->d_wino_v;
-        const bool v_ready = (dgrad && layer && !m->fused_v_layer.empty() && m->fused_v_layer == layer) ||
-                             (!dgrad && layer && !m->fwd_v_layer.empty() && m->fwd_v_layer == layer);      // (forward: written by the previous conv's fused output transform)
-        m->fused_v_layer.clear(); m->fwd_v_layer.clear();
-        if (!dgrad && layer) { auto it = m->acts.find(std::string("wv:") + layer); if (it != m->acts.end()) vbuf = it->second.p; }
-        WinoEpi we; we.bias = e.bias; we.addend = e.addend; we.mask = e.mask; we.mask_scale = e.mask_scale; we.relu = e.relu;
-        we.dropout = e.dropout; we.keep = e.keep; we.seed = m->seed; we.stream_id = e.stream_id; we.pool = e.pool_out; we.pidx = e.pool_idx;
-        we.rbits_out = e.relu_bits_out; we.rbits_in = e.relu_bits_in; we.skip_y = e.skip_y && e.pool_out;
-        if (e.relu_bits_out && layer) m->rbits_ok.insert(layer);
-        if (e.in_relu_bits_out && e.in_layer && K == 3 && !dgrad) { we.in_rbits_out = e.in_relu_bits_out; m->rbits_ok.insert(e.in_layer); }
-        const char* tag = K == 7 ? (dgrad ? "wino_gemm_fc6_dgrad" : "wino_gemm_fc6_fwd") : (dgrad ? "wino_gemm_dgrad" : "wino_gemm_fwd");
-        bool fused_out = false;
-        if (!dgrad && e.next_v && e.next_layer) { we.next_v = e.next_v; we.fused_out = &fused_out; }
-        conv_winograd(m, wino_tile_for(m, H, W, K), K, tag, x, w, y, m->d_wino_u, vbuf, m->d_wino_m, N, H, W, Cin, Cout, we, s, layer, v_ready);
-        if (fused_out) { m->fwd_v_layer = e.next_layer; if (layer) m->y_unwritten.insert(layer); }
-        return e.pool_out != nullptr;
+    if ((wino3 || wino7) && Cin % 16 == 0 && Cout % 64 == 0 && e.alpha == 1.f) {
+        // the forward algorithm on the flipped + transposed weights; v_ready: V = B^T dY B came with the weight gradient's dM (launch_wino_input_dout)
+        WinoEpi we; we.addend = e.addend; we.mask = e.mask; we.mask_scale = e.mask_scale; we.seed = m->seed; we.rbits_in = e.relu_bits_in;
+        conv_winograd(m, wino_tile_for(m, H, W, K), K, false, x, w, y, m->d_wino_u, m->d_wino_v, m->d_wino_m, N, H, W, Cin, Cout, we, s, layer, v_ready);
+        return;
     }
-    if (m) m->fused_v_layer.clear();
-    IgemmArgs a{}; a.split = split_of(m);
-    a.x = x; a.w = w; a.bias = e.bias; a.addend = e.addend; a.mask = e.mask; a.y = y;
-    a.N = N; a.Ma = H; a.Mb = W; a.M = (long long)N * H * W;
-    a.Hi = H; a.Wi = W; a.Cin = Cin; a.ldx = Cin;
-    a.KW = K; a.in_scale = 1; a.tap_step = 1; a.tap_off = -(K - 1) / 2; a.Ktot = K * K * Cin;
-    a.Ho = H; a.Wo = W; a.Cout = Cout; a.ldy = Cout;
-    a.out_scale = 1; a.out_offy = 0; a.out_offx = 0; a.phases_x = 1; a.w_phase_stride = 0;
-    a.alpha = e.alpha; a.relu = e.relu; a.mask_scale = e.mask_scale;
-    a.dropout = e.dropout; a.keep_prob = e.keep; a.seed = m ? m->seed : 0; a.stream_id = e.stream_id;
-    const double rc = real_cin ? real_cin : Cin;
-    const double flops = 2.0 * a.M * K * K * rc * Cout;
-    const double bytes = 4.0 * (a.M * rc + (double)a.M * Cout + (double)K * K * rc * Cout);
-    // 1x1 score heads: one skinny dimension (skinny.hip); everything else goes through the general tile kernels
-    auto run = [&]() {
-        if (K == 1 && !real_cin && !e.addend && !e.relu && !e.dropout) {
-            if (Cout <= 32 && !e.mask && launch_head_fwd(x, w, e.bias, y, a.M, Cin, Cout, e.alpha, s, m ? m->d_wino_u : nullptr, m ? m->ufl : 0)) return;      // (the filter-bank scratch is idle between convolutions)
-            if (Cin <= 32 && !e.bias && launch_head_dgrad(x, w, e.mask, e.mask_scale, y, a.M, Cout, Cin, e.alpha, s)) return;
-        }
-        launch_igemm(a, 1, s);
-    };
-    { ProfScope ps(m, group, flops, bytes, layer); run(); }
-    return false;
+    IgemmArgs a{}; a.addend = e.addend; a.mask = e.mask; a.alpha = e.alpha; a.mask_scale = e.mask_scale; a.keep_prob = 1.f;
+    conv_direct(m, group, a, x, w, y, N, H, W, Cin, Cout, K, s, 0, layer);
 }
 
 // transposed conv forward (k = 2s) as s*s phase-specific 2x2 convs; wp = phase-packed weights
@@ -825,14 +837,14 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
                 const char* layer = nullptr, bool fuse_dgrad_input = false, const unsigned char* pool_idx = nullptr)
 {
     // the data gradient of the layer after this one may have written this layer's dM instead of dz (backward_blocks): dz then holds nothing
-    const bool promised = m && layer && !m->dm_prefilled.empty() && m->dm_prefilled == layer;
-    if (m) m->dm_prefilled.clear();
+    const bool promised = m && m->pass.dm_prefilled.take(layer);
+    if (m) m->pass.dm_prefilled.drop();      // (a promise to another layer: d_wino_m is about to be rewritten)
     if (m && m->keep_dy && layer) {
         // (dz holds the layer's fp32 dY unless it was handed over in another form: dM from the next layer's data gradient, d(pool) with routing bytes, a bf16 copy only)
         fcn8s_model::KeptDy& k = m->kept_dy[layer];
         const size_t n = (size_t)N * H * W * Cout;
         k.n = 0;
-        if (!(promised || pool_idx || m->dy_bf16_only.count(layer) || m->dz_unwritten.count(layer))) {
+        if (!(promised || pool_idx || m->pass.dy_bf16_only.count(layer) || m->pass.dz_unwritten.count(layer))) {
             if (k.p.grow(n * sizeof(float), s)) { k.n = n; hipMemcpyAsync(k.p, dz, n * sizeof(float), hipMemcpyDeviceToDevice, s); }
             else defer_error(FCN8S_ERR_OOM, "keep_output_gradients: %s's copy cannot be allocated", layer);
         }
@@ -857,7 +869,7 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
             const long long G = bf16_guard_rows(K, Wp_), R = (long long)N * (H + 2 * pad) * Wp_;
             bool db_done = false;
             unsigned short* dyb = dyb_for(m, layer, dz, N, H, W, Cout, K, s, db, &db_done);
-            if (m->db_taken.count(layer)) db_done = true;          // (the kernel that wrote this layer's dY copy added the bias gradient too)
+            if (m->pass.db_taken.count(layer)) db_done = true;          // (the kernel that wrote this layer's dY copy added the bias gradient too)
             if (dyb) {
                 Bf16WgradArgs g{};
                 g.A = it->second + g16_off(G, Cin); g.B = dyb; g.C = dw; g.R = R; g.Ci = Cin; g.Cj = Cout; g.K = K; g.Wp = Wp_; g.a_ps = g.b_ps = g16_ps(N, H, W, K);
@@ -872,13 +884,12 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
             }
         }
     }
-    if (bf16_train_mode(m) && m->train_mode && layer && (m->in_bf16_only.count(layer) || m->dy_bf16_only.count(layer))) {
+    if (bf16_train_mode(m) && m->train_mode && layer && (m->pass.in_bf16_only.count(layer) || m->pass.dy_bf16_only.count(layer))) {
         defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's weight gradient could not run on the bf16 kernel and its fp32 input was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return;
     }
-    if (m && K == 7 && layer && alpha == 1.f && !real_cin && m->train_mode && !m->fft6_xf.empty() && m->fft6_xf == layer) {
-        m->fft6_xf.clear();                                    // weight gradient in the DFT domain (Xf kept by the forward pass)
+    if (m && K == 7 && alpha == 1.f && !real_cin && m->train_mode && m->pass.fft6_xf.take(layer)) {      // weight gradient in the DFT domain (Xf kept by the forward pass)
         if (promised) broken_promise();
-        m->dm_layer.clear(); m->fused_v_layer.clear();
+        m->pass.drop_backward_handoffs();
         conv_fft6_wgrad(m, layer, m->acts[std::string("wv:") + layer].p, dz, dw, db, N, H, W, Cin, Cout, s);
         return;
     }
@@ -911,12 +922,13 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
                       if (fuse_dgrad_input && tile >= 4 && K == 3) fused = launch_wino_input_dout(tile, dz, m->d_wino_v, m->d_wino_m, N, H, W, Cout, s, pool_idx);
                       if (!fused) launch_wino_dout(tile, dz, m->d_wino_m, N, H, W, Cout, s, K);
                   } }
-                // fc6: the non-fused transform above left dM = A dz A^T in d_wino_m; its adjoint data gradient (conv_same) consumes it
+                // fc6: the non-fused transform above left dM = A dz A^T in d_wino_m; its adjoint data gradient (conv_dgrad) consumes it
                 // (not when this step's forward ran through the DFT tiles: a kept F(4x4,4x4) bank would be stale)
-                if (K == 7 && tile == 4 && !fused && Cin % 2 == 0 && bt_gemm_ok(Cout, 4 * Cin) && m->u_train.count(std::string(layer) + "#4") && m->fft6_ready != layer) dm_ready = true;
+                if (K == 7 && tile == 4 && !fused && Cin % 2 == 0 && bt_gemm_ok(Cout, 4 * Cin) && m->u_train.count(std::string(layer) + "#4") && !m->pass.fft6_ready.holds(layer)) dm_ready = true;
             }
-            m->fused_v_layer = fused ? layer : "";
-            m->dm_layer = dm_ready ? layer : "";
+            m->pass.drop_backward_handoffs();
+            if (fused) m->pass.dgrad_v.give(layer);
+            if (dm_ready) m->pass.dm.give(layer);
             { ProfScope ps(m, K == 7 ? "wino_gemm_fc6_wgrad" : "wino_gemm_wgrad", 2.0 * NP * T * Kg * Cout, 4.0 * NP * (T * (double)(Kg + Cout) + (double)Kg * Cout), layer); launch_wgrad(g, s); }
             { ProfScope ps(m, "wino_transform", 0, 4.0 * (9.0 + NP) * Cin * Cout + 4.0 * N * H * W * Cout * (tile >= 4 ? 1.0 / (tile * tile) : 1.0));
               launch_wino_dfilter(tile, m->d_wino_u, dw, Cin, Cout, K, s);
@@ -1118,14 +1130,14 @@ void drop_shape_copies(fcn8s_model* m, bool keep_regrowable = false)
 {
     if (!m->xbf16.empty() || (!keep_regrowable && !(m->xg16.empty() && m->dyg16.empty() && m->q8.empty()))) hipStreamSynchronize(m->stream);
     m->xbf16.clear();
-    m->xg16_filled.clear(); m->dyg16_filled.clear();
+    m->pass.forget_shape_copies(keep_regrowable);
     if (keep_regrowable) {
         for (auto& kv : m->xg16) m->g16_stale.insert("x:" + kv.first);
         for (auto& kv : m->dyg16) m->g16_stale.insert("d:" + kv.first);
         return;
     }
     m->xg16.clear(); m->dyg16.clear(); m->g16_stale.clear();
-    m->q8.clear(); m->q8_filled.clear();
+    m->q8.clear();
 }
 // The banks made from one version of the parameters and kept while the model is frozen, of three kinds: the Winograd filter banks (u_cache)
 // and the bf16 kernels (wbf16_cache), with the record of which of them fcn8s_predict_tta left stale, and fp8_infer's e4m3 weight banks, which
@@ -1372,11 +1384,11 @@ unsigned short* dyb_for(fcn8s_model* m, const char* layer, const float* dy, int 
     if (db_done) *db_done = false;
     unsigned short* p = g16_for(m, m->dyg16, layer, N, H, W, C, K, s);
     if (!p) return nullptr;
-    if (!m->dyg16_filled.count(layer)) {
+    if (!m->pass.dyg16_filled.count(layer)) {
         ProfScope ps(m, "bf16_convert", 0, 4.0 * N * H * W * C + 2.0 * N * H * W * C);
         if (db && launch_f32_to_bf16_padded_colsum(dy, p, db, N, H, W, C, (K - 1) / 2, s, g16_ps(N, H, W, K))) { if (db_done) *db_done = true; }
         else launch_f32_to_bf16_padded(dy, p, N, H, W, C, (K - 1) / 2, s, g16_ps(N, H, W, K));
-        m->dyg16_filled.insert(layer);
+        m->pass.dyg16_filled.insert(layer);
     }
     return p;
 }
@@ -1411,7 +1423,7 @@ void wino_backward_operands(fcn8s_model* m, const char* layer, const float* x, c
     { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cin * nsub2 + (double)P * T * Kg) + (xb ? 2.0 * N * H * W * Cin : 0.0));
       if (xb) launch_wino_input_xb(x, it->second.p, xb, N, H, W, Cin, s, in_rbits_out);
       else launch_wino_input(tile, x, it->second.p, N, H, W, Cin, KS, s, KS == 3 ? in_rbits_out : nullptr);
-      if (in_rbits_out && in_layer && KS == 3) m->rbits_ok.insert(in_layer); }
+      if (in_rbits_out && in_layer && KS == 3) m->pass.rbits_ok.insert(in_layer); }
     const std::string key = std::string(layer) + "#" + std::to_string(tile);
     if ((KS == 3 && tile == 6) || (KS == 7 && tile == 4)) {
         DeviceBuf<float>& tu = m->u_train[key];
@@ -1518,13 +1530,13 @@ static int fp8_conv(fcn8s_model* m, const char* group, const char* layer, const 
     const int ex = fp8_ex(m, layer);
     Q8Buf* xq = q8_for(m, ln, N, H, W, Cin, K, ex, s);
     if (!xq) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of " + ln + "'s e4m3 input copy failed");
-    if (!m->q8_filled.count(ln)) {
+    if (!m->pass.q8_filled.count(ln)) {
         // the fp32 input must have been written by this pass (conv1_1, pool3, pool4): never quantize a stale buffer
-        if (Lx < 0 || m->y_unwritten.count(kFp8Inputs[Lx]))
+        if (Lx < 0 || m->pass.y_unwritten.count(kFp8Inputs[Lx]))
             return fail(m, FCN8S_ERR_STATE, "fp8_infer: " + ln + "'s fp32 input " + (Lx < 0 ? std::string("?") : std::string(kFp8Inputs[Lx])) + " was not written by this pass");
         ProfScope ps(m, "fp8_quantize_x", 0, 5.0 * N * H * W * Cin);
         launch_f32_to_fp8_padded(x, xq->p, N, H, W, Cin, (K - 1) / 2, xq->ps, ex, s);
-        m->q8_filled.insert(ln);
+        m->pass.q8_filled.insert(ln);
     }
     const W8Bank* wb = w8_for(m, layer, wname.c_str(), K * K, Cin, Cout, s);
     if (!wb) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of " + ln + "'s e4m3 weight bank failed");
@@ -1548,7 +1560,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
     if (fp8 && !m->fp8_calibrated)
         return fail(m, FCN8S_ERR_STATE, "fp8_infer: the model has no FP8 calibration (never calibrated, or its parameters changed since): run fcn8s_fp8_calibrate "
                                         "(Engine.calibrate_fp8 / FCN8s.calibrate_fp8) or restore one with fcn8s_fp8_set_calibration first");
-    if (fp8) m->q8_filled.clear();
+    m->pass.begin_forward(fp8);
     bool guard_pending = false;
     if (m->frozen && keeps_banks(m) && !m->banks_stale) {
         // the caller promised constant parameters; a cheap strided fingerprint catches the promise being broken through a side
@@ -1573,13 +1585,11 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
     const bool fill_fp = m->frozen && (!keeps_banks(m) || m->banks_stale);          // (banks_stale: kept storage, contents to be rebuilt)
     if (!m->frozen || fill_fp) prepare_forward_weights(m);        // frozen and the kept banks still valid: so are the padded / phase-packed kernels
     m->fwd_train = train;
-    m->fft6_ready.clear(); m->fft6_xf.clear(); m->fft6_dyf.clear();
     // bf16_train, evaluation / prediction (round 6): the pass takes the TRAINING pass's data flow -- every layer's input as a padded bf16 copy written by its
     // producer's epilogue (no fp32 conv -> conv tensor, no conversion pass), the flat-position kernel, pools on the bf16 copies -- instead of fp32 tensors converted
     // layer by layer for the tile kernel: 13.3 -> 9.3 ms per 16 x 1024x512 batch, 1.55 -> 1.18 ms per single image (profiles/r06_bf16_infer.txt).  Same products in the same order as the training pass:
     // its logits are the training pass's bit for bit (keep_prob 1).  What it keeps for a backward pass that never comes (routing bytes) costs one byte per window.
     const bool cp = train || (bf16_train_mode(m) && m->bf16_infer_copies);
-    m->rbits_ok.clear(); m->y_unwritten.clear(); m->in_bf16_only.clear(); m->fwd_v_layer.clear(); m->xg16_filled.clear();
     if (!m->x0_ready) { ProfScope ps(m, "preprocess", 0, (double)N * H * W * (16 + (dtype ? 12 : 3))); launch_preprocess(img_dev, dtype, A(m, "x0"), (long long)N * H * W, s); }
     const float* x = A(m, "x0");
     int h = H, w = W, cin = 4;
@@ -1588,7 +1598,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
         for (int i = 1; i <= kConvsPerBlock[b]; ++i) {
             char nm[32]; snprintf(nm, sizeof nm, "conv%d_%d", b + 1, i);
             const bool first = (b == 0 && i == 1);
-            Epi e; e.bias = Wp(m, std::string(nm) + "/biases"); e.relu = 1;
+            FwdEpi e; e.bias = Wp(m, std::string(nm) + "/biases"); e.relu = 1;
             const float* wt = first ? m->d_w1pad : Wp(m, std::string(nm) + "/filter");
             if (train && i < kConvsPerBlock[b]) {                                                            // its output is the next conv's input
                 auto it = m->acts.find(std::string("rb:") + nm);
@@ -1613,7 +1623,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                 // this conv and the next one both run through F(6x6,3x3) on the same tile grid: its output transform writes the next conv's
                 // transformed input directly (training: into the buffer kept for that conv's weight gradient) and its own output never exists
                 snprintf(nxt, sizeof nxt, "conv%d_%d", b + 1, i + 1);
-                // the buffer the next conv will read its V from -- conv_same's own rule: the one kept for its weight gradient if the workspace
+                // the buffer the next conv will read its V from -- conv_fwd's own rule: the one kept for its weight gradient if the workspace
                 // has one (whether or not this pass trains), else the shared scratch.  Training: only if that kept buffer exists -- a direct
                 // weight gradient would read the activation that no longer exists.
                 auto it = m->acts.find(std::string("wv:") + nxt);
@@ -1634,7 +1644,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                 }
                 const int rc = fp8_conv(m, "conv3x3_fwd_fp8", nm, x, N, h, w, cin, cout, 3, yq ? nullptr : A(m, nm), yq, 1, s);
                 if (rc) return rc;
-                if (yq) { m->q8_filled.insert(nx); m->y_unwritten.insert(nm); }
+                if (yq) { m->pass.q8_filled.insert(nx); m->pass.y_unwritten.insert(nm); }
                 x = A(m, nm); cin = cout;
                 continue;
             }
@@ -1642,7 +1652,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
             if (first && !bf16_train_mode(m) && !fp8_mode(m) && m->conv1_in_transform && m->widths[0] == 64 && kConvsPerBlock[0] == 2 && m->widths[0] >= m->wino_min_cin && m->wino_min_cin > 0 &&
                 m->d_wino_v && wino_tile_for(m, h, w, 3) == 6) {
                 // conv1_1's only reader is conv1_2's F(6x6,3x3) input transform: that transform evaluates conv1_1 on its own patches, straight from the
-                // image (winograd.hip: wino_input_conv1_kernel), writes conv1_2's V -- into the buffer conv_same will look for it in -- and, in training,
+                // image (winograd.hip: wino_input_conv1_kernel), writes conv1_2's V -- into the buffer conv_fwd will look for it in -- and, in training,
                 // the ReLU record the backward pass masks with.  conv1_1's 134 MB per image are never written or read.
                 auto wv = m->acts.find("wv:conv1_2");
                 auto rb = m->acts.find("rb:conv1_1");
@@ -1651,8 +1661,8 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                     const long long T = wino_tiles(6, N, h, w);
                     ProfScope ps(m, "wino_transform", 0, 4.0 * (4.0 * N * h * w + 64.0 * T * 64.0) + (train ? 8.0 * N * h * w : 0.0), nm);
                     launch_wino_input_conv1(x, m->d_w1pad, e.bias, vdst, N, h, w, s, train ? (unsigned*)rb->second.p : nullptr);
-                    if (train) m->rbits_ok.insert(nm);
-                    m->fwd_v_layer = "conv1_2"; m->y_unwritten.insert(nm);
+                    if (train) m->pass.rbits_ok.insert(nm);
+                    m->pass.fwd_v.give("conv1_2"); m->pass.y_unwritten.insert(nm);
                     done = true;
                 }
             }
@@ -1664,13 +1674,13 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                     y16 = xg16_for(m, "conv1_2", N, h, w, m->widths[0], 3, s);
                 ProfScope ps(m, "conv1_1_fwd", 2.0 * N * h * w * 27.0 * m->widths[0], 4.0 * N * h * w * 3.0 + (y16 ? 2.0 : 4.0) * N * h * w * m->widths[0], nm);
                 done = launch_conv1_fwd(x, m->d_w1pad, e.bias, y16 ? nullptr : A(m, nm), m->d_w1pad + 12 * 4 * (size_t)m->widths[0], N, h, w, m->widths[0], m->conv1_tiled, s, y16, g16_ps(N, h, w, 3));
-                if (done && y16) { m->xg16_filled.insert("conv1_2"); m->y_unwritten.insert(nm); m->in_bf16_only.insert("conv1_2"); }
+                if (done && y16) { m->pass.xg16_filled.insert("conv1_2"); m->pass.y_unwritten.insert(nm); m->pass.in_bf16_only.insert("conv1_2"); }
             }
             if (!done && bf16_train_mode(m) && !first) {
                 // FCN8S_PREC_BF16_TRAIN: every convolution but conv1_1 (3 input channels) as a direct convolution with bf16-rounded operands; the
                 // training pass keeps the layer's padded bf16 input copy for its weight gradient (the convolution starts from that copy)
                 unsigned short* xb = cp ? xg16_for(m, nm, N, h, w, cin, 3, s) : nullptr;
-                if (xb && !m->xg16_filled.count(nm)) {
+                if (xb && !m->pass.xg16_filled.count(nm)) {
                     ProfScope ps(m, "bf16_convert", 0, 4.0 * N * h * w * cin + 2.0 * N * (h + 2) * (w + 2) * cin); launch_f32_to_bf16_padded(x, xb, N, h, w, cin, 1, s, g16_ps(N, h, w, 3));
                 }
                 // the next convolution of the block reads this output as ITS padded bf16 input: this kernel's epilogue writes that copy
@@ -1693,8 +1703,8 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                 done = bf16_conv_layer(m, "conv3x3_fwd_bf16", (std::string(nm) + "/filter").c_str(), (std::string(nm) + "/biases").c_str(), x, only16 ? nullptr : A(m, nm),
                                        N, h, w, cin, m->widths[b], 3, 0, 1.f, 0, s, /*allow_small=*/false, xb, /*any_shape=*/true, yb, 1, g16_ps(N, h, w, 3), g16_ps(N, h, w, 3));
                 if (!done) return fail(m, FCN8S_ERR_SHAPE, std::string("bf16_train: ") + nm + " does not fit the bf16 convolution kernel");
-                if (done && yb) m->xg16_filled.insert(nx);
-                if (done && only16) { m->y_unwritten.insert(nm); if (!pool16) m->in_bf16_only.insert(nx); }
+                if (done && yb) m->pass.xg16_filled.insert(nx);
+                if (done && only16) { m->pass.y_unwritten.insert(nm); if (!pool16) m->pass.in_bf16_only.insert(nx); }
             }
             if (!done && bf16_fwd_mode(m) && b >= 2) {
                 // FCN8S_PREC_BF16_FWD: conv3_1 .. conv5_3 as direct convolutions with bf16-rounded operands on the 256 x 256 bf16 kernel (the
@@ -1709,7 +1719,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                     if (i > 1) {
                         snprintf(prev, sizeof prev, "conv%d_%d", b + 1, i - 1);
                         auto it = m->acts.find(std::string("rb:") + prev);
-                        if (it != m->acts.end() && !m->rbits_ok.count(prev)) irb = (unsigned*)it->second.p;
+                        if (it != m->acts.end() && !m->pass.rbits_ok.count(prev)) irb = (unsigned*)it->second.p;
                     }
                     wino_backward_operands(m, nm, x, wt, N, h, w, cin, m->widths[b], 3, s, irb, irb ? prev : nullptr, xb);
                 };
@@ -1718,12 +1728,12 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                                        N, h, w, cin, m->widths[b], 3, 0, 1.f, 0, s, /*allow_small=*/false, xb);
                 if (done && train && !xb) operands();
             }
-            if (!done) pooled = conv_same(m, first ? "conv1_1_fwd" : "conv3x3_fwd", x, wt, A(m, nm), N, h, w, cin, m->widths[b], 3, e, s, first ? 3 : 0, nm);
+            if (!done) pooled = conv_fwd(m, first ? "conv1_1_fwd" : "conv3x3_fwd", x, wt, A(m, nm), N, h, w, cin, m->widths[b], 3, e, s, first ? 3 : 0, nm);
             x = A(m, nm); cin = m->widths[b];
         }
         snprintf(pn, sizeof pn, "pool%d", b + 1);
         if (fp8) {
-            m->pool_fused[b] = false; m->pool_routed[b] = false;
+            m->pass.pool_fused[b] = false; m->pass.pool_routed[b] = false;
             if (b != 2 && b != 3) {
                 // byte max of the last conv's e4m3 copy straight into the consumer's copy (conv<b+2>_1, pad 1; fc6, pad (k - 1) / 2)
                 char pin[32], cons[32]; int ck = 3;
@@ -1733,7 +1743,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                 if (!yq) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed");
                 const Q8Buf& xi = m->q8[pin];
                 { ProfScope ps(m, "maxpool_fwd_fp8", 0, 1.25 * N * h * w * cin); launch_maxpool_fp8(xi.p, xi.ps, yq->p, yq->ps, N, h, w, cin, (ck - 1) / 2, s); }
-                m->q8_filled.insert(cons); m->y_unwritten.insert(pn);
+                m->pass.q8_filled.insert(cons); m->pass.y_unwritten.insert(pn);
             } else {
                 ProfScope ps(m, "maxpool_fwd", 0, 4.0 * N * h * w * cin * 1.25);
                 launch_maxpool_fwd(x, A(m, pn), N, h, w, cin, s);
@@ -1741,8 +1751,8 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
             x = A(m, pn); h /= 2; w /= 2;
             continue;
         }
-        m->pool_fused[b] = pooled && train;
-        m->pool_routed[b] = false;
+        m->pass.pool_fused[b] = pooled && train;
+        m->pass.pool_routed[b] = false;
         if (!pooled && bf16_train_mode(m) && cp && m->bf16_fuse_pool && cin % 4 == 0) {
             // bf16_train, training: the pool keeps its routing bytes (the backward pass reads one byte per window instead of the block's last activation)
             // and writes the consumer's padded bf16 copy itself -- conv<b+2>_1 (pad 1) or fc6 (pad 3); pool1, pool2 and pool5 have no other reader, so
@@ -1756,21 +1766,21 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
             char ix[16]; snprintf(ix, sizeof ix, "pidx%d", b + 1);
             char pin[32]; snprintf(pin, sizeof pin, "pool%din", b + 1);
             auto pi = m->xg16.find(pin);
-            const bool in16 = only16 && pi != m->xg16.end() && pi->second && m->xg16_filled.count(pin);      // the last conv wrote only its bf16 copy
+            const bool in16 = only16 && pi != m->xg16.end() && pi->second && m->pass.xg16_filled.count(pin);      // the last conv wrote only its bf16 copy
             ProfScope ps(m, "maxpool_fwd", 0, (in16 ? 2.0 : 4.0) * N * h * w * cin + 4.0 * N * h * w * cin * (only16 ? 0.0625 : 0.3125) + (yb ? 0.5 * N * h * w * cin : 0.0));
             if (in16) launch_maxpool_fwd_route16(pi->second + g16_off(bf16_guard_rows(3, w + 2), cin), g16_ps(N, h, w, 3), (unsigned char*)A(m, ix), N, h, w, cin, s, yb, (ck - 1) / 2, g16_ps(N, h / 2, w / 2, ck));
             else launch_maxpool_fwd_route(x, only16 ? nullptr : A(m, pn), (unsigned char*)A(m, ix), N, h, w, cin, s, yb, (ck - 1) / 2, g16_ps(N, h / 2, w / 2, ck),
                                           /*round16=*/(b != 2 && b != 3) ? 1 : 0);
-            m->pool_routed[b] = true; pooled = true;
-            if (yb) m->xg16_filled.insert(cons);
-            if (only16) { m->y_unwritten.insert(pn); m->in_bf16_only.insert(cons); }
+            m->pass.pool_routed[b] = true; pooled = true;
+            if (yb) m->pass.xg16_filled.insert(cons);
+            if (only16) { m->pass.y_unwritten.insert(pn); m->pass.in_bf16_only.insert(cons); }
         }
         if (!pooled) {
             // a block whose last conv did not run through the Winograd output transform (bf16 modes) but whose backward pass does run in the
             // Winograd domain: keep the same routing bytes, so that d(pool) is routed inside wino_dout_kernel and dZ is never written
             const bool route = train && cin % 4 == 0 && pool_backward_fused(m, b + 1, true);
             ProfScope ps(m, "maxpool_fwd", 0, 4.0 * N * h * w * cin * (route ? 1.3125 : 1.25));
-            if (route) { char ix[16]; snprintf(ix, sizeof ix, "pidx%d", b + 1); launch_maxpool_fwd_route(x, A(m, pn), (unsigned char*)A(m, ix), N, h, w, cin, s); m->pool_fused[b] = true; }
+            if (route) { char ix[16]; snprintf(ix, sizeof ix, "pidx%d", b + 1); launch_maxpool_fwd_route(x, A(m, pn), (unsigned char*)A(m, ix), N, h, w, cin, s); m->pass.pool_fused[b] = true; }
             else launch_maxpool_fwd(x, A(m, pn), N, h, w, cin, s);
         }
         x = A(m, pn); h /= 2; w /= 2;
@@ -1783,11 +1793,11 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
         const Q8Buf* q7 = q8_for(m, "fc7", N, h5, w5, m->widths[5], 1, fp8_ex(m, "fc7"), s);
         if (!q7) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed");
         int rc = fp8_conv(m, "fc6_fwd_fp8", "fc6", x, N, h5, w5, m->widths[4], m->widths[5], m->fc6k, nullptr, q7, 0, s); if (rc) return rc;
-        m->q8_filled.insert("fc7"); m->y_unwritten.insert("fc6");
+        m->pass.q8_filled.insert("fc7"); m->pass.y_unwritten.insert("fc6");
         rc = fp8_conv(m, "fc7_fwd_fp8", "fc7", A(m, "fc6"), N, h5, w5, m->widths[5], m->widths[6], 1, A(m, "fc7"), nullptr, 0, s); if (rc) return rc;
     } else if (bf16_train_mode(m)) {
         unsigned short* xb6 = cp ? xg16_for(m, "fc6", N, h5, w5, m->widths[4], m->fc6k, s) : nullptr;
-        if (xb6 && !m->xg16_filled.count("fc6")) { ProfScope ps(m, "bf16_convert", 0, 6.0 * N * h5 * w5 * m->widths[4]); launch_f32_to_bf16_padded(x, xb6, N, h5, w5, m->widths[4], (m->fc6k - 1) / 2, s, g16_ps(N, h5, w5, m->fc6k)); }
+        if (xb6 && !m->pass.xg16_filled.count("fc6")) { ProfScope ps(m, "bf16_convert", 0, 6.0 * N * h5 * w5 * m->widths[4]); launch_f32_to_bf16_padded(x, xb6, N, h5, w5, m->widths[4], (m->fc6k - 1) / 2, s, g16_ps(N, h5, w5, m->fc6k)); }
         unsigned short* xb7 = cp ? xg16_for(m, "fc7", N, h5, w5, m->widths[5], 1, s) : nullptr;
         const bool fuse7 = xb7 != nullptr && m->bf16_acts;      // fc7's input copy comes out of fc6's epilogue (16-byte stores since the tile kernel's epilogue goes through LDS)
         if (!bf16_conv_layer(m, "fc6_fwd_bf16", "fc6/weights", "fc6/biases", x, A(m, "fc6"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, drop, keep_prob, m->drop_stream, s, false, xb6, true,
@@ -1804,21 +1814,21 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
         bf16_conv_layer(m, "fc7_fwd_bf16", "fc7/weights", "fc7/biases", A(m, "fc6"), A(m, "fc7"), N, h5, w5, m->widths[5], m->widths[6], 1, drop, keep_prob, m->drop_stream + 1, s);
     } else {
         {
-            Epi e; e.bias = Wp(m, "fc6/biases"); e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream;
-            conv_same(m, "fc6_fwd", x, Wp(m, "fc6/weights"), A(m, "fc6"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, e, s, 0, "fc6");
+            FwdEpi e; e.bias = Wp(m, "fc6/biases"); e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream;
+            conv_fwd(m, "fc6_fwd", x, Wp(m, "fc6/weights"), A(m, "fc6"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, e, s, 0, "fc6");
         }
         {
-            Epi e; e.bias = Wp(m, "fc7/biases"); e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream + 1;
-            conv_same(m, "fc7_fwd", A(m, "fc6"), Wp(m, "fc7/weights"), A(m, "fc7"), N, h5, w5, m->widths[5], m->widths[6], 1, e, s);
+            FwdEpi e; e.bias = Wp(m, "fc7/biases"); e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream + 1;
+            conv_fwd(m, "fc7_fwd", A(m, "fc6"), Wp(m, "fc7/weights"), A(m, "fc7"), N, h5, w5, m->widths[5], m->widths[6], 1, e, s);
         }
     }
     // decoder (fcn8s_tensorflow.py:171-233)
-    { Epi e; e.bias = Wp(m, "pool3_1x1/bias"); e.alpha = 0.0001f;
-      conv_same(m, "score1x1_fwd", A(m, "pool3"), Wp(m, "pool3_1x1/kernel"), A(m, "p3"), N, H / 8, W / 8, m->widths[2], C, 1, e, s); }
-    { Epi e; e.bias = Wp(m, "pool4_1x1/bias"); e.alpha = 0.01f;
-      conv_same(m, "score1x1_fwd", A(m, "pool4"), Wp(m, "pool4_1x1/kernel"), A(m, "p4"), N, H / 16, W / 16, m->widths[3], C, 1, e, s); }
-    { Epi e; e.bias = Wp(m, "fc7_1x1/bias");
-      conv_same(m, "score1x1_fwd", A(m, "fc7"), Wp(m, "fc7_1x1/kernel"), A(m, "s7"), N, h5, w5, m->widths[6], C, 1, e, s); }
+    { FwdEpi e; e.bias = Wp(m, "pool3_1x1/bias"); e.alpha = 0.0001f;
+      conv_fwd(m, "score1x1_fwd", A(m, "pool3"), Wp(m, "pool3_1x1/kernel"), A(m, "p3"), N, H / 8, W / 8, m->widths[2], C, 1, e, s); }
+    { FwdEpi e; e.bias = Wp(m, "pool4_1x1/bias"); e.alpha = 0.01f;
+      conv_fwd(m, "score1x1_fwd", A(m, "pool4"), Wp(m, "pool4_1x1/kernel"), A(m, "p4"), N, H / 16, W / 16, m->widths[3], C, 1, e, s); }
+    { FwdEpi e; e.bias = Wp(m, "fc7_1x1/bias");
+      conv_fwd(m, "score1x1_fwd", A(m, "fc7"), Wp(m, "fc7_1x1/kernel"), A(m, "s7"), N, h5, w5, m->widths[6], C, 1, e, s); }
     tconv_fwd(m, A(m, "s7"), m->d_tph[0], Wp(m, "fc7_conv2d_trans/bias"), A(m, "p4"), A(m, "a4"), N, h5, w5, C, 4, 2, s);
     tconv_fwd(m, A(m, "a4"), m->d_tph[1], Wp(m, "fc7_pool4_conv2d_trans/bias"), A(m, "p3"), A(m, "a3"), N, H / 16, W / 16, C, 4, 2, s);
     if (m->tconv_gemm && m->logits_b) tconv_gemm_fwd(m);
@@ -1924,7 +1934,7 @@ void prepare_backward_weights(fcn8s_model* m)
     hipStream_t s = m->stream;
     ProfScope ps(m, "weight_relayout", 0, 8.0 * ((double)m->widths[5] * m->widths[6] +
                                                  (double)m->C * (m->widths[2] + m->widths[3] + m->widths[6])));
-    // (the 3x3 layers' and fc6's flipped + transposed kernels are made on demand in conv_same: the adjoint Winograd data gradients read
+    // (the 3x3 layers' and fc6's flipped + transposed kernels are made on demand in conv_dgrad: the adjoint Winograd data gradients read
     // the forward filter banks)
     launch_flip_transpose(Wp(m, "fc7/weights"), WTp(m, "fc7/weights"), 1, m->widths[5], m->widths[6], s);
     launch_flip_transpose(Wp(m, "pool3_1x1/kernel"), WTp(m, "pool3_1x1/kernel"), 1, m->widths[2], m->C, s);
@@ -1963,7 +1973,7 @@ void backward_head(fcn8s_model* m)
     // a3 = tconv4x4s2(a4) + p3 ; p3 = conv1x1(pool3 * 1e-4)
     conv_wgrad(m, "score1x1_wgrad", A(m, "pool3"), m->da3, Gp(m, "pool3_1x1/kernel"), Gp(m, "pool3_1x1/bias"), N, h3, w3, m->widths[2], C, 1, 0.0001f, s);
     l2_grad(m, "pool3_1x1/kernel");
-    { Epi e; e.alpha = 0.0001f; conv_same(m, "score1x1_dgrad", m->da3, WTp(m, "pool3_1x1/kernel"), m->gskip3, N, h3, w3, C, m->widths[2], 1, e, s); }
+    { DgradEpi e; e.alpha = 0.0001f; conv_dgrad(m, "score1x1_dgrad", m->da3, WTp(m, "pool3_1x1/kernel"), m->gskip3, N, h3, w3, C, m->widths[2], 1, e, s); }
     tconv_wgrad(m, A(m, "a4"), m->da3, Gp(m, "fc7_pool4_conv2d_trans/kernel"), N, h4, w4, C, 4, 2, s);
     launch_colsum(m->da3, Gp(m, "fc7_pool4_conv2d_trans/bias"), (long long)N * h3 * w3, C, s);
     tconv_dgrad(m, m->da3, Wp(m, "fc7_pool4_conv2d_trans/kernel"), m->da4, N, h4, w4, C, 4, 2, s);
@@ -1971,7 +1981,7 @@ void backward_head(fcn8s_model* m)
     // a4 = tconv4x4s2(s7) + p4 ; p4 = conv1x1(pool4 * 1e-2)
     conv_wgrad(m, "score1x1_wgrad", A(m, "pool4"), m->da4, Gp(m, "pool4_1x1/kernel"), Gp(m, "pool4_1x1/bias"), N, h4, w4, m->widths[3], C, 1, 0.01f, s);
     l2_grad(m, "pool4_1x1/kernel");
-    { Epi e; e.alpha = 0.01f; conv_same(m, "score1x1_dgrad", m->da4, WTp(m, "pool4_1x1/kernel"), m->gskip4, N, h4, w4, C, m->widths[3], 1, e, s); }
+    { DgradEpi e; e.alpha = 0.01f; conv_dgrad(m, "score1x1_dgrad", m->da4, WTp(m, "pool4_1x1/kernel"), m->gskip4, N, h4, w4, C, m->widths[3], 1, e, s); }
     tconv_wgrad(m, A(m, "s7"), m->da4, Gp(m, "fc7_conv2d_trans/kernel"), N, h5, w5, C, 4, 2, s);
     launch_colsum(m->da4, Gp(m, "fc7_conv2d_trans/bias"), (long long)N * h4 * w4, C, s);
     tconv_dgrad(m, m->da4, Wp(m, "fc7_conv2d_trans/kernel"), m->ds7, N, h5, w5, C, 4, 2, s);
@@ -1979,8 +1989,8 @@ void backward_head(fcn8s_model* m)
     // s7 = conv1x1(fc7)
     conv_wgrad(m, "score1x1_wgrad", A(m, "fc7"), m->ds7, Gp(m, "fc7_1x1/kernel"), Gp(m, "fc7_1x1/bias"), N, h5, w5, m->widths[6], C, 1, 1.f, s);
     l2_grad(m, "fc7_1x1/kernel");
-    { Epi e; e.mask = A(m, "fc7"); e.mask_scale = inv_keep;
-      conv_same(m, "score1x1_dgrad", m->ds7, WTp(m, "fc7_1x1/kernel"), m->gbuf[0], N, h5, w5, C, m->widths[6], 1, e, s); }
+    { DgradEpi e; e.mask = A(m, "fc7"); e.mask_scale = inv_keep;
+      conv_dgrad(m, "score1x1_dgrad", m->ds7, WTp(m, "fc7_1x1/kernel"), m->gbuf[0], N, h5, w5, C, m->widths[6], 1, e, s); }
     // fc7
     conv_wgrad(m, "fc7_wgrad", A(m, "fc6"), m->gbuf[0], Gp(m, "fc7/weights"), Gp(m, "fc7/biases"), N, h5, w5, m->widths[5], m->widths[6], 1, 1.f, s, 0, "fc7");
     mark_bucket_final(m, 0, s);
@@ -1993,13 +2003,13 @@ void backward_fc6(fcn8s_model* m)
     const int N = m->N, H = m->H, W = m->W;
     const int h5 = H / 32, w5 = W / 32;
     const float inv_keep = (m->train_mode && m->keep_prob < 1.f) ? 1.f / m->keep_prob : 1.f;
-    { Epi e; e.mask = A(m, "fc6"); e.mask_scale = inv_keep; e.w_fwd = Wp(m, "fc7/weights"); e.yb_layer = "fc6"; e.yb_K = m->fc6k;      // (w_fwd + the layer name: the bf16_train branch of conv_same)
-      conv_same(m, "fc7_dgrad", m->gbuf[0], WTp(m, "fc7/weights"), m->gbuf[1], N, h5, w5, m->widths[6], m->widths[5], 1, e, s, 0, "fc7"); }
+    { DgradEpi e; e.mask = A(m, "fc6"); e.mask_scale = inv_keep; e.w_fwd = Wp(m, "fc7/weights"); e.yb_layer = "fc6"; e.yb_K = m->fc6k;      // (w_fwd + the layer name: the bf16_train branch of conv_dgrad)
+      conv_dgrad(m, "fc7_dgrad", m->gbuf[0], WTp(m, "fc7/weights"), m->gbuf[1], N, h5, w5, m->widths[6], m->widths[5], 1, e, s, "fc7"); }
     // fc6
     conv_wgrad(m, "fc6_wgrad", A(m, "pool5"), m->gbuf[1], Gp(m, "fc6/weights"), Gp(m, "fc6/biases"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, 1.f, s, 0, "fc6");
     mark_bucket_final(m, 1, s);
-    { Epi e; e.dgrad = 1; e.w_fwd = Wp(m, "fc6/weights"); e.lazy_wt = 1;      // (flipped + transposed copy only if the adjoint path is not taken)
-      conv_same(m, "fc6_dgrad", m->gbuf[1], WTp(m, "fc6/weights"), m->gbuf[0], N, h5, w5, m->widths[5], m->widths[4], m->fc6k, e, s, 0, "fc6"); }
+    { DgradEpi e; e.w_fwd = Wp(m, "fc6/weights"); e.lazy_wt = 1;      // (flipped + transposed copy only if the adjoint path is not taken)
+      conv_dgrad(m, "fc6_dgrad", m->gbuf[1], WTp(m, "fc6/weights"), m->gbuf[0], N, h5, w5, m->widths[5], m->widths[4], m->fc6k, e, s, "fc6"); }
     m->gcur = 0;   // gbuf[0] holds d(pool5)
 }
 
@@ -2018,7 +2028,7 @@ void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
         const unsigned char* pidx = nullptr;
         {
             char ix[16]; snprintf(ix, sizeof ix, "pidx%d", b);
-            const bool wino_both = pool_backward_fused(m, b, m->pool_fused[b - 1]);
+            const bool wino_both = pool_backward_fused(m, b, m->pass.pool_fused[b - 1]);
             if (wino_both) pidx = (const unsigned char*)A(m, ix);
         }
         bool pool_done = false;
@@ -2027,12 +2037,12 @@ void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
             // column sums: the pool's backward kernel writes exactly those (gbuf[gcur ^ 1] stays unwritten; the "dz" handed on below is never dereferenced)
             unsigned short* dzb = g16_for(m, m->dyg16, last, N, h, w, cw, 3, s);
             if (dzb) {
-                ProfScope ps(m, "maxpool_bwd", 0, 4.0 * N * h * w * cw * (m->pool_routed[b - 1] ? 0.3125 : 1.25) + 2.0 * N * h * w * cw);
+                ProfScope ps(m, "maxpool_bwd", 0, 4.0 * N * h * w * cw * (m->pass.pool_routed[b - 1] ? 0.3125 : 1.25) + 2.0 * N * h * w * cw);
                 char ix[16]; snprintf(ix, sizeof ix, "pidx%d", b);
                 pool_done = launch_maxpool_bwd_bf16(A(m, last), m->gbuf[m->gcur], dzb, Gp(m, std::string(last) + "/biases"), N, h, w, cw, s,
-                                                    m->pool_routed[b - 1] ? (const unsigned char*)A(m, ix) : nullptr, g16_ps(N, h, w, 3));
+                                                    m->pass.pool_routed[b - 1] ? (const unsigned char*)A(m, ix) : nullptr, g16_ps(N, h, w, 3));
             }
-            if (pool_done) { m->dyg16_filled.insert(last); m->db_taken.insert(last); m->dz_unwritten.insert(last); m->gcur ^= 1; }
+            if (pool_done) { m->pass.dyg16_filled.insert(last); m->pass.db_taken.insert(last); m->pass.dz_unwritten.insert(last); m->gcur ^= 1; }
         }
         if (!pidx && !pool_done) {
             ProfScope ps(m, "maxpool_bwd", 0, 4.0 * N * h * w * cw * 2.25);
@@ -2048,17 +2058,17 @@ void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
             else if (b > 1) { snprintf(inname, sizeof inname, "pool%d", b - 1); xin = A(m, inname); cin = m->widths[b - 2]; }
             else { xin = A(m, "x0"); cin = 4; real_cin = 3; }
             const bool first = (b == 1 && i == 1);
-            // the data-gradient conv (cw -> cin channels) takes the Winograd path under the same conditions as conv_same()
+            // the data-gradient conv (cw -> cin channels) takes the Winograd path under the same conditions as conv_dgrad()
             const bool dgrad_wino = !first && m->wino_min_cin > 0 && cw >= m->wino_min_cin && m->d_wino_v && wino_tile_for(m, h, w) >= 4 &&
                                     cw % 16 == 0 && cin % 64 == 0;
             const unsigned char* pix = i == nconv ? pidx : nullptr;
             conv_wgrad(m, first ? "conv1_1_wgrad" : "conv3x3_wgrad", xin, dz, Gp(m, std::string(nm) + "/filter"), Gp(m, std::string(nm) + "/biases"),
                        N, h, w, cin, cw, 3, 1.f, s, real_cin, nm, dgrad_wino, pix);
             if (first) break;
-            Epi e; e.dgrad = 1; e.w_fwd = Wp(m, std::string(nm) + "/filter"); e.lazy_wt = 1;
+            DgradEpi e; e.w_fwd = Wp(m, std::string(nm) + "/filter"); e.lazy_wt = 1;
             if (i > 1) {                                                   // ReLU of the previous conv
                 e.mask = xin; e.mask_scale = 1.f; e.yb_layer = inname; e.yb_K = 3;
-                if (m->rbits_ok.count(inname)) e.relu_bits_in = (const unsigned*)A(m, (std::string("rb:") + inname).c_str());
+                if (m->pass.rbits_ok.count(inname)) e.relu_bits_in = (const unsigned*)A(m, (std::string("rb:") + inname).c_str());
                 // The previous conv takes this gradient only through dM = A dZ A^T (weight gradient in the Winograd domain, adjoint data
                 // gradient): the gather kernel can write dM directly.  Conditions = those of conv_wgrad's adjoint branch for that layer.
                 const int cin_prev = i > 2 ? cw : (b > 1 ? m->widths[b - 2] : 4);
@@ -2071,7 +2081,7 @@ void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
             }
             else if (b == 5) e.addend = m->gskip4;                        // d(pool4) also receives the pool4_1x1 path
             else if (b == 4) e.addend = m->gskip3;                        // d(pool3) also receives the pool3_1x1 path
-            conv_same(m, "conv3x3_dgrad", dz, WTp(m, std::string(nm) + "/filter"), m->gbuf[m->gcur ^ 1], N, h, w, cw, cin, 3, e, s, 0, nm);
+            conv_dgrad(m, "conv3x3_dgrad", dz, WTp(m, std::string(nm) + "/filter"), m->gbuf[m->gcur ^ 1], N, h, w, cw, cin, 3, e, s, nm);
             m->gcur ^= 1;
         }
     }
@@ -2085,8 +2095,7 @@ int do_backward_bucket(fcn8s_model* m, int bucket)
     if (!m->have_loss || !m->train_mode) return fail(m, FCN8S_ERR_STATE, "fcn8s_backward_bucket: call fcn8s_forward_loss first");
     if (bucket != m->next_bucket) return fail(m, FCN8S_ERR_STATE, "fcn8s_backward_bucket: buckets must be run in order 0, 1, ... fcn8s_num_buckets() - 1");
     if (bucket == 0) {
-        m->dyg16_filled.clear(); m->db_taken.clear(); m->dy_bf16_only.clear(); m->dz_unwritten.clear();
-        m->dm_prefilled.clear();                                           // (a promise left over from a backward pass that ended in an error)
+        m->pass.begin_backward();
         for (int b = 0; b < kNumBuckets; ++b) m->bucket_final[b] = false;
         // (a caller that skipped fcn8s_apply_update after fcn8s_allreduce_bucket: the gradient buffer is about to be cleared and rewritten,
         //  so this stream first waits for whatever the library's communicator still has in flight on it)
@@ -2310,7 +2319,7 @@ int fcn8s_fp8_calibrate(fcn8s_model* m, const void* images, int dtype, int N, in
         for (int L = 0; L < FCN8S_FP8_LAYERS; ++L) {
             const char* in = kFp8Inputs[L];
             auto it = m->acts.find(in);
-            if (it == m->acts.end() || !it->second.p || m->y_unwritten.count(in))
+            if (it == m->acts.end() || !it->second.p || m->pass.y_unwritten.count(in))
                 return fail(m, FCN8S_ERR_STATE, std::string("fcn8s_fp8_calibrate: the fp32 pass did not materialise ") + in);
             const long long n = (long long)N * (H / kFp8InDiv[L]) * (W / kFp8InDiv[L]) * m->widths[kFp8InWidth[L]];
             launch_amax(it->second.p, n, m->d_fp8_amax + L, m->stream);
@@ -3426,7 +3435,7 @@ int fcn8s_get_activation(fcn8s_model* m, const char* name, float* host, size_t n
     }
     if (strncmp(name, "q8:", 3) == 0) {      // FCN8S_PREC_FP8_INFER: a layer's e4m3 input copy of the last pass, dequantized (2^ex code: exact in fp32) as [N,H,W,Cin]
         auto k = m->q8.find(name + 3);
-        if (!fp8_mode(m) || k == m->q8.end() || !k->second.p || !m->q8_filled.count(name + 3) || fp8_layer(name + 3) < 0)
+        if (!fp8_mode(m) || k == m->q8.end() || !k->second.p || !m->pass.q8_filled.count(name + 3) || fp8_layer(name + 3) < 0)
             return fail(m, FCN8S_ERR_STATE, std::string("no e4m3 input copy of '") + (name + 3) + "': run an fp8_infer evaluation / prediction first (FP8 layers: conv1_2 .. conv5_3, fc6, fc7)");
         const Q8Buf& b = k->second;
         const size_t need = (size_t)b.N * b.H * b.W * b.C;
@@ -3457,7 +3466,7 @@ int fcn8s_get_activation(fcn8s_model* m, const char* name, float* host, size_t n
         m->logits_nhwc_valid = true;
     }
     if (n != it->second.n) return fail(m, FCN8S_ERR_SHAPE, std::string("activation '") + name + "' has " + std::to_string(it->second.n) + " elements");
-    if (m->y_unwritten.count(name))
+    if (m->pass.y_unwritten.count(name))
         return fail(m, FCN8S_ERR_STATE, std::string("activation '") + name + "' was not materialised by the last forward pass: " +
                                         (fp8_mode(m) ? std::string("fp8_infer keeps it only as its consumer's e4m3 copy (fcn8s_get_activation(m, \"q8:<consumer>\", ...))") :
                                          bf16_train_mode(m) ? "bf16_train keeps a conv -> conv activation only as the consumer's padded bf16 copy (option \"bf16_acts\" = 0 keeps the fp32 tensor too)" :
@@ -3476,7 +3485,7 @@ int fcn8s_get_relu_record(fcn8s_model* m, const char* layer, unsigned char* host
     if (sscanf(layer, "conv%d_%d", &b, &i) != 2 || b < 1 || b > 5 || i < 1 || i >= kConvsPerBlock[b - 1])
         return fail(m, FCN8S_ERR_NOT_FOUND, std::string("fcn8s_get_relu_record: '") + layer + "' is not a conv that feeds another conv");
     auto it = m->acts.find(std::string("rb:") + layer);
-    if (it == m->acts.end() || !m->rbits_ok.count(layer))
+    if (it == m->acts.end() || !m->pass.rbits_ok.count(layer))
         return fail(m, FCN8S_ERR_STATE, std::string("fcn8s_get_relu_record: the last forward pass kept no ReLU record of '") + layer + "' (the backward pass reads the activation itself)");
     const int H = m->H >> (b - 1), W = m->W >> (b - 1), Cc = m->widths[b - 1], N = m->N;
     if (n != (size_t)N * H * W * Cc) return fail(m, FCN8S_ERR_SHAPE, std::string("ReLU record of '") + layer + "' has " + std::to_string((size_t)N * H * W * Cc) + " elements");
@@ -3510,7 +3519,7 @@ int fcn8s_get_pool_routing(fcn8s_model* m, int block, unsigned char* host, size_
     if (n != want) return fail(m, FCN8S_ERR_SHAPE, "pool routing of block " + std::to_string(block) + " has " + std::to_string(want) + " bytes");
     char ix[16]; snprintf(ix, sizeof ix, "pidx%d", block);
     unsigned char* d = (unsigned char*)A(m, ix);
-    if (!pool_backward_fused(m, block, m->pool_fused[block - 1]) && !m->pool_routed[block - 1]) {      // (pool_routed: the forward pool of bf16_train kept the bytes)
+    if (!pool_backward_fused(m, block, m->pass.pool_fused[block - 1]) && !m->pass.pool_routed[block - 1]) {      // (pool_routed: the forward pool of bf16_train kept the bytes)
         // the backward pass routes through maxpool_bwd_kernel on the block's last conv output (materialised in this case): same rule
         char last[32]; snprintf(last, sizeof last, "conv%d_%d", block, kConvsPerBlock[block - 1]);
         launch_maxpool_route(A(m, last), d, m->N, h, w, cw, m->stream);
@@ -3668,8 +3677,8 @@ int fcn8s_op_conv2d(void* stream, const float* x, const float* w, const float* b
                     int N, int H, int W, int Cin, int Cout, int K, int relu)
 {
     if (Cin % 4 || Cout % 4 || K % 2 == 0) return fail(nullptr, FCN8S_ERR_BAD_ARG, "conv2d: Cin, Cout must be multiples of 4 and K odd");
-    Epi e; e.bias = bias; e.relu = relu;
-    conv_same(nullptr, "", x, w, y, N, H, W, Cin, Cout, K, e, (hipStream_t)stream);
+    FwdEpi e; e.bias = bias; e.relu = relu;
+    conv_fwd(nullptr, "", x, w, y, N, H, W, Cin, Cout, K, e, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
 
@@ -3683,7 +3692,7 @@ int fcn8s_op_conv2d_winograd(void* stream, const float* x, const float* w, const
     DeviceBuf<float> u, v, mm;
     if (!u.grow(P * Kg * Cout * 4, s) || !v.grow(P * (size_t)wino_slab(T, (int)Kg) * 4, s) || !mm.grow(P * (size_t)wino_slab(T, Cout) * 4, s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
     WinoEpi we; we.bias = bias; we.relu = relu;
-    conv_winograd(nullptr, tile, K, "", x, w, y, u, v, mm, N, H, W, Cin, Cout, we, s, nullptr);
+    conv_winograd(nullptr, tile, K, true, x, w, y, u, v, mm, N, H, W, Cin, Cout, we, s, nullptr);
     hipStreamSynchronize(s);
     OPCHK(); return FCN8S_OK;
 }
@@ -3697,7 +3706,7 @@ int fcn8s_op_conv3x3_winograd_fwd_bwd(void* stream, const float* x, const float*
         return fail(nullptr, FCN8S_ERR_BAD_ARG, "conv3x3_winograd_fwd_bwd: needs tile in {2,4,6}, Cin % 64 == 0, Cout % 64 == 0, even H and W (multiples of tile for tiles 2, 4), "
                                                 "pooled only with tiles 4 and 6, mask_mode in {0,1,2}");
     hipStream_t s = (hipStream_t)stream;
-    // a bare model context: the launch sequences below are the model's own (conv_same / conv_wgrad), with one layer called "op"
+    // a bare model context: the launch sequences below are the model's own (conv_fwd / conv_wgrad / conv_dgrad), with one layer called "op"
     fcn8s_model mm; fcn8s_model* m = &mm;
     m->stream = s; m->wino_min_cin = 16; m->wino_tile = 6; m->wino_force_tile = tile; m->N = N; m->H = H; m->W = W;
     m->precision = t_op_split == 3 ? FCN8S_PREC_F32X3 : t_op_split == 2 ? FCN8S_PREC_F32X2 : FCN8S_PREC_F32;
@@ -3717,23 +3726,23 @@ int fcn8s_op_conv3x3_winograd_fwd_bwd(void* stream, const float* x, const float*
     Act a; a.p = wv; a.n = slab_in; m->acts["wv:op"] = a;
     // forward (training mode: keeps V and the filter bank, writes the pool argmax bytes / the input's ReLU bit record)
     m->fwd_train = true; m->train_mode = true;
-    { Epi e; e.bias = bias; e.relu = 1;
+    { FwdEpi e; e.bias = bias; e.relu = 1;
       if (pooled) { e.pool_out = pool; e.pool_idx = (unsigned char*)pidx.get(); e.skip_y = y == nullptr; }
       if (mask_mode == 2) { e.in_relu_bits_out = (unsigned*)rbits.get(); e.in_layer = "prev"; }
-      conv_same(m, "op", x, w, y, N, H, W, Cin, Cout, 3, e, s, 0, "op"); }
+      conv_fwd(m, "op", x, w, y, N, H, W, Cin, Cout, 3, e, s, 0, "op"); }
     // backward: weight + bias gradient in the Winograd domain, then the data gradient (adjoint form for tile 6)
     hipMemsetAsync(dw, 0, (size_t)9 * Cin * Cout * sizeof(float), s);
     if (db) hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), s);
     conv_wgrad(m, "op", x, dy, dw, db, N, H, W, Cin, Cout, 3, 1.f, s, 0, "op", tile >= 4, pooled ? (const unsigned char*)pidx.get() : nullptr);
-    { Epi e; e.dgrad = 1; e.w_fwd = w; e.lazy_wt = 1; e.addend = dx_addend;
+    { DgradEpi e; e.w_fwd = w; e.lazy_wt = 1; e.addend = dx_addend;
       if (mask_mode) { e.mask = x; e.mask_scale = 1.f; }
-      if (mask_mode == 2 && m->rbits_ok.count("prev")) e.relu_bits_in = (const unsigned*)rbits.get();
-      conv_same(m, "op", dy, wt, dx, N, H, W, Cout, Cin, 3, e, s, 0, "op"); }
+      if (mask_mode == 2 && m->pass.rbits_ok.count("prev")) e.relu_bits_in = (const unsigned*)rbits.get();
+      conv_dgrad(m, "op", dy, wt, dx, N, H, W, Cout, Cin, 3, e, s, "op"); }
     hipStreamSynchronize(s);
     OPCHK(); return FCN8S_OK;
 }
 
-// One 7x7 SAME convolution the way fc6 runs in an fp32 training step: conv_same in training mode, conv_wgrad, conv_same as the data gradient, on a bare
+// One 7x7 SAME convolution the way fc6 runs in an fp32 training step: conv_fwd in training mode, conv_wgrad, conv_dgrad, on a bare
 // model with one layer called "op" -- which of the DFT tiles, F(4x4,4x4) and the direct kernels run is decided by the model's own rules (fft6_on,
 // fft6_wgrad_wanted, bt_gemm_ok, wino_tile_for), never by this function.  For tests only: it allocates and synchronises per call, so it says nothing about time.
 int fcn8s_op_conv7x7_fc6_fwd_bwd(void* stream, const float* x, const float* w, const float* bias, const float* dy,
@@ -3769,14 +3778,14 @@ int fcn8s_op_conv7x7_fc6_fwd_bwd(void* stream, const float* x, const float* w, c
     if (!ok) { hipStreamSynchronize(s); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
     // forward, as forward() runs fc6 (step 0: dropout stream 0)
     m->fwd_train = true; m->train_mode = true; m->drop_stream = 0;
-    { Epi e; e.bias = bias; e.relu = 1; e.dropout = keep_prob < 1.f; e.keep = keep_prob; e.stream_id = m->drop_stream;
-      conv_same(m, "fc6_fwd", x, w, y, N, H, W, Cin, Cout, 7, e, s, 0, "op"); }
+    { FwdEpi e; e.bias = bias; e.relu = 1; e.dropout = keep_prob < 1.f; e.keep = keep_prob; e.stream_id = m->drop_stream;
+      conv_fwd(m, "fc6_fwd", x, w, y, N, H, W, Cin, Cout, 7, e, s, 0, "op"); }
     // backward, as backward_fc6 runs it: the weight gradient first (it may leave dYf / dM for the data gradient), then the data gradient
     hipMemsetAsync(dw, 0, (size_t)49 * Cin * Cout * sizeof(float), s);
     if (db) hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), s);
     conv_wgrad(m, "fc6_wgrad", x, dy, dw, db, N, H, W, Cin, Cout, 7, 1.f, s, 0, "op");
-    { Epi e; e.dgrad = 1; e.w_fwd = w; e.lazy_wt = 1;
-      conv_same(m, "fc6_dgrad", dy, wt, dx, N, H, W, Cout, Cin, 7, e, s, 0, "op"); }
+    { DgradEpi e; e.w_fwd = w; e.lazy_wt = 1;
+      conv_dgrad(m, "fc6_dgrad", dy, wt, dx, N, H, W, Cout, Cin, 7, e, s, "op"); }
     if (dft_products)
         for (const auto& g : m->groups) {
             if (g.launches <= 0) continue;
@@ -3890,7 +3899,7 @@ int fcn8s_op_conv2d_bwd(void* stream, const float* x, const float* w, const floa
         DeviceBuf<float> wt;
         if (!wt.grow((size_t)K * K * Cin * Cout * sizeof(float), s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
         launch_flip_transpose(w, wt, K * K, Cin, Cout, s);
-        Epi e; conv_same(nullptr, "", dy, wt, dx, N, H, W, Cout, Cin, K, e, s);
+        conv_dgrad(nullptr, "", dy, wt, dx, N, H, W, Cout, Cin, K, DgradEpi{}, s);
         hipStreamSynchronize(s);
     }
     OPCHK(); return FCN8S_OK;
