@@ -83,6 +83,12 @@ SIGNATURES = {
     "fcn8s_accumulate_discard": (_i, [_p]),
     "fcn8s_set_grad_clip": (_i, [_p, _f]),
     "fcn8s_get_update_stats": (_i, [_p, _fp, _fp, _fp, _i64p]),
+    "fcn8s_set_ema": (_i, [_p, C.c_double, _i]),
+    "fcn8s_ema_reset": (_i, [_p]),
+    "fcn8s_ema_swap": (_i, [_p]),
+    "fcn8s_get_ema_info": (_i, [_p, _dp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "fcn8s_get_ema": (_i, [_p, _p, _sz]),
+    "fcn8s_set_ema_state": (_i, [_p, _p, _sz]),
     "fcn8s_set_loss": (_i, [_p, _p, _i, _f, _i64]),
     "fcn8s_get_loss_stats": (_i, [_p, _i64p, _i64p, _fp]),
     "fcn8s_set_lovasz": (_i, [_p, _f, _f, _i, _i, _p, _i]),
@@ -153,6 +159,10 @@ SIGNATURES = {
     "fcn8s_op_grad_norm": (_i, [_p, _p, _i64, _f, _f, _p]),
     "fcn8s_op_tf_adam_dev": (_i, [_p, _p, _p, _p, _p, _i64, _i, _f, _f, _f, _f, _p]),
     "fcn8s_op_sgd_momentum_dev": (_i, [_p, _p, _p, _p, _i64, _f, _f, _p]),
+    "fcn8s_op_ema_update": (_i, [_p, _p, _p, _i64, _f, _p]),
+    "fcn8s_op_tf_adam_ema": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _f, _f, _f, _f, _f, _p, _f]),
+    "fcn8s_op_sgd_momentum_ema": (_i, [_p, _p, _p, _p, _p, _i64, _f, _f, _f, _p, _f]),
+    "fcn8s_op_swap": (_i, [_p, _p, _p, _i64]),
 }
 
 

@@ -295,6 +295,15 @@ void launch_tf_adam_dev(float* theta, const float* g, float* m, float* v, long l
                         float lr_t, float b1, float b2, float eps, const float* s_dev, const int* ok_dev, hipStream_t s);
 void launch_sgd_momentum_dev(float* theta, const float* g, float* buf, long long n,
                              float lr, float mom, const float* s_dev, const int* ok_dev, hipStream_t s);
+// optim.hip: the moving average of the parameters.  w = (float)(1 - decay_t); s <- s - w (s - theta), the same bits from all three kernels.
+// launch_tf_adam_ema / launch_sgd_momentum_ema: the update (host scale, or s_dev / ok_dev as above when s_dev != nullptr) and the average of the
+// new theta in one pass; launch_ema_update: the average alone (ok_dev may be null); launch_swap: a <-> b.  Any float alignment of any pointer.
+void launch_tf_adam_ema(float* theta, const float* g, float* m, float* v, float* sh, long long n, float lr_t, float b1, float b2, float eps,
+                        float gscale, const float* s_dev, const int* ok_dev, float w, hipStream_t s);
+void launch_sgd_momentum_ema(float* theta, const float* g, float* buf, float* sh, long long n, float lr, float mom,
+                             float gscale, const float* s_dev, const int* ok_dev, float w, hipStream_t s);
+void launch_ema_update(float* sh, const float* theta, long long n, float w, const int* ok_dev, hipStream_t s);
+void launch_swap(float* a, float* b, long long n, hipStream_t s);
 // weight re-layouts (run once per step, tiny next to the convs)
 void launch_flip_transpose(const float* w, float* wt, int taps, int Cin, int Cout, hipStream_t s); // wt[T-1-t][co][ci] = w[t][ci][co]
 void launch_pad_cin(const float* w, float* w4, int taps, int Cin, int Cinp, int Cout, hipStream_t s);

@@ -208,6 +208,9 @@ struct fcn8s_model {
     // fcn8s_set_grad_clip: max_norm (0 = off); upd_ws = UpdateStats + the norm's kGradNormBlocks partial sums, made by fcn8s_set_grad_clip;
     // last_update_clipped: the last fcn8s_apply_update ran the norm pass (fcn8s_get_update_stats)
     float max_norm = 0.f; DeviceBuf<char> upd_ws; bool last_update_clipped = false;
+    // fcn8s_set_ema: the moving average of the parameters -- the shadow (total floats; grown when the average is first switched on -- a
+    // "workspace_allocation" -- and kept until the model goes), its decay (0 = off) and warm-up rule, and whether theta and the shadow have changed places
+    DeviceBuf<float> d_ema; double ema_decay = 0.0; int ema_warmup = 1; bool ema_swapped = false;
     DeviceBuf<unsigned long long> d_conf;
     double loss_sum = 0; int64_t loss_cnt = 0;
     float keep_prob = 1.f, l2_rate = 0.f;
@@ -1460,6 +1463,17 @@ static int fp8_exponent_host(float a)
 static int fp8_ex(const fcn8s_model* m, const char* layer) { return fp8_exponent_host(m->fp8_amax[fp8_layer(layer)]); }
 // parameters changed: the calibration no longer describes them
 static void fp8_clear_calibration(fcn8s_model* m) { if (m) m->fp8_calibrated = false; }
+// the average: while theta and the shadow have changed places (fcn8s_ema_swap) nothing trains
+static int ema_refuse_swapped(fcn8s_model* m, const char* who)
+{
+    return fail(m, FCN8S_ERR_STATE, std::string(who) + ": the averaged weights are live (fcn8s_ema_swap); swap back before training");
+}
+// w = (float)(1 - d_t), d_t = warmup ? min(d, (1 + t) / (10 + t)) : d in double, t = the global step after the update
+static float ema_one_minus_decay(double d, int warmup, int64_t t)
+{
+    if (warmup) { const double r = (1.0 + (double)t) / (10.0 + (double)t); if (r < d) d = r; }
+    return (float)(1.0 - d);
+}
 static int fp8_refuse_training(fcn8s_model* m, const char* who)
 {
     return fail(m, FCN8S_ERR_STATE, std::string(who) + ": the fp8_infer precision is inference only (evaluation, prediction); switch to another precision with "
@@ -2860,6 +2874,7 @@ int fcn8s_accumulate_bucket(fcn8s_model* m, int bucket, int flush)
 {
     if (!m || bucket < 0 || bucket >= kNumBuckets) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_accumulate_bucket: bad bucket");
     if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_accumulate_bucket");
+    if (m->ema_swapped) return ema_refuse_swapped(m, "fcn8s_accumulate_bucket");
     if (!m->have_loss || !m->train_mode || bucket >= m->next_bucket || !m->bucket_final[bucket])
         return fail(m, FCN8S_ERR_STATE, "fcn8s_accumulate_bucket: the bucket's gradients are not queued yet (call fcn8s_backward_bucket(bucket) after fcn8s_forward_loss first)");
     if (m->acc_taken[bucket]) return fail(m, FCN8S_ERR_STATE, "fcn8s_accumulate_bucket: this backward pass's bucket has already been folded or flushed");
@@ -2920,9 +2935,78 @@ int fcn8s_get_update_stats(fcn8s_model* m, float* norm, float* clip_coef, float*
     return FCN8S_OK;
 }
 
+// the shadow is there (allocated and set to theta at first use)
+static int ensure_ema(fcn8s_model* m, bool copy_theta, const char* who)
+{
+    if (m->d_ema) return FCN8S_OK;
+    if (!m->d_ema.grow(m->total * sizeof(float), m->stream, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, std::string(who) + ": the shadow cannot be allocated");
+    if (copy_theta) HIPCHK(m, hipMemcpyAsync(m->d_ema, m->d_params, m->total * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    return FCN8S_OK;
+}
+
+int fcn8s_set_ema(fcn8s_model* m, double decay, int warmup)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!(decay >= 0.0 && decay < 1.0)) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_ema: decay must be 0 (off) or in (0, 1)");
+    if (decay > 0.0) { int rc = ensure_ema(m, true, "fcn8s_set_ema"); if (rc) return rc; }
+    m->ema_decay = decay; m->ema_warmup = warmup != 0;
+    return FCN8S_OK;
+}
+
+int fcn8s_ema_reset(fcn8s_model* m)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!m->d_ema) return fail(m, FCN8S_ERR_STATE, "fcn8s_ema_reset: there is no shadow (fcn8s_set_ema)");
+    if (m->ema_swapped) return ema_refuse_swapped(m, "fcn8s_ema_reset");
+    HIPCHK(m, hipMemcpyAsync(m->d_ema, m->d_params, m->total * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    return FCN8S_OK;
+}
+
+int fcn8s_ema_swap(fcn8s_model* m)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!m->d_ema) return fail(m, FCN8S_ERR_STATE, "fcn8s_ema_swap: there is no shadow (fcn8s_set_ema)");
+    if (m->frozen) fcn8s_freeze_params(m, 0);      // the live parameters are about to change: leave the frozen state (what fcn8s_set_param does)
+    fp8_clear_calibration(m);
+    { ProfScope ps(m, "ema_swap", 0, 16.0 * m->total); launch_swap(m->d_params, m->d_ema, (long long)m->total, m->stream); }
+    m->ema_swapped = !m->ema_swapped;
+    HIPCHK(m, hipGetLastError());
+    return FCN8S_OK;
+}
+
+int fcn8s_get_ema_info(const fcn8s_model* m, double* decay, int* warmup, int* has_shadow, int* swapped)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (decay) *decay = m->ema_decay;
+    if (warmup) *warmup = m->ema_warmup;
+    if (has_shadow) *has_shadow = m->d_ema ? 1 : 0;
+    if (swapped) *swapped = m->ema_swapped ? 1 : 0;
+    return FCN8S_OK;
+}
+
+int fcn8s_get_ema(fcn8s_model* m, float* host, size_t n)
+{
+    if (!m || !host || n != m->total) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_get_ema: null argument or size mismatch");
+    if (!m->d_ema) return fail(m, FCN8S_ERR_STATE, "fcn8s_get_ema: there is no shadow (fcn8s_set_ema)");
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(host, m->d_ema, n * sizeof(float), hipMemcpyDeviceToHost));
+    return FCN8S_OK;
+}
+
+int fcn8s_set_ema_state(fcn8s_model* m, const float* host, size_t n)
+{
+    if (!m || !host || n != m->total) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_ema_state: null argument or size mismatch");
+    if (m->ema_swapped) return ema_refuse_swapped(m, "fcn8s_set_ema_state");
+    int rc = ensure_ema(m, false, "fcn8s_set_ema_state"); if (rc) return rc;
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(m->d_ema, host, n * sizeof(float), hipMemcpyHostToDevice));
+    return FCN8S_OK;
+}
+
 int fcn8s_apply_update(fcn8s_model* m, int optimizer, float lr, float grad_scale)
 {
     if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_apply_update");
+    if (m && m->ema_swapped) return ema_refuse_swapped(m, "fcn8s_apply_update");
     if (fcn8s_accumulate_pending(m) > 0)
         return fail(m, FCN8S_ERR_STATE, "fcn8s_apply_update: micro-batches are folded and not flushed (fcn8s_accumulate_bucket(m, b, 1) on the last one, or fcn8s_accumulate_discard)");
     if (m && m->frozen) fcn8s_freeze_params(m, 0);      // parameters are about to change (or a training pass starts): leave the frozen state
@@ -2939,19 +3023,30 @@ int fcn8s_apply_update(fcn8s_model* m, int optimizer, float lr, float grad_scale
         launch_grad_norm(m->d_grads, (long long)m->total, grad_scale, m->max_norm, (double*)(m->upd_ws + kUpdPartialsOff), st, false, m->stream);
     }
     m->last_update_clipped = clip;
+    // the average: w = 1 - d_t for the step this update makes; the fused kernels fold the new theta into the shadow in the update's own pass
+    const bool ema = m->ema_decay > 0.0 && m->d_ema;
+    const float ema_w = ema ? ema_one_minus_decay(m->ema_decay, m->ema_warmup, t) : 0.f;
     if (optimizer == FCN8S_OPT_TF_ADAM) {
         int rc = ensure_opt_state(m); if (rc) return rc;
         const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
         const float lr_t = lr * (float)std::sqrt(1.0 - std::pow((double)b2, (double)t)) / (float)(1.0 - std::pow((double)b1, (double)t));
-        ProfScope ps(m, "adam", 0, 28.0 * m->total);
-        if (clip) launch_tf_adam_dev(m->d_params, m->d_grads, m->d_m, m->d_v, (long long)m->total, lr_t, b1, b2, eps, &st->scale, &st->ok, m->stream);
+        ProfScope ps(m, "adam", 0, (ema ? 36.0 : 28.0) * m->total);
+        if (ema) launch_tf_adam_ema(m->d_params, m->d_grads, m->d_m, m->d_v, m->d_ema, (long long)m->total, lr_t, b1, b2, eps, grad_scale,
+                                    clip ? &st->scale : nullptr, clip ? &st->ok : nullptr, ema_w, m->stream);
+        else if (clip) launch_tf_adam_dev(m->d_params, m->d_grads, m->d_m, m->d_v, (long long)m->total, lr_t, b1, b2, eps, &st->scale, &st->ok, m->stream);
         else launch_tf_adam(m->d_params, m->d_grads, m->d_m, m->d_v, (long long)m->total, lr_t, b1, b2, eps, grad_scale, m->stream);
     } else if (optimizer == FCN8S_OPT_SGD_MOMENTUM) {
         int rc = ensure_opt_state(m); if (rc) return rc;
-        ProfScope ps(m, "sgd_momentum", 0, 20.0 * m->total);
-        if (clip) launch_sgd_momentum_dev(m->d_params, m->d_grads, m->d_m, (long long)m->total, lr, 0.9f, &st->scale, &st->ok, m->stream);
+        ProfScope ps(m, "sgd_momentum", 0, (ema ? 28.0 : 20.0) * m->total);
+        if (ema) launch_sgd_momentum_ema(m->d_params, m->d_grads, m->d_m, m->d_ema, (long long)m->total, lr, 0.9f, grad_scale,
+                                         clip ? &st->scale : nullptr, clip ? &st->ok : nullptr, ema_w, m->stream);
+        else if (clip) launch_sgd_momentum_dev(m->d_params, m->d_grads, m->d_m, (long long)m->total, lr, 0.9f, &st->scale, &st->ok, m->stream);
         else launch_sgd_momentum(m->d_params, m->d_grads, m->d_m, (long long)m->total, lr, 0.9f, grad_scale, m->stream);
     } else if (optimizer != FCN8S_OPT_NONE) return fail(m, FCN8S_ERR_BAD_ARG, "unknown optimizer");
+    else if (ema) {      // the caller has written theta: fold it as it stands on the stream
+        ProfScope ps(m, "ema_update", 0, 12.0 * m->total);
+        launch_ema_update(m->d_ema, m->d_params, (long long)m->total, ema_w, clip ? &st->ok : nullptr, m->stream);
+    }
     m->step = t;
     HIPCHK(m, hipGetLastError());
     return FCN8S_OK;
@@ -3070,6 +3165,7 @@ int fcn8s_train_step(fcn8s_model* m, const void* images, int dtype, const uint8_
                      float lr, float keep_prob, float l2_rate, int where, float* loss_out, int64_t* step_out)
 {
     if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_train_step");
+    if (m && m->ema_swapped) return ema_refuse_swapped(m, "fcn8s_train_step");
     if (m && m->frozen) fcn8s_freeze_params(m, 0);      // parameters are about to change (or a training pass starts): leave the frozen state
     int rc = fcn8s_forward_loss(m, images, dtype, labels, N, H, W, keep_prob, l2_rate, where); if (rc) return rc;
     // a model with a communicator of more than one rank trains data-parallel through this entry point too: the bucket-by-bucket
@@ -4057,6 +4153,30 @@ int fcn8s_op_sgd_momentum_dev(void* stream, float* theta, const float* g, float*
 {
     if (!out5) return fail(nullptr, FCN8S_ERR_BAD_ARG, "sgd_momentum_dev: null out5_dev");
     launch_sgd_momentum_dev(theta, g, buf, n, lr, mom, out5 + 2, (const int*)(out5 + 3), (hipStream_t)stream); OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_ema_update(void* stream, float* s, const float* theta, int64_t n, float w, const float* out5)
+{
+    if (!s || !theta || n < 0) return fail(nullptr, FCN8S_ERR_BAD_ARG, "ema_update: bad argument (null pointer or n < 0)");
+    launch_ema_update(s, theta, n, w, out5 ? (const int*)(out5 + 3) : nullptr, (hipStream_t)stream); OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_tf_adam_ema(void* stream, float* theta, const float* g, float* mm, float* v, float* s, int64_t n, int t, float lr, float b1, float b2, float eps,
+                         float gs, const float* out5, float w)
+{
+    if (!theta || !g || !mm || !v || !s || n < 0) return fail(nullptr, FCN8S_ERR_BAD_ARG, "tf_adam_ema: bad argument (null pointer or n < 0)");
+    const float lr_t = lr * (float)std::sqrt(1.0 - std::pow((double)b2, (double)t)) / (float)(1.0 - std::pow((double)b1, (double)t));
+    launch_tf_adam_ema(theta, g, mm, v, s, n, lr_t, b1, b2, eps, gs, out5 ? out5 + 2 : nullptr, out5 ? (const int*)(out5 + 3) : nullptr, w, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_sgd_momentum_ema(void* stream, float* theta, const float* g, float* buf, float* s, int64_t n, float lr, float mom, float gs, const float* out5, float w)
+{
+    if (!theta || !g || !buf || !s || n < 0) return fail(nullptr, FCN8S_ERR_BAD_ARG, "sgd_momentum_ema: bad argument (null pointer or n < 0)");
+    launch_sgd_momentum_ema(theta, g, buf, s, n, lr, mom, gs, out5 ? out5 + 2 : nullptr, out5 ? (const int*)(out5 + 3) : nullptr, w, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_swap(void* stream, float* a, float* b, int64_t n)
+{
+    if (!a || !b || n < 0) return fail(nullptr, FCN8S_ERR_BAD_ARG, "swap: bad argument (null pointer or n < 0)");
+    launch_swap(a, b, n, (hipStream_t)stream); OPCHK(); return FCN8S_OK;
 }
 
 }  // extern "C"

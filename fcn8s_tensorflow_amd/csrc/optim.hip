@@ -1,6 +1,7 @@
 // The update's own HBM-bound kernels (definitions: include/fcn8s_hip.h, "the update"): folding a gradient bucket into the accumulator and
 // flushing it back, the global norm of the flat gradient buffer in a fixed summation order, and the TF-Adam / SGD-momentum kernels that
-// read their gradient scale and the guard's verdict from device memory.  16-byte accesses, grid-stride loops capped at 2048 blocks.
+// read their gradient scale and the guard's verdict from device memory; the moving average of the parameters ("the average"): the update fused
+// with it, the average alone, and the swap.  16-byte accesses, grid-stride loops capped at 2048 blocks.
 #include "fcn8s_internal.h"
 #include <math.h>
 
@@ -178,6 +179,170 @@ void launch_sgd_momentum_dev(float* theta, const float* g, float* buf, long long
                              const float* s_dev, const int* ok_dev, hipStream_t s)
 {
     hipLaunchKernelGGL(sgd_momentum_dev_kernel, dim3(cap_blocks(n, 256)), dim3(256), 0, s, theta, g, buf, n, lr, mom, s_dev, ok_dev);
+}
+
+// ---- the moving average of the parameters (definitions: include/fcn8s_hip.h, "the average") -------------------------------------------------
+// s <- s - w (s - theta): one subtraction and one fused multiply-add, written out so that every kernel below gives the same bits
+static __device__ __forceinline__ float ema1(float s, float t, float w) { return __builtin_fmaf(-w, s - t, s); }
+
+// One element of the updates of elementwise.hip (K12) and of the _dev kernels above, with the roundings written out.  Those kernels leave the
+// contraction of a multiply-add to the compiler, and it decides differently per kernel: the float4 bodies of the Adam kernels (elements below
+// 4 (n / 4)) fuse the last product of the m and of the v update into the sum, their tail kernels (the up to three elements behind) round both
+// products first; the SGD kernels round both products of the momentum and fuse theta's.  FUSED picks the Adam form; a kernel that wants the
+// bits of those kernels picks it by the element's index, whatever lane computes the element.  (contract(off): a * b + c below is two roundings;
+// the one rounding is spelled fmaf.  The __fmul_rn family would not do: it is plain arithmetic that the compiler contracts like any other.)
+template <bool FUSED>
+static __device__ __forceinline__ void adam1(float& t, float g, float& m, float& v, float lr_t, float b1, float b2, float eps, float gs)
+{
+#pragma clang fp contract(off)
+    const float gr = g * gs, c1 = 1.f - b1, c2 = 1.f - b2;
+    if (FUSED) { m = __builtin_fmaf(c1, gr, b1 * m); v = __builtin_fmaf(c2 * gr, gr, b2 * v); }
+    else       { m = b1 * m + c1 * gr; v = b2 * v + (c2 * gr) * gr; }
+    t -= lr_t * m / (sqrtf(v) + eps);
+}
+static __device__ __forceinline__ void adam1(bool fused, float& t, float g, float& m, float& v, float lr_t, float b1, float b2, float eps, float gs)
+{
+    if (fused) adam1<true>(t, g, m, v, lr_t, b1, b2, eps, gs); else adam1<false>(t, g, m, v, lr_t, b1, b2, eps, gs);
+}
+static __device__ __forceinline__ void sgd1(float& t, float g, float& buf, float lr, float mom, float gs)
+{
+#pragma clang fp contract(off)
+    const float b = mom * buf + g * gs;
+    buf = b;
+    t = __builtin_fmaf(-lr, b, t);
+}
+
+template <bool ALIGNED> static __device__ __forceinline__ float4 ld4(const float* p, long long i)
+{
+    if (ALIGNED) return ((const float4*)p)[i];
+    const float4_u u = ((const float4_u*)p)[i];
+    return make_float4(u.x, u.y, u.z, u.w);
+}
+template <bool ALIGNED> static __device__ __forceinline__ void st4(float* p, long long i, const float4& a)
+{
+    if (ALIGNED) ((float4*)p)[i] = a;
+    else { float4_u u; u.x = a.x; u.y = a.y; u.z = a.z; u.w = a.w; ((float4_u*)p)[i] = u; }
+}
+// the scalar lanes of a launch whose body is n4 float4 from `head` on: element index of this lane, or -1 (the pattern of grad_accumulate_kernel)
+static __device__ __forceinline__ long long edge_lane(long long gtid, long long head, long long n4, long long n)
+{
+    const long long tail0 = head + n4 * 4;
+    if (gtid < head) return gtid;
+    if (gtid - head < n - tail0) return tail0 + (gtid - head);
+    return -1;
+}
+
+// The update and the average in one pass: theta, m (, v) as the kernels above compute them, then s from the new theta while it is in registers.
+// OPT 0: TF-Adam (p0 .. p3 = lr_t, beta1, beta2, eps), 1: SGD-momentum (p0, p1 = lr, momentum; v unused).  DEV: the gradient scale and the guard's
+// verdict come from s_dev / ok_dev.  theta + head is 16-byte aligned; ALIGNED: so are g, m, v and s at + head (a model's buffers).
+template <int OPT, bool DEV, bool ALIGNED>
+__global__ __launch_bounds__(256) void update_ema_kernel(float* theta, const float* g, float* m, float* v, float* s, long long head, long long n4, long long n,
+                                                         float p0, float p1, float p2, float p3, float gs_host,
+                                                         const float* __restrict__ s_dev, const int* __restrict__ ok_dev, float w)
+{
+    if (DEV) { if (*ok_dev == 0) return; }
+    const float gs = DEV ? *s_dev : gs_host;
+    const long long gtid = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const long long nb = n & ~3LL;          // Adam: the elements below take the form of the old kernels' float4 body (the launcher ends the body there), the others their tail kernel's
+    for (long long i = gtid; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        float4 t = ((float4*)(theta + head))[i];
+        const float4 gg = ld4<ALIGNED>(g + head, i);
+        float4 mm = ld4<ALIGNED>(m + head, i), ss = ld4<ALIGNED>(s + head, i);
+        if (OPT == 0) {
+            float4 vv = ld4<ALIGNED>(v + head, i);
+            adam1<true>(t.x, gg.x, mm.x, vv.x, p0, p1, p2, p3, gs); adam1<true>(t.y, gg.y, mm.y, vv.y, p0, p1, p2, p3, gs);
+            adam1<true>(t.z, gg.z, mm.z, vv.z, p0, p1, p2, p3, gs); adam1<true>(t.w, gg.w, mm.w, vv.w, p0, p1, p2, p3, gs);
+            st4<ALIGNED>(v + head, i, vv);
+        } else {
+            sgd1(t.x, gg.x, mm.x, p0, p1, gs); sgd1(t.y, gg.y, mm.y, p0, p1, gs);
+            sgd1(t.z, gg.z, mm.z, p0, p1, gs); sgd1(t.w, gg.w, mm.w, p0, p1, gs);
+        }
+        ss.x = ema1(ss.x, t.x, w); ss.y = ema1(ss.y, t.y, w); ss.z = ema1(ss.z, t.z, w); ss.w = ema1(ss.w, t.w, w);
+        ((float4*)(theta + head))[i] = t;
+        st4<ALIGNED>(m + head, i, mm);
+        st4<ALIGNED>(s + head, i, ss);
+    }
+    const long long j = edge_lane(gtid, head, n4, n);
+    if (j >= 0) {
+        float t = theta[j], mm = m[j];
+        if (OPT == 0) { float vv = v[j]; adam1(j < nb, t, g[j], mm, vv, p0, p1, p2, p3, gs); v[j] = vv; }
+        else sgd1(t, g[j], mm, p0, p1, gs);
+        theta[j] = t; m[j] = mm;
+        s[j] = ema1(s[j], t, w);
+    }
+}
+
+static void launch_update_ema(int opt, float* theta, const float* g, float* m, float* v, float* sh, long long n, float p0, float p1, float p2, float p3,
+                              float gs, const float* s_dev, const int* ok_dev, float w, hipStream_t st)
+{
+    if (n <= 0) return;
+    // Adam: no float4 of the body reaches over 4 (n / 4), so the body is all of one form; up to 3 + 6 scalar lanes
+    const long long head = head_floats(theta, n), nb = n & ~3LL, n4 = opt == 0 ? (nb > head ? (nb - head) / 4 : 0) : (n - head) / 4;
+    auto al16 = [&](const float* p) { return p == nullptr || (((uintptr_t)(p + head)) & 15) == 0; };
+    const bool al = al16(g) && al16(m) && al16(v) && al16(sh), dev = s_dev != nullptr;
+    const dim3 grid(cap_blocks(n4, 256)), block(256);          // (one block at least: the scalar lanes)
+#define UE(O, D, A) hipLaunchKernelGGL((update_ema_kernel<O, D, A>), grid, block, 0, st, theta, g, m, v, sh, head, n4, n, p0, p1, p2, p3, gs, s_dev, ok_dev, w)
+#define UE2(O) do { if (dev) { if (al) UE(O, true, true); else UE(O, true, false); } else { if (al) UE(O, false, true); else UE(O, false, false); } } while (0)
+    if (opt == 0) UE2(0); else UE2(1);
+#undef UE2
+#undef UE
+}
+void launch_tf_adam_ema(float* theta, const float* g, float* m, float* v, float* sh, long long n, float lr_t, float b1, float b2, float eps,
+                        float gscale, const float* s_dev, const int* ok_dev, float w, hipStream_t st)
+{
+    launch_update_ema(0, theta, g, m, v, sh, n, lr_t, b1, b2, eps, gscale, s_dev, ok_dev, w, st);
+}
+void launch_sgd_momentum_ema(float* theta, const float* g, float* buf, float* sh, long long n, float lr, float mom,
+                             float gscale, const float* s_dev, const int* ok_dev, float w, hipStream_t st)
+{
+    launch_update_ema(1, theta, g, buf, nullptr, sh, n, lr, mom, 0.f, 0.f, gscale, s_dev, ok_dev, w, st);
+}
+
+// the average alone (FCN8S_OPT_NONE: the caller wrote theta): s + head is 16-byte aligned; ok_dev may be null (no guard)
+template <bool ALIGNED>
+__global__ __launch_bounds__(256) void ema_update_kernel(float* s, const float* __restrict__ theta, long long head, long long n4, long long n, float w,
+                                                         const int* __restrict__ ok_dev)
+{
+    if (ok_dev && *ok_dev == 0) return;
+    const long long gtid = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    for (long long i = gtid; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        float4 ss = ((float4*)(s + head))[i];
+        const float4 t = ld4<ALIGNED>(theta + head, i);
+        ss.x = ema1(ss.x, t.x, w); ss.y = ema1(ss.y, t.y, w); ss.z = ema1(ss.z, t.z, w); ss.w = ema1(ss.w, t.w, w);
+        ((float4*)(s + head))[i] = ss;
+    }
+    const long long j = edge_lane(gtid, head, n4, n);
+    if (j >= 0) s[j] = ema1(s[j], theta[j], w);
+}
+void launch_ema_update(float* sh, const float* theta, long long n, float w, const int* ok_dev, hipStream_t st)
+{
+    if (n <= 0) return;
+    const long long head = head_floats(sh, n), n4 = (n - head) / 4;
+    const dim3 grid(cap_blocks(n4, 256)), block(256);
+    if ((((uintptr_t)(theta + head)) & 15) == 0) hipLaunchKernelGGL(ema_update_kernel<true>, grid, block, 0, st, sh, theta, head, n4, n, w, ok_dev);
+    else                                         hipLaunchKernelGGL(ema_update_kernel<false>, grid, block, 0, st, sh, theta, head, n4, n, w, ok_dev);
+}
+
+// a <-> b in place (fcn8s_ema_swap): a + head is 16-byte aligned; the ranges do not overlap
+template <bool ALIGNED>
+__global__ __launch_bounds__(256) void swap_kernel(float* a, float* b, long long head, long long n4, long long n)
+{
+    const long long gtid = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    for (long long i = gtid; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const float4 x = ((float4*)(a + head))[i], y = ld4<ALIGNED>(b + head, i);
+        ((float4*)(a + head))[i] = y;
+        st4<ALIGNED>(b + head, i, x);
+    }
+    const long long j = edge_lane(gtid, head, n4, n);
+    if (j >= 0) { const float x = a[j]; a[j] = b[j]; b[j] = x; }
+}
+void launch_swap(float* a, float* b, long long n, hipStream_t st)
+{
+    if (n <= 0) return;
+    const long long head = head_floats(a, n), n4 = (n - head) / 4;
+    const dim3 grid(cap_blocks(n4, 256)), block(256);
+    if ((((uintptr_t)(b + head)) & 15) == 0) hipLaunchKernelGGL(swap_kernel<true>, grid, block, 0, st, a, b, head, n4, n);
+    else                                     hipLaunchKernelGGL(swap_kernel<false>, grid, block, 0, st, a, b, head, n4, n);
 }
 
 }  // namespace fcn8s

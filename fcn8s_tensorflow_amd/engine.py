@@ -14,6 +14,7 @@ pass runs on the compute stream.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from collections import OrderedDict
 
@@ -129,6 +130,7 @@ class Engine:
         self.loss_config = None              # set_loss: the training loss's configuration (None = the reference's mean)
         self.lovasz_config = None            # set_lovasz: the Lovász-softmax term's configuration (None = off)
         self.grad_clip = None                # set_grad_clip: the global-norm clip's max_norm (None = off; inf = the non-finite guard alone)
+        self.ema_config = None               # set_ema: the parameter average's configuration, dict(decay, warmup) (None = off)
         self.replica_check_every = 100      # data-parallel runs: compare global step + parameter checksum across ranks every so many steps (0 = never)
         self._sync_stream()
 
@@ -482,6 +484,60 @@ class Engine:
         n = C.c_float(); c = C.c_float(); sc = C.c_float(); k = C.c_int64()
         L.check(L.lib.fcn8s_get_update_stats(self.h, C.byref(n), C.byref(c), C.byref(sc), C.byref(k)), self.h)
         return dict(norm=float(n.value), clip_coef=float(c.value), scale=float(sc.value), skipped=int(k.value))
+
+    # ---- the average of the parameters (fcn8s_set_ema; definitions in include/fcn8s_hip.h, restated in optim.py) -------------------
+    def set_ema(self, decay, warmup=True):
+        """Keep an exponential moving average of the parameters on the device: after every applied update
+        s <- s - (1 - d_t) (s - theta), d_t = min(decay, (1 + t) / (10 + t)) with `warmup` (TensorFlow's num_updates rule), else decay.
+        The shadow is allocated, and set to the parameters, when the average is first switched on; `decay` None or 0 switches it off and
+        keeps the shadow.  The update folds the new parameters into the shadow in its own pass; a skipped update leaves it alone."""
+        d, w = optim_mod.validate_ema(decay, warmup)
+        self._sync_stream()
+        L.check(L.lib.fcn8s_set_ema(self.h, d, int(w)), self.h)
+        self.ema_config = dict(decay=d, warmup=w) if d > 0 else None
+
+    def ema_info(self):
+        """dict(decay, warmup, has_shadow, swapped) as the library holds them (fcn8s_get_ema_info)."""
+        d = C.c_double(); w = C.c_int(); hs = C.c_int(); sw = C.c_int()
+        L.check(L.lib.fcn8s_get_ema_info(self.h, C.byref(d), C.byref(w), C.byref(hs), C.byref(sw)), self.h)
+        return dict(decay=float(d.value), warmup=bool(w.value), has_shadow=bool(hs.value), swapped=bool(sw.value))
+
+    def ema_reset(self):
+        """shadow = parameters (a device copy on the stream)."""
+        self._sync_stream()
+        L.check(L.lib.fcn8s_ema_reset(self.h), self.h)
+
+    def get_ema(self):
+        """The flat shadow in the library's padded layout, like get_opt_state's arrays.  While swapped it holds the raw weights."""
+        a = np.empty(self.flat_params.numel(), np.float32)
+        L.check(L.lib.fcn8s_get_ema(self.h, a.ctypes.data_as(C.c_void_p), a.size), self.h)
+        return a
+
+    def set_ema_state(self, a):
+        """Write the flat shadow (allocating it if there is none); does not switch the average on."""
+        a = np.ascontiguousarray(a, np.float32).reshape(-1)
+        L.check(L.lib.fcn8s_set_ema_state(self.h, a.ctypes.data_as(C.c_void_p), a.size), self.h)
+
+    def ema_swap(self):
+        """Exchange the parameters and the shadow in place (one kernel).  While swapped every consumer of the parameters -- evaluation,
+        prediction, fp8 calibration, get_params, save -- sees the averaged weights and every training call raises; a second swap restores
+        the raw weights bit for bit.  Like set_params it leaves the frozen state and clears an fp8 calibration."""
+        self._sync_stream()
+        L.check(L.lib.fcn8s_ema_swap(self.h), self.h)
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """with engine.averaged_weights(): ... -- the averaged weights are live inside the block, the raw ones again behind it, whatever
+        the block raises.  Without a shadow the block runs on the parameters as they are; inside another such block it changes nothing."""
+        info = self.ema_info()
+        if not info['has_shadow'] or info['swapped']:
+            yield self
+            return
+        self.ema_swap()
+        try:
+            yield self
+        finally:
+            self.ema_swap()
 
     @property
     def pending_micro_batches(self):

@@ -24,6 +24,7 @@ Differences a maintainer must know (also listed in INTEGRATION.md):
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import shutil
@@ -130,6 +131,8 @@ class FCN8s:
                                  device_id=device_id, seed=seed + rank, logical_classes=self.num_classes)
             _load_checkpoint(self.engine, os.path.join(model_load_dir, "variables", "variables.npz"), with_state=True)
             fp8_calibration = meta.get("fp8_calibration")
+            if meta.get("ema_decay"):         # behind the checkpoint: a restored shadow is kept, not set to the parameters
+                self.engine.set_ema(meta["ema_decay"], meta.get("ema_warmup", True))
         else:
             self.engine = Engine(padded_classes(num_classes), widths=widths, fc6_ksize=fc6_ksize, device_id=device_id, seed=seed + rank,
                                  logical_classes=num_classes)
@@ -212,7 +215,10 @@ class FCN8s:
               lovasz_classes='present',
               ce_weight=1.0,
               accumulation_steps=1,
-              clip_global_norm=None):
+              clip_global_norm=None,
+              ema_decay=None,
+              ema_warmup=True,
+              ema_evaluate=True):
         '''Trains the model; arguments as fcn8s_tensorflow.py:424-503.  Summaries are written as TensorBoard
         event files (`<summaries_dir>/<summaries_name>[_eval]/events.out.tfevents.*`: total_loss, learning_rate and
         mean / stddev / max / min / histogram of the ten watched weight-bias pairs, :331-366) and, for reading
@@ -227,7 +233,12 @@ class FCN8s:
         Engine.train_step for the last; optim.py), its gradient is their mean and its reported loss the mean of their losses;
         `steps_per_epoch`, the global step, the learning-rate schedule, `summaries_frequency` and the saves all count updates.
         `clip_global_norm` (positive; inf = skip non-finite updates only) clips every update's gradient by its global norm for the duration
-        of the call (Engine.set_grad_clip); `grad_norm` and `clip_coef` then join the recorded scalars, on the steps that are recorded.'''
+        of the call (Engine.set_grad_clip); `grad_norm` and `clip_coef` then join the recorded scalars, on the steps that are recorded.
+        `ema_decay` in (0, 1) keeps an exponential moving average of the parameters for the duration of the call (Engine.set_ema, optim.py;
+        `ema_warmup`: TensorFlow's num_updates rule); the engine's previous setting is restored when train() returns or raises, the shadow
+        stays.  With `ema_evaluate` the in-training evaluations and the `save_during_training` saves run on the averaged weights
+        (Engine.averaged_weights); the live weights are the raw ones again when train() returns or raises.  Use
+        `with model.averaged_weights():` around evaluate / predict / save afterwards.'''
         if self.engine.precision == 'fp8_infer':
             raise ValueError("The 'fp8_infer' precision is inference only; switch the engine to another precision "
                              "(e.g. model.engine.set_precision('bf16_train')) before training.")
@@ -239,6 +250,7 @@ class FCN8s:
         if custom_lovasz:
             loss_mod.validate_lovasz(lovasz_weight, ce_weight, lovasz_per_image, lovasz_classes, self.engine.logical_classes)
         accumulation_steps, max_norm = optim_mod.validate(accumulation_steps, clip_global_norm)
+        ema_d, ema_w = optim_mod.validate_ema(ema_decay, ema_warmup)
         if eval_dataset not in ('train', 'val'):
             raise ValueError("`eval_dataset` must be one of 'train' or 'val', but is '{}'.".format(eval_dataset))
         if eval_dataset == 'val' and (val_generator is None or val_steps is None):
@@ -264,7 +276,11 @@ class FCN8s:
         prev_loss = self.engine.loss_config
         prev_lovasz = self.engine.lovasz_config
         prev_clip = self.engine.grad_clip
+        prev_ema = self.engine.ema_config
         try:
+            if ema_d:
+                self.engine.set_ema(ema_d, ema_w)
+            averaged = self.engine.averaged_weights if (ema_evaluate and self.engine.ema_config) else contextlib.nullcontext
             if max_norm:
                 self.engine.set_grad_clip(max_norm)
             if custom_loss:
@@ -279,14 +295,16 @@ class FCN8s:
 
                 if metrics and eval_epoch:
                     generator, num_batches, description = eval_source
-                    self._evaluate(generator, metrics, num_batches, l2_regularization, description)
+                    with averaged():
+                        self._evaluate(generator, metrics, num_batches, l2_regularization, description)
                     if eval_log is not None:
                         eval_log.add(self.g_step, **{('mean_loss' if n == 'loss' else n): v for n, v in zip(self.metric_names, self.metric_values)})    # tags of :360-362
 
                 if save_during_training and epoch % save_frequency == 0 and self._wants_save(save_best_only, monitor):
-                    self.save(model_save_dir=save_dir, saver=saver, tags=save_tags, name=save_name,
-                              include_global_step=True, include_last_training_loss=True,
-                              include_metrics=bool(self.metric_names))
+                    with averaged():
+                        self.save(model_save_dir=save_dir, saver=saver, tags=save_tags, name=save_name,
+                                  include_global_step=True, include_last_training_loss=True,
+                                  include_metrics=bool(self.metric_names))
 
                 # Bests are updated after the save decision (fcn8s_tensorflow.py:648-658).
                 self.best_training_loss = min(self.best_training_loss, self.training_loss)
@@ -299,6 +317,8 @@ class FCN8s:
                 self.engine.discard_accumulated()
             if max_norm:
                 self.engine.set_grad_clip(prev_clip)
+            if ema_d:
+                self.engine.set_ema(**(prev_ema or dict(decay=None)))
             if custom_loss:
                 self.engine.set_loss(**(prev_loss or {}))
             if custom_lovasz:
@@ -387,6 +407,13 @@ class FCN8s:
 
         if self.engine.rank == 0:
             print(''.join('{}: {:.4f}  '.format(n, v) for n, v in zip(self.metric_names, self.metric_values)))
+
+    def averaged_weights(self):
+        '''Not in the reference: `with model.averaged_weights():` makes the exponential moving average of the parameters that
+        `train(..., ema_decay=...)` kept the live weights for the block -- `evaluate`, `predict*`, `evaluate_cityscapes`, `calibrate_fp8`
+        and `save` inside it work on the average -- and puts the raw weights back behind it, whatever the block raises.  Training inside
+        the block raises.  Without an average the block runs on the weights as they are.'''
+        return self.engine.averaged_weights()
 
     def calibrate_fp8(self, data_generator, num_batches):
         '''Not in the reference: switch the engine to the inference-only 'fp8_infer' precision and calibrate its static per-layer activation
@@ -667,7 +694,8 @@ class FCN8s:
     def export_tf_variables(self, prefix, include_optimizer_state=True):
         '''Not in the reference: writes all variables (and the Adam slots / global_step under the names
         tf.train.AdamOptimizer(name='adam_optimizer') gives them) as a TensorFlow tensor bundle
-        `<prefix>.index` + `<prefix>.data-00000-of-00001`, restorable with tf.train.Saver.'''
+        `<prefix>.index` + `<prefix>.data-00000-of-00001`, restorable with tf.train.Saver.  A parameter average (train's `ema_decay`)
+        is written as `<variable>/ExponentialMovingAverage`, the shadow variables of tf.train.ExponentialMovingAverage.'''
         tensors = dict(self.engine.get_params())
         if include_optimizer_state:
             m, v = self.engine.get_opt_state()
@@ -681,6 +709,11 @@ class FCN8s:
             # saveable variables (load_variables, :943) would not restore without them
             tensors['optimizer/beta1_power'] = np.asarray(0.9 ** (step + 1), dtype=np.float32)
             tensors['optimizer/beta2_power'] = np.asarray(0.999 ** (step + 1), dtype=np.float32)
+        info = self.engine.ema_info()
+        if info['has_shadow'] and not info['swapped']:      # the names tf.train.ExponentialMovingAverage.average_name gives its shadow variables
+            sh = self.engine.get_ema()
+            for k, (shape, off) in self.engine.specs.items():
+                tensors[k + tf_bundle.EMA_SUFFIX] = self.engine.unpad(k, sh[off:off + int(np.prod(shape))].reshape(shape))
         tf_bundle.write_bundle(prefix, tensors)
 
     def close(self):
@@ -698,6 +731,9 @@ def _save_checkpoint(engine, path):
     arrays['__adam_m__'] = m
     arrays['__adam_v__'] = v
     arrays['optimizer/global_step'] = np.asarray(engine.global_step, dtype=np.int64)
+    info = engine.ema_info()
+    if info['has_shadow'] and not info['swapped']:      # (inside averaged_weights() the variables ARE the average: a checkpoint to serve, without a shadow)
+        arrays['__ema__'] = engine.get_ema()
     tmp = path + '.tmp.npz'
     np.savez(tmp, **arrays)
     os.replace(tmp, path)
@@ -711,6 +747,8 @@ def _load_checkpoint(engine, path, with_state=True):
             engine.set_opt_state(data['__adam_m__'], data['__adam_v__'])
         if 'optimizer/global_step' in data.files:
             engine.global_step = int(data['optimizer/global_step'])
+        if '__ema__' in data.files:
+            engine.set_ema_state(data['__ema__'])
 
 
 def _load_tf_tensors(engine, tensors, with_state=True):
@@ -727,6 +765,12 @@ def _load_tf_tensors(engine, tensors, with_state=True):
             found = True
     if found:
         engine.set_opt_state(m, v)
+    if any(k + tf_bundle.EMA_SUFFIX in tensors for k in engine.specs):      # tf.train.ExponentialMovingAverage's shadow variables
+        s = engine.flat_params.detach().cpu().numpy().copy()                # (a variable without one keeps s = theta)
+        for k, (shape, off) in engine.specs.items():
+            if k + tf_bundle.EMA_SUFFIX in tensors:
+                s[off:off + int(np.prod(shape))] = engine.pad(k, tensors[k + tf_bundle.EMA_SUFFIX]).reshape(-1)
+        engine.set_ema_state(s)
     for key in ('optimizer/global_step', 'global_step'):
         if key in tensors:
             engine.global_step = int(np.asarray(tensors[key]).reshape(-1)[0])
@@ -737,6 +781,10 @@ def _write_meta(target, engine, tags):
     meta = {'format': 'fcn8s_tensorflow_amd/1', 'num_classes': engine.logical_classes, 'widths': list(engine.widths),
             'fc6_ksize': engine.specs['fc6/weights'][0][0], 'tags': list(tags) if tags else None,
             'global_step': engine.global_step}
+    info = engine.ema_info()
+    if info['decay'] > 0:                 # the parameter average's setting (the shadow itself: '__ema__' of the checkpoint)
+        meta['ema_decay'] = info['decay']
+        meta['ema_warmup'] = info['warmup']
     cal = engine.fp8_calibration()
     if cal is not None:                   # the 'fp8_infer' calibration (float32 values, stored exactly as Python floats)
         meta['fp8_calibration'] = [float(v) for v in cal]

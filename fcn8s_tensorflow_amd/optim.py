@@ -7,6 +7,11 @@ the caller's grad_scale carries the 1 / A.
 Clip: S = sum (double)g_i^2; norm = float32(|grad_scale| sqrt(S)); c = max_norm / max(norm, max_norm) in float32 (c = 1 for
 max_norm = inf, or 0 = off); s = float32(grad_scale * c); ok = isfinite(norm).  The optimizer computes g * s where it computes
 g * grad_scale without a clip; if not ok it touches neither the parameters nor its slots.
+
+The average (fcn8s_set_ema): a shadow s of the parameters, s = theta when it is first switched on.  After every applied update, with t
+the new global step: d_t = min(d, (1 + t) / (10 + t)) with warm-up, else d, in double (tf.train.ExponentialMovingAverage's num_updates
+rule); w = float32(1 - d_t); s <- s - w (s - theta) in float32 (assign_moving_average without zero-debias).  A skipped update leaves s
+alone, accumulation never touches it, replicas hold the same s.  d in (0, 1); 0 or None = off.
 """
 import math
 
@@ -38,6 +43,37 @@ def validate(accumulation_steps=1, clip_global_norm=None):
     if not v > 0.0:
         raise ValueError("`clip_global_norm` must be positive (inf = guard only) or None, got {!r}".format(clip_global_norm))
     return int(a), v
+
+
+def validate_ema(ema_decay=None, ema_warmup=True):
+    """-> (float decay as the C ABI receives it, 0.0 = off (None means off), bool warmup); ValueError for what fcn8s_set_ema rejects:
+    a decay that is not a number, NaN, negative or >= 1."""
+    if ema_decay is None:
+        return 0.0, bool(ema_warmup)
+    try:
+        d = float(ema_decay)
+    except (TypeError, ValueError):
+        raise ValueError("`ema_decay` must be a number in (0, 1), 0 or None (off), got {!r}".format(ema_decay))
+    if isinstance(ema_decay, bool) or math.isnan(d) or d < 0.0 or d >= 1.0:
+        raise ValueError("`ema_decay` must be in (0, 1), 0 or None (off), got {!r}".format(ema_decay))
+    return d, bool(ema_warmup)
+
+
+def ema_decay_at(decay, t, warmup=True):
+    """d_t of the update that makes the global step t (>= 1), in float64: min(decay, (1 + t) / (10 + t)) with warm-up, else decay."""
+    d = float(decay)
+    return min(d, (1.0 + float(t)) / (10.0 + float(t))) if warmup else d
+
+
+def ema_omega(decay, t, warmup=True):
+    """w = float32(1 - d_t): the weight of the new parameters in the update that makes the global step t."""
+    return np.float32(1.0 - ema_decay_at(decay, t, warmup))
+
+
+def ema_step(s, theta, omega):
+    """s - w (s - theta) in float64 with w = float64(float32(omega)) (the device: float32, one subtraction and one fused multiply-add)."""
+    s = np.asarray(s, np.float64); theta = np.asarray(theta, np.float64)
+    return s - float(np.float32(omega)) * (s - theta)
 
 
 def _flat(g):

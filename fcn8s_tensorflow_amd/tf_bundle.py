@@ -408,6 +408,7 @@ def write_bundle(prefix, tensors, shards=1, partition=None):
 # ---- mapping onto the FCN-8s variables ---------------------------------------------------------------------
 ADAM_M_SUFFIX = "/adam_optimizer"        # tf.train.AdamOptimizer(name='adam_optimizer') slot names (fcn8s_tensorflow.py:256)
 ADAM_V_SUFFIX = "/adam_optimizer_1"
+EMA_SUFFIX = "/ExponentialMovingAverage"   # tf.train.ExponentialMovingAverage.average_name(var): the shadow variable of `var`
 
 
 def find_bundle_prefix(path):

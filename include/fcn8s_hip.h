@@ -267,6 +267,40 @@ int fcn8s_accumulate_discard(fcn8s_model* m);                         /* k_b = 0
 int fcn8s_set_grad_clip(fcn8s_model* m, float max_norm);
 int fcn8s_get_update_stats(fcn8s_model* m, float* norm, float* clip_coef, float* scale, int64_t* skipped);
 
+/* ---- the average: an exponential moving average of the parameters, kept on the device (not in fcn8s_tensorflow.py; what
+ * tf.train.ExponentialMovingAverage(decay, num_updates=global_step) gives a TensorFlow 1.x training script) -----------------------------------
+ * Shadow.  The model owns one shadow s of fcn8s_param_floats() floats.  It is allocated when the average is first switched on (fcn8s_set_ema
+ *   with decay > 0, or fcn8s_set_ema_state), counted as one "workspace_allocation", and kept until fcn8s_destroy.  At that moment s = theta
+ *   (a stream-ordered device copy).  decay = 0 switches the average off and keeps the memory and the contents; switching it on again continues
+ *   from them.  fcn8s_ema_reset sets s = theta.  With the average never switched on nothing is allocated and no kernel below runs.
+ * Update.  After every applied update, with t the new global step (what fcn8s_global_step returns after the call):
+ *     d_t = warmup ? min(d, (1 + t) / (10 + t)) : d   in double (TensorFlow's num_updates rule);   w = (float)(1.0 - d_t);
+ *     s_i <- s_i - w (s_i - theta_i)   in fp32, theta the parameters after the update: d = fl(s_i - theta_i), then one fused multiply-add
+ *     fma(-w, d, s_i) (assign_moving_average without zero-debias).  d in (0, 1); 0 = off.
+ *   TF-Adam and SGD-momentum compute theta and their slots with the expressions (and the bits) of the kernels that run without an average and
+ *   fold the new theta into s in the same pass: 36 / 28 bytes per element instead of 28 / 20 (profile groups "adam" / "sgd_momentum").  With
+ *   FCN8S_OPT_NONE the caller has written theta; fcn8s_apply_update folds theta as it stands on the stream into s (group "ema_update", 12 bytes
+ *   per element).  fcn8s_train_step follows through its fcn8s_apply_update.
+ * Guard.  An update that the non-finite guard skips (ok == 0) leaves s untouched, as it leaves theta and the slots; the step still advances.
+ * Accumulation.  fcn8s_accumulate_bucket never touches s; only the update does.
+ * Data parallel.  Replicas hold identical theta, hence identical s: nothing is exchanged.
+ * Swap.  fcn8s_ema_swap exchanges theta and s in place (one kernel, no third buffer; group "ema_swap", 16 bytes per element) and toggles a
+ *   `swapped` flag.  The live parameters changed: like fcn8s_set_param it leaves the frozen state, drops the cached banks and clears an fp8
+ *   calibration.  While swapped, everything that reads parameters (evaluation, every prediction call, fp8 calibration, fcn8s_get_param) works on
+ *   the averaged weights, fcn8s_get_ema reads the raw ones, and fcn8s_apply_update, fcn8s_train_step, fcn8s_accumulate_bucket, fcn8s_ema_reset
+ *   and fcn8s_set_ema_state return FCN8S_ERR_STATE with theta, s, the slots and the step untouched: nobody trains the average by accident.  A
+ *   second swap restores the raw weights bit for bit.
+ * fcn8s_set_ema: decay NaN, negative or >= 1 is FCN8S_ERR_BAD_ARG; accepted under FCN8S_PREC_FP8_INFER (the training calls refuse there anyway).
+ * fcn8s_ema_reset, fcn8s_ema_swap, fcn8s_get_ema without a shadow: FCN8S_ERR_STATE.  fcn8s_get_ema / fcn8s_set_ema_state: the flat shadow, n ==
+ *   fcn8s_param_floats() (the layout of fcn8s_get_opt_state); set allocates the shadow if there is none and does not switch the average on.
+ * fcn8s_get_ema_info: any pointer may be NULL.  The setting and the shadow survive fcn8s_set_precision, fcn8s_set_option and freezing.       */
+int fcn8s_set_ema(fcn8s_model* m, double decay, int warmup);
+int fcn8s_ema_reset(fcn8s_model* m);
+int fcn8s_ema_swap(fcn8s_model* m);
+int fcn8s_get_ema_info(const fcn8s_model* m, double* decay, int* warmup, int* has_shadow, int* swapped);
+int fcn8s_get_ema(fcn8s_model* m, float* host, size_t nfloats);
+int fcn8s_set_ema_state(fcn8s_model* m, const float* host, size_t nfloats);
+
 /* ---- data parallelism inside the library: one RCCL rank per model (SURVEY section 7 step 7, 8b "RCCL error"; the reference is one
  * tf.Session on one device, fcn8s_tensorflow.py:65, so there is nothing to cite for the collective itself).  A caller that keeps the
  * reference's Python and binds this ABI gets multi-GPU training without torch.distributed:
@@ -694,6 +728,17 @@ int fcn8s_op_tf_adam_dev(void* stream, float* theta, const float* g, float* m, f
                          float lr, float beta1, float beta2, float eps, const float* out5_dev);
 int fcn8s_op_sgd_momentum_dev(void* stream, float* theta, const float* g, float* buf, int64_t n,
                               float lr, float momentum, const float* out5_dev);
+/* the kernels of "the average" on DEVICE pointers of any float alignment.  ema_update: s <- s - w (s - theta) over n floats, w =
+ * one_minus_decay; out5_dev (may be NULL) is a slab as fcn8s_op_grad_norm writes it: out5_dev[3] == 0 touches nothing.  tf_adam_ema /
+ * sgd_momentum_ema: fcn8s_op_tf_adam / fcn8s_op_sgd_momentum (out5_dev == NULL: host grad_scale) or their _dev forms (out5_dev != NULL:
+ * grad_scale is ignored) on theta and the slots -- the same bits --, then ema_update of s with the new theta, in one pass.  swap: the n floats
+ * at a and at b change places (the ranges must not overlap).  FCN8S_ERR_BAD_ARG for a null pointer or n < 0. */
+int fcn8s_op_ema_update(void* stream, float* s, const float* theta, int64_t n, float one_minus_decay, const float* out5_dev);
+int fcn8s_op_tf_adam_ema(void* stream, float* theta, const float* g, float* m, float* v, float* s, int64_t n, int t,
+                         float lr, float beta1, float beta2, float eps, float grad_scale, const float* out5_dev, float one_minus_decay);
+int fcn8s_op_sgd_momentum_ema(void* stream, float* theta, const float* g, float* buf, float* s, int64_t n,
+                              float lr, float momentum, float grad_scale, const float* out5_dev, float one_minus_decay);
+int fcn8s_op_swap(void* stream, float* a, float* b, int64_t n);
 
 #ifdef __cplusplus
 }
