@@ -1090,54 +1090,6 @@ void launch_axpy(float* y, const float* x, float a, long long n, hipStream_t s)
     hipLaunchKernelGGL(axpy_kernel, dim3(cap_blocks(n, 256)), dim3(256), 0, s, y, x, a, n);
 }
 
-// ---- K12: optimizers over the flat buffers -------------------------------------
-__global__ __launch_bounds__(256) void tf_adam_kernel(float4* theta, const float4* g, float4* m, float4* v,
-                                                      long long n4, float lr_t, float b1, float b2, float eps,
-                                                      float gs)
-{
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        float4 t = theta[i], gg = g[i], mm = m[i], vv = v[i];
-#define ADAM1(F) { const float gr = gg.F * gs; mm.F = b1 * mm.F + (1.f - b1) * gr; vv.F = b2 * vv.F + (1.f - b2) * gr * gr; \
-                   t.F -= lr_t * mm.F / (sqrtf(vv.F) + eps); }
-        ADAM1(x) ADAM1(y) ADAM1(z) ADAM1(w)
-#undef ADAM1
-        theta[i] = t; m[i] = mm; v[i] = vv;
-    }
-}
-__global__ void tf_adam_tail_kernel(float* theta, const float* g, float* m, float* v, long long n0, long long n,
-                                    float lr_t, float b1, float b2, float eps, float gs)
-{
-    const long long i = n0 + threadIdx.x;
-    if (i < n) {
-        const float gr = g[i] * gs;
-        m[i] = b1 * m[i] + (1.f - b1) * gr; v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
-        theta[i] -= lr_t * m[i] / (sqrtf(v[i]) + eps);
-    }
-}
-void launch_tf_adam(float* theta, const float* g, float* m, float* v, long long n,
-                    float lr_t, float b1, float b2, float eps, float gscale, hipStream_t s)
-{
-    const long long n4 = n / 4;
-    if (n4 > 0)
-        hipLaunchKernelGGL(tf_adam_kernel, dim3(cap_blocks(n4, 256)), dim3(256), 0, s, (float4*)theta, (const float4*)g,
-                           (float4*)m, (float4*)v, n4, lr_t, b1, b2, eps, gscale);
-    if (n4 * 4 < n)
-        hipLaunchKernelGGL(tf_adam_tail_kernel, dim3(1), dim3(4), 0, s, theta, g, m, v, n4 * 4, n, lr_t, b1, b2, eps, gscale);
-}
-__global__ __launch_bounds__(256) void sgd_momentum_kernel(float* theta, const float* g, float* buf, long long n,
-                                                           float lr, float mom, float gs)
-{
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float b = mom * buf[i] + g[i] * gs;
-        buf[i] = b;
-        theta[i] -= lr * b;
-    }
-}
-void launch_sgd_momentum(float* theta, const float* g, float* buf, long long n, float lr, float mom, float gscale, hipStream_t s)
-{
-    hipLaunchKernelGGL(sgd_momentum_kernel, dim3(cap_blocks(n, 256)), dim3(256), 0, s, theta, g, buf, n, lr, mom, gscale);
-}
-
 // ---- weight re-layouts ---------------------------------------------------------
 // wt[T-1-t][co][ci] = w[t][ci][co]   (data-gradient weights of a SAME conv)
 __global__ void flip_transpose_kernel(const float* w, float* wt, int taps, int Cin, int Cout)

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include "../../include/fcn8s_hip.h"      // the status codes (defer_error)
 
 // gfx950 (MI355X, CDNA4) only: the kernels rely on 160 KB of LDS per workgroup (conv_bf16_256_kernel: five 32 KB stages; wino_out_in_kernel: 96 KB
@@ -281,29 +282,28 @@ bool launch_maxpool_bwd_bf16(const float* x, const float* dy, unsigned short* dz
 void launch_colsum(const float* x, float* out, long long rows, int C, hipStream_t s);      // out[c] += sum_r x[r,c]
 void launch_sumsq(const float* x, float* out, long long n, hipStream_t s);                  // out[0] += sum x^2
 void launch_axpy(float* y, const float* x, float a, long long n, hipStream_t s);           // y += a*x
-void launch_tf_adam(float* theta, const float* g, float* m, float* v, long long n,
-                    float lr_t, float b1, float b2, float eps, float gscale, hipStream_t s);
-void launch_sgd_momentum(float* theta, const float* g, float* buf, long long n,
-                         float lr, float mom, float gscale, hipStream_t s);
-// optim.hip: gradient accumulation over micro-batches, the global-norm clip and the optimizers that read their scale from the device
+// optim.hip: gradient accumulation over micro-batches, the global-norm clip, the optimizers and the moving average of the parameters
 void launch_grad_accumulate(float* dst, const float* src, long long n, int mode, hipStream_t s);   // mode 0: dst = src, 1: dst += src; any float alignment
 constexpr int kGradNormBlocks = 2048;                                      // blocks (and partials) of the norm pass: a constant, never the device's CU count
 struct UpdateStats { float norm, clip, scale; int ok; unsigned long long skipped; };      // what grad_norm_finalize writes (a model's slab)
 // S = sum (double)g^2 through `partials` (kGradNormBlocks doubles) in a fixed order; then {norm, c, s, ok} and, if !ok, ++skipped into `out`.
 // as_floats: `out` is float[5] = {norm, c, s, ok (1.0f / 0.0f), 0} instead (fcn8s_op_grad_norm); the word at index 3 is non-zero exactly when ok
 void launch_grad_norm(const float* g, long long n, float grad_scale, float max_norm, double* partials, void* out, bool as_floats, hipStream_t s);
-// launch_tf_adam / launch_sgd_momentum with gscale = *s_dev; *ok_dev == 0: nothing is touched
-void launch_tf_adam_dev(float* theta, const float* g, float* m, float* v, long long n,
-                        float lr_t, float b1, float b2, float eps, const float* s_dev, const int* ok_dev, hipStream_t s);
-void launch_sgd_momentum_dev(float* theta, const float* g, float* buf, long long n,
-                             float lr, float mom, const float* s_dev, const int* ok_dev, hipStream_t s);
-// optim.hip: the moving average of the parameters.  w = (float)(1 - decay_t); s <- s - w (s - theta), the same bits from all three kernels.
-// launch_tf_adam_ema / launch_sgd_momentum_ema: the update (host scale, or s_dev / ok_dev as above when s_dev != nullptr) and the average of the
-// new theta in one pass; launch_ema_update: the average alone (ok_dev may be null); launch_swap: a <-> b.  Any float alignment of any pointer.
-void launch_tf_adam_ema(float* theta, const float* g, float* m, float* v, float* sh, long long n, float lr_t, float b1, float b2, float eps,
-                        float gscale, const float* s_dev, const int* ok_dev, float w, hipStream_t s);
-void launch_sgd_momentum_ema(float* theta, const float* g, float* buf, float* sh, long long n, float lr, float mom,
-                             float gscale, const float* s_dev, const int* ok_dev, float w, hipStream_t s);
+// One optimizer step over n floats at any float alignment of any pointer.  opt: FCN8S_OPT_TF_ADAM (p0 .. p3 = lr_t, beta1, beta2, eps; m, v) or
+// FCN8S_OPT_SGD_MOMENTUM (p0, p1 = lr, momentum; m is the buffer, v null).  The gradient is scaled by gs, or, when s_dev != nullptr, by *s_dev, and
+// then *ok_dev == 0 means that nothing is touched.  shadow != nullptr: the average s <- s - ema_w (s - theta) of the new theta in the same pass,
+// w = (float)(1 - decay_t), the same bits as launch_ema_update gives.
+struct UpdateArgs {
+    int opt; float* theta; const float* g; float* m; float* v; float* shadow; long long n;
+    float p0, p1, p2, p3, gs; const float* s_dev; const int* ok_dev; float ema_w;
+};
+void launch_update(const UpdateArgs& a, hipStream_t s);
+// TF-Adam's step size at step t (1-based) with both bias corrections folded in
+inline float tf_adam_lr_t(float lr, float b1, float b2, long long t)
+{
+    return lr * (float)std::sqrt(1.0 - std::pow((double)b2, (double)t)) / (float)(1.0 - std::pow((double)b1, (double)t));
+}
+// launch_ema_update: the average alone (ok_dev may be null); launch_swap: a <-> b.  Any float alignment of any pointer.
 void launch_ema_update(float* sh, const float* theta, long long n, float w, const int* ok_dev, hipStream_t s);
 void launch_swap(float* a, float* b, long long n, hipStream_t s);
 // weight re-layouts (run once per step, tiny next to the convs)

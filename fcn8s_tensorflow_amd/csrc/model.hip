@@ -3023,25 +3023,17 @@ int fcn8s_apply_update(fcn8s_model* m, int optimizer, float lr, float grad_scale
         launch_grad_norm(m->d_grads, (long long)m->total, grad_scale, m->max_norm, (double*)(m->upd_ws + kUpdPartialsOff), st, false, m->stream);
     }
     m->last_update_clipped = clip;
-    // the average: w = 1 - d_t for the step this update makes; the fused kernels fold the new theta into the shadow in the update's own pass
+    // the average: w = 1 - d_t for the step this update makes; the update kernel folds the new theta into the shadow in its own pass
     const bool ema = m->ema_decay > 0.0 && m->d_ema;
     const float ema_w = ema ? ema_one_minus_decay(m->ema_decay, m->ema_warmup, t) : 0.f;
-    if (optimizer == FCN8S_OPT_TF_ADAM) {
+    if (optimizer == FCN8S_OPT_TF_ADAM || optimizer == FCN8S_OPT_SGD_MOMENTUM) {
         int rc = ensure_opt_state(m); if (rc) return rc;
-        const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-        const float lr_t = lr * (float)std::sqrt(1.0 - std::pow((double)b2, (double)t)) / (float)(1.0 - std::pow((double)b1, (double)t));
-        ProfScope ps(m, "adam", 0, (ema ? 36.0 : 28.0) * m->total);
-        if (ema) launch_tf_adam_ema(m->d_params, m->d_grads, m->d_m, m->d_v, m->d_ema, (long long)m->total, lr_t, b1, b2, eps, grad_scale,
-                                    clip ? &st->scale : nullptr, clip ? &st->ok : nullptr, ema_w, m->stream);
-        else if (clip) launch_tf_adam_dev(m->d_params, m->d_grads, m->d_m, m->d_v, (long long)m->total, lr_t, b1, b2, eps, &st->scale, &st->ok, m->stream);
-        else launch_tf_adam(m->d_params, m->d_grads, m->d_m, m->d_v, (long long)m->total, lr_t, b1, b2, eps, grad_scale, m->stream);
-    } else if (optimizer == FCN8S_OPT_SGD_MOMENTUM) {
-        int rc = ensure_opt_state(m); if (rc) return rc;
-        ProfScope ps(m, "sgd_momentum", 0, (ema ? 28.0 : 20.0) * m->total);
-        if (ema) launch_sgd_momentum_ema(m->d_params, m->d_grads, m->d_m, m->d_ema, (long long)m->total, lr, 0.9f, grad_scale,
-                                         clip ? &st->scale : nullptr, clip ? &st->ok : nullptr, ema_w, m->stream);
-        else if (clip) launch_sgd_momentum_dev(m->d_params, m->d_grads, m->d_m, (long long)m->total, lr, 0.9f, &st->scale, &st->ok, m->stream);
-        else launch_sgd_momentum(m->d_params, m->d_grads, m->d_m, (long long)m->total, lr, 0.9f, grad_scale, m->stream);
+        const bool adam = optimizer == FCN8S_OPT_TF_ADAM;
+        UpdateArgs u = { optimizer, m->d_params, m->d_grads, m->d_m, nullptr, ema ? m->d_ema : nullptr, (long long)m->total,
+                         lr, 0.9f, 0.f, 0.f, grad_scale, clip ? &st->scale : nullptr, clip ? &st->ok : nullptr, ema_w };      // SGD: lr, momentum 0.9
+        if (adam) { u.v = m->d_v; u.p0 = tf_adam_lr_t(lr, 0.9f, 0.999f, t); u.p2 = 0.999f; u.p3 = 1e-8f; }                  // (p1: beta1 is 0.9 too)
+        ProfScope ps(m, adam ? "adam" : "sgd_momentum", 0, ((adam ? 28.0 : 20.0) + (ema ? 8.0 : 0.0)) * m->total);
+        launch_update(u, m->stream);
     } else if (optimizer != FCN8S_OPT_NONE) return fail(m, FCN8S_ERR_BAD_ARG, "unknown optimizer");
     else if (ema) {      // the caller has written theta: fold it as it stands on the stream
         ProfScope ps(m, "ema_update", 0, 12.0 * m->total);
@@ -4146,13 +4138,17 @@ int fcn8s_op_boundary_distance(void* stream, const uint8_t* label_ids, int N, in
     launch_boundary_distance(label_ids, N, H, W, R, codes_out, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
-int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* mm, float* v, int64_t n, int t, float lr, float b1, float b2, float eps, float gs)
+// the six op-level forms of the update: host scale or the slab's (out5 + 2: s, out5 + 3: ok), with or without a shadow
+static int op_update(void* stream, int opt, float* theta, const float* g, float* m, float* v, float* shadow, int64_t n,
+                     float p0, float p1, float p2, float p3, float gs, const float* out5, float w)
 {
-    const float lr_t = lr * (float)std::sqrt(1.0 - std::pow((double)b2, (double)t)) / (float)(1.0 - std::pow((double)b1, (double)t));
-    launch_tf_adam(theta, g, mm, v, n, lr_t, b1, b2, eps, gs, (hipStream_t)stream); OPCHK(); return FCN8S_OK;
+    launch_update({ opt, theta, g, m, v, shadow, n, p0, p1, p2, p3, gs, out5 ? out5 + 2 : nullptr, out5 ? (const int*)(out5 + 3) : nullptr, w }, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
 }
+int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* mm, float* v, int64_t n, int t, float lr, float b1, float b2, float eps, float gs)
+{ return op_update(stream, FCN8S_OPT_TF_ADAM, theta, g, mm, v, nullptr, n, tf_adam_lr_t(lr, b1, b2, t), b1, b2, eps, gs, nullptr, 0.f); }
 int fcn8s_op_sgd_momentum(void* stream, float* theta, const float* g, float* buf, int64_t n, float lr, float mom, float gs)
-{ launch_sgd_momentum(theta, g, buf, n, lr, mom, gs, (hipStream_t)stream); OPCHK(); return FCN8S_OK; }
+{ return op_update(stream, FCN8S_OPT_SGD_MOMENTUM, theta, g, buf, nullptr, nullptr, n, lr, mom, 0.f, 0.f, gs, nullptr, 0.f); }
 int fcn8s_op_grad_accumulate(void* stream, float* dst, const float* src, int64_t n, int mode)
 {
     if (!dst || !src || n < 0 || (mode != 0 && mode != 1)) return fail(nullptr, FCN8S_ERR_BAD_ARG, "grad_accumulate: bad argument (null pointer, n < 0, or mode outside {0, 1})");
@@ -4172,13 +4168,12 @@ int fcn8s_op_grad_norm(void* stream, const float* g, int64_t n, float grad_scale
 int fcn8s_op_tf_adam_dev(void* stream, float* theta, const float* g, float* mm, float* v, int64_t n, int t, float lr, float b1, float b2, float eps, const float* out5)
 {
     if (!out5) return fail(nullptr, FCN8S_ERR_BAD_ARG, "tf_adam_dev: null out5_dev");
-    const float lr_t = lr * (float)std::sqrt(1.0 - std::pow((double)b2, (double)t)) / (float)(1.0 - std::pow((double)b1, (double)t));
-    launch_tf_adam_dev(theta, g, mm, v, n, lr_t, b1, b2, eps, out5 + 2, (const int*)(out5 + 3), (hipStream_t)stream); OPCHK(); return FCN8S_OK;
+    return op_update(stream, FCN8S_OPT_TF_ADAM, theta, g, mm, v, nullptr, n, tf_adam_lr_t(lr, b1, b2, t), b1, b2, eps, 0.f, out5, 0.f);
 }
 int fcn8s_op_sgd_momentum_dev(void* stream, float* theta, const float* g, float* buf, int64_t n, float lr, float mom, const float* out5)
 {
     if (!out5) return fail(nullptr, FCN8S_ERR_BAD_ARG, "sgd_momentum_dev: null out5_dev");
-    launch_sgd_momentum_dev(theta, g, buf, n, lr, mom, out5 + 2, (const int*)(out5 + 3), (hipStream_t)stream); OPCHK(); return FCN8S_OK;
+    return op_update(stream, FCN8S_OPT_SGD_MOMENTUM, theta, g, buf, nullptr, nullptr, n, lr, mom, 0.f, 0.f, 0.f, out5, 0.f);
 }
 int fcn8s_op_ema_update(void* stream, float* s, const float* theta, int64_t n, float w, const float* out5)
 {
@@ -4189,15 +4184,12 @@ int fcn8s_op_tf_adam_ema(void* stream, float* theta, const float* g, float* mm, 
                          float gs, const float* out5, float w)
 {
     if (!theta || !g || !mm || !v || !s || n < 0) return fail(nullptr, FCN8S_ERR_BAD_ARG, "tf_adam_ema: bad argument (null pointer or n < 0)");
-    const float lr_t = lr * (float)std::sqrt(1.0 - std::pow((double)b2, (double)t)) / (float)(1.0 - std::pow((double)b1, (double)t));
-    launch_tf_adam_ema(theta, g, mm, v, s, n, lr_t, b1, b2, eps, gs, out5 ? out5 + 2 : nullptr, out5 ? (const int*)(out5 + 3) : nullptr, w, (hipStream_t)stream);
-    OPCHK(); return FCN8S_OK;
+    return op_update(stream, FCN8S_OPT_TF_ADAM, theta, g, mm, v, s, n, tf_adam_lr_t(lr, b1, b2, t), b1, b2, eps, gs, out5, w);
 }
 int fcn8s_op_sgd_momentum_ema(void* stream, float* theta, const float* g, float* buf, float* s, int64_t n, float lr, float mom, float gs, const float* out5, float w)
 {
     if (!theta || !g || !buf || !s || n < 0) return fail(nullptr, FCN8S_ERR_BAD_ARG, "sgd_momentum_ema: bad argument (null pointer or n < 0)");
-    launch_sgd_momentum_ema(theta, g, buf, s, n, lr, mom, gs, out5 ? out5 + 2 : nullptr, out5 ? (const int*)(out5 + 3) : nullptr, w, (hipStream_t)stream);
-    OPCHK(); return FCN8S_OK;
+    return op_update(stream, FCN8S_OPT_SGD_MOMENTUM, theta, g, buf, nullptr, s, n, lr, mom, 0.f, 0.f, gs, out5, w);
 }
 int fcn8s_op_swap(void* stream, float* a, float* b, int64_t n)
 {

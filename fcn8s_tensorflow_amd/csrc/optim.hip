@@ -1,7 +1,8 @@
 // The update's own HBM-bound kernels (definitions: include/fcn8s_hip.h, "the update"): folding a gradient bucket into the accumulator and
-// flushing it back, the global norm of the flat gradient buffer in a fixed summation order, and the TF-Adam / SGD-momentum kernels that
-// read their gradient scale and the guard's verdict from device memory; the moving average of the parameters ("the average"): the update fused
-// with it, the average alone, and the swap.  16-byte accesses, grid-stride loops capped at 2048 blocks.
+// flushing it back, the global norm of the flat gradient buffer in a fixed summation order, and the one TF-Adam / SGD-momentum kernel, which takes
+// its gradient scale from the host or, with the guard's verdict, from device memory and folds the moving average of the parameters ("the
+// average") into the same pass when there is one; the average alone, and the swap.  16-byte accesses, grid-stride loops capped at 2048 blocks
+// (the update: one float4 per lane).
 #include "fcn8s_internal.h"
 #include <math.h>
 
@@ -125,72 +126,16 @@ void launch_grad_norm(const float* g, long long n, float grad_scale, float max_n
     else           hipLaunchKernelGGL(grad_norm_finalize_kernel<false>, dim3(1), dim3(256), 0, s, (const double*)partials, grad_scale, max_norm, out);
 }
 
-// ---- the optimizers of elementwise.hip (K12) with the gradient scale and the guard's verdict read from the device ---------------------------
-// the same expressions as tf_adam_kernel / sgd_momentum_kernel: with *s_dev == gs they give the same bits
-__global__ __launch_bounds__(256) void tf_adam_dev_kernel(float4* theta, const float4* g, float4* m, float4* v,
-                                                          long long n4, float lr_t, float b1, float b2, float eps,
-                                                          const float* __restrict__ s_dev, const int* __restrict__ ok_dev)
-{
-    if (*ok_dev == 0) return;
-    const float gs = *s_dev;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        float4 t = theta[i], gg = g[i], mm = m[i], vv = v[i];
-#define ADAM1(F) { const float gr = gg.F * gs; mm.F = b1 * mm.F + (1.f - b1) * gr; vv.F = b2 * vv.F + (1.f - b2) * gr * gr; \
-                   t.F -= lr_t * mm.F / (sqrtf(vv.F) + eps); }
-        ADAM1(x) ADAM1(y) ADAM1(z) ADAM1(w)
-#undef ADAM1
-        theta[i] = t; m[i] = mm; v[i] = vv;
-    }
-}
-__global__ void tf_adam_dev_tail_kernel(float* theta, const float* g, float* m, float* v, long long n0, long long n,
-                                        float lr_t, float b1, float b2, float eps, const float* __restrict__ s_dev, const int* __restrict__ ok_dev)
-{
-    if (*ok_dev == 0) return;
-    const float gs = *s_dev;
-    const long long i = n0 + threadIdx.x;
-    if (i < n) {
-        const float gr = g[i] * gs;
-        m[i] = b1 * m[i] + (1.f - b1) * gr; v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
-        theta[i] -= lr_t * m[i] / (sqrtf(v[i]) + eps);
-    }
-}
-void launch_tf_adam_dev(float* theta, const float* g, float* m, float* v, long long n,
-                        float lr_t, float b1, float b2, float eps, const float* s_dev, const int* ok_dev, hipStream_t s)
-{
-    const long long n4 = n / 4;
-    if (n4 > 0)
-        hipLaunchKernelGGL(tf_adam_dev_kernel, dim3(cap_blocks(n4, 256)), dim3(256), 0, s, (float4*)theta, (const float4*)g,
-                           (float4*)m, (float4*)v, n4, lr_t, b1, b2, eps, s_dev, ok_dev);
-    if (n4 * 4 < n)
-        hipLaunchKernelGGL(tf_adam_dev_tail_kernel, dim3(1), dim3(4), 0, s, theta, g, m, v, n4 * 4, n, lr_t, b1, b2, eps, s_dev, ok_dev);
-}
-__global__ __launch_bounds__(256) void sgd_momentum_dev_kernel(float* theta, const float* g, float* buf, long long n,
-                                                               float lr, float mom, const float* __restrict__ s_dev, const int* __restrict__ ok_dev)
-{
-    if (*ok_dev == 0) return;
-    const float gs = *s_dev;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float b = mom * buf[i] + g[i] * gs;
-        buf[i] = b;
-        theta[i] -= lr * b;
-    }
-}
-void launch_sgd_momentum_dev(float* theta, const float* g, float* buf, long long n, float lr, float mom,
-                             const float* s_dev, const int* ok_dev, hipStream_t s)
-{
-    hipLaunchKernelGGL(sgd_momentum_dev_kernel, dim3(cap_blocks(n, 256)), dim3(256), 0, s, theta, g, buf, n, lr, mom, s_dev, ok_dev);
-}
-
 // ---- the moving average of the parameters (definitions: include/fcn8s_hip.h, "the average") -------------------------------------------------
 // s <- s - w (s - theta): one subtraction and one fused multiply-add, written out so that every kernel below gives the same bits
 static __device__ __forceinline__ float ema1(float s, float t, float w) { return __builtin_fmaf(-w, s - t, s); }
 
-// One element of the updates of elementwise.hip (K12) and of the _dev kernels above, with the roundings written out.  Those kernels leave the
-// contraction of a multiply-add to the compiler, and it decides differently per kernel: the float4 bodies of the Adam kernels (elements below
-// 4 (n / 4)) fuse the last product of the m and of the v update into the sum, their tail kernels (the up to three elements behind) round both
-// products first; the SGD kernels round both products of the momentum and fuse theta's.  FUSED picks the Adam form; a kernel that wants the
-// bits of those kernels picks it by the element's index, whatever lane computes the element.  (contract(off): a * b + c below is two roundings;
-// the one rounding is spelled fmaf.  The __fmul_rn family would not do: it is plain arithmetic that the compiler contracts like any other.)
+// ---- the update: TF-Adam / SGD-momentum, host or device gradient scale, with or without the average -- one kernel body ----------------------
+// One element of the update, with every rounding written out: the bits of a training step are pinned here, not left to the compiler's choice of
+// where to contract a multiply-add.  TF-Adam has two forms: FUSED folds the last product of the m and of the v update into the sum, the other
+// rounds both products first.  Elements below 4 (n / 4) take the fused form, the up to three behind them the other, whatever lane computes the
+// element.  SGD-momentum rounds both products of the momentum and fuses theta's.  (contract(off): a * b + c below is two roundings; the one
+// rounding is spelled fmaf.  The __fmul_rn family would not do: it is plain arithmetic that the compiler contracts like any other.)
 template <bool FUSED>
 static __device__ __forceinline__ void adam1(float& t, float g, float& m, float& v, float lr_t, float b1, float b2, float eps, float gs)
 {
@@ -232,23 +177,26 @@ static __device__ __forceinline__ long long edge_lane(long long gtid, long long 
     return -1;
 }
 
-// The update and the average in one pass: theta, m (, v) as the kernels above compute them, then s from the new theta while it is in registers.
-// OPT 0: TF-Adam (p0 .. p3 = lr_t, beta1, beta2, eps), 1: SGD-momentum (p0, p1 = lr, momentum; v unused).  DEV: the gradient scale and the guard's
-// verdict come from s_dev / ok_dev.  theta + head is 16-byte aligned; ALIGNED: so are g, m, v and s at + head (a model's buffers).
-template <int OPT, bool DEV, bool ALIGNED>
-__global__ __launch_bounds__(256) void update_ema_kernel(float* theta, const float* g, float* m, float* v, float* s, long long head, long long n4, long long n,
-                                                         float p0, float p1, float p2, float p3, float gs_host,
-                                                         const float* __restrict__ s_dev, const int* __restrict__ ok_dev, float w)
+// The one update kernel: theta, m (, v) of an optimizer step and, with EMA, s from the new theta while it is in registers (without: a.shadow is
+// null and never read).  OPT: FCN8S_OPT_TF_ADAM (p0 .. p3 = lr_t, beta1, beta2, eps) or FCN8S_OPT_SGD_MOMENTUM (p0, p1 = lr, momentum; v unused).
+// a.s_dev != nullptr: the gradient scale and the guard's verdict come from the device, and *ok_dev == 0 returns before anything else is read.
+// theta + head is 16-byte aligned; ALIGNED: so are g, m, v and s at + head (a model's buffers).
+template <int OPT, bool EMA, bool ALIGNED>
+static __device__ __forceinline__ void update_body(const UpdateArgs& a, long long head, long long n4)
 {
-    if (DEV) { if (*ok_dev == 0) return; }
-    const float gs = DEV ? *s_dev : gs_host;
+    float gs = a.gs;
+    if (a.s_dev) { if (*a.ok_dev == 0) return; gs = *a.s_dev; }
+    float* theta = a.theta; const float* g = a.g; float* m = a.m; float* v = a.v; float* s = a.shadow;
+    const long long n = a.n;
+    const float p0 = a.p0, p1 = a.p1, p2 = a.p2, p3 = a.p3, w = a.ema_w;
     const long long gtid = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    const long long nb = n & ~3LL;          // Adam: the elements below take the form of the old kernels' float4 body (the launcher ends the body there), the others their tail kernel's
+    const long long nb = n & ~3LL;          // Adam: the launcher ends the float4 body here, so the body is all of the fused form
     for (long long i = gtid; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        float4 t = ((float4*)(theta + head))[i];
+        float4 t = ((float4*)(theta + head))[i], ss;
         const float4 gg = ld4<ALIGNED>(g + head, i);
-        float4 mm = ld4<ALIGNED>(m + head, i), ss = ld4<ALIGNED>(s + head, i);
-        if (OPT == 0) {
+        float4 mm = ld4<ALIGNED>(m + head, i);
+        if (EMA) ss = ld4<ALIGNED>(s + head, i);
+        if (OPT == FCN8S_OPT_TF_ADAM) {
             float4 vv = ld4<ALIGNED>(v + head, i);
             adam1<true>(t.x, gg.x, mm.x, vv.x, p0, p1, p2, p3, gs); adam1<true>(t.y, gg.y, mm.y, vv.y, p0, p1, p2, p3, gs);
             adam1<true>(t.z, gg.z, mm.z, vv.z, p0, p1, p2, p3, gs); adam1<true>(t.w, gg.w, mm.w, vv.w, p0, p1, p2, p3, gs);
@@ -257,45 +205,45 @@ __global__ __launch_bounds__(256) void update_ema_kernel(float* theta, const flo
             sgd1(t.x, gg.x, mm.x, p0, p1, gs); sgd1(t.y, gg.y, mm.y, p0, p1, gs);
             sgd1(t.z, gg.z, mm.z, p0, p1, gs); sgd1(t.w, gg.w, mm.w, p0, p1, gs);
         }
-        ss.x = ema1(ss.x, t.x, w); ss.y = ema1(ss.y, t.y, w); ss.z = ema1(ss.z, t.z, w); ss.w = ema1(ss.w, t.w, w);
         ((float4*)(theta + head))[i] = t;
         st4<ALIGNED>(m + head, i, mm);
-        st4<ALIGNED>(s + head, i, ss);
+        if (EMA) {
+            ss.x = ema1(ss.x, t.x, w); ss.y = ema1(ss.y, t.y, w); ss.z = ema1(ss.z, t.z, w); ss.w = ema1(ss.w, t.w, w);
+            st4<ALIGNED>(s + head, i, ss);
+        }
     }
     const long long j = edge_lane(gtid, head, n4, n);
     if (j >= 0) {
         float t = theta[j], mm = m[j];
-        if (OPT == 0) { float vv = v[j]; adam1(j < nb, t, g[j], mm, vv, p0, p1, p2, p3, gs); v[j] = vv; }
+        if (OPT == FCN8S_OPT_TF_ADAM) { float vv = v[j]; adam1(j < nb, t, g[j], mm, vv, p0, p1, p2, p3, gs); v[j] = vv; }
         else sgd1(t, g[j], mm, p0, p1, gs);
         theta[j] = t; m[j] = mm;
-        s[j] = ema1(s[j], t, w);
+        if (EMA) s[j] = ema1(s[j], t, w);
     }
 }
+// (the names the profile tools know the update by)
+template <bool EMA, bool ALIGNED>
+__global__ __launch_bounds__(256) void tf_adam_kernel(UpdateArgs a, long long head, long long n4) { update_body<FCN8S_OPT_TF_ADAM, EMA, ALIGNED>(a, head, n4); }
+template <bool EMA, bool ALIGNED>
+__global__ __launch_bounds__(256) void sgd_momentum_kernel(UpdateArgs a, long long head, long long n4) { update_body<FCN8S_OPT_SGD_MOMENTUM, EMA, ALIGNED>(a, head, n4); }
 
-static void launch_update_ema(int opt, float* theta, const float* g, float* m, float* v, float* sh, long long n, float p0, float p1, float p2, float p3,
-                              float gs, const float* s_dev, const int* ok_dev, float w, hipStream_t st)
+void launch_update(const UpdateArgs& a, hipStream_t st)
 {
-    if (n <= 0) return;
+    if (a.n <= 0) return;
+    const bool adam = a.opt == FCN8S_OPT_TF_ADAM;
     // Adam: no float4 of the body reaches over 4 (n / 4), so the body is all of one form; up to 3 + 6 scalar lanes
-    const long long head = head_floats(theta, n), nb = n & ~3LL, n4 = opt == 0 ? (nb > head ? (nb - head) / 4 : 0) : (n - head) / 4;
+    const long long n = a.n, head = head_floats(a.theta, n), nb = n & ~3LL, n4 = adam ? (nb > head ? (nb - head) / 4 : 0) : (n - head) / 4;
     auto al16 = [&](const float* p) { return p == nullptr || (((uintptr_t)(p + head)) & 15) == 0; };
-    const bool al = al16(g) && al16(m) && al16(v) && al16(sh), dev = s_dev != nullptr;
-    const dim3 grid(cap_blocks(n4, 256)), block(256);          // (one block at least: the scalar lanes)
-#define UE(O, D, A) hipLaunchKernelGGL((update_ema_kernel<O, D, A>), grid, block, 0, st, theta, g, m, v, sh, head, n4, n, p0, p1, p2, p3, gs, s_dev, ok_dev, w)
-#define UE2(O) do { if (dev) { if (al) UE(O, true, true); else UE(O, true, false); } else { if (al) UE(O, false, true); else UE(O, false, false); } } while (0)
-    if (opt == 0) UE2(0); else UE2(1);
-#undef UE2
-#undef UE
-}
-void launch_tf_adam_ema(float* theta, const float* g, float* m, float* v, float* sh, long long n, float lr_t, float b1, float b2, float eps,
-                        float gscale, const float* s_dev, const int* ok_dev, float w, hipStream_t st)
-{
-    launch_update_ema(0, theta, g, m, v, sh, n, lr_t, b1, b2, eps, gscale, s_dev, ok_dev, w, st);
-}
-void launch_sgd_momentum_ema(float* theta, const float* g, float* buf, float* sh, long long n, float lr, float mom,
-                             float gscale, const float* s_dev, const int* ok_dev, float w, hipStream_t st)
-{
-    launch_update_ema(1, theta, g, buf, nullptr, sh, n, lr, mom, 0.f, 0.f, gscale, s_dev, ok_dev, w, st);
+    const bool al = al16(a.g) && al16(a.m) && al16(a.v) && al16(a.shadow);
+    // One float4 per lane, not cap_blocks' 2048 blocks (the loop stays for a grid clipped at 2^31 - 1): at 16 bytes per lane a capped grid strides
+    // 8 MB per array and iteration, and measured at the model's width that sweep runs the SGD-momentum update at 4.6 TB/s against 5.6 TB/s uncapped.
+    const long long nblk = (n4 + 255) / 256;
+    const dim3 grid((unsigned)(nblk < 1 ? 1 : nblk > 0x7fffffffLL ? 0x7fffffffLL : nblk)), block(256);          // (one block at least: the scalar lanes)
+#define UP(K, E, A) hipLaunchKernelGGL((K<E, A>), grid, block, 0, st, a, head, n4)
+#define UP2(K) do { if (a.shadow) { if (al) UP(K, true, true); else UP(K, true, false); } else { if (al) UP(K, false, true); else UP(K, false, false); } } while (0)
+    if (adam) UP2(tf_adam_kernel); else UP2(sgd_momentum_kernel);
+#undef UP2
+#undef UP
 }
 
 // the average alone (FCN8S_OPT_NONE: the caller wrote theta): s + head is 16-byte aligned; ok_dev may be null (no guard)

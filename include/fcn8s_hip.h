@@ -739,6 +739,8 @@ int fcn8s_op_boundary_pair(void* stream, const uint8_t* gt_label_ids, const void
  * either pointer.  Stream-ordered; does not synchronise; allocates nothing.  FCN8S_ERR_BAD_ARG (nothing launched) for a NULL pointer, N, H or
  * W <= 0, or R outside 1..15; FCN8S_ERR_SHAPE for H * W >= 2^31. */
 int fcn8s_op_boundary_distance(void* stream, const uint8_t* label_ids, int N, int H, int W, int R, uint8_t* codes_out);
+/* One TF-Adam (step t, 1-based) / SGD-momentum step over n floats on DEVICE pointers, the gradient scaled by grad_scale.  Every pointer may
+ * have any float (4-byte) alignment of its own.  These two, their _dev and their _ema forms below run one kernel and give the same bits. */
 int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* m, float* v, int64_t n, int t,
                      float lr, float beta1, float beta2, float eps, float grad_scale);
 int fcn8s_op_sgd_momentum(void* stream, float* theta, const float* g, float* buf, int64_t n,
@@ -746,7 +748,7 @@ int fcn8s_op_sgd_momentum(void* stream, float* theta, const float* g, float* buf
 /* the kernels of fcn8s_accumulate_bucket and of the clipped update on DEVICE pointers of any float alignment.  grad_accumulate: mode 0:
  * dst = src, 1: dst = dst + src, n floats.  grad_norm: out5_dev = float[5] {norm, c, s, ok (1 / 0), 0} of the n floats at g as defined at
  * fcn8s_set_grad_clip (max_norm = 0: c = 1); it allocates its slab of partial sums and synchronises.  tf_adam_dev / sgd_momentum_dev:
- * fcn8s_op_tf_adam / fcn8s_op_sgd_momentum with grad_scale = out5_dev[2]; out5_dev[3] == 0: nothing is touched. */
+ * fcn8s_op_tf_adam / fcn8s_op_sgd_momentum with grad_scale = out5_dev[2], at any float alignment like them; out5_dev[3] == 0: nothing is touched. */
 int fcn8s_op_grad_accumulate(void* stream, float* dst, const float* src, int64_t n, int mode);
 int fcn8s_op_grad_norm(void* stream, const float* g, int64_t n, float grad_scale, float max_norm, float* out5_dev);
 int fcn8s_op_tf_adam_dev(void* stream, float* theta, const float* g, float* m, float* v, int64_t n, int t,

@@ -3,8 +3,11 @@ the updates fused with it, and the swap -- at every float alignment of every poi
 float4 body and the scalar tail.
 
 References: optim.ema_step in float64 fed the same fp32 inputs and the same fp32 weight; the library's own fcn8s_op_tf_adam /
-fcn8s_op_sgd_momentum (and their _dev forms) for theta and the slots; fcn8s_op_ema_update on the resulting theta for the shadow."""
+fcn8s_op_sgd_momentum (and their _dev forms) for theta and the slots, held to tests/golden/update_bits.npz -- the bits of the kernels the
+one update kernel replaced (tests/golden/make_update_bits.py); fcn8s_op_ema_update on the resulting theta for the shadow."""
 import ctypes as C
+import hashlib
+import os
 
 import numpy as np
 import pytest
@@ -15,6 +18,11 @@ pytestmark = pytest.mark.gpu
 from fcn8s_tensorflow_amd import optim  # noqa: E402
 
 SIZES = (1, 3, 4, 5, 255, 1023, 1025, 262147)
+# 2048 * 256 * 4 + 1029: more float4 than 2048 blocks of 256 lanes hold -- a lane of a grid capped there takes a second one -- with a non-empty
+# tail (n mod 4 = 1).
+# The update's golden test only, at two placements.
+BIG = 2098181
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "update_bits.npz")
 SENTINEL = np.float32(-12345.5)
 PAD = 8
 OMEGAS = (np.float32(9.0 / 11.0), np.float32(1.0 - 0.999))          # warm-up's first step, and the steady state of decay 0.999
@@ -50,13 +58,12 @@ def slab(scale, ok):
     return torch.tensor([1.0, 1.0, float(scale), 1.0 if ok else 0.0, 0.0], dtype=torch.float32).cuda()
 
 
-@pytest.fixture(scope="module")
-def data():
-    """n -> dict of float32 arrays (made once, never written): theta and shadow spanning 1e-6 .. 1e3 in magnitude with both signs,
-    gradient, slots"""
+def make_inputs(sizes=SIZES + (BIG,)):
+    """n -> dict of float32 arrays (never written): theta and shadow spanning 1e-6 .. 1e3 in magnitude with both signs, gradient, slots.
+    One seeded stream in the order of `sizes`: a new size goes to the end.  (tests/golden/make_update_bits.py feeds these to the parent's kernels.)"""
     rng = np.random.default_rng(23)
     out = {}
-    for n in SIZES:
+    for n in sizes:
         mag = lambda: (10.0 ** rng.uniform(-6, 3, n) * rng.choice([-1.0, 1.0], n)).astype(np.float32)
         d = dict(theta=mag(), shadow=mag(), g=mag(), m=(rng.standard_normal(n) * 0.1).astype(np.float32),
                  v=(rng.standard_normal(n) ** 2).astype(np.float32))
@@ -65,6 +72,27 @@ def data():
             a.setflags(write=False)
         out[n] = d
     return out
+
+
+@pytest.fixture(scope="module")
+def data():
+    return make_inputs()
+
+
+@pytest.fixture(scope="module")
+def golden():
+    with np.load(GOLDEN) as z:
+        return {k: z[k] for k in z.files}
+
+
+def assert_golden(golden, opt, n, arrays, tag):
+    """arrays (theta, m, v) == the recorded bits of the replaced kernels: raw arrays at the small sizes, SHA-256 digests at the two large ones"""
+    for key, a in zip(("theta", "m", "v") if opt == "adam" else ("theta", "m"), arrays):
+        raw, dig = "%s_%s_%d" % (opt, key, n), "%s_%s_sha256_%d" % (opt, key, n)
+        if raw in golden:
+            assert a.tobytes() == golden[raw].tobytes(), (tag, key, np.flatnonzero(a.view(np.uint32) != golden[raw].view(np.uint32))[:8])
+        else:
+            assert hashlib.sha256(a.tobytes()).hexdigest() == str(golden[dig]), (tag, key)
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -119,39 +147,52 @@ def _reference_update(L, opt, d, n, gs, use_slab):
     return th.cpu().numpy(), m.cpu().numpy(), v.cpu().numpy(), th
 
 
-@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("n", SIZES + (BIG,))
 @pytest.mark.parametrize("opt", ["adam", "sgd"])
-def test_fused_update_equals_update_then_average(opt, n, data):
+def test_fused_update_equals_update_then_average(opt, n, data, golden):
     L = _lib()
     d = data[n]
     gs = 0.37
     w = OMEGAS[0]
+    # every pointer at its own alignment (o = 0: all aligned, the model's case), and all at the same odd one
+    placements = [tuple((o + k) % 4 for k in (0, 1, 2, 0, 3)) for o in range(4)] + [(0, 0, 0, 0, 0), (1, 1, 1, 1, 1), (3, 3, 3, 3, 3)]
+    if n == BIG:
+        placements = [(0, 0, 0, 0, 0), (1, 1, 1, 1, 1)]
     for use_slab in (False, True):
         th_ref, m_ref, v_ref, th_dev = _reference_update(L, opt, d, n, gs, use_slab)
         assert not np.array_equal(th_ref, d["theta"])
+        assert_golden(golden, opt, n, (th_ref, m_ref, v_ref), (opt, n, use_slab))
         s_ref = torch.from_numpy(d["shadow"].copy()).cuda()
         L.check(L.lib.fcn8s_op_ema_update(None, ptr(s_ref), ptr(th_dev), n, float(w), None))
         torch.cuda.synchronize()
         s_ref = s_ref.cpu().numpy()
-        # every pointer at its own alignment (o = 0: all aligned, the model's case), and all at the same odd one
-        for offs in [tuple((o + k) % 4 for k in (0, 1, 2, 0, 3)) for o in range(4)] + [(0, 0, 0, 0, 0), (1, 1, 1, 1, 1), (3, 3, 3, 3, 3)]:
-            th, ta = placed(d["theta"], offs[0]); g, ga = placed(d["g"], offs[1]); m, ma = placed(d["m"], offs[2])
-            v, va = placed(d["v"], offs[3]); s, sa = placed(d["shadow"], offs[4])
+        for offs in placements:
             sl = slab(gs, True) if use_slab else None
             slp = ptr(sl) if use_slab else None
             gsa = 123.0 if use_slab else gs                            # (with a slab the host scale is ignored)
-            if opt == "adam":
-                L.check(L.lib.fcn8s_op_tf_adam_ema(None, ptr(th, ta), ptr(g, ga), ptr(m, ma), ptr(v, va), ptr(s, sa), n, 3, 1e-3, 0.9, 0.999, 1e-8,
-                                                   gsa, slp, float(w)))
-            else:
-                L.check(L.lib.fcn8s_op_sgd_momentum_ema(None, ptr(th, ta), ptr(g, ga), ptr(m, ma), ptr(s, sa), n, 1e-2, 0.9, gsa, slp, float(w)))
-            torch.cuda.synchronize()
-            tag = (opt, n, use_slab, offs)
-            assert taken(th, ta, n).tobytes() == th_ref.tobytes(), tag
-            assert taken(m, ma, n).tobytes() == m_ref.tobytes(), tag
-            assert taken(v, va, n).tobytes() == (v_ref if opt == "adam" else d["v"]).tobytes(), tag
-            assert taken(s, sa, n).tobytes() == s_ref.tobytes(), tag
-            assert np.array_equal(taken(g, ga, n), d["g"])
+            for fused in (True, False):                                # with the average, and the plain / _dev form
+                th, ta = placed(d["theta"], offs[0]); g, ga = placed(d["g"], offs[1]); m, ma = placed(d["m"], offs[2])
+                v, va = placed(d["v"], offs[3]); s, sa = placed(d["shadow"], offs[4])
+                a4 = (ptr(th, ta), ptr(g, ga), ptr(m, ma), ptr(v, va))
+                if opt == "adam" and fused:
+                    L.check(L.lib.fcn8s_op_tf_adam_ema(None, *a4, ptr(s, sa), n, 3, 1e-3, 0.9, 0.999, 1e-8, gsa, slp, float(w)))
+                elif opt == "adam" and use_slab:
+                    L.check(L.lib.fcn8s_op_tf_adam_dev(None, *a4, n, 3, 1e-3, 0.9, 0.999, 1e-8, slp))
+                elif opt == "adam":
+                    L.check(L.lib.fcn8s_op_tf_adam(None, *a4, n, 3, 1e-3, 0.9, 0.999, 1e-8, gs))
+                elif fused:
+                    L.check(L.lib.fcn8s_op_sgd_momentum_ema(None, *a4[:3], ptr(s, sa), n, 1e-2, 0.9, gsa, slp, float(w)))
+                elif use_slab:
+                    L.check(L.lib.fcn8s_op_sgd_momentum_dev(None, *a4[:3], n, 1e-2, 0.9, slp))
+                else:
+                    L.check(L.lib.fcn8s_op_sgd_momentum(None, *a4[:3], n, 1e-2, 0.9, gs))
+                torch.cuda.synchronize()
+                tag = (opt, n, use_slab, offs, fused)
+                assert taken(th, ta, n).tobytes() == th_ref.tobytes(), tag
+                assert taken(m, ma, n).tobytes() == m_ref.tobytes(), tag
+                assert taken(v, va, n).tobytes() == (v_ref if opt == "adam" else d["v"]).tobytes(), tag
+                assert taken(s, sa, n).tobytes() == (s_ref if fused else d["shadow"]).tobytes(), tag
+                assert np.array_equal(taken(g, ga, n), d["g"])
     # ok = 0: nothing changes
     th, ta = placed(d["theta"], 1); g, ga = placed(d["g"], 2); m, ma = placed(d["m"], 3); v, va = placed(d["v"], 0); s, sa = placed(d["shadow"], 1)
     sl = slab(gs, False)

@@ -9,6 +9,11 @@ once per round in turn.
       unfused    off + fcn8s_op_ema_update                         40 / 32 B per element
     From bytes alone (estimates, not measurements): fused / off = 1.29 (Adam), 1.4 (SGD); unfused / off = 1.43, 1.6.
     WHAT MUST HOLD: fused < unfused in the same run (row field `fused_faster`).
+  * --baseline-lib PATH: a second copy of the library (a build of another commit, outside the tree's own) is loaded with the prototypes of
+    _lib.py.  Its off and fused forms are timed in the same rounds ("baseline_off", "baseline_fused"), and theta, m, v (and s) after one
+    step of either library from identical inputs are compared with == at full width (rows of kind "bits_vs_baseline").
+    WHAT MUST HOLD: per optimizer, off and fused, this tree's median <= the baseline's median + the baseline's own min-max spread over the
+    rounds (rows of kind "vs_baseline", field `no_slower`), and every `equal` is true; the exit status says so.
   * swap       fcn8s_op_swap, 16 B per element.
   * step       Engine.train_step at 16 x 1024x512 (device inputs, fp32) with the average off and on, alternating.
 
@@ -38,6 +43,7 @@ def main():
     ap.add_argument("--height", type=int, default=H)
     ap.add_argument("--width", type=int, default=W)
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--baseline-lib", default=None, help="libfcn8s_hip.so of another build to time and compare the updates against")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.rounds < 20 or a.step_rounds < 20:
@@ -98,6 +104,16 @@ def main():
     sgd_off = lambda: L.check(L.lib.fcn8s_op_sgd_momentum(stream(), p(th), p(gr), p(m), n, lr, 0.9, 1.0))
     sgd_fused = lambda: L.check(L.lib.fcn8s_op_sgd_momentum_ema(stream(), p(th), p(gr), p(m), p(s), n, lr, 0.9, 1.0, None, w))
     ema = lambda: L.check(L.lib.fcn8s_op_ema_update(stream(), p(s), p(th), n, w, None))
+    B = None
+    if a.baseline_lib:
+        B = C.CDLL(os.path.abspath(a.baseline_lib))
+        for name in ("fcn8s_op_tf_adam", "fcn8s_op_sgd_momentum", "fcn8s_op_tf_adam_ema", "fcn8s_op_sgd_momentum_ema"):
+            getattr(B, name).restype, getattr(B, name).argtypes = L.SIGNATURES[name]
+    base = {"tf_adam": (lambda: L.check(B.fcn8s_op_tf_adam(stream(), p(th), p(gr), p(m), p(v), n, 1000, lr, 0.9, 0.999, 1e-8, 1.0)),
+                        lambda: L.check(B.fcn8s_op_tf_adam_ema(stream(), p(th), p(gr), p(m), p(v), p(s), n, 1000, lr, 0.9, 0.999, 1e-8, 1.0, None, w))),
+            "sgd_momentum": (lambda: L.check(B.fcn8s_op_sgd_momentum(stream(), p(th), p(gr), p(m), n, lr, 0.9, 1.0)),
+                             lambda: L.check(B.fcn8s_op_sgd_momentum_ema(stream(), p(th), p(gr), p(m), p(s), n, lr, 0.9, 1.0, None, w)))}
+    held = True
 
     def then(f1, f2):
         def run():
@@ -105,7 +121,10 @@ def main():
         return run
 
     for name, off, fused, b_off, b_fused in (("tf_adam", adam_off, adam_fused, 28, 36), ("sgd_momentum", sgd_off, sgd_fused, 20, 28)):
-        r = alternate({"off": off, "fused": fused, "unfused": then(off, ema)}, a.reps, a.rounds)
+        cands = {"off": off, "fused": fused, "unfused": then(off, ema)}
+        if B:
+            cands.update(baseline_off=base[name][0], baseline_fused=base[name][1])
+        r = alternate(cands, a.reps, a.rounds)
         fo, uo, fu = ratio_spread(r["fused"], r["off"]), ratio_spread(r["unfused"], r["off"]), ratio_spread(r["fused"], r["unfused"])
         emit(dict(kind="update", optimizer=name, elements=n, off=stats(r["off"]), fused=stats(r["fused"]), unfused=stats(r["unfused"]),
                   fused_over_off=fo, unfused_over_off=uo, fused_over_unfused=fu,
@@ -113,6 +132,37 @@ def main():
                   fused_faster=bool(np.median(r["fused"]) < np.median(r["unfused"])),
                   fused_tbps=round(b_fused * n / float(np.median(r["fused"])) / 1e9, 3), off_tbps=round(b_off * n / float(np.median(r["off"])) / 1e9, 3),
                   rounds=a.rounds, reps=a.reps))
+        for leg in ("off", "fused") if B else ():
+            bl = r["baseline_" + leg]
+            spread = float(np.max(bl) - np.min(bl))
+            ok = bool(np.median(r[leg]) <= np.median(bl) + spread)
+            held = held and ok
+            emit(dict(kind="vs_baseline", optimizer=name, average=leg == "fused", this=stats(r[leg]), baseline=stats(bl),
+                      baseline_spread_ms=round(spread, 4), this_over_baseline=ratio_spread(r[leg], bl), no_slower=ok, rounds=a.rounds, reps=a.reps))
+    if B:      # one step of either library from identical inputs (slots and shadow that are not zero, a step that moves theta): the same bits
+        m.copy_(torch.randn(n, device="cuda", generator=g) * 0.1); v.copy_(torch.randn(n, device="cuda", generator=g) ** 2)
+        s.copy_(th * 1.0001)
+        for name in ("tf_adam", "sgd_momentum"):
+            for leg in ("off", "fused"):
+                got = []
+                for lib in (L.lib, B):
+                    x = [t.clone() for t in (th, m, v, s)]
+                    if name == "tf_adam" and leg == "off":
+                        rc = lib.fcn8s_op_tf_adam(stream(), p(x[0]), p(gr), p(x[1]), p(x[2]), n, 3, 1e-3, 0.9, 0.999, 1e-8, 0.37)
+                    elif name == "tf_adam":
+                        rc = lib.fcn8s_op_tf_adam_ema(stream(), p(x[0]), p(gr), p(x[1]), p(x[2]), p(x[3]), n, 3, 1e-3, 0.9, 0.999, 1e-8, 0.37, None, w)
+                    elif leg == "off":
+                        rc = lib.fcn8s_op_sgd_momentum(stream(), p(x[0]), p(gr), p(x[1]), n, 1e-2, 0.9, 0.37)
+                    else:
+                        rc = lib.fcn8s_op_sgd_momentum_ema(stream(), p(x[0]), p(gr), p(x[1]), p(x[3]), n, 1e-2, 0.9, 0.37, None, w)
+                    L.check(rc)
+                    torch.cuda.synchronize()
+                    got.append(x)
+                eq = {k: bool(torch.equal(got[0][i].view(torch.int32), got[1][i].view(torch.int32))) for i, k in enumerate(("theta", "m", "v", "s"))}
+                moved = not torch.equal(got[0][0], th)
+                held = held and all(eq.values()) and moved
+                emit(dict(kind="bits_vs_baseline", optimizer=name, average=leg == "fused", elements=n, equal=eq, theta_moved=moved))
+                del got, x
     r = alternate({"swap": lambda: L.check(L.lib.fcn8s_op_swap(stream(), p(th), p(s), n)),
                    "ema_update": ema}, a.reps - a.reps % 2 or 2, a.rounds)          # (an even number of swaps: theta is back where it was)
     emit(dict(kind="kernel", name="swap", elements=n, bytes=16 * n, swap=stats(r["swap"]), tbps=round(16 * n / float(np.median(r["swap"])) / 1e9, 3),
@@ -149,6 +199,8 @@ def main():
         with open(a.out, "w") as f:
             for row in rows:
                 f.write(json.dumps(row) + "\n")
+    if not held:
+        raise SystemExit("ema_bench.py: a comparison with --baseline-lib does not hold (rows vs_baseline / bits_vs_baseline)")
 
 
 if __name__ == "__main__":
