@@ -92,6 +92,8 @@ SIGNATURES = {
     "fcn8s_set_loss": (_i, [_p, _p, _i, _f, _i64]),
     "fcn8s_get_loss_stats": (_i, [_p, _i64p, _i64p, _fp]),
     "fcn8s_set_lovasz": (_i, [_p, _f, _f, _i, _i, _p, _i]),
+    "fcn8s_set_boundary_loss": (_i, [_p, _i, _p]),
+    "fcn8s_get_boundary_codes": (_i, [_p, _p, _i64]),
     "fcn8s_get_loss_terms": (_i, [_p, _fp, _fp, _fp]),
     "fcn8s_eval_step": (_i, [_p, _p, _i, _p, _i, _i, _i, _f, _i]),
     "fcn8s_metrics_reset": (_i, [_p]),

@@ -197,6 +197,11 @@ struct fcn8s_model {
     // fcn8s_set_loss); loss_ws = LOSS_SCRATCH_BYTES of state and histograms + (OHEM) the l_p buffer, grown on first use (a "workspace_allocation")
     int loss_mode = 0, last_loss_mode = 0; float ohem_thresh = 0.f; int64_t ohem_min_kept = 0;
     DeviceBuf<float> d_cw; DeviceBuf<char> loss_ws;
+    // fcn8s_set_boundary_loss: bnd_R = the radius (0 = off); the 256 weights per distance code in d_btab (made by fcn8s_set_boundary_loss); d_bcodes =
+    // the [N, H, W] codes of the training loss's labels, written in front of every such loss (grown on first use, a "workspace_allocation");
+    // bnd_last: the pixels of the codes the last training loss wrote, 0 = it ran without the weighting (fcn8s_get_boundary_codes).  With loss_mode == 0 the loss runs the weighted mode
+    // on unit class weights: whoever of fcn8s_set_loss / fcn8s_set_boundary_loss leaves that state writes the ones into d_cw
+    int bnd_R = 0; long long bnd_last = 0; DeviceBuf<float> d_btab; DeviceBuf<uint8_t> d_bcodes;
     // fcn8s_set_lovasz: L = lov_ce * (the cross-entropy above) + lov_w * L_lov + L2 (lov_on: not the default (1, 0)); the class mask in d_lovmask
     // (uint8[64], made by fcn8s_set_lovasz); lov_ws = the sort's scratch (LovaszLayout), grown on first use (a "workspace_allocation");
     // d_terms = the unscaled terms of the last training loss (ce, lovasz, l2; right behind d_lastbias), have_terms once a training loss ran
@@ -1868,10 +1873,11 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
 const char* kDecoderKernels[6] = {"pool3_1x1/kernel", "pool4_1x1/kernel", "fc7_1x1/kernel", "fc7_conv2d_trans/kernel",
                                   "fc7_pool4_conv2d_trans/kernel", "fc7_pool4_pool3_conv2d_trans/kernel"};
 
-// the scratch of a configured training loss (fcn8s_set_loss): state + histograms, and for OHEM the l_p buffer of npix floats
-int ensure_loss_ws(fcn8s_model* m, long long npix)
+// the scratch of a configured training loss (fcn8s_set_loss, fcn8s_set_boundary_loss) in its effective mode: state + histograms, and for OHEM
+// the l_p buffer of npix floats
+int ensure_loss_ws(fcn8s_model* m, long long npix, int mode)
 {
-    const size_t need = LOSS_SCRATCH_BYTES + (m->loss_mode == 2 ? (size_t)npix * sizeof(float) : 0);
+    const size_t need = LOSS_SCRATCH_BYTES + (mode == 2 ? (size_t)npix * sizeof(float) : 0);
     return m->loss_ws.grow(need, m->stream, &m->ws_allocs) ? FCN8S_OK : fail(m, FCN8S_ERR_OOM, "the training loss's scratch cannot be allocated");
 }
 
@@ -1886,8 +1892,17 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
     hipStream_t s = m->stream;
     const long long npix = (long long)m->N * m->H * m->W;
     const int nb = softmax_xent_blocks(npix);
-    const int mode = with_grad ? m->loss_mode : 0;            // evaluation keeps the reference's loss
-    if (mode) { int rc = ensure_loss_ws(m, npix); if (rc) return rc; }
+    const bool bnd = with_grad && m->bnd_R > 0;               // evaluation keeps the reference's loss
+    const int mode = with_grad ? (m->loss_mode ? m->loss_mode : bnd ? 1 : 0) : 0;    // the boundary weighting alone: the weighted mode, d_cw holds ones
+    if (mode) { int rc = ensure_loss_ws(m, npix, mode); if (rc) return rc; }
+    if (bnd) {
+        // the distance codes of THIS loss's labels (those the device-side augmentation left), in front of the loss on the same stream
+        if ((long long)m->H * m->W >= (1LL << 31)) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_set_boundary_loss: an image has to have fewer than 2^31 pixels");
+        if (!m->d_btab || !m->d_cw) return fail(m, FCN8S_ERR_STATE, "fcn8s_set_boundary_loss: the table is missing");
+        if (!m->d_bcodes.grow((size_t)npix, s, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "the boundary weighting's distance codes cannot be allocated");
+        ProfScope ps(m, "boundary_distance", 0, 2.0 * (double)npix);      // the labels in, the codes out
+        launch_boundary_distance(lab_dev, m->N, m->H, m->W, m->bnd_R, m->d_bcodes, s);
+    }
     OhemState* st = mode ? (OhemState*)m->loss_ws.get() : nullptr;
     const bool lov = with_grad && m->lov_on;                    // evaluation keeps the reference's loss here too
     const bool lov_sort = lov && m->lov_w != 0.f;
@@ -1900,7 +1915,7 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
     }
     // bytes: the logits once (+ dlogits) and the labels; OHEM reads the logits and labels twice and writes + reads l_p (its refinement
     // passes, 4 bytes per pixel each when min_kept decides the threshold, are not counted)
-    const double xbytes = mode == 2 ? (double)npix * (m->C * 4 * 3 + 2 + 8) : (double)npix * (m->C * 4 * (with_grad ? 2 : 1) + 1);
+    const double xbytes = (mode == 2 ? (double)npix * (m->C * 4 * 3 + 2 + 8) : (double)npix * (m->C * 4 * (with_grad ? 2 : 1) + 1)) + (bnd ? (double)npix : 0.0);   // (+ the codes)
     { ProfScope ps(m, "softmax_xent", 0, xbytes);
       if (with_grad) hipMemsetAsync(m->d_lastbias, 0, 64 * sizeof(float), s);
       const bool blk = m->tconv_gemm && m->logits_b;
@@ -1908,12 +1923,13 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
           XentEx x; x.cw = m->d_cw; x.st = st; x.hist = (unsigned*)(m->loss_ws + sizeof(OhemState));
           x.lbuf = mode == 2 ? (float*)(m->loss_ws + LOSS_SCRATCH_BYTES) : nullptr;
           if (lov) x.ce_scale = m->lov_ce;
+          if (bnd) { x.codes = m->d_bcodes; x.ptab = m->d_btab; }
           launch_softmax_xent_ex(blk ? m->logits_b : A(m, "logits"), lab_dev, blk ? m->dlogits_b : m->dlogits, m->d_partials, npix, m->C, gscale, s,
                                  m->d_lastbias, blk ? &m->pm : nullptr, m->N, x, mode == 2 ? m->ohem_thresh : 0.f, (long long)m->ohem_min_kept);
       } else
           launch_softmax_xent(blk ? m->logits_b : A(m, "logits"), lab_dev, with_grad ? (blk ? m->dlogits_b : m->dlogits) : nullptr, m->d_partials, npix, m->C,
                               gscale, s, with_grad ? m->d_lastbias : nullptr, blk ? &m->pm : nullptr, m->N); }
-    if (with_grad) m->last_loss_mode = mode;
+    if (with_grad) { m->last_loss_mode = mode; m->bnd_last = bnd ? npix : 0; }
     const float* reg = nullptr;
     if (l2_rate != 0.f) {
         hipMemsetAsync(m->d_regsum, 0, sizeof(float), s);
@@ -3079,7 +3095,7 @@ int fcn8s_set_loss(fcn8s_model* m, const float* class_weights, int nweights, flo
     if (!m) return FCN8S_ERR_BAD_ARG;
     int rc = check_loss_args(m, class_weights, nweights, m->C, ohem_thresh, ohem_min_kept, "fcn8s_set_loss"); if (rc) return rc;
     const int mode = ohem_thresh > 0.f ? 2 : class_weights ? 1 : 0;
-    if (mode) {
+    if (mode || m->bnd_R) {                                  // (the boundary weighting alone runs the weighted mode: it must see ones, not the last weights)
         if (!m->d_cw.grow(64 * sizeof(float), m->stream)) return fail(m, FCN8S_ERR_OOM, "fcn8s_set_loss: out of device memory");
         std::vector<float> w(64, 0.f);
         for (int c = 0; c < m->C; ++c) w[c] = class_weights ? class_weights[c] : 1.f;
@@ -3137,6 +3153,40 @@ int fcn8s_set_lovasz(fcn8s_model* m, float ce_weight, float lovasz_weight, int p
         m->lov_nmask = n;
     }
     m->lov_on = on; m->lov_ce = ce_weight; m->lov_w = on ? lovasz_weight : 0.f; m->lov_per_image = per_image; m->lov_all = classes_all;
+    return FCN8S_OK;
+}
+
+int fcn8s_set_boundary_loss(fcn8s_model* m, int radius, const float* table256)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (radius == 0 && !table256) { m->bnd_R = 0; return FCN8S_OK; }          // off: the table and the codes stay where they are, unused
+    if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_set_boundary_loss");
+    if (!table256) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_boundary_loss: a radius needs its table (radius 0 with a NULL table switches the weighting off)");
+    if (radius < 1 || radius > 15) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_boundary_loss: the radius must be in 1 .. 15 (a table needs its radius)");
+    for (int i = 0; i < 256; ++i)
+        if (!std::isfinite(table256[i]) || table256[i] < 0.f) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_boundary_loss: the table's entries must be finite and >= 0");
+    if (!m->d_btab.grow(256 * sizeof(float), m->stream) || !m->d_cw.grow(64 * sizeof(float), m->stream))
+        return fail(m, FCN8S_ERR_OOM, "fcn8s_set_boundary_loss: out of device memory");
+    HIPCHK(m, hipStreamSynchronize(m->stream));              // (a queued step may still read the old table)
+    HIPCHK(m, hipMemcpy(m->d_btab, table256, 256 * sizeof(float), hipMemcpyHostToDevice));
+    if (!m->loss_mode) {                                     // no class weights of fcn8s_set_loss's: d_cw holds ones (see fcn8s_set_loss)
+        std::vector<float> w(64, 0.f);
+        for (int c = 0; c < m->C; ++c) w[c] = 1.f;
+        HIPCHK(m, hipMemcpy(m->d_cw, w.data(), 64 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    m->bnd_R = radius;
+    return FCN8S_OK;
+}
+
+int fcn8s_get_boundary_codes(fcn8s_model* m, uint8_t* codes_out, int64_t nbytes)
+{
+    if (!m || !codes_out) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_get_boundary_codes: null argument");
+    if (!m->bnd_last || !m->d_bcodes)
+        return fail(m, FCN8S_ERR_STATE, "fcn8s_get_boundary_codes: the last training loss ran without the boundary weighting (fcn8s_set_boundary_loss)");
+    const int64_t n = (int64_t)m->bnd_last;
+    if (nbytes != n) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_get_boundary_codes: nbytes must equal N*H*W = " + std::to_string(n));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(codes_out, m->d_bcodes, (size_t)n, hipMemcpyDeviceToHost));
     return FCN8S_OK;
 }
 

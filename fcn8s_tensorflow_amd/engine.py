@@ -129,6 +129,8 @@ class Engine:
         self._bad = None
         self.loss_config = None              # set_loss: the training loss's configuration (None = the reference's mean)
         self.lovasz_config = None            # set_lovasz: the Lovász-softmax term's configuration (None = off)
+        self.boundary_config = None          # set_boundary_loss: the boundary weighting's configuration, dict(table, radius) (None = off)
+        self._loss_shape = None              # (N, H, W) of the last training loss (boundary_codes)
         self.grad_clip = None                # set_grad_clip: the global-norm clip's max_norm (None = off; inf = the non-finite guard alone)
         self.ema_config = None               # set_ema: the parameter average's configuration, dict(decay, warmup) (None = off)
         self.replica_check_every = 100      # data-parallel runs: compare global step + parameter checksum across ranks every so many steps (0 = never)
@@ -458,6 +460,25 @@ class Engine:
         self.lovasz_config = None if (lov == 0.0 and ce == 1.0) else dict(
             lovasz_weight=lov, ce_weight=ce, per_image=bool(pi), classes=classes if isinstance(classes, str) else list(classes))
 
+    def set_boundary_loss(self, table=None, radius=None):
+        """The boundary weighting of the training cross-entropy (fcn8s_set_boundary_loss; definitions in include/fcn8s_hip.h, restated in
+        loss.py): every training loss computes the distance codes of its own labels and weights pixel p by w_{y_p} * table[code(p)].
+        `table` = 256 weights per distance code (loss.boundary_table, loss.ignore_band_table, loss.resolve_boundary), `radius` in 1..15.
+        No arguments restore the default.  Evaluation keeps the reference's loss."""
+        T, R = loss_mod.validate_boundary(table, radius)
+        if T is None:
+            L.check(L.lib.fcn8s_set_boundary_loss(self.h, 0, None), self.h)
+        else:
+            arr = (C.c_float * 256)(*T.tolist())
+            L.check(L.lib.fcn8s_set_boundary_loss(self.h, R, arr), self.h)
+        self.boundary_config = None if T is None else dict(table=T.copy(), radius=R)
+
+    def boundary_codes(self):
+        """The uint8 [N, H, W] distance codes the last training loss computed from its labels (fcn8s_get_boundary_codes; synchronises)."""
+        out = np.empty(self._loss_shape or (1, 1, 1), np.uint8)      # (before any training loss the library answers with its state error)
+        L.check(L.lib.fcn8s_get_boundary_codes(self.h, out.ctypes.data_as(C.c_void_p), int(out.size)), self.h)
+        return out
+
     def loss_terms(self):
         """The unscaled terms of the last training loss: dict(ce, lovasz, l2) (fcn8s_get_loss_terms; synchronises)."""
         ce = C.c_float(); lv = C.c_float(); l2 = C.c_float()
@@ -556,6 +577,7 @@ class Engine:
         self._sync_stream()
         ka, pi, dt, pl, where, nhw = self._inputs(images, labels)
         N, H, W = (int(x) for x in nhw)
+        self._loss_shape = (N, H, W)
         L.check(L.lib.fcn8s_forward_loss(self.h, pi, dt, pl, N, H, W, float(keep_prob), float(l2_rate), where), self.h)
         self._release(ka)
         for b in range(self.num_buckets):
@@ -582,6 +604,7 @@ class Engine:
         pending = self.pending_micro_batches
         if ws == 1 and optimizer == L.OPT_TF_ADAM and not always and not self.native_comm and not pending and self.grad_clip is None:
             step = C.c_int64(0)
+            self._loss_shape = (N, H, W)
             L.check(L.lib.fcn8s_train_step(self.h, pi, dt, pl, N, H, W, float(learning_rate), float(keep_prob),
                                            float(l2_rate), where, None, C.byref(step)), self.h)
             self._release(ka)
@@ -592,6 +615,7 @@ class Engine:
         if trace is not None:                              # t0 in front of the forward pass: the traced times are "ms after the step's first kernel"
             t0 = self.torch.cuda.Event(enable_timing=True); t0.record()
             trace.append(("step", t0, None))
+        self._loss_shape = (N, H, W)
         L.check(L.lib.fcn8s_forward_loss(self.h, pi, dt, pl, N, H, W, float(keep_prob), float(l2_rate), where), self.h)
         self._release(ka)
         red = BucketReducer(self.flat_grads, self.buckets, self.pg, trace=trace, always=always, ready=self._bucket_ready)
@@ -676,6 +700,7 @@ class Engine:
         self._sync_stream()
         ka, pi, dt, pl, where, nhw = self._inputs(images, labels)
         N, H, W = (int(x) for x in nhw)
+        self._loss_shape = (N, H, W)
         L.check(L.lib.fcn8s_forward_loss(self.h, pi, dt, pl, N, H, W, float(keep_prob), float(l2_rate), where), self.h)
         self._release(ka)
         for b in range(self.num_buckets):

@@ -214,6 +214,10 @@ class FCN8s:
               lovasz_per_image=False,
               lovasz_classes='present',
               ce_weight=1.0,
+              boundary_weight=None,
+              boundary_sigma=None,
+              boundary_radius=None,
+              boundary_ignore_band=None,
               accumulation_steps=1,
               clip_global_norm=None,
               ema_decay=None,
@@ -229,6 +233,11 @@ class FCN8s:
         `lovasz_weight`, `lovasz_per_image`, `lovasz_classes` ('present', 'all' or a list of class ids) and `ce_weight` add the
         Lovász-softmax term for the duration of the call (Engine.set_lovasz, loss.py: ce_weight * cross-entropy + lovasz_weight * Lovász);
         the evaluations keep reporting the reference's loss, and the previous configuration is restored when train() returns or raises.
+        `boundary_weight` + `boundary_sigma` (U-Net's weight map 1 + weight * exp(-d^2 / 2 sigma^2) around the ground-truth boundaries, out to
+        `boundary_radius` pixels, default min(15, ceil(3 sigma))) and / or `boundary_ignore_band` = k (weight 0 within k pixels of a boundary)
+        weight the cross-entropy's pixels by their distance to the nearest boundary of the step's own labels for the duration of the call
+        (loss.resolve_boundary, Engine.set_boundary_loss); the evaluations keep reporting the reference's loss, and the previous
+        configuration is restored when train() returns or raises.  Data-parallel runs need nothing: each rank weights its own labels.
         `accumulation_steps` = A >= 1: an update consumes A batches from the generator (Engine.accumulate_step for the first A - 1,
         Engine.train_step for the last; optim.py), its gradient is their mean and its reported loss the mean of their losses;
         `steps_per_epoch`, the global step, the learning-rate schedule, `summaries_frequency` and the saves all count updates.
@@ -249,6 +258,8 @@ class FCN8s:
         custom_lovasz = lovasz_weight != 0 or ce_weight != 1.0
         if custom_lovasz:
             loss_mod.validate_lovasz(lovasz_weight, ce_weight, lovasz_per_image, lovasz_classes, self.engine.logical_classes)
+        boundary_table, boundary_R = loss_mod.resolve_boundary(boundary_weight, boundary_sigma, boundary_radius, boundary_ignore_band)
+        custom_boundary = boundary_table is not None
         accumulation_steps, max_norm = optim_mod.validate(accumulation_steps, clip_global_norm)
         ema_d, ema_w = optim_mod.validate_ema(ema_decay, ema_warmup)
         if eval_dataset not in ('train', 'val'):
@@ -275,6 +286,7 @@ class FCN8s:
 
         prev_loss = self.engine.loss_config
         prev_lovasz = self.engine.lovasz_config
+        prev_boundary = self.engine.boundary_config
         prev_clip = self.engine.grad_clip
         prev_ema = self.engine.ema_config
         try:
@@ -287,6 +299,8 @@ class FCN8s:
                 self.engine.set_loss(class_weights, ohem_thresh, ohem_min_kept)
             if custom_lovasz:
                 self.engine.set_lovasz(lovasz_weight, ce_weight, lovasz_per_image, lovasz_classes)
+            if custom_boundary:
+                self.engine.set_boundary_loss(boundary_table, boundary_R)
             for epoch in range(1, epochs + 1):
                 self._run_epoch(train_generator, steps_per_epoch, learning_rate_schedule, keep_prob, l2_regularization,
                                 'Epoch {}/{}'.format(epoch, epochs), training_loss_display_averaging,
@@ -323,6 +337,8 @@ class FCN8s:
                 self.engine.set_loss(**(prev_loss or {}))
             if custom_lovasz:
                 self.engine.set_lovasz(**(prev_lovasz or dict(lovasz_weight=0.0)))
+            if custom_boundary:
+                self.engine.set_boundary_loss(**(prev_boundary or {}))
             for log in (train_log, eval_log):          # the event files are complete and closed when train() returns or raises
                 if log is not None:
                     log.close()

@@ -1,7 +1,8 @@
 """Class-weighted and hard-pixel-mined (OHEM) cross-entropy for training (fcn8s_set_loss): argument validation shared with the engine,
 a float64 restatement of both modes for the tests, and class-weight recipes computed from label counts on the host.  The Lovász-softmax
 term (fcn8s_set_lovasz) has its validation and float64 restatement at the end of the file, behind the boundary-weighted cross-entropy
-(fcn8s_op_boundary_distance, fcn8s_op_softmax_xent_px): its table builders, the NumPy route of its distance codes and its validation.
+(fcn8s_set_boundary_loss; fcn8s_op_boundary_distance, fcn8s_op_softmax_xent_px): its table builders, the NumPy route of its distance codes,
+its validation and the facade's argument rule (resolve_boundary).
 
 P = pixels of the batch, V = the valid pixels (label id < C), l_p = the per-pixel loss m + log(sum exp(v - m)) - v[y_p] (>= 0),
 w_c = the class weights.
@@ -217,6 +218,34 @@ def validate_boundary(table, radius):
     if not np.isfinite(T32).all():
         raise ValueError("the boundary table's entries must be finite in float32")
     return T32, R
+
+
+def resolve_boundary(weight=None, sigma=None, radius=None, ignore_band=None):
+    """The facade's arguments (FCN8s.train(boundary_*)) -> (table, radius) for Engine.set_boundary_loss; a pure function.
+    `weight` + `sigma`: U-Net's table (boundary_table), `radius` defaulting to default_boundary_radius(sigma); `ignore_band` = k: weight 0
+    within k pixels of a boundary (ignore_band_table); both: the U-Net table with the entries d2 <= k^2 set to 0, radius max(radius, k);
+    nothing: (None, 0).  ValueError for `weight` without `sigma` or the reverse, a `radius` without them, and whatever the builders reject."""
+    if (weight is None) != (sigma is None):
+        raise ValueError("`boundary_weight` and `boundary_sigma` go together: got weight {!r}, sigma {!r}".format(weight, sigma))
+    if weight is None:
+        if radius is not None:
+            raise ValueError("`boundary_radius` needs `boundary_weight` and `boundary_sigma` (an ignore band's radius is its width)")
+        if ignore_band is None:
+            return None, 0
+        k = _boundary_radius(ignore_band)
+        return ignore_band_table(k), k
+    if radius is None:
+        if not (isinstance(sigma, (int, float, np.integer, np.floating)) and not isinstance(sigma, bool) and math.isfinite(sigma) and sigma > 0):
+            raise ValueError("the boundary sigma must be finite and > 0, got {!r}".format(sigma))
+        radius = default_boundary_radius(sigma)
+    R = _boundary_radius(radius)
+    if ignore_band is None:
+        return boundary_table(weight, sigma, R), R
+    k = _boundary_radius(ignore_band)
+    R = max(R, k)
+    T = boundary_table(weight, sigma, R)
+    T[1:k * k + 1] = 0.0
+    return T, R
 
 
 # ---- Lovász-softmax (fcn8s_set_lovasz; the definition is in include/fcn8s_hip.h) -------------------------------------------------------

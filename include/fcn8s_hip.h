@@ -228,6 +228,25 @@ int fcn8s_get_loss_stats(fcn8s_model* m, int64_t* valid, int64_t* kept, float* t
 int fcn8s_set_lovasz(fcn8s_model* m, float ce_weight, float lovasz_weight, int per_image, int classes_all, const uint8_t* class_mask, int nmask);
 int fcn8s_get_loss_terms(fcn8s_model* m, float* ce, float* lovasz, float* l2);
 
+/* ---- the training objective: boundary-weighted cross-entropy (the definition is at fcn8s_op_softmax_xent_px) ---------------------------
+ * The model rule: with the weighting on, every training loss (fcn8s_forward_loss, fcn8s_train_step, each micro-batch of an accumulated
+ * update) first computes the distance codes of ITS labels -- those the call was given, one fcn8s_op_boundary_distance launch on the model's
+ * stream, profile group "boundary_distance" -- and then runs fcn8s_set_loss's cross-entropy with w_p = fl32(w_{y_p} * table[code(p)]) in
+ * place of w_{y_p}: the denominator stays P (|K| under OHEM) and OHEM selects on the unweighted l_p.  Without a configuration of
+ * fcn8s_set_loss's the step runs the weighted mode with unit class weights, whatever order the two calls came in, and
+ * fcn8s_get_loss_stats reports |V| for it.  A table of all 1.0 changes no bit.  The setting is per model and acts on the training losses
+ * only: fcn8s_eval_step, the metrics and prediction keep the reference's loss.  It survives fcn8s_set_precision, fcn8s_set_option,
+ * fcn8s_set_loss and fcn8s_set_lovasz; under fcn8s_set_lovasz it acts on the CE term only, like the class weights.  Data parallel: each rank
+ * weights its own labels.  The codes ([N, H, W] bytes) are allocated on first use and counted in "workspace_allocations"; while the
+ * weighting is off nothing is allocated and no kernel is launched.
+ * fcn8s_set_boundary_loss: radius in 1 .. 15 and table256 = 256 host floats, each finite and >= 0; radius 0 with a NULL table switches the
+ *   weighting off.  FCN8S_ERR_BAD_ARG for anything else (a table without a radius, a radius without a table, a radius outside 1 .. 15, a
+ *   negative or non-finite entry); FCN8S_ERR_STATE for switching it on under FCN8S_PREC_FP8_INFER.  Synchronises the stream before it replaces the table.
+ * fcn8s_get_boundary_codes (tests, inspection): the [N, H, W] codes the last training loss computed, to nbytes = N*H*W host bytes
+ *   (synchronises).  FCN8S_ERR_STATE if that loss ran without the weighting, FCN8S_ERR_BAD_ARG for another nbytes.                   */
+int fcn8s_set_boundary_loss(fcn8s_model* m, int radius, const float* table256);
+int fcn8s_get_boundary_codes(fcn8s_model* m, uint8_t* codes_out, int64_t nbytes);
+
 /* ---- the update: gradient accumulation over micro-batches, a global-norm clip and a non-finite guard (not in the reference, whose step is
  * one batch, one tf.train.AdamOptimizer.minimize, fcn8s_tensorflow.py:256) ------------------------------------------------------------------
  * Accumulation.  The model owns one accumulator acc of fcn8s_param_floats() floats, cut into the gradient buffer's buckets; it is allocated at
@@ -657,8 +676,8 @@ int fcn8s_op_softmax_xent_ex(void* stream, const float* logits, const uint8_t* l
                              float* pixel_loss_dev, int64_t* stats_dev, int64_t npix, int C);
 /* Boundary-weighted cross-entropy, the kernels (a per-pixel weight by the distance to the nearest ground-truth boundary: U-Net's weight map
  * 1 + w0 exp(-d^2 / 2 sigma^2), Ronneberger et al., MICCAI 2015, or weight 0 in a band around the contours against the label noise of polygon
- * annotations).  These two ops are all there is so far: no model call switches the weighting on, and fcn8s_train_step / fcn8s_forward_loss run
- * what they ran.  Definitions, per image of a batch [N, H, W] of uint8 label ids.  Raw ids are compared: an id >= C ("ignore") is a label like
+ * annotations).  fcn8s_set_boundary_loss switches the weighting on for a model's training losses (the model rule is stated there); these two
+ * ops are its kernels on plain data.  Definitions, per image of a batch [N, H, W] of uint8 label ids.  Raw ids are compared: an id >= C ("ignore") is a label like
  * any other and a border towards it is a boundary (the rule of fcn8s_op_boundary_pair's trimap rings).  Pixels outside the image do not exist;
  * images do not see each other.
  *   d2(p) = min over q != p in the same image with y[q] != y[p] of |q - p|^2 (squared Euclidean pixel distance, an integer).

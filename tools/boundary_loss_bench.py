@@ -15,7 +15,13 @@ Loss leg, 16 x 1024x512 x 20 classes, plain layout, class weights: fcn8s_op_soft
 of the batch's labels at R = 8 and a Gaussian table, alternating single calls, device events.  The logits alone (671 MB) are more than
 2 x the cache, so every call streams them from HBM.  Both ops allocate their few KB of scratch and synchronise per call: the same overhead
 on both sides, included in both figures.
-Prints one JSON line per record and writes them to --out if given."""
+Step leg, 16 x 1024x512, the full-width model in fp32: Engine.train_step on device tensors (labels = the train ids of the same maps) with
+the weighting off and on (Engine.set_boundary_loss, R = 8, the loss leg's table), the two states alternating in blocks of --step-reps
+steps in one process, every step between two device events.  Per state: the median over its steps and the spread (max - min) of its block
+medians.  The condition row records added = on - off against what the step adds, measured in this same run: the distance kernel at this
+shape and R (distance leg) plus the table's cost in the loss kernel (loss leg, with - without), plus the off state's own spread --
+added_within_kernels_plus_noise; nothing is tuned to make it true.
+Prints one JSON line per record, writes them to --out if given and appends the step leg's records to --append-step if given."""
 import argparse
 import ctypes as C
 import json
@@ -140,21 +146,93 @@ def loss_leg(reps, warmup):
     return [rec]
 
 
+def step_leg(kernel_recs, loss_rec, warmup, reps, blocks):
+    import torch
+    from fcn8s_tensorflow_amd import cityscapes_eval as ce
+    from fcn8s_tensorflow_amd import loss as LM
+    from fcn8s_tensorflow_amd.engine import Engine
+    name, n, h, w = SHAPES[0]
+    NC, R = 20, 8
+    gt, _, _ = make_maps(n, h, w, "cityscapes_like", seed=5)
+    lut = np.full(256, 255, np.uint8)
+    lut[ce.TRAINIDS_TO_IDS_ARRAY] = np.arange(len(ce.TRAINIDS_TO_IDS_ARRAY), dtype=np.uint8)
+    lab = torch.from_numpy(lut[gt].reshape(n, h, w)).cuda()
+    g = torch.Generator(device="cuda").manual_seed(0)
+    img = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device="cuda", generator=g)
+    table = LM.boundary_table(10.0, 5.0, R)
+    e = Engine(NC, device_id=0, seed=0)
+    states = (("off", lambda: e.set_boundary_loss()), ("on", lambda: e.set_boundary_loss(table, R)))
+
+    def run(k):
+        """k steps queued back to back, each between two device events of its own -> ms per step"""
+        ev = []
+        for _ in range(k):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); e.train_step(img, lab, 1e-6, keep_prob=0.5, fetch_loss=False); b.record()
+            ev.append((a, b))
+        torch.cuda.synchronize()
+        return [a.elapsed_time(b) for a, b in ev]
+
+    for _, switch in states:                                           # both states' buffers exist before anything is timed
+        switch()
+        run(max(2, warmup))
+    allocs = e.get_option("workspace_allocations")
+    steps = {"off": [], "on": []}
+    meds = {"off": [], "on": []}
+    for _ in range(blocks):                                            # alternating blocks: both states see the same clocks and neighbours
+        for st, switch in states:
+            switch()
+            t = run(reps + 1)[1:]                                      # (the first step behind a switch is not counted)
+            steps[st] += t; meds[st].append(float(np.median(t)))
+    assert e.get_option("workspace_allocations") == allocs
+    np.testing.assert_array_equal(e.boundary_codes()[0], LM.boundary_codes_numpy(lab[0].cpu().numpy(), R))   # the timed path is the checked one
+    e.close()
+    out = []
+    stat = {}
+    for st in ("off", "on"):
+        stat[st] = (float(np.median(steps[st])), max(meds[st]) - min(meds[st]))
+        out.append(dict(leg="step", state=st, shape=name, precision="fp32", R=R if st == "on" else 0, table="1 + 10 exp(-d2 / 50)" if st == "on" else None,
+                        steps_per_block=reps, blocks=blocks, step_ms=round(stat[st][0], 4), block_median_ms_min=round(min(meds[st]), 4),
+                        block_median_ms_max=round(max(meds[st]), 4), block_median_spread_ms=round(stat[st][1], 4)))
+    d_us = next(r["distance_us"] for r in kernel_recs if r["shape"] == name and r["R"] == R)
+    table_us = loss_rec["weighted_with_table_us"] - loss_rec["weighted_us"]
+    added = stat["on"][0] - stat["off"][0]
+    bound = (d_us + table_us) * 1e-3 + stat["off"][1]
+    out.append(dict(leg="step_condition", shape=name, R=R, added_ms=round(added, 4), added_fraction_of_step=round(added / stat["off"][0], 5),
+                    t_distance_ms=round(d_us * 1e-3, 4), t_px_minus_ex_ms=round(table_us * 1e-3, 4), spread_off_ms=round(stat["off"][1], 4),
+                    bound_ms=round(bound, 4), added_within_kernels_plus_noise=bool(added <= bound)))
+    for r in out:
+        print(json.dumps(r), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20, help="launches per block")
     ap.add_argument("--blocks", type=int, default=20, help="alternating blocks")
+    ap.add_argument("--step-reps", type=int, default=8, help="timed training steps per block of the step leg")
+    ap.add_argument("--step-blocks", type=int, default=10, help="alternating blocks per state of the step leg")
     ap.add_argument("--out")
+    ap.add_argument("--append-step", help="append the step leg's records to this file")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("boundary_loss_bench.py measures on an MI355X; no GPU here")
-    recs = kernel_leg(a.warmup, a.reps, a.blocks) + loss_leg(max(20, a.reps), a.warmup)
+    kernels = kernel_leg(a.warmup, a.reps, a.blocks)
+    loss = loss_leg(max(20, a.reps), a.warmup)
+    torch.cuda.empty_cache()
+    steps = step_leg(kernels, loss[0], a.warmup, a.step_reps, a.step_blocks)
+    recs = kernels + loss + steps
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             for r in recs:
+                f.write(json.dumps(r) + "\n")
+    if a.append_step:
+        os.makedirs(os.path.dirname(os.path.abspath(a.append_step)), exist_ok=True)
+        with open(a.append_step, "a") as f:
+            for r in steps:
                 f.write(json.dumps(r) + "\n")
 
 
