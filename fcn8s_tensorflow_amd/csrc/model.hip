@@ -8,6 +8,7 @@
 #include "fcn8s_internal.h"
 #include "device_buffer.h"
 #include "pass_state.h"
+#include "conv_route.h"
 #include <cstdarg>
 
 #include <dlfcn.h>
@@ -63,6 +64,34 @@ struct ProfGroup {
 struct Act { float* p = nullptr; size_t n = 0; int H = 0, W = 0, C = 0; };
 
 const int kConvsPerBlock[5] = {2, 2, 3, 3, 3};
+
+// One weighted layer of the encoder -- conv1_1 .. conv5_3, fc6, fc7, in forward order -- as the current plan sees it (fcn8s_model::layers): filled
+// by plan_workspace, its arena views resolved by carve_workspace.  forward(), backward_blocks() and the read-back entry points walk these entries;
+// only the plan spells a layer's name.  The per-pass ledger (pass_state.h) stays keyed by `name`.
+// INVARIANT: the route facts are functions of the model's widths, the planned (N, H, W) and RouteOpts (conv_route.h), and the table lives exactly as
+// long as the arena it was planned with: every option RouteOpts reads -- winograd_min_cin, winograd_tile, winograd_tile_hires,
+// winograd_hires_pixels, winograd_fc6 -- drops the arena in fcn8s_set_option, fcn8s_set_precision drops it when a direct mode takes the first and
+// the last over, wino_force_tile belongs to the bare op models alone, and no pass starts without ensure_workspace.  Options that pick a kernel per
+// launch without dropping the arena (conv1_in_transform, ...) and what only a pass knows (train, the precision branch) are never stored here: the
+// call sites AND them with the stored fact.
+struct Layer {
+    char name[8], pool_name[8], pool_in[12];     // "conv3_2" / "fc6"; the last conv of a block: "pool3" and the key of its pool's bf16 / e4m3 input copy, "pool3in"
+    int block, pos, nconv;                       // 1-based VGG block, position in it, convs in it (fc6, fc7: blocks 6, 7 of one layer each)
+    int h, w, cin, cout, K, real_cin;            // map, channels as the kernels see them (conv1_1: cin 4, real_cin 3), kernel size
+    int prev, next;                              // the entries before / behind it, -1 at the ends (in_block_prev / in_block_next: on the same map)
+    size_t w_off, b_off;                         // kernel and bias: floats from the start of the parameter buffer (the same in d_grads and d_wt)
+    int i_y, i_rb, i_wv, i_pool, i_pidx;         // the plan's items (-1: none); carve_workspace makes the views below from them
+    float *y, *wv, *pool; unsigned* rb; unsigned char* pidx;      // activation, kept V, ReLU bit record; the block's pool and argmax bytes (every conv of the block points at them)
+    // route facts (conv_route.h), each named after its rule: the ones a pass reads outside conv_fwd / conv_wgrad / conv_dgrad, which ask the rules themselves
+    // (wv != nullptr: keeps_v)
+    int tile;                                    // wino_tile_for on this map
+    RbWriter rb_writer;
+    bool out_in_next, conv1_in_next;             // (this layer and its in-block successor)
+    bool dm_from_next, pool_in_transform;
+    ConvShape shape(int N) const { return ConvShape{N, h, w, cin, cout, K}; }
+    bool first() const { return real_cin != 0; }
+    bool last_of_block() const { return pos == nconv; }
+};
 
 }  // namespace
 
@@ -176,6 +205,7 @@ struct fcn8s_model {
     int plan_N = 0;
     DeviceBuf<char> arena;
     std::map<std::string, Act> acts;
+    std::vector<Layer> layers;                                            // the encoder's weighted layers under the current plan (struct Layer)
     // option "keep_output_gradients" (tests): every weighted layer's fp32 output gradient dY, copied as the backward pass hands it to the layer's weight gradient;
     // read back through fcn8s_get_activation("dy:<layer>")
     struct KeptDy { DeviceBuf<float> p; size_t n = 0; };                  // (n = 0: this pass handed the layer's dY over in another form)
@@ -397,13 +427,7 @@ struct DgradEpi : ConvEpi {
 // 3x3 SAME conv through Winograd F(tile x tile, 3x3): filter transform, input transform, (tile+2)^2 batched GEMMs
 // on the matrix cores (2.25x / 4x fewer MFMA flops than the direct form), output transform + fused epilogue.
 // u: [P][Cin][Cout], v: [P][T][Cin], mm: [P][T][Cout] scratch, P = (tile+2)^2, T = N*(H/tile)*(W/tile).
-// Output tile of the Winograd path for a K x K SAME conv on an H x W map (0 = none).  K = 7 (fc6): 4 (sub-filter decomposition).
-// K = 3: F(6x6) [64 positions per 36 outputs, partial edge tiles] or F(4x4) [36 per 16, needs H, W % 4 == 0], whichever multiplies
-// less on this map (small maps lose more to F(6x6)'s partial tiles than they gain); F(2x2) as the fallback.
-// The adjoint data gradients read the forward filter bank of the same step as a transposed B operand (gemm_glds_nt_kernel).  That kernel
-// only exists in the LDS-DMA form: K % 16 == 0 and whole N tiles of the width launch_igemm picks (64 for N = 64, else 128).  Other widths
-// (e.g. 192) get a second, transposed bank instead (3x3 layers) or the forward-type data gradient (fc6).
-static bool bt_gemm_ok(int K, int N) { return K % 16 == 0 && (N == 64 || N % 128 == 0); }
+// Which layer takes it, with which tile and which fusions: conv_route.h.
 // Arithmetic of the op-level entry points, which have no model: the context of the CALLING THREAD (fcn8s_set_option(NULL, "op_split_pieces", n)
 // from that thread), copied into the bare model each such call builds -- never read by a real model, never shared between threads.
 thread_local int t_op_split = 0;
@@ -431,25 +455,17 @@ static inline long long g16_off(long long G, int C) { return A_PLANES ? G * 32 :
 unsigned short* g16_for(fcn8s_model* m, fcn8s_model::G16Map& bufs, const char* layer, int N, int H, int W, int C, int K, hipStream_t s);
 unsigned short* dyb_for(fcn8s_model* m, const char* layer, const float* dy, int N, int H, int W, int C, int K, hipStream_t s, float* db = nullptr, bool* db_done = nullptr);
 
-int wino_tile_for(const fcn8s_model* m, int H, int W, int K = 3)
+// The one place an fcn8s_model becomes the options of conv_route.h (a null model -- the op entry points without a context -- has no Winograd route).
+// The bare models of the fcn8s_op_* entry points come through here like any other.
+RouteOpts route_opts(const fcn8s_model* m)
 {
-    if (!m || H % 2 || W % 2) return 0;
-    if (m->wino_force_tile && K == 3) return (m->wino_force_tile == 6 || (H % m->wino_force_tile == 0 && W % m->wino_force_tile == 0)) ? m->wino_force_tile : 0;
-    int tmax = m->wino_tile;
-    if (K == 3 && m->wino_tile_hires && m->wino_hires_pixels > 0 && (long long)H * W >= m->wino_hires_pixels && m->wino_tile_hires < tmax) tmax = m->wino_tile_hires;
-    const bool t4 = tmax >= 4 && H % 4 == 0 && W % 4 == 0;
-    if (K == 7) return (m->wino_tile >= 4 && H % 4 == 0 && W % 4 == 0) ? 4 : 0;
-    if (tmax == 6) {
-        // multiplies per channel pair = positions x GEMM rows.  For a single image the rows are rounded up to the 64-row GEMM tile: a 32x64
-        // map has 66 F(6x6) tiles -- two row tiles, the second one nearly empty -- but exactly 128 F(4x4) tiles.  Batches of two or more
-        // images are NOT treated this way: the arithmetic applied to an image must not depend on how many others share its batch (the
-        // gradient of a batch equals the mean over its halves, data-parallel shards equal the big batch).
-        auto rows = [&](long long tiles) { return m->plan_N == 1 ? (tiles + 63) / 64 * 64 : tiles; };
-        const long long c6 = 64LL * rows((long long)((H + 5) / 6) * ((W + 5) / 6)), c4 = t4 ? 36LL * rows((long long)(H / 4) * (W / 4)) : 16LL * rows((long long)(H / 2) * (W / 2));
-        if (c6 < c4) return 6;
-    }
-    return t4 ? 4 : 2;
+    RouteOpts o;
+    if (!m) { o.wino_min_cin = 0; o.wino_fc6 = 0; return o; }
+    o.wino_min_cin = m->wino_min_cin; o.wino_tile = m->wino_tile; o.wino_tile_hires = m->wino_tile_hires; o.wino_hires_pixels = m->wino_hires_pixels;
+    o.wino_force_tile = m->wino_force_tile; o.wino_fc6 = m->wino_fc6; o.plan_N = m->plan_N; o.scratch = m->d_wino_v != nullptr;
+    return o;
 }
+int wino_tile_for(const fcn8s_model* m, int H, int W, int K = 3) { return m ? wino_tile_for(route_opts(m), H, W, K) : 0; }
 long long wino_tiles(int tile, int N, int H, int W) { return (long long)N * ((H + tile - 1) / tile) * ((W + tile - 1) / tile); }
 struct WinoEpi { const float* bias = nullptr; const float* addend = nullptr; const float* mask = nullptr; float mask_scale = 1.f;
                  int relu = 0; int dropout = 0; float keep = 1.f; unsigned long long seed = 0; unsigned int stream_id = 0; float* pool = nullptr; unsigned char* pidx = nullptr;
@@ -493,7 +509,7 @@ static Fc6Scratch fc6_scratch_floats(const fcn8s_model* m, int N, int h5, int w5
 {
     Fc6Scratch r;
     const int hi = std::max(ci, co);
-    if (m->wino_fc6 && m->fc6k == 7 && wino_tile_for(m, h5, w5, 7) == 4 && ci % 16 == 0 && co % 64 == 0) {
+    if (m->fc6k == 7 && wino_shape_tile(route_opts(m), ConvShape{N, h5, w5, ci, co, 7}) == 4) {
         const size_t P = (size_t)wino_alpha(4, 7) * wino_alpha(4, 7);
         const int ns2 = wino_nsub(7) * wino_nsub(7);
         const long long T = wino_tiles(4, N, h5, w5);
@@ -667,9 +683,8 @@ bool conv_fwd(fcn8s_model* m, const char* group, const float* x, const float* w,
     if (m && K == 7 && layer && !real_cin && e.alpha == 1.f && !e.pool_out && !e.relu_bits_out && m->fwd_train && fft6_on(m, N, H, W, Cin, Cout) &&
         conv_fft6_fwd(m, layer, x, w, y, N, H, W, Cin, Cout, e.bias, e.relu, e.dropout, e.keep, e.stream_id, s)) return false;
     if (m) m->pass.drop_backward_handoffs();
-    const bool wino3 = m && K == 3 && m->wino_min_cin > 0 && Cin >= m->wino_min_cin && m->d_wino_v && wino_tile_for(m, H, W, 3) && !e.dropout;
-    const bool wino7 = m && K == 7 && m->wino_fc6 && m->d_wino_v && wino_tile_for(m, H, W, 7) == 4;
-    if ((wino3 || wino7) && Cin % 16 == 0 && Cout % 64 == 0 && e.alpha == 1.f && !real_cin) {
+    const int tile = fwd_tile(route_opts(m), ConvShape{N, H, W, Cin, Cout, K});
+    if (tile && !(K == 3 && e.dropout) && e.alpha == 1.f && !real_cin) {
         const bool v_ready = m->pass.fwd_v.take(layer);      // written by the previous conv's fused output transform
         m->pass.fwd_v.drop();                                // (another layer's V: a promise nobody collects any more)
         float* vbuf = m->d_wino_v;
@@ -681,7 +696,7 @@ bool conv_fwd(fcn8s_model* m, const char* group, const float* x, const float* w,
         if (e.in_relu_bits_out && e.in_layer && K == 3) { we.in_rbits_out = e.in_relu_bits_out; m->pass.rbits_ok.insert(e.in_layer); }
         bool fused_out = false;
         if (e.next_v && e.next_layer) { we.next_v = e.next_v; we.fused_out = &fused_out; }
-        conv_winograd(m, wino_tile_for(m, H, W, K), K, true, x, w, y, m->d_wino_u, vbuf, m->d_wino_m, N, H, W, Cin, Cout, we, s, layer, v_ready);
+        conv_winograd(m, tile, K, true, x, w, y, m->d_wino_u, vbuf, m->d_wino_m, N, H, W, Cin, Cout, we, s, layer, v_ready);
         if (fused_out) { m->pass.fwd_v.give(e.next_layer); if (layer) m->pass.y_unwritten.insert(layer); }
         return e.pool_out != nullptr;
     }
@@ -753,9 +768,9 @@ void conv_dgrad(fcn8s_model* m, const char* group, const float* x, const float* 
             return;
         }
     }
-    const bool wino3 = m && K == 3 && m->wino_min_cin > 0 && Cin >= m->wino_min_cin && m->d_wino_v && wino_tile_for(m, H, W, 3);
-    const bool wino7 = m && K == 7 && m->wino_fc6 && m->d_wino_v && wino_tile_for(m, H, W, 7) == 4;
-    if (wino3 && dm_ready && e.w_fwd && wino_tile_for(m, H, W, 3) == 6 && Cin % 64 == 0 && Cout % 64 == 0 && e.alpha == 1.f) {
+    const RouteOpts ro = route_opts(m);
+    const ConvShape fwd{N, H, W, Cout, Cin, K};          // the forward conv this is the gradient of: dX's channels -> dY's
+    if (adjoint_dgrad(ro, fwd) && dm_ready && e.w_fwd && e.alpha == 1.f) {
         // Data gradient as the adjoint of the forward Winograd algorithm: dV[xi] = dM[xi] U[xi]^T with the dM = A dY A^T the weight
         // gradient just built (d_wino_m) and the FORWARD filter bank, then dx = overlap-added B dV B^T.  (w_fwd is [3,3,Cout,Cin].)
         const int P = 64;
@@ -780,7 +795,7 @@ void conv_dgrad(fcn8s_model* m, const char* group, const float* x, const float* 
           launch_wino_dgrad_output(m->d_wino_v, e.addend, e.mask, e.mask_scale, e.relu_bits_in, y, N, H, W, Cout, s); }
         return;
     }
-    if (wino7 && dm_ready && e.alpha == 1.f && !e.mask && !e.addend && bt_gemm_ok(Cin, 4 * Cout)) {
+    if (K == 7 && fc6_wino_map(ro, H, W) && dm_ready && e.alpha == 1.f && !e.mask && !e.addend && bt_gemm_ok(Cin, 4 * Cout)) {
         auto kept = m->u_train.find(std::string(layer) + "#4");
         if (kept != m->u_train.end() && kept->second) {
             // fc6 data gradient as the adjoint of the forward sub-filter Winograd algorithm (here Cin = channels of dz = 4096, Cout = channels
@@ -798,10 +813,10 @@ void conv_dgrad(fcn8s_model* m, const char* group, const float* x, const float* 
     if (e.lazy_wt && e.w_fwd) {
         ProfScope ps(m, "weight_relayout", 0, 8.0 * K * K * Cin * Cout); launch_flip_transpose(e.w_fwd, const_cast<float*>(w), K * K, Cout, Cin, s);
     }
-    if ((wino3 || wino7) && Cin % 16 == 0 && Cout % 64 == 0 && e.alpha == 1.f) {
+    if (dgrad_tile(ro, fwd) && e.alpha == 1.f) {
         // the forward algorithm on the flipped + transposed weights; v_ready: V = B^T dY B came with the weight gradient's dM (launch_wino_input_dout)
         WinoEpi we; we.addend = e.addend; we.mask = e.mask; we.mask_scale = e.mask_scale; we.seed = m->seed; we.rbits_in = e.relu_bits_in;
-        conv_winograd(m, wino_tile_for(m, H, W, K), K, false, x, w, y, m->d_wino_u, m->d_wino_v, m->d_wino_m, N, H, W, Cin, Cout, we, s, layer, v_ready);
+        conv_winograd(m, dgrad_tile(ro, fwd), K, false, x, w, y, m->d_wino_u, m->d_wino_v, m->d_wino_m, N, H, W, Cin, Cout, we, s, layer, v_ready);
         return;
     }
     IgemmArgs a{}; a.addend = e.addend; a.mask = e.mask; a.alpha = e.alpha; a.mask_scale = e.mask_scale; a.keep_prob = 1.f;
@@ -842,8 +857,13 @@ void tconv_dgrad(fcn8s_model* m, const float* dy, const float* w, float* dx, int
 
 void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* dz, float* dw, float* db,
                 int N, int H, int W, int Cin, int Cout, int K, float alpha, hipStream_t s, int real_cin = 0,
-                const char* layer = nullptr, bool fuse_dgrad_input = false, const unsigned char* pool_idx = nullptr)
+                const char* layer = nullptr, const unsigned char* pool_idx = nullptr)
 {
+    // The data gradient of this layer follows.  fuse_dgrad_input: it runs through Winograd and its input transform V = B^T dz B can be written
+    // into d_wino_v by the same kernel that writes dM (one read of dz); adj_bytes: it is the adjoint one, which consumes dM itself
+    const RouteOpts ro = route_opts(m);
+    const ConvShape shape{N, H, W, Cin, Cout, K};
+    const bool fuse_dgrad_input = dgrad_input_fused(ro, shape), adj_bytes = adjoint_dgrad(ro, shape);
     // the data gradient of the layer after this one may have written this layer's dM instead of dz (backward_blocks): dz then holds nothing
     const bool promised = m && m->pass.dm_prefilled.take(layer);
     if (m) m->pass.dm_prefilled.drop();      // (a promise to another layer: d_wino_m is about to be rewritten)
@@ -914,10 +934,7 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
             g.Ha = 1; g.Wa = (int)T; g.Adim = Kg; g.lda = Kg; g.Areal = Kg;
             g.Bdim = Cout; g.ldb = Cout; g.KW = 1; g.a_scale = 1; g.tap_off = 0; g.ntaps = NP; g.ldc = Cout; g.alpha = 1.f; g.colsum = nullptr;
             g.batched = 1; g.a_batch_stride = wino_slab(T, Kg); g.b_batch_stride = wino_slab(T, Cout); g.c_uninitialized = 1;
-            // fuse_dgrad_input: the data gradient of this layer follows and runs through Winograd too -- its input
-            // transform V = B^T dz B is written into d_wino_v by the same kernel that writes dM (one read of dz)
             bool fused = false, dm_ready = false;
-            const bool adj_bytes = fuse_dgrad_input && tile == 6 && K == 3 && Cin % 64 == 0 && Cout % 64 == 0;
             const bool prefilled = promised && adj_bytes && !pool_idx;      // dM already in d_wino_m (wino_dgrad_output_dout_kernel)
             if (promised && !prefilled) broken_promise();
             if (prefilled) dm_ready = true;
@@ -927,7 +944,7 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
                   // adjoint data gradient (tile 6): it consumes dM itself, no second transform of dz
                   if (adj_bytes) { launch_wino_dout(6, dz, m->d_wino_m, N, H, W, Cout, s, 3, pool_idx); dm_ready = true; }
                   else {
-                      if (fuse_dgrad_input && tile >= 4 && K == 3) fused = launch_wino_input_dout(tile, dz, m->d_wino_v, m->d_wino_m, N, H, W, Cout, s, pool_idx);
+                      if (fuse_dgrad_input) fused = launch_wino_input_dout(tile, dz, m->d_wino_v, m->d_wino_m, N, H, W, Cout, s, pool_idx);
                       if (!fused) launch_wino_dout(tile, dz, m->d_wino_m, N, H, W, Cout, s, K);
                   } }
                 // fc6: the non-fused transform above left dM = A dz A^T in d_wino_m; its adjoint data gradient (conv_dgrad) consumes it
@@ -981,7 +998,7 @@ void tconv_wgrad(fcn8s_model* m, const float* x, const float* dy, float* dw, int
 // ---- workspace --------------------------------------------------------------------
 // The arena's layout for one (N, H, W): named items at 256-byte aligned offsets, then the staged images / labels, predictions and loss partials.
 struct WsItem { std::string name; size_t n; int h, w, c; float** extra; };
-struct WsPlan { std::vector<WsItem> items; std::vector<size_t> offs; size_t o_img = 0, o_lab = 0, o_pred = 0, o_part = 0, bytes = 0; };
+struct WsPlan { std::vector<WsItem> items; std::vector<Layer> layers; std::vector<size_t> offs; size_t o_img = 0, o_lab = 0, o_pred = 0, o_part = 0, bytes = 0; };
 int check_shape(fcn8s_model* m, int N, int H, int W)
 {
     if (N <= 0) return fail(m, FCN8S_ERR_SHAPE, "batch size must be positive");
@@ -989,7 +1006,32 @@ int check_shape(fcn8s_model* m, int N, int H, int W)
         return fail(m, FCN8S_ERR_SHAPE, "image height and width must be positive multiples of 32 (five 2x2 pools, then x2, x2, x8 upsampling must line up with the skip connections)");
     return FCN8S_OK;
 }
-// (sets m->plan_N = N: the batch size the per-layer Winograd tiles are chosen for, wino_tile_for, from here until the next re-plan)
+// The table's names, shapes and parameter offsets for an H x W image: the one place that spells a layer's name.
+static void fill_layer_table(const fcn8s_model* m, int H, int W, std::vector<Layer>& layers)
+{
+    layers.assign(15, Layer{});
+    int k = 0, cin = 4;
+    for (int b = 0; b < 7; ++b) {
+        const int nconv = b < 5 ? kConvsPerBlock[b] : 1, shift = std::min(b, 5);
+        for (int i = 1; i <= nconv; ++i, ++k) {
+            Layer& L = layers[k];
+            if (b < 5) snprintf(L.name, sizeof L.name, "conv%d_%d", b + 1, i); else snprintf(L.name, sizeof L.name, "fc%d", b + 1);
+            if (b < 5) { snprintf(L.pool_name, sizeof L.pool_name, "pool%d", b + 1); snprintf(L.pool_in, sizeof L.pool_in, "pool%din", b + 1); }
+            L.block = b + 1; L.pos = i; L.nconv = nconv;
+            L.h = H >> shift; L.w = W >> shift; L.cin = cin; L.cout = m->widths[b]; L.K = b < 5 ? 3 : (b == 5 ? m->fc6k : 1); L.real_cin = k == 0 ? 3 : 0;
+            L.prev = k - 1; L.next = k + 1 < 15 ? k + 1 : -1;
+            L.w_off = P(m, std::string(L.name) + (b < 5 ? "/filter" : "/weights")).offset; L.b_off = P(m, std::string(L.name) + "/biases").offset;
+            L.i_y = L.i_rb = L.i_wv = L.i_pool = L.i_pidx = -1;
+            cin = L.cout;
+        }
+    }
+}
+static Layer* in_block_next(std::vector<Layer>& v, const Layer& L) { return L.pos < L.nconv ? &v[L.next] : nullptr; }
+static Layer* in_block_prev(std::vector<Layer>& v, const Layer& L) { return L.pos > 1 ? &v[L.prev] : nullptr; }
+static Layer* find_layer(fcn8s_model* m, const char* name) { for (Layer& L : m->layers) if (!strcmp(L.name, name)) return &L; return nullptr; }
+
+// (sets m->plan_N = N: the batch size the per-layer Winograd tiles are chosen for, wino_tile_for, from here until the next re-plan.  The layer
+//  table goes into the plan, pl.layers; carve_workspace makes it the model's)
 void plan_workspace(fcn8s_model* m, int N, int H, int W, WsPlan& pl)
 {
     m->plan_N = N;
@@ -999,96 +1041,79 @@ void plan_workspace(fcn8s_model* m, int N, int H, int W, WsPlan& pl)
     items.clear(); pl.offs.clear();
     auto add = [&](const std::string& nm, int h, int w, int c, float** extra = nullptr) {
         items.push_back({nm, (size_t)N * h * w * c, h, w, c, extra});
+        return (int)items.size() - 1;
     };
+    auto add_raw = [&](const std::string& nm, size_t n, float** extra = nullptr) { items.push_back({nm, n, 0, 0, 0, extra}); return (int)items.size() - 1; };
+    // The plan is what makes the shared scratch, so its rules run with scratch = true: every fact that asks for the scratch implies a layer that
+    // scratch_channels() sizes it for (tests/test_conv_route_host.py: "fits the scratch").
+    RouteOpts ro = route_opts(m); ro.scratch = true;
+    auto slab_floats = [&](int hh, int ww, int c, int K) -> size_t {      // P slabs of wino_slab(T, nsub^2 c) floats
+        const int tile = wino_tile_for(ro, hh, ww, K);
+        if (!tile) return 0;
+        const int al = wino_alpha(tile, K), ns = wino_nsub(K);
+        return (size_t)al * al * (size_t)wino_slab(wino_tiles(tile, N, hh, ww), ns * ns * c);
+    };
+    // one walk over the layers: each layer's route facts, and the sizes that follow from them
+    fill_layer_table(m, H, W, pl.layers);
+    size_t vmax = 0, gmax = 0;         // Winograd scratch: the largest [P][T][C] tensor any layer needs (V and M of the forward and of the data-gradient conv); the largest gradient tensor
+    std::vector<size_t> n_rb(pl.layers.size(), 0), n_wv(pl.layers.size(), 0);
+    for (size_t k = 0; k < pl.layers.size(); ++k) {
+        Layer& L = pl.layers[k];
+        gmax = std::max(gmax, (size_t)N * L.h * L.w * L.cout);
+        if (L.block > 5) continue;          // (fc6's routes are conv_fwd's / conv_wgrad's own; its scratch: fc6_scratch_floats below)
+        const ConvShape sh = L.shape(N);
+        const Layer* nx = in_block_next(pl.layers, L);
+        L.tile = wino_tile_for(ro, L.h, L.w, 3);
+        L.rb_writer = nx ? relu_record_writer(ro, sh, nx->shape(N), L.first()) : RbWriter::none;      // (only a conv that feeds another conv has a record)
+        L.out_in_next = nx && out_in_fused(ro, sh, nx->shape(N));
+        L.conv1_in_next = L.first() && nx && nx->last_of_block() && conv1_in_next_transform(ro, sh, nx->shape(N));
+        L.dm_from_next = nx && dm_from_next(ro, sh);
+        L.pool_in_transform = L.last_of_block() && pool_in_transform(ro, sh, in_block_prev(pl.layers, L) != nullptr);
+        if (L.rb_writer != RbWriter::none) n_rb[k] = wino_rbits_words(L.tile, N, L.h, L.w, L.cout);
+        if (keeps_v(ro, sh)) n_wv[k] = slab_floats(L.h, L.w, L.cin, 3);          // the forward pass keeps each Winograd layer's transformed input for the weight gradient
+        if (const int c = scratch_channels(ro, sh)) vmax = std::max(vmax, slab_floats(L.h, L.w, c, 3));
+    }
+    // the arena's items, in its order
     add("x0", H, W, 4);
-    int h = H, w = W;
-    for (int b = 0; b < 5; ++b) {
-        for (int i = 1; i <= kConvsPerBlock[b]; ++i) {
-            char nm[32]; snprintf(nm, sizeof nm, "conv%d_%d", b + 1, i);
-            add(nm, h, w, m->widths[b]);
-        }
-        h /= 2; w /= 2;
-        char nm[32]; snprintf(nm, sizeof nm, "pool%d", b + 1);
-        add(nm, h, w, m->widths[b]);
+    for (Layer& L : pl.layers) {
+        if (L.block > 5) break;
+        L.i_y = add(L.name, L.h, L.w, L.cout);
+        if (L.last_of_block()) { const int ip = add(L.pool_name, L.h / 2, L.w / 2, L.cout); for (int k = 0; k < L.nconv; ++k) (&L - k)->i_pool = ip; }
     }
     const int h5 = H / 32, w5 = W / 32, h4 = H / 16, w4 = W / 16, h3 = H / 8, w3 = W / 8;
-    {   // ReLU bit masks of the convs whose output is another conv's input (read back by that conv's data gradient)
-        int cin = 3;
-        for (int b = 0, hh = H, ww = W; b < 5; ++b, hh /= 2, ww /= 2)
-            for (int i = 1; i <= kConvsPerBlock[b]; ++i) {
-                const int tile = wino_tile_for(m, hh, ww, 3);
-                // (conv1_1 is not a Winograd layer: its record is written by conv1_2's input transform, if that is one)
-                const bool by_consumer = b == 0 && i == 1 && kConvsPerBlock[0] > 1 && m->wino_min_cin > 0 && m->widths[0] >= m->wino_min_cin && m->widths[0] % 64 == 0 && tile;
-                if (by_consumer || (i < kConvsPerBlock[b] && m->wino_min_cin > 0 && cin >= m->wino_min_cin && cin % 16 == 0 && m->widths[b] % 64 == 0 && tile)) {
-                    char nm[40]; snprintf(nm, sizeof nm, "rb:conv%d_%d", b + 1, i);
-                    items.push_back({nm, wino_rbits_words(tile, N, hh, ww, m->widths[b]), 0, 0, 0, nullptr});
-                }
-                cin = m->widths[b];
-            }
-    }
-    for (int b = 0; b < 5; ++b) {      // argmax bytes of pool_b (one per pooled element), see launch_wino_output
-        char nm[16]; snprintf(nm, sizeof nm, "pidx%d", b + 1);
-        items.push_back({nm, ((size_t)N * (H >> (b + 1)) * (W >> (b + 1)) * (size_t)m->widths[b] + 3) / 4, 0, 0, 0, nullptr});
-    }
-    add("fc6", h5, w5, m->widths[5]);
-    add("fc7", h5, w5, m->widths[6]);
+    // ReLU bit masks of the convs whose output is another conv's input (read back by that conv's data gradient)
+    for (size_t k = 0; k < pl.layers.size(); ++k) if (n_rb[k]) pl.layers[k].i_rb = add_raw(std::string("rb:") + pl.layers[k].name, n_rb[k]);
+    for (Layer& L : pl.layers)      // argmax bytes of pool_b (one per pooled element), see launch_wino_output
+        if (L.block <= 5 && L.last_of_block()) {
+            const int ip = add_raw("pidx" + std::to_string(L.block), ((size_t)N * (L.h / 2) * (L.w / 2) * (size_t)L.cout + 3) / 4);
+            for (int k = 0; k < L.nconv; ++k) (&L - k)->i_pidx = ip;
+        }
+    for (Layer& L : pl.layers) if (L.block > 5) L.i_y = add(L.name, L.h, L.w, L.cout);      // fc6, fc7
     add("s7", h5, w5, C); add("p4", h4, w4, C); add("p3", h3, w3, C);
     add("a4", h4, w4, C); add("a3", h3, w3, C); add("logits", H, W, C);
     add("dlogits", H, W, C, &m->dlogits);
     if (m->tconv_gemm) {
         const size_t rows = (size_t)N * (H / 8 + 1) * (W / 8 + 1);
-        items.push_back({"logits_b", rows * 64 * C, 0, 0, 0, &m->logits_b});
-        items.push_back({"dlogits_b", rows * 64 * C, 0, 0, 0, &m->dlogits_b});
-        items.push_back({"tg_A", rows * m->tg_kp, 0, 0, 0, &m->tg_A});
-        items.push_back({"tg_dA", rows * m->tg_kp, 0, 0, 0, &m->tg_dA});
+        add_raw("logits_b", rows * 64 * C, &m->logits_b);
+        add_raw("dlogits_b", rows * 64 * C, &m->dlogits_b);
+        add_raw("tg_A", rows * m->tg_kp, &m->tg_A);
+        add_raw("tg_dA", rows * m->tg_kp, &m->tg_dA);
     }
     add("da3", h3, w3, C, &m->da3); add("da4", h4, w4, C, &m->da4); add("ds7", h5, w5, C, &m->ds7);
     add("gskip3", h3, w3, m->widths[2], &m->gskip3); add("gskip4", h4, w4, m->widths[3], &m->gskip4);
-    size_t gmax = (size_t)N * H * W * m->widths[0];
-    for (int b = 0, hh = H, ww = W; b < 5; ++b, hh /= 2, ww /= 2) {
-        size_t n = (size_t)N * hh * ww * m->widths[b]; if (n > gmax) gmax = n;
-    }
-    { size_t n = (size_t)N * h5 * w5 * (size_t)std::max(m->widths[5], m->widths[6]); if (n > gmax) gmax = n; }
-    items.push_back({"gbuf0", gmax, 0, 0, 0, &m->gbuf[0]});
-    items.push_back({"gbuf1", gmax, 0, 0, 0, &m->gbuf[1]});
+    add_raw("gbuf0", gmax, &m->gbuf[0]);
+    add_raw("gbuf1", gmax, &m->gbuf[1]);
     items.push_back({"softmax", (size_t)N * H * W * C, H, W, C, &m->d_softmax});
-    {   // Winograd scratch: the largest [P][T][C] tensor any layer needs (V and M of the forward and of the data-gradient conv)
-        auto slab_floats = [&](int hh, int ww, int c, int K) -> size_t {      // P slabs of wino_slab(T, nsub^2 c) floats
-            const int tile = wino_tile_for(m, hh, ww, K);
-            if (!tile) return 0;
-            const int al = wino_alpha(tile, K), ns = wino_nsub(K);
-            return (size_t)al * al * (size_t)wino_slab(wino_tiles(tile, N, hh, ww), ns * ns * c);
-        };
-        size_t vmax = 0;
-        if (m->wino_min_cin > 0) {
-            int cin = 3;
-            for (int b = 0, hh = H, ww = W; b < 5; ++b, hh /= 2, ww /= 2)
-                for (int i = 1; i <= kConvsPerBlock[b]; ++i) {
-                    const int cout = m->widths[b];
-                    if (std::max(cin, cout) >= m->wino_min_cin) vmax = std::max(vmax, slab_floats(hh, ww, std::max(cin, cout), 3));
-                    cin = cout;
-                }
-        }
-        const int h5_ = H / 32, w5_ = W / 32;
-        const Fc6Scratch f6 = fc6_scratch_floats(m, N, h5_, w5_, m->widths[4], m->widths[5]);
+    {
+        const Fc6Scratch f6 = fc6_scratch_floats(m, N, h5, w5, m->widths[4], m->widths[5]);
         vmax = std::max(vmax, f6.v_wino);      // V: P * T * nsub^2 * c5;  M: P * T * c6
         size_t mmax = vmax;
         vmax = std::max(vmax, f6.v_fft);       // fc6 through DFT tiles
         mmax = std::max(mmax, f6.m_fft);
-        if (vmax) { items.push_back({"wino_v", vmax, 0, 0, 0, &m->d_wino_v}); items.push_back({"wino_m", mmax, 0, 0, 0, &m->d_wino_m}); }
-        if (m->wino_min_cin > 0) {    // the forward pass keeps each Winograd layer's transformed input for the weight gradient
-            int cin = 3;
-            for (int b = 0, hh = H, ww = W; b < 5; ++b, hh /= 2, ww /= 2)
-                for (int i = 1; i <= kConvsPerBlock[b]; ++i) {
-                    if (cin >= m->wino_min_cin && cin % 16 == 0 && m->widths[b] % 64 == 0 && wino_tile_for(m, hh, ww, 3)) {
-                        char nm[40]; snprintf(nm, sizeof nm, "wv:conv%d_%d", b + 1, i);
-                        items.push_back({nm, slab_floats(hh, ww, cin, 3), 0, 0, 0, nullptr});
-                    }
-                    cin = m->widths[b];
-                }
-            // fc6's slot holds V of F(4x4,4x4) or, when the weight gradient runs in the DFT domain, Xf: sized for either
-            if (f6.wv) items.push_back({"wv:fc6", f6.wv, 0, 0, 0, nullptr});
-        }
+        if (vmax) { add_raw("wino_v", vmax, &m->d_wino_v); add_raw("wino_m", mmax, &m->d_wino_m); }
+        for (size_t k = 0; k < pl.layers.size(); ++k) if (n_wv[k]) pl.layers[k].i_wv = add_raw(std::string("wv:") + pl.layers[k].name, n_wv[k]);
+        // fc6's slot holds V of F(4x4,4x4) or, when the weight gradient runs in the DFT domain, Xf: sized for either
+        if (fc6_keeps_v(ro) && f6.wv) pl.layers[13].i_wv = add_raw("wv:fc6", f6.wv);
     }
 
     size_t bytes = 0;
@@ -1114,6 +1139,9 @@ void carve_workspace(fcn8s_model* m, int N, int H, int W, const WsPlan& pl)
         Act a; a.p = p; a.n = pl.items[i].n; a.H = pl.items[i].h; a.W = pl.items[i].w; a.C = pl.items[i].c;
         m->acts[pl.items[i].name] = a;
     }
+    m->layers = pl.layers;      // (the plan's own copy: fcn8s_predict_tta plans shapes it only wants the size of)
+    auto view = [&](int i) { return i < 0 ? nullptr : (float*)(m->arena + pl.offs[i]); };
+    for (Layer& L : m->layers) { L.y = view(L.i_y); L.wv = view(L.i_wv); L.pool = view(L.i_pool); L.rb = (unsigned*)view(L.i_rb); L.pidx = (unsigned char*)view(L.i_pidx); }
     m->d_images = m->arena + pl.o_img; m->d_labels = (uint8_t*)(m->arena + pl.o_lab);
     m->d_pred = (long long*)(m->arena + pl.o_pred); m->d_partials = (double*)(m->arena + pl.o_part);
     m->N = N; m->H = H; m->W = W;
@@ -1128,6 +1156,7 @@ void drop_arena(fcn8s_model* m)
     if (m->arena) hipStreamSynchronize(m->stream);
     m->arena.reset();
     m->N = m->H = m->W = 0; m->acts.clear();
+    for (Layer& L : m->layers) { L.y = L.wv = L.pool = nullptr; L.rb = nullptr; L.pidx = nullptr; }
     m->have_forward = m->have_loss = false;
 }
 // The per-layer padded copies whose geometry is the workspace's shape: xbf16 (bf16 forward modes), xg16 / dyg16 (bf16_train), q8 (fp8_infer).
@@ -1299,25 +1328,21 @@ void prepare_forward_weights(fcn8s_model* m)
 }
 
 // Whether the backward pass routes d(pool_b) through the argmax bytes inside the Winograd transform of conv_b_last (then neither dZ
-// nor the conv's full-resolution output is ever read again); b is the 1-based block number.  Same test as backward_blocks().
-bool pool_backward_fused(const fcn8s_model* m, int b, bool pooled_by_transform)
-{
-    const int h = m->H >> (b - 1), w = m->W >> (b - 1), cw = m->widths[b - 1], nconv = kConvsPerBlock[b - 1];
-    char last[32]; snprintf(last, sizeof last, "wv:conv%d_%d", b, nconv);
-    return pooled_by_transform && m->wino_min_cin > 0 && cw >= m->wino_min_cin && m->d_wino_v &&
-           wino_tile_for(m, h, w) >= 4 && cw % 64 == 0 && nconv > 1 && m->acts.count(last);
-}
+// nor the conv's full-resolution output is ever read again): the plan's fact, and a forward pass that kept the bytes.  `last`: the block's last conv.
+bool pool_backward_fused(const Layer& last, bool pooled_by_transform) { return pooled_by_transform && last.pool_in_transform; }
 
 // One SAME convolution with bf16-rounded operands and fp32 accumulation on the bf16 MFMA (gemm_bf16.hip), fp32 bias / ReLU / dropout epilogue,
 // fp32 output: fc6 / fc7 of FCN8S_PREC_BF16_FC, and conv3_1 .. conv5_3 as well in FCN8S_PREC_BF16_FWD.  Returns false if no bf16 kernel
 // takes the shape (the caller then uses the fp32 path).
-bool bf16_conv_layer(fcn8s_model* m, const char* tag, const char* wname, const char* bname, const float* in, float* out,
-                     int N, int h, int w, int cin, int cout, int k, int drop, float keep_prob, uint32_t stream_id, hipStream_t s, bool allow_small = true,
+bool bf16_conv_layer(fcn8s_model* m, const char* tag, const Layer& L, const float* in, float* out,
+                     int drop, float keep_prob, uint32_t stream_id, hipStream_t s, bool allow_small = true,
                      const unsigned short* xb_ready = nullptr,          // the padded bf16 copy of `in`, already made (256 x 256 kernel only)
                      bool any_shape = false,                            // bf16_train: 64- / 128-column tiles and a partial last row tile are taken too
                      unsigned short* yb = nullptr, int yb_pad = 0,      // ... and the consumer's padded bf16 copy of the output is written by the epilogue
                      long long xb_ps = 0, long long yb_ps = 0)          // plane strides of xb_ready / yb (bf16_train's per-layer copies: channel-chunk planes), 0 = [rows][C]
 {
+    const int N = m->N, h = L.h, w = L.w, cin = L.cin, cout = L.cout, k = L.K;
+    const float *wk = m->d_params + L.w_off, *bias = m->d_params + L.b_off;
     const int K = k * k * cin;
     const long long Mrows = (long long)N * h * w;
     const bool big = conv_bf16_256_ok(Mrows, cin, cout, any_shape ? 3 : m->bf16_gemm256);      // 256-row tiles, LDS-DMA, staggered wave groups
@@ -1329,7 +1354,7 @@ bool bf16_conv_layer(fcn8s_model* m, const char* tag, const char* wname, const c
     unsigned short* wbuf = m->d_wbf16;
     bool have = false;
     if (m->frozen) {
-        const std::string key = std::string(wname) + (big ? "#t" : "#b");
+        const std::string key = std::string(L.name) + (big ? "#t" : "#b");
         DeviceBuf<unsigned short>& c = m->wbf16_cache[key];
         if (c && !m->bank_stale.count("w:" + key)) { wbuf = c; have = true; }
         else if (c) { wbuf = c; m->bank_stale.erase("w:" + key); }                         // kept storage: refilled below
@@ -1337,7 +1362,7 @@ bool bf16_conv_layer(fcn8s_model* m, const char* tag, const char* wname, const c
     }
     if (!have) { ProfScope ps(m, "weight_relayout", 0, 6.0 * K * cout);
                  prof_derived(m, big ? "w_to_bf16_t_kernel" : "w_to_bf16_tiles_kernel");
-                 if (big) launch_w_to_bf16_t(Wp(m, wname), wbuf, K, cout, s); else launch_w_to_bf16_tiles(Wp(m, wname), wbuf, K, cout, s); }
+                 if (big) launch_w_to_bf16_t(wk, wbuf, K, cout, s); else launch_w_to_bf16_tiles(wk, wbuf, K, cout, s); }
     const int pad = big ? (k - 1) / 2 : 0;
     const size_t nin = (size_t)N * (h + 2 * pad) * (w + 2 * pad) * cin;
     if (nin % 8 == 0 && !(big && xb_ready)) m->d_abf16.grow(nin * sizeof(unsigned short), s, &m->ws_allocs);      // (out of memory: the paths below that need no copy)
@@ -1345,21 +1370,20 @@ bool bf16_conv_layer(fcn8s_model* m, const char* tag, const char* wname, const c
     if (big && (xb_ready || (m->d_abf16 && m->d_abf16.elems() >= nin))) {
         if (!xb_ready) { ProfScope ps(m, "weight_relayout", 0, 4.0 * Mrows * cin + 2.0 * nin); launch_f32_to_bf16_padded(in, m->d_abf16, N, h, w, cin, pad, s); }
         Bf16Conv256Args g{};
-        g.xp = xb_ready ? xb_ready : m->d_abf16; g.wt = wbuf; g.bias = Wp(m, bname); g.y = out;
+        g.xp = xb_ready ? xb_ready : m->d_abf16; g.wt = wbuf; g.bias = bias; g.y = out;
         g.N = N; g.H = h; g.W = w; g.Cin = cin; g.Cout = cout; g.K = k;
         g.relu = 1; g.dropout = drop; g.keep_prob = keep_prob; g.seed = m->seed; g.stream_id = stream_id; g.any_shape = any_shape ? 1 : 0; g.mask_scale = 1.f; g.yb = yb; g.yb_pad = yb_pad;
         g.xp_ps = xb_ready ? xb_ps : 0; g.yb_ps = yb_ps;
         g.rows_bn = m->bf16_rows_bn;
         g.guarded = (any_shape && xb_ready) ? 1 : 0;          // (the per-layer training copies carry guard rows; the shared inference copy does not)
-        const std::string lname = std::string(wname).substr(0, std::string(wname).find('/'));
-        ProfScope ps(m, tag, 2.0 * M * K * cout, (out ? 4.0 : 0.0) * M * cout + (yb ? 2.0 : 0.0) * M * cout + 2.0 * M * cin + 2.0 * K * cout, any_shape ? lname.c_str() : nullptr);
+        ProfScope ps(m, tag, 2.0 * M * K * cout, (out ? 4.0 : 0.0) * M * cout + (yb ? 2.0 : 0.0) * M * cout + 2.0 * M * cin + 2.0 * K * cout, any_shape ? L.name : nullptr);
         if (launch_conv_bf16_256(g, s)) return true;
     }
     if (!out) return false;
     if (!allow_small || cin % 32 || cout % 128) return false;
-    if (big) { prof_derived(m, "w_to_bf16_tiles_kernel"); launch_w_to_bf16_tiles(Wp(m, wname), m->d_wbf16, K, cout, s); wbuf = m->d_wbf16; }      // (could not take the 256 path after all)
+    if (big) { prof_derived(m, "w_to_bf16_tiles_kernel"); launch_w_to_bf16_tiles(wk, m->d_wbf16, K, cout, s); wbuf = m->d_wbf16; }      // (could not take the 256 path after all)
     Bf16ConvArgs a{};
-    a.x = in; a.wt = wbuf; a.bias = Wp(m, bname); a.y = out;
+    a.x = in; a.wt = wbuf; a.bias = bias; a.y = out;
     if (nin % 8 == 0 && m->d_abf16) {         // activations to bf16 once: the GEMM re-reads each A tile Cout/128 times
         ProfScope ps(m, "weight_relayout", 0, 6.0 * nin); launch_f32_to_bf16(in, m->d_abf16, (long long)N * h * w * cin, s); a.xh = m->d_abf16;
     }
@@ -1404,9 +1428,10 @@ unsigned short* dyb_for(fcn8s_model* m, const char* layer, const float* dy, int 
 // bf16 modes, training: the layer's Winograd input transform (run for the weight gradient anyway) can write the padded bf16 copy its direct
 // bf16 convolution reads -- if that convolution takes the 256 x 256 kernel and the transform is the F(6x6,3x3) one.  Returns the layer's copy
 // (allocated and its border zeroed on first use) or nullptr.
-unsigned short* xb_by_transform(fcn8s_model* m, const char* layer, int N, int H, int W, int Cin, int Cout, hipStream_t s)
+unsigned short* xb_by_transform(fcn8s_model* m, const Layer& L, int N, hipStream_t s)
 {
-    if (!m->bf16_copy_by_transform || Cin % 8 || !m->acts.count(std::string("wv:") + layer) || wino_tile_for(m, H, W, 3) != 6) return nullptr;
+    const int H = L.h, W = L.w, Cin = L.cin, Cout = L.cout; const char* layer = L.name;
+    if (!m->bf16_copy_by_transform || Cin % 8 || !L.wv || L.tile != 6) return nullptr;
     if (!conv_bf16_256_ok((long long)N * H * W, Cin, Cout, m->bf16_gemm256)) return nullptr;
     DeviceBuf<unsigned short>& p = m->xbf16[layer];
     // (sized once: the copies are dropped whenever the workspace is planned for another shape, drop_shape_copies)
@@ -1611,89 +1636,77 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
     const bool cp = train || (bf16_train_mode(m) && m->bf16_infer_copies);
     if (!m->x0_ready) { ProfScope ps(m, "preprocess", 0, (double)N * H * W * (16 + (dtype ? 12 : 3))); launch_preprocess(img_dev, dtype, A(m, "x0"), (long long)N * H * W, s); }
     const float* x = A(m, "x0");
-    int h = H, w = W, cin = 4;
+    size_t k = 0;
     for (int b = 0; b < 5; ++b) {
-        char pn[32]; bool pooled = false;
-        for (int i = 1; i <= kConvsPerBlock[b]; ++i) {
-            char nm[32]; snprintf(nm, sizeof nm, "conv%d_%d", b + 1, i);
-            const bool first = (b == 0 && i == 1);
-            FwdEpi e; e.bias = Wp(m, std::string(nm) + "/biases"); e.relu = 1;
-            const float* wt = first ? m->d_w1pad : Wp(m, std::string(nm) + "/filter");
-            if (train && i < kConvsPerBlock[b]) {                                                            // its output is the next conv's input
-                auto it = m->acts.find(std::string("rb:") + nm);
-                if (it != m->acts.end()) e.relu_bits_out = (unsigned*)it->second.p;
+        bool pooled = false;
+        for (; m->layers[k].block == b + 1; ++k) {
+            Layer& L = m->layers[k];
+            Layer* nx = in_block_next(m->layers, L);
+            const char* nm = L.name;
+            const int h = L.h, w = L.w, cin = L.cin, cout = L.cout;
+            const bool first = L.first(), last = L.last_of_block();
+            FwdEpi e; e.bias = m->d_params + L.b_off; e.relu = 1;
+            const float* wt = first ? m->d_w1pad : m->d_params + L.w_off;
+            if (train && L.rb_writer == RbWriter::self) e.relu_bits_out = L.rb;                              // its output is the next conv's input
+            if (train && L.pos == 2 && m->layers[L.prev].rb_writer == RbWriter::consumer) {                  // input = conv1_1, made by the gather kernel
+                e.in_relu_bits_out = m->layers[L.prev].rb; e.in_layer = m->layers[L.prev].name;
             }
-            if (train && b == 0 && i == 2) {                                                                 // input = conv1_1, made by the gather kernel
-                auto it = m->acts.find("rb:conv1_1");
-                if (it != m->acts.end()) { e.in_relu_bits_out = (unsigned*)it->second.p; e.in_layer = "conv1_1"; }
-            }
-            if (i == kConvsPerBlock[b]) {                                                                    // last conv of the block
-                snprintf(pn, sizeof pn, "pool%d", b + 1); e.pool_out = A(m, pn);
-                if (train) { char ix[16]; snprintf(ix, sizeof ix, "pidx%d", b + 1); e.pool_idx = (unsigned char*)A(m, ix); }
+            if (last) {
+                e.pool_out = L.pool;
+                if (train) e.pool_idx = L.pidx;
                 // The block's last conv output feeds only the pool.  If the output transform writes the pool (and, for training, the backward
                 // pass routes through the argmax bytes), the full-resolution tensor is never read again and is not written at all
                 // (2.15 GB for conv1_2 at 16 x 1024x512); fcn8s_get_activation of such a layer then returns stale data.
-                e.skip_y = !train || pool_backward_fused(m, b + 1, true);
+                e.skip_y = !train || L.pool_in_transform;
             }
-            char nxt[32] = "";
-            if (m->fuse_out_in && !first && i < kConvsPerBlock[b] && !(bf16_fwd_mode(m) && b >= 2) && !bf16_train_mode(m) && !fp8_mode(m) && (!train || e.relu_bits_out) &&
-                m->wino_min_cin > 0 && cin >= m->wino_min_cin && m->widths[b] >= m->wino_min_cin && m->widths[b] % 64 == 0 && cin % 16 == 0 &&
-                m->d_wino_v && wino_tile_for(m, h, w, 3) == 6) {
+            if (L.out_in_next && m->fuse_out_in && !(bf16_fwd_mode(m) && b >= 2) && !bf16_train_mode(m) && !fp8_mode(m) && (!train || e.relu_bits_out)) {
                 // this conv and the next one both run through F(6x6,3x3) on the same tile grid: its output transform writes the next conv's
-                // transformed input directly (training: into the buffer kept for that conv's weight gradient) and its own output never exists
-                snprintf(nxt, sizeof nxt, "conv%d_%d", b + 1, i + 1);
-                // the buffer the next conv will read its V from -- conv_fwd's own rule: the one kept for its weight gradient if the workspace
-                // has one (whether or not this pass trains), else the shared scratch.  Training: only if that kept buffer exists -- a direct
-                // weight gradient would read the activation that no longer exists.
-                auto it = m->acts.find(std::string("wv:") + nxt);
-                if (!train || it != m->acts.end()) { e.next_v = it != m->acts.end() ? it->second.p : m->d_wino_v; e.next_layer = nxt; }
+                // transformed input directly (training: into the buffer kept for that conv's weight gradient) and its own output never exists.
+                // The buffer the next conv will read its V from is the one kept for its weight gradient if the workspace has one (whether or
+                // not this pass trains), else the shared scratch.  (out_in_fused: the next conv keeps V -- a direct weight gradient would read
+                // the activation that no longer exists.)
+                e.next_v = nx->wv ? nx->wv : m->d_wino_v; e.next_layer = nx->name;
             }
             if (fp8 && !first) {
                 // FCN8S_PREC_FP8_INFER: the output goes to the next conv's e4m3 copy, to the copy the block's pool reads (blocks 1, 2, 5: codes with the exponent of
                 // the pool's consumer -- amax(pool) = amax(conv), q is monotone: the byte-max pool is exact), or to fp32 (blocks 3, 4: pool3 / pool4 feed the skip heads)
-                const int cout = m->widths[b];
-                std::string nx;
-                if (i < kConvsPerBlock[b]) { char t[32]; snprintf(t, sizeof t, "conv%d_%d", b + 1, i + 1); nx = t; }
-                else if (b != 2 && b != 3) { char t[32]; snprintf(t, sizeof t, "pool%din", b + 1); nx = t; }
+                const char* nxk = nx ? nx->name : ((b != 2 && b != 3) ? L.pool_in : nullptr);
                 const Q8Buf* yq = nullptr;
-                if (!nx.empty()) {
+                if (nxk) {
                     const char* cons = kFp8Layers[fp8_layer(nm) + 1];           // the next FP8 layer: the next conv, or the pool's consumer
-                    yq = q8_for(m, nx, N, h, w, cout, 3, fp8_ex(m, cons), s);
+                    yq = q8_for(m, nxk, N, h, w, cout, 3, fp8_ex(m, cons), s);
                     if (!yq) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed");
                 }
-                const int rc = fp8_conv(m, "conv3x3_fwd_fp8", nm, x, N, h, w, cin, cout, 3, yq ? nullptr : A(m, nm), yq, 1, s);
+                const int rc = fp8_conv(m, "conv3x3_fwd_fp8", nm, x, N, h, w, cin, cout, 3, yq ? nullptr : L.y, yq, 1, s);
                 if (rc) return rc;
-                if (yq) { m->pass.q8_filled.insert(nx); m->pass.y_unwritten.insert(nm); }
-                x = A(m, nm); cin = cout;
+                if (yq) { m->pass.q8_filled.insert(nxk); m->pass.y_unwritten.insert(nm); }
+                x = L.y;
                 continue;
             }
             bool done = false;
-            if (first && !bf16_train_mode(m) && !fp8_mode(m) && m->conv1_in_transform && m->widths[0] == 64 && kConvsPerBlock[0] == 2 && m->widths[0] >= m->wino_min_cin && m->wino_min_cin > 0 &&
-                m->d_wino_v && wino_tile_for(m, h, w, 3) == 6) {
+            if (L.conv1_in_next && m->conv1_in_transform && !bf16_train_mode(m) && !fp8_mode(m)) {
                 // conv1_1's only reader is conv1_2's F(6x6,3x3) input transform: that transform evaluates conv1_1 on its own patches, straight from the
                 // image (winograd.hip: wino_input_conv1_kernel), writes conv1_2's V -- into the buffer conv_fwd will look for it in -- and, in training,
                 // the ReLU record the backward pass masks with.  conv1_1's 134 MB per image are never written or read.
-                auto wv = m->acts.find("wv:conv1_2");
-                auto rb = m->acts.find("rb:conv1_1");
-                if (!train || (wv != m->acts.end() && rb != m->acts.end())) {
-                    float* vdst = wv != m->acts.end() ? wv->second.p : m->d_wino_v;
+                if (!train || (nx->wv && L.rb)) {
+                    float* vdst = nx->wv ? nx->wv : m->d_wino_v;
                     const long long T = wino_tiles(6, N, h, w);
                     ProfScope ps(m, "wino_transform", 0, 4.0 * (4.0 * N * h * w + 64.0 * T * 64.0) + (train ? 8.0 * N * h * w : 0.0), nm);
-                    launch_wino_input_conv1(x, m->d_w1pad, e.bias, vdst, N, h, w, s, train ? (unsigned*)rb->second.p : nullptr);
+                    launch_wino_input_conv1(x, m->d_w1pad, e.bias, vdst, N, h, w, s, train ? L.rb : nullptr);
                     if (train) m->pass.rbits_ok.insert(nm);
-                    m->pass.fwd_v.give("conv1_2"); m->pass.y_unwritten.insert(nm);
+                    m->pass.fwd_v.give(nx->name); m->pass.y_unwritten.insert(nm);
                     done = true;
                 }
             }
-            if (!done && first && m->widths[0] == 64) {            // conv1_1: write-bound gather kernel (igemm.hip: conv1_glds_kernel)
+            if (!done && first && cout == 64) {            // conv1_1: write-bound gather kernel (igemm.hip: conv1_glds_kernel)
                 // bf16_train, training: conv1_2 reads this layer as its padded bf16 copy and nobody else reads it (the mask of conv1_2's data gradient is the
                 // sign of that copy): the tile kernel writes the copy and no fp32 tensor
                 unsigned short* y16 = nullptr;
-                if (bf16_train_mode(m) && cp && m->bf16_acts && m->conv1_tiled && h % 8 == 0 && w % 16 == 0 && kConvsPerBlock[0] >= 2 && m->widths[0] % 64 == 0)
-                    y16 = xg16_for(m, "conv1_2", N, h, w, m->widths[0], 3, s);
-                ProfScope ps(m, "conv1_1_fwd", 2.0 * N * h * w * 27.0 * m->widths[0], 4.0 * N * h * w * 3.0 + (y16 ? 2.0 : 4.0) * N * h * w * m->widths[0], nm);
-                done = launch_conv1_fwd(x, m->d_w1pad, e.bias, y16 ? nullptr : A(m, nm), m->d_w1pad + 12 * 4 * (size_t)m->widths[0], N, h, w, m->widths[0], m->conv1_tiled, s, y16, g16_ps(N, h, w, 3));
-                if (done && y16) { m->pass.xg16_filled.insert("conv1_2"); m->pass.y_unwritten.insert(nm); m->pass.in_bf16_only.insert("conv1_2"); }
+                if (bf16_train_mode(m) && cp && m->bf16_acts && m->conv1_tiled && h % 8 == 0 && w % 16 == 0 && nx && cout % 64 == 0)
+                    y16 = xg16_for(m, nx->name, N, h, w, cout, 3, s);
+                ProfScope ps(m, "conv1_1_fwd", 2.0 * N * h * w * 27.0 * cout, 4.0 * N * h * w * 3.0 + (y16 ? 2.0 : 4.0) * N * h * w * cout, nm);
+                done = launch_conv1_fwd(x, m->d_w1pad, e.bias, y16 ? nullptr : L.y, m->d_w1pad + 12 * 4 * (size_t)cout, N, h, w, cout, m->conv1_tiled, s, y16, g16_ps(N, h, w, 3));
+                if (done && y16) { m->pass.xg16_filled.insert(nx->name); m->pass.y_unwritten.insert(nm); m->pass.in_bf16_only.insert(nx->name); }
             }
             if (!done && bf16_train_mode(m) && !first) {
                 // FCN8S_PREC_BF16_TRAIN: every convolution but conv1_1 (3 input channels) as a direct convolution with bf16-rounded operands; the
@@ -1703,27 +1716,26 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                     ProfScope ps(m, "bf16_convert", 0, 4.0 * N * h * w * cin + 2.0 * N * (h + 2) * (w + 2) * cin); launch_f32_to_bf16_padded(x, xb, N, h, w, cin, 1, s, g16_ps(N, h, w, 3));
                 }
                 // the next convolution of the block reads this output as ITS padded bf16 input: this kernel's epilogue writes that copy
-                unsigned short* yb = nullptr; char nx[32] = "";
-                if (cp && m->bf16_acts && i < kConvsPerBlock[b]) { snprintf(nx, sizeof nx, "conv%d_%d", b + 1, i + 1); yb = xg16_for(m, nx, N, h, w, m->widths[b], 3, s); }
+                unsigned short* yb = nullptr; const char* nxk = "";
+                if (cp && m->bf16_acts && nx) { nxk = nx->name; yb = xg16_for(m, nxk, N, h, w, cout, 3, s); }
                 // the block's LAST convolution is read by its pool only, and pool1 / pool2 / pool5 only by bf16 convolutions: the pool then takes this output
                 // as a bf16 copy of the kernel's own geometry ("pool<b>in"), picks its maxima among the bf16 values (what bf16(max of the fp32 values) is anyway)
                 // and no fp32 tensor is written (pool3 / pool4 also feed the fp32 skip heads: their blocks keep the fp32 tensor)
-                const bool pool16 = cp && m->bf16_acts && m->bf16_fuse_pool && i == kConvsPerBlock[b] && b != 2 && b != 3 && cin % 64 == 0 && m->widths[b] % 64 == 0 &&
+                const bool pool16 = cp && m->bf16_acts && m->bf16_fuse_pool && last && b != 2 && b != 3 && cin % 64 == 0 && cout % 64 == 0 &&
                                     m->widths[b == 4 ? 5 : b + 1] % 64 == 0;
-                if (pool16) { snprintf(nx, sizeof nx, "pool%din", b + 1); yb = xg16_for(m, nx, N, h, w, m->widths[b], 3, s); }
+                if (pool16) { nxk = L.pool_in; yb = xg16_for(m, nxk, N, h, w, cout, 3, s); }
                 // ... and if that is the output's only reader (option bf16_acts; the mask of the consumer's data gradient is the sign of the copy), the fp32
                 // tensor is not written at all.  (Both layers' gradients must fit the bf16 kernels: a fallback would look for the fp32 tensor.)
-                const bool only16 = yb && m->bf16_acts && cin % 64 == 0 && m->widths[b] % 64 == 0;
+                const bool only16 = yb && m->bf16_acts && cin % 64 == 0 && cout % 64 == 0;
                 // (the convolution kernels address their padded copies through a 64-bit tile base; the weight-gradient kernels' 32-bit per-lane byte offsets span TWO
                 //  32-channel planes of a copy -- launch_wgrad_bf16's limit, applied HERE, before anything is launched: a 32-channel plane of the padded map must stay
                 //  below 4 GiB, i.e. about 67 million padded positions (127 images of 1024x512).  Round 5 refused a whole copy of 4 GiB: 64 x 1024x512.)
                 if ((double)g16_ps(N, h, w, 3) * 2.0 + 65536.0 >= 4294967296.0)
                     return fail(m, FCN8S_ERR_SHAPE, std::string("bf16_train: a 32-channel plane of the padded bf16 copy of ") + nm + "'s input would reach 4 GiB at this batch size; use a smaller batch per GPU");
-                done = bf16_conv_layer(m, "conv3x3_fwd_bf16", (std::string(nm) + "/filter").c_str(), (std::string(nm) + "/biases").c_str(), x, only16 ? nullptr : A(m, nm),
-                                       N, h, w, cin, m->widths[b], 3, 0, 1.f, 0, s, /*allow_small=*/false, xb, /*any_shape=*/true, yb, 1, g16_ps(N, h, w, 3), g16_ps(N, h, w, 3));
+                done = bf16_conv_layer(m, "conv3x3_fwd_bf16", L, x, only16 ? nullptr : L.y, 0, 1.f, 0, s, /*allow_small=*/false, xb, /*any_shape=*/true, yb, 1, g16_ps(N, h, w, 3), g16_ps(N, h, w, 3));
                 if (!done) return fail(m, FCN8S_ERR_SHAPE, std::string("bf16_train: ") + nm + " does not fit the bf16 convolution kernel");
-                if (done && yb) m->pass.xg16_filled.insert(nx);
-                if (done && only16) { m->pass.y_unwritten.insert(nm); if (!pool16) m->pass.in_bf16_only.insert(nx); }
+                if (done && yb) m->pass.xg16_filled.insert(nxk);
+                if (done && only16) { m->pass.y_unwritten.insert(nm); if (!pool16) m->pass.in_bf16_only.insert(nxk); }
             }
             if (!done && bf16_fwd_mode(m) && b >= 2) {
                 // FCN8S_PREC_BF16_FWD: conv3_1 .. conv5_3 as direct convolutions with bf16-rounded operands on the 256 x 256 bf16 kernel (the
@@ -1731,43 +1743,39 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
                 // stays in the Winograd domain, so the transformed input and this step's filter bank are made here
                 // training: the transform that keeps this layer's V for the weight gradient runs first and writes the padded bf16 copy of the
                 // input on the way (the convolution then starts from it; without a kept V, or in inference, the convolution converts its input itself)
-                unsigned short* xb = train ? xb_by_transform(m, nm, N, h, w, cin, m->widths[b], s) : nullptr;
+                unsigned short* xb = train ? xb_by_transform(m, L, N, s) : nullptr;
                 auto operands = [&]() {
                     // the previous conv of the block came from the bf16 kernel too (no ReLU record): this transform of its output writes one
-                    unsigned* irb = nullptr; char prev[32] = "";
-                    if (i > 1) {
-                        snprintf(prev, sizeof prev, "conv%d_%d", b + 1, i - 1);
-                        auto it = m->acts.find(std::string("rb:") + prev);
-                        if (it != m->acts.end() && !m->pass.rbits_ok.count(prev)) irb = (unsigned*)it->second.p;
-                    }
-                    wino_backward_operands(m, nm, x, wt, N, h, w, cin, m->widths[b], 3, s, irb, irb ? prev : nullptr, xb);
+                    const Layer* pv = in_block_prev(m->layers, L);
+                    unsigned* irb = (pv && pv->rb && !m->pass.rbits_ok.count(pv->name)) ? pv->rb : nullptr;
+                    wino_backward_operands(m, nm, x, wt, N, h, w, cin, cout, 3, s, irb, irb ? pv->name : nullptr, xb);
                 };
                 if (xb) operands();
-                done = bf16_conv_layer(m, "conv3x3_fwd_bf16", (std::string(nm) + "/filter").c_str(), (std::string(nm) + "/biases").c_str(), x, A(m, nm),
-                                       N, h, w, cin, m->widths[b], 3, 0, 1.f, 0, s, /*allow_small=*/false, xb);
+                done = bf16_conv_layer(m, "conv3x3_fwd_bf16", L, x, L.y, 0, 1.f, 0, s, /*allow_small=*/false, xb);
                 if (done && train && !xb) operands();
             }
-            if (!done) pooled = conv_fwd(m, first ? "conv1_1_fwd" : "conv3x3_fwd", x, wt, A(m, nm), N, h, w, cin, m->widths[b], 3, e, s, first ? 3 : 0, nm);
-            x = A(m, nm); cin = m->widths[b];
+            if (!done) pooled = conv_fwd(m, first ? "conv1_1_fwd" : "conv3x3_fwd", x, wt, L.y, N, h, w, cin, cout, 3, e, s, L.real_cin, nm);
+            x = L.y;
         }
-        snprintf(pn, sizeof pn, "pool%d", b + 1);
+        const Layer& L = m->layers[k - 1];         // the block's last conv; m->layers[k]: the pool's consumer (the next block's first conv, or fc6)
+        const Layer& cons = m->layers[k];
+        const char* pn = L.pool_name;
+        const int h = L.h, w = L.w, cin = L.cout;
         if (fp8) {
             m->pass.pool_fused[b] = false; m->pass.pool_routed[b] = false;
             if (b != 2 && b != 3) {
                 // byte max of the last conv's e4m3 copy straight into the consumer's copy (conv<b+2>_1, pad 1; fc6, pad (k - 1) / 2)
-                char pin[32], cons[32]; int ck = 3;
-                snprintf(pin, sizeof pin, "pool%din", b + 1);
-                if (b < 4) snprintf(cons, sizeof cons, "conv%d_1", b + 2); else { snprintf(cons, sizeof cons, "fc6"); ck = m->fc6k; }
-                Q8Buf* yq = q8_for(m, cons, N, h / 2, w / 2, cin, ck, fp8_ex(m, cons), s);
+                const int ck = cons.K;
+                Q8Buf* yq = q8_for(m, cons.name, N, h / 2, w / 2, cin, ck, fp8_ex(m, cons.name), s);
                 if (!yq) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed");
-                const Q8Buf& xi = m->q8[pin];
+                const Q8Buf& xi = m->q8[L.pool_in];
                 { ProfScope ps(m, "maxpool_fwd_fp8", 0, 1.25 * N * h * w * cin); launch_maxpool_fp8(xi.p, xi.ps, yq->p, yq->ps, N, h, w, cin, (ck - 1) / 2, s); }
-                m->pass.q8_filled.insert(cons); m->pass.y_unwritten.insert(pn);
+                m->pass.q8_filled.insert(cons.name); m->pass.y_unwritten.insert(pn);
             } else {
                 ProfScope ps(m, "maxpool_fwd", 0, 4.0 * N * h * w * cin * 1.25);
-                launch_maxpool_fwd(x, A(m, pn), N, h, w, cin, s);
+                launch_maxpool_fwd(x, L.pool, N, h, w, cin, s);
             }
-            x = A(m, pn); h /= 2; w /= 2;
+            x = L.pool;
             continue;
         }
         m->pass.pool_fused[b] = pooled && train;
@@ -1776,69 +1784,68 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
             // bf16_train, training: the pool keeps its routing bytes (the backward pass reads one byte per window instead of the block's last activation)
             // and writes the consumer's padded bf16 copy itself -- conv<b+2>_1 (pad 1) or fc6 (pad 3); pool1, pool2 and pool5 have no other reader, so
             // with option bf16_acts their fp32 tensors are not written (pool3 / pool4 feed the fp32 skip heads)
-            char cons[32]; int ck = 3, cout_c = 0;
-            if (b < 4) { snprintf(cons, sizeof cons, "conv%d_1", b + 2); cout_c = m->widths[b + 1]; } else { snprintf(cons, sizeof cons, "fc6"); ck = m->fc6k; cout_c = m->widths[5]; }
+            const int ck = cons.K, cout_c = cons.cout;
             unsigned short* yb = nullptr;
             if (m->bf16_acts && cin % 64 == 0 && cout_c % 64 == 0)
-                yb = xg16_for(m, cons, N, h / 2, w / 2, cin, ck, s);
+                yb = xg16_for(m, cons.name, N, h / 2, w / 2, cin, ck, s);
             const bool only16 = yb && b != 2 && b != 3;
-            char ix[16]; snprintf(ix, sizeof ix, "pidx%d", b + 1);
-            char pin[32]; snprintf(pin, sizeof pin, "pool%din", b + 1);
-            auto pi = m->xg16.find(pin);
-            const bool in16 = only16 && pi != m->xg16.end() && pi->second && m->pass.xg16_filled.count(pin);      // the last conv wrote only its bf16 copy
+            auto pi = m->xg16.find(L.pool_in);
+            const bool in16 = only16 && pi != m->xg16.end() && pi->second && m->pass.xg16_filled.count(L.pool_in);      // the last conv wrote only its bf16 copy
             ProfScope ps(m, "maxpool_fwd", 0, (in16 ? 2.0 : 4.0) * N * h * w * cin + 4.0 * N * h * w * cin * (only16 ? 0.0625 : 0.3125) + (yb ? 0.5 * N * h * w * cin : 0.0));
-            if (in16) launch_maxpool_fwd_route16(pi->second + g16_off(bf16_guard_rows(3, w + 2), cin), g16_ps(N, h, w, 3), (unsigned char*)A(m, ix), N, h, w, cin, s, yb, (ck - 1) / 2, g16_ps(N, h / 2, w / 2, ck));
-            else launch_maxpool_fwd_route(x, only16 ? nullptr : A(m, pn), (unsigned char*)A(m, ix), N, h, w, cin, s, yb, (ck - 1) / 2, g16_ps(N, h / 2, w / 2, ck),
+            if (in16) launch_maxpool_fwd_route16(pi->second + g16_off(bf16_guard_rows(3, w + 2), cin), g16_ps(N, h, w, 3), L.pidx, N, h, w, cin, s, yb, (ck - 1) / 2, g16_ps(N, h / 2, w / 2, ck));
+            else launch_maxpool_fwd_route(x, only16 ? nullptr : L.pool, L.pidx, N, h, w, cin, s, yb, (ck - 1) / 2, g16_ps(N, h / 2, w / 2, ck),
                                           /*round16=*/(b != 2 && b != 3) ? 1 : 0);
             m->pass.pool_routed[b] = true; pooled = true;
-            if (yb) m->pass.xg16_filled.insert(cons);
-            if (only16) { m->pass.y_unwritten.insert(pn); m->pass.in_bf16_only.insert(cons); }
+            if (yb) m->pass.xg16_filled.insert(cons.name);
+            if (only16) { m->pass.y_unwritten.insert(pn); m->pass.in_bf16_only.insert(cons.name); }
         }
         if (!pooled) {
             // a block whose last conv did not run through the Winograd output transform (bf16 modes) but whose backward pass does run in the
             // Winograd domain: keep the same routing bytes, so that d(pool) is routed inside wino_dout_kernel and dZ is never written
-            const bool route = train && cin % 4 == 0 && pool_backward_fused(m, b + 1, true);
+            const bool route = train && cin % 4 == 0 && L.pool_in_transform;
             ProfScope ps(m, "maxpool_fwd", 0, 4.0 * N * h * w * cin * (route ? 1.3125 : 1.25));
-            if (route) { char ix[16]; snprintf(ix, sizeof ix, "pidx%d", b + 1); launch_maxpool_fwd_route(x, A(m, pn), (unsigned char*)A(m, ix), N, h, w, cin, s); m->pass.pool_fused[b] = true; }
-            else launch_maxpool_fwd(x, A(m, pn), N, h, w, cin, s);
+            if (route) { launch_maxpool_fwd_route(x, L.pool, L.pidx, N, h, w, cin, s); m->pass.pool_fused[b] = true; }
+            else launch_maxpool_fwd(x, L.pool, N, h, w, cin, s);
         }
-        x = A(m, pn); h /= 2; w /= 2;
+        x = L.pool;
     }
-    const int h5 = h, w5 = w;
+    const Layer &F6 = m->layers[13], &F7 = m->layers[14];
+    const int h5 = F6.h, w5 = F6.w;
+    float *w6 = m->d_params + F6.w_off, *b6 = m->d_params + F6.b_off, *w7 = m->d_params + F7.w_off, *b7 = m->d_params + F7.b_off;
     const bool drop = train && keep_prob < 1.f;
     m->drop_stream = (uint32_t)(2 * m->step);
     if (fp8) {
         // fc6 writes fc7's e4m3 copy only; fc7 writes fp32 for the fc7_1x1 head
-        const Q8Buf* q7 = q8_for(m, "fc7", N, h5, w5, m->widths[5], 1, fp8_ex(m, "fc7"), s);
+        const Q8Buf* q7 = q8_for(m, F7.name, N, h5, w5, F7.cin, 1, fp8_ex(m, F7.name), s);
         if (!q7) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed");
-        int rc = fp8_conv(m, "fc6_fwd_fp8", "fc6", x, N, h5, w5, m->widths[4], m->widths[5], m->fc6k, nullptr, q7, 0, s); if (rc) return rc;
-        m->pass.q8_filled.insert("fc7"); m->pass.y_unwritten.insert("fc6");
-        rc = fp8_conv(m, "fc7_fwd_fp8", "fc7", A(m, "fc6"), N, h5, w5, m->widths[5], m->widths[6], 1, A(m, "fc7"), nullptr, 0, s); if (rc) return rc;
+        int rc = fp8_conv(m, "fc6_fwd_fp8", F6.name, x, N, h5, w5, F6.cin, F6.cout, F6.K, nullptr, q7, 0, s); if (rc) return rc;
+        m->pass.q8_filled.insert(F7.name); m->pass.y_unwritten.insert(F6.name);
+        rc = fp8_conv(m, "fc7_fwd_fp8", F7.name, F6.y, N, h5, w5, F7.cin, F7.cout, 1, F7.y, nullptr, 0, s); if (rc) return rc;
     } else if (bf16_train_mode(m)) {
-        unsigned short* xb6 = cp ? xg16_for(m, "fc6", N, h5, w5, m->widths[4], m->fc6k, s) : nullptr;
-        if (xb6 && !m->pass.xg16_filled.count("fc6")) { ProfScope ps(m, "bf16_convert", 0, 6.0 * N * h5 * w5 * m->widths[4]); launch_f32_to_bf16_padded(x, xb6, N, h5, w5, m->widths[4], (m->fc6k - 1) / 2, s, g16_ps(N, h5, w5, m->fc6k)); }
-        unsigned short* xb7 = cp ? xg16_for(m, "fc7", N, h5, w5, m->widths[5], 1, s) : nullptr;
+        unsigned short* xb6 = cp ? xg16_for(m, F6.name, N, h5, w5, F6.cin, F6.K, s) : nullptr;
+        if (xb6 && !m->pass.xg16_filled.count(F6.name)) { ProfScope ps(m, "bf16_convert", 0, 6.0 * N * h5 * w5 * F6.cin); launch_f32_to_bf16_padded(x, xb6, N, h5, w5, F6.cin, (F6.K - 1) / 2, s, g16_ps(N, h5, w5, F6.K)); }
+        unsigned short* xb7 = cp ? xg16_for(m, F7.name, N, h5, w5, F7.cin, 1, s) : nullptr;
         const bool fuse7 = xb7 != nullptr && m->bf16_acts;      // fc7's input copy comes out of fc6's epilogue (16-byte stores since the tile kernel's epilogue goes through LDS)
-        if (!bf16_conv_layer(m, "fc6_fwd_bf16", "fc6/weights", "fc6/biases", x, A(m, "fc6"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, drop, keep_prob, m->drop_stream, s, false, xb6, true,
-                             fuse7 ? xb7 : nullptr, 0, g16_ps(N, h5, w5, m->fc6k), g16_ps(N, h5, w5, 1)))
+        if (!bf16_conv_layer(m, "fc6_fwd_bf16", F6, x, F6.y, drop, keep_prob, m->drop_stream, s, false, xb6, true,
+                             fuse7 ? xb7 : nullptr, 0, g16_ps(N, h5, w5, F6.K), g16_ps(N, h5, w5, 1)))
             return fail(m, FCN8S_ERR_SHAPE, "bf16_train: fc6 does not fit the bf16 convolution kernel");
-        if (xb7 && !fuse7) { ProfScope ps(m, "bf16_convert", 0, 6.0 * N * h5 * w5 * m->widths[5]); launch_f32_to_bf16_padded(A(m, "fc6"), xb7, N, h5, w5, m->widths[5], 0, s, g16_ps(N, h5, w5, 1)); }
-        if (!bf16_conv_layer(m, "fc7_fwd_bf16", "fc7/weights", "fc7/biases", A(m, "fc6"), A(m, "fc7"), N, h5, w5, m->widths[5], m->widths[6], 1, drop, keep_prob, m->drop_stream + 1, s, false, xb7, true, nullptr, 0, g16_ps(N, h5, w5, 1)))
+        if (xb7 && !fuse7) { ProfScope ps(m, "bf16_convert", 0, 6.0 * N * h5 * w5 * F7.cin); launch_f32_to_bf16_padded(F6.y, xb7, N, h5, w5, F7.cin, 0, s, g16_ps(N, h5, w5, 1)); }
+        if (!bf16_conv_layer(m, "fc7_fwd_bf16", F7, F6.y, F7.y, drop, keep_prob, m->drop_stream + 1, s, false, xb7, true, nullptr, 0, g16_ps(N, h5, w5, 1)))
             return fail(m, FCN8S_ERR_SHAPE, "bf16_train: fc7 does not fit the bf16 convolution kernel");
     } else if (m->precision == FCN8S_PREC_BF16_FC || bf16_fwd_mode(m)) {
         // config 5: bf16-rounded operands, fp32 accumulate, fp32 epilogue and output (gemm_bf16.hip)
-        bf16_conv_layer(m, "fc6_fwd_bf16", "fc6/weights", "fc6/biases", x, A(m, "fc6"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, drop, keep_prob, m->drop_stream, s);
+        bf16_conv_layer(m, "fc6_fwd_bf16", F6, x, F6.y, drop, keep_prob, m->drop_stream, s);
         // the fp32 gradients of fc6 run in the Winograd domain and want the transformed input and this step's filter bank
-        if (train) wino_backward_operands(m, "fc6", x, Wp(m, "fc6/weights"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, s);
-        bf16_conv_layer(m, "fc7_fwd_bf16", "fc7/weights", "fc7/biases", A(m, "fc6"), A(m, "fc7"), N, h5, w5, m->widths[5], m->widths[6], 1, drop, keep_prob, m->drop_stream + 1, s);
+        if (train) wino_backward_operands(m, F6.name, x, w6, N, h5, w5, F6.cin, F6.cout, F6.K, s);
+        bf16_conv_layer(m, "fc7_fwd_bf16", F7, F6.y, F7.y, drop, keep_prob, m->drop_stream + 1, s);
     } else {
         {
-            FwdEpi e; e.bias = Wp(m, "fc6/biases"); e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream;
-            conv_fwd(m, "fc6_fwd", x, Wp(m, "fc6/weights"), A(m, "fc6"), N, h5, w5, m->widths[4], m->widths[5], m->fc6k, e, s, 0, "fc6");
+            FwdEpi e; e.bias = b6; e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream;
+            conv_fwd(m, "fc6_fwd", x, w6, F6.y, N, h5, w5, F6.cin, F6.cout, F6.K, e, s, 0, F6.name);
         }
         {
-            FwdEpi e; e.bias = Wp(m, "fc7/biases"); e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream + 1;
-            conv_fwd(m, "fc7_fwd", A(m, "fc6"), Wp(m, "fc7/weights"), A(m, "fc7"), N, h5, w5, m->widths[5], m->widths[6], 1, e, s);
+            FwdEpi e; e.bias = b7; e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream + 1;
+            conv_fwd(m, "fc7_fwd", F6.y, w7, F7.y, N, h5, w5, F7.cin, F7.cout, 1, e, s);
         }
     }
     // decoder (fcn8s_tensorflow.py:171-233)
@@ -2048,72 +2055,54 @@ void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
 {
     hipStream_t s = m->stream;
     const int N = m->N;
-    for (int b = b_hi; b >= b_lo; --b) {
-        const int h = m->H >> (b - 1), w = m->W >> (b - 1);      // resolution of this block's convs
-        const int cw = m->widths[b - 1];
-        const int nconv = kConvsPerBlock[b - 1];
-        char last[32]; snprintf(last, sizeof last, "conv%d_%d", b, nconv);
+    for (int k = (int)m->layers.size() - 1; k >= 0; --k) {
+        Layer& L = m->layers[k];
+        if (L.block > b_hi || L.block < b_lo) continue;
+        const int b = L.block, h = L.h, w = L.w, cw = L.cout, cin = L.cin;
+        const char* nm = L.name;
+        float *gw = m->d_grads + L.w_off, *gb = m->d_grads + L.b_off;
         // d(pool_b) in gbuf[gcur] -> dZ of the last conv (ReLU mask fused).  If the forward pass kept the argmax bytes and both
         // gradients of that conv run through Winograd, the routing happens inside their shared transform and dZ is never written.
-        const unsigned char* pidx = nullptr;
-        {
-            char ix[16]; snprintf(ix, sizeof ix, "pidx%d", b);
-            const bool wino_both = pool_backward_fused(m, b, m->pass.pool_fused[b - 1]);
-            if (wino_both) pidx = (const unsigned char*)A(m, ix);
-        }
-        bool pool_done = false;
-        if (!pidx && bf16_train_mode(m) && m->bf16_fuse_pool && m->train_mode && cw % 64 == 0) {
-            // bf16_train: nobody reads the fp32 dZ of the block's last conv -- its weight and data gradients take the padded bf16 copy, its bias gradient the
-            // column sums: the pool's backward kernel writes exactly those (gbuf[gcur ^ 1] stays unwritten; the "dz" handed on below is never dereferenced)
-            unsigned short* dzb = g16_for(m, m->dyg16, last, N, h, w, cw, 3, s);
-            if (dzb) {
-                ProfScope ps(m, "maxpool_bwd", 0, 4.0 * N * h * w * cw * (m->pass.pool_routed[b - 1] ? 0.3125 : 1.25) + 2.0 * N * h * w * cw);
-                char ix[16]; snprintf(ix, sizeof ix, "pidx%d", b);
-                pool_done = launch_maxpool_bwd_bf16(A(m, last), m->gbuf[m->gcur], dzb, Gp(m, std::string(last) + "/biases"), N, h, w, cw, s,
-                                                    m->pass.pool_routed[b - 1] ? (const unsigned char*)A(m, ix) : nullptr, g16_ps(N, h, w, 3));
-            }
-            if (pool_done) { m->pass.dyg16_filled.insert(last); m->pass.db_taken.insert(last); m->pass.dz_unwritten.insert(last); m->gcur ^= 1; }
-        }
-        if (!pidx && !pool_done) {
-            ProfScope ps(m, "maxpool_bwd", 0, 4.0 * N * h * w * cw * 2.25);
-            launch_maxpool_bwd(A(m, last), m->gbuf[m->gcur], m->gbuf[m->gcur ^ 1], N, h, w, cw, 1, s);
-            m->gcur ^= 1;
-        }
-        for (int i = nconv; i >= 1; --i) {
-            char nm[32]; snprintf(nm, sizeof nm, "conv%d_%d", b, i);
-            const float* dz = m->gbuf[m->gcur];
-            const float* xin; int cin; int real_cin = 0;
-            char inname[32];
-            if (i > 1) { snprintf(inname, sizeof inname, "conv%d_%d", b, i - 1); xin = A(m, inname); cin = cw; }
-            else if (b > 1) { snprintf(inname, sizeof inname, "pool%d", b - 1); xin = A(m, inname); cin = m->widths[b - 2]; }
-            else { xin = A(m, "x0"); cin = 4; real_cin = 3; }
-            const bool first = (b == 1 && i == 1);
-            // the data-gradient conv (cw -> cin channels) takes the Winograd path under the same conditions as conv_dgrad()
-            const bool dgrad_wino = !first && m->wino_min_cin > 0 && cw >= m->wino_min_cin && m->d_wino_v && wino_tile_for(m, h, w) >= 4 &&
-                                    cw % 16 == 0 && cin % 64 == 0;
-            const unsigned char* pix = i == nconv ? pidx : nullptr;
-            conv_wgrad(m, first ? "conv1_1_wgrad" : "conv3x3_wgrad", xin, dz, Gp(m, std::string(nm) + "/filter"), Gp(m, std::string(nm) + "/biases"),
-                       N, h, w, cin, cw, 3, 1.f, s, real_cin, nm, dgrad_wino, pix);
-            if (first) break;
-            DgradEpi e; e.w_fwd = Wp(m, std::string(nm) + "/filter"); e.lazy_wt = 1;
-            if (i > 1) {                                                   // ReLU of the previous conv
-                e.mask = xin; e.mask_scale = 1.f; e.yb_layer = inname; e.yb_K = 3;
-                if (m->pass.rbits_ok.count(inname)) e.relu_bits_in = (const unsigned*)A(m, (std::string("rb:") + inname).c_str());
-                // The previous conv takes this gradient only through dM = A dZ A^T (weight gradient in the Winograd domain, adjoint data
-                // gradient): the gather kernel can write dM directly.  Conditions = those of conv_wgrad's adjoint branch for that layer.
-                const int cin_prev = i > 2 ? cw : (b > 1 ? m->widths[b - 2] : 4);
-                const bool prev_first = (b == 1 && i == 2);
-                e.yb_only = !prev_first && cin_prev % 64 == 0 && cw % 64 == 0;      // (conv1_1's weight gradient is exact fp32 and reads the fp32 tensor)
-                if (m->fuse_dgrad_dout && e.relu_bits_in && !prev_first && m->train_mode && m->d_wino_m &&
-                    wino_tile_for(m, h, w) == 6 && cw % 64 == 0 && cin_prev % 64 == 0 && m->acts.count(std::string("wv:") + inname)) {
-                    e.dm_out = m->d_wino_m; e.dm_out_layer = inname;
+        const unsigned char* pix = nullptr;
+        if (L.last_of_block()) {
+            if (pool_backward_fused(L, m->pass.pool_fused[b - 1])) pix = L.pidx;
+            bool pool_done = false;
+            if (!pix && bf16_train_mode(m) && m->bf16_fuse_pool && m->train_mode && cw % 64 == 0) {
+                // bf16_train: nobody reads the fp32 dZ of the block's last conv -- its weight and data gradients take the padded bf16 copy, its bias gradient the
+                // column sums: the pool's backward kernel writes exactly those (gbuf[gcur ^ 1] stays unwritten; the "dz" handed on below is never dereferenced)
+                unsigned short* dzb = g16_for(m, m->dyg16, nm, N, h, w, cw, 3, s);
+                if (dzb) {
+                    ProfScope ps(m, "maxpool_bwd", 0, 4.0 * N * h * w * cw * (m->pass.pool_routed[b - 1] ? 0.3125 : 1.25) + 2.0 * N * h * w * cw);
+                    pool_done = launch_maxpool_bwd_bf16(L.y, m->gbuf[m->gcur], dzb, gb, N, h, w, cw, s,
+                                                        m->pass.pool_routed[b - 1] ? L.pidx : nullptr, g16_ps(N, h, w, 3));
                 }
+                if (pool_done) { m->pass.dyg16_filled.insert(nm); m->pass.db_taken.insert(nm); m->pass.dz_unwritten.insert(nm); m->gcur ^= 1; }
             }
-            else if (b == 5) e.addend = m->gskip4;                        // d(pool4) also receives the pool4_1x1 path
-            else if (b == 4) e.addend = m->gskip3;                        // d(pool3) also receives the pool3_1x1 path
-            conv_dgrad(m, "conv3x3_dgrad", dz, WTp(m, std::string(nm) + "/filter"), m->gbuf[m->gcur ^ 1], N, h, w, cw, cin, 3, e, s, nm);
-            m->gcur ^= 1;
+            if (!pix && !pool_done) {
+                ProfScope ps(m, "maxpool_bwd", 0, 4.0 * N * h * w * cw * 2.25);
+                launch_maxpool_bwd(L.y, m->gbuf[m->gcur], m->gbuf[m->gcur ^ 1], N, h, w, cw, 1, s);
+                m->gcur ^= 1;
+            }
         }
+        const float* dz = m->gbuf[m->gcur];
+        const Layer* pv = in_block_prev(m->layers, L);                // the layer whose output this one reads: the conv in front of it, the pool of the block before, or the image
+        const float* xin = pv ? pv->y : (L.first() ? A(m, "x0") : m->layers[L.prev].pool);
+        // (whether the data gradient that follows shares this transform, and in which form, is the layer's own rule: conv_wgrad asks it)
+        conv_wgrad(m, L.first() ? "conv1_1_wgrad" : "conv3x3_wgrad", xin, dz, gw, gb, N, h, w, cin, cw, 3, 1.f, s, L.real_cin, nm, pix);
+        if (L.first()) break;
+        DgradEpi e; e.w_fwd = m->d_params + L.w_off; e.lazy_wt = 1;
+        if (pv) {                                                      // ReLU of the previous conv
+            e.mask = xin; e.mask_scale = 1.f; e.yb_layer = pv->name; e.yb_K = 3;
+            if (m->pass.rbits_ok.count(pv->name)) e.relu_bits_in = pv->rb;
+            e.yb_only = !pv->first() && pv->cin % 64 == 0 && cw % 64 == 0;      // (conv1_1's weight gradient is exact fp32 and reads the fp32 tensor)
+            // The previous conv takes this gradient only through dM = A dZ A^T (weight gradient in the Winograd domain, adjoint data
+            // gradient): the gather kernel can write dM directly.
+            if (pv->dm_from_next && m->fuse_dgrad_dout && e.relu_bits_in && m->train_mode) { e.dm_out = m->d_wino_m; e.dm_out_layer = pv->name; }
+        }
+        else if (b == 5) e.addend = m->gskip4;                        // d(pool4) also receives the pool4_1x1 path
+        else if (b == 4) e.addend = m->gskip3;                        // d(pool3) also receives the pool3_1x1 path
+        conv_dgrad(m, "conv3x3_dgrad", dz, m->d_wt + L.w_off, m->gbuf[m->gcur ^ 1], N, h, w, cw, cin, 3, e, s, nm);
+        m->gcur ^= 1;
     }
 }
 
@@ -3619,21 +3608,20 @@ int fcn8s_get_relu_record(fcn8s_model* m, const char* layer, unsigned char* host
 {
     if (!m || !layer || !host) return FCN8S_ERR_BAD_ARG;
     if (!m->have_forward || !m->train_mode) return fail(m, FCN8S_ERR_STATE, "fcn8s_get_relu_record: no training forward pass has been run");
-    int b = 0, i = 0;
-    if (sscanf(layer, "conv%d_%d", &b, &i) != 2 || b < 1 || b > 5 || i < 1 || i >= kConvsPerBlock[b - 1])
+    const Layer* L = find_layer(m, layer);
+    if (!L || !in_block_next(m->layers, *L))
         return fail(m, FCN8S_ERR_NOT_FOUND, std::string("fcn8s_get_relu_record: '") + layer + "' is not a conv that feeds another conv");
-    auto it = m->acts.find(std::string("rb:") + layer);
-    if (it == m->acts.end() || !m->pass.rbits_ok.count(layer))
+    if (!L->rb || !m->pass.rbits_ok.count(layer))
         return fail(m, FCN8S_ERR_STATE, std::string("fcn8s_get_relu_record: the last forward pass kept no ReLU record of '") + layer + "' (the backward pass reads the activation itself)");
-    const int H = m->H >> (b - 1), W = m->W >> (b - 1), Cc = m->widths[b - 1], N = m->N;
+    const int H = L->h, W = L->w, Cc = L->cout, N = m->N;
     if (n != (size_t)N * H * W * Cc) return fail(m, FCN8S_ERR_SHAPE, std::string("ReLU record of '") + layer + "' has " + std::to_string((size_t)N * H * W * Cc) + " elements");
     // layout of wino_output_kernel / wino_input_kernel / wino_out_in_kernel: RW words per (tile, channel vector), bit (oy * M + ox) * VEC + lane-channel
-    const int tile = wino_tile_for(m, H, W, 3), vec = tile == 2 ? 4 : 2, RW = (tile * tile * vec + 31) / 32, C4 = Cc / vec;
+    const int tile = L->tile, vec = tile == 2 ? 4 : 2, RW = (tile * tile * vec + 31) / 32, C4 = Cc / vec;
     const int th = (H + tile - 1) / tile, tw = (W + tile - 1) / tile;
     const size_t words = wino_rbits_words(tile, N, H, W, Cc);
     std::vector<unsigned> w(words);
     HIPCHK(m, hipStreamSynchronize(m->stream));
-    HIPCHK(m, hipMemcpy(w.data(), it->second.p, words * sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIPCHK(m, hipMemcpy(w.data(), L->rb, words * sizeof(unsigned), hipMemcpyDeviceToHost));
     for (int nn = 0; nn < N; ++nn)
         for (int y = 0; y < H; ++y)
             for (int x = 0; x < W; ++x) {
@@ -3652,15 +3640,15 @@ int fcn8s_get_pool_routing(fcn8s_model* m, int block, unsigned char* host, size_
 {
     if (!m || !host || block < 1 || block > 5) return FCN8S_ERR_BAD_ARG;
     if (!m->have_forward || !m->train_mode) return fail(m, FCN8S_ERR_STATE, "fcn8s_get_pool_routing: no training forward pass has been run");
-    const int h = m->H >> (block - 1), w = m->W >> (block - 1), cw = m->widths[block - 1];
+    const Layer* last = nullptr;
+    for (const Layer& L : m->layers) if (L.block == block && L.last_of_block()) last = &L;
+    const int h = last->h, w = last->w, cw = last->cout;
     const size_t want = (size_t)m->N * (h / 2) * (w / 2) * cw;
     if (n != want) return fail(m, FCN8S_ERR_SHAPE, "pool routing of block " + std::to_string(block) + " has " + std::to_string(want) + " bytes");
-    char ix[16]; snprintf(ix, sizeof ix, "pidx%d", block);
-    unsigned char* d = (unsigned char*)A(m, ix);
-    if (!pool_backward_fused(m, block, m->pass.pool_fused[block - 1]) && !m->pass.pool_routed[block - 1]) {      // (pool_routed: the forward pool of bf16_train kept the bytes)
+    unsigned char* d = last->pidx;
+    if (!pool_backward_fused(*last, m->pass.pool_fused[block - 1]) && !m->pass.pool_routed[block - 1]) {      // (pool_routed: the forward pool of bf16_train kept the bytes)
         // the backward pass routes through maxpool_bwd_kernel on the block's last conv output (materialised in this case): same rule
-        char last[32]; snprintf(last, sizeof last, "conv%d_%d", block, kConvsPerBlock[block - 1]);
-        launch_maxpool_route(A(m, last), d, m->N, h, w, cw, m->stream);
+        launch_maxpool_route(last->y, d, m->N, h, w, cw, m->stream);
     }
     HIPCHK(m, hipStreamSynchronize(m->stream));
     HIPCHK(m, hipMemcpy(host, d, n, hipMemcpyDeviceToHost));
@@ -3871,7 +3859,7 @@ int fcn8s_op_conv3x3_winograd_fwd_bwd(void* stream, const float* x, const float*
     // backward: weight + bias gradient in the Winograd domain, then the data gradient (adjoint form for tile 6)
     hipMemsetAsync(dw, 0, (size_t)9 * Cin * Cout * sizeof(float), s);
     if (db) hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), s);
-    conv_wgrad(m, "op", x, dy, dw, db, N, H, W, Cin, Cout, 3, 1.f, s, 0, "op", tile >= 4, pooled ? (const unsigned char*)pidx.get() : nullptr);
+    conv_wgrad(m, "op", x, dy, dw, db, N, H, W, Cin, Cout, 3, 1.f, s, 0, "op", pooled ? (const unsigned char*)pidx.get() : nullptr);
     { DgradEpi e; e.w_fwd = w; e.lazy_wt = 1; e.addend = dx_addend;
       if (mask_mode) { e.mask = x; e.mask_scale = 1.f; }
       if (mask_mode == 2 && m->pass.rbits_ok.count("prev")) e.relu_bits_in = (const unsigned*)rbits.get();

@@ -2,13 +2,14 @@
 """Digests of what a build of libfcn8s_hip.so computes and launches, one JSON line per case: for comparing two BUILDS of the library that
 are meant to be the same program (a host-side refactor of csrc/model.hip).  Not a test: it needs the other build.
 
-    python tools/pass_digest.py OUT.jsonl
+    python tools/pass_digest.py OUT.jsonl [--full]
 
 A case is one fresh engine: two training steps (SGD, keep_prob 0.5, l2 1e-3), one eval_step, one predict(argmax=False).  Its line holds
 SHA-256 digests of the two losses, the logits of the second forward pass, every gradient of step 2, the flat parameters after step 2 and the
 predict output ("values", from an engine with option deterministic = 1), and the profile tables of step 2 and of the predict -- group ->
 [launches, flops, bytes], no times -- from a second engine with default options ("launches").  fp8_infer runs the eval and predict parts on a
-calibration made the way tests/test_state_coherence_gpu.py makes it.
+calibration made the way tests/test_state_coherence_gpu.py makes it.  The file keeps one SHA-256 per case over each of the two parts (a few
+hundred bytes per case: small enough to commit); --full writes the parts themselves, to find WHICH tensor or profile group moved.
 
 Run it with one build in place, then with the other (copy the .so into place as tools/ab_libs.sh does), and diff the two files.  Before it
 writes anything the tool checks that it could tell two builds apart: the launch tables of fuse_out_in 0 / 2 and of fc6_fft 0 / 1 differ,
@@ -39,6 +40,9 @@ VARIANTS = (("fuse_out_in", 0), ("fuse_out_in", 2), ("fuse_dgrad_dout", 0), ("co
             ("fc6_fft", 0), ("bf16_acts", 0), ("bf16_fuse_pool", 0), ("keep_output_gradients", 1))
 # the options that decide something in bf16_fwd (its conv1 / conv2 blocks and all of its backward pass run through Winograd)
 BF16_FWD_VARIANTS = ("fuse_out_in", "fuse_dgrad_dout", "conv1_in_transform", "winograd_tile", "keep_output_gradients")
+# the options that move a layer from one route to another (csrc/conv_route.h), fp32 and bf16_fwd.  winograd_min_cin = 128 with WIDTHS: direct blocks
+# 1-2 and a direct conv3_1 in front of a Winograd conv3_2 -- a "wv:" / "rb:" slot exists for one neighbour only
+ROUTE_VARIANTS = ({"winograd_min_cin": 128}, {"winograd_min_cin": 0}, {"winograd_tile": 2}, {"winograd_tile_hires": 4, "winograd_hires_pixels": 8000})
 
 
 def sha(a):
@@ -140,9 +144,13 @@ def cases():
             yield p, s, WIDTHS, {}
     yield 'fp32', VARIANT_SHAPE, DEFAULT_WIDTHS, {}
     yield 'fp32', VARIANT_SHAPE, ODD_WIDTHS, {}
+    yield 'fp32', VARIANT_SHAPE, ODD_WIDTHS, {"fuse_dgrad_dout": 0}
     for k, v in VARIANTS:
         for p in ('fp32', 'bf16_train') + (('bf16_fwd',) if k in BF16_FWD_VARIANTS else ()):
             yield p, VARIANT_SHAPE, WIDTHS, {k: v}
+    for options in ROUTE_VARIANTS:
+        for p in ('fp32', 'bf16_fwd'):
+            yield p, VARIANT_SHAPE, WIDTHS, dict(options)
 
 
 def name_of(p, s, widths, options):
@@ -150,7 +158,11 @@ def name_of(p, s, widths, options):
     return "%s/%dx%dx%d%s%s" % (p, s[0], s[1], s[2], w, "".join("/%s=%d" % kv for kv in sorted(options.items())))
 
 
-def main(path):
+def compact(line):
+    return {"case": line["case"], **{k: hashlib.sha256(json.dumps(line[k], sort_keys=True).encode()).hexdigest() for k in ("values", "launches")}}
+
+
+def main(path, full=False):
     lines = {}
     for p, s, widths, options in cases():
         name = name_of(p, s, widths, options)
@@ -165,9 +177,9 @@ def main(path):
         assert other[k] != lines[base]["values"][k], ("another seed, the same digest", k)
     with open(path, "w") as f:
         for name in sorted(lines):
-            f.write(json.dumps(lines[name], sort_keys=True) + "\n")
+            f.write(json.dumps(lines[name] if full else compact(lines[name]), sort_keys=True) + "\n")
     print("%d cases -> %s" % (len(lines), path))
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    main(sys.argv[1], "--full" in sys.argv[2:])
