@@ -117,4 +117,79 @@ inline bool pool_in_transform(const RouteOpts& o, const ConvShape& last, bool ha
     return o.wino_min_cin > 0 && last.Cout >= o.wino_min_cin && o.scratch && wino_tile_for(o, last.H, last.W, 3) >= 4 && last.Cout % 64 == 0 && has_prev && keeps_v(o, last);
 }
 
+// ---- FCN8S_PREC_BF16_TRAIN: which fp32 tensor a pass keeps, which it skips -------------------------------------------------------------------------
+// The mode runs every convolution but conv1_1 on the bf16 kernels (gemm_bf16.hip), forward and backward, and hands an activation or a gradient on as
+// the READER's padded bf16 copy.  The forward pass may skip an fp32 tensor only if every later reader provably takes the bf16 form: the rules below
+// are both sides of that promise -- what forward() skips, and what backward_blocks / conv_wgrad / conv_dgrad will ask for
+// (tests/test_bf16_route_host.py checks the implications between them).
+// PRECONDITION of the mode, stated once: every one of the seven widths is a multiple of 64 (fcn8s_set_precision refuses the mode otherwise) and every
+// kernel size is odd (fcn8s_create).  conv1_1 (3 input channels, padded to 4) is therefore the ONLY layer with Cin % 64 != 0, and a block's last conv
+// always has a conv of the same width in front of it: Cin == Cout.
+// The per-launch options the rules read (bf16_opts() in model.hip fills it, per pass).  None of them drops the arena, so no fact derived from them
+// is stored in the layer table: the call sites evaluate the rules in every pass.
+struct Bf16Opts {
+    bool acts = true;                // option bf16_acts: a conv -> conv activation is kept only as the consumer's padded bf16 copy
+    bool fuse_pool = true;           // option bf16_fuse_pool: the pools keep routing bytes and read / write the bf16 copies
+    bool conv1_tiled = true;         // option conv1_tiled: conv1_1 on the spatial-tile kernel (the only one that writes a bf16 copy)
+    bool copies = true;              // the pass makes per-layer copies at all: training, or option bf16_infer_copies
+};
+// The one width / kernel-size test: the bf16 convolution and weight-gradient kernels take the layer (gemm_bf16.hip's own checks stay the kernels'
+// contract).  forward(), backward_blocks, conv_wgrad ask it of the forward shape, conv_dgrad of the transposed one.
+inline bool bf16_kernels_take(const ConvShape& s) { return s.Cin % 64 == 0 && s.Cout % 64 == 0 && s.K % 2 == 1; }
+// pool3 / pool4 also feed the fp32 skip heads (1-based block): their blocks keep the fp32 tensors.  forward()'s conv, pool and fp8 stages ask.
+inline bool pool_feeds_skip(int block) { return block == 3 || block == 4; }
+// The 32-bit per-lane byte offsets of the weight-gradient kernels span TWO 32-channel planes of a padded copy (launch_wgrad_bf16's limit, asked by
+// forward() before anything is launched): a plane of plane_elems bf16 elements must stay below 4 GiB.  Kept as found, including that it is vacuous
+// in a library built with A_PLANES = 0 (plane stride 0) -- a known finding, not this rule's to fix.
+inline bool bf16_plane_fits(long long plane_elems) { return (double)plane_elems * 2.0 + 65536.0 < 4294967296.0; }
+
+// -- forward: a convolution's output --
+// conv1_1 writes conv1_2's padded bf16 input copy and no fp32 tensor (the 64-wide tile kernel on a map of whole 8 x 16 tiles; the caller has
+// checked that conv1_1 takes the gather kernel at all).  conv1_2's gradients are then the tensor's only readers, in its bf16 form.
+inline bool conv1_writes_bf16_only(const Bf16Opts& o, const ConvShape& conv1_1, const ConvShape& next)
+{
+    return o.copies && o.acts && o.conv1_tiled && conv1_1.H % 8 == 0 && conv1_1.W % 16 == 0 && conv1_1.Cout % 64 == 0 && bf16_kernels_take(next);
+}
+// a conv's epilogue writes the in-block consumer's padded bf16 input copy (has_next: there is such a consumer)
+inline bool out_bf16_copy(const Bf16Opts& o, bool has_next) { return o.copies && o.acts && has_next; }
+// ... and that copy is the output's only form: the fp32 tensor is not written.  Its readers are the consumer's weight gradient (its input) and data
+// gradient (the ReLU mask: the sign of the copy) -- both must fit the bf16 kernels, a fallback would look for the fp32 tensor.
+inline bool out_bf16_only(const Bf16Opts& o, const ConvShape& l, const ConvShape& consumer)
+{
+    return out_bf16_copy(o, true) && bf16_kernels_take(l) && bf16_kernels_take(consumer);
+}
+// A block's LAST conv writes only the bf16 input copy of its pool ("pool<b>in"): the pool is its only reader, and pool1 / pool2 / pool5 are read by
+// bf16 convolutions only (consumer: the next block's first conv, or fc6).
+inline bool pool_in_bf16(const Bf16Opts& o, const ConvShape& last, const ConvShape& consumer, int block)
+{
+    return o.copies && o.acts && o.fuse_pool && !pool_feeds_skip(block) && bf16_kernels_take(last) && bf16_kernels_take(consumer);
+}
+// -- forward: a block's pool --
+// the pool keeps its routing bytes (the backward pass reads one byte per window instead of the block's last activation)
+inline bool pool_routes(const Bf16Opts& o, const ConvShape& last) { return o.copies && o.fuse_pool && bf16_kernels_take(last); }
+// ... and writes its consumer's padded bf16 input copy itself
+inline bool pool_out_bf16(const Bf16Opts& o, const ConvShape& last, const ConvShape& consumer) { return pool_routes(o, last) && o.acts && bf16_kernels_take(consumer); }
+// ... as the output's only form (no fp32 pool tensor)
+inline bool pool_out_bf16_only(const Bf16Opts& o, const ConvShape& last, const ConvShape& consumer, int block)
+{
+    return pool_out_bf16(o, last, consumer) && !pool_feeds_skip(block);
+}
+// ... from the last conv's bf16 copy (pool_in_bf16): that kernel has no fp32 output, so exactly where the output is bf16 only.  The rule's half;
+// the site adds the run-time half -- the copy exists and this pass filled it.
+inline bool pool_reads_bf16(const Bf16Opts& o, const ConvShape& last, const ConvShape& consumer, int block) { return pool_out_bf16_only(o, last, consumer, block); }
+// -- forward: fc6 / fc7 --  fc7's padded input copy comes out of fc6's epilogue (else: a conversion pass of fc6's fp32 output)
+inline bool fc7_in_from_fc6(const Bf16Opts& o) { return o.copies && o.acts; }
+
+// -- backward --
+// Layer l's output gradient exists only as its padded bf16 copy: the data gradient of `producer` (the next conv on l's map) writes the copy and
+// l's bias gradient instead of the fp32 tensor.  Both gradients of l then read the copy: never conv1_1, whose weight gradient is exact fp32 and
+// reads the fp32 tensor.  backward_blocks asks, conv_dgrad acts on it (DgradEpi::yb_only).
+inline bool dy_bf16_only(const Bf16Opts& o, const ConvShape& l, bool l_is_conv1_1, const ConvShape& producer)
+{
+    return o.acts && !l_is_conv1_1 && l.K == 3 && producer.K == 3 && bf16_kernels_take(l) && bf16_kernels_take(transposed(l)) && bf16_kernels_take(transposed(producer));
+}
+// The pool's backward kernel writes the bf16 dZ copy and the bias gradient of the block's last conv and no fp32 dZ: both of that conv's gradients
+// take the copy (Cin == Cout: see the precondition).  backward_blocks asks.
+inline bool pool_bwd_writes_bf16(const Bf16Opts& o, const ConvShape& last) { return o.fuse_pool && bf16_kernels_take(last); }
+
 }  // namespace fcn8s

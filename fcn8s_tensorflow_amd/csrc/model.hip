@@ -72,8 +72,8 @@ const int kConvsPerBlock[5] = {2, 2, 3, 3, 3};
 // long as the arena it was planned with: every option RouteOpts reads -- winograd_min_cin, winograd_tile, winograd_tile_hires,
 // winograd_hires_pixels, winograd_fc6 -- drops the arena in fcn8s_set_option, fcn8s_set_precision drops it when a direct mode takes the first and
 // the last over, wino_force_tile belongs to the bare op models alone, and no pass starts without ensure_workspace.  Options that pick a kernel per
-// launch without dropping the arena (conv1_in_transform, ...) and what only a pass knows (train, the precision branch) are never stored here: the
-// call sites AND them with the stored fact.
+// launch without dropping the arena (conv1_in_transform, ...; bf16_train's Bf16Opts) and what only a pass knows (train, the precision branch) are never
+// stored here: the call sites AND them with the stored fact, and ask the bf16_train rules in every pass.
 struct Layer {
     char name[8], pool_name[8], pool_in[12];     // "conv3_2" / "fc6"; the last conv of a block: "pool3" and the key of its pool's bf16 / e4m3 input copy, "pool3in"
     int block, pos, nconv;                       // 1-based VGG block, position in it, convs in it (fc6, fc7: blocks 6, 7 of one layer each)
@@ -421,7 +421,7 @@ struct DgradEpi : ConvEpi {
     int lazy_wt = 0;                                     // `w` is still to be filled from w_fwd (flip + transpose) if no path that reads w_fwd is taken
     float* dm_out = nullptr; const char* dm_out_layer = nullptr;   // adjoint path: write dM of the producing layer here instead of its dZ into y, and promise it to that layer's weight gradient (pass.dm_prefilled)
     const char* yb_layer = nullptr; int yb_K = 3;        // bf16_train: the layer whose output gradient this launch produces, and its kernel size
-    bool yb_only = false;                                // ... both of that layer's gradients take its bf16 copy: write the copy, the fp32 tensor may stay unwritten
+    bool yb_only = false;                                // ... both of that layer's gradients take its bf16 copy (dy_bf16_only): write the copy, the fp32 tensor stays unwritten
 };
 
 // 3x3 SAME conv through Winograd F(tile x tile, 3x3): filter transform, input transform, (tile+2)^2 batched GEMMs
@@ -466,6 +466,12 @@ RouteOpts route_opts(const fcn8s_model* m)
     return o;
 }
 int wino_tile_for(const fcn8s_model* m, int H, int W, int K = 3) { return m ? wino_tile_for(route_opts(m), H, W, K) : 0; }
+// ... and the per-launch options of its bf16_train rules, for a training (train) or an evaluation / prediction pass of a model in that mode
+Bf16Opts bf16_opts(const fcn8s_model* m, bool train)
+{
+    Bf16Opts o; o.acts = m->bf16_acts != 0; o.fuse_pool = m->bf16_fuse_pool != 0; o.conv1_tiled = m->conv1_tiled != 0; o.copies = train || m->bf16_infer_copies != 0;
+    return o;
+}
 long long wino_tiles(int tile, int N, int H, int W) { return (long long)N * ((H + tile - 1) / tile) * ((W + tile - 1) / tile); }
 struct WinoEpi { const float* bias = nullptr; const float* addend = nullptr; const float* mask = nullptr; float mask_scale = 1.f;
                  int relu = 0; int dropout = 0; float keep = 1.f; unsigned long long seed = 0; unsigned int stream_id = 0; float* pool = nullptr; unsigned char* pidx = nullptr;
@@ -710,7 +716,7 @@ void conv_dgrad(fcn8s_model* m, const char* group, const float* x, const float* 
                 int N, int H, int W, int Cin, int Cout, int K, const DgradEpi& e, hipStream_t s, const char* layer = nullptr)
 {
     const bool bf16_step = bf16_train_mode(m) && m->train_mode && layer;
-    if (bf16_step && e.w_fwd && e.alpha == 1.f && Cin % 32 == 0 && Cout % 64 == 0) {
+    if (bf16_step && e.w_fwd && e.alpha == 1.f && bf16_kernels_take(ConvShape{N, H, W, Cin, Cout, K})) {          // (the transposed shape: dY -> dX)
         // FCN8S_PREC_BF16_TRAIN: the SAME convolution of the padded bf16 copy of dY with the flipped kernel, wt[ci][(flipped tap, co)] bf16, on
         // conv_bf16_256_kernel; fp32 accumulate, fp32 epilogue (skip-path addend, the ReLU / dropout mask of the layer's input).
         const size_t wneed = (size_t)K * K * Cin * Cout;
@@ -725,9 +731,9 @@ void conv_dgrad(fcn8s_model* m, const char* group, const float* x, const float* 
                 auto xi = m->xg16.find(layer);
                 if (xi != m->xg16.end() && xi->second) { g.mask16 = xi->second + g16_off(bf16_guard_rows(3, W + 2), Cout); g.mask16_ps = g16_ps(N, H, W, 3); }
             }
-            // this gradient is the output gradient of layer e.yb_layer (same map).  If that layer's gradients read nothing else (option bf16_acts), this kernel's
-            // epilogue writes its padded bf16 copy instead of the fp32 gradient, and takes its column sums, that layer's bias gradient, from the fp32 values
-            const bool only16 = e.yb_layer && e.yb_only && m->bf16_acts && K == 3 && e.yb_K == 3 && Cout % 64 == 0;
+            // this gradient is the output gradient of layer e.yb_layer (same map).  If that layer's gradients read nothing else (dy_bf16_only, asked by the caller), this
+            // kernel's epilogue writes its padded bf16 copy instead of the fp32 gradient, and takes its column sums, that layer's bias gradient, from the fp32 values
+            const bool only16 = e.yb_layer && e.yb_only;
             if (only16) { g.yb = g16_for(m, m->dyg16, e.yb_layer, N, H, W, Cout, e.yb_K, s); g.yb_pad = (e.yb_K - 1) / 2; g.yb_ps = g16_ps(N, H, W, e.yb_K); }
             long long prow = 0;
             if (g.yb) {
@@ -749,9 +755,11 @@ void conv_dgrad(fcn8s_model* m, const char* group, const float* x, const float* 
                 }
                 return;
             }
-            if (g.colpart) { defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient was refused by the flat-position kernel", layer); return; }
+            if (g.colpart) { defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient was refused by the flat-position kernel", layer); return; }      // (a refused launch: unreachable by rule, kept as the guard)
         }
     }
+    // Unreachable by rule (dy_bf16_only / out_bf16_only / conv1_writes_bf16_only imply bf16_kernels_take of this launch: tests/test_bf16_route_host.py); kept as
+    // the guards for an allocation failure and a refused launch.
     if (bf16_step && m->pass.dy_bf16_only.count(layer)) {
         defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient could not run on the bf16 kernel and its fp32 output gradient was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return;
     }
@@ -888,7 +896,7 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
     const double rc = a.Areal;
     const double flops = 2.0 * a.P * K * K * rc * Cout;
     const double bytes = 4.0 * (a.P * rc + (double)a.P * Cout + (double)K * K * rc * Cout);
-    if (bf16_train_mode(m) && m->train_mode && layer && !real_cin && alpha == 1.f && Cin % 64 == 0 && Cout % 64 == 0) {
+    if (bf16_train_mode(m) && m->train_mode && layer && !real_cin && alpha == 1.f && bf16_kernels_take(shape)) {
         // FCN8S_PREC_BF16_TRAIN: dW[tap] = (padded bf16 input, moved by the tap)^T (padded bf16 dY), fp32 accumulate (gemm_bf16.hip: wgrad_bf16_kernel);
         // the bias gradient is the exact fp32 column sum of dY
         auto it = m->xg16.find(layer);
@@ -908,10 +916,11 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
                     if (db && !db_done) { ProfScope ps(m, "colsum", 0, 4.0 * a.P * Cout); launch_colsum(dz, db, a.P, Cout, s); }
                     return;
                 }
-                if (db_done) { defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's weight-gradient launch refused its shape after the bias gradient was taken", layer); return; }
+                if (db_done) { defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's weight-gradient launch refused its shape after the bias gradient was taken", layer); return; }      // (a refused launch: unreachable by rule, kept as the guard)
             }
         }
     }
+    // Unreachable by rule (whoever put the layer into either set asked bf16_kernels_take of this shape); kept as the guard for an allocation failure and a refused launch.
     if (bf16_train_mode(m) && m->train_mode && layer && (m->pass.in_bf16_only.count(layer) || m->pass.dy_bf16_only.count(layer))) {
         defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's weight gradient could not run on the bf16 kernel and its fp32 input was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return;
     }
@@ -1334,13 +1343,18 @@ bool pool_backward_fused(const Layer& last, bool pooled_by_transform) { return p
 // One SAME convolution with bf16-rounded operands and fp32 accumulation on the bf16 MFMA (gemm_bf16.hip), fp32 bias / ReLU / dropout epilogue,
 // fp32 output: fc6 / fc7 of FCN8S_PREC_BF16_FC, and conv3_1 .. conv5_3 as well in FCN8S_PREC_BF16_FWD.  Returns false if no bf16 kernel
 // takes the shape (the caller then uses the fp32 path).
-bool bf16_conv_layer(fcn8s_model* m, const char* tag, const Layer& L, const float* in, float* out,
-                     int drop, float keep_prob, uint32_t stream_id, hipStream_t s, bool allow_small = true,
-                     const unsigned short* xb_ready = nullptr,          // the padded bf16 copy of `in`, already made (256 x 256 kernel only)
-                     bool any_shape = false,                            // bf16_train: 64- / 128-column tiles and a partial last row tile are taken too
-                     unsigned short* yb = nullptr, int yb_pad = 0,      // ... and the consumer's padded bf16 copy of the output is written by the epilogue
-                     long long xb_ps = 0, long long yb_ps = 0)          // plane strides of xb_ready / yb (bf16_train's per-layer copies: channel-chunk planes), 0 = [rows][C]
+struct Bf16LayerIo {
+    const unsigned short* xb = nullptr;                  // the padded bf16 copy of `in`, already made (256 x 256 kernel only)
+    unsigned short* yb = nullptr; int yb_pad = 0;        // bf16_train: the consumer's padded bf16 copy of the output, written by the epilogue
+    long long xb_ps = 0, yb_ps = 0;                      // plane strides of xb / yb (bf16_train's per-layer copies: channel-chunk planes), 0 = [rows][C]
+    bool any_shape = false;                              // bf16_train: 64- / 128-column tiles and a partial last row tile are taken too
+    bool allow_small = true;                             // the 128 x 128 kernel may take what the 256 x 256 one does not
+    int drop = 0; float keep_prob = 1.f; uint32_t stream_id = 0;      // dropout behind the ReLU (fc6 / fc7)
+};
+bool bf16_conv_layer(fcn8s_model* m, const char* tag, const Layer& L, const float* in, float* out, hipStream_t s, const Bf16LayerIo& io = Bf16LayerIo())
 {
+    const unsigned short* xb_ready = io.xb; unsigned short* yb = io.yb; const int yb_pad = io.yb_pad, drop = io.drop; const long long xb_ps = io.xb_ps, yb_ps = io.yb_ps;
+    const bool any_shape = io.any_shape, allow_small = io.allow_small; const float keep_prob = io.keep_prob; const uint32_t stream_id = io.stream_id;
     const int N = m->N, h = L.h, w = L.w, cin = L.cin, cout = L.cout, k = L.K;
     const float *wk = m->d_params + L.w_off, *bias = m->d_params + L.b_off;
     const int K = k * k * cin;
@@ -1594,6 +1608,236 @@ static int fp8_conv(fcn8s_model* m, const char* group, const char* layer, const 
     return FCN8S_OK;
 }
 
+// ---- forward(): one function per stage of the encoder.  forward() walks the layer table and calls them ------------------------------------------------
+// What a stage reports: a status, whether it ran the layer at all (false: the next candidate's turn), whether the block's pool came out of it.
+struct FwdStep { int rc = FCN8S_OK; bool done = true, pooled = false; };
+static FwdStep fwd_failed(int rc) { return FwdStep{rc}; }
+static FwdStep fwd_declined() { return FwdStep{FCN8S_OK, false}; }
+
+// FCN8S_PREC_FP8_INFER, every conv but conv1_1: the output goes to the next conv's e4m3 copy, to the copy the block's pool reads (blocks 1, 2, 5: codes with the exponent of
+// the pool's consumer -- amax(pool) = amax(conv), q is monotone: the byte-max pool is exact), or to fp32 (blocks 3, 4: pool3 / pool4 feed the skip heads)
+static FwdStep fwd_conv_fp8(fcn8s_model* m, Layer& L, const float* x)
+{
+    hipStream_t s = m->stream; const int N = m->N;
+    const Layer* nx = in_block_next(m->layers, L);
+    const char* nxk = nx ? nx->name : (!pool_feeds_skip(L.block) ? L.pool_in : nullptr);
+    const Q8Buf* yq = nullptr;
+    if (nxk) {
+        const char* cons = kFp8Layers[fp8_layer(L.name) + 1];           // the next FP8 layer: the next conv, or the pool's consumer
+        yq = q8_for(m, nxk, N, L.h, L.w, L.cout, 3, fp8_ex(m, cons), s);
+        if (!yq) return fwd_failed(fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed"));
+    }
+    const int rc = fp8_conv(m, "conv3x3_fwd_fp8", L.name, x, N, L.h, L.w, L.cin, L.cout, 3, yq ? nullptr : L.y, yq, 1, s); if (rc) return fwd_failed(rc);
+    if (yq) { m->pass.q8_filled.insert(nxk); m->pass.y_unwritten.insert(L.name); }
+    return FwdStep{};
+}
+
+// conv1_1's special cases (L.first()): inside conv1_2's input transform, or the 64-wide gather kernel.  Declines otherwise: conv_fwd's direct path.
+static FwdStep fwd_conv1_1(fcn8s_model* m, Layer& L, const float* x, bool train, const Bf16Opts& bo)
+{
+    hipStream_t s = m->stream; const int N = m->N, h = L.h, w = L.w, cout = L.cout; const char* nm = L.name;
+    const Layer* nx = in_block_next(m->layers, L); const float* bias = m->d_params + L.b_off;
+    if (L.conv1_in_next && m->conv1_in_transform && !bf16_train_mode(m) && !fp8_mode(m)) {
+        // conv1_1's only reader is conv1_2's F(6x6,3x3) input transform: that transform evaluates conv1_1 on its own patches, straight from the
+        // image (winograd.hip: wino_input_conv1_kernel), writes conv1_2's V -- into the buffer conv_fwd will look for it in -- and, in training,
+        // the ReLU record the backward pass masks with.  conv1_1's 134 MB per image are never written or read.
+        if (!train || (nx->wv && L.rb)) {
+            float* vdst = nx->wv ? nx->wv : m->d_wino_v; const long long T = wino_tiles(6, N, h, w);
+            ProfScope ps(m, "wino_transform", 0, 4.0 * (4.0 * N * h * w + 64.0 * T * 64.0) + (train ? 8.0 * N * h * w : 0.0), nm);
+            launch_wino_input_conv1(x, m->d_w1pad, bias, vdst, N, h, w, s, train ? L.rb : nullptr);
+            if (train) m->pass.rbits_ok.insert(nm);
+            m->pass.fwd_v.give(nx->name); m->pass.y_unwritten.insert(nm);
+            return FwdStep{};
+        }
+    }
+    if (cout != 64) return fwd_declined();          // write-bound gather kernel (igemm.hip: conv1_glds_kernel)
+    // bf16_train: conv1_2 reads this layer as its padded bf16 copy and nobody else reads it (the mask of conv1_2's data gradient is the sign of that copy): the tile kernel writes the copy and no fp32 tensor
+    unsigned short* y16 = nullptr;
+    if (bf16_train_mode(m) && nx && conv1_writes_bf16_only(bo, L.shape(N), nx->shape(N))) y16 = xg16_for(m, nx->name, N, h, w, cout, 3, s);
+    ProfScope ps(m, "conv1_1_fwd", 2.0 * N * h * w * 27.0 * cout, 4.0 * N * h * w * 3.0 + (y16 ? 2.0 : 4.0) * N * h * w * cout, nm);
+    if (!launch_conv1_fwd(x, m->d_w1pad, bias, y16 ? nullptr : L.y, m->d_w1pad + 12 * 4 * (size_t)cout, N, h, w, cout, m->conv1_tiled, s, y16, g16_ps(N, h, w, 3))) return fwd_declined();
+    if (y16) { m->pass.xg16_filled.insert(nx->name); m->pass.y_unwritten.insert(nm); m->pass.in_bf16_only.insert(nx->name); }
+    return FwdStep{};
+}
+
+// FCN8S_PREC_BF16_TRAIN: every convolution but conv1_1 (3 input channels) as a direct convolution with bf16-rounded operands; the
+// training pass keeps the layer's padded bf16 input copy for its weight gradient (the convolution starts from that copy)
+static FwdStep fwd_conv_bf16_train(fcn8s_model* m, Layer& L, const float* x, const Bf16Opts& bo)
+{
+    hipStream_t s = m->stream; const int N = m->N, h = L.h, w = L.w, cin = L.cin, cout = L.cout; const char* nm = L.name;
+    const Layer* nx = in_block_next(m->layers, L); const ConvShape sh = L.shape(N);
+    unsigned short* xb = bo.copies ? xg16_for(m, nm, N, h, w, cin, 3, s) : nullptr;
+    if (xb && !m->pass.xg16_filled.count(nm)) {
+        ProfScope ps(m, "bf16_convert", 0, 4.0 * N * h * w * cin + 2.0 * N * (h + 2) * (w + 2) * cin); launch_f32_to_bf16_padded(x, xb, N, h, w, cin, 1, s, g16_ps(N, h, w, 3));
+    }
+    // the next convolution of the block reads this output as ITS padded bf16 input: this kernel's epilogue writes that copy
+    unsigned short* yb = nullptr; const char* nxk = "";
+    if (out_bf16_copy(bo, nx != nullptr)) { nxk = nx->name; yb = xg16_for(m, nxk, N, h, w, cout, 3, s); }
+    // the block's LAST convolution is read by its pool only: the pool then takes this output as a bf16 copy of the kernel's own geometry ("pool<b>in"),
+    // picks its maxima among the bf16 values (what bf16(max of the fp32 values) is anyway) and no fp32 tensor is written
+    const bool pool16 = L.last_of_block() && pool_in_bf16(bo, sh, m->layers[L.next].shape(N), L.block);
+    if (pool16) { nxk = L.pool_in; yb = xg16_for(m, nxk, N, h, w, cout, 3, s); }
+    // ... and if the copy is the output's only reader, the fp32 tensor is not written at all.  (yb without pool16: the in-block consumer's copy.)
+    const bool only16 = yb && (pool16 || out_bf16_only(bo, sh, nx->shape(N)));
+    // (launch_wgrad_bf16's limit, applied HERE, before anything is launched)
+    if (!bf16_plane_fits(g16_ps(N, h, w, 3)))
+        return fwd_failed(fail(m, FCN8S_ERR_SHAPE, std::string("bf16_train: a 32-channel plane of the padded bf16 copy of ") + nm + "'s input would reach 4 GiB at this batch size; use a smaller batch per GPU"));
+    Bf16LayerIo io; io.allow_small = false; io.any_shape = true;
+    io.xb = xb; io.xb_ps = g16_ps(N, h, w, 3); io.yb = yb; io.yb_pad = 1; io.yb_ps = g16_ps(N, h, w, 3);
+    // (unreachable by rule -- every width is a multiple of 64: bf16_kernels_take -- kept as the guard for an allocation failure and a refused launch)
+    if (!bf16_conv_layer(m, "conv3x3_fwd_bf16", L, x, only16 ? nullptr : L.y, s, io)) return fwd_failed(fail(m, FCN8S_ERR_SHAPE, std::string("bf16_train: ") + nm + " does not fit the bf16 convolution kernel"));
+    if (yb) m->pass.xg16_filled.insert(nxk);
+    if (only16) { m->pass.y_unwritten.insert(nm); if (!pool16) m->pass.in_bf16_only.insert(nxk); }
+    return FwdStep{};
+}
+
+// FCN8S_PREC_BF16_FWD: conv3_1 .. conv5_3 as direct convolutions with bf16-rounded operands on the 256 x 256 bf16 kernel (the output is materialised, the block's pool
+// runs as its own kernel, ReLU masks come from the activations); the backward pass stays in the Winograd domain, so the transformed input and this step's filter bank
+// are made here.  Declines if no bf16 kernel takes the shape.
+static FwdStep fwd_conv_bf16_fwd(fcn8s_model* m, Layer& L, const float* x, bool train)
+{
+    hipStream_t s = m->stream; const int N = m->N;
+    // training: the transform that keeps this layer's V for the weight gradient runs first and writes the padded bf16 copy of the
+    // input on the way (the convolution then starts from it; without a kept V, or in inference, the convolution converts its input itself)
+    unsigned short* xb = train ? xb_by_transform(m, L, N, s) : nullptr;
+    auto operands = [&]() {
+        // the previous conv of the block came from the bf16 kernel too (no ReLU record): this transform of its output writes one
+        const Layer* pv = in_block_prev(m->layers, L);
+        unsigned* irb = (pv && pv->rb && !m->pass.rbits_ok.count(pv->name)) ? pv->rb : nullptr;
+        wino_backward_operands(m, L.name, x, m->d_params + L.w_off, N, L.h, L.w, L.cin, L.cout, 3, s, irb, irb ? pv->name : nullptr, xb);
+    };
+    if (xb) operands();
+    Bf16LayerIo io; io.allow_small = false; io.xb = xb;
+    if (!bf16_conv_layer(m, "conv3x3_fwd_bf16", L, x, L.y, s, io)) return fwd_declined();
+    if (train && !xb) operands();
+    return FwdStep{};
+}
+
+// Every other conv: conv_fwd picks Winograd or the direct path (conv_route.h); this builds the epilogue the layer table asks for
+static FwdStep fwd_conv(fcn8s_model* m, Layer& L, const float* x, bool train)
+{
+    const Layer* nx = in_block_next(m->layers, L);
+    FwdEpi e; e.bias = m->d_params + L.b_off; e.relu = 1;
+    if (train && L.rb_writer == RbWriter::self) e.relu_bits_out = L.rb;                              // its output is the next conv's input
+    if (train && L.pos == 2 && m->layers[L.prev].rb_writer == RbWriter::consumer) {                  // input = conv1_1, made by the gather kernel
+        e.in_relu_bits_out = m->layers[L.prev].rb; e.in_layer = m->layers[L.prev].name;
+    }
+    if (L.last_of_block()) {
+        e.pool_out = L.pool;
+        if (train) e.pool_idx = L.pidx;
+        // The block's last conv output feeds only the pool.  If the output transform writes the pool (and, for training, the backward
+        // pass routes through the argmax bytes), the full-resolution tensor is never read again and is not written at all
+        // (2.15 GB for conv1_2 at 16 x 1024x512); fcn8s_get_activation of such a layer then returns stale data.
+        e.skip_y = !train || L.pool_in_transform;
+    }
+    if (L.out_in_next && m->fuse_out_in && !(bf16_fwd_mode(m) && L.block >= 3) && !bf16_train_mode(m) && !fp8_mode(m) && (!train || e.relu_bits_out)) {
+        // this conv and the next one both run through F(6x6,3x3) on the same tile grid: its output transform writes the next conv's
+        // transformed input directly (training: into the buffer kept for that conv's weight gradient) and its own output never exists.
+        // The buffer the next conv will read its V from is the one kept for its weight gradient if the workspace has one (whether or
+        // not this pass trains), else the shared scratch.  (out_in_fused: the next conv keeps V -- a direct weight gradient would read
+        // the activation that no longer exists.)
+        e.next_v = nx->wv ? nx->wv : m->d_wino_v; e.next_layer = nx->name;
+    }
+    FwdStep st;
+    const float* wt = L.first() ? m->d_w1pad : m->d_params + L.w_off;
+    st.pooled = conv_fwd(m, L.first() ? "conv1_1_fwd" : "conv3x3_fwd", x, wt, L.y, m->N, L.h, L.w, L.cin, L.cout, 3, e, m->stream, L.real_cin, L.name);
+    return st;
+}
+
+// A block's pool behind its last conv L (cons: the pool's consumer, the next block's first conv or fc6) unless that conv's output transform wrote it
+// (pooled): fp8_infer's byte max, bf16_train's routed pool on the bf16 copies, or the plain kernel with or without routing bytes
+static FwdStep fwd_pool(fcn8s_model* m, const Layer& L, const Layer& cons, const float* x, bool train, bool fp8, bool pooled, const Bf16Opts& bo)
+{
+    hipStream_t s = m->stream; const int N = m->N, b = L.block - 1, h = L.h, w = L.w, cin = L.cout; const char* pn = L.pool_name;
+    if (fp8) {
+        m->pass.pool_fused[b] = false; m->pass.pool_routed[b] = false;
+        if (!pool_feeds_skip(L.block)) {
+            // byte max of the last conv's e4m3 copy straight into the consumer's copy (conv<b+2>_1, pad 1; fc6, pad (k - 1) / 2)
+            const int ck = cons.K;
+            Q8Buf* yq = q8_for(m, cons.name, N, h / 2, w / 2, cin, ck, fp8_ex(m, cons.name), s);
+            if (!yq) return fwd_failed(fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed"));
+            const Q8Buf& xi = m->q8[L.pool_in];
+            { ProfScope ps(m, "maxpool_fwd_fp8", 0, 1.25 * N * h * w * cin); launch_maxpool_fp8(xi.p, xi.ps, yq->p, yq->ps, N, h, w, cin, (ck - 1) / 2, s); }
+            m->pass.q8_filled.insert(cons.name); m->pass.y_unwritten.insert(pn);
+        } else { ProfScope ps(m, "maxpool_fwd", 0, 4.0 * N * h * w * cin * 1.25); launch_maxpool_fwd(x, L.pool, N, h, w, cin, s); }
+        return FwdStep{};
+    }
+    m->pass.pool_fused[b] = pooled && train;
+    m->pass.pool_routed[b] = false;
+    const ConvShape last = L.shape(N), csh = cons.shape(N);
+    if (!pooled && bf16_train_mode(m) && pool_routes(bo, last)) {
+        // bf16_train, training: the pool keeps its routing bytes (the backward pass reads one byte per window instead of the block's last activation)
+        // and writes the consumer's padded bf16 copy itself -- conv<b+2>_1 (pad 1) or fc6 (pad 3); pool1, pool2 and pool5 have no other reader, so
+        // with option bf16_acts their fp32 tensors are not written (pool3 / pool4 feed the fp32 skip heads)
+        const int ck = cons.K;
+        unsigned short* yb = pool_out_bf16(bo, last, csh) ? xg16_for(m, cons.name, N, h / 2, w / 2, cin, ck, s) : nullptr;
+        const bool only16 = yb && pool_out_bf16_only(bo, last, csh, L.block);
+        auto pi = m->xg16.find(L.pool_in);
+        const bool in16 = only16 && pool_reads_bf16(bo, last, csh, L.block) && pi != m->xg16.end() && pi->second && m->pass.xg16_filled.count(L.pool_in);      // the last conv wrote only its bf16 copy
+        ProfScope ps(m, "maxpool_fwd", 0, (in16 ? 2.0 : 4.0) * N * h * w * cin + 4.0 * N * h * w * cin * (only16 ? 0.0625 : 0.3125) + (yb ? 0.5 * N * h * w * cin : 0.0));
+        if (in16) launch_maxpool_fwd_route16(pi->second + g16_off(bf16_guard_rows(3, w + 2), cin), g16_ps(N, h, w, 3), L.pidx, N, h, w, cin, s, yb, (ck - 1) / 2, g16_ps(N, h / 2, w / 2, ck));
+        else launch_maxpool_fwd_route(x, only16 ? nullptr : L.pool, L.pidx, N, h, w, cin, s, yb, (ck - 1) / 2, g16_ps(N, h / 2, w / 2, ck),
+                                      /*round16=*/pool_feeds_skip(L.block) ? 0 : 1);
+        m->pass.pool_routed[b] = true; pooled = true;
+        if (yb) m->pass.xg16_filled.insert(cons.name);
+        if (only16) { m->pass.y_unwritten.insert(pn); m->pass.in_bf16_only.insert(cons.name); }
+    }
+    if (!pooled) {
+        // a block whose last conv did not run through the Winograd output transform (bf16 modes) but whose backward pass does run in the
+        // Winograd domain: keep the same routing bytes, so that d(pool) is routed inside wino_dout_kernel and dZ is never written
+        const bool route = train && cin % 4 == 0 && L.pool_in_transform;
+        ProfScope ps(m, "maxpool_fwd", 0, 4.0 * N * h * w * cin * (route ? 1.3125 : 1.25));
+        if (route) { launch_maxpool_fwd_route(x, L.pool, L.pidx, N, h, w, cin, s); m->pass.pool_fused[b] = true; }
+        else launch_maxpool_fwd(x, L.pool, N, h, w, cin, s);
+    }
+    return FwdStep{};
+}
+
+// fc6 and fc7 on pool5 (x), each precision's own way
+static FwdStep fwd_fc(fcn8s_model* m, const float* x, float keep_prob, bool train, bool fp8, const Bf16Opts& bo)
+{
+    hipStream_t s = m->stream; const int N = m->N;
+    const Layer &F6 = m->layers[13], &F7 = m->layers[14];
+    const int h5 = F6.h, w5 = F6.w;
+    float *w6 = m->d_params + F6.w_off, *b6 = m->d_params + F6.b_off, *w7 = m->d_params + F7.w_off, *b7 = m->d_params + F7.b_off;
+    const bool drop = train && keep_prob < 1.f;
+    m->drop_stream = (uint32_t)(2 * m->step);
+    Bf16LayerIo io6, io7;          // (the bf16 precisions)
+    io6.drop = io7.drop = drop; io6.keep_prob = io7.keep_prob = keep_prob; io6.stream_id = m->drop_stream; io7.stream_id = m->drop_stream + 1;
+    if (fp8) {
+        // fc6 writes fc7's e4m3 copy only; fc7 writes fp32 for the fc7_1x1 head
+        const Q8Buf* q7 = q8_for(m, F7.name, N, h5, w5, F7.cin, 1, fp8_ex(m, F7.name), s);
+        if (!q7) return fwd_failed(fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed"));
+        int rc = fp8_conv(m, "fc6_fwd_fp8", F6.name, x, N, h5, w5, F6.cin, F6.cout, F6.K, nullptr, q7, 0, s); if (rc) return fwd_failed(rc);
+        m->pass.q8_filled.insert(F7.name); m->pass.y_unwritten.insert(F6.name);
+        rc = fp8_conv(m, "fc7_fwd_fp8", F7.name, F6.y, N, h5, w5, F7.cin, F7.cout, 1, F7.y, nullptr, 0, s); if (rc) return fwd_failed(rc);
+    } else if (bf16_train_mode(m)) {
+        unsigned short* xb6 = bo.copies ? xg16_for(m, F6.name, N, h5, w5, F6.cin, F6.K, s) : nullptr;
+        if (xb6 && !m->pass.xg16_filled.count(F6.name)) { ProfScope ps(m, "bf16_convert", 0, 6.0 * N * h5 * w5 * F6.cin); launch_f32_to_bf16_padded(x, xb6, N, h5, w5, F6.cin, (F6.K - 1) / 2, s, g16_ps(N, h5, w5, F6.K)); }
+        unsigned short* xb7 = bo.copies ? xg16_for(m, F7.name, N, h5, w5, F7.cin, 1, s) : nullptr;
+        const bool fuse7 = xb7 != nullptr && fc7_in_from_fc6(bo);      // fc7's input copy comes out of fc6's epilogue (16-byte stores since the tile kernel's epilogue goes through LDS)
+        io6.allow_small = io7.allow_small = false; io6.any_shape = io7.any_shape = true;
+        io6.xb = xb6; io6.xb_ps = g16_ps(N, h5, w5, F6.K); io6.yb = fuse7 ? xb7 : nullptr; io6.yb_pad = 0; io6.yb_ps = g16_ps(N, h5, w5, 1);
+        io7.xb = xb7; io7.xb_ps = g16_ps(N, h5, w5, 1);
+        // (both unreachable by rule, as the conv layers' text: kept as the guards for an allocation failure and a refused launch)
+        if (!bf16_conv_layer(m, "fc6_fwd_bf16", F6, x, F6.y, s, io6)) return fwd_failed(fail(m, FCN8S_ERR_SHAPE, "bf16_train: fc6 does not fit the bf16 convolution kernel"));
+        if (xb7 && !fuse7) { ProfScope ps(m, "bf16_convert", 0, 6.0 * N * h5 * w5 * F7.cin); launch_f32_to_bf16_padded(F6.y, xb7, N, h5, w5, F7.cin, 0, s, g16_ps(N, h5, w5, 1)); }
+        if (!bf16_conv_layer(m, "fc7_fwd_bf16", F7, F6.y, F7.y, s, io7)) return fwd_failed(fail(m, FCN8S_ERR_SHAPE, "bf16_train: fc7 does not fit the bf16 convolution kernel"));
+    } else if (m->precision == FCN8S_PREC_BF16_FC || bf16_fwd_mode(m)) {
+        // config 5: bf16-rounded operands, fp32 accumulate, fp32 epilogue and output (gemm_bf16.hip)
+        bf16_conv_layer(m, "fc6_fwd_bf16", F6, x, F6.y, s, io6);
+        // the fp32 gradients of fc6 run in the Winograd domain and want the transformed input and this step's filter bank
+        if (train) wino_backward_operands(m, F6.name, x, w6, N, h5, w5, F6.cin, F6.cout, F6.K, s);
+        bf16_conv_layer(m, "fc7_fwd_bf16", F7, F6.y, F7.y, s, io7);
+    } else {
+        { FwdEpi e; e.bias = b6; e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream;
+          conv_fwd(m, "fc6_fwd", x, w6, F6.y, N, h5, w5, F6.cin, F6.cout, F6.K, e, s, 0, F6.name); }
+        { FwdEpi e; e.bias = b7; e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream + 1;
+          conv_fwd(m, "fc7_fwd", F6.y, w7, F7.y, N, h5, w5, F7.cin, F7.cout, 1, e, s); }
+    }
+    return FwdStep{};
+}
+
 int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, bool train)
 {
     t_deterministic = m->deterministic;
@@ -1633,221 +1877,31 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
     // producer's epilogue (no fp32 conv -> conv tensor, no conversion pass), the flat-position kernel, pools on the bf16 copies -- instead of fp32 tensors converted
     // layer by layer for the tile kernel: 13.3 -> 9.3 ms per 16 x 1024x512 batch, 1.55 -> 1.18 ms per single image (profiles/r06_bf16_infer.txt).  Same products in the same order as the training pass:
     // its logits are the training pass's bit for bit (keep_prob 1).  What it keeps for a backward pass that never comes (routing bytes) costs one byte per window.
-    const bool cp = train || (bf16_train_mode(m) && m->bf16_infer_copies);
+    const Bf16Opts bo = bf16_opts(m, train);          // (read by the bf16_train branches alone.  bo.copies: a training pass, or option bf16_infer_copies)
     if (!m->x0_ready) { ProfScope ps(m, "preprocess", 0, (double)N * H * W * (16 + (dtype ? 12 : 3))); launch_preprocess(img_dev, dtype, A(m, "x0"), (long long)N * H * W, s); }
     const float* x = A(m, "x0");
     size_t k = 0;
     for (int b = 0; b < 5; ++b) {
-        bool pooled = false;
-        for (; m->layers[k].block == b + 1; ++k) {
+        FwdStep st;
+        for (; m->layers[k].block == b + 1; ++k) {          // each conv: the first stage that takes it
             Layer& L = m->layers[k];
-            Layer* nx = in_block_next(m->layers, L);
-            const char* nm = L.name;
-            const int h = L.h, w = L.w, cin = L.cin, cout = L.cout;
-            const bool first = L.first(), last = L.last_of_block();
-            FwdEpi e; e.bias = m->d_params + L.b_off; e.relu = 1;
-            const float* wt = first ? m->d_w1pad : m->d_params + L.w_off;
-            if (train && L.rb_writer == RbWriter::self) e.relu_bits_out = L.rb;                              // its output is the next conv's input
-            if (train && L.pos == 2 && m->layers[L.prev].rb_writer == RbWriter::consumer) {                  // input = conv1_1, made by the gather kernel
-                e.in_relu_bits_out = m->layers[L.prev].rb; e.in_layer = m->layers[L.prev].name;
+            if (fp8 && !L.first()) st = fwd_conv_fp8(m, L, x);
+            else {
+                st = L.first() ? fwd_conv1_1(m, L, x, train, bo) : fwd_declined();
+                if (!st.done && bf16_train_mode(m) && !L.first()) st = fwd_conv_bf16_train(m, L, x, bo);
+                if (!st.done && bf16_fwd_mode(m) && b >= 2) st = fwd_conv_bf16_fwd(m, L, x, train);
+                if (!st.done) st = fwd_conv(m, L, x, train);
             }
-            if (last) {
-                e.pool_out = L.pool;
-                if (train) e.pool_idx = L.pidx;
-                // The block's last conv output feeds only the pool.  If the output transform writes the pool (and, for training, the backward
-                // pass routes through the argmax bytes), the full-resolution tensor is never read again and is not written at all
-                // (2.15 GB for conv1_2 at 16 x 1024x512); fcn8s_get_activation of such a layer then returns stale data.
-                e.skip_y = !train || L.pool_in_transform;
-            }
-            if (L.out_in_next && m->fuse_out_in && !(bf16_fwd_mode(m) && b >= 2) && !bf16_train_mode(m) && !fp8_mode(m) && (!train || e.relu_bits_out)) {
-                // this conv and the next one both run through F(6x6,3x3) on the same tile grid: its output transform writes the next conv's
-                // transformed input directly (training: into the buffer kept for that conv's weight gradient) and its own output never exists.
-                // The buffer the next conv will read its V from is the one kept for its weight gradient if the workspace has one (whether or
-                // not this pass trains), else the shared scratch.  (out_in_fused: the next conv keeps V -- a direct weight gradient would read
-                // the activation that no longer exists.)
-                e.next_v = nx->wv ? nx->wv : m->d_wino_v; e.next_layer = nx->name;
-            }
-            if (fp8 && !first) {
-                // FCN8S_PREC_FP8_INFER: the output goes to the next conv's e4m3 copy, to the copy the block's pool reads (blocks 1, 2, 5: codes with the exponent of
-                // the pool's consumer -- amax(pool) = amax(conv), q is monotone: the byte-max pool is exact), or to fp32 (blocks 3, 4: pool3 / pool4 feed the skip heads)
-                const char* nxk = nx ? nx->name : ((b != 2 && b != 3) ? L.pool_in : nullptr);
-                const Q8Buf* yq = nullptr;
-                if (nxk) {
-                    const char* cons = kFp8Layers[fp8_layer(nm) + 1];           // the next FP8 layer: the next conv, or the pool's consumer
-                    yq = q8_for(m, nxk, N, h, w, cout, 3, fp8_ex(m, cons), s);
-                    if (!yq) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed");
-                }
-                const int rc = fp8_conv(m, "conv3x3_fwd_fp8", nm, x, N, h, w, cin, cout, 3, yq ? nullptr : L.y, yq, 1, s);
-                if (rc) return rc;
-                if (yq) { m->pass.q8_filled.insert(nxk); m->pass.y_unwritten.insert(nm); }
-                x = L.y;
-                continue;
-            }
-            bool done = false;
-            if (L.conv1_in_next && m->conv1_in_transform && !bf16_train_mode(m) && !fp8_mode(m)) {
-                // conv1_1's only reader is conv1_2's F(6x6,3x3) input transform: that transform evaluates conv1_1 on its own patches, straight from the
-                // image (winograd.hip: wino_input_conv1_kernel), writes conv1_2's V -- into the buffer conv_fwd will look for it in -- and, in training,
-                // the ReLU record the backward pass masks with.  conv1_1's 134 MB per image are never written or read.
-                if (!train || (nx->wv && L.rb)) {
-                    float* vdst = nx->wv ? nx->wv : m->d_wino_v;
-                    const long long T = wino_tiles(6, N, h, w);
-                    ProfScope ps(m, "wino_transform", 0, 4.0 * (4.0 * N * h * w + 64.0 * T * 64.0) + (train ? 8.0 * N * h * w : 0.0), nm);
-                    launch_wino_input_conv1(x, m->d_w1pad, e.bias, vdst, N, h, w, s, train ? L.rb : nullptr);
-                    if (train) m->pass.rbits_ok.insert(nm);
-                    m->pass.fwd_v.give(nx->name); m->pass.y_unwritten.insert(nm);
-                    done = true;
-                }
-            }
-            if (!done && first && cout == 64) {            // conv1_1: write-bound gather kernel (igemm.hip: conv1_glds_kernel)
-                // bf16_train, training: conv1_2 reads this layer as its padded bf16 copy and nobody else reads it (the mask of conv1_2's data gradient is the
-                // sign of that copy): the tile kernel writes the copy and no fp32 tensor
-                unsigned short* y16 = nullptr;
-                if (bf16_train_mode(m) && cp && m->bf16_acts && m->conv1_tiled && h % 8 == 0 && w % 16 == 0 && nx && cout % 64 == 0)
-                    y16 = xg16_for(m, nx->name, N, h, w, cout, 3, s);
-                ProfScope ps(m, "conv1_1_fwd", 2.0 * N * h * w * 27.0 * cout, 4.0 * N * h * w * 3.0 + (y16 ? 2.0 : 4.0) * N * h * w * cout, nm);
-                done = launch_conv1_fwd(x, m->d_w1pad, e.bias, y16 ? nullptr : L.y, m->d_w1pad + 12 * 4 * (size_t)cout, N, h, w, cout, m->conv1_tiled, s, y16, g16_ps(N, h, w, 3));
-                if (done && y16) { m->pass.xg16_filled.insert(nx->name); m->pass.y_unwritten.insert(nm); m->pass.in_bf16_only.insert(nx->name); }
-            }
-            if (!done && bf16_train_mode(m) && !first) {
-                // FCN8S_PREC_BF16_TRAIN: every convolution but conv1_1 (3 input channels) as a direct convolution with bf16-rounded operands; the
-                // training pass keeps the layer's padded bf16 input copy for its weight gradient (the convolution starts from that copy)
-                unsigned short* xb = cp ? xg16_for(m, nm, N, h, w, cin, 3, s) : nullptr;
-                if (xb && !m->pass.xg16_filled.count(nm)) {
-                    ProfScope ps(m, "bf16_convert", 0, 4.0 * N * h * w * cin + 2.0 * N * (h + 2) * (w + 2) * cin); launch_f32_to_bf16_padded(x, xb, N, h, w, cin, 1, s, g16_ps(N, h, w, 3));
-                }
-                // the next convolution of the block reads this output as ITS padded bf16 input: this kernel's epilogue writes that copy
-                unsigned short* yb = nullptr; const char* nxk = "";
-                if (cp && m->bf16_acts && nx) { nxk = nx->name; yb = xg16_for(m, nxk, N, h, w, cout, 3, s); }
-                // the block's LAST convolution is read by its pool only, and pool1 / pool2 / pool5 only by bf16 convolutions: the pool then takes this output
-                // as a bf16 copy of the kernel's own geometry ("pool<b>in"), picks its maxima among the bf16 values (what bf16(max of the fp32 values) is anyway)
-                // and no fp32 tensor is written (pool3 / pool4 also feed the fp32 skip heads: their blocks keep the fp32 tensor)
-                const bool pool16 = cp && m->bf16_acts && m->bf16_fuse_pool && last && b != 2 && b != 3 && cin % 64 == 0 && cout % 64 == 0 &&
-                                    m->widths[b == 4 ? 5 : b + 1] % 64 == 0;
-                if (pool16) { nxk = L.pool_in; yb = xg16_for(m, nxk, N, h, w, cout, 3, s); }
-                // ... and if that is the output's only reader (option bf16_acts; the mask of the consumer's data gradient is the sign of the copy), the fp32
-                // tensor is not written at all.  (Both layers' gradients must fit the bf16 kernels: a fallback would look for the fp32 tensor.)
-                const bool only16 = yb && m->bf16_acts && cin % 64 == 0 && cout % 64 == 0;
-                // (the convolution kernels address their padded copies through a 64-bit tile base; the weight-gradient kernels' 32-bit per-lane byte offsets span TWO
-                //  32-channel planes of a copy -- launch_wgrad_bf16's limit, applied HERE, before anything is launched: a 32-channel plane of the padded map must stay
-                //  below 4 GiB, i.e. about 67 million padded positions (127 images of 1024x512).  Round 5 refused a whole copy of 4 GiB: 64 x 1024x512.)
-                if ((double)g16_ps(N, h, w, 3) * 2.0 + 65536.0 >= 4294967296.0)
-                    return fail(m, FCN8S_ERR_SHAPE, std::string("bf16_train: a 32-channel plane of the padded bf16 copy of ") + nm + "'s input would reach 4 GiB at this batch size; use a smaller batch per GPU");
-                done = bf16_conv_layer(m, "conv3x3_fwd_bf16", L, x, only16 ? nullptr : L.y, 0, 1.f, 0, s, /*allow_small=*/false, xb, /*any_shape=*/true, yb, 1, g16_ps(N, h, w, 3), g16_ps(N, h, w, 3));
-                if (!done) return fail(m, FCN8S_ERR_SHAPE, std::string("bf16_train: ") + nm + " does not fit the bf16 convolution kernel");
-                if (done && yb) m->pass.xg16_filled.insert(nxk);
-                if (done && only16) { m->pass.y_unwritten.insert(nm); if (!pool16) m->pass.in_bf16_only.insert(nxk); }
-            }
-            if (!done && bf16_fwd_mode(m) && b >= 2) {
-                // FCN8S_PREC_BF16_FWD: conv3_1 .. conv5_3 as direct convolutions with bf16-rounded operands on the 256 x 256 bf16 kernel (the
-                // output is materialised, the block's pool runs as its own kernel, ReLU masks come from the activations); the backward pass
-                // stays in the Winograd domain, so the transformed input and this step's filter bank are made here
-                // training: the transform that keeps this layer's V for the weight gradient runs first and writes the padded bf16 copy of the
-                // input on the way (the convolution then starts from it; without a kept V, or in inference, the convolution converts its input itself)
-                unsigned short* xb = train ? xb_by_transform(m, L, N, s) : nullptr;
-                auto operands = [&]() {
-                    // the previous conv of the block came from the bf16 kernel too (no ReLU record): this transform of its output writes one
-                    const Layer* pv = in_block_prev(m->layers, L);
-                    unsigned* irb = (pv && pv->rb && !m->pass.rbits_ok.count(pv->name)) ? pv->rb : nullptr;
-                    wino_backward_operands(m, nm, x, wt, N, h, w, cin, cout, 3, s, irb, irb ? pv->name : nullptr, xb);
-                };
-                if (xb) operands();
-                done = bf16_conv_layer(m, "conv3x3_fwd_bf16", L, x, L.y, 0, 1.f, 0, s, /*allow_small=*/false, xb);
-                if (done && train && !xb) operands();
-            }
-            if (!done) pooled = conv_fwd(m, first ? "conv1_1_fwd" : "conv3x3_fwd", x, wt, L.y, N, h, w, cin, cout, 3, e, s, L.real_cin, nm);
+            if (st.rc) return st.rc;
             x = L.y;
         }
-        const Layer& L = m->layers[k - 1];         // the block's last conv; m->layers[k]: the pool's consumer (the next block's first conv, or fc6)
-        const Layer& cons = m->layers[k];
-        const char* pn = L.pool_name;
-        const int h = L.h, w = L.w, cin = L.cout;
-        if (fp8) {
-            m->pass.pool_fused[b] = false; m->pass.pool_routed[b] = false;
-            if (b != 2 && b != 3) {
-                // byte max of the last conv's e4m3 copy straight into the consumer's copy (conv<b+2>_1, pad 1; fc6, pad (k - 1) / 2)
-                const int ck = cons.K;
-                Q8Buf* yq = q8_for(m, cons.name, N, h / 2, w / 2, cin, ck, fp8_ex(m, cons.name), s);
-                if (!yq) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed");
-                const Q8Buf& xi = m->q8[L.pool_in];
-                { ProfScope ps(m, "maxpool_fwd_fp8", 0, 1.25 * N * h * w * cin); launch_maxpool_fp8(xi.p, xi.ps, yq->p, yq->ps, N, h, w, cin, (ck - 1) / 2, s); }
-                m->pass.q8_filled.insert(cons.name); m->pass.y_unwritten.insert(pn);
-            } else {
-                ProfScope ps(m, "maxpool_fwd", 0, 4.0 * N * h * w * cin * 1.25);
-                launch_maxpool_fwd(x, L.pool, N, h, w, cin, s);
-            }
-            x = L.pool;
-            continue;
-        }
-        m->pass.pool_fused[b] = pooled && train;
-        m->pass.pool_routed[b] = false;
-        if (!pooled && bf16_train_mode(m) && cp && m->bf16_fuse_pool && cin % 4 == 0) {
-            // bf16_train, training: the pool keeps its routing bytes (the backward pass reads one byte per window instead of the block's last activation)
-            // and writes the consumer's padded bf16 copy itself -- conv<b+2>_1 (pad 1) or fc6 (pad 3); pool1, pool2 and pool5 have no other reader, so
-            // with option bf16_acts their fp32 tensors are not written (pool3 / pool4 feed the fp32 skip heads)
-            const int ck = cons.K, cout_c = cons.cout;
-            unsigned short* yb = nullptr;
-            if (m->bf16_acts && cin % 64 == 0 && cout_c % 64 == 0)
-                yb = xg16_for(m, cons.name, N, h / 2, w / 2, cin, ck, s);
-            const bool only16 = yb && b != 2 && b != 3;
-            auto pi = m->xg16.find(L.pool_in);
-            const bool in16 = only16 && pi != m->xg16.end() && pi->second && m->pass.xg16_filled.count(L.pool_in);      // the last conv wrote only its bf16 copy
-            ProfScope ps(m, "maxpool_fwd", 0, (in16 ? 2.0 : 4.0) * N * h * w * cin + 4.0 * N * h * w * cin * (only16 ? 0.0625 : 0.3125) + (yb ? 0.5 * N * h * w * cin : 0.0));
-            if (in16) launch_maxpool_fwd_route16(pi->second + g16_off(bf16_guard_rows(3, w + 2), cin), g16_ps(N, h, w, 3), L.pidx, N, h, w, cin, s, yb, (ck - 1) / 2, g16_ps(N, h / 2, w / 2, ck));
-            else launch_maxpool_fwd_route(x, only16 ? nullptr : L.pool, L.pidx, N, h, w, cin, s, yb, (ck - 1) / 2, g16_ps(N, h / 2, w / 2, ck),
-                                          /*round16=*/(b != 2 && b != 3) ? 1 : 0);
-            m->pass.pool_routed[b] = true; pooled = true;
-            if (yb) m->pass.xg16_filled.insert(cons.name);
-            if (only16) { m->pass.y_unwritten.insert(pn); m->pass.in_bf16_only.insert(cons.name); }
-        }
-        if (!pooled) {
-            // a block whose last conv did not run through the Winograd output transform (bf16 modes) but whose backward pass does run in the
-            // Winograd domain: keep the same routing bytes, so that d(pool) is routed inside wino_dout_kernel and dZ is never written
-            const bool route = train && cin % 4 == 0 && L.pool_in_transform;
-            ProfScope ps(m, "maxpool_fwd", 0, 4.0 * N * h * w * cin * (route ? 1.3125 : 1.25));
-            if (route) { launch_maxpool_fwd_route(x, L.pool, L.pidx, N, h, w, cin, s); m->pass.pool_fused[b] = true; }
-            else launch_maxpool_fwd(x, L.pool, N, h, w, cin, s);
-        }
-        x = L.pool;
+        const Layer& last = m->layers[k - 1];         // the block's last conv; m->layers[k]: the pool's consumer (the next block's first conv, or fc6)
+        st = fwd_pool(m, last, m->layers[k], x, train, fp8, st.pooled, bo);
+        if (st.rc) return st.rc;
+        x = last.pool;
     }
-    const Layer &F6 = m->layers[13], &F7 = m->layers[14];
-    const int h5 = F6.h, w5 = F6.w;
-    float *w6 = m->d_params + F6.w_off, *b6 = m->d_params + F6.b_off, *w7 = m->d_params + F7.w_off, *b7 = m->d_params + F7.b_off;
-    const bool drop = train && keep_prob < 1.f;
-    m->drop_stream = (uint32_t)(2 * m->step);
-    if (fp8) {
-        // fc6 writes fc7's e4m3 copy only; fc7 writes fp32 for the fc7_1x1 head
-        const Q8Buf* q7 = q8_for(m, F7.name, N, h5, w5, F7.cin, 1, fp8_ex(m, F7.name), s);
-        if (!q7) return fail(m, FCN8S_ERR_OOM, "fp8_infer: hipMalloc of an e4m3 copy failed");
-        int rc = fp8_conv(m, "fc6_fwd_fp8", F6.name, x, N, h5, w5, F6.cin, F6.cout, F6.K, nullptr, q7, 0, s); if (rc) return rc;
-        m->pass.q8_filled.insert(F7.name); m->pass.y_unwritten.insert(F6.name);
-        rc = fp8_conv(m, "fc7_fwd_fp8", F7.name, F6.y, N, h5, w5, F7.cin, F7.cout, 1, F7.y, nullptr, 0, s); if (rc) return rc;
-    } else if (bf16_train_mode(m)) {
-        unsigned short* xb6 = cp ? xg16_for(m, F6.name, N, h5, w5, F6.cin, F6.K, s) : nullptr;
-        if (xb6 && !m->pass.xg16_filled.count(F6.name)) { ProfScope ps(m, "bf16_convert", 0, 6.0 * N * h5 * w5 * F6.cin); launch_f32_to_bf16_padded(x, xb6, N, h5, w5, F6.cin, (F6.K - 1) / 2, s, g16_ps(N, h5, w5, F6.K)); }
-        unsigned short* xb7 = cp ? xg16_for(m, F7.name, N, h5, w5, F7.cin, 1, s) : nullptr;
-        const bool fuse7 = xb7 != nullptr && m->bf16_acts;      // fc7's input copy comes out of fc6's epilogue (16-byte stores since the tile kernel's epilogue goes through LDS)
-        if (!bf16_conv_layer(m, "fc6_fwd_bf16", F6, x, F6.y, drop, keep_prob, m->drop_stream, s, false, xb6, true,
-                             fuse7 ? xb7 : nullptr, 0, g16_ps(N, h5, w5, F6.K), g16_ps(N, h5, w5, 1)))
-            return fail(m, FCN8S_ERR_SHAPE, "bf16_train: fc6 does not fit the bf16 convolution kernel");
-        if (xb7 && !fuse7) { ProfScope ps(m, "bf16_convert", 0, 6.0 * N * h5 * w5 * F7.cin); launch_f32_to_bf16_padded(F6.y, xb7, N, h5, w5, F7.cin, 0, s, g16_ps(N, h5, w5, 1)); }
-        if (!bf16_conv_layer(m, "fc7_fwd_bf16", F7, F6.y, F7.y, drop, keep_prob, m->drop_stream + 1, s, false, xb7, true, nullptr, 0, g16_ps(N, h5, w5, 1)))
-            return fail(m, FCN8S_ERR_SHAPE, "bf16_train: fc7 does not fit the bf16 convolution kernel");
-    } else if (m->precision == FCN8S_PREC_BF16_FC || bf16_fwd_mode(m)) {
-        // config 5: bf16-rounded operands, fp32 accumulate, fp32 epilogue and output (gemm_bf16.hip)
-        bf16_conv_layer(m, "fc6_fwd_bf16", F6, x, F6.y, drop, keep_prob, m->drop_stream, s);
-        // the fp32 gradients of fc6 run in the Winograd domain and want the transformed input and this step's filter bank
-        if (train) wino_backward_operands(m, F6.name, x, w6, N, h5, w5, F6.cin, F6.cout, F6.K, s);
-        bf16_conv_layer(m, "fc7_fwd_bf16", F7, F6.y, F7.y, drop, keep_prob, m->drop_stream + 1, s);
-    } else {
-        {
-            FwdEpi e; e.bias = b6; e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream;
-            conv_fwd(m, "fc6_fwd", x, w6, F6.y, N, h5, w5, F6.cin, F6.cout, F6.K, e, s, 0, F6.name);
-        }
-        {
-            FwdEpi e; e.bias = b7; e.relu = 1; e.dropout = drop; e.keep = keep_prob; e.stream_id = m->drop_stream + 1;
-            conv_fwd(m, "fc7_fwd", F6.y, w7, F7.y, N, h5, w5, F7.cin, F7.cout, 1, e, s);
-        }
-    }
+    { const FwdStep st = fwd_fc(m, x, keep_prob, train, fp8, bo); if (st.rc) return st.rc; }
+    const int h5 = H / 32, w5 = W / 32;
     // decoder (fcn8s_tensorflow.py:171-233)
     { FwdEpi e; e.bias = Wp(m, "pool3_1x1/bias"); e.alpha = 0.0001f;
       conv_fwd(m, "score1x1_fwd", A(m, "pool3"), Wp(m, "pool3_1x1/kernel"), A(m, "p3"), N, H / 8, W / 8, m->widths[2], C, 1, e, s); }
@@ -2067,7 +2121,7 @@ void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
         if (L.last_of_block()) {
             if (pool_backward_fused(L, m->pass.pool_fused[b - 1])) pix = L.pidx;
             bool pool_done = false;
-            if (!pix && bf16_train_mode(m) && m->bf16_fuse_pool && m->train_mode && cw % 64 == 0) {
+            if (!pix && bf16_train_mode(m) && m->train_mode && pool_bwd_writes_bf16(bf16_opts(m, true), L.shape(N))) {
                 // bf16_train: nobody reads the fp32 dZ of the block's last conv -- its weight and data gradients take the padded bf16 copy, its bias gradient the
                 // column sums: the pool's backward kernel writes exactly those (gbuf[gcur ^ 1] stays unwritten; the "dz" handed on below is never dereferenced)
                 unsigned short* dzb = g16_for(m, m->dyg16, nm, N, h, w, cw, 3, s);
@@ -2094,7 +2148,7 @@ void backward_blocks(fcn8s_model* m, int b_hi, int b_lo)
         if (pv) {                                                      // ReLU of the previous conv
             e.mask = xin; e.mask_scale = 1.f; e.yb_layer = pv->name; e.yb_K = 3;
             if (m->pass.rbits_ok.count(pv->name)) e.relu_bits_in = pv->rb;
-            e.yb_only = !pv->first() && pv->cin % 64 == 0 && cw % 64 == 0;      // (conv1_1's weight gradient is exact fp32 and reads the fp32 tensor)
+            e.yb_only = bf16_train_mode(m) && dy_bf16_only(bf16_opts(m, true), pv->shape(N), pv->first(), L.shape(N));
             // The previous conv takes this gradient only through dM = A dZ A^T (weight gradient in the Winograd domain, adjoint data
             // gradient): the gather kernel can write dM directly.
             if (pv->dm_from_next && m->fuse_dgrad_dout && e.relu_bits_in && m->train_mode) { e.dm_out = m->d_wino_m; e.dm_out_layer = pv->name; }

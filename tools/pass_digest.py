@@ -43,6 +43,10 @@ BF16_FWD_VARIANTS = ("fuse_out_in", "fuse_dgrad_dout", "conv1_in_transform", "wi
 # the options that move a layer from one route to another (csrc/conv_route.h), fp32 and bf16_fwd.  winograd_min_cin = 128 with WIDTHS: direct blocks
 # 1-2 and a direct conv3_1 in front of a Winograd conv3_2 -- a "wv:" / "rb:" slot exists for one neighbour only
 ROUTE_VARIANTS = ({"winograd_min_cin": 128}, {"winograd_min_cin": 0}, {"winograd_tile": 2}, {"winograd_tile_hires": 4, "winograd_hires_pixels": 8000})
+# the false sides of bf16_train's keep-or-skip rules (csrc/conv_route.h, Bf16Opts): no copies in the evaluation / prediction passes, conv1_1 on the
+# plain kernel, every fp32 tensor kept.  CONV1_128_WIDTHS: conv1_1 is not the 64-wide gather kernel and conv1_2 converts its own input
+BF16_RULE_VARIANTS = ({"bf16_infer_copies": 0}, {"conv1_tiled": 0}, {"bf16_acts": 0, "bf16_fuse_pool": 0})
+CONV1_128_WIDTHS = (128,) + WIDTHS[1:]
 
 
 def sha(a):
@@ -151,6 +155,9 @@ def cases():
     for options in ROUTE_VARIANTS:
         for p in ('fp32', 'bf16_fwd'):
             yield p, VARIANT_SHAPE, WIDTHS, dict(options)
+    for options in BF16_RULE_VARIANTS:
+        yield 'bf16_train', VARIANT_SHAPE, WIDTHS, dict(options)
+    yield 'bf16_train', VARIANT_SHAPE, CONV1_128_WIDTHS, {}
 
 
 def name_of(p, s, widths, options):
