@@ -129,6 +129,8 @@ SIGNATURES = {
     "fcn8s_profile_num_groups": (_i, [_p]),
     "fcn8s_profile_get": (_i, [_p, _i, C.POINTER(C.c_char_p), _dp, _i64p, _dp, _dp]),
     "fcn8s_op_preprocess": (_i, [_p, _p, _i, _p, _i64]),
+    "fcn8s_predict_mc": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _i64, _i, _p, _p, _p, _i]),
+    "fcn8s_op_mc_accumulate": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "fcn8s_op_tta_input": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "fcn8s_op_tta_accumulate": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i, _p, _p]),
     "fcn8s_op_crf_work_floats": (_sz, [_i, _i, _i, _i, _p]),

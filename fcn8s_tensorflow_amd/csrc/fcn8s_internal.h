@@ -369,6 +369,11 @@ void launch_tta_input(const void* img, int dtype, int N, int H, int W, int Hs, i
 // argmax_out [N,H,W] (acc not written; may be nullptr when first and last)
 void launch_tta_accumulate(const float* logits, const PixMap& map, int N, int Hs, int Ws, int flip, int C, int H, int W, float* acc,
                            int first, int last, int npasses, float* softmax_out, long long* argmax_out, hipStream_t s);
+// mc_dropout.hip (fcn8s_op_mc_accumulate / fcn8s_predict_mc).  One sample's logits over [0,H)x[0,W) of `map` into the running sums: acc [N,H,W,C] (sum of the
+// softmaxes) and ent_acc [N,H,W] (sum of their entropies); `first` stores, `last` writes no accumulator but the outputs that are not null: the mean softmax,
+// its argmax, its entropy, the mutual information.  first && last: the accumulators are not touched (and may be null).
+void launch_mc_accumulate(const float* logits, const PixMap& map, int N, int H, int W, int C, float* acc, float* ent_acc, int first, int last,
+                          int nsamples, float* softmax_out, long long* argmax_out, float* entropy_out, float* mi_out, hipStream_t s);
 // crf.hip (fcn8s_op_crf_meanfield / fcn8s_predict_crf).  One mean-field update qin -> qout [N,H,W,C] (qout != qin, qout != prob; the definition is in
 // fcn8s_hip.h): messages from qin over the (2 radius + 1)^2 window of the given dilation weighted by the uint8 image img [N,H,W,3], unary log(prob),
 // softmax; am (may be nullptr): the argmax of qout.  Defers FCN8S_ERR_SHAPE for a C / radius that crf_shape_supported refuses.

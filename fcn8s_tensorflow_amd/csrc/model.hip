@@ -10,6 +10,7 @@
 #include "pass_state.h"
 #include "conv_route.h"
 #include <cstdarg>
+#include <functional>
 
 #include <dlfcn.h>
 #include <atomic>
@@ -198,6 +199,8 @@ struct fcn8s_model {
     bool x0_ready = false;                                                // forward(): x0 is already written (fcn8s_predict_tta's tta_input), skip the preprocess kernel
     DeviceBuf<char> crf_buf;                                              // fcn8s_predict_crf: staged images, the mean softmax, the two mean-field buffers, staged output (grown, never shrunk)
     DeviceBuf<char> tta_buf;                                              // fcn8s_predict_tta: staged images, accumulator, staged output (grown, never shrunk)
+    DeviceBuf<char> mc_buf;                                               // fcn8s_predict_mc: staged images, the two accumulators, staged outputs (grown, never shrunk)
+    bool mc_masks = false;                                                // the last forward pass was fcn8s_predict_mc's: fcn8s_get_dropout_masks reports its last sample's masks
     hipStream_t stream = nullptr;
     int64_t step = 0;
     // workspace for the current (N,H,W)
@@ -1793,15 +1796,20 @@ static FwdStep fwd_pool(fcn8s_model* m, const Layer& L, const Layer& cons, const
     return FwdStep{};
 }
 
-// fc6 and fc7 on pool5 (x), each precision's own way
-static FwdStep fwd_fc(fcn8s_model* m, const float* x, float keep_prob, bool train, bool fp8, const Bf16Opts& bo)
+// Monte-Carlo dropout inference (fcn8s_predict_mc): forward() runs the encoder and the two skip heads once, then fc6 -> fc7 -> decoder once per sample with
+// dropout on at keep_prob in a prediction pass (train = false), sample s on counter streams base + 2 s (fc6) and base + 2 s + 1 (fc7), and hands each
+// sample's logits to after_sample
+struct McLoop { int samples = 1; uint32_t stream_base = 0; std::function<void(int)> after_sample; };
+
+// fc6 and fc7 on pool5 (x), each precision's own way.  mc_stream: a sample of fcn8s_predict_mc -- dropout without a training pass, on this counter stream
+static FwdStep fwd_fc(fcn8s_model* m, const float* x, float keep_prob, bool train, bool fp8, const Bf16Opts& bo, const uint32_t* mc_stream = nullptr)
 {
     hipStream_t s = m->stream; const int N = m->N;
     const Layer &F6 = m->layers[13], &F7 = m->layers[14];
     const int h5 = F6.h, w5 = F6.w;
     float *w6 = m->d_params + F6.w_off, *b6 = m->d_params + F6.b_off, *w7 = m->d_params + F7.w_off, *b7 = m->d_params + F7.b_off;
-    const bool drop = train && keep_prob < 1.f;
-    m->drop_stream = (uint32_t)(2 * m->step);
+    const bool drop = (train || mc_stream) && keep_prob < 1.f;
+    m->drop_stream = mc_stream ? *mc_stream : (uint32_t)(2 * m->step);
     Bf16LayerIo io6, io7;          // (the bf16 precisions)
     io6.drop = io7.drop = drop; io6.keep_prob = io7.keep_prob = keep_prob; io6.stream_id = m->drop_stream; io7.stream_id = m->drop_stream + 1;
     if (fp8) {
@@ -1838,7 +1846,7 @@ static FwdStep fwd_fc(fcn8s_model* m, const float* x, float keep_prob, bool trai
     return FwdStep{};
 }
 
-int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, bool train)
+int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, bool train, const McLoop* mc = nullptr)
 {
     t_deterministic = m->deterministic;
     hipStream_t s = m->stream;
@@ -1900,20 +1908,38 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
         if (st.rc) return st.rc;
         x = last.pool;
     }
-    { const FwdStep st = fwd_fc(m, x, keep_prob, train, fp8, bo); if (st.rc) return st.rc; }
     const int h5 = H / 32, w5 = W / 32;
-    // decoder (fcn8s_tensorflow.py:171-233)
-    { FwdEpi e; e.bias = Wp(m, "pool3_1x1/bias"); e.alpha = 0.0001f;
-      conv_fwd(m, "score1x1_fwd", A(m, "pool3"), Wp(m, "pool3_1x1/kernel"), A(m, "p3"), N, H / 8, W / 8, m->widths[2], C, 1, e, s); }
-    { FwdEpi e; e.bias = Wp(m, "pool4_1x1/bias"); e.alpha = 0.01f;
-      conv_fwd(m, "score1x1_fwd", A(m, "pool4"), Wp(m, "pool4_1x1/kernel"), A(m, "p4"), N, H / 16, W / 16, m->widths[3], C, 1, e, s); }
-    { FwdEpi e; e.bias = Wp(m, "fc7_1x1/bias");
-      conv_fwd(m, "score1x1_fwd", A(m, "fc7"), Wp(m, "fc7_1x1/kernel"), A(m, "s7"), N, h5, w5, m->widths[6], C, 1, e, s); }
-    tconv_fwd(m, A(m, "s7"), m->d_tph[0], Wp(m, "fc7_conv2d_trans/bias"), A(m, "p4"), A(m, "a4"), N, h5, w5, C, 4, 2, s);
-    tconv_fwd(m, A(m, "a4"), m->d_tph[1], Wp(m, "fc7_pool4_conv2d_trans/bias"), A(m, "p3"), A(m, "a3"), N, H / 16, W / 16, C, 4, 2, s);
-    if (m->tconv_gemm && m->logits_b) tconv_gemm_fwd(m);
-    else tconv_fwd(m, A(m, "a3"), m->d_tph[2], Wp(m, "fc7_pool4_pool3_conv2d_trans/bias"), nullptr, A(m, "logits"), N, H / 8, W / 8, C, 16, 8, s);
-    m->logits_nhwc_valid = !(m->tconv_gemm && m->logits_b);
+    // decoder (fcn8s_tensorflow.py:171-233): the two skip heads, which read the encoder alone, and the part behind fc7
+    auto skip_heads = [&]() {
+        { FwdEpi e; e.bias = Wp(m, "pool3_1x1/bias"); e.alpha = 0.0001f;
+          conv_fwd(m, "score1x1_fwd", A(m, "pool3"), Wp(m, "pool3_1x1/kernel"), A(m, "p3"), N, H / 8, W / 8, m->widths[2], C, 1, e, s); }
+        { FwdEpi e; e.bias = Wp(m, "pool4_1x1/bias"); e.alpha = 0.01f;
+          conv_fwd(m, "score1x1_fwd", A(m, "pool4"), Wp(m, "pool4_1x1/kernel"), A(m, "p4"), N, H / 16, W / 16, m->widths[3], C, 1, e, s); }
+    };
+    auto fc7_head_and_upsampling = [&]() {
+        { FwdEpi e; e.bias = Wp(m, "fc7_1x1/bias");
+          conv_fwd(m, "score1x1_fwd", A(m, "fc7"), Wp(m, "fc7_1x1/kernel"), A(m, "s7"), N, h5, w5, m->widths[6], C, 1, e, s); }
+        tconv_fwd(m, A(m, "s7"), m->d_tph[0], Wp(m, "fc7_conv2d_trans/bias"), A(m, "p4"), A(m, "a4"), N, h5, w5, C, 4, 2, s);
+        tconv_fwd(m, A(m, "a4"), m->d_tph[1], Wp(m, "fc7_pool4_conv2d_trans/bias"), A(m, "p3"), A(m, "a3"), N, H / 16, W / 16, C, 4, 2, s);
+        if (m->tconv_gemm && m->logits_b) tconv_gemm_fwd(m);
+        else tconv_fwd(m, A(m, "a3"), m->d_tph[2], Wp(m, "fc7_pool4_pool3_conv2d_trans/bias"), nullptr, A(m, "logits"), N, H / 8, W / 8, C, 16, 8, s);
+        m->logits_nhwc_valid = !(m->tconv_gemm && m->logits_b);
+    };
+    if (!mc) {
+        { const FwdStep st = fwd_fc(m, x, keep_prob, train, fp8, bo); if (st.rc) return st.rc; }
+        skip_heads();
+        fc7_head_and_upsampling();
+    } else {
+        // What the repeated part reads and nothing in it writes: pool5 (or fc6's padded bf16 copy of it, a buffer of its own), p3 and p4 -- arena items of their own;
+        // the transform-domain scratch (wino_v / wino_m) is filled again from pool5 by every sample's fc6 and is no input of it.
+        skip_heads();
+        for (int k = 0; k < mc->samples; ++k) {
+            const uint32_t sid = mc->stream_base + 2u * (uint32_t)k;
+            const FwdStep st = fwd_fc(m, x, keep_prob, train, fp8, bo, &sid); if (st.rc) return st.rc;
+            fc7_head_and_upsampling();
+            mc->after_sample(k);
+        }
+    }
     if (fill_fp) {                        // this pass (re)built the cache: remember what it was built from
         launch_fingerprint(m->d_params, (long long)m->total, m->d_fp, s);
         hipMemcpyAsync(&m->frozen_fp, m->d_fp, sizeof m->frozen_fp, hipMemcpyDeviceToHost, s);
@@ -1924,10 +1950,10 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
         hipEventSynchronize(m->fp_event);
         if (*m->h_fp != m->frozen_fp) {            // the parameters changed behind the library's back: this pass used stale banks -- again, without them
             drop_banks(m);
-            return forward(m, img_dev, dtype, keep_prob, train);
+            return forward(m, img_dev, dtype, keep_prob, train, mc);
         }
     }
-    m->have_forward = true; m->train_mode = train; m->keep_prob = keep_prob;
+    m->have_forward = true; m->train_mode = train; m->keep_prob = keep_prob; m->mc_masks = mc != nullptr;
     return FCN8S_OK;
 }
 
@@ -3465,6 +3491,87 @@ int fcn8s_predict_tta(fcn8s_model* m, const void* images, int dtype, int N, int 
     return FCN8S_OK;
 }
 
+// ---- Monte-Carlo dropout inference (definition: fcn8s_hip.h at fcn8s_predict_mc) --------------------------------------------------
+// One prediction forward whose encoder and skip heads run once and whose fc6 -> fc7 -> decoder part runs `samples` times with dropout on (forward()'s
+// McLoop); behind each sample mc_accumulate folds its logits, read over [0,H)x[0,W) through the PixMap, into the running sums, and the last sample
+// writes the outputs.  The image is padded to multiples of 32 by tta_input (a shape that needs no padding goes through the preprocess kernel, as
+// fcn8s_predict).  The call runs with frozen parameters, as fcn8s_predict_tta: fc6's transformed bank is built once, and a model that was not frozen
+// keeps the banks' storage with their contents marked stale.
+int fcn8s_predict_mc(fcn8s_model* m, const void* images, int dtype, int N, int H, int W, int samples, float keep_prob, int64_t sample_offset,
+                     int argmax, void* out, float* entropy_out, float* mi_out, int where)
+{
+    if (!m || !images) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: null argument");
+    if (!out && !entropy_out && !mi_out) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: no output was asked for (out, entropy_out and mi_out are all null)");
+    if (dtype != FCN8S_IMG_U8 && dtype != FCN8S_IMG_F32) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: unknown image dtype");
+    if (where != FCN8S_HOST && where != FCN8S_DEVICE) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: `where` must be FCN8S_HOST or FCN8S_DEVICE");
+    if (samples < 1 || samples > FCN8S_MC_MAX_SAMPLES) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: between 1 and 256 samples");
+    if (!(keep_prob > 0.f) || !(keep_prob <= 1.f)) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: keep_prob must lie in (0, 1]");
+    if (sample_offset < 0 || sample_offset + samples > (int64_t)1 << 30)
+        return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: sample_offset must be >= 0 with sample_offset + samples <= 2^30 (the counter streams 0x80000000 + 2 (offset + s) of the masks)");
+    if (fp8_mode(m)) return fail(m, FCN8S_ERR_STATE, "fcn8s_predict_mc: fp8_infer has no Monte-Carlo dropout -- its fc6 / fc7 kernels have no dropout epilogue; set another precision for the call");
+    if (N <= 0 || H <= 0 || W <= 0) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_mc: N, H and W must be positive");
+    const int Hp = (H + 31) / 32 * 32, Wp = (W + 31) / 32 * 32, C = m->C, S = samples;
+    if ((double)N * Hp * Wp > (double)(1LL << 31)) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_mc: the padded shape is too large to plan");
+    const bool padded = Hp != H || Wp != W, host = where == FCN8S_HOST;
+    int rc = ensure_workspace(m, N, Hp, Wp); if (rc) return rc;
+    // scratch: the staged images (host input), the two accumulators (S > 1), the staged outputs (host output)
+    const size_t npix = (size_t)N * H * W, eb = dtype == FCN8S_IMG_U8 ? 1 : 4;
+    const size_t b_img = host ? align_up(npix * 3 * eb, 256) : 0;
+    const size_t b_acc = S > 1 ? align_up(npix * C * sizeof(float), 256) : 0, b_eacc = S > 1 ? align_up(npix * sizeof(float), 256) : 0;
+    const size_t n_out = out ? (argmax ? npix * sizeof(long long) : npix * C * sizeof(float)) : 0;
+    const size_t b_out = host ? align_up(n_out, 256) : 0, b_map = host ? align_up(npix * sizeof(float), 256) : 0;
+    const size_t total = b_img + b_acc + b_eacc + b_out + (entropy_out ? b_map : 0) + (mi_out ? b_map : 0);
+    if (total && !m->mc_buf.grow(total, m->stream, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "fcn8s_predict_mc: its scratch cannot be allocated");
+    hipStream_t s = m->stream;
+    const void* img = images;
+    if (host) { HIPCHK(m, hipMemcpyAsync(m->mc_buf, images, npix * 3 * eb, hipMemcpyHostToDevice, s)); img = m->mc_buf; }
+    char* q = m->mc_buf ? (char*)m->mc_buf + b_img : nullptr;
+    float* acc = b_acc ? (float*)q : nullptr;          q += b_acc;
+    float* eacc = b_eacc ? (float*)q : nullptr;        q += b_eacc;
+    void* d_out = out ? (host ? (void*)q : out) : nullptr;                                   q += b_out;
+    float* d_ent = entropy_out ? (host ? (float*)q : entropy_out) : nullptr;                 q += (host && entropy_out) ? b_map : 0;
+    float* d_mi = mi_out ? (host ? (float*)q : mi_out) : nullptr;
+    float* sm = (out && !argmax) ? (float*)d_out : nullptr;
+    long long* am = (out && argmax) ? (long long*)d_out : nullptr;
+    const bool was_frozen = m->frozen;
+    m->frozen = true;                     // the parameters are constant for the call: every sample after the first reuses fc6's / fc7's banks
+    take_deferred_error(nullptr);
+    if (padded) {
+        ProfScope ps(m, "tta_input", 0, (double)npix * 3 * eb + 16.0 * N * Hp * Wp);
+        launch_tta_input(img, dtype, N, H, W, H, W, Hp, Wp, 0, A(m, "x0"), s);
+        m->x0_ready = true;
+    }
+    McLoop mc; mc.samples = S; mc.stream_base = 0x80000000u + 2u * (uint32_t)sample_offset;
+    mc.after_sample = [&](int k) {
+        const PixMap pm = LGM(m) ? *LGM(m) : PixMap{0, Hp, Wp, 0, 0, 0};
+        const bool first = k == 0, last = k == S - 1;
+        // algorithmic bytes: the valid logits once, both accumulators read (not first) / written (not last), the outputs (last)
+        const double by = 4.0 * npix * C + ((first ? 0.0 : 1.0) + (last ? 0.0 : 1.0)) * 4.0 * npix * (C + 1) +
+                          (last ? (sm ? 4.0 * npix * C : 0.0) + (am ? 8.0 * npix : 0.0) + (d_ent ? 4.0 * npix : 0.0) + (d_mi ? 4.0 * npix : 0.0) : 0.0);
+        ProfScope ps(m, "mc_accumulate", 0, by);
+        launch_mc_accumulate(LG(m), pm, N, H, W, C, acc, eacc, first, last, S, sm, am, d_ent, d_mi, s);
+    };
+    rc = forward(m, img, dtype, keep_prob, false, &mc);
+    m->x0_ready = false;
+    if (rc) take_deferred_error(nullptr); else rc = deferred_rc(m);
+    if (!was_frozen) {                    // leave unfrozen: the banks stay allocated for the next call, their contents are stale from now on
+        for (auto& kv : m->u_cache) m->bank_stale.insert("u:" + kv.first);
+        for (auto& kv : m->wbf16_cache) m->bank_stale.insert("w:" + kv.first);
+        m->banks_stale = true;
+        m->w8_valid.clear();
+        m->frozen = false;
+    }
+    if (rc) return rc;
+    HIPCHK(m, hipGetLastError());
+    if (host) {
+        if (out) HIPCHK(m, hipMemcpyAsync(out, d_out, n_out, hipMemcpyDeviceToHost, s));
+        if (entropy_out) HIPCHK(m, hipMemcpyAsync(entropy_out, d_ent, npix * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (mi_out) HIPCHK(m, hipMemcpyAsync(mi_out, d_mi, npix * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHK(m, hipStreamSynchronize(s));
+    }
+    return FCN8S_OK;
+}
+
 // ---- mean-field CRF refinement (definition: fcn8s_hip.h at fcn8s_crf_params) ------------------------------------------------------
 // the field of p that lies outside its range, or nullptr
 static const char* crf_bad_field(const fcn8s_crf_params* p)
@@ -3714,7 +3821,7 @@ int fcn8s_get_dropout_masks(fcn8s_model* m, float* h6, size_t n6, float* h7, siz
     if (!m || !m->have_forward) return fail(m, FCN8S_ERR_STATE, "no forward pass has been run");
     const Act& a6 = m->acts.at("fc6"); const Act& a7 = m->acts.at("fc7");
     if (n6 != a6.n || n7 != a7.n) return fail(m, FCN8S_ERR_SHAPE, "mask size mismatch");
-    const float keep = (m->train_mode ? m->keep_prob : 1.f);
+    const float keep = ((m->train_mode || m->mc_masks) ? m->keep_prob : 1.f);
     DeviceBuf<float> d;
     if (!d.grow(std::max(n6, n7) * sizeof(float), m->stream)) return fail(m, FCN8S_ERR_OOM, "fcn8s_get_dropout_masks: out of device memory");
     launch_dropout_mask(d, (long long)n6, keep, m->seed, m->drop_stream, m->stream);
@@ -3806,6 +3913,17 @@ int fcn8s_op_tta_accumulate(void* stream, const float* logits, int N, int Hp, in
         return fail(nullptr, FCN8S_ERR_BAD_ARG, "tta_accumulate: bad argument");
     const PixMap pm{0, Hp, Wp, 0, 0, 0};
     launch_tta_accumulate(logits, pm, N, Hs, Ws, flip ? 1 : 0, C, H, W, acc, first ? 1 : 0, last ? 1 : 0, npasses, softmax_out, (long long*)argmax_out, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
+
+int fcn8s_op_mc_accumulate(void* stream, const float* logits, int N, int H, int W, int C, float* acc, float* ent_acc, int first, int last, int nsamples,
+                           float* softmax_out, int64_t* argmax_out, float* entropy_out, float* mi_out)
+{
+    if (!logits || N <= 0 || H <= 0 || W <= 0 || C <= 0 || nsamples < 1 || ((!acc || !ent_acc) && !(first && last))
+        || ((uintptr_t)logits | (uintptr_t)acc | (uintptr_t)softmax_out) % 16)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "mc_accumulate: bad argument");
+    const PixMap pm{0, H, W, 0, 0, 0};
+    launch_mc_accumulate(logits, pm, N, H, W, C, acc, ent_acc, first ? 1 : 0, last ? 1 : 0, nsamples, softmax_out, (long long*)argmax_out, entropy_out, mi_out, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
 

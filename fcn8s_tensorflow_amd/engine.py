@@ -25,6 +25,7 @@ from . import crf as crf_mod
 from . import loss as loss_mod
 from . import optim as optim_mod
 from . import tta
+from . import mc_dropout
 from .dp import BucketReducer
 
 
@@ -901,6 +902,40 @@ class Engine:
         L.check(L.lib.fcn8s_predict_tta(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), int(bool(argmax)),
                                         out.ctypes.data_as(C.c_void_p), where), self.h)
         return out if argmax or self.logical_classes == self.num_classes else np.ascontiguousarray(out[..., :self.logical_classes])
+
+    def predict_mc(self, images, samples=20, keep_prob=0.5, sample_offset=0, argmax=True, entropy=True, mutual_information=True):
+        """Monte-Carlo dropout inference (fcn8s_predict_mc; the definition is in mc_dropout.py): `samples` stochastic passes with dropout
+        on behind fc6 and fc7 at `keep_prob` -- the encoder runs once, fc6 -> fc7 -> decoder once per sample -- and the mean of their
+        softmaxes.  Returns (prediction, entropy | None, mutual_information | None): the mean softmax float32 [N,H,W,C] or (argmax) its
+        int64 argmax [N,H,W]; the predictive entropy of the mean and the mutual information between prediction and weights, float32
+        [N,H,W].  Sample s of the call draws its masks on the counter streams mc_dropout.stream_ids(sample_offset, s).  Images of any
+        size; host or device inputs and outputs, as `predict`."""
+        S, keep, off = mc_dropout.validate(samples, keep_prob, sample_offset)
+        self._sync_stream()
+        ka_i, pi, dt, where, nhw = self._images(images)
+        N, H, W = (int(x) for x in nhw)
+        torch = self.torch
+        if where == L.DEVICE:
+            out = torch.empty((N, H, W), dtype=torch.int64, device=self.device) if argmax else \
+                torch.empty((N, H, W, self.num_classes), dtype=torch.float32, device=self.device)
+            ent = torch.empty((N, H, W), dtype=torch.float32, device=self.device) if entropy else None
+            mi = torch.empty((N, H, W), dtype=torch.float32, device=self.device) if mutual_information else None
+            L.check(L.lib.fcn8s_predict_mc(self.h, pi, dt, N, H, W, S, keep, off, int(bool(argmax)), C.c_void_p(out.data_ptr()),
+                                           C.c_void_p(ent.data_ptr()) if entropy else None, C.c_void_p(mi.data_ptr()) if mutual_information else None,
+                                           where), self.h)
+            self._release(ka_i)
+            if not argmax and self.logical_classes != self.num_classes:
+                out = out[..., :self.logical_classes].contiguous()
+            return out, ent, mi
+        out = np.empty((N, H, W), np.int64) if argmax else np.empty((N, H, W, self.num_classes), np.float32)
+        ent = np.empty((N, H, W), np.float32) if entropy else None
+        mi = np.empty((N, H, W), np.float32) if mutual_information else None
+        L.check(L.lib.fcn8s_predict_mc(self.h, pi, dt, N, H, W, S, keep, off, int(bool(argmax)), out.ctypes.data_as(C.c_void_p),
+                                       ent.ctypes.data_as(C.c_void_p) if entropy else None, mi.ctypes.data_as(C.c_void_p) if mutual_information else None,
+                                       where), self.h)
+        if not argmax and self.logical_classes != self.num_classes:
+            out = np.ascontiguousarray(out[..., :self.logical_classes])
+        return out, ent, mi
 
     def predict_crf(self, images, crf, scales=(1.0,), flip=False, argmax=True):
         """`predict_tta` with these arguments followed by a mean-field CRF on its mean softmax and the uint8 images (fcn8s_predict_crf; the

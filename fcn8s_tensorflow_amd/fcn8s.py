@@ -472,6 +472,18 @@ class FCN8s:
             return self.engine.predict(images, argmax=argmax)
         return self.engine.predict_tta(images, scales=(1.0,) if scales is None else scales, flip=flip, argmax=argmax)
 
+    def predict_uncertainty(self, images, samples=20, keep_prob=0.5, argmax=True, sample_offset=0):
+        '''Not in the reference: Monte-Carlo dropout inference (mc_dropout.py; fcn8s_predict_mc).  Dropout stays on behind fc6 and fc7,
+        `samples` stochastic passes are drawn -- the VGG trunk runs once, fc6 -> fc7 -> decoder once per sample -- and their softmaxes are
+        averaged.  Returns (prediction, entropy, mutual_information): int64 class ids (N,H,W) of the mean softmax or (argmax=False) the
+        mean softmax (N,H,W,C); the predictive entropy of the mean and the mutual information between prediction and weights, float32
+        (N,H,W), in nats.  `sample_offset` moves the call to other masks (sample s uses the streams of index sample_offset + s); two
+        identical calls return identical bits.  Images of any size.  Works inside `averaged_weights()`.'''
+        if isinstance(images, (list, tuple)):
+            images = np.asarray(images)
+        return self.engine.predict_mc(images, samples=samples, keep_prob=keep_prob, sample_offset=sample_offset, argmax=argmax,
+                                      entropy=True, mutual_information=True)
+
     def predict_and_save(self,
                          results_dir,
                          images_dir,

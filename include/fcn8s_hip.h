@@ -437,6 +437,36 @@ typedef struct fcn8s_crf_params {
 int fcn8s_predict_crf(fcn8s_model* m, const void* images, int image_dtype, int N, int H, int W, const float* scales, int nscales, int flip,
                       const fcn8s_crf_params* crf_params, int argmax, void* out, int where);
 
+/* ---- Monte-Carlo dropout inference: the mean prediction and per-pixel uncertainty maps ------------------------------------------------ *
+ * (Gal & Ghahramani 2016; Kendall et al., "Bayesian SegNet", 2015; Kendall & Gal 2017.)  Dropout stays on behind fc6 and fc7 at test time,
+ * S stochastic passes are drawn and their softmaxes averaged.
+ * images: N same-size images [N,H,W,3], H, W >= 1, uint8 or float32; samples = S in 1..FCN8S_MC_MAX_SAMPLES; keep_prob in (0, 1];
+ * sample_offset = o >= 0 with o + S <= 2^30.  The image is preprocessed and padded bottom / right to multiples of 32 with zeros in the
+ * preprocessed domain, exactly as the scale-1, unmirrored pass of fcn8s_predict_tta (H and W multiples of 32: fcn8s_predict's input path);
+ * nothing is resized.  Sample s = 0 .. S-1: the prediction forward of the current precision mode with dropout behind fc6 and fc7 in the
+ * training step's arithmetic (ReLU output times mask / keep_prob); fc6's mask is launch_dropout_mask(keep_prob, seed, stream) with the model's seed
+ * on counter stream 0x80000000 + 2 (o + s), fc7's on that stream + 1 -- disjoint from training's streams 2 step and 2 step + 1 (step < 2^30), so
+ * no call replays a training mask.  keep_prob = 1 draws no mask: every sample is the plain prediction.  Only fc6 and fc7 are stochastic: conv1_1 ..
+ * pool5 and the pool3 / pool4 score heads run ONCE per call, fc6 -> fc7 -> decoder once per sample.
+ * Per pixel, C classes, logits l_s of sample s, fp32 throughout, natural logarithm:
+ *     p_s  = softmax(l_s) = expf(l_s - max) / sum                       h(p) = -sum_c p_c logf(max(p_c, FLT_MIN))      (folded in class order)
+ *     mean = (sum_s p_s) * (1 / S)           summed in sample order, then one multiply by the fp32 reciprocal
+ *     entropy            = h(mean)                                      the total predictive uncertainty
+ *     mutual_information = max(0, entropy - (sum_s h(p_s)) * (1 / S))    its epistemic part (BALD): what the samples disagree about
+ *     argmax of mean, lowest index on ties
+ * out = the mean, float32 [N,H,W,C], or (argmax != 0) its int64 argmax [N,H,W], or NULL; entropy_out, mi_out = float32 [N,H,W] or NULL.
+ * The two accumulators and the host staging belong to the model and only grow: a repeated identical call allocates nothing
+ * ("workspace_allocations").  The parameters are treated as frozen for the call, as in fcn8s_predict_tta, and the model's frozen state is
+ * unchanged afterwards.  After the call fcn8s_get_dropout_masks reports the masks of the call's LAST sample.  Profile group "mc_accumulate",
+ * one entry per sample.  Two identical calls give identical bits.
+ * FCN8S_ERR_BAD_ARG: samples, keep_prob or sample_offset out of range; out, entropy_out and mi_out all NULL.  FCN8S_ERR_STATE: the fp8_infer
+ * precision, whose fc6 / fc7 kernels have no dropout epilogue.  Nothing is launched then. */
+#define FCN8S_MC_MAX_SAMPLES 256
+int fcn8s_predict_mc(fcn8s_model* m, const void* images, int image_dtype, int N, int H, int W,
+                     int samples, float keep_prob, int64_t sample_offset,
+                     int argmax, void* out /* int64 [N,H,W] or float32 [N,H,W,C] */,
+                     float* entropy_out /* [N,H,W] or NULL */, float* mi_out /* [N,H,W] or NULL */, int where);
+
 /* ---- state that must round-trip: global_step :246,:526; Adam slots ---------- */
 int64_t fcn8s_global_step(const fcn8s_model* m);
 int     fcn8s_set_global_step(fcn8s_model* m, int64_t step);
@@ -577,6 +607,12 @@ int fcn8s_op_preprocess(void* stream, const void* images, int image_dtype, float
 int fcn8s_op_tta_input(void* stream, const uint8_t* images, int N, int H, int W, int Hs, int Ws, int Hp, int Wp, int flip, float* out4);
 int fcn8s_op_tta_accumulate(void* stream, const float* logits, int N, int Hp, int Wp, int Hs, int Ws, int flip, int C, int H, int W, float* acc,
                             int first, int last, int npasses, float* softmax_out, int64_t* argmax_out);
+/* fcn8s_predict_mc's kernel on DEVICE pointers: one sample's plain logits [N,H,W,C] into the running sums acc [N,H,W,C] and ent_acc [N,H,W]
+ * (`first` stores instead of adding; `last` writes no accumulator but every output that is not NULL: the mean softmax, its int64 argmax, its
+ * entropy, the mutual information -- the definition is at fcn8s_predict_mc).  first && last (S = 1) touches no accumulator: both may be NULL. */
+int fcn8s_op_mc_accumulate(void* stream, const float* logits /*[N,H,W,C] plain*/, int N, int H, int W, int C,
+                           float* acc, float* ent_acc, int first, int last, int nsamples,
+                           float* softmax_out, int64_t* argmax_out, float* entropy_out, float* mi_out);   /* any output may be NULL */
 /* the mean field of fcn8s_predict_crf on DEVICE pointers (definition: at fcn8s_crf_params): prob, q_out float32 [N,H,W,C] (16-byte aligned,
  * C a multiple of 4), images uint8 [N,H,W,3]; work: scratch of fcn8s_op_crf_work_floats(N, H, W, C, p) floats (may be NULL when that is
  * 0); q_out (Q^T) and argmax_out (int64 [N,H,W]) may each be NULL, not both.  prob is not written and may not overlap work or q_out.
