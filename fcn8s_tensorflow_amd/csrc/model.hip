@@ -544,7 +544,7 @@ static size_t fc6_bank_floats(int ci, int co)
 // One batched GEMM per transform position (a DFT plane, a Winograd position): [T x K] x [K x Nc] per position, the slabs wino_slab() apart.
 // split, fixed_tile and a transposed B operand (bt, ldw) are the caller's.  fc6's DFT planes take fixed_tile = 1: 128-row tiles and no
 // split-K whatever the batch (a DP shard computes the big batch's bits)
-static IgemmArgs fft6_gemm(const float* x, const float* w, float* y, long long T, int K, int Nc)
+static IgemmArgs position_gemm(const float* x, const float* w, float* y, long long T, int K, int Nc)
 {
     IgemmArgs a{};
     a.x = x; a.w = w; a.y = y;
@@ -556,6 +556,18 @@ static IgemmArgs fft6_gemm(const float* x, const float* w, float* y, long long T
     a.alpha = 1.f; a.mask_scale = 1.f;
     a.batched = 1; a.x_batch_stride = wino_slab(T, K); a.y_batch_stride = wino_slab(T, Nc);
     return a;
+}
+// ... and its weight-gradient twin: C[p] = A[p]^T B[p] over the T rows of a position, [Kg x Cout] per position, every element written once (plain stores,
+// no bias sums).  split is the caller's.
+static WgradArgs position_wgrad(const float* A, const float* B, float* C, long long T, int Kg, int Cout, int positions)
+{
+    WgradArgs g{};
+    g.A = A; g.B = B; g.C = C;
+    g.N = 1; g.Pa = 1; g.Pb = (int)T; g.P = T;
+    g.Ha = 1; g.Wa = (int)T; g.Adim = Kg; g.lda = Kg; g.Areal = Kg;
+    g.Bdim = Cout; g.ldb = Cout; g.KW = 1; g.a_scale = 1; g.tap_off = 0; g.ntaps = positions; g.ldc = Cout; g.alpha = 1.f; g.colsum = nullptr;
+    g.batched = 1; g.a_batch_stride = wino_slab(T, Kg); g.b_batch_stride = wino_slab(T, Cout); g.c_uninitialized = 1;
+    return g;
 }
 // forward: Uf (kept for the data gradient), Xf, the 292 plane GEMMs, the output transform with fc6's epilogue.  false: not taken (no bank memory)
 static bool conv_fft6_fwd(fcn8s_model* m, const char* layer, const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout,
@@ -575,7 +587,7 @@ static bool conv_fft6_fwd(fcn8s_model* m, const char* layer, const float* x, con
       launch_fft_fc6_filter(w, uf, Cin, Cout, s); launch_fft_fc6_input(x, xf, N, H, W, Cin, s); }
     if (want_v) { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cin * 4 + 49.0 * wino_tiles(4, N, H, W) * 4 * Cin));
                   launch_wino_input(4, x, wv->second.p, N, H, W, Cin, 7, s); }
-    IgemmArgs a = fft6_gemm(xf, uf, m->d_wino_m, T, Cin, Cout); a.fixed_tile = 1;
+    IgemmArgs a = position_gemm(xf, uf, m->d_wino_m, T, Cin, Cout); a.fixed_tile = 1;
     { ProfScope ps(m, "fc6_fft_gemm_fwd", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
     { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)P * T * Cout + (double)N * H * W * Cout));
       launch_fft_fc6_output(m->d_wino_m, bias, y, N, H, W, Cout, relu, dropout, keep, m->seed, stream_id, s); }
@@ -592,31 +604,26 @@ static void conv_fft6_wgrad(fcn8s_model* m, const char* layer, const float* xf, 
     const long long T = fft_fc6_tiles(N, H, W);
     { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)N * H * W * Cout + (double)P * T * Cout)); launch_fft_fc6_dout(dz, m->d_wino_m, N, H, W, Cout, s); }
     m->pass.fft6_dyf.give(layer);
-    WgradArgs g{}; g.split = 0;
-    g.A = xf; g.B = m->d_wino_m; g.C = m->d_wino_u;
-    g.N = 1; g.Pa = 1; g.Pb = (int)T; g.P = T;
-    g.Ha = 1; g.Wa = (int)T; g.Adim = Cin; g.lda = Cin; g.Areal = Cin;
-    g.Bdim = Cout; g.ldb = Cout; g.KW = 1; g.a_scale = 1; g.tap_off = 0; g.ntaps = P; g.ldc = Cout; g.alpha = 1.f; g.colsum = nullptr;
-    g.batched = 1; g.a_batch_stride = wino_slab(T, Cin); g.b_batch_stride = wino_slab(T, Cout); g.c_uninitialized = 1;
+    WgradArgs g = position_wgrad(xf, m->d_wino_m, m->d_wino_u, T, Cin, Cout, P); g.split = 0;
     { ProfScope ps(m, "fc6_fft_gemm_wgrad", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_wgrad(g, s); }
     { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * (P + 49.0) * Cin * Cout); launch_fft_fc6_dfilter(m->d_wino_u, dw, Cin, Cout, s); }
     if (db) { ProfScope ps(m, "colsum", 0, 4.0 * N * H * W * Cout); launch_colsum(dz, db, (long long)N * H * W, Cout, s); }
 }
-// data gradient (Cin = channels of dz, Cout = channels of dx): dYf = output^T(dz), dXf[p] = dYf[p] Uf[p]^T with this step's bank read
+// data gradient (Cdy / Cdx: channels of dz / of dx): dYf = output^T(dz), dXf[p] = dYf[p] Uf[p]^T with this step's bank read
 // transposed, dx = input^T(dXf) (patch gradients, then the overlap-add gather)
-static void conv_fft6_dgrad(fcn8s_model* m, const char* layer, const float* dz, const float* uf, float* dx, int N, int H, int W, int Cin, int Cout, hipStream_t s)
+static void conv_fft6_dgrad(fcn8s_model* m, const char* layer, const float* dz, const float* uf, float* dx, int N, int H, int W, int Cdy, int Cdx, hipStream_t s)
 {
     const int P = fft_fc6_planes();
     const long long T = fft_fc6_tiles(N, H, W);
     if (!m->pass.fft6_dyf.take(layer)) {     // (else the weight gradient just wrote dYf of this dz into d_wino_m)
         m->pass.fft6_dyf.drop();
-        ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)N * H * W * Cin + (double)P * T * Cin)); launch_fft_fc6_dout(dz, m->d_wino_m, N, H, W, Cin, s);
+        ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)N * H * W * Cdy + (double)P * T * Cdy)); launch_fft_fc6_dout(dz, m->d_wino_m, N, H, W, Cdy, s);
     }
-    IgemmArgs a = fft6_gemm(m->d_wino_m, uf, m->d_wino_v, T, Cin, Cout);
-    a.fixed_tile = 1; a.bt = 1; a.ldw = Cin;
-    { ProfScope ps(m, "fc6_fft_gemm_dgrad", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
-    { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)P * T * Cout + 2.0 * 196.0 * T * Cout + (double)N * H * W * Cout));
-      launch_fft_fc6_din(m->d_wino_v, m->d_wino_m, dx, N, H, W, Cout, s); }
+    IgemmArgs a = position_gemm(m->d_wino_m, uf, m->d_wino_v, T, Cdy, Cdx);
+    a.fixed_tile = 1; a.bt = 1; a.ldw = Cdy;
+    { ProfScope ps(m, "fc6_fft_gemm_dgrad", 2.0 * P * T * Cdy * Cdx, 4.0 * P * (T * (double)(Cdy + Cdx) + (double)Cdy * Cdx), layer); launch_igemm(a, P, s); }
+    { ProfScope ps(m, "fc6_fft_transform", 0, 4.0 * ((double)P * T * Cdx + 2.0 * 196.0 * T * Cdx + (double)N * H * W * Cdx));
+      launch_fft_fc6_din(m->d_wino_v, m->d_wino_m, dx, N, H, W, Cdx, s); }
 }
 
 // KS = 3, or 7 (3x3 grid of 3x3 sub-filters, GEMM depth 9*Cin -- see winograd.hip).  fwd: a forward convolution (its filter bank is kept for a
@@ -627,7 +634,7 @@ void conv_winograd(fcn8s_model* m, int tile, int KS, bool fwd, const float* x, c
     const int P = wino_alpha(tile, KS) * wino_alpha(tile, KS), nsub2 = wino_nsub(KS) * wino_nsub(KS);
     const long long T = wino_tiles(tile, N, H, W);
     const int Kg = nsub2 * Cin;
-    IgemmArgs a = fft6_gemm(v, u, mm, T, Kg, Cout); a.split = split_of(m);
+    IgemmArgs a = position_gemm(v, u, mm, T, Kg, Cout); a.split = split_of(m);
     const double tb = 4.0 * ((double)N * H * W * Cin * nsub2 + (double)P * T * Kg), ob = 4.0 * ((double)N * H * W * Cout * ((e.pool ? (e.skip_y ? 0.25 : 1.25) : 1.0) + (e.rbits_in ? 1.0 / 32 : (e.mask ? 1.0 : 0.0)) + (e.addend ? 1.0 : 0.0) + (e.rbits_out ? 1.0 / 32 : 0.0)) + (double)P * T * Cout);   // y (+ pool) written, ReLU mask / skip addend read
     // frozen parameters (evaluate / predict loops): the transformed filter bank of each forward layer is computed once and kept
     bool u_cached = false;
@@ -714,124 +721,174 @@ bool conv_fwd(fcn8s_model* m, const char* group, const float* x, const float* w,
     return false;
 }
 
-// Data gradient of a SAME conv: x is dY (Cin channels), y is dX (Cout channels), `w` holds (or, e.lazy_wt, is to hold) the flipped + transposed weights.
-void conv_dgrad(fcn8s_model* m, const char* group, const float* x, const float* w, float* y,
-                int N, int H, int W, int Cin, int Cout, int K, const DgradEpi& e, hipStream_t s, const char* layer = nullptr)
+// ---- the backward launchers: conv_dgrad and conv_wgrad are drivers over one function per route -------------------------------------------------------
+// What every route receives.  fwd is the shape of the FORWARD convolution, the form conv_route.h speaks: the weight gradient reads X (fwd.Cin channels)
+// and dZ (fwd.Cout); the data gradient reads dY (fwd.Cout channels) and writes dX (fwd.Cin).
+struct BwdCall {
+    fcn8s_model* m;                  // null: an op-level entry point without a model (only the direct forms run)
+    hipStream_t s;
+    const char* layer;               // null: a layer that no ledger entry and no kept bank knows (the score heads, the model-less entry points)
+    const char* group;               // profile group of the direct form
+    ConvShape fwd;
+    bool promised = false;           // conv_wgrad: the layer was handed dM instead of dZ (pass.dm_prefilled)
+};
+// What a route reports.  taken: the launch sequence is finished, a deferred error that ends the pass included.  declined: the next candidate's turn.
+enum class Route { taken, declined };
+static bool bf16_train_step(const BwdCall& c) { return bf16_train_mode(c.m) && c.m->train_mode && c.layer; }
+
+// FCN8S_PREC_BF16_TRAIN: the SAME convolution of the padded bf16 copy of dY with the flipped kernel, wt[ci][(flipped tap, co)] bf16, on
+// conv_bf16_256_kernel; fp32 accumulate, fp32 epilogue (skip-path addend, the ReLU / dropout mask of the layer's input).  Where it declines past its
+// condition it has grown d_wbf16 and, after a refused launch without column partials, run the weight relayout: conv_dgrad's guards come next.
+static Route dgrad_bf16_train(const BwdCall& c, const float* dy, float* dx, const DgradEpi& e)
 {
-    const bool bf16_step = bf16_train_mode(m) && m->train_mode && layer;
-    if (bf16_step && e.w_fwd && e.alpha == 1.f && bf16_kernels_take(ConvShape{N, H, W, Cin, Cout, K})) {          // (the transposed shape: dY -> dX)
-        // FCN8S_PREC_BF16_TRAIN: the SAME convolution of the padded bf16 copy of dY with the flipped kernel, wt[ci][(flipped tap, co)] bf16, on
-        // conv_bf16_256_kernel; fp32 accumulate, fp32 epilogue (skip-path addend, the ReLU / dropout mask of the layer's input).
-        const size_t wneed = (size_t)K * K * Cin * Cout;
-        const bool ok = m->d_wbf16.grow(wneed * sizeof(unsigned short), s, &m->ws_allocs);
-        unsigned short* dyb = ok ? dyb_for(m, layer, x, N, H, W, Cin, K, s) : nullptr;
-        if (dyb) {
-            { ProfScope ps(m, "weight_relayout", 0, 6.0 * wneed); launch_w_to_bf16_flip_t(e.w_fwd, m->d_wbf16, K, Cout, Cin, s); }
-            Bf16Conv256Args g{};
-            g.xp = dyb; g.xp_ps = g16_ps(N, H, W, K); g.wt = m->d_wbf16; g.y = y; g.N = N; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.K = K;
-            g.addend = e.addend; g.mask = e.mask; g.mask_scale = e.mask_scale; g.any_shape = 1; g.guarded = 1; g.rows_bn = m->bf16_rows_bn;
-            if (e.mask && K == 3 && e.mask_scale == 1.f) {          // the mask is the ReLU of this layer's input: its sign is in the layer's own bf16 input copy
-                auto xi = m->xg16.find(layer);
-                if (xi != m->xg16.end() && xi->second) { g.mask16 = xi->second + g16_off(bf16_guard_rows(3, W + 2), Cout); g.mask16_ps = g16_ps(N, H, W, 3); }
-            }
-            // this gradient is the output gradient of layer e.yb_layer (same map).  If that layer's gradients read nothing else (dy_bf16_only, asked by the caller), this
-            // kernel's epilogue writes its padded bf16 copy instead of the fp32 gradient, and takes its column sums, that layer's bias gradient, from the fp32 values
-            const bool only16 = e.yb_layer && e.yb_only;
-            if (only16) { g.yb = g16_for(m, m->dyg16, e.yb_layer, N, H, W, Cout, e.yb_K, s); g.yb_pad = (e.yb_K - 1) / 2; g.yb_ps = g16_ps(N, H, W, e.yb_K); }
-            long long prow = 0;
-            if (g.yb) {
-                prow = ((long long)N * (H + 2) * (W + 2) + conv_bf16_rows_bm(Cout, g.rows_bn) - 1) / conv_bf16_rows_bm(Cout, g.rows_bn);
-                g.colpart = det_scratch(s, (size_t)prow * Cout);
-                if (g.colpart) g.y = nullptr; else prow = 0;
-            }
-            const double M = (double)N * H * W;
-            bool done;
-            { ProfScope ps(m, K == 1 ? "fc7_dgrad_bf16" : (K == 3 ? "conv3x3_dgrad_bf16" : "fc6_dgrad_bf16"), 2.0 * M * K * K * Cin * Cout,
-                           (g.y ? 4.0 : 0.0) * M * Cout + (g.yb ? 2.0 : 0.0) * M * Cout + (g.mask16 ? 2.0 : (e.mask ? 4.0 : 0.0)) * M * Cout + 2.0 * M * Cin + 2.0 * wneed, layer);
-              done = launch_conv_bf16_256(g, s); }
-            if (done) {
-                if (g.yb) m->pass.dyg16_filled.insert(e.yb_layer);
-                if (g.colpart) {
-                    ProfScope ps(m, "colsum", 0, 4.0 * prow * Cout);
-                    launch_colsum(g.colpart, Gp(m, std::string(e.yb_layer) + "/biases"), prow, Cout, s);
-                    m->pass.db_taken.insert(e.yb_layer); m->pass.dy_bf16_only.insert(e.yb_layer);
-                }
-                return;
-            }
-            if (g.colpart) { defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient was refused by the flat-position kernel", layer); return; }      // (a refused launch: unreachable by rule, kept as the guard)
-        }
+    fcn8s_model* m = c.m; hipStream_t s = c.s; const char* layer = c.layer;
+    const int N = c.fwd.N, H = c.fwd.H, W = c.fwd.W, K = c.fwd.K, Cdy = c.fwd.Cout, Cdx = c.fwd.Cin;
+    if (!(bf16_train_step(c) && e.w_fwd && e.alpha == 1.f && bf16_kernels_take(transposed(c.fwd)))) return Route::declined;
+    const size_t wneed = (size_t)K * K * Cdy * Cdx;
+    const bool ok = m->d_wbf16.grow(wneed * sizeof(unsigned short), s, &m->ws_allocs);
+    unsigned short* dyb = ok ? dyb_for(m, layer, dy, N, H, W, Cdy, K, s) : nullptr;
+    if (!dyb) return Route::declined;
+    { ProfScope ps(m, "weight_relayout", 0, 6.0 * wneed); launch_w_to_bf16_flip_t(e.w_fwd, m->d_wbf16, K, Cdx, Cdy, s); }
+    Bf16Conv256Args g{};
+    g.xp = dyb; g.xp_ps = g16_ps(N, H, W, K); g.wt = m->d_wbf16; g.y = dx; g.N = N; g.H = H; g.W = W; g.Cin = Cdy; g.Cout = Cdx; g.K = K;
+    g.addend = e.addend; g.mask = e.mask; g.mask_scale = e.mask_scale; g.any_shape = 1; g.guarded = 1; g.rows_bn = m->bf16_rows_bn;
+    if (e.mask && K == 3 && e.mask_scale == 1.f) {          // the mask is the ReLU of this layer's input: its sign is in the layer's own bf16 input copy
+        auto xi = m->xg16.find(layer);
+        if (xi != m->xg16.end() && xi->second) { g.mask16 = xi->second + g16_off(bf16_guard_rows(3, W + 2), Cdx); g.mask16_ps = g16_ps(N, H, W, 3); }
     }
+    // this gradient is the output gradient of layer e.yb_layer (same map).  If that layer's gradients read nothing else (dy_bf16_only, asked by the caller), this
+    // kernel's epilogue writes its padded bf16 copy instead of the fp32 gradient, and takes its column sums, that layer's bias gradient, from the fp32 values
+    const bool only16 = e.yb_layer && e.yb_only;
+    if (only16) { g.yb = g16_for(m, m->dyg16, e.yb_layer, N, H, W, Cdx, e.yb_K, s); g.yb_pad = (e.yb_K - 1) / 2; g.yb_ps = g16_ps(N, H, W, e.yb_K); }
+    long long prow = 0;
+    if (g.yb) {
+        prow = ((long long)N * (H + 2) * (W + 2) + conv_bf16_rows_bm(Cdx, g.rows_bn) - 1) / conv_bf16_rows_bm(Cdx, g.rows_bn);
+        g.colpart = det_scratch(s, (size_t)prow * Cdx);
+        if (g.colpart) g.y = nullptr; else prow = 0;
+    }
+    const double M = (double)N * H * W;
+    bool done;
+    { ProfScope ps(m, K == 1 ? "fc7_dgrad_bf16" : (K == 3 ? "conv3x3_dgrad_bf16" : "fc6_dgrad_bf16"), 2.0 * M * K * K * Cdy * Cdx,
+                   (g.y ? 4.0 : 0.0) * M * Cdx + (g.yb ? 2.0 : 0.0) * M * Cdx + (g.mask16 ? 2.0 : (e.mask ? 4.0 : 0.0)) * M * Cdx + 2.0 * M * Cdy + 2.0 * wneed, layer);
+      done = launch_conv_bf16_256(g, s); }
+    if (done) {
+        if (g.yb) m->pass.dyg16_filled.insert(e.yb_layer);
+        if (g.colpart) {
+            ProfScope ps(m, "colsum", 0, 4.0 * prow * Cdx);
+            launch_colsum(g.colpart, Gp(m, std::string(e.yb_layer) + "/biases"), prow, Cdx, s);
+            m->pass.db_taken.insert(e.yb_layer); m->pass.dy_bf16_only.insert(e.yb_layer);
+        }
+        return Route::taken;
+    }
+    if (g.colpart) { defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient was refused by the flat-position kernel", layer); return Route::taken; }      // (a refused launch: unreachable by rule, kept as the guard)
+    return Route::declined;
+}
+
+// fc6 in the DFT domain (conv_fft6_dgrad), with the filter bank this step's forward pass kept and holds ready
+static Route dgrad_fft6(const BwdCall& c, const float* dy, float* dx, const DgradEpi& e)
+{
+    fcn8s_model* m = c.m; const char* layer = c.layer;
+    const int N = c.fwd.N, H = c.fwd.H, W = c.fwd.W, Cdy = c.fwd.Cout, Cdx = c.fwd.Cin;
+    if (!(m && c.fwd.K == 7 && layer && e.alpha == 1.f && !e.addend && !e.mask && !e.relu_bits_in)) return Route::declined;
+    auto kept = m->u_train.find(std::string(layer) + "#fft");
+    if (!(m->pass.fft6_ready.holds(layer) && kept != m->u_train.end() && kept->second && fft6_on(m, N, H, W, Cdx, Cdy) && bt_gemm_ok(Cdy, Cdx))) return Route::declined;
+    conv_fft6_dgrad(m, layer, dy, kept->second, dx, N, H, W, Cdy, Cdx, c.s);
+    return Route::taken;
+}
+
+// 3x3, F(6x6): the adjoint of the forward Winograd algorithm, dV[xi] = dM[xi] U[xi]^T with the dM = A dY A^T the weight gradient just built (d_wino_m)
+// and the FORWARD filter bank, then dx = overlap-added B dV B^T.  (e.w_fwd is [3,3,Cdx,Cdy].)
+static Route dgrad_adjoint(const BwdCall& c, bool dm_ready, float* dx, const DgradEpi& e)
+{
+    fcn8s_model* m = c.m; hipStream_t s = c.s; const char* layer = c.layer;
+    const int N = c.fwd.N, H = c.fwd.H, W = c.fwd.W, Cdy = c.fwd.Cout, Cdx = c.fwd.Cin;
+    if (!(adjoint_dgrad(route_opts(m), c.fwd) && dm_ready && e.w_fwd && e.alpha == 1.f)) return Route::declined;
+    const int P = 64;
+    const long long T = wino_tiles(6, N, H, W);
+    IgemmArgs a = position_gemm(m->d_wino_m, m->d_wino_u, m->d_wino_v, T, Cdy, Cdx); a.split = split_of(m);
+    auto kept = m->u_train.find(std::string(layer) + "#6");
+    if (kept != m->u_train.end() && kept->second && bt_gemm_ok(Cdy, Cdx)) {
+        a.w = kept->second; a.bt = 1; a.ldw = Cdy;          // the forward bank U[xi][Cdx][Cdy], read transposed
+    } else {
+        // (a filter transform of the BACKWARD pass, into shared scratch: nothing a frozen model keeps, so no prof_derived count)
+        ProfScope ps(m, "wino_transform", 0, (double)(9 + P) * 4 * Cdy * Cdx); launch_wino_filter(6, e.w_fwd, m->d_wino_u, Cdx, Cdy, 3, s, 1);
+    }
+    { ProfScope ps(m, "wino_gemm_dgrad", 2.0 * P * T * Cdy * Cdx, 4.0 * P * (T * (double)(Cdy + Cdx) + (double)Cdy * Cdx), layer); launch_igemm(a, P, s); }
+    if (e.dm_out && e.dm_out_layer && e.relu_bits_in && !e.addend && e.mask_scale == 1.f) {
+        // the consumer of this gradient is the previous conv's weight gradient in the Winograd domain: hand it dM, skip dZ
+        ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cdx / 32 + 2.0 * P * T * Cdx));
+        launch_wino_dgrad_output_dout(m->d_wino_v, e.relu_bits_in, e.dm_out, N, H, W, Cdx, s);
+        m->pass.dm_prefilled.give(e.dm_out_layer);
+        return Route::taken;
+    }
+    { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cdx * (1.0 + (e.relu_bits_in ? 1.0 / 32 : (e.mask ? 1.0 : 0.0)) + (e.addend ? 1.0 : 0.0)) + (double)P * T * Cdx));
+      launch_wino_dgrad_output(m->d_wino_v, e.addend, e.mask, e.mask_scale, e.relu_bits_in, dx, N, H, W, Cdx, s); }
+    return Route::taken;
+}
+
+// fc6, F(4x4,4x4): the adjoint of the forward sub-filter Winograd algorithm (default widths: Cdy = 4096, Cdx = 512),
+// dV[xi][t][sub * Cdx + c] = dM[xi][t][:] . U[xi][sub * Cdx + c][:] with the forward bank of this step read as a transposed B operand, then the
+// overlap-add gather (winograd.hip).  No transform of dz, no second filter bank, no flipped copy.
+static Route dgrad_fc6_adjoint(const BwdCall& c, bool dm_ready, float* dx, const DgradEpi& e)
+{
+    fcn8s_model* m = c.m; hipStream_t s = c.s; const char* layer = c.layer;
+    const int N = c.fwd.N, H = c.fwd.H, W = c.fwd.W, Cdy = c.fwd.Cout, Cdx = c.fwd.Cin;
+    if (!(c.fwd.K == 7 && fc6_wino_map(route_opts(m), H, W) && dm_ready && e.alpha == 1.f && !e.mask && !e.addend && bt_gemm_ok(Cdy, 4 * Cdx))) return Route::declined;
+    auto kept = m->u_train.find(std::string(layer) + "#4");
+    if (!(kept != m->u_train.end() && kept->second)) return Route::declined;
+    const int P = 49, Ng = 4 * Cdx;
+    const long long T = wino_tiles(4, N, H, W);
+    IgemmArgs a = position_gemm(m->d_wino_m, kept->second, m->d_wino_v, T, Cdy, Ng); a.split = split_of(m);
+    a.bt = 1; a.ldw = Cdy;
+    { ProfScope ps(m, "wino_gemm_fc6_dgrad", 2.0 * P * T * Cdy * Ng, 4.0 * P * (T * (double)(Cdy + Ng) + (double)Cdy * Ng), layer); launch_igemm(a, P, s); }
+    { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cdx + (double)P * T * Ng)); launch_wino_dgrad_output_sub44(m->d_wino_v, dx, N, H, W, Cdx, s); }
+    return Route::taken;
+}
+
+// The forward algorithm on the flipped + transposed weights wt; v_ready: V = B^T dY B came with the weight gradient's dM (launch_wino_input_dout)
+static Route dgrad_winograd(const BwdCall& c, bool v_ready, const float* dy, const float* wt, float* dx, const DgradEpi& e)
+{
+    fcn8s_model* m = c.m;
+    const int tile = dgrad_tile(route_opts(m), c.fwd);
+    if (!(tile && e.alpha == 1.f)) return Route::declined;
+    WinoEpi we; we.addend = e.addend; we.mask = e.mask; we.mask_scale = e.mask_scale; we.seed = m->seed; we.rbits_in = e.relu_bits_in;
+    conv_winograd(m, tile, c.fwd.K, false, dy, wt, dx, m->d_wino_u, m->d_wino_v, m->d_wino_m, c.fwd.N, c.fwd.H, c.fwd.W, c.fwd.Cout, c.fwd.Cin, we, c.s, c.layer, v_ready);
+    return Route::taken;
+}
+
+// The direct form on wt: where every data gradient ends that no route above took
+static void dgrad_direct(const BwdCall& c, const float* dy, const float* wt, float* dx, const DgradEpi& e)
+{
+    IgemmArgs a{}; a.addend = e.addend; a.mask = e.mask; a.alpha = e.alpha; a.mask_scale = e.mask_scale; a.keep_prob = 1.f;
+    conv_direct(c.m, c.group, a, dy, wt, dx, c.fwd.N, c.fwd.H, c.fwd.W, c.fwd.Cout, c.fwd.Cin, c.fwd.K, c.s, 0, c.layer);
+}
+
+// Data gradient of a SAME conv: dy has Cdy channels, dx gets Cdx, `wt` holds (or, e.lazy_wt, is to hold) the flipped + transposed weights.
+// The routes in order; the ledger's backward hand-offs are taken and dropped here, between the bf16 route and the rest.
+void conv_dgrad(fcn8s_model* m, const char* group, const float* dy, const float* wt, float* dx,
+                int N, int H, int W, int Cdy, int Cdx, int K, const DgradEpi& e, hipStream_t s, const char* layer = nullptr)
+{
+    const BwdCall c{m, s, layer, group, ConvShape{N, H, W, Cdx, Cdy, K}};
+    if (dgrad_bf16_train(c, dy, dx, e) == Route::taken) return;
     // Unreachable by rule (dy_bf16_only / out_bf16_only / conv1_writes_bf16_only imply bf16_kernels_take of this launch: tests/test_bf16_route_host.py); kept as
     // the guards for an allocation failure and a refused launch.
-    if (bf16_step && m->pass.dy_bf16_only.count(layer)) {
+    if (bf16_train_step(c) && m->pass.dy_bf16_only.count(layer)) {
         defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient could not run on the bf16 kernel and its fp32 output gradient was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return;
     }
-    if (bf16_step && e.mask && m->pass.in_bf16_only.count(layer)) {
+    if (bf16_train_step(c) && e.mask && m->pass.in_bf16_only.count(layer)) {
         defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's data gradient could not run on the bf16 kernel and its fp32 mask was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return;
     }
     // what the layer's weight gradient left in the scratch for this call; anything left for another layer is void, this convolution overwrites it
     const bool dm_ready = m && m->pass.dm.take(layer), v_ready = m && m->pass.dgrad_v.take(layer);
     if (m) m->pass.drop_backward_handoffs();
-    if (m && K == 7 && layer && e.alpha == 1.f && !e.addend && !e.mask && !e.relu_bits_in) {
-        auto kept = m->u_train.find(std::string(layer) + "#fft");
-        if (m->pass.fft6_ready.holds(layer) && kept != m->u_train.end() && kept->second && fft6_on(m, N, H, W, Cout, Cin) && bt_gemm_ok(Cin, Cout)) {
-            conv_fft6_dgrad(m, layer, x, kept->second, y, N, H, W, Cin, Cout, s);
-            return;
-        }
+    if (dgrad_fft6(c, dy, dx, e) == Route::taken) return;
+    if (dgrad_adjoint(c, dm_ready, dx, e) == Route::taken) return;
+    if (dgrad_fc6_adjoint(c, dm_ready, dx, e) == Route::taken) return;
+    if (e.lazy_wt && e.w_fwd) {          // (the routes above read w_fwd itself)
+        ProfScope ps(m, "weight_relayout", 0, 8.0 * K * K * Cdy * Cdx); launch_flip_transpose(e.w_fwd, const_cast<float*>(wt), K * K, Cdx, Cdy, s);
     }
-    const RouteOpts ro = route_opts(m);
-    const ConvShape fwd{N, H, W, Cout, Cin, K};          // the forward conv this is the gradient of: dX's channels -> dY's
-    if (adjoint_dgrad(ro, fwd) && dm_ready && e.w_fwd && e.alpha == 1.f) {
-        // Data gradient as the adjoint of the forward Winograd algorithm: dV[xi] = dM[xi] U[xi]^T with the dM = A dY A^T the weight
-        // gradient just built (d_wino_m) and the FORWARD filter bank, then dx = overlap-added B dV B^T.  (w_fwd is [3,3,Cout,Cin].)
-        const int P = 64;
-        const long long T = wino_tiles(6, N, H, W);
-        IgemmArgs a = fft6_gemm(m->d_wino_m, m->d_wino_u, m->d_wino_v, T, Cin, Cout); a.split = split_of(m);
-        auto kept = m->u_train.find(std::string(layer) + "#6");
-        if (kept != m->u_train.end() && kept->second && bt_gemm_ok(Cin, Cout)) {
-            a.w = kept->second; a.bt = 1; a.ldw = Cin;          // the forward bank U[xi][ci_fwd = Cout here][co_fwd = Cin here], read transposed
-        } else {
-            // (a filter transform of the BACKWARD pass, into shared scratch: nothing a frozen model keeps, so no prof_derived count)
-            ProfScope ps(m, "wino_transform", 0, (double)(9 + P) * 4 * Cin * Cout); launch_wino_filter(6, e.w_fwd, m->d_wino_u, Cout, Cin, 3, s, 1);
-        }
-        { ProfScope ps(m, "wino_gemm_dgrad", 2.0 * P * T * Cin * Cout, 4.0 * P * (T * (double)(Cin + Cout) + (double)Cin * Cout), layer); launch_igemm(a, P, s); }
-        if (e.dm_out && e.dm_out_layer && e.relu_bits_in && !e.addend && e.mask_scale == 1.f) {
-            // the consumer of this gradient is the previous conv's weight gradient in the Winograd domain: hand it dM, skip dZ
-            ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cout / 32 + 2.0 * P * T * Cout));
-            launch_wino_dgrad_output_dout(m->d_wino_v, e.relu_bits_in, e.dm_out, N, H, W, Cout, s);
-            m->pass.dm_prefilled.give(e.dm_out_layer);
-            return;
-        }
-        { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cout * (1.0 + (e.relu_bits_in ? 1.0 / 32 : (e.mask ? 1.0 : 0.0)) + (e.addend ? 1.0 : 0.0)) + (double)P * T * Cout));
-          launch_wino_dgrad_output(m->d_wino_v, e.addend, e.mask, e.mask_scale, e.relu_bits_in, y, N, H, W, Cout, s); }
-        return;
-    }
-    if (K == 7 && fc6_wino_map(ro, H, W) && dm_ready && e.alpha == 1.f && !e.mask && !e.addend && bt_gemm_ok(Cin, 4 * Cout)) {
-        auto kept = m->u_train.find(std::string(layer) + "#4");
-        if (kept != m->u_train.end() && kept->second) {
-            // fc6 data gradient as the adjoint of the forward sub-filter Winograd algorithm (here Cin = channels of dz = 4096, Cout = channels
-            // of dx = 512): dV[xi][t][sub * Cout + c] = dM[xi][t][:] . U[xi][sub * Cout + c][:] with the forward bank of this step read as a
-            // transposed B operand, then the overlap-add gather (winograd.hip).  No transform of dz, no second filter bank, no flipped copy.
-            const int P = 49, Ng = 4 * Cout;
-            const long long T = wino_tiles(4, N, H, W);
-            IgemmArgs a = fft6_gemm(m->d_wino_m, kept->second, m->d_wino_v, T, Cin, Ng); a.split = split_of(m);
-            a.bt = 1; a.ldw = Cin;
-            { ProfScope ps(m, "wino_gemm_fc6_dgrad", 2.0 * P * T * Cin * Ng, 4.0 * P * (T * (double)(Cin + Ng) + (double)Cin * Ng), layer); launch_igemm(a, P, s); }
-            { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cout + (double)P * T * Ng)); launch_wino_dgrad_output_sub44(m->d_wino_v, y, N, H, W, Cout, s); }
-            return;
-        }
-    }
-    if (e.lazy_wt && e.w_fwd) {
-        ProfScope ps(m, "weight_relayout", 0, 8.0 * K * K * Cin * Cout); launch_flip_transpose(e.w_fwd, const_cast<float*>(w), K * K, Cout, Cin, s);
-    }
-    if (dgrad_tile(ro, fwd) && e.alpha == 1.f) {
-        // the forward algorithm on the flipped + transposed weights; v_ready: V = B^T dY B came with the weight gradient's dM (launch_wino_input_dout)
-        WinoEpi we; we.addend = e.addend; we.mask = e.mask; we.mask_scale = e.mask_scale; we.seed = m->seed; we.rbits_in = e.relu_bits_in;
-        conv_winograd(m, dgrad_tile(ro, fwd), K, false, x, w, y, m->d_wino_u, m->d_wino_v, m->d_wino_m, N, H, W, Cin, Cout, we, s, layer, v_ready);
-        return;
-    }
-    IgemmArgs a{}; a.addend = e.addend; a.mask = e.mask; a.alpha = e.alpha; a.mask_scale = e.mask_scale; a.keep_prob = 1.f;
-    conv_direct(m, group, a, x, w, y, N, H, W, Cin, Cout, K, s, 0, layer);
+    if (dgrad_winograd(c, v_ready, dy, wt, dx, e) == Route::taken) return;
+    dgrad_direct(c, dy, wt, dx, e);
 }
 
 // transposed conv forward (k = 2s) as s*s phase-specific 2x2 convs; wp = phase-packed weights
@@ -866,29 +923,121 @@ void tconv_dgrad(fcn8s_model* m, const float* dy, const float* w, float* dx, int
     ProfScope ps(m, "tconv_dgrad", flops, 4.0 * ((double)N * Hi * S * Wi * S * C + (double)a.M * C)); launch_igemm(a, 1, s);
 }
 
-void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* dz, float* dw, float* db,
-                int N, int H, int W, int Cin, int Cout, int K, float alpha, hipStream_t s, int real_cin = 0,
-                const char* layer = nullptr, const unsigned char* pool_idx = nullptr)
+static void broken_promise(const BwdCall& c) { defer_error(FCN8S_ERR_STATE, "%s was handed dM instead of dZ but does not take the Winograd-domain path", c.layer); }
+
+// Option keep_output_gradients: the layer's fp32 dY, copied before any route consumes it
+static void keep_output_gradient(const BwdCall& c, const float* dz, const unsigned char* pool_idx)
 {
-    // The data gradient of this layer follows.  fuse_dgrad_input: it runs through Winograd and its input transform V = B^T dz B can be written
-    // into d_wino_v by the same kernel that writes dM (one read of dz); adj_bytes: it is the adjoint one, which consumes dM itself
-    const RouteOpts ro = route_opts(m);
-    const ConvShape shape{N, H, W, Cin, Cout, K};
-    const bool fuse_dgrad_input = dgrad_input_fused(ro, shape), adj_bytes = adjoint_dgrad(ro, shape);
-    // the data gradient of the layer after this one may have written this layer's dM instead of dz (backward_blocks): dz then holds nothing
-    const bool promised = m && m->pass.dm_prefilled.take(layer);
-    if (m) m->pass.dm_prefilled.drop();      // (a promise to another layer: d_wino_m is about to be rewritten)
-    if (m && m->keep_dy && layer) {
-        // (dz holds the layer's fp32 dY unless it was handed over in another form: dM from the next layer's data gradient, d(pool) with routing bytes, a bf16 copy only)
-        fcn8s_model::KeptDy& k = m->kept_dy[layer];
-        const size_t n = (size_t)N * H * W * Cout;
-        k.n = 0;
-        if (!(promised || pool_idx || m->pass.dy_bf16_only.count(layer) || m->pass.dz_unwritten.count(layer))) {
-            if (k.p.grow(n * sizeof(float), s)) { k.n = n; hipMemcpyAsync(k.p, dz, n * sizeof(float), hipMemcpyDeviceToDevice, s); }
-            else defer_error(FCN8S_ERR_OOM, "keep_output_gradients: %s's copy cannot be allocated", layer);
-        }
+    fcn8s_model* m = c.m; const char* layer = c.layer;
+    if (!(m && m->keep_dy && layer)) return;
+    // (dz holds the layer's fp32 dY unless it was handed over in another form: dM from the next layer's data gradient, d(pool) with routing bytes, a bf16 copy only)
+    fcn8s_model::KeptDy& k = m->kept_dy[layer];
+    const size_t n = (size_t)c.fwd.N * c.fwd.H * c.fwd.W * c.fwd.Cout;
+    k.n = 0;
+    if (!(c.promised || pool_idx || m->pass.dy_bf16_only.count(layer) || m->pass.dz_unwritten.count(layer))) {
+        if (k.p.grow(n * sizeof(float), c.s)) { k.n = n; hipMemcpyAsync(k.p, dz, n * sizeof(float), hipMemcpyDeviceToDevice, c.s); }
+        else defer_error(FCN8S_ERR_OOM, "keep_output_gradients: %s's copy cannot be allocated", layer);
     }
-    auto broken_promise = [&]() { defer_error(FCN8S_ERR_STATE, "%s was handed dM instead of dZ but does not take the Winograd-domain path", layer); };
+}
+
+// FCN8S_PREC_BF16_TRAIN: dW[tap] = (padded bf16 input, moved by the tap)^T (padded bf16 dY), fp32 accumulate (gemm_bf16.hip: wgrad_bf16_kernel);
+// the bias gradient is the exact fp32 column sum of dY.  Declines without the layer's input copy or its dY copy, and after a refused launch that
+// has not taken the bias gradient: conv_wgrad's guard comes next.
+static Route wgrad_bf16_train(const BwdCall& c, const float* dz, float* dw, float* db, float alpha, int real_cin)
+{
+    fcn8s_model* m = c.m; hipStream_t s = c.s; const char* layer = c.layer;
+    const int N = c.fwd.N, H = c.fwd.H, W = c.fwd.W, Cin = c.fwd.Cin, Cout = c.fwd.Cout, K = c.fwd.K;
+    if (!(bf16_train_step(c) && !real_cin && alpha == 1.f && bf16_kernels_take(c.fwd))) return Route::declined;
+    auto it = m->xg16.find(layer);
+    if (!(it != m->xg16.end() && it->second)) return Route::declined;
+    const long long P = (long long)N * H * W;
+    const int pad = (K - 1) / 2, Wp_ = W + 2 * pad;
+    const long long G = bf16_guard_rows(K, Wp_), R = (long long)N * (H + 2 * pad) * Wp_;
+    bool db_done = false;
+    unsigned short* dyb = dyb_for(m, layer, dz, N, H, W, Cout, K, s, db, &db_done);
+    if (m->pass.db_taken.count(layer)) db_done = true;          // (the kernel that wrote this layer's dY copy added the bias gradient too)
+    if (!dyb) return Route::declined;
+    Bf16WgradArgs g{};
+    g.A = it->second + g16_off(G, Cin); g.B = dyb; g.C = dw; g.R = R; g.Ci = Cin; g.Cj = Cout; g.K = K; g.Wp = Wp_; g.a_ps = g.b_ps = g16_ps(N, H, W, K);
+    bool done;
+    { ProfScope ps(m, K == 1 ? "fc7_wgrad_bf16" : (K == 3 ? "conv3x3_wgrad_bf16" : "fc6_wgrad_bf16"), 2.0 * P * K * K * (double)Cin * Cout, 2.0 * K * K * R * (Cin + Cout) + 4.0 * K * K * Cin * Cout, layer);
+      done = launch_wgrad_bf16(g, s); }
+    if (done) {
+        if (db && !db_done) { ProfScope ps(m, "colsum", 0, 4.0 * P * Cout); launch_colsum(dz, db, P, Cout, s); }
+        return Route::taken;
+    }
+    if (db_done) { defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's weight-gradient launch refused its shape after the bias gradient was taken", layer); return Route::taken; }      // (a refused launch: unreachable by rule, kept as the guard)
+    return Route::declined;
+}
+
+// fc6 in the DFT domain (conv_fft6_wgrad), on the Xf the forward pass kept: taking pass.fft6_xf, the last operand of the condition, is what decides
+static Route wgrad_fft6(const BwdCall& c, const float* dz, float* dw, float* db, float alpha, int real_cin)
+{
+    fcn8s_model* m = c.m; const char* layer = c.layer;
+    if (!(m && c.fwd.K == 7 && alpha == 1.f && !real_cin && m->train_mode && m->pass.fft6_xf.take(layer))) return Route::declined;
+    if (c.promised) broken_promise(c);
+    m->pass.drop_backward_handoffs();
+    conv_fft6_wgrad(m, layer, m->acts[std::string("wv:") + layer].p, dz, dw, db, c.fwd.N, c.fwd.H, c.fwd.W, c.fwd.Cin, c.fwd.Cout, c.s);
+    return Route::taken;
+}
+
+// 3x3 and fc6 in the Winograd domain, on the V the forward pass kept ("wv:<layer>"): dM = A dz A^T into d_wino_m, dU[xi] = V[xi]^T dM[xi], dW = G^T dU G.
+// The layer's data gradient follows, and what this route leaves for it in the scratch it gives to the ledger: dM (pass.dm) for the adjoint routes,
+// V = B^T dz B (pass.dgrad_v) for the forward-type one.
+static Route wgrad_winograd(const BwdCall& c, const float* dz, float* dw, float* db, float alpha, int real_cin, const unsigned char* pool_idx)
+{
+    fcn8s_model* m = c.m; hipStream_t s = c.s; const char* layer = c.layer;
+    const int N = c.fwd.N, H = c.fwd.H, W = c.fwd.W, Cin = c.fwd.Cin, Cout = c.fwd.Cout, K = c.fwd.K;
+    if (!(m && (K == 3 || K == 7) && layer && alpha == 1.f && !real_cin && m->train_mode)) return Route::declined;
+    auto it = m->acts.find(std::string("wv:") + layer);
+    // (fc6's slot also exists on maps that only the DFT tiles cover, e.g. 10x13: no F(4x4,4x4) tile there)
+    if (!(it != m->acts.end() && m->d_wino_m && (K == 3 || wino_tile_for(m, H, W, 7) == 4))) return Route::declined;
+    // fuse_dgrad_input: the data gradient runs through Winograd and its input transform V = B^T dz B can be written into d_wino_v by the same
+    // kernel that writes dM (one read of dz); adj_bytes: it is the adjoint one, which consumes dM itself
+    const RouteOpts ro = route_opts(m);
+    const bool fuse_dgrad_input = dgrad_input_fused(ro, c.fwd), adj_bytes = adjoint_dgrad(ro, c.fwd);
+    const int tile = wino_tile_for(m, H, W, K), NP = wino_alpha(tile, K) * wino_alpha(tile, K);
+    const long long T = wino_tiles(tile, N, H, W);
+    const int Kg = wino_nsub(K) * wino_nsub(K) * Cin;           // rows of V / dU: [sub-filter][channel]
+    WgradArgs g = position_wgrad(it->second.p, m->d_wino_m, m->d_wino_u, T, Kg, Cout, NP); g.split = split_of(m);
+    bool fused = false, dm_ready = false;
+    const bool prefilled = c.promised && adj_bytes && !pool_idx;      // dM already in d_wino_m (wino_dgrad_output_dout_kernel)
+    if (c.promised && !prefilled) broken_promise(c);
+    if (prefilled) dm_ready = true;
+    else {
+        { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cout * (pool_idx ? 0.3125 : 1.0) + ((fuse_dgrad_input && !adj_bytes) ? 2.0 : 1.0) * NP * T * Cout));
+          // pool_idx: dz is d(pool) [N,H/2,W/2,Cout]; the max-pool backward happens inside the transform (the caller checked eligibility)
+          // adjoint data gradient (tile 6): it consumes dM itself, no second transform of dz
+          if (adj_bytes) { launch_wino_dout(6, dz, m->d_wino_m, N, H, W, Cout, s, 3, pool_idx); dm_ready = true; }
+          else {
+              if (fuse_dgrad_input) fused = launch_wino_input_dout(tile, dz, m->d_wino_v, m->d_wino_m, N, H, W, Cout, s, pool_idx);
+              if (!fused) launch_wino_dout(tile, dz, m->d_wino_m, N, H, W, Cout, s, K);
+          } }
+        // fc6: the non-fused transform above left dM = A dz A^T in d_wino_m; its adjoint data gradient (dgrad_fc6_adjoint) consumes it
+        // (not when this step's forward ran through the DFT tiles: a kept F(4x4,4x4) bank would be stale)
+        if (K == 7 && tile == 4 && !fused && Cin % 2 == 0 && bt_gemm_ok(Cout, 4 * Cin) && m->u_train.count(std::string(layer) + "#4") && !m->pass.fft6_ready.holds(layer)) dm_ready = true;
+    }
+    m->pass.drop_backward_handoffs();
+    if (fused) m->pass.dgrad_v.give(layer);
+    if (dm_ready) m->pass.dm.give(layer);
+    { ProfScope ps(m, K == 7 ? "wino_gemm_fc6_wgrad" : "wino_gemm_wgrad", 2.0 * NP * T * Kg * Cout, 4.0 * NP * (T * (double)(Kg + Cout) + (double)Kg * Cout), layer); launch_wgrad(g, s); }
+    { ProfScope ps(m, "wino_transform", 0, 4.0 * (9.0 + NP) * Cin * Cout + 4.0 * N * H * W * Cout * (tile >= 4 ? 1.0 / (tile * tile) : 1.0));
+      launch_wino_dfilter(tile, m->d_wino_u, dw, Cin, Cout, K, s);
+      // bias gradient = sum of dz over all pixels.  dM[(1,1)] = sum_kl A^T(k,1) dz[k][l] A^T(l,1) and column 1 of A^T is all ones:
+      // the slab of position (1,1) holds the per-tile sums -- 16x fewer bytes than dz, and dz need not exist
+      if (db) {
+          if (tile >= 4) launch_colsum(m->d_wino_m + (wino_alpha(tile, K) + 1) * wino_slab(T, Cout), db, T, Cout, s);
+          else launch_colsum(dz, db, (long long)N * H * W, Cout, s);
+      } }
+    return Route::taken;
+}
+
+// The direct forms, where every weight gradient ends that no route above took: the skinny kernel of the score heads, the per-tap kernels, conv1_1's own,
+// the general one
+static void wgrad_direct(const BwdCall& c, const float* x, const float* dz, float* dw, float* db, float alpha, int real_cin)
+{
+    fcn8s_model* m = c.m; hipStream_t s = c.s;
+    const int N = c.fwd.N, H = c.fwd.H, W = c.fwd.W, Cin = c.fwd.Cin, Cout = c.fwd.Cout, K = c.fwd.K;
     WgradArgs a{}; a.split = split_of(m);
     a.A = x; a.B = dz; a.C = dw;
     a.N = N; a.Pa = H; a.Pb = W; a.P = (long long)N * H * W;
@@ -899,86 +1048,6 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
     const double rc = a.Areal;
     const double flops = 2.0 * a.P * K * K * rc * Cout;
     const double bytes = 4.0 * (a.P * rc + (double)a.P * Cout + (double)K * K * rc * Cout);
-    if (bf16_train_mode(m) && m->train_mode && layer && !real_cin && alpha == 1.f && bf16_kernels_take(shape)) {
-        // FCN8S_PREC_BF16_TRAIN: dW[tap] = (padded bf16 input, moved by the tap)^T (padded bf16 dY), fp32 accumulate (gemm_bf16.hip: wgrad_bf16_kernel);
-        // the bias gradient is the exact fp32 column sum of dY
-        auto it = m->xg16.find(layer);
-        if (it != m->xg16.end() && it->second) {
-            const int pad = (K - 1) / 2, Wp_ = W + 2 * pad;
-            const long long G = bf16_guard_rows(K, Wp_), R = (long long)N * (H + 2 * pad) * Wp_;
-            bool db_done = false;
-            unsigned short* dyb = dyb_for(m, layer, dz, N, H, W, Cout, K, s, db, &db_done);
-            if (m->pass.db_taken.count(layer)) db_done = true;          // (the kernel that wrote this layer's dY copy added the bias gradient too)
-            if (dyb) {
-                Bf16WgradArgs g{};
-                g.A = it->second + g16_off(G, Cin); g.B = dyb; g.C = dw; g.R = R; g.Ci = Cin; g.Cj = Cout; g.K = K; g.Wp = Wp_; g.a_ps = g.b_ps = g16_ps(N, H, W, K);
-                bool done;
-                { ProfScope ps(m, K == 1 ? "fc7_wgrad_bf16" : (K == 3 ? "conv3x3_wgrad_bf16" : "fc6_wgrad_bf16"), flops, 2.0 * K * K * R * (Cin + Cout) + 4.0 * K * K * Cin * Cout, layer);
-                  done = launch_wgrad_bf16(g, s); }
-                if (done) {
-                    if (db && !db_done) { ProfScope ps(m, "colsum", 0, 4.0 * a.P * Cout); launch_colsum(dz, db, a.P, Cout, s); }
-                    return;
-                }
-                if (db_done) { defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's weight-gradient launch refused its shape after the bias gradient was taken", layer); return; }      // (a refused launch: unreachable by rule, kept as the guard)
-            }
-        }
-    }
-    // Unreachable by rule (whoever put the layer into either set asked bf16_kernels_take of this shape); kept as the guard for an allocation failure and a refused launch.
-    if (bf16_train_mode(m) && m->train_mode && layer && (m->pass.in_bf16_only.count(layer) || m->pass.dy_bf16_only.count(layer))) {
-        defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's weight gradient could not run on the bf16 kernel and its fp32 input was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return;
-    }
-    if (m && K == 7 && alpha == 1.f && !real_cin && m->train_mode && m->pass.fft6_xf.take(layer)) {      // weight gradient in the DFT domain (Xf kept by the forward pass)
-        if (promised) broken_promise();
-        m->pass.drop_backward_handoffs();
-        conv_fft6_wgrad(m, layer, m->acts[std::string("wv:") + layer].p, dz, dw, db, N, H, W, Cin, Cout, s);
-        return;
-    }
-    if (m && (K == 3 || K == 7) && layer && alpha == 1.f && !real_cin && m->train_mode) {
-        auto it = m->acts.find(std::string("wv:") + layer);
-        // (fc6's slot also exists on maps that only the DFT tiles cover, e.g. 10x13: no F(4x4,4x4) tile there)
-        if (it != m->acts.end() && m->d_wino_m && (K == 3 || wino_tile_for(m, H, W, 7) == 4)) {             // weight gradient in the Winograd domain (V kept by the forward pass)
-            const int tile = wino_tile_for(m, H, W, K), NP = wino_alpha(tile, K) * wino_alpha(tile, K);
-            const long long T = wino_tiles(tile, N, H, W);
-            const int Kg = wino_nsub(K) * wino_nsub(K) * Cin;           // rows of V / dU: [sub-filter][channel]
-            WgradArgs g{}; g.split = split_of(m);
-            g.A = it->second.p; g.B = m->d_wino_m; g.C = m->d_wino_u;
-            g.N = 1; g.Pa = 1; g.Pb = (int)T; g.P = T;
-            g.Ha = 1; g.Wa = (int)T; g.Adim = Kg; g.lda = Kg; g.Areal = Kg;
-            g.Bdim = Cout; g.ldb = Cout; g.KW = 1; g.a_scale = 1; g.tap_off = 0; g.ntaps = NP; g.ldc = Cout; g.alpha = 1.f; g.colsum = nullptr;
-            g.batched = 1; g.a_batch_stride = wino_slab(T, Kg); g.b_batch_stride = wino_slab(T, Cout); g.c_uninitialized = 1;
-            bool fused = false, dm_ready = false;
-            const bool prefilled = promised && adj_bytes && !pool_idx;      // dM already in d_wino_m (wino_dgrad_output_dout_kernel)
-            if (promised && !prefilled) broken_promise();
-            if (prefilled) dm_ready = true;
-            else {
-                { ProfScope ps(m, "wino_transform", 0, 4.0 * ((double)N * H * W * Cout * (pool_idx ? 0.3125 : 1.0) + ((fuse_dgrad_input && !adj_bytes) ? 2.0 : 1.0) * NP * T * Cout));
-                  // pool_idx: dz is d(pool) [N,H/2,W/2,Cout]; the max-pool backward happens inside the transform (the caller checked eligibility)
-                  // adjoint data gradient (tile 6): it consumes dM itself, no second transform of dz
-                  if (adj_bytes) { launch_wino_dout(6, dz, m->d_wino_m, N, H, W, Cout, s, 3, pool_idx); dm_ready = true; }
-                  else {
-                      if (fuse_dgrad_input) fused = launch_wino_input_dout(tile, dz, m->d_wino_v, m->d_wino_m, N, H, W, Cout, s, pool_idx);
-                      if (!fused) launch_wino_dout(tile, dz, m->d_wino_m, N, H, W, Cout, s, K);
-                  } }
-                // fc6: the non-fused transform above left dM = A dz A^T in d_wino_m; its adjoint data gradient (conv_dgrad) consumes it
-                // (not when this step's forward ran through the DFT tiles: a kept F(4x4,4x4) bank would be stale)
-                if (K == 7 && tile == 4 && !fused && Cin % 2 == 0 && bt_gemm_ok(Cout, 4 * Cin) && m->u_train.count(std::string(layer) + "#4") && !m->pass.fft6_ready.holds(layer)) dm_ready = true;
-            }
-            m->pass.drop_backward_handoffs();
-            if (fused) m->pass.dgrad_v.give(layer);
-            if (dm_ready) m->pass.dm.give(layer);
-            { ProfScope ps(m, K == 7 ? "wino_gemm_fc6_wgrad" : "wino_gemm_wgrad", 2.0 * NP * T * Kg * Cout, 4.0 * NP * (T * (double)(Kg + Cout) + (double)Kg * Cout), layer); launch_wgrad(g, s); }
-            { ProfScope ps(m, "wino_transform", 0, 4.0 * (9.0 + NP) * Cin * Cout + 4.0 * N * H * W * Cout * (tile >= 4 ? 1.0 / (tile * tile) : 1.0));
-              launch_wino_dfilter(tile, m->d_wino_u, dw, Cin, Cout, K, s);
-              // bias gradient = sum of dz over all pixels.  dM[(1,1)] = sum_kl A^T(k,1) dz[k][l] A^T(l,1) and column 1 of A^T is all ones:
-              // the slab of position (1,1) holds the per-tile sums -- 16x fewer bytes than dz, and dz need not exist
-              if (db) {
-                  if (tile >= 4) launch_colsum(m->d_wino_m + (wino_alpha(tile, K) + 1) * wino_slab(T, Cout), db, T, Cout, s);
-                  else launch_colsum(dz, db, (long long)N * H * W, Cout, s);
-              } }
-            return;
-        }
-    }
-    if (promised) broken_promise();
     const bool taps = (K == 3 || K == 7) && alpha == 1.f && !real_cin;
     const bool first = K == 3 && alpha == 1.f && real_cin == 3 && Cin == 4;
     auto run = [&]() {
@@ -990,7 +1059,29 @@ void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* 
         if (first && launch_conv1_wgrad(x, dz, dw, db, N, H, W, Cout, m->conv1_wgrad_mfma, s)) return;
         launch_wgrad(a, s);
     };
-    { ProfScope ps(m, group, flops, bytes, layer); run(); }
+    { ProfScope ps(m, c.group, flops, bytes, c.layer); run(); }
+}
+
+// Weight (and bias) gradient of a SAME conv.  The routes in order; whether the layer was handed dM instead of dZ (pass.dm_prefilled, from the data
+// gradient of the layer after it: backward_blocks) is taken here and travels in the call, and a promise no Winograd-domain route can keep is reported
+// before the DFT route runs, inside the Winograd route, and before the direct one.
+void conv_wgrad(fcn8s_model* m, const char* group, const float* x, const float* dz, float* dw, float* db,
+                int N, int H, int W, int Cin, int Cout, int K, float alpha, hipStream_t s, int real_cin = 0,
+                const char* layer = nullptr, const unsigned char* pool_idx = nullptr)
+{
+    BwdCall c{m, s, layer, group, ConvShape{N, H, W, Cin, Cout, K}};
+    c.promised = m && m->pass.dm_prefilled.take(layer);      // dz then holds nothing
+    if (m) m->pass.dm_prefilled.drop();      // (a promise to another layer: d_wino_m is about to be rewritten)
+    keep_output_gradient(c, dz, pool_idx);
+    if (wgrad_bf16_train(c, dz, dw, db, alpha, real_cin) == Route::taken) return;
+    // Unreachable by rule (whoever put the layer into either set asked bf16_kernels_take of this shape); kept as the guard for an allocation failure and a refused launch.
+    if (bf16_train_step(c) && (m->pass.in_bf16_only.count(layer) || m->pass.dy_bf16_only.count(layer))) {
+        defer_error(FCN8S_ERR_SHAPE, "bf16_train: %s's weight gradient could not run on the bf16 kernel and its fp32 input was not kept (option \"bf16_acts\" = 0 keeps it)", layer); return;
+    }
+    if (wgrad_fft6(c, dz, dw, db, alpha, real_cin) == Route::taken) return;
+    if (wgrad_winograd(c, dz, dw, db, alpha, real_cin, pool_idx) == Route::taken) return;
+    if (c.promised) broken_promise(c);
+    wgrad_direct(c, x, dz, dw, db, alpha, real_cin);
 }
 
 void tconv_wgrad(fcn8s_model* m, const float* x, const float* dy, float* dw, int N, int Hi, int Wi, int C,

@@ -12,8 +12,8 @@ calibration made the way tests/test_state_coherence_gpu.py makes it.  The file k
 hundred bytes per case: small enough to commit); --full writes the parts themselves, to find WHICH tensor or profile group moved.
 
 Run it with one build in place, then with the other (copy the .so into place as tools/ab_libs.sh does), and diff the two files.  Before it
-writes anything the tool checks that it could tell two builds apart: the launch tables of fuse_out_in 0 / 2 and of fc6_fft 0 / 1 differ,
-and the value digests of two parameter seeds differ."""
+writes anything the tool checks that it could tell two builds apart: the launch tables of fuse_out_in 0 / 2, of fc6_fft 0 / 1 and (on
+fc6's 4x4 map) of winograd_fc6 1 / 0 differ, and the value digests of two parameter seeds differ."""
 import hashlib
 import json
 import os
@@ -47,6 +47,14 @@ ROUTE_VARIANTS = ({"winograd_min_cin": 128}, {"winograd_min_cin": 0}, {"winograd
 # plain kernel, every fp32 tensor kept.  CONV1_128_WIDTHS: conv1_1 is not the 64-wide gather kernel and conv1_2 converts its own input
 BF16_RULE_VARIANTS = ({"bf16_infer_copies": 0}, {"conv1_tiled": 0}, {"bf16_acts": 0, "bf16_fuse_pool": 0})
 CONV1_128_WIDTHS = (128,) + WIDTHS[1:]
+# fc6's own backward routes (conv_wgrad / conv_dgrad): SHAPES give it maps of 2x3, 3x5 and 6x6, none of which has an F(4x4,4x4) tile.  128x128: a 4x4 map,
+# the DFT tiles are not cheaper (292 planes against 196 positions) -- F(4x4,4x4) forward, the Winograd-domain weight gradient, the adjoint data gradient
+# (winograd_fc6 = 0: the direct taps and the lazy flipped kernel).  128x256, two images: a 4x8 map, the DFT forward is cheaper (292 against 392) -- the
+# weight gradient in F(4x4,4x4) under a held fft6_ready or (fc6_fft_wgrad = 2) in the DFT domain, the data gradient in the DFT domain.
+# ODD_WIDTHS: fc6 is 64 -> 128, the adjoint route's transposed-bank GEMM takes it
+FC6_ROUTE_CASES = (('fp32', (1, 128, 128), WIDTHS, {}), ('fp32', (1, 128, 128), WIDTHS, {"winograd_fc6": 0}),
+                   ('fp32', (2, 128, 256), WIDTHS, {}), ('fp32', (2, 128, 256), WIDTHS, {"fc6_fft": 0}), ('fp32', (2, 128, 256), WIDTHS, {"fc6_fft_wgrad": 2}),
+                   ('bf16_fwd', (1, 128, 128), WIDTHS, {}), ('fp32', (1, 128, 128), ODD_WIDTHS, {}))
 
 
 def sha(a):
@@ -158,6 +166,8 @@ def cases():
     for options in BF16_RULE_VARIANTS:
         yield 'bf16_train', VARIANT_SHAPE, WIDTHS, dict(options)
     yield 'bf16_train', VARIANT_SHAPE, CONV1_128_WIDTHS, {}
+    for p, s, widths, options in FC6_ROUTE_CASES:
+        yield p, s, widths, dict(options)
 
 
 def name_of(p, s, widths, options):
@@ -177,7 +187,8 @@ def main(path, full=False):
         print(name, flush=True)
     # the tool has force: what it digests moves when the program does
     base = "fp32/1x96x160"
-    for a, b in (("fp32/1x96x160/fuse_out_in=0", "fp32/1x96x160/fuse_out_in=2"), (base, "fp32/1x96x160/fc6_fft=0")):
+    for a, b in (("fp32/1x96x160/fuse_out_in=0", "fp32/1x96x160/fuse_out_in=2"), (base, "fp32/1x96x160/fc6_fft=0"),
+                 ("fp32/1x128x128", "fp32/1x128x128/winograd_fc6=0")):
         assert lines[a]["launches"]["step2"] != lines[b]["launches"]["step2"], ("the launch tables do not tell these apart", a, b)
     other = run('fp32', VARIANT_SHAPE, WIDTHS, {}, 2, True)
     for k in ("loss", "logits", "params", "predict"):
