@@ -157,6 +157,7 @@ SIGNATURES = {
     "fcn8s_op_confusion": (_i, [_p, _p, _p, _i64, _p, _i]),
     "fcn8s_op_cityscapes_work_bytes": (_sz, [_i]),
     "fcn8s_op_cityscapes_pair": (_i, [_p, _p, _p, _p, _i, _i, _i64, _p, _p, _p, _i, _p]),
+    "fcn8s_op_reliability_pair": (_i, [_p, _p, _p, _p, _i, _i64, _i, _p, _p, _i, _i, _p, _p, _p, _p]),
     "fcn8s_op_boundary_pair": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "fcn8s_op_boundary_distance": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "fcn8s_op_tf_adam": (_i, [_p, _p, _p, _p, _p, _i64, _i, _f, _f, _f, _f, _f]),

@@ -388,6 +388,11 @@ void launch_crf_argmax(const float* p, long long npix, int C, long long* am, hip
 size_t cityscapes_work_bytes(int N);
 void launch_cityscapes_pair(const uint8_t* gt, const uint16_t* inst, const void* pred, int pred_kind, int N, long long P,
                             unsigned long long* conf, void* work, int* entries, int max_entries, unsigned long long* counts, hipStream_t s);
+// reliability.hip (fcn8s_op_reliability_pair; the definition is in fcn8s_hip.h).  One kernel; calib [B][3], sums [4], hist [1 + J][FCN8S_REL_SCORE_BINS][2]
+// and bad [2] are accumulated into.  scores / scales: host arrays of J device pointers / floats.  C >= 2, 1 <= B <= 64, 0 <= J <= 3, P < 2^31.
+void launch_reliability_pair(const float* prob, const uint8_t* gt, const uint8_t* lut, const float* const* scores, const float* scales, int J,
+                             int N, long long P, int C, int B, unsigned long long* calib, unsigned long long* sums, unsigned long long* hist,
+                             unsigned long long* bad, hipStream_t s);
 // boundary.hip (fcn8s_op_boundary_pair; the definition is in fcn8s_hip.h).  One kernel; rings [R + 1][34][34], bprec / brec [R + 2][34] and bad [1] are
 // accumulated into.  1 <= R <= 16, H * W < 2^31.
 void launch_boundary_pair(const uint8_t* gt, const void* pred, int pred_kind, int N, int H, int W, int R, unsigned long long* rings,

@@ -4419,6 +4419,21 @@ int fcn8s_op_cityscapes_pair(void* stream, const uint8_t* gt_label_ids, const ui
                            (unsigned long long*)counts, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
+int fcn8s_op_reliability_pair(void* stream, const float* prob, const uint8_t* gt, const uint8_t* lut, int N, int64_t P, int C,
+                              const float* const* scores, const float* scales, int J, int B,
+                              int64_t* calib, int64_t* sums, int64_t* hist, int64_t* bad)
+{
+    bool ok = prob && gt && lut && calib && sums && hist && bad && N > 0 && P > 0 && C >= 2 && B >= 1 && B <= 64 && J >= 0 && J <= 3
+              && (J == 0 || (scores && scales));
+    for (int j = 0; ok && j < J; ++j) ok = scores[j] && std::isfinite(scales[j]) && scales[j] > 0.f;
+    if (!ok)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "reliability_pair: bad argument (null pointer, N, P <= 0, C < 2, B outside 1 .. 64, J outside 0 .. 3, or a scale that is not finite and positive)");
+    if (P >= (1LL << 31)) return fail(nullptr, FCN8S_ERR_SHAPE, "reliability_pair: an image has to have fewer than 2^31 pixels");
+    take_deferred_error(nullptr);
+    launch_reliability_pair(prob, gt, lut, scores, scales, J, N, P, C, B, (unsigned long long*)calib, (unsigned long long*)sums,
+                            (unsigned long long*)hist, (unsigned long long*)bad, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
 int fcn8s_op_boundary_pair(void* stream, const uint8_t* gt_label_ids, const void* pred, int pred_kind, int N, int H, int W, int R,
                            int64_t* rings, int64_t* bprec, int64_t* brec, int64_t* bad)
 {

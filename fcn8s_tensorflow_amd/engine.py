@@ -967,6 +967,14 @@ class Engine:
                                         out.ctypes.data_as(C.c_void_p), where), self.h)
         return out if argmax or self.logical_classes == self.num_classes else np.ascontiguousarray(out[..., :self.logical_classes])
 
+    def reliability_pair(self, prob, gt, lut, scores=(), scales=(), bins=15, tables=None):
+        """One `fcn8s_op_reliability_pair` call (reliability.py; the definition is in include/fcn8s_hip.h) on device tensors: `prob` float32
+        [N,H,W,C] as `predict(argmax=False)`, `predict_tta`, `predict_crf` and `predict_mc` return it, `gt` uint8 [N,H,W], `lut` 256 uint8
+        (true class = lut[gt]; 255 = ignore), up to 3 float32 uncertainty maps [N,H,W] with their scales.  The counts are accumulated into
+        `tables` (calib, sums, hist, bad: int64 device tensors; None makes zeroed ones), which stay on the device and are returned."""
+        from . import reliability
+        return reliability.counts_device(prob, gt, lut, scores=scores, scales=scales, bins=bins, tables=tables)
+
     # ---- introspection (tests, bench) -----------------------------------------------------------
     def activation(self, name, shape, missing_ok=False):
         """fcn8s_get_activation.  A conv whose output transform was fused with the next conv's input transform (option `fuse_out_in`)

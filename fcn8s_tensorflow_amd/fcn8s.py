@@ -629,6 +629,77 @@ class FCN8s:
             ce.write_result_json(res, json_path)
         return res
 
+    def evaluate_reliability(self, images_dir, ground_truth_search, samples=None, keep_prob=0.5, sample_offset=0, scales=None, flip=False,
+                             crf=None, bins=15, score_max=None, image_file_extension='png', json_path=None):
+        '''Not in the reference: what this model's softmax and uncertainty maps are worth on a Cityscapes-style directory -- calibration
+        (ECE, MCE, the reliability diagram, NLL, Brier score) and error detection (AUROC, AUPR, risk-coverage, AURC and E-AURC of
+        "uncertainty predicts a wrong pixel") -- scored where the predictions already are (reliability.py; `fcn8s_op_reliability_pair`).
+        Files are paired as in `evaluate_cityscapes`; per image: decode, one upload, the prediction on the device with `argmax=False`,
+        upload of the label-id map, one op call.  The softmax never visits the host; the tables stay on the device and are downloaded
+        once at the end.  Pixels whose label has train id 0 (void) are ignored, as in the official evaluation.  Routes:
+        `samples=S`: `predict_uncertainty` (Monte-Carlo dropout at `keep_prob`, `sample_offset`); scores 'maxProb', 'entropy' and
+        'mutualInformation'.  `samples=None` without `scales` / `flip` / `crf`: the same route with one sample and no dropout -- `predict`
+        bit for bit, with the entropy map; scores 'maxProb' and 'entropy'.  With `scales` / `flip` / `crf`: `predict(argmax=False, ...)`,
+        'maxProb' only; `samples` together with them raises ValueError (the Monte-Carlo route has no such passes).  `bins`: confidence
+        bins of the calibration (1..64); `score_max`: the uncertainty that lands in the last of the 1024 histogram bins, default
+        ln(num_classes).  Returns `reliability.Evaluator.results()` plus 'nbPixels' and 'route'; `json_path`: also write it
+        (`reliability.write_result_json`).  Works inside `averaged_weights()`.'''
+        from PIL import Image
+        import torch
+        from . import cityscapes_eval as ce, reliability as rel
+        if self.num_classes != 20:
+            raise ValueError("the Cityscapes evaluation uses the 20 Cityscapes train ids; this model has {} classes.".format(self.num_classes))
+        passes = scales is not None or bool(flip) or crf_mod.resolve(crf) is not None
+        if samples is not None and passes:
+            raise ValueError("`samples` runs the Monte-Carlo dropout route, which has no `scales` / `flip` / `crf` passes; use one or the other.")
+        if samples is not None:
+            route, names = 'mc', ('entropy', 'mutualInformation')
+        elif not passes:
+            route, names, samples, keep_prob, sample_offset = 'single', ('entropy',), 1, 1.0, 0
+        else:
+            route, names = 'passes', ()
+        ev = rel.Evaluator(bins=bins, num_classes=self.num_classes, lut=rel.cityscapes_lut(), score_names=names, score_max=score_max)
+        gts = sorted(glob(ground_truth_search))
+        if not gts:
+            raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
+        walk = ce.walk_predictions(images_dir)
+        paths = [ce.find_prediction(images_dir, g, walk, extension=image_file_extension) for g in gts]
+        dev = self.engine.device
+        pixels = 0
+        kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
+        tr = trange(len(gts), file=sys.stdout)
+        tr.set_description('Evaluating')
+        self.engine.freeze(True)
+        try:
+            for i in tr:
+                image = torch.from_numpy(np.array(Image.open(paths[i]).convert('RGB'))[None]).to(dev)
+                if route == 'passes':
+                    prob, maps = self.predict(image, argmax=False, scales=scales, flip=flip, **kw), ()
+                else:
+                    prob, ent, mi = self.engine.predict_mc(image, samples=samples, keep_prob=keep_prob, sample_offset=sample_offset, argmax=False,
+                                                           entropy=True, mutual_information=route == 'mc')
+                    maps = (ent, mi) if route == 'mc' else (ent,)
+                gt = np.array(Image.open(gts[i]))
+                if prob.shape[2] != gt.shape[1]:
+                    raise ValueError("Image widths of " + paths[i] + " and " + gts[i] + " are not equal.")
+                if prob.shape[1] != gt.shape[0]:
+                    raise ValueError("Image heights of " + paths[i] + " and " + gts[i] + " are not equal.")
+                if gt.ndim != 2 or gt.max() >= ce.NUM_IDS:
+                    raise ValueError("Unknown label with id {:}".format(int(gt.max())))
+                ev.add(prob, torch.from_numpy(gt.astype(np.uint8)[None]).to(dev), maps)
+                pixels += gt.size
+        finally:
+            self.engine.freeze(False)
+        res = ev.results()
+        bad = res["tables"]["bad"]
+        if bad.any():
+            raise ValueError("{} pixels hold a train id outside 0..19 and {} a confidence or uncertainty that is not finite".format(int(bad[0]), int(bad[1])))
+        res["nbPixels"] = pixels
+        res["route"] = route
+        if json_path is not None:
+            rel.write_result_json(res, json_path)
+        return res
+
     def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement, scales=None, flip=False, crf=None):
         '''Loop body of predict_and_save (fcn8s_tensorflow.py:829-855).'''
         from PIL import Image

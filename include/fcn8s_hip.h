@@ -763,6 +763,36 @@ int fcn8s_op_confusion(void* stream, const uint8_t* label_ids, const int64_t* pr
 size_t fcn8s_op_cityscapes_work_bytes(int N);
 int fcn8s_op_cityscapes_pair(void* stream, const uint8_t* gt_label_ids, const uint16_t* gt_instance_ids, const void* pred, int pred_kind,
                              int N, int64_t P, int64_t* conf, void* work, int32_t* entries, int max_entries, int64_t* counts);
+/* The counting half of the calibration and error-detection measures of a softmax against its ground truth (expected calibration error and
+ * reliability diagram: Guo et al., ICML 2017; NLL and Brier score; AUROC / AUPR / risk-coverage of "uncertainty predicts a wrong pixel":
+ * Hendrycks & Gimpel, ICLR 2017, Geifman & El-Yaniv, NeurIPS 2017) for a batch of N images of P pixels each on DEVICE pointers, in one pass that
+ * reads every input byte once.  The measures themselves are taken from the tables in float64 on the host (reliability.py).
+ *   prob [N,P,C] float32, as fcn8s_predict (argmax = 0), fcn8s_predict_tta, fcn8s_predict_crf and fcn8s_predict_mc write it; any C >= 2 and any
+ *   float alignment (16-byte loads are used when the pointer is 16-byte aligned and C % 4 == 0).  gt [N,P] uint8, any alignment; lut: 256 uint8 on
+ *   the device.  scores: HOST array of J DEVICE pointers, 0 <= J <= 3, to float32 [N,P] uncertainty maps (entropy, mutual information, anything
+ *   where larger means less sure; may be NULL when J == 0); scales: HOST array of J floats, each finite and > 0.
+ *   Per pixel, t = lut[gt].  t == 255: the pixel is ignored and counted nowhere.  C <= t < 255: bad[0] += 1 and nothing else.  Otherwise, in fp32,
+ *   no product contracted into a sum:
+ *     k = argmax_c p_c (the lowest index on ties; c replaces the running maximum only if p_c > it, so a NaN at c > 0 never wins), conf = p_k,
+ *     ok = (k == t).  If conf or one of the J scores is NaN or +-inf: bad[1] += 1 and nothing else (the other p_c are not examined).
+ *     b = min(B - 1, (int)(conf * (float)B)), 0 for conf < 0;  calib[b] += {1, ok, q_conf},  q_conf = (int64)rintf(conf * 2^24)
+ *     sums += {1, ok, q_nll, q_brier},  q_nll = (int64)rintf(-logf(max(p_t, FLT_MIN)) * 2^16),
+ *                                       q_brier = (int64)rintf((sum_c (p_c - [c == t])^2, folded in class order from 0) * 2^23)
+ *     Score histograms of M = FCN8S_REL_SCORE_BINS bins in ascending uncertainty: score 0 is u = 1 - conf with scale (float)M (the maximum softmax
+ *     probability baseline), score j >= 1 is the caller's map j - 1 with scales[j - 1];  for a score s with scale sigma:
+ *     bin = s > 0 ? min(M - 1, (int)(s * sigma)) : 0  (a product beyond int's range lands in M - 1);  hist[j][bin][ok ? 0 : 1] += 1.
+ *   The fixed point makes every sum an integer (at most 2^-25, 2^-17, 2^-24 of quantisation per pixel) that is the same bits on every run.
+ *   calib [B][3], sums [4], hist [1 + J][M][2], bad [2], all int64, are accumulated into, over the N images and over calls (the caller clears
+ *   them).  1 <= B <= 64.  Stream-ordered; does not synchronise; allocates nothing; needs no scratch.  FCN8S_ERR_BAD_ARG (nothing launched) for a
+ *   NULL prob / gt / lut / table, N or P <= 0, C < 2, B outside 1..64, J outside 0..3, a NULL scores / scales array or score pointer among the J, a
+ *   scale that is not finite and > 0; FCN8S_ERR_SHAPE for P >= 2^31.
+ *   The kernel takes FCN8S_REL_TILE_PIXELS pixels per block and trip on at most FCN8S_REL_MAX_BLOCKS blocks (more only beyond 2^41 pixels). */
+#define FCN8S_REL_SCORE_BINS 1024
+#define FCN8S_REL_TILE_PIXELS 256
+#define FCN8S_REL_MAX_BLOCKS 1024
+int fcn8s_op_reliability_pair(void* stream, const float* prob, const uint8_t* gt, const uint8_t* lut, int N, int64_t P, int C,
+                              const float* const* scores, const float* scales, int J, int B,
+                              int64_t* calib, int64_t* sums, int64_t* hist, int64_t* bad);
 /* Boundary measures of a segmentation against its ground truth -- the counting half of the trimap IoU (accuracy inside a band of width r around
  * the ground-truth boundaries: Kraehenbuehl & Koltun 2011, Chen et al. 2015) and of the boundary F-score (Csurka et al., BMVC 2013) -- for a batch
  * of N images of H x W pixels on DEVICE pointers.  All integers.
