@@ -393,6 +393,12 @@ void launch_cityscapes_pair(const uint8_t* gt, const uint16_t* inst, const void*
 void launch_reliability_pair(const float* prob, const uint8_t* gt, const uint8_t* lut, const float* const* scores, const float* scales, int J,
                              int N, long long P, int C, int B, unsigned long long* calib, unsigned long long* sums, unsigned long long* hist,
                              unsigned long long* bad, hipStream_t s);
+// temperature.hip (fcn8s_op_temperature_nll / fcn8s_op_temperature_apply; the definition is in fcn8s_hip.h).  One kernel each.  nll [K], count [1] and
+// bad [2] are accumulated into; betas: host array of K floats in [2^-6, 2^6], 1 <= K <= FCN8S_TS_MAX_CANDIDATES.  apply: out (may alias prob) and /
+// or entropy_out, not both null.  C >= 2, P < 2^31.
+void launch_temperature_nll(const float* prob, const uint8_t* gt, const uint8_t* lut, int N, long long P, int C, const float* betas, int K,
+                            unsigned long long* nll, unsigned long long* count, unsigned long long* bad, hipStream_t s);
+void launch_temperature_apply(const float* prob, int N, long long P, int C, float beta, float* out, float* entropy_out, hipStream_t s);
 // boundary.hip (fcn8s_op_boundary_pair; the definition is in fcn8s_hip.h).  One kernel; rings [R + 1][34][34], bprec / brec [R + 2][34] and bad [1] are
 // accumulated into.  1 <= R <= 16, H * W < 2^31.
 void launch_boundary_pair(const uint8_t* gt, const void* pred, int pred_kind, int N, int H, int W, int R, unsigned long long* rings,

@@ -6,6 +6,7 @@
 //                          max(0, h(mean) - mean_s h(p_s)) were asked for.  S = 1 (first and last) touches no accumulator.
 // One thread per pixel, grid-stride loops capped at 2048 blocks, no atomics (every pixel belongs to one thread): two runs give the same bits.
 #include "fcn8s_internal.h"
+#include "entropy_term.h"
 #include <cfloat>
 
 namespace fcn8s {
@@ -22,15 +23,7 @@ static __device__ __forceinline__ long long mc_slot(const PixMap& m, int n, int 
     const int S = m.S, oy = y + S / 2, ox = x + S / 2;
     return ((((long long)n * m.QH + oy / S) * m.QW + ox / S) * S + oy % S) * S + ox % S;
 }
-// One term of h(p) = -sum_c p_c logf(max(p_c, FLT_MIN)), added to the running sum.  THE one place the entropy's arithmetic is written: h(p_s) and
-// h(mean) both fold their classes through it in class order, with contraction off, so the same p gives the same bits in both places (the
-// identity "no dropout -> mutual information == 0.0" rests on that: a multiply-add contracted in one inlined copy and not in the other breaks it).
-static __device__ __forceinline__ float mc_h_add(float h, float p)
-{
-#pragma clang fp contract(off)
-    const float t = p * logf(fmaxf(p, FLT_MIN));
-    return h - t;
-}
+// mc_h_add, the one term of the entropy, lives in entropy_term.h (temperature.hip folds h of a calibrated distribution through it too)
 
 struct McGeom {
     PixMap map; int N, H, W;

@@ -4434,6 +4434,29 @@ int fcn8s_op_reliability_pair(void* stream, const float* prob, const uint8_t* gt
                             (unsigned long long*)hist, (unsigned long long*)bad, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
+static bool temperature_beta_ok(float b) { return std::isfinite(b) && b >= 0.015625f && b <= 64.f; }
+int fcn8s_op_temperature_nll(void* stream, const float* prob, const uint8_t* gt, const uint8_t* lut, int N, int64_t P, int C,
+                             const float* betas, int K, int64_t* nll, int64_t* count, int64_t* bad)
+{
+    bool ok = prob && gt && lut && betas && nll && count && bad && N > 0 && P > 0 && C >= 2 && K >= 1 && K <= FCN8S_TS_MAX_CANDIDATES;
+    for (int k = 0; ok && k < K; ++k) ok = temperature_beta_ok(betas[k]);
+    if (!ok)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "temperature_nll: bad argument (null pointer, N, P <= 0, C < 2, K outside 1 .. 32, or a beta that is not finite or outside [2^-6, 2^6])");
+    if (P >= (1LL << 31)) return fail(nullptr, FCN8S_ERR_SHAPE, "temperature_nll: an image has to have fewer than 2^31 pixels");
+    take_deferred_error(nullptr);
+    launch_temperature_nll(prob, gt, lut, N, P, C, betas, K, (unsigned long long*)nll, (unsigned long long*)count, (unsigned long long*)bad,
+                           (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_temperature_apply(void* stream, const float* prob, int N, int64_t P, int C, float beta, float* out, float* entropy_out)
+{
+    if (!prob || (!out && !entropy_out) || N <= 0 || P <= 0 || C < 2 || !temperature_beta_ok(beta))
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "temperature_apply: bad argument (null prob, both outputs null, N, P <= 0, C < 2, or a beta that is not finite or outside [2^-6, 2^6])");
+    if (P >= (1LL << 31)) return fail(nullptr, FCN8S_ERR_SHAPE, "temperature_apply: an image has to have fewer than 2^31 pixels");
+    take_deferred_error(nullptr);
+    launch_temperature_apply(prob, N, P, C, beta, out, entropy_out, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
 int fcn8s_op_boundary_pair(void* stream, const uint8_t* gt_label_ids, const void* pred, int pred_kind, int N, int H, int W, int R,
                            int64_t* rings, int64_t* bprec, int64_t* brec, int64_t* bad)
 {

@@ -975,6 +975,26 @@ class Engine:
         from . import reliability
         return reliability.counts_device(prob, gt, lut, scores=scores, scales=scales, bins=bins, tables=tables)
 
+    def temperature_nll(self, prob, gt, lut, betas, tables=None):
+        """One `fcn8s_op_temperature_nll` call (temperature.py; the definition is in include/fcn8s_hip.h) on device tensors: the NLL of `prob`
+        (float32 [N,H,W,C], as the predict routes return it with argmax=False) calibrated at each of the up to 32 `betas` = 1 / T (host values)
+        against `gt` uint8 [N,H,W] through `lut` (true class = lut[gt]; 255 = ignore), accumulated into `tables` (int64 [K + 3] on the device:
+        nll [K], count, bad [2]; None makes a zeroed one), which stays on the device and is returned."""
+        from . import temperature
+        return temperature.nll_device(prob, gt, lut, betas, tables=tables)
+
+    def temperature_apply(self, prob, temperature, entropy=False, out=None):
+        """One `fcn8s_op_temperature_apply` call: `prob` (float32 [N,H,W,C]) calibrated at `temperature`.  A device tensor: into `out` (None: a
+        new tensor; `prob` itself: in place; False: not written); a host array is uploaded, and the results come back as arrays.  Returns
+        (calibrated | None, entropy | None): with `entropy`, the entropy [N,H,W] of the calibrated distribution from the same launch."""
+        from . import temperature as ts
+        torch = self.torch
+        if isinstance(prob, torch.Tensor):
+            return ts.apply_device(prob, temperature, entropy=entropy, out=out)
+        dev = torch.from_numpy(np.ascontiguousarray(prob, dtype=np.float32)).to(self.device)
+        q, h = ts.apply_device(dev, temperature, entropy=entropy, out=False if out is False else dev)
+        return (None if q is None else q.cpu().numpy()), (None if h is None else h.cpu().numpy())
+
     # ---- introspection (tests, bench) -----------------------------------------------------------
     def activation(self, name, shape, missing_ok=False):
         """fcn8s_get_activation.  A conv whose output transform was fused with the next conv's input transform (option `fuse_out_in`)

@@ -49,6 +49,7 @@ except Exception:  # pragma: no cover
 
 from . import _lib as L
 from . import crf as crf_mod
+from . import temperature as ts_mod
 from . import loss as loss_mod
 from . import optim as optim_mod
 from . import tf_bundle
@@ -105,6 +106,7 @@ class FCN8s:
         self.training_loss = None
         self.best_training_loss = 99999999.9
         self.g_step = None
+        self.temperature = None          # set by fit_temperature (or restored from a saved model); `predict(temperature=...)` takes it
 
         if device_id is None:
             device_id = int(os.environ.get("LOCAL_RANK", "0"))
@@ -131,6 +133,7 @@ class FCN8s:
                                  device_id=device_id, seed=seed + rank, logical_classes=self.num_classes)
             _load_checkpoint(self.engine, os.path.join(model_load_dir, "variables", "variables.npz"), with_state=True)
             fp8_calibration = meta.get("fp8_calibration")
+            self.temperature = meta.get("temperature")
             if meta.get("ema_decay"):         # behind the checkpoint: a restored shadow is kept, not set to the parameters
                 self.engine.set_ema(meta["ema_decay"], meta.get("ema_warmup", True))
         else:
@@ -454,7 +457,7 @@ class FCN8s:
         self._evaluate(data_generator, metrics, num_batches, l2_regularization, description='Running evaluation')
         self.eval_dataset = dataset
 
-    def predict(self, images, argmax=True, scales=None, flip=False, crf=None):
+    def predict(self, images, argmax=True, scales=None, flip=False, crf=None, temperature=None):
         '''fcn8s_tensorflow.py:743-770.  `images`: array-like of rank 4 (a list of HWC arrays works).
         Returns int64 class ids (N,H,W) or the float32 softmax (N,H,W,C).
         Not in the reference: `scales` (1 to 8 factors in (0, 4]) and / or `flip` average the softmax over resized and mirrored passes
@@ -462,15 +465,24 @@ class FCN8s:
         any size at its own resolution.  Without them, height and width must be multiples of 32, as in the reference.
         `crf` (also not in the reference): refine the (mean) softmax by a mean-field CRF over a local window whose pairwise term reads
         the colours of the uint8 input (crf.py; fcn8s_predict_crf) -- True for the default parameters, a dict of fields or a crf.Params to
-        override them, None / False for no CRF.  Images of any size, as with `scales=(1.0,)`.'''
+        override them, None / False for no CRF.  Images of any size, as with `scales=(1.0,)`.
+        `temperature` (also not in the reference): with `argmax=False`, the returned distribution calibrated at that temperature
+        (temperature.py; one `fcn8s_op_temperature_apply` on the result, whichever route made it) -- `fit_temperature` finds the value and
+        keeps it in `self.temperature`.  None or 1.0, or `argmax=True` (the map cannot change an argmax): nothing is launched.'''
         if isinstance(images, (list, tuple)):
             images = np.asarray(images)
+        if temperature is not None:
+            temperature = ts_mod.validate_temperature(temperature)
         params = crf_mod.resolve(crf)
         if params is not None:
-            return self.engine.predict_crf(images, params, scales=(1.0,) if scales is None else scales, flip=flip, argmax=argmax)
-        if scales is None and not flip:
-            return self.engine.predict(images, argmax=argmax)
-        return self.engine.predict_tta(images, scales=(1.0,) if scales is None else scales, flip=flip, argmax=argmax)
+            out = self.engine.predict_crf(images, params, scales=(1.0,) if scales is None else scales, flip=flip, argmax=argmax)
+        elif scales is None and not flip:
+            out = self.engine.predict(images, argmax=argmax)
+        else:
+            out = self.engine.predict_tta(images, scales=(1.0,) if scales is None else scales, flip=flip, argmax=argmax)
+        if argmax or temperature is None or temperature == 1.0:
+            return out
+        return self.engine.temperature_apply(out, temperature, out=out)[0]
 
     def predict_uncertainty(self, images, samples=20, keep_prob=0.5, argmax=True, sample_offset=0):
         '''Not in the reference: Monte-Carlo dropout inference (mc_dropout.py; fcn8s_predict_mc).  Dropout stays on behind fc6 and fc7,
@@ -630,7 +642,7 @@ class FCN8s:
         return res
 
     def evaluate_reliability(self, images_dir, ground_truth_search, samples=None, keep_prob=0.5, sample_offset=0, scales=None, flip=False,
-                             crf=None, bins=15, score_max=None, image_file_extension='png', json_path=None):
+                             crf=None, bins=15, score_max=None, image_file_extension='png', json_path=None, temperature=None):
         '''Not in the reference: what this model's softmax and uncertainty maps are worth on a Cityscapes-style directory -- calibration
         (ECE, MCE, the reliability diagram, NLL, Brier score) and error detection (AUROC, AUPR, risk-coverage, AURC and E-AURC of
         "uncertainty predicts a wrong pixel") -- scored where the predictions already are (reliability.py; `fcn8s_op_reliability_pair`).
@@ -643,10 +655,21 @@ class FCN8s:
         'maxProb' only; `samples` together with them raises ValueError (the Monte-Carlo route has no such passes).  `bins`: confidence
         bins of the calibration (1..64); `score_max`: the uncertainty that lands in the last of the 1024 histogram bins, default
         ln(num_classes).  Returns `reliability.Evaluator.results()` plus 'nbPixels' and 'route'; `json_path`: also write it
-        (`reliability.write_result_json`).  Works inside `averaged_weights()`.'''
+        (`reliability.write_result_json`).  Works inside `averaged_weights()`.
+        `temperature=T`: score the distribution calibrated at T (`fit_temperature`) -- one `fcn8s_op_temperature_apply` per image, in place;
+        on the single-pass route the 'entropy' score is the calibrated distribution's, from the same launch.  None or 1.0: nothing is
+        launched.  Together with `samples=S` it raises ValueError: calibrating Monte-Carlo samples needs the temperature inside each
+        sample's softmax, which `fcn8s_predict_mc` does not take.'''
         from PIL import Image
         import torch
         from . import cityscapes_eval as ce, reliability as rel
+        if temperature is not None:
+            temperature = ts_mod.validate_temperature(temperature)
+            if samples is not None:
+                raise ValueError("`temperature` with `samples`: calibrating Monte-Carlo samples needs the temperature inside each sample's softmax; "
+                                 "score the single-pass, `scales` / `flip` or `crf` route instead.")
+            if temperature == 1.0:
+                temperature = None
         if self.num_classes != 20:
             raise ValueError("the Cityscapes evaluation uses the 20 Cityscapes train ids; this model has {} classes.".format(self.num_classes))
         passes = scales is not None or bool(flip) or crf_mod.resolve(crf) is not None
@@ -679,6 +702,9 @@ class FCN8s:
                     prob, ent, mi = self.engine.predict_mc(image, samples=samples, keep_prob=keep_prob, sample_offset=sample_offset, argmax=False,
                                                            entropy=True, mutual_information=route == 'mc')
                     maps = (ent, mi) if route == 'mc' else (ent,)
+                if temperature is not None:
+                    _, ent_q = self.engine.temperature_apply(prob, temperature, entropy=route == 'single', out=prob)
+                    maps = (ent_q,) if route == 'single' else ()
                 gt = np.array(Image.open(gts[i]))
                 if prob.shape[2] != gt.shape[1]:
                     raise ValueError("Image widths of " + paths[i] + " and " + gts[i] + " are not equal.")
@@ -698,6 +724,71 @@ class FCN8s:
         res["route"] = route
         if json_path is not None:
             rel.write_result_json(res, json_path)
+        return res
+
+    def fit_temperature(self, images_dir, ground_truth_search, scales=None, flip=False, crf=None, passes=2, candidates=32, t_min=0.125, t_max=8.0,
+                        image_file_extension='png', json_path=None):
+        '''Not in the reference: temperature scaling (Guo et al., ICML 2017; temperature.py), the remedy for what `evaluate_reliability`
+        measures.  Fits the one scalar T that minimises the NLL of the calibrated distribution on a Cityscapes-style directory and keeps
+        it in `self.temperature` (`save` stores it; `predict(..., temperature=model.temperature)` and
+        `evaluate_reliability(..., temperature=...)` apply it).  Files are paired, the weights frozen and every image predicted on the
+        device exactly as `evaluate_reliability` does on its single-pass route (no `scales` / `flip` / `crf`) or its passes route; per image
+        one `fcn8s_op_temperature_nll` call evaluates all `candidates` (3..32) temperatures of the sweep's grid on the softmax where it is.
+        `passes` sweeps over the files: the first grid is log-spaced over [t_min, t_max] and contains T = 1, each later one spans the two
+        neighbours of the minimum (the NLL is convex in 1 / T).  K + 3 integers come back to the host per sweep.  Pixels whose label has
+        train id 0 (void) are ignored.  Returns 'temperature', 'atBound' (the minimum is t_min or t_max: widen the range), 'nllBefore'
+        (T = 1) and 'nllAfter' (means per counted pixel), 'candidates' (per sweep the list of (T, mean NLL)), 'pixels', 'nbPixels' and
+        'route'; `json_path`: also write it.  Works inside `averaged_weights()`.'''
+        from PIL import Image
+        import torch
+        from . import cityscapes_eval as ce, reliability as rel
+        if self.num_classes != 20:
+            raise ValueError("the Cityscapes evaluation uses the 20 Cityscapes train ids; this model has {} classes.".format(self.num_classes))
+        ts_mod.validate_fit(passes, candidates, t_min, t_max)
+        route = 'passes' if scales is not None or bool(flip) or crf_mod.resolve(crf) is not None else 'single'
+        gts = sorted(glob(ground_truth_search))
+        if not gts:
+            raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
+        walk = ce.walk_predictions(images_dir)
+        paths = [ce.find_prediction(images_dir, g, walk, extension=image_file_extension) for g in gts]
+        dev = self.engine.device
+        kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
+        lut = rel.cityscapes_lut()
+        nb = [0]
+
+        def sweep(betas):
+            fitter = ts_mod.Fitter(betas, lut, num_classes=self.num_classes)
+            nb[0] = 0
+            tr = trange(len(gts), file=sys.stdout)
+            tr.set_description('Fitting temperature')
+            for i in tr:
+                image = torch.from_numpy(np.array(Image.open(paths[i]).convert('RGB'))[None]).to(dev)
+                if route == 'passes':
+                    prob = self.predict(image, argmax=False, scales=scales, flip=flip, **kw)
+                else:
+                    prob = self.engine.predict_mc(image, samples=1, keep_prob=1.0, sample_offset=0, argmax=False, entropy=False,
+                                                  mutual_information=False)[0]
+                gt = np.array(Image.open(gts[i]))
+                if prob.shape[2] != gt.shape[1]:
+                    raise ValueError("Image widths of " + paths[i] + " and " + gts[i] + " are not equal.")
+                if prob.shape[1] != gt.shape[0]:
+                    raise ValueError("Image heights of " + paths[i] + " and " + gts[i] + " are not equal.")
+                if gt.ndim != 2 or gt.max() >= ce.NUM_IDS:
+                    raise ValueError("Unknown label with id {:}".format(int(gt.max())))
+                fitter.add(prob, torch.from_numpy(gt.astype(np.uint8)[None]).to(dev))
+                nb[0] += gt.size
+            return fitter.result()
+
+        self.engine.freeze(True)
+        try:
+            res = ts_mod.fit(sweep, passes=passes, candidates=candidates, t_min=t_min, t_max=t_max)
+        finally:
+            self.engine.freeze(False)
+        res["nbPixels"] = nb[0]
+        res["route"] = route
+        self.temperature = res["temperature"]
+        if json_path is not None:
+            ts_mod.write_result_json(res, json_path)
         return res
 
     def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement, scales=None, flip=False, crf=None):
@@ -769,11 +860,11 @@ class FCN8s:
                     raise AssertionError("Export directory already exists. Please specify a different export directory: {}".format(target))
                 os.makedirs(os.path.join(target, 'variables'))
                 _save_checkpoint(self.engine, os.path.join(target, 'variables', 'variables.npz'))
-                _write_meta(target, self.engine, tags)
+                _write_meta(target, self.engine, tags, self.temperature)
             else:
                 os.makedirs(target, exist_ok=True)
                 _save_checkpoint(self.engine, os.path.join(target, 'variables.npz'))
-                _write_meta(target, self.engine, tags)      # (the reference builds a fresh Saver per save() call, :927-934, so its
+                _write_meta(target, self.engine, tags, self.temperature)      # (the reference builds a fresh Saver per save() call, :927-934, so its
                                                             #  max_to_keep=5 never deletes an earlier checkpoint: nothing is pruned here either)
         self.last_saved_model_name = model_name
 
@@ -876,7 +967,7 @@ def _load_tf_tensors(engine, tensors, with_state=True):
             break
 
 
-def _write_meta(target, engine, tags):
+def _write_meta(target, engine, tags, temperature=None):
     meta = {'format': 'fcn8s_tensorflow_amd/1', 'num_classes': engine.logical_classes, 'widths': list(engine.widths),
             'fc6_ksize': engine.specs['fc6/weights'][0][0], 'tags': list(tags) if tags else None,
             'global_step': engine.global_step}
@@ -887,6 +978,8 @@ def _write_meta(target, engine, tags):
     cal = engine.fp8_calibration()
     if cal is not None:                   # the 'fp8_infer' calibration (float32 values, stored exactly as Python floats)
         meta['fp8_calibration'] = [float(v) for v in cal]
+    if temperature is not None:           # the fitted temperature of fit_temperature
+        meta['temperature'] = float(temperature)
     with open(os.path.join(target, 'fcn8s_meta.json'), 'w') as f:
         json.dump(meta, f)
 

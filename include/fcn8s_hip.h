@@ -793,6 +793,37 @@ int fcn8s_op_cityscapes_pair(void* stream, const uint8_t* gt_label_ids, const ui
 int fcn8s_op_reliability_pair(void* stream, const float* prob, const uint8_t* gt, const uint8_t* lut, int N, int64_t P, int C,
                               const float* const* scores, const float* scales, int J, int B,
                               int64_t* calib, int64_t* sums, int64_t* hist, int64_t* bad);
+/* Temperature scaling (Guo et al., ICML 2017): the remedy for what fcn8s_op_reliability_pair measures.  One scalar T is fitted on a validation set by
+ * minimising the NLL of the calibrated distribution and then applied; the argmax never changes.  The map acts on a distribution, so it applies to
+ * whatever a route returns (single pass, multi-scale / flip mean, CRF output).  For beta = 1 / T and a row p of C floats, in fp32 with the natural
+ * logarithm, no product contracted into a sum:
+ *     l_c = logf(max(p_c, FLT_MIN));   m = max_c l_c;   d_c = l_c - m        (d of the argmax is exactly 0)
+ *     e_c = expf(beta * d_c);          s = sum_c e_c   folded in class order from 0   (s >= 1)
+ *     q_c = e_c / s                                    the calibrated distribution
+ *     nll(beta) = logf(s) - beta * d_t                 (>= 0), t = the true class
+ *   For a single-pass softmax this is softmax(z / T) exactly in real arithmetic.  nll is convex in beta, so a bracketing grid search is safe (the
+ *   host side of the fit is temperature.py).  The kernels evaluate e_c as v_exp_f32(fl(beta * log2(e)) * d_c); temperature.hip bounds the difference.
+ * fcn8s_op_temperature_nll: the objective for K candidates in one pass over a batch of N images of P pixels each on DEVICE pointers.
+ *   prob [N,P,C] float32, any C >= 2 and any float alignment; gt [N,P] uint8, any alignment; lut: 256 uint8 on the device; betas: HOST array of K
+ *   floats, 1 <= K <= FCN8S_TS_MAX_CANDIDATES, each finite and in [2^-6, 2^6].  Per pixel, t = lut[gt].  t == 255: the pixel is ignored.
+ *   C <= t < 255: bad[0] += 1 and nothing else.  Any p_c NaN or +-inf (tested before the clamp): bad[1] += 1 and nothing else.  Otherwise
+ *   count += 1 and, for every k, nll[k] += (int64)rintf(nll(beta_k) * 2^16); the l_c and d_c are formed once per pixel for all K candidates.
+ *   nll [K], count [1], bad [2], all int64, are accumulated into, over the N images and over calls (the caller clears them).  Integers only: two
+ *   runs give the same bits and any partition of the pixels over calls gives the same tables.  Stream-ordered; does not synchronise; allocates
+ *   nothing; needs no scratch.  FCN8S_ERR_BAD_ARG (nothing launched) for a NULL pointer, N or P <= 0, C < 2, K outside 1..32, a beta that is not
+ *   finite or outside [2^-6, 2^6]; FCN8S_ERR_SHAPE for P >= 2^31.
+ * fcn8s_op_temperature_apply: out [N,P,C] (may be NULL; may be prob itself: in place) = q, entropy_out [N,P] (may be NULL) = h(q) =
+ *   -sum_c q_c logf(max(q_c, FLT_MIN)) folded in class order (the arithmetic of fcn8s_predict_mc's entropy).  A row that holds a NaN or +-inf
+ *   becomes all NaN, with NaN entropy, so that a later fcn8s_op_reliability_pair counts it in bad[1].  beta as above.  Stream-ordered; does not
+ *   synchronise; allocates nothing.  FCN8S_ERR_BAD_ARG (nothing launched) for a NULL prob, both outputs NULL, N or P <= 0, C < 2, a beta out of
+ *   range; FCN8S_ERR_SHAPE for P >= 2^31.
+ *   Both kernels take FCN8S_TS_TILE_PIXELS pixels per block and trip on at most FCN8S_TS_MAX_BLOCKS blocks. */
+#define FCN8S_TS_MAX_CANDIDATES 32
+#define FCN8S_TS_TILE_PIXELS 256
+#define FCN8S_TS_MAX_BLOCKS 1024
+int fcn8s_op_temperature_nll(void* stream, const float* prob, const uint8_t* gt, const uint8_t* lut, int N, int64_t P, int C,
+                             const float* betas, int K, int64_t* nll, int64_t* count, int64_t* bad);
+int fcn8s_op_temperature_apply(void* stream, const float* prob, int N, int64_t P, int C, float beta, float* out, float* entropy_out);
 /* Boundary measures of a segmentation against its ground truth -- the counting half of the trimap IoU (accuracy inside a band of width r around
  * the ground-truth boundaries: Kraehenbuehl & Koltun 2011, Chen et al. 2015) and of the boundary F-score (Csurka et al., BMVC 2013) -- for a batch
  * of N images of H x W pixels on DEVICE pointers.  All integers.
