@@ -190,13 +190,12 @@ struct fcn8s_model {
     int bf16_acts = 1;                                                    // option: bf16_train training passes keep a conv -> conv activation only as the consumer's padded bf16 copy (the producer's epilogue writes it; no fp32 tensor, no conversion pass)
     // FCN8S_PREC_FP8_INFER: the calibration (per FP8 layer the max |input| of the fp32 pass; it describes the parameters, not the mode), the device scratch of
     // fcn8s_fp8_calibrate, the e4m3 copies (kept with the workspace) and the weight banks (valid across passes only while frozen: w8_valid)
-    bool fp8_calibrated = false, fp8_calibrating = false; float fp8_amax[FCN8S_FP8_LAYERS] = {}; DeviceBuf<unsigned> d_fp8_amax;
+    bool fp8_calibrated = false; float fp8_amax[FCN8S_FP8_LAYERS] = {}; DeviceBuf<unsigned> d_fp8_amax;
     std::map<std::string, Q8Buf> q8;
     std::map<std::string, W8Bank> w8; std::set<std::string> w8_valid;
     int saved_wino_min_cin = -1, saved_wino_fc6 = -1;                      // the options the mode overrides (the direct path carries it), restored on leaving
     int bf16_copy_by_transform = 1;                                       // option: 0 = every bf16 layer converts its input with a pass of its own (round 3's path)
     int64_t ws_allocs = 0;                                                // statistic "workspace_allocations": device allocations for the workspace, the TTA scratch, the bf16 copies and the cached filter banks
-    bool x0_ready = false;                                                // forward(): x0 is already written (fcn8s_predict_tta's tta_input), skip the preprocess kernel
     DeviceBuf<char> crf_buf;                                              // fcn8s_predict_crf: staged images, the mean softmax, the two mean-field buffers, staged output (grown, never shrunk)
     DeviceBuf<char> tta_buf;                                              // fcn8s_predict_tta: staged images, accumulator, staged output (grown, never shrunk)
     DeviceBuf<char> mc_buf;                                               // fcn8s_predict_mc: staged images, the two accumulators, staged outputs (grown, never shrunk)
@@ -1937,13 +1936,18 @@ static FwdStep fwd_fc(fcn8s_model* m, const float* x, float keep_prob, bool trai
     return FwdStep{};
 }
 
-int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, bool train, const McLoop* mc = nullptr)
+// What one forward() call is asked for: a training pass or a prediction pass, its dropout, x0 already written (tta_input ran: the preprocess kernel is
+// skipped), fcn8s_fp8_calibrate's fp32 pass of the fp8_infer mode, fcn8s_predict_mc's sample loop
+struct FwdCall { float keep_prob = 1.f; bool train = false, x0_written = false, calibrating = false; const McLoop* mc = nullptr; };
+
+int forward(fcn8s_model* m, const void* img_dev, int dtype, const FwdCall& call)
 {
+    const float keep_prob = call.keep_prob; const bool train = call.train; const McLoop* mc = call.mc;
     t_deterministic = m->deterministic;
     hipStream_t s = m->stream;
     const int N = m->N, H = m->H, W = m->W, C = m->C;
     // FCN8S_PREC_FP8_INFER: evaluation / prediction through the e4m3 kernels; the calibration pass (fcn8s_fp8_calibrate) is the fp32 direct path
-    const bool fp8 = fp8_mode(m) && !train && !m->fp8_calibrating;
+    const bool fp8 = fp8_mode(m) && !train && !call.calibrating;
     if (fp8 && !m->fp8_calibrated)
         return fail(m, FCN8S_ERR_STATE, "fp8_infer: the model has no FP8 calibration (never calibrated, or its parameters changed since): run fcn8s_fp8_calibrate "
                                         "(Engine.calibrate_fp8 / FCN8s.calibrate_fp8) or restore one with fcn8s_fp8_set_calibration first");
@@ -1977,7 +1981,7 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
     // layer by layer for the tile kernel: 13.3 -> 9.3 ms per 16 x 1024x512 batch, 1.55 -> 1.18 ms per single image (profiles/r06_bf16_infer.txt).  Same products in the same order as the training pass:
     // its logits are the training pass's bit for bit (keep_prob 1).  What it keeps for a backward pass that never comes (routing bytes) costs one byte per window.
     const Bf16Opts bo = bf16_opts(m, train);          // (read by the bf16_train branches alone.  bo.copies: a training pass, or option bf16_infer_copies)
-    if (!m->x0_ready) { ProfScope ps(m, "preprocess", 0, (double)N * H * W * (16 + (dtype ? 12 : 3))); launch_preprocess(img_dev, dtype, A(m, "x0"), (long long)N * H * W, s); }
+    if (!call.x0_written) { ProfScope ps(m, "preprocess", 0, (double)N * H * W * (16 + (dtype ? 12 : 3))); launch_preprocess(img_dev, dtype, A(m, "x0"), (long long)N * H * W, s); }
     const float* x = A(m, "x0");
     size_t k = 0;
     for (int b = 0; b < 5; ++b) {
@@ -2041,14 +2045,99 @@ int forward(fcn8s_model* m, const void* img_dev, int dtype, float keep_prob, boo
         hipEventSynchronize(m->fp_event);
         if (*m->h_fp != m->frozen_fp) {            // the parameters changed behind the library's back: this pass used stale banks -- again, without them
             drop_banks(m);
-            return forward(m, img_dev, dtype, keep_prob, train, mc);
+            return forward(m, img_dev, dtype, call);
         }
     }
     m->have_forward = true; m->train_mode = train; m->keep_prob = keep_prob; m->mc_masks = mc != nullptr;
     return FCN8S_OK;
 }
 
-const char* kDecoderKernels[6] = {"pool3_1x1/kernel", "pool4_1x1/kernel", "fc7_1x1/kernel", "fc7_conv2d_trans/kernel",
+// forward() as an entry point runs it: with the thread's deferred-error slot empty in front (a call that returned early on this thread may have left it
+// set), and what a launcher deferred during the pass as the result
+int run_forward(fcn8s_model* m, const void* img_dev, int dtype, const FwdCall& call)
+{
+    take_deferred_error(nullptr);
+    const int rc = forward(m, img_dev, dtype, call);
+    if (rc) { take_deferred_error(nullptr); return rc; }
+    return deferred_rc(m);
+}
+// One whole pass over a batch of the caller's: the workspace for its shape, the inputs on the device (*lab_dev: where the labels are), forward()
+int run_pass(fcn8s_model* m, const void* images, int dtype, const uint8_t* labels, int N, int H, int W, int where, const FwdCall& call,
+             const uint8_t** lab_dev = nullptr)
+{
+    int rc = ensure_workspace(m, N, H, W); if (rc) return rc;
+    const void* img; const uint8_t* lab;
+    rc = stage_inputs(m, images, dtype, labels, where, &img, &lab); if (rc) return rc;
+    if (lab_dev) *lab_dev = lab;
+    return run_forward(m, img, dtype, call);
+}
+
+// ---- what fcn8s_predict_tta, fcn8s_predict_mc and fcn8s_predict_crf share ----------------------------------------------------------------
+// A call of several passes runs with frozen parameters: each transformed filter bank is built once and every pass after the first reuses it.  A model
+// that was not frozen keeps the banks' storage after the call with its contents marked stale (bank_stale, banks_stale; fp8_infer: its weight banks
+// are re-quantized): the next call rebuilds each bank once into it, allocating nothing.  Whichever way the call returns.
+struct FrozenForCall {
+    fcn8s_model* const m; const bool was_frozen;
+    explicit FrozenForCall(fcn8s_model* model) : m(model), was_frozen(model->frozen) { m->frozen = true; }
+    ~FrozenForCall()
+    {
+        if (was_frozen) return;
+        for (auto& kv : m->u_cache) m->bank_stale.insert("u:" + kv.first);
+        for (auto& kv : m->wbf16_cache) m->bank_stale.insert("w:" + kv.first);
+        m->banks_stale = true;
+        m->w8_valid.clear();
+        m->frozen = false;
+    }
+};
+
+// A call's scratch in one of the model's grown-only buffers: take() every item in its order (each starts 256-byte aligned), grow() once, then ptr()
+// resolves an item (nullptr for one of 0 bytes).  A call that takes nothing allocates nothing.
+struct Scratch {
+    DeviceBuf<char>& buf; size_t total = 0;
+    struct Item { size_t off = 0, bytes = 0; };
+    Item take(size_t bytes) { const Item it{total, bytes}; total += align_up(bytes, 256); return it; }
+    bool grow(fcn8s_model* m) { return !total || buf.grow(total, m->stream, &m->ws_allocs); }
+    template <class T> T* ptr(const Item& it) const { return it.bytes ? (T*)(buf.get() + it.off) : nullptr; }
+};
+
+// The host / device boundary of a prediction call.  FCN8S_HOST: the images and every output that was asked for are items of the scratch, staged in
+// by stage() and copied out by copy_out(); FCN8S_DEVICE: the caller's own pointers, and neither takes a byte.  input() / output() in the scratch's order.
+struct PredictIo {
+    fcn8s_model* m; Scratch& sc; const bool host;
+    struct Port { void* user = nullptr; size_t bytes = 0; Scratch::Item item; } in, outs[3];
+    int nouts = 0;
+    PredictIo(fcn8s_model* model, Scratch& scratch, int where) : m(model), sc(scratch), host(where == FCN8S_HOST) {}
+    void input(const void* images, size_t bytes) { in = Port{const_cast<void*>(images), bytes, sc.take(host ? bytes : 0)}; }
+    int output(void* user, size_t bytes) { outs[nouts] = Port{user, bytes, sc.take(host && user ? bytes : 0)}; return nouts++; }
+    // (behind sc.grow())
+    const void* images_dev() const { return host ? sc.ptr<void>(in.item) : in.user; }
+    int stage() { if (host) HIPCHK(m, hipMemcpyAsync(sc.ptr<void>(in.item), in.user, in.bytes, hipMemcpyHostToDevice, m->stream)); return FCN8S_OK; }
+    void* dev(int o) const { return host ? sc.ptr<void>(outs[o].item) : outs[o].user; }          // (nullptr: this output was not asked for)
+    void split(int o, bool argmax, float** sm, long long** am) const { *sm = argmax ? nullptr : (float*)dev(o); *am = argmax ? (long long*)dev(o) : nullptr; }
+    int copy_out()
+    {
+        for (int o = 0; host && o < nouts; ++o)
+            if (outs[o].user) HIPCHK(m, hipMemcpyAsync(outs[o].user, dev(o), outs[o].bytes, hipMemcpyDeviceToHost, m->stream));
+        if (host) HIPCHK(m, hipStreamSynchronize(m->stream));
+        return FCN8S_OK;
+    }
+};
+
+// The refusals they share, under the caller's name; each caller keeps its own rules between them, in its own order
+int check_predict_args(fcn8s_model* m, const char* who, int dtype, int where)
+{
+    if (dtype != FCN8S_IMG_U8 && dtype != FCN8S_IMG_F32) return fail(m, FCN8S_ERR_BAD_ARG, std::string(who) + ": unknown image dtype");
+    if (where != FCN8S_HOST && where != FCN8S_DEVICE) return fail(m, FCN8S_ERR_BAD_ARG, std::string(who) + ": `where` must be FCN8S_HOST or FCN8S_DEVICE");
+    return FCN8S_OK;
+}
+int check_predict_shape(fcn8s_model* m, const char* who, int N, int H, int W)
+{ return N <= 0 || H <= 0 || W <= 0 ? fail(m, FCN8S_ERR_SHAPE, std::string(who) + ": N, H and W must be positive") : FCN8S_OK; }
+int check_padded_shape(fcn8s_model* m, const char* who, const char* which, int N, int Hp, int Wp)
+{ return (double)N * Hp * Wp > (double)(1LL << 31) ? fail(m, FCN8S_ERR_SHAPE, std::string(who) + ": " + which + " padded shape is too large to plan") : FCN8S_OK; }
+// how the last pass's logits (LG) are laid out: the blocked layout of the GEMM route, or plain NHWC over the padded map
+PixMap logits_map(fcn8s_model* m, int Hp, int Wp) { return LGM(m) ? *LGM(m) : PixMap{0, Hp, Wp, 0, 0, 0}; }
+
+const char* kDecoderKernels[6] ={"pool3_1x1/kernel", "pool4_1x1/kernel", "fc7_1x1/kernel", "fc7_conv2d_trans/kernel",
                                   "fc7_pool4_conv2d_trans/kernel", "fc7_pool4_pool3_conv2d_trans/kernel"};
 
 // the scratch of a configured training loss (fcn8s_set_loss, fcn8s_set_boundary_loss) in its effective mode: state + histograms, and for OHEM
@@ -2488,20 +2577,15 @@ int fcn8s_fp8_calibrate(fcn8s_model* m, const void* images, int dtype, int N, in
 {
     if (!m || !images) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_fp8_calibrate: null argument");
     if (!fp8_mode(m)) return fail(m, FCN8S_ERR_STATE, "fcn8s_fp8_calibrate: set the fp8_infer precision first (fcn8s_set_precision(m, FCN8S_PREC_FP8_INFER))");
-    int rc = ensure_workspace(m, N, H, W); if (rc) return rc;
-    const void* img; const uint8_t* lab;
-    rc = stage_inputs(m, images, dtype, nullptr, where, &img, &lab); if (rc) return rc;
+    int rc = check_shape(m, N, H, W); if (rc) return rc;          // (a refused shape allocates nothing)
+    // the amax scratch, in front of the pass: nothing on the stream touches it before launch_amax below
     if (!m->d_fp8_amax.grow(FCN8S_FP8_LAYERS * sizeof(unsigned), m->stream)) return fail(m, FCN8S_ERR_OOM, "fcn8s_fp8_calibrate: out of device memory");
     float start[FCN8S_FP8_LAYERS] = {};
     if (!reset && m->fp8_calibrated) memcpy(start, m->fp8_amax, sizeof start);
     HIPCHK(m, hipStreamSynchronize(m->stream));
     HIPCHK(m, hipMemcpy(m->d_fp8_amax, start, sizeof start, hipMemcpyHostToDevice));
-    take_deferred_error(nullptr);
-    m->fp8_calibrating = true;
-    rc = forward(m, img, dtype, 1.0f, false);
-    m->fp8_calibrating = false;
-    if (rc) { take_deferred_error(nullptr); return rc; }
-    rc = deferred_rc(m); if (rc) return rc;
+    FwdCall call; call.calibrating = true;
+    rc = run_pass(m, images, dtype, nullptr, N, H, W, where, call); if (rc) return rc;
     {
         double by = 0;
         for (int L = 0; L < FCN8S_FP8_LAYERS; ++L) by += 4.0 * N * (H / kFp8InDiv[L]) * (W / kFp8InDiv[L]) * m->widths[kFp8InWidth[L]];
@@ -2719,12 +2803,9 @@ int fcn8s_forward_loss(fcn8s_model* m, const void* images, int dtype, const uint
     fp8_clear_calibration(m);
     if (!m || !images || !labels) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_forward_loss: null argument");
     if (!(keep_prob > 0.f && keep_prob <= 1.f)) return fail(m, FCN8S_ERR_BAD_ARG, "keep_prob must be in (0, 1]");
-    int rc = ensure_workspace(m, N, H, W); if (rc) return rc;
-    const void* img; const uint8_t* lab;
-    rc = stage_inputs(m, images, dtype, labels, where, &img, &lab); if (rc) return rc;
-    take_deferred_error(nullptr);                      // (a slot left set by a call that returned early on this thread)
-    rc = forward(m, img, dtype, keep_prob, true); if (rc) { take_deferred_error(nullptr); return rc; }
-    rc = deferred_rc(m); if (rc) return rc;
+    FwdCall call; call.keep_prob = keep_prob; call.train = true;
+    const uint8_t* lab;
+    int rc = run_pass(m, images, dtype, labels, N, H, W, where, call, &lab); if (rc) return rc;
     rc = compute_loss(m, lab, l2_rate, true); if (rc) return rc;
     m->next_bucket = 0;
     for (int b = 0; b < kNumBuckets; ++b) m->acc_taken[b] = false;
@@ -3392,12 +3473,8 @@ int fcn8s_eval_step(fcn8s_model* m, const void* images, int dtype, const uint8_t
                     float l2_rate, int where)
 {
     if (!m || !images || !labels) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_eval_step: null argument");
-    int rc = ensure_workspace(m, N, H, W); if (rc) return rc;
-    const void* img; const uint8_t* lab;
-    rc = stage_inputs(m, images, dtype, labels, where, &img, &lab); if (rc) return rc;
-    take_deferred_error(nullptr);
-    rc = forward(m, img, dtype, 1.0f, false); if (rc) { take_deferred_error(nullptr); return rc; }
-    rc = deferred_rc(m); if (rc) return rc;
+    const uint8_t* lab;
+    int rc = run_pass(m, images, dtype, labels, N, H, W, where, FwdCall{}, &lab); if (rc) return rc;
     rc = compute_loss(m, lab, l2_rate, false); if (rc) return rc;
     const long long npix = (long long)N * H * W;
     { ProfScope ps(m, "softmax_argmax", 0, (double)npix * (m->C * 4 + 8)); launch_softmax_argmax(LG(m), nullptr, m->d_pred, npix, m->C, m->stream, LGM(m), m->N); }
@@ -3468,12 +3545,7 @@ int fcn8s_metrics_get_ex(fcn8s_model* m, double* mean_loss, double* mean_iou, do
 int fcn8s_predict(fcn8s_model* m, const void* images, int dtype, int N, int H, int W, int argmax, void* out, int where)
 {
     if (!m || !images || !out) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict: null argument");
-    int rc = ensure_workspace(m, N, H, W); if (rc) return rc;
-    const void* img; const uint8_t* lab;
-    rc = stage_inputs(m, images, dtype, nullptr, where, &img, &lab); if (rc) return rc;
-    take_deferred_error(nullptr);
-    rc = forward(m, img, dtype, 1.0f, false); if (rc) { take_deferred_error(nullptr); return rc; }
-    rc = deferred_rc(m); if (rc) return rc;
+    int rc = run_pass(m, images, dtype, nullptr, N, H, W, where, FwdCall{}); if (rc) return rc;
     const long long npix = (long long)N * H * W;
     if (where == FCN8S_DEVICE) {
         ProfScope ps(m, "softmax_argmax", 0, (double)npix * (m->C * 4 + 8));
@@ -3498,16 +3570,14 @@ int fcn8s_predict(fcn8s_model* m, const void* images, int dtype, int N, int H, i
 // bit-exact with resample_u8), mirrored, preprocessed and zero padded to Hp x Wp = 32 ceil(Hs / 32) x 32 ceil(Ws / 32) by tta_input straight into x0;
 // the predict forward; tta_accumulate reads the logits over [0,Hs)x[0,Ws) through the PixMap, un-mirrors, resizes them to H x W (half-pixel
 // bilinear), softmaxes and sums in pass order; the last pass writes the mean (or its argmax).  All passes share one arena sized for the largest,
-// and the call runs with frozen parameters: each transformed filter bank is built once.  A model that was not frozen keeps the banks' storage
-// after the call with its contents marked stale (bank_stale): the next call rebuilds each bank once into it, allocating nothing.
+// and the call runs with frozen parameters (FrozenForCall).
 int fcn8s_predict_tta(fcn8s_model* m, const void* images, int dtype, int N, int H, int W, const float* scales, int nscales, int flip,
                       int argmax, void* out, int where)
 {
     if (!m || !images || !out || !scales) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_tta: null argument");
-    if (dtype != FCN8S_IMG_U8 && dtype != FCN8S_IMG_F32) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_tta: unknown image dtype");
-    if (where != FCN8S_HOST && where != FCN8S_DEVICE) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_tta: `where` must be FCN8S_HOST or FCN8S_DEVICE");
+    int rc = check_predict_args(m, "fcn8s_predict_tta", dtype, where); if (rc) return rc;
     if (nscales < 1 || nscales > 8) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_tta: between 1 and 8 scales");
-    if (N <= 0 || H <= 0 || W <= 0) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_tta: N, H and W must be positive");
+    rc = check_predict_shape(m, "fcn8s_predict_tta", N, H, W); if (rc) return rc;
     int hs[8], ws[8], hp[8], wp[8];
     for (int k = 0; k < nscales; ++k) {
         const float sc = scales[k];
@@ -3517,7 +3587,7 @@ int fcn8s_predict_tta(fcn8s_model* m, const void* images, int dtype, int N, int 
         hp[k] = (hs[k] + 31) / 32 * 32; wp[k] = (ws[k] + 31) / 32 * 32;
         if (dtype == FCN8S_IMG_F32 && (hs[k] != H || ws[k] != W))
             return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_tta: float32 images are taken only when no pass resizes them (every scale maps H x W to itself)");
-        if ((double)N * hp[k] * wp[k] > (double)(1LL << 31)) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_tta: a pass's padded shape is too large to plan");
+        rc = check_padded_shape(m, "fcn8s_predict_tta", "a pass's", N, hp[k], wp[k]); if (rc) return rc;
     }
     flip = flip ? 1 : 0;
     // the identity case is fcn8s_predict itself (bit for bit)
@@ -3534,133 +3604,85 @@ int fcn8s_predict_tta(fcn8s_model* m, const void* images, int dtype, int N, int 
     }
     // scratch: the staged images (host input), the accumulator (P > 1), the staged output (host output)
     const size_t npix = (size_t)N * H * W, eb = dtype == FCN8S_IMG_U8 ? 1 : 4;
-    const size_t b_img = where == FCN8S_HOST ? align_up(npix * 3 * eb, 256) : 0, b_acc = P > 1 ? align_up(npix * C * sizeof(float), 256) : 0;
-    const size_t b_out = where == FCN8S_HOST ? align_up(argmax ? npix * sizeof(long long) : npix * C * sizeof(float), 256) : 0;
-    if (b_img + b_acc + b_out && !m->tta_buf.grow(b_img + b_acc + b_out, m->stream, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "fcn8s_predict_tta: its scratch cannot be allocated");
+    Scratch sc{m->tta_buf}; PredictIo io(m, sc, where);
+    io.input(images, npix * 3 * eb);
+    const Scratch::Item i_acc = sc.take(P > 1 ? npix * C * sizeof(float) : 0);
+    const int o = io.output(out, argmax ? npix * sizeof(long long) : npix * C * sizeof(float));
+    if (!sc.grow(m)) return fail(m, FCN8S_ERR_OOM, "fcn8s_predict_tta: its scratch cannot be allocated");
+    rc = io.stage(); if (rc) return rc;
     hipStream_t s = m->stream;
-    const void* img = images;
-    if (where == FCN8S_HOST) { HIPCHK(m, hipMemcpyAsync(m->tta_buf, images, npix * 3 * eb, hipMemcpyHostToDevice, s)); img = m->tta_buf; }
-    float* acc = b_acc ? (float*)(m->tta_buf + b_img) : nullptr;
-    void* dout = where == FCN8S_HOST ? (void*)(m->tta_buf + b_img + b_acc) : out;
-    float* sm = argmax ? nullptr : (float*)dout;
-    long long* am = argmax ? (long long*)dout : nullptr;
-    const bool was_frozen = m->frozen;
-    m->frozen = true;                     // the parameters are constant for the call: every pass after the first reuses the transformed banks
-    take_deferred_error(nullptr);
-    int rc = FCN8S_OK;
-    for (int pi = 0; pi < P && !rc; ++pi) {
+    const void* img = io.images_dev();
+    float* acc = sc.ptr<float>(i_acc); float* sm; long long* am;
+    io.split(o, argmax != 0, &sm, &am);
+    FwdCall call; call.x0_written = true;
+    FrozenForCall frozen(m);
+    for (int pi = 0; pi < P; ++pi) {
         const int k = pi / (1 + flip), f = flip ? pi % 2 : 0;
-        rc = ensure_workspace_at_least(m, N, hp[k], wp[k], need); if (rc) break;
+        rc = ensure_workspace_at_least(m, N, hp[k], wp[k], need); if (rc) return rc;
         { ProfScope ps(m, "tta_input", 0, (double)npix * 3 * eb + 16.0 * N * hp[k] * wp[k]);
           launch_tta_input(img, dtype, N, H, W, hs[k], ws[k], hp[k], wp[k], f, A(m, "x0"), s); }
-        m->x0_ready = true;
-        rc = forward(m, img, dtype, 1.0f, false);
-        m->x0_ready = false;
-        if (rc) { take_deferred_error(nullptr); break; }
-        rc = deferred_rc(m); if (rc) break;
-        const PixMap pm = LGM(m) ? *LGM(m) : PixMap{0, hp[k], wp[k], 0, 0, 0};
+        rc = run_forward(m, img, dtype, call); if (rc) return rc;
         const bool first = pi == 0, last = pi == P - 1;
         // algorithmic bytes: the valid logits once, the accumulator read (not first) / written (not last), the result (last)
         const double by = 4.0 * N * hs[k] * ws[k] * C + (first ? 0.0 : 4.0 * npix * C) + (last ? 0.0 : 4.0 * npix * C) + (last ? (argmax ? 8.0 * npix : 4.0 * npix * C) : 0.0);
         { ProfScope ps(m, "tta_accumulate", 0, by);
-          launch_tta_accumulate(LG(m), pm, N, hs[k], ws[k], f, C, H, W, acc, first, last, P, sm, am, s); }
+          launch_tta_accumulate(LG(m), logits_map(m, hp[k], wp[k]), N, hs[k], ws[k], f, C, H, W, acc, first, last, P, sm, am, s); }
     }
-    m->x0_ready = false;
-    if (!was_frozen) {                    // leave unfrozen: the banks stay allocated for the next call, their contents are stale from now on
-        for (auto& kv : m->u_cache) m->bank_stale.insert("u:" + kv.first);
-        for (auto& kv : m->wbf16_cache) m->bank_stale.insert("w:" + kv.first);
-        m->banks_stale = true;
-        m->w8_valid.clear();              // (fp8_infer: the weight banks are re-quantized by the next pass)
-        m->frozen = false;
-    }
-    if (rc) return rc;
     HIPCHK(m, hipGetLastError());
-    if (where == FCN8S_HOST) {
-        HIPCHK(m, hipMemcpyAsync(out, dout, argmax ? npix * sizeof(long long) : npix * C * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(m, hipStreamSynchronize(s));
-    }
-    return FCN8S_OK;
+    return io.copy_out();
 }
 
 // ---- Monte-Carlo dropout inference (definition: fcn8s_hip.h at fcn8s_predict_mc) --------------------------------------------------
 // One prediction forward whose encoder and skip heads run once and whose fc6 -> fc7 -> decoder part runs `samples` times with dropout on (forward()'s
 // McLoop); behind each sample mc_accumulate folds its logits, read over [0,H)x[0,W) through the PixMap, into the running sums, and the last sample
 // writes the outputs.  The image is padded to multiples of 32 by tta_input (a shape that needs no padding goes through the preprocess kernel, as
-// fcn8s_predict).  The call runs with frozen parameters, as fcn8s_predict_tta: fc6's transformed bank is built once, and a model that was not frozen
-// keeps the banks' storage with their contents marked stale.
+// fcn8s_predict).  The call runs with frozen parameters (FrozenForCall): every sample after the first reuses fc6's / fc7's banks.
 int fcn8s_predict_mc(fcn8s_model* m, const void* images, int dtype, int N, int H, int W, int samples, float keep_prob, int64_t sample_offset,
                      int argmax, void* out, float* entropy_out, float* mi_out, int where)
 {
     if (!m || !images) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: null argument");
     if (!out && !entropy_out && !mi_out) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: no output was asked for (out, entropy_out and mi_out are all null)");
-    if (dtype != FCN8S_IMG_U8 && dtype != FCN8S_IMG_F32) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: unknown image dtype");
-    if (where != FCN8S_HOST && where != FCN8S_DEVICE) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: `where` must be FCN8S_HOST or FCN8S_DEVICE");
+    int rc = check_predict_args(m, "fcn8s_predict_mc", dtype, where); if (rc) return rc;
     if (samples < 1 || samples > FCN8S_MC_MAX_SAMPLES) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: between 1 and 256 samples");
     if (!(keep_prob > 0.f) || !(keep_prob <= 1.f)) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: keep_prob must lie in (0, 1]");
     if (sample_offset < 0 || sample_offset + samples > (int64_t)1 << 30)
         return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_mc: sample_offset must be >= 0 with sample_offset + samples <= 2^30 (the counter streams 0x80000000 + 2 (offset + s) of the masks)");
     if (fp8_mode(m)) return fail(m, FCN8S_ERR_STATE, "fcn8s_predict_mc: fp8_infer has no Monte-Carlo dropout -- its fc6 / fc7 kernels have no dropout epilogue; set another precision for the call");
-    if (N <= 0 || H <= 0 || W <= 0) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_mc: N, H and W must be positive");
+    rc = check_predict_shape(m, "fcn8s_predict_mc", N, H, W); if (rc) return rc;
     const int Hp = (H + 31) / 32 * 32, Wp = (W + 31) / 32 * 32, C = m->C, S = samples;
-    if ((double)N * Hp * Wp > (double)(1LL << 31)) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_mc: the padded shape is too large to plan");
-    const bool padded = Hp != H || Wp != W, host = where == FCN8S_HOST;
-    int rc = ensure_workspace(m, N, Hp, Wp); if (rc) return rc;
+    rc = check_padded_shape(m, "fcn8s_predict_mc", "the", N, Hp, Wp); if (rc) return rc;
+    rc = ensure_workspace(m, N, Hp, Wp); if (rc) return rc;
     // scratch: the staged images (host input), the two accumulators (S > 1), the staged outputs (host output)
     const size_t npix = (size_t)N * H * W, eb = dtype == FCN8S_IMG_U8 ? 1 : 4;
-    const size_t b_img = host ? align_up(npix * 3 * eb, 256) : 0;
-    const size_t b_acc = S > 1 ? align_up(npix * C * sizeof(float), 256) : 0, b_eacc = S > 1 ? align_up(npix * sizeof(float), 256) : 0;
-    const size_t n_out = out ? (argmax ? npix * sizeof(long long) : npix * C * sizeof(float)) : 0;
-    const size_t b_out = host ? align_up(n_out, 256) : 0, b_map = host ? align_up(npix * sizeof(float), 256) : 0;
-    const size_t total = b_img + b_acc + b_eacc + b_out + (entropy_out ? b_map : 0) + (mi_out ? b_map : 0);
-    if (total && !m->mc_buf.grow(total, m->stream, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "fcn8s_predict_mc: its scratch cannot be allocated");
+    Scratch sc{m->mc_buf}; PredictIo io(m, sc, where);
+    io.input(images, npix * 3 * eb);
+    const Scratch::Item i_acc = sc.take(S > 1 ? npix * C * sizeof(float) : 0), i_eacc = sc.take(S > 1 ? npix * sizeof(float) : 0);
+    const int o_out = io.output(out, argmax ? npix * sizeof(long long) : npix * C * sizeof(float));
+    const int o_ent = io.output(entropy_out, npix * sizeof(float)), o_mi = io.output(mi_out, npix * sizeof(float));
+    if (!sc.grow(m)) return fail(m, FCN8S_ERR_OOM, "fcn8s_predict_mc: its scratch cannot be allocated");
+    rc = io.stage(); if (rc) return rc;
     hipStream_t s = m->stream;
-    const void* img = images;
-    if (host) { HIPCHK(m, hipMemcpyAsync(m->mc_buf, images, npix * 3 * eb, hipMemcpyHostToDevice, s)); img = m->mc_buf; }
-    char* q = m->mc_buf ? (char*)m->mc_buf + b_img : nullptr;
-    float* acc = b_acc ? (float*)q : nullptr;          q += b_acc;
-    float* eacc = b_eacc ? (float*)q : nullptr;        q += b_eacc;
-    void* d_out = out ? (host ? (void*)q : out) : nullptr;                                   q += b_out;
-    float* d_ent = entropy_out ? (host ? (float*)q : entropy_out) : nullptr;                 q += (host && entropy_out) ? b_map : 0;
-    float* d_mi = mi_out ? (host ? (float*)q : mi_out) : nullptr;
-    float* sm = (out && !argmax) ? (float*)d_out : nullptr;
-    long long* am = (out && argmax) ? (long long*)d_out : nullptr;
-    const bool was_frozen = m->frozen;
-    m->frozen = true;                     // the parameters are constant for the call: every sample after the first reuses fc6's / fc7's banks
-    take_deferred_error(nullptr);
-    if (padded) {
-        ProfScope ps(m, "tta_input", 0, (double)npix * 3 * eb + 16.0 * N * Hp * Wp);
-        launch_tta_input(img, dtype, N, H, W, H, W, Hp, Wp, 0, A(m, "x0"), s);
-        m->x0_ready = true;
-    }
+    const void* img = io.images_dev();
+    float *acc = sc.ptr<float>(i_acc), *eacc = sc.ptr<float>(i_eacc), *d_ent = (float*)io.dev(o_ent), *d_mi = (float*)io.dev(o_mi), *sm; long long* am;
+    io.split(o_out, argmax != 0, &sm, &am);
     McLoop mc; mc.samples = S; mc.stream_base = 0x80000000u + 2u * (uint32_t)sample_offset;
+    FwdCall call; call.keep_prob = keep_prob; call.mc = &mc; call.x0_written = Hp != H || Wp != W;
     mc.after_sample = [&](int k) {
-        const PixMap pm = LGM(m) ? *LGM(m) : PixMap{0, Hp, Wp, 0, 0, 0};
         const bool first = k == 0, last = k == S - 1;
         // algorithmic bytes: the valid logits once, both accumulators read (not first) / written (not last), the outputs (last)
         const double by = 4.0 * npix * C + ((first ? 0.0 : 1.0) + (last ? 0.0 : 1.0)) * 4.0 * npix * (C + 1) +
                           (last ? (sm ? 4.0 * npix * C : 0.0) + (am ? 8.0 * npix : 0.0) + (d_ent ? 4.0 * npix : 0.0) + (d_mi ? 4.0 * npix : 0.0) : 0.0);
         ProfScope ps(m, "mc_accumulate", 0, by);
-        launch_mc_accumulate(LG(m), pm, N, H, W, C, acc, eacc, first, last, S, sm, am, d_ent, d_mi, s);
+        launch_mc_accumulate(LG(m), logits_map(m, Hp, Wp), N, H, W, C, acc, eacc, first, last, S, sm, am, d_ent, d_mi, s);
     };
-    rc = forward(m, img, dtype, keep_prob, false, &mc);
-    m->x0_ready = false;
-    if (rc) take_deferred_error(nullptr); else rc = deferred_rc(m);
-    if (!was_frozen) {                    // leave unfrozen: the banks stay allocated for the next call, their contents are stale from now on
-        for (auto& kv : m->u_cache) m->bank_stale.insert("u:" + kv.first);
-        for (auto& kv : m->wbf16_cache) m->bank_stale.insert("w:" + kv.first);
-        m->banks_stale = true;
-        m->w8_valid.clear();
-        m->frozen = false;
+    FrozenForCall frozen(m);
+    if (call.x0_written) {
+        ProfScope ps(m, "tta_input", 0, (double)npix * 3 * eb + 16.0 * N * Hp * Wp);
+        launch_tta_input(img, dtype, N, H, W, H, W, Hp, Wp, 0, A(m, "x0"), s);
     }
-    if (rc) return rc;
+    rc = run_forward(m, img, dtype, call); if (rc) return rc;
     HIPCHK(m, hipGetLastError());
-    if (host) {
-        if (out) HIPCHK(m, hipMemcpyAsync(out, d_out, n_out, hipMemcpyDeviceToHost, s));
-        if (entropy_out) HIPCHK(m, hipMemcpyAsync(entropy_out, d_ent, npix * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (mi_out) HIPCHK(m, hipMemcpyAsync(mi_out, d_mi, npix * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(m, hipStreamSynchronize(s));
-    }
-    return FCN8S_OK;
+    return io.copy_out();
 }
 
 // ---- mean-field CRF refinement (definition: fcn8s_hip.h at fcn8s_crf_params) ------------------------------------------------------
@@ -3707,34 +3729,29 @@ int fcn8s_predict_crf(fcn8s_model* m, const void* images, int dtype, int N, int 
     if (!crf || crf->iterations == 0) return fcn8s_predict_tta(m, images, dtype, N, H, W, scales, nscales, flip, argmax, out, where);
     if (!images || !out || !scales) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_crf: null argument");
     if (dtype != FCN8S_IMG_U8) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_crf: the mean field (iterations > 0) reads the colours of uint8 images; float32 images are not taken");
-    if (where != FCN8S_HOST && where != FCN8S_DEVICE) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_predict_crf: `where` must be FCN8S_HOST or FCN8S_DEVICE");
-    if (N <= 0 || H <= 0 || W <= 0) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_crf: N, H and W must be positive");
+    int rc = check_predict_args(m, "fcn8s_predict_crf", dtype, where); if (rc) return rc;
+    rc = check_predict_shape(m, "fcn8s_predict_crf", N, H, W); if (rc) return rc;
     const int C = m->C;
     if (!crf_shape_supported(C, crf->radius)) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_predict_crf: this many classes do not fit the mean field's LDS tile at this radius");
     // scratch: the staged images (host input), the mean softmax, the two mean-field buffers, the staged output (host output)
-    const size_t npix = (size_t)N * H * W, b_q = align_up(npix * C * sizeof(float), 256);
-    const bool host = where == FCN8S_HOST;
-    const size_t b_img = host ? align_up(npix * 3, 256) : 0;
-    const size_t b_out = host ? (argmax ? align_up(npix * sizeof(long long), 256) : b_q) : 0;
-    const size_t need = b_img + 3 * b_q + b_out;
-    if (!m->crf_buf.grow(need, m->stream, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "fcn8s_predict_crf: its scratch cannot be allocated");
-    hipStream_t s = m->stream;
-    const uint8_t* img = (const uint8_t*)images;
-    if (host) { HIPCHK(m, hipMemcpyAsync(m->crf_buf, images, npix * 3, hipMemcpyHostToDevice, s)); img = (const uint8_t*)m->crf_buf.get(); }
-    float* prob = (float*)(m->crf_buf + b_img);
-    float* work = (float*)(m->crf_buf + b_img + b_q);          // 2 b_q bytes: crf_run's two halves of N H W C floats
-    void* dout = host ? (void*)(m->crf_buf + b_img + 3 * b_q) : out;
-    int rc = fcn8s_predict_tta(m, img, dtype, N, H, W, scales, nscales, flip, 0, prob, FCN8S_DEVICE); if (rc) return rc;
+    const size_t npix = (size_t)N * H * W, qb = npix * C * sizeof(float);
+    Scratch sc{m->crf_buf}; PredictIo io(m, sc, where);
+    io.input(images, npix * 3);
+    const Scratch::Item i_prob = sc.take(qb), i_work = sc.take(qb);          // work: crf_run's two halves of N H W C floats, ...
+    sc.take(qb);                                                             // ... the second one's room
+    const int o = io.output(out, argmax ? npix * sizeof(long long) : qb);
+    if (!sc.grow(m)) return fail(m, FCN8S_ERR_OOM, "fcn8s_predict_crf: its scratch cannot be allocated");
+    rc = io.stage(); if (rc) return rc;
+    const uint8_t* img = (const uint8_t*)io.images_dev();
+    float *prob = sc.ptr<float>(i_prob), *sm; long long* am;
+    io.split(o, argmax != 0, &sm, &am);
+    rc = fcn8s_predict_tta(m, img, dtype, N, H, W, scales, nscales, flip, 0, prob, FCN8S_DEVICE); if (rc) return rc;
     take_deferred_error(nullptr);
     // argmax: Q^T goes to a work half; softmax: the last update writes it where it is wanted
-    crf_run(m, s, prob, img, N, H, W, C, crf, work, argmax ? nullptr : (float*)dout, argmax ? (long long*)dout : nullptr);
+    crf_run(m, m->stream, prob, img, N, H, W, C, crf, sc.ptr<float>(i_work), sm, am);
     rc = deferred_rc(m); if (rc) return rc;
     HIPCHK(m, hipGetLastError());
-    if (host) {
-        HIPCHK(m, hipMemcpyAsync(out, dout, argmax ? npix * sizeof(long long) : npix * C * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(m, hipStreamSynchronize(s));
-    }
-    return FCN8S_OK;
+    return io.copy_out();
 }
 
 // ---- asynchronous host boundary ------------------------------------------------------------------

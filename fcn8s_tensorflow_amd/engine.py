@@ -835,6 +835,25 @@ class Engine:
                                            C.c_void_p(pd.data_ptr()), N, H, W, Ho, Wo, int(void_class_id)))
         return out, lab_out
 
+    def _alloc_out(self, shape, dtype, where):
+        """An uninitialised output where the call's inputs are -- a torch tensor on the device, a numpy array on the host -- and the pointer to pass."""
+        if where == L.DEVICE:
+            t = self.torch.empty(shape, dtype=getattr(self.torch, np.dtype(dtype).name), device=self.device)
+            return t, C.c_void_p(t.data_ptr())
+        a = np.empty(shape, dtype)
+        return a, a.ctypes.data_as(C.c_void_p)
+
+    def _predict_out(self, nhw, argmax, where):
+        """A prediction's output: int64 [N,H,W] (argmax) or float32 [N,H,W,num_classes], as `_alloc_out`."""
+        return self._alloc_out(nhw, np.int64, where) if argmax else self._alloc_out(nhw + (self.num_classes,), np.float32, where)
+
+    def _trim_classes(self, out, argmax):
+        """A prediction without the padded classes (`logical_classes` < `num_classes`)."""
+        if argmax or self.logical_classes == self.num_classes:
+            return out
+        out = out[..., :self.logical_classes]
+        return np.ascontiguousarray(out) if isinstance(out, np.ndarray) else out.contiguous()
+
     def predict(self, images, argmax=True):
         """sess.run(predictions_argmax | softmax_output) (fcn8s_tensorflow.py:764-770)."""
         self._sync_stream()
@@ -843,16 +862,10 @@ class Engine:
         else:
             ka_i, pi, dt, where, nhw = self._images(images)
         N, H, W = (int(x) for x in nhw)
-        torch = self.torch
-        if where == L.DEVICE:
-            out = torch.empty((N, H, W), dtype=torch.int64, device=self.device) if argmax else \
-                torch.empty((N, H, W, self.num_classes), dtype=torch.float32, device=self.device)
-            L.check(L.lib.fcn8s_predict(self.h, pi, dt, N, H, W, int(bool(argmax)), C.c_void_p(out.data_ptr()), where), self.h)
-            self._release(ka_i)
-            return out if argmax or self.logical_classes == self.num_classes else out[..., :self.logical_classes].contiguous()
-        out = np.empty((N, H, W), np.int64) if argmax else np.empty((N, H, W, self.num_classes), np.float32)
-        L.check(L.lib.fcn8s_predict(self.h, pi, dt, N, H, W, int(bool(argmax)), out.ctypes.data_as(C.c_void_p), where), self.h)
-        return out if argmax or self.logical_classes == self.num_classes else np.ascontiguousarray(out[..., :self.logical_classes])
+        out, po = self._predict_out((N, H, W), argmax, where)
+        L.check(L.lib.fcn8s_predict(self.h, pi, dt, N, H, W, int(bool(argmax)), po, where), self.h)
+        self._release(ka_i)
+        return self._trim_classes(out, argmax)
 
     # ---- fp8_infer calibration (include/fcn8s_hip.h: fcn8s_fp8_calibrate) ---------------------------------------------------
     def calibrate_fp8(self, images, reset=False):
@@ -890,18 +903,10 @@ class Engine:
         if dt == L.IMG_F32 and tta.resizes(H, W, sc):
             raise ValueError("float32 images are taken only when no pass resizes them; pass uint8 images to predict at scales %s" % (sc,))
         arr = (C.c_float * len(sc))(*sc)
-        torch = self.torch
-        if where == L.DEVICE:
-            out = torch.empty((N, H, W), dtype=torch.int64, device=self.device) if argmax else \
-                torch.empty((N, H, W, self.num_classes), dtype=torch.float32, device=self.device)
-            L.check(L.lib.fcn8s_predict_tta(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), int(bool(argmax)),
-                                            C.c_void_p(out.data_ptr()), where), self.h)
-            self._release(ka_i)
-            return out if argmax or self.logical_classes == self.num_classes else out[..., :self.logical_classes].contiguous()
-        out = np.empty((N, H, W), np.int64) if argmax else np.empty((N, H, W, self.num_classes), np.float32)
-        L.check(L.lib.fcn8s_predict_tta(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), int(bool(argmax)),
-                                        out.ctypes.data_as(C.c_void_p), where), self.h)
-        return out if argmax or self.logical_classes == self.num_classes else np.ascontiguousarray(out[..., :self.logical_classes])
+        out, po = self._predict_out((N, H, W), argmax, where)
+        L.check(L.lib.fcn8s_predict_tta(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), int(bool(argmax)), po, where), self.h)
+        self._release(ka_i)
+        return self._trim_classes(out, argmax)
 
     def predict_mc(self, images, samples=20, keep_prob=0.5, sample_offset=0, argmax=True, entropy=True, mutual_information=True):
         """Monte-Carlo dropout inference (fcn8s_predict_mc; the definition is in mc_dropout.py): `samples` stochastic passes with dropout
@@ -914,28 +919,12 @@ class Engine:
         self._sync_stream()
         ka_i, pi, dt, where, nhw = self._images(images)
         N, H, W = (int(x) for x in nhw)
-        torch = self.torch
-        if where == L.DEVICE:
-            out = torch.empty((N, H, W), dtype=torch.int64, device=self.device) if argmax else \
-                torch.empty((N, H, W, self.num_classes), dtype=torch.float32, device=self.device)
-            ent = torch.empty((N, H, W), dtype=torch.float32, device=self.device) if entropy else None
-            mi = torch.empty((N, H, W), dtype=torch.float32, device=self.device) if mutual_information else None
-            L.check(L.lib.fcn8s_predict_mc(self.h, pi, dt, N, H, W, S, keep, off, int(bool(argmax)), C.c_void_p(out.data_ptr()),
-                                           C.c_void_p(ent.data_ptr()) if entropy else None, C.c_void_p(mi.data_ptr()) if mutual_information else None,
-                                           where), self.h)
-            self._release(ka_i)
-            if not argmax and self.logical_classes != self.num_classes:
-                out = out[..., :self.logical_classes].contiguous()
-            return out, ent, mi
-        out = np.empty((N, H, W), np.int64) if argmax else np.empty((N, H, W, self.num_classes), np.float32)
-        ent = np.empty((N, H, W), np.float32) if entropy else None
-        mi = np.empty((N, H, W), np.float32) if mutual_information else None
-        L.check(L.lib.fcn8s_predict_mc(self.h, pi, dt, N, H, W, S, keep, off, int(bool(argmax)), out.ctypes.data_as(C.c_void_p),
-                                       ent.ctypes.data_as(C.c_void_p) if entropy else None, mi.ctypes.data_as(C.c_void_p) if mutual_information else None,
-                                       where), self.h)
-        if not argmax and self.logical_classes != self.num_classes:
-            out = np.ascontiguousarray(out[..., :self.logical_classes])
-        return out, ent, mi
+        out, po = self._predict_out((N, H, W), argmax, where)
+        ent, pe = self._alloc_out((N, H, W), np.float32, where) if entropy else (None, None)
+        mi, pm = self._alloc_out((N, H, W), np.float32, where) if mutual_information else (None, None)
+        L.check(L.lib.fcn8s_predict_mc(self.h, pi, dt, N, H, W, S, keep, off, int(bool(argmax)), po, pe, pm, where), self.h)
+        self._release(ka_i)
+        return self._trim_classes(out, argmax), ent, mi
 
     def predict_crf(self, images, crf, scales=(1.0,), flip=False, argmax=True):
         """`predict_tta` with these arguments followed by a mean-field CRF on its mean softmax and the uint8 images (fcn8s_predict_crf; the
@@ -954,18 +943,10 @@ class Engine:
             raise ValueError("float32 images are taken only when no pass resizes them; pass uint8 images to predict at scales %s" % (sc,))
         arr = (C.c_float * len(sc))(*sc)
         cp = L.CrfParams(**params.as_dict())
-        torch = self.torch
-        if where == L.DEVICE:
-            out = torch.empty((N, H, W), dtype=torch.int64, device=self.device) if argmax else \
-                torch.empty((N, H, W, self.num_classes), dtype=torch.float32, device=self.device)
-            L.check(L.lib.fcn8s_predict_crf(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), C.byref(cp), int(bool(argmax)),
-                                            C.c_void_p(out.data_ptr()), where), self.h)
-            self._release(ka_i)
-            return out if argmax or self.logical_classes == self.num_classes else out[..., :self.logical_classes].contiguous()
-        out = np.empty((N, H, W), np.int64) if argmax else np.empty((N, H, W, self.num_classes), np.float32)
-        L.check(L.lib.fcn8s_predict_crf(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), C.byref(cp), int(bool(argmax)),
-                                        out.ctypes.data_as(C.c_void_p), where), self.h)
-        return out if argmax or self.logical_classes == self.num_classes else np.ascontiguousarray(out[..., :self.logical_classes])
+        out, po = self._predict_out((N, H, W), argmax, where)
+        L.check(L.lib.fcn8s_predict_crf(self.h, pi, dt, N, H, W, arr, len(sc), int(bool(flip)), C.byref(cp), int(bool(argmax)), po, where), self.h)
+        self._release(ka_i)
+        return self._trim_classes(out, argmax)
 
     def reliability_pair(self, prob, gt, lut, scores=(), scales=(), bins=15, tables=None):
         """One `fcn8s_op_reliability_pair` call (reliability.py; the definition is in include/fcn8s_hip.h) on device tensors: `prob` float32

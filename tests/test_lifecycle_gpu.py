@@ -41,9 +41,10 @@ def cycle(img, lab):
     peak = live()
     # frozen inference: the cached filter banks (u_cache)
     e.freeze(True); e.predict(img); e.predict(img); e.freeze(False)
-    # multi-scale + flip (tta_buf, the re-plan path), then the CRF on top of it (crf_buf)
+    # multi-scale + flip (tta_buf, the re-plan path), then the CRF on top of it (crf_buf), then Monte-Carlo dropout (mc_buf)
     e.predict_tta(img, scales=(0.5, 1.0), flip=True)
     e.predict_crf(img, True)
+    e.predict_mc(img, samples=2)
     # bf16 forward modes: xbf16, d_wbf16, d_abf16, and frozen the per-layer bf16 kernels (wbf16_cache)
     e.set_precision('bf16_fwd')
     e.train_step(img, lab, 1e-4, keep_prob=0.5)

@@ -368,3 +368,49 @@ def test_fp8_calibration_while_frozen():
         assert np.abs(got - base).max() > 0                          # the activation scales did change
         assert sum(n for k, n in derived_work(prof).items() if k.startswith("fp8_quantize_w")) == 0, derived_work(prof)
     e.close()
+
+
+# ---- 10. a pass refused inside predict_tta ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("frozen", (True, False), ids=("frozen", "unfrozen"))
+def test_refused_pass_inside_predict_tta(frozen):
+    """An fp8_infer model that was never calibrated: predict_tta's first pass is refused by forward() (FCN8S_ERR_STATE, a host-side return)
+    after the call has frozen the model for its passes.  The model is left as it was found -- frozen or not -- and, once calibrated, predicts
+    bit for bit what a fresh model does that never saw the refused call; unfrozen, also after new parameters and a new calibration (the
+    refused call marked the banks stale like any other)."""
+    import ctypes as C
+    from fcn8s_tensorflow_amd import _lib as L
+    img = _images((1, 64, 64), 4)
+    tta = dict(scales=(0.5, 1.0), argmax=False)                      # two passes, 32 x 32 and 64 x 64: not the identity shortcut
+
+    def calibrated(flat):
+        f = fresh('fp8_infer', flat)
+        if frozen:
+            f.freeze(True)
+        f.calibrate_fp8(img, reset=True)
+        return f
+    e = fresh('fp8_infer', params(1)[1])
+    if frozen:
+        e.freeze(True)
+    with pytest.raises(L.Fcn8sError, match="no FP8 calibration"):
+        e.predict_tta(img, **tta)
+    assert e.get_option("frozen") == int(frozen)
+    out = np.empty((1, 64, 64, CLASSES), np.float32)
+    rc = L.lib.fcn8s_predict_tta(e.h, img.ctypes.data_as(C.c_void_p), L.IMG_U8, 1, 64, 64, (C.c_float * 2)(0.5, 1.0), 2, 0, 0,
+                                 out.ctypes.data_as(C.c_void_p), L.HOST)
+    assert rc == L.ERR_STATE
+    assert e.get_option("frozen") == int(frozen)
+    e.calibrate_fp8(img, reset=True)
+    f = calibrated(params(1)[1])
+    first = e.predict_tta(img, **tta)
+    np.testing.assert_array_equal(first, f.predict_tta(img, **tta))
+    assert e.get_option("frozen") == int(frozen)
+    f.close()
+    if not frozen:
+        e.set_params(params(2)[0])
+        e.calibrate_fp8(img, reset=True)
+        f = calibrated(params(2)[1])
+        second = e.predict_tta(img, **tta)
+        np.testing.assert_array_equal(second, f.predict_tta(img, **tta))
+        moved(second, first)
+        f.close()
+    e.close()
