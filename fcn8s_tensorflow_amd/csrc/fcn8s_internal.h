@@ -406,6 +406,14 @@ void launch_boundary_pair(const uint8_t* gt, const void* pred, int pred_kind, in
 // boundary_weight.hip (fcn8s_op_boundary_distance; the definition is in fcn8s_hip.h at fcn8s_op_softmax_xent_px).  One kernel; codes [N][H][W] uint8 =
 // d2 if <= R * R, else 255.  1 <= R <= 15, H * W < 2^31; any alignment of either pointer.
 void launch_boundary_distance(const uint8_t* labels, int N, int H, int W, int R, uint8_t* codes, hipStream_t s);
+// regions.hip (fcn8s_op_regions_label / fcn8s_op_regions_clean; the definition is in fcn8s_hip.h).  Both clear the header of `work` first; label writes
+// comp and (unless null) area, int32 [N][H][W]; clean rewrites labels in place over `rounds` rounds and writes stats [rounds][4] (may be null).
+// H * W < 2^31, N <= 65535, work: regions_work_bytes(N, H, W) bytes, 16-byte aligned.  regions_status: {flag bits, bad pixels} of the last call.
+size_t regions_work_bytes(int N, int H, int W);
+void launch_regions_label(const void* labels, int label_kind, int N, int H, int W, int connectivity, int* comp, int* area, void* work, hipStream_t s);
+void launch_regions_clean(void* labels, int label_kind, int N, int H, int W, int connectivity, const int* min_area, int rounds, void* work,
+                          unsigned long long* stats, hipStream_t s);
+bool regions_status(const void* work, long long* status2, hipStream_t s);
 // wrapping sum over every 61st element's bit pattern (weighted by position): changes whenever an optimizer step or a bulk copy touches the buffer
 void launch_fingerprint(const float* x, long long n, unsigned long long* out, hipStream_t s);
 void launch_init_normal(float* w, long long n, float stddev, int truncated, unsigned long long seed,

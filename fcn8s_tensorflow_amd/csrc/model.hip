@@ -4494,6 +4494,39 @@ int fcn8s_op_boundary_distance(void* stream, const uint8_t* label_ids, int N, in
     launch_boundary_distance(label_ids, N, H, W, R, codes_out, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
+size_t fcn8s_op_regions_work_bytes(int N, int H, int W) { return (long long)H * W >= (1LL << 31) ? 0 : regions_work_bytes(N, H, W); }
+static int regions_args(const char* what, const void* labels, int label_kind, int N, int H, int W, int connectivity, const void* work, bool rest_ok)
+{
+    if (!labels || !work || (uintptr_t)work % 16 || !rest_ok || (label_kind != 0 && label_kind != 1) || (connectivity != 4 && connectivity != 8) || N <= 0 || H <= 0 || W <= 0)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, std::string(what) + ": bad argument (null pointer, work not 16-byte aligned, label_kind outside {0, 1}, connectivity outside {4, 8}, rounds outside 1 .. 8, or N, H, W <= 0)");
+    if ((long long)H * W >= (1LL << 31) || N > 65535) return fail(nullptr, FCN8S_ERR_SHAPE, std::string(what) + ": an image has to have fewer than 2^31 pixels and a batch at most 65535 images");
+    return FCN8S_OK;
+}
+int fcn8s_op_regions_label(void* stream, const void* labels, int label_kind, int N, int H, int W, int connectivity, int32_t* comp_out, int32_t* area_out, void* work)
+{
+    const int rc = regions_args("regions_label", labels, label_kind, N, H, W, connectivity, work, comp_out != nullptr);
+    if (rc) return rc;
+    take_deferred_error(nullptr);
+    launch_regions_label(labels, label_kind, N, H, W, connectivity, comp_out, area_out, work, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_regions_clean(void* stream, void* labels, int label_kind, int N, int H, int W, int connectivity, const int32_t* min_area_dev, int rounds,
+                           void* work, int64_t* stats_dev)
+{
+    const int rc = regions_args("regions_clean", labels, label_kind, N, H, W, connectivity, work, min_area_dev != nullptr && rounds >= 1 && rounds <= 8);
+    if (rc) return rc;
+    take_deferred_error(nullptr);
+    launch_regions_clean(labels, label_kind, N, H, W, connectivity, min_area_dev, rounds, work, (unsigned long long*)stats_dev, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
+int fcn8s_op_regions_status(void* stream, const void* work, int64_t* status_host)
+{
+    if (!work || !status_host) return fail(nullptr, FCN8S_ERR_BAD_ARG, "regions_status: null pointer");
+    long long st[2] = {0, 0};
+    if (!regions_status(work, st, (hipStream_t)stream)) return fail(nullptr, FCN8S_ERR_HIP, "regions_status: the header could not be read");
+    status_host[0] = st[0]; status_host[1] = st[1];
+    return FCN8S_OK;
+}
 // the six op-level forms of the update: host scale or the slab's (out5 + 2: s, out5 + 3: ok), with or without a shadow
 static int op_update(void* stream, int opt, float* theta, const float* g, float* m, float* v, float* shadow, int64_t n,
                      float p0, float p1, float p2, float p3, float gs, const float* out5, float w)

@@ -976,6 +976,24 @@ class Engine:
         q, h = ts.apply_device(dev, temperature, entropy=entropy, out=False if out is False else dev)
         return (None if q is None else q.cpu().numpy()), (None if h is None else h.cpu().numpy())
 
+    def regions_label(self, labels, connectivity=4, area=True):
+        """One `fcn8s_op_regions_label` call (regions.py; the definition is in include/fcn8s_hip.h) on a device tensor of class ids, int64 as
+        `predict` returns them or uint8, [H,W] or [N,H,W]: (comp, area | None), int32 device tensors of the same shape -- the id (smallest
+        pixel index, per image) and the pixel count of every pixel's connected component under `connectivity` (4 or 8)."""
+        from . import regions
+        comp, ar, self._regions_work = regions.label_device(labels, connectivity=connectivity, area=area, work=getattr(self, "_regions_work", None))
+        return comp, ar
+
+    def regions_clean(self, labels, min_area, connectivity=4, rounds=1, stats=False):
+        """One `fcn8s_op_regions_clean` call, in place, on a device tensor of class ids (int64 or uint8, [H,W] or [N,H,W]): `rounds` rounds in
+        which every component smaller than `min_area` (an int, or a table of 256 per class, 0 = never) takes the class of its largest
+        4-adjacent neighbour that is not small.  The scratch is kept on the engine and regrown only when a larger one is needed.  Returns
+        the int64 [rounds, 4] stats (components, small, relabelled, pixels changed) as a device tensor when `stats`, else None."""
+        from . import regions
+        st, self._regions_work = regions.clean_device(labels, min_area, connectivity=connectivity, rounds=rounds, stats=stats,
+                                                      work=getattr(self, "_regions_work", None))
+        return st
+
     # ---- introspection (tests, bench) -----------------------------------------------------------
     def activation(self, name, shape, missing_ok=False):
         """fcn8s_get_activation.  A conv whose output transform was fused with the next conv's input transform (option `fuse_out_in`)

@@ -50,6 +50,7 @@ except Exception:  # pragma: no cover
 from . import _lib as L
 from . import crf as crf_mod
 from . import temperature as ts_mod
+from . import regions as regions_mod
 from . import loss as loss_mod
 from . import optim as optim_mod
 from . import tf_bundle
@@ -457,7 +458,8 @@ class FCN8s:
         self._evaluate(data_generator, metrics, num_batches, l2_regularization, description='Running evaluation')
         self.eval_dataset = dataset
 
-    def predict(self, images, argmax=True, scales=None, flip=False, crf=None, temperature=None):
+    def predict(self, images, argmax=True, scales=None, flip=False, crf=None, temperature=None, min_region=None, region_connectivity=4,
+                region_rounds=1):
         '''fcn8s_tensorflow.py:743-770.  `images`: array-like of rank 4 (a list of HWC arrays works).
         Returns int64 class ids (N,H,W) or the float32 softmax (N,H,W,C).
         Not in the reference: `scales` (1 to 8 factors in (0, 4]) and / or `flip` average the softmax over resized and mirrored passes
@@ -468,11 +470,28 @@ class FCN8s:
         override them, None / False for no CRF.  Images of any size, as with `scales=(1.0,)`.
         `temperature` (also not in the reference): with `argmax=False`, the returned distribution calibrated at that temperature
         (temperature.py; one `fcn8s_op_temperature_apply` on the result, whichever route made it) -- `fit_temperature` finds the value and
-        keeps it in `self.temperature`.  None or 1.0, or `argmax=True` (the map cannot change an argmax): nothing is launched.'''
+        keeps it in `self.temperature`.  None or 1.0, or `argmax=True` (the map cannot change an argmax): nothing is launched.
+        `min_region` (also not in the reference): connected-region cleanup of the argmax map (regions.py; `fcn8s_op_regions_clean`) --
+        every connected component (`region_connectivity` 4 or 8) of fewer pixels than the threshold takes the class of its largest
+        4-adjacent neighbour that is not small itself, `region_rounds` (1..8) times.  An int, a sequence of one int per class or a dict
+        {class: area} (0 = that class is never merged away); None / 0 / False: nothing is launched.  On every route the cleanup acts on
+        the argmax where it lies on the device, before any download (host images are uploaded once for that).  Needs `argmax=True`.'''
         if isinstance(images, (list, tuple)):
             images = np.asarray(images)
         if temperature is not None:
             temperature = ts_mod.validate_temperature(temperature)
+        table = regions_mod.resolve(min_region, self.num_classes)
+        if table is not None:
+            if not argmax:
+                raise ValueError("`min_region` cleans the argmax map; a cleaned softmax is not defined: needs argmax=True.")
+            regions_mod._check(region_connectivity, region_rounds)
+            torch = self.engine.torch
+            on_host = not (isinstance(images, torch.Tensor) and images.is_cuda)
+            if on_host:
+                images = self.engine._images(images, force_device=True)[0]
+            out = self.predict(images, argmax=True, scales=scales, flip=flip, crf=crf)
+            self.engine.regions_clean(out, table, connectivity=region_connectivity, rounds=region_rounds)
+            return out.cpu().numpy() if on_host else out
         params = crf_mod.resolve(crf)
         if params is not None:
             out = self.engine.predict_crf(images, params, scales=(1.0,) if scales is None else scales, flip=flip, argmax=argmax)
@@ -507,9 +526,16 @@ class FCN8s:
                          overwrite_existing=True,
                          scales=None,
                          flip=False,
-                         crf=None):
+                         crf=None,
+                         min_region=None,
+                         region_connectivity=4,
+                         region_rounds=1):
         '''fcn8s_tensorflow.py:772-855 (PIL instead of scipy.misc / helpers.visualization_utils).  `scales` / `flip` / `crf`: as in `predict`
-        (images of any size; `resize` is then optional).'''
+        (images of any size; `resize` is then optional).  `min_region` / `region_connectivity` / `region_rounds`: as in `predict`; the
+        overlay then shows the cleaned argmax map.'''
+        regions = None
+        if regions_mod.resolve(min_region, self.num_classes) is not None:
+            regions = dict(min_region=min_region, region_connectivity=region_connectivity, region_rounds=region_rounds)
         from PIL import Image
 
         if overwrite_existing and os.path.exists(results_dir):
@@ -527,18 +553,19 @@ class FCN8s:
         self.engine.freeze(True)            # constant weights for the whole directory
         try:
             for i in tr:
-                self._segment_file(image_paths[i], results_dir, color_map, resize, include_unprocessed_image, arrangement, scales, flip, crf)
+                self._segment_file(image_paths[i], results_dir, color_map, resize, include_unprocessed_image, arrangement, scales, flip, crf, regions)
         finally:
             self.engine.freeze(False)
 
     def predict_and_export_label_ids(self, results_dir, images_dir, resize=False, image_file_extension='png', overwrite_existing=True,
-                                     scales=None, flip=False, crf=None):
+                                     scales=None, flip=False, crf=None, min_region=None, region_connectivity=4, region_rounds=1):
         '''Not in the reference: runs every `*.png` below `images_dir` (sub-directories = cities, as in leftImg8bit/val) through the
         model and writes the argmax as single-channel label-id PNGs under the same file names into `results_dir` -- the input of the
         official scorer (cityscapesscripts/evaluation/evalPixelLevelSemanticLabeling.py:72-106, 553-555; cityscapes_eval.evaluate_directory
         here).  Predictions are train ids 0..19 (0 = void) mapped through labels.py:188-192; `resize=(h, w)` feeds the network a
         resized image and writes the prediction back at the file's own size (nearest neighbour).  `scales` / `flip` / `crf`: as in `predict`
-        (multi-scale / flip averaging on images of any size; `resize` is then optional).'''
+        (multi-scale / flip averaging on images of any size; `resize` is then optional).  `min_region` / `region_connectivity` /
+        `region_rounds`: as in `predict` -- the train-id map is cleaned on the device before it is downloaded and mapped.'''
         from PIL import Image
         from . import cityscapes_eval as ce
         if self.num_classes != 20:
@@ -557,6 +584,8 @@ class FCN8s:
                 if resize and not np.array_equal((pil.height, pil.width), resize):
                     pil = pil.resize((resize[1], resize[0]), Image.BILINEAR)
                 kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
+                if regions_mod.resolve(min_region, self.num_classes) is not None:
+                    kw.update(min_region=min_region, region_connectivity=region_connectivity, region_rounds=region_rounds)
                 pred = np.asarray(self.predict([np.asarray(pil)], argmax=True, scales=scales, flip=flip, **kw))[0]
                 ids = Image.fromarray(ce.TRAINIDS_TO_IDS_ARRAY[pred])
                 if ids.size != size:
@@ -567,7 +596,7 @@ class FCN8s:
         return len(paths)
 
     def evaluate_cityscapes(self, images_dir, ground_truth_search, resize=False, image_file_extension='png', scales=None, flip=False, crf=None,
-                            instance_level=True, json_path=None, boundary_radius=None):
+                            instance_level=True, json_path=None, boundary_radius=None, min_region=None, region_connectivity=4, region_rounds=1):
         '''Not in the reference: the official Cityscapes pixel-level table (IoU and iIoU, for classes and for categories) of this model in
         one call, scored where the predictions already are.  Every ground-truth file of the glob `ground_truth_search` (the official one is
         `<cityscapes>/gtFine/val/*/*_gtFine_labelIds.png`) is paired with its image `<city>_<seq>_<frame>*.<ext>` below `images_dir`; per
@@ -580,7 +609,10 @@ class FCN8s:
         (instance-level only).  `boundary_radius=R` (1..16): one more call per image, `fcn8s_op_boundary_pair`, on the prediction and the
         label map that are already on the device, and the trimap IoU for the band widths 1..R around the ground-truth boundaries and the
         boundary F-score for the tolerances 0..R in the result (`cityscapes_eval.trimap_scores`, `boundary_f_scores`): what `scales`,
-        `flip` or `crf` change at the contours.  With None nothing more is launched and the dict is the one described above.'''
+        `flip` or `crf` change at the contours.  With None nothing more is launched and the dict is the one described above.
+        `min_region` / `region_connectivity` / `region_rounds`: as in `predict` -- the argmax is cleaned on the device
+        (`fcn8s_op_regions_clean`) before the counting calls see it: every speck it removes is a closed contour without a match in the
+        ground truth.  With None nothing more is launched and the dict is the same, key for key.'''
         from PIL import Image
         import torch
         from . import cityscapes_eval as ce
@@ -597,6 +629,8 @@ class FCN8s:
         ev = ce.PixelLevelEvaluator(instance_level=instance_level, boundary_radius=boundary_radius)
         pixels = 0
         kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
+        if regions_mod.resolve(min_region, self.num_classes) is not None:
+            kw.update(min_region=min_region, region_connectivity=region_connectivity, region_rounds=region_rounds)
         tr = trange(len(gts), file=sys.stdout)
         tr.set_description('Evaluating')
         self.engine.freeze(True)
@@ -791,7 +825,8 @@ class FCN8s:
             ts_mod.write_result_json(res, json_path)
         return res
 
-    def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement, scales=None, flip=False, crf=None):
+    def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement, scales=None, flip=False, crf=None,
+                      regions=None):
         '''Loop body of predict_and_save (fcn8s_tensorflow.py:829-855).'''
         from PIL import Image
         pil = Image.open(filepath).convert('RGB')
@@ -801,7 +836,10 @@ class FCN8s:
         img_height, img_width, img_ch = image.shape
 
         kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
-        prediction = self.predict([image], argmax=False, scales=scales, flip=flip, **kw)
+        if regions is None:
+            prediction = self.predict([image], argmax=False, scales=scales, flip=flip, **kw)
+        else:                                   # the cleaned argmax map, one-hot: the overlay takes its argmax
+            prediction = np.eye(self.num_classes, dtype=np.float32)[self.predict([image], argmax=True, scales=scales, flip=flip, **kw, **regions)]
         processed = print_segmentation_onto_image(image=image, prediction=prediction, color_map=color_map)
 
         if include_unprocessed_image:

@@ -855,6 +855,38 @@ int fcn8s_op_boundary_pair(void* stream, const uint8_t* gt_label_ids, const void
  * either pointer.  Stream-ordered; does not synchronise; allocates nothing.  FCN8S_ERR_BAD_ARG (nothing launched) for a NULL pointer, N, H or
  * W <= 0, or R outside 1..15; FCN8S_ERR_SHAPE for H * W >= 2^31. */
 int fcn8s_op_boundary_distance(void* stream, const uint8_t* label_ids, int N, int H, int W, int R, uint8_t* codes_out);
+/* Connected regions of a label map, and the cleanup of small ones (the usual post-processing of an argmax map: the specks inside a car or on a
+ * wall are merged into a neighbour), for a batch of N maps of H x W pixels on DEVICE pointers.  All integers.
+ *   Per image: a label map L[H, W] of class ids 0..255, pixel index i = y * W + x.  labels [N,H,W]: label_kind 0 = int64 as fcn8s_predict writes
+ *   it (read as 16-byte loads where the address allows), 1 = uint8 (any alignment, any W).  connectivity is 4 or 8.
+ *   Components.  A component is a maximal set of pixels of equal class connected under `connectivity`.  Its id is the smallest pixel index it
+ *   contains; ids are per image (not offset by n * H * W) and depend on nothing but the map.  comp[p] = the id of p's component, area[p] = the
+ *   number of pixels of p's component, both int32 [N,H,W], both stored at every pixel.
+ *   Small.  A component of class c is small when area < min_area[c]; min_area[c] <= 0: class c is never small.  min_area: 256 int32 on the device.
+ *   One round of cleanup.  For a small component S look at every pair (p in S, q 4-adjacent to p, q not in S) -- 4-adjacent under either
+ *   connectivity.  Only a q whose component T is not small is a candidate.  S takes the class of the candidate T with the largest area, the
+ *   smaller id on equal areas (the label found at pixel id(T)); without a candidate S keeps its class.  All decisions of a round are taken on that
+ *   round's input map and applied together.  `rounds` rounds (1..8) run back to back, each on the components of the previous round's output.
+ *   stats (may be NULL) [rounds][4] int64, written, not accumulated: components, small components, relabelled components, pixels changed.
+ *   A label outside 0..255 in an int64 map is the caller's error; such a pixel is a component of its own (area 1) that is never small, is no
+ *   candidate, and is never written; the pixels of this kind met by the call are counted in the work header (fcn8s_op_regions_status).
+ * fcn8s_op_regions_label writes comp_out and, unless it is NULL, area_out.  fcn8s_op_regions_clean rewrites labels in place.
+ * work: fcn8s_op_regions_work_bytes(N, H, W) bytes of 16-byte aligned device scratch = a header of 8192 bytes + 16 bytes per pixel (label uses the
+ * first 256 bytes alone);
+ * its content on entry does not matter, and a buffer that is large enough may be reused for any shape.
+ * Both are a block-based union-find in which only integer min / max / add atomics decide anything: two runs give the same bits.  Every loop is
+ * bounded: a find follows strictly decreasing indices, a union gives up after a fixed number of retries; a loop that meets what cannot be
+ * (never seen) sets a bit in the work header instead of spinning.  fcn8s_op_regions_status synchronises the stream and copies {those bits (0 = sound),
+ * pixels with a label out of range} of the most recent label / clean call on `work` into status_host[2].
+ * label and clean are stream-ordered, do not synchronise and allocate nothing.  FCN8S_ERR_BAD_ARG (nothing launched) for a NULL labels / comp_out /
+ * min_area / work, a work that is not 16-byte aligned, label_kind outside {0, 1}, connectivity outside {4, 8}, rounds outside 1..8, N, H or W <= 0;
+ * FCN8S_ERR_SHAPE for H * W >= 2^31 or N > 65535. */
+size_t fcn8s_op_regions_work_bytes(int N, int H, int W);
+int fcn8s_op_regions_label(void* stream, const void* labels, int label_kind, int N, int H, int W, int connectivity,
+                           int32_t* comp_out, int32_t* area_out, void* work);
+int fcn8s_op_regions_clean(void* stream, void* labels, int label_kind, int N, int H, int W, int connectivity,
+                           const int32_t* min_area_dev, int rounds, void* work, int64_t* stats_dev);
+int fcn8s_op_regions_status(void* stream, const void* work, int64_t* status_host);
 /* One TF-Adam (step t, 1-based) / SGD-momentum step over n floats on DEVICE pointers, the gradient scaled by grad_scale.  Every pointer may
  * have any float (4-byte) alignment of its own.  These two, their _dev and their _ema forms below run one kernel and give the same bits. */
 int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* m, float* v, int64_t n, int t,
