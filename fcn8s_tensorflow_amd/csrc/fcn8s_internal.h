@@ -163,6 +163,7 @@ extern thread_local int t_deterministic;
 float* det_scratch(hipStream_t s, size_t floats);              // per-(device, stream) scratch, grown on demand; nullptr if the allocation failed
 float* scratch2(hipStream_t s, size_t floats);                 // a second such buffer (the column sums' partials, which run beside a det_scratch user)
 void scratch_release(hipStream_t s);                           // frees both buffers of the calling device's stream s (fcn8s_destroy; the stream is idle)
+long long scratch_bytes_live();                                // bytes the two per-(device, stream) pools hold right now, all devices and streams (option "scratch_bytes_live")
 // C[r][c] (= or +=) sum_{k < nsplit, in order} ws[k * slab + r * ldc + c]   for r < rows, c < cols
 void launch_det_reduce(float* C, const float* ws, long long rows, int cols, int ldc, long long slab, int nsplit, bool accumulate, hipStream_t s);
 // 3x3 / 7x7 SAME conv weight (+bias) gradient, several taps per block (3x3: all nine, 7x7: one filter row);

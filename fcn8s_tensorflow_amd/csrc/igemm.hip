@@ -14,6 +14,7 @@
 #include "fcn8s_internal.h"
 #include <cmath>
 #include <cstdlib>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <string>
@@ -49,18 +50,19 @@ namespace {
 struct ScratchBuf { float* p = nullptr; size_t cap = 0; };
 std::mutex g_scratch_mu;
 std::map<std::pair<int, hipStream_t>, ScratchBuf> g_scratch[2];      // [0] det_scratch, [1] scratch2 (column sums)
+std::atomic<long long> g_scratch_bytes{0};                            // what the two pools hold right now (option "scratch_bytes_live")
 float* scratch_get(int which, hipStream_t s, size_t floats, size_t floor_)
 {
     int dev = 0; (void)hipGetDevice(&dev);
     std::lock_guard<std::mutex> lk(g_scratch_mu);
     ScratchBuf& b = g_scratch[which][std::make_pair(dev, s)];
     if (b.cap < floats) {
-        if (b.p) hipFree(b.p);                     // (synchronises the device: nothing still reads the old buffer)
+        if (b.p) { hipFree(b.p); g_scratch_bytes -= (long long)(b.cap * sizeof(float)); }   // (synchronises the device: nothing still reads the old buffer)
         b.p = nullptr; b.cap = 0;
         size_t want = floats + floats / 4 + (1u << 20);
         if (want < floor_) want = floor_;
         if (hipMalloc((void**)&b.p, want * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        b.cap = want;
+        b.cap = want; g_scratch_bytes += (long long)(want * sizeof(float));
     }
     return b.p;
 }
@@ -74,9 +76,10 @@ void scratch_release(hipStream_t s)
     std::lock_guard<std::mutex> lk(g_scratch_mu);
     for (auto& pool : g_scratch) {
         auto it = pool.find(std::make_pair(dev, s));
-        if (it != pool.end()) { if (it->second.p) hipFree(it->second.p); pool.erase(it); }
+        if (it != pool.end()) { if (it->second.p) { hipFree(it->second.p); g_scratch_bytes -= (long long)(it->second.cap * sizeof(float)); } pool.erase(it); }
     }
 }
+long long scratch_bytes_live() { return g_scratch_bytes.load(); }
 __global__ __launch_bounds__(256) void det_reduce_kernel(float* __restrict__ C, const float* __restrict__ ws, const long long n, const int cols, const int ldc,
                                                          const long long slab, const int nsplit, const int accumulate)
 {

@@ -201,6 +201,8 @@ struct fcn8s_model {
     DeviceBuf<char> mc_buf;                                               // fcn8s_predict_mc: staged images, the two accumulators, staged outputs (grown, never shrunk)
     bool mc_masks = false;                                                // the last forward pass was fcn8s_predict_mc's: fcn8s_get_dropout_masks reports its last sample's masks
     hipStream_t stream = nullptr;
+    // fcn8s_set_stream: every stream the model was given (fcn8s_destroy gives their scratch back) and the event that orders a new stream behind the old one's queue
+    std::set<hipStream_t> streams_seen; hipEvent_t move_ev = nullptr;
     int64_t step = 0;
     // workspace for the current (N,H,W)
     int N = 0, H = 0, W = 0;
@@ -272,6 +274,7 @@ struct fcn8s_model {
         for (auto& g : groups) for (auto& ev : g.ev) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
         for (auto& e : bucket_ev) if (e) hipEventDestroy(e);
         if (loss_ev) hipEventDestroy(loss_ev);
+        if (move_ev) hipEventDestroy(move_ev);
         if (fp_event) hipEventDestroy(fp_event);
         for (auto& sl : slots) { if (sl.ready) hipEventDestroy(sl.ready); if (sl.consumed) hipEventDestroy(sl.consumed); }
         if (copy_stream) hipStreamDestroy(copy_stream);
@@ -2517,7 +2520,12 @@ int fcn8s_destroy(fcn8s_model* m)
     const std::string comm_text = rc_comm ? m->err : std::string();
     hipDeviceSynchronize();
     // the per-stream scratch of the streams this model ran on (the caller's stream may live on: what it holds is given back, the next user grows its own)
-    scratch_release(m->stream);
+    // (the scratch is keyed by the calling device: release under the model's, whichever one the caller has current)
+    m->streams_seen.insert(m->stream);
+    int cur = m->device; (void)hipGetDevice(&cur);
+    if (cur != m->device && hipSetDevice(m->device) != hipSuccess) (void)hipGetLastError();
+    for (hipStream_t s : m->streams_seen) scratch_release(s);
+    if (cur != m->device) (void)hipSetDevice(cur);
     delete m;
     // the model is gone either way; a communicator that had failed is reported once, with its reason in fcn8s_last_error(NULL)
     if (rc_comm) { g_last_error = comm_text; return rc_comm; }
@@ -2655,7 +2663,7 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
 {
     if (!key) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_option: null key");
     const std::string k = key;
-    if (k == "device_bytes_live") return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_option: 'device_bytes_live' is read-only");
+    if (k == "device_bytes_live" || k == "scratch_bytes_live") return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_option: '" + k + "' is read-only");
     if (!m) {
         if (k == "op_f32x3") { t_op_split = value ? 3 : 0; return FCN8S_OK; }
         if (k == "op_deterministic") { t_deterministic = value ? 1 : 0; return FCN8S_OK; }
@@ -2702,6 +2710,7 @@ int fcn8s_get_option(const fcn8s_model* m, const char* key, int64_t* value)
     if (!key || !value) return FCN8S_ERR_BAD_ARG;
     const std::string k = key;
     if (k == "device_bytes_live") { *value = g_device_bytes_live.load(); return FCN8S_OK; }      // (process-wide: with or without a model)
+    if (k == "scratch_bytes_live") { *value = scratch_bytes_live(); return FCN8S_OK; }           // (process-wide too: the per-(device, stream) scratch)
     if (!m) {
         if (k == "op_f32x3") { *value = t_op_split == 3; return FCN8S_OK; }
         if (k == "op_deterministic") { *value = t_deterministic; return FCN8S_OK; }
@@ -2722,7 +2731,32 @@ int fcn8s_get_option(const fcn8s_model* m, const char* key, int64_t* value)
     return FCN8S_OK;
 }
 
-int fcn8s_set_stream(fcn8s_model* m, void* s) { if (!m) return FCN8S_ERR_BAD_ARG; m->stream = (hipStream_t)s; return FCN8S_OK; }
+// The model's own state (parameters, workspace, kept banks, optimizer slots, metrics) follows it across streams: the new stream waits, on the device, for
+// everything the model has queued on the old one.  One event, made at the first move; the host waits only if that event cannot be made, recorded or
+// waited for (a caller that destroyed the old stream too early, say): then the old stream, or failing that the device, is synchronised instead.  The
+// model moves to the new stream either way, so such a mistake does not tie it to a dead handle.
+int fcn8s_set_stream(fcn8s_model* m, void* s)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    hipStream_t to = (hipStream_t)s;
+    if (to == m->stream) return FCN8S_OK;
+    int cur = m->device; (void)hipGetDevice(&cur);           // the event belongs to the model's device, whichever one the caller has current
+    if (cur != m->device) HIPCHK(m, hipSetDevice(m->device));
+    hipError_t e = hipSuccess;
+    if (!m->move_ev) { e = hipEventCreateWithFlags(&m->move_ev, hipEventDisableTiming); if (e != hipSuccess) m->move_ev = nullptr; }
+    if (e == hipSuccess) e = hipEventRecord(m->move_ev, m->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(to, m->move_ev, 0);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        e = hipStreamSynchronize(m->stream);
+        if (e != hipSuccess) { (void)hipGetLastError(); e = hipDeviceSynchronize(); }
+    }
+    m->streams_seen.insert(m->stream);
+    m->stream = to;
+    if (cur != m->device) (void)hipSetDevice(cur);
+    HIPCHK(m, e);                                            // (only if the device itself could not be synchronised)
+    return FCN8S_OK;
+}
 int fcn8s_synchronize(fcn8s_model* m) { if (!m) return FCN8S_ERR_BAD_ARG; HIPCHK(m, hipStreamSynchronize(m->stream)); return FCN8S_OK; }
 
 int fcn8s_num_params(const fcn8s_model* m) { return m ? (int)m->params.size() : 0; }

@@ -118,7 +118,18 @@ int         fcn8s_layout_bucket(const fcn8s_config* cfg, int bucket, size_t* off
 int         fcn8s_create(const fcn8s_config* cfg, fcn8s_model** out);
 int         fcn8s_destroy(fcn8s_model* m);                           /* frees everything; FCN8S_ERR_RCCL (text: fcn8s_last_error(NULL)) if the model's communicator had failed */
 const char* fcn8s_last_error(const fcn8s_model* m);                  /* m may be NULL: last create() error */
-int         fcn8s_set_stream(fcn8s_model* m, void* hip_stream);      /* run on the caller's stream (e.g. torch's current stream) */
+/* fcn8s_set_stream: run on the caller's stream (e.g. torch's current stream).  Every later call needs no ordering but that stream's: what it reads
+ * must be ready on that stream, and what it writes is ready there when its work on that stream is.  Not all of the work is queued on that stream:
+ * the library has streams of its own (staging copies, weight gradients, the communicator), ordered against the caller's by events, and a call
+ * that reads a value back copies it with a blocking hipMemcpy after it has synchronised the caller's stream -- right in value, though such a call
+ * also waits for whatever the NULL stream is busy with.  The model's internal state (parameters it owns, gradients, workspace, kept filter banks,
+ * optimizer slots, the average, metrics) follows the model across streams: when the handle changes, the new stream is made to wait (an event, no
+ * host synchronisation) for everything the model has queued on the old one, so a step on stream A followed by a call on stream B is ordered as if
+ * both had run on one stream.  The old stream must still exist at that moment; if it does not, or the event fails otherwise, the host is
+ * synchronised instead and the model moves all the same.  The caller's own tensors -- images, labels, DEVICE outputs, ext_params / ext_grads when
+ * the caller writes them -- remain the caller's to order against the stream it hands over.
+ * fcn8s_destroy gives back the per-stream scratch of every stream the model was given. */
+int         fcn8s_set_stream(fcn8s_model* m, void* hip_stream);
 int         fcn8s_synchronize(fcn8s_model* m);
 
 /* ---- variables (graph.get_tensor_by_name, :331-350; Saver :124,:927,:943) --- */
@@ -551,6 +562,9 @@ int fcn8s_fp8_set_calibration(fcn8s_model* m, const float* amax, int n);
  *                              the scratch of fcn8s_predict_tta and fcn8s_predict_crf, its bf16 copies and its cached (frozen / TTA) filter banks
  *     "frozen"                 (read-only) 1 while fcn8s_freeze_params(m, 1) holds
  *     "device_bytes_live"      (read-only, process-wide: m may be NULL) device bytes the library's models and op-level calls hold right now (not the per-stream scratch)
+ *     "scratch_bytes_live"     (read-only, process-wide: m may be NULL) device bytes of the per-(device, stream) scratch (slab reductions, column sums, split-K
+ *                              slabs) held right now.  A model's fcn8s_destroy releases the scratch of every stream it ran on; op-level calls have no owner, so
+ *                              what they grow on a stream stays until a model that ran on that stream is destroyed: at most two buffers per distinct stream
  *     "comm_timeout_ms" 600000 the communicator's watchdog (see fcn8s_comm_init): a collective older than this is given up, the communicator aborted
  *   op-context options (m == NULL): the arithmetic of the op-level entry points below, which have no model.  The value belongs to the
  *   CALLING THREAD (thread-local) and is read by that thread's later fcn8s_op_* calls only; no model ever reads it, so two models -- or a
@@ -597,7 +611,11 @@ int fcn8s_profile_get(fcn8s_model* m, int group, const char** name, double* tota
                       int64_t* launches, double* flops, double* bytes);
 
 /* ---- single ops on DEVICE pointers (unit parity tests; same kernels the model
- * uses).  `stream` may be NULL (default stream).                                 */
+ * uses).  `stream` may be NULL (default stream).  Every entry needs no ordering but
+ * that of `stream` (an entry that returns a value to the host synchronises `stream`,
+ * then copies with a blocking hipMemcpy).  The scratch such a call grows
+ * for `stream` has no owner (see "scratch_bytes_live"): bounded by the number of
+ * distinct streams.                                                               */
 int fcn8s_op_preprocess(void* stream, const void* images, int image_dtype, float* out4, int64_t npix);
 /* the two kernels of fcn8s_predict_tta on DEVICE pointers.  tta_input: uint8 [N,H,W,3] -> the forward's input [N,Hp,Wp,4] (resize to
  * Hs x Ws as fcn8s_op_resample_u8, mirror if flip, fcn8s_op_preprocess's arithmetic, zeros outside [0,Hs)x[0,Ws)).  tta_accumulate: plain
