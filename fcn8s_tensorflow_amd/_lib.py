@@ -95,6 +95,9 @@ SIGNATURES = {
     "fcn8s_set_boundary_loss": (_i, [_p, _i, _p]),
     "fcn8s_get_boundary_codes": (_i, [_p, _p, _i64]),
     "fcn8s_get_loss_terms": (_i, [_p, _fp, _fp, _fp]),
+    "fcn8s_set_soft_targets": (_i, [_p, _f, _f, _i]),
+    "fcn8s_bind_soft_targets": (_i, [_p, _p, _i, _i, _i, _i, _i64]),
+    "fcn8s_get_soft_target_term": (_i, [_p, _fp]),
     "fcn8s_eval_step": (_i, [_p, _p, _i, _p, _i, _i, _i, _f, _i]),
     "fcn8s_metrics_reset": (_i, [_p]),
     "fcn8s_metrics_get": (_i, [_p, _dp, _dp, _dp]),

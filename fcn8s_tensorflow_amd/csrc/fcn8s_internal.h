@@ -257,6 +257,15 @@ void launch_lovasz_loss(const float* x, int is_logits, const uint8_t* labels, co
 void launch_lovasz_backward(const float* x, int is_logits, const uint8_t* labels, const PixMap* map, int N, long long npix, const LovaszLayout& y,
                             char* ws, float lambda, int accumulate, float* out, float* colsum, hipStream_t s);
 void launch_lovasz_total(float* terms, float lce, float* loss_out, hipStream_t s);   // no Lovász term: loss = lce terms[0] + terms[2], terms[1] = 0
+// ---- the soft-target term (soft_targets.hip; fcn8s_set_soft_targets, fcn8s_bind_soft_targets in include/fcn8s_hip.h) ------------------
+// One launch behind the cross-entropy (and the Lovász term): dlogits (plain [npix, C] or blocked, map) += lambda (T / npix) (s - q) over the pixels of
+// U and the columns < K, then one small kernel: term[0] = L_kd, loss[0] += lambda L_kd, lastbias[c] += the contribution's column sums.  probs: the
+// target rows, K floats every row_stride floats, in pixel order.  ws: soft_targets_scratch_bytes() of per-block partials.  C <= 64.
+size_t soft_targets_scratch_bytes();
+double soft_targets_bytes(long long npix, int C, int K);      // the algorithmic bytes (profile group "soft_targets")
+void launch_soft_targets(const float* logits, float* dlogits, const float* probs, const uint8_t* labels, const PixMap* map, int N, long long npix, int C,
+                         int K, long long row_stride, float lambda, float temperature, int all_pixels, char* ws, float* loss, float* term,
+                         float* lastbias, hipStream_t s);
 void launch_softmax_argmax(const float* logits, float* softmax_out, long long* argmax_out,
                            long long npix, int C, hipStream_t s, const PixMap* map = nullptr, int N = 0);
 // ---- the k = 2s transposed conv as one GEMM (see PixMap): operand / result re-layouts, all tiny next to the GEMMs -------------

@@ -241,6 +241,13 @@ struct fcn8s_model {
     // d_terms = the unscaled terms of the last training loss (ce, lovasz, l2; right behind d_lastbias), have_terms once a training loss ran
     bool lov_on = false, have_terms = false; float lov_ce = 1.f, lov_w = 0.f; int lov_per_image = 0, lov_all = 0;
     DeviceBuf<uint8_t> d_lovmask; int lov_nmask = 0; DeviceBuf<char> lov_ws; float* d_terms = nullptr;
+    // fcn8s_set_soft_targets: L += kd_w * L_kd at temperature kd_T over the valid pixels (kd_all: over every pixel); kd_w == 0: off.  kd_probs = the
+    // caller's target rows bound by fcn8s_bind_soft_targets (not owned; kd_K floats every kd_stride, for a batch of kd_N x kd_H x kd_W), nullptr once a
+    // training loss has consumed them.  kd_ws = the per-block partials, grown on first use (a "workspace_allocation"); the term lands in d_terms[3];
+    // have_kd: the last training loss ran with the term
+    float kd_w = 0.f, kd_T = 1.f; int kd_all = 0; bool have_kd = false;
+    const float* kd_probs = nullptr; int kd_N = 0, kd_H = 0, kd_W = 0, kd_K = 0; long long kd_stride = 0;
+    DeviceBuf<char> kd_ws;
     // fcn8s_accumulate_bucket: the accumulator (total floats, the gradient buffer's buckets; grown at the first fold -- a "workspace_allocation" --
     // and kept until the model goes), per bucket the micro-batches folded and not yet flushed, and whether this backward pass's bucket was taken
     DeviceBuf<float> d_acc; int acc_k[FCN8S_MAX_BUCKETS] = {0}; bool acc_taken[FCN8S_MAX_BUCKETS] = {false};
@@ -2219,6 +2226,17 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
                                m->d_lastbias, s);
     } else if (lov)
         launch_lovasz_total(m->d_terms, m->lov_ce, m->d_loss, s);
+    if (with_grad) m->have_kd = false;
+    if (with_grad && m->kd_w != 0.f) {
+        // L_kd and its gradient against the bound target rows (fcn8s_forward_loss has checked the binding): dlogits += kd_w d L_kd / d logits, then
+        // the loss, the term and the bias column sums -- all in front of the loss copy below
+        if (!m->kd_ws.grow(soft_targets_scratch_bytes(), s, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "the soft-target term's scratch cannot be allocated");
+        ProfScope ps(m, "soft_targets", 0, soft_targets_bytes(npix, m->C, m->kd_K));
+        const bool blk = m->tconv_gemm && m->logits_b;
+        launch_soft_targets(blk ? m->logits_b : A(m, "logits"), blk ? m->dlogits_b : m->dlogits, m->kd_probs, lab_dev, blk ? &m->pm : nullptr, m->N, npix,
+                            m->C, m->kd_K, m->kd_stride, m->kd_w, m->kd_T, m->kd_all, m->kd_ws, m->d_loss, m->d_terms + 3, m->d_lastbias, s);
+        m->have_kd = true;
+    }
     // The loss is final here, a third of the way into a training step: queue its copy now, so that fcn8s_read_loss waits for this
     // point of the stream only and the host can go on queueing the next step while the backward pass runs (the reference fetches
     // the loss every step, fcn8s_tensorflow.py:554-578; waiting for the whole stream left the GPU idle for ~2 ms per step).
@@ -2837,10 +2855,17 @@ int fcn8s_forward_loss(fcn8s_model* m, const void* images, int dtype, const uint
     fp8_clear_calibration(m);
     if (!m || !images || !labels) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_forward_loss: null argument");
     if (!(keep_prob > 0.f && keep_prob <= 1.f)) return fail(m, FCN8S_ERR_BAD_ARG, "keep_prob must be in (0, 1]");
+    if (m->kd_w != 0.f) {                                    // never train silently without a configured term
+        if (!m->kd_probs) return fail(m, FCN8S_ERR_STATE, "fcn8s_set_soft_targets is on and no targets are bound: call fcn8s_bind_soft_targets before every training loss");
+        if (m->kd_N != N || m->kd_H != H || m->kd_W != W)
+            return fail(m, FCN8S_ERR_SHAPE, "the bound soft targets are for a batch of " + std::to_string(m->kd_N) + " x " + std::to_string(m->kd_H) + " x " +
+                        std::to_string(m->kd_W) + ", the training loss for " + std::to_string(N) + " x " + std::to_string(H) + " x " + std::to_string(W));
+    }
     FwdCall call; call.keep_prob = keep_prob; call.train = true;
     const uint8_t* lab;
     int rc = run_pass(m, images, dtype, labels, N, H, W, where, call, &lab); if (rc) return rc;
     rc = compute_loss(m, lab, l2_rate, true); if (rc) return rc;
+    m->kd_probs = nullptr;                                   // a binding is consumed by exactly one training loss
     m->next_bucket = 0;
     for (int b = 0; b < kNumBuckets; ++b) m->acc_taken[b] = false;
     HIPCHK(m, hipGetLastError());
@@ -3475,6 +3500,42 @@ int fcn8s_get_loss_terms(fcn8s_model* m, float* ce, float* lovasz, float* l2)
     if (ce) *ce = t[0];
     if (lovasz) *lovasz = t[1];
     if (l2) *l2 = t[2];
+    return FCN8S_OK;
+}
+
+int fcn8s_set_soft_targets(fcn8s_model* m, float weight, float temperature, int all_pixels)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!std::isfinite(weight) || weight < 0.f) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_soft_targets: the weight must be finite and >= 0");
+    if (!std::isfinite(temperature) || !(temperature > 0.f)) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_soft_targets: the temperature must be finite and > 0");
+    if (all_pixels != 0 && all_pixels != 1) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_soft_targets: all_pixels must be 0 or 1");
+    if (weight == 0.f) { m->kd_w = 0.f; m->kd_T = 1.f; m->kd_all = 0; m->kd_probs = nullptr; m->have_kd = false; return FCN8S_OK; }    // off: any binding is dropped
+    if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_set_soft_targets");
+    m->kd_w = weight; m->kd_T = temperature; m->kd_all = all_pixels;
+    return FCN8S_OK;
+}
+
+int fcn8s_bind_soft_targets(fcn8s_model* m, const float* probs_dev, int N, int H, int W, int ncols, int64_t row_stride)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!probs_dev) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_bind_soft_targets: null argument");
+    if (m->kd_w == 0.f) return fail(m, FCN8S_ERR_STATE, "fcn8s_bind_soft_targets: the soft-target term is off (fcn8s_set_soft_targets)");
+    if (N <= 0 || H <= 0 || W <= 0) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_bind_soft_targets: N, H and W must be positive");
+    if (ncols < 1 || ncols > m->C) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_bind_soft_targets: ncols must be in 1 .. num_classes (" + std::to_string(m->C) + ")");
+    if (row_stride < ncols) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_bind_soft_targets: row_stride must be >= ncols");
+    if (((uintptr_t)probs_dev & 3) != 0) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_bind_soft_targets: the targets must be 4-byte aligned");
+    m->kd_probs = probs_dev; m->kd_N = N; m->kd_H = H; m->kd_W = W; m->kd_K = ncols; m->kd_stride = (long long)row_stride;
+    return FCN8S_OK;
+}
+
+int fcn8s_get_soft_target_term(fcn8s_model* m, float* kd)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!m->have_kd) return fail(m, FCN8S_ERR_STATE, "fcn8s_get_soft_target_term: the last training loss ran without the soft-target term");
+    float t = 0.f;
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(&t, m->d_terms + 3, sizeof t, hipMemcpyDeviceToHost));
+    if (kd) *kd = t;
     return FCN8S_OK;
 }
 

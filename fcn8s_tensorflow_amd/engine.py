@@ -131,6 +131,8 @@ class Engine:
         self.loss_config = None              # set_loss: the training loss's configuration (None = the reference's mean)
         self.lovasz_config = None            # set_lovasz: the Lovász-softmax term's configuration (None = off)
         self.boundary_config = None          # set_boundary_loss: the boundary weighting's configuration, dict(table, radius) (None = off)
+        self.soft_target_config = None       # set_soft_targets: the soft-target term's configuration, dict(weight, temperature, pixels) (None = off)
+        self._soft_targets = None            # bind_soft_targets: the bound tensor, kept alive until a training loss has consumed it
         self._loss_shape = None              # (N, H, W) of the last training loss (boundary_codes)
         self.grad_clip = None                # set_grad_clip: the global-norm clip's max_norm (None = off; inf = the non-finite guard alone)
         self.ema_config = None               # set_ema: the parameter average's configuration, dict(decay, warmup) (None = off)
@@ -327,7 +329,7 @@ class Engine:
             if nbad:
                 self._bad.zero_()
                 raise ValueError("labels must be one-hot along the last axis (%d rows of the last %s were not); "
-                                 "soft labels are not supported" % (nbad, "batch" if self._label_calls <= 2 else "64 batches"))
+                                 "soft targets go through set_soft_targets / bind_soft_targets, not through the labels" % (nbad, "batch" if self._label_calls <= 2 else "64 batches"))
         return ids
 
     def _inputs(self, images, labels):
@@ -486,6 +488,42 @@ class Engine:
         L.check(L.lib.fcn8s_get_loss_terms(self.h, C.byref(ce), C.byref(lv), C.byref(l2)), self.h)
         return dict(ce=float(ce.value), lovasz=float(lv.value), l2=float(l2.value))
 
+    def set_soft_targets(self, weight=None, temperature=1.0, pixels='valid'):
+        """The soft-target (distillation) term of the training loss (fcn8s_set_soft_targets; definitions in include/fcn8s_hip.h, restated in
+        loss.py): L += weight * L_kd, L_kd = (T^2 / P) sum_p KL(teacher_p || student_p) at `temperature` over the pixels with a valid label
+        (`pixels` = 'valid') or over every pixel ('all': a batch whose labels are all "ignore" still has a loss).  Every training loss then
+        needs targets bound with bind_soft_targets first.  No weight (or 0) switches the term off and drops a binding.  Evaluation and
+        prediction keep the reference's loss."""
+        w, t, ap = loss_mod.validate_soft_targets(weight, temperature, pixels)
+        L.check(L.lib.fcn8s_set_soft_targets(self.h, w, t, ap), self.h)
+        if w == 0.0:
+            self._soft_targets = None
+        self.soft_target_config = None if w == 0.0 else dict(weight=w, temperature=t, pixels=pixels)
+
+    def bind_soft_targets(self, probs):
+        """The targets of the NEXT training loss (fcn8s_bind_soft_targets): a cuda float32 tensor [N, H, W, logical_classes] whose last
+        dimension has unit stride and whose rows are evenly spaced -- a contiguous tensor, or the view predict(argmax=False) returns under
+        padded classes, which is bound through its row stride without a copy.  The tensor is kept alive until a training loss has consumed
+        it; the loss reads it on the engine's stream (torch's current one), so a tensor produced on that stream needs no further ordering."""
+        torch = self.torch
+        if not isinstance(probs, torch.Tensor) or probs.device != self.device or probs.dtype != torch.float32:
+            raise ValueError("soft targets must be a float32 tensor on %s" % (self.device,))
+        if probs.dim() != 4 or probs.shape[-1] != self.logical_classes:
+            raise ValueError("soft targets must be [N, H, W, %d], got %s" % (self.logical_classes, tuple(probs.shape)))
+        N, H, W, K = (int(x) for x in probs.shape)
+        sn, sh, sw, sc = (int(x) for x in probs.stride())
+        if (K > 1 and sc != 1) or sw < K or (W > 1 and sh != W * sw) or (H > 1 and sn != H * W * sw):
+            raise ValueError("soft targets need a unit last-dimension stride and evenly spaced rows (strides %s): pass a contiguous tensor "
+                             "or a class-slice of one" % ((sn, sh, sw, sc),))
+        L.check(L.lib.fcn8s_bind_soft_targets(self.h, C.c_void_p(probs.data_ptr()), N, H, W, K, sw), self.h)
+        self._soft_targets = probs
+
+    def soft_target_term(self):
+        """The unscaled L_kd of the last training loss (fcn8s_get_soft_target_term; synchronises); raises if that loss ran without the term."""
+        kd = C.c_float()
+        L.check(L.lib.fcn8s_get_soft_target_term(self.h, C.byref(kd)), self.h)
+        return float(kd.value)
+
     def loss_stats(self):
         """|V|, |K| and the threshold t of the last training loss (fcn8s_get_loss_stats; synchronises)."""
         v = C.c_int64(); kp = C.c_int64(); t = C.c_float()
@@ -581,6 +619,7 @@ class Engine:
         self._loss_shape = (N, H, W)
         L.check(L.lib.fcn8s_forward_loss(self.h, pi, dt, pl, N, H, W, float(keep_prob), float(l2_rate), where), self.h)
         self._release(ka)
+        self._soft_targets = None                          # (a binding is consumed by the loss that has just been queued)
         for b in range(self.num_buckets):
             L.check(L.lib.fcn8s_backward_bucket(self.h, b), self.h)
             L.check(L.lib.fcn8s_accumulate_bucket(self.h, b, 0), self.h)
@@ -609,6 +648,7 @@ class Engine:
             L.check(L.lib.fcn8s_train_step(self.h, pi, dt, pl, N, H, W, float(learning_rate), float(keep_prob),
                                            float(l2_rate), where, None, C.byref(step)), self.h)
             self._release(ka)
+            self._soft_targets = None
             if fetch_loss:
                 L.check(L.lib.fcn8s_read_loss(self.h, C.byref(loss)), self.h)
             return (float(loss.value) if fetch_loss else None), int(step.value)
@@ -619,6 +659,7 @@ class Engine:
         self._loss_shape = (N, H, W)
         L.check(L.lib.fcn8s_forward_loss(self.h, pi, dt, pl, N, H, W, float(keep_prob), float(l2_rate), where), self.h)
         self._release(ka)
+        self._soft_targets = None                          # (a binding is consumed by the loss that has just been queued)
         red = BucketReducer(self.flat_grads, self.buckets, self.pg, trace=trace, always=always, ready=self._bucket_ready)
         # bucket b is final once call b has returned (include/fcn8s_hip.h): {fc7, decoder}, {fc6}, {conv4, conv5}, {conv1 .. conv3}
         # leave in that order, each while the rest of the backward pass runs
@@ -704,6 +745,7 @@ class Engine:
         self._loss_shape = (N, H, W)
         L.check(L.lib.fcn8s_forward_loss(self.h, pi, dt, pl, N, H, W, float(keep_prob), float(l2_rate), where), self.h)
         self._release(ka)
+        self._soft_targets = None                          # (a binding is consumed by the loss that has just been queued)
         for b in range(self.num_buckets):
             L.check(L.lib.fcn8s_backward_bucket(self.h, b), self.h)
         loss = C.c_float(0.0)

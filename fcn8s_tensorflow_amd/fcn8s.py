@@ -226,7 +226,12 @@ class FCN8s:
               clip_global_norm=None,
               ema_decay=None,
               ema_warmup=True,
-              ema_evaluate=True):
+              ema_evaluate=True,
+              teacher=None,
+              distill_weight=1.0,
+              distill_temperature=1.0,
+              distill_pixels='valid',
+              teacher_predict=None):
         '''Trains the model; arguments as fcn8s_tensorflow.py:424-503.  Summaries are written as TensorBoard
         event files (`<summaries_dir>/<summaries_name>[_eval]/events.out.tfevents.*`: total_loss, learning_rate and
         mean / stddev / max / min / histogram of the ten watched weight-bias pairs, :331-366) and, for reading
@@ -251,7 +256,17 @@ class FCN8s:
         `ema_warmup`: TensorFlow's num_updates rule); the engine's previous setting is restored when train() returns or raises, the shadow
         stays.  With `ema_evaluate` the in-training evaluations and the `save_during_training` saves run on the averaged weights
         (Engine.averaged_weights); the live weights are the raw ones again when train() returns or raises.  Use
-        `with model.averaged_weights():` around evaluate / predict / save afterwards.'''
+        `with model.averaged_weights():` around evaluate / predict / save afterwards.
+        `teacher` adds the soft-target term distill_weight * T^2 / P * sum_p KL(teacher_p || student_p) at T = `distill_temperature` for the
+        duration of the call (Engine.set_soft_targets, loss.py; `distill_pixels` = 'valid': the pixels with a label, 'all': every pixel, so that
+        unlabelled frames train too): another FCN8s on the same device with the same number of classes (any widths or precision), or a
+        callable mapping the batch's device images (a cuda tensor [N, H, W, 3]) to a cuda float32 softmax [N, H, W, num_classes].  Per batch,
+        each accumulated micro-batch included, the images are uploaded once, the teacher runs device in / device out, its result is bound
+        (Engine.bind_soft_targets) and the step runs on the same device images.  `teacher_predict`: keywords of the teacher's `predict`
+        (`scales`, `flip`, `crf`, `temperature`), or `samples` / `keep_prob` for the Monte-Carlo mean of `predict_uncertainty`.  A teacher
+        model is frozen for the duration of the call and its frozen state restored afterwards; the student's previous soft-target setting is
+        restored when train() returns or raises.  While a teacher is set the batches are fed unstaged (no copy of batch k + 1 behind step
+        k).  `distill_loss` (the unscaled term) joins the recorded scalars on the steps that are recorded.'''
         if self.engine.precision == 'fp8_infer':
             raise ValueError("The 'fp8_infer' precision is inference only; switch the engine to another precision "
                              "(e.g. model.engine.set_precision('bf16_train')) before training.")
@@ -266,6 +281,7 @@ class FCN8s:
         custom_boundary = boundary_table is not None
         accumulation_steps, max_norm = optim_mod.validate(accumulation_steps, clip_global_norm)
         ema_d, ema_w = optim_mod.validate_ema(ema_decay, ema_warmup)
+        teacher_fn = self._resolve_teacher(teacher, teacher_predict, distill_weight, distill_temperature, distill_pixels)
         if eval_dataset not in ('train', 'val'):
             raise ValueError("`eval_dataset` must be one of 'train' or 'val', but is '{}'.".format(eval_dataset))
         if eval_dataset == 'val' and (val_generator is None or val_steps is None):
@@ -293,7 +309,14 @@ class FCN8s:
         prev_boundary = self.engine.boundary_config
         prev_clip = self.engine.grad_clip
         prev_ema = self.engine.ema_config
+        prev_soft = self.engine.soft_target_config
+        teacher_engine = teacher.engine if (teacher_fn is not None and isinstance(teacher, FCN8s)) else None
+        teacher_was_frozen = bool(teacher_engine.get_option("frozen")) if teacher_engine is not None else False
         try:
+            if teacher_fn is not None:
+                self.engine.set_soft_targets(distill_weight, distill_temperature, distill_pixels)
+                if teacher_engine is not None:
+                    teacher_engine.freeze(True)
             if ema_d:
                 self.engine.set_ema(ema_d, ema_w)
             averaged = self.engine.averaged_weights if (ema_evaluate and self.engine.ema_config) else contextlib.nullcontext
@@ -308,7 +331,7 @@ class FCN8s:
             for epoch in range(1, epochs + 1):
                 self._run_epoch(train_generator, steps_per_epoch, learning_rate_schedule, keep_prob, l2_regularization,
                                 'Epoch {}/{}'.format(epoch, epochs), training_loss_display_averaging,
-                                train_log, summaries_frequency, accumulation_steps)
+                                train_log, summaries_frequency, accumulation_steps, teacher_fn)
                 eval_epoch = epoch % eval_frequency == 0
 
                 if metrics and eval_epoch:
@@ -343,36 +366,85 @@ class FCN8s:
                 self.engine.set_lovasz(**(prev_lovasz or dict(lovasz_weight=0.0)))
             if custom_boundary:
                 self.engine.set_boundary_loss(**(prev_boundary or {}))
+            if teacher_fn is not None:
+                self.engine.set_soft_targets(**(prev_soft or {}))
+                if teacher_engine is not None:
+                    teacher_engine.freeze(teacher_was_frozen)
             for log in (train_log, eval_log):          # the event files are complete and closed when train() returns or raises
                 if log is not None:
                     log.close()
 
-    def _run_epoch(self, generator, steps, schedule, keep_prob, l2_rate, title, window, log, log_every, accumulation_steps=1):
+    def _resolve_teacher(self, teacher, teacher_predict, weight, temperature, pixels):
+        '''train()'s teacher arguments -> None (no teacher, or weight 0) or a function: device images -> device softmax.'''
+        if teacher is None:
+            if teacher_predict is not None:
+                raise ValueError("`teacher_predict` needs a `teacher`.")
+            return None
+        w, _, _ = loss_mod.validate_soft_targets(weight, temperature, pixels)
+        kw = dict(teacher_predict or {})
+        if not isinstance(teacher, FCN8s):
+            if not callable(teacher):
+                raise ValueError("`teacher` must be an FCN8s or a callable mapping device images to a device softmax, got {!r}.".format(teacher))
+            if kw:
+                raise ValueError("`teacher_predict` goes with an FCN8s teacher; a callable teacher takes the images alone.")
+            return teacher if w else None
+        if teacher is self or teacher.engine is self.engine:
+            raise ValueError("`teacher` must be another model: training changes the student's weights under a frozen teacher.")
+        if teacher.engine.device != self.engine.device:
+            raise ValueError("`teacher` must live on the student's device ({}), but is on {}.".format(self.engine.device, teacher.engine.device))
+        if teacher.engine.logical_classes != self.engine.logical_classes:
+            raise ValueError("`teacher` has {} classes, the student {}.".format(teacher.engine.logical_classes, self.engine.logical_classes))
+        monte_carlo = 'samples' in kw or 'keep_prob' in kw
+        allowed = {'samples', 'keep_prob'} if monte_carlo else {'scales', 'flip', 'crf', 'temperature'}
+        if set(kw) - allowed:
+            raise ValueError("`teacher_predict` takes `scales`, `flip`, `crf`, `temperature`, or `samples` / `keep_prob` for the Monte-Carlo "
+                             "mean; got {}.".format(sorted(kw)))
+        if not w:
+            return None
+        if monte_carlo:
+            return lambda images: teacher.predict_uncertainty(images, argmax=False, **kw)[0]
+        return lambda images: teacher.predict(images, argmax=False, **kw)
+
+    def _bind_teacher(self, teacher_fn, images):
+        '''One batch under a teacher: the images on the device (uploaded once), the teacher's softmax of them bound as the next training
+        loss's targets.  Returns the device images for the step.'''
+        dev = self.engine._images(images, force_device=True)[0]
+        self.engine.bind_soft_targets(teacher_fn(dev))
+        return dev
+
+    def _run_epoch(self, generator, steps, schedule, keep_prob, l2_rate, title, window, log, log_every, accumulation_steps=1, teacher_fn=None):
         '''One epoch of train steps (fcn8s_tensorflow.py:542-590): a step runs with the schedule's value
         at the global step before it; `training_loss` is the mean over the last `window` steps.  With `accumulation_steps` = A > 1 a
         step is one update over A batches: A - 1 accumulated micro-batches, then the train step; its loss is the mean of the A losses.'''
         recent = deque(maxlen=window)
         bar = trange(steps, file=sys.stdout, disable=self.engine.rank != 0)
         bar.set_description(title)
-        feed = _Feeder(self.engine, generator, steps * accumulation_steps)        # batch k+1 is decoded / staged / copied while step k runs
+        # batch k+1 is decoded / staged / copied while step k runs (under a teacher: decoded only -- the teacher reads the images as a tensor)
+        feed = _Feeder(self.engine, generator, steps * accumulation_steps, stage=teacher_fn is None)
         try:
             for _ in bar:
                 lr = self._lr
                 micro = []
                 for _k in range(accumulation_steps - 1):
                     images, labels = feed.next()
+                    if teacher_fn is not None:
+                        images = self._bind_teacher(teacher_fn, images)
                     micro.append(self.engine.accumulate_step(images, labels, keep_prob=keep_prob, l2_rate=l2_rate))
                 images, labels = feed.next()
+                if teacher_fn is not None:
+                    images = self._bind_teacher(teacher_fn, images)
                 loss, self.g_step = self.engine.train_step(images, labels, learning_rate=lr, keep_prob=keep_prob, l2_rate=l2_rate)
                 if micro:
                     loss = float(np.mean(micro + [loss]))
                 self.variables_updated = True
                 if log is not None and (self.g_step - 1) % log_every == 0:
+                    extra = {}
                     if self.engine.grad_clip is not None:      # (reading them synchronises: only on the steps that are recorded)
                         st = self.engine.update_stats()
-                        log.add(self.g_step, total_loss=loss, learning_rate=lr, grad_norm=st['norm'], clip_coef=st['clip_coef'])
-                    else:
-                        log.add(self.g_step, total_loss=loss, learning_rate=lr)
+                        extra.update(grad_norm=st['norm'], clip_coef=st['clip_coef'])
+                    if teacher_fn is not None:                 # (the last micro-batch's term)
+                        extra.update(distill_loss=self.engine.soft_target_term())
+                    log.add(self.g_step, total_loss=loss, learning_rate=lr, **extra)
                 recent.append(loss)
                 self.training_loss = float(np.mean(recent))
                 bar.set_postfix(ordered_dict={'loss': self.training_loss, 'learning rate': lr})
@@ -1040,7 +1112,7 @@ class _Feeder:
     `next_ids()` (the same batch with class ids instead of the 20x larger one-hot rows); any other generator is consumed through
     next() and its arrays are fed as they are.  Exactly `count` batches are consumed, as in the reference's loops."""
 
-    def __init__(self, engine, generator, count):
+    def __init__(self, engine, generator, count, stage=True):
         import queue
         import threading
         self.q = queue.Queue(maxsize=1)
@@ -1063,7 +1135,7 @@ class _Feeder:
                     if self.stop.is_set():
                         return
                     images, labels = pull() if pull is not None else next(generator)
-                    if (isinstance(images, np.ndarray) and images.dtype == np.uint8 and isinstance(labels, np.ndarray)
+                    if (stage and isinstance(images, np.ndarray) and images.dtype == np.uint8 and isinstance(labels, np.ndarray)
                             and labels.dtype == np.uint8 and labels.ndim == 3 and images.ndim == 4):
                         item = (engine.stage(images, labels, slot=i % L.NUM_STAGE_SLOTS), None)
                     else:

@@ -1,8 +1,9 @@
 """Class-weighted and hard-pixel-mined (OHEM) cross-entropy for training (fcn8s_set_loss): argument validation shared with the engine,
 a float64 restatement of both modes for the tests, and class-weight recipes computed from label counts on the host.  The Lovász-softmax
-term (fcn8s_set_lovasz) has its validation and float64 restatement at the end of the file, behind the boundary-weighted cross-entropy
+term (fcn8s_set_lovasz) has its validation and float64 restatement behind the boundary-weighted cross-entropy
 (fcn8s_set_boundary_loss; fcn8s_op_boundary_distance, fcn8s_op_softmax_xent_px): its table builders, the NumPy route of its distance codes,
-its validation and the facade's argument rule (resolve_boundary).
+its validation and the facade's argument rule (resolve_boundary).  The soft-target term (fcn8s_set_soft_targets) closes the file: its
+validation and its float64 and float32 restatements.
 
 P = pixels of the batch, V = the valid pixels (label id < C), l_p = the per-pixel loss m + log(sum exp(v - m)) - v[y_p] (>= 0),
 w_c = the class weights.
@@ -365,3 +366,79 @@ def lovasz_restate(x, labels, N, per_image=False, classes='present', x_is='logit
     gz = p * (gp - (gp * p).sum(1, keepdims=True))
     gz[~valid] = 0.0
     return dict(loss=total / S, class_loss=class_loss, participating=part, grad_prob=gp, grad_logits=gz)
+
+
+# ---- soft targets (fcn8s_set_soft_targets, fcn8s_bind_soft_targets; the definition is in include/fcn8s_hip.h) ----------------------------
+def validate_soft_targets(weight=None, temperature=1.0, pixels='valid'):
+    """-> (float32 weight (0.0 = off), float32 temperature, all_pixels 0/1); ValueError for what fcn8s_set_soft_targets rejects.  `weight`
+    None or 0 is "off"; `pixels` is 'valid' (the pixels with a label id < C) or 'all'."""
+    def number(v, name):
+        if isinstance(v, bool):
+            raise ValueError("`{}` must be a number, got {!r}".format(name, v))
+        try:
+            with np.errstate(over='ignore'):
+                return float(np.float32(v))
+        except (TypeError, ValueError):
+            raise ValueError("`{}` must be a number, got {!r}".format(name, v))
+    w = 0.0 if weight is None else number(weight, 'weight')
+    if not math.isfinite(w) or w < 0:
+        raise ValueError("the soft-target weight must be finite and >= 0, got {!r}".format(weight))
+    t = number(temperature, 'temperature')
+    if not (math.isfinite(t) and t > 0):
+        raise ValueError("the soft-target temperature must be finite and > 0, got {!r}".format(temperature))
+    if pixels not in ('valid', 'all'):
+        raise ValueError("`pixels` must be 'valid' or 'all', got {!r}".format(pixels))
+    return w, t, int(pixels == 'all')
+
+
+def soft_target_restate(logits, targets, labels, weight=1.0, temperature=1.0, pixels='valid', ncols=None, dtype=np.float64):
+    """The soft-target term restated: logits (P, C), targets (P, >= K) rows of probabilities (columns >= K = `ncols`, default C, do not take
+    part), labels (P,) ids (>= C: outside U under 'valid').  `dtype` float64: the definition in float64 (the reference of the tests);
+    float32: every operation rounded to float32 in the kernel's order (classes summed in order, no fused product), kd_p summed in float64 --
+    its distance to the float64 result is the scale of what fp32 can be asked for.
+    -> dict(term = L_kd, loss = weight * L_kd, kd (P,) (0 outside U), dlogits (P, C) = weight (T / P) (s - q), bias (C,) = its column sums
+    (float64 sums), used (P,) bool)."""
+    w, T, all_pixels = validate_soft_targets(weight, temperature, pixels)
+    ft = np.dtype(dtype).type
+    if ft not in (np.float64, np.float32):
+        raise ValueError("dtype must be float64 or float32")
+    z = np.asarray(logits)
+    P, C = z.shape
+    K = C if ncols is None else int(ncols)
+    if not 1 <= K <= C:
+        raise ValueError("`ncols` must be in 1..%d, got %r" % (C, ncols))
+    t = np.asarray(targets)
+    if t.ndim != 2 or t.shape[0] != P or t.shape[1] < K:
+        raise ValueError("`targets` must be (%d, >= %d), got %s" % (P, K, t.shape))
+    lab = np.asarray(labels).reshape(-1).astype(np.int64)
+    used = np.ones(P, bool) if all_pixels else lab < C
+    z = z[:, :K].astype(ft)
+    t = t[:, :K].astype(ft)
+    beta = ft(1.0) / ft(T)
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        fin = np.isfinite(t).all(1)
+        l = np.log(np.maximum(np.where(np.isfinite(t), t, ft(1.0)), ft(np.finfo(np.float32).tiny))).astype(ft)
+        a = (beta * (l - l.max(1, keepdims=True))).astype(ft)
+        b = (beta * (z - z.max(1, keepdims=True))).astype(ft)
+        ea, eb = np.exp(a).astype(ft), np.exp(b).astype(ft)
+        Sq, Ss = np.zeros(P, ft), np.zeros(P, ft)
+        for c in range(K):                                    # classes summed in order
+            Sq = (Sq + ea[:, c]).astype(ft)
+            Ss = (Ss + eb[:, c]).astype(ft)
+        q, s = (ea / Sq[:, None]).astype(ft), (eb / Ss[:, None]).astype(ft)
+        lq, ls = (a - np.log(Sq).astype(ft)[:, None]).astype(ft), (b - np.log(Ss).astype(ft)[:, None]).astype(ft)
+        kd = np.zeros(P, ft)
+        for c in range(K):
+            kd = (kd + (q[:, c] * (lq[:, c] - ls[:, c]).astype(ft)).astype(ft)).astype(ft)
+        coef = ft(w) * (ft(T) / ft(P))
+        g = (coef * (s - q).astype(ft)).astype(ft)
+    kd = np.where(fin, kd, ft(np.nan))
+    g[~fin] = np.nan
+    kd = np.where(used, kd, ft(0.0))
+    g[~used] = 0.0
+    d = np.zeros((P, C), ft)
+    d[:, :K] = g
+    term = float(kd.astype(np.float64).sum() * (float(T) * float(T) / P))
+    if ft is np.float32:
+        term = float(np.float32(term))
+    return dict(term=term, loss=w * term, kd=kd, dlogits=d, bias=d.astype(np.float64).sum(0), used=used)

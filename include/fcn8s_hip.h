@@ -258,6 +258,44 @@ int fcn8s_get_loss_terms(fcn8s_model* m, float* ce, float* lovasz, float* l2);
 int fcn8s_set_boundary_loss(fcn8s_model* m, int radius, const float* table256);
 int fcn8s_get_boundary_codes(fcn8s_model* m, uint8_t* codes_out, int64_t nbytes);
 
+/* ---- the training objective: soft targets (distillation; Hinton, Vinyals, Dean 2015): KL(teacher || student) at a temperature ---------------
+ * Definitions, per training loss on each rank's own batch:
+ *   P = N*H*W pixels, p = (n*H + h)*W + w, logits z (the library's C classes), labels y_p.  Bound targets t[p, 0..K), K = ncols <= C (the caller's
+ *   logical classes), row p at probs_dev + p * row_stride.  Columns >= K do not take part: target 0, gradient 0 (a padding class's -1e30 logit never
+ *   meets a logarithm).  beta = 1 / T, T finite and > 0.  U = the pixels with y_p < C (all_pixels = 0), or every pixel (all_pixels = 1).
+ *   For p in U, in fp32 with expf and logf, classes summed in order, no product contracted into a sum:
+ *     teacher (the tempered map of temperature.py / fcn8s_op_temperature_apply):
+ *       l_c = logf(max(t_c, FLT_MIN)); a_c = beta (l_c - max_c l); Sq = sum_c expf(a_c); q_c = expf(a_c) / Sq; log q_c = a_c - logf(Sq)
+ *     student:
+ *       b_c = beta (z_c - max_{c<K} z); Ss = sum_c expf(b_c); s_c = expf(b_c) / Ss; log s_c = b_c - logf(Ss)
+ *     kd_p = sum_{c<K} q_c (log q_c - log s_c)
+ *   L_kd = (T^2 / P) sum_{p in U} kd_p -- the denominator is P, as the cross-entropy's, so equal data-parallel shards keep matching the big batch;
+ *   the kd_p are summed in double (per thread, then per block, then over the blocks in a fixed order) and the product is rounded to float once.
+ *   L = ce_weight * L_ce + lovasz_weight * L_lov + weight * L_kd + (the L2 term as before).
+ *   Gradient: dlogits[p,c] += fl(weight * fl(T / P)) * (s_c - q_c) for p in U and c < K; the same contribution reaches the last transposed conv's
+ *   bias gradient.  Class weights, OHEM and the boundary table act on the CE term only.
+ *   A target row with a non-finite entry makes that pixel's term and its gradient row NaN, as fcn8s_op_temperature_apply does: the loss shows it and
+ *   the guard of fcn8s_set_grad_clip skips the update.
+ * One launch behind the cross-entropy (and the Lovász term) plus a one-block reduction, both in front of the loss copy; it works on the logits where
+ * they lie (plain or in the blocked layout of "tconv_gemm").  Deterministic whatever the `deterministic` option says: per-block partial sums reduced
+ * in a fixed order, no float atomics.  The term acts on the training losses only (fcn8s_forward_loss, fcn8s_train_step, each micro-batch of an
+ * accumulated update); evaluation, the metrics and prediction keep the reference's loss and neither consume nor read a binding.  The per-block
+ * partials (about 270 KB) are allocated on first use and counted in "workspace_allocations".  Profile group "soft_targets".
+ * fcn8s_set_soft_targets: weight 0 switches the term off and drops any binding -- then nothing is launched or allocated and the step is bit for bit
+ *   what it was.  FCN8S_ERR_BAD_ARG for a non-finite or negative weight, a temperature that is not finite and > 0, all_pixels outside {0, 1};
+ *   FCN8S_ERR_STATE for switching it on under FCN8S_PREC_FP8_INFER.  The setting survives fcn8s_set_precision, fcn8s_set_option, fcn8s_set_loss,
+ *   fcn8s_set_lovasz and fcn8s_set_boundary_loss.
+ * fcn8s_bind_soft_targets: probs_dev = device float32, N*H*W rows of ncols floats every row_stride floats.  The binding is consumed by exactly one
+ *   training loss, which reads the buffer on the model's stream (ordering against the writer is the caller's, as for device images; the buffer must
+ *   live until that loss has run).  With the term on and nothing bound a training loss returns FCN8S_ERR_STATE, with a binding for another N, H, W
+ *   FCN8S_ERR_SHAPE, both before anything is launched.  FCN8S_ERR_BAD_ARG: NULL or misaligned probs_dev, ncols outside 1 .. num_classes,
+ *   row_stride < ncols; FCN8S_ERR_SHAPE: N, H or W <= 0; FCN8S_ERR_STATE: the term is off.
+ * fcn8s_get_soft_target_term: the unscaled L_kd of the last training loss (synchronises, like fcn8s_get_loss_terms); FCN8S_ERR_STATE if that loss
+ *   ran without the term, or after the term was switched off.  fcn8s_get_loss_terms is what it was.                                       */
+int fcn8s_set_soft_targets(fcn8s_model* m, float weight, float temperature, int all_pixels);
+int fcn8s_bind_soft_targets(fcn8s_model* m, const float* probs_dev, int N, int H, int W, int ncols, int64_t row_stride);
+int fcn8s_get_soft_target_term(fcn8s_model* m, float* kd);   /* unscaled L_kd of the last training loss; synchronises like fcn8s_get_loss_terms */
+
 /* ---- the update: gradient accumulation over micro-batches, a global-norm clip and a non-finite guard (not in the reference, whose step is
  * one batch, one tf.train.AdamOptimizer.minimize, fcn8s_tensorflow.py:256) ------------------------------------------------------------------
  * Accumulation.  The model owns one accumulator acc of fcn8s_param_floats() floats, cut into the gradient buffer's buckets; it is allocated at
