@@ -549,9 +549,11 @@ class PixelLevelEvaluator:
     """Accumulates the official confusion matrix from FCN-8s predictions (train ids, as `FCN8s.predict`
     returns them) and Cityscapes `*_gtFine_labelIds` ground truth, and reports the 19-class scores; with `instance_level`, the
     instance statistics from `*_gtFine_instanceIds` maps and the iIoU scores as well (the evaluator's default table); with
-    `boundary_radius=R` (1..16), the trimap IoU for the band widths 1..R and the boundary F-score for the tolerances 0..R as well."""
+    `boundary_radius=R` (1..16), the trimap IoU for the band widths 1..R and the boundary F-score for the tolerances 0..R as well; with
+    `panoptic=4` or `8` (needs `instance_level`), panoptic quality with the predicted things split into connected components of that
+    connectivity (panoptic.py has the definition and its caveat)."""
 
-    def __init__(self, instance_level=False, boundary_radius=None):
+    def __init__(self, instance_level=False, boundary_radius=None, panoptic=None):
         self.conf = np.zeros((NUM_IDS, NUM_IDS), np.int64)
         self.instance_level = bool(instance_level)
         self.inst_stats = new_instance_stats() if self.instance_level else None
@@ -561,6 +563,21 @@ class PixelLevelEvaluator:
             self.rings = np.zeros((R + 1, NUM_IDS, NUM_IDS), np.int64)
             self.bprec = np.zeros((R + 2, NUM_IDS), np.int64)
             self.brec = np.zeros((R + 2, NUM_IDS), np.int64)
+        self.panoptic = _check_panoptic(panoptic, self.instance_level)
+        if self.panoptic is not None:
+            from . import panoptic as pq
+            self.panoptic_stats = pq.new_stats()
+            self._panoptic_work = None
+
+    def add_panoptic_rows(self, rows, bad):
+        """The rows of `panoptic.pair_rows_numpy` / `pair_rows_device` for one image or a list of images, in file order."""
+        from . import panoptic as pq
+        if isinstance(rows, np.ndarray):
+            rows, bad = [rows], [bad]
+        if int(np.sum(bad)):
+            raise ValueError("{} pixels of the instance map hold a value whose label is beyond 33 (or the prediction an id out of range).".format(int(np.sum(bad))))
+        for r in rows:
+            pq.stats_add(self.panoptic_stats, r)
 
     def add_boundary_tables(self, tables):
         rings, bprec, brec = tables
@@ -589,6 +606,10 @@ class PixelLevelEvaluator:
             conf, entries = pair_counts_device(pred, gt, inst, max_entries)
             if self.boundary_radius is not None:
                 self.add_boundary_tables(boundary_counts_device(pred, gt, self.boundary_radius))
+            if self.panoptic is not None:
+                from . import panoptic as pq
+                rows, bad, self._panoptic_work = pq.pair_rows_device(pred, inst, connectivity=self.panoptic, work=self._panoptic_work)
+                self.add_panoptic_rows(rows, bad)
         else:
             to_np = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
             inst = None
@@ -599,6 +620,9 @@ class PixelLevelEvaluator:
             conf, entries = pair_counts_numpy(to_np(pred_train_ids), to_np(gt_label_ids), inst, pred_is_train_ids)
             if self.boundary_radius is not None:
                 self.add_boundary_tables(boundary_counts_numpy(to_np(pred_train_ids), to_np(gt_label_ids), self.boundary_radius, pred_is_train_ids))
+            if self.panoptic is not None:
+                from . import panoptic as pq
+                self.add_panoptic_rows(*pq.pair_rows_numpy(to_np(pred_train_ids), inst, self.panoptic, pred_is_train_ids))
         self.conf += conf
         if entries is not None:
             for e in entries:
@@ -633,6 +657,10 @@ class PixelLevelEvaluator:
                         "trimapClassScores": OrderedDict((n, v[:R]) for n, v in tri["trimapClassScores"].items()),
                         "trimapRings": self.rings, "boundaryPrecisionCounts": self.bprec, "boundaryRecallCounts": self.brec})
             res.update(boundary_f_scores(self.bprec, self.brec))
+        if self.panoptic is not None:
+            from . import panoptic as pq
+            res["panopticConnectivity"] = self.panoptic
+            res.update(pq.results(self.panoptic_stats))
         return res
 
 
@@ -645,6 +673,19 @@ def instance_map_tensor(inst, device):
             raise ValueError("instance ids do not fit 16 bits")
         a = a.astype(np.uint16)
     return torch.from_numpy(a.view(np.int16)).to(device)
+
+
+PANOPTIC_RESULT_KEYS = ("panopticConnectivity", "panopticQuality", "panopticClassScores", "panopticTp", "panopticFp", "panopticFn", "panopticIouSum")
+
+
+def _check_panoptic(panoptic, instance_level):
+    if panoptic is None:
+        return None
+    if isinstance(panoptic, bool) or panoptic not in (4, 8):
+        raise ValueError("`panoptic` is None or the connectivity of the predicted things' components, 4 or 8, not {!r}".format(panoptic))
+    if not instance_level:
+        raise ValueError("`panoptic` takes its ground-truth segments from the instance-id maps: needs instance_level=True.")
+    return int(panoptic)
 
 
 BOUNDARY_RESULT_KEYS = ("boundaryRadius", "trimapScoreClasses", "trimapScoreCategories", "trimapClassScores", "boundaryFScoreClasses",
@@ -667,7 +708,7 @@ def result_dict(res):
         whole[k] = OrderedDict(res[k])
     for k in ("averageScoreClasses", "averageScoreInstClasses", "averageScoreCategories", "averageScoreInstCategories"):
         whole[k] = res[k]
-    for k in BOUNDARY_RESULT_KEYS:                                 # not the evaluator's: present only after an evaluation with a boundary radius
+    for k in BOUNDARY_RESULT_KEYS + PANOPTIC_RESULT_KEYS:          # not the evaluator's: present only after an evaluation that asked for them
         if k in res:
             whole[k] = res[k].tolist() if isinstance(res[k], np.ndarray) else res[k]
     return whole
@@ -730,17 +771,18 @@ def instance_file_of(ground_truth_file):
     return ground_truth_file.replace("labelIds", "instanceIds")
 
 
-def evaluate_file_pairs(prediction_files, ground_truth_files, device=None, instance_level=False, boundary_radius=None):
+def evaluate_file_pairs(prediction_files, ground_truth_files, device=None, instance_level=False, boundary_radius=None, panoptic=None):
     """evaluateImgLists / evaluatePair (evalPixelLevelSemanticLabeling.py:454-498, 550-635): accumulate conf[gt, pred] over
     pairs of label-id PNGs with the evaluator's checks, then the class / category scores.  `device`: a torch cuda device
     to count on the GPU (the library's kernels), None = NumPy.  `instance_level`: also read each ground truth's `*_instanceIds.png`
     and report the iIoU scores (`classInstScores`, `categoryInstScores`, their averages, `instStats`).  `boundary_radius=R`: also the
     trimap IoU for the band widths 1..R around the ground-truth boundaries and the boundary F-score for the tolerances 0..R (the
-    `trimap*` / `boundary*` keys; `trimap_scores`, `boundary_f_scores`)."""
+    `trimap*` / `boundary*` keys; `trimap_scores`, `boundary_f_scores`).  `panoptic=4` or `8` (needs `instance_level`): also panoptic
+    quality, the predicted things split into connected components of that connectivity (the `panoptic*` keys; panoptic.py)."""
     from PIL import Image
     if len(prediction_files) != len(ground_truth_files):
         raise ValueError("List of images for prediction and groundtruth are not of equal size.")
-    ev = PixelLevelEvaluator(instance_level=instance_level, boundary_radius=boundary_radius)
+    ev = PixelLevelEvaluator(instance_level=instance_level, boundary_radius=boundary_radius, panoptic=panoptic)
     pixels = 0
     for pf, gf in zip(prediction_files, ground_truth_files):
         pred, gt = np.array(Image.open(pf)), np.array(Image.open(gf))
@@ -791,11 +833,11 @@ def evaluate_file_pairs(prediction_files, ground_truth_files, device=None, insta
     return res
 
 
-def evaluate_directory(ground_truth_search, prediction_path, device=None, instance_level=False, boundary_radius=None):
+def evaluate_directory(ground_truth_search, prediction_path, device=None, instance_level=False, boundary_radius=None, panoptic=None):
     """The evaluator's no-argument mode (:667-676): every ground-truth file matching the glob (the official one is
     `<cityscapes>/gtFine/val/*/*_gtFine_labelIds.png`) against its prediction below `prediction_path`."""
     gts = sorted(glob.glob(ground_truth_search))
     if not gts:
         raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
     walk = walk_predictions(prediction_path)
-    return evaluate_file_pairs([find_prediction(prediction_path, g, walk) for g in gts], gts, device, instance_level, boundary_radius)
+    return evaluate_file_pairs([find_prediction(prediction_path, g, walk) for g in gts], gts, device, instance_level, boundary_radius, panoptic)

@@ -1036,6 +1036,16 @@ class Engine:
                                                       work=getattr(self, "_regions_work", None))
         return st
 
+    def panoptic_pair(self, pred, inst, connectivity=4):
+        """The segment pair table of panoptic quality (panoptic.py; the definition is in include/fcn8s_hip.h) of a device tensor of class ids
+        (int64 train ids as `predict` returns them, or uint8 label ids; [H,W] or [N,H,W]) against the uint16 instance map `inst` (a 16-bit
+        device tensor or a NumPy map): one `fcn8s_op_regions_label` and one `fcn8s_op_panoptic_pair` call.  Returns (list of int64 rows
+        (kp, kg, pixels) per image in ascending order, int64 array of bad pixels per image).  The scratch is kept on the engine and regrown
+        only when a larger one is needed."""
+        from . import panoptic
+        rows, bad, self._panoptic_work = panoptic.pair_rows_device(pred, inst, connectivity=connectivity, work=getattr(self, "_panoptic_work", None))
+        return rows, bad
+
     # ---- introspection (tests, bench) -----------------------------------------------------------
     def activation(self, name, shape, missing_ok=False):
         """fcn8s_get_activation.  A conv whose output transform was fused with the next conv's input transform (option `fuse_out_in`)

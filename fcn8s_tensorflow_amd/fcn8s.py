@@ -668,7 +668,8 @@ class FCN8s:
         return len(paths)
 
     def evaluate_cityscapes(self, images_dir, ground_truth_search, resize=False, image_file_extension='png', scales=None, flip=False, crf=None,
-                            instance_level=True, json_path=None, boundary_radius=None, min_region=None, region_connectivity=4, region_rounds=1):
+                            instance_level=True, json_path=None, boundary_radius=None, min_region=None, region_connectivity=4, region_rounds=1,
+                            panoptic=None):
         '''Not in the reference: the official Cityscapes pixel-level table (IoU and iIoU, for classes and for categories) of this model in
         one call, scored where the predictions already are.  Every ground-truth file of the glob `ground_truth_search` (the official one is
         `<cityscapes>/gtFine/val/*/*_gtFine_labelIds.png`) is paired with its image `<city>_<seq>_<frame>*.<ext>` below `images_dir`; per
@@ -684,7 +685,13 @@ class FCN8s:
         `flip` or `crf` change at the contours.  With None nothing more is launched and the dict is the one described above.
         `min_region` / `region_connectivity` / `region_rounds`: as in `predict` -- the argmax is cleaned on the device
         (`fcn8s_op_regions_clean`) before the counting calls see it: every speck it removes is a closed contour without a match in the
-        ground truth.  With None nothing more is launched and the dict is the same, key for key.'''
+        ground truth.  With None nothing more is launched and the dict is the same, key for key.
+        `panoptic=4` or `8` (needs `instance_level`): panoptic quality as well (panoptic.py; PQ = SQ x RQ, Kirillov et al., CVPR 2019) -- per
+        image one `fcn8s_op_regions_label` and one `fcn8s_op_panoptic_pair` call on the argmax (after any `min_region` cleanup) and the
+        instance map that are already on the device; the `panoptic*` keys of the result.  The predicted things are split into connected
+        components of that connectivity, the naive way to turn a semantic map into instances: touching cars are one segment, so PQ of the
+        things measures the semantic model plus that rule; PQ of the stuff classes and the fp counts -- the specks -- are the figures this
+        is for.  With None nothing more is launched or allocated and the dict is the same, key for key.'''
         from PIL import Image
         import torch
         from . import cityscapes_eval as ce
@@ -698,7 +705,7 @@ class FCN8s:
         walk = ce.walk_predictions(images_dir)
         paths = [ce.find_prediction(images_dir, g, walk, extension=image_file_extension) for g in gts]
         dev = self.engine.device
-        ev = ce.PixelLevelEvaluator(instance_level=instance_level, boundary_radius=boundary_radius)
+        ev = ce.PixelLevelEvaluator(instance_level=instance_level, boundary_radius=boundary_radius, panoptic=panoptic)
         pixels = 0
         kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
         if regions_mod.resolve(min_region, self.num_classes) is not None:

@@ -943,6 +943,42 @@ int fcn8s_op_regions_label(void* stream, const void* labels, int label_kind, int
 int fcn8s_op_regions_clean(void* stream, void* labels, int label_kind, int N, int H, int W, int connectivity,
                            const int32_t* min_area_dev, int rounds, void* work, int64_t* stats_dev);
 int fcn8s_op_regions_status(void* stream, const void* work, int64_t* status_host);
+/* The counting half of panoptic quality (PQ = SQ x RQ: Kirillov et al., CVPR 2019; reported by the Cityscapes benchmark since 2019) for a batch of N
+ * images of H x W pixels on DEVICE pointers: per image the sparse joint table "pixels shared by predicted segment kp and ground-truth segment kg".
+ * All integers.  Train ids are those of labels.py as modified by the reference's author: 0 = void, 1..11 = stuff, 12..19 = things (the labels that
+ * have instances and are evaluated: person .. bicycle).
+ *   Predicted segments, from the argmax a[p] (pred_kind 0: int64 train ids 0..19 as fcn8s_predict writes them; pred_kind 1: uint8 label ids 0..33,
+ *   mapped to train ids first -- labels.py id -> trainId) and pred_comp[p] = comp_out of fcn8s_op_regions_label on the same map (connectivity 4 or 8
+ *   is the caller's choice there):
+ *     a = 0 (void): no segment, kp = 0;  stuff class c: one segment per image, kp = c;
+ *     thing class c: one segment per connected component, kp = 2^31 | comp << 5 | c   (hence H * W <= 2^26).
+ *     A prediction outside 0..19 (a label id outside 0..33) is counted as bad and the pixel is skipped.
+ *   Ground-truth segments, from the instance map alone (uint16, *_gtFine_instanceIds.png), as the official panoptic conversion does.  For the
+ *   value v: L = v if v < 1000 else v / 1000, t = trainId(L).
+ *     t = 0 (void or ignoreInEval): kg = 0;  L > 33: the pixel is counted as bad and skipped;  stuff: kg = t;
+ *     a thing with v >= 1000: kg = 2^31 | (v % 1000) << 5 | t;   a thing with v < 1000 is a crowd region, one per class: kg = 2^30 | t.
+ *   The table of an image holds every distinct (kp, kg) with its pixel count, void on either side included: the counts sum to H * W minus the
+ *   bad pixels.
+ *   rows [N][max_rows][3] int64 = {kp, kg, pixels} of image n, in no particular order (callers sort); counts [N][4] int64, written, not
+ *   accumulated = {rows found -- it may exceed max_rows, then only max_rows rows were written and the call is to be repeated with more room --,
+ *   bad pixels, 1 if the hash table was too small (then the rows are to be discarded and the call repeated with more slots), pixels counted}.
+ *   work: fcn8s_op_panoptic_work_bytes(N, slots_per_image) bytes of 16-byte aligned device scratch = 16 bytes per slot (0 for a slot count that
+ *   is refused); its content on entry does not matter.  slots_per_image: a power of two in 1 .. 2^28; a table of at least 2 H W slots cannot
+ *   be too small.  Any pointer alignment of the three maps (16-byte loads where the address allows, scalar loads otherwise).
+ *   Scores (panoptic.py; float64 on the host, rows in ascending (kp, kg) order, images in file order).  Segment areas are the marginals of the
+ *   table.  A row with kp != 0, kg != 0, kg no crowd region and equal classes has iou = n / (area_p + area_g - n - count(kp, 0)); iou > 0.5 is a
+ *   match: tp[c] += 1, iou_sum[c] += iou.  An unmatched ground-truth segment that is no crowd region: fn[c] += 1.  An unmatched predicted
+ *   segment: fp[c] += 1, unless (count(kp, 0) + count(kp, crowd of c)) / area_p > 0.5.  Per class PQ = iou_sum / (tp + fp / 2 + fn / 2),
+ *   SQ = iou_sum / tp (0 when tp = 0), RQ = tp / (tp + fp / 2 + fn / 2); averages over the classes with tp + fp + fn > 0.
+ *   Connected components are the naive way to turn a semantic map into instances (touching cars are one segment): PQ of the things measures
+ *   the semantic model plus that rule; PQ of the stuff classes and the fp counts are what the table is for.
+ * Only compare-and-swap on a slot's key and integer adds on its count decide anything: two runs give the same set of rows.  No kernel waits
+ * for another block and every probe loop is bounded.  Stream-ordered; does not synchronise; allocates nothing.  FCN8S_ERR_BAD_ARG (nothing
+ * launched) for a NULL pointer, a work that is not 16-byte aligned, pred_kind outside {0, 1}, N, H or W <= 0, max_rows < 1, slots_per_image no
+ * power of two in 1 .. 2^28; FCN8S_ERR_SHAPE for H * W > 2^26 or N > 65535. */
+size_t fcn8s_op_panoptic_work_bytes(int N, int64_t slots_per_image);
+int fcn8s_op_panoptic_pair(void* stream, const uint16_t* gt_instance_ids, const void* pred, int pred_kind, const int32_t* pred_comp, int N, int H, int W,
+                           void* work, int64_t slots_per_image, int64_t* rows, int64_t max_rows, int64_t* counts);
 /* One TF-Adam (step t, 1-based) / SGD-momentum step over n floats on DEVICE pointers, the gradient scaled by grad_scale.  Every pointer may
  * have any float (4-byte) alignment of its own.  These two, their _dev and their _ema forms below run one kernel and give the same bits. */
 int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* m, float* v, int64_t n, int t,
