@@ -409,6 +409,11 @@ void launch_reliability_pair(const float* prob, const uint8_t* gt, const uint8_t
 void launch_temperature_nll(const float* prob, const uint8_t* gt, const uint8_t* lut, int N, long long P, int C, const float* betas, int K,
                             unsigned long long* nll, unsigned long long* count, unsigned long long* bad, hipStream_t s);
 void launch_temperature_apply(const float* prob, int N, long long P, int C, float beta, float* out, float* entropy_out, hipStream_t s);
+// pseudo_label.hip (fcn8s_op_pseudo_label; the definition is in fcn8s_hip.h).  One kernel; hist [C][FCN8S_PL_BINS] (may be null), counts [C][2] and
+// misc [3] are accumulated into.  thresholds, out_ids, base, score and labels_out may be null (not labels_out and hist both).  2 <= C <= 255, P < 2^31.
+void launch_pseudo_label(const float* prob, int N, long long P, int C, const float* thresholds, const uint8_t* out_ids, int ignore_id,
+                         const uint8_t* base, int base_fill, const float* score, float score_max, uint8_t* labels_out,
+                         unsigned long long* hist, unsigned long long* counts, unsigned long long* misc, hipStream_t s);
 // boundary.hip (fcn8s_op_boundary_pair; the definition is in fcn8s_hip.h).  One kernel; rings [R + 1][34][34], bprec / brec [R + 2][34] and bad [1] are
 // accumulated into.  1 <= R <= 16, H * W < 2^31.
 void launch_boundary_pair(const uint8_t* gt, const void* pred, int pred_kind, int N, int H, int W, int R, unsigned long long* rings,

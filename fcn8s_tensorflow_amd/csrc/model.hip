@@ -4569,6 +4569,19 @@ int fcn8s_op_temperature_apply(void* stream, const float* prob, int N, int64_t P
     launch_temperature_apply(prob, N, P, C, beta, out, entropy_out, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
+int fcn8s_op_pseudo_label(void* stream, const float* prob, int N, int64_t P, int C, const float* thresholds, const uint8_t* out_ids, int ignore_id,
+                          const uint8_t* base, int base_fill, const float* score, float score_max, uint8_t* labels_out,
+                          int64_t* hist, int64_t* counts, int64_t* misc)
+{
+    if (!prob || !counts || !misc || (!labels_out && !hist) || N <= 0 || P <= 0 || C < 2 || C > 255 || ignore_id < 0 || ignore_id > 255
+        || base_fill < 0 || base_fill > 255 || (base && !labels_out) || !std::isfinite(score_max))
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "pseudo_label: bad argument (null prob / counts / misc, labels_out and hist both null, N, P <= 0, C outside 2 .. 255, ignore_id or base_fill outside 0 .. 255, base without labels_out, or a score_max that is not finite)");
+    if (P >= (1LL << 31)) return fail(nullptr, FCN8S_ERR_SHAPE, "pseudo_label: an image has to have fewer than 2^31 pixels");
+    take_deferred_error(nullptr);
+    launch_pseudo_label(prob, N, P, C, thresholds, out_ids, ignore_id, base, base_fill, score, score_max, labels_out,
+                        (unsigned long long*)hist, (unsigned long long*)counts, (unsigned long long*)misc, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
 int fcn8s_op_boundary_pair(void* stream, const uint8_t* gt_label_ids, const void* pred, int pred_kind, int N, int H, int W, int R,
                            int64_t* rings, int64_t* bprec, int64_t* brec, int64_t* bad)
 {

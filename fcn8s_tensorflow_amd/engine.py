@@ -1018,6 +1018,18 @@ class Engine:
         q, h = ts.apply_device(dev, temperature, entropy=entropy, out=False if out is False else dev)
         return (None if q is None else q.cpu().numpy()), (None if h is None else h.cpu().numpy())
 
+    def pseudo_label(self, prob, thresholds=None, out_ids=None, ignore_id=255, base=None, base_fill=None, score=None, score_max=None, labels=True,
+                     tables=None):
+        """One `fcn8s_op_pseudo_label` call (pseudo_label.py; the definition is in include/fcn8s_hip.h) on device tensors, on the current
+        stream: `prob` float32 [N,H,W,C] as `predict(argmax=False)`, `predict_tta`, `predict_crf` and `predict_mc` return it (the padded
+        classes already trimmed, as for `reliability_pair`); per class a threshold and the label to write (None: 0 and the class itself);
+        `base` uint8 [N,H,W] labels to complete where they equal `base_fill`; `score` float32 [N,H,W] gated at `score_max`.  Returns
+        (labels uint8 [N,H,W] with `ignore_id` where a pixel is not kept, or None with labels=False; tables), `tables` a dict of the int64
+        device tensors hist [C,1024] (None in it: not kept), counts [C,2], misc [3] that are accumulated into -- None makes zeroed ones."""
+        from . import pseudo_label
+        return pseudo_label.labels_device(prob, thresholds=thresholds, out_ids=out_ids, ignore_id=ignore_id, base=base, base_fill=base_fill,
+                                          score=score, score_max=score_max, labels=labels, tables=tables)
+
     def regions_label(self, labels, connectivity=4, area=True):
         """One `fcn8s_op_regions_label` call (regions.py; the definition is in include/fcn8s_hip.h) on a device tensor of class ids, int64 as
         `predict` returns them or uint8, [H,W] or [N,H,W]: (comp, area | None), int32 device tensors of the same shape -- the id (smallest

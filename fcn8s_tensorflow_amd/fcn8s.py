@@ -50,6 +50,7 @@ except Exception:  # pragma: no cover
 from . import _lib as L
 from . import crf as crf_mod
 from . import temperature as ts_mod
+from . import pseudo_label as pl_mod
 from . import regions as regions_mod
 from . import loss as loss_mod
 from . import optim as optim_mod
@@ -108,6 +109,7 @@ class FCN8s:
         self.best_training_loss = 99999999.9
         self.g_step = None
         self.temperature = None          # set by fit_temperature (or restored from a saved model); `predict(temperature=...)` takes it
+        self.pseudo_label_thresholds = None   # set by fit_pseudo_label_thresholds; they belong to a dataset and are not saved with the model
 
         if device_id is None:
             device_id = int(os.environ.get("LOCAL_RANK", "0"))
@@ -902,6 +904,166 @@ class FCN8s:
         self.temperature = res["temperature"]
         if json_path is not None:
             ts_mod.write_result_json(res, json_path)
+        return res
+
+    def _pseudo_label_route(self, scales, flip, crf, temperature, samples, keep_prob, mi_max):
+        '''The prediction route of the two pseudo-label sweeps, with `evaluate_reliability`'s refusals: (name, predict) where
+        `predict(image)` takes a uint8 device tensor (1,H,W,3) and returns (softmax on the device, score map | None).'''
+        if temperature is not None:
+            temperature = ts_mod.validate_temperature(temperature)
+        passes = scales is not None or bool(flip) or crf_mod.resolve(crf) is not None
+        pl_mod.validate(self.num_classes, samples=samples, mi_max=mi_max, temperature=temperature, passes=passes)
+        kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
+        if samples is not None:
+            def predict(image):
+                prob, _, mi = self.engine.predict_mc(image, samples=samples, keep_prob=keep_prob, sample_offset=0, argmax=False, entropy=False,
+                                                     mutual_information=mi_max is not None)
+                return prob, mi
+            return 'mc', predict
+        if passes:
+            return 'passes', lambda image: (self.predict(image, argmax=False, scales=scales, flip=flip, temperature=temperature, **kw), None)
+
+        def single(image):              # as in evaluate_reliability: one sample without dropout is `predict` bit for bit, on images of any size
+            prob = self.engine.predict_mc(image, samples=1, keep_prob=1.0, sample_offset=0, argmax=False, entropy=False, mutual_information=False)[0]
+            if temperature is not None and temperature != 1.0:
+                self.engine.temperature_apply(prob, temperature, out=prob)
+            return prob, None
+        return 'single', single
+
+    def fit_pseudo_label_thresholds(self, images_dir, portion=0.2, t_min=0.0, t_max=None, scales=None, flip=False, crf=None, temperature=None,
+                                    samples=None, keep_prob=0.5, mi_max=None, resize=False, image_file_extension='png', json_path=None):
+        '''Not in the reference: the first sweep of class-balanced self-training (CBST, Zou et al., ECCV 2018; pseudo_label.py) -- one
+        confidence threshold per class for pseudo-labelling the unlabelled (or coarsely labelled) images below `images_dir`, set where
+        `portion` (a value in (0, 1], or one per class) of the pixels predicted as that class lies above it.  One global threshold gives
+        every kept pixel to road, sky and building; a threshold per class keeps the same share of pole, rider and bicycle.
+        Walks every `*.<ext>` below `images_dir` as `predict_and_export_label_ids` does; per image: decode, one upload, the prediction on the
+        device with `argmax=False`, one `fcn8s_op_pseudo_label` call without labels that adds the maximum softmax probability of every pixel
+        to its predicted class's histogram of 1024 bins.  The softmax never visits the host; the tables are downloaded once at the end.
+        Routes and refusals as in `evaluate_reliability`: `samples=S` is the Monte-Carlo dropout mean at `keep_prob`, and `mi_max` then
+        keeps out of the histograms the pixels whose mutual information exceeds it; otherwise `scales` / `flip` / `crf` / `temperature` as
+        in `predict`.  `temperature` or `scales` / `flip` / `crf` together with `samples` raise ValueError.  `resize=(h, w)` feeds the
+        network resized images.  Thresholds are bin edges j / 1024 clamped to [t_min, t_max] (`pseudo_label.thresholds_from_hist`), so that
+        the export sweep keeps exactly the histogram's tail.  Returns dict(thresholds float32[C], bins int64[C], hist, counts, misc, summary,
+        nbImages, route) and keeps the thresholds in `self.pseudo_label_thresholds`; they belong to this directory, not to the model:
+        `save` does not store them.  `json_path`: also write the result.  Works inside `averaged_weights()`.'''
+        from PIL import Image
+        import torch
+        pl_mod.validate(self.num_classes, portion=portion, t_min=t_min, t_max=t_max)
+        route, predict = self._pseudo_label_route(scales, flip, crf, temperature, samples, keep_prob, mi_max)
+        paths = sorted(glob(os.path.join(images_dir, '**', '*.' + image_file_extension), recursive=True))
+        if not paths:
+            raise ValueError("Cannot find any images below: {}".format(images_dir))
+        dev = self.engine.device
+        tables = None
+        tr = trange(len(paths), file=sys.stdout)
+        tr.set_description('Fitting pseudo-label thresholds')
+        was_frozen = bool(self.engine.get_option("frozen"))
+        self.engine.freeze(True)
+        try:
+            for i in tr:
+                pil = Image.open(paths[i]).convert('RGB')
+                if resize and not np.array_equal((pil.height, pil.width), resize):
+                    pil = pil.resize((resize[1], resize[0]), Image.BILINEAR)
+                prob, score = predict(torch.from_numpy(np.array(pil)[None]).to(dev))
+                _, tables = self.engine.pseudo_label(prob, score=score, score_max=mi_max if score is not None else None, labels=False, tables=tables)
+        finally:
+            self.engine.freeze(was_frozen)
+        host = pl_mod.tables_to_host(tables, self.num_classes)
+        thr, bins = pl_mod.thresholds_from_hist(host["hist"], portion, t_min=t_min, t_max=t_max)
+        kept = pl_mod.tail_sums(host["hist"], bins)                     # what the export sweep keeps at these thresholds
+        expected = np.stack([kept, host["counts"].sum(1) - kept], 1)
+        res = dict(thresholds=thr, bins=bins, hist=host["hist"], counts=host["counts"], misc=host["misc"],
+                   summary=pl_mod.summary(host["hist"], expected, host["misc"], thr), nbImages=len(paths), route=route)
+        self.pseudo_label_thresholds = thr
+        if json_path is not None:
+            pl_mod.write_result_json(res, json_path)
+        return res
+
+    def predict_and_export_pseudo_labels(self, results_dir, images_dir, thresholds=None, ignore_id=255, id_space='train', base_search=None,
+                                         base_fill=None, scales=None, flip=False, crf=None, temperature=None, samples=None, keep_prob=0.5,
+                                         mi_max=None, resize=False, image_file_extension='png', overwrite_existing=True, json_path=None):
+        '''Not in the reference: the second sweep of class-balanced self-training -- pseudo-label maps for every `*.<ext>` below `images_dir`,
+        written as single-channel PNGs under the images' basenames into `results_dir`: the predicted class where its maximum softmax
+        probability clears the class's threshold, `ignore_id` elsewhere.  A later `train()` reads them through the ordinary `BatchGenerator`;
+        the loss ignores label ids >= num_classes, so no teacher is on the device and nothing changes in the step.
+        `thresholds`: one per class; None takes `self.pseudo_label_thresholds` (`fit_pseudo_label_thresholds`) and raises when there are
+        none.  `id_space='train'` writes train ids; 'label' writes Cityscapes label ids through `cityscapes_eval.TRAINIDS_TO_IDS_ARRAY`
+        (20-class models only) -- `ignore_id` must then be an id that the `convert_ids_to_ids` table given to the `BatchGenerator` sends to a
+        value >= num_classes, as it is written as it is.  `base_search` / `base_fill`: a glob of existing label maps (a coarse annotation)
+        to complete; a map belongs to the image of the same `<city>_<seq>_<frame>` -- `evaluate_cityscapes`' naming rule in the other
+        direction, its basename is `<city>_<seq>_<frame>_*` -- and a missing or a second partner raises ValueError.  Each map is uploaded;
+        its pixels that differ from `base_fill` are written as they are, and only the others are predicted.  It has to have the size of the
+        prediction, so `resize` with it raises.  Routes as in `fit_pseudo_label_thresholds`; with `samples` and `mi_max`, pixels whose mutual
+        information exceeds `mi_max` are ignored.  Per image: decode, one upload, the prediction with `argmax=False` on the device, one
+        `fcn8s_op_pseudo_label` call, and the download of the label map -- 1 byte per pixel, not the 4 C of the softmax.  `resize=(h, w)`
+        behaves as in `predict_and_export_label_ids`: the labels come back to the file's size by PIL's nearest neighbour.  Returns
+        `pseudo_label.summary` of the whole sweep plus 'thresholds', 'images' (per file: kept, dropped, badRows, passedThrough,
+        droppedByScore), 'nbImages' and 'route'; `json_path`: also write it.
+        Not done here: filling labels on the fly inside `train(teacher=...)`, iterating rounds with a growing portion (the caller loops over
+        fit, export and train), spatial priors (CBST-SP), and any change to `BatchGenerator`.'''
+        from PIL import Image
+        import torch
+        from . import cityscapes_eval as ce
+        if thresholds is None:
+            thresholds = self.pseudo_label_thresholds
+            if thresholds is None:
+                raise ValueError("no thresholds: pass `thresholds` or run `fit_pseudo_label_thresholds` first.")
+        v = pl_mod.validate(self.num_classes, thresholds=thresholds, ignore_id=ignore_id, id_space=id_space, base_search=base_search, base_fill=base_fill,
+                            resize=resize)
+        route, predict = self._pseudo_label_route(scales, flip, crf, temperature, samples, keep_prob, mi_max)
+        paths = sorted(glob(os.path.join(images_dir, '**', '*.' + image_file_extension), recursive=True))
+        if not paths:
+            raise ValueError("Cannot find any images below: {}".format(images_dir))
+        bases = None
+        if base_search is not None:
+            found = sorted(glob(base_search))
+            bases = [pl_mod.find_base(p, found) for p in paths]
+        if overwrite_existing and os.path.exists(results_dir):
+            shutil.rmtree(results_dir)
+        os.makedirs(results_dir, exist_ok=True)
+        dev = self.engine.device
+        Cn = self.num_classes
+        thr = torch.from_numpy(v["thresholds"]).to(dev)
+        oid = torch.from_numpy(ce.TRAINIDS_TO_IDS_ARRAY.astype(np.uint8)).to(dev) if id_space == 'label' else None
+        flat = torch.zeros(2 * Cn + 3, dtype=torch.int64, device=dev)           # counts and misc in one piece: one small download per image
+        tables = dict(hist=None, counts=flat[:2 * Cn].view(Cn, 2), misc=flat[2 * Cn:])
+        seen = np.zeros(2 * Cn + 3, np.int64)
+        images = []
+        tr = trange(len(paths), file=sys.stdout)
+        tr.set_description('Exporting pseudo-labels')
+        was_frozen = bool(self.engine.get_option("frozen"))
+        self.engine.freeze(True)
+        try:
+            for i in tr:
+                pil = Image.open(paths[i]).convert('RGB')
+                size = pil.size
+                if resize and not np.array_equal((pil.height, pil.width), resize):
+                    pil = pil.resize((resize[1], resize[0]), Image.BILINEAR)
+                prob, score = predict(torch.from_numpy(np.array(pil)[None]).to(dev))
+                base = None
+                if bases is not None:
+                    bm = np.array(Image.open(bases[i]))
+                    if bm.ndim != 2 or bm.dtype != np.uint8:
+                        raise ValueError("The base label map " + bases[i] + " is not a single-channel 8-bit image.")
+                    if bm.shape != tuple(prob.shape[1:3]):
+                        raise ValueError("Image sizes of " + paths[i] + " and " + bases[i] + " are not equal.")
+                    base = torch.from_numpy(bm[None]).to(dev)
+                labels, _ = self.engine.pseudo_label(prob, thresholds=thr, out_ids=oid, ignore_id=v["ignore_id"], base=base, base_fill=v["base_fill"],
+                                                     score=score, score_max=mi_max if score is not None else None, labels=True, tables=tables)
+                out = Image.fromarray(labels[0].cpu().numpy())
+                now = flat.cpu().numpy()
+                d, seen = now - seen, now
+                images.append(dict(file=os.path.basename(paths[i]), kept=int(d[0:2 * Cn:2].sum()), dropped=int(d[1:2 * Cn:2].sum()),
+                                   badRows=int(d[2 * Cn]), passedThrough=int(d[2 * Cn + 1]), droppedByScore=int(d[2 * Cn + 2])))
+                if out.size != size:
+                    out = out.resize(size, Image.NEAREST)
+                out.save(os.path.join(results_dir, os.path.basename(paths[i])))
+        finally:
+            self.engine.freeze(was_frozen)
+        res = pl_mod.summary(None, seen[:2 * Cn].reshape(Cn, 2), seen[2 * Cn:], v["thresholds"])
+        res.update(thresholds=v["thresholds"], images=images, nbImages=len(paths), route=route)
+        if json_path is not None:
+            pl_mod.write_result_json(res, json_path)
         return res
 
     def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement, scales=None, flip=False, crf=None,

@@ -880,6 +880,38 @@ int fcn8s_op_reliability_pair(void* stream, const float* prob, const uint8_t* gt
 int fcn8s_op_temperature_nll(void* stream, const float* prob, const uint8_t* gt, const uint8_t* lut, int N, int64_t P, int C,
                              const float* betas, int K, int64_t* nll, int64_t* count, int64_t* bad);
 int fcn8s_op_temperature_apply(void* stream, const float* prob, int N, int64_t P, int C, float beta, float* out, float* entropy_out);
+/* Class-balanced pseudo-labels (self-training on hard labels with one confidence threshold per class: CBST, Zou et al., ECCV 2018) from a softmax,
+ * for a batch of N images of P pixels each on DEVICE pointers, in one pass that reads every input byte once.  Two uses: the fit sweep
+ * (labels_out NULL) fills, per predicted class, a histogram of the maximum softmax probability, from which the host takes the thresholds
+ * (pseudo_label.py); the export sweep writes label maps that hold the class where it clears its threshold and ignore_id elsewhere.
+ *   prob [N,P,C] float32, as fcn8s_predict (argmax = 0), fcn8s_predict_tta, fcn8s_predict_crf and fcn8s_predict_mc write it; any 2 <= C <= 255 and
+ *   any float alignment (16-byte loads are used when the pointer is 16-byte aligned and C % 4 == 0).  thresholds: float32[C], may be NULL: every
+ *   threshold is 0.  out_ids: uint8[C], the label written for class k, may be NULL: k itself.  ignore_id (0..255): written where a pixel is not
+ *   kept.  base [N,P] uint8 or NULL: existing labels, with base_fill (0..255) marking the pixels to fill.  score [N,P] float32 or NULL: an
+ *   uncertainty map, gated at score_max (finite).  labels_out [N,P] uint8, any alignment; may be NULL: tables only.
+ *   Tables, all int64, accumulated into, over the N images and over calls (the caller clears them): hist [C][M], M = FCN8S_PL_BINS (may be
+ *   NULL); counts [C][2] = {kept, dropped}; misc [3] = {bad rows, passed-through base pixels, dropped by score}.
+ *   Per pixel p, in this order, in fp32, nothing contracted:
+ *     1. base given and base[p] != base_fill: labels_out[p] = base[p], misc[1] += 1, and nothing else (the row is not examined).
+ *     2. k = argmax_c p_c (the lowest index on ties; c replaces the running maximum only if p_c > it, so a NaN at c > 0 never wins), conf = p_k.
+ *        conf NaN or +-inf: misc[0] += 1, the label is ignore_id, and nothing else.
+ *     3. score given and not (score[p] <= score_max) (a NaN score fails): misc[2] += 1, counts[k][1] += 1, the label is ignore_id; the pixel
+ *        does not enter hist.
+ *     4. b = conf > 0 ? min(M - 1, (int)(conf * (float)M)) : 0;  hist[k][b] += 1.
+ *     5. conf >= thresholds[k]: the label is out_ids[k] and counts[k][0] += 1; otherwise the label is ignore_id and counts[k][1] += 1.
+ *   M is a power of two, so conf * M is exact, and for a threshold on a bin edge j / M: conf >= j / M <=> b >= j for every conf in [0, 1).  With
+ *   edge thresholds the kept count of class k in a second sweep therefore equals the tail sum of hist[k][j ..] of the first, exactly.
+ *   Integers only decide the tables: two runs give the same bits, and so does any partition of the pixels over calls.  Stream-ordered; does not
+ *   synchronise; allocates nothing; needs no scratch.  FCN8S_ERR_BAD_ARG (nothing launched) for a NULL prob / counts / misc, labels_out and hist
+ *   both NULL, N or P <= 0, C outside 2..255, ignore_id or base_fill outside 0..255, base without labels_out, a score_max that is not finite;
+ *   FCN8S_ERR_SHAPE for P >= 2^31.
+ *   The kernel takes FCN8S_PL_TILE_PIXELS pixels per block and trip on at most FCN8S_PL_MAX_BLOCKS blocks (more only beyond 2^40 pixels). */
+#define FCN8S_PL_BINS 1024
+#define FCN8S_PL_TILE_PIXELS 256
+#define FCN8S_PL_MAX_BLOCKS 512
+int fcn8s_op_pseudo_label(void* stream, const float* prob, int N, int64_t P, int C, const float* thresholds, const uint8_t* out_ids, int ignore_id,
+                          const uint8_t* base, int base_fill, const float* score, float score_max, uint8_t* labels_out,
+                          int64_t* hist, int64_t* counts, int64_t* misc);
 /* Boundary measures of a segmentation against its ground truth -- the counting half of the trimap IoU (accuracy inside a band of width r around
  * the ground-truth boundaries: Kraehenbuehl & Koltun 2011, Chen et al. 2015) and of the boundary F-score (Csurka et al., BMVC 2013) -- for a batch
  * of N images of H x W pixels on DEVICE pointers.  All integers.
