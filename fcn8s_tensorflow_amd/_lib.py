@@ -172,6 +172,8 @@ SIGNATURES = {
     "fcn8s_op_regions_status": (_i, [_p, _p, _i64p]),
     "fcn8s_op_panoptic_work_bytes": (_sz, [_i, _i64]),
     "fcn8s_op_panoptic_pair": (_i, [_p, _p, _p, _i, _p, _i, _i, _i, _p, _i64, _p, _i64, _p]),
+    "fcn8s_op_instance_work_bytes": (_sz, [_i, _i64]),
+    "fcn8s_op_instance_pair": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _i64, _p, _i64, _p]),
     "fcn8s_op_tf_adam": (_i, [_p, _p, _p, _p, _p, _i64, _i, _f, _f, _f, _f, _f]),
     "fcn8s_op_sgd_momentum": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f]),
     "fcn8s_op_grad_accumulate": (_i, [_p, _p, _p, _i64, _i]),

@@ -435,6 +435,13 @@ bool regions_status(const void* work, long long* status2, hipStream_t s);
 size_t panoptic_work_bytes(int N, long long slots);
 void launch_panoptic_pair(const uint16_t* inst, const void* pred, int pred_kind, const int* comp, int N, int H, int W, void* work, long long slots,
                           long long* rows, long long max_rows, unsigned long long* counts, hipStream_t s);
+// instances.hip (fcn8s_op_instance_pair; the definition is in fcn8s_hip.h).  Clear, count, compact: rows [N][max_rows][4] = {kp, v, pixels, sum of
+// terms} in no particular order, counts [N][5] = {rows found, labels >= 20, table too small, pixels counted, q out of range}.  inst may be null.
+// C >= 20, H * W <= 2^26, N <= 65535, slots a power of two in 1 .. 2^28, work: instance_work_bytes(N, slots) bytes (0 for slots it refuses),
+// 16-byte aligned.
+size_t instance_work_bytes(int N, long long slots);
+void launch_instance_pair(const float* prob, int C, const uint8_t* labels, const int* comp, const uint16_t* inst, int N, int H, int W, void* work,
+                          long long slots, long long* rows, long long max_rows, unsigned long long* counts, hipStream_t s);
 // wrapping sum over every 61st element's bit pattern (weighted by position): changes whenever an optimizer step or a bulk copy touches the buffer
 void launch_fingerprint(const float* x, long long n, unsigned long long* out, hipStream_t s);
 void launch_init_normal(float* w, long long n, float stddev, int truncated, unsigned long long seed,

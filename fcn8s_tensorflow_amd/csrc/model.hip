@@ -4649,6 +4649,20 @@ int fcn8s_op_panoptic_pair(void* stream, const uint16_t* gt_instance_ids, const 
                          (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
+size_t fcn8s_op_instance_work_bytes(int N, int64_t slots_per_image) { return instance_work_bytes(N, slots_per_image); }
+int fcn8s_op_instance_pair(void* stream, const float* prob, int C, const uint8_t* labels, const int32_t* comp, const uint16_t* gt_instance_ids, int N, int H, int W,
+                           void* work, int64_t slots_per_image, int64_t* rows, int64_t max_rows, int64_t* counts)
+{
+    if (!prob || !labels || !comp || !work || (uintptr_t)work % 16 || (uintptr_t)prob % 4 || !rows || !counts || C < 20 || N <= 0 || H <= 0 || W <= 0
+        || max_rows < 1 || instance_work_bytes(N > 0 ? N : 1, slots_per_image) == 0)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "instance_pair: bad argument (null pointer, work not 16-byte aligned, C < 20, N, H, W <= 0, max_rows < 1, or slots_per_image no power of two in 1 .. 2^28)");
+    if ((long long)H * W > (1LL << 26) || N > 65535 || (long long)C * 4 > (1LL << 20))
+        return fail(nullptr, FCN8S_ERR_SHAPE, "instance_pair: an image has to have at most 2^26 pixels (26-bit component ids), a batch at most 65535 images and a row at most 2^18 classes");
+    take_deferred_error(nullptr);
+    launch_instance_pair(prob, C, labels, comp, gt_instance_ids, N, H, W, work, slots_per_image, (long long*)rows, max_rows, (unsigned long long*)counts,
+                         (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
 // the six op-level forms of the update: host scale or the slab's (out5 + 2: s, out5 + 3: ok), with or without a shadow
 static int op_update(void* stream, int opt, float* theta, const float* g, float* m, float* v, float* shadow, int64_t n,
                      float p0, float p1, float p2, float p3, float gs, const float* out5, float w)

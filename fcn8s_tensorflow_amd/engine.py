@@ -1058,6 +1058,18 @@ class Engine:
         rows, bad, self._panoptic_work = panoptic.pair_rows_device(pred, inst, connectivity=connectivity, work=getattr(self, "_panoptic_work", None))
         return rows, bad
 
+    def instance_pair(self, prob, labels, comp, inst=None):
+        """The instance pair table of instance-level AP (instances.py; the definition is in include/fcn8s_hip.h) of device tensors: `prob`
+        float32 [N,H,W,C] (or [H,W,C]) as `predict(argmax=False)` and its siblings return it, `labels` uint8 train ids [N,H,W] -- the class
+        every pixel ended up with --, `comp` int32, `regions_label` of that map, and the uint16 instance map `inst` (a 16-bit device tensor,
+        a NumPy map, or None: no ground truth, the export route): one `fcn8s_op_instance_pair` call.  Returns (list of int64 rows (kp, v,
+        pixels, sum of confidence terms) per image in ascending order, int64 array [N, 2] of pixels with a label >= 20 and with a
+        probability outside [0, 1]).  The scratch is kept on the engine and regrown only when a larger one is needed; a hash table or a
+        row buffer that the op reports as too small is doubled and the call repeated."""
+        from . import instances
+        rows, bad, self._instance_work = instances.pair_rows_device(prob, labels, comp, inst, work=getattr(self, "_instance_work", None))
+        return rows, bad
+
     # ---- introspection (tests, bench) -----------------------------------------------------------
     def activation(self, name, shape, missing_ok=False):
         """fcn8s_get_activation.  A conv whose output transform was fused with the next conv's input transform (option `fuse_out_in`)

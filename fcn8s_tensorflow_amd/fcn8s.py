@@ -1066,6 +1066,127 @@ class FCN8s:
             pl_mod.write_result_json(res, json_path)
         return res
 
+    def _instance_route(self, connectivity, min_instance_pixels, samples, keep_prob, scales, flip, crf, temperature, min_region, region_connectivity,
+                        region_rounds):
+        '''The device path of the two instance-level sweeps: `table(image, inst)` takes a uint8 device tensor (1,H,W,3) and the image's
+        instance map (NumPy, or None) and returns (softmax, uint8 labels, int32 components, rows, bad) -- everything but the rows on the
+        device.  Routes and refusals are those of `evaluate_reliability`.'''
+        if self.num_classes != 20:
+            raise ValueError("the Cityscapes evaluation uses the 20 Cityscapes train ids; this model has {} classes.".format(self.num_classes))
+        regions_mod._check(connectivity)
+        if isinstance(min_instance_pixels, bool) or not isinstance(min_instance_pixels, (int, np.integer)) or min_instance_pixels < 0:
+            raise ValueError("`min_instance_pixels` is a non-negative integer, not {!r}".format(min_instance_pixels))
+        clean = regions_mod.resolve(min_region, self.num_classes)
+        if clean is not None:
+            regions_mod._check(region_connectivity, region_rounds)
+        route, predict = self._pseudo_label_route(scales, flip, crf, temperature, samples, keep_prob, None)
+
+        def table(image, inst):
+            prob, _score = predict(image)
+            labels, _t = self.engine.pseudo_label(prob, labels=True)            # zero thresholds, the identity table: the argmax as uint8
+            if clean is not None:
+                self.engine.regions_clean(labels, clean, connectivity=region_connectivity, rounds=region_rounds)
+            comp, _area = self.engine.regions_label(labels, connectivity=connectivity, area=False)
+            rows, bad = self.engine.instance_pair(prob, labels, comp, inst)
+            return prob, labels, comp, rows, bad
+        return route, table
+
+    def evaluate_cityscapes_instances(self, images_dir, ground_truth_search, connectivity=4, min_instance_pixels=0, samples=None, keep_prob=0.5,
+                                      scales=None, flip=False, crf=None, temperature=None, min_region=None, region_connectivity=4, region_rounds=1,
+                                      image_file_extension='png', json_path=None):
+        '''Not in the reference's model code: the official Cityscapes instance-level table (AP over the overlaps 0.5 .. 0.95 and AP50%, per
+        thing class and on average; instances.py has the definition) of this model in one call, scored where the predictions already are.
+        The predicted instances are the connected components (`connectivity` 4 or 8) of the thing classes of the argmax, and the confidence
+        of an instance is the mean probability of the assigned class over its pixels -- so a calibrated `temperature`, the Monte-Carlo mean
+        (`samples`, `keep_prob`), `scales` / `flip` averaging and the `crf`, which IoU and PQ cannot see where they do not move the argmax,
+        show up here as a ranking of segments, and `min_region` cleanup as fewer of them.
+        Every ground-truth file of the glob `ground_truth_search` (the official one is `<cityscapes>/gtFine/val/*/*_gtFine_instanceIds.png`)
+        is paired with its image `<city>_<seq>_<frame>*.<ext>` below `images_dir` as in `evaluate_cityscapes`; per image: decode, one upload,
+        the softmax on the device through `evaluate_reliability`'s routes (and its refusals), one `fcn8s_op_pseudo_label` call for the uint8
+        argmax, an optional `fcn8s_op_regions_clean`, one `fcn8s_op_regions_label` and one `fcn8s_op_instance_pair` call against the uploaded
+        instance map.  The softmax never visits the host; a few hundred table rows per image do.  `min_instance_pixels`: predicted instances
+        of fewer pixels are dropped on the host before the matching.  Returns `instances.results(...)` plus 'nbPixels', 'route' and
+        'connectivity'; `json_path`: also write it in the layout of resultInstanceLevelSemanticLabeling.json.  Works inside
+        `averaged_weights()`.
+        Caveat: connected components merge touching cars, so this AP measures the semantic model plus that rule -- a baseline and a speck
+        detector, not an instance-segmentation method.'''
+        from PIL import Image
+        import torch
+        from . import cityscapes_eval as ce, instances as ins
+        route, table = self._instance_route(connectivity, min_instance_pixels, samples, keep_prob, scales, flip, crf, temperature, min_region,
+                                            region_connectivity, region_rounds)
+        gts = sorted(glob(ground_truth_search))
+        if not gts:
+            raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
+        walk = ce.walk_predictions(images_dir)
+        paths = [ce.find_prediction(images_dir, g, walk, extension=image_file_extension) for g in gts]
+        dev = self.engine.device
+        stats = ins.new_stats()
+        pixels = 0
+        tr = trange(len(gts), file=sys.stdout)
+        tr.set_description('Evaluating')
+        was_frozen = bool(self.engine.get_option("frozen"))
+        self.engine.freeze(True)
+        try:
+            for i in tr:
+                image = torch.from_numpy(np.array(Image.open(paths[i]).convert('RGB'))[None]).to(dev)
+                inst = np.array(Image.open(gts[i]))
+                if inst.ndim != 2 or inst.shape != tuple(image.shape[1:3]):
+                    raise ValueError("Image sizes of " + paths[i] + " and " + gts[i] + " are not equal.")
+                _prob, _labels, _comp, rows, bad = table(image, inst[None])
+                if bad.any():
+                    raise ValueError("{}: {} pixels hold a label outside 0..19 and {} a probability outside [0, 1]".format(paths[i], int(bad[0, 0]), int(bad[0, 1])))
+                ins.stats_add(stats, rows[0], min_instance_pixels)
+                pixels += inst.size
+        finally:
+            self.engine.freeze(was_frozen)
+        res = ins.results(stats)
+        res["nbPixels"] = pixels
+        res["route"] = route
+        res["connectivity"] = int(connectivity)
+        if json_path is not None:
+            ins.write_result_json(res, json_path)
+        return res
+
+    def predict_and_export_instances(self, results_dir, images_dir, connectivity=4, min_instance_pixels=0, samples=None, keep_prob=0.5, scales=None,
+                                     flip=False, crf=None, temperature=None, min_region=None, region_connectivity=4, region_rounds=1,
+                                     image_file_extension='png', overwrite_existing=True):
+        '''Not in the reference's model code: the predictions of `evaluate_cityscapes_instances` for every `*.<ext>` below `images_dir`,
+        written into `results_dir` in the official instance-level result format (`instances.write_export`): per image `<basename>.txt` with
+        one line `<relative mask path> <label id> <confidence>` per instance and one binary mask PNG per instance.  The same device path
+        without ground truth; the component map (4 bytes per pixel) and the table rows are downloaded, the softmax is not.
+        `instances.evaluate_directory` on this export gives the dict of `evaluate_cityscapes_instances` with the same arguments.  Returns
+        dict(files = the text files in image order, nbImages, nbInstances, route).'''
+        from PIL import Image
+        import torch
+        from . import instances as ins
+        route, table = self._instance_route(connectivity, min_instance_pixels, samples, keep_prob, scales, flip, crf, temperature, min_region,
+                                            region_connectivity, region_rounds)
+        paths = sorted(glob(os.path.join(images_dir, '**', '*.' + image_file_extension), recursive=True))
+        if not paths:
+            raise ValueError("Cannot find any images below: {}".format(images_dir))
+        if overwrite_existing and os.path.exists(results_dir):
+            shutil.rmtree(results_dir)
+        os.makedirs(results_dir, exist_ok=True)
+        dev = self.engine.device
+        files, count = [], 0
+        tr = trange(len(paths), file=sys.stdout)
+        tr.set_description('Exporting instances')
+        was_frozen = bool(self.engine.get_option("frozen"))
+        self.engine.freeze(True)
+        try:
+            for i in tr:
+                image = torch.from_numpy(np.array(Image.open(paths[i]).convert('RGB'))[None]).to(dev)
+                _prob, _labels, comp, rows, bad = table(image, None)
+                if bad.any():
+                    raise ValueError("{}: {} pixels hold a label outside 0..19 and {} a probability outside [0, 1]".format(paths[i], int(bad[0, 0]), int(bad[0, 1])))
+                files.append(ins.write_export(results_dir, os.path.splitext(os.path.basename(paths[i]))[0], comp[0].cpu().numpy(), rows[0], min_instance_pixels))
+                with open(files[-1]) as f:
+                    count += sum(1 for _line in f)
+        finally:
+            self.engine.freeze(was_frozen)
+        return dict(files=files, nbImages=len(paths), nbInstances=count, route=route)
+
     def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement, scales=None, flip=False, crf=None,
                       regions=None):
         '''Loop body of predict_and_save (fcn8s_tensorflow.py:829-855).'''

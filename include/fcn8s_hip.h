@@ -1011,6 +1011,48 @@ int fcn8s_op_regions_status(void* stream, const void* work, int64_t* status_host
 size_t fcn8s_op_panoptic_work_bytes(int N, int64_t slots_per_image);
 int fcn8s_op_panoptic_pair(void* stream, const uint16_t* gt_instance_ids, const void* pred, int pred_kind, const int32_t* pred_comp, int N, int H, int W,
                            void* work, int64_t slots_per_image, int64_t* rows, int64_t max_rows, int64_t* counts);
+/* The counting half of instance-level AP (the Cityscapes instance-level evaluation: AP over the overlaps 0.5 .. 0.95 and AP50% per thing class) for
+ * a batch of N images of H x W pixels on DEVICE pointers: per image the sparse joint table "pixels shared by predicted instance kp and ground-truth
+ * instance value v", with the summed confidence of those pixels.  Train ids as above: 0 = void, 1..11 = stuff, 12..19 = things.  C >= 20.
+ *   Inputs per pixel p: labels[p], a uint8 train id -- the class the pixel ended up with: the argmax of the softmax, possibly after
+ *   fcn8s_op_regions_clean; comp[p] = comp_out of fcn8s_op_regions_label on that same map; prob [N,H*W,C] float32 as fcn8s_predict (argmax = 0)
+ *   and its siblings write it; v[p] = gt_instance_ids[p] (uint16, *_gtFine_instanceIds.png), 0 when the pointer is NULL (the export route).
+ *   Predicted key.  labels[p] in 12..19: kp = 2^31 | comp << 5 | labels[p], the thing key of fcn8s_op_panoptic_pair (hence H * W <= 2^26).  Otherwise
+ *   kp = 0, "no instance"; a label >= 20 also gives kp = 0 and is counted as bad.
+ *   Ground-truth key.  The raw value v and nothing else -- not fcn8s_op_panoptic_pair's kg, which sends every ignoreInEval label to 0: the
+ *   instance-level evaluation does not (a caravan instance 29001 is neither void nor a match; only values that equal an ignored label id,
+ *   v < 1000, are void).  The raw value lets the host apply those rules exactly.
+ *   Confidence.  Where kp != 0: q = prob[p][labels[p]], the probability of the assigned class (which also holds after a cleanup), and the term
+ *   t = (int64)rintf(q * 2^24), the fixed point of fcn8s_op_reliability_pair.  A q that is not in [0, 1] (NaN fails the test) gives t = 0 and is
+ *   counted.  Where kp = 0 the row is not examined and t = 0.
+ *   The table of an image holds every distinct (kp, v), kp = 0 included, with n = its pixel count and s = the sum of its terms: the counts sum
+ *   to H * W.  n <= 2^26 and t <= 2^24, so s < 2^51.
+ *   rows [N][max_rows][4] int64 = {kp, v, n, s} of image n, in no particular order (callers sort); counts [N][5] int64, written, not accumulated
+ *   = {rows found -- it may exceed max_rows, then only max_rows rows were written and the call is to be repeated with more room --, pixels with a
+ *   label >= 20, 1 if the hash table was too small (then the rows are to be discarded and the call repeated with more slots), pixels counted,
+ *   pixels with q out of range}.
+ *   work: fcn8s_op_instance_work_bytes(N, slots_per_image) bytes of 16-byte aligned device scratch = 32 bytes per slot (0 for a slot count that
+ *   is refused); its content on entry does not matter.  slots_per_image: a power of two in 1 .. 2^28; a table of at least 2 H W slots cannot
+ *   be too small.  Any byte alignment of the three maps and any float alignment of prob (16-byte loads of the rows when prob is 16-byte
+ *   aligned and C % 4 == 0, 4-byte loads otherwise).
+ *   Host half (instances.py; float64).  Area of a predicted instance = sum_v n; confidence = sum_v s / (area * 2^24); void intersection = sum of
+ *   n over the void v (v < 1000 whose label is ignored in the evaluation); intersection with a ground-truth instance = n(kp, v) for the v
+ *   whose label (v if v < 1000, else v / 1000) is the instance's class; ground-truth pixel count of v = sum_kp n (which is why kp = 0 is in the
+ *   table); v / 1000 > 33 is refused for the image.  Then the matching and the curve of the Cityscapes instance-level evaluation: overlaps
+ *   0.5 .. 0.95 in steps of 0.05; ground-truth regions below 100 pixels and group regions (v < 1000 of the class) are ignore regions; a prediction
+ *   without a match is dropped when its ignored share exceeds the overlap threshold; hard false negatives are counted; AP is the step-wise
+ *   integral of the precision-recall curve; averages are NaN-skipping means over the classes.  The distance-based variants are not taken.
+ *   Connected components are the naive way to turn a semantic map into instances (touching cars are one instance): AP under this rule measures
+ *   the semantic model plus that rule -- a baseline and a speck detector, not an instance-segmentation method.
+ * Only compare-and-swap on a slot's key and integer adds on its count and sum decide anything: two runs give the same set of rows.  No kernel
+ * waits for another block and every probe loop is bounded.  Stream-ordered; does not synchronise; allocates nothing.  FCN8S_ERR_BAD_ARG (nothing
+ * launched, outputs untouched) for a NULL prob / labels / comp / work / rows / counts, a work that is not 16-byte aligned, a prob that is not
+ * 4-byte aligned, C < 20, N, H or W <= 0, max_rows < 1, slots_per_image no power of two in 1 .. 2^28; FCN8S_ERR_SHAPE for H * W > 2^26,
+ * N > 65535 or C > 2^18. */
+size_t fcn8s_op_instance_work_bytes(int N, int64_t slots_per_image);
+int fcn8s_op_instance_pair(void* stream, const float* prob, int C, const uint8_t* labels, const int32_t* comp,
+                           const uint16_t* gt_instance_ids /* may be NULL */, int N, int H, int W,
+                           void* work, int64_t slots_per_image, int64_t* rows, int64_t max_rows, int64_t* counts);
 /* One TF-Adam (step t, 1-based) / SGD-momentum step over n floats on DEVICE pointers, the gradient scaled by grad_scale.  Every pointer may
  * have any float (4-byte) alignment of its own.  These two, their _dev and their _ema forms below run one kernel and give the same bits. */
 int fcn8s_op_tf_adam(void* stream, float* theta, const float* g, float* m, float* v, int64_t n, int t,
