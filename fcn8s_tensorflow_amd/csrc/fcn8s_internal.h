@@ -414,6 +414,11 @@ void launch_temperature_apply(const float* prob, int N, long long P, int C, floa
 void launch_pseudo_label(const float* prob, int N, long long P, int C, const float* thresholds, const uint8_t* out_ids, int ignore_id,
                          const uint8_t* base, int base_fill, const float* score, float score_max, uint8_t* labels_out,
                          unsigned long long* hist, unsigned long long* counts, unsigned long long* misc, hipStream_t s);
+// class_mix.hip (fcn8s_op_class_mix; the definition is in fcn8s_hip.h).  Clear, presence, selection, mix.  2 <= C <= 255, N <= 256, P < 2^31; work:
+// class_mix_work_bytes(N) bytes at any alignment; selected_out may be null.
+size_t class_mix_work_bytes(int N);
+void launch_class_mix(const uint8_t* images, const uint8_t* labels, const int* src, int N, long long P, int C, unsigned long long seed,
+                      unsigned long long draw, void* work, uint8_t* out_images, uint8_t* out_labels, uint8_t* selected_out, hipStream_t s);
 // boundary.hip (fcn8s_op_boundary_pair; the definition is in fcn8s_hip.h).  One kernel; rings [R + 1][34][34], bprec / brec [R + 2][34] and bad [1] are
 // accumulated into.  1 <= R <= 16, H * W < 2^31.
 void launch_boundary_pair(const uint8_t* gt, const void* pred, int pred_kind, int N, int H, int W, int R, unsigned long long* rings,

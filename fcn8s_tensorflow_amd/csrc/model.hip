@@ -4582,6 +4582,24 @@ int fcn8s_op_pseudo_label(void* stream, const float* prob, int N, int64_t P, int
                         (unsigned long long*)hist, (unsigned long long*)counts, (unsigned long long*)misc, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
+size_t fcn8s_op_class_mix_work_bytes(int N) { return class_mix_work_bytes(N); }
+int fcn8s_op_class_mix(void* stream, const uint8_t* images, const uint8_t* labels, const int32_t* src, int N, int64_t P, int C, uint64_t seed, uint64_t draw,
+                       void* work, uint8_t* out_images, uint8_t* out_labels, uint8_t* selected_out)
+{
+    if (!images || !labels || !src || !work || !out_images || !out_labels || N <= 0 || P <= 0 || C < 2 || C > 255 || draw >= (1ULL << 48))
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "class_mix: bad argument (null images / labels / src / work / out_images / out_labels, N, P <= 0, C outside 2 .. 255, or draw >= 2^48)");
+    if (N > 256 || P >= (1LL << 31)) return fail(nullptr, FCN8S_ERR_SHAPE, "class_mix: a batch has at most 256 images and an image fewer than 2^31 pixels");
+    const uintptr_t T = (uintptr_t)N * (uintptr_t)P;
+    const uintptr_t in[3][2] = {{(uintptr_t)images, 3 * T}, {(uintptr_t)labels, T}, {(uintptr_t)src, (uintptr_t)N * 4}};
+    const uintptr_t out[2][2] = {{(uintptr_t)out_images, 3 * T}, {(uintptr_t)out_labels, T}};
+    for (int o = 0; o < 2; ++o)
+        for (int i = 0; i < 3; ++i)
+            if (out[o][0] < in[i][0] + in[i][1] && in[i][0] < out[o][0] + out[o][1])
+                return fail(nullptr, FCN8S_ERR_BAD_ARG, "class_mix: an output overlaps an input");
+    take_deferred_error(nullptr);
+    launch_class_mix(images, labels, src, N, P, C, seed, draw, work, out_images, out_labels, selected_out, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
 int fcn8s_op_boundary_pair(void* stream, const uint8_t* gt_label_ids, const void* pred, int pred_kind, int N, int H, int W, int R,
                            int64_t* rings, int64_t* bprec, int64_t* brec, int64_t* bad)
 {

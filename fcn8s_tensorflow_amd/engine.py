@@ -1030,6 +1030,22 @@ class Engine:
         return pseudo_label.labels_device(prob, thresholds=thresholds, out_ids=out_ids, ignore_id=ignore_id, base=base, base_fill=base_fill,
                                           score=score, score_max=score_max, labels=labels, tables=tables)
 
+    def class_mix(self, images, labels, src=None, seed=0, draw=0, num_classes=None, status=False, selected=False):
+        """One `fcn8s_op_class_mix` call (class_mix.py; the definition is in include/fcn8s_hip.h) on uint8 device tensors [N,H,W,3] and
+        [N,H,W], on the current stream: for destination n, half of the classes present in image src[n] (None: (n + 1) mod N) are pasted onto
+        image n, pixels and labels alike; the choice is a function of (`seed`, `draw`, n).  `num_classes` None: the model's.  The scratch is
+        kept on the engine and regrown only when a larger one is needed.  Returns new tensors (images, labels), followed by the uint8
+        [N, 256] table of selected classes with `selected`, and by the flag (1: a src[n] lay outside [0, N) and counted as n) with `status`,
+        which synchronises and is meant for tests."""
+        from . import class_mix
+        out_i, out_l, sel, self._class_mix_work = class_mix.mix_device(
+            images, labels, src=src, seed=seed, draw=draw, num_classes=self.logical_classes if num_classes is None else num_classes,
+            selected=selected, work=getattr(self, "_class_mix_work", None))
+        res = (out_i, out_l) + ((sel,) if selected else ())
+        if status:
+            res += (class_mix.flag_of(self._class_mix_work, labels.shape[0]),)
+        return res
+
     def regions_label(self, labels, connectivity=4, area=True):
         """One `fcn8s_op_regions_label` call (regions.py; the definition is in include/fcn8s_hip.h) on a device tensor of class ids, int64 as
         `predict` returns them or uint8, [H,W] or [N,H,W]: (comp, area | None), int32 device tensors of the same shape -- the id (smallest

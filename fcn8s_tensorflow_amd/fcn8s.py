@@ -51,6 +51,7 @@ from . import _lib as L
 from . import crf as crf_mod
 from . import temperature as ts_mod
 from . import pseudo_label as pl_mod
+from . import class_mix as cm_mod
 from . import regions as regions_mod
 from . import loss as loss_mod
 from . import optim as optim_mod
@@ -233,7 +234,13 @@ class FCN8s:
               distill_weight=1.0,
               distill_temperature=1.0,
               distill_pixels='valid',
-              teacher_predict=None):
+              teacher_predict=None,
+              unlabeled_generator=None,
+              unlabeled_labeler='self',
+              unlabeled_thresholds=None,
+              unlabeled_predict=None,
+              unlabeled_mix=True,
+              unlabeled_seed=0):
         '''Trains the model; arguments as fcn8s_tensorflow.py:424-503.  Summaries are written as TensorBoard
         event files (`<summaries_dir>/<summaries_name>[_eval]/events.out.tfevents.*`: total_loss, learning_rate and
         mean / stddev / max / min / histogram of the ten watched weight-bias pairs, :331-366) and, for reading
@@ -268,7 +275,26 @@ class FCN8s:
         (`scales`, `flip`, `crf`, `temperature`), or `samples` / `keep_prob` for the Monte-Carlo mean of `predict_uncertainty`.  A teacher
         model is frozen for the duration of the call and its frozen state restored afterwards; the student's previous soft-target setting is
         restored when train() returns or raises.  While a teacher is set the batches are fed unstaged (no copy of batch k + 1 behind step
-        k).  `distill_loss` (the unscaled term) joins the recorded scalars on the steps that are recorded.'''
+        k).  `distill_loss` (the unscaled term) joins the recorded scalars on the steps that are recorded.
+        `unlabeled_generator` adds online self-training with class mixing (ClassMix, Olsson et al. 2021; DACS, Tranheden et al. 2021;
+        class_mix.py): per update, and per micro-batch under `accumulation_steps`, a batch of M >= 2 unlabelled uint8 images of the labelled
+        batch's height and width is drawn from it (of a tuple the first element is taken), uploaded once and labelled on the device:
+        `unlabeled_labeler` = 'self' predicts with the student as it is (dropout off), 'ema' with its averaged weights (a mean teacher: the
+        prediction runs inside `averaged_weights()`, the raw weights are back before the step; needs `ema_decay` or an existing average),
+        another FCN8s on the same device with the same number of classes predicts with that model, frozen for the call as a `teacher` is.
+        `unlabeled_predict`: keywords of that prediction (`scales`, `flip`, `crf`, `temperature`, or `samples` / `keep_prob` / `mi_max`, as in
+        `fit_pseudo_label_thresholds`).  The softmax becomes hard labels by `Engine.pseudo_label` with `unlabeled_thresholds` (a float, one
+        value per class, or None: `self.pseudo_label_thresholds`, and ValueError if there are none) and the ignore id 255; with
+        `unlabeled_mix`, `Engine.class_mix` then pastes half of the classes of image (n + 1) mod M onto image n, pixels and labels alike,
+        with seed `unlabeled_seed` + rank and draw (global step) * accumulation_steps + micro-batch index, so that a resumed run mixes as the
+        uninterrupted one would.  The labelled batch's labels are brought to uint8 ids on the device, both batches are joined into one of
+        N + M images and the ordinary step runs on it: the loss ignores ids >= num_classes and its mean runs over all (N + M) H W pixels, so
+        the unlabelled term's weight is its pixel share.  The batches are fed unstaged, as under a teacher.  `pseudo_kept`, the share of the
+        unlabelled pixels that kept a label (the last micro-batch's), joins the recorded scalars on the steps that are recorded.  Together
+        with `teacher` it raises.  With 'self' and 'ema' the student's engine sees batches of M and of N + M in turn and re-allocates its
+        workspace at every change of shape, which can cost far more than the prediction (README: timing); a labeler model of its own keeps
+        both engines on one shape.  Not done here: a separate weight on the unlabelled term (change M), DACS's colour jitter and blur,
+        CutMix boxes, mixing labelled with unlabelled images, and any change to `BatchGenerator`.'''
         if self.engine.precision == 'fp8_infer':
             raise ValueError("The 'fp8_infer' precision is inference only; switch the engine to another precision "
                              "(e.g. model.engine.set_precision('bf16_train')) before training.")
@@ -284,6 +310,8 @@ class FCN8s:
         accumulation_steps, max_norm = optim_mod.validate(accumulation_steps, clip_global_norm)
         ema_d, ema_w = optim_mod.validate_ema(ema_decay, ema_warmup)
         teacher_fn = self._resolve_teacher(teacher, teacher_predict, distill_weight, distill_temperature, distill_pixels)
+        unlabeled = self._resolve_unlabeled(unlabeled_generator, unlabeled_labeler, unlabeled_thresholds, unlabeled_predict, unlabeled_mix,
+                                            unlabeled_seed, teacher, bool(ema_d))
         if eval_dataset not in ('train', 'val'):
             raise ValueError("`eval_dataset` must be one of 'train' or 'val', but is '{}'.".format(eval_dataset))
         if eval_dataset == 'val' and (val_generator is None or val_steps is None):
@@ -314,7 +342,11 @@ class FCN8s:
         prev_soft = self.engine.soft_target_config
         teacher_engine = teacher.engine if (teacher_fn is not None and isinstance(teacher, FCN8s)) else None
         teacher_was_frozen = bool(teacher_engine.get_option("frozen")) if teacher_engine is not None else False
+        labeler_engine = unlabeled.labeler_engine if unlabeled is not None else None
+        labeler_was_frozen = bool(labeler_engine.get_option("frozen")) if labeler_engine is not None else False
         try:
+            if labeler_engine is not None:
+                labeler_engine.freeze(True)
             if teacher_fn is not None:
                 self.engine.set_soft_targets(distill_weight, distill_temperature, distill_pixels)
                 if teacher_engine is not None:
@@ -333,7 +365,7 @@ class FCN8s:
             for epoch in range(1, epochs + 1):
                 self._run_epoch(train_generator, steps_per_epoch, learning_rate_schedule, keep_prob, l2_regularization,
                                 'Epoch {}/{}'.format(epoch, epochs), training_loss_display_averaging,
-                                train_log, summaries_frequency, accumulation_steps, teacher_fn)
+                                train_log, summaries_frequency, accumulation_steps, teacher_fn, unlabeled)
                 eval_epoch = epoch % eval_frequency == 0
 
                 if metrics and eval_epoch:
@@ -372,6 +404,8 @@ class FCN8s:
                 self.engine.set_soft_targets(**(prev_soft or {}))
                 if teacher_engine is not None:
                     teacher_engine.freeze(teacher_was_frozen)
+            if labeler_engine is not None:
+                labeler_engine.freeze(labeler_was_frozen)
             for log in (train_log, eval_log):          # the event files are complete and closed when train() returns or raises
                 if log is not None:
                     log.close()
@@ -414,7 +448,75 @@ class FCN8s:
         self.engine.bind_soft_targets(teacher_fn(dev))
         return dev
 
-    def _run_epoch(self, generator, steps, schedule, keep_prob, l2_rate, title, window, log, log_every, accumulation_steps=1, teacher_fn=None):
+    def _resolve_unlabeled(self, generator, labeler, thresholds, predict, mix, seed, teacher, ema_requested):
+        '''train()'s unlabelled-batch arguments -> None (no generator) or the state of the route: the generator, `label` (device images ->
+        (device softmax, score map | None)), the thresholds on the device, the tables `Engine.pseudo_label` counts into, and the mixing's
+        settings.'''
+        if generator is None:
+            if labeler != 'self' or thresholds is not None or predict is not None:
+                raise ValueError("`unlabeled_labeler`, `unlabeled_thresholds` and `unlabeled_predict` need an `unlabeled_generator`.")
+            return None
+        has_average = ema_requested or self.engine.ema_info()['has_shadow']
+        v = cm_mod.validate(self.num_classes, labeler=labeler, thresholds=thresholds, predict=predict, mix=mix, seed=seed, teacher=teacher,
+                            has_average=has_average, model_thresholds=self.pseudo_label_thresholds, student=self)
+        model = self if isinstance(labeler, str) else labeler
+        kw = v['predict']
+        _, routed = model._pseudo_label_route(kw.get('scales'), kw.get('flip', False), kw.get('crf'), kw.get('temperature'), kw.get('samples'),
+                                              kw.get('keep_prob', 0.5), kw.get('mi_max'))
+        predict_fn = routed if kw else (lambda images: (model.predict(images, argmax=False), None))
+        if labeler == 'ema':
+            def label(images):
+                with self.engine.averaged_weights():
+                    return predict_fn(images)
+        else:
+            label = predict_fn
+        torch = self.engine.torch
+        dev = self.engine.device
+        Cn = self.num_classes
+        flat = torch.zeros(2 * Cn + 3, dtype=torch.int64, device=dev)
+        return _Unlabeled(generator=generator, label=label, thresholds=torch.from_numpy(v['thresholds']).to(dev), mi_max=kw.get('mi_max'),
+                          mix=v['mix'], seed=v['seed'] + self.engine.rank, flat=flat,
+                          tables=dict(hist=None, counts=flat[:2 * Cn].view(Cn, 2), misc=flat[2 * Cn:]),
+                          labeler_engine=None if isinstance(labeler, str) else labeler.engine)
+
+    def _join_unlabeled(self, unl, images, labels, draw):
+        '''One batch of the self-training route: the labelled batch on the device with uint8 ids, an unlabelled batch drawn, labelled,
+        thresholded and (with `mix`) class-mixed on the device, both joined.  Returns the device images and labels for the step.'''
+        torch = self.engine.torch
+        dev = self.engine.device
+        x = self.engine._images(images, force_device=True)[0]
+        if x.dtype != torch.uint8:
+            raise ValueError("`unlabeled_generator` needs uint8 images from `train_generator` (the joined batch is one uint8 tensor).")
+        nhw = tuple(int(d) for d in x.shape[:3])
+        lab_rank = labels.dim() if isinstance(labels, torch.Tensor) else np.ndim(labels)
+        if lab_rank == 4:
+            t = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels))
+            ids = self.engine._onehot_to_ids(t, nhw)
+        elif lab_rank == 3:
+            ids = (labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.uint8)))
+            ids = ids.to(torch.uint8).to(dev).contiguous()
+            if tuple(ids.shape) != nhw:
+                raise ValueError("labels shape %s does not match images %s" % (tuple(ids.shape), nhw))
+        else:
+            raise ValueError("labels must be one-hot (batch, height, width, num_classes) or class ids (batch, height, width)")
+        batch = next(unl.generator)
+        if isinstance(batch, tuple):
+            batch = batch[0]
+        u = self.engine._images(batch, force_device=True)[0]
+        if u.dtype != torch.uint8 or u.shape[0] < 2 or tuple(u.shape[1:3]) != nhw[1:]:
+            raise ValueError("`unlabeled_generator` must yield at least 2 uint8 images of the labelled batch's size {}x{}, got {} of dtype {}."
+                             .format(nhw[1], nhw[2], tuple(u.shape), u.dtype))
+        prob, score = unl.label(u)
+        unl.flat.zero_()
+        pseudo, _ = self.engine.pseudo_label(prob, thresholds=unl.thresholds, ignore_id=255, score=score,
+                                             score_max=unl.mi_max if score is not None else None, labels=True, tables=unl.tables)
+        unl.pixels = int(pseudo.numel())
+        if unl.mix:
+            u, pseudo = self.engine.class_mix(u, pseudo, seed=unl.seed, draw=draw)
+        return torch.cat([x, u]), torch.cat([ids, pseudo])
+
+    def _run_epoch(self, generator, steps, schedule, keep_prob, l2_rate, title, window, log, log_every, accumulation_steps=1, teacher_fn=None,
+                   unlabeled=None):
         '''One epoch of train steps (fcn8s_tensorflow.py:542-590): a step runs with the schedule's value
         at the global step before it; `training_loss` is the mean over the last `window` steps.  With `accumulation_steps` = A > 1 a
         step is one update over A batches: A - 1 accumulated micro-batches, then the train step; its loss is the mean of the A losses.'''
@@ -422,7 +524,7 @@ class FCN8s:
         bar = trange(steps, file=sys.stdout, disable=self.engine.rank != 0)
         bar.set_description(title)
         # batch k+1 is decoded / staged / copied while step k runs (under a teacher: decoded only -- the teacher reads the images as a tensor)
-        feed = _Feeder(self.engine, generator, steps * accumulation_steps, stage=teacher_fn is None)
+        feed = _Feeder(self.engine, generator, steps * accumulation_steps, stage=teacher_fn is None and unlabeled is None)
         try:
             for _ in bar:
                 lr = self._lr
@@ -431,10 +533,14 @@ class FCN8s:
                     images, labels = feed.next()
                     if teacher_fn is not None:
                         images = self._bind_teacher(teacher_fn, images)
+                    if unlabeled is not None:
+                        images, labels = self._join_unlabeled(unlabeled, images, labels, self.g_step * accumulation_steps + _k)
                     micro.append(self.engine.accumulate_step(images, labels, keep_prob=keep_prob, l2_rate=l2_rate))
                 images, labels = feed.next()
                 if teacher_fn is not None:
                     images = self._bind_teacher(teacher_fn, images)
+                if unlabeled is not None:
+                    images, labels = self._join_unlabeled(unlabeled, images, labels, self.g_step * accumulation_steps + accumulation_steps - 1)
                 loss, self.g_step = self.engine.train_step(images, labels, learning_rate=lr, keep_prob=keep_prob, l2_rate=l2_rate)
                 if micro:
                     loss = float(np.mean(micro + [loss]))
@@ -446,6 +552,8 @@ class FCN8s:
                         extra.update(grad_norm=st['norm'], clip_coef=st['clip_coef'])
                     if teacher_fn is not None:                 # (the last micro-batch's term)
                         extra.update(distill_loss=self.engine.soft_target_term())
+                    if unlabeled is not None:                  # (the last micro-batch's share; the download synchronises)
+                        extra.update(pseudo_kept=float(unlabeled.tables['counts'][:, 0].sum().item()) / unlabeled.pixels)
                     log.add(self.g_step, total_loss=loss, learning_rate=lr, **extra)
                 recent.append(loss)
                 self.training_loss = float(np.mean(recent))
@@ -1392,6 +1500,14 @@ def _read_meta(model_dir):
         raise IOError("SavedModel file does not exist at: {}".format(model_dir))
     with open(f) as fh:
         return json.load(fh)
+
+
+class _Unlabeled:
+    """The state of train()'s self-training route for one call (FCN8s._resolve_unlabeled)."""
+
+    def __init__(self, **kw):
+        self.pixels = 0
+        self.__dict__.update(kw)
 
 
 class _Feeder:

@@ -912,6 +912,30 @@ int fcn8s_op_temperature_apply(void* stream, const float* prob, int N, int64_t P
 int fcn8s_op_pseudo_label(void* stream, const float* prob, int N, int64_t P, int C, const float* thresholds, const uint8_t* out_ids, int ignore_id,
                           const uint8_t* base, int base_fill, const float* score, float score_max, uint8_t* labels_out,
                           int64_t* hist, int64_t* counts, int64_t* misc);
+/* ClassMix (Olsson et al., WACV 2021; the mixing of DACS, Tranheden et al., WACV 2021) for a batch of N images of P pixels each on DEVICE
+ * pointers: half of the classes present in a source image are cut out along its label mask and pasted onto a destination image, pixels and
+ * labels alike.  Integers only.
+ *   images [N,P,3] uint8, labels [N,P] uint8 (ids >= C, the ignore id among them, are not classes), src [N] int32 on the device: the source
+ *   image of destination n.  2 <= C <= 255.  For destination n with source s = src[n]:
+ *   1. Presence.  Class c < C is present in s when at least one pixel of labels[s] equals c; k = the number of present classes.
+ *   2. Selection.  key(c) = philox_u32(draw * 2^16 + n * 2^8 + c, seed, 0x434D4958), the library's counter-based generator (ten Philox-4x32
+ *      rounds; the dropout masks use the same).  rank(c) = the number of present c' with (key(c'), c') < (key(c), c), compared lexicographically.
+ *      c is selected iff it is present and rank(c) < m, m = ceil(k / 2) (ClassMix's count); k = 0 selects nothing.  selected_out [N][256] uint8
+ *      (may be NULL) holds 1 or 0 per class, 0 for every c >= C.
+ *   3. Mix.  Where labels[s][p] < C and that class is selected: out_images[n][p][:] = images[s][p][:] and out_labels[n][p] = labels[s][p];
+ *      elsewhere both come from image n.  src[n] == n is legal and yields image n.
+ *   A src[n] outside [0, N) cannot be refused on the host: the kernels treat it as n and set a flag.
+ * work: fcn8s_op_class_mix_work_bytes(N) bytes of device scratch at any alignment, whose content on entry does not matter.  Behind its first
+ * 16-byte boundary b it holds the presence sets (32 N bytes), the tables (256 N bytes) and, at b + 288 N, the flag: a uint32 that is 0 after a
+ * call whose src was in range and 1 otherwise.
+ * Any byte alignment of every pointer: every stream moves as 16-byte accesses of whole lines of memory, byte by byte at its ragged ends; no byte
+ * outside the outputs is written.  The outputs must not overlap the inputs.  Only integer ORs and compares decide anything: two runs give the same
+ * bits.  Stream-ordered; does not synchronise; allocates nothing.  FCN8S_ERR_BAD_ARG (nothing launched, the outputs untouched) for a NULL images /
+ * labels / src / work / out_images / out_labels, N or P <= 0, C outside 2..255, draw >= 2^48, an output range that overlaps images, labels or
+ * src; FCN8S_ERR_SHAPE for N > 256 or P >= 2^31. */
+size_t fcn8s_op_class_mix_work_bytes(int N);
+int fcn8s_op_class_mix(void* stream, const uint8_t* images, const uint8_t* labels, const int32_t* src, int N, int64_t P, int C, uint64_t seed,
+                       uint64_t draw, void* work, uint8_t* out_images, uint8_t* out_labels, uint8_t* selected_out);
 /* Boundary measures of a segmentation against its ground truth -- the counting half of the trimap IoU (accuracy inside a band of width r around
  * the ground-truth boundaries: Kraehenbuehl & Koltun 2011, Chen et al. 2015) and of the boundary F-score (Csurka et al., BMVC 2013) -- for a batch
  * of N images of H x W pixels on DEVICE pointers.  All integers.
