@@ -419,6 +419,12 @@ void launch_pseudo_label(const float* prob, int N, long long P, int C, const flo
 size_t class_mix_work_bytes(int N);
 void launch_class_mix(const uint8_t* images, const uint8_t* labels, const int* src, int N, long long P, int C, unsigned long long seed,
                       unsigned long long draw, void* work, uint8_t* out_images, uint8_t* out_labels, uint8_t* selected_out, hipStream_t s);
+// strong_augment.hip (fcn8s_op_strong_augment; the definition is in fcn8s_hip.h).  Clear and grey sum (only with a contrast strength), augment.  jitter
+// [5], blur [3] and taps [Q][R + 1] are HOST arrays, validated by the caller and passed on by value; any of the first two may be null (taps with blur).
+// N <= 256, H * W < 2^31, H, W > R; work: strong_augment_work_bytes(N) bytes at any alignment; params_out may be null.
+size_t strong_augment_work_bytes(int N);
+void launch_strong_augment(const uint8_t* images, int N, int H, int W, unsigned long long seed, unsigned long long draw, const int* jitter, const int* blur,
+                           const unsigned short* taps, void* work, uint8_t* out_images, int* params_out, hipStream_t s);
 // boundary.hip (fcn8s_op_boundary_pair; the definition is in fcn8s_hip.h).  One kernel; rings [R + 1][34][34], bprec / brec [R + 2][34] and bad [1] are
 // accumulated into.  1 <= R <= 16, H * W < 2^31.
 void launch_boundary_pair(const uint8_t* gt, const void* pred, int pred_kind, int N, int H, int W, int R, unsigned long long* rings,

@@ -4600,6 +4600,38 @@ int fcn8s_op_class_mix(void* stream, const uint8_t* images, const uint8_t* label
     launch_class_mix(images, labels, src, N, P, C, seed, draw, work, out_images, out_labels, selected_out, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
+size_t fcn8s_op_strong_augment_work_bytes(int N) { return strong_augment_work_bytes(N); }
+int fcn8s_op_strong_augment(void* stream, const uint8_t* images, int N, int H, int W, uint64_t seed, uint64_t draw, const int32_t* jitter, const int32_t* blur,
+                            const uint16_t* taps, void* work, uint8_t* out_images, int32_t* params_out)
+{
+    if (!images || !work || !out_images || N <= 0 || H <= 0 || W <= 0 || draw >= (1ULL << 48))
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "strong_augment: bad argument (null images / work / out_images, N, H or W <= 0, or draw >= 2^48)");
+    if (jitter && (jitter[0] < 0 || jitter[0] > 65536 || jitter[1] < 0 || jitter[1] > 65536 || jitter[2] < 0 || jitter[2] > 65536 || jitter[3] < 0 ||
+                   jitter[3] > 65536 || jitter[4] < 0 || jitter[4] > 90))
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "strong_augment: jitter is {gate 0..65536, contrast, saturation, brightness 0..65536, hue 0..90}");
+    if (blur) {
+        if (blur[0] < 0 || blur[0] > 65536 || blur[1] < 1 || blur[1] > 16 || blur[2] < 1 || blur[2] > 7 || !taps)
+            return fail(nullptr, FCN8S_ERR_BAD_ARG, "strong_augment: blur is {gate 0..65536, levels 1..16, radius 1..7} and needs taps");
+        for (int q = 0; q < blur[1]; ++q) {
+            const uint16_t* w = taps + q * (blur[2] + 1);
+            int sum = w[0];
+            for (int i = 1; i <= blur[2]; ++i) {
+                if (w[i] > w[i - 1]) return fail(nullptr, FCN8S_ERR_BAD_ARG, "strong_augment: a row of taps increases");
+                sum += 2 * w[i];
+            }
+            if (sum != 2048) return fail(nullptr, FCN8S_ERR_BAD_ARG, "strong_augment: a row of taps does not sum to 2048 (w[0] + 2 (w[1] + ... + w[R]))");
+        }
+    }
+    if (N > 256 || (int64_t)H * W >= (1LL << 31))
+        return fail(nullptr, FCN8S_ERR_SHAPE, "strong_augment: a batch has at most 256 images and an image fewer than 2^31 pixels");
+    if (blur && (H <= blur[2] || W <= blur[2])) return fail(nullptr, FCN8S_ERR_SHAPE, "strong_augment: the blur needs H > R and W > R (one reflection)");
+    const uintptr_t T = (uintptr_t)N * (uintptr_t)H * (uintptr_t)W * 3;
+    if ((uintptr_t)out_images < (uintptr_t)images + T && (uintptr_t)images < (uintptr_t)out_images + T)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "strong_augment: out_images overlaps images (the blur reads neighbours: not in place)");
+    take_deferred_error(nullptr);
+    launch_strong_augment(images, N, H, W, seed, draw, jitter, blur, taps, work, out_images, params_out, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
 int fcn8s_op_boundary_pair(void* stream, const uint8_t* gt_label_ids, const void* pred, int pred_kind, int N, int H, int W, int R,
                            int64_t* rings, int64_t* bprec, int64_t* brec, int64_t* bad)
 {

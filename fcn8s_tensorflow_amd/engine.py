@@ -1046,6 +1046,18 @@ class Engine:
             res += (class_mix.flag_of(self._class_mix_work, labels.shape[0]),)
         return res
 
+    def strong_augment(self, images, seed=0, draw=0, jitter=None, blur=None, params=False):
+        """One `fcn8s_op_strong_augment` call (strong_augment.py; the definition is in include/fcn8s_hip.h) on a uint8 device tensor
+        [N,H,W,3], on the current stream: per image a gated colour jitter (`jitter` = five ints {gate, contrast, saturation, brightness,
+        hue}, None: none) and a gated Gaussian blur (`blur` = (gate, taps [Q, R + 1]) with `strong_augment.taps_table`'s taps, None: none);
+        the draws are a function of (`seed`, `draw`, n) with `class_mix`'s counters.  The small arrays travel in the launch arguments:
+        nothing is uploaded and nothing synchronises.  The scratch is kept on the engine and regrown only when a larger one is needed.
+        Returns a new tensor, with `params` (images, int32 [N, 8] = {colour step ran, c16, s16, b16, dh, m, blur ran, q} per image)."""
+        from . import strong_augment
+        out, par, self._strong_augment_work = strong_augment.augment_device(
+            images, seed=seed, draw=draw, jitter=jitter, blur=blur, params=params, work=getattr(self, "_strong_augment_work", None))
+        return (out, par) if params else out
+
     def regions_label(self, labels, connectivity=4, area=True):
         """One `fcn8s_op_regions_label` call (regions.py; the definition is in include/fcn8s_hip.h) on a device tensor of class ids, int64 as
         `predict` returns them or uint8, [H,W] or [N,H,W]: (comp, area | None), int32 device tensors of the same shape -- the id (smallest

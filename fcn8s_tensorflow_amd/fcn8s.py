@@ -52,6 +52,7 @@ from . import crf as crf_mod
 from . import temperature as ts_mod
 from . import pseudo_label as pl_mod
 from . import class_mix as cm_mod
+from . import strong_augment as sa_mod
 from . import regions as regions_mod
 from . import loss as loss_mod
 from . import optim as optim_mod
@@ -240,7 +241,8 @@ class FCN8s:
               unlabeled_thresholds=None,
               unlabeled_predict=None,
               unlabeled_mix=True,
-              unlabeled_seed=0):
+              unlabeled_seed=0,
+              unlabeled_augment=None):
         '''Trains the model; arguments as fcn8s_tensorflow.py:424-503.  Summaries are written as TensorBoard
         event files (`<summaries_dir>/<summaries_name>[_eval]/events.out.tfevents.*`: total_loss, learning_rate and
         mean / stddev / max / min / histogram of the ten watched weight-bias pairs, :331-366) and, for reading
@@ -293,8 +295,15 @@ class FCN8s:
         unlabelled pixels that kept a label (the last micro-batch's), joins the recorded scalars on the steps that are recorded.  Together
         with `teacher` it raises.  With 'self' and 'ema' the student's engine sees batches of M and of N + M in turn and re-allocates its
         workspace at every change of shape, which can cost far more than the prediction (README: timing); a labeler model of its own keeps
-        both engines on one shape.  Not done here: a separate weight on the unlabelled term (change M), DACS's colour jitter and blur,
-        CutMix boxes, mixing labelled with unlabelled images, and any change to `BatchGenerator`.'''
+        both engines on one shape.
+        `unlabeled_augment` adds DACS's strong augmentation of the student's view (strong_augment.py): after the mixing -- and with
+        `unlabeled_mix=False` too -- `Engine.strong_augment` recolours and blurs the unlabelled images with the mixing's seed and draw; the
+        labeler has already seen the clean images and the labels do not change.  None: off (nothing new is launched or allocated); True:
+        `strong_augment.DEFAULTS` (colour jitter with probability 0.8 and strength 0.25 on brightness, contrast and saturation, hue within a
+        quarter of +-90 units, Gaussian blur with probability 0.5, sigma in [0.15, 1.15] in 16 levels, radius 4 -- DACS's settings as
+        recalled, not checked against its code); a dict overrides fields of those.  Without `unlabeled_generator` it raises.
+        Not done here: a separate weight on the unlabelled term (change M), CutMix boxes, geometric strong augmentation, augmenting or
+        mixing the labelled images, and any change to `BatchGenerator`.'''
         if self.engine.precision == 'fp8_infer':
             raise ValueError("The 'fp8_infer' precision is inference only; switch the engine to another precision "
                              "(e.g. model.engine.set_precision('bf16_train')) before training.")
@@ -311,7 +320,7 @@ class FCN8s:
         ema_d, ema_w = optim_mod.validate_ema(ema_decay, ema_warmup)
         teacher_fn = self._resolve_teacher(teacher, teacher_predict, distill_weight, distill_temperature, distill_pixels)
         unlabeled = self._resolve_unlabeled(unlabeled_generator, unlabeled_labeler, unlabeled_thresholds, unlabeled_predict, unlabeled_mix,
-                                            unlabeled_seed, teacher, bool(ema_d))
+                                            unlabeled_seed, teacher, bool(ema_d), unlabeled_augment)
         if eval_dataset not in ('train', 'val'):
             raise ValueError("`eval_dataset` must be one of 'train' or 'val', but is '{}'.".format(eval_dataset))
         if eval_dataset == 'val' and (val_generator is None or val_steps is None):
@@ -448,14 +457,16 @@ class FCN8s:
         self.engine.bind_soft_targets(teacher_fn(dev))
         return dev
 
-    def _resolve_unlabeled(self, generator, labeler, thresholds, predict, mix, seed, teacher, ema_requested):
+    def _resolve_unlabeled(self, generator, labeler, thresholds, predict, mix, seed, teacher, ema_requested, augment=None):
         '''train()'s unlabelled-batch arguments -> None (no generator) or the state of the route: the generator, `label` (device images ->
         (device softmax, score map | None)), the thresholds on the device, the tables `Engine.pseudo_label` counts into, and the mixing's
         settings.'''
         if generator is None:
             if labeler != 'self' or thresholds is not None or predict is not None:
                 raise ValueError("`unlabeled_labeler`, `unlabeled_thresholds` and `unlabeled_predict` need an `unlabeled_generator`.")
+            sa_mod.validate(augment, has_generator=False)
             return None
+        augment = sa_mod.validate(augment)
         has_average = ema_requested or self.engine.ema_info()['has_shadow']
         v = cm_mod.validate(self.num_classes, labeler=labeler, thresholds=thresholds, predict=predict, mix=mix, seed=seed, teacher=teacher,
                             has_average=has_average, model_thresholds=self.pseudo_label_thresholds, student=self)
@@ -475,13 +486,13 @@ class FCN8s:
         Cn = self.num_classes
         flat = torch.zeros(2 * Cn + 3, dtype=torch.int64, device=dev)
         return _Unlabeled(generator=generator, label=label, thresholds=torch.from_numpy(v['thresholds']).to(dev), mi_max=kw.get('mi_max'),
-                          mix=v['mix'], seed=v['seed'] + self.engine.rank, flat=flat,
+                          mix=v['mix'], seed=v['seed'] + self.engine.rank, flat=flat, augment=augment,
                           tables=dict(hist=None, counts=flat[:2 * Cn].view(Cn, 2), misc=flat[2 * Cn:]),
                           labeler_engine=None if isinstance(labeler, str) else labeler.engine)
 
     def _join_unlabeled(self, unl, images, labels, draw):
         '''One batch of the self-training route: the labelled batch on the device with uint8 ids, an unlabelled batch drawn, labelled,
-        thresholded and (with `mix`) class-mixed on the device, both joined.  Returns the device images and labels for the step.'''
+        thresholded, (with `mix`) class-mixed and (with `augment`) recoloured and blurred on the device, both joined.  Returns the device images and labels for the step.'''
         torch = self.engine.torch
         dev = self.engine.device
         x = self.engine._images(images, force_device=True)[0]
@@ -513,6 +524,8 @@ class FCN8s:
         unl.pixels = int(pseudo.numel())
         if unl.mix:
             u, pseudo = self.engine.class_mix(u, pseudo, seed=unl.seed, draw=draw)
+        if unl.augment is not None:                                 # the student's view only: the labeler has seen the clean images
+            u = self.engine.strong_augment(u, seed=unl.seed, draw=draw, jitter=unl.augment['jitter'], blur=unl.augment['blur'])
         return torch.cat([x, u]), torch.cat([ids, pseudo])
 
     def _run_epoch(self, generator, steps, schedule, keep_prob, l2_rate, title, window, log, log_every, accumulation_steps=1, teacher_fn=None,

@@ -936,6 +936,36 @@ int fcn8s_op_pseudo_label(void* stream, const float* prob, int N, int64_t P, int
 size_t fcn8s_op_class_mix_work_bytes(int N);
 int fcn8s_op_class_mix(void* stream, const uint8_t* images, const uint8_t* labels, const int32_t* src, int N, int64_t P, int C, uint64_t seed,
                        uint64_t draw, void* work, uint8_t* out_images, uint8_t* out_labels, uint8_t* selected_out);
+/* Strong photometric augmentation of a batch of N uint8 RGB images of H x W pixels on DEVICE pointers -- the colour jitter and Gaussian blur that
+ * DACS (Tranheden et al., WACV 2021) and ClassMix (Olsson et al., WACV 2021) apply to the student's input and not to the labeler's.  Integers plus
+ * the float32 steps of the 8-bit HSV -> RGB conversion of fcn8s_op_augment_u8 (OpenCV's RGB2HSV_b / HSV2RGB_b, H in [0, 180)).
+ *   images, out_images [N,H,W,3] uint8 on the device, at any byte alignment; they must not overlap (the blur reads neighbours).
+ *   jitter, blur and taps are HOST pointers, read before the call returns and passed to the kernels by value (no device table, no upload):
+ *   jitter = {gate, Cs, Ss, Bs, Hs} int32, NULL = no colour step; blur = {gate, Q, R} int32 with taps [Q][R + 1] uint16, both NULL = no blur.
+ *   Gates lie in 0..65536 (65536 = always), 0 <= Cs, Ss, Bs <= 65536, 0 <= Hs <= 90, 1 <= Q <= 16, 1 <= R <= 7; every row w of taps has
+ *   w[0] + 2 (w[1] + ... + w[R]) = 2048 and w[i] <= w[i - 1].
+ *   Draws.  u_j = philox_u32(draw * 2^16 + n * 2^8 + j, seed, 0x53415547) for j = 0..6: the library's generator on a stream of its own, with
+ *   fcn8s_op_class_mix's counters, so that one (seed, draw) serves both.  U(u, S) = -S + ((u (2 S + 1)) >> 32) in 64 bits: uniform in [-S, S].
+ *   Colour step, for image n iff (u_0 >> 16) < gate:
+ *   1. Contrast, only when Cs != 0: c16 = 65536 + U(u_1, Cs); m = (2 G + P) / (2 P) in integers, P = H W, G = the sum over the INPUT image of
+ *      g = (4899 R + 9617 G + 1868 B + 8192) >> 14; per channel t = x c16 + m (65536 - c16) + 32768 (signed 32 bits), x' = clamp(t >> 16, 0, 255)
+ *      with an arithmetic shift.
+ *   2. HSV, only when Ss | Bs | Hs != 0: (H, S, V) = RGB2HSV_b(x'); H' = (H + 180 + U(u_4, Hs)) mod 180; S' = min(255, (S s16 + 32768) >> 16) with
+ *      s16 = 65536 + U(u_2, Ss); V' likewise with b16 = 65536 + U(u_3, Bs); x'' = HSV2RGB_b(H', S', V').  All strengths 0 leave every byte as it is.
+ *   Blur, for image n iff (u_5 >> 16) < blur gate, of the colour step's output: q = (u_6 Q) >> 32, w = taps[q]; separable, per channel, borders
+ *   reflect-101 (index -i reads i, W - 1 + i reads W - 1 - i); a = sum_i w[|i|] x[. + i] along the row, b = sum_i w[|i|] a[. + i] down the column
+ *   (b <= 255 * 2^22), out = (b + 2^21) >> 22: no intermediate rounding.  An image whose gates both fail is copied.
+ *   params_out [N][8] int32 on the device (may be NULL): per image {colour step ran, c16, s16, b16, dh, m, blur ran, q}, 0 for what did not run
+ *   (c16 and m without contrast, s16, b16 and dh without the HSV step, q without the blur).
+ * work: fcn8s_op_strong_augment_work_bytes(N) bytes of device scratch at any alignment, whose content on entry does not matter; it holds the N
+ * 64-bit grey sums at its first 16-byte boundary.  The sums are integer adds (one 64-bit atomic per block): two runs give the same bits.
+ * Stream-ordered; does not synchronise; allocates nothing.  No byte outside out_images is written.
+ * FCN8S_ERR_BAD_ARG (nothing launched, the outputs untouched) for a NULL images / work / out_images, N, H or W <= 0, draw >= 2^48, a gate or a
+ * strength out of range, Q outside 1..16, R outside 1..7, taps NULL when blur is not, a row of taps that does not sum to 2048 or increases,
+ * out_images overlapping images; FCN8S_ERR_SHAPE for N > 256, H W >= 2^31, or H <= R or W <= R when blur is not NULL (one reflection suffices). */
+size_t fcn8s_op_strong_augment_work_bytes(int N);
+int fcn8s_op_strong_augment(void* stream, const uint8_t* images, int N, int H, int W, uint64_t seed, uint64_t draw, const int32_t* jitter,
+                            const int32_t* blur, const uint16_t* taps, void* work, uint8_t* out_images, int32_t* params_out);
 /* Boundary measures of a segmentation against its ground truth -- the counting half of the trimap IoU (accuracy inside a band of width r around
  * the ground-truth boundaries: Kraehenbuehl & Koltun 2011, Chen et al. 2015) and of the boundary F-score (Csurka et al., BMVC 2013) -- for a batch
  * of N images of H x W pixels on DEVICE pointers.  All integers.
