@@ -22,7 +22,6 @@ from __future__ import annotations
 
 import ctypes as C
 import fnmatch
-import glob
 import json
 import math
 import os
@@ -836,8 +835,6 @@ def evaluate_file_pairs(prediction_files, ground_truth_files, device=None, insta
 def evaluate_directory(ground_truth_search, prediction_path, device=None, instance_level=False, boundary_radius=None, panoptic=None):
     """The evaluator's no-argument mode (:667-676): every ground-truth file matching the glob (the official one is
     `<cityscapes>/gtFine/val/*/*_gtFine_labelIds.png`) against its prediction below `prediction_path`."""
-    gts = sorted(glob.glob(ground_truth_search))
-    if not gts:
-        raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
-    walk = walk_predictions(prediction_path)
-    return evaluate_file_pairs([find_prediction(prediction_path, g, walk) for g in gts], gts, device, instance_level, boundary_radius, panoptic)
+    from . import sweeps
+    gts, predictions = sweeps.paired_files(prediction_path, ground_truth_search, 'png')
+    return evaluate_file_pairs(predictions, gts, device, instance_level, boundary_radius, panoptic)

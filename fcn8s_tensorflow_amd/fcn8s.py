@@ -54,6 +54,7 @@ from . import pseudo_label as pl_mod
 from . import class_mix as cm_mod
 from . import strong_augment as sa_mod
 from . import regions as regions_mod
+from . import sweeps
 from . import loss as loss_mod
 from . import optim as optim_mod
 from . import tf_bundle
@@ -472,8 +473,9 @@ class FCN8s:
                             has_average=has_average, model_thresholds=self.pseudo_label_thresholds, student=self)
         model = self if isinstance(labeler, str) else labeler
         kw = v['predict']
-        _, routed = model._pseudo_label_route(kw.get('scales'), kw.get('flip', False), kw.get('crf'), kw.get('temperature'), kw.get('samples'),
-                                              kw.get('keep_prob', 0.5), kw.get('mi_max'))
+        route = sweeps.resolve_route(model, kw.get('scales'), kw.get('flip', False), kw.get('crf'), kw.get('temperature'), kw.get('samples'),
+                                     kw.get('keep_prob', 0.5), mi_max=kw.get('mi_max'))
+        routed = lambda images: route.softmax(images, mutual_information=kw.get('mi_max') is not None)[::2]
         predict_fn = routed if kw else (lambda images: (model.predict(images, argmax=False), None))
         if labeler == 'ema':
             def label(images):
@@ -731,7 +733,6 @@ class FCN8s:
         regions = None
         if regions_mod.resolve(min_region, self.num_classes) is not None:
             regions = dict(min_region=min_region, region_connectivity=region_connectivity, region_rounds=region_rounds)
-        from PIL import Image
 
         if overwrite_existing and os.path.exists(results_dir):
             shutil.rmtree(results_dir)
@@ -745,12 +746,9 @@ class FCN8s:
         tr = trange(num_images, file=sys.stdout)
         tr.set_description('Processing images')
 
-        self.engine.freeze(True)            # constant weights for the whole directory
-        try:
+        with sweeps.frozen(self.engine):
             for i in tr:
                 self._segment_file(image_paths[i], results_dir, color_map, resize, include_unprocessed_image, arrangement, scales, flip, crf, regions)
-        finally:
-            self.engine.freeze(False)
 
     def predict_and_export_label_ids(self, results_dir, images_dir, resize=False, image_file_extension='png', overwrite_existing=True,
                                      scales=None, flip=False, crf=None, min_region=None, region_connectivity=4, region_rounds=1):
@@ -768,26 +766,18 @@ class FCN8s:
         if overwrite_existing and os.path.exists(results_dir):
             shutil.rmtree(results_dir)
         os.makedirs(results_dir, exist_ok=True)
-        paths = sorted(glob(os.path.join(images_dir, '**', '*.' + image_file_extension), recursive=True))
+        paths = sweeps.image_files(images_dir, image_file_extension, allow_none=True)
         tr = trange(len(paths), file=sys.stdout)
         tr.set_description('Exporting label ids')
-        self.engine.freeze(True)
-        try:
+        with sweeps.frozen(self.engine):
             for i in tr:
-                pil = Image.open(paths[i]).convert('RGB')
-                size = pil.size
-                if resize and not np.array_equal((pil.height, pil.width), resize):
-                    pil = pil.resize((resize[1], resize[0]), Image.BILINEAR)
-                kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
-                if regions_mod.resolve(min_region, self.num_classes) is not None:
-                    kw.update(min_region=min_region, region_connectivity=region_connectivity, region_rounds=region_rounds)
-                pred = np.asarray(self.predict([np.asarray(pil)], argmax=True, scales=scales, flip=flip, **kw))[0]
+                image, size = sweeps.load_image(paths[i], resize, 'cpu')        # a host image: the call uploads it and downloads the ids
+                pred = np.asarray(self.predict(image, argmax=True, scales=scales, flip=flip, crf=crf, min_region=min_region,
+                                               region_connectivity=region_connectivity, region_rounds=region_rounds))[0]
                 ids = Image.fromarray(ce.TRAINIDS_TO_IDS_ARRAY[pred])
                 if ids.size != size:
                     ids = ids.resize(size, Image.NEAREST)
                 ids.save(os.path.join(results_dir, os.path.basename(paths[i])))
-        finally:
-            self.engine.freeze(False)
         return len(paths)
 
     def evaluate_cityscapes(self, images_dir, ground_truth_search, resize=False, image_file_extension='png', scales=None, flip=False, crf=None,
@@ -822,39 +812,23 @@ class FCN8s:
             raise ValueError("the Cityscapes evaluation uses the 20 Cityscapes train ids; this model has {} classes.".format(self.num_classes))
         if json_path is not None and not instance_level:
             raise ValueError("`json_path` writes the evaluator's result file, which holds the instance-level scores: needs instance_level=True.")
-        gts = sorted(glob(ground_truth_search))
-        if not gts:
-            raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
-        walk = ce.walk_predictions(images_dir)
-        paths = [ce.find_prediction(images_dir, g, walk, extension=image_file_extension) for g in gts]
+        gts, paths = sweeps.paired_files(images_dir, ground_truth_search, image_file_extension)
         dev = self.engine.device
         ev = ce.PixelLevelEvaluator(instance_level=instance_level, boundary_radius=boundary_radius, panoptic=panoptic)
         pixels = 0
-        kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
-        if regions_mod.resolve(min_region, self.num_classes) is not None:
-            kw.update(min_region=min_region, region_connectivity=region_connectivity, region_rounds=region_rounds)
         tr = trange(len(gts), file=sys.stdout)
         tr.set_description('Evaluating')
-        self.engine.freeze(True)
-        try:
+        with sweeps.frozen(self.engine):
             for i in tr:
-                pil = Image.open(paths[i]).convert('RGB')
-                size = pil.size
-                if resize and not np.array_equal((pil.height, pil.width), resize):
-                    pil = pil.resize((resize[1], resize[0]), Image.BILINEAR)
-                image = torch.from_numpy(np.array(pil)[None]).to(dev)
-                pred = self.predict(image, argmax=True, scales=scales, flip=flip, **kw)[0]               # int64 train ids, on the device
+                image, size = sweeps.load_image(paths[i], resize, dev)
+                pred = self.predict(image, argmax=True, scales=scales, flip=flip, crf=crf, min_region=min_region,
+                                    region_connectivity=region_connectivity, region_rounds=region_rounds)[0]       # int64 train ids, on the device
                 train_ids = True
-                if pil.size != size:
+                if (pred.shape[1], pred.shape[0]) != size:
                     ids = Image.fromarray(ce.TRAINIDS_TO_IDS_ARRAY[pred.cpu().numpy()]).resize(size, Image.NEAREST)
                     pred = torch.from_numpy(np.array(ids)).to(dev); train_ids = False
                 gt = np.array(Image.open(gts[i]))
-                if pred.shape[1] != gt.shape[1]:
-                    raise ValueError("Image widths of " + paths[i] + " and " + gts[i] + " are not equal.")
-                if pred.shape[0] != gt.shape[0]:
-                    raise ValueError("Image heights of " + paths[i] + " and " + gts[i] + " are not equal.")
-                if gt.max() >= ce.NUM_IDS:
-                    raise ValueError("Unknown label with id {:}".format(int(gt.max())))
+                sweeps.check_label_map(gt, pred.shape, paths[i], gts[i])
                 inst = None
                 if instance_level:
                     inf = ce.instance_file_of(gts[i])
@@ -868,8 +842,6 @@ class FCN8s:
                 pixels += gt.size
                 if int(ev.conf.sum()) != pixels:
                     raise ValueError("Number of analyzed pixels and entries in confusion matrix disagree: contMatrix {}, pixels {}".format(int(ev.conf.sum()), pixels))
-        finally:
-            self.engine.freeze(False)
         res = ev.results()
         res["confMatrix"] = ev.conf
         res["nbPixels"] = pixels
@@ -898,66 +870,30 @@ class FCN8s:
         sample's softmax, which `fcn8s_predict_mc` does not take.'''
         from PIL import Image
         import torch
-        from . import cityscapes_eval as ce, reliability as rel
-        if temperature is not None:
-            temperature = ts_mod.validate_temperature(temperature)
-            if samples is not None:
-                raise ValueError("`temperature` with `samples`: calibrating Monte-Carlo samples needs the temperature inside each sample's softmax; "
-                                 "score the single-pass, `scales` / `flip` or `crf` route instead.")
-            if temperature == 1.0:
-                temperature = None
+        from . import reliability as rel
+        route = sweeps.resolve_route(self, scales, flip, crf, temperature, samples, keep_prob, sample_offset, verb='score')
         if self.num_classes != 20:
             raise ValueError("the Cityscapes evaluation uses the 20 Cityscapes train ids; this model has {} classes.".format(self.num_classes))
-        passes = scales is not None or bool(flip) or crf_mod.resolve(crf) is not None
-        if samples is not None and passes:
-            raise ValueError("`samples` runs the Monte-Carlo dropout route, which has no `scales` / `flip` / `crf` passes; use one or the other.")
-        if samples is not None:
-            route, names = 'mc', ('entropy', 'mutualInformation')
-        elif not passes:
-            route, names, samples, keep_prob, sample_offset = 'single', ('entropy',), 1, 1.0, 0
-        else:
-            route, names = 'passes', ()
+        names = {'mc': ('entropy', 'mutualInformation'), 'single': ('entropy',), 'passes': ()}[route.name]
         ev = rel.Evaluator(bins=bins, num_classes=self.num_classes, lut=rel.cityscapes_lut(), score_names=names, score_max=score_max)
-        gts = sorted(glob(ground_truth_search))
-        if not gts:
-            raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
-        walk = ce.walk_predictions(images_dir)
-        paths = [ce.find_prediction(images_dir, g, walk, extension=image_file_extension) for g in gts]
+        gts, paths = sweeps.paired_files(images_dir, ground_truth_search, image_file_extension)
         dev = self.engine.device
         pixels = 0
-        kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
         tr = trange(len(gts), file=sys.stdout)
         tr.set_description('Evaluating')
-        self.engine.freeze(True)
-        try:
+        with sweeps.frozen(self.engine):
             for i in tr:
-                image = torch.from_numpy(np.array(Image.open(paths[i]).convert('RGB'))[None]).to(dev)
-                if route == 'passes':
-                    prob, maps = self.predict(image, argmax=False, scales=scales, flip=flip, **kw), ()
-                else:
-                    prob, ent, mi = self.engine.predict_mc(image, samples=samples, keep_prob=keep_prob, sample_offset=sample_offset, argmax=False,
-                                                           entropy=True, mutual_information=route == 'mc')
-                    maps = (ent, mi) if route == 'mc' else (ent,)
-                if temperature is not None:
-                    _, ent_q = self.engine.temperature_apply(prob, temperature, entropy=route == 'single', out=prob)
-                    maps = (ent_q,) if route == 'single' else ()
+                prob, *maps = route.softmax(sweeps.load_image(paths[i], False, dev)[0], entropy=True, mutual_information=True)
                 gt = np.array(Image.open(gts[i]))
-                if prob.shape[2] != gt.shape[1]:
-                    raise ValueError("Image widths of " + paths[i] + " and " + gts[i] + " are not equal.")
-                if prob.shape[1] != gt.shape[0]:
-                    raise ValueError("Image heights of " + paths[i] + " and " + gts[i] + " are not equal.")
-                if gt.ndim != 2 or gt.max() >= ce.NUM_IDS:
-                    raise ValueError("Unknown label with id {:}".format(int(gt.max())))
-                ev.add(prob, torch.from_numpy(gt.astype(np.uint8)[None]).to(dev), maps)
+                sweeps.check_label_map(gt, prob.shape[1:3], paths[i], gts[i])
+                ev.add(prob, torch.from_numpy(gt.astype(np.uint8)[None]).to(dev), tuple(maps[:len(names)]))
                 pixels += gt.size
-        finally:
-            self.engine.freeze(False)
         res = ev.results()
         bad = res["tables"]["bad"]
         if bad.any():
             raise ValueError("{} pixels hold a train id outside 0..19 and {} a confidence or uncertainty that is not finite".format(int(bad[0]), int(bad[1])))
         res["nbPixels"] = pixels
-        res["route"] = route
+        res["route"] = route.name
         if json_path is not None:
             rel.write_result_json(res, json_path)
         return res
@@ -977,18 +913,13 @@ class FCN8s:
         'route'; `json_path`: also write it.  Works inside `averaged_weights()`.'''
         from PIL import Image
         import torch
-        from . import cityscapes_eval as ce, reliability as rel
+        from . import reliability as rel
         if self.num_classes != 20:
             raise ValueError("the Cityscapes evaluation uses the 20 Cityscapes train ids; this model has {} classes.".format(self.num_classes))
         ts_mod.validate_fit(passes, candidates, t_min, t_max)
-        route = 'passes' if scales is not None or bool(flip) or crf_mod.resolve(crf) is not None else 'single'
-        gts = sorted(glob(ground_truth_search))
-        if not gts:
-            raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
-        walk = ce.walk_predictions(images_dir)
-        paths = [ce.find_prediction(images_dir, g, walk, extension=image_file_extension) for g in gts]
+        route = sweeps.resolve_route(self, scales, flip, crf)
+        gts, paths = sweeps.paired_files(images_dir, ground_truth_search, image_file_extension)
         dev = self.engine.device
-        kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
         lut = rel.cityscapes_lut()
         nb = [0]
 
@@ -998,58 +929,21 @@ class FCN8s:
             tr = trange(len(gts), file=sys.stdout)
             tr.set_description('Fitting temperature')
             for i in tr:
-                image = torch.from_numpy(np.array(Image.open(paths[i]).convert('RGB'))[None]).to(dev)
-                if route == 'passes':
-                    prob = self.predict(image, argmax=False, scales=scales, flip=flip, **kw)
-                else:
-                    prob = self.engine.predict_mc(image, samples=1, keep_prob=1.0, sample_offset=0, argmax=False, entropy=False,
-                                                  mutual_information=False)[0]
+                prob = route.softmax(sweeps.load_image(paths[i], False, dev)[0])[0]
                 gt = np.array(Image.open(gts[i]))
-                if prob.shape[2] != gt.shape[1]:
-                    raise ValueError("Image widths of " + paths[i] + " and " + gts[i] + " are not equal.")
-                if prob.shape[1] != gt.shape[0]:
-                    raise ValueError("Image heights of " + paths[i] + " and " + gts[i] + " are not equal.")
-                if gt.ndim != 2 or gt.max() >= ce.NUM_IDS:
-                    raise ValueError("Unknown label with id {:}".format(int(gt.max())))
+                sweeps.check_label_map(gt, prob.shape[1:3], paths[i], gts[i])
                 fitter.add(prob, torch.from_numpy(gt.astype(np.uint8)[None]).to(dev))
                 nb[0] += gt.size
             return fitter.result()
 
-        self.engine.freeze(True)
-        try:
+        with sweeps.frozen(self.engine):
             res = ts_mod.fit(sweep, passes=passes, candidates=candidates, t_min=t_min, t_max=t_max)
-        finally:
-            self.engine.freeze(False)
         res["nbPixels"] = nb[0]
-        res["route"] = route
+        res["route"] = route.name
         self.temperature = res["temperature"]
         if json_path is not None:
             ts_mod.write_result_json(res, json_path)
         return res
-
-    def _pseudo_label_route(self, scales, flip, crf, temperature, samples, keep_prob, mi_max):
-        '''The prediction route of the two pseudo-label sweeps, with `evaluate_reliability`'s refusals: (name, predict) where
-        `predict(image)` takes a uint8 device tensor (1,H,W,3) and returns (softmax on the device, score map | None).'''
-        if temperature is not None:
-            temperature = ts_mod.validate_temperature(temperature)
-        passes = scales is not None or bool(flip) or crf_mod.resolve(crf) is not None
-        pl_mod.validate(self.num_classes, samples=samples, mi_max=mi_max, temperature=temperature, passes=passes)
-        kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
-        if samples is not None:
-            def predict(image):
-                prob, _, mi = self.engine.predict_mc(image, samples=samples, keep_prob=keep_prob, sample_offset=0, argmax=False, entropy=False,
-                                                     mutual_information=mi_max is not None)
-                return prob, mi
-            return 'mc', predict
-        if passes:
-            return 'passes', lambda image: (self.predict(image, argmax=False, scales=scales, flip=flip, temperature=temperature, **kw), None)
-
-        def single(image):              # as in evaluate_reliability: one sample without dropout is `predict` bit for bit, on images of any size
-            prob = self.engine.predict_mc(image, samples=1, keep_prob=1.0, sample_offset=0, argmax=False, entropy=False, mutual_information=False)[0]
-            if temperature is not None and temperature != 1.0:
-                self.engine.temperature_apply(prob, temperature, out=prob)
-            return prob, None
-        return 'single', single
 
     def fit_pseudo_label_thresholds(self, images_dir, portion=0.2, t_min=0.0, t_max=None, scales=None, flip=False, crf=None, temperature=None,
                                     samples=None, keep_prob=0.5, mi_max=None, resize=False, image_file_extension='png', json_path=None):
@@ -1067,34 +961,23 @@ class FCN8s:
         the export sweep keeps exactly the histogram's tail.  Returns dict(thresholds float32[C], bins int64[C], hist, counts, misc, summary,
         nbImages, route) and keeps the thresholds in `self.pseudo_label_thresholds`; they belong to this directory, not to the model:
         `save` does not store them.  `json_path`: also write the result.  Works inside `averaged_weights()`.'''
-        from PIL import Image
-        import torch
         pl_mod.validate(self.num_classes, portion=portion, t_min=t_min, t_max=t_max)
-        route, predict = self._pseudo_label_route(scales, flip, crf, temperature, samples, keep_prob, mi_max)
-        paths = sorted(glob(os.path.join(images_dir, '**', '*.' + image_file_extension), recursive=True))
-        if not paths:
-            raise ValueError("Cannot find any images below: {}".format(images_dir))
+        route = sweeps.resolve_route(self, scales, flip, crf, temperature, samples, keep_prob, mi_max=mi_max)
+        paths = sweeps.image_files(images_dir, image_file_extension)
         dev = self.engine.device
         tables = None
         tr = trange(len(paths), file=sys.stdout)
         tr.set_description('Fitting pseudo-label thresholds')
-        was_frozen = bool(self.engine.get_option("frozen"))
-        self.engine.freeze(True)
-        try:
+        with sweeps.frozen(self.engine):
             for i in tr:
-                pil = Image.open(paths[i]).convert('RGB')
-                if resize and not np.array_equal((pil.height, pil.width), resize):
-                    pil = pil.resize((resize[1], resize[0]), Image.BILINEAR)
-                prob, score = predict(torch.from_numpy(np.array(pil)[None]).to(dev))
-                _, tables = self.engine.pseudo_label(prob, score=score, score_max=mi_max if score is not None else None, labels=False, tables=tables)
-        finally:
-            self.engine.freeze(was_frozen)
+                prob, _, score = route.softmax(sweeps.load_image(paths[i], resize, dev)[0], mutual_information=mi_max is not None)
+                _, tables = self.engine.pseudo_label(prob, score=score, score_max=mi_max, labels=False, tables=tables)
         host = pl_mod.tables_to_host(tables, self.num_classes)
         thr, bins = pl_mod.thresholds_from_hist(host["hist"], portion, t_min=t_min, t_max=t_max)
         kept = pl_mod.tail_sums(host["hist"], bins)                     # what the export sweep keeps at these thresholds
         expected = np.stack([kept, host["counts"].sum(1) - kept], 1)
         res = dict(thresholds=thr, bins=bins, hist=host["hist"], counts=host["counts"], misc=host["misc"],
-                   summary=pl_mod.summary(host["hist"], expected, host["misc"], thr), nbImages=len(paths), route=route)
+                   summary=pl_mod.summary(host["hist"], expected, host["misc"], thr), nbImages=len(paths), route=route.name)
         self.pseudo_label_thresholds = thr
         if json_path is not None:
             pl_mod.write_result_json(res, json_path)
@@ -1131,10 +1014,8 @@ class FCN8s:
                 raise ValueError("no thresholds: pass `thresholds` or run `fit_pseudo_label_thresholds` first.")
         v = pl_mod.validate(self.num_classes, thresholds=thresholds, ignore_id=ignore_id, id_space=id_space, base_search=base_search, base_fill=base_fill,
                             resize=resize)
-        route, predict = self._pseudo_label_route(scales, flip, crf, temperature, samples, keep_prob, mi_max)
-        paths = sorted(glob(os.path.join(images_dir, '**', '*.' + image_file_extension), recursive=True))
-        if not paths:
-            raise ValueError("Cannot find any images below: {}".format(images_dir))
+        route = sweeps.resolve_route(self, scales, flip, crf, temperature, samples, keep_prob, mi_max=mi_max)
+        paths = sweeps.image_files(images_dir, image_file_extension)
         bases = None
         if base_search is not None:
             found = sorted(glob(base_search))
@@ -1152,15 +1033,10 @@ class FCN8s:
         images = []
         tr = trange(len(paths), file=sys.stdout)
         tr.set_description('Exporting pseudo-labels')
-        was_frozen = bool(self.engine.get_option("frozen"))
-        self.engine.freeze(True)
-        try:
+        with sweeps.frozen(self.engine):
             for i in tr:
-                pil = Image.open(paths[i]).convert('RGB')
-                size = pil.size
-                if resize and not np.array_equal((pil.height, pil.width), resize):
-                    pil = pil.resize((resize[1], resize[0]), Image.BILINEAR)
-                prob, score = predict(torch.from_numpy(np.array(pil)[None]).to(dev))
+                image, size = sweeps.load_image(paths[i], resize, dev)
+                prob, _, score = route.softmax(image, mutual_information=mi_max is not None)
                 base = None
                 if bases is not None:
                     bm = np.array(Image.open(bases[i]))
@@ -1170,7 +1046,7 @@ class FCN8s:
                         raise ValueError("Image sizes of " + paths[i] + " and " + bases[i] + " are not equal.")
                     base = torch.from_numpy(bm[None]).to(dev)
                 labels, _ = self.engine.pseudo_label(prob, thresholds=thr, out_ids=oid, ignore_id=v["ignore_id"], base=base, base_fill=v["base_fill"],
-                                                     score=score, score_max=mi_max if score is not None else None, labels=True, tables=tables)
+                                                     score=score, score_max=mi_max, labels=True, tables=tables)
                 out = Image.fromarray(labels[0].cpu().numpy())
                 now = flat.cpu().numpy()
                 d, seen = now - seen, now
@@ -1179,19 +1055,16 @@ class FCN8s:
                 if out.size != size:
                     out = out.resize(size, Image.NEAREST)
                 out.save(os.path.join(results_dir, os.path.basename(paths[i])))
-        finally:
-            self.engine.freeze(was_frozen)
         res = pl_mod.summary(None, seen[:2 * Cn].reshape(Cn, 2), seen[2 * Cn:], v["thresholds"])
-        res.update(thresholds=v["thresholds"], images=images, nbImages=len(paths), route=route)
+        res.update(thresholds=v["thresholds"], images=images, nbImages=len(paths), route=route.name)
         if json_path is not None:
             pl_mod.write_result_json(res, json_path)
         return res
 
-    def _instance_route(self, connectivity, min_instance_pixels, samples, keep_prob, scales, flip, crf, temperature, min_region, region_connectivity,
+    def _instance_table(self, connectivity, min_instance_pixels, samples, keep_prob, scales, flip, crf, temperature, min_region, region_connectivity,
                         region_rounds):
-        '''The device path of the two instance-level sweeps: `table(image, inst)` takes a uint8 device tensor (1,H,W,3) and the image's
-        instance map (NumPy, or None) and returns (softmax, uint8 labels, int32 components, rows, bad) -- everything but the rows on the
-        device.  Routes and refusals are those of `evaluate_reliability`.'''
+        '''The arguments and the device path of the two instance-level sweeps: (route, table) where `table(image, inst, path)` takes a uint8
+        device tensor (1,H,W,3) and the image's instance map (NumPy, or None) and returns (int32 components on the device, rows).'''
         if self.num_classes != 20:
             raise ValueError("the Cityscapes evaluation uses the 20 Cityscapes train ids; this model has {} classes.".format(self.num_classes))
         regions_mod._check(connectivity)
@@ -1200,17 +1073,19 @@ class FCN8s:
         clean = regions_mod.resolve(min_region, self.num_classes)
         if clean is not None:
             regions_mod._check(region_connectivity, region_rounds)
-        route, predict = self._pseudo_label_route(scales, flip, crf, temperature, samples, keep_prob, None)
+        route = sweeps.resolve_route(self, scales, flip, crf, temperature, samples, keep_prob)
 
-        def table(image, inst):
-            prob, _score = predict(image)
+        def table(image, inst, path):
+            prob = route.softmax(image)[0]
             labels, _t = self.engine.pseudo_label(prob, labels=True)            # zero thresholds, the identity table: the argmax as uint8
             if clean is not None:
                 self.engine.regions_clean(labels, clean, connectivity=region_connectivity, rounds=region_rounds)
             comp, _area = self.engine.regions_label(labels, connectivity=connectivity, area=False)
             rows, bad = self.engine.instance_pair(prob, labels, comp, inst)
-            return prob, labels, comp, rows, bad
-        return route, table
+            if bad.any():
+                raise ValueError("{}: {} pixels hold a label outside 0..19 and {} a probability outside [0, 1]".format(path, int(bad[0, 0]), int(bad[0, 1])))
+            return comp, rows
+        return route.name, table
 
     def evaluate_cityscapes_instances(self, images_dir, ground_truth_search, connectivity=4, min_instance_pixels=0, samples=None, keep_prob=0.5,
                                       scales=None, flip=False, crf=None, temperature=None, min_region=None, region_connectivity=4, region_rounds=1,
@@ -1232,35 +1107,23 @@ class FCN8s:
         Caveat: connected components merge touching cars, so this AP measures the semantic model plus that rule -- a baseline and a speck
         detector, not an instance-segmentation method.'''
         from PIL import Image
-        import torch
-        from . import cityscapes_eval as ce, instances as ins
-        route, table = self._instance_route(connectivity, min_instance_pixels, samples, keep_prob, scales, flip, crf, temperature, min_region,
+        from . import instances as ins
+        route, table = self._instance_table(connectivity, min_instance_pixels, samples, keep_prob, scales, flip, crf, temperature, min_region,
                                             region_connectivity, region_rounds)
-        gts = sorted(glob(ground_truth_search))
-        if not gts:
-            raise ValueError("Cannot find any ground truth images to use for evaluation. Searched for: {}".format(ground_truth_search))
-        walk = ce.walk_predictions(images_dir)
-        paths = [ce.find_prediction(images_dir, g, walk, extension=image_file_extension) for g in gts]
-        dev = self.engine.device
+        gts, paths = sweeps.paired_files(images_dir, ground_truth_search, image_file_extension)
         stats = ins.new_stats()
         pixels = 0
         tr = trange(len(gts), file=sys.stdout)
         tr.set_description('Evaluating')
-        was_frozen = bool(self.engine.get_option("frozen"))
-        self.engine.freeze(True)
-        try:
+        with sweeps.frozen(self.engine):
             for i in tr:
-                image = torch.from_numpy(np.array(Image.open(paths[i]).convert('RGB'))[None]).to(dev)
+                image = sweeps.load_image(paths[i], False, self.engine.device)[0]
                 inst = np.array(Image.open(gts[i]))
                 if inst.ndim != 2 or inst.shape != tuple(image.shape[1:3]):
                     raise ValueError("Image sizes of " + paths[i] + " and " + gts[i] + " are not equal.")
-                _prob, _labels, _comp, rows, bad = table(image, inst[None])
-                if bad.any():
-                    raise ValueError("{}: {} pixels hold a label outside 0..19 and {} a probability outside [0, 1]".format(paths[i], int(bad[0, 0]), int(bad[0, 1])))
+                _comp, rows = table(image, inst[None], paths[i])
                 ins.stats_add(stats, rows[0], min_instance_pixels)
                 pixels += inst.size
-        finally:
-            self.engine.freeze(was_frozen)
         res = ins.results(stats)
         res["nbPixels"] = pixels
         res["route"] = route
@@ -1278,54 +1141,39 @@ class FCN8s:
         without ground truth; the component map (4 bytes per pixel) and the table rows are downloaded, the softmax is not.
         `instances.evaluate_directory` on this export gives the dict of `evaluate_cityscapes_instances` with the same arguments.  Returns
         dict(files = the text files in image order, nbImages, nbInstances, route).'''
-        from PIL import Image
-        import torch
         from . import instances as ins
-        route, table = self._instance_route(connectivity, min_instance_pixels, samples, keep_prob, scales, flip, crf, temperature, min_region,
+        route, table = self._instance_table(connectivity, min_instance_pixels, samples, keep_prob, scales, flip, crf, temperature, min_region,
                                             region_connectivity, region_rounds)
-        paths = sorted(glob(os.path.join(images_dir, '**', '*.' + image_file_extension), recursive=True))
-        if not paths:
-            raise ValueError("Cannot find any images below: {}".format(images_dir))
+        paths = sweeps.image_files(images_dir, image_file_extension)
         if overwrite_existing and os.path.exists(results_dir):
             shutil.rmtree(results_dir)
         os.makedirs(results_dir, exist_ok=True)
-        dev = self.engine.device
         files, count = [], 0
         tr = trange(len(paths), file=sys.stdout)
         tr.set_description('Exporting instances')
-        was_frozen = bool(self.engine.get_option("frozen"))
-        self.engine.freeze(True)
-        try:
+        with sweeps.frozen(self.engine):
             for i in tr:
-                image = torch.from_numpy(np.array(Image.open(paths[i]).convert('RGB'))[None]).to(dev)
-                _prob, _labels, comp, rows, bad = table(image, None)
-                if bad.any():
-                    raise ValueError("{}: {} pixels hold a label outside 0..19 and {} a probability outside [0, 1]".format(paths[i], int(bad[0, 0]), int(bad[0, 1])))
+                comp, rows = table(sweeps.load_image(paths[i], False, self.engine.device)[0], None, paths[i])
                 files.append(ins.write_export(results_dir, os.path.splitext(os.path.basename(paths[i]))[0], comp[0].cpu().numpy(), rows[0], min_instance_pixels))
                 with open(files[-1]) as f:
                     count += sum(1 for _line in f)
-        finally:
-            self.engine.freeze(was_frozen)
         return dict(files=files, nbImages=len(paths), nbInstances=count, route=route)
 
     def _segment_file(self, filepath, results_dir, color_map, resize, include_unprocessed_image, arrangement, scales=None, flip=False, crf=None,
                       regions=None):
         '''Loop body of predict_and_save (fcn8s_tensorflow.py:829-855).'''
         from PIL import Image
-        pil = Image.open(filepath).convert('RGB')
-        if resize and not np.array_equal((pil.height, pil.width), resize):
-            pil = pil.resize((resize[1], resize[0]), Image.BILINEAR)
-        image = np.asarray(pil)
+        image = sweeps.load_image(filepath, resize, 'cpu')[0][0].numpy()
         img_height, img_width, img_ch = image.shape
 
-        kw = dict(crf=crf) if crf_mod.resolve(crf) is not None else {}
         if regions is None:
-            prediction = self.predict([image], argmax=False, scales=scales, flip=flip, **kw)
+            prediction = self.predict([image], argmax=False, scales=scales, flip=flip, crf=crf)
         else:                                   # the cleaned argmax map, one-hot: the overlay takes its argmax
-            prediction = np.eye(self.num_classes, dtype=np.float32)[self.predict([image], argmax=True, scales=scales, flip=flip, **kw, **regions)]
+            prediction = np.eye(self.num_classes, dtype=np.float32)[self.predict([image], argmax=True, scales=scales, flip=flip, crf=crf, **regions)]
         processed = print_segmentation_onto_image(image=image, prediction=prediction, color_map=color_map)
 
         if include_unprocessed_image:
+            pil = Image.fromarray(image)
             if arrangement == 'vertical':
                 canvas = Image.new('RGB', (img_width, 2 * img_height))
                 canvas.paste(processed, (0, 0)); canvas.paste(pil, (0, img_height))

@@ -19,6 +19,8 @@ from fractions import Fraction
 
 import numpy as np
 
+from . import sweeps
+
 BINS = 1024                  # FCN8S_PL_BINS
 TILE_PIXELS = 256            # FCN8S_PL_TILE_PIXELS: pixels per block and trip of the kernel
 MAX_BLOCKS = 512             # FCN8S_PL_MAX_BLOCKS: beyond TILE_PIXELS * MAX_BLOCKS pixels a block takes a second trip
@@ -230,17 +232,7 @@ def validate(num_classes, portion=0.2, t_min=0.0, t_max=None, thresholds=None, i
         base_fill = _check_id(base_fill, "base_fill")
         if resize:
             raise ValueError("`base_search` with `resize`: the base maps have the files' size, the prediction the resized one")
-    if samples is not None and passes:
-        raise ValueError("`samples` runs the Monte-Carlo dropout route, which has no `scales` / `flip` / `crf` passes; use one or the other.")
-    if samples is not None and temperature is not None:
-        raise ValueError("`temperature` with `samples`: calibrating Monte-Carlo samples needs the temperature inside each sample's softmax; "
-                         "use the single-pass, `scales` / `flip` or `crf` route instead.")
-    if mi_max is not None:
-        if samples is None:
-            raise ValueError("`mi_max` gates on the mutual information of the Monte-Carlo route: it needs `samples`")
-        if not math.isfinite(float(mi_max)):
-            raise ValueError("`mi_max` must be finite, got {!r}".format(mi_max))
-        mi_max = float(mi_max)
+    mi_max = sweeps.check_route(passes, samples, temperature, mi_max)
     return dict(portions=por, bins_range=rng, thresholds=thr, ignore_id=ignore_id, base_fill=base_fill, mi_max=mi_max)
 
 
