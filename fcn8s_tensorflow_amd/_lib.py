@@ -20,6 +20,7 @@ COMM_ID_BYTES = 128
 NUM_STAGE_SLOTS = 3
 PREC_F32, PREC_BF16_FC, PREC_F32X3, PREC_BF16_FWD, PREC_F32X2, PREC_BF16_FWD_X2, PREC_BF16_TRAIN = 0, 1, 2, 3, 4, 5, 6
 PREC_FP8_INFER = 7
+ENT_UNLABELED, ENT_VALID, ENT_ALL = 0, 1, 2   # fcn8s_set_entropy_term's pixel sets
 FP8_LAYERS = 14   # inputs of conv1_2 .. conv5_3, fc6, fc7, in that order
 
 
@@ -98,6 +99,10 @@ SIGNATURES = {
     "fcn8s_set_soft_targets": (_i, [_p, _f, _f, _i]),
     "fcn8s_bind_soft_targets": (_i, [_p, _p, _i, _i, _i, _i, _i64]),
     "fcn8s_get_soft_target_term": (_i, [_p, _fp]),
+    "fcn8s_set_entropy_term": (_i, [_p, _f, _i, _i, _i]),
+    "fcn8s_get_entropy_term": (_i, [_p, _fp]),
+    "fcn8s_op_entropy_term_work_bytes": (_sz, []),
+    "fcn8s_op_entropy_term": (_i, [_p, _p, _p, _p, _i, _i64, _i, _i, _i, _i, _f, _p, _sz, _p, _p]),
     "fcn8s_eval_step": (_i, [_p, _p, _i, _p, _i, _i, _i, _f, _i]),
     "fcn8s_metrics_reset": (_i, [_p]),
     "fcn8s_metrics_get": (_i, [_p, _dp, _dp, _dp]),

@@ -266,6 +266,14 @@ double soft_targets_bytes(long long npix, int C, int K);      // the algorithmic
 void launch_soft_targets(const float* logits, float* dlogits, const float* probs, const uint8_t* labels, const PixMap* map, int N, long long npix, int C,
                          int K, long long row_stride, float lambda, float temperature, int all_pixels, char* ws, float* loss, float* term,
                          float* lastbias, hipStream_t s);
+// ---- the entropy term (entropy_min.hip; fcn8s_set_entropy_term, fcn8s_op_entropy_term in include/fcn8s_hip.h) --------------------------
+// One launch behind the soft-target term: dlogits (plain [npix, C] or blocked, map; null: not touched) += coef (-s (ls + h_p)) over the pixels of U
+// and the columns < K, then one small kernel: term[0] = L_ent, loss[0] += weight L_ent (null: the op), bias[c] += (bias_add) or = the contribution's
+// column sums, c < C (null: none).  ws: entropy_term_scratch_bytes() of per-block partials, 8-byte aligned.  2 <= K <= C <= 64.
+size_t entropy_term_scratch_bytes();
+double entropy_term_bytes(long long npix, int C);             // the algorithmic bytes (profile group "entropy_term")
+void launch_entropy_term(const float* logits, float* dlogits, const uint8_t* labels, const PixMap* map, int N, long long npix, int C, int K, int pixel_set,
+                         int first_image, float weight, char* ws, float* loss, float* term, float* bias, int bias_add, hipStream_t s);
 void launch_softmax_argmax(const float* logits, float* softmax_out, long long* argmax_out,
                            long long npix, int C, hipStream_t s, const PixMap* map = nullptr, int N = 0);
 // ---- the k = 2s transposed conv as one GEMM (see PixMap): operand / result re-layouts, all tiny next to the GEMMs -------------

@@ -248,6 +248,11 @@ struct fcn8s_model {
     float kd_w = 0.f, kd_T = 1.f; int kd_all = 0; bool have_kd = false;
     const float* kd_probs = nullptr; int kd_N = 0, kd_H = 0, kd_W = 0, kd_K = 0; long long kd_stride = 0;
     DeviceBuf<char> kd_ws;
+    // fcn8s_set_entropy_term: L += ent_w * L_ent over the pixel set ent_set of the images >= ent_first, ent_K logical classes; ent_w == 0: off.
+    // ent_ws = the per-block partials, grown on first use (a "workspace_allocation"); the term lands in d_terms[4]; have_ent: the last training
+    // loss ran with the term
+    float ent_w = 0.f; int ent_set = 0, ent_K = 0, ent_first = 0; bool have_ent = false;
+    DeviceBuf<char> ent_ws;
     // fcn8s_accumulate_bucket: the accumulator (total floats, the gradient buffer's buckets; grown at the first fold -- a "workspace_allocation" --
     // and kept until the model goes), per bucket the micro-batches folded and not yet flushed, and whether this backward pass's bucket was taken
     DeviceBuf<float> d_acc; int acc_k[FCN8S_MAX_BUCKETS] = {0}; bool acc_taken[FCN8S_MAX_BUCKETS] = {false};
@@ -2237,6 +2242,17 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
                             m->C, m->kd_K, m->kd_stride, m->kd_w, m->kd_T, m->kd_all, m->kd_ws, m->d_loss, m->d_terms + 3, m->d_lastbias, s);
         m->have_kd = true;
     }
+    if (with_grad) m->have_ent = false;
+    if (with_grad && m->ent_w != 0.f) {
+        // L_ent and its gradient on the student's own prediction: dlogits += ent_w d L_ent / d logits, then the loss, the term and the bias column
+        // sums -- all in front of the loss copy below
+        if (!m->ent_ws.grow(entropy_term_scratch_bytes(), s, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "the entropy term's scratch cannot be allocated");
+        ProfScope ps(m, "entropy_term", 0, entropy_term_bytes(npix, m->C));
+        const bool blk = m->tconv_gemm && m->logits_b;
+        launch_entropy_term(blk ? m->logits_b : A(m, "logits"), blk ? m->dlogits_b : m->dlogits, lab_dev, blk ? &m->pm : nullptr, m->N, npix, m->C, m->ent_K,
+                            m->ent_set, m->ent_first, m->ent_w, m->ent_ws, m->d_loss, m->d_terms + 4, m->d_lastbias, 1, s);
+        m->have_ent = true;
+    }
     // The loss is final here, a third of the way into a training step: queue its copy now, so that fcn8s_read_loss waits for this
     // point of the stream only and the host can go on queueing the next step while the backward pass runs (the reference fetches
     // the loss every step, fcn8s_tensorflow.py:554-578; waiting for the whole stream left the GPU idle for ~2 ms per step).
@@ -2513,7 +2529,7 @@ int fcn8s_create(const fcn8s_config* cfg, fcn8s_model** out)
         if (m->fc6k == 7) m->ufl = std::max(m->ufl, fc6_bank_floats(m->widths[4], m->widths[5]));
         dev(m->d_wino_u, m->ufl);
     }
-    dev(m->d_loss, 2 + 64 + 4, true);
+    dev(m->d_loss, 2 + 64 + 5, true);
     m->d_regsum = m->d_loss + 1; m->d_lastbias = m->d_loss + 2; m->d_terms = m->d_loss + 2 + 64;
     dev(m->d_conf, cc, true); dev(m->d_fp, 1);
     m->tg_kp = (4 * m->C + 63) / 64 * 64;
@@ -3536,6 +3552,30 @@ int fcn8s_get_soft_target_term(fcn8s_model* m, float* kd)
     HIPCHK(m, hipStreamSynchronize(m->stream));
     HIPCHK(m, hipMemcpy(&t, m->d_terms + 3, sizeof t, hipMemcpyDeviceToHost));
     if (kd) *kd = t;
+    return FCN8S_OK;
+}
+
+int fcn8s_set_entropy_term(fcn8s_model* m, float weight, int pixel_set, int ncols, int first_image)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!std::isfinite(weight)) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_entropy_term: the weight must be finite");
+    if (pixel_set < 0 || pixel_set > 2) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_entropy_term: pixel_set must be 0 (unlabeled), 1 (valid) or 2 (all)");
+    if (ncols < 2 || ncols > m->C) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_entropy_term: ncols must be in 2 .. num_classes (" + std::to_string(m->C) + ")");
+    if (first_image < 0) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_entropy_term: first_image must be >= 0");
+    if (weight == 0.f) { m->ent_w = 0.f; m->ent_set = 0; m->ent_K = 0; m->ent_first = 0; m->have_ent = false; return FCN8S_OK; }    // off
+    if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_set_entropy_term");
+    m->ent_w = weight; m->ent_set = pixel_set; m->ent_K = ncols; m->ent_first = first_image;
+    return FCN8S_OK;
+}
+
+int fcn8s_get_entropy_term(fcn8s_model* m, float* term)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!m->have_ent) return fail(m, FCN8S_ERR_STATE, "fcn8s_get_entropy_term: the last training loss ran without the entropy term");
+    float t = 0.f;
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(&t, m->d_terms + 4, sizeof t, hipMemcpyDeviceToHost));
+    if (term) *term = t;
     return FCN8S_OK;
 }
 
@@ -4598,6 +4638,25 @@ int fcn8s_op_class_mix(void* stream, const uint8_t* images, const uint8_t* label
                 return fail(nullptr, FCN8S_ERR_BAD_ARG, "class_mix: an output overlaps an input");
     take_deferred_error(nullptr);
     launch_class_mix(images, labels, src, N, P, C, seed, draw, work, out_images, out_labels, selected_out, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
+size_t fcn8s_op_entropy_term_work_bytes(void) { return entropy_term_scratch_bytes() + 8; }      // (+ 8: the partials start at the next multiple of 8)
+int fcn8s_op_entropy_term(void* stream, const float* logits, float* dlogits, const uint8_t* labels, int N, int64_t HW, int C, int ncols, int pixel_set,
+                          int first_image, float weight, void* work, size_t work_bytes, float* term_out, float* bias_out)
+{
+    if (!logits || !labels || !work || !term_out) return fail(nullptr, FCN8S_ERR_BAD_ARG, "entropy_term: null logits, labels, work or term_out");
+    if ((((uintptr_t)logits | (uintptr_t)dlogits | (uintptr_t)term_out | (uintptr_t)bias_out) & 3) != 0)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "entropy_term: logits, dlogits, term_out and bias_out must be 4-byte aligned");
+    if (!std::isfinite(weight)) return fail(nullptr, FCN8S_ERR_BAD_ARG, "entropy_term: the weight must be finite");
+    if (C < 2 || C > 64) return fail(nullptr, FCN8S_ERR_BAD_ARG, "entropy_term: C must be in 2 .. 64");
+    if (pixel_set < 0 || pixel_set > 2 || ncols < 2 || ncols > C || first_image < 0)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "entropy_term: pixel_set must be 0, 1 or 2, ncols in 2 .. C and first_image >= 0");
+    if (N <= 0 || HW <= 0 || HW > (int64_t)((1LL << 40) / N)) return fail(nullptr, FCN8S_ERR_SHAPE, "entropy_term: N and HW must be positive (and N * HW below 2^40)");
+    if (work_bytes < fcn8s_op_entropy_term_work_bytes()) return fail(nullptr, FCN8S_ERR_BAD_ARG, "entropy_term: work is smaller than fcn8s_op_entropy_term_work_bytes()");
+    char* ws = (char*)(((uintptr_t)work + 7) & ~(uintptr_t)7);
+    take_deferred_error(nullptr);
+    launch_entropy_term(logits, dlogits, labels, nullptr, N, (long long)N * HW, C, ncols, pixel_set, first_image, weight, ws, nullptr, term_out, bias_out, 0,
+                        (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
 size_t fcn8s_op_strong_augment_work_bytes(int N) { return strong_augment_work_bytes(N); }

@@ -133,6 +133,7 @@ class Engine:
         self.boundary_config = None          # set_boundary_loss: the boundary weighting's configuration, dict(table, radius) (None = off)
         self.soft_target_config = None       # set_soft_targets: the soft-target term's configuration, dict(weight, temperature, pixels) (None = off)
         self._soft_targets = None            # bind_soft_targets: the bound tensor, kept alive until a training loss has consumed it
+        self.entropy_config = None           # set_entropy_term: the entropy term's configuration, dict(weight, pixels, first_image) (None = off)
         self._loss_shape = None              # (N, H, W) of the last training loss (boundary_codes)
         self.grad_clip = None                # set_grad_clip: the global-norm clip's max_norm (None = off; inf = the non-finite guard alone)
         self.ema_config = None               # set_ema: the parameter average's configuration, dict(decay, warmup) (None = off)
@@ -523,6 +524,55 @@ class Engine:
         kd = C.c_float()
         L.check(L.lib.fcn8s_get_soft_target_term(self.h, C.byref(kd)), self.h)
         return float(kd.value)
+
+    def set_entropy_term(self, weight=None, pixels='unlabeled', first_image=0):
+        """The entropy term of the training loss (fcn8s_set_entropy_term; definitions in include/fcn8s_hip.h, restated in loss.py):
+        L += weight * L_ent, L_ent = (1 / (P log K)) sum_{p in U} h_p, h_p the entropy of the student's own softmax over the K =
+        `logical_classes` classes; U = the pixels of the images >= `first_image` that have no label (`pixels` = 'unlabeled': id >= num_classes),
+        a label ('valid') or either ('all').  A positive weight minimises the entropy (Grandvalet & Bengio 2005; ADVENT's MinEnt), a negative
+        one is the confidence penalty (Pereyra et al. 2017).  No weight (or 0) switches the term off.  Host state only: nothing is launched,
+        allocated or waited for.  Evaluation and prediction keep the reference's loss."""
+        w, ps, first = loss_mod.validate_entropy_term(weight, pixels, first_image)
+        if w != 0.0 and self.logical_classes < 2:
+            raise ValueError("the entropy term needs at least 2 classes, the model has %d" % self.logical_classes)
+        L.check(L.lib.fcn8s_set_entropy_term(self.h, w, ps, self.logical_classes if w != 0.0 else self.num_classes, first), self.h)
+        self.entropy_config = None if w == 0.0 else dict(weight=w, pixels=pixels, first_image=first)
+
+    def entropy_term(self):
+        """The unscaled L_ent of the last training loss (fcn8s_get_entropy_term; synchronises); raises if that loss ran without the term."""
+        v = C.c_float()
+        L.check(L.lib.fcn8s_get_entropy_term(self.h, C.byref(v)), self.h)
+        return float(v.value)
+
+    def entropy_term_op(self, logits, labels, weight=1.0, pixels='unlabeled', ncols=None, first_image=0, dlogits=None, bias=False):
+        """One `fcn8s_op_entropy_term` call on device tensors, on the current stream: `logits` float32 [N, ..., C] (contiguous), `labels` uint8
+        [N, ...] of the same pixels.  `dlogits` (a float32 tensor of the logits' shape, or None) gets the gradient contribution added in
+        place.  Returns (term, bias | None): device tensors of 1 and (with `bias`) C floats; nothing synchronises.  The scratch is kept on the
+        engine."""
+        torch = self.torch
+        w, ps, first = loss_mod.validate_entropy_term(weight, pixels, first_image)
+        if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() < 2 or not logits.is_contiguous():
+            raise ValueError("logits have to be a contiguous float32 tensor [N, ..., C] on the GPU")
+        if not isinstance(labels, torch.Tensor) or labels.device != logits.device or labels.dtype != torch.uint8 or not labels.is_contiguous() \
+                or tuple(labels.shape) != tuple(logits.shape[:-1]):
+            raise ValueError("labels have to be a contiguous uint8 tensor of the logits' pixels on the same device")
+        if dlogits is not None and (not isinstance(dlogits, torch.Tensor) or dlogits.device != logits.device or dlogits.dtype != torch.float32
+                                    or tuple(dlogits.shape) != tuple(logits.shape) or not dlogits.is_contiguous()):
+            raise ValueError("dlogits have to be a contiguous float32 tensor of the logits' shape on the same device")
+        N, Cn = int(logits.shape[0]), int(logits.shape[-1])
+        HW = int(labels.numel()) // max(N, 1)
+        nbytes = int(L.lib.fcn8s_op_entropy_term_work_bytes())
+        work = getattr(self, "_entropy_work", None)
+        if work is None or work.numel() < nbytes or work.device != logits.device:
+            work = self._entropy_work = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+        term = torch.empty(1, dtype=torch.float32, device=logits.device)
+        b = torch.empty(Cn, dtype=torch.float32, device=logits.device) if bias else None
+        stream = C.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)
+        L.check(L.lib.fcn8s_op_entropy_term(stream, C.c_void_p(logits.data_ptr()), C.c_void_p(dlogits.data_ptr()) if dlogits is not None else None,
+                                            C.c_void_p(labels.data_ptr()), N, HW, Cn, Cn if ncols is None else int(ncols), ps, first, w,
+                                            C.c_void_p(work.data_ptr()), nbytes, C.c_void_p(term.data_ptr()),
+                                            C.c_void_p(b.data_ptr()) if bias else None))
+        return term, b
 
     def loss_stats(self):
         """|V|, |K| and the threshold t of the last training loss (fcn8s_get_loss_stats; synchronises)."""

@@ -243,7 +243,10 @@ class FCN8s:
               unlabeled_predict=None,
               unlabeled_mix=True,
               unlabeled_seed=0,
-              unlabeled_augment=None):
+              unlabeled_augment=None,
+              entropy_weight=0.0,
+              entropy_pixels='unlabeled',
+              entropy_images='all'):
         '''Trains the model; arguments as fcn8s_tensorflow.py:424-503.  Summaries are written as TensorBoard
         event files (`<summaries_dir>/<summaries_name>[_eval]/events.out.tfevents.*`: total_loss, learning_rate and
         mean / stddev / max / min / histogram of the ten watched weight-bias pairs, :331-366) and, for reading
@@ -303,7 +306,19 @@ class FCN8s:
         `strong_augment.DEFAULTS` (colour jitter with probability 0.8 and strength 0.25 on brightness, contrast and saturation, hue within a
         quarter of +-90 units, Gaussian blur with probability 0.5, sigma in [0.15, 1.15] in 16 levels, radius 4 -- DACS's settings as
         recalled, not checked against its code); a dict overrides fields of those.  Without `unlabeled_generator` it raises.
-        Not done here: a separate weight on the unlabelled term (change M), CutMix boxes, geometric strong augmentation, augmenting or
+        `entropy_weight` adds the entropy of the student's own prediction to the loss for the duration of the call (Engine.set_entropy_term,
+        loss.py): entropy_weight / (P log K) * sum_{p in U} h_p over the K classes, P all pixels of the step's batch.  A positive weight is
+        entropy minimisation (Grandvalet & Bengio 2005; MinEnt of ADVENT, Vu et al. 2019, which uses 0.001 -- that paper's value as recalled,
+        not checked against its code), the one term that trains on a pixel without a label and needs no labeler, threshold or second model; a
+        negative weight is the confidence penalty on labelled pixels (Pereyra et al. 2017); 0, the default, is off: nothing is launched or
+        allocated and the step is bit for bit what it was.  `entropy_pixels`: 'unlabeled' (the pixels whose label id is >= num_classes: void
+        pixels, and under `unlabeled_generator` the pixels below their class threshold), 'valid' (the pixels with a label) or 'all'.
+        `entropy_images`: 'all' takes every image of the batch; 'unlabeled' needs `unlabeled_generator` (it raises otherwise) and restricts the
+        term to the M unlabelled images of the joined batch, so that the void pixels of the labelled images stay out.  It combines with
+        `teacher` and with every `unlabeled_*` keyword.  The engine's previous setting is restored when train() returns or raises.
+        `entropy_loss` (the unscaled term, the last micro-batch's) joins the recorded scalars on the steps that are recorded.
+        Not done here: a separate weight on the unlabelled term (change M), a per-class or per-pixel weight or a threshold on the entropy,
+        ADVENT's adversarial branch, CutMix boxes, geometric strong augmentation, augmenting or
         mixing the labelled images, and any change to `BatchGenerator`.'''
         if self.engine.precision == 'fp8_infer':
             raise ValueError("The 'fp8_infer' precision is inference only; switch the engine to another precision "
@@ -322,6 +337,7 @@ class FCN8s:
         teacher_fn = self._resolve_teacher(teacher, teacher_predict, distill_weight, distill_temperature, distill_pixels)
         unlabeled = self._resolve_unlabeled(unlabeled_generator, unlabeled_labeler, unlabeled_thresholds, unlabeled_predict, unlabeled_mix,
                                             unlabeled_seed, teacher, bool(ema_d), unlabeled_augment)
+        entropy = self._resolve_entropy(entropy_weight, entropy_pixels, entropy_images, unlabeled_generator)
         if eval_dataset not in ('train', 'val'):
             raise ValueError("`eval_dataset` must be one of 'train' or 'val', but is '{}'.".format(eval_dataset))
         if eval_dataset == 'val' and (val_generator is None or val_steps is None):
@@ -350,6 +366,7 @@ class FCN8s:
         prev_clip = self.engine.grad_clip
         prev_ema = self.engine.ema_config
         prev_soft = self.engine.soft_target_config
+        prev_entropy = self.engine.entropy_config
         teacher_engine = teacher.engine if (teacher_fn is not None and isinstance(teacher, FCN8s)) else None
         teacher_was_frozen = bool(teacher_engine.get_option("frozen")) if teacher_engine is not None else False
         labeler_engine = unlabeled.labeler_engine if unlabeled is not None else None
@@ -372,10 +389,14 @@ class FCN8s:
                 self.engine.set_lovasz(lovasz_weight, ce_weight, lovasz_per_image, lovasz_classes)
             if custom_boundary:
                 self.engine.set_boundary_loss(boundary_table, boundary_R)
+            if entropy is not None and not entropy['per_batch']:
+                self.engine.set_entropy_term(entropy['weight'], entropy['pixels'])
+            if unlabeled is not None:
+                unlabeled.entropy = entropy if (entropy is not None and entropy['per_batch']) else None
             for epoch in range(1, epochs + 1):
                 self._run_epoch(train_generator, steps_per_epoch, learning_rate_schedule, keep_prob, l2_regularization,
                                 'Epoch {}/{}'.format(epoch, epochs), training_loss_display_averaging,
-                                train_log, summaries_frequency, accumulation_steps, teacher_fn, unlabeled)
+                                train_log, summaries_frequency, accumulation_steps, teacher_fn, unlabeled, entropy is not None)
                 eval_epoch = epoch % eval_frequency == 0
 
                 if metrics and eval_epoch:
@@ -410,6 +431,8 @@ class FCN8s:
                 self.engine.set_lovasz(**(prev_lovasz or dict(lovasz_weight=0.0)))
             if custom_boundary:
                 self.engine.set_boundary_loss(**(prev_boundary or {}))
+            if entropy is not None:
+                self.engine.set_entropy_term(**(prev_entropy or {}))
             if teacher_fn is not None:
                 self.engine.set_soft_targets(**(prev_soft or {}))
                 if teacher_engine is not None:
@@ -450,6 +473,18 @@ class FCN8s:
         if monte_carlo:
             return lambda images: teacher.predict_uncertainty(images, argmax=False, **kw)[0]
         return lambda images: teacher.predict(images, argmax=False, **kw)
+
+    def _resolve_entropy(self, weight, pixels, images, unlabeled_generator):
+        '''train()'s entropy arguments -> None (weight 0: off) or dict(weight, pixels, per_batch): with `per_batch` (entropy_images =
+        'unlabeled') the term is set for every joined batch with first_image = the labelled batch's size.'''
+        w, _, _ = loss_mod.validate_entropy_term(weight, pixels, 0)
+        if images not in ('all', 'unlabeled'):
+            raise ValueError("`entropy_images` must be 'all' or 'unlabeled', got {!r}.".format(images))
+        if images == 'unlabeled' and unlabeled_generator is None:
+            raise ValueError("entropy_images='unlabeled' needs an `unlabeled_generator`: without one the batch has no unlabelled images.")
+        if not w:
+            return None
+        return dict(weight=w, pixels=pixels, per_batch=images == 'unlabeled')
 
     def _bind_teacher(self, teacher_fn, images):
         '''One batch under a teacher: the images on the device (uploaded once), the teacher's softmax of them bound as the next training
@@ -528,10 +563,12 @@ class FCN8s:
             u, pseudo = self.engine.class_mix(u, pseudo, seed=unl.seed, draw=draw)
         if unl.augment is not None:                                 # the student's view only: the labeler has seen the clean images
             u = self.engine.strong_augment(u, seed=unl.seed, draw=draw, jitter=unl.augment['jitter'], blur=unl.augment['blur'])
+        if unl.entropy is not None:                                 # the term on the M unlabelled images only (host state: nothing is launched)
+            self.engine.set_entropy_term(unl.entropy['weight'], unl.entropy['pixels'], first_image=nhw[0])
         return torch.cat([x, u]), torch.cat([ids, pseudo])
 
     def _run_epoch(self, generator, steps, schedule, keep_prob, l2_rate, title, window, log, log_every, accumulation_steps=1, teacher_fn=None,
-                   unlabeled=None):
+                   unlabeled=None, entropy=False):
         '''One epoch of train steps (fcn8s_tensorflow.py:542-590): a step runs with the schedule's value
         at the global step before it; `training_loss` is the mean over the last `window` steps.  With `accumulation_steps` = A > 1 a
         step is one update over A batches: A - 1 accumulated micro-batches, then the train step; its loss is the mean of the A losses.'''
@@ -567,6 +604,8 @@ class FCN8s:
                         extra.update(grad_norm=st['norm'], clip_coef=st['clip_coef'])
                     if teacher_fn is not None:                 # (the last micro-batch's term)
                         extra.update(distill_loss=self.engine.soft_target_term())
+                    if entropy:                                # (the last micro-batch's term)
+                        extra.update(entropy_loss=self.engine.entropy_term())
                     if unlabeled is not None:                  # (the last micro-batch's share; the download synchronises)
                         extra.update(pseudo_kept=float(unlabeled.tables['counts'][:, 0].sum().item()) / unlabeled.pixels)
                     log.add(self.g_step, total_loss=loss, learning_rate=lr, **extra)
@@ -1368,6 +1407,7 @@ class _Unlabeled:
 
     def __init__(self, **kw):
         self.pixels = 0
+        self.entropy = None          # train(entropy_images='unlabeled'): the term's weight and pixel set, set per joined batch
         self.__dict__.update(kw)
 
 

@@ -2,8 +2,8 @@
 a float64 restatement of both modes for the tests, and class-weight recipes computed from label counts on the host.  The Lovász-softmax
 term (fcn8s_set_lovasz) has its validation and float64 restatement behind the boundary-weighted cross-entropy
 (fcn8s_set_boundary_loss; fcn8s_op_boundary_distance, fcn8s_op_softmax_xent_px): its table builders, the NumPy route of its distance codes,
-its validation and the facade's argument rule (resolve_boundary).  The soft-target term (fcn8s_set_soft_targets) closes the file: its
-validation and its float64 and float32 restatements.
+its validation and the facade's argument rule (resolve_boundary).  The soft-target term (fcn8s_set_soft_targets) follows with its
+validation and its float64 and float32 restatements, and the entropy term (fcn8s_set_entropy_term) closes the file in the same way.
 
 P = pixels of the batch, V = the valid pixels (label id < C), l_p = the per-pixel loss m + log(sum exp(v - m)) - v[y_p] (>= 0),
 w_c = the class weights.
@@ -442,3 +442,88 @@ def soft_target_restate(logits, targets, labels, weight=1.0, temperature=1.0, pi
     if ft is np.float32:
         term = float(np.float32(term))
     return dict(term=term, loss=w * term, kd=kd, dlogits=d, bias=d.astype(np.float64).sum(0), used=used)
+
+
+# ---- the entropy term (fcn8s_set_entropy_term, fcn8s_op_entropy_term; the definition is in include/fcn8s_hip.h) --------------------------
+ENTROPY_PIXEL_SETS = ('unlabeled', 'valid', 'all')      # the index is the C ABI's pixel_set
+
+
+def validate_entropy_term(weight=None, pixels='unlabeled', first_image=0):
+    """-> (float32 weight (0.0 = off; negative = the confidence penalty), pixel_set 0/1/2, first_image); ValueError for what
+    fcn8s_set_entropy_term rejects.  `weight` None or 0 is "off"; `pixels` is 'unlabeled' (label id >= C), 'valid' (< C) or 'all'."""
+    if weight is None:
+        w = 0.0
+    else:
+        if isinstance(weight, bool):
+            raise ValueError("`weight` must be a number, got {!r}".format(weight))
+        try:
+            with np.errstate(over='ignore'):
+                w = float(np.float32(weight))
+        except (TypeError, ValueError):
+            raise ValueError("`weight` must be a number, got {!r}".format(weight))
+    if not math.isfinite(w):
+        raise ValueError("the entropy weight must be finite, got {!r}".format(weight))
+    if not isinstance(pixels, str) or pixels not in ENTROPY_PIXEL_SETS:
+        raise ValueError("`pixels` must be 'unlabeled', 'valid' or 'all', got {!r}".format(pixels))
+    if isinstance(first_image, bool) or not isinstance(first_image, (int, np.integer)) or not 0 <= int(first_image) < 1 << 31:
+        raise ValueError("`first_image` must be an integer in [0, 2^31), got {!r}".format(first_image))
+    return w, ENTROPY_PIXEL_SETS.index(pixels), int(first_image)
+
+
+def entropy_restate(logits, labels, weight=1.0, pixels='unlabeled', ncols=None, first_image=0, pixels_per_image=None, dtype=np.float64):
+    """The entropy term restated: logits (P, C), labels (P,) ids, K = `ncols` (default C) logical classes, U = the pixels of the images >=
+    `first_image` (an image = `pixels_per_image` consecutive pixels; None: the batch is one image) whose label is >= C ('unlabeled'), < C
+    ('valid') or anything ('all').  `dtype` float64: the definition in float64 (the reference of the tests); float32: every operation rounded
+    to float32 in the kernel's order (classes summed in order, no fused product), h_p summed in float64 -- its distance to the float64 result
+    is the scale of what fp32 can be asked for.
+    -> dict(term = L_ent, loss = weight * L_ent, h (P,) (0 outside U), dlogits (P, C) = coef (-s (b - m)), m = sum s b, bias (C,) = its column sums
+    (float64 sums), used (P,) bool)."""
+    w, pset, first = validate_entropy_term(weight, pixels, first_image)
+    ft = np.dtype(dtype).type
+    if ft not in (np.float64, np.float32):
+        raise ValueError("dtype must be float64 or float32")
+    z = np.asarray(logits)
+    if z.ndim != 2:
+        raise ValueError("`logits` must be (P, C), got %s" % (z.shape,))
+    P, C = z.shape
+    K = C if ncols is None else int(ncols)
+    if not 2 <= K <= C:
+        raise ValueError("`ncols` must be in 2..%d, got %r" % (C, ncols))
+    lab = np.asarray(labels).reshape(-1).astype(np.int64)
+    if lab.size != P:
+        raise ValueError("`labels` must hold one id per row of `logits` (%d), got %d" % (P, lab.size))
+    ppi = P if pixels_per_image is None else int(pixels_per_image)
+    if ppi < 1 or P % ppi:
+        raise ValueError("`pixels_per_image` must divide the number of pixels (%d), got %r" % (P, pixels_per_image))
+    used = np.arange(P) >= min(first, P // ppi) * ppi
+    if pset == 0:
+        used &= lab >= C
+    elif pset == 1:
+        used &= lab < C
+    z = z[:, :K].astype(ft)
+    den = float(P) * math.log(float(K))
+    coef = ft(np.float32(w / den)) if ft is np.float32 else ft(w / den)
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        b = (z - z.max(1, keepdims=True)).astype(ft)
+        e = np.exp(b).astype(ft)
+        S = np.zeros(P, ft)
+        for c in range(K):                                    # classes summed in order
+            S = (S + e[:, c]).astype(ft)
+        s = (e / S[:, None]).astype(ft)
+        ls = (b - np.log(S).astype(ft)[:, None]).astype(ft)
+        acc = np.zeros(P, ft)
+        for c in range(K):
+            acc = (acc + (s[:, c] * ls[:, c]).astype(ft)).astype(ft)
+        h = -acc
+        mb = np.zeros(P, ft)                                  # m_p = sum_c s_c b_c: ls_c + h_p is taken as b_c - m_p (see the header)
+        for c in range(K):
+            mb = (mb + (s[:, c] * b[:, c]).astype(ft)).astype(ft)
+        g = (coef * (-(s * (b - mb[:, None]).astype(ft)).astype(ft))).astype(ft)
+    h = np.where(used, h, ft(0.0))
+    g[~used] = 0.0
+    d = np.zeros((P, C), ft)
+    d[:, :K] = g
+    term = float(h.astype(np.float64).sum() / den)
+    if ft is np.float32:
+        term = float(np.float32(term))
+    return dict(term=term, loss=w * term, h=h, dlogits=d, bias=d.astype(np.float64).sum(0), used=used)

@@ -296,6 +296,57 @@ int fcn8s_set_soft_targets(fcn8s_model* m, float weight, float temperature, int 
 int fcn8s_bind_soft_targets(fcn8s_model* m, const float* probs_dev, int N, int H, int W, int ncols, int64_t row_stride);
 int fcn8s_get_soft_target_term(fcn8s_model* m, float* kd);   /* unscaled L_kd of the last training loss; synchronises like fcn8s_get_loss_terms */
 
+/* ---- the training objective: an entropy term on the student's own prediction (entropy minimisation: Grandvalet & Bengio 2005; "MinEnt" of ADVENT,
+ * Vu et al. 2019; with a negative weight the confidence penalty of Pereyra et al. 2017) -------------------------------------------------------------
+ * Definitions, per training loss on each rank's own batch:
+ *   P = N*H*W pixels, p = (n*H + h)*W + w, logits z (the library's C classes), labels y_p.  K = ncols, 2 <= K <= C (the caller's logical classes).
+ *   Columns >= K do not take part: gradient exactly 0, and a padding class's -1e30 logit never meets expf or a product.  f = first_image >= 0.
+ *   U = the pixels of the images n >= f with  y_p >= C (pixel_set = FCN8S_ENT_UNLABELED),  y_p < C (FCN8S_ENT_VALID),  any label (FCN8S_ENT_ALL);
+ *   f >= N: U is empty, the term is 0 and nothing changes.
+ *   For p in U, in fp32 with expf and logf, classes summed in order, no product contracted into a sum:
+ *     b_c = z_c - max_{c<K} z;  S = sum_{c<K} expf(b_c);  s_c = expf(b_c) / S;  ls_c = b_c - logf(S)
+ *     h_p = -sum_{c<K} s_c ls_c        (the log-softmax form: an s_c that underflowed multiplies a finite ls_c, so no clamp is needed -- this is
+ *                                       not the clamped entropy of the prediction routes)
+ *   L_ent = (1 / (P log K)) sum_{p in U} h_p -- the denominator is P, as the cross-entropy's and L_kd's, so equal data-parallel shards keep matching
+ *   the big batch; the division by log K puts a pixel's value in [0, 1].  The h_p are summed in double (per thread, then per block, then over the
+ *   blocks in a fixed order), the sum is divided by the double P * log((double)K) and the quotient is rounded to float once.
+ *   L = (everything as before) + fl(weight * L_ent).
+ *   Gradient: dlogits[p,c] += coef * (-(s_c * (ls_c + h_p))) for p in U and c < K, with coef = weight / (P log K) computed in double from the float
+ *   weight and rounded to float once.  The sum ls_c + h_p is evaluated with its two logf(S) cancelled on paper: ls_c + h_p = b_c - m_p,
+ *   m_p = sum_{c<K} s_c b_c (fp32, classes in order, no product contracted; equal when sum_c s_c = 1), so the kernel computes
+ *   coef * (-(s_c * (b_c - m_p))).  Taken as written, fl(ls_c + h_p) on a row of equal logits is what K roundings of sum s_c ls_c leave of
+ *   logf(K) - logf(K), a few 1e-7 and not 0; in this form such a row has b = 0, m_p = 0 and a gradient row of exact zeros, and the difference
+ *   between the two forms is s_c logf(S) (sum s - 1), below the rounding of either.  h_p and L_ent are the sums written above; the same contribution reaches the last transposed conv's bias gradient.  Every other entry of dlogits gets
+ *   -0.0f added, which changes no float.  Class weights, OHEM, the boundary table, the Lovász term and the soft-target term act as before.
+ *   A row with a NaN or an infinite logit among its columns < K makes that pixel's h_p and its gradient row NaN: the loss shows it and the guard of
+ *   fcn8s_set_grad_clip skips the update.
+ * One launch behind the cross-entropy (and the Lovász and soft-target terms) plus a one-block reduction, both in front of the loss copy; it works on
+ * the logits where they lie (plain or in the blocked layout of "tconv_gemm").  Deterministic whatever the `deterministic` option says: per-block
+ * partial sums reduced in a fixed order, no float atomics.  The term acts on the training losses only (fcn8s_forward_loss, fcn8s_train_step, each
+ * micro-batch of an accumulated update); evaluation, the metrics and prediction keep the reference's loss.  The per-block partials (about 270 KB)
+ * are allocated on first use and counted in "workspace_allocations".  Profile group "entropy_term", (12 C + 1) bytes per pixel.
+ * fcn8s_set_entropy_term: host state only (no launch, no allocation, no synchronisation).  weight: any finite float; > 0 minimises the entropy, < 0
+ *   is the confidence penalty, 0 switches the term off -- then nothing is launched or allocated and the step is bit for bit what it was.
+ *   FCN8S_ERR_BAD_ARG for a non-finite weight, pixel_set outside {0, 1, 2}, ncols outside 2 .. num_classes, first_image < 0 (whatever the weight);
+ *   FCN8S_ERR_STATE for switching it on under FCN8S_PREC_FP8_INFER.  The setting survives fcn8s_set_precision, fcn8s_set_option, fcn8s_set_loss,
+ *   fcn8s_set_lovasz, fcn8s_set_boundary_loss and fcn8s_set_soft_targets.
+ * fcn8s_get_entropy_term: the unscaled L_ent of the last training loss (synchronises, like fcn8s_get_loss_terms); FCN8S_ERR_STATE if that loss ran
+ *   without the term, or after the term was switched off.  fcn8s_get_loss_terms and fcn8s_get_soft_target_term are what they were.
+ * fcn8s_op_entropy_term: the same kernel and reduction on the caller's buffers, stream-ordered, allocating nothing: logits and dlogits device float32
+ *   [N*HW, C] in the plain layout at any 4-byte alignment, labels device uint8 [N*HW] at any alignment, work = fcn8s_op_entropy_term_work_bytes()
+ *   bytes of device scratch at any alignment (work_bytes = what is passed).  term_out[0] = L_ent; bias_out (may be NULL) = the C column sums of the
+ *   contribution; dlogits (may be NULL: the term and the column sums only) += the contribution.  FCN8S_ERR_BAD_ARG: a NULL logits, labels, work or
+ *   term_out, a misaligned float pointer, a non-finite weight, pixel_set, ncols or first_image as above, C outside 2 .. 64, work_bytes too small;
+ *   FCN8S_ERR_SHAPE: N or HW <= 0.  A refused call leaves every output untouched.                                                             */
+#define FCN8S_ENT_UNLABELED 0
+#define FCN8S_ENT_VALID 1
+#define FCN8S_ENT_ALL 2
+int fcn8s_set_entropy_term(fcn8s_model* m, float weight, int pixel_set, int ncols, int first_image);
+int fcn8s_get_entropy_term(fcn8s_model* m, float* term);     /* unscaled L_ent of the last training loss; synchronises like fcn8s_get_loss_terms */
+size_t fcn8s_op_entropy_term_work_bytes(void);
+int fcn8s_op_entropy_term(void* stream, const float* logits, float* dlogits, const uint8_t* labels, int N, int64_t HW, int C, int ncols, int pixel_set,
+                          int first_image, float weight, void* work, size_t work_bytes, float* term_out, float* bias_out);
+
 /* ---- the update: gradient accumulation over micro-batches, a global-norm clip and a non-finite guard (not in the reference, whose step is
  * one batch, one tf.train.AdamOptimizer.minimize, fcn8s_tensorflow.py:256) ------------------------------------------------------------------
  * Accumulation.  The model owns one accumulator acc of fcn8s_param_floats() floats, cut into the gradient buffer's buckets; it is allocated at
