@@ -116,6 +116,18 @@ inline bool pool_in_transform(const RouteOpts& o, const ConvShape& last, bool ha
 {
     return o.wino_min_cin > 0 && last.Cout >= o.wino_min_cin && o.scratch && wino_tile_for(o, last.H, last.W, 3) >= 4 && last.Cout % 64 == 0 && has_prev && keeps_v(o, last);
 }
+// The block's last conv runs its 64 position GEMMs, the output transform and the pool in ONE kernel (wino_gemm_out64_kernel: a block owns all 64
+// positions of 16 tiles, M is never written): F(6x6,3x3), 64 -> 64 channels, and the pool its output's only reader -- conv1_2.  It reads the
+// layer's shape and never N: which tiles share a block changes no tile's arithmetic, and an image's result must not depend on its batch
+// (wino_tile_for's invariant; the batch enters only where it enters the tile itself, plan_N == 1 on small maps, and with the tile the whole
+// algorithm changes anyway).  The layer's filter bank is then kept twice: the standard one and the kernel's MFMA-ordered copy behind it.
+// Only conv1_2 gets that (last_is_conv1_2: the last conv of block 1): it is the layer the kernel was built and measured for -- the full-resolution
+// map, where M's round trip is 7.7 GB per launch.  A 64-wide last conv of a deeper block (narrow models: a few tiles per image) keeps the two kernels
+// and, with them, the arithmetic the suite's tightest bounds on such models were measured with.
+inline bool gemm_out_fused64(const RouteOpts& o, const ConvShape& last, bool has_prev, bool last_is_conv1_2)
+{
+    return last_is_conv1_2 && last.K == 3 && last.Cin == 64 && last.Cout == 64 && fwd_tile(o, last) == 6 && pool_in_transform(o, last, has_prev);
+}
 
 // ---- FCN8S_PREC_BF16_TRAIN: which fp32 tensor a pass keeps, which it skips -------------------------------------------------------------------------
 // The mode runs every convolution but conv1_1 on the bf16 kernels (gemm_bf16.hip), forward and backward, and hands an activation or a gradient on as

@@ -88,7 +88,7 @@ struct Layer {
     int tile;                                    // wino_tile_for on this map
     RbWriter rb_writer;
     bool out_in_next, conv1_in_next;             // (this layer and its in-block successor)
-    bool dm_from_next, pool_in_transform;
+    bool dm_from_next, pool_in_transform, gemm_out_fused64;
     ConvShape shape(int N) const { return ConvShape{N, h, w, cin, cout, K}; }
     bool first() const { return real_cin != 0; }
     bool last_of_block() const { return pos == nconv; }
@@ -168,6 +168,7 @@ struct fcn8s_model {
     int fuse_out_in = 1;                                                  // option: inside a block, conv L's output transform writes conv L+1's V directly (Y is never written): 0 never, 1 unless the row ranges would get too short, 2 always
     int conv1_tiled = 1, conv1_wgrad_mfma = 1;                            // options: conv1_1 forward on the spatial-tile kernel / its weight gradient on the matrix core
     int conv1_in_transform = 1;                                           // option: conv1_1 is evaluated inside conv1_2's input transform (its activation tensor is never written)
+    int gemm_out_fused64 = 1;                                             // option: conv1_2 (64 -> 64, F(6x6), its pool the only reader) runs position GEMMs, output transform and pool in one kernel (M is never written); 0 = the two kernels
     DeviceBuf<unsigned short> d_wbf16;                                    // bf16 copy of one layer's kernel at a time (K-tile-major or transposed)
     std::map<std::string, DeviceBuf<unsigned short>> wbf16_cache;                 // ... per layer, valid while frozen
     // fcn8s_predict_tta on a model that is not frozen keeps the storage of the banks it built (u_cache / wbf16_cache) but not their contents: the keys
@@ -429,6 +430,7 @@ struct FwdEpi : ConvEpi {
     unsigned* relu_bits_out = nullptr;                   // Winograd path: also record (y > 0), one bit per element
     unsigned* in_relu_bits_out = nullptr; const char* in_layer = nullptr;   // Winograd path: record (x > 0) of the input too (wino_input_kernel), under this producer's name in pass.rbits_ok
     float* next_v = nullptr; const char* next_layer = nullptr;     // Winograd F(6x6) path: write the NEXT conv's V here instead of this conv's output, and promise it to that conv (pass.fwd_v)
+    bool gemm_out_fused64 = false;                       // the layer's rule gemm_out_fused64 holds and option "gemm_out_fused64" is on: position GEMMs + output transform + pool in one kernel where this launch allows it (conv_winograd)
 };
 struct DgradEpi : ConvEpi {
     const float* addend = nullptr;                       // added to dX (the skip paths' gradients)
@@ -494,7 +496,8 @@ struct WinoEpi { const float* bias = nullptr; const float* addend = nullptr; con
                  int relu = 0; int dropout = 0; float keep = 1.f; unsigned long long seed = 0; unsigned int stream_id = 0; float* pool = nullptr; unsigned char* pidx = nullptr;
                  unsigned* rbits_out = nullptr; const unsigned* rbits_in = nullptr; int skip_y = 0;
                  unsigned* in_rbits_out = nullptr;       // ReLU bit record of the INPUT, written by the input transform
-                 float* next_v = nullptr; bool* fused_out = nullptr; };     // output transform fused with the next conv's input transform (winograd.hip: wino_out_in_kernel)
+                 float* next_v = nullptr; bool* fused_out = nullptr;        // output transform fused with the next conv's input transform (winograd.hip: wino_out_in_kernel)
+                 bool gemm_out_fused64 = false; };                          // rule gemm_out_fused64 and its option: see conv_winograd
 // fc6 through 14x14 real-DFT tiles (fft_fc6.hip) in the fp32 training step of an unfrozen model.  Frozen inference keeps its cached
 // F(4x4,4x4) bank (at batch 1 the 2.45 GB DFT bank would cost more than it saves), the other precisions keep their own fc6 paths, and the
 // weight gradient stays in F(4x4,4x4) (V of pool5 is written here for it).  ci / co: channels of the FORWARD conv.
@@ -652,28 +655,46 @@ void conv_winograd(fcn8s_model* m, int tile, int KS, bool fwd, const float* x, c
     const double tb = 4.0 * ((double)N * H * W * Cin * nsub2 + (double)P * T * Kg), ob = 4.0 * ((double)N * H * W * Cout * ((e.pool ? (e.skip_y ? 0.25 : 1.25) : 1.0) + (e.rbits_in ? 1.0 / 32 : (e.mask ? 1.0 : 0.0)) + (e.addend ? 1.0 : 0.0) + (e.rbits_out ? 1.0 / 32 : 0.0)) + (double)P * T * Cout);   // y (+ pool) written, ReLU mask / skip addend read
     // frozen parameters (evaluate / predict loops): the transformed filter bank of each forward layer is computed once and kept
     bool u_cached = false;
+    // rule gemm_out_fused64 (the caller's e.gemm_out_fused64: the layer's fact and the option): the layer's bank is kept twice, the standard one -- this
+    // step's adjoint data gradient reads it -- and, behind it in the same buffer, the copy in wino_gemm_out64_kernel's operand order.  Both are
+    // written whenever the bank is, whatever this launch then runs: a cached bank outlives the launch (a frozen model may change its precision).
+    const size_t bank = (size_t)P * Kg * Cout;
+    const bool bank2 = m && layer && fwd && e.gemm_out_fused64 && tile == 6 && KS == 3 && Cin == 64 && Cout == 64;
+    const size_t bank_bytes = (bank + (bank2 ? wino_gemm_out64_bank_floats() : 0)) * sizeof(float);
+    size_t u_floats = m && u == m->d_wino_u ? m->ufl : bank;      // floats behind u
     const char* tag = KS == 7 ? (fwd ? "wino_gemm_fc6_fwd" : "wino_gemm_fc6_dgrad") : (fwd ? "wino_gemm_fwd" : "wino_gemm_dgrad");
     if (m && m->frozen && layer && fwd) {
         DeviceBuf<float>& cu = m->u_cache[std::string(layer) + "#" + std::to_string(tile)];       // (the tile, hence the bank's shape, depends on the image size)
         const std::string key = "u:" + std::string(layer) + "#" + std::to_string(tile);
-        if (cu && !m->bank_stale.count(key)) { u = cu; u_cached = true; }
-        else if (cu) { u = cu; m->bank_stale.erase(key); }                                  // kept storage: refilled below
-        else if (cu.grow((size_t)P * Kg * Cout * sizeof(float), s, &m->ws_allocs)) u = cu;  // filled below, reused from the next call on (out of memory: the shared scratch)
+        if (cu && !m->bank_stale.count(key)) { u = cu; u_cached = true; u_floats = cu.elems(); }
+        else if (cu) { u = cu; u_floats = cu.elems(); m->bank_stale.erase(key); }           // kept storage: refilled below
+        else if (cu.grow(bank_bytes, s, &m->ws_allocs)) { u = cu; u_floats = cu.elems(); }  // filled below, reused from the next call on (out of memory: the shared scratch)
         a.w = u;
     }
     if (m && !u_cached && m->fwd_train && layer && fwd && ((KS == 3 && tile == 6) || (KS == 7 && tile == 4))) {
         DeviceBuf<float>& tu = m->u_train[std::string(layer) + "#" + std::to_string(tile)];
-        if (tu.grow((size_t)P * Kg * Cout * sizeof(float), s)) { u = tu; a.w = u; }
+        if (tu.grow(bank_bytes, s)) { u = tu; a.w = u; u_floats = tu.elems(); }
     }
+    float* const u64 = bank2 && u_floats >= bank + wino_gemm_out64_bank_floats() ? u + bank : nullptr;
+    // What only this launch knows, ANDed with the rule: the fp32 precision (f32x3 / f32x2 and the bf16 modes that reach this layer through Winograd --
+    // bf16_fc, bf16_fwd -- keep the arithmetic they were measured and bounded with; bf16_train and fp8_infer never come here), nobody asks for the
+    // full-resolution activation, and the plain epilogue bias + ReLU + pool.  Declined: the two kernels, exactly as ever.
+    const bool gemm_out64 = u64 && m->precision == FCN8S_PREC_F32 && split_of(m) == 0 && e.pool && e.skip_y && e.bias && e.relu && !e.addend && !e.mask && !e.dropout && !e.rbits_in && !e.rbits_out && !e.next_v;
     // v_ready: V is already written (forward: by the previous conv's fused output transform; data gradient: with the weight gradient's dM)
-    auto pre = [&]() { if (!u_cached) { prof_derived(m, "wino_filter_kernel"); launch_wino_filter(tile, wk, u, Cin, Cout, KS, s); } if (!v_ready) launch_wino_input(tile, x, v, N, H, W, Cin, KS, s, e.in_rbits_out); };
+    auto pre = [&]() { if (!u_cached) { prof_derived(m, "wino_filter_kernel"); launch_wino_filter(tile, wk, u, Cin, Cout, KS, s, 0, u64); } if (!v_ready) launch_wino_input(tile, x, v, N, H, W, Cin, KS, s, e.in_rbits_out); };
     auto post = [&]() {
         if (e.next_v && tile == 6 && KS == 3 && e.relu && e.bias && !e.addend && !e.mask && !e.dropout && !e.pool && !e.rbits_in &&
             launch_wino_out_in(mm, e.bias, e.next_v, e.rbits_out, N, H, W, Cout, s, m && m->fuse_out_in >= 2)) { if (e.fused_out) *e.fused_out = true; return; }
         launch_wino_output(tile, mm, e.bias, e.addend, e.mask, e.mask_scale, e.relu, (e.skip_y && e.pool) ? nullptr : y, N, H, W, Cout, e.dropout, e.keep, e.seed, e.stream_id, s, e.pool, e.pidx, KS, e.rbits_out, e.rbits_in); };
     // (bytes of the fused form: M read, the next conv's V written, the ReLU record)
     const double ob_fused = 4.0 * (2.0 * P * T * Cout + (e.rbits_out ? (double)N * H * W * Cout / 32 : 0.0));
-    { ProfScope ps(m, "wino_transform", 0, (v_ready ? 0.0 : tb) + (u_cached ? 0.0 : (double)(KS * KS + P * nsub2) * 4 * Cin * Cout)); pre(); }
+    { ProfScope ps(m, "wino_transform", 0, (v_ready ? 0.0 : tb) + (u_cached ? 0.0 : (double)(KS * KS + P * nsub2 + (u64 ? P : 0)) * 4 * Cin * Cout)); pre(); }
+    if (gemm_out64) {
+        // one kernel from V to the pool: the scope keeps its name and flops (the roofline tables and pass_state.h's ledger stay comparable); bytes = V, the bank, pool and argmax bytes
+        ProfScope ps(m, tag, 2.0 * P * T * Kg * Cout, 4.0 * P * (T * (double)Kg + (double)Kg * Cout) + (double)N * H * W * Cout * (1.0 + (e.pidx ? 0.25 : 0.0)), layer);
+        if (!launch_wino_gemm_out64(v, u64, e.bias, e.pool, e.pidx, N, H, W, s)) defer_error(FCN8S_ERR_HIP, "wino_gemm_out64_kernel could not be launched for %s (%d x %d x %d)", layer, N, H, W);
+        return;
+    }
     { ProfScope ps(m, tag, 2.0 * P * T * Kg * Cout, 4.0 * P * (T * (double)(Kg + Cout) + (double)Kg * Cout), layer); launch_igemm(a, P, s); }
     { ProfScope ps(m, "wino_transform", 0, ob); post(); if (e.fused_out && *e.fused_out && m && m->profile && !m->groups.empty()) { const int g = group_id(m, "wino_transform"); m->groups[g].bytes += ob_fused - ob; } }
 }
@@ -726,6 +747,7 @@ bool conv_fwd(fcn8s_model* m, const char* group, const float* x, const float* w,
         if (e.in_relu_bits_out && e.in_layer && K == 3) { we.in_rbits_out = e.in_relu_bits_out; m->pass.rbits_ok.insert(e.in_layer); }
         bool fused_out = false;
         if (e.next_v && e.next_layer) { we.next_v = e.next_v; we.fused_out = &fused_out; }
+        we.gemm_out_fused64 = e.gemm_out_fused64;
         conv_winograd(m, tile, K, true, x, w, y, m->d_wino_u, vbuf, m->d_wino_m, N, H, W, Cin, Cout, we, s, layer, v_ready);
         if (fused_out) { m->pass.fwd_v.give(e.next_layer); if (layer) m->pass.y_unwritten.insert(layer); }
         return e.pool_out != nullptr;
@@ -1186,6 +1208,7 @@ void plan_workspace(fcn8s_model* m, int N, int H, int W, WsPlan& pl)
         L.conv1_in_next = L.first() && nx && nx->last_of_block() && conv1_in_next_transform(ro, sh, nx->shape(N));
         L.dm_from_next = nx && dm_from_next(ro, sh);
         L.pool_in_transform = L.last_of_block() && pool_in_transform(ro, sh, in_block_prev(pl.layers, L) != nullptr);
+        L.gemm_out_fused64 = L.last_of_block() && gemm_out_fused64(ro, sh, in_block_prev(pl.layers, L) != nullptr, L.block == 1);
         if (L.rb_writer != RbWriter::none) n_rb[k] = wino_rbits_words(L.tile, N, L.h, L.w, L.cout);
         if (keeps_v(ro, sh)) n_wv[k] = slab_floats(L.h, L.w, L.cin, 3);          // the forward pass keeps each Winograd layer's transformed input for the weight gradient
         if (const int c = scratch_channels(ro, sh)) vmax = std::max(vmax, slab_floats(L.h, L.w, c, 3));
@@ -1837,6 +1860,7 @@ static FwdStep fwd_conv(fcn8s_model* m, Layer& L, const float* x, bool train)
         // pass routes through the argmax bytes), the full-resolution tensor is never read again and is not written at all
         // (2.15 GB for conv1_2 at 16 x 1024x512); fcn8s_get_activation of such a layer then returns stale data.
         e.skip_y = !train || L.pool_in_transform;
+        e.gemm_out_fused64 = L.gemm_out_fused64 && m->gemm_out_fused64;
     }
     if (L.out_in_next && m->fuse_out_in && !(bf16_fwd_mode(m) && L.block >= 3) && !bf16_train_mode(m) && !fp8_mode(m) && (!train || e.relu_bits_out)) {
         // this conv and the next one both run through F(6x6,3x3) on the same tile grid: its output transform writes the next conv's
@@ -2685,6 +2709,7 @@ static int* model_option(fcn8s_model* m, const std::string& key)
     if (key == "conv1_wgrad_mfma") return &m->conv1_wgrad_mfma;
     if (key == "bf16_copy_by_transform") return &m->bf16_copy_by_transform;
     if (key == "conv1_in_transform") return &m->conv1_in_transform;
+    if (key == "gemm_out_fused64") return &m->gemm_out_fused64;
     if (key == "deterministic") return &m->deterministic;
     if (key == "bf16_acts") return &m->bf16_acts;
     if (key == "bf16_rows_bn") return &m->bf16_rows_bn;

@@ -158,7 +158,7 @@ template <bool NT> static __device__ __forceinline__ void store_pair16(VecF<2>* 
 // transpose_out (nsub == 1 only): u[xi][co][ci] instead of u[xi][ci][co] -- the B operand of the data gradient computed as the
 // adjoint of the forward algorithm (launch_wino_dgrad_output), dV[xi] = dM[xi] U[xi]^T
 template <int M, int R>
-__global__ void wino_filter_kernel(const float* w, float* u, int Cin, int Cout, int KS, int nsub, int transpose_out)
+__global__ void wino_filter_kernel(const float* w, float* u, int Cin, int Cout, int KS, int nsub, int transpose_out, float* u_mfma64)
 {
     constexpr int A = WinoMat<M, R>::A;
     const long long cc = (long long)Cin * Cout, total = cc * nsub * nsub, ucc = cc * nsub * nsub;
@@ -192,6 +192,10 @@ __global__ void wino_filter_kernel(const float* w, float* u, int Cin, int Cout, 
 #pragma unroll
                 for (int k = 0; k < R; ++k) s = fmaf(t[a][k], WinoMat<M, R>::g(b, k), s);
                 u[(long long)(a * A + b) * ucc + (transpose_out ? i0 : i)] = s;           // row (sub*Cin + ci), column co
+                // second copy in the operand order of wino_gemm_out64_kernel (64 -> 64 channels, one sub-filter, not transposed: the launcher's checks):
+                // [pos][kc][nb][lane][s] = U[pos][16 kc + 4 (lane / 16) + s][16 nb + lane % 16]
+                if (u_mfma64) { const int ci = (int)(e / Cout), co = (int)(e - (long long)ci * Cout);
+                                u_mfma64[(a * A + b) * 4096 + ((((ci >> 4) * 4 + (co >> 4)) * 64 + ((ci >> 2) & 3) * 16 + (co & 15)) << 2) + (ci & 3)] = s; }
             }
     }
 }
@@ -1214,15 +1218,17 @@ long long wino_slab(long long T, int C)
 {
     return T * C + 1088;
 }
-void launch_wino_filter(int tile, const float* w, float* u, int Cin, int Cout, int KS, hipStream_t s, int transpose_out)
+void launch_wino_filter(int tile, const float* w, float* u, int Cin, int Cout, int KS, hipStream_t s, int transpose_out, float* u_mfma64)
 {
     const int nsub = wino_nsub(KS);
     const int g = wcap((long long)Cin * Cout * nsub * nsub);
     if (nsub != 1) transpose_out = 0;
-    if (tile == 6)                    hipLaunchKernelGGL((wino_filter_kernel<6, 3>), dim3(g), dim3(256), 0, s, w, u, Cin, Cout, KS, nsub, transpose_out);
-    else if (tile == 4 && wino_r(KS) == 4) hipLaunchKernelGGL((wino_filter_kernel<4, 4>), dim3(g), dim3(256), 0, s, w, u, Cin, Cout, KS, nsub, transpose_out);
-    else if (tile == 4)               hipLaunchKernelGGL((wino_filter_kernel<4, 3>), dim3(g), dim3(256), 0, s, w, u, Cin, Cout, KS, nsub, transpose_out);
-    else                              hipLaunchKernelGGL((wino_filter_kernel<2, 3>), dim3(g), dim3(256), 0, s, w, u, Cin, Cout, KS, nsub, transpose_out);
+    if (tile != 6 || KS != 3 || Cin != 64 || Cout != 64 || transpose_out) u_mfma64 = nullptr;      // (the copy exists for F(6x6,3x3), 64 -> 64 only)
+    float* const no64 = nullptr;
+    if (tile == 6)                    hipLaunchKernelGGL((wino_filter_kernel<6, 3>), dim3(g), dim3(256), 0, s, w, u, Cin, Cout, KS, nsub, transpose_out, u_mfma64);
+    else if (tile == 4 && wino_r(KS) == 4) hipLaunchKernelGGL((wino_filter_kernel<4, 4>), dim3(g), dim3(256), 0, s, w, u, Cin, Cout, KS, nsub, transpose_out, no64);
+    else if (tile == 4)               hipLaunchKernelGGL((wino_filter_kernel<4, 3>), dim3(g), dim3(256), 0, s, w, u, Cin, Cout, KS, nsub, transpose_out, no64);
+    else                              hipLaunchKernelGGL((wino_filter_kernel<2, 3>), dim3(g), dim3(256), 0, s, w, u, Cin, Cout, KS, nsub, transpose_out, no64);
 }
 void launch_wino_dgrad_output(const float* dv, const float* addend, const float* mask, float mask_scale, const unsigned* rbits_in, float* y,
                               int N, int H, int W, int C, hipStream_t s)

@@ -627,6 +627,12 @@ int fcn8s_fp8_set_calibration(fcn8s_model* m, const float* amax, int n);
  *                              patches and straight from the preprocessed image: conv1_1's activation tensor (134 MB per 1024x512 image) is never written
  *                              or read, fcn8s_get_activation("conv1_1") returns FCN8S_ERR_STATE (fcn8s_get_relu_record still answers in training).  Same
  *                              products in another summation order (VALU fma chain instead of the MFMA kernel's).  0 = conv1_1 as a kernel of its own
+ *     "gemm_out_fused64"  1    forward: conv1_2 (64 -> 64, F(6x6,3x3), its output read by its pool alone) runs its 64 position GEMMs, the output
+ *                              transform, bias, ReLU and the 2x2/2 max-pool with its argmax bytes in one kernel (wino_gemm_out64_kernel): the layer's
+ *                              Winograd-domain output (3.86 GB at 16 x 1024x512) is never written.  The same fma chains as the output transform behind
+ *                              a GEMM of another summation order: results agree with the two-kernel route to round-off.  Only FCN8S_PREC_F32
+ *                              takes it: a launch under any other precision runs the two kernels.  Like the other route options it drops the workspace and the kept filter banks when it
+ *                              changes.  0 = position GEMM + output transform
  *     "bf16_copy_by_transform" 1  FCN8S_PREC_BF16_FWD / _X2, training: the padded bf16 copy of a layer's input that its direct bf16 convolution reads is
  *                              written by the layer's Winograd input transform (which runs anyway, for the weight gradient) instead of a
  *                              conversion pass of its own over the activations (identical bits); 0 = the separate pass

@@ -37,7 +37,7 @@ TRAINING = ('fp32', 'f32x3', 'f32x2', 'bf16_fc', 'bf16_fwd', 'bf16_fwd_x2', 'bf1
 SHAPES = ((2, 64, 96), (1, 96, 160), (1, 192, 192))
 VARIANT_SHAPE = (1, 96, 160)
 VARIANTS = (("fuse_out_in", 0), ("fuse_out_in", 2), ("fuse_dgrad_dout", 0), ("conv1_in_transform", 0), ("winograd_tile", 4), ("fc6_fft_wgrad", 2),
-            ("fc6_fft", 0), ("bf16_acts", 0), ("bf16_fuse_pool", 0), ("keep_output_gradients", 1))
+            ("fc6_fft", 0), ("bf16_acts", 0), ("bf16_fuse_pool", 0), ("keep_output_gradients", 1), ("gemm_out_fused64", 0))
 # the options that decide something in bf16_fwd (its conv1 / conv2 blocks and all of its backward pass run through Winograd)
 BF16_FWD_VARIANTS = ("fuse_out_in", "fuse_dgrad_dout", "conv1_in_transform", "winograd_tile", "keep_output_gradients")
 # the options that move a layer from one route to another (csrc/conv_route.h), fp32 and bf16_fwd.  winograd_min_cin = 128 with WIDTHS: direct blocks
