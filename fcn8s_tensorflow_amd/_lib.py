@@ -148,6 +148,7 @@ SIGNATURES = {
     "fcn8s_op_conv2d": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i]),
     "fcn8s_op_conv2d_winograd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i]),
     "fcn8s_op_conv3x3_winograd_fwd_bwd": (_i, [_p] * 11 + [_i] * 8),
+    "fcn8s_op_conv3x3_winograd_pool": (_i, [_p] * 6 + [_i] * 7 + [C.POINTER(_i)]),
     "fcn8s_op_conv7x7_fc6_fwd_bwd": (_i, [_p] * 9 + [_i] * 6 + [_f, C.c_uint64, C.POINTER(_i)]),
     "fcn8s_op_conv2d_bf16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i]),
     "fcn8s_op_conv2d_bf16_train": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i]),

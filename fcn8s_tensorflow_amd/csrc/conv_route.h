@@ -124,6 +124,8 @@ inline bool pool_in_transform(const RouteOpts& o, const ConvShape& last, bool ha
 // Only conv1_2 gets that (last_is_conv1_2: the last conv of block 1): it is the layer the kernel was built and measured for -- the full-resolution
 // map, where M's round trip is 7.7 GB per launch.  A 64-wide last conv of a deeper block (narrow models: a few tiles per image) keeps the two kernels
 // and, with them, the arithmetic the suite's tightest bounds on such models were measured with.
+// (The op-level entry points fcn8s_op_conv3x3_winograd_fwd_bwd / _pool have one layer and no table: they set the caller's flag from the op context
+// "op_gemm_out_fused64", default 0, and conv_winograd's own conditions decide as for a model.)
 inline bool gemm_out_fused64(const RouteOpts& o, const ConvShape& last, bool has_prev, bool last_is_conv1_2)
 {
     return last_is_conv1_2 && last.K == 3 && last.Cin == 64 && last.Cout == 64 && fwd_tile(o, last) == 6 && pool_in_transform(o, last, has_prev);

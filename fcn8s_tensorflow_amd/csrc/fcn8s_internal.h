@@ -341,7 +341,7 @@ long long wino_slab(long long T, int C);   // floats between the slabs of consec
 void launch_wino_filter(int tile, const float* w, float* u, int Cin, int Cout, int KS, hipStream_t s, int transpose_out = 0, float* u_mfma64 = nullptr);   // w[KS*KS][Cin][Cout] -> u[P][nsub*Cin][Cout]  (transpose_out: u[P][Cout][Cin], KS = 3 only; u_mfma64: F(6x6,3x3) 64 -> 64, a second copy in wino_gemm_out64_kernel's operand order)
 // F(6x6,3x3), 64 -> 64 channels, pooled: the 64 position GEMMs, the output transform (bias, ReLU) and the 2x2/2 max-pool with its argmax bytes in one kernel
 // (wino_fused64.hip) -- v[64][T][64] and the MFMA-ordered bank straight to pool [N,H/2,W/2,64] and pidx (may be null); M is never written.  false: not launched.
-bool launch_wino_gemm_out64(const float* v, const float* u_mfma64, const float* bias, float* pool, unsigned char* pidx, int N, int H, int W, hipStream_t s);
+bool launch_wino_gemm_out64(const float* v, const float* u_mfma64, const float* bias, float* pool, unsigned char* pidx, int N, int H, int W, hipStream_t s, int nt = -1);   // nt: 0 / 1 overrides the size rule for the non-temporal instantiation
 size_t wino_gemm_out64_bank_floats();      // floats of the MFMA-ordered bank
 void launch_wino_input(int tile, const float* x, float* v, int N, int H, int W, int C, int KS, hipStream_t s, unsigned* rbits_out = nullptr);   // x[N,H,W,C] -> v[P][T][nsub*C]
 void launch_wino_input_conv1(const float* x0, const float* w4, const float* bias, float* v, int N, int H, int W, hipStream_t s, unsigned* rbits_out = nullptr);   // conv1_1 + conv1_2's F(6x6,3x3) input transform

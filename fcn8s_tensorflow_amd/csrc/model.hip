@@ -169,6 +169,8 @@ struct fcn8s_model {
     int conv1_tiled = 1, conv1_wgrad_mfma = 1;                            // options: conv1_1 forward on the spatial-tile kernel / its weight gradient on the matrix core
     int conv1_in_transform = 1;                                           // option: conv1_1 is evaluated inside conv1_2's input transform (its activation tensor is never written)
     int gemm_out_fused64 = 1;                                             // option: conv1_2 (64 -> 64, F(6x6), its pool the only reader) runs position GEMMs, output transform and pool in one kernel (M is never written); 0 = the two kernels
+    int gemm_out64_nt = -1;                                               // op entries (op context "op_gemm_out_fused64" = 2): 1 = wino_gemm_out64_kernel's non-temporal instantiation whatever the size; -1 = the launcher's own rule (every real model)
+    int gemm_out64_launches = 0;                                          // launches of wino_gemm_out64_kernel (what fcn8s_op_conv3x3_winograd_pool reports)
     DeviceBuf<unsigned short> d_wbf16;                                    // bf16 copy of one layer's kernel at a time (K-tile-major or transposed)
     std::map<std::string, DeviceBuf<unsigned short>> wbf16_cache;                 // ... per layer, valid while frozen
     // fcn8s_predict_tta on a model that is not frozen keeps the storage of the banks it built (u_cache / wbf16_cache) but not their contents: the keys
@@ -451,6 +453,7 @@ struct DgradEpi : ConvEpi {
 // from that thread), copied into the bare model each such call builds -- never read by a real model, never shared between threads.
 thread_local int t_op_split = 0;
 thread_local int t_op_rows_bn = 0;       // op context: the form of the flat-position 3 x 3 kernel fcn8s_op_conv2d_bf16_train asks for (option "op_bf16_rows_bn")
+thread_local int t_op_fused64 = 0;       // op context: fcn8s_op_conv3x3_winograd_fwd_bwd / _pool ask for wino_gemm_out64_kernel (option "op_gemm_out_fused64": 1, 2 = its non-temporal instantiation)
 thread_local int t_op_planes = 1;        // op context: fcn8s_op_conv2d_bf16_train keeps its padded copies as channel-chunk planes (option "op_bf16_planes")
 int split_of(const fcn8s_model* m)
 {
@@ -692,7 +695,8 @@ void conv_winograd(fcn8s_model* m, int tile, int KS, bool fwd, const float* x, c
     if (gemm_out64) {
         // one kernel from V to the pool: the scope keeps its name and flops (the roofline tables and pass_state.h's ledger stay comparable); bytes = V, the bank, pool and argmax bytes
         ProfScope ps(m, tag, 2.0 * P * T * Kg * Cout, 4.0 * P * (T * (double)Kg + (double)Kg * Cout) + (double)N * H * W * Cout * (1.0 + (e.pidx ? 0.25 : 0.0)), layer);
-        if (!launch_wino_gemm_out64(v, u64, e.bias, e.pool, e.pidx, N, H, W, s)) defer_error(FCN8S_ERR_HIP, "wino_gemm_out64_kernel could not be launched for %s (%d x %d x %d)", layer, N, H, W);
+        m->gemm_out64_launches += 1;
+        if (!launch_wino_gemm_out64(v, u64, e.bias, e.pool, e.pidx, N, H, W, s, m->gemm_out64_nt)) defer_error(FCN8S_ERR_HIP, "wino_gemm_out64_kernel could not be launched for %s (%d x %d x %d)", layer, N, H, W);
         return;
     }
     { ProfScope ps(m, tag, 2.0 * P * T * Kg * Cout, 4.0 * P * (T * (double)(Kg + Cout) + (double)Kg * Cout), layer); launch_igemm(a, P, s); }
@@ -2727,6 +2731,7 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
         if (k == "op_f32x3") { t_op_split = value ? 3 : 0; return FCN8S_OK; }
         if (k == "op_deterministic") { t_deterministic = value ? 1 : 0; return FCN8S_OK; }
         if (k == "op_bf16_planes") { t_op_planes = value ? 1 : 0; return FCN8S_OK; }
+        if (k == "op_gemm_out_fused64") { if (value < 0 || value > 2) return fail(nullptr, FCN8S_ERR_BAD_ARG, "op_gemm_out_fused64 must be 0, 1 or 2"); t_op_fused64 = (int)value; return FCN8S_OK; }
         if (k == "op_bf16_rows_bn") { if (value != 0 && value != 64 && value != 128) return fail(nullptr, FCN8S_ERR_BAD_ARG, "op_bf16_rows_bn must be 0, 64 or 128"); t_op_rows_bn = (int)value; return FCN8S_OK; }
         if (k == "op_split_pieces") {
             if (value != 0 && value != 2 && value != 3) return fail(nullptr, FCN8S_ERR_BAD_ARG, "fcn8s_set_option: op_split_pieces is 0, 2 or 3");
@@ -2774,6 +2779,7 @@ int fcn8s_get_option(const fcn8s_model* m, const char* key, int64_t* value)
         if (k == "op_f32x3") { *value = t_op_split == 3; return FCN8S_OK; }
         if (k == "op_deterministic") { *value = t_deterministic; return FCN8S_OK; }
         if (k == "op_bf16_planes") { *value = t_op_planes; return FCN8S_OK; }
+        if (k == "op_gemm_out_fused64") { *value = t_op_fused64; return FCN8S_OK; }
         if (k == "op_bf16_rows_bn") { *value = t_op_rows_bn; return FCN8S_OK; }
         if (k == "op_split_pieces") { *value = t_op_split; return FCN8S_OK; }
         return FCN8S_ERR_NOT_FOUND;
@@ -4283,7 +4289,9 @@ int fcn8s_op_conv3x3_winograd_fwd_bwd(void* stream, const float* x, const float*
     DeviceBuf<float> wino_v, wino_m, wv, wt, pidx, rbits;
     bool ok = true;
     auto dalloc = [&](DeviceBuf<float>& b, size_t nfloats) { ok = ok && b.grow(nfloats * sizeof(float), s); };
-    dalloc(m->d_wino_u, (size_t)P * cmax * cmax); dalloc(wino_v, slab_max); dalloc(wino_m, slab_max);
+    m->ufl = (size_t)P * cmax * cmax + (t_op_fused64 ? wino_gemm_out64_bank_floats() : 0);       // (the second, MFMA-ordered bank behind the first)
+    if (t_op_fused64 == 2) m->gemm_out64_nt = 1;
+    dalloc(m->d_wino_u, m->ufl); dalloc(wino_v, slab_max); dalloc(wino_m, slab_max);
     dalloc(wv, slab_in); dalloc(wt, (size_t)9 * Cin * Cout);
     if (pooled) dalloc(pidx, ((size_t)N * (H / 2) * (W / 2) * Cout + 3) / 4);
     if (mask_mode == 2) dalloc(rbits, wino_rbits_words(tile, N, H, W, Cin));
@@ -4293,6 +4301,7 @@ int fcn8s_op_conv3x3_winograd_fwd_bwd(void* stream, const float* x, const float*
     // forward (training mode: keeps V and the filter bank, writes the pool argmax bytes / the input's ReLU bit record)
     m->fwd_train = true; m->train_mode = true;
     { FwdEpi e; e.bias = bias; e.relu = 1;
+      e.gemm_out_fused64 = t_op_fused64 != 0;            // asked for: whether the kernel runs is conv_winograd's decision
       if (pooled) { e.pool_out = pool; e.pool_idx = (unsigned char*)pidx.get(); e.skip_y = y == nullptr; }
       if (mask_mode == 2) { e.in_relu_bits_out = (unsigned*)rbits.get(); e.in_layer = "prev"; }
       conv_fwd(m, "op", x, w, y, N, H, W, Cin, Cout, 3, e, s, 0, "op"); }
@@ -4304,6 +4313,49 @@ int fcn8s_op_conv3x3_winograd_fwd_bwd(void* stream, const float* x, const float*
       if (mask_mode) { e.mask = x; e.mask_scale = 1.f; }
       if (mask_mode == 2 && m->pass.rbits_ok.count("prev")) e.relu_bits_in = (const unsigned*)rbits.get();
       conv_dgrad(m, "op", dy, wt, dx, N, H, W, Cout, Cin, 3, e, s, "op"); }
+    hipStreamSynchronize(s);
+    OPCHK(); return FCN8S_OK;
+}
+
+// One 3x3 SAME conv + bias + ReLU + 2x2/2 max-pool the way the last conv of a block runs forward: the model's own conv_fwd on a bare model with
+// one layer called "op", the full-resolution output never written.  train: V is kept in the layer's own slot, the bank in u_train, the argmax
+// bytes go to pidx; else (as fcn8s_predict) V goes to the shared scratch and no bytes are written.  Whether wino_gemm_out64_kernel runs (op context
+// "op_gemm_out_fused64") is conv_winograd's decision; *fused reports it.  Every scratch buffer is an allocation of its own, all of it NaN: what a
+// model's shared workspace holds behind a slab is another layer's leftovers.  For tests only: it allocates and synchronises per call.
+int fcn8s_op_conv3x3_winograd_pool(void* stream, const float* x, const float* w, const float* bias, float* pool, unsigned char* pidx,
+                                   int N, int H, int W, int Cin, int Cout, int tile, int train, int* fused)
+{
+    if (fused) *fused = 0;
+    if ((tile != 4 && tile != 6) || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 64 || Cout % 64 || H % 2 || W % 2 || (tile != 6 && (H % tile || W % tile)) ||
+        !x || !w || !bias || !pool)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "conv3x3_winograd_pool: needs tile in {4,6}, Cin % 64 == 0, Cout % 64 == 0, even H and W (multiples of 4 for tile 4), non-null x, w, bias, pool");
+    hipStream_t s = (hipStream_t)stream;
+    fcn8s_model mm; fcn8s_model* m = &mm;
+    m->stream = s; m->wino_min_cin = 16; m->wino_tile = 6; m->wino_force_tile = tile; m->N = N; m->H = H; m->W = W;
+    m->precision = t_op_split == 3 ? FCN8S_PREC_F32X3 : t_op_split == 2 ? FCN8S_PREC_F32X2 : FCN8S_PREC_F32;
+    if (t_op_fused64 == 2) m->gemm_out64_nt = 1;
+    const int al = tile + 2, P = al * al, cmax = std::max(Cin, Cout);
+    const long long T = wino_tiles(tile, N, H, W);
+    const size_t v_floats = (size_t)P * (size_t)wino_slab(T, Cin), m_floats = (size_t)P * (size_t)wino_slab(T, Cout);
+    DeviceBuf<float> wino_v, wino_m, wv;
+    bool ok = true;
+    auto dalloc = [&](DeviceBuf<float>& b, size_t nfloats) {
+        ok = ok && b.grow(nfloats * sizeof(float), s);
+        if (ok) hipMemsetAsync(b, 0xFF, nfloats * sizeof(float), s);
+    };
+    // (the bank with room for the second, MFMA-ordered copy behind it: the inference call has no u_train to put them in)
+    m->ufl = (size_t)P * cmax * cmax + wino_gemm_out64_bank_floats();
+    dalloc(m->d_wino_u, m->ufl); dalloc(wino_v, v_floats); dalloc(wino_m, m_floats);
+    if (train) dalloc(wv, v_floats);
+    if (!ok) { hipStreamSynchronize(s); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
+    m->d_wino_v = wino_v; m->d_wino_m = wino_m;
+    if (train) { Act a; a.p = wv; a.n = v_floats; m->acts["wv:op"] = a; }
+    m->fwd_train = train != 0; m->train_mode = train != 0;
+    { FwdEpi e; e.bias = bias; e.relu = 1; e.pool_out = pool; e.skip_y = 1;
+      if (train) e.pool_idx = pidx;
+      e.gemm_out_fused64 = t_op_fused64 != 0;
+      conv_fwd(m, "op", x, w, nullptr, N, H, W, Cin, Cout, 3, e, s, 0, "op"); }
+    if (fused) *fused = m->gemm_out64_launches > 0;
     hipStreamSynchronize(s);
     OPCHK(); return FCN8S_OK;
 }

@@ -141,13 +141,14 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_out64_kernel(const float* __
 size_t wino_gemm_out64_bank_floats() { return (size_t)64 * 64 * 64; }
 
 // false: not launched (the caller runs the position GEMM and the output transform)
-bool launch_wino_gemm_out64(const float* v, const float* up, const float* bias, float* pool, unsigned char* pidx, int N, int H, int W, hipStream_t s)
+// nt: -1 = the size rule below picks the non-temporal instantiation; 0 / 1 = the caller does (the op-level entry points, for their small shapes)
+bool launch_wino_gemm_out64(const float* v, const float* up, const float* bias, float* pool, unsigned char* pidx, int N, int H, int W, hipStream_t s, int nt)
 {
     if (!v || !up || !bias || !pool || N <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2) return false;
     const long long T = (long long)N * ((H + 5) / 6) * ((W + 5) / 6);
     const long long blocks = (T + kF64Tiles - 1) / kF64Tiles;
     if (blocks > 0x7fffffffLL) return false;
-    const bool big = (double)N * H * W * 64 >= 64e6;          // launch_wino_output's rule: bytes of the pool this launch writes
+    const bool big = nt >= 0 ? nt != 0 : (double)N * H * W * 64 >= 64e6;          // launch_wino_output's rule: bytes of the pool this launch writes
     const hipError_t e = hipFuncSetAttribute(big ? reinterpret_cast<const void*>(&wino_gemm_out64_kernel<true>) : reinterpret_cast<const void*>(&wino_gemm_out64_kernel<false>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kF64LdsBytes);
     if (e != hipSuccess) { defer_error(FCN8S_ERR_HIP, "wino_gemm_out64: %zu bytes of LDS refused (%s)", kF64LdsBytes, hipGetErrorString(e)); return false; }

@@ -669,6 +669,10 @@ int fcn8s_fp8_set_calibration(fcn8s_model* m, const float* amax, int n);
  *     "op_bf16_planes"    1    fcn8s_op_conv2d_bf16_train keeps its padded bf16 copies as channel-chunk planes [C / 32][rows][32] (what FCN8S_PREC_BF16_TRAIN does);
  *                              0 = [rows][C], the layout the kernels also take (same results)
  *     "op_bf16_rows_bn"   0    the same switch ("bf16_rows_bn": 0 / 64 = 256 x 64 blocks, 128 = 128 x 128) for fcn8s_op_conv2d_bf16_train
+ *     "op_gemm_out_fused64" 0  fcn8s_op_conv3x3_winograd_fwd_bwd and fcn8s_op_conv3x3_winograd_pool ask for the route of "gemm_out_fused64" (their bare models set the
+ *                              layer's fact and the option; whether wino_gemm_out64_kernel then runs stays the launch's own decision: 64 -> 64 channels, tile 6,
+ *                              the fp32 arithmetic, the pool as the only output): 1 = asked for, 2 = the same with the kernel's non-temporal-store instantiation
+ *                              whatever the size (a model launches it from 64e6 pooled bytes up), 0 = position GEMM + output transform.  Other values: FCN8S_ERR_BAD_ARG
  *     "op_deterministic"  0    the slab reductions of "deterministic" for the op-level entry points (a model call on the same thread sets the
  *                              thread's switch from that model's option: set it again before the next op-level call)
  * Unknown keys return FCN8S_ERR_NOT_FOUND. */
@@ -767,10 +771,22 @@ int fcn8s_op_conv2d_winograd(void* stream, const float* x, const float* w_hwio, 
  *             as the adjoint of the forward algorithm (dV = dM U^T on the transposed-B GEMM, overlap-add gather), for tiles 2 / 4 as a
  *             forward-type Winograd conv on flipped filters; + dx_addend (optional skip gradient), then masked by (x > 0) if
  *             mask_mode = 1 (x read as the mask) or 2 (one-bit record written by this conv's input transform, the conv1_1 case).
+ * With op context "op_gemm_out_fused64" on, y == NULL, pooled != 0, tile 6 and 64 -> 64 channels the forward is wino_gemm_out64_kernel (conv1_2's route).
  * Not in the reference; exists so that the Winograd backward has op-level parity tests. */
 int fcn8s_op_conv3x3_winograd_fwd_bwd(void* stream, const float* x, const float* w_hwio, const float* bias, const float* dy, const float* dx_addend,
                                       float* y, float* pool, float* dx, float* dw, float* db,
                                       int N, int H, int W, int Cin, int Cout, int tile, int pooled, int mask_mode);
+/* One 3x3 SAME conv + bias + ReLU + 2x2/2 max-pool the way the LAST conv of a block runs forward, through the model's own launch sequence (Winograd
+ * F(tile x tile, 3x3), tile = 4 or 6; Cin, Cout multiples of 64; even H, W, multiples of 4 for tile 4): pool = maxpool2x2(relu(conv(x, w) + bias))
+ * [N,H/2,W/2,Cout]; the full-resolution output is never written.
+ *   train != 0  a training pass: V is kept in the layer's own slot, the filter bank for the step, and pidx (device, one byte per pooled element, may be
+ *               NULL) receives the argmax bytes of fcn8s_get_pool_routing;
+ *   train == 0  an inference pass (fcn8s_predict): V goes to the shared scratch, the bank to the filter-bank scratch, pidx is not written.
+ *   fused (host, may be NULL) receives 1 if wino_gemm_out64_kernel was launched (op context "op_gemm_out_fused64" asks for it; the launch decides), else 0.
+ * Every scratch buffer (V, M, the filter bank with room for the second copy behind it, the kept V) is an allocation of its own, filled with NaNs before
+ * the call.  Not in the reference; for tests only -- it allocates and synchronises per call, so it says nothing about time. */
+int fcn8s_op_conv3x3_winograd_pool(void* stream, const float* x, const float* w_hwio, const float* bias, float* pool, unsigned char* pidx,
+                                   int N, int H, int W, int Cin, int Cout, int tile, int train, int* fused);
 /* One 7x7 SAME conv the way fc6 runs in an fp32 TRAINING step, forward and backward, through the model's own launch sequences and under the
  * model's own rules for which kernels take a shape (Cin % 16 == 0, Cout % 128 == 0):
  *   forward   y = dropout(relu(conv(x, w) + bias)); bias may be NULL; dropout only if keep_prob < 1, with `seed` and the Philox stream fc6 has in a

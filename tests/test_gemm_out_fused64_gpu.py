@@ -6,9 +6,10 @@ is the summation order of the 64-term position GEMMs: everything agrees to round
 A narrow model (widths[0] = 64 puts conv1_2 on the route, the rest as small as smoke()'s) on the two shapes that walk the kernel's edge cases:
   1 x 64x64: 11 x 11 = 121 tiles -- seven full blocks of 16 tiles and one of 9 (clamped loads, skipped stores), partial edge tiles both ways (64 = 10 * 6 + 4)
   2 x 32x64: 6 x 11 = 66 tiles per image, 132 in all -- the block of tiles 64..79 straddles the two images
-(No op-level entry point reaches the route -- the bare models of fcn8s_op_* never set it -- so there is no fewer-than-one-block case, and since the rule
-implies that the pool is routed in the transform, no pass of a model on this route can ask for conv1_2's full-resolution activation: of the two
-declining cases only the precision can be exercised: f32x3 and bf16_fc.)
+(The kernel alone -- launches of fewer than 16 tiles, every (H % 6, W % 6) edge, the argmax bytes against a rule of their own, the second filter
+bank -- is held to float64 at op level in tests/test_gemm_out_fused64_ops_gpu.py; this module is the route inside a model.  Since the rule implies
+that the pool is routed in the transform, no pass of a model on this route can ask for conv1_2's full-resolution activation: of the two declining
+cases only the precision can be exercised: f32x3 and bf16_fc.)
 
 Tolerances are those of test_model_gpu.py::test_conv1_1_inside_conv1_2_input_transform, the same kind of change (a summation order inside block 1)."""
 import functools

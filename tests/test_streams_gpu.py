@@ -51,6 +51,7 @@ from tests.test_ops_gpu import rel_err  # noqa: E402
 from tests import test_fc6_fft_ops_gpu as fc6t, test_fp8_gpu as fp8t, test_loss_gpu as losst, test_boundary_loss_ops_gpu as pxt  # noqa: E402
 from tests import test_reliability_ops_gpu as relt, test_temperature_ops_gpu as tst, test_mc_dropout_ops_gpu as mct, test_crf_gpu as crft  # noqa: E402
 from tests import test_predict_tta_gpu as ttat  # noqa: E402
+from tests import test_gemm_out_fused64_ops_gpu as f64t  # noqa: E402
 
 DELAY_MULTIPLE = 4
 DELAY_FLOOR_MS = 5.0
@@ -444,6 +445,39 @@ def winograd_fwd_rows(shape):
 
 winograd_fwd_rows((3, 2, 4, 32, 64, 6, 3))
 winograd_fwd_rows((1, 4, 4, 16, 32, 4, 7))
+
+def winograd_pool_rows(shape, option):
+    N, Hh, W = shape
+
+    @row("conv3x3_winograd_pool %s op_gemm_out_fused64 %d" % (shape, option), ("fcn8s_op_conv3x3_winograd_pool",))
+    class _:
+        @staticmethod
+        def make(seed):
+            x, k, b = f64t.inputs(N, Hh, W)
+            if seed != 1:                                        # the warm-up's other data
+                x, k, b = (np.roll(a, 1) for a in (x, k, b))
+            pshape = (N, Hh // 2, W // 2, f64t.CH)
+            return Case(dict(x=np.array(x), w=np.array(k), b=np.array(b)), dict(pool=F(*pshape), byte=(pshape, np.uint8)),
+                        ref=f64t.reference(N, Hh, W) if seed == 1 else None)
+
+        @staticmethod
+        def call(L, s, b, case):
+            fused = C.c_int(-1)
+            with f64t.op_context(op_gemm_out_fused64=option):
+                L.check(L.lib.fcn8s_op_conv3x3_winograd_pool(s, ptr(b["x"]), ptr(b["w"]), ptr(b["b"]), ptr(b["pool"]), ptr(b["byte"]), N, Hh, W, f64t.CH, f64t.CH,
+                                                             f64t.TILE, 1, C.byref(fused)))
+            return dict(fused=np.array(fused.value))
+
+        @staticmethod
+        def check(case, got):
+            ref = case.aux["ref"]
+            assert int(got["fused"]) == (option != 0)
+            assert rel_err(got["pool"], ref["pool"]) < 1e-4                                       # test_gemm_out_fused64_ops_gpu's bars
+            assert not ((got["byte"] != ref["byte"]) & ~ref["amb"]).any()
+
+
+winograd_pool_rows((3, 14, 20), 1)
+winograd_pool_rows((1, 6, 102), 2)
 
 FC6_SHAPE = min(fc6t.CASES, key=lambda c: c[0] * c[1] * c[2] * c[3] * c[4])[:5]
 
