@@ -103,6 +103,9 @@ SIGNATURES = {
     "fcn8s_get_entropy_term": (_i, [_p, _fp]),
     "fcn8s_op_entropy_term_work_bytes": (_sz, []),
     "fcn8s_op_entropy_term": (_i, [_p, _p, _p, _p, _i, _i64, _i, _i, _i, _i, _f, _p, _sz, _p, _p]),
+    "fcn8s_set_focal": (_i, [_p, _f]),
+    "fcn8s_op_focal_xent_work_bytes": (_sz, []),
+    "fcn8s_op_focal_xent": (_i, [_p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _i64, _i, _p, _sz]),
     "fcn8s_eval_step": (_i, [_p, _p, _i, _p, _i, _i, _i, _f, _i]),
     "fcn8s_metrics_reset": (_i, [_p]),
     "fcn8s_metrics_get": (_i, [_p, _dp, _dp, _dp]),

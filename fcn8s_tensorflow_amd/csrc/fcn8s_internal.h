@@ -274,6 +274,16 @@ size_t entropy_term_scratch_bytes();
 double entropy_term_bytes(long long npix, int C);             // the algorithmic bytes (profile group "entropy_term")
 void launch_entropy_term(const float* logits, float* dlogits, const uint8_t* labels, const PixMap* map, int N, long long npix, int C, int K, int pixel_set,
                          int first_image, float weight, char* ws, float* loss, float* term, float* bias, int bias_add, hipStream_t s);
+// ---- the focal loss (focal.hip; fcn8s_set_focal, fcn8s_op_focal_xent in include/fcn8s_hip.h) ------------------------------------------
+// One launch in the cross-entropy's place: dlogits (plain [npix, C] or blocked, map; null: not touched) = the focal gradient rows (stored; zeros for
+// ignored pixels and for slots outside the image), then one small kernel: sum_out[0] = the double sum of w_p f l (null: not written; the model hands it
+// to finalize_loss as its one partial), loss[0] = fl(sum / npix) (null: the model), st = the loss state that receives |V| (null: none), bias[c] = the
+// gradient's column sums, c < C (null: none).  cw = C class weights (null: all 1); codes (indexed like the labels) and ptab (256 weights) both set or
+// both null.  ws: focal_xent_scratch_bytes() of per-block partials, 8-byte aligned.  2 <= C <= 64, 0 < gamma <= 8.
+size_t focal_xent_scratch_bytes();
+double focal_xent_bytes(long long npix, int C, bool codes);   // the algorithmic bytes (profile group "focal_xent")
+void launch_focal_xent(const float* logits, float* dlogits, const uint8_t* labels, const float* cw, const uint8_t* codes, const float* ptab, const PixMap* map,
+                       int N, long long npix, int C, float gamma, float gscale, char* ws, double* sum_out, float* loss, OhemState* st, float* bias, hipStream_t s);
 void launch_softmax_argmax(const float* logits, float* softmax_out, long long* argmax_out,
                            long long npix, int C, hipStream_t s, const PixMap* map = nullptr, int N = 0);
 // ---- the k = 2s transposed conv as one GEMM (see PixMap): operand / result re-layouts, all tiny next to the GEMMs -------------

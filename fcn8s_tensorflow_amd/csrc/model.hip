@@ -256,6 +256,10 @@ struct fcn8s_model {
     // loss ran with the term
     float ent_w = 0.f; int ent_set = 0, ent_K = 0, ent_first = 0; bool have_ent = false;
     DeviceBuf<char> ent_ws;
+    // fcn8s_set_focal: focal_gamma > 0: the focal launch (focal.hip) stands where the cross-entropy's stands in a training loss; 0: off.  focal_ws = the
+    // per-block partials, grown on first use (a "workspace_allocation")
+    float focal_gamma = 0.f;
+    DeviceBuf<char> focal_ws;
     // fcn8s_accumulate_bucket: the accumulator (total floats, the gradient buffer's buckets; grown at the first fold -- a "workspace_allocation" --
     // and kept until the model goes), per bucket the micro-batches folded and not yet flushed, and whether this backward pass's bucket was taken
     DeviceBuf<float> d_acc; int acc_k[FCN8S_MAX_BUCKETS] = {0}; bool acc_taken[FCN8S_MAX_BUCKETS] = {false};
@@ -2204,7 +2208,10 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
     const int nb = softmax_xent_blocks(npix);
     const bool bnd = with_grad && m->bnd_R > 0;               // evaluation keeps the reference's loss
     const int mode = with_grad ? (m->loss_mode ? m->loss_mode : bnd ? 1 : 0) : 0;    // the boundary weighting alone: the weighted mode, d_cw holds ones
-    if (mode) { int rc = ensure_loss_ws(m, npix, mode); if (rc) return rc; }
+    const bool focal = with_grad && m->focal_gamma > 0.f;      // the focal launch in the cross-entropy's place (mode is 0 or 1: OHEM is refused with it)
+    if (focal && mode == 2) return fail(m, FCN8S_ERR_STATE, "fcn8s_set_focal: the focal loss does not combine with OHEM");
+    if (mode || focal) { int rc = ensure_loss_ws(m, npix, mode ? mode : 1); if (rc) return rc; }       // (focal: the state that holds |V| for fcn8s_get_loss_stats)
+    if (focal && !m->focal_ws.grow(focal_xent_scratch_bytes(), s, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "the focal loss's scratch cannot be allocated");
     if (bnd) {
         // the distance codes of THIS loss's labels (those the device-side augmentation left), in front of the loss on the same stream
         if ((long long)m->H * m->W >= (1LL << 31)) return fail(m, FCN8S_ERR_SHAPE, "fcn8s_set_boundary_loss: an image has to have fewer than 2^31 pixels");
@@ -2226,6 +2233,16 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
     // bytes: the logits once (+ dlogits) and the labels; OHEM reads the logits and labels twice and writes + reads l_p (its refinement
     // passes, 4 bytes per pixel each when min_kept decides the threshold, are not counted)
     const double xbytes = (mode == 2 ? (double)npix * (m->C * 4 * 3 + 2 + 8) : (double)npix * (m->C * 4 * (with_grad ? 2 : 1) + 1)) + (bnd ? (double)npix : 0.0);   // (+ the codes)
+    if (focal) {
+        // L_foc and its gradient: one launch plus a one-block reduction that leave what the cross-entropy's launch leaves -- the loss sum as the one
+        // partial finalize_loss reads, d_lastbias (set, all 64 columns defined by the memset), |V| in the loss state -- so that everything behind is untouched
+        ProfScope ps(m, "focal_xent", 0, focal_xent_bytes(npix, m->C, bnd));
+        hipMemsetAsync(m->d_lastbias, 0, 64 * sizeof(float), s);
+        const bool blk = m->tconv_gemm && m->logits_b;
+        launch_focal_xent(blk ? m->logits_b : A(m, "logits"), blk ? m->dlogits_b : m->dlogits, lab_dev, mode ? (const float*)m->d_cw : nullptr,
+                          bnd ? (const uint8_t*)m->d_bcodes : nullptr, bnd ? (const float*)m->d_btab : nullptr, blk ? &m->pm : nullptr, m->N, npix, m->C,
+                          m->focal_gamma, gscale, m->focal_ws, m->d_partials, nullptr, (OhemState*)m->loss_ws.get(), m->d_lastbias, s);
+    } else
     { ProfScope ps(m, "softmax_xent", 0, xbytes);
       if (with_grad) hipMemsetAsync(m->d_lastbias, 0, 64 * sizeof(float), s);
       const bool blk = m->tconv_gemm && m->logits_b;
@@ -2239,14 +2256,14 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
       } else
           launch_softmax_xent(blk ? m->logits_b : A(m, "logits"), lab_dev, with_grad ? (blk ? m->dlogits_b : m->dlogits) : nullptr, m->d_partials, npix, m->C,
                               gscale, s, with_grad ? m->d_lastbias : nullptr, blk ? &m->pm : nullptr, m->N); }
-    if (with_grad) { m->last_loss_mode = mode; m->bnd_last = bnd ? npix : 0; }
+    if (with_grad) { m->last_loss_mode = focal ? 1 : mode; m->bnd_last = bnd ? npix : 0; }     // (focal: |V| is reported as in the weighted mode)
     const float* reg = nullptr;
     if (l2_rate != 0.f) {
         hipMemsetAsync(m->d_regsum, 0, sizeof(float), s);
         for (auto k : kDecoderKernels) launch_sumsq(Wp(m, k), m->d_regsum, (long long)P(m, k).numel, s);
         reg = m->d_regsum;
     }
-    launch_finalize_loss(m->d_partials, nb, npix, reg, l2_rate, m->d_loss, s, mode == 2 ? &st->kept : nullptr, with_grad ? m->d_terms : nullptr);
+    launch_finalize_loss(m->d_partials, focal ? 1 : nb, npix, reg, l2_rate, m->d_loss, s, mode == 2 ? &st->kept : nullptr, with_grad ? m->d_terms : nullptr);
     if (with_grad) m->have_terms = true;
     if (lov_sort) {
         // L_lov and its gradient: keys, sort, Jaccard scan (the loss, now final), then dlogits += lov_w d L_lov / d logits and the bias column sums
@@ -3442,7 +3459,9 @@ int fcn8s_set_loss(fcn8s_model* m, const float* class_weights, int nweights, flo
     if (!m) return FCN8S_ERR_BAD_ARG;
     int rc = check_loss_args(m, class_weights, nweights, m->C, ohem_thresh, ohem_min_kept, "fcn8s_set_loss"); if (rc) return rc;
     const int mode = ohem_thresh > 0.f ? 2 : class_weights ? 1 : 0;
-    if (mode || m->bnd_R) {                                  // (the boundary weighting alone runs the weighted mode: it must see ones, not the last weights)
+    if (mode == 2 && m->focal_gamma > 0.f)
+        return fail(m, FCN8S_ERR_STATE, "fcn8s_set_loss: OHEM does not combine with the focal loss (fcn8s_set_focal); switch one of them off");
+    if (mode || m->bnd_R) {                                // (the boundary weighting alone runs the weighted mode: it must see ones, not the last weights)
         if (!m->d_cw.grow(64 * sizeof(float), m->stream)) return fail(m, FCN8S_ERR_OOM, "fcn8s_set_loss: out of device memory");
         std::vector<float> w(64, 0.f);
         for (int c = 0; c < m->C; ++c) w[c] = class_weights ? class_weights[c] : 1.f;
@@ -3607,6 +3626,18 @@ int fcn8s_get_entropy_term(fcn8s_model* m, float* term)
     HIPCHK(m, hipStreamSynchronize(m->stream));
     HIPCHK(m, hipMemcpy(&t, m->d_terms + 4, sizeof t, hipMemcpyDeviceToHost));
     if (term) *term = t;
+    return FCN8S_OK;
+}
+
+int fcn8s_set_focal(fcn8s_model* m, float gamma)
+{
+    if (!m) return FCN8S_ERR_BAD_ARG;
+    if (!std::isfinite(gamma) || gamma < 0.f || gamma > 8.f) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_focal: gamma must be 0 (off) or in (0, 8]");
+    if (gamma == 0.f) { m->focal_gamma = 0.f; return FCN8S_OK; }    // off
+    if (fp8_mode(m)) return fp8_refuse_training(m, "fcn8s_set_focal");
+    if (m->loss_mode == 2)
+        return fail(m, FCN8S_ERR_STATE, "fcn8s_set_focal: the focal loss does not combine with OHEM (fcn8s_set_loss); switch one of them off");
+    m->focal_gamma = gamma;
     return FCN8S_OK;
 }
 
@@ -4734,6 +4765,26 @@ int fcn8s_op_entropy_term(void* stream, const float* logits, float* dlogits, con
     take_deferred_error(nullptr);
     launch_entropy_term(logits, dlogits, labels, nullptr, N, (long long)N * HW, C, ncols, pixel_set, first_image, weight, ws, nullptr, term_out, bias_out, 0,
                         (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
+size_t fcn8s_op_focal_xent_work_bytes(void) { return focal_xent_scratch_bytes() + 8; }          // (+ 8: the partials start at the next multiple of 8)
+int fcn8s_op_focal_xent(void* stream, const float* logits, const uint8_t* labels, const float* class_weights_dev, const uint8_t* codes_dev,
+                        const float* table256_dev, float gamma, float* dlogits, float* loss_dev, float* bias_out, int64_t npix, int C, void* work,
+                        size_t work_bytes)
+{
+    if (!logits || !labels || !loss_dev || !work) return fail(nullptr, FCN8S_ERR_BAD_ARG, "focal_xent: null logits, labels, loss_dev or work");
+    if ((((uintptr_t)logits | (uintptr_t)class_weights_dev | (uintptr_t)table256_dev | (uintptr_t)dlogits | (uintptr_t)loss_dev | (uintptr_t)bias_out) & 3) != 0)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "focal_xent: logits, class weights, table, dlogits, loss_dev and bias_out must be 4-byte aligned");
+    if (!std::isfinite(gamma) || !(gamma > 0.f) || gamma > 8.f)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "focal_xent: gamma must be in (0, 8] (gamma 0 is the plain cross-entropy: fcn8s_op_softmax_xent, _ex, _px)");
+    if (C < 2 || C > 64) return fail(nullptr, FCN8S_ERR_BAD_ARG, "focal_xent: C must be in 2 .. 64");
+    if (!codes_dev != !table256_dev) return fail(nullptr, FCN8S_ERR_BAD_ARG, "focal_xent: codes and table must both be given or both be NULL");
+    if (npix <= 0 || npix > (1LL << 40)) return fail(nullptr, FCN8S_ERR_SHAPE, "focal_xent: npix must be positive (and at most 2^40)");
+    if (work_bytes < fcn8s_op_focal_xent_work_bytes()) return fail(nullptr, FCN8S_ERR_BAD_ARG, "focal_xent: work is smaller than fcn8s_op_focal_xent_work_bytes()");
+    char* ws = (char*)(((uintptr_t)work + 7) & ~(uintptr_t)7);
+    take_deferred_error(nullptr);
+    launch_focal_xent(logits, dlogits, labels, class_weights_dev, codes_dev, table256_dev, nullptr, 1, (long long)npix, C, gamma, 1.0f / (float)npix, ws, nullptr,
+                      loss_dev, nullptr, bias_out, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
 size_t fcn8s_op_strong_augment_work_bytes(int N) { return strong_augment_work_bytes(N); }

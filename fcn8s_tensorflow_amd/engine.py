@@ -134,6 +134,7 @@ class Engine:
         self.soft_target_config = None       # set_soft_targets: the soft-target term's configuration, dict(weight, temperature, pixels) (None = off)
         self._soft_targets = None            # bind_soft_targets: the bound tensor, kept alive until a training loss has consumed it
         self.entropy_config = None           # set_entropy_term: the entropy term's configuration, dict(weight, pixels, first_image) (None = off)
+        self.focal_config = None             # set_focal: the focal loss's configuration, dict(gamma) (None = off)
         self._loss_shape = None              # (N, H, W) of the last training loss (boundary_codes)
         self.grad_clip = None                # set_grad_clip: the global-norm clip's max_norm (None = off; inf = the non-finite guard alone)
         self.ema_config = None               # set_ema: the parameter average's configuration, dict(decay, warmup) (None = off)
@@ -573,6 +574,56 @@ class Engine:
                                             C.c_void_p(work.data_ptr()), nbytes, C.c_void_p(term.data_ptr()),
                                             C.c_void_p(b.data_ptr()) if bias else None))
         return term, b
+
+    def set_focal(self, gamma=None):
+        """The focal loss of training (fcn8s_set_focal; definitions in include/fcn8s_hip.h, restated in loss.py): the per-pixel cross-entropy
+        l_p becomes (1 - p_y)^gamma l_p, `gamma` in (0, 8] (2 is the paper's default).  The class weights of set_loss act as its alpha, the
+        boundary table acts on it, the Lovász, soft-target and entropy terms add behind it; OHEM and the focal loss refuse each other.  No gamma
+        (or 0) switches it off.  Host state only: nothing is launched, allocated or waited for.  Evaluation and prediction keep the reference's
+        loss."""
+        g = loss_mod.validate_focal(gamma, (self.loss_config or {}).get('ohem_thresh'))
+        L.check(L.lib.fcn8s_set_focal(self.h, g), self.h)
+        self.focal_config = None if g == 0.0 else dict(gamma=g)
+
+    def focal_xent_op(self, logits, labels, gamma, class_weights=None, codes=None, table=None, dlogits=None, bias=False):
+        """One `fcn8s_op_focal_xent` call on device tensors, on the current stream: `logits` float32 [N, ..., C] (contiguous), `labels` uint8
+        [N, ...] of the same pixels, `class_weights` a float32 device tensor of C weights or None, `codes` (uint8, the labels' shape) and `table`
+        (256 float32) both given or both None.  `dlogits` (a float32 tensor of the logits' shape, or None) is overwritten by the gradient.
+        Returns (loss, bias | None): device tensors of 1 and (with `bias`) C floats; nothing synchronises.  The scratch is kept on the engine."""
+        torch = self.torch
+        g = loss_mod.validate_focal(gamma)
+        if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() < 2 or not logits.is_contiguous():
+            raise ValueError("logits have to be a contiguous float32 tensor [N, ..., C] on the GPU")
+        if not isinstance(labels, torch.Tensor) or labels.device != logits.device or labels.dtype != torch.uint8 or not labels.is_contiguous() \
+                or tuple(labels.shape) != tuple(logits.shape[:-1]):
+            raise ValueError("labels have to be a contiguous uint8 tensor of the logits' pixels on the same device")
+        if dlogits is not None and (not isinstance(dlogits, torch.Tensor) or dlogits.device != logits.device or dlogits.dtype != torch.float32
+                                    or tuple(dlogits.shape) != tuple(logits.shape) or not dlogits.is_contiguous()):
+            raise ValueError("dlogits have to be a contiguous float32 tensor of the logits' shape on the same device")
+        Cn = int(logits.shape[-1])
+        if class_weights is not None and (not isinstance(class_weights, torch.Tensor) or class_weights.device != logits.device
+                                          or class_weights.dtype != torch.float32 or class_weights.numel() != Cn or not class_weights.is_contiguous()):
+            raise ValueError("class_weights have to be a contiguous float32 tensor of C = %d weights on the same device" % Cn)
+        if (codes is None) != (table is None):
+            raise ValueError("codes and table have to be given together")
+        if codes is not None:
+            if not isinstance(codes, torch.Tensor) or codes.device != logits.device or codes.dtype != torch.uint8 or not codes.is_contiguous() \
+                    or tuple(codes.shape) != tuple(labels.shape):
+                raise ValueError("codes have to be a contiguous uint8 tensor of the labels' shape on the same device")
+            if not isinstance(table, torch.Tensor) or table.device != logits.device or table.dtype != torch.float32 or table.numel() != 256 \
+                    or not table.is_contiguous():
+                raise ValueError("table has to be a contiguous float32 tensor of 256 weights on the same device")
+        nbytes = int(L.lib.fcn8s_op_focal_xent_work_bytes())
+        work = getattr(self, "_focal_work", None)
+        if work is None or work.numel() < nbytes or work.device != logits.device:
+            work = self._focal_work = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+        b = torch.empty(Cn, dtype=torch.float32, device=logits.device) if bias else None
+        stream = C.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        L.check(L.lib.fcn8s_op_focal_xent(stream, ptr(logits), ptr(labels), ptr(class_weights), ptr(codes), ptr(table), g, ptr(dlogits), ptr(loss), ptr(b),
+                                          int(labels.numel()), Cn, ptr(work), nbytes))
+        return loss, b
 
     def loss_stats(self):
         """|V|, |K| and the threshold t of the last training loss (fcn8s_get_loss_stats; synchronises)."""

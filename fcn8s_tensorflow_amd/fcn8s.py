@@ -246,7 +246,8 @@ class FCN8s:
               unlabeled_augment=None,
               entropy_weight=0.0,
               entropy_pixels='unlabeled',
-              entropy_images='all'):
+              entropy_images='all',
+              focal_gamma=0.0):
         '''Trains the model; arguments as fcn8s_tensorflow.py:424-503.  Summaries are written as TensorBoard
         event files (`<summaries_dir>/<summaries_name>[_eval]/events.out.tfevents.*`: total_loss, learning_rate and
         mean / stddev / max / min / histogram of the ten watched weight-bias pairs, :331-366) and, for reading
@@ -317,6 +318,13 @@ class FCN8s:
         term to the M unlabelled images of the joined batch, so that the void pixels of the labelled images stay out.  It combines with
         `teacher` and with every `unlabeled_*` keyword.  The engine's previous setting is restored when train() returns or raises.
         `entropy_loss` (the unscaled term, the last micro-batch's) joins the recorded scalars on the steps that are recorded.
+        `focal_gamma` in (0, 8] turns the cross-entropy into the focal loss (Lin et al. 2017) for the duration of the call (Engine.set_focal,
+        loss.py): every pixel's l_p is scaled by (1 - p_y)^gamma, so that the many easy pixels and confident pseudo-labels stop dominating the
+        gradient; the denominator stays P.  2 is the paper's default, not a value tuned here.  `class_weights` act as its alpha, the boundary
+        table acts on it, the Lovász, soft-target and entropy terms add behind it; together with `ohem_thresh` (or an OHEM configuration the
+        engine already has) it raises, because both address the same thing.  0, the default, is off: nothing new is launched or allocated and
+        the step is bit for bit what it was.  The evaluations keep reporting the reference's loss, and the engine's previous setting is
+        restored when train() returns or raises.
         Not done here: a separate weight on the unlabelled term (change M), a per-class or per-pixel weight or a threshold on the entropy,
         ADVENT's adversarial branch, CutMix boxes, geometric strong augmentation, augmenting or
         mixing the labelled images, and any change to `BatchGenerator`.'''
@@ -338,6 +346,9 @@ class FCN8s:
         unlabeled = self._resolve_unlabeled(unlabeled_generator, unlabeled_labeler, unlabeled_thresholds, unlabeled_predict, unlabeled_mix,
                                             unlabeled_seed, teacher, bool(ema_d), unlabeled_augment)
         entropy = self._resolve_entropy(entropy_weight, entropy_pixels, entropy_images, unlabeled_generator)
+        focal = loss_mod.validate_focal(focal_gamma, ohem_thresh if custom_loss else (self.engine.loss_config or {}).get('ohem_thresh'))
+        if not focal and self.engine.focal_config is not None:
+            loss_mod.validate_focal(self.engine.focal_config['gamma'], ohem_thresh)     # the engine's own focal setting meets this call's OHEM
         if eval_dataset not in ('train', 'val'):
             raise ValueError("`eval_dataset` must be one of 'train' or 'val', but is '{}'.".format(eval_dataset))
         if eval_dataset == 'val' and (val_generator is None or val_steps is None):
@@ -367,6 +378,7 @@ class FCN8s:
         prev_ema = self.engine.ema_config
         prev_soft = self.engine.soft_target_config
         prev_entropy = self.engine.entropy_config
+        prev_focal = self.engine.focal_config
         teacher_engine = teacher.engine if (teacher_fn is not None and isinstance(teacher, FCN8s)) else None
         teacher_was_frozen = bool(teacher_engine.get_option("frozen")) if teacher_engine is not None else False
         labeler_engine = unlabeled.labeler_engine if unlabeled is not None else None
@@ -389,6 +401,8 @@ class FCN8s:
                 self.engine.set_lovasz(lovasz_weight, ce_weight, lovasz_per_image, lovasz_classes)
             if custom_boundary:
                 self.engine.set_boundary_loss(boundary_table, boundary_R)
+            if focal:
+                self.engine.set_focal(focal)
             if entropy is not None and not entropy['per_batch']:
                 self.engine.set_entropy_term(entropy['weight'], entropy['pixels'])
             if unlabeled is not None:
@@ -425,6 +439,8 @@ class FCN8s:
                 self.engine.set_grad_clip(prev_clip)
             if ema_d:
                 self.engine.set_ema(**(prev_ema or dict(decay=None)))
+            if focal:                                   # (in front of the loss: a previous OHEM configuration comes back only with the focal loss off)
+                self.engine.set_focal(**(prev_focal or {}))
             if custom_loss:
                 self.engine.set_loss(**(prev_loss or {}))
             if custom_lovasz:

@@ -3,7 +3,7 @@ a float64 restatement of both modes for the tests, and class-weight recipes comp
 term (fcn8s_set_lovasz) has its validation and float64 restatement behind the boundary-weighted cross-entropy
 (fcn8s_set_boundary_loss; fcn8s_op_boundary_distance, fcn8s_op_softmax_xent_px): its table builders, the NumPy route of its distance codes,
 its validation and the facade's argument rule (resolve_boundary).  The soft-target term (fcn8s_set_soft_targets) follows with its
-validation and its float64 and float32 restatements, and the entropy term (fcn8s_set_entropy_term) closes the file in the same way.
+validation and its float64 and float32 restatements, the entropy term (fcn8s_set_entropy_term) comes next in the same way, and the focal loss (fcn8s_set_focal) closes the file.
 
 P = pixels of the batch, V = the valid pixels (label id < C), l_p = the per-pixel loss m + log(sum exp(v - m)) - v[y_p] (>= 0),
 w_c = the class weights.
@@ -527,3 +527,92 @@ def entropy_restate(logits, labels, weight=1.0, pixels='unlabeled', ncols=None, 
     if ft is np.float32:
         term = float(np.float32(term))
     return dict(term=term, loss=w * term, h=h, dlogits=d, bias=d.astype(np.float64).sum(0), used=used)
+
+
+# ---- the focal loss (fcn8s_set_focal, fcn8s_op_focal_xent; the definition is in include/fcn8s_hip.h) -------------------------------------
+FOCAL_GAMMA_MAX = 8.0
+
+
+def validate_focal(gamma, ohem_thresh=None):
+    """-> float32 gamma as a float (0.0 = off); ValueError for what fcn8s_set_focal rejects: a gamma that is no number, not finite, negative or
+    above 8, and gamma > 0 together with an OHEM threshold (both address the easy pixels; the library refuses the pair with FCN8S_ERR_STATE).
+    `gamma` None or 0 is "off"."""
+    if gamma is None:
+        g = 0.0
+    else:
+        if isinstance(gamma, bool):
+            raise ValueError("`gamma` must be a number, got {!r}".format(gamma))
+        try:
+            with np.errstate(over='ignore'):
+                g = float(np.float32(gamma))
+        except (TypeError, ValueError):
+            raise ValueError("`gamma` must be a number, got {!r}".format(gamma))
+    if not math.isfinite(g) or g < 0.0 or g > FOCAL_GAMMA_MAX:
+        raise ValueError("the focal gamma must be 0 (off) or in (0, 8], got {!r}".format(gamma))
+    if g > 0.0 and ohem_thresh is not None and ohem_thresh != 0:
+        raise ValueError("the focal loss (gamma = {!r}) does not combine with OHEM (ohem_thresh = {!r}): use one of them".format(gamma, ohem_thresh))
+    return g
+
+
+def focal_restate(logits, labels, gamma, class_weights=None, pixel_weights=None, dtype=np.float64, gscale=None):
+    """The focal loss restated: logits (P, C), labels (P,) ids (>= C: ignored), `gamma` in (0, 8], `class_weights` (C,) or None (all 1),
+    `pixel_weights` (P,) = the float32 b_p of the boundary weighting or None: the weight of a pixel is the float32 product float32(w_{y_p}) * b_p,
+    as the kernel forms it.  `dtype` float32: the header's definition step by step, every operation rounded to float32 (classes summed in order, no
+    fused product), w_p (f l) summed in float64; float64: the same formulas in double -- the reference of the tests, and its distance to the float32
+    form is the scale of what fp32 can be asked for.  `gscale` (default 1 / P, formed in `dtype`) = ce_weight / P of the model.
+    -> dict(loss = L_foc, dlogits (P, C), bias (C,) = its column sums (float64 sums), f (P,) = t u, a (P,) (both 0 on ignored pixels), valid (P,) bool)."""
+    g = validate_focal(gamma)
+    if g == 0.0:
+        raise ValueError("gamma = 0 is the plain cross-entropy (loss.restate)")
+    ft = np.dtype(dtype).type
+    if ft not in (np.float64, np.float32):
+        raise ValueError("dtype must be float64 or float32")
+    z = np.asarray(logits)
+    if z.ndim != 2:
+        raise ValueError("`logits` must be (P, C), got %s" % (z.shape,))
+    P, C = z.shape
+    lab = np.asarray(labels).reshape(-1).astype(np.int64)
+    if lab.size != P:
+        raise ValueError("`labels` must hold one id per row of `logits` (%d), got %d" % (P, lab.size))
+    valid = lab < C
+    y = np.where(valid, lab, 0)
+    w = np.ones(P, np.float32) if class_weights is None else np.asarray(class_weights, np.float32).reshape(-1)[y]
+    if pixel_weights is not None:
+        b = np.asarray(pixel_weights, np.float32).reshape(-1)
+        if b.size != P:
+            raise ValueError("`pixel_weights` must hold one weight per pixel (%d), got %d" % (P, b.size))
+        w = (w * b).astype(np.float32)
+    w = w.astype(ft)
+    gam = ft(g)
+    gs = (ft(1.0) / ft(P)) if gscale is None else ft(gscale)
+    tiny = ft(np.finfo(np.float32).tiny)                       # FLT_MIN in both forms
+    z = z.astype(ft)
+    rows = np.arange(P)
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore', under='ignore'):
+        m = z.max(1)
+        e = np.exp((z - m[:, None]).astype(ft)).astype(ft)
+        S = np.zeros(P, ft)
+        R = np.zeros(P, ft)
+        for c in range(C):                                    # classes summed in order; R skips y
+            S = (S + e[:, c]).astype(ft)
+            R = np.where(y == c, R, (R + e[:, c]).astype(ft))
+        l = ((m + np.log(S).astype(ft)).astype(ft) - z[rows, y]).astype(ft)
+        u = (R / S).astype(ft)
+        sy = (e[rows, y] / S).astype(ft)
+        t = np.exp(((gam - ft(1.0)) * np.log(np.maximum(u, tiny)).astype(ft)).astype(ft)).astype(ft)
+        f = (t * u).astype(ft)
+        a = (t * (u + (gam * (l * sy).astype(ft)).astype(ft)).astype(ft)).astype(ft)
+        zero = u == 0
+        f = np.where(zero, ft(0.0), f)
+        a = np.where(zero, ft(0.0), a)
+        fl = (f * l).astype(ft)
+        cp = ((gs * w).astype(ft) * a).astype(ft)
+        d = (e * (cp / S).astype(ft)[:, None]).astype(ft)
+        d[rows, y] = -((cp * u).astype(ft))
+    d[~valid] = 0.0
+    f = np.where(valid, f, ft(0.0))
+    a = np.where(valid, a, ft(0.0))
+    loss = float(np.where(valid, w.astype(np.float64) * fl.astype(np.float64), 0.0).sum() / float(P))      # (zeros, not a selection: one summation order)
+    if ft is np.float32:
+        loss = float(np.float32(loss))
+    return dict(loss=loss, dlogits=d, bias=d.astype(np.float64).sum(0), f=f, a=a, valid=valid)

@@ -347,6 +347,51 @@ size_t fcn8s_op_entropy_term_work_bytes(void);
 int fcn8s_op_entropy_term(void* stream, const float* logits, float* dlogits, const uint8_t* labels, int N, int64_t HW, int C, int ncols, int pixel_set,
                           int first_image, float weight, void* work, size_t work_bytes, float* term_out, float* bias_out);
 
+/* ---- the training objective: the focal loss (Lin, Goyal, Girshick, He, Dollár, ICCV 2017), the smooth counterpart of OHEM -----------------------------
+ * Definitions, per training loss on each rank's own batch:
+ *   P = N*H*W pixels, logits z over the library's C columns, labels y_p (ids >= C: ignored, no loss and a gradient row of zeros).  gamma: a float with
+ *   0 < gamma <= 8 (0: off).  w_p = w_{y_p}, the class weight of fcn8s_set_loss (1 without one); under fcn8s_set_boundary_loss w_p = fl(w_{y_p} *
+ *   table[code(p)]), exactly as the weighted mode forms it.  Class weights so act as the alpha of the alpha-balanced focal loss.
+ *   Per valid pixel, in fp32 with expf and logf, classes summed in order, no product contracted into a sum:
+ *     m = max_c z_c;  e_c = expf(z_c - m);  S = sum_c e_c;  l = (m + logf(S)) - z_y            (the cross-entropy's own l_p, >= 0)
+ *     R = sum_{c != y} e_c (class order, y skipped);  u = R / S (= 1 - s_y, with no subtraction);  s_y = e_y / S
+ *     u == 0:  f = 0, a = 0
+ *     else:    t = expf((gamma - 1) * logf(max(u, FLT_MIN)));  f = t * u;  a = t * (u + gamma * (l * s_y))
+ *   L_foc = (1/P) sum_{p valid} w_p (f l): the float product f l times the float w_p, multiplied and summed in double (per thread, then per block, then
+ *   over the blocks in a fixed order); the sum is divided by P and rounded to float once.  The denominator is P, as the cross-entropy's, so equal
+ *   data-parallel shards keep matching the big batch.
+ *   Gradient: d(u^gamma l)/dz_c = (s_c - [c = y]) (u^gamma + gamma l s_y u^(gamma - 1)), so a is the scalar that multiplies the cross-entropy's
+ *   gradient row.  g_p = gscale * w_p (gscale = ce_weight / P as the cross-entropy forms it);  c_p = g_p * a;
+ *     dlogits[p,c] = e_c * (c_p / S) for c != y;   dlogits[p,y] = -(c_p * u)                   (the y column never comes from s_y - 1)
+ *   A padding column's -1e30 logit gives e = 0 and a gradient of exactly 0.  gamma = 1 gives t = 1 exactly.  Non-finite logits behave as in the
+ *   cross-entropy.
+ *   L = ce_weight * L_foc + (the Lovász, soft-target, entropy and L2 terms as before): L_foc stands in L_ce's place, in the `ce` slot of
+ *   fcn8s_get_loss_terms too; fcn8s_get_loss_stats reports |V|, kept = |V| and threshold 0, with or without a configuration of fcn8s_set_loss's.
+ * OHEM together with gamma > 0 is refused, because both address the same thing: fcn8s_set_focal returns FCN8S_ERR_STATE while an OHEM threshold is
+ * set, and fcn8s_set_loss returns it for an OHEM threshold while gamma > 0.
+ * One launch in the cross-entropy's place plus a one-block reduction; it works on the logits where they lie (plain or in the blocked layout of
+ * "tconv_gemm") and moves the bytes of the weighted cross-entropy.  Deterministic whatever the `deterministic` option says: per-block partial sums
+ * reduced in a fixed order, no float atomics.  The setting acts on the training losses only (fcn8s_forward_loss, fcn8s_train_step, each micro-batch of
+ * an accumulated update); evaluation, the metrics and prediction keep the reference's loss.  The per-block partials (about 280 KB) and, without a
+ * configuration of fcn8s_set_loss's, the loss state that holds |V| are allocated on first use and counted in "workspace_allocations".  Profile group
+ * "focal_xent" (in place of "softmax_xent"), (8 C + 1) bytes per pixel, + 1 with the boundary codes.
+ * fcn8s_set_focal: host state only (no launch, no allocation, no synchronisation).  gamma 0 switches it off -- then nothing new is launched or
+ *   allocated and the step is bit for bit what it was.  FCN8S_ERR_BAD_ARG for a non-finite gamma, gamma < 0 or gamma > 8; FCN8S_ERR_STATE for
+ *   switching it on under FCN8S_PREC_FP8_INFER or while OHEM is configured.  The setting survives fcn8s_set_precision, fcn8s_set_option and the
+ *   other loss setters.
+ * fcn8s_op_focal_xent: the same kernel and reduction on the caller's buffers, stream-ordered, allocating nothing: logits device float32 [npix, C] in
+ *   the plain layout at any 4-byte alignment, labels (and codes) device uint8 [npix] at any alignment, class_weights_dev = C device floats or NULL (all
+ *   1), codes_dev and table256_dev (256 device floats) both set or both NULL, work = fcn8s_op_focal_xent_work_bytes() bytes of device scratch at any
+ *   alignment (work_bytes = what is passed), gscale = 1 / (float)npix.  dlogits (may be NULL) is STORED, not added to: this is the cross-entropy's
+ *   role.  loss_dev[0] = L_foc; bias_out (may be NULL) = the C column sums of dlogits.  FCN8S_ERR_BAD_ARG: a NULL logits, labels, loss_dev or work, a
+ *   misaligned float pointer, gamma not in (0, 8] (gamma = 0 is what the plain ops compute), C outside 2 .. 64, codes without a table or a table
+ *   without codes, work_bytes too small; FCN8S_ERR_SHAPE: npix <= 0.  A refused call leaves every output untouched.                            */
+int fcn8s_set_focal(fcn8s_model* m, float gamma);
+size_t fcn8s_op_focal_xent_work_bytes(void);
+int fcn8s_op_focal_xent(void* stream, const float* logits, const uint8_t* labels, const float* class_weights_dev, const uint8_t* codes_dev,
+                        const float* table256_dev, float gamma, float* dlogits, float* loss_dev, float* bias_out, int64_t npix, int C, void* work,
+                        size_t work_bytes);
+
 /* ---- the update: gradient accumulation over micro-batches, a global-norm clip and a non-finite guard (not in the reference, whose step is
  * one batch, one tf.train.AdamOptimizer.minimize, fcn8s_tensorflow.py:256) ------------------------------------------------------------------
  * Accumulation.  The model owns one accumulator acc of fcn8s_param_floats() floats, cut into the gradient buffer's buckets; it is allocated at
