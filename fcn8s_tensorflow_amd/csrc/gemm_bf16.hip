@@ -13,6 +13,7 @@
 // Block = 256 threads (4 wave64) -> 128 pixels x 128 couts, wave tile 64 x 64 = 2 x 2 MFMA tiles, 8 MFMAs per wave
 // per K-tile, global -> register -> LDS double buffering with one barrier per K-tile.
 #include "fcn8s_internal.h"
+#include "split_route.h"
 #include <string>
 #include <algorithm>
 
@@ -241,6 +242,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const Bf16ConvArgs p)
 // loop without its loads reaches 1200, its MFMAs alone 1320 -- the data-dependent power ceiling of the bf16 pipe (guide 5.4 rule 25), not 2500.
 namespace {
 constexpr int G_BM = 256, G_BN = 256, G_BK = 32, G_ROWB = G_BK * 2, G_ABYTES = G_BM * G_ROWB;
+static_assert(fcn8s::kBf16KTile == G_BK && fcn8s::kBf16RowTile == G_BM, "split_route.h restates the K-tile and the row tile");
 
 static __device__ __forceinline__ void glds16b(const void* sbase, unsigned voff, unsigned lds_byte_off)
 {
@@ -994,10 +996,9 @@ bool launch_conv_bf16_256(const Bf16Conv256Args& a0, hipStream_t s)
         // ... and the forward pass of the same shapes at batch 1 (bias, ReLU, the consumer's copy of an UNPADDED map): the slabs are added by splitk_epilogue_kernel
         // (note: the bias is added FIRST there, before the slabs -- in the one-pass kernel it is added last; both are the fp32 sum of the same terms to round-off)
         const bool fwd_epi = !plain && a.K != 3 && !a.addend && !a.mask && !a.dropout && !a.colpart && (a.y || a.yb) && (!a.yb || a.yb_pad == 0) && a.Cout % 8 == 0;      // (3 x 3 layers: the flat-position kernel)
-        if (a.any_shape && fwd_epi && a.Cout % 256 == 0 && rt0 * (a.Cout / 256) <= 64 && nkt_all >= 64) {
-            long long ks = 256 / (rt0 * (a.Cout / 256));
-            if (ks > 8) ks = 8;
-            if (ks > nkt_all / 16) ks = nkt_all / 16;            // at least 16 K-tiles per slab
+        // (how many slabs: bf16_gemm_fwd_slabs, split_route.h -- one image's tile count, never the batch's: an image's bits must not depend on its batch)
+        if (a.any_shape && fwd_epi) {
+            const long long ks = fcn8s::bf16_gemm_fwd_slabs(fcn8s::ConvShape{a.N, a.H, a.W, a.Cin, a.Cout, a.K});
             float* part = ks >= 2 ? det_scratch(s, (size_t)(ks * a.M * a.Cout)) : nullptr;
             if (part) {
                 Bf16Conv256Args k = a;
@@ -1041,9 +1042,9 @@ bool launch_conv_bf16_256(const Bf16Conv256Args& a0, hipStream_t s)
         const unsigned blocks = (unsigned)(((R + tbm - 1) / tbm) * (a.Cout / tbn));
         // few blocks behind many K-tiles (conv5_x of one image: 24 blocks x 48 K-tiles, 0.046 -> 0.030 ms; conv4_x's 72 blocks gained nothing from three slabs): split K over blockIdx.y into slabs, forward epilogue only
         // (bias, ReLU, fp32 pixels and / or the consumer's copy); the sum is bias LAST here as in the one-pass kernel, its terms in slab order
-        const long long nkt_all = 3LL * (a.Cin / G_BK);
-        if (tbn == 64 && blocks <= 48 && nkt_all >= 24 && !a.addend && !a.mask && !a.mask16 && !a.dropout && !a.colpart && (a.y || a.yb)) {
-            long long ks = 256 / blocks; if (ks > 8) ks = 8; if (ks > nkt_all / 6) ks = nkt_all / 6;
+        // (how many slabs: bf16_rows_slabs, split_route.h -- one image alone; a batch of two or more runs one pass whatever its size)
+        if (!a.addend && !a.mask && !a.mask16 && !a.dropout && !a.colpart && (a.y || a.yb)) {
+            const long long ks = fcn8s::bf16_rows_slabs(fcn8s::ConvShape{a.N, a.H, a.W, a.Cin, a.Cout, a.K}, tbn, tbm);
             float* part = ks >= 2 ? det_scratch(s, (size_t)(ks * R * a.Cout)) : nullptr;
             if (part) {
                 Bf16Conv256Args k = a; k.ksplit = (int)ks; k.part = part;

@@ -726,7 +726,7 @@ static void conv_direct(fcn8s_model* m, const char* group, IgemmArgs a, const fl
     // 1x1 score heads: one skinny dimension (skinny.hip); everything else goes through the general tile kernels
     auto run = [&]() {
         if (K == 1 && !real_cin && !a.addend && !a.relu && !a.dropout) {
-            if (Cout <= 32 && !a.mask && launch_head_fwd(x, w, a.bias, y, a.M, Cin, Cout, a.alpha, s, m ? m->d_wino_u : nullptr, m ? m->ufl : 0)) return;      // (the filter-bank scratch is idle between convolutions)
+            if (Cout <= 32 && !a.mask && launch_head_fwd(x, w, a.bias, y, a.M, N, Cin, Cout, a.alpha, s, m ? m->d_wino_u : nullptr, m ? m->ufl : 0)) return;      // (the filter-bank scratch is idle between convolutions)
             if (Cin <= 32 && !a.bias && launch_head_dgrad(x, w, a.mask, a.mask_scale, y, a.M, Cout, Cin, a.alpha, s)) return;
         }
         launch_igemm(a, 1, s);
@@ -4281,6 +4281,19 @@ int fcn8s_op_conv2d(void* stream, const float* x, const float* w, const float* b
 {
     if (Cin % 4 || Cout % 4 || K % 2 == 0) return fail(nullptr, FCN8S_ERR_BAD_ARG, "conv2d: Cin, Cout must be multiples of 4 and K odd");
     FwdEpi e; e.bias = bias; e.relu = relu;
+    if (K == 1 && Cout <= 32 && !relu && N > 0 && H > 0 && W > 0) {
+        // a score head: a bare model whose idle filter-bank scratch is large enough for the eight-slab form, as a model's is -- whether
+        // the launch splits is then launch_head_fwd's decision (split_route.h), as in a model, and not a matter of a missing scratch
+        hipStream_t s = (hipStream_t)stream;
+        fcn8s_model mm; fcn8s_model* m = &mm;
+        m->stream = s; m->N = N; m->H = H; m->W = W;
+        m->precision = t_op_split == 3 ? FCN8S_PREC_F32X3 : t_op_split == 2 ? FCN8S_PREC_F32X2 : FCN8S_PREC_F32;
+        m->ufl = (size_t)8 * N * H * W * Cout;
+        if (!m->d_wino_u.grow(m->ufl * sizeof(float), s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+        conv_fwd(m, "", x, w, y, N, H, W, Cin, Cout, K, e, s);
+        hipStreamSynchronize(s);
+        OPCHK(); return FCN8S_OK;
+    }
     conv_fwd(nullptr, "", x, w, y, N, H, W, Cin, Cout, K, e, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }

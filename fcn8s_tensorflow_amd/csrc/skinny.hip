@@ -6,6 +6,7 @@
 // in L1/L2), and the reduction dimension is split over the waves of a block (forward, weight gradient) so that even the
 // 512-row bs1 problem fills the chip.  Summation order is fixed (LDS reduction in wave order) in the forward kernel.
 #include "fcn8s_internal.h"
+#include "split_route.h"
 
 namespace fcn8s {
 
@@ -230,12 +231,14 @@ __global__ __launch_bounds__(256) void head_fwd_reduce_kernel(const float* __res
     y[i] = s + (bias ? bias[i % C] : 0.f);
 }
 template <int C>
-static bool launch_head_fwd_c(const float* x, const float* w, const float* bias, float* y, long long M, int K, float alpha, hipStream_t s, float* scratch, size_t scratch_floats)
+static bool launch_head_fwd_c(const float* x, const float* w, const float* bias, float* y, long long M, int images, int K, float alpha, hipStream_t s, float* scratch, size_t scratch_floats)
 {
     const unsigned blocks = (unsigned)((M + 31) / 32);
-    // few row blocks and a long reduction: split K over 8 blocks as well (deterministic two-pass sum)
-    constexpr int SPLITS = 8;
-    if (blocks <= 64 && K % (SPLITS * 16 * 32) == 0 && scratch && scratch_floats >= (size_t)SPLITS * M * C && (M * C) % 4 == 0) {
+    // few row blocks and a long reduction: split K over 8 blocks as well (deterministic two-pass sum).  Whether: head_fwd_splits (split_route.h), which
+    // sees one image's rows and the image count -- a batch of two or more runs one pass whatever its size, so that an image's bits do not depend on it
+    constexpr int SPLITS = fcn8s::kHeadSplits;
+    const bool split = images >= 1 && M % images == 0 && fcn8s::head_fwd_splits(fcn8s::ConvShape{images, 1, (int)(M / images), K, C, 1}) == SPLITS;
+    if (split && scratch && scratch_floats >= (size_t)SPLITS * M * C) {
         hipLaunchKernelGGL((head_fwd_kernel<16, C>), dim3(blocks, SPLITS), dim3(1024), 0, s, x, w, bias, y, M, K, alpha, scratch);
         hipLaunchKernelGGL(head_fwd_reduce_kernel, dim3((unsigned)((M * C + 255) / 256)), dim3(256), 0, s, scratch, bias, y, M * C, C, SPLITS);
         return true;
@@ -246,11 +249,11 @@ static bool launch_head_fwd_c(const float* x, const float* w, const float* bias,
     else return false;
     return true;
 }
-bool launch_head_fwd(const float* x, const float* w, const float* bias, float* y, long long M, int K, int C, float alpha, hipStream_t s, float* scratch, size_t scratch_floats)
+bool launch_head_fwd(const float* x, const float* w, const float* bias, float* y, long long M, int images, int K, int C, float alpha, hipStream_t s, float* scratch, size_t scratch_floats)
 {
     if (M < 1) return false;
-    if (C == 20) return launch_head_fwd_c<20>(x, w, bias, y, M, K, alpha, s, scratch, scratch_floats);
-    if (C == 4) return launch_head_fwd_c<4>(x, w, bias, y, M, K, alpha, s, scratch, scratch_floats);
+    if (C == 20) return launch_head_fwd_c<20>(x, w, bias, y, M, images, K, alpha, s, scratch, scratch_floats);
+    if (C == 4) return launch_head_fwd_c<4>(x, w, bias, y, M, images, K, alpha, s, scratch, scratch_floats);
     return false;
 }
 

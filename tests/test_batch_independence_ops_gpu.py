@@ -1,0 +1,360 @@
+"""An image's forward bits do not depend on its batch -- route by route, at op level, exactly.
+
+conv_route.h (wino_tile_for, gemm_out_fused64) and split_route.h state the invariant: the arithmetic applied to an image must not depend on how
+many others share its batch (the gradient of a batch equals the mean over its halves, a data-parallel shard computes the big batch's bits).  A
+comparison with float64 to 1e-5 cannot see a summation order that changes with N; these tests can.  Every case runs one op entry point on
+x[:N] for several N, on single images and on an interior pair, and asserts on the uint32 view of the fp32 outputs:
+
+  A  among batches of two or more: image i has the same bits in every batch with N >= 2 that contains it.  No tolerance.
+  B  one image alone (N = 1) has them too -- unless (route, shape) is in SINGLE_IMAGE_EXCEPTIONS, which names the rule that says so
+     (a named function of csrc/split_route.h or csrc/conv_route.h; tests/test_split_route_host.py checks the names).  An excepted case
+     is held to 1e-5 of the output's largest value instead: the same terms in another order.
+  C  placement: with every image but one zeroed, the others come out as max(bias, 0) (bias with relu = 0; zero for a gradient or a pool;
+     bias + addend for the transposed convolution) bit for bit, and the live image as in the full batch: the tile-to-image bookkeeping
+     where a row tile straddles two images.
+
+Shapes: (a) per route one ragged map -- H W or (H + 2)(W + 2) no multiple of the row tile, so tiles straddle images -- at N in {1, 2, 3, 5};
+(b) for each launcher that used to read the total block count (split_route.h) one case whose batch sizes straddle every threshold of the
+inline formulas those rules replaced; the comment on a case says which decision changed between which N.  tests/test_split_route_host.py
+proves, from a transcription of those formulas, that the (b) cases do straddle them.
+
+fp32 launches that combine split-K partials in atomics (launch_igemm_cfg: a linear epilogue behind >= 64 K-tiles) are not reproducible from
+run to run and are kept out: the direct fp32 cases run relu = 1 (no linear epilogue), the score heads run skinny.hip's kernels (no atomics),
+and the Winograd cases stay below 64 K-tiles of 16 (Cin < 1024; 9 Cin < 1024 for the 7x7 sub-filter form)."""
+import contextlib
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from fcn8s_tensorflow_amd import fp8  # noqa: E402
+
+
+def _lib():
+    from fcn8s_tensorflow_amd import _lib
+    return _lib
+
+
+def dev(a):
+    return torch.as_tensor(np.ascontiguousarray(a)).cuda()
+
+
+def ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def rel_err(a, b):
+    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
+    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
+
+
+@contextlib.contextmanager
+def op_context(**options):
+    L = _lib()
+    saved = {}
+    try:
+        for k, v in options.items():
+            cur = C.c_int64(-1)
+            L.check(L.lib.fcn8s_get_option(None, k.encode(), C.byref(cur)))
+            saved[k] = cur.value
+            L.check(L.lib.fcn8s_set_option(None, k.encode(), v))
+        yield
+    finally:
+        for k, v in saved.items():
+            L.lib.fcn8s_set_option(None, k.encode(), v)
+
+
+# (route, (H, W, Cin, Cout, K)) -> the rule that lets ONE image alone differ from the same image in a batch.  Every entry is a launch that splits K
+# at N = 1 (batch-1 inference keeps its kernels) and runs one pass from N = 2 on.
+SINGLE_IMAGE_EXCEPTIONS = {
+    ("conv2d/r0", (5, 7, 4096, 20, 1)): "head_fwd_splits",              # 2 blocks of 32 rows behind 4096 channels: 8 slabs alone
+    ("conv2d/r0", (16, 32, 4096, 20, 1)): "head_fwd_splits",            # 16 blocks: 8 slabs alone
+    ("bf16_train_fwd/64", (16, 16, 512, 512, 3)): "bf16_rows_slabs",    # 16 blocks x 48 K-tiles: 8 slabs alone
+    ("bf16_train_dx/64", (16, 16, 512, 512, 3)): "bf16_rows_slabs",
+    ("bf16_train_fwd/64", (16, 16, 2048, 4096, 1)): "bf16_gemm_fwd_slabs",      # 16 tiles x 64 K-tiles: 4 slabs alone
+    ("bf16_train_fwd/64", (16, 16, 4096, 2048, 1)): "bf16_gemm_fwd_slabs",      # 8 tiles x 128 K-tiles: 8 slabs alone
+    ("bf16_train_fwd/64", (16, 16, 64, 1024, 7)): "bf16_gemm_fwd_slabs",        # 4 tiles x 98 K-tiles: 6 slabs alone
+}
+# The unmasked data gradient of the fc6 class (conv_bf16_256_kernel's `plain` split: >= 512 K-tiles behind fewer than 128 tiles) still counts the
+# batch's tiles: the c5 training leg's time rides on its slab count.  Pinned as found: reproducible, and the float64 product to round-off.
+KNOWN_BATCH_DEPENDENT = {
+    ("bf16_train_dx/64", (32, 64, 256, 384, 7)): "launch_conv_bf16_256's plain split: 8 N tiles give 8 slabs at N <= 4, 6 at N = 5",
+}
+
+
+# ---- the routes: name -> (inputs with a leading image axis, call(*inputs) -> [N, ...] fp32, value of an empty image) -----------------------
+class Route:
+    """One op entry point on one layer shape with seeded weights.  per_image: arrays with a leading image axis that are cut together (the first
+    one is what assertion C zeroes); call(*cut) returns the fp32 output, leading axis = images; empty(out_shape) is an empty image's output."""
+    def __init__(self, per_image, call, empty):
+        self.per_image, self.call, self.empty = per_image, call, empty
+        for a in per_image:
+            a.setflags(write=False)
+
+
+def _weights(rng, H, W, Cin, Cout, K, nmax):
+    x = rng.standard_normal((nmax, H, W, Cin)).astype(np.float32)
+    w = (rng.standard_normal((K, K, Cin, Cout)) / np.sqrt(K * K * Cin)).astype(np.float32)
+    b = (0.5 * rng.standard_normal(Cout)).astype(np.float32)
+    return x, w, b
+
+
+def _bias_image(b, relu):
+    v = np.maximum(b, np.float32(0)) if relu else b
+    return lambda shape: np.broadcast_to(v, shape)
+
+
+def _zeros(shape):
+    return np.zeros(shape, np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def route(name, shape, nmax):
+    L = _lib()
+    H, W, Cin, Cout, K = shape
+    kind, _, arg = name.partition("/")
+    rng = np.random.default_rng(1000 + 7 * H + 13 * W + Cin + 3 * Cout + K)
+    x, w, b = _weights(rng, H, W, Cin, Cout, K, nmax)
+    wd, bd = dev(w), dev(b)
+
+    if kind == "conv2d":                                 # fcn8s_op_conv2d, arg = r<relu>
+        relu = int(arg[1:])
+        def call(xs):
+            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H, W, Cout), float("nan")).cuda()
+            L.check(L.lib.fcn8s_op_conv2d(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), n, H, W, Cin, Cout, K, relu))
+            torch.cuda.synchronize(); return y.cpu().numpy()
+        return Route((x,), call, _bias_image(b, relu))
+    if kind == "wino":                                   # fcn8s_op_conv2d_winograd, arg = tile
+        tile = int(arg)
+        def call(xs):
+            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H, W, Cout), float("nan")).cuda()
+            L.check(L.lib.fcn8s_op_conv2d_winograd(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), n, H, W, Cin, Cout, K, 1, tile))
+            torch.cuda.synchronize(); return y.cpu().numpy()
+        return Route((x,), call, _bias_image(b, 1))
+    if kind == "wino_pool":                              # fcn8s_op_conv3x3_winograd_pool (inference form), arg = op_gemm_out_fused64
+        option = int(arg)
+        def call(xs):
+            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H // 2, W // 2, Cout), float("nan")).cuda()
+            fused = C.c_int(-1)
+            with op_context(op_gemm_out_fused64=option):
+                L.check(L.lib.fcn8s_op_conv3x3_winograd_pool(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), None, n, H, W, Cin, Cout, 6, 0, C.byref(fused)))
+            torch.cuda.synchronize()
+            assert fused.value == option
+            return y.cpu().numpy()
+        return Route((x,), call, _bias_image(b, 1))
+    if kind == "bf16":                                   # fcn8s_op_conv2d_bf16 (the bf16_fc mode's kernel)
+        def call(xs):
+            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H, W, Cout), float("nan")).cuda()
+            L.check(L.lib.fcn8s_op_conv2d_bf16(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), n, H, W, Cin, Cout, K, 1))
+            torch.cuda.synchronize(); return y.cpu().numpy()
+        return Route((x,), call, _bias_image(b, 1))
+    if kind == "bf16_train_fwd":                         # fcn8s_op_conv2d_bf16_train, forward; arg = op_bf16_rows_bn form
+        form = int(arg)
+        def call(xs):
+            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H, W, Cout), float("nan")).cuda()
+            with op_context(op_bf16_rows_bn=form):
+                L.check(L.lib.fcn8s_op_conv2d_bf16_train(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), 1, None, None, None, None, None, n, H, W, Cin, Cout, K))
+            torch.cuda.synchronize(); return y.cpu().numpy()
+        return Route((x,), call, _bias_image(b, 1))
+    if kind in ("bf16_train_dx", "bf16_train_dxm"):      # ... its data gradient of dy, unmasked / masked by the sign of a per-image tensor
+        form = int(arg)
+        dy = rng.standard_normal((nmax, H, W, Cout)).astype(np.float32)
+        mask = rng.standard_normal((nmax, H, W, Cin)).astype(np.float32)
+        masked = kind == "bf16_train_dxm"
+        def call(dys, ms=None):
+            n = dys.shape[0]; dyd = dev(dys); md = dev(ms) if masked else None
+            dx = torch.full((n, H, W, Cin), float("nan")).cuda()
+            with op_context(op_bf16_rows_bn=form):
+                L.check(L.lib.fcn8s_op_conv2d_bf16_train(None, None, ptr(wd), None, None, 0, ptr(dyd), ptr(md), ptr(dx), None, None, n, H, W, Cin, Cout, K))
+            torch.cuda.synchronize(); return dx.cpu().numpy()
+        r = Route((dy, mask) if masked else (dy,), call, _zeros)
+        r.w = w
+        return r
+    if kind == "fp8":                                    # fcn8s_op_conv2d_fp8: one activation exponent for every batch size
+        ex = fp8.exponent(8.0)
+        def call(xs):
+            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H, W, Cout), float("nan")).cuda()
+            L.check(L.lib.fcn8s_op_conv2d_fp8(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), 1, ex, n, H, W, Cin, Cout, K))
+            torch.cuda.synchronize(); return y.cpu().numpy()
+        return Route((x,), call, _bias_image(b, 1))
+    if kind == "tconv":                                  # fcn8s_op_conv2d_transpose with the addend: C = Cin = Cout classes, K = 2 S
+        S = K // 2
+        wt = (rng.standard_normal((K, K, Cin, Cin)) * 0.1).astype(np.float32)
+        add = rng.standard_normal((nmax, H * S, W * S, Cin)).astype(np.float32)
+        wtd = dev(wt)
+        def call(xs, adds):
+            n = xs.shape[0]; xd, ad = dev(xs), dev(adds); y = torch.full((n, H * S, W * S, Cin), float("nan")).cuda()
+            L.check(L.lib.fcn8s_op_conv2d_transpose(None, ptr(xd), ptr(wtd), ptr(bd), ptr(ad), ptr(y), n, H, W, Cin, K, S))
+            torch.cuda.synchronize(); return y.cpu().numpy()
+        r = Route((x, add), call, None)
+        r.empty_of = lambda i: (b + add[i]).astype(np.float32)           # one fp32 addition: commutative, so exact whichever operand comes first
+        return r
+    if kind == "maxpool":
+        xr = np.maximum(x, np.float32(0))                                # post-ReLU: many exact ties
+        def call(xs):
+            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H // 2, W // 2, Cin), float("nan")).cuda()
+            L.check(L.lib.fcn8s_op_maxpool2x2(None, ptr(xd), ptr(y), n, H, W, Cin))
+            torch.cuda.synchronize(); return y.cpu().numpy()
+        return Route((xr,), call, _zeros)
+    raise KeyError(name)
+
+
+def alone_vs_batch(call, x, Ns):
+    """call(*cut) on x[:N] for every N in Ns, on x[i:i+1] for i in {0, N - 1}, and on one interior pair x[i:i+2] when N >= 3 (x: a tuple of
+    per-image arrays cut together).  Returns {"batch": {N: out}, "alone": {i: out[0]}, "pair": {i: out}}."""
+    cut = lambda lo, hi: tuple(a[lo:hi] for a in x)
+    out = {"batch": {}, "alone": {}, "pair": {}}
+    for N in Ns:
+        out["batch"][N] = call(*cut(0, N))
+        for i in {0, N - 1}:
+            if i not in out["alone"]:
+                out["alone"][i] = out["batch"][1][0] if (i == 0 and 1 in out["batch"]) else call(*cut(i, i + 1))[0]
+        if N >= 3:
+            i = (N - 1) // 2
+            if i not in out["pair"]:
+                out["pair"][i] = call(*cut(i, i + 2))
+    return out
+
+
+def check_case(name, shape, Ns):
+    r = route(name, shape, max(Ns))
+    out = alone_vs_batch(r.call, r.per_image, Ns)
+    big = [N for N in sorted(Ns) if N >= 2]
+    ref = out["batch"][big[-1]]
+    assert np.isfinite(ref).all()
+    assert ref.std() > 0
+    fails = []                                           # (all three are evaluated: a report says which of A, B, C a case misses)
+    differ = lambda u, v: int((bits(u) != bits(v)).sum())
+    # A: among batches of two or more
+    for N in big[:-1]:
+        if differ(out["batch"][N], ref[:N]):
+            fails.append("A: N = %d against N = %d: %d of %d elements differ" % (N, big[-1], differ(out["batch"][N], ref[:N]), ref[:N].size))
+    for i, pair in out["pair"].items():
+        if differ(pair, ref[i:i + 2]):
+            fails.append("A: the pair at image %d against N = %d: %d of %d elements differ" % (i, big[-1], differ(pair, ref[i:i + 2]), pair.size))
+    # B: one image alone
+    rule = SINGLE_IMAGE_EXCEPTIONS.get((name, shape))
+    for i, one in sorted(out["alone"].items()):
+        if rule:
+            e = rel_err(one, ref[i])
+            print("%s %s: image %d alone (excepted by %s): %d of %d elements differ, %.3g of the largest entry" % (name, shape, i, rule, differ(one, ref[i]), one.size, e))
+            if not e < 1e-5:
+                fails.append("B, excepted by %s: image %d alone is %.3g of the largest entry away" % (rule, i, e))
+        elif differ(one, ref[i]):
+            fails.append("B: image %d alone against N = %d: %d of %d elements differ" % (i, big[-1], differ(one, ref[i]), one.size))
+    # C: placement, at the largest tested batch of at most five images (else the smallest batch of two or more)
+    small = [N for N in big if N <= 5]
+    Nc = small[-1] if small else big[0]
+    live = Nc // 2
+    x0 = np.zeros_like(r.per_image[0][:Nc]); x0[live] = r.per_image[0][live]
+    got = r.call(x0, *(a[:Nc] for a in r.per_image[1:]))
+    full = out["batch"][Nc]
+    empty = lambda i: r.empty_of(i) if r.empty is None else r.empty(full[i].shape)
+    for i in range(Nc):
+        if i == live and differ(got[i], full[i]):
+            fails.append("C: the live image %d of %d: %d elements differ from the full batch" % (i, Nc, differ(got[i], full[i])))
+        if i != live and differ(got[i], empty(i)):
+            fails.append("C: the empty image %d of %d: %d elements are not the bias" % (i, Nc, differ(got[i], empty(i))))
+    assert differ(full[live], empty(live))               # (the live image does say something)
+    assert not fails, "%s %s: %s" % (name, shape, "; ".join(fails))
+    return out
+
+
+RAGGED_NS = (1, 2, 3, 5)
+# (a) one ragged map per route: no multiple of any row tile (32, 64, 128, 256 rows; 16 / 64 Winograd tiles), so tiles straddle images
+RAGGED_CASES = [
+    # route, (H, W, Cin, Cout, K)
+    ("conv2d/r1", (6, 10, 4, 64, 3)),            # conv1_1's class: the scalar-gather kernel (Cin % 16 != 0)
+    ("conv2d/r1", (6, 10, 64, 128, 3)),          # relu = 1: no linear epilogue, no atomics
+    ("conv2d/r1", (6, 10, 32, 64, 7)),
+    ("conv2d/r1", (6, 10, 256, 128, 1)),         # relu = 1: the LDS-DMA GEMM with an epilogue, never the atomic split
+    ("conv2d/r0", (5, 7, 256, 20, 1)),           # the score heads (skinny.hip, no atomics): 35 rows per image against 32-row blocks
+    ("conv2d/r0", (5, 7, 512, 20, 1)),
+    ("conv2d/r0", (5, 7, 4096, 20, 1)),          # head_fwd_splits: 8 slabs at N = 1 (and, before the rule, at every N here)
+    ("conv2d/r0", (5, 7, 96, 4, 1)),
+    ("wino/2", (6, 10, 32, 64, 3)),              # 15 tiles per image
+    ("wino/4", (12, 20, 32, 64, 3)),             # 15 tiles per image
+    ("wino/6", (14, 20, 64, 64, 3)),             # 12 tiles per image, partial edge tiles both ways
+    ("wino/6", (34, 22, 64, 128, 3)),            # 24 tiles per image
+    ("wino/4", (12, 20, 32, 64, 7)),             # the 7x7 sub-filter form
+    ("wino_pool/0", (14, 20, 64, 64, 3)),
+    ("wino_pool/1", (14, 20, 64, 64, 3)),        # wino_gemm_out64_kernel: 16 tiles per block, 12 per image
+    ("bf16/0", (6, 10, 64, 128, 3)),
+    ("bf16/0", (5, 7, 128, 128, 1)),
+    ("bf16_train_fwd/64", (6, 10, 64, 128, 3)),  # 96 padded positions per image against 256-row tiles
+    ("bf16_train_fwd/128", (6, 10, 64, 128, 3)), # ... against 128-row tiles
+    ("bf16_train_dxm/64", (6, 10, 64, 128, 3)),  # a masked launch never splits
+    ("bf16_train_dxm/128", (6, 10, 128, 128, 3)),
+    ("bf16_train_dx/64", (6, 10, 64, 128, 3)),   # 12 K-tiles: under the rows kernel's 24
+    ("bf16_train_dx/128", (6, 10, 128, 128, 3)),
+    ("bf16_train_fwd/64", (5, 7, 128, 256, 1)),  # 35 rows per image against 256-row tiles; 4 K-tiles
+    ("bf16_train_dxm/64", (5, 7, 128, 256, 1)),
+    ("bf16_train_dx/64", (5, 7, 128, 256, 1)),
+    ("bf16_train_fwd/64", (6, 10, 64, 128, 7)),  # 98 K-tiles but no 256-column tile: one pass at every N
+    ("bf16_train_dxm/64", (6, 10, 64, 128, 7)),
+    ("bf16_train_dx/64", (6, 10, 64, 128, 7)),   # 196 K-tiles: under the plain split's 512
+    ("fp8/0", (6, 10, 64, 128, 3)),
+    ("fp8/0", (5, 7, 128, 64, 1)),
+    ("tconv/0", (3, 5, 20, 20, 4)),              # 2x upsampling, 20 classes, with the addend
+    ("tconv/0", (3, 5, 20, 20, 16)),             # 8x
+    ("maxpool/0", (6, 10, 64, 64, 1)),
+]
+# (b) the three launchers that read the total block count: batch sizes on both sides of every threshold of the inline formulas split_route.h replaced
+THRESHOLD_CASES = [
+    ("bf16_train_fwd/64", (16, 16, 512, 512, 3), (1, 2, 4, 5)),       # rows kernel, 48 K-tiles: 16 / 24 blocks -> 8 slabs at N = 1, 2; 48 blocks -> 5 at N = 4; 56 blocks -> one pass at N = 5
+    ("bf16_train_dx/64", (16, 16, 512, 512, 3), (1, 2, 4, 5)),        # ... the unmasked data gradient takes the same branch
+    ("bf16_train_dxm/64", (16, 16, 512, 512, 3), (1, 2, 4, 5)),       # ... the masked one never did
+    ("bf16_train_fwd/64", (16, 16, 2048, 4096, 1), (1, 4, 5)),        # fc7's class, 64 K-tiles: 16 / 64 tiles -> 4 slabs at N = 1, 4; 80 tiles -> one pass at N = 5
+    ("bf16_train_fwd/64", (16, 16, 4096, 2048, 1), (1, 2, 5, 8, 9)),  # 128 K-tiles: 8 / 16 tiles -> 8 slabs at N = 1, 2; 40 -> 6 at N = 5; 64 -> 4 at N = 8; 72 -> one pass at N = 9
+    ("bf16_train_fwd/64", (16, 16, 64, 1024, 7), (1, 11, 17)),        # fc6's class, 98 K-tiles: 4 tiles -> 6 slabs at N = 1; 44 -> 5 at N = 11; 68 -> one pass at N = 17
+    ("conv2d/r0", (16, 32, 4096, 20, 1), (1, 4, 5)),                  # fc7's score head (no atomics: two-pass sum): 64 blocks -> 8 slabs at N <= 4; 80 -> one pass at N = 5
+]
+
+
+@pytest.mark.parametrize("name,shape", RAGGED_CASES)
+def test_ragged_map(name, shape):
+    check_case(name, shape, RAGGED_NS)
+
+
+@pytest.mark.parametrize("name,shape,Ns", THRESHOLD_CASES)
+def test_batch_sizes_across_the_old_thresholds(name, shape, Ns):
+    check_case(name, shape, Ns)
+
+
+@pytest.mark.parametrize("key", sorted(KNOWN_BATCH_DEPENDENT))
+def test_known_batch_dependent_launch_is_reproducible_and_close(key):
+    """The fc6-class unmasked data gradient (see KNOWN_BATCH_DEPENDENT): two identical calls give identical bits, at both batch sizes, and each
+    batch is within 1e-5 (of the largest entry) of the float64 product of the same bf16-rounded operands -- test_conv_bf16_train_kernels' bound.
+    The float64 product is taken on the first and last 16 input channels (a slab order is common to all of them): an eighth of the work."""
+    name, shape = key
+    H, W, Cin, Cout, K = shape
+    r = route(name, shape, 5)
+    dy = r.per_image[0]
+    sel = np.r_[0:16, Cin - 16:Cin]
+    rb = lambda a: torch.tensor(np.ascontiguousarray(a)).to(torch.bfloat16).double()
+    wr = rb(r.w[:, :, sel, :]).permute(3, 2, 0, 1)                                       # [Cout][16 + 16][K][K]
+    ref = torch.nn.grad.conv2d_input((5, sel.size, H, W), wr, rb(dy).permute(0, 3, 1, 2), padding=(K - 1) // 2).permute(0, 2, 3, 1).numpy()
+    outs = {}
+    for N in (2, 5):
+        a, b = r.call(dy[:N]), r.call(dy[:N])
+        assert np.array_equal(bits(a), bits(b)), N
+        e = rel_err(a[..., sel], ref[:N])
+        print("%s %s N = %d: %.3g of the largest entry against float64" % (name, shape, N, e))
+        assert e < 1e-5, (N, e)
+        outs[N] = a
+    print("N = 2 and N = 5 agree bit for bit on their common images: %s" % np.array_equal(bits(outs[2]), bits(outs[5][:2])))
+
+
+def test_the_exception_tables_name_tested_cases():
+    """Every key of the two tables is a case of this file (an entry nobody runs would excuse nothing and hide nothing)."""
+    cases = {(n, s) for n, s in RAGGED_CASES} | {(n, s) for n, s, _ in THRESHOLD_CASES}
+    assert set(SINGLE_IMAGE_EXCEPTIONS) <= cases
+    assert not set(KNOWN_BATCH_DEPENDENT) & cases

@@ -864,7 +864,7 @@ def test_bf16_train_batch_of_64_is_its_four_images_sixteen_times():
     for i in (0, 5, 37, 62, 63):
         d = float(np.abs(logits64[i] - logits4[i % R]).max())
         dmax = max(dmax, d)
-        assert d <= 1e-5 * scale, (i, d, scale)            # (measured 6.4e-7: the forward kernels add a dot product's terms in the same order whatever the batch)
+        assert d <= 1e-5 * scale, (i, d, scale)            # (measured 6.4e-7.  The forward kernels add a dot product's terms in the same order in every batch of two or more: the K splits are decided per image by csrc/split_route.h -- bf16_rows_slabs, bf16_gemm_fwd_slabs, head_fwd_splits -- and never by the batch's block count; tests/test_batch_independence_*_gpu.py hold that bit for bit at the sizes where the old inline formulas changed their mind, which this size never was)
     print("bf16_train, batch 64: logits of images 0, 5, 37, 62, 63 differ from the four-image batch's by at most %.2e of their scale" % (dmax / scale))
     loss, step = e.train_step(big_i, big_l, 1e-4, keep_prob=0.5)
     assert np.isfinite(loss) and step == 1
