@@ -4,6 +4,7 @@
 // matrix, column sums (bias gradients), optimizer updates and the small weight
 // re-layouts.  16-byte vector accesses, grid-stride loops capped at 2048 blocks.
 #include "fcn8s_internal.h"
+#include "loss_tile.h"
 #include "cv_resize.h"
 #include <math.h>
 #include <map>
@@ -401,20 +402,6 @@ static __device__ __forceinline__ double block_sum(double v, double* sh)
     double t = 0;
     if (threadIdx.x == 0) for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
     return t;   // valid in thread 0
-}
-
-// slot -> pixel index of a (possibly blocked, see PixMap) logits tensor; -1 = the slot lies outside the image
-static __device__ __forceinline__ long long slot_pixel(long long slot, const PixMap& m)
-{
-    if (!m.blocked) return slot;
-    const int S = m.S;
-    const int rx = (int)(slot % S); long long t = slot / S;
-    const int r = (int)(t % S); t /= S;
-    const int qx = (int)(t % m.QW); t /= m.QW;
-    const int q = (int)(t % m.QH); const long long n = t / m.QH;
-    const int oy = q * S - S / 2 + r, ox = qx * S - S / 2 + rx;
-    if ((unsigned)oy >= (unsigned)m.H || (unsigned)ox >= (unsigned)m.W) return -1;
-    return (n * m.H + oy) * m.W + ox;
 }
 
 // ---- K10: fused softmax cross-entropy (loss partial sums + dlogits) ---------

@@ -16,6 +16,7 @@
 // Every sum is integer or in a fixed order: the path is deterministic and has no float atomics.  Non-participating segment-classes
 // (w == 0) return at once from every sort kernel; `present` mode reads G from device memory for that.
 #include "fcn8s_internal.h"
+#include "loss_tile.h"
 
 namespace fcn8s {
 namespace {
@@ -33,20 +34,6 @@ static __device__ __forceinline__ double lov_block_sum(double v, double* sh)
     if (threadIdx.x == 0) for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
     __syncthreads();
     return t;   // valid in thread 0
-}
-
-// slot -> pixel of a (possibly blocked) logits tensor, as elementwise.hip's slot_pixel
-static __device__ __forceinline__ long long lov_slot_pixel(long long slot, const PixMap& m)
-{
-    if (!m.blocked) return slot;
-    const int S = m.S;
-    const int rx = (int)(slot % S); long long t = slot / S;
-    const int r = (int)(t % S); t /= S;
-    const int qx = (int)(t % m.QW); t /= m.QW;
-    const int q = (int)(t % m.QH); const long long n = t / m.QH;
-    const int oy = q * S - S / 2 + r, ox = qx * S - S / 2 + rx;
-    if ((unsigned)oy >= (unsigned)m.H || (unsigned)ox >= (unsigned)m.W) return -1;
-    return (n * m.H + oy) * m.W + ox;
 }
 
 // the pixel's probabilities, bit for bit those of softmax_argmax_kernel(_c): prob_c = expf(z_c - max) / sum, classes summed in order
@@ -80,7 +67,7 @@ __global__ __launch_bounds__(256) void lov_key_kernel(const float* __restrict__ 
     const long long s0 = (long long)s * slots_per_seg;
     for (long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x; q < slots_per_seg; q += (long long)gridDim.x * blockDim.x) {
         const long long slot = s0 + q;
-        const long long pix = lov_slot_pixel(slot, map);
+        const long long pix = slot_pixel(slot, map);
         if (pix < 0) continue;
         const long long i = pix - (long long)s * L;               // index inside the segment
         const int lab = labels[pix];
@@ -314,7 +301,7 @@ __global__ __launch_bounds__(256) void lov_bwd_kernel(const float* __restrict__ 
 #pragma unroll
     for (int i = 0; i < CM; ++i) cs[i] = 0.f;
     for (long long slot = blockIdx.x * (long long)blockDim.x + threadIdx.x; slot < nslot; slot += (long long)gridDim.x * blockDim.x) {
-        const long long pix = lov_slot_pixel(slot, map);
+        const long long pix = slot_pixel(slot, map);
         if (pix < 0) continue;                                       // (a slot outside the image keeps its zero gradient)
         const int lab = labels[pix];
         float* o = out + slot * C;

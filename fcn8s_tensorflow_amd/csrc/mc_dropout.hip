@@ -16,7 +16,7 @@ static inline int mc_blocks(long long work)
     long long b = (work + 255) / 256;
     return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
 }
-// slot of pixel (n, y, x) of the map (tta.hip's tta_slot: the inverse of slot_pixel in elementwise.hip)
+// slot of pixel (n, y, x) of the map (tta.hip's tta_slot: the inverse of slot_pixel in loss_tile.h)
 static __device__ __forceinline__ long long mc_slot(const PixMap& m, int n, int y, int x)
 {
     if (!m.blocked) return ((long long)n * m.H + y) * m.W + x;

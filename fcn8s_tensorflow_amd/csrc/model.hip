@@ -2206,6 +2206,11 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
     hipStream_t s = m->stream;
     const long long npix = (long long)m->N * m->H * m->W;
     const int nb = softmax_xent_blocks(npix);
+    // the last pass's logits and their gradient in the layout they live in (blocked: the GEMM route of the last transposed conv), for every launch below
+    const bool blk = m->tconv_gemm && m->logits_b;
+    const float* lg = blk ? m->logits_b : A(m, "logits");
+    float* dlg = blk ? m->dlogits_b : m->dlogits;
+    const PixMap* pm = blk ? &m->pm : nullptr;
     const bool bnd = with_grad && m->bnd_R > 0;               // evaluation keeps the reference's loss
     const int mode = with_grad ? (m->loss_mode ? m->loss_mode : bnd ? 1 : 0) : 0;    // the boundary weighting alone: the weighted mode, d_cw holds ones
     const bool focal = with_grad && m->focal_gamma > 0.f;      // the focal launch in the cross-entropy's place (mode is 0 or 1: OHEM is refused with it)
@@ -2238,24 +2243,22 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
         // partial finalize_loss reads, d_lastbias (set, all 64 columns defined by the memset), |V| in the loss state -- so that everything behind is untouched
         ProfScope ps(m, "focal_xent", 0, focal_xent_bytes(npix, m->C, bnd));
         hipMemsetAsync(m->d_lastbias, 0, 64 * sizeof(float), s);
-        const bool blk = m->tconv_gemm && m->logits_b;
-        launch_focal_xent(blk ? m->logits_b : A(m, "logits"), blk ? m->dlogits_b : m->dlogits, lab_dev, mode ? (const float*)m->d_cw : nullptr,
-                          bnd ? (const uint8_t*)m->d_bcodes : nullptr, bnd ? (const float*)m->d_btab : nullptr, blk ? &m->pm : nullptr, m->N, npix, m->C,
+        launch_focal_xent(lg, dlg, lab_dev, mode ? (const float*)m->d_cw : nullptr,
+                          bnd ? (const uint8_t*)m->d_bcodes : nullptr, bnd ? (const float*)m->d_btab : nullptr, pm, m->N, npix, m->C,
                           m->focal_gamma, gscale, m->focal_ws, m->d_partials, nullptr, (OhemState*)m->loss_ws.get(), m->d_lastbias, s);
     } else
     { ProfScope ps(m, "softmax_xent", 0, xbytes);
       if (with_grad) hipMemsetAsync(m->d_lastbias, 0, 64 * sizeof(float), s);
-      const bool blk = m->tconv_gemm && m->logits_b;
       if (mode) {
           XentEx x; x.cw = m->d_cw; x.st = st; x.hist = (unsigned*)(m->loss_ws + sizeof(OhemState));
           x.lbuf = mode == 2 ? (float*)(m->loss_ws + LOSS_SCRATCH_BYTES) : nullptr;
           if (lov) x.ce_scale = m->lov_ce;
           if (bnd) { x.codes = m->d_bcodes; x.ptab = m->d_btab; }
-          launch_softmax_xent_ex(blk ? m->logits_b : A(m, "logits"), lab_dev, blk ? m->dlogits_b : m->dlogits, m->d_partials, npix, m->C, gscale, s,
-                                 m->d_lastbias, blk ? &m->pm : nullptr, m->N, x, mode == 2 ? m->ohem_thresh : 0.f, (long long)m->ohem_min_kept);
+          launch_softmax_xent_ex(lg, lab_dev, dlg, m->d_partials, npix, m->C, gscale, s,
+                                 m->d_lastbias, pm, m->N, x, mode == 2 ? m->ohem_thresh : 0.f, (long long)m->ohem_min_kept);
       } else
-          launch_softmax_xent(blk ? m->logits_b : A(m, "logits"), lab_dev, with_grad ? (blk ? m->dlogits_b : m->dlogits) : nullptr, m->d_partials, npix, m->C,
-                              gscale, s, with_grad ? m->d_lastbias : nullptr, blk ? &m->pm : nullptr, m->N); }
+          launch_softmax_xent(lg, lab_dev, with_grad ? dlg : nullptr, m->d_partials, npix, m->C,
+                              gscale, s, with_grad ? m->d_lastbias : nullptr, pm, m->N); }
     if (with_grad) { m->last_loss_mode = focal ? 1 : mode; m->bnd_last = bnd ? npix : 0; }     // (focal: |V| is reported as in the weighted mode)
     const float* reg = nullptr;
     if (l2_rate != 0.f) {
@@ -2268,11 +2271,9 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
     if (lov_sort) {
         // L_lov and its gradient: keys, sort, Jaccard scan (the loss, now final), then dlogits += lov_w d L_lov / d logits and the bias column sums
         ProfScope ps(m, "lovasz", 0, lovasz_bytes(npix, m->C, m->lov_nmask));
-        const bool blk = m->tconv_gemm && m->logits_b;
-        const float* lg = blk ? m->logits_b : A(m, "logits");
-        launch_lovasz_loss(lg, 1, lab_dev, blk ? &m->pm : nullptr, m->N, npix, ly, m->lov_all, m->d_lovmask, m->lov_ws, nullptr, m->d_terms,
+        launch_lovasz_loss(lg, 1, lab_dev, pm, m->N, npix, ly, m->lov_all, m->d_lovmask, m->lov_ws, nullptr, m->d_terms,
                            m->lov_ce, m->lov_w, m->d_loss, s);
-        launch_lovasz_backward(lg, 1, lab_dev, blk ? &m->pm : nullptr, m->N, npix, ly, m->lov_ws, m->lov_w, 1, blk ? m->dlogits_b : m->dlogits,
+        launch_lovasz_backward(lg, 1, lab_dev, pm, m->N, npix, ly, m->lov_ws, m->lov_w, 1, dlg,
                                m->d_lastbias, s);
     } else if (lov)
         launch_lovasz_total(m->d_terms, m->lov_ce, m->d_loss, s);
@@ -2282,8 +2283,7 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
         // the loss, the term and the bias column sums -- all in front of the loss copy below
         if (!m->kd_ws.grow(soft_targets_scratch_bytes(), s, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "the soft-target term's scratch cannot be allocated");
         ProfScope ps(m, "soft_targets", 0, soft_targets_bytes(npix, m->C, m->kd_K));
-        const bool blk = m->tconv_gemm && m->logits_b;
-        launch_soft_targets(blk ? m->logits_b : A(m, "logits"), blk ? m->dlogits_b : m->dlogits, m->kd_probs, lab_dev, blk ? &m->pm : nullptr, m->N, npix,
+        launch_soft_targets(lg, dlg, m->kd_probs, lab_dev, pm, m->N, npix,
                             m->C, m->kd_K, m->kd_stride, m->kd_w, m->kd_T, m->kd_all, m->kd_ws, m->d_loss, m->d_terms + 3, m->d_lastbias, s);
         m->have_kd = true;
     }
@@ -2293,8 +2293,7 @@ int compute_loss(fcn8s_model* m, const uint8_t* lab_dev, float l2_rate, bool wit
         // sums -- all in front of the loss copy below
         if (!m->ent_ws.grow(entropy_term_scratch_bytes(), s, &m->ws_allocs)) return fail(m, FCN8S_ERR_OOM, "the entropy term's scratch cannot be allocated");
         ProfScope ps(m, "entropy_term", 0, entropy_term_bytes(npix, m->C));
-        const bool blk = m->tconv_gemm && m->logits_b;
-        launch_entropy_term(blk ? m->logits_b : A(m, "logits"), blk ? m->dlogits_b : m->dlogits, lab_dev, blk ? &m->pm : nullptr, m->N, npix, m->C, m->ent_K,
+        launch_entropy_term(lg, dlg, lab_dev, pm, m->N, npix, m->C, m->ent_K,
                             m->ent_set, m->ent_first, m->ent_w, m->ent_ws, m->d_loss, m->d_terms + 4, m->d_lastbias, 1, s);
         m->have_ent = true;
     }

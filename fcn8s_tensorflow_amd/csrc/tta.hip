@@ -67,7 +67,7 @@ static __device__ __forceinline__ HalfTap half_pixel_tap(int d, int src, int dst
     return t;
 }
 // slot of pixel (n, y, x) of the padded map (PixMap: map.H x map.W pixels; blocked: rows (n, q, qx) of S x S blocks that start at
-// (S q - S/2, S qx - S/2), columns (r, rx, class) -- the inverse of slot_pixel in elementwise.hip)
+// (S q - S/2, S qx - S/2), columns (r, rx, class) -- the inverse of slot_pixel in loss_tile.h)
 static __device__ __forceinline__ long long tta_slot(const PixMap& m, int n, int y, int x)
 {
     if (!m.blocked) return ((long long)n * m.H + y) * m.W + x;

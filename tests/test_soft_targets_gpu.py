@@ -139,6 +139,45 @@ def test_model_matches_restatement(precision, widths, tconv_gemm, shape):
 
 
 @pytest.mark.parametrize("tconv_gemm", [0, 1])
+@pytest.mark.parametrize("num_classes", [12, 24])
+def test_model_matches_restatement_at_other_class_counts(num_classes, tconv_gemm):
+    """C = K = 12 (image stride 12) and 24 (stride 28): the kernel's generic 16-byte path, which a model of 20 classes never takes.  The bars of
+    test_model_matches_restatement."""
+    from fcn8s_tensorflow_amd.engine import Engine
+    n, h, w = SHAPES["1x32x32"]
+    rng = np.random.default_rng(14)
+    P = orc.init_params(num_classes, SMALL, seed=6, decoder_std_scale=3.0, bias_std=0.05)
+    img = rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)
+    lab = rng.integers(0, num_classes, (n, h, w), dtype=np.uint8)
+    lab[rng.random((n, h, w)) < 0.1] = 255
+    e = Engine(num_classes, widths=SMALL, device_id=0, seed=0, options=dict(tconv_gemm=tconv_gemm))
+    e.set_params(P)
+    for i, (T, pixels) in enumerate(((1.0, "valid"), (2.0, "all"))):
+        tg = sharpened_rows((n, h, w), num_classes, 40 + i)
+        weight = 0.7
+        e.set_soft_targets(weight, T, pixels)
+        e.bind_soft_targets(as_device(tg, i == 1))
+        loss = e.forward_backward(img, lab, keep_prob=1.0)
+        term = e.soft_target_term()
+        logits = e.activation("logits", (n, h, w, num_classes)).reshape(-1, num_classes)
+        r = restated(logits, lab, n, tg, weight, T, pixels, num_classes)
+        db = e.get_grads()[LAST_BIAS]
+        dev = dict(loss=abs(loss - r["loss"]) / r["loss"], term=abs(term - r["term"]) / r["term"],
+                   bias=np.abs(db - r["dlogits"].sum(0)).max() / r["scale"])
+        if tconv_gemm == 0:
+            dl = e.activation("dlogits", (n, h, w, num_classes)).reshape(-1, num_classes)
+            dev["d"] = np.abs(dl - r["dlogits"]).max() / np.abs(r["dlogits"]).max()
+        print("C = %d tconv_gemm=%d T=%g %s: device %s; float32 restatement E %s"
+              % (num_classes, tconv_gemm, T, pixels, {k: "%.2e" % v for k, v in dev.items()}, {k: "%.2e" % v for k, v in r["E"].items()}))
+        assert dev["loss"] <= max(1e-5, 8 * r["E"]["term"]), (loss, r["loss"])
+        assert dev["term"] <= max(1e-5, 8 * r["E"]["term"]), (term, r["term"])
+        assert dev["bias"] <= max(1e-5, 8 * r["E"]["bias"]), (db, r["dlogits"].sum(0))
+        if tconv_gemm == 0:
+            assert dev["d"] <= max(2e-6, 8 * r["E"]["d"])
+    e.close()
+
+
+@pytest.mark.parametrize("tconv_gemm", [0, 1])
 @pytest.mark.parametrize("strided", [False, True])
 def test_nineteen_logical_classes(tconv_gemm, strided):
     """K = 19 of C = 20 (the 4-byte target path, rows of 19 in strides of 19 or 20): the padding class's -1e30 logit takes no part."""
