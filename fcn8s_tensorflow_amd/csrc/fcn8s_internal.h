@@ -163,6 +163,11 @@ extern thread_local int t_deterministic;
 float* det_scratch(hipStream_t s, size_t floats);              // per-(device, stream) scratch, grown on demand; nullptr if the allocation failed
 float* scratch2(hipStream_t s, size_t floats);                 // a second such buffer (the column sums' partials, which run beside a det_scratch user)
 void scratch_release(hipStream_t s);                           // frees both buffers of the calling device's stream s (fcn8s_destroy; the stream is idle)
+// op context "op_poison_scratch" (tests; 0 everywhere else): every hand-out of the two pools is filled with 0xFF bytes on the caller's stream, so a
+// producer and its consumer must sit under ONE hand-out (they do at all ten call sites: a det_scratch user that ends in launch_colsum meets
+// scratch2, the other pool).  t_scratch_poisoned_bytes: what has been filled since the option was last set ("op_scratch_poisoned_bytes").
+extern thread_local int t_poison_scratch;
+extern thread_local long long t_scratch_poisoned_bytes;
 long long scratch_bytes_live();                                // bytes the two per-(device, stream) pools hold right now, all devices and streams (option "scratch_bytes_live")
 // C[r][c] (= or +=) sum_{k < nsplit, in order} ws[k * slab + r * ldc + c]   for r < rows, c < cols
 void launch_det_reduce(float* C, const float* ws, long long rows, int cols, int ldc, long long slab, int nsplit, bool accumulate, hipStream_t s);

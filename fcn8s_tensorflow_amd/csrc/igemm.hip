@@ -42,6 +42,8 @@ static __device__ __forceinline__ unsigned xcd_swizzle(unsigned p, unsigned tota
 }
 
 thread_local int t_deterministic = 0;
+thread_local int t_poison_scratch = 0;                    // op context "op_poison_scratch" (tests): see scratch_get
+thread_local long long t_scratch_poisoned_bytes = 0;      // ... and the bytes it has filled since the option was last set ("op_scratch_poisoned_bytes")
 // Scratch for the slab reductions, the column-sum partials and the split-K slabs: one buffer per (device, stream) -- launches on one stream are ordered, two streams
 // never share a buffer, and a stream handle (the NULL stream above all) means a different queue on every device.  Grown on demand; released by
 // scratch_release when the model that owns the stream is destroyed (round 5 kept every buffer for the life of the process, keyed by the handle alone: a handle
@@ -63,6 +65,12 @@ float* scratch_get(int which, hipStream_t s, size_t floats, size_t floor_)
         if (want < floor_) want = floor_;
         if (hipMalloc((void**)&b.p, want * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         b.cap = want; g_scratch_bytes += (long long)(want * sizeof(float));
+    }
+    // op context "op_poison_scratch": what is handed out is NaN (all bits set), behind everything queued on the caller's stream -- a consumer that
+    // reads a slab or a partial row its producer did not write under THIS hand-out gets a NaN, not the previous call's leftovers
+    if (t_poison_scratch && floats) {
+        hipMemsetAsync(b.p, 0xFF, floats * sizeof(float), s);
+        t_scratch_poisoned_bytes += (long long)(floats * sizeof(float));
     }
     return b.p;
 }

@@ -2742,11 +2742,12 @@ int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value)
 {
     if (!key) return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_option: null key");
     const std::string k = key;
-    if (k == "device_bytes_live" || k == "scratch_bytes_live") return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_option: '" + k + "' is read-only");
+    if (k == "device_bytes_live" || k == "scratch_bytes_live" || k == "op_scratch_poisoned_bytes") return fail(m, FCN8S_ERR_BAD_ARG, "fcn8s_set_option: '" + k + "' is read-only");
     if (!m) {
         if (k == "op_f32x3") { t_op_split = value ? 3 : 0; return FCN8S_OK; }
         if (k == "op_deterministic") { t_deterministic = value ? 1 : 0; return FCN8S_OK; }
         if (k == "op_bf16_planes") { t_op_planes = value ? 1 : 0; return FCN8S_OK; }
+        if (k == "op_poison_scratch") { t_poison_scratch = value ? 1 : 0; t_scratch_poisoned_bytes = 0; return FCN8S_OK; }      // (tests: scratch_get, igemm.hip)
         if (k == "op_gemm_out_fused64") { if (value < 0 || value > 2) return fail(nullptr, FCN8S_ERR_BAD_ARG, "op_gemm_out_fused64 must be 0, 1 or 2"); t_op_fused64 = (int)value; return FCN8S_OK; }
         if (k == "op_bf16_rows_bn") { if (value != 0 && value != 64 && value != 128) return fail(nullptr, FCN8S_ERR_BAD_ARG, "op_bf16_rows_bn must be 0, 64 or 128"); t_op_rows_bn = (int)value; return FCN8S_OK; }
         if (k == "op_split_pieces") {
@@ -2795,6 +2796,8 @@ int fcn8s_get_option(const fcn8s_model* m, const char* key, int64_t* value)
         if (k == "op_f32x3") { *value = t_op_split == 3; return FCN8S_OK; }
         if (k == "op_deterministic") { *value = t_deterministic; return FCN8S_OK; }
         if (k == "op_bf16_planes") { *value = t_op_planes; return FCN8S_OK; }
+        if (k == "op_poison_scratch") { *value = t_poison_scratch; return FCN8S_OK; }
+        if (k == "op_scratch_poisoned_bytes") { *value = t_scratch_poisoned_bytes; return FCN8S_OK; }
         if (k == "op_gemm_out_fused64") { *value = t_op_fused64; return FCN8S_OK; }
         if (k == "op_bf16_rows_bn") { *value = t_op_rows_bn; return FCN8S_OK; }
         if (k == "op_split_pieces") { *value = t_op_split; return FCN8S_OK; }
@@ -4289,6 +4292,7 @@ int fcn8s_op_conv2d(void* stream, const float* x, const float* w, const float* b
         m->precision = t_op_split == 3 ? FCN8S_PREC_F32X3 : t_op_split == 2 ? FCN8S_PREC_F32X2 : FCN8S_PREC_F32;
         m->ufl = (size_t)8 * N * H * W * Cout;
         if (!m->d_wino_u.grow(m->ufl * sizeof(float), s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+        hipMemsetAsync(m->d_wino_u, 0xFF, m->ufl * sizeof(float), s);          // NaN: in a model these slabs hold the last filter bank
         conv_fwd(m, "", x, w, y, N, H, W, Cin, Cout, K, e, s);
         hipStreamSynchronize(s);
         OPCHK(); return FCN8S_OK;
@@ -4306,6 +4310,8 @@ int fcn8s_op_conv2d_winograd(void* stream, const float* x, const float* w, const
     const size_t T = (size_t)wino_tiles(tile, N, H, W), P = (size_t)wino_alpha(tile, K) * wino_alpha(tile, K), Kg = (size_t)wino_nsub(K) * wino_nsub(K) * Cin;
     DeviceBuf<float> u, v, mm;
     if (!u.grow(P * Kg * Cout * 4, s) || !v.grow(P * (size_t)wino_slab(T, (int)Kg) * 4, s) || !mm.grow(P * (size_t)wino_slab(T, Cout) * 4, s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+    // all of it NaN, as in fcn8s_op_conv3x3_winograd_pool: what a model's workspace holds behind a slab or beyond row T is another layer's leftovers
+    hipMemsetAsync(u, 0xFF, u.bytes(), s); hipMemsetAsync(v, 0xFF, v.bytes(), s); hipMemsetAsync(mm, 0xFF, mm.bytes(), s);
     WinoEpi we; we.bias = bias; we.relu = relu;
     conv_winograd(nullptr, tile, K, true, x, w, y, u, v, mm, N, H, W, Cin, Cout, we, s, nullptr);
     hipStreamSynchronize(s);
@@ -4331,7 +4337,10 @@ int fcn8s_op_conv3x3_winograd_fwd_bwd(void* stream, const float* x, const float*
     // (what the model keeps in its arena is this call's own; the model frees d_wino_u and the banks it makes behind this function's back)
     DeviceBuf<float> wino_v, wino_m, wv, wt, pidx, rbits;
     bool ok = true;
-    auto dalloc = [&](DeviceBuf<float>& b, size_t nfloats) { ok = ok && b.grow(nfloats * sizeof(float), s); };
+    auto dalloc = [&](DeviceBuf<float>& b, size_t nfloats) {          // all of it NaN, as in fcn8s_op_conv3x3_winograd_pool
+        ok = ok && b.grow(nfloats * sizeof(float), s);
+        if (ok) hipMemsetAsync(b, 0xFF, nfloats * sizeof(float), s);
+    };
     m->ufl = (size_t)P * cmax * cmax + (t_op_fused64 ? wino_gemm_out64_bank_floats() : 0);       // (the second, MFMA-ordered bank behind the first)
     if (t_op_fused64 == 2) m->gemm_out64_nt = 1;
     dalloc(m->d_wino_u, m->ufl); dalloc(wino_v, slab_max); dalloc(wino_m, slab_max);
@@ -4465,6 +4474,7 @@ int fcn8s_op_conv2d_bf16(void* stream, const float* x, const float* w, const flo
     hipStream_t s = (hipStream_t)stream;
     DeviceBuf<unsigned short> wt;
     if (!wt.grow((size_t)K * K * Cin * Cout * 2, s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+    hipMemsetAsync(wt, 0xFF, wt.bytes(), s);          // (bf16 NaNs)
     launch_w_to_bf16_tiles(w, wt, K * K * Cin, Cout, s);
     Bf16ConvArgs a{};
     a.x = x; a.wt = wt; a.bias = bias; a.y = y; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.K = K; a.relu = relu;
@@ -4490,6 +4500,8 @@ int fcn8s_op_conv2d_bf16_train(void* stream, const float* x, const float* w, con
     DeviceBuf<unsigned short> xb, dyb, wt;
     const size_t nx = (size_t)(R + 2 * G) * Cin, ny = (size_t)(R + 2 * G) * Cout, nw = (size_t)K * K * Cin * Cout;
     if (!wt.grow(nw * 2, s) || (x && !xb.grow(nx * 2, s, nullptr, true)) || (dy && !dyb.grow(ny * 2, s, nullptr, true))) { hipStreamSynchronize(s); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
+    // (bf16 NaNs in the weight copy; xb and dyb stay zeroed: their zero border and guard rows ARE the padding, interleaved with the interior row by row)
+    hipMemsetAsync(wt, 0xFF, wt.bytes(), s);
     if (x) {
         launch_f32_to_bf16_padded(x, xb + OX, N, H, W, Cin, pad, s, PS);
     }
@@ -4534,6 +4546,7 @@ int fcn8s_op_conv2d_fp8(void* stream, const float* x, const float* w, const floa
     const size_t xb = (size_t)R * Cin, wb = (size_t)K * K * Cin * Cout;
     DeviceBuf<unsigned char> xq, wq;
     if (!xq.grow(xb, s, nullptr, true) || !wq.grow(wb + 8 * (size_t)Cout, s)) { hipStreamSynchronize(s); return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc"); }
+    hipMemsetAsync(wq, 0xFF, wq.bytes(), s);          // (e4m3 NaNs, exponents of -1; xq stays zeroed: its zero border is the padding)
     launch_f32_to_fp8_padded(x, xq, N, H, W, Cin, pad, R * 64, x_exp, s);
     int* ew = reinterpret_cast<int*>(wq + wb);
     launch_w_to_fp8(w, wq, ew, reinterpret_cast<unsigned*>(wq + wb + 4 * (size_t)Cout), K * K * Cin, Cout, s);
@@ -4559,6 +4572,7 @@ int fcn8s_op_conv2d_bwd(void* stream, const float* x, const float* w, const floa
     if (dx) {
         DeviceBuf<float> wt;
         if (!wt.grow((size_t)K * K * Cin * Cout * sizeof(float), s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+        hipMemsetAsync(wt, 0xFF, wt.bytes(), s);
         launch_flip_transpose(w, wt, K * K, Cin, Cout, s);
         conv_dgrad(nullptr, "", dy, wt, dx, N, H, W, Cout, Cin, K, DgradEpi{}, s);
         hipStreamSynchronize(s);
@@ -4584,6 +4598,7 @@ int fcn8s_op_conv2d_transpose(void* stream, const float* x, const float* w, cons
     hipStream_t s = (hipStream_t)stream;
     DeviceBuf<float> wp;
     if (!wp.grow((size_t)S * S * 4 * C * C * sizeof(float), s)) return fail(nullptr, FCN8S_ERR_OOM, "hipMalloc");
+    hipMemsetAsync(wp, 0xFF, wp.bytes(), s);
     launch_tconv_phase_pack(w, wp, K, S, C, s);
     tconv_fwd(nullptr, x, wp, bias, addend, y, N, Hi, Wi, C, K, S, s);
     hipStreamSynchronize(s);

@@ -720,6 +720,11 @@ int fcn8s_fp8_set_calibration(fcn8s_model* m, const float* amax, int n);
  *                              whatever the size (a model launches it from 64e6 pooled bytes up), 0 = position GEMM + output transform.  Other values: FCN8S_ERR_BAD_ARG
  *     "op_deterministic"  0    the slab reductions of "deterministic" for the op-level entry points (a model call on the same thread sets the
  *                              thread's switch from that model's option: set it again before the next op-level call)
+ *     "op_poison_scratch" 0    for tests: while 1, every hand-out of the two per-(device, stream) scratch pools (split-K slabs, slab reductions, column-sum
+ *                              partials) is filled with 0xFF bytes -- fp32 NaNs -- on the caller's stream first, so a consumer that reads what its producer
+ *                              did not write gets a NaN instead of an earlier call's leftovers.  Results do not change; every hand-out costs a fill.  (The
+ *                              pools are shared code: a model call made on the same thread while the option is 1 gets the fill too.)
+ *     "op_scratch_poisoned_bytes"  (read-only) the bytes so filled on this thread since "op_poison_scratch" was last set
  * Unknown keys return FCN8S_ERR_NOT_FOUND. */
 int fcn8s_set_option(fcn8s_model* m, const char* key, int64_t value);
 int fcn8s_get_option(const fcn8s_model* m, const char* key, int64_t* value);

@@ -32,6 +32,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from fcn8s_tensorflow_amd import fp8  # noqa: E402
+from tests import hostile  # noqa: E402
+from tests.hostile import inp, out  # noqa: E402
 
 
 def _lib():
@@ -39,8 +41,11 @@ def _lib():
     return _lib
 
 
-def dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a)).cuda()
+@pytest.fixture(autouse=True)
+def hostile_memory():
+    """tests/hostile.py's memory for every test: fenced inputs checked intact, outputs NaN until written, NaN scratch pools, verify() at the end"""
+    with hostile.session(_lib()) as arena:
+        yield arena
 
 
 def ptr(t):
@@ -123,26 +128,25 @@ def route(name, shape, nmax):
     kind, _, arg = name.partition("/")
     rng = np.random.default_rng(1000 + 7 * H + 13 * W + Cin + 3 * Cout + K)
     x, w, b = _weights(rng, H, W, Cin, Cout, K, nmax)
-    wd, bd = dev(w), dev(b)
 
     if kind == "conv2d":                                 # fcn8s_op_conv2d, arg = r<relu>
         relu = int(arg[1:])
         def call(xs):
-            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H, W, Cout), float("nan")).cuda()
+            n = xs.shape[0]; xd, wd, bd = inp(xs), inp(w), inp(b); y = out((n, H, W, Cout))
             L.check(L.lib.fcn8s_op_conv2d(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), n, H, W, Cin, Cout, K, relu))
             torch.cuda.synchronize(); return y.cpu().numpy()
         return Route((x,), call, _bias_image(b, relu))
     if kind == "wino":                                   # fcn8s_op_conv2d_winograd, arg = tile
         tile = int(arg)
         def call(xs):
-            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H, W, Cout), float("nan")).cuda()
+            n = xs.shape[0]; xd, wd, bd = inp(xs), inp(w), inp(b); y = out((n, H, W, Cout))
             L.check(L.lib.fcn8s_op_conv2d_winograd(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), n, H, W, Cin, Cout, K, 1, tile))
             torch.cuda.synchronize(); return y.cpu().numpy()
         return Route((x,), call, _bias_image(b, 1))
     if kind == "wino_pool":                              # fcn8s_op_conv3x3_winograd_pool (inference form), arg = op_gemm_out_fused64
         option = int(arg)
         def call(xs):
-            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H // 2, W // 2, Cout), float("nan")).cuda()
+            n = xs.shape[0]; xd, wd, bd = inp(xs), inp(w), inp(b); y = out((n, H // 2, W // 2, Cout))
             fused = C.c_int(-1)
             with op_context(op_gemm_out_fused64=option):
                 L.check(L.lib.fcn8s_op_conv3x3_winograd_pool(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), None, n, H, W, Cin, Cout, 6, 0, C.byref(fused)))
@@ -152,14 +156,14 @@ def route(name, shape, nmax):
         return Route((x,), call, _bias_image(b, 1))
     if kind == "bf16":                                   # fcn8s_op_conv2d_bf16 (the bf16_fc mode's kernel)
         def call(xs):
-            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H, W, Cout), float("nan")).cuda()
+            n = xs.shape[0]; xd, wd, bd = inp(xs), inp(w), inp(b); y = out((n, H, W, Cout))
             L.check(L.lib.fcn8s_op_conv2d_bf16(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), n, H, W, Cin, Cout, K, 1))
             torch.cuda.synchronize(); return y.cpu().numpy()
         return Route((x,), call, _bias_image(b, 1))
     if kind == "bf16_train_fwd":                         # fcn8s_op_conv2d_bf16_train, forward; arg = op_bf16_rows_bn form
         form = int(arg)
         def call(xs):
-            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H, W, Cout), float("nan")).cuda()
+            n = xs.shape[0]; xd, wd, bd = inp(xs), inp(w), inp(b); y = out((n, H, W, Cout))
             with op_context(op_bf16_rows_bn=form):
                 L.check(L.lib.fcn8s_op_conv2d_bf16_train(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), 1, None, None, None, None, None, n, H, W, Cin, Cout, K))
             torch.cuda.synchronize(); return y.cpu().numpy()
@@ -170,8 +174,8 @@ def route(name, shape, nmax):
         mask = rng.standard_normal((nmax, H, W, Cin)).astype(np.float32)
         masked = kind == "bf16_train_dxm"
         def call(dys, ms=None):
-            n = dys.shape[0]; dyd = dev(dys); md = dev(ms) if masked else None
-            dx = torch.full((n, H, W, Cin), float("nan")).cuda()
+            n = dys.shape[0]; dyd, wd = inp(dys), inp(w); md = inp(ms) if masked else None
+            dx = out((n, H, W, Cin))
             with op_context(op_bf16_rows_bn=form):
                 L.check(L.lib.fcn8s_op_conv2d_bf16_train(None, None, ptr(wd), None, None, 0, ptr(dyd), ptr(md), ptr(dx), None, None, n, H, W, Cin, Cout, K))
             torch.cuda.synchronize(); return dx.cpu().numpy()
@@ -181,7 +185,7 @@ def route(name, shape, nmax):
     if kind == "fp8":                                    # fcn8s_op_conv2d_fp8: one activation exponent for every batch size
         ex = fp8.exponent(8.0)
         def call(xs):
-            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H, W, Cout), float("nan")).cuda()
+            n = xs.shape[0]; xd, wd, bd = inp(xs), inp(w), inp(b); y = out((n, H, W, Cout))
             L.check(L.lib.fcn8s_op_conv2d_fp8(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), 1, ex, n, H, W, Cin, Cout, K))
             torch.cuda.synchronize(); return y.cpu().numpy()
         return Route((x,), call, _bias_image(b, 1))
@@ -189,9 +193,8 @@ def route(name, shape, nmax):
         S = K // 2
         wt = (rng.standard_normal((K, K, Cin, Cin)) * 0.1).astype(np.float32)
         add = rng.standard_normal((nmax, H * S, W * S, Cin)).astype(np.float32)
-        wtd = dev(wt)
         def call(xs, adds):
-            n = xs.shape[0]; xd, ad = dev(xs), dev(adds); y = torch.full((n, H * S, W * S, Cin), float("nan")).cuda()
+            n = xs.shape[0]; xd, ad, wtd, bd = inp(xs), inp(adds), inp(wt), inp(b); y = out((n, H * S, W * S, Cin))
             L.check(L.lib.fcn8s_op_conv2d_transpose(None, ptr(xd), ptr(wtd), ptr(bd), ptr(ad), ptr(y), n, H, W, Cin, K, S))
             torch.cuda.synchronize(); return y.cpu().numpy()
         r = Route((x, add), call, None)
@@ -200,7 +203,7 @@ def route(name, shape, nmax):
     if kind == "maxpool":
         xr = np.maximum(x, np.float32(0))                                # post-ReLU: many exact ties
         def call(xs):
-            n = xs.shape[0]; xd = dev(xs); y = torch.full((n, H // 2, W // 2, Cin), float("nan")).cuda()
+            n = xs.shape[0]; xd = inp(xs); y = out((n, H // 2, W // 2, Cin))
             L.check(L.lib.fcn8s_op_maxpool2x2(None, ptr(xd), ptr(y), n, H, W, Cin))
             torch.cuda.synchronize(); return y.cpu().numpy()
         return Route((xr,), call, _zeros)

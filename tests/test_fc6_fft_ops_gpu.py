@@ -20,11 +20,16 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+from tests import hostile  # noqa: E402
+from tests.hostile import inp, out  # noqa: E402
 from tests.test_ops_gpu import _lib, ptr, rel_err  # noqa: E402
 
 
-def dev(a):
-    return torch.tensor(a).cuda()          # (a copy: the shared inputs are read-only)
+@pytest.fixture(autouse=True)
+def hostile_memory():
+    """tests/hostile.py's memory for every test: fenced inputs checked intact, outputs NaN until written, NaN scratch pools, verify() at the end"""
+    with hostile.session(_lib()) as arena:
+        yield arena
 
 
 BAR = 2e-5
@@ -76,16 +81,16 @@ def case(N, H, W, Cin, Cout):
 
 
 def run(shape, path, images=None, bias=True, keep=1.0, seed=0):
-    """One call of the op on `shape` (optionally on its first `images` images only); outputs pre-filled with 7.0: everything is assigned."""
+    """One call of the op on `shape` (optionally on its first `images` images only); the outputs are the arena's: everything is assigned."""
     L = _lib()
     N, H, W, Cin, Cout = shape
     c = case(*shape)
     n = images or N
-    xd, wd, dyd = dev(c["x"][:n]), dev(c["w"]), dev(c["dy"][:n])
-    bd = dev(c["b"]) if bias else None
-    y, dx = torch.full((n, H, W, Cout), 7.0).cuda(), torch.full((n, H, W, Cin), 7.0).cuda()
-    dw = torch.full((7, 7, Cin, Cout), 7.0).cuda()
-    db = torch.full((Cout,), 7.0).cuda() if bias else None
+    xd, wd, dyd = inp(c["x"][:n]), inp(c["w"]), inp(c["dy"][:n])
+    bd = inp(c["b"]) if bias else None
+    y, dx = out((n, H, W, Cout)), out((n, H, W, Cin))
+    dw = out((7, 7, Cin, Cout))
+    db = out((Cout,)) if bias else None
     bits = C.c_int(-1)
     L.check(L.lib.fcn8s_op_conv7x7_fc6_fwd_bwd(None, ptr(xd), ptr(wd), ptr(bd), ptr(dyd), ptr(y), ptr(dx), ptr(dw), ptr(db),
                                                 n, H, W, Cin, Cout, path, keep, seed, C.byref(bits)))
@@ -163,7 +168,7 @@ def test_fc6_dropout_on_partial_tiles():
 def test_fc6_op_argument_checks():
     L = _lib()
     N, H, W, Cin, Cout = 1, 8, 8, 64, 128
-    t = {k: torch.zeros(n).cuda() for k, n in (("x", N * H * W * Cin), ("w", 49 * Cin * Cout), ("dy", N * H * W * Cout), ("y", N * H * W * Cout),
+    t = {k: (out((n,)) if k in ("y", "dx", "dw") else inp(np.zeros(n, np.float32))) for k, n in (("x", N * H * W * Cin), ("w", 49 * Cin * Cout), ("dy", N * H * W * Cout), ("y", N * H * W * Cout),
                                                ("dx", N * H * W * Cin), ("dw", 49 * Cin * Cout))}
 
     def call(cin=Cin, cout=Cout, path=2, keep=1.0, null=None):

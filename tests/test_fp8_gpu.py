@@ -13,12 +13,9 @@ pytestmark = pytest.mark.gpu
 from oracle import fcn8s_oracle as orc  # noqa: E402  (checker only)
 from fcn8s_tensorflow_amd import fp8  # noqa: E402
 from fcn8s_tensorflow_amd import _lib as L  # noqa: E402
+from tests import hostile  # noqa: E402
 
 WIDTHS = (64, 64, 128, 256, 256, 256, 128)
-
-
-def dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a)).cuda()
 
 
 def ptr(t):
@@ -26,14 +23,17 @@ def ptr(t):
 
 
 def op_conv_fp8(x, w, b, x_exp, relu=1):
+    """One call on tests/hostile.py's memory (the model-level tests of this module run on the model's own): x, w, b fenced by NaN bands and
+    checked intact, y NaN inside its bands until written, verify() before the result is handed back."""
     N, H, W, Cin = x.shape
     K, Cout = w.shape[0], w.shape[-1]
-    xd, wd = dev(x.astype(np.float32)), dev(w.astype(np.float32))
-    bd = dev(b.astype(np.float32)) if b is not None else None
-    y = torch.empty((N, H, W, Cout), dtype=torch.float32, device='cuda')
-    L.check(L.lib.fcn8s_op_conv2d_fp8(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), relu, x_exp, N, H, W, Cin, Cout, K))
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
+    with hostile.session(L) as arena:
+        xd, wd = arena.inp(x.astype(np.float32), "x"), arena.inp(w.astype(np.float32), "w")
+        bd = arena.inp(b.astype(np.float32), "b") if b is not None else None
+        y = arena.out((N, H, W, Cout), name="y")
+        L.check(L.lib.fcn8s_op_conv2d_fp8(None, ptr(xd), ptr(wd), ptr(bd), ptr(y), relu, x_exp, N, H, W, Cin, Cout, K))
+        torch.cuda.synchronize()
+        return y.cpu().numpy()
 
 
 def conv64(x, w):

@@ -4,7 +4,8 @@ ReLU and the 2x2/2 max-pool with its argmax bytes) at op level, against float64 
 fcn8s_op_conv3x3_winograd_pool runs the model's own conv_fwd on a bare model; the op context "op_gemm_out_fused64" (0 = position GEMM + output
 transform, 1 = ask for the fused kernel, 2 = the same with its non-temporal-store instantiation) picks the route, and the entry reports whether the
 kernel was launched.  Channels are 64 -> 64 and the tile is 6 throughout (the only shape class the kernel takes).  Every scratch buffer of the entry is
-NaN before the call, and `pool` / `pidx` lie in the middle of larger sentinel-filled tensors.
+NaN before the call, and every tensor the entry sees is tests/hostile.py's: x, k, b fenced by NaN bands and checked intact, `pool` / `pidx` all 0xFF
+bytes inside their bands until written.
 
 Shapes (N, H, W) and the tile count T = N ceil(H / 6) ceil(W / 6); one block of the kernel owns 16 tiles:
   (1, 2, 2)     T = 1    one partial tile, one window: fifteen of the block's sixteen rows are clamped to tile T - 1
@@ -31,11 +32,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import fcn8s_oracle as orc  # noqa: E402  (checker only)
+from tests import hostile  # noqa: E402
+from tests.hostile import inp, out  # noqa: E402
 from tests.test_ops_gpu import check_conv3x3_winograd_backward, rel_err  # noqa: E402
 
 CH = 64
 TILE = 6
-BAND = 4096
+UNWRITTEN = 0xFF                                                                           # a byte of `pidx` no kernel stored
 EDGE_SHAPES = tuple((3, h, w) for h in (12, 14, 16) for w in (18, 20, 22))
 SHAPES = ((1, 2, 2), (1, 12, 12), (1, 24, 24), (1, 6, 102), (5, 6, 6), (2, 34, 22)) + EDGE_SHAPES
 BWD_CASES = (((1, 34, 22), 2), ((3, 14, 20), 1), ((1, 12, 12), 0), ((1, 6, 102), 1))     # (shape, mask_mode)
@@ -46,6 +49,13 @@ OPTION = b"op_gemm_out_fused64"
 def lib():
     from fcn8s_tensorflow_amd import _lib
     return _lib
+
+
+@pytest.fixture(autouse=True)
+def hostile_memory():
+    """tests/hostile.py's memory for every test (check_conv3x3_winograd_backward draws on it too): NaN scratch pools, verify() at the end"""
+    with hostile.session(lib()) as arena:
+        yield arena
 
 
 def ptr(t):
@@ -112,25 +122,26 @@ def reference(n, h, w):
 
 
 def call(x, k, b, option, train, f32x3=0):
-    """One fcn8s_op_conv3x3_winograd_pool call under the given op context.  pool and pidx are the middles of larger tensors: NaN / 0xEE inside,
-    a sentinel in the BAND elements on either side.  Returns the pool, the bytes, the entry's `fused` report and what became of the bands."""
+    """One fcn8s_op_conv3x3_winograd_pool call under the given op context, on the current test's arena: pool and pidx all 0xFF bytes (NaN /
+    UNWRITTEN) inside their bands; an inference pass must leave pidx alone.  Returns the pool, the bytes, the entry's `fused` report and
+    whether the arena verifies (bands and fences whole, inputs intact, every pool element written) -- the fixture verifies again at the end."""
     L = lib()
     n, h, w, _ = x.shape
-    cnt = n * (h // 2) * (w // 2) * CH
-    xd, kd, bd = (torch.tensor(np.asarray(a)).cuda() for a in (x, k, b))
-    pbuf = torch.full((2 * BAND + cnt,), -7.5, dtype=torch.float32, device="cuda")
-    ibuf = torch.full((2 * BAND + cnt,), 0x5A, dtype=torch.uint8, device="cuda")
-    pool, pidx = pbuf[BAND:BAND + cnt], ibuf[BAND:BAND + cnt]
-    pool.fill_(float("nan")); pidx.fill_(0xEE)
+    shape = (n, h // 2, w // 2, CH)
+    xd, kd, bd = inp(x, "x"), inp(k, "k"), inp(b, "b")
+    pool, pidx = out(shape, name="pool"), out(shape, torch.uint8, name="pidx", untouched=not train)
     fused = C.c_int(-1)
     torch.cuda.synchronize()
     with op_context(op_gemm_out_fused64=option, op_f32x3=f32x3):
         L.check(L.lib.fcn8s_op_conv3x3_winograd_pool(None, ptr(xd), ptr(kd), ptr(bd), ptr(pool), ptr(pidx), n, h, w, CH, CH, TILE, train, C.byref(fused)))
     torch.cuda.synchronize()
-    ph, ih = pbuf.cpu().numpy(), ibuf.cpu().numpy()
-    bands = bool((ph[:BAND] == -7.5).all() and (ph[BAND + cnt:] == -7.5).all() and (ih[:BAND] == 0x5A).all() and (ih[BAND + cnt:] == 0x5A).all())
-    shape = (n, h // 2, w // 2, CH)
-    return dict(pool=ph[BAND:BAND + cnt].reshape(shape), byte=ih[BAND:BAND + cnt].reshape(shape), fused=fused.value, bands=bands)
+    try:
+        hostile.current().verify()
+        bands = True
+    except hostile.HostileMemoryError as e:
+        print(e)
+        bands = False
+    return dict(pool=pool.cpu().numpy(), byte=pidx.cpu().numpy(), fused=fused.value, bands=bands)
 
 
 @functools.lru_cache(maxsize=None)
@@ -226,9 +237,9 @@ def test_nothing_stray_is_written_or_read(n, h, w):
             assert r["bands"], what
             assert np.isfinite(r["pool"]).all(), what
             if train:
-                assert not (r["byte"] == 0xEE).any() and r["byte"].max() <= 4, what
+                assert not (r["byte"] == UNWRITTEN).any() and r["byte"].max() <= 4, what
             else:
-                assert (r["byte"] == 0xEE).all(), what                  # an inference pass writes no bytes
+                assert (r["byte"] == UNWRITTEN).all(), what                 # an inference pass writes no bytes
 
 
 # ---- 4. exact cases ---------------------------------------------------------------------------------------------------------------------

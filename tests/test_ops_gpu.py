@@ -1,6 +1,9 @@
 """Parity of every HIP kernel (called through the C ABI's op-level entry points)
 against the CPU oracle on the same seeded inputs.  Tolerances are stated per test;
-fp32 accumulation-order differences only."""
+fp32 accumulation-order differences only.
+
+Every device tensor a call sees comes from tests/hostile.py (inp / out / inout below): 1 MiB of NaN bytes on either side, inputs checked intact,
+outputs NaN until written, and the scratch pools NaN at every hand-out -- the module's autouse fixture verifies all of it after each test."""
 import ctypes as C
 
 import numpy as np
@@ -10,6 +13,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import fcn8s_oracle as orc  # noqa: E402  (checker only)
+from tests import hostile  # noqa: E402
+from tests.hostile import inout, inp, out  # noqa: E402
 
 
 def _lib():
@@ -21,8 +26,12 @@ def _lib():
     return _lib
 
 
-def dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a)).cuda()
+@pytest.fixture(autouse=True)
+def hostile_memory():
+    """Every test of this module runs on tests/hostile.py's memory: inputs fenced by NaN bands and checked intact, outputs NaN inside their bands
+    until written, the two per-stream scratch pools NaN at every hand-out; verify() ends the test."""
+    with hostile.session(_lib()) as arena:
+        yield arena
 
 
 def ptr(t):
@@ -53,6 +62,11 @@ CONV_CASES = [
     (1, 9, 5, 96, 4, 1),
     (1, 4, 8, 2112, 20, 1),
     (1, 64, 128, 256, 20, 1),
+    (1, 8, 8, 4096, 20, 1),     # one image behind 4096 channels: head_fwd_kernel's eight K slabs (split_route.h splits for N = 1 alone) and their reduction
+    # the bias gradient's column sums (launch_colsum): 32768 rows of 64 columns are 128 partial rows, colsum_final_kernel's eight-deep loop;
+    # 4096 columns are four column tiles of colsum_kernel at 256 threads per row
+    (1, 128, 256, 4, 64, 1),
+    (1, 4, 8, 64, 4096, 1),
 ]
 
 
@@ -72,8 +86,8 @@ def test_conv2d_fwd_bwd(N, H, W, Cin, Cout, K):
     y_ref = yt.detach().permute(0, 2, 3, 1).numpy()
     dx_ref = xt.grad.permute(0, 2, 3, 1).numpy(); dw_ref = wt.grad.numpy(); db_ref = bt.grad.numpy()
 
-    dx_, dw_, db_, y_ = torch.empty(N, H, W, Cin).cuda(), torch.empty(K, K, Cin, Cout).cuda(), torch.empty(Cout).cuda(), torch.empty(N, H, W, Cout).cuda()
-    xd, wd, bd, dyd = dev(x), dev(w), dev(b), dev(dy)
+    dx_, dw_, db_, y_ = out((N, H, W, Cin)), out((K, K, Cin, Cout)), out((Cout,)), out((N, H, W, Cout))
+    xd, wd, bd, dyd = inp(x), inp(w), inp(b), inp(dy)
     L.check(L.lib.fcn8s_op_conv2d(None, ptr(xd), ptr(wd), ptr(bd), ptr(y_), N, H, W, Cin, Cout, K, 0))
     L.check(L.lib.fcn8s_op_conv2d_bwd(None, ptr(xd), ptr(wd), ptr(dyd), ptr(dx_), ptr(dw_), ptr(db_), N, H, W, Cin, Cout, K))
     torch.cuda.synchronize()
@@ -81,9 +95,33 @@ def test_conv2d_fwd_bwd(N, H, W, Cin, Cout, K):
     assert rel_err(dx_.cpu().numpy(), dx_ref) < 2e-5
     assert rel_err(dw_.cpu().numpy(), dw_ref) < 2e-5
     assert rel_err(db_.cpu().numpy(), db_ref) < 2e-5
+    # the bias gradient alone: the two-kernel column sum (launch_colsum), whichever kernel summed the columns beside dw above
+    db2 = out((Cout,))
+    L.check(L.lib.fcn8s_op_conv2d_bwd(None, None, None, ptr(dyd), None, None, ptr(db2), N, H, W, Cin, Cout, K))
+    torch.cuda.synchronize()
+    print("conv2d %s: db against float64 %.3g beside dw, %.3g from the column sum alone (of max |db|)"
+          % ((N, H, W, Cin, Cout, K), rel_err(db_.cpu().numpy(), db_ref), rel_err(db2.cpu().numpy(), db_ref)))
+    assert rel_err(db2.cpu().numpy(), db_ref) < 2e-5
     # ReLU epilogue
     L.check(L.lib.fcn8s_op_conv2d(None, ptr(xd), ptr(wd), ptr(bd), ptr(y_), N, H, W, Cin, Cout, K, 1))
     assert rel_err(y_.cpu().numpy(), np.maximum(y_ref, 0)) < 2e-5
+
+
+@pytest.mark.parametrize("case", [(1, 64, 128, 256, 20, 1), (1, 128, 256, 4, 64, 1), (1, 4, 8, 64, 4096, 1)])
+def test_scratch_pools_are_poisoned_where_a_case_draws_on_them(case):
+    """The fixture's NaN fill of the two per-stream pools did run: a score head whose bias gradient takes sixteen partial rows, and the two
+    column-sum shapes (128 partial rows; four column tiles), count the bytes handed out.  (The K slabs of the one-image score head,
+    (1, 8, 8, 4096, 20, 1), live in the entry's own filter-bank scratch, which the entry fills itself; a batch of two never splits.)"""
+    L = _lib()
+    assert hostile.poisoned_bytes(L) == 0
+    test_conv2d_fwd_bwd(*case)
+    N, H, W, Cin, Cout, K = case
+    assert hostile.poisoned_bytes(L) >= 4 * Cout * 2          # at least two partial rows of Cout floats
+    got = C.c_int64(-1)
+    L.check(L.lib.fcn8s_get_option(None, b"op_poison_scratch", C.byref(got)))
+    assert got.value == 1
+    with pytest.raises(ValueError):
+        L.check(L.lib.fcn8s_set_option(None, b"op_scratch_poisoned_bytes", 0))      # read-only
 
 
 @pytest.mark.parametrize("N,H,W,Cin,Cout,tile", [(1, 4, 6, 16, 32, 2), (2, 8, 16, 64, 128, 2), (1, 16, 32, 256, 256, 2), (3, 2, 2, 32, 64, 2),
@@ -98,13 +136,13 @@ def test_conv3x3_winograd(N, H, W, Cin, Cout, tile, K=3):
     b = rng.standard_normal(Cout).astype(np.float32)
     ref = orc.conv2d_same_t(torch.tensor(x).permute(0, 3, 1, 2).double(), torch.tensor(w).double(), torch.tensor(b).double(), relu=True)
     ref = ref.permute(0, 2, 3, 1).numpy()
-    xd, wd, bd = dev(x), dev(w), dev(b)
-    y_ = torch.empty(N, H, W, Cout).cuda()
+    xd, wd, bd = inp(x), inp(w), inp(b)
+    y_ = out((N, H, W, Cout))
     L.check(L.lib.fcn8s_op_conv2d_winograd(None, ptr(xd), ptr(wd), ptr(bd), ptr(y_), N, H, W, Cin, Cout, K, 1, tile))
     torch.cuda.synchronize()
     tol = 1e-5 if tile == 2 else 1e-4          # fp32 F(4x4,3x3) / F(6x6,3x3) carry ~1e-5 / 2e-5 of the output range (winograd.hip header)
     assert rel_err(y_.cpu().numpy(), ref) < tol
-    yd = torch.empty(N, H, W, Cout).cuda()
+    yd = out((N, H, W, Cout))
     L.check(L.lib.fcn8s_op_conv2d(None, ptr(xd), ptr(wd), ptr(bd), ptr(yd), N, H, W, Cin, Cout, K, 1))
     torch.cuda.synchronize()
     assert rel_err(y_.cpu().numpy(), yd.cpu().numpy()) < tol       # and against the direct kernel
@@ -149,7 +187,7 @@ def check_conv3x3_winograd_backward(N, H, W, Cin, Cout, tile, pooled, mask_mode,
     z = orc.conv2d_same_t(xt, wt, bt, relu=False)
     yt = torch.relu(z)
     if pooled:
-        out = orc.maxpool2x2_t(yt)
+        pool_ref = orc.maxpool2x2_t(yt)
         dy = rng.standard_normal((N, H // 2, W // 2, Cout)).astype(np.float32)
         # max-pool routing is discontinuous: a window whose two largest entries agree to the fp32 Winograd round-off (1e-5 of the range) may
         # legitimately send its gradient to the other pixel (at 8x8x512 one such window moved a whole 3x3x512 patch of dx by 1e-2).  Those
@@ -159,25 +197,25 @@ def check_conv3x3_winograd_backward(N, H, W, Cin, Cout, tile, pooled, mask_mode,
         near_tie = (srt[..., 3] > 0) & (srt[..., 3] - srt[..., 2] < 1e-4 * np.abs(ynp).max())
         assert near_tie.mean() < 0.01
         dy[near_tie] = 0.0
-        out.backward(torch.tensor(dy).permute(0, 3, 1, 2).double())
+        pool_ref.backward(torch.tensor(dy).permute(0, 3, 1, 2).double())
     else:
         dy = rng.standard_normal((N, H, W, Cout)).astype(np.float32)      # gradient w.r.t. the pre-activation (the ReLU mask is the consumer's job)
         z.backward(torch.tensor(dy).permute(0, 3, 1, 2).double())
-        out = None
+        pool_ref = None
     dx_ref = xt.grad.permute(0, 2, 3, 1).numpy() + skip
     if mask_mode:
         dx_ref = dx_ref * (x > 0)
     dw_ref, db_ref = wt.grad.numpy(), bt.grad.numpy()
-    xd, wd, bd, dyd, sk = dev(x), dev(w), dev(b), dev(dy), dev(skip)
-    y_ = None if pooled else torch.empty(N, H, W, Cout).cuda()
-    pool_ = torch.empty(N, H // 2, W // 2, Cout).cuda() if pooled else None
-    dx_, dw_, db_ = torch.empty(N, H, W, Cin).cuda(), torch.empty(3, 3, Cin, Cout).cuda(), torch.empty(Cout).cuda()
+    xd, wd, bd, dyd, sk = inp(x), inp(w), inp(b), inp(dy), inp(skip)
+    y_ = None if pooled else out((N, H, W, Cout))
+    pool_ = out((N, H // 2, W // 2, Cout)) if pooled else None
+    dx_, dw_, db_ = out((N, H, W, Cin)), out((3, 3, Cin, Cout)), out((Cout,))
     L.check(L.lib.fcn8s_op_conv3x3_winograd_fwd_bwd(None, ptr(xd), ptr(wd), ptr(bd), ptr(dyd), ptr(sk), ptr(y_), ptr(pool_), ptr(dx_), ptr(dw_), ptr(db_),
                                                     N, H, W, Cin, Cout, tile, pooled, mask_mode))
     torch.cuda.synchronize()
     tol = 2e-5 if tile == 2 else 1e-4
     if pooled:
-        assert rel_err(pool_.cpu().numpy(), out.detach().permute(0, 2, 3, 1).numpy()) < tol
+        assert rel_err(pool_.cpu().numpy(), pool_ref.detach().permute(0, 2, 3, 1).numpy()) < tol
     else:
         assert rel_err(y_.cpu().numpy(), yt.detach().permute(0, 2, 3, 1).numpy()) < tol
     assert rel_err(dx_.cpu().numpy(), dx_ref) < tol, rel_err(dx_.cpu().numpy(), dx_ref)
@@ -220,8 +258,8 @@ def test_conv_bf16_mfma(N, H, W, Cin, Cout, K):
     ref = orc.conv2d_same_t(xr, wr, torch.tensor(b).double(), relu=True).permute(0, 2, 3, 1).numpy()
     exact = orc.conv2d_same_t(torch.tensor(x).double().permute(0, 3, 1, 2), torch.tensor(w).double(), torch.tensor(b).double(), relu=True)
     exact = exact.permute(0, 2, 3, 1).numpy()
-    xd, wd, bd = dev(x), dev(w), dev(b)
-    y_ = torch.empty(N, H, W, Cout).cuda()
+    xd, wd, bd = inp(x), inp(w), inp(b)
+    y_ = out((N, H, W, Cout))
     L.check(L.lib.fcn8s_op_conv2d_bf16(None, ptr(xd), ptr(wd), ptr(bd), ptr(y_), N, H, W, Cin, Cout, K, 1))
     torch.cuda.synchronize()
     y = y_.cpu().numpy()
@@ -264,9 +302,9 @@ def test_conv_bf16_train_kernels(N, H, W, Cin, Cout, K):
     dw_ref = torch.nn.grad.conv2d_weight(xr, wr.shape, dyr, padding=pad).permute(2, 3, 1, 0).numpy()
     db_ref = dy.astype(np.float64).sum((0, 1, 2))
     dw_exact = torch.nn.grad.conv2d_weight(nchw(torch.tensor(x).double()), wr.shape, nchw(torch.tensor(dy).double()), padding=pad).permute(2, 3, 1, 0).numpy()
-    xd, wd, bd, dyd, md = dev(x), dev(w), dev(b), dev(dy), dev(mask)
-    y_, dx_ = torch.empty(N, H, W, Cout).cuda(), torch.empty(N, H, W, Cin).cuda()
-    dw_, db_ = torch.full((K, K, Cin, Cout), 7.0).cuda(), torch.full((Cout,), 7.0).cuda()      # (garbage: the gradients are assigned, not accumulated)
+    xd, wd, bd, dyd, md = inp(x), inp(w), inp(b), inp(dy), inp(mask)
+    y_, dx_ = out((N, H, W, Cout)), out((N, H, W, Cin))
+    dw_, db_ = out((K, K, Cin, Cout)), out((Cout,))      # (garbage: the gradients are assigned, not accumulated)
     L.check(L.lib.fcn8s_op_conv2d_bf16_train(None, ptr(xd), ptr(wd), ptr(bd), ptr(y_), 1, ptr(dyd), ptr(md), ptr(dx_), ptr(dw_), ptr(db_), N, H, W, Cin, Cout, K))
     torch.cuda.synchronize()
     assert rel_err(y_.cpu().numpy(), y_ref) < 1e-5
@@ -275,7 +313,7 @@ def test_conv_bf16_train_kernels(N, H, W, Cin, Cout, K):
     assert rel_err(db_.cpu().numpy(), db_ref) < 1e-5
     assert 1e-5 < rel_err(dw_.cpu().numpy(), dw_exact) < 3e-2
     # the data gradient without a mask (fc6's case: an identity epilogue -- few output tiles behind a long reduction split K into slabs added in split order)
-    dx2 = torch.full((N, H, W, Cin), 7.0).cuda()
+    dx2 = out((N, H, W, Cin))
     L.check(L.lib.fcn8s_op_conv2d_bf16_train(None, None, ptr(wd), None, None, 0, ptr(dyd), None, ptr(dx2), None, None, N, H, W, Cin, Cout, K))
     torch.cuda.synchronize()
     assert rel_err(dx2.cpu().numpy(), nhwc(torch.nn.grad.conv2d_input(xr.shape, wr, dyr, padding=pad))) < 1e-5
@@ -284,7 +322,7 @@ def test_conv_bf16_train_kernels(N, H, W, Cin, Cout, K):
     try:
         outs = []
         for _ in range(2):
-            t = torch.empty(K, K, Cin, Cout).cuda()
+            t = out((K, K, Cin, Cout))
             L.check(L.lib.fcn8s_op_conv2d_bf16_train(None, ptr(xd), None, None, None, 0, ptr(dyd), None, None, ptr(t), None, N, H, W, Cin, Cout, K))
             torch.cuda.synchronize()
             outs.append(t.cpu().numpy())
@@ -295,7 +333,7 @@ def test_conv_bf16_train_kernels(N, H, W, Cin, Cout, K):
     # the padded copies as [rows][C] instead of channel-chunk planes (the layout the other bf16 modes hand these kernels): the same results
     L.check(L.lib.fcn8s_set_option(None, b"op_bf16_planes", 0))
     try:
-        y2, dx3, dw2 = torch.empty(N, H, W, Cout).cuda(), torch.empty(N, H, W, Cin).cuda(), torch.empty(K, K, Cin, Cout).cuda()
+        y2, dx3, dw2 = out((N, H, W, Cout)), out((N, H, W, Cin)), out((K, K, Cin, Cout))
         L.check(L.lib.fcn8s_op_conv2d_bf16_train(None, ptr(xd), ptr(wd), ptr(bd), ptr(y2), 1, ptr(dyd), ptr(md), ptr(dx3), ptr(dw2), None, N, H, W, Cin, Cout, K))
         torch.cuda.synchronize()
     finally:
@@ -335,26 +373,26 @@ def test_conv_bf16_train_rows_forms(N, H, W, Cin, Cout):
     xr, wr, dyr = nchw(rb(x)), rb(w).permute(3, 2, 0, 1), nchw(rb(dy))
     y_ref = nhwc(torch.relu(torch.nn.functional.conv2d(xr, wr, torch.tensor(b).double(), padding=1)))
     dx_ref = nhwc(torch.nn.grad.conv2d_input(xr.shape, wr, dyr, padding=1)) * (mask > 0)
-    xd, wd, bd, dyd, md = dev(x), dev(w), dev(b), dev(dy), dev(mask)
-    out = {}
+    xd, wd, bd, dyd, md = inp(x), inp(w), inp(b), inp(dy), inp(mask)
+    res = {}
     for form in (128, 64):
         L.check(L.lib.fcn8s_set_option(None, b"op_bf16_rows_bn", form))
         try:
-            y_, dx_ = torch.full((N, H, W, Cout), 7.0).cuda(), torch.full((N, H, W, Cin), 7.0).cuda()
+            y_, dx_ = out((N, H, W, Cout)), out((N, H, W, Cin))
             L.check(L.lib.fcn8s_op_conv2d_bf16_train(None, ptr(xd), ptr(wd), ptr(bd), ptr(y_), 1, ptr(dyd), ptr(md), ptr(dx_), None, None, N, H, W, Cin, Cout, K))
             torch.cuda.synchronize()
         finally:
             L.check(L.lib.fcn8s_set_option(None, b"op_bf16_rows_bn", 0))
-        out[form] = (y_.cpu().numpy(), dx_.cpu().numpy())
-        assert rel_err(out[form][0], y_ref) < 1e-5, form
-        assert rel_err(out[form][1], dx_ref) < 1e-5, form
+        res[form] = (y_.cpu().numpy(), dx_.cpu().numpy())
+        assert rel_err(res[form][0], y_ref) < 1e-5, form
+        assert rel_err(res[form][1], dx_ref) < 1e-5, form
     # (a forward launch with few blocks behind >= 24 K-tiles -- Cin >= 256 at these sizes -- splits K into slabs added in slab order, and the two forms cut the
     #  K range differently: the same terms in another order)
     if Cin >= 256:
-        assert rel_err(out[128][0], out[64][0]) < 2e-6
+        assert rel_err(res[128][0], res[64][0]) < 2e-6
     else:
-        np.testing.assert_array_equal(out[128][0], out[64][0])
-    np.testing.assert_array_equal(out[128][1], out[64][1])
+        np.testing.assert_array_equal(res[128][0], res[64][0])
+    np.testing.assert_array_equal(res[128][1], res[64][1])
 
 
 @pytest.mark.parametrize("N,H,W,C", [(2, 8, 8, 64), (1, 4, 6, 8), (1, 32, 64, 128)])
@@ -365,8 +403,8 @@ def test_maxpool(N, H, W, C):
     dy = rng.standard_normal((N, H // 2, W // 2, C)).astype(np.float32)
     xt = torch.tensor(x).permute(0, 3, 1, 2).requires_grad_(True)
     yt = orc.maxpool2x2_t(xt)
-    xd, dyd = dev(x), dev(dy)
-    y_ = torch.empty(N, H // 2, W // 2, C).cuda(); dx_ = torch.empty(N, H, W, C).cuda()
+    xd, dyd = inp(x), inp(dy)
+    y_ = out((N, H // 2, W // 2, C)); dx_ = out((N, H, W, C))
     L.check(L.lib.fcn8s_op_maxpool2x2(None, ptr(xd), ptr(y_), N, H, W, C))
     np.testing.assert_array_equal(y_.cpu().numpy(), yt.detach().permute(0, 2, 3, 1).numpy())
     # backward with the fused ReLU mask == autograd through relu(pre)->pool when x = relu(pre)
@@ -392,9 +430,9 @@ def test_conv2d_transpose_fwd_bwd(N, Hi, Wi, C, K, S):
     bt = torch.tensor(b).double().requires_grad_(True)
     yt = orc.conv2d_transpose_same_t(xt, wt, bt, S) + torch.tensor(add).permute(0, 3, 1, 2).double()
     yt.backward(torch.tensor(dy).permute(0, 3, 1, 2).double())
-    xd, wd, bd, ad, dyd = dev(x), dev(w), dev(b), dev(add), dev(dy)
-    y_ = torch.empty(N, Hi * S, Wi * S, C).cuda()
-    dx_, dw_, db_ = torch.empty(N, Hi, Wi, C).cuda(), torch.empty(K, K, C, C).cuda(), torch.empty(C).cuda()
+    xd, wd, bd, ad, dyd = inp(x), inp(w), inp(b), inp(add), inp(dy)
+    y_ = out((N, Hi * S, Wi * S, C))
+    dx_, dw_, db_ = out((N, Hi, Wi, C)), out((K, K, C, C)), out((C,))
     L.check(L.lib.fcn8s_op_conv2d_transpose(None, ptr(xd), ptr(wd), ptr(bd), ptr(ad), ptr(y_), N, Hi, Wi, C, K, S))
     L.check(L.lib.fcn8s_op_conv2d_transpose_bwd(None, ptr(xd), ptr(wd), ptr(dyd), ptr(dx_), ptr(dw_), ptr(db_), N, Hi, Wi, C, K, S))
     torch.cuda.synchronize()
@@ -413,12 +451,12 @@ def test_softmax_xent_and_argmax(npix, Cc):
     lt = torch.tensor(logits).double().requires_grad_(True)
     loss = torch.nn.functional.cross_entropy(lt, torch.tensor(labels.astype(np.int64)))
     loss.backward()
-    ld, lab = dev(logits), dev(labels)
-    dl = torch.empty(npix, Cc).cuda(); lo = torch.zeros(1).cuda()
+    ld, lab = inp(logits), inp(labels)
+    dl = out((npix, Cc)); lo = inout(np.zeros(1, np.float32))
     L.check(L.lib.fcn8s_op_softmax_xent(None, ptr(ld), ptr(lab), ptr(dl), ptr(lo), npix, Cc))
     assert abs(float(lo.cpu()) - float(loss.detach())) < 1e-5 * max(1.0, abs(float(loss.detach())))
     assert np.abs(dl.cpu().numpy() - lt.grad.numpy()).max() < 1e-6
-    sm = torch.empty(npix, Cc).cuda(); am = torch.empty(npix, dtype=torch.int64).cuda()
+    sm = out((npix, Cc)); am = out((npix,), torch.int64)
     L.check(L.lib.fcn8s_op_softmax_argmax(None, ptr(ld), ptr(sm), ptr(am), npix, Cc))
     sm_ref = orc.softmax(logits)
     assert np.abs(sm.cpu().numpy() - sm_ref).max() < 1e-6
@@ -429,8 +467,8 @@ def test_argmax_ties_lowest_index():
     L = _lib()
     logits = np.zeros((64, 20), np.float32)
     logits[:, 7] = 1.0; logits[:, 11] = 1.0       # exact tie -> lowest index (7)
-    am = torch.empty(64, dtype=torch.int64).cuda()
-    ld = dev(logits)
+    am = out((64,), torch.int64)
+    ld = inp(logits)
     L.check(L.lib.fcn8s_op_softmax_argmax(None, ptr(ld), None, ptr(am), 64, 20))
     torch.cuda.synchronize()
     assert (am.cpu().numpy() == 7).all()
@@ -441,8 +479,8 @@ def test_confusion_matrix():
     rng = np.random.default_rng(5)
     n, Cc = 100000, 20
     lab = rng.integers(0, Cc, n).astype(np.uint8); pred = rng.integers(0, Cc, n).astype(np.int64)
-    conf = torch.zeros(Cc * Cc, dtype=torch.int64).cuda()
-    labd, predd = dev(lab), dev(pred)
+    conf = inout(np.zeros(Cc * Cc, np.int64))
+    labd, predd = inp(lab), inp(pred)
     for _ in range(2):
         L.check(L.lib.fcn8s_op_confusion(None, ptr(labd), ptr(predd), n, ptr(conf), Cc))
     torch.cuda.synchronize()
@@ -454,20 +492,20 @@ def test_optimizers():
     rng = np.random.default_rng(6)
     n = 100003
     th = rng.standard_normal(n).astype(np.float32); m = np.zeros(n, np.float32); v = np.zeros(n, np.float32)
-    thd, md, vd = dev(th), dev(m), dev(v)
+    thd, md, vd = inout(th), inout(m), inout(v)
     for t in range(1, 4):
         g = rng.standard_normal(n).astype(np.float32)
         th, m, v = orc.tf_adam_step(th, g, m, v, t, 1e-3)
-        gd = dev(g)
+        gd = inp(g)
         L.check(L.lib.fcn8s_op_tf_adam(None, ptr(thd), ptr(gd), ptr(md), ptr(vd), n, t, 1e-3, 0.9, 0.999, 1e-8, 1.0))
         torch.cuda.synchronize()
     assert np.abs(thd.cpu().numpy() - th).max() < 2e-6
     assert np.abs(md.cpu().numpy() - m).max() < 1e-6 and np.abs(vd.cpu().numpy() - v).max() < 1e-6
-    buf = np.zeros(n, np.float32); bd = dev(buf); th2 = th.copy(); th2d = dev(th2)
+    buf = np.zeros(n, np.float32); bd = inout(buf); th2 = th.copy(); th2d = inout(th2)
     for _ in range(3):
         g = rng.standard_normal(n).astype(np.float32)
         th2, buf = orc.sgd_momentum_step(th2, g, buf, 1e-2)
-        gd = dev(g)
+        gd = inp(g)
         L.check(L.lib.fcn8s_op_sgd_momentum(None, ptr(th2d), ptr(gd), ptr(bd), n, 1e-2, 0.9, 1.0))
         torch.cuda.synchronize()
     assert np.abs(th2d.cpu().numpy() - th2).max() < 2e-6
@@ -477,12 +515,12 @@ def test_preprocess():
     L = _lib()
     rng = np.random.default_rng(7)
     img = rng.integers(0, 256, (2, 4, 8, 3), dtype=np.uint8)
-    out = torch.empty(2, 4, 8, 4).cuda()
-    imgd = dev(img)
-    L.check(L.lib.fcn8s_op_preprocess(None, ptr(imgd), 0, ptr(out), 2 * 4 * 8))
+    o4 = out((2, 4, 8, 4))
+    imgd = inp(img)
+    L.check(L.lib.fcn8s_op_preprocess(None, ptr(imgd), 0, ptr(o4), 2 * 4 * 8))
     torch.cuda.synchronize()
     ref = orc.preprocess_t(torch.tensor(img).float()).numpy()
-    o = out.cpu().numpy()
+    o = o4.cpu().numpy()
     np.testing.assert_allclose(o[..., :3], ref, rtol=0, atol=1e-5)
     assert (o[..., 3] == 0).all()
 
@@ -497,7 +535,7 @@ def test_split_piece_count_sets_the_product_accuracy():
     N, H, W, Cin, Cout = 2, 32, 32, 512, 256
     x = rng.standard_normal((N, H, W, Cin)).astype(np.float32)
     w = (rng.standard_normal((1, 1, Cin, Cout)) / np.sqrt(Cin)).astype(np.float32)
-    xd, wd = dev(x), dev(w)
+    xd, wd = inp(x), inp(w)
     want = x.reshape(-1, Cin).astype(np.float64) @ w.reshape(Cin, Cout).astype(np.float64)
 
     def two_pieces(a):
@@ -515,7 +553,7 @@ def test_split_piece_count_sets_the_product_accuracy():
     try:
         for pieces in (0, 3, 2):
             L.check(L.lib.fcn8s_set_option(None, b"op_split_pieces", pieces))
-            y = torch.empty(N, H, W, Cout).cuda()
+            y = out((N, H, W, Cout))
             L.check(L.lib.fcn8s_op_conv2d(None, ptr(xd), ptr(wd), None, ptr(y), N, H, W, Cin, Cout, 1, 0))
             torch.cuda.synchronize()
             got = y.cpu().numpy().reshape(-1, Cout)
