@@ -177,6 +177,8 @@ SIGNATURES = {
     "fcn8s_op_class_mix": (_i, [_p, _p, _p, _p, _i, _i64, _i, C.c_uint64, C.c_uint64, _p, _p, _p, _p]),
     "fcn8s_op_strong_augment_work_bytes": (_sz, [_i]),
     "fcn8s_op_strong_augment": (_i, [_p, _p, _i, _i, _i, C.c_uint64, C.c_uint64, _p, _p, _p, _p, _p, _p]),
+    "fcn8s_op_fda_work_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "fcn8s_op_fda_transfer": (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "fcn8s_op_boundary_pair": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "fcn8s_op_boundary_distance": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "fcn8s_op_regions_work_bytes": (_sz, [_i, _i, _i]),

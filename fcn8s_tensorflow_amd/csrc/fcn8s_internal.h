@@ -453,6 +453,12 @@ void launch_class_mix(const uint8_t* images, const uint8_t* labels, const int* s
 size_t strong_augment_work_bytes(int N);
 void launch_strong_augment(const uint8_t* images, int N, int H, int W, unsigned long long seed, unsigned long long draw, const int* jitter, const int* blur,
                            const unsigned short* taps, void* work, uint8_t* out_images, int* params_out, hipStream_t s);
+// fda.hip (fcn8s_op_fda_transfer; the definition is in fcn8s_hip.h).  Tables and pairs, row DFT (MFMA), column DFT, delta, column synthesis, row synthesis
+// (MFMA).  N, M <= 256, H * W < 2^31, 0 <= b <= 96, 2 b + 1 <= min(H, W); work: fda_work_bytes(N, M, H, W, b) bytes at any alignment; pair_dev and one of
+// the two outputs may be null.
+size_t fda_work_bytes(int N, int M, int H, int W, int b);
+void launch_fda_transfer(const uint8_t* images, int N, const uint8_t* targets, int M, int H, int W, int b, const int* pair_dev, void* work, uint8_t* out_u8,
+                         float* out_f32, hipStream_t s);
 // boundary.hip (fcn8s_op_boundary_pair; the definition is in fcn8s_hip.h).  One kernel; rings [R + 1][34][34], bprec / brec [R + 2][34] and bad [1] are
 // accumulated into.  1 <= R <= 16, H * W < 2^31.
 void launch_boundary_pair(const uint8_t* gt, const void* pred, int pred_kind, int N, int H, int W, int R, unsigned long long* rings,

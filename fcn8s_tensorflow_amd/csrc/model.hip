@@ -4846,6 +4846,33 @@ int fcn8s_op_strong_augment(void* stream, const uint8_t* images, int N, int H, i
     launch_strong_augment(images, N, H, W, seed, draw, jitter, blur, taps, work, out_images, params_out, (hipStream_t)stream);
     OPCHK(); return FCN8S_OK;
 }
+size_t fcn8s_op_fda_work_bytes(int N, int M, int H, int W, int b) { return fda_work_bytes(N, M, H, W, b); }
+int fcn8s_op_fda_transfer(void* stream, const uint8_t* images, int N, const uint8_t* targets, int M, int H, int W, int b, const int32_t* pair_dev, void* work,
+                          uint8_t* out_u8, float* out_f32)
+{
+    if (!images || !targets || !work || (!out_u8 && !out_f32) || N <= 0 || M <= 0 || H <= 0 || W <= 0)
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "fda_transfer: bad argument (null images / targets / work, both outputs null, or N, M, H or W <= 0)");
+    if (b < 0 || b > 96 || 2 * b + 1 > (H < W ? H : W))
+        return fail(nullptr, FCN8S_ERR_BAD_ARG, "fda_transfer: the half-width b must satisfy 0 <= b <= 96 and 2 b + 1 <= min(H, W)");
+    if (((uintptr_t)out_f32 & 3) != 0) return fail(nullptr, FCN8S_ERR_BAD_ARG, "fda_transfer: out_f32 must be 4-byte aligned");
+    if (N > 256 || M > 256 || (int64_t)H * W >= (1LL << 31))
+        return fail(nullptr, FCN8S_ERR_SHAPE, "fda_transfer: a batch has at most 256 images and an image fewer than 2^31 pixels");
+    {
+        const uintptr_t P3 = (uintptr_t)H * (uintptr_t)W * 3;
+        const uintptr_t in[4][2] = {{(uintptr_t)images, (uintptr_t)N * P3}, {(uintptr_t)targets, (uintptr_t)M * P3},
+                                    {(uintptr_t)pair_dev, pair_dev ? (uintptr_t)N * 4 : 0}, {(uintptr_t)work, (uintptr_t)fda_work_bytes(N, M, H, W, b)}};
+        const uintptr_t out[2][2] = {{(uintptr_t)out_u8, out_u8 ? (uintptr_t)N * P3 : 0}, {(uintptr_t)out_f32, out_f32 ? (uintptr_t)N * P3 * 4 : 0}};
+        for (int o = 0; o < 2; ++o)
+            for (int i = 0; i < 4; ++i)
+                if (out[o][1] && in[i][1] && out[o][0] < in[i][0] + in[i][1] && in[i][0] < out[o][0] + out[o][1])
+                    return fail(nullptr, FCN8S_ERR_BAD_ARG, "fda_transfer: an output overlaps images, targets, pair_dev or work");
+        if (out[0][1] && out[1][1] && out[0][0] < out[1][0] + out[1][1] && out[1][0] < out[0][0] + out[0][1])
+            return fail(nullptr, FCN8S_ERR_BAD_ARG, "fda_transfer: the two outputs overlap");
+    }
+    take_deferred_error(nullptr);
+    launch_fda_transfer(images, N, targets, M, H, W, b, pair_dev, work, out_u8, out_f32, (hipStream_t)stream);
+    OPCHK(); return FCN8S_OK;
+}
 int fcn8s_op_boundary_pair(void* stream, const uint8_t* gt_label_ids, const void* pred, int pred_kind, int N, int H, int W, int R,
                            int64_t* rings, int64_t* bprec, int64_t* brec, int64_t* bad)
 {

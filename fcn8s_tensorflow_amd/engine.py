@@ -1159,6 +1159,24 @@ class Engine:
             images, seed=seed, draw=draw, jitter=jitter, blur=blur, params=params, work=getattr(self, "_strong_augment_work", None))
         return (out, par) if params else out
 
+    def fda_transfer(self, images, targets, b=None, beta=0.01, pair=None, out_float=False, status=False):
+        """One `fcn8s_op_fda_transfer` call (fda.py; the definition is in include/fcn8s_hip.h) on uint8 device tensors [N,H,W,3] and [M,H,W,3]
+        of one height and width, on the current stream: Fourier domain adaptation -- the amplitudes of the (2 b + 1)^2 lowest frequencies of
+        source n become those of target pair[n] (None: n mod M; a sequence of N ints in [0, M); or an int32 device tensor of N), the phases
+        stay.  `b` None: `fda.half_width(H, W, beta)` = floor(min(H, W) beta), the published rule.  The scratch is kept on the engine and
+        regrown only when a larger one is needed.  Returns a new tensor, uint8 (clamp(rint(y), 0, 255)) or, with `out_float`, the float32 y;
+        followed by the flag (1: a pair[n] of a device tensor lay outside [0, M) and counted as n mod M) with `status`, which synchronises
+        and is meant for tests."""
+        from . import fda
+        if b is None:
+            if not hasattr(images, "shape") or len(images.shape) != 4:
+                raise ValueError("images have to be a contiguous uint8 tensor [N,H,W,3] on the GPU")
+            if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)) or not 0.0 <= float(beta) <= 0.5:
+                raise ValueError("`beta` must be a number in [0, 0.5], got {!r}".format(beta))
+            b = fda.half_width(images.shape[1], images.shape[2], beta)
+        out, self._fda_work = fda.transfer_device(images, targets, b, pair=pair, out_float=out_float, work=getattr(self, "_fda_work", None))
+        return (out, fda.flag_of(self._fda_work)) if status else out
+
     def regions_label(self, labels, connectivity=4, area=True):
         """One `fcn8s_op_regions_label` call (regions.py; the definition is in include/fcn8s_hip.h) on a device tensor of class ids, int64 as
         `predict` returns them or uint8, [H,W] or [N,H,W]: (comp, area | None), int32 device tensors of the same shape -- the id (smallest

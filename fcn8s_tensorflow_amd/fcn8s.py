@@ -53,6 +53,7 @@ from . import temperature as ts_mod
 from . import pseudo_label as pl_mod
 from . import class_mix as cm_mod
 from . import strong_augment as sa_mod
+from . import fda as fda_mod
 from . import regions as regions_mod
 from . import sweeps
 from . import loss as loss_mod
@@ -247,7 +248,8 @@ class FCN8s:
               entropy_weight=0.0,
               entropy_pixels='unlabeled',
               entropy_images='all',
-              focal_gamma=0.0):
+              focal_gamma=0.0,
+              fda_beta=None):
         '''Trains the model; arguments as fcn8s_tensorflow.py:424-503.  Summaries are written as TensorBoard
         event files (`<summaries_dir>/<summaries_name>[_eval]/events.out.tfevents.*`: total_loss, learning_rate and
         mean / stddev / max / min / histogram of the ten watched weight-bias pairs, :331-366) and, for reading
@@ -325,7 +327,17 @@ class FCN8s:
         engine already has) it raises, because both address the same thing.  0, the default, is off: nothing new is launched or allocated and
         the step is bit for bit what it was.  The evaluations keep reporting the reference's loss, and the engine's previous setting is
         restored when train() returns or raises.
-        Not done here: a separate weight on the unlabelled term (change M), a per-class or per-pixel weight or a threshold on the entropy,
+        `fda_beta` adds Fourier domain adaptation of the labelled batch (FDA, Yang & Soatto 2020; fda.py): a float in (0, 0.09] needs
+        `unlabeled_generator` (it raises otherwise); per batch, and per micro-batch under `accumulation_steps`, the labelled uint8 images x
+        become `Engine.fda_transfer(x, u, beta=fda_beta, pair=(n + draw) mod M)` -- the amplitudes of the (2 b + 1)^2 lowest frequencies,
+        b = floor(min(H, W) fda_beta), of labelled image n are replaced by those of the CLEAN unlabelled image (n + draw) mod M, the phases
+        stay -- as soon as the unlabelled batch u is on the device and before anything changes it.  `draw` is the mixing's, so a resumed run
+        pairs as the uninterrupted one would.  The labels do not change, the labeler still sees the clean u, and everything downstream is
+        as it is without the keyword; it works with every `unlabeled_labeler`, with `unlabeled_mix=False` and under `accumulation_steps`.
+        0.01 is the paper's smallest band, not a value tuned here.  A b above 96 (a short side of 1078 or more at 0.09) raises when the first
+        batch of that size is joined, before anything of that batch is launched; an update that it cuts short is discarded.  None, the default, is off: nothing new is launched or allocated.
+        Not done here: the paper's multi-band ensemble of three models, a style source other than the unlabelled batch, FDA of the unlabelled
+        images, float training images, a separate weight on the unlabelled term (change M), a per-class or per-pixel weight or a threshold on the entropy,
         ADVENT's adversarial branch, CutMix boxes, geometric strong augmentation, augmenting or
         mixing the labelled images, and any change to `BatchGenerator`.'''
         if self.engine.precision == 'fp8_infer':
@@ -344,7 +356,7 @@ class FCN8s:
         ema_d, ema_w = optim_mod.validate_ema(ema_decay, ema_warmup)
         teacher_fn = self._resolve_teacher(teacher, teacher_predict, distill_weight, distill_temperature, distill_pixels)
         unlabeled = self._resolve_unlabeled(unlabeled_generator, unlabeled_labeler, unlabeled_thresholds, unlabeled_predict, unlabeled_mix,
-                                            unlabeled_seed, teacher, bool(ema_d), unlabeled_augment)
+                                            unlabeled_seed, teacher, bool(ema_d), unlabeled_augment, fda_beta)
         entropy = self._resolve_entropy(entropy_weight, entropy_pixels, entropy_images, unlabeled_generator)
         focal = loss_mod.validate_focal(focal_gamma, ohem_thresh if custom_loss else (self.engine.loss_config or {}).get('ohem_thresh'))
         if not focal and self.engine.focal_config is not None:
@@ -459,6 +471,19 @@ class FCN8s:
                 if log is not None:
                     log.close()
 
+    def fda_transfer(self, images, targets, beta=0.01, pair=None):
+        '''Fourier domain adaptation (FDA, Yang & Soatto 2020; fda.py, `Engine.fda_transfer`) of uint8 `images` [N,H,W,3] towards uint8
+        `targets` [M,H,W,3] of the same height and width: the amplitudes of the (2 b + 1)^2 lowest frequencies, b = floor(min(H, W) beta),
+        of image n become those of target pair[n] (None: n mod M), the phases stay.  NumPy arrays or device tensors; returns the same kind
+        (uint8, clamp(rint(y), 0, 255)).'''
+        torch = self.engine.torch
+        on_device = isinstance(images, torch.Tensor) and images.is_cuda
+        x, t = (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in (images, targets))
+        if x.dtype != torch.uint8 or t.dtype != torch.uint8 or x.dim() != 4 or t.dim() != 4:
+            raise ValueError("`images` and `targets` must be uint8 [N, H, W, 3].")
+        out = self.engine.fda_transfer(x.to(self.engine.device).contiguous(), t.to(self.engine.device).contiguous(), beta=beta, pair=pair)
+        return out if on_device else out.cpu().numpy()
+
     def _resolve_teacher(self, teacher, teacher_predict, weight, temperature, pixels):
         '''train()'s teacher arguments -> None (no teacher, or weight 0) or a function: device images -> device softmax.'''
         if teacher is None:
@@ -509,7 +534,7 @@ class FCN8s:
         self.engine.bind_soft_targets(teacher_fn(dev))
         return dev
 
-    def _resolve_unlabeled(self, generator, labeler, thresholds, predict, mix, seed, teacher, ema_requested, augment=None):
+    def _resolve_unlabeled(self, generator, labeler, thresholds, predict, mix, seed, teacher, ema_requested, augment=None, fda_beta=None):
         '''train()'s unlabelled-batch arguments -> None (no generator) or the state of the route: the generator, `label` (device images ->
         (device softmax, score map | None)), the thresholds on the device, the tables `Engine.pseudo_label` counts into, and the mixing's
         settings.'''
@@ -517,8 +542,10 @@ class FCN8s:
             if labeler != 'self' or thresholds is not None or predict is not None:
                 raise ValueError("`unlabeled_labeler`, `unlabeled_thresholds` and `unlabeled_predict` need an `unlabeled_generator`.")
             sa_mod.validate(augment, has_generator=False)
+            fda_mod.validate(fda_beta, has_generator=False)
             return None
         augment = sa_mod.validate(augment)
+        fda_beta = fda_mod.validate(fda_beta)
         has_average = ema_requested or self.engine.ema_info()['has_shadow']
         v = cm_mod.validate(self.num_classes, labeler=labeler, thresholds=thresholds, predict=predict, mix=mix, seed=seed, teacher=teacher,
                             has_average=has_average, model_thresholds=self.pseudo_label_thresholds, student=self)
@@ -539,19 +566,23 @@ class FCN8s:
         Cn = self.num_classes
         flat = torch.zeros(2 * Cn + 3, dtype=torch.int64, device=dev)
         return _Unlabeled(generator=generator, label=label, thresholds=torch.from_numpy(v['thresholds']).to(dev), mi_max=kw.get('mi_max'),
-                          mix=v['mix'], seed=v['seed'] + self.engine.rank, flat=flat, augment=augment,
+                          mix=v['mix'], seed=v['seed'] + self.engine.rank, flat=flat, augment=augment, fda_beta=fda_beta,
                           tables=dict(hist=None, counts=flat[:2 * Cn].view(Cn, 2), misc=flat[2 * Cn:]),
                           labeler_engine=None if isinstance(labeler, str) else labeler.engine)
 
     def _join_unlabeled(self, unl, images, labels, draw):
         '''One batch of the self-training route: the labelled batch on the device with uint8 ids, an unlabelled batch drawn, labelled,
-        thresholded, (with `mix`) class-mixed and (with `augment`) recoloured and blurred on the device, both joined.  Returns the device images and labels for the step.'''
+        thresholded, (with `mix`) class-mixed and (with `augment`) recoloured and blurred on the device, both joined; with `fda_beta` the labelled images are first
+        adapted to the clean unlabelled ones.  Returns the device images and labels for the step.'''
         torch = self.engine.torch
         dev = self.engine.device
         x = self.engine._images(images, force_device=True)[0]
         if x.dtype != torch.uint8:
             raise ValueError("`unlabeled_generator` needs uint8 images from `train_generator` (the joined batch is one uint8 tensor).")
         nhw = tuple(int(d) for d in x.shape[:3])
+        fda_b = None
+        if unl.fda_beta is not None:                                # refused here: nothing of this batch has been launched, no unlabelled batch drawn
+            fda_b = fda_mod.check_half_width(nhw[1], nhw[2], fda_mod.half_width(nhw[1], nhw[2], unl.fda_beta))
         lab_rank = labels.dim() if isinstance(labels, torch.Tensor) else np.ndim(labels)
         if lab_rank == 4:
             t = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels))
@@ -570,6 +601,11 @@ class FCN8s:
         if u.dtype != torch.uint8 or u.shape[0] < 2 or tuple(u.shape[1:3]) != nhw[1:]:
             raise ValueError("`unlabeled_generator` must yield at least 2 uint8 images of the labelled batch's size {}x{}, got {} of dtype {}."
                              .format(nhw[1], nhw[2], tuple(u.shape), u.dtype))
+        if unl.fda_beta is not None:                                # the labelled images take the clean unlabelled images' low-frequency amplitudes
+            if unl.fda_base is None or unl.fda_base.numel() != nhw[0]:          # 0 .. N - 1 on the device, made once: the pairing uploads nothing
+                unl.fda_base = torch.arange(nhw[0], dtype=torch.int32, device=dev)
+            pair = torch.remainder(unl.fda_base + int(draw) % int(u.shape[0]), int(u.shape[0]))
+            x = self.engine.fda_transfer(x, u, b=fda_b, pair=pair)
         prob, score = unl.label(u)
         unl.flat.zero_()
         pseudo, _ = self.engine.pseudo_label(prob, thresholds=unl.thresholds, ignore_id=255, score=score,
@@ -1424,6 +1460,7 @@ class _Unlabeled:
     def __init__(self, **kw):
         self.pixels = 0
         self.entropy = None          # train(entropy_images='unlabeled'): the term's weight and pixel set, set per joined batch
+        self.fda_base = None         # train(fda_beta=...): int32 0 .. N - 1 on the device, made at the first joined batch
         self.__dict__.update(kw)
 
 

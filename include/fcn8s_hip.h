@@ -1089,6 +1089,39 @@ int fcn8s_op_class_mix(void* stream, const uint8_t* images, const uint8_t* label
 size_t fcn8s_op_strong_augment_work_bytes(int N);
 int fcn8s_op_strong_augment(void* stream, const uint8_t* images, int N, int H, int W, uint64_t seed, uint64_t draw, const int32_t* jitter,
                             const int32_t* blur, const uint16_t* taps, void* work, uint8_t* out_images, int32_t* params_out);
+/* Fourier domain adaptation (FDA: Yang & Soatto, CVPR 2020) of a batch of N source images towards M target images, uint8 RGB of the same H x W on
+ * DEVICE pointers: the amplitudes of the (2 b + 1)^2 lowest frequencies of every source image become those of its target image, the phases stay.
+ *   images [N,H,W,3], targets [M,H,W,3] uint8; pair_dev [N] int32 on the device, pair[n] in [0, M) the target of source n (NULL: n mod M);
+ *   b the half-width, 0 <= b <= 96 and B = 2 b + 1 <= min(H, W) (beta <= 0.09 up to a short side of 1024; the window never wraps onto itself).
+ *   Per source n, target t = pair[n] and channel, for u, v in {-b .. b}:
+ *     F_s(u,v) = sum_h sum_w x_s[h,w] exp(-2 pi i (u h / H + v w / W)),  F_t likewise from x_t
+ *     A_s = |F_s|, A_t = |F_t|, phi = F_s / A_s (phi = 1 where A_s = 0: numpy's angle(0) = 0)
+ *     Delta(u,v) = phi (A_t - A_s)
+ *     y[h,w] = x_s[h,w] + 1 / (H W) Re sum_u sum_v Delta(u,v) exp(+2 pi i (u h / H + v w / W))
+ *     out_f32 = y, out_u8 = clamp(rintf(y), 0, 255)
+ *   which equals the published fft2 / fftshift / window [c - b : c + b + 1] / ifftshift / ifft2 route (c = floor(H / 2), floor(W / 2)); the published
+ *   code does not clip, it trains on floats.  Four rules belong to the definition:
+ *   1. Twiddles.  Every exp(+-2 pi i k / n) comes from the integer-reduced phase (f index) mod n (here: a table of sincospi(2 k / n), k < n).
+ *   2. Equal spectra cancel exactly.  F_s and F_t come from one instruction sequence, so a source whose target holds the same bytes has
+ *      A_t - A_s = 0 exactly: out_u8 == x_s and out_f32 == float(x_s) with ==.
+ *   3. Fixed order, batch independence.  No float atomics; every sum is taken in a fixed order; the bits of an image's output depend on that image,
+ *      its target, H, W and b only -- not on N, M, the image's place in the batch or what work held on entry.
+ *   4. The ill-conditioned case.  Where A_s lies below the rounding of its own sum (a constant source at b >= 1) the phase is noise, as it is in the
+ *      published float64 code; such outputs are finite, no more.
+ *   The implementation uses F(-u,-v) = conj F(u,v) of a real image: it computes the columns v = 0 .. b and takes the other half of the window as
+ *   their conjugates.  The two large products (rows of an image against the W twiddles, both ways) are float32 v_mfma_f32_32x32x2_f32 chains, the
+ *   sum over h and Delta are double, the sum over u is a float32 fmaf chain.
+ * work: fcn8s_op_fda_work_bytes(N, M, H, W, b) bytes of device scratch at any alignment, whose content on entry does not matter (the twiddle tables
+ * are rebuilt by a small kernel in every call).  At its first 16-byte boundary it holds the flag: a uint32 that is 0 after a call whose pair_dev
+ * was in range and 1 otherwise -- a pair_dev[n] outside [0, M) lives on the device, cannot be refused, and counts as n mod M.
+ * images, targets and out_u8 at any byte alignment (16-byte accesses of whole lines, byte by byte at the ragged ends), out_f32 4-byte aligned;
+ * one of the two outputs may be NULL; no byte outside the outputs is written; the outputs must not overlap the inputs, work or each other.
+ * Stream-ordered; does not synchronise; allocates nothing.  FCN8S_ERR_BAD_ARG (nothing launched, the outputs untouched) for a NULL images / targets /
+ * work, both outputs NULL, N, M, H or W <= 0, b < 0, b > 96, 2 b + 1 > min(H, W), a misaligned out_f32, an overlap; FCN8S_ERR_SHAPE for N or M > 256
+ * or H W >= 2^31. */
+size_t fcn8s_op_fda_work_bytes(int N, int M, int H, int W, int b);
+int fcn8s_op_fda_transfer(void* stream, const uint8_t* images, int N, const uint8_t* targets, int M, int H, int W, int b, const int32_t* pair_dev,
+                          void* work, uint8_t* out_u8, float* out_f32);
 /* Boundary measures of a segmentation against its ground truth -- the counting half of the trimap IoU (accuracy inside a band of width r around
  * the ground-truth boundaries: Kraehenbuehl & Koltun 2011, Chen et al. 2015) and of the boundary F-score (Csurka et al., BMVC 2013) -- for a batch
  * of N images of H x W pixels on DEVICE pointers.  All integers.
